@@ -16,6 +16,9 @@ Workloads (--workload): c2 = BASELINE.json configs[1], 1000 x 5 Mbp; c3part = th
 src/types.h:25-27): --scaling weak (default) keeps per-GPU work fixed (genomes N x longer, rank r owns the buckets
 congruent to r mod N); --scaling strong shards ONE database of the workload's size (kmdb_db_upload_shard).  The
 partial matrices are summed with one RCCL reduce.  `python bench.py --gpus N` starts its own N ranks.
+A plain run sets up (synthetic database, upload, first call), warms up, times the --steps calls and prints its line; --full adds
+the CPU / reference baselines (cpu_baseline, wall.reference_* / frontend_*), the rows that ride along in the default line (extra.*)
+and roofline.measured_copy_GBs.  --dump-outputs DIR writes what the last timed call returned (dump_outputs()).
 
 Prints ONE JSON line on stdout (rank 0); progress goes to stderr.
 """
@@ -51,10 +54,27 @@ WORKLOADS = {
     "parts": dict(samples=2000, clade_size=50, length=300_000),                            # all2all-parts cell: two halves of one collection
 }
 MODE_WORKLOAD = {"all2all": "c2", "all2all-sp": "c4part", "new2all": "c5part", "db2db": "parts"}
+DUMP_BYTES = 60 << 20          # --dump-outputs: all files together stay below 64 MB
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed call returned in its last step, as float64 (every uint32 count is exact in it).  An array
+    larger than its share of DUMP_BYTES is written as a fixed, seeded sample of its elements (flat index order) with their flat indices
+    beside it in <name>_index.npy, so that two builds given the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size * 8 > share:
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    log("outputs of the last timed step written to %s: %s" % (out_dir, ", ".join(sorted(arrays))))
 
 
 ALL2ALL_SOURCES = ("a2a_blocks.hip", "a2a_v1.hip", "device_common.h", "engine.hip", "engine_internal.h", "engine_state.h", "layout.hip", "prim.h")
@@ -462,6 +482,7 @@ def secondary_mode(args, K, S, device, embedded=False):
             log("synth db: %d k-mers, %d patterns in %.1f s" % (pat["dictionary"].numel(), arr["num_kmers"].size, time.time() - t0))
             d, upload_s = up(arr, N, None)
             sp, dev_ms, call_ms = timed(lambda: (d.all2all_sparse(), d))
+            outputs = {"row_ptr": sp.row_ptr, "col": sp.col, "val": sp.val}
             st = d.stats()
             alg = pattern_bytes(arr) + 8 * int(sp.nnz)
             units, metric, unit = float(st["sum_pairs"]), "all2all-sp k-mer pair-comparisons/sec", "kmer-pair-comparisons/s"
@@ -505,6 +526,7 @@ def secondary_mode(args, K, S, device, embedded=False):
             qs_dev = [S.kmers_of(g.strain(chosen[i * len(chosen) // NQ], N + i), k, f) for i in range(NQ)]
             qs = [q.cpu().numpy().view(np.uint64) for q in qs_dev]
             got, dev_ms, call_ms = timed(lambda: (d.new2all(qs), d))
+            outputs = {"rows": got}
             # algorithmic bytes: 16 B per looked-up k-mer + the root-path bytes of every distinct hit pattern + 4 N per query
             node_b = torch.from_numpy(40 + 16 * ((arr["num_bits"].astype(np.int64) + 127) // 128)).to(device)
             par = torch.from_numpy(arr["parent_id"].astype(np.int64)).to(device)
@@ -592,6 +614,7 @@ def secondary_mode(args, K, S, device, embedded=False):
             d, ub = up(arr_b, len(ids_b), tab_b)
             upload_s = ua + ub
             got, dev_ms, call_ms = timed(lambda: (d.db2db(da), d))
+            outputs = {"matrix": got}
             # algorithmic bytes: every stored k-mer of the row database looked up in the column database (8 B item read + 8 B item probed),
             # both pattern sections once, the result once
             alg = 16 * int(pb["dictionary"].numel()) + pattern_bytes(arr_a) + pattern_bytes(arr_b) + 4 * len(ids_a) * len(ids_b)
@@ -616,6 +639,8 @@ def secondary_mode(args, K, S, device, embedded=False):
             cfg = {"workload": "%s: %s split into two databases of %d / %d samples (even / odd ids), db2db" % (args.workload, desc, len(ids_b), len(ids_a)),
                    "patterns": [int(d.P), int(da.P)]}
             kernel = "kmdb_db2db_dense: item probe of the row database's tables in the column database's + pair-of-paths accumulation"
+    if args.dump_outputs and not embedded:
+        dump_outputs(args.dump_outputs, outputs)
     achieved = alg / (dev_ms * 1e-3) / 1e9
     out = {"metric": metric, "value": units / (dev_ms * 1e-3), "unit": unit, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dev_ms,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
@@ -764,6 +789,8 @@ def node_driver(args):
     sum_pairs = int((arr["num_kmers"].astype(np.uint64) * (n_p * (n_p - np.uint64(1)) // np.uint64(2))).sum())
     assert int(M.astype(np.uint64).sum()) == sum_pairs, "matrix checksum mismatch: %d vs %d" % (int(M.astype(np.uint64).sum()), sum_pairs)
     assert np.array_equal(M, first), "warm call differs from the first call"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"matrix": M})
     cells = args.samples * (args.samples - 1) // 2
     alg = int((40 + 16 * ((arr["num_bits"].astype(np.int64) + 127) // 128)).sum()) + 4 * cells
     ms = elapsed / args.steps * 1e3
@@ -862,10 +889,21 @@ def main():
     ap.add_argument("--one-rank-group", action="store_true",
                     help="--gpus 1 only: run the multi-rank code path (process group, collective of every step, per-rank figures) on a ONE-rank "
                          "RCCL group — what a one-GPU box can exercise of the --gpus N path; a functional check, never a reported number")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU / reference baselines (--no-cpu-baseline still drops them), the rows that ride along in "
+                         "the default line (--no-extra still drops them) and the measured copy bandwidth. Without it a run sets up, warms up, "
+                         "times --steps calls and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float64; an output larger than its share "
+                         "of %d MiB as a fixed, seeded sample of its elements + <name>_index.npy)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if args.generate_spec is not None:
         generator_child(json.loads(args.generate_spec))
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra = True
     if args.workload is None:
         # one GPU: BASELINE configs[1]; several: configs[2] — 10 000 samples, every rank one GPU's share of the 5 Mbp genomes (c3gpu =
         # 5 Mbp / 8: at --gpus 8 with the default --scaling weak the job IS configs[2])
@@ -877,6 +915,8 @@ def main():
     if args.driver == "auto":
         # (--backend gloo is the functional test of the rank form on a box with fewer GPUs than ranks: it keeps the rank form)
         args.driver = "node" if (args.gpus > 1 and args.mode == "all2all" and not args.one_rank_group and args.backend == "nccl") else "ranks"
+    if args.dump_outputs and args.driver == "ranks" and (args.gpus > 1 or args.one_rank_group) and (args.collective == "reduce_scatter" or args.mode == "all2all-sp"):
+        ap.error("--dump-outputs: with --collective reduce_scatter or --mode all2all-sp over ranks the output stays in chunks on the ranks")
     if args.driver == "node":
         if args.mode != "all2all":
             raise SystemExit("bench.py: --driver node is for the all2all mode")
@@ -1032,6 +1072,8 @@ def main():
         assert got == int(sum_pairs), "matrix checksum mismatch: %d vs %d" % (got, int(sum_pairs))
         if world == 1:
             assert np.array_equal(M[:cells].cpu().numpy().view(np.uint32), first), "warm call differs from the first call"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"matrix": M[:cells].cpu().numpy().view(np.uint32)})
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -1091,11 +1133,12 @@ def main():
                 "per_kernel_ms": {"decode": float(pk[0]), "emit_narrow": float(pk[1]), "wide_list+emit_wide": float(pk[2]), "apply": float(pk[3]),
                                   "whole_call": kern_ms},
                 "cold_call_frac": alg / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "measured_copy_GBs": measured_copy_gbs(device),      # what a plain copy reaches on this box (peak above is the nominal figure)
                 "block_records_per_launch": stl["n_records"], "first_block_records_per_launch": stl["n_direct"], "wide_nodes": stl["n_wide"], "nodes_joined_per_tile": stl["n_joined"],
                 "record_chunks": stl["n_chunks"],
             },
         }
+        if args.full:
+            out["roofline"]["measured_copy_GBs"] = measured_copy_gbs(device)      # what a plain copy reaches on the device (peak above is the nominal figure)
         if not multi and not args.no_cpu_baseline:
             from oracle import oracle as O
             db.close()

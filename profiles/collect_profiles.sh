@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the per-round profile evidence on the GPU box (run from the repo root):
 #   bash profiles/collect_profiles.sh <tag> [all|stats|pmc]        e.g. r02_v3        (BENCH_ARGS="--workload c3part" for another workload)
-# 1. bench line (with cpu_baseline)   2. rocprofv3 kernel stats of the same command
+# 1. bench line (--full: with cpu_baseline)   2. rocprofv3 kernel stats of the same command
 # 3. HBM traffic: FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc passes (never combined with other trace domains)
 set -u
 TAG=${1:-rXX}
@@ -12,7 +12,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 BA=${BENCH_ARGS:-}
 if [ "$WHAT" = "all" ]; then
-python bench.py $BA 2> $OUT/${TAG}_bench.err | tee $OUT/${TAG}_bench.json
+python bench.py --full $BA 2> $OUT/${TAG}_bench.err | tee $OUT/${TAG}_bench.json
 fi
 if [ "$WHAT" != "pmc" ]; then
 rm -rf /tmp/prof_stats

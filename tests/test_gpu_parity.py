@@ -1520,14 +1520,14 @@ def test_degenerate_databases(K, O, dev, tmp_path):
 
 
 def test_bench_contract_single_and_two_ranks(dev, tmp_path):
-    """bench.py prints ONE JSON line with the contract's keys; the multi-rank path (prefix-bucket shards +
-    matrix reduce) runs end to end with two ranks sharing this GPU over gloo and reproduces the
-    single-rank checksum structure (the bench asserts sum(M) == sum_p w_p C(n_p,2) over all ranks)."""
+    """bench.py prints ONE JSON line with the contract's keys (--full: with the CPU baseline) and --dump-outputs writes the matrix of
+    the last timed call; the multi-rank path (prefix-bucket shards + matrix reduce) runs end to end with two ranks sharing this GPU over
+    gloo and reproduces the single-rank checksum structure (the bench asserts sum(M) == sum_p w_p C(n_p,2) over all ranks)."""
     import json
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--length", "60000", "--cpu-sample-length", "20000",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--length", "60000", "--cpu-sample-length", "20000",
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1543,6 +1543,10 @@ def test_bench_contract_single_and_two_ranks(dev, tmp_path):
     assert d["config"]["path"] == "block-record pipeline" and d["roofline"]["block_records_per_launch"] > 0
     if d["cpu_baseline"]["kind"] == "reference":
         assert "full" in d["cpu_baseline"]["sample"]           # the reference timed on the whole database of the timed workload
+    m = np.load(str(tmp_path / "out" / "matrix.npy"))
+    n = d["config"]["samples"]
+    assert m.dtype == np.float64 and m.shape == (n * (n - 1) // 2,)
+    assert abs(m.sum() - d["value"] * d["ms_per_step"] * 1e-3) <= 1e-9 * m.sum()      # value = sum of the matrix per second of one step
     # `--gpus 2` with NO launcher: bench.py starts its own two ranks (weak scaling: per-rank databases)
     # (strong scaling with the reduce to rank 0 ran here too until round 5: its two halves are the runs below; the suite has a time limit)
     for scaling, collective in (("weak", "reduce"), ("strong", "reduce_scatter")):
@@ -1609,7 +1613,7 @@ def test_bench_secondary_modes(dev, mode):
     whole-output identity and (oracle/_ref present) compares every row with the real reference's output."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", mode, "--samples", "600", "--length", "20000", "--queries", "24",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", mode, "--samples", "600", "--length", "20000", "--queries", "24",
                         "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
