@@ -23,7 +23,9 @@
 extern "C" {
 #endif
 
-#define KMDB_ABI_VERSION 7
+#define KMDB_ABI_VERSION 8
+/* ABI 8 is ABI 7 plus entry points (tree ranges): no struct changed its size or the order of its fields, so the library also accepts a
+ * kmdb_db_view whose abi_version is 7 — a caller compiled against the previous header runs unchanged. */
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -62,7 +64,7 @@ typedef struct kmdb_opts {
     /* pattern-stream sharding of ONE resident database: this call adds the pairs of the patterns in
      * slice `shard_index` of `shard_count` equal slices of the (DFS-ordered) pattern stream; partial
      * matrices from all slices sum (uint32, wrap-around) to the full result.  {0,1} = everything.
-     * (Prefix-bucket shards, one per GPU, are made at upload: kmdb_db_upload_shard.) */
+     * (Prefix-bucket shards and tree ranges, one per GPU, are made at upload: kmdb_db_upload_shard, kmdb_db_upload_range.) */
     uint32_t shard_index;
     uint32_t shard_count;
     uint32_t bubble_size;          /* all2all-sp: -bubble-size (params.h:78), kept for CLI compat; 0 = default 8000 */
@@ -142,8 +144,8 @@ typedef struct kmdb_stats {        /* measurements of the LAST call on this db h
     uint32_t sized_call;           /* 1: the last call measured its own grid sizes (first call on a handle, two host syncs more) */
     uint32_t n_joined;             /* nodes with many blocks whose records were never written: joined per tile by the second level (ABI 6; 0 when it is off) */
     uint64_t n_patterns;           /* patterns resident in HBM: all of the view's, or for kmdb_db_upload_shard only the nodes whose subtree
-                                      holds a k-mer of the shard */
-    uint64_t h2d_bytes;            /* bytes kmdb_db_upload[_shard] copied to the device (ABI 6) */
+                                      holds a k-mer of the shard, or for kmdb_db_upload_range the nodes of the range and the ancestors of its first node */
+    uint64_t h2d_bytes;            /* bytes kmdb_db_upload[_shard|_range] copied to the device (ABI 6) */
     uint64_t n_direct;             /* block records that were never written: first-block records (X, X) the narrow kernel applied where it emitted them,
                                       tile in registers, one write-back per slice of the pattern stream (ABI 7; n_records counts the written ones) */
 } kmdb_stats;
@@ -168,6 +170,18 @@ int  kmdb_db_upload(const kmdb_db_view* view, const kmdb_opts* opts, int with_ha
  * hashtables (load mode Everything). */
 int  kmdb_db_upload_shard(const kmdb_db_view* view, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index,
                           uint32_t shard_count, kmdb_db** out);
+/* One tree range of the database (the pattern / subtree is the natural unit of all2all; ABI 8).  Serves the all2all call
+ * sites, console_all2all.cpp:26,31-36, which load the database with SkipHashtables: the view needs NO hashtables (n_buckets may be 0).
+ * The DFS pre-order of the pattern tree (children of a node, and the roots, in ascending pattern id: the order of the resident stream)
+ * is cut into range_count contiguous stretches of about equal estimated cost; the handle holds the nodes of stretch range_index at their
+ * on-disk num_kmers, and the ancestors of the stretch's first node that lie before it at weight 0 (they only supply sample ids):
+ * kmdb_stats.n_patterns = nodes of the range + depth of its first node - 1.  Every pattern adds w_p to the cells of its own id list
+ * independently of every other, so the partial matrices of the ranges sum (uint32, wrap-around) to the matrix of the whole database, and
+ * kmdb_stats.sum_pairs (the range's own sum_p w_p C(n_p, 2)) is the sum of the range's matrix.  The cuts depend on (view, range_count)
+ * only: processes that each upload one range agree.  An empty range (range_count > patterns) holds pattern 0 at weight 0: a zero matrix.
+ * For all2all / all2all-sp only — no hashtables are copied (new2all and db2db need every pattern id); kmdb_opts.shard_index /
+ * shard_count slice the handle's resident stream as on any other.  range_count == 1 is kmdb_db_upload(view, opts, 0, out). */
+int  kmdb_db_upload_range(const kmdb_db_view* view, const kmdb_opts* opts, uint32_t range_index, uint32_t range_count, kmdb_db** out);
 void kmdb_db_free(kmdb_db* db);
 /* Waits for the handle's background housekeeping (the upload's host staging buffers are given back by a helper thread after the first
  * call).  A front-end that ends the process right after its call waits here first: the helper's threads free the pages several times
@@ -270,9 +284,10 @@ typedef struct kmdb_node kmdb_node;
 typedef struct kmdb_node_stats {   /* the LAST call on the node handle; maxima over the devices */
     uint32_t n_shards, n_devices;
     int32_t  rccl_version;         /* ncclGetVersion, 0 when RCCL was not needed */
-    uint32_t reserved;
-    double   upload_s;             /* kmdb_node_upload, wall clock */
-    double   plan_s;               /* of it: the host's plan of all shards (one pass over the hashtable items, one sweep over the tree) */
+    uint32_t partition;            /* KMDB_PARTITION_* of the upload (ABI 8; the field was reserved, 0 = prefix buckets, before) */
+    double   upload_s;             /* kmdb_node_upload[_partition], wall clock */
+    double   plan_s;               /* of it: the host's plan of all shards (prefix: one pass over the hashtable items, one sweep over the tree;
+                                      ranges: two sweeps over parent_id and num_samples) */
     double   call_ms;              /* HIP events around the slowest device's kmdb_all2all_dense_device calls (all its shards) */
     double   collective_ms;        /* HIP events around ncclReduceScatter on the slowest device */
     double   d2h_ms;               /* dense: copy of the device's chunk to the host; sparse: compaction + copy of its CSR */
@@ -291,6 +306,15 @@ typedef struct kmdb_node_device_stats {
 } kmdb_node_device_stats;
 int  kmdb_node_device_stats_get(const kmdb_node* node, uint32_t slot, kmdb_node_device_stats* out);
 int  kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, const int32_t* devices, uint32_t n_devices, kmdb_node** out);
+/* The same with the partition named (ABI 8; kmdb_node_upload = KMDB_PARTITION_PREFIX).  KMDB_PARTITION_RANGE: shard s is tree range s of
+ * n_shards (kmdb_db_upload_range; one plan for all of them), again on devices[s % D] — the partition of all2all / all2all-sp as the
+ * reference loads them (console_all2all.cpp:26,31-36: SkipHashtables): the view needs no hashtables, and the devices together hold
+ * P + sum over the ranges of (depth of the first node - 1) nodes instead of a near-whole tree per prefix shard.  Everything after the
+ * upload (own shards summed on the device, reduce-scatter, dense copy / sparse compaction) is the same for both. */
+#define KMDB_PARTITION_PREFIX 0
+#define KMDB_PARTITION_RANGE  1
+int  kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_shards, const int32_t* devices, uint32_t n_devices, int partition,
+                                kmdb_node** out);
 void kmdb_node_free(kmdb_node* node);
 int  kmdb_node_stats_get(const kmdb_node* node, kmdb_node_stats* out);
 /* = kmdb_all2all_dense over all shards: out_lower_tri N(N-1)/2 uint32 in host memory */
@@ -327,6 +351,14 @@ uint64_t    kmdbh_db_pattern_section_bytes(const kmdbh_db* db);
  * it keeps (those whose subtree holds a k-mer of a bucket b with b % n_shards == s; bucket = kmer >> 32, types.h:25-27) and the
  * k-mers it owns (items of those buckets, hashmap_lp.h:71-78).  The view must carry the hashtables. */
 int  kmdbh_shard_plan_counts(const kmdb_db_view* view, uint32_t n_shards, uint64_t* kept_nodes, uint64_t* kmers);
+/* The host's plan of the tree ranges kmdb_node_upload_partition / kmdb_db_upload_range work from (no GPU, no hashtables; ABI 8; call sites
+ * served: console_all2all.cpp:26,31-36): from parent_id and num_samples alone, the DFS pre-order (children of a node, and the roots, in
+ * ascending pattern id) cut into n_ranges contiguous stretches balanced by an estimate of the nodes' cost.  Per range s: own_nodes = nodes
+ * of the stretch, first_depth = depth of its first node (a root has depth 1; 0 for an empty range), kept_nodes = own_nodes + first_depth - 1
+ * (0 for an empty range), est_cost = the estimate's sum over the stretch; range_of[p] = the range of pattern p.  range_of and first_depth
+ * may be NULL.  A pure function of (view, n_ranges). */
+int  kmdbh_range_plan(const kmdb_db_view* view, uint32_t n_ranges, uint64_t* kept_nodes, uint64_t* own_nodes, uint64_t* est_cost,
+                      uint32_t* range_of, uint32_t* first_depth);
 
 /* KmerHelper::extract + MinHashFilter (kmer_extract.h:13-97, filter.h:28-115), nt alphabets.
  * Writes at most len k-mers to out; returns the count. */

@@ -25,5 +25,6 @@ from .capi import (  # noqa: F401
     lib,
     lib_path,
     make_view,
+    range_plan,
     sort_unique,
 )

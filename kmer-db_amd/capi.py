@@ -5,7 +5,7 @@ import sys
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -60,7 +60,7 @@ class _Stats(C.Structure):
 
 
 class _NodeStats(C.Structure):
-    _fields_ = [("n_shards", C.c_uint32), ("n_devices", C.c_uint32), ("rccl_version", C.c_int32), ("reserved", C.c_uint32),
+    _fields_ = [("n_shards", C.c_uint32), ("n_devices", C.c_uint32), ("rccl_version", C.c_int32), ("partition", C.c_uint32),
                 ("upload_s", C.c_double), ("plan_s", C.c_double), ("call_ms", C.c_double), ("collective_ms", C.c_double), ("d2h_ms", C.c_double)]
 
 
@@ -75,14 +75,15 @@ FLAG_FORCE_TILE = 4
 FLAG_NO_FALLBACK = 8
 FLAG_ONE_SHOT = 16
 PATH_NONE, PATH_RECORDS, PATH_TILE, PATH_GLOBAL = 0, 1, 2, 3
+PARTITIONS = ("prefix", "range")      # KMDB_PARTITION_*
 
 # every symbol include/kmdb_amd.h declares
 EXPORTS = [
-    "kmdb_last_error", "kmdb_abi_version", "kmdb_device_count", "kmdb_device_prepare", "kmdb_db_upload", "kmdb_db_upload_shard", "kmdb_db_free", "kmdb_db_settle", "kmdb_db_stats", "kmdb_db_fallback_reason",
-    "kmdb_node_upload", "kmdb_node_free", "kmdb_node_stats_get", "kmdb_node_device_stats_get", "kmdb_node_all2all_dense", "kmdb_node_all2all_sparse",
+    "kmdb_last_error", "kmdb_abi_version", "kmdb_device_count", "kmdb_device_prepare", "kmdb_db_upload", "kmdb_db_upload_shard", "kmdb_db_upload_range", "kmdb_db_free", "kmdb_db_settle", "kmdb_db_stats", "kmdb_db_fallback_reason",
+    "kmdb_node_upload", "kmdb_node_upload_partition", "kmdb_node_free", "kmdb_node_stats_get", "kmdb_node_device_stats_get", "kmdb_node_all2all_dense", "kmdb_node_all2all_sparse",
     "kmdb_all2all_dense", "kmdb_all2all_dense_device", "kmdb_all2all_sparse", "kmdb_all2all_sparse_filtered", "kmdb_sparse_from_dense_device", "kmdbh_metric", "kmdbh_metric_id", "kmdb_sparse_free",
     "kmdb_new2all_batch", "kmdb_new2all_batch_sparse", "kmdb_new2all_batch_seq", "kmdb_new2all_batch_seq_alphabet", "kmdb_db2db_dense",
-    "kmdbh_shard_plan_counts", "kmdbh_db_load", "kmdbh_db_free", "kmdbh_db_release_patterns", "kmdbh_db_view", "kmdbh_db_kmer_length", "kmdbh_db_fraction",
+    "kmdbh_shard_plan_counts", "kmdbh_range_plan", "kmdbh_db_load", "kmdbh_db_free", "kmdbh_db_release_patterns", "kmdbh_db_view", "kmdbh_db_kmer_length", "kmdbh_db_fraction",
     "kmdbh_db_start_fraction", "kmdbh_db_alphabet", "kmdbh_db_n_samples", "kmdbh_db_sample_name",
     "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique",
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
@@ -108,11 +109,14 @@ def lib():
     L.kmdb_last_error.restype = C.c_char_p
     L.kmdb_db_upload.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_int, C.POINTER(C.c_void_p)]
     L.kmdb_db_upload_shard.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.kmdb_db_upload_range.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.kmdb_db_free.argtypes = [C.c_void_p]
     L.kmdb_db_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
     L.kmdb_db_fallback_reason.argtypes = [C.c_void_p]
     L.kmdb_db_fallback_reason.restype = C.c_char_p
     L.kmdb_node_upload.argtypes = [C.POINTER(_View), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.kmdb_node_upload_partition.argtypes = [C.POINTER(_View), C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.kmdbh_range_plan.argtypes = [C.POINTER(_View), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmdb_node_free.argtypes = [C.c_void_p]
     L.kmdb_node_stats_get.argtypes = [C.c_void_p, C.POINTER(_NodeStats)]
     L.kmdb_node_device_stats_get.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_NodeDeviceStats)]
@@ -224,6 +228,11 @@ class HostDB:
         _check(L.kmdbh_shard_plan_counts(self.view, n_shards, kept.ctypes.data, kmers.ctypes.data))
         return kept, kmers
 
+    def range_plan(self, n_ranges):
+        """kmdbh_range_plan: the tree ranges of the database, planned on the host without the hashtables — a dict of
+        kept / own / cost / first_depth per range and range_of per pattern"""
+        return range_plan(self.view, n_ranges)
+
     def release_patterns(self):
         """kmdbh_db_release_patterns: the pattern arrays' pages go back to the kernel (after the upload); names and counts stay"""
         lib().kmdbh_db_release_patterns(self._h)
@@ -265,6 +274,17 @@ class HostDB:
             self.close()
         except Exception:
             pass
+
+
+def range_plan(view, n_ranges):
+    """kmdbh_range_plan on a view (HostDB.view, or C.pointer(view) of make_view's)"""
+    R = max(int(n_ranges), 0)
+    out = {"kept": np.zeros(max(R, 1), np.uint64), "own": np.zeros(max(R, 1), np.uint64), "cost": np.zeros(max(R, 1), np.uint64),
+           "range_of": np.zeros(max(int(view.contents.n_patterns), 1), np.uint32), "first_depth": np.zeros(max(R, 1), np.uint32)}
+    _check(lib().kmdbh_range_plan(view, int(n_ranges), out["kept"].ctypes.data, out["own"].ctypes.data, out["cost"].ctypes.data,
+                                  out["range_of"].ctypes.data, out["first_depth"].ctypes.data))
+    out["range_of"] = out["range_of"][: int(view.contents.n_patterns)]
+    return {k: (a if k == "range_of" else a[:R]) for k, a in out.items()}
 
 
 def make_view(kmer_length, n_samples, num_kmers, parent_id, num_samples, num_local, last_sample_id, num_bits,
@@ -309,9 +329,11 @@ class SparseRows:
 class DeviceDB:
     """A database resident in HBM (kmdb_db_upload)."""
 
-    def __init__(self, src, device=0, with_hashtables=False, flags=0, prefix_shard=None):
+    def __init__(self, src, device=0, with_hashtables=False, flags=0, prefix_shard=None, tree_range=None):
         """prefix_shard=(index, count): keep only the k-mers of the prefix buckets b with b % count == index
-        (kmdb_db_upload_shard; the source must carry the hashtables)."""
+        (kmdb_db_upload_shard; the source must carry the hashtables).
+        tree_range=(index, count): keep only the patterns of range `index` of `count` ranges of the tree's DFS pre-order, and the
+        ancestors of its first node at weight 0 (kmdb_db_upload_range; all2all / all2all-sp only, no hashtables needed)."""
         self._keep = None
         if isinstance(src, HostDB):
             view = src.view
@@ -323,7 +345,11 @@ class DeviceDB:
         self.device = device
         self._d = C.c_void_p()
         o = _opts(device, (0, 1), flags)
-        if prefix_shard is None:
+        if tree_range is not None:
+            if prefix_shard is not None or with_hashtables:
+                raise ValueError("tree_range goes with neither prefix_shard nor with_hashtables")
+            _check(lib().kmdb_db_upload_range(view, C.byref(o), int(tree_range[0]), int(tree_range[1]), C.byref(self._d)))
+        elif prefix_shard is None:
             _check(lib().kmdb_db_upload(view, C.byref(o), int(with_hashtables), C.byref(self._d)))
         else:
             _check(lib().kmdb_db_upload_shard(view, C.byref(o), int(with_hashtables), int(prefix_shard[0]), int(prefix_shard[1]),
@@ -460,14 +486,17 @@ class DeviceDB:
 
 
 class NodeDB:
-    """One database prefix-sharded over the devices of the node (kmdb_node_upload): n_shards shards, shard s on devices[s % D]."""
+    """One database sharded over the devices of the node (kmdb_node_upload_partition): n_shards shards, shard s on devices[s % D];
+    partition "prefix" (prefix buckets, needs the hashtables) or "range" (ranges of the pattern tree, all2all without them)."""
 
-    def __init__(self, src, n_shards, devices=(0,)):
+    def __init__(self, src, n_shards, devices=(0,), partition="prefix"):
         self._keep = src
         view = src.view if isinstance(src, HostDB) else C.pointer(src[0])
         self._n = C.c_void_p()
         devs = (C.c_int32 * len(devices))(*devices)
-        _check(lib().kmdb_node_upload(view, int(n_shards), devs, len(devices), C.byref(self._n)))
+        if partition not in PARTITIONS:
+            raise ValueError("partition is one of " + ", ".join(PARTITIONS))
+        _check(lib().kmdb_node_upload_partition(view, int(n_shards), devs, len(devices), PARTITIONS.index(partition), C.byref(self._n)))
         self.N = int(view.contents.n_samples)
 
     def tri_size(self):
@@ -497,6 +526,7 @@ class NodeDB:
         s = _NodeStats()
         _check(lib().kmdb_node_stats_get(self._n, C.byref(s)))
         out = {f: getattr(s, f) for f, _ in _NodeStats._fields_}
+        out["partition"] = PARTITIONS[s.partition]
         out["devices"] = []
         for slot in range(s.n_devices):
             ds = _NodeDeviceStats()

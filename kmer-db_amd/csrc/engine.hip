@@ -29,6 +29,7 @@ static thread_local std::string g_last_error;
 int kmdb_set_error(const std::string& msg) { g_last_error = msg; return 1; }
 extern "C" const char* kmdb_last_error(void) { return g_last_error.c_str(); }
 extern "C" int kmdb_abi_version(void) { return KMDB_ABI_VERSION; }
+static_assert(KMDB_ABI_THIS == KMDB_ABI_VERSION, "kmdb_internal.h: kmdb_abi_compatible names the header's version");
 
 extern "C" int kmdb_device_prepare(int32_t device) {
     int n = 0;
@@ -192,9 +193,12 @@ __global__ __launch_bounds__(64) void row_tiles_kernel(const uint32_t* __restric
 // ------------------------------------------------------------------------------------------
 namespace {
 
-int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan, kmdb_db** out) {
+// plan / rplan: the part of the database this handle holds — shard `shard_index` of `shard_count` prefix-bucket shards (plan == nullptr: planned
+// here), or range `shard_index` of rplan's tree ranges; neither (shard_count 1): the whole database
+int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
+                const kmdb_range_plan* rplan, kmdb_db** out) {
     *out = nullptr;
-    if (!v || v->abi_version != KMDB_ABI_VERSION) return kmdb_set_error("kmdb_db_upload: bad view / ABI version");
+    if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload: bad view / ABI version");
     if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
     const uint64_t P = v->n_patterns, N = v->n_samples;
     if (P >= (1ull << 31)) return kmdb_set_error("kmdb_db_upload: more than 2^31 patterns");
@@ -210,7 +214,7 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
     HIP_TRY(hipSetDevice(device));
     // a prefix shard uploaded by itself plans itself: its k-mer counts from its own buckets, its nodes by one sweep (host_shards.cpp)
     kmdb_shard_plan own_plan;
-    if (shard_count > 1 && !plan) {
+    if (shard_count > 1 && !plan && !rplan) {
         if (kmdb_shard_plan_build(v, shard_count, std::vector<uint32_t>{shard_index}, &own_plan)) return 1;
         plan = &own_plan;
     }
@@ -234,7 +238,15 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
         t_mark = now;
     };
     part("streams + events (first use of the device)");
-    if (kmdb_layout_upload(db, v, with_hashtables, shard_index, shard_count, plan)) return fail();
+    {
+        kmdb_kept_nodes sel;
+        if (rplan) sel = kmdb_kept_of_range(*rplan, shard_index);
+        else if (plan && shard_count > 1) sel = kmdb_kept_of_shard(*plan, shard_index);
+        const bool part_of_db = rplan || (plan && shard_count > 1);
+        const int rc = kmdb_layout_upload(db, v, with_hashtables, part_of_db ? &sel : nullptr);
+        if (plan && shard_count > 1) plan->release_weights(shard_index);      // the shard's P counters go back
+        if (rc) return fail();
+    }
     part("layout incl. release of its temporaries");
     // the working set of all2all: now for an all2all upload, on the first all2all call for a new2all / db2db upload
     if (!with_hashtables && kmdb_blocks_prepare(db)) return fail();
@@ -254,16 +266,38 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
 }  // namespace
 
 extern "C" int kmdb_db_upload(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, kmdb_db** out) {
-    return upload_impl(v, opts, with_hashtables, 0, 1, nullptr, out);
+    return upload_impl(v, opts, with_hashtables, 0, 1, nullptr, nullptr, out);
 }
 extern "C" int kmdb_db_upload_shard(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count,
                                     kmdb_db** out) {
-    return upload_impl(v, opts, with_hashtables, shard_index, shard_count, nullptr, out);
+    return upload_impl(v, opts, with_hashtables, shard_index, shard_count, nullptr, nullptr, out);
+}
+extern "C" int kmdb_db_upload_range(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t range_index, uint32_t range_count, kmdb_db** out) {
+    if (!out) return kmdb_set_error("kmdb_db_upload_range: null argument");
+    *out = nullptr;
+    if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload_range: bad view / ABI version");
+    if (range_count == 0 || range_count > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_db_upload_range: range_count must be between 1 and " + std::to_string(KMDB_MAX_SHARDS));
+    if (range_index >= range_count) return kmdb_set_error("kmdb_db_upload_range: range_index >= range_count");
+    if (range_count == 1) return kmdb_db_upload(v, opts, 0, out);
+    // a range uploaded by itself plans all ranges (two sweeps over parent_id and num_samples, host_ranges.cpp): the cuts are a pure function
+    // of the view and the count, so processes that each upload one range of the same database agree
+    try {
+        kmdb_range_plan plan;
+        if (kmdb_range_plan_build(v, range_count, &plan)) return 1;
+        return upload_impl(v, opts, 0, range_index, range_count, nullptr, &plan, out);
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string("kmdb_db_upload_range: ") + e.what());
+    }
+}
+int kmdb_db_upload_range_planned(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t range_index, const kmdb_range_plan* plan, kmdb_db** out) {
+    if (!out || !plan) return kmdb_set_error("kmdb_db_upload_range: null argument");
+    if (range_index >= plan->n_ranges) return kmdb_set_error("kmdb_db_upload_range: range_index >= range_count");
+    return upload_impl(v, opts, 0, range_index, plan->n_ranges, nullptr, plan, out);
 }
 int kmdb_db_upload_planned(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
                            kmdb_db** out) {
     if (!out) return kmdb_set_error("kmdb_db_upload_shard: null argument");
-    return upload_impl(v, opts, with_hashtables, shard_index, shard_count, plan, out);
+    return upload_impl(v, opts, with_hashtables, shard_index, shard_count, plan, nullptr, out);
 }
 
 extern "C" void kmdb_db_settle(kmdb_db* db) {

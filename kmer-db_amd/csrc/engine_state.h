@@ -247,10 +247,13 @@ constexpr int KMDB_CHAIN_MAX = 4096;  // longest root path (in nodes) the chain 
                                       // the deeper the tree, the fewer waves share a workgroup)
 
 // ---- layout.hip: host conversion + device layout of the view (fills the structural arrays and stats)
-int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan);
+// sel == nullptr: the whole view at its on-disk weights; else the nodes and weights of one part (a prefix shard, a tree range)
+int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, const kmdb_kept_nodes* sel);
 // kmdb_db_upload_shard with a plan the caller made for several shards at once (node.hip); plan == nullptr: the shard is planned by itself
 int kmdb_db_upload_planned(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
                            kmdb_db** out);
+// kmdb_db_upload_range with a plan the caller made for all ranges (node.hip)
+int kmdb_db_upload_range_planned(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t range_index, const kmdb_range_plan* plan, kmdb_db** out);
 
 // ---- a2a_v1.hip: tree-form scatter kernels (LDS tile / HBM atomics); M is zeroed, wprefix is scanned
 int kmdb_v1_run(kmdb_db* db, uint32_t* M, uint32_t seg_begin, uint32_t seg_end, uint32_t flags, hipStream_t st);

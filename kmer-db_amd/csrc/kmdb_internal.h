@@ -9,6 +9,12 @@
 // records the message for kmdb_last_error() and returns a non-zero status
 int kmdb_set_error(const std::string& msg);
 
+// kmdb_db_view.abi_version of a caller this library serves: ABI 8 only ADDED entry points (no struct of ABI 7 changed its size or the order of
+// its fields; kmdb_node_stats.reserved, always 0, became `partition`, where 0 is the prefix partition), so a program compiled against the
+// header of ABI 7 — a maintainer's glue that has not been rebuilt — keeps working with this library.
+constexpr uint32_t KMDB_ABI_OLDEST_COMPATIBLE = 7, KMDB_ABI_THIS = 8;
+inline bool kmdb_abi_compatible(uint32_t caller) { return caller >= KMDB_ABI_OLDEST_COMPATIBLE && caller <= KMDB_ABI_THIS; }
+
 // Gives the pages inside the regions back to the kernel, on up to `threads` threads (host_db.cpp).  madvise(MADV_DONTNEED) takes the
 // address-space lock SHARED: the threads, and the page faults and allocations of every other thread, go on side by side, where a munmap
 // of gigabytes holds the lock exclusively for as long as it frees pages.  The regions stay mapped (they read as zeros afterwards):
@@ -38,3 +44,55 @@ struct kmdb_shard_plan {
 };
 // plans the listed shards (all of them: kmdb_node_upload; one: kmdb_db_upload_shard); 0, or 1 with the error set
 int kmdb_shard_plan_build(const kmdb_db_view* v, uint32_t n_shards, const std::vector<uint32_t>& shards, kmdb_shard_plan* plan);
+
+// ---- host_ranges.cpp: the tree ranges of one database (the pattern / subtree is the natural all2all unit), planned from
+// parent_id and num_samples alone — no hashtables.  The DFS pre-order of the device layout (children of a node and the roots in ascending
+// pattern id: layout.hip) is cut into n_ranges contiguous stretches of about equal estimated cost; range s = positions [cut[s], cut[s + 1]).
+// A range also lays out the ancestors of its FIRST node that lie before it, with weight 0 (they only supply sample ids): a subtree is a
+// contiguous stretch of the pre-order, so every out-of-range ancestor of any node of the range is one of those.
+//   kept(s) = own(s) + depth(first node of s) - 1,   depth of a root = 1
+// The plan is a pure function of (view, n_ranges): processes that each upload "range s of R" agree without talking to each other.
+// It holds one 4-byte position per pattern and R short ancestor lists — no per-shard array.
+struct kmdb_range_plan {
+    uint64_t P = 0;
+    uint32_t n_ranges = 0;
+    std::vector<uint32_t> pre;                 // [P] pre-order position of every pattern
+    std::vector<uint32_t> cut;                 // [n_ranges + 1] ascending, cut[0] = 0, cut[n_ranges] = P
+    std::vector<std::vector<uint32_t>> anc;    // [n_ranges] pattern ids of the out-of-range ancestors of the range's first node, root first (ascending)
+    std::vector<uint64_t> cost;                // [n_ranges] estimated cost of the range's own nodes
+    uint64_t own(uint32_t s) const { return cut[s + 1] - cut[s]; }
+    uint64_t kept(uint32_t s) const { return own(s) + anc[s].size(); }
+    uint32_t first_depth(uint32_t s) const { return own(s) ? (uint32_t)anc[s].size() + 1u : 0u; }
+};
+// 0, or 1 with the error set
+int kmdb_range_plan_build(const kmdb_db_view* v, uint32_t n_ranges, kmdb_range_plan* plan);
+
+// ---- which nodes an upload lays out and with which weight: what the pruned branch of kmdb_layout_upload (layout.hip) asks of a plan.
+// Both partitions answer through it: a prefix shard keeps the nodes whose subtree holds one of its k-mers, at its own k-mer counts; a
+// tree range keeps its own nodes at their on-disk num_kmers and the out-of-range ancestors of its first node at 0.
+struct kmdb_kept_nodes {
+    const char* what = "";                     // "prefix shard" / "tree range" (messages)
+    uint64_t kept = 0;                         // nodes to lay out
+    // prefix shard
+    const unsigned char* mask = nullptr;       // kmdb_shard_plan::mask[shard >> 3]
+    unsigned char bit = 0;
+    const uint32_t* w = nullptr;               // kmdb_shard_plan::w[shard]
+    // tree range
+    const uint32_t* pre = nullptr;             // kmdb_range_plan::pre
+    uint32_t lo = 0, hi = 0;                   // own nodes: lo <= pre[p] < hi
+    const uint32_t* anc = nullptr;             // ascending pattern ids of the zero-weight nodes (all of them before `lo` in the pre-order,
+    uint32_t n_anc = 0;                        // or pattern 0 alone for an empty range: every array stays non-empty)
+
+    bool owns(uint64_t p) const { return pre[p] - lo < hi - lo; }
+    bool keeps(uint64_t p) const {
+        if (mask) return (mask[p] & bit) != 0;
+        if (owns(p)) return true;
+        uint32_t a = 0, b = n_anc;             // (a handful of entries: the depth of the range's first node)
+        while (a < b) { const uint32_t m = (a + b) / 2; if (anc[m] < p) a = m + 1; else b = m; }
+        return a < n_anc && anc[a] == p;
+    }
+    // truncated exactly like the reference's to_add (similarity_calculator.cpp:222)
+    uint32_t weight(uint64_t p, const int64_t* num_kmers) const { return mask ? w[p] : (owns(p) ? (uint32_t)num_kmers[p] : 0u); }
+};
+kmdb_kept_nodes kmdb_kept_of_shard(const kmdb_shard_plan& plan, uint32_t shard);
+kmdb_kept_nodes kmdb_kept_of_range(const kmdb_range_plan& plan, uint32_t range);

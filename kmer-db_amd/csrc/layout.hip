@@ -246,14 +246,15 @@ void kmdb_release_staging(kmdb_db* db) {
     });                                                       // joined by kmdb_db_settle / kmdb_db_free
 }
 
-int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan) {
+int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, const kmdb_kept_nodes* sel) {
     const uint64_t P_view = v->n_patterns;
-    // A prefix shard planned on the host (host_shards.cpp) lays out only the nodes it keeps: the fields of those nodes are narrowed, their
-    // streams packed, and nothing else crosses PCIe — no hashtable slots, no node of another shard's part of the tree.  (A shard that owns
-    // no k-mer at all keeps the whole tree with zero weights: every array stays non-empty.)
+    // A part of the database planned on the host — a prefix shard (host_shards.cpp) or a tree range (host_ranges.cpp); `sel` says which
+    // nodes and at which weight — lays out only the nodes it keeps: the fields of those nodes are narrowed, their streams packed, and
+    // nothing else crosses PCIe — no hashtable slots, no node of another part of the tree.  (A prefix shard that owns no k-mer at all
+    // keeps the whole tree with zero weights: every array stays non-empty.)
     // (An upload that carries the hashtables keeps the whole tree: new2all's pattern ids must all resolve.)
-    const bool pruned = plan && shard_count > 1 && !with_hashtables && !getenv("KMDB_SHARD_WHOLE_TREE") && plan->kept[shard_index] > 0 && plan->kept[shard_index] < P_view;
-    uint64_t P = pruned ? plan->kept[shard_index] : P_view;    // nodes laid out
+    const bool pruned = sel && !with_hashtables && !getenv("KMDB_SHARD_WHOLE_TREE") && sel->kept > 0 && sel->kept < P_view;
+    uint64_t P = pruned ? sel->kept : P_view;                  // nodes laid out
     uint64_t h2d_bytes = 0;
     const uint64_t N = v->n_samples;
     const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
@@ -285,28 +286,27 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         fn(0u, (uint64_t)0, P_view / T);
         for (auto& th : pool) th.join();
     };
-    const uint32_t* plan_w = plan && shard_count > 1 ? plan->w[shard_index] : nullptr;     // the shard's own k-mers per pattern
-    if (plan && shard_count > 1 && !plan_w) return kmdb_set_error("kmdb_db_upload_shard: the shard is not part of the plan");
+    if (sel && sel->mask && !sel->w) return kmdb_set_error("kmdb_db_upload_shard: the shard is not part of the plan");
     HostBuf<uint32_t> h_newidx(pruned ? P_view : 1);           // pruned: a kept node's index among the kept ones
     std::vector<uint64_t> part_kept(T + 1, 0);
     if (pruned) {
         if (!h_newidx.p) return kmdb_set_error("kmdb_db_upload: out of host memory");
         run_parts([&](unsigned t, uint64_t lo, uint64_t hi) {
             uint64_t c = 0;
-            for (uint64_t p = lo; p < hi; ++p) c += plan->keeps(shard_index, p) ? 1u : 0u;
+            for (uint64_t p = lo; p < hi; ++p) c += sel->keeps(p) ? 1u : 0u;
             part_kept[t + 1] = c;
         });
         for (unsigned t = 0; t < T; ++t) part_kept[t + 1] += part_kept[t];
-        if (part_kept[T] != P) return kmdb_set_error("kmdb_db_upload_shard: internal: the plan's count of kept nodes is off");
+        if (part_kept[T] != P) return kmdb_set_error(std::string("kmdb_db_upload: internal: the count of kept nodes of the ") + sel->what + " is off");
         run_parts([&](unsigned t, uint64_t lo, uint64_t hi) {
             uint64_t o = part_kept[t];
-            for (uint64_t p = lo; p < hi; ++p) if (plan->keeps(shard_index, p)) h_newidx[p] = (uint32_t)o++;
+            for (uint64_t p = lo; p < hi; ++p) if (sel->keeps(p)) h_newidx[p] = (uint32_t)o++;
         });
     }
     run_parts([&](unsigned t, uint64_t lo, uint64_t hi) {
         uint64_t nbsum = 0, o = pruned ? part_kept[t] : lo;
         for (uint64_t p = lo; p < hi; ++p) {
-            if (pruned && !plan->keeps(shard_index, p)) continue;
+            if (pruned && !sel->keeps(p)) continue;
             const int64_t par = v->parent_id[p];
             const uint32_t n = v->num_samples[p], l = v->num_local[p], nb = v->num_bits[p], last = v->last_sample_id[p];
             if (par >= (int64_t)p) bad = 1;
@@ -316,7 +316,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
             h_last[o] = l ? last : 0u;
             h_n[o] = n;
             h_nbits[o] = nb;
-            h_w[o] = plan_w ? plan_w[p] : (uint32_t)v->num_kmers[p];     // truncated exactly like the reference's to_add (similarity_calculator.cpp:222)
+            h_w[o] = sel ? sel->weight(p, v->num_kmers) : (uint32_t)v->num_kmers[p];     // truncated exactly like the reference's to_add (similarity_calculator.cpp:222)
             nbsum += nb;
             ++o;
         }
@@ -333,7 +333,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         // streams of different threads can share a word at the range boundaries: OR the words in atomically
         uint64_t pos = part_bits[t];
         for (uint64_t p = lo; p < hi; ++p) {
-            if (pruned && !plan->keeps(shard_index, p)) continue;
+            if (pruned && !sel->keeps(p)) continue;
             const uint32_t nb = v->num_bits[p];
             if (!nb) continue;
             const uint64_t* src = v->data + v->data_offset[p];
@@ -375,15 +375,14 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         h2d_bytes += (v->n_buckets + 1) * 8 + n_slots * 8;
         dev_ht_bytes = (v->n_buckets + 1) * 8 + n_slots * 8 + P * 4;
     }
-    if (shard_count > 1 && !plan) return kmdb_set_error("kmdb_db_upload_shard: internal: a prefix shard without a plan");
-    // (prefix-bucket shard: the weights came from the plan — the shard's own k-mer counts, partial matrices of all shards sum to the full
-    // one — and, unless the upload carries the hashtables (new2all's pattern ids must all resolve: whole tree), only the kept nodes)
+    // (a part of the database: the weights came from the plan — a prefix shard's own k-mer counts, a tree range's num_kmers inside the range
+    // and 0 for the ancestors before it; partial matrices of all parts sum to the full one — and, unless the upload carries the hashtables
+    // (new2all's pattern ids must all resolve: whole tree), only the kept nodes)
     HIP_TRY(hipStreamSynchronize(st));
     phase("H2D");
-    if (pruned && verbose) fprintf(stderr, "[kmdb] upload: prefix shard %u / %u keeps %llu of %llu patterns (%.1f MB over PCIe)\n", shard_index, shard_count,
+    if (pruned && verbose) fprintf(stderr, "[kmdb] upload: the %s keeps %llu of %llu patterns (%.1f MB over PCIe)\n", sel->what,
                                    (unsigned long long)P, (unsigned long long)P_view, h2d_bytes / 1e6);
     if (pruned) db->P = P;
-    if (plan && shard_count > 1) plan->release_weights(shard_index);
     h_newidx.reset();
     for (HostRegion r : {h_parent.release(), h_ll.release(), h_last.release(), h_n.release(), h_nbits.release(), h_w.release(), h_bits.release()})
         if (r.p) db->staging.emplace_back(r.p, r.bytes);
@@ -489,7 +488,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     DevTmp<LayStats> d_stats;
     if (d_stats.alloc(1)) return 1;
     HIP_TRY(hipMemsetAsync(d_stats.p, 0, sizeof(LayStats), st));
-    if (shard_count <= 1) {
+    if (!sel) {
         // the checksum sum_p w_p C(n_p, 2) is defined on the full 64-bit counts
         if (d_wfull.alloc(P)) return 1;
         HIP_TRY(hipMemcpyAsync(d_wfull.p, v->num_kmers, P * 8, hipMemcpyHostToDevice, st));

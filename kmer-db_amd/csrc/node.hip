@@ -9,6 +9,9 @@
 // SURVEY 8e), and every device brings ITS chunk to the host (dense) or compacts it where it is (sparse:
 // kmdb_sparse_from_dense_device).  RCCL is loaded with dlopen when a second device is used, so a one-GPU box needs no librccl
 // (KMDB_NODE_FORCE_RCCL=1 runs the same RCCL calls on a one-rank communicator: the part of the path a one-GPU box can exercise).
+// kmdb_node_upload_partition(KMDB_PARTITION_RANGE): shard s is range s of S contiguous ranges of the pattern tree's DFS pre-order instead
+// (kmdb_db_upload_range, host_ranges.cpp) — all2all as the reference loads it, without the hashtables (console_all2all.cpp:26); everything
+// after the upload is shared by the two partitions.
 #include "engine_state.h"
 
 #include <rccl/rccl.h>
@@ -226,12 +229,19 @@ void node_fill_stats(kmdb_node* nd) {
 }  // namespace
 
 extern "C" int kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, const int32_t* devices, uint32_t n_devices, kmdb_node** out) {
+    return kmdb_node_upload_partition(view, n_shards, devices, n_devices, KMDB_PARTITION_PREFIX, out);
+}
+
+extern "C" int kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_shards, const int32_t* devices, uint32_t n_devices, int partition,
+                                          kmdb_node** out) {
     if (!out) return kmdb_set_error("kmdb_node_upload: null argument");
     *out = nullptr;
-    if (!view || view->abi_version != KMDB_ABI_VERSION) return kmdb_set_error("kmdb_node_upload: bad view / ABI version");
+    if (partition != KMDB_PARTITION_PREFIX && partition != KMDB_PARTITION_RANGE) return kmdb_set_error("kmdb_node_upload: unknown partition (KMDB_PARTITION_PREFIX or KMDB_PARTITION_RANGE)");
+    const bool ranges = partition == KMDB_PARTITION_RANGE;
+    if (!view || !kmdb_abi_compatible(view->abi_version)) return kmdb_set_error("kmdb_node_upload: bad view / ABI version");
     if (n_shards == 0 || n_devices == 0 || !devices) return kmdb_set_error("kmdb_node_upload: no shards / no devices");
     if (n_shards > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_node_upload: more than " + std::to_string(KMDB_MAX_SHARDS) + " shards");
-    if (n_shards > 1 && view->n_buckets == 0) return kmdb_set_error("kmdb_node_upload: prefix shards need the hashtables (load the database with mode Everything)");
+    if (!ranges && n_shards > 1 && view->n_buckets == 0) return kmdb_set_error("kmdb_node_upload: prefix shards need the hashtables (load the database with mode Everything)");
     const uint32_t D = std::min(n_shards, n_devices);           // a device without a shard would only add zeros to the reduce
     for (uint32_t a = 0; a < D; ++a)
         for (uint32_t b = a + 1; b < D; ++b)
@@ -246,6 +256,7 @@ extern "C" int kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, con
     nd->meet.n = D;
     const char* force = getenv("KMDB_NODE_FORCE_RCCL");
     nd->use_rccl = D > 1 || (force && force[0] == '1');
+    nd->stats.partition = (uint32_t)partition;
     const auto t0 = std::chrono::steady_clock::now();
     // The shards are planned on the host (host_shards.cpp: one pass over the hashtable items, one sweep over the tree) — all at once while their
     // weight counters (4 bytes per pattern and shard until a shard's upload releases its own) fit a budget, else in rounds of whole multiples of
@@ -261,11 +272,19 @@ extern "C" int kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, con
     uint64_t budget = 16ull << 30;
     if (const char* e = getenv("KMDB_PLAN_BUDGET_MB")) if (*e) budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;      // (tests: several rounds on a small database)
     const uint64_t per_shard = std::max<uint64_t>(view->n_patterns * 4, 1);
-    const uint32_t group = n_shards == 1 ? 1u : (uint32_t)std::min<uint64_t>(n_shards, std::max<uint64_t>(D, budget / per_shard / D * D));
+    // (tree ranges: one plan for all of them — a position per pattern and a short ancestor list per range (host_ranges.cpp), nothing per shard
+    // that a budget would have to bound — so one round)
+    const uint32_t group = n_shards == 1 || ranges ? n_shards : (uint32_t)std::min<uint64_t>(n_shards, std::max<uint64_t>(D, budget / per_shard / D * D));
+    kmdb_range_plan rplan;
+    if (ranges && n_shards > 1 && !rc) {
+        const auto p0 = std::chrono::steady_clock::now();
+        rc = kmdb_range_plan_build(view, n_shards, &rplan);
+        nd->stats.plan_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
+    }
     for (uint32_t g0 = 0; g0 < n_shards && !rc; g0 += group) {
         const uint32_t g1 = std::min(n_shards, g0 + group);
         kmdb_shard_plan plan;
-        if (n_shards > 1) {
+        if (n_shards > 1 && !ranges) {
             const auto p0 = std::chrono::steady_clock::now();
             std::vector<uint32_t> subset;
             for (uint32_t sh = g0; sh < g1; ++sh) subset.push_back(sh);
@@ -280,7 +299,8 @@ extern "C" int kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, con
             for (uint32_t sh = g0; sh < g1; ++sh) {
                 if (sh % D != d) continue;
                 kmdb_db* db = nullptr;
-                if (n_shards == 1 ? kmdb_db_upload(view, &o, 0, &db) : kmdb_db_upload_planned(view, &o, 0, sh, n_shards, &plan, &db)) return 1;
+                if (n_shards == 1 ? kmdb_db_upload(view, &o, 0, &db)
+                                  : ranges ? kmdb_db_upload_range_planned(view, &o, sh, &rplan, &db) : kmdb_db_upload_planned(view, &o, 0, sh, n_shards, &plan, &db)) return 1;
                 s.shards.push_back(db);
                 kmdb_stats st{};
                 if (!kmdb_db_stats(db, &st)) { s.h2d_bytes += st.h2d_bytes; s.n_patterns += st.n_patterns; }

@@ -175,7 +175,7 @@ void check(int rc) {
 struct Db {
     kmdbh_db* h = nullptr;
     kmdb_db* d = nullptr;
-    kmdb_node* node = nullptr;               // -gpus N: the database prefix-sharded over the devices of the node
+    kmdb_node* node = nullptr;               // -gpus N: the database sharded over the devices of the node (prefix buckets or tree ranges)
     std::thread dropper;                     // gives the host image's pages back while the run goes on (uploaded())
     // the database is on the device: from here on only names and k-mer counts are read from the host image
     void uploaded() { if (h && !dropper.joinable()) dropper = std::thread([hh = h]() { kmdbh_db_release_patterns(hh); }); }
@@ -186,6 +186,7 @@ struct Common {
     int threads = 0;
     int device = 0;
     int gpus = 0;                            // -gpus N: N prefix-bucket shards over the node's devices (0: one device, no sharding)
+    int partition = KMDB_PARTITION_PREFIX;   // -partition prefix|range: what a shard of -gpus N is (all2all, all2all-sp)
     bool sparse = false;
     Filters filters;
     RowSampler sampler;
@@ -194,20 +195,26 @@ struct Common {
 // -gpus N (all2all, all2all-sp): the database is read WITH its hashtables (the shard weights come from the items' prefix buckets),
 // shard s of N goes to device s % D of the D devices the node has (from -gpu on), and the partial matrices meet in one RCCL
 // reduce-scatter (kmdb_node_*).  On a node with fewer devices than shards the shards of a device run one after the other.
+// -partition range: shard s is range s of N ranges of the pattern tree instead; nothing of it needs a hashtable, so the database is read
+// with mode 2 (SkipHashtables) as the reference's all2all reads it (console_all2all.cpp:26).
 void node_upload(Db& db, const std::string& path, const Common& c) {
-    check(kmdbh_db_load(path.c_str(), c.gpus > 1 ? 0 : 2, &db.h));
+    const bool ranges = c.partition == KMDB_PARTITION_RANGE;
+    check(kmdbh_db_load(path.c_str(), c.gpus > 1 && !ranges ? 0 : 2, &db.h));
     const int have = kmdb_device_count();
     if (have <= c.device) throw std::runtime_error("no usable GPU (device " + std::to_string(c.device) + ")");
     std::vector<int32_t> devs;
     for (int d = c.device; d < have && (int)devs.size() < c.gpus; ++d) devs.push_back(d);
-    check(kmdb_node_upload(kmdbh_db_view(db.h), (uint32_t)c.gpus, devs.data(), (uint32_t)devs.size(), &db.node));
+    check(kmdb_node_upload_partition(kmdbh_db_view(db.h), (uint32_t)c.gpus, devs.data(), (uint32_t)devs.size(), c.partition, &db.node));
     kmdb_node_stats st{};
     check(kmdb_node_stats_get(db.node, &st));
-    std::cerr << "Database sharded by k-mer prefix bucket: " << st.n_shards << " shards on " << st.n_devices << " GPU(s)" << std::endl;
+    if (ranges) std::cerr << "Database loaded without hashtables and sharded by range of the pattern tree: ";
+    else std::cerr << "Database sharded by k-mer prefix bucket: ";
+    std::cerr << st.n_shards << " shards on " << st.n_devices << " GPU(s)" << std::endl;
 }
 void node_report(const Db& db) {
     kmdb_node_stats st{};
     if (kmdb_node_stats_get(db.node, &st)) return;
+    std::cerr << "  partition: " << (st.partition == KMDB_PARTITION_RANGE ? "range" : "prefix") << " (plan " << st.plan_s << " s)" << std::endl;
     std::cerr << "  per device: compute " << st.call_ms << " ms, RCCL reduce-scatter " << st.collective_ms << " ms";
     if (st.rccl_version) std::cerr << " (RCCL " << st.rccl_version << ")";
     std::cerr << ", result to host " << st.d2h_ms << " ms" << std::endl;
@@ -1071,6 +1078,8 @@ void usage() {
                  "Common options: -t <threads>, -gpu <device>\n"
                  "all2all / all2all-sp: -gpus <N>  the k-mer space in N prefix-bucket shards over the node's GPUs (from -gpu on), partial matrices\n"
                  "                                  summed by one RCCL reduce-scatter; more shards than devices: a device runs its shards in turn\n"
+                 "                      -partition prefix|range  (with -gpus) what a shard is: the k-mers of a set of prefix buckets (default; the\n"
+                 "                                  database is read with its hashtables), or a range of the pattern tree (read without them)\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
@@ -1093,6 +1102,13 @@ int main(int argc, char** argv) {
             c.gpus = std::atoi(v.c_str());
             if (c.gpus < 1 || c.gpus > 4096) throw std::runtime_error("-gpus expects a number of prefix-bucket shards (1 or more)");
             if (mode != "all2all" && mode != "all2all-sp" && mode != "all2all-parts") throw std::runtime_error("-gpus applies to all2all, all2all-sp and all2all-parts");
+        }
+        if (take_option(args, "-partition", v)) {
+            if (v == "prefix") c.partition = KMDB_PARTITION_PREFIX;
+            else if (v == "range") c.partition = KMDB_PARTITION_RANGE;
+            else throw std::runtime_error("-partition expects prefix or range");
+            if (mode != "all2all" && mode != "all2all-sp") throw std::runtime_error("-partition applies to all2all and all2all-sp");
+            if (c.gpus < 1) throw std::runtime_error("-partition goes with -gpus <N>");
         }
         take_switch(args, "-v");
         take_switch(args, "-vv");
