@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define KMDB_ABI_VERSION 8
-/* ABI 8 is ABI 7 plus entry points (tree ranges): no struct changed its size or the order of its fields, so the library also accepts a
+/* ABI 8 is ABI 7 plus entry points (tree ranges; query shards): no struct changed its size or the order of its fields, so the library also accepts a
  * kmdb_db_view whose abi_version is 7 — a caller compiled against the previous header runs unchanged. */
 
 /* ---------------------------------------------------------------------------------------
@@ -182,6 +182,20 @@ int  kmdb_db_upload_shard(const kmdb_db_view* view, const kmdb_opts* opts, int w
  * For all2all / all2all-sp only — no hashtables are copied (new2all and db2db need every pattern id); kmdb_opts.shard_index /
  * shard_count slice the handle's resident stream as on any other.  range_count == 1 is kmdb_db_upload(view, opts, 0, out). */
 int  kmdb_db_upload_range(const kmdb_db_view* view, const kmdb_opts* opts, uint32_t range_index, uint32_t range_count, kmdb_db** out);
+/* One QUERY shard of the database (prefix buckets are the natural new2all partition).  Makes the query call sites multi-GPU:
+ * one2all / one2all_sp at console_new2all.cpp:64-95 (:82, :78) and console_one2all.cpp — a database whose tables do not fit one device
+ * answers queries from several.  The handle holds the pruned tree of prefix shard shard_index of shard_count (the nodes whose subtree holds
+ * a k-mer of a bucket b with b % shard_count == shard_index, at the shard's own weights, exactly as kmdb_db_upload_shard lays it out) AND
+ * the slots of those buckets only: local bucket b / shard_count, capacities and slot order unchanged (probing stays slot-exact), every
+ * value rewritten from the view's pattern id to the node's index in the handle's own layout (the empty marker INT32_MAX stays).  No slot
+ * of a foreign bucket crosses PCIe and nothing of the size of the view's pattern or slot count stays on the device; kmdb_stats.h2d_bytes,
+ * device_bytes and n_patterns report what the shard holds.  The new2all entry points on such a handle count only the k-mers of its own
+ * buckets (a foreign k-mer is a miss): every k-mer belongs to one bucket, so the rows of the shards sum (uint32) to the rows of the whole
+ * database, and out_kmer_counts of the sequence entry sum to the query's count.  All2all on it gives the shard's partial matrix as on
+ * any prefix shard.  A shard that owns no k-mer is a valid handle (zero rows, a zero matrix; it keeps the tree at weight 0 like an empty
+ * prefix shard).  The view must carry the hashtables; a value that is no pattern id of the view is refused.  shard_count == 1 is
+ * kmdb_db_upload(view, opts, 1, out). */
+int  kmdb_db_upload_query_shard(const kmdb_db_view* view, const kmdb_opts* opts, uint32_t shard_index, uint32_t shard_count, kmdb_db** out);
 void kmdb_db_free(kmdb_db* db);
 /* Waits for the handle's background housekeeping (the upload's host staging buffers are given back by a helper thread after the first
  * call).  A front-end that ends the process right after its call waits here first: the helper's threads free the pages several times
@@ -260,6 +274,17 @@ int  kmdb_new2all_batch_seq_alphabet(kmdb_db* db, const char* const* seqs, const
                                      double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
                                      const kmdb_opts* opts);
 
+/* kmdb_new2all_batch / kmdb_new2all_batch_seq_alphabet with the rows left on the device: they are ADDED (uint32) into out_dev, a
+ * caller-owned, caller-zeroed nq x N uint32 buffer in DEVICE memory, on opts->stream (the handle's own stream when NULL) — what the
+ * query shards of one database on one device, and the devices of a node before their reduce, accumulate into (the multi-GPU form of
+ * console_new2all.cpp:78,82 and console_one2all.cpp).  Any handle with tables serves them, not only query shards.  The calls return
+ * when their last kernel has ended.  On a query-shard handle out_kmer_counts[q] counts the unique k-mers of the shard's own buckets. */
+int  kmdb_new2all_batch_device(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq, void* out_dev,
+                               const kmdb_opts* opts);
+int  kmdb_new2all_batch_seq_alphabet_device(kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                            double start_fraction, int32_t alphabet, void* out_dev, uint64_t* out_kmer_counts,
+                                            const kmdb_opts* opts);
+
 /* Replaces SimilarityCalculator::db2db_sp(db_row, db_col, SparseMatrix&, bubbles) (similarity_calculator.cpp:1225-1540),
  * the off-diagonal cell of the all2all-parts grid (call sites console_all2all_parts.cpp:180,226): both databases
  * resident with hashtables on the same device.  out: n_samples(db_row) x n_samples(db_col) uint32, row-major, host
@@ -313,6 +338,10 @@ int  kmdb_node_upload(const kmdb_db_view* view, uint32_t n_shards, const int32_t
  * upload (own shards summed on the device, reduce-scatter, dense copy / sparse compaction) is the same for both. */
 #define KMDB_PARTITION_PREFIX 0
 #define KMDB_PARTITION_RANGE  1
+/* KMDB_PARTITION_PREFIX_TABLES: shard s is QUERY shard s of n_shards (kmdb_db_upload_query_shard: the prefix shard's pruned tree and the
+ * slots of its own buckets), on devices[s % D] — the partition of new2all / one2all (console_new2all.cpp:64-95, console_one2all.cpp); the
+ * view must carry the hashtables.  all2all / all2all-sp work on such a node as on a prefix node; kmdb_node_new2all_* need it. */
+#define KMDB_PARTITION_PREFIX_TABLES 2
 int  kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_shards, const int32_t* devices, uint32_t n_devices, int partition,
                                 kmdb_node** out);
 void kmdb_node_free(kmdb_node* node);
@@ -323,6 +352,21 @@ int  kmdb_node_all2all_dense(kmdb_node* node, uint32_t* out_lower_tri, const kmd
  * kmdb_all2all_sparse); rows concatenate over the devices' chunks in ascending column order */
 int  kmdb_node_all2all_sparse(kmdb_node* node, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
                               kmdb_sparse_rows* out, const kmdb_opts* opts);
+/* = kmdb_new2all_batch / _seq_alphabet / _sparse over the query shards of a node uploaded with KMDB_PARTITION_PREFIX_TABLES (any other
+ * partition is refused): one2all<false> / one2all_sp of console_new2all.cpp:82 / :78 and console_one2all.cpp over the GPUs of a node.
+ * Every device adds the rows of its own shards into one nq x N buffer (kmdb_new2all_batch*_device); with D > 1 the buffers meet in ONE
+ * ncclReduceScatter (uint32 sum) over D flat chunks of ceil(nq N / D) cells and every device copies its chunk to out_dense.  K-mer entry:
+ * a sorted query holds a bucket as one contiguous run — the host cuts every query at the bucket boundaries (kmdbh_query_shard_runs) and a
+ * device receives only the runs of its own shards, so every query k-mer crosses PCIe once in all.  Sequence entry: the text goes to every
+ * device and each shard keeps the positions of its own buckets before it sorts; out_kmer_counts is the sum over the shards.
+ * kmdb_node_stats / kmdb_node_device_stats are filled as for all2all (call_ms: the device's own shards). */
+int  kmdb_node_new2all_batch(kmdb_node* node, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense,
+                             const kmdb_opts* opts);
+int  kmdb_node_new2all_batch_seq_alphabet(kmdb_node* node, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                          double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
+                                          const kmdb_opts* opts);
+int  kmdb_node_new2all_batch_sparse(kmdb_node* node, const uint64_t* const* kmers, const size_t* counts, size_t nq, kmdb_sparse_rows* out,
+                                    const kmdb_opts* opts);
 
 /* ---------------------------------------------------------------------------------------
  * Host-side helpers of the front-end (no GPU needed).  They mirror the reference's loader
@@ -351,6 +395,18 @@ uint64_t    kmdbh_db_pattern_section_bytes(const kmdbh_db* db);
  * it keeps (those whose subtree holds a k-mer of a bucket b with b % n_shards == s; bucket = kmer >> 32, types.h:25-27) and the
  * k-mers it owns (items of those buckets, hashmap_lp.h:71-78).  The view must carry the hashtables. */
 int  kmdbh_shard_plan_counts(const kmdb_db_view* view, uint32_t n_shards, uint64_t* kept_nodes, uint64_t* kmers);
+/* The host's plan of the query shards kmdb_db_upload_query_shard / KMDB_PARTITION_PREFIX_TABLES work from (no GPU; call sites served:
+ * console_new2all.cpp:64-95, console_one2all.cpp): per shard s the nodes it keeps and the k-mers it owns (as above), the slots of its own
+ * bucket table (the sum of the capacities of the buckets b with b % n_shards == s, unchanged) and the number of those buckets,
+ * ceil((n_buckets - s) / n_shards); local bucket = b / n_shards.  The view must carry the hashtables. */
+int  kmdbh_query_shard_plan_counts(const kmdb_db_view* view, uint32_t n_shards, uint64_t* kept_nodes, uint64_t* kmers, uint64_t* slots,
+                                   uint64_t* buckets);
+/* The stretches of a sorted, duplicate-free query (KmerHelper::unique, console_new2all.cpp:73) that query shard `shard` of n_shards owns:
+ * bucket = kmer >> 32 (types.h:25-27), so a bucket is one contiguous run and a shard's k-mers are the runs [run_begin[i], run_end[i]) —
+ * maximal, ascending, disjoint; over all shards they cover the query once.  Returns the number of runs; writes the first `cap` of them
+ * (run_begin / run_end may be NULL with cap 0 to count). */
+size_t kmdbh_query_shard_runs(const uint64_t* kmers, size_t count, uint32_t n_shards, uint32_t shard, uint64_t* run_begin, uint64_t* run_end,
+                              size_t cap);
 /* The host's plan of the tree ranges kmdb_node_upload_partition / kmdb_db_upload_range work from (no GPU, no hashtables; ABI 8; call sites
  * served: console_all2all.cpp:26,31-36): from parent_id and num_samples alone, the DFS pre-order (children of a node, and the roots, in
  * ascending pattern id) cut into n_ranges contiguous stretches balanced by an estimate of the nodes' cost.  Per range s: own_nodes = nodes

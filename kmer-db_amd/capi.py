@@ -75,15 +75,16 @@ FLAG_FORCE_TILE = 4
 FLAG_NO_FALLBACK = 8
 FLAG_ONE_SHOT = 16
 PATH_NONE, PATH_RECORDS, PATH_TILE, PATH_GLOBAL = 0, 1, 2, 3
-PARTITIONS = ("prefix", "range")      # KMDB_PARTITION_*
+PARTITIONS = ("prefix", "range", "prefix-tables")      # KMDB_PARTITION_*
 
 # every symbol include/kmdb_amd.h declares
 EXPORTS = [
-    "kmdb_last_error", "kmdb_abi_version", "kmdb_device_count", "kmdb_device_prepare", "kmdb_db_upload", "kmdb_db_upload_shard", "kmdb_db_upload_range", "kmdb_db_free", "kmdb_db_settle", "kmdb_db_stats", "kmdb_db_fallback_reason",
+    "kmdb_last_error", "kmdb_abi_version", "kmdb_device_count", "kmdb_device_prepare", "kmdb_db_upload", "kmdb_db_upload_shard", "kmdb_db_upload_range", "kmdb_db_upload_query_shard", "kmdb_db_free", "kmdb_db_settle", "kmdb_db_stats", "kmdb_db_fallback_reason",
     "kmdb_node_upload", "kmdb_node_upload_partition", "kmdb_node_free", "kmdb_node_stats_get", "kmdb_node_device_stats_get", "kmdb_node_all2all_dense", "kmdb_node_all2all_sparse",
+    "kmdb_node_new2all_batch", "kmdb_node_new2all_batch_seq_alphabet", "kmdb_node_new2all_batch_sparse", "kmdb_new2all_batch_device", "kmdb_new2all_batch_seq_alphabet_device",
     "kmdb_all2all_dense", "kmdb_all2all_dense_device", "kmdb_all2all_sparse", "kmdb_all2all_sparse_filtered", "kmdb_sparse_from_dense_device", "kmdbh_metric", "kmdbh_metric_id", "kmdb_sparse_free",
     "kmdb_new2all_batch", "kmdb_new2all_batch_sparse", "kmdb_new2all_batch_seq", "kmdb_new2all_batch_seq_alphabet", "kmdb_db2db_dense",
-    "kmdbh_shard_plan_counts", "kmdbh_range_plan", "kmdbh_db_load", "kmdbh_db_free", "kmdbh_db_release_patterns", "kmdbh_db_view", "kmdbh_db_kmer_length", "kmdbh_db_fraction",
+    "kmdbh_shard_plan_counts", "kmdbh_query_shard_plan_counts", "kmdbh_query_shard_runs", "kmdbh_range_plan", "kmdbh_db_load", "kmdbh_db_free", "kmdbh_db_release_patterns", "kmdbh_db_view", "kmdbh_db_kmer_length", "kmdbh_db_fraction",
     "kmdbh_db_start_fraction", "kmdbh_db_alphabet", "kmdbh_db_n_samples", "kmdbh_db_sample_name",
     "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique",
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
@@ -110,6 +111,17 @@ def lib():
     L.kmdb_db_upload.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_int, C.POINTER(C.c_void_p)]
     L.kmdb_db_upload_shard.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.kmdb_db_upload_range.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.kmdb_db_upload_query_shard.argtypes = [C.POINTER(_View), C.POINTER(_Opts), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.kmdb_new2all_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_new2all_batch_seq_alphabet_device.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                                         C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_node_new2all_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_node_new2all_batch_sparse.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_node_new2all_batch_seq_alphabet.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdbh_query_shard_plan_counts.argtypes = [C.POINTER(_View), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmdbh_query_shard_runs.restype = C.c_size_t
+    L.kmdbh_query_shard_runs.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
     L.kmdb_db_free.argtypes = [C.c_void_p]
     L.kmdb_db_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
     L.kmdb_db_fallback_reason.argtypes = [C.c_void_p]
@@ -228,6 +240,12 @@ class HostDB:
         _check(L.kmdbh_shard_plan_counts(self.view, n_shards, kept.ctypes.data, kmers.ctypes.data))
         return kept, kmers
 
+    def query_shard_plan_counts(self, n_shards):
+        """kmdbh_query_shard_plan_counts: (nodes kept, k-mers owned, slots, buckets) per query shard, planned on the host"""
+        out = [np.zeros(n_shards, np.uint64) for _ in range(4)]
+        _check(lib().kmdbh_query_shard_plan_counts(self.view, n_shards, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
     def range_plan(self, n_ranges):
         """kmdbh_range_plan: the tree ranges of the database, planned on the host without the hashtables — a dict of
         kept / own / cost / first_depth per range and range_of per pattern"""
@@ -287,6 +305,16 @@ def range_plan(view, n_ranges):
     return {k: (a if k == "range_of" else a[:R]) for k, a in out.items()}
 
 
+def query_shard_runs(kmers, n_shards, shard):
+    """kmdbh_query_shard_runs: the (begin, end) stretches of a sorted query that query shard `shard` of n_shards owns"""
+    a = np.ascontiguousarray(kmers, np.uint64)
+    n = int(lib().kmdbh_query_shard_runs(a.ctypes.data, a.size, int(n_shards), int(shard), None, None, 0))
+    b = np.zeros(max(n, 1), np.uint64)
+    e = np.zeros(max(n, 1), np.uint64)
+    lib().kmdbh_query_shard_runs(a.ctypes.data, a.size, int(n_shards), int(shard), b.ctypes.data, e.ctypes.data, n)
+    return [(int(x), int(y)) for x, y in zip(b[:n], e[:n])]
+
+
 def make_view(kmer_length, n_samples, num_kmers, parent_id, num_samples, num_local, last_sample_id, num_bits,
               data_offset, data, bucket_offset=None, slots=None):
     """Build a kmdb_db_view over caller-owned numpy arrays; returns (view, keepalive)."""
@@ -329,8 +357,10 @@ class SparseRows:
 class DeviceDB:
     """A database resident in HBM (kmdb_db_upload)."""
 
-    def __init__(self, src, device=0, with_hashtables=False, flags=0, prefix_shard=None, tree_range=None):
-        """prefix_shard=(index, count): keep only the k-mers of the prefix buckets b with b % count == index
+    def __init__(self, src, device=0, with_hashtables=False, flags=0, prefix_shard=None, tree_range=None, query_shard=None):
+        """query_shard=(index, count): the pruned tree of that prefix shard AND the slots of its own buckets (kmdb_db_upload_query_shard):
+        new2all on it counts the k-mers of its own buckets, the rows of all shards sum to the database's.
+        prefix_shard=(index, count): keep only the k-mers of the prefix buckets b with b % count == index
         (kmdb_db_upload_shard; the source must carry the hashtables).
         tree_range=(index, count): keep only the patterns of range `index` of `count` ranges of the tree's DFS pre-order, and the
         ancestors of its first node at weight 0 (kmdb_db_upload_range; all2all / all2all-sp only, no hashtables needed)."""
@@ -345,7 +375,11 @@ class DeviceDB:
         self.device = device
         self._d = C.c_void_p()
         o = _opts(device, (0, 1), flags)
-        if tree_range is not None:
+        if query_shard is not None:
+            if prefix_shard is not None or tree_range is not None:
+                raise ValueError("query_shard goes with neither prefix_shard nor tree_range")
+            _check(lib().kmdb_db_upload_query_shard(view, C.byref(o), int(query_shard[0]), int(query_shard[1]), C.byref(self._d)))
+        elif tree_range is not None:
             if prefix_shard is not None or with_hashtables:
                 raise ValueError("tree_range goes with neither prefix_shard nor with_hashtables")
             _check(lib().kmdb_db_upload_range(view, C.byref(o), int(tree_range[0]), int(tree_range[1]), C.byref(self._d)))
@@ -426,6 +460,31 @@ class DeviceDB:
         _check(lib().kmdb_new2all_batch(self._d, ptrs, cnts, nq, out.ctypes.data if out.size else None, C.byref(o)))
         return out
 
+    def new2all_device(self, queries, dev_ptr, stream=None):
+        """kmdb_new2all_batch_device: the rows are ADDED into the caller's zeroed nq x N uint32 device buffer at dev_ptr
+        (e.g. a torch tensor's data_ptr())"""
+        qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
+        nq = len(qs)
+        ptrs = (C.c_void_p * max(nq, 1))(*[q.ctypes.data for q in qs])
+        cnts = (C.c_size_t * max(nq, 1))(*[q.size for q in qs])
+        o = _opts(self.device, stream=stream)
+        _check(lib().kmdb_new2all_batch_device(self._d, ptrs, cnts, nq, C.c_void_p(dev_ptr), C.byref(o)))
+
+    def new2all_seq_device(self, seqs, dev_ptr, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None, stream=None):
+        """kmdb_new2all_batch_seq_alphabet_device: as new2all_seq, the rows ADDED into the device buffer at dev_ptr; returns the
+        unique k-mer count per query (on a query shard: of its own buckets)"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        nq = len(bs)
+        ptrs = (C.c_char_p * max(nq, 1))(*bs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(b) for b in bs])
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        o = _opts(self.device, stream=stream)
+        _check(lib().kmdb_new2all_batch_seq_alphabet_device(self._d, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet),
+                                                            C.c_void_p(dev_ptr), cnt.ctypes.data, C.byref(o)))
+        return cnt[:nq]
+
     def db2db(self, col):
         """shared k-mers between every sample of this database (rows) and every sample of `col` (columns)"""
         out = np.zeros((self.N, col.N), dtype=np.uint32)
@@ -487,7 +546,8 @@ class DeviceDB:
 
 class NodeDB:
     """One database sharded over the devices of the node (kmdb_node_upload_partition): n_shards shards, shard s on devices[s % D];
-    partition "prefix" (prefix buckets, needs the hashtables) or "range" (ranges of the pattern tree, all2all without them)."""
+    partition "prefix" (prefix buckets, needs the hashtables), "range" (ranges of the pattern tree, all2all without them) or
+    "prefix-tables" (query shards: a prefix shard's tree and the slots of its own buckets — what new2all / one2all need)."""
 
     def __init__(self, src, n_shards, devices=(0,), partition="prefix"):
         self._keep = src
@@ -517,6 +577,40 @@ class NodeDB:
         cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
         _check(lib().kmdb_node_all2all_sparse(self._n, fs, len(filters), None if cnt is None else cnt.ctypes.data,
                                               -1 if measure is None else METRICS.index(measure), C.byref(raw), None))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
+    def new2all(self, queries):
+        qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
+        nq = len(qs)
+        ptrs = (C.c_void_p * max(nq, 1))(*[q.ctypes.data for q in qs])
+        cnts = (C.c_size_t * max(nq, 1))(*[q.size for q in qs])
+        out = np.zeros((nq, self.N), dtype=np.uint32)
+        _check(lib().kmdb_node_new2all_batch(self._n, ptrs, cnts, nq, out.ctypes.data if out.size else None, None))
+        return out
+
+    def new2all_seq(self, seqs, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        nq = len(bs)
+        ptrs = (C.c_char_p * max(nq, 1))(*bs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(b) for b in bs])
+        out = np.zeros((nq, self.N), dtype=np.uint32)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        _check(lib().kmdb_node_new2all_batch_seq_alphabet(self._n, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet),
+                                                          out.ctypes.data if out.size else None, cnt.ctypes.data, None))
+        return out, cnt[:nq]
+
+    def new2all_sparse(self, queries):
+        qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
+        nq = len(qs)
+        ptrs = (C.c_void_p * max(nq, 1))(*[q.ctypes.data for q in qs])
+        cnts = (C.c_size_t * max(nq, 1))(*[q.size for q in qs])
+        raw = _Sparse()
+        _check(lib().kmdb_node_new2all_batch_sparse(self._n, ptrs, cnts, nq, C.byref(raw), None))
         try:
             return SparseRows(raw)
         finally:

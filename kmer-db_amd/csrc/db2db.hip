@@ -359,6 +359,7 @@ static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmd
     if (kmdb_engine_get(db_col, &ec)) return 1;
     if (!er.n_buckets || !er.slots || !ec.n_buckets || !ec.slots)
         return kmdb_set_error("kmdb_db2db_dense: both databases must be uploaded with hashtables");
+    if (er.qs_count > 1 || ec.qs_count > 1) return kmdb_set_error("kmdb_db2db_dense: a query shard holds only its own buckets (upload the parts with kmdb_db_upload)");
     if (er.kmer_length != ec.kmer_length) return kmdb_set_error("kmdb_db2db_dense: the databases have different k-mer lengths");
     if (er.device != ec.device) return kmdb_set_error("kmdb_db2db_dense: the databases live on different devices");
     // (sample ids take 20 bits here as everywhere: round 4's limit of 65 535 samples per part — a 16-bit block index array of fixed size in the

@@ -196,7 +196,7 @@ namespace {
 // plan / rplan: the part of the database this handle holds — shard `shard_index` of `shard_count` prefix-bucket shards (plan == nullptr: planned
 // here), or range `shard_index` of rplan's tree ranges; neither (shard_count 1): the whole database
 int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
-                const kmdb_range_plan* rplan, kmdb_db** out) {
+                const kmdb_range_plan* rplan, kmdb_db** out, bool query_shard = false) {
     *out = nullptr;
     if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload: bad view / ABI version");
     if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
@@ -242,6 +242,7 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
         kmdb_kept_nodes sel;
         if (rplan) sel = kmdb_kept_of_range(*rplan, shard_index);
         else if (plan && shard_count > 1) sel = kmdb_kept_of_shard(*plan, shard_index);
+        if (query_shard && plan && shard_count > 1) { sel.what = "query shard"; sel.qs_index = shard_index; sel.qs_count = shard_count; }
         const bool part_of_db = rplan || (plan && shard_count > 1);
         const int rc = kmdb_layout_upload(db, v, with_hashtables, part_of_db ? &sel : nullptr);
         if (plan && shard_count > 1) plan->release_weights(shard_index);      // the shard's P counters go back
@@ -271,6 +272,20 @@ extern "C" int kmdb_db_upload(const kmdb_db_view* v, const kmdb_opts* opts, int 
 extern "C" int kmdb_db_upload_shard(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count,
                                     kmdb_db** out) {
     return upload_impl(v, opts, with_hashtables, shard_index, shard_count, nullptr, nullptr, out);
+}
+// a query shard: the prefix shard's pruned tree with the slots of its own buckets (layout.hip)
+int kmdb_db_upload_query_planned(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan, kmdb_db** out) {
+    if (!out) return kmdb_set_error("kmdb_db_upload_query_shard: null argument");
+    *out = nullptr;
+    if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload_query_shard: bad view / ABI version");
+    if (shard_count == 0 || shard_count > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_db_upload_query_shard: shard_count must be between 1 and " + std::to_string(KMDB_MAX_SHARDS));
+    if (shard_index >= shard_count) return kmdb_set_error("kmdb_db_upload_query_shard: shard_index >= shard_count");
+    if (shard_count == 1) return kmdb_db_upload(v, opts, 1, out);
+    if (!v->n_buckets) return kmdb_set_error("kmdb_db_upload_query_shard: the view carries no hashtables (load the database with mode Everything)");
+    return upload_impl(v, opts, 1, shard_index, shard_count, plan, nullptr, out, true);
+}
+extern "C" int kmdb_db_upload_query_shard(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t shard_index, uint32_t shard_count, kmdb_db** out) {
+    return kmdb_db_upload_query_planned(v, opts, shard_index, shard_count, nullptr, out);
 }
 extern "C" int kmdb_db_upload_range(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t range_index, uint32_t range_count, kmdb_db** out) {
     if (!out) return kmdb_set_error("kmdb_db_upload_range: null argument");
@@ -332,7 +347,7 @@ int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* o) {
     o->meta = db->meta; o->bitpos = db->bitpos; o->parent = db->parent; o->w = db->w; o->sub_end = db->sub_end;
     o->ck_ofs = db->ck_ofs; o->ck_bit = db->ck_bit; o->ck_id = db->ck_id;
     o->bits = db->bits; o->n_buckets = db->n_buckets; o->bucket_offset = db->bucket_offset; o->slots = db->slots;
-    o->pid2dfs = db->pid2dfs; o->stream = db->stream;
+    o->pid2dfs = db->pid2dfs; o->qs_index = db->qs_index; o->qs_count = db->qs_count; o->stream = db->stream;
     o->max_depth = db->max_depth; o->list_sets = &db->list_sets; o->list_sets_nb = &db->list_sets_nb; o->list_sets_tried = &db->list_sets_tried;
     o->rl_ofs = &db->rl_ofs; o->rl_runs = &db->rl_runs; o->rl_node = &db->rl_node; o->rl_tried = &db->rl_tried;
     o->device_bytes = &db->stats.device_bytes;

@@ -26,6 +26,7 @@ struct kmdb_engine_view {
     const uint64_t* bucket_offset;
     const uint64_t* slots;
     const uint32_t* pid2dfs;
+    uint32_t qs_index, qs_count;   // query shard: qs_count > 1, the tables hold the buckets b % qs_count == qs_index at b / qs_count and DFS indices as values; pid2dfs is null
     uint32_t max_depth;            // nodes on the longest root path
     // list store of db2db.hip, kept with the handle: the full sample list of every pattern as a bit set of list_sets_nb words
     // (built on the first db2db call that can afford it, freed by kmdb_db_free)
@@ -45,6 +46,10 @@ struct kmdb_engine_view {
 // also builds the v1 / new2all node arrays on first use; non-zero on failure
 int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* out);
 void kmdb_engine_set_times(kmdb_db* db, double kernel_ms, double dominant_ms);
+
+// host compaction of dense new2all rows into the CSR of one2all_sp (new2all.hip; node.hip uses it after its reduce); 0, or 1 with the error set
+struct kmdb_sparse_rows;
+int kmdb_rows_to_sparse(const uint32_t* dense, size_t nq, uint64_t N, kmdb_sparse_rows* out);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

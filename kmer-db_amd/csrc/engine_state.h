@@ -211,6 +211,9 @@ struct kmdb_db {
     uint64_t* bucket_offset = nullptr;
     uint64_t* slots = nullptr;
     uint32_t* pid2dfs = nullptr;    // original pattern id -> DFS index
+    // query shard (kmdb_db_upload_query_shard; qs_count > 1): the tables above are those of the buckets b with b % qs_count == qs_index only
+    // (local bucket b / qs_count), their values are DFS indices of this handle's own layout, and there is no pid2dfs
+    uint32_t qs_index = 0, qs_count = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // side stream: the stream chunks are sorted and applied next to the wide kernel
     hipEvent_t ev_side[2] = {nullptr, nullptr};
@@ -252,6 +255,8 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
 // kmdb_db_upload_shard with a plan the caller made for several shards at once (node.hip); plan == nullptr: the shard is planned by itself
 int kmdb_db_upload_planned(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
                            kmdb_db** out);
+// kmdb_db_upload_query_shard with such a plan
+int kmdb_db_upload_query_planned(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan, kmdb_db** out);
 // kmdb_db_upload_range with a plan the caller made for all ranges (node.hip)
 int kmdb_db_upload_range_planned(const kmdb_db_view* v, const kmdb_opts* opts, uint32_t range_index, const kmdb_range_plan* plan, kmdb_db** out);
 

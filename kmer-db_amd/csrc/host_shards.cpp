@@ -54,6 +54,40 @@ extern "C" int kmdbh_shard_plan_counts(const kmdb_db_view* view, uint32_t n_shar
     return 0;
 }
 
+// The plan of the QUERY shards (kmdb_db_upload_query_shard, KMDB_PARTITION_PREFIX_TABLES): the prefix shards' nodes and k-mers, and the own
+// bucket table of every shard — local bucket b / n_shards at the bucket's own capacity.
+extern "C" int kmdbh_query_shard_plan_counts(const kmdb_db_view* view, uint32_t n_shards, uint64_t* kept_nodes, uint64_t* kmers, uint64_t* slots,
+                                             uint64_t* buckets) {
+    if (!view || !kept_nodes || !kmers || !slots || !buckets || n_shards == 0) return kmdb_set_error("kmdbh_query_shard_plan_counts: null argument / no shards");
+    if (kmdbh_shard_plan_counts(view, n_shards, kept_nodes, kmers)) return 1;
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        kmdb_query_shard_tables(view, s, n_shards, &buckets[s], &slots[s]);
+    }
+    return 0;
+}
+void kmdb_query_shard_tables(const kmdb_db_view* v, uint32_t shard, uint32_t n_shards, uint64_t* n_buckets, uint64_t* n_slots) {
+    uint64_t nb = 0, ns = 0;
+    for (uint64_t b = shard; b < v->n_buckets; b += n_shards) { ++nb; ns += v->bucket_offset[b + 1] - v->bucket_offset[b]; }
+    *n_buckets = nb; *n_slots = ns;
+}
+
+extern "C" size_t kmdbh_query_shard_runs(const uint64_t* kmers, size_t count, uint32_t n_shards, uint32_t shard, uint64_t* run_begin, uint64_t* run_end,
+                                         size_t cap) {
+    if (!kmers || !n_shards) return 0;
+    size_t n = 0;
+    size_t last_end = (size_t)-1;                             // a run that ends where the next own bucket starts goes on
+    kmdb_for_bucket_runs(kmers, count, [&](uint64_t b, size_t i, size_t e) {
+        if (b % n_shards != shard) return;
+        if (n && last_end == i) { if (n - 1 < cap && run_end) run_end[n - 1] = e; }
+        else {
+            if (n < cap && run_begin && run_end) { run_begin[n] = i; run_end[n] = e; }
+            ++n;
+        }
+        last_end = e;
+    });
+    return n;
+}
+
 namespace {
 // work(t) for t < T on T threads; a thread that cannot be started (std::system_error) has its share done by the caller, and every
 // started thread is joined before anything propagates (a joinable std::thread that is destroyed calls std::terminate)

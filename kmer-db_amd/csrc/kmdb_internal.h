@@ -45,6 +45,22 @@ struct kmdb_shard_plan {
 // plans the listed shards (all of them: kmdb_node_upload; one: kmdb_db_upload_shard); 0, or 1 with the error set
 int kmdb_shard_plan_build(const kmdb_db_view* v, uint32_t n_shards, const std::vector<uint32_t>& shards, kmdb_shard_plan* plan);
 
+// the own bucket table of query shard `shard` of n_shards: its buckets (b % n_shards == shard, local index b / n_shards) and their slots
+void kmdb_query_shard_tables(const kmdb_db_view* v, uint32_t shard, uint32_t n_shards, uint64_t* n_buckets, uint64_t* n_slots);
+
+// The buckets of a sorted query (KmerHelper::unique; bucket = kmer >> 32, types.h:25-27): fn(bucket, begin, end) for every maximal stretch
+// [begin, end) of k-mers of one bucket, ascending.  What kmdbh_query_shard_runs and the node driver's split of k-mer queries are made of.
+template <class F>
+inline void kmdb_for_bucket_runs(const uint64_t* kmers, size_t count, F&& fn) {
+    for (size_t i = 0; i < count;) {
+        const uint64_t b = kmers[i] >> 32;
+        size_t e = i + 1;
+        while (e < count && (kmers[e] >> 32) == b) ++e;
+        fn(b, i, e);
+        i = e;
+    }
+}
+
 // ---- host_ranges.cpp: the tree ranges of one database (the pattern / subtree is the natural all2all unit), planned from
 // parent_id and num_samples alone — no hashtables.  The DFS pre-order of the device layout (children of a node and the roots in ascending
 // pattern id: layout.hip) is cut into n_ranges contiguous stretches of about equal estimated cost; range s = positions [cut[s], cut[s + 1]).
@@ -82,6 +98,8 @@ struct kmdb_kept_nodes {
     uint32_t lo = 0, hi = 0;                   // own nodes: lo <= pre[p] < hi
     const uint32_t* anc = nullptr;             // ascending pattern ids of the zero-weight nodes (all of them before `lo` in the pre-order,
     uint32_t n_anc = 0;                        // or pattern 0 alone for an empty range: every array stays non-empty)
+    // query shard (kmdb_db_upload_query_shard): a prefix shard that also carries the slots of its own buckets, qs_count > 0
+    uint32_t qs_index = 0, qs_count = 0;
 
     bool owns(uint64_t p) const { return pre[p] - lo < hi - lo; }
     bool keeps(uint64_t p) const {

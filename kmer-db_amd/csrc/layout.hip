@@ -62,6 +62,16 @@ __global__ void lay_pid2dfs_kernel(const uint32_t* __restrict__ acc, uint32_t n,
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = acc[i] - 1u;
 }
+// query shard: the values of its own slots, kept index -> DFS index, in place (the host wrote the kept index while it packed the shard's
+// buckets; acc[i] - 1 = pre-order position of kept node i).  One slot per thread and step, the wave reads 512 contiguous bytes; only the value
+// word is written back.  The empty marker stays; the host has checked every other value against the kept count.
+__global__ __launch_bounds__(256) void lay_slots_to_dfs_kernel(uint64_t* __restrict__ slots, uint64_t n_slots, const uint32_t* __restrict__ acc, uint32_t P) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_slots; j += stride) {
+        const uint32_t val = (uint32_t)(slots[j] >> 32);
+        if (val != 0x7fffffffu && val < P) ((uint32_t*)(slots + j))[1] = acc[val] - 1u;
+    }
+}
 __global__ void lay_gather_u32_kernel(const uint32_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint32_t* __restrict__ dst) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
@@ -253,7 +263,9 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     // nothing else crosses PCIe — no hashtable slots, no node of another part of the tree.  (A prefix shard that owns no k-mer at all
     // keeps the whole tree with zero weights: every array stays non-empty.)
     // (An upload that carries the hashtables keeps the whole tree: new2all's pattern ids must all resolve.)
-    const bool pruned = sel && !with_hashtables && !getenv("KMDB_SHARD_WHOLE_TREE") && sel->kept > 0 && sel->kept < P_view;
+    // (A query shard is the exception: it carries only the slots of its own buckets, their values rewritten for the pruned layout below.)
+    const bool qshard = sel && sel->qs_count > 1 && with_hashtables && v->n_buckets;
+    const bool pruned = sel && (!with_hashtables || qshard) && !getenv("KMDB_SHARD_WHOLE_TREE") && sel->kept > 0 && sel->kept < P_view;
     uint64_t P = pruned ? sel->kept : P_view;                  // nodes laid out
     uint64_t h2d_bytes = 0;
     const uint64_t N = v->n_samples;
@@ -348,6 +360,45 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
             }
         }
     });
+    // ---- query shard: its own buckets packed back to back (local bucket b / count at the bucket's capacity, slot order kept), every value
+    // rewritten to the node's index among the kept ones; the device turns that into the DFS index once the pre-order is known
+    uint64_t qs_buckets = 0, qs_slots = 0;
+    if (qshard) kmdb_query_shard_tables(v, sel->qs_index, sel->qs_count, &qs_buckets, &qs_slots);
+    HostBuf<uint64_t> h_qoff(qs_buckets + 1), h_qslots(qs_slots);      // (one page each when the upload is no query shard)
+    if (qshard) {
+        HostBuf<uint64_t>& off = h_qoff;
+        HostBuf<uint64_t>& sl = h_qslots;
+        if (!off.p || !sl.p) return kmdb_set_error("kmdb_db_upload_query_shard: out of host memory");
+        off[0] = 0;
+        for (uint64_t lb = 0; lb < qs_buckets; ++lb) {
+            const uint64_t b = lb * sel->qs_count + sel->qs_index;
+            off[lb + 1] = off[lb] + (v->bucket_offset[b + 1] - v->bucket_offset[b]);
+        }
+        const unsigned TQ = (unsigned)std::min<uint64_t>(std::min(64u, hw), std::max<uint64_t>(1, qs_slots / (1u << 20)));
+        std::atomic<int> bad_val{0};
+        auto pack = [&](unsigned t) {
+            for (uint64_t lb = qs_buckets * t / TQ; lb < qs_buckets * (t + 1) / TQ; ++lb) {
+                const uint64_t b = lb * sel->qs_count + sel->qs_index;
+                const uint64_t* src = v->slots + v->bucket_offset[b];
+                uint64_t* dst = sl.p + off[lb];
+                const uint64_t cap = off[lb + 1] - off[lb];
+                for (uint64_t j = 0; j < cap; ++j) {
+                    const uint64_t it = src[j];
+                    const int32_t val = (int32_t)(it >> 32);
+                    if (val == INT32_MAX) { dst[j] = it; continue; }
+                    if (val < 0 || (uint64_t)val >= P_view || (pruned && !sel->keeps((uint64_t)val))) { bad_val = 1; dst[j] = it | (0x7fffffffull << 32); continue; }
+                    dst[j] = (it & 0xFFFFFFFFull) | ((uint64_t)(pruned ? h_newidx[(uint64_t)val] : (uint32_t)val) << 32);
+                }
+            }
+        };
+        {
+            std::vector<std::thread> pool;
+            for (unsigned t = 1; t < TQ; ++t) pool.emplace_back(pack, t);
+            pack(0u);
+            for (auto& th : pool) th.join();
+        }
+        if (bad_val) return kmdb_set_error("kmdb_db_upload_query_shard: a hashtable value is no pattern id of the view");
+    }
     phase("host: narrow fields + pack streams");
 
     // ---- H2D
@@ -365,7 +416,16 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     h2d_bytes += P * 24 + n_bit_words * 8;
     DevTmp<unsigned long long> d_wfull;                       // sum_pairs uses the untruncated counts
     uint64_t dev_ht_bytes = 0;
-    if (with_hashtables && v->n_buckets) {
+    if (qshard) {
+        // only the shard's own bucket table: no slot of a foreign bucket crosses PCIe, and no pid2dfs array is made (the slots hold DFS indices)
+        db->n_buckets = qs_buckets; db->qs_index = sel->qs_index; db->qs_count = sel->qs_count;
+        HIP_TRY(hipMalloc((void**)&db->bucket_offset, (qs_buckets + 1) * 8));
+        HIP_TRY(hipMalloc((void**)&db->slots, std::max<uint64_t>(qs_slots, 1) * 8));
+        HIP_TRY(hipMemcpyAsync(db->bucket_offset, h_qoff.p, (qs_buckets + 1) * 8, hipMemcpyHostToDevice, st));
+        if (qs_slots) HIP_TRY(hipMemcpyAsync(db->slots, h_qslots.p, qs_slots * 8, hipMemcpyHostToDevice, st));
+        h2d_bytes += (qs_buckets + 1) * 8 + qs_slots * 8;
+        dev_ht_bytes = (qs_buckets + 1) * 8 + std::max<uint64_t>(qs_slots, 1) * 8;
+    } else if (with_hashtables && v->n_buckets) {
         const uint64_t n_slots = v->bucket_offset[v->n_buckets];
         db->n_buckets = v->n_buckets;
         HIP_TRY(hipMalloc((void**)&db->bucket_offset, (v->n_buckets + 1) * 8));
@@ -384,7 +444,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
                                    (unsigned long long)P, (unsigned long long)P_view, h2d_bytes / 1e6);
     if (pruned) db->P = P;
     h_newidx.reset();
-    for (HostRegion r : {h_parent.release(), h_ll.release(), h_last.release(), h_n.release(), h_nbits.release(), h_w.release(), h_bits.release()})
+    for (HostRegion r : {h_parent.release(), h_ll.release(), h_last.release(), h_n.release(), h_nbits.release(), h_w.release(), h_bits.release(), h_qoff.release(), h_qslots.release()})
         if (r.p) db->staging.emplace_back(r.p, r.bytes);
 
     // ---- device: DFS pre-order
@@ -503,7 +563,13 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     HIP_TRY(hipMemcpyAsync(hflags, flags.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (hflags[1]) return kmdb_set_error("kmdb_db_upload: pattern tree is not a forest");
-    if (with_hashtables && v->n_buckets) {
+    if (qshard) {
+        if (qs_slots) {
+            hipLaunchKernelGGL(lay_slots_to_dfs_kernel, dim3((unsigned)std::min<uint64_t>((qs_slots + 255) / 256, 8192)), dim3(256), 0, st, db->slots, qs_slots, acc[cur].p, (uint32_t)P);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    } else if (with_hashtables && v->n_buckets) {
         // pid -> DFS index for the hash lookups of new2all
         HIP_TRY(hipMalloc((void**)&db->pid2dfs, std::max<uint64_t>(P, 1) * 4));
         hipLaunchKernelGGL(lay_pid2dfs_kernel, dim3(G), dim3(B), 0, st, acc[cur].p, (uint32_t)P, db->pid2dfs);

@@ -22,6 +22,12 @@
 //           histogram of the workgroup, flushed with one global atomic per touched sample.  A local
 //           list of up to 32 ids is decoded by the visiting thread, a longer one by the whole workgroup
 //           in pieces of 32 ids from the list index (checkpoints built with the node arrays).
+//
+// Query shards (kmdb_db_upload_query_shard; console_new2all.cpp:64-95 and console_one2all.cpp over several GPUs): the handle holds the slots
+// of the prefix buckets b with b % count == index only.  The probe tests ownership first (a foreign k-mer is a miss), takes the local bucket
+// b / count and reads the DFS index straight from the slot; the sequence entry drops the positions of foreign buckets before its sorts.
+// kmdb_new2all_batch_device / kmdb_new2all_batch_seq_alphabet_device leave the rows on the device, ADDED into the caller's buffer (the walk
+// flushes with global atomics anyway): what the shards of a device, and the devices of a node before their reduce, accumulate into.
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
 #include "engine_internal.h"
@@ -46,24 +52,34 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {        // murmur3 final
     return h;
 }
 
-// (1) probe: one thread per k-mer of the batch
+// the bucket of a k-mer word (src/types.h:25-27) and whether query shard qs_index of qs_count owns it: ONE function for the probe, the
+// sequence path's compaction and (on the host, kmdbh_query_shard_runs) the split of k-mer queries
+__device__ __forceinline__ bool n2a_owned(unsigned long long kmer, uint32_t qs_index, uint32_t qs_count) {
+    return (uint32_t)(kmer >> 32) % qs_count == qs_index;
+}
+
+// (1) probe: one thread per k-mer of the batch.  QS: the handle is a query shard — n_buckets / bucket_offset / slots are its OWN bucket table
+// (local bucket b / qs_count), a k-mer of a foreign bucket is a miss before anything is read, and a slot's value is the DFS index itself
+// (no pid2dfs load).
+template <bool QS>
 __global__ void n2a_probe_kernel(const uint64_t* __restrict__ kmers, const uint64_t* __restrict__ qoff, uint32_t nq, size_t total,
                                  uint64_t n_buckets, const uint64_t* __restrict__ bucket_offset, const uint64_t* __restrict__ slots,
-                                 const uint32_t* __restrict__ pid2dfs, const uint32_t* __restrict__ w, uint32_t pbits,
-                                 unsigned long long* __restrict__ keys) {
+                                 const uint32_t* __restrict__ pid2dfs, const uint32_t* __restrict__ w, uint32_t pbits, uint32_t P,
+                                 uint32_t qs_index, uint32_t qs_count, unsigned long long* __restrict__ keys) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
         unsigned long long key = N2_INVALID;
         const uint64_t k = kmers[i];
-        const uint64_t b = k >> 32;
+        uint64_t b = k >> 32;
+        if (QS) b = n2a_owned(k, qs_index, qs_count) ? (uint32_t)b / qs_count : ~0ull;      // (a foreign bucket: no local bucket)
         if (b < n_buckets) {
             const uint64_t off = bucket_offset[b];
             const uint64_t cap = bucket_offset[b + 1] - off;
             if (cap) {
                 const int32_t val = kmdb_probe(slots, off, cap, (uint32_t)k);
-                if (val != 0x7fffffff) {
-                    const uint32_t d = pid2dfs[val];
+                if (val != 0x7fffffff && (!QS || (uint32_t)val < P)) {
+                    const uint32_t d = QS ? (uint32_t)val : pid2dfs[val];
                     if (w[d] != 0) {                              // :847-848 skips patterns without k-mers
                         // query of this k-mer: binary search in the batch's offsets
                         uint32_t lo = 0, hi = nq;
@@ -490,9 +506,11 @@ static bool n2a_run_index(const kmdb_engine_view& e, hipStream_t st) {
 }
 
 // probe / sort / count / walk over a batch whose k-mers (sorted and unique per query, query by query) and
-// query offsets are already on the device
+// query offsets are already on the device.  out_dev == nullptr: the rows go to out_dense in host memory (a zeroed buffer of the call's own,
+// copied back); else they are ADDED into the caller's nq x N device buffer — the walk flushes with global atomics either way — and nothing
+// is zeroed or copied.
 static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, const uint64_t* d_kmers, const uint64_t* d_qoff_p,
-                   size_t total, size_t nq, uint32_t* out_dense) {
+                   size_t total, size_t nq, uint32_t* out_dense, uint32_t* out_dev = nullptr) {
     const uint64_t N = e.N;
     DevBuf d_keys, d_keys2, d_uniq, d_cnt, d_csum, d_nruns, d_qstart, d_sim, d_tmp;
     N2_TRY(d_keys.alloc(total * 8));
@@ -502,7 +520,8 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
     N2_TRY(d_csum.alloc((total + 2) * 4));
     N2_TRY(d_nruns.alloc(16));
     N2_TRY(d_qstart.alloc((nq + 2) * 4));
-    N2_TRY(d_sim.alloc(nq * N * 4));
+    if (!out_dev) N2_TRY(d_sim.alloc(nq * N * 4));
+    uint32_t* const sim = out_dev ? out_dev : d_sim.as<uint32_t>();
     size_t tb_sort = 0, tb_rle = 0, tb_scan = 0;
     N2_TRY(prim::sort_keys(nullptr, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
                                              (int)total, 0, 64, st));
@@ -510,7 +529,7 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
                                                  d_cnt.as<uint32_t>(), d_nruns.as<uint32_t>(), (int)total, st));
     N2_TRY(prim::exclusive_sum(nullptr, tb_scan, d_cnt.as<uint32_t>(), d_csum.as<uint32_t>(), (int)(total + 1), st));
     N2_TRY(d_tmp.alloc(std::max(tb_sort, std::max(tb_rle, tb_scan))));
-    N2_TRY(hipMemsetAsync(d_sim.p, 0, std::max<uint64_t>(nq * N * 4, 4), st));
+    if (!out_dev) N2_TRY(hipMemsetAsync(d_sim.p, 0, std::max<uint64_t>(nq * N * 4, 4), st));
 
     // the run index of the handle: made on its first new2all call (outside the call's device time, inside its wall time)
     const bool runidx = n2a_run_index(e, st);
@@ -525,8 +544,12 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
         uint32_t pbits = 1, qbits = 1;
         while ((1ull << pbits) <= e.P) ++pbits;
         while ((1ull << qbits) < nq) ++qbits;
-        hipLaunchKernelGGL(n2a_probe_kernel, dim3(blocks), dim3(256), 0, st, d_kmers, d_qoff_p, (uint32_t)nq,
-                           total, e.n_buckets, e.bucket_offset, e.slots, e.pid2dfs, e.w, pbits, d_keys.as<unsigned long long>());
+        if (e.qs_count > 1)
+            hipLaunchKernelGGL(n2a_probe_kernel<true>, dim3(blocks), dim3(256), 0, st, d_kmers, d_qoff_p, (uint32_t)nq, total, e.n_buckets, e.bucket_offset, e.slots,
+                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, e.qs_index, e.qs_count, d_keys.as<unsigned long long>());
+        else
+            hipLaunchKernelGGL(n2a_probe_kernel<false>, dim3(blocks), dim3(256), 0, st, d_kmers, d_qoff_p, (uint32_t)nq, total, e.n_buckets, e.bucket_offset, e.slots,
+                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, 0u, 1u, d_keys.as<unsigned long long>());
         N2_TRY(hipGetLastError());
         N2_TRY(prim::sort_keys(d_tmp.p, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
                                                  (int)total, 0, std::min(64u, pbits + qbits), st));
@@ -552,7 +575,7 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
 #define N2A_WALK(H, T, Q, R)                                                                                                             \
     hipLaunchKernelGGL((n2a_walk_kernel<H, T, Q, R>), dim3(wblocks), dim3(T), (H) ? N * 4 : 0, st, d_uniq.as<unsigned long long>(),      \
                        d_csum.as<uint32_t>(), d_qstart.as<uint32_t>(), nruns, (uint32_t)nq, e.meta, e.bitpos, e.parent, e.sub_end,       \
-                       e.bits, e.ck_ofs, e.ck_bit, e.ck_id, (const uint32_t*)*e.rl_ofs, (const uint32_t*)*e.rl_runs, packed_nodes ? (const uint4*)*e.rl_node : (const uint4*)nullptr, (uint32_t)N, pbits, d_sim.as<uint32_t>())
+                       e.bits, e.ck_ofs, e.ck_bit, e.ck_id, (const uint32_t*)*e.rl_ofs, (const uint32_t*)*e.rl_runs, packed_nodes ? (const uint4*)*e.rl_node : (const uint4*)nullptr, (uint32_t)N, pbits, sim)
             if (runidx) {
                 if (threads == 1024) { if (lds_hist) N2A_WALK(true, 1024, 1024, true); else N2A_WALK(false, 1024, 1024, true); }
                 else { if (lds_hist) N2A_WALK(true, 512, 1024, true); else N2A_WALK(false, 512, 1024, true); }
@@ -569,31 +592,40 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
     float ms = 0;
     N2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
     kmdb_engine_set_times(dbh, ms, ms);
-    if (nq * N) N2_TRY(hipMemcpy(out_dense, d_sim.p, nq * N * 4, hipMemcpyDeviceToHost));
+    if (!out_dev && nq * N) N2_TRY(hipMemcpy(out_dense, d_sim.p, nq * N * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
-static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense, const kmdb_opts* opts);
+// out_is_dev: `out` is the caller's device buffer and the rows are added into it (kmdb_new2all_batch_device)
+static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out, bool out_is_dev, const kmdb_opts* opts);
 
-extern "C" int kmdb_new2all_batch(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq,
-                                  uint32_t* out_dense, const kmdb_opts* opts) {
-    if (!dbh || (nq && (!kmers || !counts || !out_dense))) return kmdb_set_error("kmdb_new2all_batch: null argument");
+static int new2all_batch_impl(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out, bool out_is_dev, const kmdb_opts* opts) {
+    if (!dbh || (nq && (!kmers || !counts || !out))) return kmdb_set_error("kmdb_new2all_batch: null argument");
     kmdb_engine_view e;
     if (kmdb_engine_get(dbh, &e)) return 1;
     for (size_t q0 = 0; q0 < nq;) {
         size_t q1 = q0;
         uint64_t total = 0;
         do { total += counts[q1]; ++q1; } while (q1 < nq && total + counts[q1] <= (1ull << 30));      // k-mers per piece
-        if (new2all_once(dbh, kmers + q0, counts + q0, q1 - q0, out_dense + q0 * e.N, opts)) return 1;
+        if (new2all_once(dbh, kmers + q0, counts + q0, q1 - q0, out + q0 * e.N, out_is_dev, opts)) return 1;
         q0 = q1;
     }
     return 0;
 }
+extern "C" int kmdb_new2all_batch(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq,
+                                  uint32_t* out_dense, const kmdb_opts* opts) {
+    return new2all_batch_impl(dbh, kmers, counts, nq, out_dense, false, opts);
+}
+extern "C" int kmdb_new2all_batch_device(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, void* out_dev,
+                                         const kmdb_opts* opts) {
+    return new2all_batch_impl(dbh, kmers, counts, nq, (uint32_t*)out_dev, true, opts);
+}
 
-static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense, const kmdb_opts* opts) {
+static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out, bool out_is_dev, const kmdb_opts* opts) {
     kmdb_engine_view e;
     if (kmdb_engine_get(dbh, &e)) return 1;
-    if (!e.n_buckets || !e.slots) return kmdb_set_error("kmdb_new2all_batch: database was uploaded without hashtables");
+    // (a query shard may own no bucket at all — more shards than buckets: its tables are empty, not missing, and every k-mer is a miss)
+    if ((!e.n_buckets && e.qs_count <= 1) || !e.slots) return kmdb_set_error("kmdb_new2all_batch: database was uploaded without hashtables");
     if (nq >= (1ull << 31)) return kmdb_set_error("kmdb_new2all_batch: too many queries in one batch");
     N2_TRY(hipSetDevice(e.device));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)e.stream;
@@ -608,7 +640,7 @@ static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t
     for (size_t q = 0; q < nq; ++q)
         if (counts[q]) N2_TRY(hipMemcpyAsync(d_k.as<uint64_t>() + qoff[q], kmers[q], counts[q] * 8, hipMemcpyHostToDevice, st));
     N2_TRY(hipMemcpyAsync(d_qoff.p, qoff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, st));
-    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_dense);
+    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -678,6 +710,49 @@ __global__ __launch_bounds__(256) void n2a_extract_kernel(ExtractParams p) {
     p.qid[i] = q;
 }
 
+// Sequence entry on a query shard: of the extracted positions only those whose k-mer the shard owns go on to the sorts (the bucket of the
+// word as extracted, widening included: n2a_owned, the function the probe uses) — about 1 / qs_count of them; dropped windows (query ~0)
+// leave here too.  A workgroup takes a tile of 256 x N2_OWN_ITEMS positions with coalesced loads, ranks its kept positions with wave
+// ballots, and reserves its stretch of the output with ONE atomic for the whole tile (a reservation per 2048 positions; a counter every
+// thread or wave adds to is what DESIGN 4 (2) measured as the slow way).  The order inside the output does not matter: two radix sorts follow.
+constexpr uint32_t N2_OWN_ITEMS = 8;
+__global__ __launch_bounds__(256) void n2a_own_positions_kernel(const unsigned long long* __restrict__ kmer, const uint32_t* __restrict__ qid, uint64_t n,
+                                                                uint32_t qs_index, uint32_t qs_count, unsigned long long* __restrict__ kmer_out,
+                                                                uint32_t* __restrict__ qid_out, unsigned long long* __restrict__ counter) {
+    __shared__ uint32_t wave_cnt[4];
+    __shared__ unsigned long long tile_base;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * (256u * N2_OWN_ITEMS);
+    unsigned long long kv[N2_OWN_ITEMS];
+    uint32_t qv[N2_OWN_ITEMS], rank[N2_OWN_ITEMS];
+    uint32_t mine = 0;                                           // kept positions of this wave so far (the same in all its lanes)
+#pragma unroll
+    for (uint32_t it = 0; it < N2_OWN_ITEMS; ++it) {
+        const uint64_t i = tile0 + (uint64_t)it * 256u + threadIdx.x;
+        bool keep = false;
+        kv[it] = 0; qv[it] = 0xFFFFFFFFu;
+        if (i < n) {
+            kv[it] = kmer[i]; qv[it] = qid[i];
+            keep = qv[it] != 0xFFFFFFFFu && n2a_owned(kv[it], qs_index, qs_count);
+        }
+        const unsigned long long bal = __ballot(keep);
+        rank[it] = keep ? mine + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)) : 0xFFFFFFFFu;
+        mine += (uint32_t)__popcll(bal);
+    }
+    if (lane == 0) wave_cnt[wv] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t all = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        tile_base = all ? atomicAdd(counter, (unsigned long long)all) : 0ull;
+    }
+    __syncthreads();
+    unsigned long long base = tile_base;
+    for (uint32_t w2 = 0; w2 < wv; ++w2) base += wave_cnt[w2];
+#pragma unroll
+    for (uint32_t it = 0; it < N2_OWN_ITEMS; ++it)
+        if (rank[it] != 0xFFFFFFFFu) { kmer_out[base + rank[it]] = kv[it]; qid_out[base + rank[it]] = qv[it]; }      // (base + rank < kept positions <= n)
+}
+
 // head of a run of equal (query, k-mer) among the sorted positions
 __global__ void n2a_heads_kernel(const unsigned long long* __restrict__ kmer, const uint32_t* __restrict__ qid, uint64_t n,
                                  uint32_t* __restrict__ head) {
@@ -712,7 +787,7 @@ static uint64_t n2_seq_budget() {                        // bases per piece (one
 }
 
 static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
-                            double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
+                            double start_fraction, int32_t alphabet, uint32_t* out, bool out_is_dev, uint64_t* out_kmer_counts,
                             const kmdb_opts* opts);
 
 extern "C" int kmdb_new2all_batch_seq(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
@@ -722,9 +797,20 @@ extern "C" int kmdb_new2all_batch_seq(kmdb_db* dbh, const char* const* seqs, con
                                            out_dense, out_kmer_counts, opts);
 }
 
+static int new2all_seq_impl(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction, double start_fraction,
+                            int32_t alphabet, uint32_t* out_dense, bool out_is_dev, uint64_t* out_kmer_counts, const kmdb_opts* opts);
 extern "C" int kmdb_new2all_batch_seq_alphabet(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
                                                double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
                                                const kmdb_opts* opts) {
+    return new2all_seq_impl(dbh, seqs, seq_lens, nq, fraction, start_fraction, alphabet, out_dense, false, out_kmer_counts, opts);
+}
+extern "C" int kmdb_new2all_batch_seq_alphabet_device(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                      double start_fraction, int32_t alphabet, void* out_dev, uint64_t* out_kmer_counts,
+                                                      const kmdb_opts* opts) {
+    return new2all_seq_impl(dbh, seqs, seq_lens, nq, fraction, start_fraction, alphabet, (uint32_t*)out_dev, true, out_kmer_counts, opts);
+}
+static int new2all_seq_impl(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction, double start_fraction,
+                            int32_t alphabet, uint32_t* out_dense, bool out_is_dev, uint64_t* out_kmer_counts, const kmdb_opts* opts) {
     if (!dbh || (nq && (!seqs || !seq_lens || !out_dense || !out_kmer_counts))) return kmdb_set_error("kmdb_new2all_batch_seq: null argument");
     if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error("kmdb_new2all_batch_seq: unknown alphabet " + std::to_string(alphabet));
     kmdb_engine_view e;
@@ -735,7 +821,7 @@ extern "C" int kmdb_new2all_batch_seq_alphabet(kmdb_db* dbh, const char* const* 
         size_t q1 = q0;
         uint64_t bases = 0;
         do { bases += seq_lens[q1]; ++q1; } while (q1 < nq && bases + seq_lens[q1] <= budget);
-        if (new2all_seq_once(dbh, seqs + q0, seq_lens + q0, q1 - q0, fraction, start_fraction, alphabet, out_dense + q0 * e.N,
+        if (new2all_seq_once(dbh, seqs + q0, seq_lens + q0, q1 - q0, fraction, start_fraction, alphabet, out_dense + q0 * e.N, out_is_dev,
                              out_kmer_counts + q0, opts)) return 1;
         q0 = q1;
     }
@@ -743,11 +829,11 @@ extern "C" int kmdb_new2all_batch_seq_alphabet(kmdb_db* dbh, const char* const* 
 }
 
 static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
-                            double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
+                            double start_fraction, int32_t alphabet, uint32_t* out, bool out_is_dev, uint64_t* out_kmer_counts,
                             const kmdb_opts* opts) {
     kmdb_engine_view e;
     if (kmdb_engine_get(dbh, &e)) return 1;
-    if (!e.n_buckets || !e.slots) return kmdb_set_error("kmdb_new2all_batch_seq: database was uploaded without hashtables");
+    if ((!e.n_buckets && e.qs_count <= 1) || !e.slots) return kmdb_set_error("kmdb_new2all_batch_seq: database was uploaded without hashtables");
     const uint32_t k = e.kmer_length;
     ExtractParams p{};
     int preserve_strand = 0;
@@ -766,7 +852,6 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
     N2_TRY(d_soff.alloc((nq + 1) * 8));
     N2_TRY(d_kmer.alloc(L * 8)); N2_TRY(d_kmer2.alloc(L * 8));
     N2_TRY(d_qid.alloc(L * 4)); N2_TRY(d_qid2.alloc(L * 4));
-    N2_TRY(d_head.alloc((L + 1) * 4)); N2_TRY(d_hscan.alloc((L + 1) * 4));
     N2_TRY(d_qoff.alloc((nq + 1) * 8));
     for (size_t q = 0; q < nq; ++q)
         if (seq_lens[q]) N2_TRY(hipMemcpyAsync(d_seq.as<char>() + soff[q], seqs[q], seq_lens[q], hipMemcpyHostToDevice, st));
@@ -783,42 +868,61 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
         p.hi = (uint64_t)(u64max * (start_fraction + fraction));
         p.quarter_len = (uint64_t)std::ceil((double)k / 4.0);
         p.kmer = d_kmer.as<unsigned long long>(); p.qid = d_qid.as<uint32_t>();
-        const unsigned blocks = (unsigned)((L + 255) / 256);
-        hipLaunchKernelGGL(n2a_extract_kernel, dim3(blocks), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(n2a_extract_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, p);
         N2_TRY(hipGetLastError());
-        const int kbits = (int)std::min<uint32_t>(64u, p.bits * k + p.widen);
-        int qbits = 1;
-        while ((1ull << qbits) < nq) ++qbits;
-        size_t tb1 = 0, tb2 = 0, tb3 = 0;
-        N2_TRY(prim::sort_pairs(nullptr, tb1, d_kmer.as<unsigned long long>(), d_kmer2.as<unsigned long long>(),
-                                                  d_qid.as<uint32_t>(), d_qid2.as<uint32_t>(), (int)L, 0, kbits, st));
-        N2_TRY(prim::sort_pairs(nullptr, tb2, d_qid2.as<uint32_t>(), d_qid.as<uint32_t>(),
-                                                  d_kmer2.as<unsigned long long>(), d_kmer.as<unsigned long long>(), (int)L, 0, 32, st));
-        N2_TRY(prim::exclusive_sum(nullptr, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(L + 1), st));
-        N2_TRY(d_tmp.alloc(std::max(tb1, std::max(tb2, tb3))));
-        N2_TRY(prim::sort_pairs(d_tmp.p, tb1, d_kmer.as<unsigned long long>(), d_kmer2.as<unsigned long long>(),
-                                                  d_qid.as<uint32_t>(), d_qid2.as<uint32_t>(), (int)L, 0, kbits, st));
-        // dropped positions carry query ~0: all 32 bits take part so that they sort behind every query
-        (void)qbits;
-        N2_TRY(prim::sort_pairs(d_tmp.p, tb2, d_qid2.as<uint32_t>(), d_qid.as<uint32_t>(),
-                                                  d_kmer2.as<unsigned long long>(), d_kmer.as<unsigned long long>(), (int)L, 0, 32, st));
-        N2_TRY(hipMemsetAsync(d_head.p, 0, (L + 1) * 4, st));
-        hipLaunchKernelGGL(n2a_heads_kernel, dim3(blocks), dim3(256), 0, st, d_kmer.as<unsigned long long>(), d_qid.as<uint32_t>(), L,
-                           d_head.as<uint32_t>());
-        N2_TRY(prim::exclusive_sum(d_tmp.p, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(L + 1), st));
-        uint32_t n_unique = 0;
-        N2_TRY(hipMemcpyAsync(&n_unique, d_hscan.as<uint32_t>() + L, 4, hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(n2a_query_offsets_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st, d_qid.as<uint32_t>(),
-                           d_hscan.as<uint32_t>(), L, (uint32_t)nq, d_qoff.as<uint64_t>());
-        N2_TRY(hipGetLastError());
-        N2_TRY(hipStreamSynchronize(st));
-        total = n_unique;
-        N2_TRY(d_k.alloc(total * 8));
-        hipLaunchKernelGGL(n2a_compact_kernel, dim3(blocks), dim3(256), 0, st, d_kmer.as<unsigned long long>(), d_head.as<uint32_t>(),
-                           d_hscan.as<uint32_t>(), L, d_k.as<uint64_t>());
-        N2_TRY(hipGetLastError());
-        N2_TRY(hipMemcpyAsync(qoff.data(), d_qoff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-        N2_TRY(hipStreamSynchronize(st));
+        // the sorts ping-pong between two buffer pairs: (kA, qA) holds the positions, (kB, qB) is the other side
+        unsigned long long *kA = d_kmer.as<unsigned long long>(), *kB = d_kmer2.as<unsigned long long>();
+        uint32_t *qA = d_qid.as<uint32_t>(), *qB = d_qid2.as<uint32_t>();
+        uint64_t n = L;                                          // positions that go through the sorts
+        if (e.qs_count > 1) {
+            // a query shard: only the positions whose k-mer it owns (n2a_own_positions_kernel), BEFORE the sorts
+            DevBuf d_own;
+            N2_TRY(d_own.alloc(8));
+            N2_TRY(hipMemsetAsync(d_own.p, 0, 8, st));
+            hipLaunchKernelGGL(n2a_own_positions_kernel, dim3((unsigned)((L + 256u * N2_OWN_ITEMS - 1) / (256u * N2_OWN_ITEMS))), dim3(256), 0, st, kA, qA, L,
+                               e.qs_index, e.qs_count, kB, qB, d_own.as<unsigned long long>());
+            N2_TRY(hipGetLastError());
+            unsigned long long own = 0;
+            N2_TRY(hipMemcpyAsync(&own, d_own.p, 8, hipMemcpyDeviceToHost, st));
+            N2_TRY(hipStreamSynchronize(st));
+            if (own > L) return kmdb_set_error("kmdb_new2all_batch_seq: internal error (more own positions than positions)");
+            n = own;
+            std::swap(kA, kB); std::swap(qA, qB);
+        }
+        if (n) {
+            // (sized by the positions that go on: on a query shard the two L-sized buffer pairs above are still needed — the compaction writes
+            // into the second pair, whose length is not known before it ran — but everything from here on is about 1 / qs_count of that)
+            N2_TRY(d_head.alloc((n + 1) * 4)); N2_TRY(d_hscan.alloc((n + 1) * 4));
+            const unsigned blocks = (unsigned)((n + 255) / 256);
+            const int kbits = (int)std::min<uint32_t>(64u, p.bits * k + p.widen);
+            size_t tb1 = 0, tb2 = 0, tb3 = 0;
+            N2_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
+            N2_TRY(prim::sort_pairs(nullptr, tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
+            N2_TRY(prim::exclusive_sum(nullptr, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(n + 1), st));
+            N2_TRY(d_tmp.alloc(std::max(tb1, std::max(tb2, tb3))));
+            N2_TRY(prim::sort_pairs(d_tmp.p, tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
+            // dropped positions carry query ~0: all 32 bits take part so that they sort behind every query
+            N2_TRY(prim::sort_pairs(d_tmp.p, tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
+            N2_TRY(hipMemsetAsync(d_head.p, 0, (n + 1) * 4, st));
+            hipLaunchKernelGGL(n2a_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, qA, n, d_head.as<uint32_t>());
+            N2_TRY(prim::exclusive_sum(d_tmp.p, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(n + 1), st));
+            uint32_t n_unique = 0;
+            N2_TRY(hipMemcpyAsync(&n_unique, d_hscan.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+            hipLaunchKernelGGL(n2a_query_offsets_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st, qA,
+                               d_hscan.as<uint32_t>(), n, (uint32_t)nq, d_qoff.as<uint64_t>());
+            N2_TRY(hipGetLastError());
+            N2_TRY(hipStreamSynchronize(st));
+            total = n_unique;
+            N2_TRY(d_k.alloc(total * 8));
+            hipLaunchKernelGGL(n2a_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, d_head.as<uint32_t>(),
+                               d_hscan.as<uint32_t>(), n, d_k.as<uint64_t>());
+            N2_TRY(hipGetLastError());
+            N2_TRY(hipMemcpyAsync(qoff.data(), d_qoff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+            N2_TRY(hipStreamSynchronize(st));
+        } else {                                                 // (a shard that owns none of the batch's k-mers)
+            N2_TRY(d_k.alloc(16));
+            N2_TRY(hipMemsetAsync(d_qoff.p, 0, (nq + 1) * 8, st));
+        }
     } else {
         N2_TRY(d_k.alloc(16));
         N2_TRY(hipMemsetAsync(d_qoff.p, 0, (nq + 1) * 8, st));
@@ -826,19 +930,10 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
     for (size_t q = 0; q < nq; ++q) out_kmer_counts[q] = qoff[q + 1] - qoff[q];
     // the sort buffers are not needed any more: release them before the probe pipeline allocates its own
     d_kmer.reset(); d_kmer2.reset(); d_qid2.reset(); d_head.reset(); d_hscan.reset(); d_qid.reset();
-    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_dense);
+    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
 }
 
-extern "C" int kmdb_new2all_batch_sparse(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq,
-                                         kmdb_sparse_rows* out, const kmdb_opts* opts) {
-    if (!out) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
-    std::memset(out, 0, sizeof *out);
-    kmdb_engine_view e;
-    if (!dbh) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
-    if (kmdb_engine_get(dbh, &e)) return 1;
-    const uint64_t N = e.N;
-    std::vector<uint32_t> dense(std::max<uint64_t>(nq * N, 1));
-    if (kmdb_new2all_batch(dbh, kmers, counts, nq, dense.data(), opts)) return 1;
+int kmdb_rows_to_sparse(const uint32_t* dense, size_t nq, uint64_t N, kmdb_sparse_rows* out) {
     // one2all_sp returns the (sample, count) pairs with count > 0 ordered by sample id (:1040-1047)
     out->n_rows = nq;
     out->row_ptr = (uint64_t*)std::malloc((nq + 1) * 8);
@@ -856,4 +951,17 @@ extern "C" int kmdb_new2all_batch_sparse(kmdb_db* dbh, const uint64_t* const* km
         for (uint64_t s = 0; s < N; ++s)
             if (dense[q * N + s]) { out->col[o] = (uint32_t)s; out->val[o] = dense[q * N + s]; ++o; }
     return 0;
+}
+
+extern "C" int kmdb_new2all_batch_sparse(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq,
+                                         kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    if (!out) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
+    std::memset(out, 0, sizeof *out);
+    kmdb_engine_view e;
+    if (!dbh) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
+    if (kmdb_engine_get(dbh, &e)) return 1;
+    const uint64_t N = e.N;
+    std::vector<uint32_t> dense(std::max<uint64_t>(nq * N, 1));
+    if (kmdb_new2all_batch(dbh, kmers, counts, nq, dense.data(), opts)) return 1;
+    return kmdb_rows_to_sparse(dense.data(), nq, N, out);
 }

@@ -12,6 +12,10 @@
 // kmdb_node_upload_partition(KMDB_PARTITION_RANGE): shard s is range s of S contiguous ranges of the pattern tree's DFS pre-order instead
 // (kmdb_db_upload_range, host_ranges.cpp) — all2all as the reference loads it, without the hashtables (console_all2all.cpp:26); everything
 // after the upload is shared by the two partitions.
+// kmdb_node_upload_partition(KMDB_PARTITION_PREFIX_TABLES) + kmdb_node_new2all_*: the query call sites made multi-GPU — one2all<false> /
+// one2all_sp at src/console_new2all.cpp:64-95 (:82, :78) and src/console_one2all.cpp.  Shard s is QUERY shard s (kmdb_db_upload_query_shard:
+// the prefix shard's pruned tree and the slots of its own buckets); a call adds the rows of a device's shards into one nq x N buffer
+// (kmdb_new2all_batch*_device) and the buffers meet in the same reduce-scatter, behind the same rendezvous (node_collective).
 #include "engine_state.h"
 
 #include <rccl/rccl.h>
@@ -74,6 +78,11 @@ struct DevSlot {
     uint32_t* acc = nullptr;                                 // [per * D] the device's partial matrix (the triangle padded to equal chunks)
     uint32_t* tmp = nullptr;                                 // [cells] a further shard's matrix before it is added (only with several shards per device)
     uint32_t* chunk = nullptr;                               // [per] this device's chunk of the reduced matrix (D > 1)
+    // new2all (KMDB_PARTITION_PREFIX_TABLES): the rows of a batch, nq x N padded to D equal chunks, and this device's chunk of their sum; kept
+    // with the node and grown on demand
+    uint32_t* rows = nullptr;
+    uint32_t* rows_chunk = nullptr;
+    uint64_t rows_cap = 0, rows_chunk_cap = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // start of the call, end of the device's own shards, end of the collective, end of the copy
     ncclComm_t comm = nullptr;
@@ -111,6 +120,7 @@ struct kmdb_node {
     int rccl_version = 0;
     bool use_rccl = false;                                   // more than one device — or KMDB_NODE_FORCE_RCCL=1 on one device: the same calls on a
                                                              // one-rank communicator (what a one-GPU box can exercise of the RCCL path)
+    int partition = KMDB_PARTITION_PREFIX;
     kmdb_node_stats stats{};
     Rendezvous meet;
     std::atomic<bool> aborted{false};                        // a collective failed after the rendezvous: the communicators are gone
@@ -166,15 +176,12 @@ int node_own_shards(kmdb_node* nd, size_t d, const kmdb_opts* opts) {
     NODE_TRY(hipEventRecord(s.ev[1], s.stream));
     return 0;
 }
-// the partial matrix of device slot d in acc (all its shards), then the node's reduce-scatter behind it ON THE SAME STREAM (no host
-// wait in between: the collective starts when the device's last kernel ends); ev[2] marks its end.  The caller queues its copy /
-// compaction behind that and waits once.
-int node_accumulate(kmdb_node* nd, size_t d, bool dev_ok, const kmdb_opts* opts) {
+// What every call of the node has behind its devices' own work: the rendezvous, the node's ONE reduce-scatter of `count` cells per rank
+// (send: count x D cells, recv: this rank's chunk) ON THE DEVICE'S STREAM, and the abort of all communicators when a rank fails inside it.
+// own / own_msg: how the device's own part ended.  ev[2] marks the end of the collective.  Shared by all2all (node_accumulate) and new2all.
+int node_collective(kmdb_node* nd, size_t d, bool dev_ok, int own, const std::string& own_msg, const void* send, void* recv, uint64_t count) {
     DevSlot& s = nd->dev[d];
-    s.call_ms = s.collective_ms = s.d2h_ms = 0;
-    const int own = dev_ok ? node_own_shards(nd, d, opts) : 1;
-    const std::string own_msg = own ? kmdb_last_error() : "";
-    if (nd->use_rccl && nd->per) {
+    if (nd->use_rccl && count) {
         // every device thread arrives here, failed or not; the collective is entered by all or by none
         if (!nd->meet.arrive(own == 0)) {
             // nobody enters the collective.  A thread that succeeded still has its kernels queued: they finish before the call returns, so that
@@ -182,7 +189,7 @@ int node_accumulate(kmdb_node* nd, size_t d, bool dev_ok, const kmdb_opts* opts)
             if (dev_ok) (void)hipStreamSynchronize(s.stream);
             return kmdb_set_error(own ? own_msg : std::string("another device failed before the reduce-scatter: the collective was not entered"));
         }
-        const ncclResult_t r = nd->rccl.ReduceScatter(s.acc, s.chunk, nd->per, ncclUint32, ncclSum, s.comm, s.stream);
+        const ncclResult_t r = nd->rccl.ReduceScatter(send, recv, count, ncclUint32, ncclSum, s.comm, s.stream);
         if (r != ncclSuccess) {
             // a rank that fails AFTER the rendezvous leaves its peers inside the collective: every communicator of the node is aborted (they are
             // all this process's), which releases them with an error; the handle's collectives are unusable from here on
@@ -194,6 +201,16 @@ int node_accumulate(kmdb_node* nd, size_t d, bool dev_ok, const kmdb_opts* opts)
     } else if (own) return kmdb_set_error(own_msg);
     NODE_TRY(hipEventRecord(s.ev[2], s.stream));
     return 0;
+}
+// the partial matrix of device slot d in acc (all its shards), then the node's reduce-scatter behind it ON THE SAME STREAM (no host
+// wait in between: the collective starts when the device's last kernel ends); ev[2] marks its end.  The caller queues its copy /
+// compaction behind that and waits once.
+int node_accumulate(kmdb_node* nd, size_t d, bool dev_ok, const kmdb_opts* opts) {
+    DevSlot& s = nd->dev[d];
+    s.call_ms = s.collective_ms = s.d2h_ms = 0;
+    const int own = dev_ok ? node_own_shards(nd, d, opts) : 1;
+    const std::string own_msg = own ? kmdb_last_error() : "";
+    return node_collective(nd, d, dev_ok, own, own_msg, s.acc, s.chunk, nd->per);
 }
 // after the stream has drained: the device's times from its events
 int node_times(kmdb_node* nd, size_t d) {
@@ -236,12 +253,15 @@ extern "C" int kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_s
                                           kmdb_node** out) {
     if (!out) return kmdb_set_error("kmdb_node_upload: null argument");
     *out = nullptr;
-    if (partition != KMDB_PARTITION_PREFIX && partition != KMDB_PARTITION_RANGE) return kmdb_set_error("kmdb_node_upload: unknown partition (KMDB_PARTITION_PREFIX or KMDB_PARTITION_RANGE)");
+    if (partition != KMDB_PARTITION_PREFIX && partition != KMDB_PARTITION_RANGE && partition != KMDB_PARTITION_PREFIX_TABLES)
+        return kmdb_set_error("kmdb_node_upload: unknown partition (KMDB_PARTITION_PREFIX, KMDB_PARTITION_RANGE or KMDB_PARTITION_PREFIX_TABLES)");
     const bool ranges = partition == KMDB_PARTITION_RANGE;
+    const bool tables = partition == KMDB_PARTITION_PREFIX_TABLES;      // query shards: the prefix shard's tree and the slots of its own buckets
     if (!view || !kmdb_abi_compatible(view->abi_version)) return kmdb_set_error("kmdb_node_upload: bad view / ABI version");
     if (n_shards == 0 || n_devices == 0 || !devices) return kmdb_set_error("kmdb_node_upload: no shards / no devices");
     if (n_shards > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_node_upload: more than " + std::to_string(KMDB_MAX_SHARDS) + " shards");
     if (!ranges && n_shards > 1 && view->n_buckets == 0) return kmdb_set_error("kmdb_node_upload: prefix shards need the hashtables (load the database with mode Everything)");
+    if (tables && view->n_buckets == 0) return kmdb_set_error("kmdb_node_upload: query shards need the hashtables (load the database with mode Everything)");
     const uint32_t D = std::min(n_shards, n_devices);           // a device without a shard would only add zeros to the reduce
     for (uint32_t a = 0; a < D; ++a)
         for (uint32_t b = a + 1; b < D; ++b)
@@ -256,7 +276,7 @@ extern "C" int kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_s
     nd->meet.n = D;
     const char* force = getenv("KMDB_NODE_FORCE_RCCL");
     nd->use_rccl = D > 1 || (force && force[0] == '1');
-    nd->stats.partition = (uint32_t)partition;
+    nd->stats.partition = (uint32_t)partition; nd->partition = partition;
     const auto t0 = std::chrono::steady_clock::now();
     // The shards are planned on the host (host_shards.cpp: one pass over the hashtable items, one sweep over the tree) — all at once while their
     // weight counters (4 bytes per pattern and shard until a shard's upload releases its own) fit a budget, else in rounds of whole multiples of
@@ -299,7 +319,8 @@ extern "C" int kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_s
             for (uint32_t sh = g0; sh < g1; ++sh) {
                 if (sh % D != d) continue;
                 kmdb_db* db = nullptr;
-                if (n_shards == 1 ? kmdb_db_upload(view, &o, 0, &db)
+                if (n_shards == 1 ? kmdb_db_upload(view, &o, tables ? 1 : 0, &db)
+                                  : tables ? kmdb_db_upload_query_planned(view, &o, sh, n_shards, &plan, &db)
                                   : ranges ? kmdb_db_upload_range_planned(view, &o, sh, &rplan, &db) : kmdb_db_upload_planned(view, &o, 0, sh, n_shards, &plan, &db)) return 1;
                 s.shards.push_back(db);
                 kmdb_stats st{};
@@ -349,7 +370,7 @@ extern "C" void kmdb_node_free(kmdb_node* nd) {
         (void)hipSetDevice(s.device);
         if (s.comm && nd->rccl.CommDestroy) (void)nd->rccl.CommDestroy(s.comm);
         for (kmdb_db* db : s.shards) kmdb_db_free(db);
-        for (void* p : {(void*)s.acc, (void*)s.tmp, (void*)s.chunk}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)s.acc, (void*)s.tmp, (void*)s.chunk, (void*)s.rows, (void*)s.rows_chunk}) if (p) (void)hipFree(p);
         for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
@@ -444,4 +465,152 @@ extern "C" int kmdb_node_all2all_sparse(kmdb_node* nd, const kmdb_cell_filter* f
     for (auto& p : part) kmdb_sparse_free(&p);
     if (rc) { const std::string msg = kmdb_last_error(); kmdb_sparse_free(out); return kmdb_set_error(msg); }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// new2all / one2all over the query shards of the node (KMDB_PARTITION_PREFIX_TABLES): console_new2all.cpp:64-95 (:78, :82) and
+// console_one2all.cpp made multi-GPU.  Every k-mer belongs to one prefix bucket, so a query's row is the uint32 sum of the rows the shards
+// compute from their own buckets: a device adds its shards' rows into one buffer, the devices' buffers meet in the node's reduce-scatter.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+const char* partition_name(int p) { return p == KMDB_PARTITION_RANGE ? "range" : p == KMDB_PARTITION_PREFIX_TABLES ? "prefix-tables" : "prefix"; }
+
+// run(d, k, shard handle, rows, opts): shard k of device slot d adds its rows of the batch into `rows` on the slot's stream
+template <class Run>
+int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, uint32_t* out_dense, const kmdb_opts* opts, Run&& run) {
+    if (!nd) return kmdb_set_error(std::string(who) + ": null argument");
+    if (nd->partition != KMDB_PARTITION_PREFIX_TABLES)
+        return kmdb_set_error(std::string(who) + ": the node was uploaded with partition " + partition_name(nd->partition) +
+                              "; new2all needs the query shards of KMDB_PARTITION_PREFIX_TABLES (prefix-tables)");
+    if (nd->aborted) return kmdb_set_error(std::string(who) + ": an earlier collective failed and the node's communicators were aborted (upload again)");
+    const size_t D = nd->dev.size();
+    const uint64_t cells = (uint64_t)nq * nd->N;
+    const uint64_t per = D > 1 ? (cells + D - 1) / D : cells;      // cells per rank of the reduce-scatter
+    if (cells && !out_dense) return kmdb_set_error(std::string(who) + ": null argument");
+    const int rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
+        DevSlot& s = nd->dev[d];
+        s.call_ms = s.collective_ms = s.d2h_ms = 0;
+        auto own_part = [&]() -> int {
+            if (per * D > s.rows_cap || !s.rows) {
+                if (s.rows) (void)hipFree(s.rows);
+                s.rows = nullptr; s.rows_cap = 0;
+                NODE_TRY(hipMalloc((void**)&s.rows, std::max<uint64_t>(per * D, 1) * 4));
+                s.rows_cap = per * D;
+            }
+            if (nd->use_rccl && (per > s.rows_chunk_cap || !s.rows_chunk)) {
+                if (s.rows_chunk) (void)hipFree(s.rows_chunk);
+                s.rows_chunk = nullptr; s.rows_chunk_cap = 0;
+                NODE_TRY(hipMalloc((void**)&s.rows_chunk, std::max<uint64_t>(per, 1) * 4));
+                s.rows_chunk_cap = per;
+            }
+            kmdb_opts o{};
+            if (opts) o = *opts;
+            o.abi_version = KMDB_ABI_VERSION; o.device = s.device; o.stream = s.stream; o.shard_index = 0; o.shard_count = 1;
+            NODE_TRY(hipEventRecord(s.ev[0], s.stream));
+            if (per * D) NODE_TRY(hipMemsetAsync(s.rows, 0, per * D * 4, s.stream));
+            for (size_t k = 0; k < s.shards.size(); ++k)
+                if (run(d, k, s.shards[k], s.rows, &o)) return 1;
+            NODE_TRY(hipEventRecord(s.ev[1], s.stream));
+            return 0;
+        };
+        const int own = dev_ok ? own_part() : 1;
+        const std::string own_msg = own ? kmdb_last_error() : "";
+        if (node_collective(nd, d, dev_ok, own, own_msg, s.rows, s.rows_chunk, per)) return 1;
+        const uint32_t* p = s.rows;
+        uint64_t lo = 0, hi = cells;
+        if (nd->use_rccl) { p = s.rows_chunk; lo = std::min<uint64_t>(cells, per * d); hi = std::min<uint64_t>(cells, per * (d + 1)); }
+        if (hi > lo) NODE_TRY(hipMemcpyAsync(out_dense + lo, p, (hi - lo) * 4, hipMemcpyDeviceToHost, s.stream));
+        NODE_TRY(hipEventRecord(s.ev[3], s.stream));
+        NODE_TRY(hipStreamSynchronize(s.stream));
+        return node_times(nd, d);
+    });
+    node_fill_stats(nd);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int kmdb_node_new2all_batch(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense,
+                                       const kmdb_opts* opts) {
+    if (nq && (!kmers || !counts)) return kmdb_set_error("kmdb_node_new2all_batch: null argument");
+    if (!nd) return kmdb_set_error("kmdb_node_new2all_batch: null argument");
+    // The split of the batch (kmdbh_query_shard_runs' rule, from the same kmdb_for_bucket_runs): a sorted query holds a bucket as one contiguous
+    // run, so ONE pass of a device's thread over the batch deals every run of a bucket b to shard b % n_shards where that shard lives on the
+    // device (slot k = shard / D); only those k-mers go to the device.  Made when the device's first shard runs, used by all its shards.
+    struct ShardPart { std::vector<uint64_t> own; std::vector<size_t> off; };
+    std::vector<std::vector<ShardPart>> split;
+    try { split.resize(nd->dev.size()); } catch (const std::exception&) { return kmdb_set_error("kmdb_node_new2all_batch: out of host memory"); }
+    return node_new2all_call(nd, "kmdb_node_new2all_batch", nq, out_dense, opts, [&](size_t d, size_t k, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) -> int {
+        // (runs on the device's own thread: nothing may leave it as an exception, and a failure must still reach the rendezvous as a status)
+        try {
+            const size_t D = nd->dev.size(), K = nd->dev[d].shards.size();
+            const uint32_t n = nd->n_shards;
+            std::vector<ShardPart>& parts = split[d];
+            if (k == 0) {
+                parts.assign(K, ShardPart());
+                for (auto& p : parts) p.off.assign(nq + 1, 0);
+                for (size_t q = 0; q < nq; ++q) {
+                    const uint64_t* src = kmers[q];
+                    kmdb_for_bucket_runs(src, counts[q], [&](uint64_t b, size_t i, size_t e) {
+                        const uint64_t sh = b % n;
+                        if (sh % D == d) { auto& own = parts[sh / D].own; own.insert(own.end(), src + i, src + e); }
+                    });
+                    for (auto& p : parts) p.off[q + 1] = p.own.size();
+                }
+            }
+            ShardPart& mine = parts[k];
+            std::vector<const uint64_t*> ptrs(nq);
+            std::vector<size_t> cnt(nq);
+            for (size_t q = 0; q < nq; ++q) { ptrs[q] = mine.own.data() + mine.off[q]; cnt[q] = mine.off[q + 1] - mine.off[q]; }
+            const int rc = kmdb_new2all_batch_device(db, ptrs.data(), cnt.data(), nq, rows, o);
+            std::vector<uint64_t>().swap(mine.own);                // (the call has ended: its k-mers are on the device no longer needed)
+            return rc;
+        } catch (const std::exception& e) {
+            return kmdb_set_error(std::string("kmdb_node_new2all_batch: ") + e.what());
+        }
+    });
+}
+
+extern "C" int kmdb_node_new2all_batch_seq_alphabet(kmdb_node* nd, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                    double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
+                                                    const kmdb_opts* opts) {
+    if (nq && (!seqs || !seq_lens || !out_kmer_counts)) return kmdb_set_error("kmdb_node_new2all_batch_seq_alphabet: null argument");
+    try {
+        // the text goes to every device; a shard keeps the positions of its own buckets, so its counts are those of its own unique k-mers
+        std::vector<std::vector<uint64_t>> per_dev(nd ? nd->dev.size() : 0, std::vector<uint64_t>(nq, 0));
+        const int rc = node_new2all_call(nd, "kmdb_node_new2all_batch_seq_alphabet", nq, out_dense, opts,
+                                         [&](size_t d, size_t, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) -> int {
+            try {                                                  // (a device thread: nothing may leave it as an exception)
+                std::vector<uint64_t> cnt(std::max<size_t>(nq, 1), 0);
+                if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, cnt.data(), o)) return 1;
+                for (size_t q = 0; q < nq; ++q) per_dev[d][q] += cnt[q];
+                return 0;
+            } catch (const std::exception& e) {
+                return kmdb_set_error(std::string("kmdb_node_new2all_batch_seq_alphabet: ") + e.what());
+            }
+        });
+        if (rc) return rc;
+        for (size_t q = 0; q < nq; ++q) {
+            uint64_t sum = 0;
+            for (auto& v : per_dev) sum += v[q];
+            out_kmer_counts[q] = sum;
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string("kmdb_node_new2all_batch_seq_alphabet: ") + e.what());
+    }
+}
+
+extern "C" int kmdb_node_new2all_batch_sparse(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, kmdb_sparse_rows* out,
+                                              const kmdb_opts* opts) {
+    if (!nd || !out) return kmdb_set_error("kmdb_node_new2all_batch_sparse: null argument");
+    std::memset(out, 0, sizeof *out);
+    try {
+        std::vector<uint32_t> dense(std::max<uint64_t>((uint64_t)nq * nd->N, 1));
+        if (kmdb_node_new2all_batch(nd, kmers, counts, nq, dense.data(), opts)) return 1;
+        return kmdb_rows_to_sparse(dense.data(), nq, nd->N, out);
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string("kmdb_node_new2all_batch_sparse: ") + e.what());
+    }
 }

@@ -197,9 +197,11 @@ struct Common {
 // reduce-scatter (kmdb_node_*).  On a node with fewer devices than shards the shards of a device run one after the other.
 // -partition range: shard s is range s of N ranges of the pattern tree instead; nothing of it needs a hashtable, so the database is read
 // with mode 2 (SkipHashtables) as the reference's all2all reads it (console_all2all.cpp:26).
+// new2all / one2all -gpus N: query shards (KMDB_PARTITION_PREFIX_TABLES) — a shard holds the prefix shard's pruned tree and the slots of its own
+// buckets, so the database is always read with its hashtables.
 void node_upload(Db& db, const std::string& path, const Common& c) {
-    const bool ranges = c.partition == KMDB_PARTITION_RANGE;
-    check(kmdbh_db_load(path.c_str(), c.gpus > 1 && !ranges ? 0 : 2, &db.h));
+    const bool ranges = c.partition == KMDB_PARTITION_RANGE, tables = c.partition == KMDB_PARTITION_PREFIX_TABLES;
+    check(kmdbh_db_load(path.c_str(), tables || (c.gpus > 1 && !ranges) ? 0 : 2, &db.h));
     const int have = kmdb_device_count();
     if (have <= c.device) throw std::runtime_error("no usable GPU (device " + std::to_string(c.device) + ")");
     std::vector<int32_t> devs;
@@ -208,13 +210,14 @@ void node_upload(Db& db, const std::string& path, const Common& c) {
     kmdb_node_stats st{};
     check(kmdb_node_stats_get(db.node, &st));
     if (ranges) std::cerr << "Database loaded without hashtables and sharded by range of the pattern tree: ";
+    else if (tables) std::cerr << "Database sharded by k-mer prefix bucket, every shard with the tables of its own buckets: ";
     else std::cerr << "Database sharded by k-mer prefix bucket: ";
     std::cerr << st.n_shards << " shards on " << st.n_devices << " GPU(s)" << std::endl;
 }
 void node_report(const Db& db) {
     kmdb_node_stats st{};
     if (kmdb_node_stats_get(db.node, &st)) return;
-    std::cerr << "  partition: " << (st.partition == KMDB_PARTITION_RANGE ? "range" : "prefix") << " (plan " << st.plan_s << " s)" << std::endl;
+    std::cerr << "  partition: " << (st.partition == KMDB_PARTITION_RANGE ? "range" : st.partition == KMDB_PARTITION_PREFIX_TABLES ? "prefix-tables" : "prefix") << " (plan " << st.plan_s << " s)" << std::endl;
     std::cerr << "  per device: compute " << st.call_ms << " ms, RCCL reduce-scatter " << st.collective_ms << " ms";
     if (st.rccl_version) std::cerr << " (RCCL " << st.rccl_version << ")";
     std::cerr << ", result to host " << st.d2h_ms << " ms" << std::endl;
@@ -716,9 +719,13 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     Db db;
     std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
     auto t0 = clk::now();
-    check(kmdbh_db_load(args[0].c_str(), 0, &db.h));
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
-    check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 1, &db.d));
+    // -gpus N: N query shards over the node's devices (console_new2all.cpp:64-95 made multi-GPU: kmdb_node_new2all_*)
+    if (c.gpus > 0) { c.partition = KMDB_PARTITION_PREFIX_TABLES; node_upload(db, args[0], c); }
+    else {
+        check(kmdbh_db_load(args[0].c_str(), 0, &db.h));
+        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 1, &db.d));
+    }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const uint32_t k = kmdbh_db_kmer_length(db.h);
@@ -758,7 +765,8 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             std::vector<size_t> kc(by_kmers.size());
             std::vector<uint32_t> part(by_kmers.size() * n + 1);
             for (size_t t = 0; t < by_kmers.size(); ++t) { ptrs[t] = batch[by_kmers[t]].kmers.data(); kc[t] = batch[by_kmers[t]].kmers.size(); }
-            check(kmdb_new2all_batch(db.d, ptrs.data(), kc.data(), by_kmers.size(), part.data(), &o));
+            if (db.node) check(kmdb_node_new2all_batch(db.node, ptrs.data(), kc.data(), by_kmers.size(), part.data(), nullptr));
+            else check(kmdb_new2all_batch(db.d, ptrs.data(), kc.data(), by_kmers.size(), part.data(), &o));
             for (size_t t = 0; t < by_kmers.size(); ++t) {
                 cnts[by_kmers[t]] = kc[t];
                 std::copy(part.begin() + t * n, part.begin() + (t + 1) * n, out.begin() + by_kmers[t] * n);
@@ -770,7 +778,8 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             std::vector<uint64_t> uniq(by_text.size());
             std::vector<uint32_t> part(by_text.size() * n + 1);
             for (size_t t = 0; t < by_text.size(); ++t) { ptrs[t] = batch[by_text[t]].text.data(); lens[t] = batch[by_text[t]].text.size(); }
-            check(kmdb_new2all_batch_seq_alphabet(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, part.data(), uniq.data(), &o));
+            if (db.node) check(kmdb_node_new2all_batch_seq_alphabet(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, part.data(), uniq.data(), nullptr));
+            else check(kmdb_new2all_batch_seq_alphabet(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, part.data(), uniq.data(), &o));
             for (size_t t = 0; t < by_text.size(); ++t) {
                 cnts[by_text[t]] = (size_t)uniq[t];
                 std::copy(part.begin() + t * n, part.begin() + (t + 1) * n, out.begin() + by_text[t] * n);
@@ -861,6 +870,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
         }
     }
     flush();
+    if (db.node) node_report(db);                                  // (the last batch's call)
     std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
     return 0;
 }
@@ -876,9 +886,13 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
     Db db;
     std::cerr << "Loading k-mer database " << args[0] << ":" << std::endl;
     auto t0 = clk::now();
-    check(kmdbh_db_load(args[0].c_str(), 0, &db.h));
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
-    check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 1, &db.d));
+    // -gpus N: N query shards over the node's devices (console_one2all.cpp made multi-GPU: kmdb_node_new2all_*)
+    if (c.gpus > 0) { c.partition = KMDB_PARTITION_PREFIX_TABLES; node_upload(db, args[0], c); }
+    else {
+        check(kmdbh_db_load(args[0].c_str(), 0, &db.h));
+        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 1, &db.d));
+    }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const uint32_t k = kmdbh_db_kmer_length(db.h);
@@ -901,7 +915,8 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
         for (auto& r : recs) { text += r.seq; text += '\n'; }
         const char* tp = text.data();
         size_t tl = text.size();
-        check(kmdb_new2all_batch_seq_alphabet(db.d, &tp, &tl, 1, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), alphabet, sims.data(), &cnt, &o));
+        if (db.node) check(kmdb_node_new2all_batch_seq_alphabet(db.node, &tp, &tl, 1, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), alphabet, sims.data(), &cnt, nullptr));
+        else check(kmdb_new2all_batch_seq_alphabet(db.d, &tp, &tl, 1, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), alphabet, sims.data(), &cnt, &o));
     } else {
         std::vector<uint64_t> kmers(bases + 1);
         size_t kc = 0;
@@ -909,9 +924,11 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
             kc += kmdbh_extract_kmers_alphabet(r.seq.data(), r.seq.size(), k, alphabet, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), kmers.data() + kc);
         kc = kmdbh_sort_unique(kmers.data(), kc);
         const uint64_t* kp = kmers.data();
-        check(kmdb_new2all_batch(db.d, &kp, &kc, 1, sims.data(), &o));
+        if (db.node) check(kmdb_node_new2all_batch(db.node, &kp, &kc, 1, sims.data(), nullptr));
+        else check(kmdb_new2all_batch(db.d, &kp, &kc, 1, sims.data(), &o));
         cnt = kc;
     }
+    if (db.node) node_report(db);
     std::cerr << "Number of k-mers: " << cnt << std::endl;
     std::ofstream ofs(args[2]);
     write_header(db, ofs);
@@ -1080,6 +1097,8 @@ void usage() {
                  "                                  summed by one RCCL reduce-scatter; more shards than devices: a device runs its shards in turn\n"
                  "                      -partition prefix|range  (with -gpus) what a shard is: the k-mers of a set of prefix buckets (default; the\n"
                  "                                  database is read with its hashtables), or a range of the pattern tree (read without them)\n"
+                 "new2all / one2all: -gpus <N>     the database in N query shards over the node's GPUs (from -gpu on): a shard holds the tree and the\n"
+                 "                                  hashtable slots of its own prefix buckets; the rows of the shards are summed by one RCCL reduce-scatter\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
@@ -1101,7 +1120,7 @@ int main(int argc, char** argv) {
         if (take_option(args, "-gpus", v)) {
             c.gpus = std::atoi(v.c_str());
             if (c.gpus < 1 || c.gpus > 4096) throw std::runtime_error("-gpus expects a number of prefix-bucket shards (1 or more)");
-            if (mode != "all2all" && mode != "all2all-sp" && mode != "all2all-parts") throw std::runtime_error("-gpus applies to all2all, all2all-sp and all2all-parts");
+            if (mode != "all2all" && mode != "all2all-sp" && mode != "all2all-parts" && mode != "new2all" && mode != "one2all") throw std::runtime_error("-gpus applies to all2all, all2all-sp, all2all-parts, new2all and one2all");
         }
         if (take_option(args, "-partition", v)) {
             if (v == "prefix") c.partition = KMDB_PARTITION_PREFIX;
