@@ -24,8 +24,10 @@ extern "C" {
 #endif
 
 #define KMDB_ABI_VERSION 8
-/* ABI 8 is ABI 7 plus entry points (tree ranges; query shards): no struct changed its size or the order of its fields, so the library also accepts a
- * kmdb_db_view whose abi_version is 7 — a caller compiled against the previous header runs unchanged. */
+/* ABI 8 is ABI 7 plus entry points (tree ranges; query shards; sampled rows): no struct changed its size or the order of its fields, so the library
+ * also accepts a kmdb_db_view whose abi_version is 7 — a caller compiled against the previous header runs unchanged.  The sampled-rows entry points
+ * (KMDB_HAS_SAMPLED_ROWS) are additive in the same way: the version number stays 8 and a caller built against an earlier ABI 8 header is served. */
+#define KMDB_HAS_SAMPLED_ROWS 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -243,6 +245,43 @@ int  kmdb_sparse_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t 
 /* NOTE on streams: the call reads cells_dev on opts->stream (the handle's own stream when NULL) and does NOT order itself after
  * the caller's producer: the cells must be complete on that stream (or the device idle) before the call — after an RCCL collective
  * on another stream, wait for it first (hipStreamWaitEvent / hipStreamSynchronize). */
+/* ---------------------------------------------------------------------------------------
+ * all2all-sp -sample-rows <criterion>:<count> (params.cpp:533-557): every sample keeps its `count` best neighbours.  A pair (i, j), i > j, with
+ * a non-zero cell that passes the filters has ONE score, metric(cell, kmers[i], kmers[j], k) with the triangle's row i as the row sample, and is
+ * offered to sample i AND to sample j (SparseMatrix::add_to_sampler, array.h:450-540); a sample keeps the `count` best by score descending, then
+ * sample id ascending (the heap order of sampler.h:45-50).  The device selects candidates on the criterion's plain ratio, widened by the margin
+ * of the filters, so that neither the sparse matrix nor anything proportional to its non-zeros reaches the host; the host decides the candidates
+ * with kmdbh_metric.  Rows the margin cannot settle are fetched again whole inside the call: the result is always what the reference's Sampler keeps.
+ * ------------------------------------------------------------------------------------- */
+typedef struct kmdb_sample_stats { /* the LAST sampled call on the handle */
+    uint64_t candidates;           /* cells the device emitted (after re-fetches) */
+    uint64_t rows_truncated;       /* rows cut at their count-th best proxy less the margin with cells left below the cut */
+    uint64_t rows_refetched;       /* rows of `count` candidates or more that a filter bound inside the margin left undecided: fetched again whole */
+    uint64_t d2h_bytes;            /* bytes copied back: row pointers, 8 per candidate, one counter */
+    double   select_ms;            /* HIP events around the selection passes (kmdb_stats.kernel_ms holds the whole call) */
+    uint32_t triangle_reads;       /* passes over the (touched tiles of the) triangle: 4 histogram, 1 count, 1 emit; 2 more for a re-fetch */
+    uint32_t reserved;
+} kmdb_sample_stats;
+/* Replaces all2all_sp + add_to_sampler + Sampler::saveRowSparse (console_all2all_sparse.cpp:44,70-89; array.h:450-540; sampler.h): accumulate,
+ * candidates, exact decision and re-fetch inside the call.  out: row s = the kept neighbours of sample s in ascending id, val = common k-mers,
+ * measure = the score.  criterion: KMDB_METRIC_*; count >= 1; sample_kmers as in kmdb_all2all_sparse_filtered (required: every criterion but
+ * num-kmers needs it).  Refused with kmdb_opts.shard_count > 1, like the filtered call. */
+int  kmdb_all2all_sampled(kmdb_db* db, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion,
+                          uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts);
+/* The candidates of a flat cell range the CALLER accumulated (cells_dev, cell_lo, cell_hi and the stream note as in kmdb_sparse_from_dense_device):
+ * the multi-GPU form of console_all2all_sparse.cpp:70-89.  out_candidates: symmetric rows, ascending columns, val = common k-mers, no measures —
+ * per sample a superset of its `count` best cells among the cells of the range (exact filters included: the re-fetch happens here).  A sample's
+ * best `count` within a range is a superset of its share of the global best `count`, so the candidates of several ranges go to
+ * kmdbh_sample_rows_select together. */
+int  kmdb_sampled_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
+                                    size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count,
+                                    kmdb_sparse_rows* out_candidates, const kmdb_opts* opts);
+int  kmdb_db_sample_stats(const kmdb_db* db, kmdb_sample_stats* out);
+/* The exact decision (Sampler with strategy best, sampler.h:44-67,123-139; no GPU): any number of candidate parts of the same collection — rows of
+ * (col, val) — in, per sample the `count` best cells that pass the filters out, ascending id, val = common k-mers, measure = score.  Does not depend
+ * on the order of the candidates within or across parts; a pair listed twice counts once. */
+int  kmdbh_sample_rows_select(int criterion, uint32_t count, int kmer_length, const uint32_t* sample_kmers, const kmdb_cell_filter* filters,
+                              size_t n_filters, const kmdb_sparse_rows* const* parts, size_t n_parts, kmdb_sparse_rows* out);
 /* the measure itself (params.cpp:14-42): uint32 wrap-around integer parts, double arithmetic */
 double kmdbh_metric(int metric, uint32_t common, uint32_t cnt_row, uint32_t cnt_col, int kmer_length);
 /* KMDB_METRIC_* of a criterion name ("jaccard", "min", ..., "num-kmers"), -1 if unknown */
@@ -352,6 +391,10 @@ int  kmdb_node_all2all_dense(kmdb_node* node, uint32_t* out_lower_tri, const kmd
  * kmdb_all2all_sparse); rows concatenate over the devices' chunks in ascending column order */
 int  kmdb_node_all2all_sparse(kmdb_node* node, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
                               kmdb_sparse_rows* out, const kmdb_opts* opts);
+/* = kmdb_all2all_sampled over all shards, any partition (console_all2all_sparse.cpp:70-89 over the GPUs of a node): every device selects the
+ * candidates of its reduce-scatter chunk (kmdb_sampled_from_dense_device), the host decides once (kmdbh_sample_rows_select). */
+int  kmdb_node_all2all_sampled(kmdb_node* node, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion,
+                               uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts);
 /* = kmdb_new2all_batch / _seq_alphabet / _sparse over the query shards of a node uploaded with KMDB_PARTITION_PREFIX_TABLES (any other
  * partition is refused): one2all<false> / one2all_sp of console_new2all.cpp:82 / :78 and console_one2all.cpp over the GPUs of a node.
  * Every device adds the rows of its own shards into one nq x N buffer (kmdb_new2all_batch*_device); with D > 1 the buffers meet in ONE

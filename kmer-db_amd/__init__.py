@@ -26,5 +26,6 @@ from .capi import (  # noqa: F401
     lib_path,
     make_view,
     range_plan,
+    sample_rows_select,
     sort_unique,
 )

@@ -69,6 +69,11 @@ class _NodeDeviceStats(C.Structure):
                 ("d2h_ms", C.c_double), ("h2d_bytes", C.c_uint64), ("n_patterns", C.c_uint64), ("n_records", C.c_uint64)]
 
 
+class _SampleStats(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("rows_truncated", C.c_uint64), ("rows_refetched", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("select_ms", C.c_double), ("triangle_reads", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 FLAG_FORCE_GLOBAL_ATOMICS = 1
 FLAG_FORCE_DIRECT = 2
 FLAG_FORCE_TILE = 4
@@ -88,6 +93,7 @@ EXPORTS = [
     "kmdbh_db_start_fraction", "kmdbh_db_alphabet", "kmdbh_db_n_samples", "kmdbh_db_sample_name",
     "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique",
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
+    "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
 ]
 
 
@@ -140,6 +146,13 @@ def lib():
     L.kmdb_all2all_sparse_filtered.argtypes = [C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_sparse_from_dense_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
                                                 C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_all2all_sampled.argtypes = [C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_sampled_from_dense_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.c_uint32,
+                                                 C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_node_all2all_sampled.argtypes = [C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_db_sample_stats.argtypes = [C.c_void_p, C.POINTER(_SampleStats)]
+    L.kmdbh_sample_rows_select.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.POINTER(C.POINTER(_Sparse)), C.c_size_t,
+                                           C.POINTER(_Sparse)]
     L.kmdbh_metric.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.kmdbh_metric.restype = C.c_double
     L.kmdbh_metric_id.argtypes = [C.c_char_p]
@@ -340,6 +353,21 @@ def make_view(kmer_length, n_samples, num_kmers, parent_id, num_samples, num_loc
     return v, keep
 
 
+def _filters(filters):
+    """[(criterion name, lo, hi)], None = unbounded -> a kmdb_cell_filter array"""
+    fs = (_CellFilter * max(1, len(filters)))()
+    for i, (name, lo, hi) in enumerate(filters):
+        fs[i].metric = METRICS.index(name)
+        fs[i].lo = -np.finfo(np.float64).max if lo is None else lo
+        fs[i].hi = np.finfo(np.float64).max if hi is None else hi
+    return fs
+
+
+def _criterion(criterion):
+    """a criterion name, or the raw KMDB_METRIC_* number (passed on unchecked: the library refuses what it does not know)"""
+    return METRICS.index(criterion) if isinstance(criterion, str) else int(criterion)
+
+
 class SparseRows:
     def __init__(self, raw):
         n, nnz = int(raw.n_rows), int(raw.nnz)
@@ -449,6 +477,39 @@ class DeviceDB:
             return SparseRows(raw)
         finally:
             lib().kmdb_sparse_free(C.byref(raw))
+
+    def all2all_sampled(self, criterion, count, sample_kmers, filters=(), shard=(0, 1)):
+        """kmdb_all2all_sampled: per sample its `count` best neighbours by `criterion` (all2all-sp -sample-rows criterion:count) — ascending ids,
+        val = common k-mers, measure = the score.  The candidates are selected on the device, the decision is the host's."""
+        raw = _Sparse()
+        o = _opts(self.device, shard)
+        cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
+        _check(lib().kmdb_all2all_sampled(self._d, _filters(filters), len(filters), None if cnt is None else cnt.ctypes.data, _criterion(criterion), int(count),
+                                          C.byref(raw), C.byref(o)))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
+    def sampled_from_dense_device(self, dev_ptr, criterion, count, sample_kmers, cell_lo=0, cell_hi=None, filters=(), stream=None):
+        """kmdb_sampled_from_dense_device: the candidates (symmetric rows, no measures) of caller-accumulated cells [cell_lo, cell_hi), dev_ptr =
+        device address of cell_lo; the candidates of several ranges go to sample_rows_select together."""
+        raw = _Sparse()
+        o = _opts(self.device, stream=stream)
+        cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
+        _check(lib().kmdb_sampled_from_dense_device(self._d, C.c_void_p(dev_ptr), int(cell_lo), self.tri_size() if cell_hi is None else int(cell_hi),
+                                                    _filters(filters), len(filters), None if cnt is None else cnt.ctypes.data, _criterion(criterion), int(count),
+                                                    C.byref(raw), C.byref(o)))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
+    def sample_stats(self):
+        """kmdb_db_sample_stats: the last sampled call on the handle"""
+        s = _SampleStats()
+        _check(lib().kmdb_db_sample_stats(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
 
     def new2all(self, queries):
         qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
@@ -582,6 +643,17 @@ class NodeDB:
         finally:
             lib().kmdb_sparse_free(C.byref(raw))
 
+    def all2all_sampled(self, criterion, count, sample_kmers, filters=()):
+        """kmdb_node_all2all_sampled: DeviceDB.all2all_sampled over the shards of the node, any partition"""
+        raw = _Sparse()
+        cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
+        _check(lib().kmdb_node_all2all_sampled(self._n, _filters(filters), len(filters), None if cnt is None else cnt.ctypes.data, _criterion(criterion), int(count),
+                                               C.byref(raw), None))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
     def new2all(self, queries):
         qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
         nq = len(qs)
@@ -641,6 +713,41 @@ class NodeDB:
 
 
 # ------------------------------------------------------------------------------------------------
+def _raw_rows(n_rows, row_ptr, col, val):
+    """a kmdb_sparse_rows over caller-owned numpy arrays; returns (struct, keepalive)"""
+    keep = [np.ascontiguousarray(row_ptr, np.uint64), np.ascontiguousarray(col, np.uint32), np.ascontiguousarray(val, np.uint32)]
+    if keep[1].size == 0:
+        keep[1] = np.zeros(1, np.uint32)
+        keep[2] = np.zeros(1, np.uint32)
+    r = _Sparse()
+    r.n_rows = int(n_rows)
+    r.nnz = int(keep[0][-1]) if keep[0].size else 0
+    r.row_ptr = keep[0].ctypes.data_as(C.POINTER(C.c_uint64))
+    r.col = keep[1].ctypes.data_as(C.POINTER(C.c_uint32))
+    r.val = keep[2].ctypes.data_as(C.POINTER(C.c_uint32))
+    return r, keep
+
+
+def sample_rows_select(criterion, count, kmer_length, sample_kmers, parts, filters=()):
+    """kmdbh_sample_rows_select (no GPU): parts = candidate rows, each a SparseRows or a (row_ptr, col, val) triple over the same samples ->
+    SparseRows of the `count` best cells per sample that pass the filters: ascending ids, val = common k-mers, measure = the score"""
+    raws, keep = [], []
+    for p in parts:
+        rp, col, val = (p.row_ptr, p.col, p.val) if isinstance(p, SparseRows) else p
+        r, k = _raw_rows(len(rp) - 1, rp, col, val)
+        raws.append(r)
+        keep.append(k)
+    arr = (C.POINTER(_Sparse) * max(1, len(raws)))(*[C.pointer(r) for r in raws])
+    cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
+    out = _Sparse()
+    _check(lib().kmdbh_sample_rows_select(_criterion(criterion), int(count), int(kmer_length), None if cnt is None else cnt.ctypes.data, _filters(filters),
+                                          len(filters), arr, len(raws), C.byref(out)))
+    try:
+        return SparseRows(out)
+    finally:
+        lib().kmdb_sparse_free(C.byref(out))
+
+
 def extract_kmers(seq, k, fraction=1.0, start_fraction=0.0, preserve_strand=False):
     if isinstance(seq, str):
         seq = seq.encode()

@@ -8,12 +8,15 @@
 // uint32 adds wrap and commute, so any schedule is bit-exact with the reference.
 #include "device_common.h"
 #include "engine_internal.h"
+#include "cell_filter.h"
+#include "sample_rows.h"
 
 #include "prim.h"
 
 #include <sys/mman.h>
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <limits>
 #include <thread>
 #include <vector>
@@ -61,35 +64,6 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // dense -> CSR compaction for the sparse entry point
 // ------------------------------------------------------------------------------------------
-// Device side of the -min / -max filters: every bound is brought to one of six plain ratios of the cell
-// (log-based measures are monotone in theirs) and widened by a safety margin on the host; a cell that misses a widened bound is
-// dropped here, the rest is decided on the host with the reference's own arithmetic.
-enum { RATIO_JACCARD = 0, RATIO_MIN, RATIO_MAX, RATIO_COSINE, RATIO_QUERY, RATIO_NUM };
-constexpr int DEV_FILTER_MAX = 12;      // one bound per criterion of Params::availableMetrics (9) and a few repeats
-struct DevFilter {
-    int n;                          // bounds in use (0: keep every non-zero cell)
-    int kind[DEV_FILTER_MAX];
-    double lo[DEV_FILTER_MAX], hi[DEV_FILTER_MAX];
-    const uint32_t* counts;         // [N] k-mer counts of the samples
-};
-__device__ __forceinline__ bool dev_keep(const DevFilter& f, uint32_t c, uint32_t row, uint32_t col) {
-    if (c == 0) return false;
-    if (f.n == 0) return true;
-    const uint32_t a = f.counts[row], b = f.counts[col];
-    for (int i = 0; i < f.n; ++i) {
-        double x;
-        switch (f.kind[i]) {
-        case RATIO_JACCARD: x = (double)c / (double)(uint32_t)(a + b - c); break;
-        case RATIO_MIN:     x = (double)c / (double)(a < b ? a : b); break;
-        case RATIO_MAX:     x = (double)c / (double)(a > b ? a : b); break;
-        case RATIO_COSINE:  x = (double)c / sqrt((double)(uint32_t)(a * b)); break;
-        case RATIO_QUERY:   x = (double)c / (double)a; break;
-        default:            x = (double)c; break;
-        }
-        if (!(x >= f.lo[i] && x <= f.hi[i])) return false;      // NaN fails, as on the host
-    }
-    return true;
-}
 // The columns of row `row` inside the flat cell range [cell_lo, cell_hi) of the lower triangle (row i at i (i - 1) / 2,
 // reference src/array.h:136-140): [j0, j1).  M points at cell `cell_lo`.
 __device__ __forceinline__ void row_span(uint64_t row, uint64_t cell_lo, uint64_t cell_hi, uint64_t& j0, uint64_t& j1) {
@@ -701,6 +675,198 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
             });
         }
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// -sample-rows <criterion>:<count> with the selection on the device (sample_rows.hip) and the decision on the host (host_sampler.cpp).
+// Replaces all2all_sp + SparseMatrix::add_to_sampler + Sampler::saveRowSparse (console_all2all_sparse.cpp:70-89, array.h:450-540, sampler.h)
+// without the full sparse matrix ever leaving HBM.
+// ------------------------------------------------------------------------------------------
+namespace {
+struct Proxy { int kind, flip; };
+// the plain ratio a criterion is monotone in (ratio_bound's mapping) and whether the criterion falls with it
+Proxy proxy_of(int criterion) {
+    switch (criterion) {
+    case KMDB_METRIC_JACCARD: return {RATIO_JACCARD, 0};
+    case KMDB_METRIC_MIN: return {RATIO_MIN, 0};
+    case KMDB_METRIC_MAX: return {RATIO_MAX, 0};
+    case KMDB_METRIC_COSINE: return {RATIO_COSINE, 0};
+    case KMDB_METRIC_MASH: return {RATIO_JACCARD, 1};
+    case KMDB_METRIC_ANI: return {RATIO_JACCARD, 0};
+    case KMDB_METRIC_ANI_SHORTER: return {RATIO_MIN, 0};
+    case KMDB_METRIC_MASH_QUERY: return {RATIO_QUERY, 1};
+    default: return {RATIO_NUM, 0};
+    }
+}
+double host_proxy(Proxy p, uint32_t c, uint32_t a, uint32_t b) {
+    double x;
+    switch (p.kind) {
+    case RATIO_JACCARD: x = (double)c / (double)(uint32_t)(a + b - c); break;
+    case RATIO_MIN:     x = (double)c / (double)std::min(a, b); break;
+    case RATIO_MAX:     x = (double)c / (double)std::max(a, b); break;
+    case RATIO_COSINE:  x = (double)c / std::sqrt((double)(uint32_t)(a * b)); break;
+    case RATIO_QUERY:   x = (double)c / (double)a; break;
+    default:            x = (double)c; break;
+    }
+    return p.flip ? -x : x;
+}
+int check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count) {
+    if (count == 0) return kmdb_set_error(std::string(who) + ": count must be at least 1");
+    if (criterion < 0 || criterion >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + ": unknown criterion");
+    if (!sample_kmers) return kmdb_set_error(std::string(who) + ": sample_kmers is NULL");
+    return check_filters(who, filters, n_filters, sample_kmers, -1);
+}
+struct DevFree {
+    std::vector<void*> p;
+    ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
+};
+
+// The candidates of the symmetric rows of the cells [cell_lo, cell_hi) — complete: every row holds its `count` best cells by the exact decision
+// among the cells of the range (rows the margin band could not settle are fetched again whole).
+int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dense_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
+                 size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    std::memset(out, 0, sizeof *out);
+    HIP_TRY(hipSetDevice(db->device));
+    const uint64_t N = db->N;
+    const uint64_t cells = N ? N * (N - 1) / 2 : 0;
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
+    DevFree dev;
+    uint32_t *M = nullptr, *d_counts = nullptr;
+    if (!from_cells) { HIP_TRY(hipMalloc((void**)&M, std::max<uint64_t>(cells, 1) * 4)); dev.p.push_back(M); }
+    HIP_TRY(hipMalloc((void**)&d_counts, std::max<uint64_t>(N, 1) * 4));
+    dev.p.push_back(d_counts);
+    HIP_TRY(hipMemcpyAsync(d_counts, sample_kmers, N * 4, hipMemcpyHostToDevice, st));
+    const int k = (int)db->kmer_length;
+    const Proxy px = proxy_of(criterion);
+    kmdb_sample_job job;
+    job.N = N; job.counts_dev = d_counts; job.kind = px.kind; job.flip = px.flip; job.count = count; job.n_bounds = n_filters;
+    for (size_t i = 0; i < n_filters; ++i) {
+        const RatioBound rb = ratio_bound(filters[i], k);
+        job.bound_kind[i] = rb.kind; job.bound_lo[i] = rb.lo; job.bound_hi[i] = rb.hi;
+    }
+    if (!from_cells) {
+        if (run_dense(db, M, opts, st)) return 1;
+        job.cells = M; job.cell_lo = 0; job.cell_hi = cells;
+        // the block-record pipeline just told which tiles it added to: only those are read (KMDB_SP_ALL_TILES=1: every tile — A/B)
+        if (db->stats.path == KMDB_PATH_RECORDS && db->tile_touched && N > 1 && !getenv("KMDB_SP_ALL_TILES")) { job.touched = db->tile_touched; job.width = db->width; }
+    } else {
+        HIP_TRY(hipEventRecord(db->ev[0], st)); HIP_TRY(hipEventRecord(db->ev[1], st)); HIP_TRY(hipEventRecord(db->ev[2], st));
+        db->stats.path = KMDB_PATH_NONE;
+        job.cells = (const uint32_t*)dense_dev; job.cell_lo = cell_lo; job.cell_hi = cell_hi;
+    }
+    kmdb_sample_stats& ss = db->sample_stats;
+    ss = kmdb_sample_stats{};
+    try {
+        kmdb_sample_result res;
+        if (kmdb_sample_candidates(st, job, nullptr, 0, &res)) return 1;
+        ss.rows_truncated = res.rows_truncated; ss.d2h_bytes = res.d2h_bytes; ss.select_ms = res.select_ms; ss.triangle_reads = res.passes;
+        // Completeness.  A row that came out whole is decided.  A truncated row holds every cell whose key is >= the key of T_s, its count-th best
+        // proxy, less the margin: when `count` of its candidates at or above T_s pass the EXACT filters, no cell the device held back can be among
+        // the row's best.  T_s is recomputed here from the candidates (they include all cells at or above it).  A row of fewer than `count`
+        // candidates was not truncated; without filters every candidate passes.
+        std::vector<uint32_t> again;
+        if (n_filters) {
+            std::vector<uint32_t> keys;
+            for (uint64_t s = 0; s < N; ++s) {
+                const uint64_t b = res.row_ptr[s], e = res.row_ptr[s + 1];
+                if (e - b < count) continue;
+                keys.clear();
+                for (uint64_t x = b; x < e; ++x) {
+                    const uint32_t o = res.col[x];
+                    keys.push_back(kmdb_sample_proxy_key(host_proxy(px, res.val[x], sample_kmers[std::max<uint64_t>(s, o)], sample_kmers[std::min<uint64_t>(s, o)])));
+                }
+                std::vector<uint32_t> sorted(keys);
+                std::nth_element(sorted.begin(), sorted.begin() + (count - 1), sorted.end(), std::greater<uint32_t>());
+                const uint32_t T = sorted[count - 1];
+                uint64_t ok = 0;
+                for (uint64_t x = b; x < e && ok < count; ++x) {
+                    if (keys[x - b] < T) continue;
+                    const uint32_t o = res.col[x], a = sample_kmers[std::max<uint64_t>(s, o)], bb = sample_kmers[std::min<uint64_t>(s, o)];
+                    bool pass = true;
+                    for (size_t q = 0; q < n_filters && pass; ++q) {
+                        const double v = kmdbh_metric(filters[q].metric, res.val[x], a, bb, k);
+                        pass = v >= filters[q].lo && v <= filters[q].hi;
+                    }
+                    ok += pass ? 1 : 0;
+                }
+                if (ok < count) again.push_back((uint32_t)s);
+            }
+        }
+        kmdb_sample_result whole;
+        if (!again.empty()) {
+            if (kmdb_sample_candidates(st, job, again.data(), again.size(), &whole)) return 1;
+            ss.rows_refetched = again.size(); ss.d2h_bytes += whole.d2h_bytes; ss.select_ms += whole.select_ms; ss.triangle_reads += whole.passes;
+        }
+        if (finish_stats(db, st)) return 1;
+        kmdb_release_staging(db);
+        uint64_t nnz = 0;
+        {
+            size_t a = 0;
+            for (uint64_t s = 0; s < N; ++s) {
+                const bool re = a < again.size() && again[a] == s;
+                if (re) ++a;
+                const kmdb_sample_result& r = re ? whole : res;
+                nnz += r.row_ptr[s + 1] - r.row_ptr[s];
+            }
+        }
+        out->n_rows = N; out->nnz = nnz;
+        out->row_ptr = (uint64_t*)std::malloc((N + 1) * 8);
+        out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+        out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+        if (!out->row_ptr || !out->col || !out->val) { kmdb_sparse_free(out); return kmdb_set_error(std::string(who) + ": out of host memory for the result"); }
+        uint64_t w = 0;
+        size_t a = 0;
+        for (uint64_t s = 0; s < N; ++s) {
+            out->row_ptr[s] = w;
+            const bool re = a < again.size() && again[a] == s;
+            if (re) ++a;
+            const kmdb_sample_result& r = re ? whole : res;
+            const uint64_t b = r.row_ptr[s], n = r.row_ptr[s + 1] - b;
+            if (n) { std::memcpy(out->col + w, r.col.data() + b, n * 4); std::memcpy(out->val + w, r.val.data() + b, n * 4); }
+            w += n;
+        }
+        out->row_ptr[N] = w;
+        ss.candidates = nnz;
+        return 0;
+    } catch (const std::exception& e) {
+        kmdb_sparse_free(out);
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+}  // namespace
+
+extern "C" int kmdb_sampled_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
+                                              size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out_candidates,
+                                              const kmdb_opts* opts) {
+    const char* who = "kmdb_sampled_from_dense_device";
+    if (!db || !out_candidates) return kmdb_set_error(std::string(who) + ": null argument");
+    if (check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    const uint64_t cells = db->N ? db->N * (db->N - 1) / 2 : 0;
+    if (cell_hi > cells) cell_hi = cells;
+    if (cell_lo > cell_hi) return kmdb_set_error(std::string(who) + ": cell_lo > cell_hi");
+    if (!cells_dev && cell_hi > cell_lo) return kmdb_set_error(std::string(who) + ": null matrix");
+    return sampled_impl(who, db, true, cells_dev, cell_lo, cell_hi, filters, n_filters, sample_kmers, criterion, count, out_candidates, opts);
+}
+
+extern "C" int kmdb_all2all_sampled(kmdb_db* db, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count,
+                                    kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    const char* who = "kmdb_all2all_sampled";
+    if (!db || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    if (check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    // the rank of a cell is a condition on the whole cell: a slice of the pattern stream (opts->shard_*) holds partial sums only
+    if (opts && opts->shard_count > 1) return kmdb_set_error(std::string(who) + ": the selection needs the whole database (shard_count must be 1)");
+    kmdb_sparse_rows cand;
+    if (sampled_impl(who, db, false, nullptr, 0, ~0ull, filters, n_filters, sample_kmers, criterion, count, &cand, opts)) return 1;
+    const kmdb_sparse_rows* parts[1] = {&cand};
+    const int rc = kmdbh_sample_rows_select(criterion, count, (int)db->kmer_length, sample_kmers, filters, n_filters, parts, 1, out);
+    kmdb_sparse_free(&cand);
+    return rc;
+}
+
+extern "C" int kmdb_db_sample_stats(const kmdb_db* db, kmdb_sample_stats* out) {
+    if (!db || !out) return kmdb_set_error("kmdb_db_sample_stats: null argument");
+    *out = db->sample_stats;
     return 0;
 }
 

@@ -114,7 +114,7 @@ struct Rendezvous {
 
 struct kmdb_node {
     uint64_t N = 0, cells = 0, per = 0;
-    uint32_t n_shards = 0;
+    uint32_t n_shards = 0, kmer_length = 0;
     std::vector<DevSlot> dev;
     Rccl rccl;
     int rccl_version = 0;
@@ -269,7 +269,7 @@ extern "C" int kmdb_node_upload_partition(const kmdb_db_view* view, uint32_t n_s
     kmdb_node* nd = nullptr;
     try {                                                       // (nothing may leave through the C boundary: allocation and thread failures end in kmdb_set_error)
     nd = new kmdb_node();
-    nd->N = view->n_samples; nd->cells = nd->N ? nd->N * (nd->N - 1) / 2 : 0; nd->n_shards = n_shards;
+    nd->N = view->n_samples; nd->kmer_length = view->kmer_length; nd->cells = nd->N ? nd->N * (nd->N - 1) / 2 : 0; nd->n_shards = n_shards;
     nd->per = D > 1 ? (nd->cells + D - 1) / D : nd->cells;
     nd->dev.resize(D);
     for (uint32_t d = 0; d < D; ++d) nd->dev[d].device = devices[d];
@@ -465,6 +465,43 @@ extern "C" int kmdb_node_all2all_sparse(kmdb_node* nd, const kmdb_cell_filter* f
     for (auto& p : part) kmdb_sparse_free(&p);
     if (rc) { const std::string msg = kmdb_last_error(); kmdb_sparse_free(out); return kmdb_set_error(msg); }
     return 0;
+}
+
+extern "C" int kmdb_node_all2all_sampled(kmdb_node* nd, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion,
+                                         uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    const char* who = "kmdb_node_all2all_sampled";
+    if (!nd || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    // (argument errors before any device thread starts: a refusal must not leave a rank waiting at the rendezvous)
+    if (count == 0) return kmdb_set_error(std::string(who) + ": count must be at least 1");
+    if (criterion < 0 || criterion >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + ": unknown criterion");
+    if (!sample_kmers) return kmdb_set_error(std::string(who) + ": sample_kmers is NULL");
+    if (n_filters && !filters) return kmdb_set_error(std::string(who) + ": null argument");
+    if (nd->aborted) return kmdb_set_error(std::string(who) + ": an earlier collective failed and the node's communicators were aborted (upload again)");
+    std::memset(out, 0, sizeof *out);
+    const size_t D = nd->dev.size();
+    std::vector<kmdb_sparse_rows> part(D);
+    for (auto& p : part) std::memset(&p, 0, sizeof p);
+    int rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
+        if (node_accumulate(nd, d, dev_ok, opts)) return 1;
+        DevSlot& s = nd->dev[d];
+        if (s.shards.empty()) return kmdb_set_error(std::string(who) + ": a device without a shard");
+        const uint32_t* p; uint64_t lo, hi;
+        node_chunk(nd, d, p, lo, hi);
+        kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = s.device; o.shard_count = 1; o.stream = s.stream;
+        // the cells are complete sums here: every device selects on its own chunk, on the same stream behind the collective
+        if (kmdb_sampled_from_dense_device(s.shards[0], p, lo, hi, filters, n_filters, sample_kmers, criterion, count, &part[d], &o)) return 1;
+        NODE_TRY(hipEventRecord(s.ev[3], s.stream));
+        NODE_TRY(hipStreamSynchronize(s.stream));
+        return node_times(nd, d);
+    });
+    node_fill_stats(nd);
+    if (!rc) {
+        std::vector<const kmdb_sparse_rows*> ptrs;
+        for (auto& p : part) ptrs.push_back(&p);
+        rc = kmdbh_sample_rows_select(criterion, count, (int)nd->kmer_length, sample_kmers, filters, n_filters, ptrs.data(), ptrs.size(), out);
+    }
+    for (auto& p : part) kmdb_sparse_free(&p);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,0 +1,32 @@
+// sample_rows.h — the device selection of `-sample-rows` candidates (sample_rows.hip) as the entry points of engine.hip call it.  Not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+struct kmdb_sample_job {
+    const uint32_t* cells = nullptr;        // device: cell `cell_lo` of the lower triangle
+    uint64_t N = 0, cell_lo = 0, cell_hi = 0;
+    const unsigned char* touched = nullptr; // device, or nullptr: the tile flags of the block-record pipeline (kmdb_db.tile_touched) ...
+    uint32_t width = 64;                    // ... and the block width they were made for
+    const uint32_t* counts_dev = nullptr;   // device: [N] k-mer counts of the samples
+    size_t n_bounds = 0;                    // the widened bounds of the filters on their plain ratios (RATIO_* of cell_filter.h)
+    int bound_kind[12] = {};
+    double bound_lo[12] = {}, bound_hi[12] = {};
+    int kind = 0, flip = 0;                 // the criterion's proxy: RATIO_*; 1: negated (the measure falls with its ratio)
+    uint32_t count = 0;
+};
+struct kmdb_sample_result {
+    std::vector<uint64_t> row_ptr;          // [N + 1] symmetric rows, ascending columns
+    std::vector<uint32_t> col, val;
+    uint64_t rows_truncated = 0, d2h_bytes = 0;
+    double select_ms = 0;                   // HIP events around the passes
+    uint32_t passes = 0;                    // reads of the triangle
+};
+// The candidates of every sample's symmetric row.  only_rows != nullptr: the re-fetch — the listed rows whole, nothing of the others.
+// Runs on `st` behind whatever produced the cells and returns when the result is on the host.  0, or 1 with the error set.
+int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& job, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out);
+// the device's ranking key of a proxy value (order-preserving key of the proxy rounded to float; the largest key for NaN and infinities)
+uint32_t kmdb_sample_proxy_key(double proxy);

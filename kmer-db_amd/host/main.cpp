@@ -118,11 +118,19 @@ struct Filters {
 // byte-identical.  Without one the reference keeps a RANDOM subset (sampler.h:69-79: mt19937_64 with the default seed per sample, drawn in the
 // order in which its hash tables happen to list a row): here the same draws, over the pairs in ascending order of the other sample — the same
 // kind of subset, not the same bytes.
+// all2all-sp with a criterion never fills this sampler: the candidates are selected on the device and decided by the library
+// (kmdb_all2all_sampled / kmdb_node_all2all_sampled).  all2all-parts does — its cells come from kmdb_db2db_dense in host memory —, from several
+// workers at once: add() takes the lock of the sample's stripe, and with a criterion a row is pruned to its `cap` best whenever it reaches
+// 2 * cap items (the order is total, so what is left at the end is the same: never more than 2 * cap items per sample, as the reference's heap
+// never holds more than cap + 1).
 struct RowSampler {
     struct Item { uint32_t item, value; double score; };
     size_t cap = 0;
     bool best = false;
+    int criterion_id = -1;
     metric_fn criterion = nullptr;
+    static constexpr size_t STRIPES = 1024;
+    std::unique_ptr<std::mutex[]> stripes{new std::mutex[STRIPES]};
     std::vector<std::vector<Item>> rows;
     std::vector<size_t> seen;
     std::vector<std::mt19937_64> rng;
@@ -136,7 +144,7 @@ struct RowSampler {
             const std::string name = v.substr(0, sep);
             auto avail = metrics();
             if (!avail.count(name)) throw std::runtime_error("Sampling parameters error - unknown measure: " + name);
-            criterion = avail[name]; best = true;
+            criterion = avail[name]; best = true; criterion_id = kmdbh_metric_id(name.c_str());
             num = v.substr(sep + 1);
         }
         std::istringstream iss(num);
@@ -145,10 +153,11 @@ struct RowSampler {
     void init(size_t n) { rows.assign(n, {}); if (!best) { seen.assign(n, 0); rng.assign(n, std::mt19937_64()); } }
     static bool better(const Item& x, const Item& y) { return x.score != y.score ? x.score > y.score : x.item < y.item; }
     void add(size_t sample, uint32_t item, uint32_t value, double score) {
+        std::lock_guard<std::mutex> g(stripes[sample % STRIPES]);
         auto& r = rows[sample];
         r.push_back(Item{item, value, score});
         if (best) {
-            // (all candidates of a row are kept until the row is written: the `cap` best are chosen then)
+            if (r.size() >= 2 * cap) { std::nth_element(r.begin(), r.begin() + (std::ptrdiff_t)cap, r.end(), better); r.resize(cap); }
             return;
         }
         ++seen[sample];
@@ -408,10 +417,23 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
             fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
         std::vector<uint32_t> counts(n);
         for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
+        if (c.sampler.on() && c.sampler.best) {
+            // -sample-rows <criterion>:<count> (console_all2all_sparse.cpp:70-89): candidates on the device, the exact decision in the library —
+            // `sp` holds the sampled rows themselves, every bound applied
+            if (db.node) { check(kmdb_node_all2all_sampled(db.node, fl.data(), fl.size(), counts.data(), c.sampler.criterion_id, (uint32_t)std::min<size_t>(c.sampler.cap, 0xFFFFFFFFu), &sp, nullptr)); node_report(db); }
+            else {
+                check(kmdb_all2all_sampled(db.d, fl.data(), fl.size(), counts.data(), c.sampler.criterion_id, (uint32_t)std::min<size_t>(c.sampler.cap, 0xFFFFFFFFu), &sp, &o));
+                kmdb_sample_stats ss{};
+                if (!kmdb_db_sample_stats(db.d, &ss))
+                    std::cerr << "(" << ss.candidates << " candidates, " << ss.rows_truncated << " rows truncated, " << ss.rows_refetched << " fetched again, selection "
+                              << ss.select_ms << " ms, " << ss.d2h_bytes << " bytes to the host) ";
+            }
+        } else {
         if (fl.size() > 8) fl.clear();                          // (the host-side pass below applies every bound anyway)
         if (db.node) { check(kmdb_node_all2all_sparse(db.node, fl.data(), fl.size(), counts.data(), -1, &sp, nullptr)); node_report(db); }
         else if (fl.empty()) check(kmdb_all2all_sparse(db.d, &sp, &o));
         else check(kmdb_all2all_sparse_filtered(db.d, fl.data(), fl.size(), counts.data(), -1, &sp, &o));
+        }
     }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     db.uploaded();                                             // (after the call: the page drop and the call's first allocations get in each other's way)
@@ -421,8 +443,10 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     std::vector<char> row(10000 + n * 100);
     std::vector<uint32_t> cols, vals;
     size_t saved = 0;
-    if (c.sampler.on()) {
-        // -sample-rows (console_all2all_sparse.cpp:70-76, array.h:450-540): every pair that passes the filters is offered to both its samples
+    const bool sampled_rows = c.sampler.on() && c.sampler.best;      // `sp` holds the rows to write
+    if (c.sampler.on() && !sampled_rows) {
+        // -sample-rows <count>, the random strategy (console_all2all_sparse.cpp:70-76, array.h:450-540): every pair that passes the filters is
+        // offered to both its samples
         c.sampler.init(n);
         for (uint64_t i = 0; i < n; ++i)
             for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e) {
@@ -435,7 +459,8 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     }
     for (uint64_t i = 0; i < n; ++i) {
         cols.clear(); vals.clear();
-        if (c.sampler.on()) c.sampler.finish_row(i, cols, vals);
+        if (sampled_rows) { cols.assign(sp.col + sp.row_ptr[i], sp.col + sp.row_ptr[i + 1]); vals.assign(sp.val + sp.row_ptr[i], sp.val + sp.row_ptr[i + 1]); }
+        else if (c.sampler.on()) c.sampler.finish_row(i, cols, vals);
         else
         for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
             if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
@@ -583,8 +608,7 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
                 }
             if (c.sampler.on()) {
                 // -sample-rows (console_all2all_parts.cpp:137,191,237,275): the pairs go to the sampler (both samples of a pair), the rows are
-                // written when every cell is done — one lock for all workers: the pairs of one sample arrive from several block rows
-                std::lock_guard<std::mutex> g(mu);
+                // written when every cell is done — the pairs of one sample arrive from several block rows: add() locks the sample's stripe
                 for (size_t e = 0; e < cols.size(); ++e) {
                     const double sc = c.sampler.score(vals[e], cr, (uint32_t)counts[cols[e]], (int)k);
                     c.sampler.add(row_shift + r, cols[e], vals[e], sc);
