@@ -148,8 +148,10 @@ typedef struct kmdb_stats {        /* measurements of the LAST call on this db h
     uint64_t n_patterns;           /* patterns resident in HBM: all of the view's, or for kmdb_db_upload_shard only the nodes whose subtree
                                       holds a k-mer of the shard, or for kmdb_db_upload_range the nodes of the range and the ancestors of its first node */
     uint64_t h2d_bytes;            /* bytes kmdb_db_upload[_shard|_range] copied to the device (ABI 6) */
-    uint64_t n_direct;             /* block records that were never written: first-block records (X, X) the narrow kernel applied where it emitted them,
-                                      tile in registers, one write-back per slice of the pattern stream (ABI 7; n_records counts the written ones) */
+    uint64_t n_direct;             /* first-block records (X, X) with a weight below 128 that never went through the record pools, summed over the slices
+                                      of the pattern stream a call takes.  Default (KMDB_K1N_MODE=2): written compacted, 12 bytes each, by the narrow kernel
+                                      and read back by k2d_kernel, tile in registers, one write-back per change of block.  KMDB_K1N_MODE=1: applied where the
+                                      narrow kernel emitted them, never written.  KMDB_K1N_MODE=0: always 0 (ABI 7; n_records counts the pool's records) */
 } kmdb_stats;
 
 const char* kmdb_last_error(void);

@@ -3742,7 +3742,7 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
         // asked for more slices) leaves a partial sum behind: everything again from a zeroed matrix
         const uint32_t S = std::max<uint32_t>(1u, db->n_slices);
         bool again = false;
-        uint64_t records = 0;
+        uint64_t records = 0, direct = 0;
         // the launch sizes a call measures belong to one emit range: kept per slice, so that a sliced database reaches the warm path too
         if (db->slice_counts.size() != S) db->slice_counts.assign(S, kmdb_db::SliceCounts{});
         bool decoded = false;
@@ -3763,9 +3763,10 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
             else {
                 sc = kmdb_db::SliceCounts{true, lo, hi, db->last_n_wide, db->last_n_chunks, db->last_n_raw, db->last_n_rowjobs, db->last_n_sorted, db->last_n_k2jobs};
                 records += db->last_records;
+                direct += db->last_n_direct;
             }
         }
-        if (!again) { db->last_records = records; db->have_counts = true; return 0; }
+        if (!again) { db->last_records = records; db->last_n_direct = direct; db->have_counts = true; return 0; }
         HIP_TRY(hipMemsetAsync(M, 0, cells * 4, st));
     }
     return kmdb_set_error("kmdb_blocks_run: the record pools did not converge");
