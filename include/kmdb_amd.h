@@ -28,6 +28,8 @@ extern "C" {
  * also accepts a kmdb_db_view whose abi_version is 7 — a caller compiled against the previous header runs unchanged.  The sampled-rows entry points
  * (KMDB_HAS_SAMPLED_ROWS) are additive in the same way: the version number stays 8 and a caller built against an earlier ABI 8 header is served. */
 #define KMDB_HAS_SAMPLED_ROWS 1
+/* So is the sparse, filtered form of db2db (kmdb_db2db_sparse_filtered, kmdb_db2db_stats_get): two more entry points, the version stays 8. */
+#define KMDB_HAS_DB2DB_SPARSE 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -334,6 +336,32 @@ int  kmdb_new2all_batch_seq_alphabet_device(kmdb_db* db, const char* const* seqs
  * bytes per pattern, at most 8 GB; counted in kmdb_stats.device_bytes, freed by kmdb_db_free): the other cells of the grid that
  * use the part read them instead of rebuilding them. */
 int  kmdb_db2db_dense(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts);
+/* Replaces db2db_sp FOLLOWED BY SparseMatrix::compact2 with the -min / -max CombinedFilter, which is how the reference keeps a cell of the
+ * all2all-parts grid (console_all2all_parts.cpp:179-195 and 225-241: db2db_sp at :180 / :226, compact2(filter) right after it; array.h:391-446,
+ * sparse_filters.h:38-61).  The cell is accumulated in HBM as for kmdb_db2db_dense and compacted there: only the 64 x 64 tiles that received a
+ * contribution are read, the bounds — widened by a safety margin, as in kmdb_all2all_sparse_filtered — are applied before anything leaves the
+ * device, and the remaining cells are decided on the host with kmdbh_metric.  Neither the nr x nc rectangle nor its zeros cross PCIe.
+ * out: n_rows = n_samples(db_row); row r lists (col, val) with val > 0, 0 <= col < n_samples(db_col), ascending col — the content of the
+ * reference's SparseMatrix after db2db_sp + compact2(filter).
+ * In every measure a = row_sample_kmers[r], the ROW sample's k-mer count, and b = col_sample_kmers[col], the COLUMN sample's — the order of
+ * CombinedFilter(..., db_row->getSampleKmersCount(), db_col->getSampleKmersCount(), ...); mash-query tells the two apart.
+ * measure >= 0 fills out->measure per kept cell (kmdbh_metric), -1 leaves it NULL.  n_filters == 0 with measure < 0 keeps every non-zero cell and
+ * allows NULL count arrays; filters or a measure need both.  db_row == db_col is allowed: the full square, diagonal included, as the dense call.
+ * Refused before any device work: NULL handles / out, filters or a measure without both count arrays, an unknown metric or measure, more than
+ * 12 bounds; and everything kmdb_db2db_dense refuses (no hashtables, a query shard, different k-mer lengths or devices, its size limits).
+ * KMDB_SP_ALL_TILES=1 reads every tile (A/B), as for all2all-sp. */
+int  kmdb_db2db_sparse_filtered(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters,
+                                const uint32_t* row_sample_kmers /* [nr] */, const uint32_t* col_sample_kmers /* [nc] */,
+                                int measure /* KMDB_METRIC_* or -1 */, kmdb_sparse_rows* out, const kmdb_opts* opts);
+typedef struct kmdb_db2db_stats {  /* the LAST kmdb_db2db_* call with this handle as the ROW database */
+    uint64_t tiles;                /* ceil(nr / 64) * ceil(nc / 64) */
+    uint64_t tiles_touched;        /* tiles that received a block record = tiles the compaction read (0 after a dense call) */
+    uint64_t nnz_device;           /* cells that passed the widened bounds and left HBM */
+    uint64_t nnz;                  /* cells returned after the exact decision on the host */
+    uint64_t d2h_bytes;            /* result bytes copied to the host: row pointers + 8 per device-kept cell (dense call: 4 nr nc) */
+    double   compact_ms;           /* HIP events around flags + count + scan + compact (kmdb_stats.kernel_ms holds the whole call) */
+} kmdb_db2db_stats;
+int  kmdb_db2db_stats_get(const kmdb_db* db_row, kmdb_db2db_stats* out);
 
 /* ---------------------------------------------------------------------------------------
  * One database over the GPUs of a node (north_star: prefix buckets sharded across the GPUs, one RCCL reduce of the

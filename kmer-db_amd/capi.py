@@ -74,6 +74,11 @@ class _SampleStats(C.Structure):
                 ("select_ms", C.c_double), ("triangle_reads", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _Db2dbStats(C.Structure):
+    _fields_ = [("tiles", C.c_uint64), ("tiles_touched", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64),
+                ("compact_ms", C.c_double)]
+
+
 FLAG_FORCE_GLOBAL_ATOMICS = 1
 FLAG_FORCE_DIRECT = 2
 FLAG_FORCE_TILE = 4
@@ -94,6 +99,7 @@ EXPORTS = [
     "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique",
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
     "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
+    "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
 ]
 
 
@@ -160,6 +166,9 @@ def lib():
     L.kmdb_new2all_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_new2all_batch_sparse.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_db2db_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_db2db_sparse_filtered.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Sparse),
+                                             C.POINTER(_Opts)]
+    L.kmdb_db2db_stats_get.argtypes = [C.c_void_p, C.POINTER(_Db2dbStats)]
     L.kmdb_new2all_batch_seq.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int,
                                          C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_new2all_batch_seq_alphabet.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
@@ -553,6 +562,28 @@ class DeviceDB:
         o = _opts(self.device)
         _check(lib().kmdb_db2db_dense(self._d, col._d, buf.ctypes.data, C.byref(o)))
         return out
+
+    def db2db_sparse(self, col, filters=(), row_kmers=None, col_kmers=None, measure=None):
+        """kmdb_db2db_sparse_filtered: the cell (this database's samples = rows, `col`'s = columns) as sparse rows, compacted and filtered on the
+        device — db2db_sp + compact2(filter).  filters: [(criterion name, lo, hi)], None = unbounded; row_kmers / col_kmers: the k-mer counts of
+        the row and the column samples (a and b of every measure, in that order); measure: a criterion name whose value is returned per kept cell."""
+        raw = _Sparse()
+        o = _opts(self.device)
+        rk = None if row_kmers is None else np.ascontiguousarray(row_kmers, np.uint32)
+        ck = None if col_kmers is None else np.ascontiguousarray(col_kmers, np.uint32)
+        _check(lib().kmdb_db2db_sparse_filtered(self._d, col._d, _filters(filters), len(filters), None if rk is None else rk.ctypes.data,
+                                                None if ck is None else ck.ctypes.data, -1 if measure is None else _criterion(measure),
+                                                C.byref(raw), C.byref(o)))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
+    def db2db_stats(self):
+        """kmdb_db2db_stats_get: the last db2db call with this handle as the row database"""
+        s = _Db2dbStats()
+        _check(lib().kmdb_db2db_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _Db2dbStats._fields_}
 
     def new2all_seq(self, seqs, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
         """queries given as sequence text (bytes / str); k-mer extraction, minhash filter, sort + unique on the device.

@@ -1,5 +1,5 @@
-// cell_filter.h — the device side of the -min / -max filters, shared by the compaction kernels of engine.hip and the row selection of
-// sample_rows.hip.  Internal to each translation unit (anonymous namespace).
+// cell_filter.h — the device side of the -min / -max filters, shared by the compaction kernels of engine.hip and db2db.hip and the row
+// selection of sample_rows.hip.  Internal to each translation unit (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -16,10 +16,9 @@ struct DevFilter {
     double lo[DEV_FILTER_MAX], hi[DEV_FILTER_MAX];
     const uint32_t* counts;         // [N] k-mer counts of the samples
 };
-__device__ __forceinline__ bool dev_keep(const DevFilter& f, uint32_t c, uint32_t row, uint32_t col) {
-    if (c == 0) return false;
-    if (f.n == 0) return true;
-    const uint32_t a = f.counts[row], b = f.counts[col];
+// the bounds on a non-zero cell whose k-mer counts the caller holds: a of the ROW sample, b of the COLUMN sample (the two may come from
+// different arrays: db2db.hip's cell of two databases)
+__device__ __forceinline__ bool dev_keep_ab(const DevFilter& f, uint32_t c, uint32_t a, uint32_t b) {
     for (int i = 0; i < f.n; ++i) {
         double x;
         switch (f.kind[i]) {
@@ -33,6 +32,11 @@ __device__ __forceinline__ bool dev_keep(const DevFilter& f, uint32_t c, uint32_
         if (!(x >= f.lo[i] && x <= f.hi[i])) return false;      // NaN fails, as on the host
     }
     return true;
+}
+__device__ __forceinline__ bool dev_keep(const DevFilter& f, uint32_t c, uint32_t row, uint32_t col) {
+    if (c == 0) return false;
+    if (f.n == 0) return true;
+    return dev_keep_ab(f, c, f.counts[row], f.counts[col]);
 }
 // the plain ratio of kind `kind` of a cell (the same expressions as above): what a bound is brought to, and the proxy a row selection ranks by
 __device__ __forceinline__ double dev_ratio(int kind, uint32_t c, uint32_t a, uint32_t b) {

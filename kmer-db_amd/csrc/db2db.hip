@@ -17,6 +17,11 @@
 //            mask, column mask, count) per pair of non-empty blocks into a pool, in arrival order
 //   apply    kmdb_rect_sort_apply (a2a_blocks.hip): the all2all pipeline's counting sort by block pair and its matrix-core
 //            accumulation kernel, writing the dense rows x columns matrix.
+// kmdb_db2db_dense copies that matrix to the host.  kmdb_db2db_sparse_filtered (db2db_sp + SparseMatrix::compact2 with the -min / -max
+// CombinedFilter, src/console_all2all_parts.cpp:179-195, 225-241; src/array.h:391-446) compacts it where it is:
+//   flags    one byte per 64 x 64 tile of the cell, set from the key words of the emit pool: the tiles that received a block record
+//   compact  one wave per row over the flagged tiles of its row block: widened bounds (cell_filter.h), per-row counts, exclusive sum,
+//            (col, val) in ascending columns; the exact decision is the host's (kmdb_sparse_decide, engine.hip)
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
 #include "engine_internal.h"
@@ -24,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include "prim.h"
 #include "hash_probe.h"
+#include "cell_filter.h"
 
 #include <algorithm>
 #include <cstring>
@@ -31,6 +37,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 namespace {
 
@@ -266,6 +273,53 @@ __global__ __launch_bounds__(256) void d2_emit_kernel(D2Db row, D2Db col, const 
     if (COUNT && lane == 0 && mine) atomicAdd(&n_records[(wid % 64u) * 8u], mine);
 }
 
+// ---- the sparse form of the cell
+// The tiles that received a block record: the stream of a key word is row block * nbc + column block (d2_emit_kernel); a slot never written is
+// all ones, and 2^key_bits > n_tiles + 1, so its stream lies beyond the tiles.  (Every writer stores 1: plain byte stores.)
+__global__ __launch_bounds__(256) void d2_tile_flags_kernel(const uint32_t* __restrict__ wkey, uint32_t nslots, uint32_t kmask, uint32_t n_tiles,
+                                                            unsigned char* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nslots) return;
+    const uint32_t s = wkey[i] & kmask;
+    if (s < n_tiles) flags[s] = 1;
+}
+
+// Dense cell -> CSR over the FLAGGED tiles only, the rectangle's counterpart of row_tiles_kernel (engine.hip).  One wave per row of the cell: it
+// takes the nbc flags of its row block 64 per round by ballot and reads, for every flagged tile, the row's 64 cells (a lane each).  A lane whose
+// column is >= nc loads nothing — in a row-major rectangle that address is a cell of the NEXT row — and the cell offset row * nc + column is
+// 64-bit (66 000 x 66 000 cells exceed 2^32).  COMPACT false: row_nnz[row] = kept cells; true: (col, val) from row_ptr[row] on, ascending columns.
+template <bool COMPACT>
+__global__ __launch_bounds__(64) void d2_row_tiles_kernel(const uint32_t* __restrict__ M, uint32_t nr, uint32_t nc, uint32_t nbc,
+                                                          const unsigned char* __restrict__ flags, unsigned long long* __restrict__ row_nnz,
+                                                          const unsigned long long* __restrict__ row_ptr, uint32_t* __restrict__ col,
+                                                          uint32_t* __restrict__ val, const DevFilter f, const uint32_t* __restrict__ col_counts) {
+    const uint32_t row = blockIdx.x;
+    if (row >= nr) return;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t* r = M + (uint64_t)row * nc;
+    const unsigned char* fl = flags + (size_t)(row >> 6) * nbc;
+    const uint32_t a = f.n ? f.counts[row] : 0u;               // the ROW sample's k-mer count
+    unsigned long long out = COMPACT ? row_ptr[row] : 0ull;
+    uint32_t count = 0;
+    for (uint32_t Y0 = 0; Y0 < nbc; Y0 += 64u) {
+        const uint32_t Yl = Y0 + lane;
+        unsigned long long m = __ballot(Yl < nbc && fl[Yl] != 0);
+        while (m) {
+            const uint32_t Y = Y0 + (uint32_t)__builtin_ctzll(m);
+            m &= m - 1;
+            const uint32_t j = Y * 64u + lane;
+            uint32_t v = j < nc ? r[j] : 0u;
+            if (v && f.n && !dev_keep_ab(f, v, a, col_counts[j])) v = 0u;
+            const unsigned long long bal = __ballot(v != 0);
+            if (COMPACT) {
+                if (v) { const unsigned long long o = out + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)); col[o] = j; val[o] = v; }
+                out += (uint32_t)__popcll(bal);
+            } else count += (uint32_t)__popcll(bal);
+        }
+    }
+    if (!COMPACT && lane == 0) row_nnz[row] = count;
+}
+
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -325,11 +379,19 @@ const unsigned long long* d2_list_store(const kmdb_engine_view& e, hipStream_t s
             return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
     } while (0)
 
-static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts, bool allow_store);
+// what the sparse entry asks of the call (nullptr: the dense entry)
+struct D2Sparse {
+    const kmdb_cell_filter* filters;
+    size_t n_filters;
+    const uint32_t *row_kmers, *col_kmers;
+    int measure;
+    kmdb_sparse_rows* out;
+};
+static int db2db_impl(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts, bool allow_store);
 
-extern "C" int kmdb_db2db_dense(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts) {
-    if (!db_row || !db_col || !out) return kmdb_set_error("kmdb_db2db_dense: null argument");
-    int rc = db2db_impl(db_row, db_col, out, opts, true);
+// the call, and once more without the handles' list stores when it ran out of HBM
+static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts) {
+    int rc = db2db_impl(who, db_row, db_col, out, sp, opts, true);
     if (rc && std::strstr(kmdb_last_error(), hipGetErrorString(hipErrorOutOfMemory))) {
         // out of HBM inside the call: the handles' list stores (up to 8 GB each) are the part that can go — the pairs' lists are then built
         // by climbing, as on handles that never had a store — and the call is tried once more
@@ -347,21 +409,41 @@ extern "C" int kmdb_db2db_dense(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out,
         (void)hipGetLastError();
         if (freed) {
             if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] db2db: out of device memory; list stores dropped, the call is repeated on the climbing path\n");
-            rc = db2db_impl(db_row, db_col, out, opts, false);
+            rc = db2db_impl(who, db_row, db_col, out, sp, opts, false);
         }
     }
     return rc;
 }
 
-static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts, bool allow_store) {
+extern "C" int kmdb_db2db_dense(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts) {
+    if (!db_row || !db_col || !out) return kmdb_set_error("kmdb_db2db_dense: null argument");
+    return db2db_call("kmdb_db2db_dense", db_row, db_col, out, nullptr, opts);
+}
+
+extern "C" int kmdb_db2db_sparse_filtered(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters,
+                                          const uint32_t* row_sample_kmers, const uint32_t* col_sample_kmers, int measure, kmdb_sparse_rows* out,
+                                          const kmdb_opts* opts) {
+    const char* who = "kmdb_db2db_sparse_filtered";
+    if (!db_row || !db_col || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    // (bounds and measures need the k-mer counts of both sides: a = the row sample's, b = the column sample's)
+    if (kmdb_check_filters(who, filters, n_filters, row_sample_kmers && col_sample_kmers ? row_sample_kmers : nullptr, measure)) return 1;
+    std::memset(out, 0, sizeof *out);
+    const D2Sparse sp{filters, n_filters, row_sample_kmers, col_sample_kmers, measure, out};
+    const int rc = db2db_call(who, db_row, db_col, nullptr, &sp, opts);
+    if (rc) kmdb_sparse_free(out);
+    return rc;
+}
+
+static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts, bool allow_store) {
+    const std::string who(who_);
     kmdb_engine_view er, ec;
     if (kmdb_engine_get(db_row, &er)) return 1;
     if (kmdb_engine_get(db_col, &ec)) return 1;
     if (!er.n_buckets || !er.slots || !ec.n_buckets || !ec.slots)
-        return kmdb_set_error("kmdb_db2db_dense: both databases must be uploaded with hashtables");
-    if (er.qs_count > 1 || ec.qs_count > 1) return kmdb_set_error("kmdb_db2db_dense: a query shard holds only its own buckets (upload the parts with kmdb_db_upload)");
-    if (er.kmer_length != ec.kmer_length) return kmdb_set_error("kmdb_db2db_dense: the databases have different k-mer lengths");
-    if (er.device != ec.device) return kmdb_set_error("kmdb_db2db_dense: the databases live on different devices");
+        return kmdb_set_error(who + ": both databases must be uploaded with hashtables");
+    if (er.qs_count > 1 || ec.qs_count > 1) return kmdb_set_error(who + ": a query shard holds only its own buckets (upload the parts with kmdb_db_upload)");
+    if (er.kmer_length != ec.kmer_length) return kmdb_set_error(who + ": the databases have different k-mer lengths");
+    if (er.device != ec.device) return kmdb_set_error(who + ": the databases live on different devices");
     // (sample ids take 20 bits here as everywhere: round 4's limit of 65 535 samples per part — a 16-bit block index array of fixed size in the
     // pair kernel — is gone; what bounds a part now is the pair kernel's LDS and the 2^22 block pairs of the stream keys, checked below)
     D2_TRY(hipSetDevice(er.device));
@@ -369,13 +451,23 @@ static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmd
     const uint64_t nr = er.N, nc = ec.N;
     uint64_t n_slots = 0;
     D2_TRY(hipMemcpy(&n_slots, ec.bucket_offset + ec.n_buckets, 8, hipMemcpyDeviceToHost));
-    if (n_slots >= (1ull << 31)) return kmdb_set_error("kmdb_db2db_dense: column database has more than 2^31 hashtable slots");
+    if (n_slots >= (1ull << 31)) return kmdb_set_error(who + ": column database has more than 2^31 hashtable slots");
     DevBuf d_keys, d_keys2, d_uniq, d_cnt, d_nruns, d_out, d_tmp, d_flag;
     D2_TRY(d_keys.alloc(n_slots * 8)); D2_TRY(d_keys2.alloc(n_slots * 8)); D2_TRY(d_uniq.alloc((n_slots + 1) * 8));
     D2_TRY(d_cnt.alloc((n_slots + 1) * 4)); D2_TRY(d_nruns.alloc(16)); D2_TRY(d_out.alloc(nr * nc * 4)); D2_TRY(d_flag.alloc(16));
     D2_TRY(hipMemsetAsync(d_out.p, 0, std::max<uint64_t>(nr * nc * 4, 4), st));
     D2_TRY(hipMemsetAsync(d_flag.p, 0, 16, st));
-    hipEvent_t ev0 = (hipEvent_t)er.ev[0], ev3 = (hipEvent_t)er.ev[3];
+    // the cell in tiles of 64 x 64; sparse entry: one flag byte per tile (KMDB_SP_ALL_TILES=1: every tile counts as touched, as for all2all-sp — A/B)
+    const uint32_t nbr = (uint32_t)((nr + 63) / 64), nbc = (uint32_t)((nc + 63) / 64);
+    const uint64_t n_tiles = (uint64_t)nbr * nbc;
+    const bool all_tiles = sp && getenv("KMDB_SP_ALL_TILES");
+    bool any_records = false, flags_timed = false;
+    DevBuf d_tiles;
+    if (sp) {
+        D2_TRY(d_tiles.alloc(n_tiles));
+        D2_TRY(hipMemsetAsync(d_tiles.p, all_tiles ? 1 : 0, std::max<uint64_t>(n_tiles, 1), st));
+    }
+    hipEvent_t ev0 = (hipEvent_t)er.ev[0], ev1 = (hipEvent_t)er.ev[1], ev2 = (hipEvent_t)er.ev[2], ev3 = (hipEvent_t)er.ev[3];
     D2_TRY(hipEventRecord(ev0, st));
     const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
     auto t_mark = std::chrono::steady_clock::now();
@@ -413,13 +505,12 @@ static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmd
         phase("probe + sort + run lengths");
         if (nruns) {
             // pairs -> block records -> sorted by block pair -> accumulated on the matrix cores (a2a_blocks.hip)
-            const uint32_t nbr = (uint32_t)((nr + 63) / 64), nbc = (uint32_t)((nc + 63) / 64);
             int key_bits = 1;
             while ((1ull << key_bits) <= (uint64_t)nbr * nbc + 1) ++key_bits;
             const uint32_t dbits = (uint32_t)(32 - key_bits - 2);
-            if ((uint64_t)nbr * nbc + 1 >= (1ull << 22)) return kmdb_set_error("kmdb_db2db_dense: more than 2^22 block pairs (parts of " + std::to_string(nr) + " x " + std::to_string(nc) + " samples)");
+            if ((uint64_t)nbr * nbc + 1 >= (1ull << 22)) return kmdb_set_error(who + ": more than 2^22 block pairs (parts of " + std::to_string(nr) + " x " + std::to_string(nc) + " samples)");
             const size_t wave_lds = d2_wave_words(nbr, nbc) * 8;
-            if (wave_lds > (size_t)(150u << 10)) return kmdb_set_error("kmdb_db2db_dense: the sample lists of a pattern pair do not fit the LDS (parts of " + std::to_string(nr) + " + " + std::to_string(nc) + " samples; about 540 000 in all is the limit)");
+            if (wave_lds > (size_t)(150u << 10)) return kmdb_set_error(who + ": the sample lists of a pattern pair do not fit the LDS (parts of " + std::to_string(nr) + " + " + std::to_string(nc) + " samples; about 540 000 in all is the limit)");
             const uint32_t wpb = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (size_t)(150u << 10) / wave_lds));
             const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)nruns + wpb - 1) / wpb, 256 * 8);
             const size_t lds = wave_lds * wpb;
@@ -465,7 +556,7 @@ static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmd
                 const uint64_t grabs = (total + total / 8) / D2_GRAB / D2_CURSORS + (uint64_t)grid * wpb / D2_CURSORS + 130;
                 const uint64_t region = grabs * D2_GRAB;
                 slots = region * D2_CURSORS;
-                if (slots >= (1ull << 31)) return kmdb_set_error("kmdb_db2db_dense: more than 2^31 block records");
+                if (slots >= (1ull << 31)) return kmdb_set_error(who + ": more than 2^31 block records");
                 if (d_wkey.p) { (void)hipFree(d_wkey.p); d_wkey.p = nullptr; (void)hipFree(d_wrec.p); d_wrec.p = nullptr; }
                 D2_TRY(d_wkey.alloc(slots * 4)); D2_TRY(d_wrec.alloc(slots * 16));
                 D2_TRY(hipMemsetAsync(d_wkey.p, 0xFF, slots * 4, st));
@@ -484,21 +575,112 @@ static int db2db_impl(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmd
                 D2_TRY(hipStreamSynchronize(st));
                 if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] db2db: %u pattern pairs, pool for %llu records (%s)%s\n", nruns, total, attempt ? "counted" : "estimate", ovf ? ": too small" : "");
                 if (!ovf) break;
-                if (attempt) return kmdb_set_error("kmdb_db2db_dense: internal error (record pool overflow)");
+                if (attempt) return kmdb_set_error(who + ": internal error (record pool overflow)");
             }
             phase("pool + emit");
+            any_records = true;
+            if (sp && !all_tiles) {
+                // the tiles this call adds to, from the pool's key words (before the sort takes the pool)
+                D2_TRY(hipEventRecord(ev1, st));
+                hipLaunchKernelGGL(d2_tile_flags_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_wkey.as<uint32_t>(), (uint32_t)slots,
+                                   (1u << key_bits) - 1u, (uint32_t)n_tiles, d_tiles.as<unsigned char>());
+                D2_TRY(hipGetLastError());
+                D2_TRY(hipEventRecord(ev2, st));
+                flags_timed = true;
+            }
             if (kmdb_rect_sort_apply(st, d_wkey.as<uint32_t>(), d_wrec.p, (uint32_t)slots, nbr, nbc, key_bits, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc)) return 1;
             phase("sort + apply");
         }
     }
+    kmdb_db2db_stats& ds = *er.d2_stats;
+    ds = kmdb_db2db_stats{};
+    ds.tiles = n_tiles;
+    if (!sp) {
+        D2_TRY(hipEventRecord(ev3, st));
+        D2_TRY(hipEventSynchronize(ev3));
+        float ms = 0;
+        D2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+        kmdb_engine_set_times(db_row, ms, ms);
+        uint32_t too_long = 0;
+        D2_TRY(hipMemcpy(&too_long, d_flag.p, 4, hipMemcpyDeviceToHost));
+        if (too_long) return kmdb_set_error(who + ": internal error");
+        if (nr * nc) D2_TRY(hipMemcpy(out, d_out.p, nr * nc * 4, hipMemcpyDeviceToHost));
+        ds.d2h_bytes = nr * nc * 4;
+        return 0;
+    }
+    // ---- the sparse entry: the cell stays in d_out and is compacted there (count per row, exclusive sum, (col, val) in ascending columns)
+    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } c0, c1;
+    D2_TRY(hipEventCreate(&c0.e)); D2_TRY(hipEventCreate(&c1.e));
+    DevBuf d_nnz, d_ptr, d_col, d_val, d_rk, d_ck, d_scan;
+    DevFilter df{};
+    if (sp->n_filters) {
+        D2_TRY(d_rk.alloc(nr * 4)); D2_TRY(d_ck.alloc(nc * 4));
+        if (nr) D2_TRY(hipMemcpyAsync(d_rk.p, sp->row_kmers, nr * 4, hipMemcpyHostToDevice, st));
+        if (nc) D2_TRY(hipMemcpyAsync(d_ck.p, sp->col_kmers, nc * 4, hipMemcpyHostToDevice, st));
+        df.n = (int)sp->n_filters; df.counts = d_rk.as<uint32_t>();
+        kmdb_dev_bounds(sp->filters, sp->n_filters, (int)er.kmer_length, df.kind, df.lo, df.hi);
+    }
+    D2_TRY(d_nnz.alloc((nr + 1) * 8)); D2_TRY(d_ptr.alloc((nr + 1) * 8));
+    // (a cell without a single block record has no tile to read: its counts stay zero)
+    const bool scan = nr && nc && (any_records || all_tiles);
+    D2_TRY(hipEventRecord(c0.e, st));
+    D2_TRY(hipMemsetAsync(d_nnz.p, 0, (nr + 1) * 8, st));
+    if (scan) {
+        hipLaunchKernelGGL((d2_row_tiles_kernel<false>), dim3((unsigned)nr), dim3(64), 0, st, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc, nbc,
+                           d_tiles.as<unsigned char>(), d_nnz.as<unsigned long long>(), (const unsigned long long*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, df, d_ck.as<uint32_t>());
+        D2_TRY(hipGetLastError());
+    }
+    size_t scan_bytes = 0;
+    D2_TRY(prim::exclusive_sum(nullptr, scan_bytes, d_nnz.as<unsigned long long>(), d_ptr.as<unsigned long long>(), (size_t)(nr + 1), st));
+    D2_TRY(d_scan.alloc(scan_bytes));
+    D2_TRY(prim::exclusive_sum(d_scan.p, scan_bytes, d_nnz.as<unsigned long long>(), d_ptr.as<unsigned long long>(), (size_t)(nr + 1), st));
+    std::vector<unsigned long long> h_ptr(nr + 1, 0);
+    std::vector<unsigned char> h_tiles(n_tiles, 0);
+    D2_TRY(hipMemcpyAsync(h_ptr.data(), d_ptr.p, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (n_tiles) D2_TRY(hipMemcpyAsync(h_tiles.data(), d_tiles.p, n_tiles, hipMemcpyDeviceToHost, st));
+    D2_TRY(hipStreamSynchronize(st));
+    const uint64_t nnz_dev = h_ptr[nr];
+    D2_TRY(d_col.alloc(nnz_dev * 4)); D2_TRY(d_val.alloc(nnz_dev * 4));
+    if (scan && nnz_dev) {
+        hipLaunchKernelGGL((d2_row_tiles_kernel<true>), dim3((unsigned)nr), dim3(64), 0, st, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc, nbc,
+                           d_tiles.as<unsigned char>(), (unsigned long long*)nullptr, d_ptr.as<unsigned long long>(), d_col.as<uint32_t>(),
+                           d_val.as<uint32_t>(), df, d_ck.as<uint32_t>());
+        D2_TRY(hipGetLastError());
+    }
+    D2_TRY(hipEventRecord(c1.e, st));
     D2_TRY(hipEventRecord(ev3, st));
     D2_TRY(hipEventSynchronize(ev3));
-    float ms = 0;
+    float ms = 0, ms_flags = 0, ms_compact = 0;
     D2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+    D2_TRY(hipEventElapsedTime(&ms_compact, c0.e, c1.e));
+    if (flags_timed) D2_TRY(hipEventElapsedTime(&ms_flags, ev1, ev2));
     kmdb_engine_set_times(db_row, ms, ms);
     uint32_t too_long = 0;
     D2_TRY(hipMemcpy(&too_long, d_flag.p, 4, hipMemcpyDeviceToHost));
-    if (too_long) return kmdb_set_error("kmdb_db2db_dense: internal error");
-    if (nr * nc) D2_TRY(hipMemcpy(out, d_out.p, nr * nc * 4, hipMemcpyDeviceToHost));
+    if (too_long) return kmdb_set_error(who + ": internal error");
+    kmdb_sparse_rows* o = sp->out;
+    o->n_rows = nr;
+    o->nnz = nnz_dev;
+    o->row_ptr = (uint64_t*)std::malloc((nr + 1) * 8);
+    o->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz_dev, 1) * 4);
+    o->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz_dev, 1) * 4);
+    if (!o->row_ptr || !o->col || !o->val) return kmdb_set_error(who + ": out of host memory for the result");
+    for (uint64_t i = 0; i <= nr; ++i) o->row_ptr[i] = h_ptr[i];
+    if (nnz_dev) {
+        D2_TRY(hipMemcpy(o->col, d_col.p, nnz_dev * 4, hipMemcpyDeviceToHost));
+        D2_TRY(hipMemcpy(o->val, d_val.p, nnz_dev * 4, hipMemcpyDeviceToHost));
+    }
+    for (unsigned char t : h_tiles) ds.tiles_touched += t != 0;
+    ds.nnz_device = nnz_dev;
+    ds.d2h_bytes = (nr + 1) * 8 + nnz_dev * 8;
+    ds.compact_ms = (double)ms_flags + (double)ms_compact;
+    // the exact decision: every cell the widened bounds let through, by the reference's arithmetic (a = row sample, b = column sample)
+    if ((sp->n_filters || sp->measure >= 0) &&
+        kmdb_sparse_decide(who_, o, sp->filters, sp->n_filters, sp->row_kmers, sp->col_kmers, sp->measure, (int)er.kmer_length)) return 1;
+    ds.nnz = o->nnz;
+    if (verbose)
+        fprintf(stderr, "[kmdb] db2db: sparse cell: %llu of %llu tiles touched, %llu cells left the device, %llu kept, compaction %.3f ms\n",
+                (unsigned long long)ds.tiles_touched, (unsigned long long)ds.tiles, (unsigned long long)ds.nnz_device, (unsigned long long)ds.nnz, ds.compact_ms);
     return 0;
 }

@@ -324,7 +324,7 @@ int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* o) {
     o->pid2dfs = db->pid2dfs; o->qs_index = db->qs_index; o->qs_count = db->qs_count; o->stream = db->stream;
     o->max_depth = db->max_depth; o->list_sets = &db->list_sets; o->list_sets_nb = &db->list_sets_nb; o->list_sets_tried = &db->list_sets_tried;
     o->rl_ofs = &db->rl_ofs; o->rl_runs = &db->rl_runs; o->rl_node = &db->rl_node; o->rl_tried = &db->rl_tried;
-    o->device_bytes = &db->stats.device_bytes;
+    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats;
     for (int i = 0; i < 4; ++i) o->ev[i] = db->ev[i];
     return 0;
 }
@@ -514,10 +514,17 @@ RatioBound ratio_bound(const kmdb_cell_filter& f, int k) {
 }
 }  // namespace
 
+void kmdb_dev_bounds(const kmdb_cell_filter* filters, size_t n_filters, int kmer_length, int* kind, double* lo, double* hi) {
+    for (size_t i = 0; i < n_filters; ++i) {
+        const RatioBound rb = ratio_bound(filters[i], kmer_length);
+        kind[i] = rb.kind; lo[i] = rb.lo; hi[i] = rb.hi;
+    }
+}
+
 static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters, size_t n_filters,
                        const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
 
-static int check_filters(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure) {
+int kmdb_check_filters(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure) {
     if ((n_filters && !filters) || ((n_filters || measure >= 0) && !sample_kmers)) return kmdb_set_error(std::string(who) + ": null argument");
     if (measure >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + ": unknown measure");
     if (n_filters > (size_t)DEV_FILTER_MAX) return kmdb_set_error(std::string(who) + ": more than " + std::to_string(DEV_FILTER_MAX) + " bounds");
@@ -532,7 +539,7 @@ extern "C" int kmdb_all2all_sparse(kmdb_db* db, kmdb_sparse_rows* out, const kmd
 
 extern "C" int kmdb_all2all_sparse_filtered(kmdb_db* db, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
                                             kmdb_sparse_rows* out, const kmdb_opts* opts) {
-    if (check_filters("kmdb_all2all_sparse_filtered", filters, n_filters, sample_kmers, measure)) return 1;
+    if (kmdb_check_filters("kmdb_all2all_sparse_filtered", filters, n_filters, sample_kmers, measure)) return 1;
     // bounds are conditions on the whole cell: a slice of the pattern stream (opts->shard_*) holds partial sums only
     if ((n_filters || measure >= 0) && opts && opts->shard_count > 1) return kmdb_set_error("kmdb_all2all_sparse_filtered: filters need the whole database (shard_count must be 1)");
     return sparse_impl(db, false, nullptr, 0, ~0ull, filters, n_filters, sample_kmers, measure, out, opts);
@@ -541,12 +548,60 @@ extern "C" int kmdb_all2all_sparse_filtered(kmdb_db* db, const kmdb_cell_filter*
 extern "C" int kmdb_sparse_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
                                              size_t n_filters, const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
     if (!db || !out) return kmdb_set_error("kmdb_sparse_from_dense_device: null argument");
-    if (check_filters("kmdb_sparse_from_dense_device", filters, n_filters, sample_kmers, measure)) return 1;
+    if (kmdb_check_filters("kmdb_sparse_from_dense_device", filters, n_filters, sample_kmers, measure)) return 1;
     const uint64_t cells = db->N ? db->N * (db->N - 1) / 2 : 0;
     if (cell_hi > cells) cell_hi = cells;
     if (cell_lo > cell_hi) return kmdb_set_error("kmdb_sparse_from_dense_device: cell_lo > cell_hi");
     if (!cells_dev && cell_hi > cell_lo) return kmdb_set_error("kmdb_sparse_from_dense_device: null matrix");
     return sparse_impl(db, true, cells_dev, cell_lo, cell_hi, filters, n_filters, sample_kmers, measure, out, opts);
+}
+
+// The host side of a filtered sparse call: every cell that left the device is decided by the reference's own arithmetic (a = the row sample's k-mer
+// count, b = the column sample's: CombinedFilter, sparse_filters.h:38-61), the rows are compacted in place and the measures computed.  The all2all
+// calls pass one count array twice, db2db.hip the arrays of its two databases.
+int kmdb_sparse_decide(const char* who, kmdb_sparse_rows* out, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers,
+                       const uint32_t* col_kmers, int measure, int k) {
+    const uint64_t N = out->n_rows;
+    const unsigned nthr = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
+    std::vector<uint64_t> kept(N + 1, 0);
+    auto rows_of = [&](unsigned t, auto&& fn) { for (uint64_t i = (uint64_t)N * t / nthr; i < (uint64_t)N * (t + 1) / nthr; ++i) fn(i); };
+    auto parallel = [&](auto&& fn) {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nthr; ++t) th.emplace_back([&, t]() { rows_of(t, fn); });
+        for (auto& x : th) x.join();
+    };
+    parallel([&](uint64_t i) {                             // pass 1: filter every row in place (write position <= read position)
+        uint64_t w = out->row_ptr[i];
+        for (uint64_t e = out->row_ptr[i]; e < out->row_ptr[i + 1]; ++e) {
+            const uint32_t c = out->val[e], cj = out->col[e];
+            bool ok = true;
+            for (size_t q = 0; q < n_filters && ok; ++q) {
+                const double x = kmdbh_metric(filters[q].metric, c, row_kmers[i], col_kmers[cj], k);
+                ok = x >= filters[q].lo && x <= filters[q].hi;
+            }
+            if (ok) { out->col[w] = cj; out->val[w] = c; ++w; }
+        }
+        kept[i + 1] = w - out->row_ptr[i];
+    });
+    std::vector<uint64_t> new_ptr(N + 1, 0);
+    for (uint64_t i = 0; i < N; ++i) new_ptr[i + 1] = new_ptr[i] + kept[i + 1];
+    // pass 2: close the gaps (ascending rows; a row never moves right)
+    for (uint64_t i = 0; i < N; ++i)
+        if (new_ptr[i] != out->row_ptr[i] && kept[i + 1]) {
+            std::memmove(out->col + new_ptr[i], out->col + out->row_ptr[i], kept[i + 1] * 4);
+            std::memmove(out->val + new_ptr[i], out->val + out->row_ptr[i], kept[i + 1] * 4);
+        }
+    for (uint64_t i = 0; i <= N; ++i) out->row_ptr[i] = new_ptr[i];
+    out->nnz = new_ptr[N];
+    if (measure >= 0) {
+        out->measure = (double*)std::malloc(std::max<uint64_t>(out->nnz, 1) * 8);
+        if (!out->measure) { kmdb_sparse_free(out); return kmdb_set_error(std::string(who) + ": out of host memory for the measures"); }
+        parallel([&](uint64_t i) {
+            for (uint64_t e = out->row_ptr[i]; e < out->row_ptr[i + 1]; ++e)
+                out->measure[e] = kmdbh_metric(measure, out->val[e], row_kmers[i], col_kmers[out->col[e]], k);
+        });
+    }
+    return 0;
 }
 
 // from_cells: compact the caller's cells [cell_lo, cell_hi) (dense_dev points at cell_lo); else accumulate the whole triangle first
@@ -575,10 +630,7 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
         SP_TRY(hipMalloc((void**)&d_counts, std::max<uint64_t>(N, 1) * 4));
         SP_TRY(hipMemcpyAsync(d_counts, sample_kmers, N * 4, hipMemcpyHostToDevice, st));
         df.n = (int)n_filters; df.counts = d_counts;
-        for (size_t i = 0; i < n_filters; ++i) {
-            const RatioBound rb = ratio_bound(filters[i], (int)db->kmer_length);
-            df.kind[i] = rb.kind; df.lo[i] = rb.lo; df.hi[i] = rb.hi;
-        }
+        kmdb_dev_bounds(filters, n_filters, (int)db->kmer_length, df.kind, df.lo, df.hi);
     }
     const uint32_t* cellsp = (const uint32_t*)dense_dev;
     if (!from_cells) {
@@ -632,49 +684,7 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
 #undef SP_TRY
     cleanup();
     kmdb_release_staging(db);
-    if (n_filters || measure >= 0) {
-        // the host side: every surviving cell decided by the reference's own arithmetic, rows compacted in place, measures computed
-        const int k = (int)db->kmer_length;
-        const unsigned nthr = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
-        std::vector<uint64_t> kept(N + 1, 0);
-        auto rows_of = [&](unsigned t, auto&& fn) { for (uint64_t i = (uint64_t)N * t / nthr; i < (uint64_t)N * (t + 1) / nthr; ++i) fn(i); };
-        auto parallel = [&](auto&& fn) {
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nthr; ++t) th.emplace_back([&, t]() { rows_of(t, fn); });
-            for (auto& x : th) x.join();
-        };
-        parallel([&](uint64_t i) {                             // pass 1: filter every row in place (write position <= read position)
-            uint64_t w = out->row_ptr[i];
-            for (uint64_t e = out->row_ptr[i]; e < out->row_ptr[i + 1]; ++e) {
-                const uint32_t c = out->val[e], cj = out->col[e];
-                bool ok = true;
-                for (size_t q = 0; q < n_filters && ok; ++q) {
-                    const double x = kmdbh_metric(filters[q].metric, c, sample_kmers[i], sample_kmers[cj], k);
-                    ok = x >= filters[q].lo && x <= filters[q].hi;
-                }
-                if (ok) { out->col[w] = cj; out->val[w] = c; ++w; }
-            }
-            kept[i + 1] = w - out->row_ptr[i];
-        });
-        std::vector<uint64_t> new_ptr(N + 1, 0);
-        for (uint64_t i = 0; i < N; ++i) new_ptr[i + 1] = new_ptr[i] + kept[i + 1];
-        // pass 2: close the gaps (ascending rows; a row never moves right)
-        for (uint64_t i = 0; i < N; ++i)
-            if (new_ptr[i] != out->row_ptr[i] && kept[i + 1]) {
-                std::memmove(out->col + new_ptr[i], out->col + out->row_ptr[i], kept[i + 1] * 4);
-                std::memmove(out->val + new_ptr[i], out->val + out->row_ptr[i], kept[i + 1] * 4);
-            }
-        for (uint64_t i = 0; i <= N; ++i) out->row_ptr[i] = new_ptr[i];
-        out->nnz = new_ptr[N];
-        if (measure >= 0) {
-            out->measure = (double*)std::malloc(std::max<uint64_t>(out->nnz, 1) * 8);
-            if (!out->measure) { kmdb_sparse_free(out); return kmdb_set_error("kmdb_all2all_sparse: out of host memory for the measures"); }
-            parallel([&](uint64_t i) {
-                for (uint64_t e = out->row_ptr[i]; e < out->row_ptr[i + 1]; ++e)
-                    out->measure[e] = kmdbh_metric(measure, out->val[e], sample_kmers[i], sample_kmers[out->col[e]], k);
-            });
-        }
-    }
+    if (n_filters || measure >= 0) return kmdb_sparse_decide("kmdb_all2all_sparse", out, filters, n_filters, sample_kmers, sample_kmers, measure, (int)db->kmer_length);
     return 0;
 }
 
@@ -715,7 +725,7 @@ int check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n
     if (count == 0) return kmdb_set_error(std::string(who) + ": count must be at least 1");
     if (criterion < 0 || criterion >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + ": unknown criterion");
     if (!sample_kmers) return kmdb_set_error(std::string(who) + ": sample_kmers is NULL");
-    return check_filters(who, filters, n_filters, sample_kmers, -1);
+    return kmdb_check_filters(who, filters, n_filters, sample_kmers, -1);
 }
 struct DevFree {
     std::vector<void*> p;
@@ -862,6 +872,12 @@ extern "C" int kmdb_all2all_sampled(kmdb_db* db, const kmdb_cell_filter* filters
     const int rc = kmdbh_sample_rows_select(criterion, count, (int)db->kmer_length, sample_kmers, filters, n_filters, parts, 1, out);
     kmdb_sparse_free(&cand);
     return rc;
+}
+
+extern "C" int kmdb_db2db_stats_get(const kmdb_db* db_row, kmdb_db2db_stats* out) {
+    if (!db_row || !out) return kmdb_set_error("kmdb_db2db_stats_get: null argument");
+    *out = db_row->d2_stats;
+    return 0;
 }
 
 extern "C" int kmdb_db_sample_stats(const kmdb_db* db, kmdb_sample_stats* out) {

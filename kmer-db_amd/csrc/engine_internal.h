@@ -39,6 +39,7 @@ struct kmdb_engine_view {
     uint4** rl_node;               // and the walk's 16-byte node records {subtree end, parent, first run or the only id, min(l, 65535) | min(runs, 65535) << 16}
     bool* rl_tried;
     uint64_t* device_bytes;
+    struct kmdb_db2db_stats* d2_stats;   // the last db2db call with this handle as the row database (kmdb_db2db_stats_get)
     void* stream;
     void* ev[4];
 };
@@ -50,6 +51,17 @@ void kmdb_engine_set_times(kmdb_db* db, double kernel_ms, double dominant_ms);
 // host compaction of dense new2all rows into the CSR of one2all_sp (new2all.hip; node.hip uses it after its reduce); 0, or 1 with the error set
 struct kmdb_sparse_rows;
 int kmdb_rows_to_sparse(const uint32_t* dense, size_t nq, uint64_t N, kmdb_sparse_rows* out);
+
+// ---- the -min / -max filters of the sparse calls (engine.hip; db2db.hip uses them for its cell of two databases)
+struct kmdb_cell_filter;
+// argument checks of a filtered call, before any device work; sample_kmers: the count array (null when the caller holds none); 0, or 1 with the error set
+int kmdb_check_filters(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure);
+// every host bound as the device's widened bound on a plain ratio (ratio_bound and its margin): kind / lo / hi of cell_filter.h's DevFilter
+void kmdb_dev_bounds(const kmdb_cell_filter* filters, size_t n_filters, int kmer_length, int* kind, double* lo, double* hi);
+// The exact decision on the host: every cell of `out` the device kept is decided by kmdbh_metric(metric, c, row_kmers[row], col_kmers[col], k)
+// against the bounds, the rows are compacted in place and, with measure >= 0, out->measure is filled.  0, or 1 with the error set (out freed).
+int kmdb_sparse_decide(const char* who, kmdb_sparse_rows* out, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers,
+                       const uint32_t* col_kmers, int measure, int kmer_length);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

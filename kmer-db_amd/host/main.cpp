@@ -480,7 +480,7 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
 
 // ---- all2all-parts (console_all2all_parts.cpp:21-399): a collection split into several databases --------------
 // Grid of cells (row part, column part <= row part): the diagonal cells are all2all_sp of one database, the others
-// db2db_sp of two (similarity_calculator.cpp:1225-1540 -> kmdb_db2db_dense).  Row k of row part i is written as the
+// db2db_sp + compact2 of two (similarity_calculator.cpp:1225-1540, console_all2all_parts.cpp:179-195 -> kmdb_db2db_sparse_filtered).  Row k of row part i is written as the
 // concatenation of its cells' sparse rows with the column index shifted by the samples of the earlier parts
 // (:292-310), which is the sparse lower-triangular matrix of the whole collection.
 int run_all2all_parts(std::vector<std::string>& args, Common& c) {
@@ -553,6 +553,14 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
     std::mutex mu;
     std::condition_variable cv;
     std::exception_ptr failure;
+    // the -min / -max bounds go with every cell's call (as for all2all-sp); the k-mer counts as the library takes them (num_kmers_t = uint32)
+    std::vector<kmdb_cell_filter> fl;
+    for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+    if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
+        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+    if (fl.size() > 8) fl.clear();                                // (the rows are checked with every bound below anyway)
+    std::vector<uint32_t> counts32(counts.begin(), counts.end());
+    const bool dense_cells = std::getenv("KMDB_PARTS_DENSE_CELLS") != nullptr;
     auto block_row = [&](Worker& wk, size_t i) {
         auto get = [&](size_t p, size_t keep) -> Db& {
             if (wk.resident[p]) return *wk.resident[p];
@@ -573,33 +581,60 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
         const uint64_t row_shift = row_start[i];
         Db& drow = get(i, i);
         const uint64_t nr = part_n[i];
-        std::vector<std::vector<uint32_t>> cross(i);              // cross[j]: nr x part_n[j]
+        // A cell is kept as the reference keeps it (:179-195, 225-241: db2db_sp, then compact2 with the -min / -max filter): compacted and filtered
+        // on the device, a CSR per earlier part of the block row.  KMDB_PARTS_DENSE_CELLS=1: the dense rectangles of kmdb_db2db_dense, scanned on the
+        // host (the previous path, for A/B); the bytes written are the same.
+        std::vector<kmdb_sparse_rows> cross_sp(dense_cells ? 0 : i, kmdb_sparse_rows{});
+        std::vector<std::vector<uint32_t>> cross(dense_cells ? i : 0);   // cross[j]: nr x part_n[j]
+        struct FreeRows { std::vector<kmdb_sparse_rows>& v; ~FreeRows() { for (auto& x : v) kmdb_sparse_free(&x); } } free_rows{cross_sp};
+        const uint32_t* row_counts = counts32.data() + row_shift;
         for (size_t j = 0; j < i; ++j) {
             { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << j + 1 << ")" << std::endl; }
             Db& dcol = get(j, i);
-            cross[j].resize(nr * part_n[j] + 1);
-            if (kmdb_db2db_dense(drow.d, dcol.d, cross[j].data(), &wk.o)) {
-                // out of HBM inside the call (its scratch, lazily made working sets): the other resident parts go, one more try
+            if (dense_cells) {
+                cross[j].resize(nr * part_n[j] + 1);
+                if (kmdb_db2db_dense(drow.d, dcol.d, cross[j].data(), &wk.o)) {
+                    // out of HBM inside the call (its scratch, lazily made working sets): the other resident parts go, one more try
+                    for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i && q != j) wk.resident[q].reset();
+                    check(kmdb_db2db_dense(drow.d, dcol.d, cross[j].data(), &wk.o));
+                }
+                continue;
+            }
+            const uint32_t* col_counts = counts32.data() + row_start[j];
+            if (kmdb_db2db_sparse_filtered(drow.d, dcol.d, fl.data(), fl.size(), row_counts, col_counts, -1, &cross_sp[j], &wk.o)) {
                 for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i && q != j) wk.resident[q].reset();
-                check(kmdb_db2db_dense(drow.d, dcol.d, cross[j].data(), &wk.o));
+                check(kmdb_db2db_sparse_filtered(drow.d, dcol.d, fl.data(), fl.size(), row_counts, col_counts, -1, &cross_sp[j], &wk.o));
             }
         }
         { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << i + 1 << ")" << std::endl; }
         kmdb_sparse_rows sp{};
-        if (kmdb_all2all_sparse(drow.d, &sp, &wk.o)) {
+        auto diagonal = [&]() {
+            if (dense_cells || fl.empty()) return kmdb_all2all_sparse(drow.d, &sp, &wk.o);
+            return kmdb_all2all_sparse_filtered(drow.d, fl.data(), fl.size(), row_counts, -1, &sp, &wk.o);
+        };
+        if (diagonal()) {
             for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i) wk.resident[q].reset();
-            check(kmdb_all2all_sparse(drow.d, &sp, &wk.o));
+            check(diagonal());
         }
         for (uint64_t r = 0; r < nr; ++r) {
             cols.clear(); vals.clear();
             const uint32_t cr = (uint32_t)counts[row_shift + r];
             uint64_t shift = 0;
             for (size_t j = 0; j < i; ++j) {
-                const uint32_t* m = cross[j].data() + r * part_n[j];
-                for (uint64_t cidx = 0; cidx < part_n[j]; ++cidx)
-                    if (m[cidx] && c.filters.pass(m[cidx], cr, (uint32_t)counts[shift + cidx], (int)k)) {
-                        cols.push_back((uint32_t)(shift + cidx)); vals.push_back(m[cidx]);
-                    }
+                if (dense_cells) {
+                    const uint32_t* m = cross[j].data() + r * part_n[j];
+                    for (uint64_t cidx = 0; cidx < part_n[j]; ++cidx)
+                        if (m[cidx] && c.filters.pass(m[cidx], cr, (uint32_t)counts[shift + cidx], (int)k)) {
+                            cols.push_back((uint32_t)(shift + cidx)); vals.push_back(m[cidx]);
+                        }
+                } else {
+                    // (the bounds were applied inside the call; pass() is the front-end's own statement of them and costs a look per KEPT cell)
+                    const kmdb_sparse_rows& x = cross_sp[j];
+                    for (uint64_t e = x.row_ptr[r]; e < x.row_ptr[r + 1]; ++e)
+                        if (c.filters.pass(x.val[e], cr, (uint32_t)counts[shift + x.col[e]], (int)k)) {
+                            cols.push_back((uint32_t)(shift + x.col[e])); vals.push_back(x.val[e]);
+                        }
+                }
                 shift += part_n[j];
             }
             for (uint64_t e = sp.row_ptr[r]; e < sp.row_ptr[r + 1]; ++e)
