@@ -58,6 +58,16 @@ __device__ __forceinline__ uint32_t xcd_contiguous(uint32_t b, uint32_t n) {
     return (b & 7u) * (n >> 3) + (b >> 3);
 }
 
+// A kernel's parameter block where it lies in the kernarg segment (the kernel's only argument: offset 0), behind a pointer the compiler cannot see
+// through.  What is read through it is loaded where it is used (a scalar load, from the constant cache) instead of being held in scalar registers across
+// the loops from the kernel's start: the emit kernels take some twenty pointers, most of them read once per batch of 64 nodes or once per run.
+#define KARG(P) const P __attribute__((address_space(4)))*
+template <class P> __device__ __forceinline__ KARG(P) kernarg_reread() {
+    KARG(P) p = (KARG(P))__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 __device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src) {
     const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, WAVE);
     const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, WAVE);
@@ -99,6 +109,17 @@ struct PoolView {
     uint32_t pshift;               // row mode, != 0: packed records — the weight digit (and its index) sit in the column mask word from bit `pshift` (= the
                                    // block width) on, 64 - pshift - 2 bits of digit; the key word beside the record holds the stream only and stays behind in the sort
 };
+// What the emit kernels hold of a PoolView: the members every record store reads, by value, and the view itself where it lies in the kernel's parameter block.
+// The others (cursors, capacities, the chunk table, the counters: read once per grab of chunks or when a pool runs over) are re-read from there at their
+// point of use — pool_cold() — instead of occupying scalar registers for the whole kernel.  A PoolView serves the same functions (all members by value).
+struct PoolRef {
+    KARG(PoolView) k;
+    unsigned char* rec; uint32_t* recw;        // row mode
+    uint32_t* wkey; WideRec* wrec;             // few streams
+    uint32_t kbits, dbits, pshift;
+};
+__device__ __forceinline__ const PoolView* pool_cold(const PoolView& pv) { return &pv; }
+__device__ __forceinline__ KARG(PoolView) pool_cold(const PoolRef& pv) { KARG(PoolView) k = pv.k; asm volatile("" : "+s"(k)); return k; }
 struct Resv { uint32_t base1, n1, base2; };   // slots [base1, base1 + n1) and [base2, ...) for the rest
 __device__ __forceinline__ uint32_t resv_slot(const Resv& r, uint32_t rank) { return rank < r.n1 ? r.base1 + rank : r.base2 + (rank - r.n1); }
 
@@ -143,33 +164,33 @@ __device__ __forceinline__ void arena_init(WaveArena& A, uint32_t* lds, uint32_t
     for (uint32_t e = lane; e <= A.tmask; e += WAVE) { A.t_slot[e] = KEY_NONE; if (!A.direct) A.t_key[e] = KEY_NONE; }
     lds_sync();
 }
-__device__ __forceinline__ uint32_t arena_take(WaveArena& A, const PoolView& pv, uint32_t s, uint32_t lane) {
+template <class PV> __device__ __forceinline__ uint32_t arena_take(WaveArena& A, const PV& pv, uint32_t s, uint32_t lane) {
     if (A.stock == 0) {
         uint32_t base = 0;
         A.sub = (A.sub + 61u) % KMDB_SUBPOOLS;                        // every grab from another sub-pool: a wave with much output does not drain one
-        if (lane == 0) base = atomicAdd(&pv.sub_cursor[A.sub * 16u], ARENA_GRAB);
+        if (lane == 0) base = atomicAdd(&pool_cold(pv)->sub_cursor[A.sub * 16u], ARENA_GRAB);
         base = bcast(base, 0);
-        if (base + ARENA_GRAB > pv.sub_cap) {                        // stays in range; the call is repeated with a larger pool
-            if (lane == 0) atomicOr(&pv.counters[KCTR_POOL_OVERFLOW], 1u);
-            base = pv.sub_cap - ARENA_GRAB;
+        if (base + ARENA_GRAB > pool_cold(pv)->sub_cap) {                        // stays in range; the call is repeated with a larger pool
+            if (lane == 0) atomicOr(&pool_cold(pv)->counters[KCTR_POOL_OVERFLOW], 1u);
+            base = pool_cold(pv)->sub_cap - ARENA_GRAB;
         }
         A.next = base; A.stock = ARENA_GRAB;
     }
     const uint32_t id = A.next * KMDB_SUBPOOLS + A.sub;
     ++A.next; --A.stock;
-    if (lane == 0) pv.chunk_key[id] = s;
+    if (lane == 0) pool_cold(pv)->chunk_key[id] = s;
     return id;
 }
 // next chunk of the wide pool
-__device__ __forceinline__ uint32_t arena_take_wide(WaveArena& A, const PoolView& pv, uint32_t lane) {
+template <class PV> __device__ __forceinline__ uint32_t arena_take_wide(WaveArena& A, const PV& pv, uint32_t lane) {
     if (A.wstock == 0) {
         uint32_t base = 0;
         A.wsub = (A.wsub + 61u) % KMDB_SUBPOOLS;                     // every grab from another sub-pool: waves with much output do not drain one
-        if (lane == 0) base = atomicAdd(&pv.wsub_cursor[A.wsub * 16u], WIDE_GRAB);
+        if (lane == 0) base = atomicAdd(&pool_cold(pv)->wsub_cursor[A.wsub * 16u], WIDE_GRAB);
         base = bcast(base, 0);
-        if (base + WIDE_GRAB > pv.wsub_cap) {                     // stays in range; the call is repeated with a larger pool
-            if (lane == 0) atomicOr(&pv.counters[KCTR_WIDE_OVERFLOW], 1u);
-            base = pv.wsub_cap - WIDE_GRAB;
+        if (base + WIDE_GRAB > pool_cold(pv)->wsub_cap) {                     // stays in range; the call is repeated with a larger pool
+            if (lane == 0) atomicOr(&pool_cold(pv)->counters[KCTR_WIDE_OVERFLOW], 1u);
+            base = pool_cold(pv)->wsub_cap - WIDE_GRAB;
         }
         A.wnext = base; A.wstock = WIDE_GRAB;
     }
@@ -179,7 +200,7 @@ __device__ __forceinline__ uint32_t arena_take_wide(WaveArena& A, const PoolView
 }
 // cnt (1..64) slots of stream s; s and cnt wave-uniform, every lane of the wave calls
 // cnt (1..64) slots of the wide pool: records of all streams share the wave's one open chunk, a device-wide sort groups them
-__device__ __forceinline__ Resv arena_reserve_wide(WaveArena& A, const PoolView& pv, uint32_t cnt, uint32_t lane) {
+template <class PV> __device__ __forceinline__ Resv arena_reserve_wide(WaveArena& A, const PV& pv, uint32_t cnt, uint32_t lane) {
     if (!A.dopen) { A.dslot = arena_take_wide(A, pv, lane) << WCH_SHIFT; A.dopen = 1; }
     const uint32_t v = A.dslot, rem = WCH_REC - (v & (WCH_REC - 1u));
     if (cnt < rem) { A.dslot = v + cnt; return Resv{v, cnt, 0u}; }
@@ -217,18 +238,18 @@ __device__ __forceinline__ Resv arena_reserve(WaveArena& A, const PoolView& pv, 
     lds_sync();
     return r;
 }
-__device__ __forceinline__ void arena_finish(const WaveArena& A, const PoolView& pv, uint32_t lane) {
+template <class PV> __device__ __forceinline__ void arena_finish(const WaveArena& A, const PV& pv, uint32_t lane) {
     if (A.tmask == 0) return;                                   // no stream table (never-written slots of the wide pool keep their 0xFFFFFFFF key)
     for (uint32_t e = lane; e <= A.tmask; e += WAVE) {
         const uint32_t v = A.t_slot[e];
-        if (v != KEY_NONE && (A.direct || A.t_key[e] != KEY_NONE)) pv.chunk_fill[v >> CH_SHIFT] = v & (CH_REC - 1u);
+        if (v != KEY_NONE && (A.direct || A.t_key[e] != KEY_NONE)) pool_cold(pv)->chunk_fill[v >> CH_SHIFT] = v & (CH_REC - 1u);
     }
 }
 
 // diagonal streams (X == Y, cols == rows) pack 8-byte rows into the first half of their chunks
 // the records `on` of a wave step into the wide pool: one reservation for all lanes per weight digit (nearly always one digit).
 // Every lane of the wave calls.
-__device__ __forceinline__ void wide_emit(WaveArena& A, const PoolView& pv, bool on, unsigned long long rows, unsigned long long cols, uint32_t w, uint32_t stream,
+template <class PV> __device__ __forceinline__ void wide_emit(WaveArena& A, const PV& pv, bool on, unsigned long long rows, unsigned long long cols, uint32_t w, uint32_t stream,
                                           uint32_t lane, unsigned long long lt_mask) {
     // (packed records, pv.pshift != 0: the weight digit and its index in the spare bits of the column word, the key word = the stream only)
     const uint32_t dbits = pv.pshift ? (64u - pv.pshift - 2u < 16u ? 64u - pv.pshift - 2u : 16u) : pv.dbits;
@@ -270,7 +291,7 @@ __device__ __forceinline__ void rowtab_init(RowTab& R, uint32_t* lds, uint32_t n
     for (uint32_t e = lane; e < 2u * n; e += WAVE) lds[e] = 0u;         // end == 0: no open chunk
     lds_sync();
 }
-__device__ __forceinline__ void row_emit(WaveArena& A, const PoolView& pv, const RowTab& R, bool on, uint32_t X, unsigned long long rows, unsigned long long cols,
+template <class PV> __device__ __forceinline__ void row_emit(WaveArena& A, const PV& pv, const RowTab& R, bool on, uint32_t X, unsigned long long rows, unsigned long long cols,
                                          uint32_t w, uint32_t stream, uint32_t lane, unsigned long long lt_mask) {
     const uint32_t dbits = pv.pshift ? (64u - pv.pshift - 2u < 16u ? 64u - pv.pshift - 2u : 16u) : pv.dbits;
     const uint32_t dmask = (1u << dbits) - 1u;
@@ -303,13 +324,13 @@ __device__ __forceinline__ void row_emit(WaveArena& A, const PoolView& pv, const
             const uint32_t tot = R.pos[X0];                        // after every lane's reservation
             const uint32_t over = tot - e0;                        // slots needed beyond the open chunk (no open chunk: e0 == 0, positions count from 0)
             const uint32_t nnew = (over + CH_REC - 1u) >> CH_SHIFT;
-            if (lane == 0 && e0) pv.chunk_fill[(e0 - 1u) >> CH_SHIFT] = CH_REC;
+            if (lane == 0 && e0) pool_cold(pv)->chunk_fill[(e0 - 1u) >> CH_SHIFT] = CH_REC;
             const bool mine = ovf && X == X0;
             const uint32_t qv = p - e0;
             uint32_t cl = 0;
             for (uint32_t i = 0; i < nnew; ++i) {
-                cl = arena_take(A, pv, pv.n_states + X0, lane);        // key of a row chunk: n_states + row
-                if (lane == 0 && i + 1u < nnew) pv.chunk_fill[cl] = CH_REC;
+                cl = arena_take(A, pv, pool_cold(pv)->n_states + X0, lane);        // key of a row chunk: n_states + row
+                if (lane == 0 && i + 1u < nnew) pool_cold(pv)->chunk_fill[cl] = CH_REC;
                 if (mine && (qv >> CH_SHIFT) == i) p = (cl << CH_SHIFT) | (qv & (CH_REC - 1u));
             }
             if (lane == 0) { R.pos[X0] = (cl << CH_SHIFT) + (over - ((nnew - 1u) << CH_SHIFT)); R.end[X0] = (cl << CH_SHIFT) + CH_REC; }
@@ -330,12 +351,20 @@ __device__ __forceinline__ void row_emit(WaveArena& A, const PoolView& pv, const
         on = on && w != 0;
     }
 }
-__device__ __forceinline__ void rowtab_finish(const RowTab& R, const PoolView& pv, uint32_t lane) {
+template <class PV> __device__ __forceinline__ void rowtab_finish(const RowTab& R, const PV& pv, uint32_t lane) {
     lds_sync();
     for (uint32_t X = lane; X < R.n; X += WAVE) {
         const uint32_t e = R.end[X];
-        if (e) pv.chunk_fill[(e - 1u) >> CH_SHIFT] = CH_REC - (e - R.pos[X]);
+        if (e) pool_cold(pv)->chunk_fill[(e - 1u) >> CH_SHIFT] = CH_REC - (e - R.pos[X]);
     }
+}
+// the emit path of a kernel instantiation: ROWS = many streams (row chunks), otherwise few streams (the wide pool in arrival order).  The other
+// path's code, and with it the state it keeps live, does not exist in the instantiation.
+template <bool ROWS, class PV>
+__device__ __forceinline__ void rec_emit(WaveArena& A, const PV& pv, const RowTab& R, bool on, uint32_t X, unsigned long long rows, unsigned long long cols,
+                                         uint32_t w, uint32_t stream, uint32_t lane, unsigned long long lt_mask) {
+    if constexpr (ROWS) row_emit(A, pv, R, on, X, rows, cols, w, stream, lane, lt_mask);
+    else wide_emit(A, pv, on, rows, cols, w, stream, lane, lt_mask);
 }
 // stream chunks hold the records (X, X, rows) of one block X: 8-byte rows in the first half of the chunk, weights beside
 __device__ __forceinline__ void rec_store_diag(const PoolView& pv, uint32_t slot, unsigned long long rows, uint32_t w) {
@@ -743,7 +772,8 @@ __host__ __device__ inline size_t k1n_wave_bytes(uint32_t chain_cap, uint32_t tb
 // of these is written, grouped or read again (C2: 47 M of 125 M records, the whole stream-chunk path and the apply kernel beside the
 // wide kernel).  The rare others — a lane whose first block is not the wave's current one, a weight of 128 or more — take the
 // records' way through the wide pool / the row chunks as in all_wide mode.
-template <int MODE, int MINW>
+// (NParams must stay the kernel's ONLY argument: kernarg_reread<NParams>() and PoolRef::k read it at offset 0 of the kernarg segment)
+template <int MODE, int MINW, bool ROWS>
 __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_eu(MINW, 8))) void k1n_kernel(const NParams q) {
     constexpr bool DIRECT = MODE == 1, FLAT = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -763,14 +793,19 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
         __syncthreads();
     }
     if (seg >= q.n_segs) return;
-    const uint32_t n_rows = q.pool.row_mode ? q.n_keys : 0u;
+    const uint32_t n_rows = ROWS ? q.n_keys : 0u;                       // (the host picks the instantiation by the handle's row mode)
     unsigned char* wbase = lds_raw + k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, n_rows) * wave;
     uint32_t* table = (uint32_t*)wbase;                                                      // open chunks
     ulonglong2* chain_m = (ulonglong2*)(wbase + arena_table_bytes(q.tbits, q.n_keys));      // [chain_cap] one slot per depth:
     uint32_t* chain_b = (uint32_t*)(chain_m + q.chain_cap);                                  // the latest node of that depth on the current root path
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     RowTab RT{nullptr, nullptr, 0u};
-    if (n_rows) rowtab_init(RT, (uint32_t*)(wbase + (((size_t)q.chain_cap * 20 + 15) & ~(size_t)15) + arena_table_bytes(q.tbits, q.n_keys)), n_rows, lane);
+    if constexpr (ROWS) rowtab_init(RT, (uint32_t*)(wbase + (((size_t)q.chain_cap * 20 + 15) & ~(size_t)15) + arena_table_bytes(q.tbits, q.n_keys)), n_rows, lane);
+    // the pool: what a record store reads is held, the rest is re-read from the parameter block where it is used (PoolRef)
+    PoolRef pv{};
+    pv.k = &((KARG(NParams))__builtin_amdgcn_kernarg_segment_ptr())->pool;
+    pv.kbits = q.pool.kbits; pv.dbits = q.pool.dbits; pv.pshift = q.pool.pshift;
+    if constexpr (ROWS) { pv.rec = q.pool.rec; pv.recw = q.pool.recw; } else { pv.wkey = q.pool.wkey; pv.wrec = q.pool.wrec; }
     const uint32_t first = seg * q.nseg_nodes;
     const uint32_t end = (q.P - first) < q.nseg_nodes ? q.P : first + q.nseg_nodes;
 
@@ -783,14 +818,15 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
 
     // chain slots of the first node's ancestors: inclusive merge along the root path
     {
-        const uint32_t d = q.seg_anc_n[seg];
+        KARG(NParams) qr = kernarg_reread<NParams>();                    // (once per slice: read where used, not held)
+        const uint32_t d = qr->seg_anc_n[seg];
         NSum carry = nsum_make(BNONE, 0ull, BNONE, 0ull, false);
         for (uint32_t cb = 0; cb < d; cb += WAVE) {
             const uint32_t k = cb + lane;
             const bool on = k < d;
             NSum S = nsum_make(BNONE, 0ull, BNONE, 0ull, false);
             if (on) {
-                const uint32_t node = q.seg_anc[(size_t)seg * q.chain_cap + k];
+                const uint32_t node = qr->seg_anc[(size_t)seg * q.chain_cap + k];
                 const uint32_t info = q.p0_info[node];
                 uint32_t e1b = BNONE; unsigned long long e1m = 0;
                 if ((info >> 16) > 1u) { const uint32_t po = q.pair_ofs[node]; e1b = q.pair_blk[po]; e1m = q.pair_mask[po]; }
@@ -976,10 +1012,8 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
                     if (mine) rec_store_diag(q.pool, resv_slot(r, (uint32_t)__popcll(bc & lt_mask)), F0, w);
                     pend &= ~bc;
                 }
-            } else if (n_rows) {
-                row_emit(A, q.pool, RT, d0, w0, F0, F0, w, tri32(w0) + w0, lane, lt_mask);
             } else {
-                wide_emit(A, q.pool, d0, F0, F0, w, tri32(w0) + w0, lane, lt_mask);
+                rec_emit<ROWS>(A, pv, RT, d0, w0, F0, F0, w, tri32(w0) + w0, lane, lt_mask);
             }
         };
         if (!DIRECT) first_block_records();
@@ -988,13 +1022,8 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
         {
             const bool act2 = act && F1 != 0;
             if (__ballot(act2)) {
-                if (n_rows) {
-                    row_emit(A, q.pool, RT, act2, w1, F1, F0, w, tri32(w1) + w0, lane, lt_mask);
-                    row_emit(A, q.pool, RT, act2 && __popcll(F1) >= 2, w1, F1, F1, w, tri32(w1) + w1, lane, lt_mask);
-                } else {
-                    wide_emit(A, q.pool, act2, F1, F0, w, tri32(w1) + w0, lane, lt_mask);
-                    wide_emit(A, q.pool, act2 && __popcll(F1) >= 2, F1, F1, w, tri32(w1) + w1, lane, lt_mask);
-                }
+                rec_emit<ROWS>(A, pv, RT, act2, w1, F1, F0, w, tri32(w1) + w0, lane, lt_mask);
+                rec_emit<ROWS>(A, pv, RT, act2 && __popcll(F1) >= 2, w1, F1, F1, w, tri32(w1) + w1, lane, lt_mask);
             }
         }
         // ---- chain slots for the next batch: the nodes on the root path of this batch's last node, i.e. the
@@ -1015,10 +1044,11 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
         if (DIRECT) first_block_records();
     }
     if (DIRECT && curX != BNONE && !(q.dbg & 1u)) dflush();
-    if (DIRECT && lane == 0 && n_direct) atomicAdd(&q.direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], n_direct);
-    if (FLAT && lane == 0) { q.slice_cnt[seg] = flat_n; if (flat_n) atomicAdd(&q.direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], flat_n); }
-    arena_finish(A, q.pool, lane);
-    if (n_rows) rowtab_finish(RT, q.pool, lane);
+    KARG(NParams) qe = kernarg_reread<NParams>();                        // (the slice's end)
+    if (DIRECT && lane == 0 && n_direct) atomicAdd(&qe->direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], n_direct);
+    if (FLAT && lane == 0) { qe->slice_cnt[seg] = flat_n; if (flat_n) atomicAdd(&qe->direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], flat_n); }
+    if constexpr (MODE == 0) arena_finish(A, q.pool, lane);               // (the other modes open no stream chunk)
+    if constexpr (ROWS) rowtab_finish(RT, pv, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1058,27 +1088,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const uint32_t s0 = (blockIdx.x * 4u + wave) * q.slices;
     if (s0 >= q.n_segs) return;
     const uint32_t s1 = s0 + q.slices < q.n_segs ? s0 + q.slices : q.n_segs;
-    k2_v16i c00 = {}, c10 = {}, c11 = {};
-    uint32_t curX = BNONE;
     const TrConst trc = tr_const(lane);
-    auto flush = [&]() {
-        // one HBM atomic per non-zero cell (D layout of the MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)).  Cell (rb + r, rb + c)
-        // of the triangle sits at tri64(rb) + rb + [rb r + r (r - 1) / 2 + c]: a wave-uniform base and a 32-bit offset per lane
-        const uint32_t rb = curX * q.bwidth;
-        uint32_t* const Mb = q.M + (tri64((uint64_t)rb) + rb);
-        const uint32_t lim = q.N - rb;                                  // rows of the block inside the matrix (masks never hold an id beyond N: belt and braces)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const uint32_t row0 = (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * half, row1 = row0 + 32u;
-            const uint32_t o0 = rb * row0 + row0 * (row0 - 1u) / 2u + l31, o1 = rb * row1 + row1 * (row1 - 1u) / 2u + l31;
-            const uint32_t v00 = (uint32_t)c00[r], v10 = (uint32_t)c10[r], v11 = (uint32_t)c11[r];
-            if (v00 && l31 < row0 && row0 < lim) atomicAdd(Mb + o0, v00);
-            if (v10 && row1 < lim) atomicAdd(Mb + o1, v10);
-            if (v11 && l31 < row0 && row1 < lim) atomicAdd(Mb + o1 + 32u, v11);
-            c00[r] = 0; c10[r] = 0; c11[r] = 0;
-        }
-        if (lane == 0 && q.touched) q.touched[tri32(curX) + curX] = 1;      // (all2all-sp scans only the tiles a call added to)
-    };
     auto spread = [&](unsigned long long word, uint32_t shift, const unsigned long long* lut) -> k2_v4i {
         const uint32_t f = (uint32_t)(word >> shift) & 0xFFFFu;
         k2_v4i r;
@@ -1086,7 +1096,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         r[0] = (int)(uint32_t)lo; r[1] = (int)(uint32_t)(lo >> 32); r[2] = (int)(uint32_t)hi; r[3] = (int)(uint32_t)(hi >> 32);
         return r;
     };
-    // the 64 records of a step, one per lane; the next step's are requested before this one is applied
+    // the 64 records of a step, one per lane (m, wx; pend: those not applied yet); the next step's are requested before this one is applied
     uint32_t s = s0, n = q.slice_cnt[s0], b = 0;
     auto skip_empty = [&]() { while (b >= n && s + 1u < s1) { ++s; n = q.slice_cnt[s]; b = 0; } };
     skip_empty();
@@ -1096,24 +1106,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         if (b + lane < n) { const size_t i = (size_t)s * q.nseg_nodes + b + lane; nm = q.dmask[i]; nwx = q.dwx[i]; }
     };
     if (b < n) fetch();
+    unsigned long long m = 0, pend = 0;
+    uint32_t wx = 0;
+    auto next_step = [&]() -> bool {
+        if (b >= n) return false;
+        m = nm; wx = nwx;
+        b += WAVE;
+        skip_empty();
+        if (b < n) fetch();
+        pend = __ballot(m != 0ull);
+        return true;
+    };
+    // One tile per turn of the outer loop: the accumulators are cleared at its top, take the records of block X0 for as many steps as the block lasts, and
+    // are written back at its bottom.  (Cleared INSIDE a conditional write-back in the middle of the step loop, every accumulator was live on both sides of
+    // the branch and the allocator kept two copies of the tile: 31 registers in scratch at 128, still 8 at 168.)
     for (;;) {
-        // a step of 64 records — or, behind the last one, an empty step whose "block" differs from every tile: the ONE write-back site serves the
-        // changes of block and the end (a second inlined copy of its 48 conditional atomics cost 60 registers)
-        const bool cur = b < n;
-        const unsigned long long m = cur ? nm : 0ull;
-        const uint32_t wx = cur ? nwx : 0u;
-        if (cur) {
-            b += WAVE;
-            skip_empty();
-            if (b < n) fetch();
-        }
-        unsigned long long pend = __ballot(m != 0ull);
+        while (!pend && next_step()) {}
+        if (!pend) break;
+        const uint32_t X0 = bcast(wx >> 8, (uint32_t)__builtin_ctzll(pend));
+        k2_v16i c00 = {}, c10 = {}, c11 = {};
         for (;;) {
-            const uint32_t X0 = pend ? bcast(wx >> 8, (uint32_t)__builtin_ctzll(pend)) : BNONE;
-            if (X0 != curX) { if (curX != BNONE) flush(); curX = X0; }
-            if (!pend) break;
-            const bool mine = m != 0ull && (wx >> 8) == X0;
-            pend &= ~__ballot(mine);
+            const bool mine = ((pend >> lane) & 1ull) && (wx >> 8) == X0;
+            const unsigned long long bm = __ballot(mine);
+            if (!bm) break;                                      // the step's next record belongs to another tile
+            pend &= ~bm;
             const unsigned long long Rt = transpose64(mine ? m : 0ull, trc);        // lane r: bit k <=> record k of the step has id r of the block
             unsigned long long ra0, ra1;
             {
@@ -1136,9 +1152,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                 c11 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, c11, 0, 0, 0);
             }
             lds_sync();
-            if (!pend) break;                                    // (the step's records are in; a change of block is seen with the next step)
+            if (pend || !next_step()) break;                     // records of another block left in the step, or the last step done
         }
-        if (!cur) break;
+        // write-back: one HBM atomic per non-zero cell (D layout of the MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)).  Cell (rb + r, rb + c)
+        // of the triangle sits at tri64(rb) + rb + [rb r + r (r - 1) / 2 + c]: a wave-uniform base and a 32-bit offset per lane
+        const uint32_t rb = X0 * q.bwidth;
+        uint32_t* const Mb = q.M + (tri64((uint64_t)rb) + rb);
+        const uint32_t lim = q.N - rb;                                  // rows of the block inside the matrix (masks never hold an id beyond N: belt and braces)
+        // (the lane's part of the 48 offsets and conditions does not depend on the tile: seen through, it is computed once before the loop and kept — some
+        // hundred registers beside the 48 accumulators.  Behind the empty asm it is a few instructions per atomic, computed where it is used.)
+        uint32_t h4 = 4u * half, lc = l31;
+        asm volatile("" : "+v"(h4), "+v"(lc));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t row0 = (uint32_t)((r & 3) + 8 * (r >> 2)) + h4, row1 = row0 + 32u;
+            const uint32_t o0 = rb * row0 + row0 * (row0 - 1u) / 2u + lc, o1 = rb * row1 + row1 * (row1 - 1u) / 2u + lc;
+            const uint32_t v00 = (uint32_t)c00[r], v10 = (uint32_t)c10[r], v11 = (uint32_t)c11[r];
+            if (v00 && lc < row0 && row0 < lim) atomicAdd(Mb + o0, v00);
+            if (v10 && row1 < lim) atomicAdd(Mb + o1, v10);
+            if (v11 && lc < row0 && row1 < lim) atomicAdd(Mb + o1 + 32u, v11);
+        }
+        if (lane == 0 && q.touched) q.touched[tri32(X0) + X0] = 1;      // (all2all-sp scans only the tiles a call added to)
     }
 }
 
@@ -1239,6 +1273,7 @@ struct WParams {
     L2View l2;
 };
 constexpr int K1W_WAVES = 2;
+constexpr int K1W_MINW_FEW = 5;            // waves per SIMD the few-streams instantiation is compiled for (4 / 5 / 6 measured: DESIGN §8; 6 needs 52 bytes of scratch per lane)
 
 constexpr uint32_t L2_MIN_BLOCKS = 24;     // nodes with that many blocks take the second level (measured at 10 000 samples: 11 -> 21.9 ms, 24 -> 20.0; KMDB_L2_MIN moves it)
 constexpr uint32_t L2_NODE_GRAB = 16, L2_ENT_GRAB = 1024, L2_SUB = 16;   // node indices / entries a wave takes per device atomic, from one of L2_SUB cursors each
@@ -1277,14 +1312,18 @@ __host__ __device__ inline size_t k1w_core_bytes(uint32_t arena_cap, uint32_t e_
 __host__ __device__ inline size_t k1w_wave_bytes(uint32_t arena_cap, uint32_t e_cap, uint32_t chain_cap, uint32_t n_rows) {
     return k1w_core_bytes(arena_cap, e_cap, chain_cap) + rowtab_bytes(n_rows);
 }
+// The arrays of a fixed size come first: their addresses are the wave's base plus a constant, which the LDS instructions take as an immediate
+// offset — only the seven arrays whose place depends on the database (arena_cap, e_cap, chain_cap) cost a register each.  Same bytes as before
+// (k1w_core_bytes), every array aligned to its element.
 __device__ __forceinline__ K1WLds k1w_carve(unsigned char* p, uint32_t arena_cap, uint32_t e_cap, uint32_t chain_cap) {
     K1WLds L;
-    L.ent_mask = (unsigned long long*)p;  L.e_mask = L.ent_mask + arena_cap;  L.ch_last = L.e_mask + e_cap;  L.own_m0 = L.ch_last + chain_cap;
-    L.own_desc = L.own_m0 + 64;
-    L.ox_mask = L.own_desc + 64;
-    L.ch_node = (uint32_t*)(L.ox_mask + K1W_OXCAP);  L.own_po = L.ch_node + chain_cap;  L.st_w = L.own_po + 64;  L.queue = L.st_w + 64;
-    L.ent_blk = (uint16_t*)(L.queue + K1W_QCAP);  L.e_blk = L.ent_blk + arena_cap;  L.ch_len = L.e_blk + e_cap;  L.st_start = L.ch_len + chain_cap;
-    L.st_pre = L.st_start + 64;  L.ox_blk = L.st_pre + 64;
+    L.own_m0 = (unsigned long long*)p;  L.own_desc = L.own_m0 + 64;  L.ox_mask = L.own_desc + 64;
+    L.own_po = (uint32_t*)(L.ox_mask + K1W_OXCAP);  L.st_w = L.own_po + 64;  L.queue = L.st_w + 64;
+    L.st_start = (uint16_t*)(L.queue + K1W_QCAP);  L.st_pre = L.st_start + 64;  L.ox_blk = L.st_pre + 64;
+    static_assert((4 * (64 + 64 + K1W_QCAP)) % 8 == 0 && (2 * (64 + 64 + K1W_OXCAP)) % 8 == 0, "the 8-byte arrays behind the fixed part stay aligned");
+    L.ent_mask = (unsigned long long*)(L.ox_blk + K1W_OXCAP);  L.e_mask = L.ent_mask + arena_cap;  L.ch_last = L.e_mask + e_cap;
+    L.ch_node = (uint32_t*)(L.ch_last + chain_cap);
+    L.ent_blk = (uint16_t*)(L.ch_node + chain_cap);  L.e_blk = L.ent_blk + arena_cap;  L.ch_len = L.e_blk + e_cap;
     return L;
 }
 
@@ -1313,23 +1352,34 @@ __global__ void wrun_anc_kernel(const uint32_t* __restrict__ widx, uint32_t n_wi
 //   number of entries and the mask of the node's own last entry.  At the start of a run the chain is built from the root path of
 //   the slice's first node (a table made at upload): the lists of all its wide ancestors in one scan.
 // No node climbs parent links, and a list may have as many entries as there are blocks.
-__global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) {
+// ROWS / L2: the record path of the call (few streams; row mode; row mode with the second level), chosen by the host: an instantiation holds
+// neither the code nor the registers of the paths it does not take.
+// (WParams must stay the kernel's ONLY argument: kernarg_reread<WParams>() and PoolRef::k read it at offset 0 of the kernarg segment)
+// (few streams: pinned at five waves per SIMD — left to itself the allocator lands on either side of the 96 registers that five waves allow)
+template <bool ROWS, bool L2>
+__global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_eu(ROWS ? 4 : K1W_MINW_FEW, 8))) void k1w_kernel(const WParams q) {
+    static_assert(ROWS || !L2, "the second level runs in row mode only");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const uint32_t lane = lane_id();
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t wid = blockIdx.x * (blockDim.x >> 6) + wave;         // 1 or K1W_WAVES waves per workgroup, by the LDS a wave needs
     if (wid >= q.n_waves) return;
-    unsigned char* wbase = lds_raw + k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows) * wave;
+    unsigned char* wbase = lds_raw + k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, ROWS ? q.n_rows : 0u) * wave;
     const K1WLds L = k1w_carve(wbase, q.arena_cap, q.e_cap, q.chain_cap);
     RowTab RT{nullptr, nullptr, 0u};
-    if (q.n_rows) rowtab_init(RT, (uint32_t*)(wbase + k1w_core_bytes(q.arena_cap, q.e_cap, q.chain_cap)), q.n_rows, lane);
-    auto iswide = [&](uint32_t y) -> bool { return (q.widebits[y >> 6] >> (y & 63u)) & 1ull; };
+    if constexpr (ROWS) rowtab_init(RT, (uint32_t*)(wbase + k1w_core_bytes(q.arena_cap, q.e_cap, q.chain_cap)), q.n_rows, lane);
+    // the pool: what a record store reads is held, the rest is re-read from the parameter block where it is used (PoolRef)
+    PoolRef pv{};
+    pv.k = &((KARG(WParams))__builtin_amdgcn_kernarg_segment_ptr())->pool;
+    pv.kbits = q.pool.kbits; pv.dbits = q.pool.dbits; pv.pshift = q.pool.pshift;
+    if constexpr (ROWS) { pv.rec = q.pool.rec; pv.recw = q.pool.recw; } else { pv.wkey = q.pool.wkey; pv.wrec = q.pool.wrec; }
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     WaveArena A;
     arena_init(A, nullptr, 0u, 0u, wid + 64u, lane);
     uint32_t n_miss = 0;
 
     uint32_t l2_nodes = 0;
+    const uint32_t l2_min = L2 ? q.l2.min_blocks : 0u;
     uint32_t l2_gnext = 0, l2_gstock = 0, l2_enext = 0, l2_estock = 0;     // second level: the wave's stock of node indices and entries (wave-uniform)
     // record-parallel emission of the lanes in `on` (list of lane j: m entries from st_start[j]): a node with m blocks owns
     // m (m + 1) / 2 records (block pairs a >= b), one record per lane and step
@@ -1345,38 +1395,39 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                 // entry e of the node's list: the first prej from the chain list, the others from its row
                 auto cmask = [&](uint32_t e) -> unsigned long long { return e < prej ? L.e_mask[e] : L.ent_mask[stj + e - prej]; };
                 auto cblk = [&](uint32_t e) -> uint32_t { return e < prej ? (uint32_t)L.e_blk[e] : (uint32_t)L.ent_blk[stj + e - prej]; };
-                if (q.l2.on && mj >= q.l2.min_blocks) {
+                if constexpr (L2) if (mj >= l2_min) {
+                    KARG(WParams) ql = kernarg_reread<WParams>();                // (once per heavy node: the second level's arrays are read where used)
                     // second level: the node's entries instead of its records
                     const uint32_t sub = wid % L2_SUB;
                     if (l2_gstock == 0u) {
                         uint32_t b = 0;
-                        if (lane == 0) b = atomicAdd(&q.l2.cursors[sub * 16u], L2_NODE_GRAB);
+                        if (lane == 0) b = atomicAdd(&ql->l2.cursors[sub * 16u], L2_NODE_GRAB);
                         b = bcast(b, 0);
                         // the grabs of the L2_SUB cursors interleave (grab n of cursor k = indices [(n L2_SUB + k) GRAB, + GRAB)): the indices in use
                         // stay dense from 0 on as long as the cursors advance alike, and the tile jobs scan the bitmaps only that far
                         const uint32_t g0 = ((b / L2_NODE_GRAB) * L2_SUB + sub) * L2_NODE_GRAB;
-                        if (g0 + L2_NODE_GRAB <= q.l2.node_cap) { l2_gnext = g0; l2_gstock = L2_NODE_GRAB; }
+                        if (g0 + L2_NODE_GRAB <= ql->l2.node_cap) { l2_gnext = g0; l2_gstock = L2_NODE_GRAB; }
                     }
                     if (l2_estock < mj) {
                         uint32_t b = 0;
-                        if (lane == 0) b = atomicAdd(&q.l2.cursors[(L2_SUB + sub) * 16u], L2_ENT_GRAB);
+                        if (lane == 0) b = atomicAdd(&ql->l2.cursors[(L2_SUB + sub) * 16u], L2_ENT_GRAB);
                         b = bcast(b, 0);
-                        if (b + L2_ENT_GRAB <= q.l2.ent_cap / L2_SUB) { l2_enext = sub * (q.l2.ent_cap / L2_SUB) + b; l2_estock = L2_ENT_GRAB; }
+                        if (b + L2_ENT_GRAB <= ql->l2.ent_cap / L2_SUB) { l2_enext = sub * (ql->l2.ent_cap / L2_SUB) + b; l2_estock = L2_ENT_GRAB; }
                         else l2_estock = 0u;
                     }
                     if (l2_gstock == 0u || l2_estock < mj) {             // out of indices or entries: the call is repeated with larger arrays
-                        if (lane == 0) atomicOr(&q.pool.counters[KCTR_L2_OVERFLOW], 1u);
+                        if (lane == 0) atomicOr(&ql->pool.counters[KCTR_L2_OVERFLOW], 1u);
                         continue;
                     }
                     const uint32_t g = l2_gnext;
                     ++l2_gnext; --l2_gstock;
                     for (uint32_t e = lane; e < mj; e += WAVE) {
                         const uint32_t idx = l2_enext + e, blk = cblk(e);
-                        q.l2.ent_g[idx] = g; q.l2.ent_blk[idx] = (uint16_t)blk; q.l2.ent_mask[idx] = cmask(e);
-                        atomicOr(&q.l2.bitmap[(size_t)blk * q.l2.W + (g >> 6)], 1ull << (g & 63u));
+                        ql->l2.ent_g[idx] = g; ql->l2.ent_blk[idx] = (uint16_t)blk; ql->l2.ent_mask[idx] = cmask(e);
+                        atomicOr(&ql->l2.bitmap[(size_t)blk * ql->l2.W + (g >> 6)], 1ull << (g & 63u));
                     }
                     l2_enext += mj; l2_estock -= mj;
-                    if (lane == 0) q.l2.node_w[g] = wj;
+                    if (lane == 0) ql->l2.node_w[g] = wj;
                     ++l2_nodes;
                     continue;
                 }
@@ -1398,8 +1449,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                         if (a == b) FY = FX;
                         stream = tri32(X) + Y;
                     }
-                    if (q.n_rows) row_emit(A, q.pool, RT, rec_on, X, FX, FY, wj, stream, lane, lt_mask);
-                    else wide_emit(A, q.pool, rec_on, FX, FY, wj, stream, lane, lt_mask);
+                    rec_emit<ROWS>(A, pv, RT, rec_on, X, FX, FY, wj, stream, lane, lt_mask);
                 }
             }
             on = on && m < K1W_HEAVY;
@@ -1439,8 +1489,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
             }
             // few streams: the step's records go to the wide pool in arrival order (one reservation for all lanes); many: to
             // the chunks of their block rows
-            if (q.n_rows) row_emit(A, q.pool, RT, rec_on, X, FX, diag ? FX : FY, ww, stream, lane, lt_mask);
-            else wide_emit(A, q.pool, rec_on, FX, diag ? FX : FY, ww, stream, lane, lt_mask);
+            rec_emit<ROWS>(A, pv, RT, rec_on, X, FX, diag ? FX : FY, ww, stream, lane, lt_mask);
         }
         lds_sync();
     };
@@ -1451,31 +1500,33 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
     // single counter would be a hot address: same-address device atomics run at some ten million per second).
     for (;;) {
         uint32_t run = 0;
-        const uint32_t n_cls = q.n_waves < K1W_CTRS ? q.n_waves : K1W_CTRS;       // classes of runs = counters in use (every class needs a wave)
-        if (lane == 0) run = atomicAdd(&q.run_ctr[(wid % n_cls) * 16u], 1u);
+        KARG(WParams) qh = kernarg_reread<WParams>();                    // (once per run)
+        const uint32_t n_cls = qh->n_waves < K1W_CTRS ? qh->n_waves : K1W_CTRS;       // classes of runs = counters in use (every class needs a wave)
+        if (lane == 0) run = atomicAdd(&qh->run_ctr[(wid % n_cls) * 16u], 1u);
         run = bcast(run, 0) * n_cls + wid % n_cls;
-        if (run >= q.n_runs) break;
-        const uint32_t kb = run * q.run_nodes;
-        const uint32_t ke = q.n_wide - kb < q.run_nodes ? q.n_wide : kb + q.run_nodes;
+        if (run >= qh->n_runs) break;
+        const uint32_t kb = run * qh->run_nodes;
+        const uint32_t ke = qh->n_wide - kb < qh->run_nodes ? qh->n_wide : kb + qh->run_nodes;
         // ---- the chain at the start of the run: the wide nodes on the root path of the run's first node.  Wide nodes are a
         // suffix of a root path; the topmost one starts from its (narrow) parent's (blocks, masks).
         {
-            for (uint32_t e = lane; e < q.chain_cap; e += WAVE) L.ch_node[e] = 0xFFFFFFFFu;
-            const uint32_t d = q.seg_anc_n[run];
+            KARG(WParams) qr = kernarg_reread<WParams>();                // (once per run: read where used, not held)
+            for (uint32_t e = lane; e < qr->chain_cap; e += WAVE) L.ch_node[e] = 0xFFFFFFFFu;
+            const uint32_t d = qr->seg_anc_n[run];
             LSum carry = lsum_none();
             bool started = false;
             for (uint32_t cb = 0; cb < d; cb += WAVE) {
                 const uint32_t j = cb + lane;
                 const bool on = j < d;
-                const uint32_t a = on ? q.seg_anc[(size_t)run * q.chain_cap + j] : 0u;
-                const unsigned long long wb = __ballot(on && iswide(a));
+                const uint32_t a = on ? qr->seg_anc[(size_t)run * qr->chain_cap + j] : 0u;
+                const unsigned long long wb = __ballot(on && ((qr->widebits[a >> 6] >> (a & 63u)) & 1ull));
                 if (!started && !wb) continue;
                 const uint32_t t = started ? 0u : (uint32_t)__builtin_ctzll(wb);
                 if (!started) {
                     const uint32_t at = bcast(a, t);
-                    if (q.parent[at] >= 0) {
-                        const uint32_t fb = q.fn_blk[at];
-                        const ulonglong2 fm = q.fn_mask[at];
+                    if (qr->parent[at] >= 0) {
+                        const uint32_t fb = qr->fn_blk[at];
+                        const ulonglong2 fm = qr->fn_mask[at];
                         carry = lsum_of_fn(fb, fm);
                         if (lane == 0) {
                             if (carry.c >= 1u) { L.e_blk[0] = (uint16_t)(fb & 0xFFFFu); L.e_mask[0] = fm.x; }
@@ -1485,13 +1536,13 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                     started = true;
                 }
                 const bool act = on && lane >= t;
-                const uint32_t info = act ? q.p0_info[a] : 0u;
+                const uint32_t info = act ? qr->p0_info[a] : 0u;
                 const uint32_t np = info >> 16, b0 = info & 0xFFFFu;
-                const unsigned long long m0 = act ? q.p0_mask[a] : 0ull;
-                const uint32_t po = np > 1u ? q.pair_ofs[a] : 0u;
+                const unsigned long long m0 = act ? qr->p0_mask[a] : 0ull;
+                const uint32_t po = np > 1u ? qr->pair_ofs[a] : 0u;
                 uint32_t lb = b0;
                 unsigned long long lm = m0;
-                if (np > 1u) { lb = q.pair_blk[po + np - 2u]; lm = q.pair_mask[po + np - 2u]; }
+                if (np > 1u) { lb = qr->pair_blk[po + np - 2u]; lm = qr->pair_mask[po + np - 2u]; }
                 LSum S = np ? LSum{lm, np, b0, lb} : lsum_none();
                 if (lane == t) S = lsum_merge(carry, S);
 #pragma unroll
@@ -1505,7 +1556,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                 const uint32_t idx0 = Pp.c - (seam ? 1u : 0u);
                 if (act && np) {
                     if (!seam) { L.e_blk[idx0] = (uint16_t)b0; L.e_mask[idx0] = m0; }
-                    for (uint32_t p = 1; p < np; ++p) { L.e_blk[idx0 + p] = q.pair_blk[po + p - 1u]; L.e_mask[idx0 + p] = q.pair_mask[po + p - 1u]; }
+                    for (uint32_t p = 1; p < np; ++p) { L.e_blk[idx0 + p] = qr->pair_blk[po + p - 1u]; L.e_mask[idx0 + p] = qr->pair_mask[po + p - 1u]; }
                 }
                 lds_sync();
                 if (seam) atomicOr(&L.e_mask[idx0], m0);
@@ -1519,28 +1570,29 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
         for (uint32_t k0 = kb; k0 < ke; k0 += WAVE) {
             const uint32_t nv = ke - k0 < (uint32_t)WAVE ? ke - k0 : (uint32_t)WAVE;
             const bool valid = lane < nv;
-            const uint32_t node = valid ? q.widx[k0 + lane] : 0u;
-            const uint32_t nlv = valid ? q.nl[node] : 0u;
-            const uint32_t wv = valid ? q.w[node] : 0u;
-            const bool act = valid && wv != 0 && nlv >= 2u && node >= q.emit_lo && node < q.emit_hi;
-            const int32_t par = valid ? q.parent[node] : -1;
-            const uint32_t dep = valid ? (uint32_t)(q.dflag[node] & 0x7FFFu) : 0x7FFFu;
-            const uint32_t info = valid ? q.p0_info[node] : 0u;
+            KARG(WParams) qb = kernarg_reread<WParams>();                // (once per batch: the node arrays' pointers are read where used, not held)
+            const uint32_t node = valid ? qb->widx[k0 + lane] : 0u;
+            const uint32_t nlv = valid ? qb->nl[node] : 0u;
+            const uint32_t wv = valid ? qb->w[node] : 0u;
+            const bool act = valid && wv != 0 && nlv >= 2u && node >= qb->emit_lo && node < qb->emit_hi;
+            const int32_t par = valid ? qb->parent[node] : -1;
+            const uint32_t dep = valid ? (uint32_t)(qb->dflag[node] & 0x7FFFu) : 0x7FFFu;
+            const uint32_t info = valid ? qb->p0_info[node] : 0u;
             const uint32_t np = info >> 16, b0 = info & 0xFFFFu;
-            const unsigned long long m0 = valid ? q.p0_mask[node] : 0ull;
+            const unsigned long long m0 = valid ? qb->p0_mask[node] : 0ull;
             // (every load that needs only `node` or `par` is requested here, whether its value will be used or not: the batch start is a chain of
             // dependent round trips — node, its fields, pair_ofs, the pairs; the parent's flags, then fn_* or wide_base — at four waves per SIMD.
             // pair_ofs of a node without further pairs and fn_* of a node with a wide parent were never written: what is read is not used.)
-            const uint32_t po_raw = valid ? q.pair_ofs[node] : 0u;
-            const uint32_t fnb_raw = valid ? q.fn_blk[node] : 0u;
-            const ulonglong2 fnm_raw = valid ? q.fn_mask[node] : make_ulonglong2(0ull, 0ull);
+            const uint32_t po_raw = valid ? qb->pair_ofs[node] : 0u;
+            const uint32_t fnb_raw = valid ? qb->fn_blk[node] : 0u;
+            const ulonglong2 fnm_raw = valid ? qb->fn_mask[node] : make_ulonglong2(0ull, 0ull);
             const uint32_t pw = (valid && par >= 0) ? (uint32_t)par >> 6 : 0u;
-            const unsigned long long pwbits = (valid && par >= 0) ? q.widebits[pw] : 0ull;
-            const uint32_t pwbase = (valid && par >= 0) ? q.wide_base[pw] : 0u;
+            const unsigned long long pwbits = (valid && par >= 0) ? qb->widebits[pw] : 0ull;
+            const uint32_t pwbase = (valid && par >= 0) ? qb->wide_base[pw] : 0u;
             const uint32_t po = np > 1u ? po_raw : 0u;
             uint32_t lb = b0;
             unsigned long long lm = m0;
-            if (np > 1u) { lb = q.pair_blk[po + np - 2u]; lm = q.pair_mask[po + np - 2u]; }
+            if (np > 1u) { lb = qb->pair_blk[po + np - 2u]; lm = qb->pair_mask[po + np - 2u]; }
             // ---- where the parent's list comes from
             uint32_t base = WB_NONE, link = 0, pre0 = 0;
             LSum Pb = lsum_none();
@@ -1553,7 +1605,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                     if (prank >= k0) { base = WB_LANE; link = prank - k0; }
                     else {
                         base = WB_CHAIN; link = dep - 2u;
-                        if (link < q.chain_cap && L.ch_node[link] == (uint32_t)par) {
+                        if (link < qb->chain_cap && L.ch_node[link] == (uint32_t)par) {
                             const uint32_t cl = L.ch_len[link];
                             Pb = LSum{L.ch_last[link], cl, 0u, cl ? (uint32_t)L.e_blk[cl - 1u] : BLK_NONE};
                             pre0 = cl ? cl - 1u : 0u;              // all but the last entry of the chain node's list are taken from the chain list where they are
@@ -1591,7 +1643,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                 const uint32_t xincl = wave_incl_scan(nx, lane);
                 const uint32_t x0 = xincl - nx;
                 const bool fits = nx && xincl <= K1W_OXCAP;
-                if (fits) for (uint32_t t = 0; t < nx; ++t) { L.ox_blk[x0 + t] = q.pair_blk[po + t]; L.ox_mask[x0 + t] = q.pair_mask[po + t]; }
+                if (fits) for (uint32_t t = 0; t < nx; ++t) { L.ox_blk[x0 + t] = qb->pair_blk[po + t]; L.ox_mask[x0 + t] = qb->pair_mask[po + t]; }
                 // (a walk over the in-batch parents reads one descriptor and one mask per node: the walks are chains of dependent LDS reads,
                 // and five separate arrays made every step five of them — profiles/r05_j5: rows were 36 % of the kernel)
                 L.own_desc[lane] = (unsigned long long)(b0 & 0xFFFFu) | ((unsigned long long)(link & 0xFFFFu) << 16) | ((unsigned long long)(fits ? x0 : 0xFFFFu) << 32) |
@@ -1605,10 +1657,10 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
             while (fin < nv) {
                 const uint32_t c = (lane >= fin && need) ? slen : 0u;
                 const uint32_t incl = wave_incl_scan(c, lane);
-                const unsigned long long over = __ballot(incl > q.arena_cap);
+                const unsigned long long over = __ballot(incl > qb->arena_cap);
                 uint32_t hi = over ? (uint32_t)__builtin_ctzll(over) : (uint32_t)WAVE;
-                if (hi <= fin) { if (lane == 0) atomicOr(&q.pool.counters[KCTR_LIST_OVERFLOW], 1u); hi = fin + 1u; }     // a single list longer than the arena: cannot happen
-                const bool on = need && lane >= fin && lane < hi && incl <= q.arena_cap;
+                if (hi <= fin) { if (lane == 0) atomicOr(&pool_cold(pv)->counters[KCTR_LIST_OVERFLOW], 1u); hi = fin + 1u; }     // a single list longer than the arena: cannot happen
+                const bool on = need && lane >= fin && lane < hi && incl <= qb->arena_cap;
                 const uint32_t start = incl - c;
                 if (on) {
                     // fill the row right to left: own pairs, the in-batch parents' pairs, then the base
@@ -1631,7 +1683,8 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                             if (yox != 0xFFFFu) for (uint32_t t = ynx; t-- > 0u;) rpush(L.ox_blk[yox + t], L.ox_mask[yox + t]);
                             else {
                                 const uint32_t ypo = L.own_po[y];
-                                for (uint32_t t = ynx; t-- > 0u;) rpush(q.pair_blk[ypo + t], q.pair_mask[ypo + t]);
+                                KARG(WParams) qp = kernarg_reread<WParams>();        // (the rare node whose further pairs found no room in ox_*)
+                                for (uint32_t t = ynx; t-- > 0u;) rpush(qp->pair_blk[ypo + t], qp->pair_mask[ypo + t]);
                             }
                         }
                         if (ynp) rpush((uint32_t)dsc & 0xFFFFu, ym0);
@@ -1666,7 +1719,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
                 }
                 uint32_t later = (uint32_t)__shfl_down((int)mdep, 1, WAVE);
                 if (lane == (uint32_t)WAVE - 1u) later = 0xFFFFFFFFu;
-                if (valid && dep < later && dep - 1u < q.chain_cap) { L.ch_node[dep - 1u] = node; L.ch_len[dep - 1u] = (uint16_t)len; L.ch_last[dep - 1u] = S.lm; }
+                if (valid && dep < later && dep - 1u < qb->chain_cap) { L.ch_node[dep - 1u] = node; L.ch_len[dep - 1u] = (uint16_t)len; L.ch_last[dep - 1u] = S.lm; }
                 // the last node's list becomes the chain list: its first entries are there already, its row follows them
                 const uint32_t ll = bcast(slen, nv - 1u), ls = bcast(last_start, nv - 1u), lp = bcast(pre, nv - 1u);
                 for (uint32_t e = lane; e < ll; e += WAVE) { L.e_blk[lp + e] = L.ent_blk[ls + e]; L.e_mask[lp + e] = L.ent_mask[ls + e]; }
@@ -1674,10 +1727,10 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) void k1w_kernel(const WParams q) 
             }
         }
     }
-    arena_finish(A, q.pool, lane);
-    if (q.n_rows) rowtab_finish(RT, q.pool, lane);
-    if (lane == 0 && n_miss) atomicAdd(&q.pool.counters[KCTR_SLOW], n_miss);
-    if (lane == 0 && l2_nodes) atomicAdd(&q.pool.counters[KCTR_L2_NODES], l2_nodes);
+    arena_finish(A, pv, lane);
+    if constexpr (ROWS) rowtab_finish(RT, pv, lane);
+    if (lane == 0 && n_miss) atomicAdd(&pool_cold(pv)->counters[KCTR_SLOW], n_miss);
+    if constexpr (L2) if (lane == 0 && l2_nodes) atomicAdd(&pool_cold(pv)->counters[KCTR_L2_NODES], l2_nodes);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2801,6 +2854,20 @@ PoolView pool_view(const kmdb_db* db, bool dense) {
 void free_and_null(void** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
 #define FREE_NULL(x) free_and_null((void**)&(x))
 
+// ---- the emit kernels' instantiations: ONE place maps a handle's record path to the function that is configured, queried and launched
+struct K1nPick { void (*fn)(const NParams); const char* name; };
+K1nPick k1n_pick(int mode, int minw, bool rows) {
+    if (mode == 2) return rows ? K1nPick{k1n_kernel<2, 4, true>, "k1n<2, rows>"} : K1nPick{k1n_kernel<2, 4, false>, "k1n<2, no rows>"};
+    if (mode == 0) return rows ? K1nPick{k1n_kernel<0, 4, true>, "k1n<0, rows>"} : K1nPick{k1n_kernel<0, 4, false>, "k1n<0, no rows>"};
+    if (minw >= 4) return rows ? K1nPick{k1n_kernel<1, 4, true>, "k1n<1, 4 waves, rows>"} : K1nPick{k1n_kernel<1, 4, false>, "k1n<1, 4 waves, no rows>"};
+    return rows ? K1nPick{k1n_kernel<1, 3, true>, "k1n<1, 3 waves, rows>"} : K1nPick{k1n_kernel<1, 3, false>, "k1n<1, 3 waves, no rows>"};
+}
+struct K1wPick { void (*fn)(const WParams); const char* name; };
+K1wPick k1w_pick(bool rows, bool l2) {
+    if (!rows) return K1wPick{k1w_kernel<false, false>, "k1w<no rows, no L2>"};
+    return l2 ? K1wPick{k1w_kernel<true, true>, "k1w<rows, L2>"} : K1wPick{k1w_kernel<true, false>, "k1w<rows, no L2>"};
+}
+
 constexpr uint32_t K1W_MAX_WAVES = 8192;
 constexpr uint32_t K1W_RUN_NODES = 256;     // wide nodes per run of a wave (round-robin: heavy nodes sit together in the DFS order)
 struct U32toU64 { __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; } };
@@ -3368,13 +3435,13 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         // (mode 1 holds 48 accumulator registers beside the narrow kernel's 95: three waves per SIMD without spills, or four with 84 bytes of
         // scratch per lane — KMDB_K1N_MINW=4, A/B)
         static const int minw = getenv("KMDB_K1N_MINW") ? atoi(getenv("KMDB_K1N_MINW")) : 3;
-        const void* fn = db->k1n_mode == 2 ? (const void*)k1n_kernel<2, 4> : db->k1n_mode == 1 ? (minw >= 4 ? (const void*)k1n_kernel<1, 4> : (const void*)k1n_kernel<1, 3>) : (const void*)k1n_kernel<0, 4>;
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // the instantiation of the call's record path: the attribute and the launch take the same function
+        const K1nPick pick = k1n_pick(db->k1n_mode, minw, row_mode);
+        HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const dim3 grid((q.n_segs + waves - 1) / waves), block(WAVE * waves);
-        if (db->k1n_mode == 2) hipLaunchKernelGGL((k1n_kernel<2, 4>), grid, block, lds, st, q);
-        else if (db->k1n_mode == 0) hipLaunchKernelGGL((k1n_kernel<0, 4>), grid, block, lds, st, q);
-        else if (minw >= 4) hipLaunchKernelGGL((k1n_kernel<1, 4>), grid, block, lds, st, q);
-        else hipLaunchKernelGGL((k1n_kernel<1, 3>), grid, block, lds, st, q);
+        if (!db->have_counts && getenv("KMDB_VERBOSE"))
+            fprintf(stderr, "[kmdb] narrow kernel: %u slices, %zu B of LDS per wave, %u per workgroup, instantiation %s\n", q.n_segs, wave_lds, waves, pick.name);
+        hipLaunchKernelGGL(pick.fn, grid, block, lds, st, q);
         HIP_TRY(hipGetLastError());
     }
     if (stage("narrow emit")) return 1;
@@ -3497,14 +3564,18 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         q.n_rows = row_mode ? db->NB : 0u;
         const size_t wave_lds = k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows);
         const uint32_t waves = wave_lds * K1W_WAVES <= (size_t)(64u << 10) ? (uint32_t)K1W_WAVES : 1u;
-        HIP_TRY(hipFuncSetAttribute((const void*)k1w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
+        // the instantiation of the call's record path: the attribute, the occupancy query and the launch take the same function
+        const K1wPick pick = k1w_pick(row_mode, db->l2_on);
+        HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
         // As many waves as the chip holds at once, each with an equal share of the runs (dealt round-robin): with more, the waves
         // beyond the first round start when the first ones end, and all take equally long — 1.6 rounds cost 2 (measured at 10 000
         // samples: 4096 waves at 10 per CU took 8.8 ms, of which every wave ran 4.4).
-        if (!db->k1w_slots) {
+        // (the count is kept on the handle with the instantiation it was asked for: KMDB_L2 may change between the calls of a handle)
+        if (!db->k1w_slots || db->k1w_slots_fn != (const void*)pick.fn) {
             int per_cu = 0, dev = 0;
             hipDeviceProp_t prop;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k1w_kernel, (int)(WAVE * waves), wave_lds * waves));
+            db->k1w_slots = 0; db->k1w_slots_fn = (const void*)pick.fn;
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pick.fn, (int)(WAVE * waves), wave_lds * waves));
             HIP_TRY(hipGetDevice(&dev));
             HIP_TRY(hipGetDeviceProperties(&prop, dev));
             db->k1w_slots = (uint32_t)std::max(1, per_cu) * waves * (uint32_t)std::max(1, prop.multiProcessorCount);
@@ -3513,9 +3584,9 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         q.run_ctr = db->run_ctr;
         if (const char* e = getenv("KMDB_K1W_WAVES")) q.n_waves = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(db->k1w_waves, q.n_runs), (uint32_t)atoi(e)));
         if (!db->have_counts && getenv("KMDB_VERBOSE"))
-            fprintf(stderr, "[kmdb] wide kernel: %u wide nodes in %u runs, %u waves (%u fit the chip, %zu B of LDS per wave, %u per workgroup)\n", n_wide, q.n_runs, q.n_waves,
-                    db->k1w_slots, wave_lds, waves);
-        hipLaunchKernelGGL(k1w_kernel, dim3((q.n_waves + waves - 1) / waves), dim3(WAVE * waves), wave_lds * waves, st, q);
+            fprintf(stderr, "[kmdb] wide kernel: %u wide nodes in %u runs, %u waves (%u fit the chip, %zu B of LDS per wave, %u per workgroup), instantiation %s\n", n_wide,
+                    q.n_runs, q.n_waves, db->k1w_slots, wave_lds, waves, pick.name);
+        hipLaunchKernelGGL(pick.fn, dim3((q.n_waves + waves - 1) / waves), dim3(WAVE * waves), wave_lds * waves, st, q);
         if (db->l2_on) {
             // rank directories, list offsets, lists, and the tile joins adding into M (a tile whose blocks have no list leaves at once)
             const uint32_t NB = db->NB, W = db->l2_node_cap / 64u;

@@ -153,6 +153,7 @@ struct kmdb_db {
     size_t rs_tmp_bytes = 0;
     uint64_t sorted_cap = 0;                           // records the sorted arrays (swkey / swrec) hold
     uint32_t last_n_rowjobs = 0, last_n_sorted = 0, last_n_k2jobs = 0, k1w_waves = 0, k1w_slots = 0;   // (k1w_waves: most the pools are sized for; k1w_slots: waves the chip holds at once)
+    const void* k1w_slots_fn = nullptr;                // the wide kernel's instantiation k1w_slots was asked for
     uint32_t* cs_rows = nullptr;                       // two-pass sort: row starts / first workgroup / first table entry, [3][NB + 1]
     uint32_t *cs_hist = nullptr, *cs_offs = nullptr;   // counting sort of the wide pool: [stream][block] counts / offsets (+ total)
     void* cs_tmp = nullptr;
