@@ -30,6 +30,9 @@ extern "C" {
 #define KMDB_HAS_SAMPLED_ROWS 1
 /* So is the sparse, filtered form of db2db (kmdb_db2db_sparse_filtered, kmdb_db2db_stats_get): two more entry points, the version stays 8. */
 #define KMDB_HAS_DB2DB_SPARSE 1
+/* And the sparse, filtered form of new2all (kmdb_new2all_batch_sparse_filtered and its relatives, kmdb_new2all_sparse_stats_get): seven more
+ * entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_NEW2ALL_SPARSE_FILTERED 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -298,7 +301,8 @@ int    kmdbh_metric_id(const char* name);
 int  kmdb_new2all_batch(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq,
                         uint32_t* out_dense, const kmdb_opts* opts);
 /* Replaces one2all_sp (similarity_calculator.cpp:929-1051; call site console_new2all.cpp:78):
- * row q = ascending (sample_id, count) pairs with count > 0. */
+ * row q = ascending (sample_id, count) pairs with count > 0.  = kmdb_new2all_batch_sparse_filtered without bounds: the rows are compacted
+ * on the device, neither the nq x N rectangle nor its zeros cross PCIe.  (Also serves a query shard: its partial rows.) */
 int  kmdb_new2all_batch_sparse(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq,
                                kmdb_sparse_rows* out, const kmdb_opts* opts);
 /* The same with the query-side loader on the device: replaces, per query, the k-mer extraction of
@@ -327,6 +331,47 @@ int  kmdb_new2all_batch_device(kmdb_db* db, const uint64_t* const* kmers, const 
 int  kmdb_new2all_batch_seq_alphabet_device(kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
                                             double start_fraction, int32_t alphabet, void* out_dev, uint64_t* out_kmer_counts,
                                             const kmdb_opts* opts);
+
+/* Replaces one2all_sp FOLLOWED BY the CombinedFilter of the query's row, which is how the reference writes `new2all -sparse` (console_new2all.cpp:76-78:
+ * one2all_sp per query; :130-148: the row's cells through CombinedFilter(metrics, queryKmersCounts, db.getSampleKmersCount(), kmerLength)).  The rows
+ * of the batch are accumulated in HBM as for kmdb_new2all_batch_device and compacted there: one wave per segment of 2048 columns of a row, the
+ * bounds — widened by a safety margin, as in kmdb_all2all_sparse_filtered — applied before anything leaves the device, the remaining cells decided on
+ * the host with kmdbh_metric.  Only the row pointers and 8 bytes per device-kept cell cross PCIe; the call holds the whole batch's nq x N x 4 bytes
+ * on the device.
+ * out: n_rows = nq; row q lists (col, val) with val > 0, 0 <= col < n_samples, ascending col.
+ * In every measure a = the QUERY's k-mer count — counts[q], its number of unique k-mers, truncated to uint32 like the reference's num_kmers_t —
+ * and b = sample_kmers[col], the database sample's: the order of the reference's CombinedFilter; mash-query tells the two apart.
+ * measure >= 0 fills out->measure per kept cell (kmdbh_metric), -1 leaves it NULL.  n_filters == 0 with measure < 0 keeps every non-zero cell and
+ * allows a NULL sample_kmers; filters or a measure need it.
+ * Refused before any device work, under the entry point's name: a NULL handle or out, filters or a measure without sample_kmers, an unknown metric or
+ * measure, more than 12 bounds, a handle without hashtables, and a QUERY SHARD handle (kmdb_db_upload_query_shard): its cells are partial sums and
+ * so are its counts — sum the shards' rows (kmdb_new2all_batch_device) and compact them with kmdb_new2all_rows_sparse_device, or use the node entry. */
+int  kmdb_new2all_batch_sparse_filtered(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                        size_t n_filters, const uint32_t* sample_kmers /* [N] */, int measure /* KMDB_METRIC_* or -1 */,
+                                        kmdb_sparse_rows* out, const kmdb_opts* opts);
+/* The same with the query-side loader on the device (kmdb_new2all_batch_seq_alphabet): a = out_kmer_counts[q], the device extractor's unique count. */
+int  kmdb_new2all_batch_seq_alphabet_sparse_filtered(kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                     double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                     const uint32_t* sample_kmers /* [N] */, int measure, kmdb_sparse_rows* out,
+                                                     uint64_t* out_kmer_counts, const kmdb_opts* opts);
+/* The compaction alone, on rows the CALLER accumulated (kmdb_new2all_batch*_device, the sum over query shards, a rank's chunk after a reduce-scatter):
+ * the flat range [cell_lo, cell_hi) of the row-major nq x N rectangle, cell q * N + s = query q, sample s; rows_dev points at cell `cell_lo`, as
+ * cells_dev of kmdb_sparse_from_dense_device does (the whole batch is {0, nq * N}).  out has all nq rows; rows outside the range are empty and a row
+ * cut by a range end lists only its cells inside, so the outputs of consecutive ranges concatenate row by row (ascending columns).
+ * query_kmers: [nq] uint32 in host memory, needed with filters or a measure.  The cells are complete sums here, so any handle of the database serves,
+ * a query shard included.  Also refused: cell_lo > cell_hi, cell_hi > nq * N.  The stream note of kmdb_sparse_from_dense_device applies: the call
+ * reads rows_dev on opts->stream (the handle's own when NULL) and does not order itself after the caller's producer. */
+int  kmdb_new2all_rows_sparse_device(kmdb_db* db, const void* rows_dev, size_t nq, uint64_t cell_lo, uint64_t cell_hi,
+                                     const uint32_t* query_kmers /* [nq], host */, const kmdb_cell_filter* filters, size_t n_filters,
+                                     const uint32_t* sample_kmers /* [N] */, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
+typedef struct kmdb_new2all_sparse_stats {   /* the LAST sparse new2all call on the handle / the node */
+    uint64_t cells;                /* cells in the compacted range (node: summed over the devices) */
+    uint64_t nnz_device;           /* cells that passed the widened bounds and left HBM */
+    uint64_t nnz;                  /* cells returned after the exact decision on the host */
+    uint64_t d2h_bytes;            /* result bytes copied to the host: 8 (nq + 1) + 8 nnz_device per compaction */
+    double   compact_ms;           /* HIP events around count + scan + compact (node: the slowest device) */
+} kmdb_new2all_sparse_stats;
+int  kmdb_new2all_sparse_stats_get(const kmdb_db* db, kmdb_new2all_sparse_stats* out);
 
 /* Replaces SimilarityCalculator::db2db_sp(db_row, db_col, SparseMatrix&, bubbles) (similarity_calculator.cpp:1225-1540),
  * the off-diagonal cell of the all2all-parts grid (call sites console_all2all_parts.cpp:180,226): both databases
@@ -440,6 +485,21 @@ int  kmdb_node_new2all_batch_seq_alphabet(kmdb_node* node, const char* const* se
                                           const kmdb_opts* opts);
 int  kmdb_node_new2all_batch_sparse(kmdb_node* node, const uint64_t* const* kmers, const size_t* counts, size_t nq, kmdb_sparse_rows* out,
                                     const kmdb_opts* opts);
+/* = kmdb_new2all_batch_sparse_filtered / kmdb_new2all_batch_seq_alphabet_sparse_filtered over the query shards of the node (console_new2all.cpp:76-78,
+ * 130-148 over the GPUs of a node; a node of any other partition is refused under the entry point's name).  The rows meet as for
+ * kmdb_node_new2all_batch; then every device compacts ITS OWN chunk of the reduce-scatter (the whole buffer with one device) on its own stream —
+ * the cells are complete sums there, so the widened bounds apply —, the parts are concatenated row by row on the host and the exact decision runs
+ * once.  Sequence entry: a query's count is the sum over the shards, complete only once every device has reported, so its compaction is a second
+ * pass over the devices while the chunks are still resident.  kmdb_node_new2all_batch_sparse is the k-mer entry without bounds. */
+int  kmdb_node_new2all_batch_sparse_filtered(kmdb_node* node, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                             size_t n_filters, const uint32_t* sample_kmers /* [N] */, int measure, kmdb_sparse_rows* out,
+                                             const kmdb_opts* opts);
+int  kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(kmdb_node* node, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                          double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                          const uint32_t* sample_kmers /* [N] */, int measure, kmdb_sparse_rows* out,
+                                                          uint64_t* out_kmer_counts, const kmdb_opts* opts);
+/* the last sparse new2all call on the node: cells, nnz_device and d2h_bytes summed over the devices, the slowest device's compact_ms */
+int  kmdb_node_new2all_sparse_stats_get(const kmdb_node* node, kmdb_new2all_sparse_stats* out);
 
 /* ---------------------------------------------------------------------------------------
  * Host-side helpers of the front-end (no GPU needed).  They mirror the reference's loader

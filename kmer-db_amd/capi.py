@@ -79,6 +79,10 @@ class _Db2dbStats(C.Structure):
                 ("compact_ms", C.c_double)]
 
 
+class _New2allSparseStats(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
+
+
 FLAG_FORCE_GLOBAL_ATOMICS = 1
 FLAG_FORCE_DIRECT = 2
 FLAG_FORCE_TILE = 4
@@ -100,6 +104,8 @@ EXPORTS = [
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
     "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
     "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
+    "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
+    "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
 ]
 
 
@@ -169,6 +175,16 @@ def lib():
     L.kmdb_db2db_sparse_filtered.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Sparse),
                                              C.POINTER(_Opts)]
     L.kmdb_db2db_stats_get.argtypes = [C.c_void_p, C.POINTER(_Db2dbStats)]
+    for name in ("kmdb_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_sparse_filtered"):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
+                                     C.POINTER(_Sparse), C.POINTER(_Opts)]
+    for name in ("kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered"):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32, C.POINTER(_CellFilter),
+                                     C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_new2all_rows_sparse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p,
+                                                  C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_new2all_sparse_stats_get.argtypes = [C.c_void_p, C.POINTER(_New2allSparseStats)]
+    L.kmdb_node_new2all_sparse_stats_get.argtypes = [C.c_void_p, C.POINTER(_New2allSparseStats)]
     L.kmdb_new2all_batch_seq.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int,
                                          C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_new2all_batch_seq_alphabet.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
@@ -375,6 +391,34 @@ def _filters(filters):
 def _criterion(criterion):
     """a criterion name, or the raw KMDB_METRIC_* number (passed on unchecked: the library refuses what it does not know)"""
     return METRICS.index(criterion) if isinstance(criterion, str) else int(criterion)
+
+
+def _u32(a):
+    return None if a is None else np.ascontiguousarray(a, np.uint32)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _kmer_queries(queries):
+    """sorted unique k-mer arrays -> (keepalive, pointer array, count array, nq)"""
+    qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
+    nq = len(qs)
+    return qs, (C.c_void_p * max(nq, 1))(*[q.ctypes.data for q in qs]), (C.c_size_t * max(nq, 1))(*[q.size for q in qs]), nq
+
+
+def _text_queries(seqs):
+    bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    nq = len(bs)
+    return bs, (C.c_char_p * max(nq, 1))(*bs), (C.c_size_t * max(nq, 1))(*[len(b) for b in bs]), nq
+
+
+def _rows_out(raw):
+    try:
+        return SparseRows(raw)
+    finally:
+        lib().kmdb_sparse_free(C.byref(raw))
 
 
 class SparseRows:
@@ -615,6 +659,45 @@ class DeviceDB:
         finally:
             lib().kmdb_sparse_free(C.byref(raw))
 
+    def new2all_sparse_filtered(self, queries, filters=(), sample_kmers=None, measure=None):
+        """kmdb_new2all_batch_sparse_filtered: the rows of the queries (sorted unique k-mer arrays) compacted and filtered on the device — one2all_sp +
+        the row's CombinedFilter.  filters: [(criterion name, lo, hi)], None = unbounded; sample_kmers: the database samples' k-mer counts (b of every
+        measure; a is the query's own count); measure: a criterion name whose value is returned per kept cell."""
+        keep, ptrs, cnts, nq = _kmer_queries(queries)
+        raw, o, sk = _Sparse(), _opts(self.device), _u32(sample_kmers)
+        _check(lib().kmdb_new2all_batch_sparse_filtered(self._d, ptrs, cnts, nq, _filters(filters), len(filters), _ptr(sk),
+                                                        -1 if measure is None else _criterion(measure), C.byref(raw), C.byref(o)))
+        return _rows_out(raw)
+
+    def new2all_seq_sparse(self, seqs, filters=(), sample_kmers=None, measure=None, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        """kmdb_new2all_batch_seq_alphabet_sparse_filtered: as new2all_sparse_filtered with the queries given as sequence text; returns
+        (SparseRows, unique k-mer count per query)"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        keep, ptrs, lens, nq = _text_queries(seqs)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        raw, o, sk = _Sparse(), _opts(self.device), _u32(sample_kmers)
+        _check(lib().kmdb_new2all_batch_seq_alphabet_sparse_filtered(self._d, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet), _filters(filters),
+                                                                     len(filters), _ptr(sk), -1 if measure is None else _criterion(measure), C.byref(raw),
+                                                                     cnt.ctypes.data, C.byref(o)))
+        return _rows_out(raw), cnt[:nq]
+
+    def new2all_rows_sparse_device(self, dev_ptr, nq, cell_lo=0, cell_hi=None, query_kmers=None, filters=(), sample_kmers=None, measure=None, stream=None):
+        """kmdb_new2all_rows_sparse_device: the compaction alone, on the cells [cell_lo, cell_hi) of a row-major nq x N uint32 buffer the caller
+        accumulated; dev_ptr = device address of cell_lo.  All nq rows come back; a row cut by a range end lists only its cells inside."""
+        raw, o = _Sparse(), _opts(self.device, stream=stream)
+        qk, sk = _u32(query_kmers), _u32(sample_kmers)
+        _check(lib().kmdb_new2all_rows_sparse_device(self._d, C.c_void_p(dev_ptr), int(nq), int(cell_lo), int(nq) * self.N if cell_hi is None else int(cell_hi),
+                                                     _ptr(qk), _filters(filters), len(filters), _ptr(sk), -1 if measure is None else _criterion(measure),
+                                                     C.byref(raw), C.byref(o)))
+        return _rows_out(raw)
+
+    def new2all_sparse_stats(self):
+        """kmdb_new2all_sparse_stats_get: the last sparse new2all call on the handle"""
+        s = _New2allSparseStats()
+        _check(lib().kmdb_new2all_sparse_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _New2allSparseStats._fields_}
+
     def stats(self):
         s = _Stats()
         _check(lib().kmdb_db_stats(self._d, C.byref(s)))
@@ -707,17 +790,36 @@ class NodeDB:
                                                           out.ctypes.data if out.size else None, cnt.ctypes.data, None))
         return out, cnt[:nq]
 
-    def new2all_sparse(self, queries):
-        qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
-        nq = len(qs)
-        ptrs = (C.c_void_p * max(nq, 1))(*[q.ctypes.data for q in qs])
-        cnts = (C.c_size_t * max(nq, 1))(*[q.size for q in qs])
+    def new2all_sparse(self, queries, filters=(), sample_kmers=None, measure=None):
+        """kmdb_node_new2all_batch_sparse (no bounds, no measure) / kmdb_node_new2all_batch_sparse_filtered: DeviceDB.new2all_sparse_filtered over the
+        query shards of the node — every device compacts its own chunk of the summed rows"""
+        keep, ptrs, cnts, nq = _kmer_queries(queries)
         raw = _Sparse()
-        _check(lib().kmdb_node_new2all_batch_sparse(self._n, ptrs, cnts, nq, C.byref(raw), None))
-        try:
-            return SparseRows(raw)
-        finally:
-            lib().kmdb_sparse_free(C.byref(raw))
+        if not filters and sample_kmers is None and measure is None:
+            _check(lib().kmdb_node_new2all_batch_sparse(self._n, ptrs, cnts, nq, C.byref(raw), None))
+        else:
+            sk = _u32(sample_kmers)
+            _check(lib().kmdb_node_new2all_batch_sparse_filtered(self._n, ptrs, cnts, nq, _filters(filters), len(filters), _ptr(sk),
+                                                                 -1 if measure is None else _criterion(measure), C.byref(raw), None))
+        return _rows_out(raw)
+
+    def new2all_seq_sparse(self, seqs, filters=(), sample_kmers=None, measure=None, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        """kmdb_node_new2all_batch_seq_alphabet_sparse_filtered: (SparseRows, unique k-mer count per query)"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        keep, ptrs, lens, nq = _text_queries(seqs)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        raw, sk = _Sparse(), _u32(sample_kmers)
+        _check(lib().kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(self._n, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet),
+                                                                          _filters(filters), len(filters), _ptr(sk), -1 if measure is None else _criterion(measure),
+                                                                          C.byref(raw), cnt.ctypes.data, None))
+        return _rows_out(raw), cnt[:nq]
+
+    def new2all_sparse_stats(self):
+        """kmdb_node_new2all_sparse_stats_get: the last sparse new2all call on the node (sums over the devices, the slowest compact_ms)"""
+        s = _New2allSparseStats()
+        _check(lib().kmdb_node_new2all_sparse_stats_get(self._n, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _New2allSparseStats._fields_}
 
     def stats(self):
         s = _NodeStats()

@@ -324,7 +324,7 @@ int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* o) {
     o->pid2dfs = db->pid2dfs; o->qs_index = db->qs_index; o->qs_count = db->qs_count; o->stream = db->stream;
     o->max_depth = db->max_depth; o->list_sets = &db->list_sets; o->list_sets_nb = &db->list_sets_nb; o->list_sets_tried = &db->list_sets_tried;
     o->rl_ofs = &db->rl_ofs; o->rl_runs = &db->rl_runs; o->rl_node = &db->rl_node; o->rl_tried = &db->rl_tried;
-    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats;
+    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats; o->n2s_stats = &db->n2s_stats;
     for (int i = 0; i < 4; ++i) o->ev[i] = db->ev[i];
     return 0;
 }
@@ -872,6 +872,12 @@ extern "C" int kmdb_all2all_sampled(kmdb_db* db, const kmdb_cell_filter* filters
     const int rc = kmdbh_sample_rows_select(criterion, count, (int)db->kmer_length, sample_kmers, filters, n_filters, parts, 1, out);
     kmdb_sparse_free(&cand);
     return rc;
+}
+
+extern "C" int kmdb_new2all_sparse_stats_get(const kmdb_db* db, kmdb_new2all_sparse_stats* out) {
+    if (!db || !out) return kmdb_set_error("kmdb_new2all_sparse_stats_get: null argument");
+    *out = db->n2s_stats;
+    return 0;
 }
 
 extern "C" int kmdb_db2db_stats_get(const kmdb_db* db_row, kmdb_db2db_stats* out) {

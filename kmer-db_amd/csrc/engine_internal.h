@@ -40,6 +40,7 @@ struct kmdb_engine_view {
     bool* rl_tried;
     uint64_t* device_bytes;
     struct kmdb_db2db_stats* d2_stats;   // the last db2db call with this handle as the row database (kmdb_db2db_stats_get)
+    struct kmdb_new2all_sparse_stats* n2s_stats;   // the last sparse new2all call on the handle (kmdb_new2all_sparse_stats_get)
     void* stream;
     void* ev[4];
 };
@@ -48,12 +49,19 @@ struct kmdb_engine_view {
 int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* out);
 void kmdb_engine_set_times(kmdb_db* db, double kernel_ms, double dominant_ms);
 
-// host compaction of dense new2all rows into the CSR of one2all_sp (new2all.hip; node.hip uses it after its reduce); 0, or 1 with the error set
+// ---- the sparse form of new2all (new2all_sparse.hip; node.hip compacts every device's chunk with it)
 struct kmdb_sparse_rows;
-int kmdb_rows_to_sparse(const uint32_t* dense, size_t nq, uint64_t N, kmdb_sparse_rows* out);
+struct kmdb_cell_filter;
+struct kmdb_opts;
+struct kmdb_new2all_sparse_stats;
+// The device half of kmdb_new2all_rows_sparse_device: the cells [cell_lo, cell_hi) of a row-major nq x N buffer (cells_dev points at cell_lo,
+// complete on the stream of `opts`) -> CSR of all nq rows in `out`, the widened bounds applied (a = query_kmers[row], b = sample_kmers[col]);
+// no exact decision.  stats (may be null): cells, nnz_device (= nnz), d2h_bytes, compact_ms.  0, or 1 with the error set (out freed).
+int kmdb_n2a_rows_compact(const char* who, kmdb_db* db, const uint32_t* cells_dev, size_t nq, uint64_t cell_lo, uint64_t cell_hi, const uint32_t* query_kmers,
+                          const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, kmdb_sparse_rows* out, const kmdb_opts* opts,
+                          kmdb_new2all_sparse_stats* stats);
 
 // ---- the -min / -max filters of the sparse calls (engine.hip; db2db.hip uses them for its cell of two databases)
-struct kmdb_cell_filter;
 // argument checks of a filtered call, before any device work; sample_kmers: the count array (null when the caller holds none); 0, or 1 with the error set
 int kmdb_check_filters(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure);
 // every host bound as the device's widened bound on a plain ratio (ratio_bound and its margin): kind / lo / hi of cell_filter.h's DevFilter

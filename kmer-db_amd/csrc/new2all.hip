@@ -932,36 +932,3 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
     d_kmer.reset(); d_kmer2.reset(); d_qid2.reset(); d_head.reset(); d_hscan.reset(); d_qid.reset();
     return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
 }
-
-int kmdb_rows_to_sparse(const uint32_t* dense, size_t nq, uint64_t N, kmdb_sparse_rows* out) {
-    // one2all_sp returns the (sample, count) pairs with count > 0 ordered by sample id (:1040-1047)
-    out->n_rows = nq;
-    out->row_ptr = (uint64_t*)std::malloc((nq + 1) * 8);
-    uint64_t nnz = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        out->row_ptr[q] = nnz;
-        for (uint64_t s = 0; s < N; ++s) nnz += dense[q * N + s] != 0;
-    }
-    out->row_ptr[nq] = nnz;
-    out->nnz = nnz;
-    out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
-    out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
-    uint64_t o = 0;
-    for (size_t q = 0; q < nq; ++q)
-        for (uint64_t s = 0; s < N; ++s)
-            if (dense[q * N + s]) { out->col[o] = (uint32_t)s; out->val[o] = dense[q * N + s]; ++o; }
-    return 0;
-}
-
-extern "C" int kmdb_new2all_batch_sparse(kmdb_db* dbh, const uint64_t* const* kmers, const size_t* counts, size_t nq,
-                                         kmdb_sparse_rows* out, const kmdb_opts* opts) {
-    if (!out) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
-    std::memset(out, 0, sizeof *out);
-    kmdb_engine_view e;
-    if (!dbh) return kmdb_set_error("kmdb_new2all_batch_sparse: null argument");
-    if (kmdb_engine_get(dbh, &e)) return 1;
-    const uint64_t N = e.N;
-    std::vector<uint32_t> dense(std::max<uint64_t>(nq * N, 1));
-    if (kmdb_new2all_batch(dbh, kmers, counts, nq, dense.data(), opts)) return 1;
-    return kmdb_rows_to_sparse(dense.data(), nq, N, out);
-}

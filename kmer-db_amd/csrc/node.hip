@@ -122,6 +122,7 @@ struct kmdb_node {
                                                              // one-rank communicator (what a one-GPU box can exercise of the RCCL path)
     int partition = KMDB_PARTITION_PREFIX;
     kmdb_node_stats stats{};
+    kmdb_new2all_sparse_stats n2s_stats{};                   // the last sparse new2all call (kmdb_node_new2all_sparse_stats_get)
     Rendezvous meet;
     std::atomic<bool> aborted{false};                        // a collective failed after the rendezvous: the communicators are gone
 };
@@ -513,9 +514,19 @@ namespace {
 
 const char* partition_name(int p) { return p == KMDB_PARTITION_RANGE ? "range" : p == KMDB_PARTITION_PREFIX_TABLES ? "prefix-tables" : "prefix"; }
 
-// run(d, k, shard handle, rows, opts): shard k of device slot d adds its rows of the batch into `rows` on the slot's stream
-template <class Run>
-int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, uint32_t* out_dense, const kmdb_opts* opts, Run&& run) {
+// where device slot d's cells of the summed rows are: the pointer and the flat range of the nq x N rectangle
+void node_rows_chunk(const kmdb_node* nd, size_t d, uint64_t cells, uint64_t per, const uint32_t*& p, uint64_t& lo, uint64_t& hi) {
+    const DevSlot& s = nd->dev[d];
+    p = s.rows; lo = 0; hi = cells;
+    if (nd->use_rccl) { p = s.rows_chunk; lo = std::min<uint64_t>(cells, per * d); hi = std::min<uint64_t>(cells, per * (d + 1)); }
+}
+uint64_t node_rows_per(const kmdb_node* nd, uint64_t cells) { const size_t D = nd->dev.size(); return D > 1 ? (cells + D - 1) / D : cells; }
+
+// run(d, k, shard handle, rows, opts): shard k of device slot d adds its rows of the batch into `rows` on the slot's stream.
+// finish(d, chunk, lo, hi): what the device does with ITS cells [lo, hi) of the summed rows, behind the collective on the same stream (the dense
+// entries queue their copy to the host, the sparse ones compact the chunk where it is); the stream is waited for after it.
+template <class Run, class Finish>
+int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, const kmdb_opts* opts, Run&& run, Finish&& finish) {
     if (!nd) return kmdb_set_error(std::string(who) + ": null argument");
     if (nd->partition != KMDB_PARTITION_PREFIX_TABLES)
         return kmdb_set_error(std::string(who) + ": the node was uploaded with partition " + partition_name(nd->partition) +
@@ -523,8 +534,7 @@ int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, uint32_t* out_d
     if (nd->aborted) return kmdb_set_error(std::string(who) + ": an earlier collective failed and the node's communicators were aborted (upload again)");
     const size_t D = nd->dev.size();
     const uint64_t cells = (uint64_t)nq * nd->N;
-    const uint64_t per = D > 1 ? (cells + D - 1) / D : cells;      // cells per rank of the reduce-scatter
-    if (cells && !out_dense) return kmdb_set_error(std::string(who) + ": null argument");
+    const uint64_t per = node_rows_per(nd, cells);                 // cells per rank of the reduce-scatter
     const int rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
         DevSlot& s = nd->dev[d];
         s.call_ms = s.collective_ms = s.d2h_ms = 0;
@@ -554,10 +564,9 @@ int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, uint32_t* out_d
         const int own = dev_ok ? own_part() : 1;
         const std::string own_msg = own ? kmdb_last_error() : "";
         if (node_collective(nd, d, dev_ok, own, own_msg, s.rows, s.rows_chunk, per)) return 1;
-        const uint32_t* p = s.rows;
-        uint64_t lo = 0, hi = cells;
-        if (nd->use_rccl) { p = s.rows_chunk; lo = std::min<uint64_t>(cells, per * d); hi = std::min<uint64_t>(cells, per * (d + 1)); }
-        if (hi > lo) NODE_TRY(hipMemcpyAsync(out_dense + lo, p, (hi - lo) * 4, hipMemcpyDeviceToHost, s.stream));
+        const uint32_t* p; uint64_t lo, hi;
+        node_rows_chunk(nd, d, cells, per, p, lo, hi);
+        if (finish(d, p, lo, hi)) return 1;
         NODE_TRY(hipEventRecord(s.ev[3], s.stream));
         NODE_TRY(hipStreamSynchronize(s.stream));
         return node_times(nd, d);
@@ -566,19 +575,14 @@ int node_new2all_call(kmdb_node* nd, const char* who, size_t nq, uint32_t* out_d
     return rc;
 }
 
-}  // namespace
-
-extern "C" int kmdb_node_new2all_batch(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense,
-                                       const kmdb_opts* opts) {
-    if (nq && (!kmers || !counts)) return kmdb_set_error("kmdb_node_new2all_batch: null argument");
-    if (!nd) return kmdb_set_error("kmdb_node_new2all_batch: null argument");
-    // The split of the batch (kmdbh_query_shard_runs' rule, from the same kmdb_for_bucket_runs): a sorted query holds a bucket as one contiguous
-    // run, so ONE pass of a device's thread over the batch deals every run of a bucket b to shard b % n_shards where that shard lives on the
-    // device (slot k = shard / D); only those k-mers go to the device.  Made when the device's first shard runs, used by all its shards.
+// The split of a k-mer batch (kmdbh_query_shard_runs' rule, from the same kmdb_for_bucket_runs): a sorted query holds a bucket as one contiguous
+// run, so ONE pass of a device's thread over the batch deals every run of a bucket b to shard b % n_shards where that shard lives on the
+// device (slot k = shard / D); only those k-mers go to the device.  Made when the device's first shard runs, used by all its shards.
+struct KmerRun {
     struct ShardPart { std::vector<uint64_t> own; std::vector<size_t> off; };
+    kmdb_node* nd; const char* who; const uint64_t* const* kmers; const size_t* counts; size_t nq;
     std::vector<std::vector<ShardPart>> split;
-    try { split.resize(nd->dev.size()); } catch (const std::exception&) { return kmdb_set_error("kmdb_node_new2all_batch: out of host memory"); }
-    return node_new2all_call(nd, "kmdb_node_new2all_batch", nq, out_dense, opts, [&](size_t d, size_t k, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) -> int {
+    int operator()(size_t d, size_t k, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) {
         // (runs on the device's own thread: nothing may leave it as an exception, and a failure must still reach the rendezvous as a status)
         try {
             const size_t D = nd->dev.size(), K = nd->dev[d].shards.size();
@@ -604,50 +608,206 @@ extern "C" int kmdb_node_new2all_batch(kmdb_node* nd, const uint64_t* const* kme
             std::vector<uint64_t>().swap(mine.own);                // (the call has ended: its k-mers are on the device no longer needed)
             return rc;
         } catch (const std::exception& e) {
-            return kmdb_set_error(std::string("kmdb_node_new2all_batch: ") + e.what());
+            return kmdb_set_error(std::string(who) + ": " + e.what());
         }
-    });
+    }
+};
+
+// The text goes to every device; a shard keeps the positions of its own buckets, so its counts are those of its own unique k-mers: per_dev[d]
+// sums the device's shards, the sum over the devices is the query's count.
+struct SeqRun {
+    const char* who; const char* const* seqs; const size_t* seq_lens; size_t nq; double fraction, start_fraction; int32_t alphabet;
+    std::vector<std::vector<uint64_t>> per_dev;
+    int operator()(size_t d, size_t, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) {
+        try {                                                  // (a device thread: nothing may leave it as an exception)
+            std::vector<uint64_t> cnt(std::max<size_t>(nq, 1), 0);
+            if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, cnt.data(), o)) return 1;
+            for (size_t q = 0; q < nq; ++q) per_dev[d][q] += cnt[q];
+            return 0;
+        } catch (const std::exception& e) {
+            return kmdb_set_error(std::string(who) + ": " + e.what());
+        }
+    }
+    uint64_t count(size_t q) const { uint64_t sum = 0; for (auto& v : per_dev) sum += v[q]; return sum; }
+};
+
+// the dense entries' finish: every device its own chunk to the host, side by side over PCIe, queued behind its collective
+auto node_rows_to_host(kmdb_node* nd, uint32_t* out_dense) {
+    return [nd, out_dense](size_t d, const uint32_t* p, uint64_t lo, uint64_t hi) -> int {
+        if (hi > lo) NODE_TRY(hipMemcpyAsync(out_dense + lo, p, (hi - lo) * 4, hipMemcpyDeviceToHost, nd->dev[d].stream));
+        return 0;
+    };
+}
+
+}  // namespace
+
+extern "C" int kmdb_node_new2all_batch(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, uint32_t* out_dense,
+                                       const kmdb_opts* opts) {
+    const char* who = "kmdb_node_new2all_batch";
+    if (nq && (!kmers || !counts)) return kmdb_set_error(std::string(who) + ": null argument");
+    if (!nd) return kmdb_set_error(std::string(who) + ": null argument");
+    if (nq && nd->N && !out_dense && nd->partition == KMDB_PARTITION_PREFIX_TABLES) return kmdb_set_error(std::string(who) + ": null argument");
+    KmerRun run{nd, who, kmers, counts, nq, {}};
+    try { run.split.resize(nd->dev.size()); } catch (const std::exception&) { return kmdb_set_error(std::string(who) + ": out of host memory"); }
+    return node_new2all_call(nd, who, nq, opts, run, node_rows_to_host(nd, out_dense));
 }
 
 extern "C" int kmdb_node_new2all_batch_seq_alphabet(kmdb_node* nd, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
                                                     double start_fraction, int32_t alphabet, uint32_t* out_dense, uint64_t* out_kmer_counts,
                                                     const kmdb_opts* opts) {
-    if (nq && (!seqs || !seq_lens || !out_kmer_counts)) return kmdb_set_error("kmdb_node_new2all_batch_seq_alphabet: null argument");
+    const char* who = "kmdb_node_new2all_batch_seq_alphabet";
+    if (nq && (!seqs || !seq_lens || !out_kmer_counts)) return kmdb_set_error(std::string(who) + ": null argument");
+    if (nd && nq && nd->N && !out_dense && nd->partition == KMDB_PARTITION_PREFIX_TABLES) return kmdb_set_error(std::string(who) + ": null argument");
     try {
-        // the text goes to every device; a shard keeps the positions of its own buckets, so its counts are those of its own unique k-mers
-        std::vector<std::vector<uint64_t>> per_dev(nd ? nd->dev.size() : 0, std::vector<uint64_t>(nq, 0));
-        const int rc = node_new2all_call(nd, "kmdb_node_new2all_batch_seq_alphabet", nq, out_dense, opts,
-                                         [&](size_t d, size_t, kmdb_db* db, uint32_t* rows, const kmdb_opts* o) -> int {
-            try {                                                  // (a device thread: nothing may leave it as an exception)
-                std::vector<uint64_t> cnt(std::max<size_t>(nq, 1), 0);
-                if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, cnt.data(), o)) return 1;
-                for (size_t q = 0; q < nq; ++q) per_dev[d][q] += cnt[q];
-                return 0;
-            } catch (const std::exception& e) {
-                return kmdb_set_error(std::string("kmdb_node_new2all_batch_seq_alphabet: ") + e.what());
-            }
-        });
+        SeqRun run{who, seqs, seq_lens, nq, fraction, start_fraction, alphabet, {}};
+        run.per_dev.assign(nd ? nd->dev.size() : 0, std::vector<uint64_t>(nq, 0));
+        const int rc = node_new2all_call(nd, who, nq, opts, run, node_rows_to_host(nd, out_dense));
         if (rc) return rc;
-        for (size_t q = 0; q < nq; ++q) {
-            uint64_t sum = 0;
-            for (auto& v : per_dev) sum += v[q];
-            out_kmer_counts[q] = sum;
-        }
+        for (size_t q = 0; q < nq; ++q) out_kmer_counts[q] = run.count(q);
         return 0;
     } catch (const std::exception& e) {
-        return kmdb_set_error(std::string("kmdb_node_new2all_batch_seq_alphabet: ") + e.what());
+        return kmdb_set_error(std::string(who) + ": " + e.what());
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// new2all -sparse over the node (console_new2all.cpp:76-78, 130-148): the summed rows stay where the reduce-scatter left them and every
+// device compacts ITS chunk (kmdb_n2a_rows_compact, new2all_sparse.hip: widened bounds, a = the query's count); the host concatenates the
+// parts row by row — device order = ascending cells — and decides once (kmdb_sparse_decide).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// counts_known: the queries' counts are known before the rows are (k-mer entry): the compaction is queued behind the collective.  Else (text
+// entry) they are complete only once every device has reported: query_counts() is called after the first pass and the compaction is a second
+// pass over the devices, the chunks still resident.
+template <class Run, class Counts>
+int node_new2all_sparse(kmdb_node* nd, const char* who, size_t nq, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
+                        kmdb_sparse_rows* out, const kmdb_opts* opts, bool counts_known, Run& run, Counts&& query_counts) {
+    std::memset(out, 0, sizeof *out);
+    const size_t D = nd->dev.size();
+    std::vector<kmdb_sparse_rows> part(D);
+    for (auto& p : part) std::memset(&p, 0, sizeof p);
+    std::vector<kmdb_new2all_sparse_stats> pst(D);
+    std::vector<uint32_t> qk;
+    auto compact = [&](size_t d, const uint32_t* p, uint64_t lo, uint64_t hi) -> int {
+        DevSlot& s = nd->dev[d];
+        kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = s.device; o.shard_count = 1; o.stream = s.stream;
+        return kmdb_n2a_rows_compact(who, s.shards[0], p, nq, lo, hi, qk.data(), filters, n_filters, sample_kmers, &part[d], &o, &pst[d]);
+    };
+    int rc;
+    if (counts_known) {
+        query_counts(qk);
+        rc = node_new2all_call(nd, who, nq, opts, run, compact);
+    } else {
+        rc = node_new2all_call(nd, who, nq, opts, run, [](size_t, const uint32_t*, uint64_t, uint64_t) -> int { return 0; });
+        if (!rc) {
+            query_counts(qk);
+            const uint64_t cells = (uint64_t)nq * nd->N, per = node_rows_per(nd, cells);
+            rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
+                if (!dev_ok) return 1;
+                DevSlot& s = nd->dev[d];
+                const uint32_t* p; uint64_t lo, hi;
+                node_rows_chunk(nd, d, cells, per, p, lo, hi);
+                NODE_TRY(hipEventRecord(s.ev[2], s.stream));
+                if (compact(d, p, lo, hi)) return 1;
+                NODE_TRY(hipEventRecord(s.ev[3], s.stream));
+                NODE_TRY(hipStreamSynchronize(s.stream));
+                float c = 0;
+                NODE_TRY(hipEventElapsedTime(&c, s.ev[2], s.ev[3]));
+                s.d2h_ms = c;
+                return 0;
+            });
+            node_fill_stats(nd);
+        }
+    }
+    kmdb_new2all_sparse_stats ns{};
+    if (!rc) {
+        uint64_t nnz = 0;
+        for (size_t d = 0; d < D; ++d) {
+            nnz += part[d].nnz;
+            ns.cells += pst[d].cells; ns.nnz_device += pst[d].nnz_device; ns.d2h_bytes += pst[d].d2h_bytes; ns.compact_ms = std::max(ns.compact_ms, pst[d].compact_ms);
+        }
+        out->n_rows = nq; out->nnz = nnz;
+        out->row_ptr = (uint64_t*)std::malloc((nq + 1) * 8);
+        out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+        out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+        if (!out->row_ptr || !out->col || !out->val) rc = kmdb_set_error(std::string(who) + ": out of host memory for the result");
+        else {
+            uint64_t w = 0;
+            for (uint64_t i = 0; i < nq; ++i) {
+                out->row_ptr[i] = w;
+                for (auto& p : part) {
+                    if (!p.row_ptr) continue;
+                    const uint64_t a = p.row_ptr[i], b = p.row_ptr[i + 1];
+                    if (b == a) continue;
+                    std::memcpy(out->col + w, p.col + a, (b - a) * 4);
+                    std::memcpy(out->val + w, p.val + a, (b - a) * 4);
+                    w += b - a;
+                }
+            }
+            out->row_ptr[nq] = w;
+        }
+    }
+    for (auto& p : part) kmdb_sparse_free(&p);
+    if (rc) { const std::string msg = kmdb_last_error(); kmdb_sparse_free(out); return kmdb_set_error(msg); }
+    if ((n_filters || measure >= 0) && kmdb_sparse_decide(who, out, filters, n_filters, qk.data(), sample_kmers, measure, (int)nd->kmer_length)) return 1;
+    ns.nnz = out->nnz;
+    nd->n2s_stats = ns;
+    return 0;
+}
+
+int node_new2all_sparse_kmers(const char* who, kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                              size_t n_filters, const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    // (argument errors before any device thread starts: a refusal must not leave a rank waiting at the rendezvous)
+    if (!nd || !out || (nq && (!kmers || !counts))) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_filters(who, filters, n_filters, sample_kmers, measure)) return 1;
+    try {
+        KmerRun run{nd, who, kmers, counts, nq, {}};
+        run.split.resize(nd->dev.size());
+        return node_new2all_sparse(nd, who, nq, filters, n_filters, sample_kmers, measure, out, opts, true, run, [&](std::vector<uint32_t>& qk) {
+            qk.assign(std::max<size_t>(nq, 1), 0);
+            for (size_t q = 0; q < nq; ++q) qk[q] = (uint32_t)counts[q];
+        });
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+
+}  // namespace
+
+extern "C" int kmdb_node_new2all_batch_sparse_filtered(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq,
+                                                       const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
+                                                       kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    return node_new2all_sparse_kmers("kmdb_node_new2all_batch_sparse_filtered", nd, kmers, counts, nq, filters, n_filters, sample_kmers, measure, out, opts);
+}
+
+// one2all_sp over the node without bounds (console_new2all.cpp:78): the same path, every non-zero cell
 extern "C" int kmdb_node_new2all_batch_sparse(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, kmdb_sparse_rows* out,
                                               const kmdb_opts* opts) {
-    if (!nd || !out) return kmdb_set_error("kmdb_node_new2all_batch_sparse: null argument");
-    std::memset(out, 0, sizeof *out);
+    return node_new2all_sparse_kmers("kmdb_node_new2all_batch_sparse", nd, kmers, counts, nq, nullptr, 0, nullptr, -1, out, opts);
+}
+
+extern "C" int kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(kmdb_node* nd, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                                    double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                                    const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out,
+                                                                    uint64_t* out_kmer_counts, const kmdb_opts* opts) {
+    const char* who = "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered";
+    if (!nd || !out || (nq && (!seqs || !seq_lens || !out_kmer_counts))) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_filters(who, filters, n_filters, sample_kmers, measure)) return 1;
     try {
-        std::vector<uint32_t> dense(std::max<uint64_t>((uint64_t)nq * nd->N, 1));
-        if (kmdb_node_new2all_batch(nd, kmers, counts, nq, dense.data(), opts)) return 1;
-        return kmdb_rows_to_sparse(dense.data(), nq, nd->N, out);
+        SeqRun run{who, seqs, seq_lens, nq, fraction, start_fraction, alphabet, {}};
+        run.per_dev.assign(nd->dev.size(), std::vector<uint64_t>(nq, 0));
+        return node_new2all_sparse(nd, who, nq, filters, n_filters, sample_kmers, measure, out, opts, false, run, [&](std::vector<uint32_t>& qk) {
+            qk.assign(std::max<size_t>(nq, 1), 0);
+            for (size_t q = 0; q < nq; ++q) { out_kmer_counts[q] = run.count(q); qk[q] = (uint32_t)out_kmer_counts[q]; }
+        });
     } catch (const std::exception& e) {
-        return kmdb_set_error(std::string("kmdb_node_new2all_batch_sparse: ") + e.what());
+        return kmdb_set_error(std::string(who) + ": " + e.what());
     }
+}
+
+extern "C" int kmdb_node_new2all_sparse_stats_get(const kmdb_node* nd, kmdb_new2all_sparse_stats* out) {
+    if (!nd || !out) return kmdb_set_error("kmdb_node_new2all_sparse_stats_get: null argument");
+    *out = nd->n2s_stats;
+    return 0;
 }

@@ -810,46 +810,91 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     // written in the same order (the reference re-orders through a priority queue, :60,114-117)
     std::vector<Query> batch;
     size_t batch_bases = 0;                    // flushed by size as well as by count: the engine's scratch grows with the bases
+    // -sparse: the rows are compacted and the -min / -max bounds applied on the device (kmdb_new2all_batch*_sparse_filtered: one2all_sp + the row's
+    // CombinedFilter, console_new2all.cpp:76-78, 130-148); KMDB_N2A_DENSE_ROWS=1 keeps the dense rows and the host's filter (A/B, same bytes)
+    const bool sparse_on_device = c.sparse && !std::getenv("KMDB_N2A_DENSE_ROWS");
+    const bool verbose = std::getenv("KMDB_VERBOSE") != nullptr;
+    std::vector<kmdb_cell_filter> fl;
+    std::vector<uint32_t> sample_counts(n);
+    for (uint64_t j = 0; j < n; ++j) sample_counts[j] = (uint32_t)kmdbh_db_sample_kmers(db.h, j);
+    if (sparse_on_device) {
+        for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+        if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
+            fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+    }
     auto flush = [&]() {
         if (batch.empty()) return;
         batch_bases = 0;
         std::vector<size_t> cnts(batch.size());
-        std::vector<uint32_t> out(batch.size() * n + 1);
+        std::vector<uint32_t> out(sparse_on_device ? 1 : batch.size() * n + 1);
         // a query is either sequence text (loader + KmerHelper::unique + one2all on the device, kmdb_new2all_batch_seq) or,
         // with -host-extract and for genomes beyond the device loader's 2^31 positions, a k-mer list (kmdb_new2all_batch)
         std::vector<size_t> by_text, by_kmers;
         for (size_t q = 0; q < batch.size(); ++q) (batch[q].from_kmers ? by_kmers : by_text).push_back(q);
+        // sparse rows of the two halves, and where query q's row is: {half, row}
+        struct Rows { kmdb_sparse_rows r{}; ~Rows() { kmdb_sparse_free(&r); } } sp[2];
+        std::vector<std::pair<int, size_t>> where(batch.size());
+        kmdb_new2all_sparse_stats tot{};
+        auto account = [&]() {
+            kmdb_new2all_sparse_stats st{};
+            if (db.node ? kmdb_node_new2all_sparse_stats_get(db.node, &st) : kmdb_new2all_sparse_stats_get(db.d, &st)) return;
+            tot.cells += st.cells; tot.nnz_device += st.nnz_device; tot.nnz += st.nnz; tot.d2h_bytes += st.d2h_bytes; tot.compact_ms += st.compact_ms;
+        };
         if (!by_kmers.empty()) {
             std::vector<const uint64_t*> ptrs(by_kmers.size());
             std::vector<size_t> kc(by_kmers.size());
-            std::vector<uint32_t> part(by_kmers.size() * n + 1);
             for (size_t t = 0; t < by_kmers.size(); ++t) { ptrs[t] = batch[by_kmers[t]].kmers.data(); kc[t] = batch[by_kmers[t]].kmers.size(); }
+            if (sparse_on_device) {
+                if (db.node) check(kmdb_node_new2all_batch_sparse_filtered(db.node, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(), -1, &sp[0].r, nullptr));
+                else check(kmdb_new2all_batch_sparse_filtered(db.d, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(), -1, &sp[0].r, &o));
+                account();
+                for (size_t t = 0; t < by_kmers.size(); ++t) { cnts[by_kmers[t]] = kc[t]; where[by_kmers[t]] = {0, t}; }
+            } else {
+            std::vector<uint32_t> part(by_kmers.size() * n + 1);
             if (db.node) check(kmdb_node_new2all_batch(db.node, ptrs.data(), kc.data(), by_kmers.size(), part.data(), nullptr));
             else check(kmdb_new2all_batch(db.d, ptrs.data(), kc.data(), by_kmers.size(), part.data(), &o));
             for (size_t t = 0; t < by_kmers.size(); ++t) {
                 cnts[by_kmers[t]] = kc[t];
                 std::copy(part.begin() + t * n, part.begin() + (t + 1) * n, out.begin() + by_kmers[t] * n);
             }
+            }
         }
         if (!by_text.empty()) {
             std::vector<const char*> ptrs(by_text.size());
             std::vector<size_t> lens(by_text.size());
             std::vector<uint64_t> uniq(by_text.size());
-            std::vector<uint32_t> part(by_text.size() * n + 1);
             for (size_t t = 0; t < by_text.size(); ++t) { ptrs[t] = batch[by_text[t]].text.data(); lens[t] = batch[by_text[t]].text.size(); }
+            if (sparse_on_device) {
+                if (db.node) check(kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(), sample_counts.data(), -1, &sp[1].r, uniq.data(), nullptr));
+                else check(kmdb_new2all_batch_seq_alphabet_sparse_filtered(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(), sample_counts.data(), -1, &sp[1].r, uniq.data(), &o));
+                account();
+                for (size_t t = 0; t < by_text.size(); ++t) { cnts[by_text[t]] = (size_t)uniq[t]; where[by_text[t]] = {1, t}; }
+            } else {
+            std::vector<uint32_t> part(by_text.size() * n + 1);
             if (db.node) check(kmdb_node_new2all_batch_seq_alphabet(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, part.data(), uniq.data(), nullptr));
             else check(kmdb_new2all_batch_seq_alphabet(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, part.data(), uniq.data(), &o));
             for (size_t t = 0; t < by_text.size(); ++t) {
                 cnts[by_text[t]] = (size_t)uniq[t];
                 std::copy(part.begin() + t * n, part.begin() + (t + 1) * n, out.begin() + by_text[t] * n);
             }
+            }
         }
+        if (sparse_on_device && verbose)
+            std::cerr << "[kmdb] new2all: sparse batch of " << batch.size() << " queries: " << tot.cells << " cells, " << tot.nnz_device << " left the device, "
+                      << tot.nnz << " kept, compaction " << tot.compact_ms << " ms, " << tot.d2h_bytes << " bytes to the host" << std::endl;
         std::vector<uint32_t> cols, vals;
         for (size_t q = 0; q < batch.size(); ++q) {
-            const uint32_t* r = out.data() + q * n;
             if (row.size() < 10000 + n * 100 + batch[q].name.size()) row.resize(10000 + n * 100 + batch[q].name.size());
             size_t len;
-            if (c.sparse) {
+            if (sparse_on_device) {
+                // the library decided every cell with kmdbh_metric; the front-end's own filter sees the same cells and agrees bit for bit
+                const kmdb_sparse_rows& r = sp[where[q].first].r;
+                cols.clear(); vals.clear();
+                for (uint64_t e = r.row_ptr[where[q].second]; e < r.row_ptr[where[q].second + 1]; ++e)
+                    if (c.filters.pass(r.val[e], (uint32_t)cnts[q], sample_counts[r.col[e]], (int)k)) { cols.push_back(r.col[e]); vals.push_back(r.val[e]); }
+                len = kmdbh_format_sparse_row(batch[q].name.c_str(), cnts[q], cols.data(), vals.data(), cols.size(), row.data());
+            } else if (c.sparse) {
+                const uint32_t* r = out.data() + q * n;
                 cols.clear(); vals.clear();
                 for (uint64_t j = 0; j < n; ++j)           // one2all_sp keeps count>0 (:1040-1047), then the filter (:131-148)
                     if (r[j] && c.filters.pass(r[j], (uint32_t)cnts[q], (uint32_t)kmdbh_db_sample_kmers(db.h, j), (int)k)) {
@@ -857,7 +902,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
                     }
                 len = kmdbh_format_sparse_row(batch[q].name.c_str(), cnts[q], cols.data(), vals.data(), cols.size(), row.data());
             } else {
-                len = kmdbh_format_dense_row(batch[q].name.c_str(), cnts[q], r, n, row.data());
+                len = kmdbh_format_dense_row(batch[q].name.c_str(), cnts[q], out.data() + q * n, n, row.data());
             }
             ofs.write(row.data(), (std::streamsize)len);
         }
