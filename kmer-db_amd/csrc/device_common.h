@@ -77,116 +77,11 @@ struct BitCursor {
     }
 };
 
-// Same decoder with a deeper look-ahead (PF words in flight): for the threads that walk long streams
-// alone, where the single look-ahead word of BitCursor leaves a full memory latency per 64 bits.
-template <int PF>
-struct BitCursorDeep {
-    const uint64_t* __restrict__ bits;
-    uint64_t wi;
-    uint64_t c[PF + 2];
-    uint32_t s;
-    __device__ __forceinline__ BitCursorDeep(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
-        wi = pos >> 6;
-        s = (uint32_t)pos & 63u;
-#pragma unroll
-        for (int k = 0; k < PF + 2; ++k) c[k] = bits[wi + k];
-    }
-    __device__ __forceinline__ uint32_t next() {
-        const uint64_t win = s ? ((c[0] << s) | (c[1] >> (64u - s))) : c[0];
-        uint32_t ones = (uint32_t)__clzll((long long)~win);
-        ones = ones > 31u ? 31u : ones;
-        const uint32_t low = (uint32_t)((win << ones) >> (63u - ones));
-        s += 2u * ones + 1u;
-        if (s >= 64u) {
-            s -= 64u;
-            ++wi;
-#pragma unroll
-            for (int k = 0; k < PF + 1; ++k) c[k] = c[k + 1];
-            c[PF + 1] = bits[wi + PF + 1];
-        }
-        return low | (1u << ones);
-    }
-};
-
-// Run-aware reader of the same streams.  Most deltas of a local list are 1 (code "0": the samples of a
-// cluster are consecutive ids), so the decoder consumes a whole run of "0" codes with one count-leading-zeros
-// and only walks code by code through the larger deltas.  NW stream words live in registers and are all fetched
-// together: a load inside the decode loop would put a full memory latency on every word the cursor crosses
-// (the loop is divergent, so some lane crosses a word in nearly every iteration).  RELOAD = false: the stream
-// is known to end inside the first NW words.  RELOAD = true: when only one word is left, the next NW - 1 are
-// fetched in one go.
-template <int NW, bool RELOAD>
-struct RunCursor {
-    const uint64_t* __restrict__ bits;
-    uint64_t wi;
-    uint64_t c[NW];
-    uint32_t s;                                    // bit offset inside c[0]
-    uint32_t valid;                                // words of c[] that hold stream data
-    __device__ __forceinline__ RunCursor(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
-        wi = pos >> 6;
-        s = (uint32_t)pos & 63u;
-        valid = NW;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) c[k] = bits[wi + k];
-    }
-    __device__ __forceinline__ void advance(uint32_t nbits) {          // nbits <= 64
-        s += nbits;
-        if (s >= 64u) {
-            s -= 64u;
-            ++wi;
-#pragma unroll
-            for (int k = 0; k + 1 < NW; ++k) c[k] = c[k + 1];
-            if (RELOAD) {
-                if (--valid == 1u) {
-#pragma unroll
-                    for (int k = 1; k < NW; ++k) c[k] = bits[wi + k];
-                    valid = NW;
-                }
-            } else c[NW - 1] = 0;
-        }
-    }
-    __device__ __forceinline__ uint64_t window() const { return s ? ((c[0] << s) | (c[1] >> (64u - s))) : c[0]; }
-    // number of consecutive "0" codes (deltas of 1) at the cursor, at most `limit`; consumes them
-    __device__ __forceinline__ uint32_t zeros(uint32_t limit) {
-        const uint64_t win = window();
-        uint32_t z = win ? (uint32_t)__clzll((long long)win) : 64u;
-        z = z < limit ? z : limit;
-        if (z) advance(z);
-        return z;
-    }
-    // One step of the run-aware decoder: z consecutive "0" codes (deltas of 1, at most `limit`) and, when it is
-    // complete inside the 64-bit window, the code that follows them (value >= 2; 0 = none taken).  One window
-    // extraction serves both.
-    __device__ __forceinline__ void step(uint32_t limit, uint32_t& z, uint32_t& v) {
-        const uint64_t win = window();
-        z = win ? (uint32_t)__clzll((long long)win) : 64u;
-        z = z < limit ? z : limit;
-        v = 0;
-        uint32_t used = z;
-        if (z < limit && z < 64u) {
-            const uint64_t rest = win << z;                          // starts with a 1 bit
-            uint32_t ones = (uint32_t)__clzll((long long)~rest);
-            ones = ones > 31u ? 31u : ones;
-            const uint32_t len = 2u * ones + 1u;
-            if (z + len <= 64u) {
-                v = (uint32_t)((rest << ones) >> (63u - ones)) | (1u << ones);
-                used += len;
-            }
-        }
-        advance(used);
-    }
-    // one code that is known to start with a 1 bit (value >= 2)
-    __device__ __forceinline__ uint32_t big() {
-        const uint64_t win = window();
-        uint32_t ones = (uint32_t)__clzll((long long)~win);
-        ones = ones > 31u ? 31u : ones;
-        const uint32_t low = (uint32_t)((win << ones) >> (63u - ones));
-        advance(2u * ones + 1u);
-        return low | (1u << ones);
-    }
-};
-
-// The same reader on 32-bit units: ids are below 2^16, so a gamma code has at most 31 bits and one 32-bit window holds a run
+// Run-aware reader of the same streams on 32-bit units.  Most deltas of a local list are 1 (code "0": the samples of a cluster are
+// consecutive ids), so the decoder consumes a whole run of "0" codes with one count-leading-zeros and only walks code by code through
+// the larger deltas.  The units live in registers and are fetched together: a load inside the decode loop would put a full memory
+// latency on every unit the cursor crosses (the loop is divergent, so some lane crosses a unit in nearly every iteration).
+// Ids are below 2^16 in most collections, so a gamma code has at most 31 bits and one 32-bit window holds a run
 // of "0" codes and, when it fits behind them, the code that follows — with v_alignbit_b32 and a 32-bit count-leading-zeros
 // instead of 64-bit shifts (the decode loop is bound by VALU issue).  Unit u of the stream (MSB-first inside little-endian
 // uint64 words: a word's high half comes first) is the uint32 at index u ^ 1.  NU units are fetched together before the loop;

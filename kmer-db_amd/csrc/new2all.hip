@@ -103,7 +103,7 @@ __global__ void n2a_query_ranges_kernel(const unsigned long long* __restrict__ u
     qstart[q] = lo;
 }
 
-struct N2Cursor {                                                 // gamma stream reader (see BitCursor in engine.hip)
+struct N2Cursor {                                                 // gamma stream reader (see BitCursor in device_common.h)
     const uint64_t* __restrict__ bits;
     uint64_t wi, c0, c1;
     uint32_t s;
