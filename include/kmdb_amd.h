@@ -568,6 +568,10 @@ size_t kmdbh_extract_kmers_alphabet(const char* seq, size_t len, uint32_t k, int
 /* Alphabet::mapping (alphabet.h:41-58): symbol code of every byte (-1: not a symbol), number of symbols, bits per symbol, strand flag.
  * 0 on success, 1 for an unknown alphabet. */
 int    kmdbh_alphabet_table(int32_t alphabet, int8_t* map256, uint32_t* n_symbols, uint32_t* bits_per_symbol, int* preserve_strand);
+/* The hash window of MinHashFilter (filter.h:42-43), additive in ABI 8: a k-mer is kept when lo <= hash < hi.  Both extractors above and
+ * the device loader take their thresholds from here.  A bound at or beyond 2^64 (a window that ends at 1: -f 0.7 -f-start 0.3) becomes 0,
+ * as in the reference built with its own flags: such a window keeps no k-mer. */
+void   kmdbh_minhash_window(double fraction, double start_fraction, uint64_t* lo, uint64_t* hi);
 /* KmerHelper::unique (kmer_extract.h:112-118): sort + dedupe in place, returns new count */
 size_t kmdbh_sort_unique(uint64_t* kmers, size_t n);
 

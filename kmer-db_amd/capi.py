@@ -100,7 +100,7 @@ EXPORTS = [
     "kmdb_new2all_batch", "kmdb_new2all_batch_sparse", "kmdb_new2all_batch_seq", "kmdb_new2all_batch_seq_alphabet", "kmdb_db2db_dense",
     "kmdbh_shard_plan_counts", "kmdbh_query_shard_plan_counts", "kmdbh_query_shard_runs", "kmdbh_range_plan", "kmdbh_db_load", "kmdbh_db_free", "kmdbh_db_release_patterns", "kmdbh_db_view", "kmdbh_db_kmer_length", "kmdbh_db_fraction",
     "kmdbh_db_start_fraction", "kmdbh_db_alphabet", "kmdbh_db_n_samples", "kmdbh_db_sample_name",
-    "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique",
+    "kmdbh_db_sample_kmers", "kmdbh_db_pattern_section_bytes", "kmdbh_extract_kmers", "kmdbh_extract_kmers_alphabet", "kmdbh_alphabet_table", "kmdbh_sort_unique", "kmdbh_minhash_window",
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
     "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
     "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
@@ -216,6 +216,8 @@ def lib():
     L.kmdbh_extract_kmers_alphabet.restype = C.c_size_t
     L.kmdbh_extract_kmers_alphabet.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_double, C.c_double, C.c_void_p]
     L.kmdbh_alphabet_table.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    L.kmdbh_minhash_window.restype = None
+    L.kmdbh_minhash_window.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.kmdbh_sort_unique.restype = C.c_size_t
     L.kmdbh_sort_unique.argtypes = [C.c_void_p, C.c_size_t]
     L.kmdbh_format_header.restype = C.c_size_t
@@ -900,6 +902,13 @@ def extract_kmers_alphabet(seq, k, alphabet, fraction=1.0, start_fraction=0.0):
     out = np.zeros(max(1, len(seq)), dtype=np.uint64)
     n = lib().kmdbh_extract_kmers_alphabet(seq, len(seq), k, a, fraction, start_fraction, out.ctypes.data)
     return out[:n]
+
+
+def minhash_window(fraction, start_fraction=0.0):
+    """kmdbh_minhash_window: (lo, hi) of the hash window — a k-mer is kept when lo <= hash < hi (a window that ends at 1 has hi = 0)"""
+    lo, hi = C.c_uint64(), C.c_uint64()
+    lib().kmdbh_minhash_window(float(fraction), float(start_fraction), C.byref(lo), C.byref(hi))
+    return int(lo.value), int(hi.value)
 
 
 def sort_unique(kmers):

@@ -55,6 +55,22 @@ inline uint64_t minhash_value(uint64_t word, uint64_t quarter_len) {
 
 }  // namespace
 
+// The hash window of MinHashFilter (src/filter.h:42-43): [2^64 * start, 2^64 * (start + fraction)), each bound the product of
+// (double)UINT64_MAX = 2^64 with a fraction, cut to 64 bits.  A product that does not fit (2^64 and above: every window that ends at 1 or
+// beyond; a NaN as well) has no defined conversion in C++; the reference as its own build flags compile it (g++ -O3 -mavx2, x86-64) yields 0
+// there, so such a window keeps NOTHING.  That value is written out here instead of being left to the compiler — the one definition every
+// loader of this project takes its thresholds from (parity with the reference build is the contract, not an intended meaning).
+extern "C" void kmdbh_minhash_window(double fraction, double start_fraction, uint64_t* lo, uint64_t* hi) {
+    const double two64 = 18446744073709551616.0;                 // == (double)UINT64_MAX
+    const auto cut = [two64](double x) -> uint64_t {
+        if (!(x < two64)) return 0;                              // out of range (or NaN): what the reference build gives
+        if (!(x > 0.0)) return 0;                                // (negative fractions are refused by the front-end; never converted here)
+        return (uint64_t)x;
+    };
+    if (lo) *lo = cut(two64 * start_fraction);
+    if (hi) *hi = cut(two64 * (start_fraction + fraction));
+}
+
 extern "C" size_t kmdbh_extract_kmers(const char* seq, size_t len, uint32_t k, double fraction, double start_fraction,
                                       int preserve_strand, uint64_t* out) {
     if (k == 0 || k > 31 || len < k) return 0;
@@ -64,9 +80,8 @@ extern "C" size_t kmdbh_extract_kmers(const char* seq, size_t len, uint32_t k, d
     const unsigned widen = prefix_bits < 8 ? (unsigned)(8 - prefix_bits) : 0u;
     const uint64_t tail = widen ? ((1ull << widen) - 1) : 0ull;
     const bool subsample = fraction < 1.0;
-    const double u64max = (double)std::numeric_limits<uint64_t>::max();
-    const uint64_t lo = (uint64_t)(u64max * start_fraction);
-    const uint64_t hi = (uint64_t)(u64max * (start_fraction + fraction));
+    uint64_t lo = 0, hi = 0;
+    kmdbh_minhash_window(fraction, start_fraction, &lo, &hi);
     const uint64_t quarter_len = (uint64_t)std::ceil((double)k / 4.0);
 
     uint64_t fwd = 0, rc = 0;
@@ -130,9 +145,8 @@ extern "C" size_t kmdbh_extract_kmers_alphabet(const char* seq, size_t len, uint
     const unsigned widen = prefix_bits < 8 ? (unsigned)(8 - prefix_bits) : 0u;
     const uint64_t tail = widen ? ((1ull << widen) - 1) : 0ull;
     const bool subsample = fraction < 1.0;
-    const double u64max = (double)std::numeric_limits<uint64_t>::max();
-    const uint64_t lo = (uint64_t)(u64max * start_fraction);
-    const uint64_t hi = (uint64_t)(u64max * (start_fraction + fraction));
+    uint64_t lo = 0, hi = 0;
+    kmdbh_minhash_window(fraction, start_fraction, &lo, &hi);
     const uint64_t quarter_len = (uint64_t)std::ceil((double)k / 4.0);
     uint64_t fwd = 0, rc = 0;
     uint32_t valid_run = 0;

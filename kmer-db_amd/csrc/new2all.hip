@@ -863,9 +863,7 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
         p.seq = d_seq.as<char>(); p.soff = d_soff.as<uint64_t>(); p.nq = (uint32_t)nq; p.total_len = L; p.k = k;
         p.widen = prefix_bits < 8 ? (uint32_t)(8 - prefix_bits) : 0u;
         p.preserve = preserve_strand; p.subsample = fraction < 1.0;
-        const double u64max = (double)std::numeric_limits<uint64_t>::max();          // src/filter.h:38-51
-        p.lo = (uint64_t)(u64max * start_fraction);
-        p.hi = (uint64_t)(u64max * (start_fraction + fraction));
+        kmdbh_minhash_window(fraction, start_fraction, &p.lo, &p.hi);                 // src/filter.h:38-51; the host's one definition (host_kmers.cpp)
         p.quarter_len = (uint64_t)std::ceil((double)k / 4.0);
         p.kmer = d_kmer.as<unsigned long long>(); p.qid = d_qid.as<uint32_t>();
         hipLaunchKernelGGL(n2a_extract_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, p);

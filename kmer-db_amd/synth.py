@@ -95,10 +95,22 @@ _WINDOWS_AT_ONCE = 1 << 16       # kmers_of: genomes up to this many k-mer windo
 _WEIGHTS = {}                    # (k, device) -> 4^j, j < k
 
 
-def kmers_of(codes, k, fraction=1.0, start_fraction=0.0, prefix_shard=None):
+def minhash_window(fraction, start_fraction=0.0):
+    """(lo, hi) of the hash window, lo <= hash < hi: the rule of kmdbh_minhash_window (csrc/host_kmers.cpp) restated — a bound is the
+    product of 2^64 (= (double)UINT64_MAX) with the fraction cut to an integer, and a product at or beyond 2^64 becomes 0 as in the
+    reference built with its own flags: a window that ends at 1 keeps nothing."""
+    two64 = float(1 << 64)
+
+    def cut(x):
+        return int(x) if 0.0 < x < two64 else 0
+    return cut(two64 * start_fraction), cut(two64 * (start_fraction + fraction))
+
+
+def kmers_of(codes, k, fraction=1.0, start_fraction=0.0, prefix_shard=None, preserve_strand=False):
     """Sorted, duplicate-free k-mer words of one genome (torch int64 holding the uint64 bit pattern;
     all words are < 2^62 so signed order == unsigned order).  prefix_shard=(index, count): only the k-mers whose prefix
-    bucket (kmer >> 32) is congruent to index modulo count (dropped before the sort)."""
+    bucket (kmer >> 32) is congruent to index modulo count (dropped before the sort).  preserve_strand: the forward word
+    instead of the canonical one (the nt-preserve alphabet)."""
     L = codes.numel()
     if L < k:
         return torch.zeros(0, dtype=torch.int64, device=codes.device)
@@ -124,7 +136,7 @@ def kmers_of(codes, k, fraction=1.0, start_fraction=0.0, prefix_shard=None):
             seg = b[j: j + n]
             fwd = (fwd << 2) | seg
             rc = rc | ((3 - seg) << (2 * j))
-    can = torch.minimum(fwd, rc)
+    can = fwd if preserve_strand else torch.minimum(fwd, rc)
     prefix_bits = 2 * k - 32
     if prefix_bits < 8:
         s = 8 - prefix_bits
@@ -147,10 +159,9 @@ def kmers_of(codes, k, fraction=1.0, start_fraction=0.0, prefix_shard=None):
         h1 = h1 + h2
         h2 = h2 + h1
         hv = h1 ^ h2
-        lo = int(float(_M64) * start_fraction)
-        hi = int(float(_M64) * (start_fraction + fraction))
+        lo, hi = minhash_window(fraction, start_fraction)
         sign = _i64(1 << 63)
-        keep = ((hv ^ sign) >= _i64(lo ^ (1 << 63))) & ((hv ^ sign) < _i64(min(hi, _M64) ^ (1 << 63)))
+        keep = ((hv ^ sign) >= _i64(lo ^ (1 << 63))) & ((hv ^ sign) < _i64(hi ^ (1 << 63)))
         can = can[keep]
     if prefix_shard is not None and prefix_shard[1] > 1:
         can = can[((can >> 32) % prefix_shard[1]) == prefix_shard[0]]
@@ -428,14 +439,15 @@ def build_hashtables(dictionary, kmer_pid, k):
     return boff, slots
 
 
-def write_db(path, k, fraction, names, sample_counts, arrays, n_buckets=None, kmers_count=0, tables=None):
+def write_db(path, k, fraction, names, sample_counts, arrays, n_buckets=None, kmers_count=0, tables=None, start_fraction=0.0, alphabet=0):
     """Serialise in the reference's .db format (prefix_kmer_db.cpp:438-574).  Without `tables` the raw
     hashtables are EMPTY — enough for all2all / all2all-sp, which skip them (console_all2all.cpp:26); with
-    tables = build_hashtables(...) the file also serves new2all."""
+    tables = build_hashtables(...) the file also serves new2all.  start_fraction (`build -f-start`) goes into the header field the
+    reference writes it to (:454), alphabet = the AlphabetType (0 nt, 1 nt-preserve: the two this module derives k-mers for)."""
     if n_buckets is None:
         n_buckets = 1 << max(8, 2 * k - 32)
     with open(path, "wb") as f:
-        f.write(struct.pack("<QIddiBQ", 1, k, fraction, 0.0, 0, 1, kmers_count))
+        f.write(struct.pack("<QIddiBQ", 1, k, fraction, float(start_fraction), int(alphabet), 1, kmers_count))
         f.write(struct.pack("<Q", len(names)))
         for nm, c in zip(names, sample_counts):
             b = nm.encode()
@@ -486,7 +498,7 @@ def write_db(path, k, fraction, names, sample_counts, arrays, n_buckets=None, km
             start = end
 
 
-def write_db_fast(path, k, fraction, names, sample_counts, arrays, kmers_count=0, device="cpu", n_buckets=None):
+def write_db_fast(path, k, fraction, names, sample_counts, arrays, kmers_count=0, device="cpu", n_buckets=None, start_fraction=0.0):
     """write_db for databases of 10^8 patterns: the pattern section (prefix_kmer_db.cpp:438-574, pattern.cpp:15-46) is
     assembled as one uint64 image with vectorised torch ops on `device` and written block by block; the raw
     hashtables are EMPTY (all2all / all2all-sp skip them, console_all2all.cpp:26)."""
@@ -515,7 +527,7 @@ def write_db_fast(path, k, fraction, names, sample_counts, arrays, kmers_count=0
     del data, doff
     cum = (off[1:] * 8).cpu().numpy()                                    # bytes up to and including pattern p
     with open(path, "wb") as f:
-        f.write(struct.pack("<QIddiBQ", 1, k, fraction, 0.0, 0, 1, kmers_count))
+        f.write(struct.pack("<QIddiBQ", 1, k, fraction, float(start_fraction), 0, 1, kmers_count))
         f.write(struct.pack("<Q", len(names)))
         for nm, c in zip(names, sample_counts):
             b = nm.encode()
@@ -550,9 +562,9 @@ def shard_item_lists(dictionary, kmer_pid, k):
 
 
 def synth_database(n_samples, clade_size, length, k=18, fraction=1.0, seed=20260928, r1=0.10, r2=0.01,
-                   device="cpu", progress=None):
+                   device="cpu", progress=None, start_fraction=0.0, preserve_strand=False):
     """Genomes -> k-mers -> patterns.  Returns (genomes, pat) with pat as in build_patterns()."""
     g = CladeGenomes(n_samples, clade_size, length, r1, r2, seed, device)
-    fn = lambda i: kmers_of(g.sample(i), k, fraction)         # noqa: E731
+    fn = lambda i: kmers_of(g.sample(i), k, fraction, start_fraction, preserve_strand=preserve_strand)         # noqa: E731
     pat = build_patterns(fn, n_samples, device, progress=progress)
     return g, pat

@@ -1,7 +1,8 @@
 """ctypes front for the CPU ORACLE (test infrastructure, NOT product code).
 
 Wraps oracle/libkmdb_oracle.so (C restatement, see kmdb_oracle.h) and, when present, the
-oracle/_ref/ref_driver binary (the real reference hot path compiled from /root/reference).
+oracle/_ref/ref_driver binary (the real reference hot path compiled from the reference's sources) and the
+oracle/_ref/ref_extract binary (the reference's own k-mer extractor).
 Also restates the reference consoles' CSV text format so whole-pipeline outputs can be pinned
 byte-for-byte against the reference's golden files:
 
@@ -24,6 +25,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libkmdb_oracle.so")
 REF_DRIVER = os.path.join(HERE, "_ref", "ref_driver")
+REF_EXTRACT = os.path.join(HERE, "_ref", "ref_extract")
 
 
 class _Pattern(C.Structure):
@@ -88,17 +90,27 @@ def lib():
 REF_BRANCHES = {}          # "file:function" -> True (reference compared) / False (reference absent)
 
 
-def have_ref():
+def _have(binary, depth):
     import inspect
-    ok = os.path.exists(REF_DRIVER)
+    ok = os.path.exists(binary)
     try:
-        fr = inspect.stack()[1]
+        fr = inspect.stack()[depth]
         REF_BRANCHES[os.path.basename(fr.filename) + ":" + fr.function] = ok
     except Exception:                            # (never let the bookkeeping break a comparison)
         pass
     if not ok and os.environ.get("KMDB_REQUIRE_REF", "") == "1":
-        raise AssertionError("KMDB_REQUIRE_REF=1: oracle/_ref/ref_driver (the compiled reference) is missing — build it where /root/reference exists (make -C oracle)")
+        raise AssertionError("KMDB_REQUIRE_REF=1: oracle/_ref/%s (the compiled reference) is missing — build it where the reference's sources exist (make -C oracle)"
+                             % os.path.basename(binary))
     return ok
+
+
+def have_ref():
+    return _have(REF_DRIVER, 2)
+
+
+def have_ref_extract():
+    """oracle/_ref/ref_extract (the reference's own KmerHelper::extract) is built: recorded per caller like have_ref()"""
+    return _have(REF_EXTRACT, 2)
 
 
 # ----------------------------------------------------------------------------------------
@@ -307,6 +319,40 @@ def _run_ref(args):
 
 def ref_build(kmers_bin, out_db, threads=1, alphabet="nt"):
     return _run_ref(["build", kmers_bin, out_db, threads, alphabet])
+
+
+def ref_extract(alphabet, k, fraction, start_fraction, texts, with_window=False):
+    """The reference's own KmerHelper::extract over `alphabet` (a name of ALPHABETS) with FilterFactory::create(fraction, start, k), one call
+    per text (7-bit ASCII bytes): a list of uint64 arrays, the words IN EXTRACTION ORDER — sort and unique are the caller's.  The two
+    doubles travel as C99 hex floats, bit for bit.  with_window: also (lo, hi), the thresholds the reference's MinHashFilter object held."""
+    import tempfile
+    texts = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    assert all(max(t, default=0) < 0x80 for t in texts), "ref_extract takes 7-bit ASCII only (alphabet.h:68 indexes with a signed char)"
+    with tempfile.TemporaryDirectory() as td:
+        rin, rout = os.path.join(td, "records.bin"), os.path.join(td, "words.bin")
+        with open(rin, "wb") as f:
+            for t in texts:
+                f.write(struct.pack("<Q", len(t)))
+                f.write(t)
+        r = subprocess.run([REF_EXTRACT, alphabet, str(int(k)), float(fraction).hex(), float(start_fraction).hex(), rin, rout], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("ref_extract failed: " + r.stderr[-2000:])
+        raw = np.fromfile(rout, dtype=np.uint64)
+    out, at = [], 0
+    for _ in texts:
+        n = int(raw[at])
+        out.append(raw[at + 1: at + 1 + n].copy())
+        at += 1 + n
+    assert at == raw.size, "ref_extract wrote %d words, %d were read" % (raw.size, at)
+    if with_window:
+        info = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        return out, (int(info["lo"]), int(info["hi"]))
+    return out
+
+
+def ref_window(fraction, start_fraction):
+    """(lo, hi) of MinHashFilter(fraction, start) as the reference build computes them (filter.h:42-43)"""
+    return ref_extract("nt", 1, fraction, start_fraction, [], with_window=True)[1]
 
 
 def ref_all2all(db_path, out_path, threads=1, buffer_mb=8):
