@@ -33,6 +33,9 @@ extern "C" {
 /* And the sparse, filtered form of new2all (kmdb_new2all_batch_sparse_filtered and its relatives, kmdb_new2all_sparse_stats_get): seven more
  * entry points and one struct of their own, the version stays 8. */
 #define KMDB_HAS_NEW2ALL_SPARSE_FILTERED 1
+/* And the minhash mode: a k-mer extractor that needs no database (kmdb_minhash_batch_seq_alphabet and its helpers) and the reader / writer of
+ * <sample>.minhash files (kmdbh_minhash_store, kmdbh_minhash_load): eight more entry points and two structs of their own, the version stays 8. */
+#define KMDB_HAS_MINHASH 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -574,6 +577,56 @@ int    kmdbh_alphabet_table(int32_t alphabet, int8_t* map256, uint32_t* n_symbol
 void   kmdbh_minhash_window(double fraction, double start_fraction, uint64_t* lo, uint64_t* hi);
 /* KmerHelper::unique (kmer_extract.h:112-118): sort + dedupe in place, returns new count */
 size_t kmdbh_sort_unique(uint64_t* kmers, size_t n);
+
+/* ---------------------------------------------------------------------------------------
+ * The minhash mode (README 2.4 of the reference: minhash every sample once into <sample>.minhash, then feed the files to build / new2all /
+ * one2all with -from-minhash).  Additive in ABI 8 (KMDB_HAS_MINHASH).
+ * ------------------------------------------------------------------------------------- */
+/* The sorted unique k-mer words of a batch of samples: sample s holds kmers[offsets[s] .. offsets[s + 1]).  Library-allocated, free with
+ * kmdb_kmer_lists_free(). */
+typedef struct kmdb_kmer_lists {
+    uint64_t  n_samples;
+    uint64_t* offsets;             /* [n_samples + 1] */
+    uint64_t* kmers;               /* [offsets[n_samples]] */
+} kmdb_kmer_lists;
+/* Replaces, for a whole batch of samples, the loader + KmerHelper::sortAndUnique of MinhashConsole::run (console_minhash.cpp:19-40; also what
+ * console_new2all.cpp:73 and console_one2all.cpp:64-66 do per query): the device extracts the k-mers of every sample, keeps those inside the
+ * hash window (kmdbh_minhash_window(fraction, start_fraction); fraction >= 1: no filter, NullFilter) and returns them sorted and unique —
+ * the words of kmdbh_extract_kmers_alphabet + kmdbh_sort_unique, widening included.  No database handle is needed.
+ * seqs[s]: the text of sample s, its records joined by '\n' (the form kmdb_new2all_batch_seq_alphabet takes); '\n' and every byte outside the
+ * alphabet end a window.  The device (opts->device) and the stream (opts->stream, NULL: the default stream) come from opts; opts may be NULL
+ * (device 0).  The words are filtered BEFORE they are stored (count, scan, write), so device memory beyond the text grows with what is kept.
+ * A batch is cut into pieces at sample boundaries (KMDB_MINHASH_BASES_PER_PIECE bases, default 2^29).  Refused: an unknown alphabet, a k the
+ * alphabet cannot hold (alphabet.h:37), a single sample of 2^31 - 2 bases or more (extract it on the host). */
+int  kmdb_minhash_batch_seq_alphabet(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length,
+                                     double fraction, double start_fraction, int32_t alphabet, kmdb_kmer_lists* out, const kmdb_opts* opts);
+void kmdb_kmer_lists_free(kmdb_kmer_lists* lists);
+/* The extractor's geometry: a thread takes a run of *positions_per_thread consecutive positions of the batch's flat text, a workgroup a tile of
+ * *positions_per_tile (tests place their edges by these). */
+void kmdb_minhash_geometry(uint32_t* positions_per_thread, uint32_t* positions_per_tile);
+typedef struct kmdb_minhash_stats {   /* the LAST kmdb_minhash_batch_seq_alphabet call of the calling thread, summed over its pieces */
+    uint64_t pieces;
+    uint64_t bases;                /* bytes of text */
+    uint64_t kept;                 /* words that passed the filter (before sort + unique) */
+    uint64_t unique;               /* words returned */
+    uint64_t scratch_bytes;        /* device memory of the largest piece, text included */
+    double   h2d_ms;               /* HIP events: allocation of the text + its copy to the device */
+    double   count_ms;             /* pass 1 (extraction, tile counts) */
+    double   scan_ms;              /* scan of the tile counts, the total to the host */
+    double   write_ms;             /* pass 2 (extraction, kept words written) */
+    double   sort_ms;              /* the two radix sorts */
+    double   unique_ms;            /* head flags, scan, compaction, the lists to the host */
+} kmdb_minhash_stats;
+int  kmdb_minhash_stats_get(kmdb_minhash_stats* out);
+/* Replaces MihashedInputFile::store (minhashed_input_file.h:109-118, call site console_minhash.cpp:47), byte for byte: u32 0xfedcba98, u64 count,
+ * count x u64 words, u32 k, f64 fraction; little-endian, no padding.  `path` is the full file name: the caller appends ".minhash" (no GPU). */
+int  kmdbh_minhash_store(const char* path, const uint64_t* kmers, size_t count, uint32_t kmer_length, double fraction);
+/* Replaces MihashedInputFile::open + load (minhashed_input_file.h:58-105; call sites console_one2all.cpp:57, the loader of console_new2all.cpp
+ * and console_build.cpp with -from-minhash).  The words come back as stored: no filter is applied to them.  The file's size is checked against
+ * 24 + 8 * count BEFORE anything is allocated (a damaged count field is an error, not an allocation); a wrong signature is refused.
+ * *kmers is library-allocated: free with kmdbh_minhash_free() (no GPU). */
+int  kmdbh_minhash_load(const char* path, uint64_t** kmers, size_t* count, uint32_t* kmer_length, double* fraction);
+void kmdbh_minhash_free(uint64_t* kmers);
 
 /* CSV text (console_all2all.cpp:40-78, console_new2all.cpp:99-160, conversion.h:246-298).
  * Each returns bytes written to `out` (caller sizes it: 10000 + 100*N like the reference). */

@@ -25,6 +25,11 @@ from .capi import (  # noqa: F401
     lib,
     lib_path,
     make_view,
+    minhash_batch,
+    minhash_geometry,
+    minhash_load,
+    minhash_stats,
+    minhash_store,
     range_plan,
     sample_rows_select,
     sort_unique,

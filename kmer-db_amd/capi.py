@@ -79,6 +79,16 @@ class _Db2dbStats(C.Structure):
                 ("compact_ms", C.c_double)]
 
 
+class _KmerLists(C.Structure):
+    _fields_ = [("n_samples", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("kmers", C.POINTER(C.c_uint64))]
+
+
+class _MinhashStats(C.Structure):
+    _fields_ = [("pieces", C.c_uint64), ("bases", C.c_uint64), ("kept", C.c_uint64), ("unique", C.c_uint64), ("scratch_bytes", C.c_uint64),
+                ("h2d_ms", C.c_double), ("count_ms", C.c_double), ("scan_ms", C.c_double), ("write_ms", C.c_double), ("sort_ms", C.c_double),
+                ("unique_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -106,6 +116,7 @@ EXPORTS = [
     "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
     "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
+    "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
 ]
 
 
@@ -220,6 +231,16 @@ def lib():
     L.kmdbh_minhash_window.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.kmdbh_sort_unique.restype = C.c_size_t
     L.kmdbh_sort_unique.argtypes = [C.c_void_p, C.c_size_t]
+    L.kmdb_minhash_batch_seq_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double, C.c_double, C.c_int32, C.POINTER(_KmerLists), C.c_void_p]
+    L.kmdb_kmer_lists_free.restype = None
+    L.kmdb_kmer_lists_free.argtypes = [C.POINTER(_KmerLists)]
+    L.kmdb_minhash_geometry.restype = None
+    L.kmdb_minhash_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.kmdb_minhash_stats_get.argtypes = [C.POINTER(_MinhashStats)]
+    L.kmdbh_minhash_store.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double]
+    L.kmdbh_minhash_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    L.kmdbh_minhash_free.restype = None
+    L.kmdbh_minhash_free.argtypes = [C.POINTER(C.c_uint64)]
     L.kmdbh_format_header.restype = C.c_size_t
     L.kmdbh_format_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.kmdbh_format_dense_row.restype = C.c_size_t
@@ -909,6 +930,55 @@ def minhash_window(fraction, start_fraction=0.0):
     lo, hi = C.c_uint64(), C.c_uint64()
     lib().kmdbh_minhash_window(float(fraction), float(start_fraction), C.byref(lo), C.byref(hi))
     return int(lo.value), int(hi.value)
+
+
+def minhash_geometry():
+    """kmdb_minhash_geometry: (positions per thread R, positions per tile T) of the device extractor"""
+    r, t = C.c_uint32(), C.c_uint32()
+    lib().kmdb_minhash_geometry(C.byref(r), C.byref(t))
+    return int(r.value), int(t.value)
+
+
+def minhash_batch(seqs, k, alphabet="nt", fraction=1.0, start_fraction=0.0, device=0, stream=None):
+    """kmdb_minhash_batch_seq_alphabet: the sorted unique k-mer words of every sample (its records joined by '\n'), extracted and filtered on the
+    device — a list of uint64 arrays.  alphabet = index into ALPHABETS or its name."""
+    a = ALPHABETS.index(alphabet) if isinstance(alphabet, str) else int(alphabet)
+    keep, ptrs, lens, n = _text_queries(seqs)
+    out = _KmerLists()
+    o = _opts(device, stream=stream)
+    _check(lib().kmdb_minhash_batch_seq_alphabet(ptrs, lens, n, int(k), float(fraction), float(start_fraction), a, C.byref(out), C.byref(o)))
+    try:
+        off = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy()
+        total = int(off[n])
+        flat = np.ctypeslib.as_array(out.kmers, shape=(total,)).copy() if total else np.zeros(0, np.uint64)
+        return [flat[int(off[s]): int(off[s + 1])] for s in range(n)]
+    finally:
+        lib().kmdb_kmer_lists_free(C.byref(out))
+
+
+def minhash_stats():
+    """kmdb_minhash_stats_get: the last minhash_batch call of this thread as a dict (stage times in ms from HIP events, kept / unique words,
+    device bytes of the largest piece)"""
+    st = _MinhashStats()
+    _check(lib().kmdb_minhash_stats_get(C.byref(st)))
+    return {f: getattr(st, f) for f, _ in _MinhashStats._fields_}
+
+
+def minhash_store(path, kmers, k, fraction):
+    """kmdbh_minhash_store: the bytes of MihashedInputFile::store; `path` is the full file name (<sample>.minhash)"""
+    a = np.ascontiguousarray(kmers, np.uint64)
+    _check(lib().kmdbh_minhash_store(os.fsencode(path), a.ctypes.data, a.size, int(k), float(fraction)))
+
+
+def minhash_load(path):
+    """kmdbh_minhash_load: (words as stored, k, fraction) of a <sample>.minhash file"""
+    p, n, k, f = C.POINTER(C.c_uint64)(), C.c_size_t(), C.c_uint32(), C.c_double()
+    _check(lib().kmdbh_minhash_load(os.fsencode(path), C.byref(p), C.byref(n), C.byref(k), C.byref(f)))
+    try:
+        words = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint64)
+    finally:
+        lib().kmdbh_minhash_free(p)
+    return words, int(k.value), float(f.value)
 
 
 def sort_unique(kmers):

@@ -1,0 +1,398 @@
+// minhash.hip — a stand-alone k-mer extractor behind kmdb_minhash_batch_seq_alphabet (include/kmdb_amd.h): no database handle.
+//
+// Replaces, for a batch of samples, what MinhashConsole::run does per sample on the host (reference src/console_minhash.cpp:19-52):
+// the loader's KmerHelper::extract under a MinHashFilter (src/kmer_extract.h:13-97, src/filter.h:28-115) followed by
+// KmerHelper::sortAndUnique (:40).  The words are bit for bit those of kmdbh_extract_kmers_alphabet + kmdbh_sort_unique (csrc/host_kmers.cpp)
+// and of n2a_extract_kernel (csrc/new2all.hip): symbol codes, canonical choice, widening and hash are restated here, the window [lo, hi)
+// comes from kmdbh_minhash_window on the host.
+//
+//   text     the samples of a piece, each followed by one '\n', in one flat buffer with MH_PAD bytes of '\n' in front and a tail of '\n' up
+//            to a whole tile: '\n' is outside every alphabet, so no window crosses a sample, and no kernel checks a bound on the text
+//   extract  a workgroup takes a tile of T = 256 * R positions.  It maps the tile's bytes (and the MH_PAD in front) to symbol codes through
+//            the alphabet table in LDS, once, with coalesced 16-byte loads; a thread then takes a run of R consecutive positions: it warms up
+//            on the k - 1 codes in front of the run and advances the forward word and its reverse complement by ONE symbol per position
+//            (two shift / or steps, not a k-step loop), counting the valid symbols since the last invalid one: a position yields a word
+//            when that count is at least k.  The hash is computed for those positions only.
+//   filter   BEFORE anything is stored — count, scan, write: pass 1 stores the tile's number of kept words and nothing else, an exclusive
+//            scan gives every tile its offset and the call the exact total, pass 2 repeats the extraction, ranks its kept words with wave
+//            ballots and writes (word, sample) at tile offset + rank.  No atomics, no overflow path, a deterministic order, and every
+//            allocation from here on is sized by what is KEPT (at the mode's default fraction 0.01: a hundredth of the positions).
+//   sort     two stable radix sorts over the kept words only (by word, then by sample), head flags, scan, compaction: the sorted unique
+//            words sample by sample, and the per-sample offsets.
+#include "kmdb_amd.h"
+#include "kmdb_internal.h"
+
+#include <hip/hip_runtime.h>
+#include "prim.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr uint32_t MH_R = 16;                      // positions per thread (a run)
+constexpr uint32_t MH_THREADS = 256;
+constexpr uint32_t MH_T = MH_THREADS * MH_R;       // positions per workgroup (a tile)
+constexpr uint32_t MH_PAD = 32;                    // bytes of '\n' in front of the text: the warm-up of the first run (k - 1 <= 30) reads them
+static_assert(MH_R == 16, "a run is one 16-byte LDS read");
+
+__device__ __forceinline__ uint64_t mh_mix64(uint64_t v) {
+    v ^= v >> 33; v *= 0xff51afd7ed558ccdull;
+    v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ull;
+    v ^= v >> 33;
+    return v;
+}
+
+struct MhParams {
+    const unsigned char* text;     // MH_PAD + n_tiles * MH_T bytes; position i is text[MH_PAD + i]
+    const int8_t* map;             // Alphabet::mapping (alphabet.h:41-58), 256 entries in device memory
+    const uint64_t* soff;          // [n_samples + 1] first position of every sample (sample s ends with the '\n' at soff[s + 1] - 1)
+    uint32_t n_samples;
+    uint32_t k, bits, size, widen;
+    int preserve, subsample;
+    uint64_t lo, hi;               // kmdbh_minhash_window
+    uint64_t seed;                 // 42 ^ ceil(k / 4): the part of the hash that does not depend on the word, folded on the host
+    uint64_t word_mask;            // 2^(bits * k) - 1
+};
+
+// WRITE == false: tile_cnt[tile] = kept words of the tile.  WRITE == true: (word, sample) of every kept word at tile_off[tile] + rank.
+template <bool WRITE>
+__global__ __launch_bounds__(MH_THREADS) void mh_extract_kernel(MhParams p, uint32_t* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_off,
+                                                                unsigned long long* __restrict__ kmer_out, uint32_t* __restrict__ sid_out) {
+    __shared__ int8_t tab[256];
+    __shared__ uint4 code4[(MH_PAD + MH_T) / 16];      // symbol codes of the positions [tile0 - MH_PAD, tile0 + MH_T), -1: no symbol
+    __shared__ uint32_t wave_cnt[MH_THREADS / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * MH_T;
+    tab[tid] = p.map[tid];
+    __syncthreads();
+    // (text + tile0 is the byte of position tile0 - MH_PAD: 16-byte aligned, MH_T and MH_PAD being multiples of 16)
+    const uint4* __restrict__ src = (const uint4*)(p.text + tile0);
+    for (uint32_t w = tid; w < (MH_PAD + MH_T) / 16; w += MH_THREADS) {
+        const uint4 v = src[w];
+        const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+        uint32_t o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            o[q] = (uint32_t)(uint8_t)tab[in[q] & 255u] | ((uint32_t)(uint8_t)tab[(in[q] >> 8) & 255u] << 8) |
+                   ((uint32_t)(uint8_t)tab[(in[q] >> 16) & 255u] << 16) | ((uint32_t)(uint8_t)tab[in[q] >> 24] << 24);
+        code4[w] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    __syncthreads();
+    const int8_t* code = (const int8_t*)code4;
+    const uint32_t r0 = MH_PAD + tid * MH_R;           // LDS index of the run's first position
+    const uint32_t top = p.bits * (p.k - 1);
+    uint64_t fwd = 0, rc = 0;
+    uint32_t valid = 0;                                // valid symbols since the last invalid one (a tile is far below 2^32 positions)
+    auto step = [&](int c) {
+        if (c < 0) { c = 0; valid = 0; } else ++valid;
+        fwd = ((fwd << p.bits) | (uint64_t)c) & p.word_mask;
+        rc = (rc >> p.bits) | ((uint64_t)(p.size - 1u - (uint32_t)c) << top);         // (kmer_extract.h:73; compared only where the strand is not preserved: nt)
+    };
+    for (uint32_t j = r0 - (p.k - 1); j < r0; ++j) step(code[j]);                    // warm-up: k - 1 <= MH_PAD - 2
+    const uint4 mine4 = code4[r0 / 16];
+    const uint32_t cw[4] = {mine4.x, mine4.y, mine4.z, mine4.w};
+    unsigned long long kv[WRITE ? MH_R : 1];
+    uint32_t rank[WRITE ? MH_R : 1];
+    uint32_t mine = 0;                                 // kept words of this wave so far (the same in all its lanes)
+#pragma unroll
+    for (uint32_t it = 0; it < MH_R; ++it) {
+        step((int)(int8_t)((cw[it / 4] >> (8 * (it % 4))) & 255u));
+        bool keep = valid >= p.k;
+        uint64_t w = 0;
+        if (keep) {
+            w = (p.preserve || fwd < rc) ? fwd : rc;
+            w = (w << p.widen) | (w & ((1ull << p.widen) - 1ull));
+            if (p.subsample) {                                                       // MinHashFilter (filter.h:96-115)
+                uint64_t a = w * 0x87c37b91114253d5ull;
+                a = (a << 31) | (a >> 33);
+                a *= 0x4cf5ad432745937full;
+                uint64_t h1 = a ^ p.seed, h2 = p.seed;
+                h1 += h2; h2 += h1;
+                h1 = mh_mix64(h1); h2 = mh_mix64(h2);
+                h1 += h2; h2 += h1;
+                const uint64_t h = h1 ^ h2;
+                keep = h >= p.lo && h < p.hi;
+            }
+        }
+        const unsigned long long bal = __ballot(keep);
+        if constexpr (WRITE) {
+            kv[it] = w;
+            rank[it] = keep ? mine + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)) : 0xFFFFFFFFu;
+        }
+        mine += (uint32_t)__popcll(bal);
+    }
+    if (lane == 0) wave_cnt[wv] = mine;
+    __syncthreads();
+    if constexpr (!WRITE) {
+        if (tid == 0) tile_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    } else {
+    uint64_t base = tile_off[blockIdx.x];
+    for (uint32_t w2 = 0; w2 < wv; ++w2) base += wave_cnt[w2];
+    // the sample of the run's first position; a kept word further on belongs to a later sample when its position passed that sample's end
+    const uint64_t pos0 = tile0 + (uint64_t)tid * MH_R;
+    uint32_t s = 0;
+    bool searched = false;
+#pragma unroll
+    for (uint32_t it = 0; it < MH_R; ++it) {
+        if (rank[it] == 0xFFFFFFFFu) continue;
+        const uint64_t pos = pos0 + it;
+        if (!searched) {
+            uint32_t a = 0, b = p.n_samples;           // the last sample with soff[s] <= pos (pos < soff[n_samples]: a kept position is a symbol of a sample)
+            while (b - a > 1) { const uint32_t mid = (a + b) / 2; if (p.soff[mid] <= pos) a = mid; else b = mid; }
+            s = a;
+            searched = true;
+        } else {
+            while (pos >= p.soff[s + 1]) ++s;          // (s + 1 <= n_samples, as above)
+        }
+        kmer_out[base + rank[it]] = kv[it];            // (base + rank < the scan's total = the size of both arrays)
+        sid_out[base + rank[it]] = s;
+    }
+    }
+}
+
+// head of a run of equal (sample, k-mer) among the sorted kept words
+__global__ void mh_heads_kernel(const unsigned long long* __restrict__ kmer, const uint32_t* __restrict__ sid, uint64_t n, uint32_t* __restrict__ head) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    head[i] = (i == 0 || sid[i - 1] != sid[i] || kmer[i - 1] != kmer[i]) ? 1u : 0u;
+}
+
+__global__ void mh_compact_kernel(const unsigned long long* __restrict__ kmer, const uint32_t* __restrict__ head, const uint32_t* __restrict__ hscan,
+                                  uint64_t n, uint64_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && head[i]) out[hscan[i]] = kmer[i];
+}
+
+// off[s] = number of unique k-mers of the samples before s = scanned heads at the first sorted word of a sample >= s
+__global__ void mh_sample_offsets_kernel(const uint32_t* __restrict__ sid, const uint32_t* __restrict__ hscan, uint64_t n, uint32_t n_samples,
+                                         uint64_t* __restrict__ off) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > n_samples) return;
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (sid[mid] < s) lo = mid + 1; else hi = mid; }
+    off[s] = hscan[lo];                            // hscan has n + 1 entries
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t b, uint64_t* account) {
+        bytes = std::max<size_t>(b, 16);
+        if (account) *account += bytes;
+        return hipMalloc(&p, bytes);
+    }
+    template <class T> T* as() { return (T*)p; }
+};
+struct Ev {
+    hipEvent_t e = nullptr;
+    ~Ev() { if (e) (void)hipEventDestroy(e); }
+};
+
+thread_local kmdb_minhash_stats g_stats;
+
+}  // namespace
+
+#define MH_TRY(expr)                                                                            \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
+    } while (0)
+
+// bases per piece (one longer sample still goes alone).  At fraction 1 the device holds about 42 bytes per base, and the kept
+// words of a piece — at most its bases — stay below 2^31, the size rocPRIM's sorts are given as an int here.
+static uint64_t mh_budget() {
+    if (const char* e = getenv("KMDB_MINHASH_BASES_PER_PIECE")) return std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    return 512ull << 20;
+}
+
+extern "C" void kmdb_minhash_geometry(uint32_t* positions_per_thread, uint32_t* positions_per_tile) {
+    if (positions_per_thread) *positions_per_thread = MH_R;
+    if (positions_per_tile) *positions_per_tile = MH_T;
+}
+
+extern "C" void kmdb_kmer_lists_free(kmdb_kmer_lists* lists) {
+    if (!lists) return;
+    free(lists->offsets);
+    free(lists->kmers);
+    lists->offsets = nullptr; lists->kmers = nullptr; lists->n_samples = 0;
+}
+
+extern "C" int kmdb_minhash_stats_get(kmdb_minhash_stats* out) {
+    if (!out) return kmdb_set_error("kmdb_minhash_stats_get: null argument");
+    *out = g_stats;
+    return 0;
+}
+
+// one piece: the samples [0, n) of the arguments; their unique words are appended to `kmers` (`total` words so far) and off[s + 1] is set
+static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, const MhParams& proto, const int8_t* d_map, hipStream_t st,
+                   uint64_t** kmers, uint64_t* total, uint64_t* off) {
+    std::vector<uint64_t> soff(n + 1, 0);
+    for (size_t s = 0; s < n; ++s) soff[s + 1] = soff[s] + seq_lens[s] + 1;        // (the '\n' behind every sample)
+    const uint64_t L = soff[n];
+    const uint64_t n_tiles = (L + MH_T - 1) / MH_T;
+    uint64_t scratch = 0;
+    DevBuf d_text, d_soff, d_cnt, d_off, d_kA, d_kB, d_sA, d_sB, d_head, d_hscan, d_uniq, d_uoff, d_tmp;
+    Ev ev[7];
+    for (auto& e : ev) MH_TRY(hipEventCreate(&e.e));
+    MH_TRY(hipEventRecord(ev[0].e, st));
+    const size_t text_bytes = MH_PAD + n_tiles * MH_T;
+    MH_TRY(d_text.alloc(text_bytes, &scratch));
+    MH_TRY(d_soff.alloc((n + 1) * 8, &scratch));
+    MH_TRY(d_cnt.alloc((n_tiles + 1) * 4, &scratch));
+    MH_TRY(d_off.alloc((n_tiles + 1) * 4, &scratch));
+    MH_TRY(d_uoff.alloc((n + 1) * 8, &scratch));
+    MH_TRY(hipMemsetAsync(d_text.p, '\n', text_bytes, st));
+    for (size_t s = 0; s < n; ++s)
+        if (seq_lens[s]) MH_TRY(hipMemcpyAsync(d_text.as<char>() + MH_PAD + soff[s], seqs[s], seq_lens[s], hipMemcpyHostToDevice, st));
+    MH_TRY(hipMemcpyAsync(d_soff.p, soff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    MH_TRY(hipMemsetAsync(d_cnt.p, 0, (n_tiles + 1) * 4, st));
+    MH_TRY(hipEventRecord(ev[1].e, st));
+    MhParams p = proto;
+    p.text = d_text.as<unsigned char>(); p.map = d_map; p.soff = d_soff.as<uint64_t>(); p.n_samples = (uint32_t)n;
+    // pass 1: the tiles' counts; their scan: every tile's offset and, in the entry behind the last tile, the total
+    hipLaunchKernelGGL(mh_extract_kernel<false>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, d_cnt.as<uint32_t>(), (const uint32_t*)nullptr,
+                       (unsigned long long*)nullptr, (uint32_t*)nullptr);
+    MH_TRY(hipGetLastError());
+    MH_TRY(hipEventRecord(ev[2].e, st));
+    size_t tb0 = 0;
+    MH_TRY(prim::exclusive_sum(nullptr, tb0, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n_tiles + 1, st));
+    MH_TRY(d_tmp.alloc(tb0, &scratch));
+    MH_TRY(prim::exclusive_sum(d_tmp.p, tb0, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n_tiles + 1, st));
+    uint32_t kept32 = 0;
+    MH_TRY(hipMemcpyAsync(&kept32, d_off.as<uint32_t>() + n_tiles, 4, hipMemcpyDeviceToHost, st));
+    MH_TRY(hipStreamSynchronize(st));
+    const uint64_t kept = kept32;
+    if (kept > L) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (more kept words than positions)");
+    MH_TRY(hipEventRecord(ev[3].e, st));
+    uint64_t n_unique = 0;
+    std::vector<uint64_t> uoff(n + 1, 0);
+    if (kept) {
+        MH_TRY(d_kA.alloc(kept * 8, &scratch)); MH_TRY(d_kB.alloc(kept * 8, &scratch));
+        MH_TRY(d_sA.alloc(kept * 4, &scratch)); MH_TRY(d_sB.alloc(kept * 4, &scratch));
+        MH_TRY(d_head.alloc((kept + 1) * 4, &scratch)); MH_TRY(d_hscan.alloc((kept + 1) * 4, &scratch));
+        unsigned long long *kA = d_kA.as<unsigned long long>(), *kB = d_kB.as<unsigned long long>();
+        uint32_t *sA = d_sA.as<uint32_t>(), *sB = d_sB.as<uint32_t>();
+        // pass 2: the same extraction, the kept words written at tile offset + rank
+        hipLaunchKernelGGL(mh_extract_kernel<true>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, (uint32_t*)nullptr, (const uint32_t*)d_off.as<uint32_t>(), kA, sA);
+        MH_TRY(hipGetLastError());
+        MH_TRY(hipEventRecord(ev[4].e, st));
+        const unsigned blocks = (unsigned)((kept + 255) / 256);
+        const int kbits = (int)std::min<uint32_t>(64u, p.bits * p.k + p.widen);
+        int sbits = 1;
+        while (sbits < 32 && (1ull << sbits) < n) ++sbits;          // the sample ids in use: only those bits are sorted
+        size_t tb1 = 0, tb2 = 0, tb3 = 0;
+        MH_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
+        MH_TRY(prim::sort_pairs(nullptr, tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));
+        MH_TRY(prim::exclusive_sum(nullptr, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(kept + 1), st));
+        DevBuf d_tmp2;
+        MH_TRY(d_tmp2.alloc(std::max(tb1, std::max(tb2, tb3)), &scratch));
+        MH_TRY(prim::sort_pairs(d_tmp2.p, tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
+        MH_TRY(prim::sort_pairs(d_tmp2.p, tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));     // stable: the words stay ascending inside a sample
+        MH_TRY(hipEventRecord(ev[5].e, st));
+        MH_TRY(hipMemsetAsync(d_head.p, 0, (kept + 1) * 4, st));
+        hipLaunchKernelGGL(mh_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, sA, kept, d_head.as<uint32_t>());
+        MH_TRY(prim::exclusive_sum(d_tmp2.p, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(kept + 1), st));
+        uint32_t nu32 = 0;
+        MH_TRY(hipMemcpyAsync(&nu32, d_hscan.as<uint32_t>() + kept, 4, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(mh_sample_offsets_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, sA, d_hscan.as<uint32_t>(), kept, (uint32_t)n,
+                           d_uoff.as<uint64_t>());
+        MH_TRY(hipGetLastError());
+        MH_TRY(hipStreamSynchronize(st));
+        n_unique = nu32;
+        if (n_unique > kept) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (more unique words than kept words)");
+        MH_TRY(d_uniq.alloc(n_unique * 8, &scratch));
+        hipLaunchKernelGGL(mh_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), kept, d_uniq.as<uint64_t>());
+        MH_TRY(hipGetLastError());
+        MH_TRY(hipMemcpyAsync(uoff.data(), d_uoff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_unique) * 8);
+        if (!grown) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: out of host memory");
+        *kmers = grown;
+        if (n_unique) MH_TRY(hipMemcpyAsync(grown + *total, d_uniq.p, n_unique * 8, hipMemcpyDeviceToHost, st));
+        MH_TRY(hipStreamSynchronize(st));
+        if (uoff[n] != n_unique) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (the sample offsets do not end at the unique count)");
+    } else {
+        MH_TRY(hipEventRecord(ev[4].e, st));
+        MH_TRY(hipEventRecord(ev[5].e, st));
+    }
+    MH_TRY(hipEventRecord(ev[6].e, st));
+    MH_TRY(hipEventSynchronize(ev[6].e));
+    for (size_t s = 0; s < n; ++s) off[s + 1] = *total + uoff[s + 1];
+    *total += n_unique;
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 6; ++i) MH_TRY(hipEventElapsedTime(&ms[i], ev[i].e, ev[i + 1].e));
+    g_stats.pieces += 1; g_stats.bases += L - n; g_stats.kept += kept; g_stats.unique += n_unique;
+    g_stats.scratch_bytes = std::max<uint64_t>(g_stats.scratch_bytes, scratch);
+    g_stats.h2d_ms += ms[0]; g_stats.count_ms += ms[1]; g_stats.scan_ms += ms[2]; g_stats.write_ms += ms[3]; g_stats.sort_ms += ms[4]; g_stats.unique_ms += ms[5];
+    return 0;
+}
+
+static int mh_batch(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t k, double fraction, double start_fraction, int32_t alphabet,
+                    kmdb_kmer_lists* out, const kmdb_opts* opts) {
+    const char* who = "kmdb_minhash_batch_seq_alphabet";
+    if (!out || (n_samples && (!seqs || !seq_lens))) return kmdb_set_error(std::string(who) + ": null argument");
+    out->n_samples = 0; out->offsets = nullptr; out->kmers = nullptr;
+    if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error(std::string(who) + ": unknown alphabet " + std::to_string(alphabet));
+    if (opts && opts->abi_version && !kmdb_abi_compatible(opts->abi_version)) return kmdb_set_error(std::string(who) + ": kmdb_opts.abi_version is not served by this library");
+    int8_t map[256];
+    MhParams p{};
+    if (kmdbh_alphabet_table(alphabet, map, &p.size, &p.bits, &p.preserve)) return kmdb_set_error(std::string(who) + ": unknown alphabet");
+    if (k == 0 || k > 64u / p.bits - 1u) return kmdb_set_error(std::string(who) + ": k-mer length must be 1.." + std::to_string(64u / p.bits - 1u) + " for this alphabet (alphabet.h:37)");
+    static_assert(MH_PAD >= 32, "the warm-up of a run reads k - 1 <= 30 codes in front of it");
+    if (n_samples >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": too many samples in one batch");
+    for (size_t s = 0; s < n_samples; ++s) {
+        if (seq_lens[s] && !seqs[s]) return kmdb_set_error(std::string(who) + ": null argument");
+        if (seq_lens[s] >= (1ull << 31) - 2) return kmdb_set_error(std::string(who) + ": a single sample of 2^31 bases or more; extract its k-mers on the host (kmdbh_extract_kmers_alphabet, kmdbh_sort_unique)");
+    }
+    g_stats = kmdb_minhash_stats{};
+    uint64_t* offsets = (uint64_t*)calloc(n_samples + 1, 8);
+    if (!offsets) return kmdb_set_error(std::string(who) + ": out of host memory");
+    uint64_t* kmers = nullptr;
+    uint64_t total = 0;
+    struct Guard { uint64_t*& a; uint64_t*& b; bool armed = true; ~Guard() { if (armed) { free(a); free(b); } } } guard{offsets, kmers};
+    if (n_samples) {
+        const int prefix_bits = (int)(p.bits * k) - 32;
+        p.k = k;
+        p.widen = prefix_bits < 8 ? (uint32_t)(8 - prefix_bits) : 0u;
+        p.subsample = fraction < 1.0;
+        kmdbh_minhash_window(fraction, start_fraction, &p.lo, &p.hi);               // src/filter.h:38-51; the host's one definition (host_kmers.cpp)
+        p.seed = 42ull ^ (uint64_t)std::ceil((double)k / 4.0);
+        p.word_mask = (1ull << (p.bits * k)) - 1ull;                                // (bits * k <= 63)
+        MH_TRY(hipSetDevice(opts ? opts->device : 0));
+        hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t) nullptr;
+        DevBuf d_map;
+        MH_TRY(d_map.alloc(256, nullptr));
+        MH_TRY(hipMemcpyAsync(d_map.p, map, 256, hipMemcpyHostToDevice, st));
+        MH_TRY(hipStreamSynchronize(st));                                           // (`map` lives on this frame)
+        // samples are independent: cut the batch where the accumulated bases pass the budget
+        const uint64_t budget = mh_budget();
+        for (size_t s0 = 0; s0 < n_samples;) {
+            size_t s1 = s0;
+            uint64_t bases = 0;
+            do { bases += seq_lens[s1] + 1; ++s1; } while (s1 < n_samples && bases + seq_lens[s1] + 1 <= budget && bases + seq_lens[s1] + 1 < (1ull << 31) - 2);
+            if (mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, d_map.as<int8_t>(), st, &kmers, &total, offsets + s0)) return 1;
+            s0 = s1;
+        }
+    }
+    if (!kmers) kmers = (uint64_t*)malloc(8);
+    if (!kmers) return kmdb_set_error(std::string(who) + ": out of host memory");
+    guard.armed = false;
+    out->n_samples = n_samples; out->offsets = offsets; out->kmers = kmers;
+    return 0;
+}
+
+extern "C" int kmdb_minhash_batch_seq_alphabet(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length, double fraction,
+                                               double start_fraction, int32_t alphabet, kmdb_kmer_lists* out, const kmdb_opts* opts) {
+    try {
+        return mh_batch(seqs, seq_lens, n_samples, kmer_length, fraction, start_fraction, alphabet, out, opts);
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string("kmdb_minhash_batch_seq_alphabet: ") + e.what());
+    }
+}

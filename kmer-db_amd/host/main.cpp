@@ -6,6 +6,7 @@
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
+//     kmer-db-amd minhash    [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] <samples>
 // mirroring the reference consoles (reference src/console_all2all.cpp, console_all2all_sparse.cpp,
 // console_new2all.cpp) around the calls that the C ABI replaces.  Options that only tune the
 // reference's CPU engine (-t, -rt, -buffer, -bubble-size) are accepted; -t also sizes the
@@ -765,16 +766,155 @@ std::string basename_of(const std::string& p) {
     return s == std::string::npos ? p : p.substr(s + 1);
 }
 
+const char* const KMC_REFUSAL = "KMC k-mer input (-from-kmers) is not supported by the GPU front-end";
+
+// <entry>.minhash as MihashedInputFile::open reads it (minhashed_input_file.h:58-84): false when it cannot be opened or is damaged
+bool load_minhash(const std::string& entry, std::vector<uint64_t>& kmers, uint32_t& k) {
+    uint64_t* p = nullptr;
+    size_t n = 0;
+    double f = 0;
+    if (kmdbh_minhash_load((entry + ".minhash").c_str(), &p, &n, &k, &f)) return false;
+    try { kmers.assign(p, p + n); } catch (...) { kmdbh_minhash_free(p); throw; }
+    kmdbh_minhash_free(p);
+    return true;
+}
+
+// ---- minhash (console_minhash.cpp:7-52, params.cpp:674-716): every sample's filtered, sorted, unique k-mers into <sample>.minhash --------
+// The loader + KmerHelper::sortAndUnique run on the device for a batch of samples at a time (kmdb_minhash_batch_seq_alphabet);
+// -host-extract — and a sample beyond the device loader's 32-bit positions — takes kmdbh_extract_kmers_alphabet + kmdbh_sort_unique and
+// never touches a device.  The files are MihashedInputFile::store's, byte for byte (kmdbh_minhash_store).
+int run_minhash(std::vector<std::string>& args, Common& c) {
+    if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    if (take_switch(args, "-multisample-fasta"))
+        throw std::runtime_error("minhash -multisample-fasta is not supported: the reference stores every sample of the file under the file's own name, and only the last one survives");
+    const bool host_extract = take_switch(args, "-host-extract");
+    double fraction = 0.01;                                        // the mode's own default (params.cpp:130-133)
+    uint32_t k = 18;
+    std::string v;
+    if (take_option(args, "-f", v)) { std::istringstream iss(v); if (!(iss >> fraction)) throw std::runtime_error("Unable to parse the fraction: " + v); }
+    take_option(args, "-f-start", v);                              // accepted and ignored: the mode's filter starts at 0 (console_minhash.cpp:19)
+    if (take_option(args, "-k", v)) k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+    int32_t alphabet = KMDB_ALPHABET_NT;
+    if (take_option(args, "-alphabet", v)) {
+        static const char* names[KMDB_ALPHABET_COUNT] = {"nt", "nt-preserve", "aa", "aa11_diamond", "aa12_mmseqs", "aa6_dayhoff"};      // alphabet.h:79-86
+        alphabet = -1;
+        for (int a = 0; a < KMDB_ALPHABET_COUNT; ++a) if (v == names[a]) alphabet = a;
+        if (alphabet < 0) throw std::runtime_error("Unknown alphabet: " + v);
+    }
+    if (take_switch(args, "-preserve-strand")) {
+        if (alphabet != KMDB_ALPHABET_NT) throw std::runtime_error("Switch -preserve-strand applies only to nt alphabet");
+        alphabet = KMDB_ALPHABET_NT_PRESERVE;
+    }
+    if (args.size() != 1) throw usage_error("minhash");
+    {
+        int8_t map[256];
+        uint32_t size = 0, bits = 0;
+        kmdbh_alphabet_table(alphabet, map, &size, &bits, nullptr);
+        if (k == 0 || k > 64u / bits - 1u) throw std::runtime_error("k-mer length must be 1.." + std::to_string(64u / bits - 1u) + " for this alphabet");
+    }
+    std::cerr << "Minhashing samples..." << std::endl;
+    // LoaderEx::configure (loader_ex.cpp:87-122): a FASTA file is one sample, anything else a list of samples
+    std::vector<std::string> entries;
+    bool is_fasta = false;
+    for (const char* ext : {".fa", ".fna", ".fasta", ".fastq", ".gz", ".fa.gz", ".fna.gz", ".fasta.gz", ".fastq.gz"}) {
+        const size_t n = std::strlen(ext);
+        if (args[0].size() >= n && args[0].compare(args[0].size() - n, n, ext) == 0) is_fasta = true;
+    }
+    if (is_fasta) entries.push_back(args[0]);
+    else {
+        std::ifstream lst(args[0]);
+        if (!lst) throw std::runtime_error("Unable to open input file " + args[0]);
+        for (std::string e; lst >> e;) entries.push_back(e);
+    }
+    const auto total0 = clk::now();
+    kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
+    const int nthreads = c.threads > 0 ? c.threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    struct Sample { std::string entry, text; std::vector<uint64_t> kmers; bool ok = false, on_host = false; };
+    auto store = [&](const std::string& entry, const uint64_t* km, size_t n) {
+        check(kmdbh_minhash_store((entry + ".minhash").c_str(), km, n, k, fraction));      // console_minhash.cpp:47
+    };
+    size_t stored = 0;
+    const size_t BATCH = 64, BATCH_BASES = 512u << 20;             // by count and by bases, as new2all batches its queries
+    for (size_t base = 0; base < entries.size();) {
+        // the next batch: read and split on a pool of threads (the host path extracts there too), in input order
+        const size_t cnt = std::min(BATCH, entries.size() - base);
+        std::vector<Sample> ss(cnt);
+        std::atomic<size_t> next{0};
+        std::atomic<int> failed{0};
+        auto worker = [&]() {
+            try {
+                for (size_t i; (i = next.fetch_add(1)) < cnt;) {
+                    Sample& s = ss[i];
+                    s.entry = entries[base + i];
+                    std::string data;
+                    if (!slurp(s.entry, data)) continue;
+                    std::vector<Record> recs;
+                    split_fasta(data, recs);
+                    size_t bytes = 0, total = 0;
+                    for (auto& r : recs) { bytes += r.seq.size() + 1; total += r.seq.size(); }
+                    s.on_host = host_extract || bytes >= LONG_QUERY_BASES;
+                    if (s.on_host) {
+                        s.kmers.resize(total + 1);
+                        size_t n = 0;
+                        for (auto& r : recs) n += kmdbh_extract_kmers_alphabet(r.seq.data(), r.seq.size(), k, alphabet, fraction, 0.0, s.kmers.data() + n);
+                        s.kmers.resize(kmdbh_sort_unique(s.kmers.data(), n));        // KmerHelper::sortAndUnique (console_minhash.cpp:40)
+                    } else {
+                        s.text.reserve(bytes);
+                        for (auto& r : recs) { s.text += r.seq; s.text += '\n'; }
+                    }
+                    s.ok = true;
+                }
+            } catch (...) { failed = 1; }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 0; t < std::min<int>(nthreads, (int)cnt); ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+        if (failed) throw std::runtime_error("out of memory while reading the samples");
+        // device calls over stretches of the batch of at most BATCH_BASES bases
+        for (size_t i0 = 0; i0 < cnt;) {
+            std::vector<size_t> idx;
+            size_t bases = 0, i1 = i0;
+            for (; i1 < cnt && (idx.empty() || bases + ss[i1].text.size() <= BATCH_BASES); ++i1)
+                if (ss[i1].ok && !ss[i1].on_host) { idx.push_back(i1); bases += ss[i1].text.size(); }
+            kmdb_kmer_lists lists{};
+            if (!idx.empty()) {
+                std::vector<const char*> ptrs(idx.size());
+                std::vector<size_t> lens(idx.size());
+                for (size_t t = 0; t < idx.size(); ++t) { ptrs[t] = ss[idx[t]].text.data(); lens[t] = ss[idx[t]].text.size(); }
+                check(kmdb_minhash_batch_seq_alphabet(ptrs.data(), lens.data(), idx.size(), k, fraction, 0.0, alphabet, &lists, &o));
+            }
+            struct FreeLists { kmdb_kmer_lists& l; ~FreeLists() { kmdb_kmer_lists_free(&l); } } free_lists{lists};
+            size_t t = 0;
+            for (size_t i = i0; i < i1; ++i) {
+                const Sample& s = ss[i];
+                if (!s.ok) { std::cerr << "failed:" << s.entry << std::endl; continue; }
+                if (s.on_host) store(s.entry, s.kmers.data(), s.kmers.size());
+                else { store(s.entry, lists.kmers + lists.offsets[t], (size_t)(lists.offsets[t + 1] - lists.offsets[t])); ++t; }
+                ++stored;
+            }
+            i0 = i1;
+        }
+        base += cnt;
+    }
+    std::cerr << stored << " of " << entries.size() << " samples minhashed" << std::endl;
+    std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
+    return 0;
+}
+
+
 // ---- new2all (console_new2all.cpp:12-174) ---------------------------------------------------------
 int run_new2all(std::vector<std::string>& args, Common& c) {
-    if (take_switch(args, "-from-kmers") || take_switch(args, "-from-minhash"))
-        throw std::runtime_error("only genome (FASTA) query input is supported by the GPU front-end");
+    if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    // -from-minhash: every list entry names <entry>.minhash; its words go to the k-mer entries AS STORED — the database's filter is not applied
+    // again (MihashedInputFile::load, minhashed_input_file.h:88-105)
+    const bool from_minhash = take_switch(args, "-from-minhash");
     const bool multi = take_switch(args, "-multisample-fasta");
+    if (multi && from_minhash) throw usage_error("new2all");
     const bool host_extract = take_switch(args, "-host-extract");   // k-mer extraction on the host instead of the device
     c.sparse = take_switch(args, "-sparse");
     if (c.sparse) c.filters.parse(args);
     if (args.size() != 3) throw usage_error("new2all");
-    std::cerr << "Set of new samples  (from genomes) versus entire database comparison" << std::endl;
+    std::cerr << "Set of new samples  (from " << (from_minhash ? "minhashed k-mers" : "genomes") << ") versus entire database comparison" << std::endl;
     Db db;
     std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
     auto t0 = clk::now();
@@ -954,6 +1094,14 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             std::atomic<size_t> next{0};
             auto worker = [&]() {
                 for (size_t i; (i = next.fetch_add(1)) < cntq;) {
+                    if (from_minhash) {
+                        uint32_t fk = 0;
+                        if (!load_minhash(entries[base + i], qs[i].kmers, fk)) continue;      // (cannot be opened, or damaged)
+                        qs[i].name = basename_of(entries[base + i]);
+                        qs[i].from_kmers = true;
+                        okv[i] = 1;
+                        continue;
+                    }
                     std::string data;
                     if (!slurp(entries[base + i], data)) continue;
                     std::vector<Record> recs;
@@ -983,10 +1131,11 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
 // Same engine call as new2all with a batch of one; the row is labelled with the path as given on the
 // command line and the file does not end with a newline (console_one2all.cpp:88-93).
 int run_one2all(std::vector<std::string>& args, Common& c) {
-    if (take_switch(args, "-from-kmers") || take_switch(args, "-from-minhash"))
-        throw std::runtime_error("only genome (FASTA) query input is supported by the GPU front-end");
+    if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    const bool from_minhash = take_switch(args, "-from-minhash");      // the sample argument names <sample>.minhash (console_one2all.cpp:55-58)
+    if (from_minhash && take_switch(args, "-multisample-fasta")) throw usage_error("one2all");
     if (args.size() != 3) throw usage_error("one2all");
-    std::cerr << "One new sample  (from genomes) versus entire database comparison" << std::endl;
+    std::cerr << "One new sample  (from " << (from_minhash ? "minhashed k-mers" : "genomes") << ") versus entire database comparison" << std::endl;
     Db db;
     std::cerr << "Loading k-mer database " << args[0] << ":" << std::endl;
     auto t0 = clk::now();
@@ -1003,7 +1152,12 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
     const int32_t alphabet = kmdbh_db_alphabet(db.h);
     if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) throw std::runtime_error("Invalid alphabet type");
     std::string data;
-    if (!slurp(args[1], data)) throw std::runtime_error("Cannot open sample file: " + args[1]);
+    std::vector<uint64_t> stored;
+    uint32_t stored_k = 0;
+    if (from_minhash) {
+        if (!load_minhash(args[1], stored, stored_k)) throw std::runtime_error("Cannot open sample file: " + args[1]);
+        if (stored_k != k) throw std::runtime_error("Sample and database k-mer length differ");      // console_one2all.cpp:67-69
+    } else if (!slurp(args[1], data)) throw std::runtime_error("Cannot open sample file: " + args[1]);
     std::vector<Record> recs;
     split_fasta(data, recs);
     // loader (kmer_extract.h, filter.h), KmerHelper::sortAndUnique (console_one2all.cpp:64-66) and one2all on the device;
@@ -1013,7 +1167,14 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
     uint64_t cnt = 0;
     std::vector<uint32_t> sims(n + 1);
     std::cerr << "Calculating similarity vector..." << std::endl;
-    if (bases < LONG_QUERY_BASES) {
+    if (from_minhash) {
+        // the words as stored: already sorted and unique (console_minhash.cpp:40), the total is the stored count
+        const uint64_t* kp = stored.data();
+        size_t kc = stored.size();
+        if (db.node) check(kmdb_node_new2all_batch(db.node, &kp, &kc, 1, sims.data(), nullptr));
+        else check(kmdb_new2all_batch(db.d, &kp, &kc, 1, sims.data(), &o));
+        cnt = kc;
+    } else if (bases < LONG_QUERY_BASES) {
         std::string text;
         text.reserve(bases);
         for (auto& r : recs) { text += r.seq; text += '\n'; }
@@ -1192,8 +1353,9 @@ void usage() {
                  "USAGE\n"
                  "    kmer-db-amd all2all [-sparse [-min [<criterion>:]<v>] [-max [<criterion>:]<v>]] <database> <common_table>\n"
                  "    kmer-db-amd all2all-sp [-min ...] [-max ...] <database> <common_table>\n"
-                 "    kmer-db-amd new2all [-multisample-fasta] [-sparse [-min ...] [-max ...]] <database> <sample_list> <common_table>\n"
-                 "    kmer-db-amd one2all <database> <sample> <similarity_vector>\n"
+                 "    kmer-db-amd new2all [-multisample-fasta | -from-minhash] [-sparse [-min ...] [-max ...]] <database> <sample_list> <common_table>\n"
+                 "    kmer-db-amd one2all [-from-minhash] <database> <sample> <similarity_vector>\n"
+                 "    kmer-db-amd minhash [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] [-preserve-strand] [-host-extract] <samples>\n"
                  "    kmer-db-amd all2all-parts [-min ...] [-max ...] <db_list> <common_table>\n"
                  "    kmer-db-amd distance [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* <measure> <common_table> <output>\n"
                  "Common options: -t <threads>, -gpu <device>\n"
@@ -1203,6 +1365,9 @@ void usage() {
                  "                                  database is read with its hashtables), or a range of the pattern tree (read without them)\n"
                  "new2all / one2all: -gpus <N>     the database in N query shards over the node's GPUs (from -gpu on): a shard holds the tree and the\n"
                  "                                  hashtable slots of its own prefix buckets; the rows of the shards are summed by one RCCL reduce-scatter\n"
+                 "                   -from-minhash the samples are <sample>.minhash files (written by the minhash mode): their k-mers are used as stored\n"
+                 "minhash: <samples> is a list of FASTA files (or one FASTA file); <sample>.minhash = its k-mers that pass the filter (-f, default 0.01),\n"
+                 "                   sorted and unique, extracted on the GPU; -host-extract extracts them on the host and needs no GPU\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
@@ -1241,6 +1406,7 @@ int main(int argc, char** argv) {
         if (mode == "one2all") return run_one2all(args, c);
         if (mode == "all2all-parts") return run_all2all_parts(args, c);
         if (mode == "distance") return run_distance(args);
+        if (mode == "minhash") return run_minhash(args, c);
         usage();
         return -1;
     } catch (usage_error&) {
