@@ -36,6 +36,9 @@ extern "C" {
 /* And the minhash mode: a k-mer extractor that needs no database (kmdb_minhash_batch_seq_alphabet and its helpers) and the reader / writer of
  * <sample>.minhash files (kmdbh_minhash_store, kmdbh_minhash_load): eight more entry points and two structs of their own, the version stays 8. */
 #define KMDB_HAS_MINHASH 1
+/* And the build mode: a database grown on the device from the samples' k-mer lists (kmdb_build_*) and the writer of .db files
+ * (kmdbh_db_store): seven more entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_BUILD 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -627,6 +630,60 @@ int  kmdbh_minhash_store(const char* path, const uint64_t* kmers, size_t count, 
  * *kmers is library-allocated: free with kmdbh_minhash_free() (no GPU). */
 int  kmdbh_minhash_load(const char* path, uint64_t** kmers, size_t* count, uint32_t* kmer_length, double* fraction);
 void kmdbh_minhash_free(uint64_t* kmers);
+
+/* ---------------------------------------------------------------------------------------
+ * The build mode (console_build.cpp): genomes in, a database out.  Additive in ABI 8 (KMDB_HAS_BUILD).
+ * The builder keeps the whole state of PrefixKmerDb on the device: the sorted dictionary of the distinct k-mers with the pattern id of each,
+ * the pattern fields, and one (pattern, sample) event per "sample appended to the pattern's local ids".  Samples take their ids in the order
+ * they are added; the pattern ids are those of the reference's addKmers run with ONE thread (prefix_kmer_db.cpp:181-240: the groups of a
+ * sample in ascending old pattern id, the group of the k-mers new to the database first).  How the samples are cut into calls changes nothing.
+ * Device memory: 12 bytes per distinct k-mer (twice that while a call merges new k-mers in), 24 per pattern, 8 per event, 36 per k-mer of
+ * the largest sample of a call; at finish 24 more per event, 36 more per pattern, the streams and the tables.  An allocation the device
+ * cannot serve is refused with the bytes it needed — the builder does not spill to the host — and leaves the builder DEAD: every later
+ * call but kmdb_build_free / kmdb_build_stats_get is refused.  So does any HIP error inside a call.  A refusal that is found before the
+ * state is touched (a list out of order, a sample too long, an add after finish) leaves the builder as it was.
+ * ------------------------------------------------------------------------------------- */
+typedef struct kmdb_builder kmdb_builder;
+typedef struct kmdb_build_stats {  /* the whole life of the builder so far */
+    uint64_t samples;              /* samples added (empty ones included) */
+    uint64_t kmers_added;          /* sum of the samples' list lengths */
+    uint64_t distinct_kmers;       /* size of the dictionary */
+    uint64_t patterns;             /* pattern 0 included */
+    uint64_t events;               /* (pattern, sample) pairs = sum of num_local over the patterns */
+    uint64_t peak_device_bytes;    /* most device memory the builder held at once */
+    double   merge_ms;             /* HIP events: new k-mers found and merged into the dictionary (once per call) */
+    double   lookup_ms;            /* ... per sample: position and pattern of every k-mer */
+    double   sort_ms;              /* ... per sample: radix sort by pattern */
+    double   group_ms;             /* ... per sample: groups, extend / new pattern, the k-mers' new ids */
+    double   encode_ms;            /* finish: events grouped by pattern, gamma streams */
+    double   tables_ms;            /* finish: the prefix-bucket hashtables */
+    double   copy_back_ms;         /* finish: everything to the host */
+} kmdb_build_stats;
+/* Replaces PrefixKmerDb's constructor + initialize (console_build.cpp:38-60; prefix_kmer_db.cpp:20-63).  fraction / start_fraction are the
+ * filter of the text entry and the values of the database's header (the reference's build always stores start 0, prefix_kmer_db.cpp:454:
+ * this library stores the start it used, so that new2all filters its queries with the builder's window).  opts: device and stream; NULL = device 0.
+ * Refused: an unknown alphabet, a k the alphabet cannot hold (alphabet.h:37). */
+int  kmdb_build_begin(uint32_t kmer_length, double fraction, double start_fraction, int32_t alphabet, const kmdb_opts* opts, kmdb_builder** out);
+/* Replaces one db.addKmers per sample (console_build.cpp:111; prefix_kmer_db.cpp:244-434) for n_samples samples: kmers[s] = the sample's k-mers,
+ * STRICTLY ascending (the stored words of a <sample>.minhash, or kmdbh_extract_kmers_alphabet + kmdbh_sort_unique) — uploaded as they are and
+ * checked on the device.  Refused before the builder's state changes: a list that is not strictly ascending, a sample of 2^32 k-mers or more
+ * (the reference's count is 32 bits; this builder indexes a sample's k-mers with 31), an add after finish. */
+int  kmdb_build_add_kmers(kmdb_builder* b, const char* const* names, const uint64_t* const* kmers, const size_t* counts, size_t n_samples);
+/* The same from text (console_build.cpp:111 with the loader in front of it, genome_input_file.h): seqs[s] = the sample's records joined by '\n',
+ * the form kmdb_minhash_batch_seq_alphabet takes.  Extracted, filtered with the builder's window, sorted and made unique on the device with
+ * that entry's own kernels; the lists never visit the host. */
+int  kmdb_build_add_seq_alphabet(kmdb_builder* b, const char* const* names, const char* const* seqs, const size_t* seq_lens, size_t n_samples);
+/* Replaces what PrefixKmerDb::serialize reads out of the live object (console_build.cpp:149; prefix_kmer_db.cpp:438-574): gamma streams, tables,
+ * everything copied into a kmdbh_db — free it with kmdbh_db_free; upload it (kmdb_db_upload(kmdbh_db_view(h), ...)) or store it.  The
+ * builder takes no more samples afterwards and can be finished once. */
+int  kmdb_build_finish(kmdb_builder* b, kmdbh_db** out);
+void kmdb_build_free(kmdb_builder* b);
+int  kmdb_build_stats_get(const kmdb_builder* b, kmdb_build_stats* out);
+/* PrefixKmerDb::serialize(file, true) (prefix_kmer_db.cpp:438-574; call site console_build.cpp:149): header fields :449-457, samples, raw tables
+ * (hashmap_lp.h:481-528), patterns in blocks of at most 64 MB cut by the reference's own rule (:545-569).  is_parent goes into bytes 32..35 of
+ * every pattern header, zeros into bytes 36..39 (the reference leaves those four unwritten: pattern.cpp:35-37).  Any kmdbh_db that holds its
+ * tables (kmdbh_db_load mode 0, kmdb_build_finish) can be stored; no GPU. */
+int  kmdbh_db_store(const kmdbh_db* db, const char* path);
 
 /* CSV text (console_all2all.cpp:40-78, console_new2all.cpp:99-160, conversion.h:246-298).
  * Each returns bytes written to `out` (caller sizes it: 10000 + 100*N like the reference). */

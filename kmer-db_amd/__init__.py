@@ -10,6 +10,7 @@ The directory is called ``kmer-db_amd`` (not importable by name); load it with
 """
 from .capi import (  # noqa: F401
     ABI_VERSION,
+    Builder,
     DeviceDB,
     HostDB,
     KmdbError,

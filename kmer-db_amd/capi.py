@@ -89,6 +89,12 @@ class _MinhashStats(C.Structure):
                 ("unique_ms", C.c_double)]
 
 
+class _BuildStats(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("kmers_added", C.c_uint64), ("distinct_kmers", C.c_uint64), ("patterns", C.c_uint64), ("events", C.c_uint64),
+                ("peak_device_bytes", C.c_uint64), ("merge_ms", C.c_double), ("lookup_ms", C.c_double), ("sort_ms", C.c_double), ("group_ms", C.c_double),
+                ("encode_ms", C.c_double), ("tables_ms", C.c_double), ("copy_back_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -117,6 +123,7 @@ EXPORTS = [
     "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
+    "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
 ]
 
 
@@ -241,6 +248,14 @@ def lib():
     L.kmdbh_minhash_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     L.kmdbh_minhash_free.restype = None
     L.kmdbh_minhash_free.argtypes = [C.POINTER(C.c_uint64)]
+    L.kmdb_build_begin.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.kmdb_build_add_kmers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.kmdb_build_add_seq_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.kmdb_build_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.kmdb_build_free.restype = None
+    L.kmdb_build_free.argtypes = [C.c_void_p]
+    L.kmdb_build_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildStats)]
+    L.kmdbh_db_store.argtypes = [C.c_void_p, C.c_char_p]
     L.kmdbh_format_header.restype = C.c_size_t
     L.kmdbh_format_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.kmdbh_format_dense_row.restype = C.c_size_t
@@ -275,9 +290,12 @@ def _opts(device=0, shard=(0, 1), flags=0, stream=None, bubble=0):
 class HostDB:
     """A .db file parsed by the front-end's reader (kmdbh_db_load)."""
 
-    def __init__(self, path, skip_hashtables=False):
+    def __init__(self, path, skip_hashtables=False, _handle=None):
         self._h = C.c_void_p()
-        _check(lib().kmdbh_db_load(os.fsencode(path), 2 if skip_hashtables else 0, C.byref(self._h)))
+        if _handle is not None:                    # a database made in memory (Builder.finish): the object owns the handle
+            self._h = _handle
+        else:
+            _check(lib().kmdbh_db_load(os.fsencode(path), 2 if skip_hashtables else 0, C.byref(self._h)))
         L = lib()
         self.N = int(L.kmdbh_db_n_samples(self._h))
         self.k = int(L.kmdbh_db_kmer_length(self._h))
@@ -337,6 +355,10 @@ class HostDB:
             out["bucket_offset"] = arr(v.bucket_offset, int(v.n_buckets) + 1, np.uint64)
             out["slots"] = arr(v.slots, int(out["bucket_offset"][-1]), np.uint64)
         return out
+
+    def store(self, path):
+        """kmdbh_db_store: the file PrefixKmerDb::serialize(file, true) writes; the database must hold its tables"""
+        _check(lib().kmdbh_db_store(self._h, os.fsencode(path)))
 
     def header_bytes(self):
         buf = C.create_string_buffer(20000 + 200 * self.N + sum(len(n) for n in self.names))
@@ -979,6 +1001,57 @@ def minhash_load(path):
     finally:
         lib().kmdbh_minhash_free(p)
     return words, int(k.value), float(f.value)
+
+
+class Builder:
+    """kmdb_build_*: a database grown on the device from the samples' k-mer lists or texts, in the order they are added.
+    finish() -> HostDB (upload it with DeviceDB, or .store(path) it)."""
+
+    def __init__(self, k, fraction=1.0, start_fraction=0.0, alphabet="nt", device=0, stream=None):
+        a = ALPHABETS.index(alphabet) if isinstance(alphabet, str) else int(alphabet)
+        self._b = C.c_void_p()
+        o = _opts(device, stream=stream)
+        _check(lib().kmdb_build_begin(int(k), float(fraction), float(start_fraction), a, C.byref(o), C.byref(self._b)))
+
+    @staticmethod
+    def _names(names):
+        bs = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        return bs, (C.c_char_p * max(len(bs), 1))(*bs)
+
+    def add_kmers(self, names, lists):
+        """strictly ascending uint64 lists, one per name (kmdb_build_add_kmers)"""
+        keep_n, nptr = self._names(names)
+        keep, ptrs, cnts, n = _kmer_queries(lists)
+        assert n == len(keep_n)
+        _check(lib().kmdb_build_add_kmers(self._b, nptr, ptrs, cnts, n))
+
+    def add_seqs(self, names, seqs):
+        """texts, records joined by '\n', extracted on the device with the builder's k / fraction / alphabet (kmdb_build_add_seq_alphabet)"""
+        keep_n, nptr = self._names(names)
+        keep, ptrs, lens, n = _text_queries(seqs)
+        assert n == len(keep_n)
+        _check(lib().kmdb_build_add_seq_alphabet(self._b, nptr, ptrs, lens, n))
+
+    def finish(self):
+        h = C.c_void_p()
+        _check(lib().kmdb_build_finish(self._b, C.byref(h)))
+        return HostDB(None, _handle=h)
+
+    def stats(self):
+        st = _BuildStats()
+        _check(lib().kmdb_build_stats_get(self._b, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _BuildStats._fields_}
+
+    def close(self):
+        if self._b:
+            lib().kmdb_build_free(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sort_unique(kmers):

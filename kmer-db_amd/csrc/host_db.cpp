@@ -364,6 +364,150 @@ static int db_load_impl(const char* path, int mode, kmdbh_db** out) {
     return 0;
 }
 
+static void db_set_view(kmdbh_db* db, uint64_t n_buckets) {
+    kmdb_db_view& v = db->view;
+    v.abi_version = KMDB_ABI_VERSION;
+    v.kmer_length = db->kmer_length;
+    v.n_samples = db->names.size();
+    v.n_patterns = db->num_kmers.size();
+    v.num_kmers = db->num_kmers.data();
+    v.parent_id = db->parent_id.data();
+    v.num_samples = db->num_samples.data();
+    v.num_local = db->num_local.data();
+    v.last_sample_id = db->last_id.data();
+    v.num_bits = db->num_bits.data();
+    v.data_offset = db->data_offset.data();
+    v.data = db->data.data();
+    v.n_data_words = db->data.size();
+    v.n_buckets = n_buckets;
+    v.bucket_offset = n_buckets ? db->bucket_offset.data() : nullptr;
+    v.slots = n_buckets ? db->slots.data() : nullptr;
+}
+
+kmdbh_db* kmdbh_db_make(uint32_t kmer_length, double fraction, double start_fraction, int32_t alphabet, uint64_t kmers_count,
+                        std::vector<std::string>&& names, std::vector<uint64_t>&& sample_kmers, uint64_t P, uint64_t n_words, uint64_t nb,
+                        uint64_t n_slots, kmdbh_db_arrays* a) {
+    auto* db = new (std::nothrow) kmdbh_db();
+    if (!db) { kmdb_set_error("kmdbh_db_make: out of memory"); return nullptr; }
+    db->format_word = 1;                              // SERIALIZATION_RAW_HASHTABLES: the one form kmdbh_db_load reads and kmdbh_db_store writes
+    db->kmer_length = kmer_length; db->fraction = fraction; db->start_fraction = start_fraction; db->alphabet = alphabet;
+    db->is_initialized = 1; db->kmers_count = kmers_count;
+    db->names = std::move(names); db->sample_kmers = std::move(sample_kmers);
+    if (!db->num_kmers.alloc(P) || !db->parent_id.alloc(P) || !db->num_samples.alloc(P) || !db->num_local.alloc(P) || !db->last_id.alloc(P) ||
+        !db->num_bits.alloc(P) || !db->data_offset.alloc(P) || !db->data.alloc(n_words + 2) || !db->bucket_offset.alloc(nb + 1) || !db->slots.alloc(n_slots)) {
+        delete db;
+        kmdb_set_error("kmdbh_db_make: out of memory");
+        return nullptr;
+    }
+    db->data[n_words] = 0; db->data[n_words + 1] = 0;
+    db->pattern_section_bytes = PAT_HEADER * P + 8 * n_words;
+    db_set_view(db, nb);
+    *a = kmdbh_db_arrays{db->num_kmers.data(), db->parent_id.data(), db->num_samples.data(), db->num_local.data(), db->last_id.data(), db->num_bits.data(),
+                         db->data_offset.data(), db->data.data(), db->bucket_offset.data(), db->slots.data()};
+    return db;
+}
+
+// ---- PrefixKmerDb::serialize(file, true) (prefix_kmer_db.cpp:438-574) ---------------------------------------------------------------
+namespace {
+struct Out {
+    FILE* f = nullptr;
+    bool ok = true;
+    ~Out() { if (f) std::fclose(f); }
+    void put(const void* p, size_t n) { if (ok && n && std::fwrite(p, 1, n, f) != n) ok = false; }
+    template <class T> void val(T v) { put(&v, sizeof v); }
+};
+constexpr size_t IO_BUFFER_BYTES = (size_t)64 << 20;   // prefix_kmer_db.h:179
+constexpr size_t SIZEOF_PATTERN_T = 48;                // the reference's split rule counts the in-memory object (pattern.h:83-85), not the 40 packed bytes
+}  // namespace
+
+static int db_store_impl(const kmdbh_db* db, const char* path) {
+    const kmdb_db_view& v = db->view;
+    if (!v.n_buckets || !v.bucket_offset || !v.slots)
+        return kmdb_set_error("kmdbh_db_store: the database holds no hashtables (it was loaded with SkipHashtables)");
+    Out o;
+    o.f = std::fopen(path, "wb");
+    if (!o.f) return kmdb_set_error(std::string("kmdbh_db_store: cannot open ") + path);
+    std::setvbuf(o.f, nullptr, _IOFBF, 1 << 22);
+    // :449-472
+    o.val<uint64_t>(db->format_word | 1ull);
+    o.val<uint32_t>(db->kmer_length);
+    o.val<double>(db->fraction);
+    o.val<double>(db->start_fraction);
+    o.val<int32_t>(db->alphabet);
+    o.val<uint8_t>(db->is_initialized);
+    o.val<uint64_t>(db->kmers_count);
+    o.val<uint64_t>(db->names.size());
+    for (size_t i = 0; i < db->names.size(); ++i) {
+        o.val<uint64_t>(db->sample_kmers[i]);
+        o.val<uint64_t>(db->names[i].size());
+        o.put(db->names[i].data(), db->names[i].size());
+    }
+    // the raw tables (hashmap_lp.h:481-528): every header field follows from the capacity and the fill — size_when_restruct is set with the
+    // capacity (:105, :154, :442), ht_memory is the bytes of the live array (:110-118, :452-461), ht_total / ht_match are never touched
+    o.val<uint64_t>(v.n_buckets);
+    std::vector<uint64_t> bv, items;
+    for (uint64_t b = 0; b < v.n_buckets; ++b) {
+        const uint64_t* s = v.slots + v.bucket_offset[b];
+        const uint64_t cap = v.bucket_offset[b + 1] - v.bucket_offset[b];
+        bv.assign((cap + 63) / 64, 0);
+        items.clear();
+        for (uint64_t i = 0; i < cap; ++i)
+            if ((int32_t)(s[i] >> 32) != INT32_MAX) { bv[i >> 6] |= 1ull << (i & 63); items.push_back(s[i]); }
+        o.val<double>(0.8);
+        o.val<uint64_t>(items.size());
+        o.val<uint64_t>(cap);
+        o.val<uint64_t>((uint64_t)((double)cap * 0.8));
+        o.val<uint64_t>(cap - 1);
+        o.val<uint64_t>(cap * 8);
+        o.val<uint64_t>(0);
+        o.val<uint64_t>(0);
+        o.put(bv.data(), bv.size() * 8);
+        o.put(items.data(), items.size() * 8);
+    }
+    // the patterns (:534-573, pattern.cpp:15-46).  is_parent is not part of the view: it is "some pattern names this one as its parent"
+    // (pattern.h:106-114 sets it when a child is made, nothing clears it)
+    const uint64_t P = v.n_patterns;
+    o.val<uint64_t>(P);
+    std::vector<uint8_t> is_parent(P, 0);
+    for (uint64_t p = 0; p < P; ++p)
+        if (v.parent_id[p] >= 0 && (uint64_t)v.parent_id[p] < P) is_parent[(size_t)v.parent_id[p]] = 1;
+    std::vector<char> block;
+    auto flush = [&]() {
+        o.val<uint64_t>(block.size());
+        o.put(block.data(), block.size());
+        block.clear();
+    };
+    for (uint64_t p = 0; p < P; ++p) {
+        const size_t data_bytes = v.num_bits[p] ? (size_t)(((uint64_t)v.num_bits[p] + 127) / 128) * 16 : 0;
+        if (block.size() + SIZEOF_PATTERN_T + data_bytes > IO_BUFFER_BYTES) flush();          // :552-557
+        char h[PAT_HEADER];
+        const uint32_t f[4] = {v.num_samples[p], v.num_local[p], v.last_sample_id[p], v.num_bits[p]};
+        const uint64_t isp = is_parent[p];            // 4 bytes written, 8 advanced (pattern.cpp:35-37): bytes 36..39 are zeros here
+        std::memcpy(h, &v.num_kmers[p], 8);
+        std::memcpy(h + 8, &v.parent_id[p], 8);
+        std::memcpy(h + 16, f, 16);
+        std::memcpy(h + 32, &isp, 8);
+        block.insert(block.end(), h, h + PAT_HEADER);
+        if (data_bytes) {
+            const char* d = (const char*)(v.data + v.data_offset[p]);
+            block.insert(block.end(), d, d + data_bytes);
+        }
+    }
+    flush();                                          // :567-569: the last block is written even when it is empty
+    if (o.ok && std::fflush(o.f) != 0) o.ok = false;
+    if (!o.ok) return kmdb_set_error(std::string("kmdbh_db_store: write error on ") + path);
+    return 0;
+}
+
+extern "C" int kmdbh_db_store(const kmdbh_db* db, const char* path) {
+    if (!db || !path) return kmdb_set_error("kmdbh_db_store: null argument");
+    try {
+        return db_store_impl(db, path);
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string("kmdbh_db_store: ") + e.what());
+    }
+}
+
 void kmdb_drop_pages(const std::vector<std::pair<void*, size_t>>& regions, unsigned threads) {
     const size_t page = 4096, step = (size_t)32 << 20;
     std::vector<std::pair<char*, size_t>> chunks;

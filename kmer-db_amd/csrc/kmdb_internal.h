@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -20,6 +21,28 @@ inline bool kmdb_abi_compatible(uint32_t caller) { return caller >= KMDB_ABI_OLD
 // of gigabytes holds the lock exclusively for as long as it frees pages.  The regions stay mapped (they read as zeros afterwards):
 // unmapping them later, or the end of the process, finds nothing left to free.
 void kmdb_drop_pages(const std::vector<std::pair<void*, size_t>>& regions, unsigned threads);
+
+// ---- host_db.cpp: a kmdbh_db made in memory instead of parsed from a file (build.hip: the result of kmdb_build_finish).  The arrays are
+// allocated at their final sizes (data: n_data_words + 2, the loader's padding pair, zeroed here) and handed out for the caller to fill;
+// the view is complete on return.  nullptr with the error set when the host is out of memory.
+struct kmdbh_db;
+struct kmdbh_db_arrays {
+    int64_t *num_kmers, *parent_id;
+    uint32_t *num_samples, *num_local, *last_sample_id, *num_bits;
+    uint64_t *data_offset, *data, *bucket_offset, *slots;
+};
+kmdbh_db* kmdbh_db_make(uint32_t kmer_length, double fraction, double start_fraction, int32_t alphabet, uint64_t kmers_count,
+                        std::vector<std::string>&& names, std::vector<uint64_t>&& sample_kmers, uint64_t n_patterns, uint64_t n_data_words,
+                        uint64_t n_buckets, uint64_t n_slots, kmdbh_db_arrays* arrays);
+
+// ---- minhash.hip: the extractor behind kmdb_minhash_batch_seq_alphabet with the lists LEFT ON THE DEVICE (build.hip adds them to its
+// tree from there).  The batch is cut into pieces as for the public entry; for every piece `sink` is called once, after the piece's last
+// kernel has ended: d_kmers = the sorted unique words of the piece's n samples, sample s at [off[s], off[s + 1]) (off in host memory,
+// off[0] = 0); the device buffer is released when the sink returns.  A non-zero return of the sink ends the call with that status.
+using kmdb_device_lists_sink = std::function<int(const uint64_t* d_kmers, const uint64_t* off, size_t n, void* stream)>;
+struct kmdb_opts;
+int kmdb_minhash_device_lists(const char* who, const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length, double fraction,
+                              double start_fraction, int32_t alphabet, const kmdb_opts* opts, const kmdb_device_lists_sink& sink);
 
 // ---- host_shards.cpp: the prefix shards of one database, planned on the host in ONE pass over its hashtables and ONE sweep over its
 // tree, for all shards at once (bucket = kmer >> 32, reference src/types.h:25-27; items src/hashmap_lp.h:71-78).

@@ -182,7 +182,8 @@ __global__ void mh_sample_offsets_kernel(const uint32_t* __restrict__ sid, const
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     hipError_t alloc(size_t b, uint64_t* account) {
         bytes = std::max<size_t>(b, 16);
         if (account) *account += bytes;
@@ -232,8 +233,9 @@ extern "C" int kmdb_minhash_stats_get(kmdb_minhash_stats* out) {
 }
 
 // one piece: the samples [0, n) of the arguments; their unique words are appended to `kmers` (`total` words so far) and off[s + 1] is set
+// (with a sink the words stay on the device: the sink reads them there and nothing of the piece's lists is copied to the host)
 static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, const MhParams& proto, const int8_t* d_map, hipStream_t st,
-                   uint64_t** kmers, uint64_t* total, uint64_t* off) {
+                   uint64_t** kmers, uint64_t* total, uint64_t* off, const kmdb_device_lists_sink* sink) {
     std::vector<uint64_t> soff(n + 1, 0);
     for (size_t s = 0; s < n; ++s) soff[s + 1] = soff[s] + seq_lens[s] + 1;        // (the '\n' behind every sample)
     const uint64_t L = soff[n];
@@ -312,10 +314,12 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
         hipLaunchKernelGGL(mh_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), kept, d_uniq.as<uint64_t>());
         MH_TRY(hipGetLastError());
         MH_TRY(hipMemcpyAsync(uoff.data(), d_uoff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-        uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_unique) * 8);
-        if (!grown) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: out of host memory");
-        *kmers = grown;
-        if (n_unique) MH_TRY(hipMemcpyAsync(grown + *total, d_uniq.p, n_unique * 8, hipMemcpyDeviceToHost, st));
+        if (!sink) {
+            uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_unique) * 8);
+            if (!grown) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: out of host memory");
+            *kmers = grown;
+            if (n_unique) MH_TRY(hipMemcpyAsync(grown + *total, d_uniq.p, n_unique * 8, hipMemcpyDeviceToHost, st));
+        }
         MH_TRY(hipStreamSynchronize(st));
         if (uoff[n] != n_unique) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (the sample offsets do not end at the unique count)");
     } else {
@@ -324,6 +328,11 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
     }
     MH_TRY(hipEventRecord(ev[6].e, st));
     MH_TRY(hipEventSynchronize(ev[6].e));
+    if (sink) {
+        // the sorts' double buffers and the flags are done with: the sink's own work gets their memory
+        for (DevBuf* b : {&d_kA, &d_kB, &d_sA, &d_sB, &d_head, &d_hscan, &d_text, &d_cnt, &d_off}) b->release();
+        if (const int rc = (*sink)(d_uniq.as<uint64_t>(), uoff.data(), n, (void*)st)) return rc;
+    }
     for (size_t s = 0; s < n; ++s) off[s + 1] = *total + uoff[s + 1];
     *total += n_unique;
     float ms[6] = {0, 0, 0, 0, 0, 0};
@@ -334,11 +343,11 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
     return 0;
 }
 
-static int mh_batch(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t k, double fraction, double start_fraction, int32_t alphabet,
-                    kmdb_kmer_lists* out, const kmdb_opts* opts) {
-    const char* who = "kmdb_minhash_batch_seq_alphabet";
-    if (!out || (n_samples && (!seqs || !seq_lens))) return kmdb_set_error(std::string(who) + ": null argument");
-    out->n_samples = 0; out->offsets = nullptr; out->kmers = nullptr;
+// out: the lists on the host (the public entry); sink: the lists on the device, piece by piece (kmdb_minhash_device_lists) — one of the two
+static int mh_batch(const char* who, const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t k, double fraction, double start_fraction,
+                    int32_t alphabet, kmdb_kmer_lists* out, const kmdb_opts* opts, const kmdb_device_lists_sink* sink) {
+    if ((!out && !sink) || (n_samples && (!seqs || !seq_lens))) return kmdb_set_error(std::string(who) + ": null argument");
+    if (out) { out->n_samples = 0; out->offsets = nullptr; out->kmers = nullptr; }
     if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error(std::string(who) + ": unknown alphabet " + std::to_string(alphabet));
     if (opts && opts->abi_version && !kmdb_abi_compatible(opts->abi_version)) return kmdb_set_error(std::string(who) + ": kmdb_opts.abi_version is not served by this library");
     int8_t map[256];
@@ -377,10 +386,11 @@ static int mh_batch(const char* const* seqs, const size_t* seq_lens, size_t n_sa
             size_t s1 = s0;
             uint64_t bases = 0;
             do { bases += seq_lens[s1] + 1; ++s1; } while (s1 < n_samples && bases + seq_lens[s1] + 1 <= budget && bases + seq_lens[s1] + 1 < (1ull << 31) - 2);
-            if (mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, d_map.as<int8_t>(), st, &kmers, &total, offsets + s0)) return 1;
+            if (const int rc = mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, d_map.as<int8_t>(), st, &kmers, &total, offsets + s0, sink)) return rc;
             s0 = s1;
         }
     }
+    if (sink) return 0;                            // (the guard frees the offsets; no words came to the host)
     if (!kmers) kmers = (uint64_t*)malloc(8);
     if (!kmers) return kmdb_set_error(std::string(who) + ": out of host memory");
     guard.armed = false;
@@ -391,8 +401,13 @@ static int mh_batch(const char* const* seqs, const size_t* seq_lens, size_t n_sa
 extern "C" int kmdb_minhash_batch_seq_alphabet(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length, double fraction,
                                                double start_fraction, int32_t alphabet, kmdb_kmer_lists* out, const kmdb_opts* opts) {
     try {
-        return mh_batch(seqs, seq_lens, n_samples, kmer_length, fraction, start_fraction, alphabet, out, opts);
+        return mh_batch("kmdb_minhash_batch_seq_alphabet", seqs, seq_lens, n_samples, kmer_length, fraction, start_fraction, alphabet, out, opts, nullptr);
     } catch (const std::exception& e) {
         return kmdb_set_error(std::string("kmdb_minhash_batch_seq_alphabet: ") + e.what());
     }
+}
+
+int kmdb_minhash_device_lists(const char* who, const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length, double fraction,
+                              double start_fraction, int32_t alphabet, const kmdb_opts* opts, const kmdb_device_lists_sink& sink) {
+    return mh_batch(who, seqs, seq_lens, n_samples, kmer_length, fraction, start_fraction, alphabet, nullptr, opts, &sink);
 }

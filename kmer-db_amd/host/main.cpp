@@ -7,6 +7,7 @@
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
 //     kmer-db-amd minhash    [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] <samples>
+//     kmer-db-amd build      [-k <kmer-length>] [-f <fraction>] [-alphabet <name>] [-multisample-fasta | -from-minhash] <samples> <db>
 // mirroring the reference consoles (reference src/console_all2all.cpp, console_all2all_sparse.cpp,
 // console_new2all.cpp) around the calls that the C ABI replaces.  Options that only tune the
 // reference's CPU engine (-t, -rt, -buffer, -bubble-size) are accepted; -t also sizes the
@@ -902,6 +903,177 @@ int run_minhash(std::vector<std::string>& args, Common& c) {
 }
 
 
+// ---- build (console_build.cpp:33-158, params.cpp:459-513, loader_ex.cpp:86-124, 165-168): genomes (or <sample>.minhash files) in, a database out ----
+// db.addKmers per sample (:111) is kmdb_build_add_seq_alphabet / kmdb_build_add_kmers for a batch of samples, serialize (:149) is
+// kmdb_build_finish + kmdbh_db_store.  The samples take their ids in input order; a file that cannot be opened prints "failed:<path>" and takes none.
+int run_build(std::vector<std::string>& args, Common& c) {
+    const bool from_kmers = take_switch(args, "-from-kmers"), from_minhash = take_switch(args, "-from-minhash");
+    if (from_kmers && from_minhash) throw std::runtime_error("-from-kmers and -from-minhash switches exclude one another.");      // params.cpp:499-502
+    if (from_kmers) throw std::runtime_error(KMC_REFUSAL);
+    if (take_switch(args, "-extend")) throw std::runtime_error("build -extend is not supported: rebuild from the sample list");
+    const bool host_extract = take_switch(args, "-host-extract");
+    double fraction = 1.0, fstart = 0.0;
+    uint32_t k = 18;
+    int32_t alphabet = KMDB_ALPHABET_NT;
+    bool multi = false;
+    std::string v;
+    if (!from_minhash) {
+        if (take_option(args, "-f", v)) { std::istringstream iss(v); if (!(iss >> fraction)) throw std::runtime_error("Unable to parse the fraction: " + v); }
+        if (take_option(args, "-f-start", v)) { std::istringstream iss(v); if (!(iss >> fstart)) throw std::runtime_error("Unable to parse the start fraction: " + v); }
+        multi = take_switch(args, "-multisample-fasta");
+        if (take_option(args, "-alphabet", v)) {
+            static const char* names[KMDB_ALPHABET_COUNT] = {"nt", "nt-preserve", "aa", "aa11_diamond", "aa12_mmseqs", "aa6_dayhoff"};      // alphabet.h:79-86
+            alphabet = -1;
+            for (int a = 0; a < KMDB_ALPHABET_COUNT; ++a) if (v == names[a]) alphabet = a;
+            if (alphabet < 0) throw std::runtime_error("Unknown alphabet: " + v);
+        }
+        if (take_switch(args, "-preserve-strand")) {
+            if (alphabet != KMDB_ALPHABET_NT) throw std::runtime_error("Switch -preserve-strand applies only to nt alphabet");
+            alphabet = KMDB_ALPHABET_NT_PRESERVE;
+        }
+        if (take_option(args, "-k", v)) k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        int8_t map[256];
+        uint32_t size = 0, bits = 0;
+        kmdbh_alphabet_table(alphabet, map, &size, &bits, nullptr);
+        if (k == 0 || k > 64u / bits - 1u) throw std::runtime_error("K-mer length for the given alphabet cannot exceed " + std::to_string(64u / bits - 1u));
+    }
+    if (args.size() != 2) throw usage_error("build");
+    std::cerr << "Building database (from " << (from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
+    // LoaderEx::configure (loader_ex.cpp:87-122): a FASTA file is one input file, anything else a list of them
+    std::vector<std::string> entries;
+    bool is_fasta = false;
+    for (const char* ext : {".fa", ".fna", ".fasta", ".fastq", ".gz", ".fa.gz", ".fna.gz", ".fasta.gz", ".fastq.gz"}) {
+        const size_t n = std::strlen(ext);
+        if (args[0].size() >= n && args[0].compare(args[0].size() - n, n, ext) == 0) is_fasta = true;
+    }
+    if (is_fasta) entries.push_back(args[0]);
+    else {
+        std::ifstream lst(args[0]);
+        if (!lst) throw std::runtime_error("Unable to open input file " + args[0]);
+        for (std::string e; lst >> e;) entries.push_back(e);
+    }
+    std::cerr << "Processing samples..." << std::endl;
+    const auto total0 = clk::now();
+    double extract_s = 0, update_s = 0;
+    kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
+    const int nthreads = c.threads > 0 ? c.threads : (int)std::max(1u, std::thread::hardware_concurrency());
+    struct Builder { kmdb_builder* b = nullptr; ~Builder() { kmdb_build_free(b); } } bld;
+    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } built;
+    struct Sample { std::string name, text; std::vector<uint64_t> kmers; bool on_host = false; };
+    struct File { std::string entry; std::vector<Sample> samples; bool ok = false; uint32_t k = 0; double fraction = 0; };
+    size_t added = 0;
+    const size_t BATCH = 64, BATCH_BASES = 512u << 20;             // by count and by bases, as the minhash mode batches its samples
+    for (size_t base = 0; base < entries.size();) {
+        const size_t cnt = std::min(BATCH, entries.size() - base);
+        std::vector<File> files(cnt);
+        std::atomic<size_t> next{0};
+        std::atomic<int> failed{0};
+        const auto t_read = clk::now();
+        auto worker = [&]() {
+            try {
+                for (size_t i; (i = next.fetch_add(1)) < cnt;) {
+                    File& f = files[i];
+                    f.entry = entries[base + i];
+                    if (from_minhash) {
+                        Sample s;
+                        s.on_host = true;
+                        s.name = basename_of(f.entry);
+                        uint64_t* p = nullptr;
+                        size_t n = 0;
+                        if (kmdbh_minhash_load((f.entry + ".minhash").c_str(), &p, &n, &f.k, &f.fraction)) continue;
+                        try { s.kmers.assign(p, p + n); } catch (...) { kmdbh_minhash_free(p); throw; }
+                        kmdbh_minhash_free(p);
+                        f.samples.push_back(std::move(s));
+                        f.ok = true;
+                        continue;
+                    }
+                    std::string data;
+                    if (!slurp(f.entry, data)) continue;
+                    std::vector<Record> recs;
+                    split_fasta(data, recs);
+                    // one sample per file, named after the file (loader_ex.cpp:165-168) — or, with -multisample-fasta, one per record, named by its header
+                    const size_t ns = multi ? recs.size() : 1;
+                    for (size_t r0 = 0; r0 < ns; ++r0) {
+                        const size_t r1 = multi ? r0 + 1 : recs.size();
+                        Sample s;
+                        s.name = multi ? recs[r0].header : basename_of(f.entry);
+                        size_t bytes = 0, total = 0;
+                        for (size_t r = r0; r < r1; ++r) { bytes += recs[r].seq.size() + 1; total += recs[r].seq.size(); }
+                        s.on_host = host_extract || bytes >= LONG_QUERY_BASES;
+                        if (s.on_host) {
+                            s.kmers.resize(total + 1);
+                            size_t n = 0;
+                            for (size_t r = r0; r < r1; ++r) n += kmdbh_extract_kmers_alphabet(recs[r].seq.data(), recs[r].seq.size(), k, alphabet, fraction, fstart, s.kmers.data() + n);
+                            s.kmers.resize(kmdbh_sort_unique(s.kmers.data(), n));      // console_build.cpp:97-102
+                        } else {
+                            s.text.reserve(bytes);
+                            for (size_t r = r0; r < r1; ++r) { s.text += recs[r].seq; s.text += '\n'; }
+                        }
+                        f.samples.push_back(std::move(s));
+                    }
+                    f.ok = true;
+                }
+            } catch (...) { failed = 1; }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 0; t < std::min<int>(nthreads, (int)cnt); ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+        if (failed) throw std::runtime_error("out of memory while reading the samples");
+        extract_s += since(t_read);
+        // the batch's samples in input order
+        std::vector<Sample*> ss;
+        for (File& f : files) {
+            if (!f.ok) { std::cerr << "failed:" << f.entry << std::endl; continue; }
+            if (from_minhash) {
+                if (!bld.b) { k = f.k; fraction = f.fraction; }
+                // AbstractKmerDb::addKmers (kmer_db.h:116-121)
+                if (f.k != k) throw std::runtime_error("Error in AbstractKmerDb::addKmers(): adding kmers of different length");
+                if (f.fraction != fraction) throw std::runtime_error("Error in AbstractKmerDb::addKmers(): adding kmers of different minhash fraction");
+            }
+            if (!bld.b) check(kmdb_build_begin(k, fraction, fstart, alphabet, &o, &bld.b));
+            for (Sample& s : f.samples) ss.push_back(&s);
+        }
+        // stretches of one kind (text: at most BATCH_BASES bases), one call each: the sample ids follow the input order
+        const auto t_add = clk::now();
+        for (size_t i0 = 0; i0 < ss.size();) {
+            size_t i1 = i0, bases = 0;
+            const bool on_host = ss[i0]->on_host;
+            for (; i1 < ss.size() && ss[i1]->on_host == on_host && (on_host || i1 == i0 || bases + ss[i1]->text.size() <= BATCH_BASES); ++i1) bases += ss[i1]->text.size();
+            const size_t m = i1 - i0;
+            std::vector<const char*> names(m);
+            for (size_t t = 0; t < m; ++t) names[t] = ss[i0 + t]->name.c_str();
+            if (on_host) {
+                std::vector<const uint64_t*> ptrs(m);
+                std::vector<size_t> kc(m);
+                for (size_t t = 0; t < m; ++t) { ptrs[t] = ss[i0 + t]->kmers.data(); kc[t] = ss[i0 + t]->kmers.size(); }
+                check(kmdb_build_add_kmers(bld.b, names.data(), ptrs.data(), kc.data(), m));
+            } else {
+                std::vector<const char*> ptrs(m);
+                std::vector<size_t> lens(m);
+                for (size_t t = 0; t < m; ++t) { ptrs[t] = ss[i0 + t]->text.data(); lens[t] = ss[i0 + t]->text.size(); }
+                check(kmdb_build_add_seq_alphabet(bld.b, names.data(), ptrs.data(), lens.data(), m));
+            }
+            added += m;
+            i0 = i1;
+        }
+        update_s += since(t_add);
+        base += cnt;
+    }
+    std::cerr << added << "/" << added << "                      " << std::endl;
+    if (!bld.b) throw std::runtime_error("no sample could be read: the database would be empty");
+    std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl
+              << "Kmer sorting/unique time: " << extract_s << std::endl << "Database update time:" << update_s << std::endl;
+    check(kmdb_build_finish(bld.b, &built.h));
+    kmdb_build_stats st{};
+    if (std::getenv("KMDB_VERBOSE") && !kmdb_build_stats_get(bld.b, &st))
+        std::cerr << "[kmdb] build: " << st.samples << " samples, " << st.kmers_added << " k-mers, " << st.distinct_kmers << " distinct, " << st.patterns << " patterns, "
+                  << st.events << " events, peak " << st.peak_device_bytes << " device bytes; merge " << st.merge_ms << " lookup " << st.lookup_ms << " sort " << st.sort_ms
+                  << " group " << st.group_ms << " encode " << st.encode_ms << " tables " << st.tables_ms << " copy-back " << st.copy_back_ms << " ms" << std::endl;
+    std::cerr << "Serializing database..." << std::endl;
+    check(kmdbh_db_store(built.h, args[1].c_str()));
+    return 0;
+}
+
 // ---- new2all (console_new2all.cpp:12-174) ---------------------------------------------------------
 int run_new2all(std::vector<std::string>& args, Common& c) {
     if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
@@ -1356,6 +1528,8 @@ void usage() {
                  "    kmer-db-amd new2all [-multisample-fasta | -from-minhash] [-sparse [-min ...] [-max ...]] <database> <sample_list> <common_table>\n"
                  "    kmer-db-amd one2all [-from-minhash] <database> <sample> <similarity_vector>\n"
                  "    kmer-db-amd minhash [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] [-preserve-strand] [-host-extract] <samples>\n"
+                 "    kmer-db-amd build [-k <kmer-length>] [-f <fraction>] [-f-start <v>] [-alphabet <name>] [-preserve-strand] [-multisample-fasta] [-host-extract] <sample_list | fasta> <database>\n"
+                 "    kmer-db-amd build -from-minhash <sample_list> <database>\n"
                  "    kmer-db-amd all2all-parts [-min ...] [-max ...] <db_list> <common_table>\n"
                  "    kmer-db-amd distance [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* <measure> <common_table> <output>\n"
                  "Common options: -t <threads>, -gpu <device>\n"
@@ -1368,6 +1542,8 @@ void usage() {
                  "                   -from-minhash the samples are <sample>.minhash files (written by the minhash mode): their k-mers are used as stored\n"
                  "minhash: <samples> is a list of FASTA files (or one FASTA file); <sample>.minhash = its k-mers that pass the filter (-f, default 0.01),\n"
                  "                   sorted and unique, extracted on the GPU; -host-extract extracts them on the host and needs no GPU\n"
+                 "build: the database is grown on the GPU from the samples in input order and written in the reference's format; -from-minhash takes\n"
+                 "                   <sample>.minhash files (k and fraction from the files); -extend and -from-kmers are refused\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
@@ -1407,6 +1583,7 @@ int main(int argc, char** argv) {
         if (mode == "all2all-parts") return run_all2all_parts(args, c);
         if (mode == "distance") return run_distance(args);
         if (mode == "minhash") return run_minhash(args, c);
+        if (mode == "build") return run_build(args, c);
         usage();
         return -1;
     } catch (usage_error&) {
