@@ -39,6 +39,9 @@ extern "C" {
 /* And the build mode: a database grown on the device from the samples' k-mer lists (kmdb_build_*) and the writer of .db files
  * (kmdbh_db_store): seven more entry points and one struct of their own, the version stays 8. */
 #define KMDB_HAS_BUILD 1
+/* And the seed of the build mode: a builder that starts from a stored database (kmdb_build_begin_from_db, kmdb_build_seed_stats_get): two more
+ * entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_BUILD_SEED 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -664,6 +667,33 @@ typedef struct kmdb_build_stats {  /* the whole life of the builder so far */
  * this library stores the start it used, so that new2all filters its queries with the builder's window).  opts: device and stream; NULL = device 0.
  * Refused: an unknown alphabet, a k the alphabet cannot hold (alphabet.h:37). */
 int  kmdb_build_begin(uint32_t kmer_length, double fraction, double start_fraction, int32_t alphabet, const kmdb_opts* opts, kmdb_builder** out);
+/* Replaces db->deserialize followed by the filter and alphabet taken from the database (console_build.cpp:48-57: `build -extend`): a builder whose
+ * state is the one a builder holds after the samples of `db` were added one by one — so that extending build(A) with the samples B gives the file
+ * build(A followed by B) gives.  k, fraction, start fraction, alphabet, sample names and per-sample k-mer counts are the database's; new samples
+ * are numbered from its n_samples on; kmdb_build_add_*, kmdb_build_finish, kmdb_build_free and kmdb_build_stats_get behave as on that builder
+ * (kmdb_build_stats: samples / distinct_kmers / patterns / events / peak_device_bytes include the seed, kmers_added and the stage times count
+ * only the add calls).  Everything happens on the device: the tables' items are compacted to (k-mer, pattern id) pairs and sorted into the
+ * dictionary, is_parent — which a stored database does not carry — is recomputed from parent_id, and every pattern's gamma stream is decoded
+ * into its (pattern, sample) events.  Any numbering of the patterns with parent_id[p] < p is taken (a database the reference built with several
+ * threads).  `db` must hold its tables (kmdbh_db_load mode 0, or the result of kmdb_build_finish) and is only read; it may be freed afterwards.
+ * Refused before any device work: a database without tables, 2^31 patterns, events or distinct k-mers or more, a bucket count that is not the
+ * one of k.  Refused after the device's checks, each with its own message: a table value that is 0 or no pattern id, a k-mer stored twice or
+ * wider than k symbols, k-mers per pattern that differ from num_kmers, a stream that does not end at num_bits or lies outside the data words,
+ * sample ids that do not ascend below n_samples, parent_id[p] >= p.  Every stream read is clamped to the pattern's own words: a damaged file
+ * is a refusal, never a fault.  Device memory is accounted and limited as for every builder (KMDB_BUILD_DEVICE_BYTES); the slots go up in
+ * pieces of KMDB_BUILD_SEED_SLOTS_PER_PIECE (default 2^27).  On any refusal *out stays NULL and nothing is left allocated. */
+int  kmdb_build_begin_from_db(const kmdbh_db* db, const kmdb_opts* opts, kmdb_builder** out);
+typedef struct kmdb_build_seed_stats {   /* what kmdb_build_begin_from_db did (zeros on a builder made by kmdb_build_begin) */
+    uint64_t samples, distinct_kmers, patterns, events;   /* of the seed */
+    uint64_t slots;                /* slots of the database's tables that went through the device */
+    uint64_t h2d_bytes;            /* bytes copied to the device */
+    double   upload_ms;            /* HIP events: the host-to-device copies */
+    double   dict_ms;              /* ... flag, scan, compaction of the slots; the sort into the dictionary */
+    double   tree_ms;              /* ... is_parent from parent_id */
+    double   decode_ms;            /* ... scan of num_local, the gamma streams decoded into events (their checks included) */
+    double   check_ms;             /* ... the dictionary's order and width, k-mers per pattern against num_kmers */
+} kmdb_build_seed_stats;
+int  kmdb_build_seed_stats_get(const kmdb_builder* b, kmdb_build_seed_stats* out);
 /* Replaces one db.addKmers per sample (console_build.cpp:111; prefix_kmer_db.cpp:244-434) for n_samples samples: kmers[s] = the sample's k-mers,
  * STRICTLY ascending (the stored words of a <sample>.minhash, or kmdbh_extract_kmers_alphabet + kmdbh_sort_unique) — uploaded as they are and
  * checked on the device.  Refused before the builder's state changes: a list that is not strictly ascending, a sample of 2^32 k-mers or more

@@ -95,6 +95,12 @@ class _BuildStats(C.Structure):
                 ("encode_ms", C.c_double), ("tables_ms", C.c_double), ("copy_back_ms", C.c_double)]
 
 
+class _BuildSeedStats(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("distinct_kmers", C.c_uint64), ("patterns", C.c_uint64), ("events", C.c_uint64), ("slots", C.c_uint64),
+                ("h2d_bytes", C.c_uint64), ("upload_ms", C.c_double), ("dict_ms", C.c_double), ("tree_ms", C.c_double), ("decode_ms", C.c_double),
+                ("check_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -124,6 +130,7 @@ EXPORTS = [
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
     "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
+    "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
 ]
 
 
@@ -255,6 +262,8 @@ def lib():
     L.kmdb_build_free.restype = None
     L.kmdb_build_free.argtypes = [C.c_void_p]
     L.kmdb_build_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildStats)]
+    L.kmdb_build_begin_from_db.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.kmdb_build_seed_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildSeedStats)]
     L.kmdbh_db_store.argtypes = [C.c_void_p, C.c_char_p]
     L.kmdbh_format_header.restype = C.c_size_t
     L.kmdbh_format_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -1012,6 +1021,21 @@ class Builder:
         self._b = C.c_void_p()
         o = _opts(device, stream=stream)
         _check(lib().kmdb_build_begin(int(k), float(fraction), float(start_fraction), a, C.byref(o), C.byref(self._b)))
+
+    @classmethod
+    def from_db(cls, hostdb, device=0, stream=None):
+        """kmdb_build_begin_from_db: a builder seeded on the device from a HostDB that holds its tables; k, fraction, alphabet, names and
+        counts are the database's, new samples are numbered from hostdb.N on"""
+        self = cls.__new__(cls)
+        self._b = C.c_void_p()
+        o = _opts(device, stream=stream)
+        _check(lib().kmdb_build_begin_from_db(hostdb._h, C.byref(o), C.byref(self._b)))
+        return self
+
+    def seed_stats(self):
+        st = _BuildSeedStats()
+        _check(lib().kmdb_build_seed_stats_get(self._b, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _BuildSeedStats._fields_}
 
     @staticmethod
     def _names(names):

@@ -23,6 +23,7 @@
 //                >= 16 that keeps the fill at or below 0.8 (hashmap_lp.h:420-437); home slot and probing as csrc/hash_probe.h reads them;
 //                placement by 64-bit atomic minimum: linear probing with priorities, one table whatever the order of arrival
 //            (e) everything copied into a kmdbh_db
+//   seed     (f) kmdb_build_begin_from_db: the reverse of (c) - (e), a stored database loaded into the state above (bd_seed, further down)
 // Wave-64, 256 threads per block, one element per thread; every kernel checks its own bounds and no kernel uses scratch (the compile's
 // resource remarks are read by tests/test_build.py).
 #include "kmdb_amd.h"
@@ -295,6 +296,110 @@ __global__ __launch_bounds__(BD_THREADS) void bd_insert_kernel(const uint64_t* _
     *failed = 1;
 }
 
+// ---- the seed: a stored database back into the state above (kmdb_build_begin_from_db) ------------------------------------------------
+// One word per check of the seed; all of them are read once, after the last kernel.
+enum : uint32_t { BD_BAD_VALUE = 0, BD_BAD_TWICE, BD_BAD_WIDE, BD_BAD_COUNT, BD_BAD_STREAM, BD_BAD_IDS, BD_BAD_PARENT, BD_BAD_WORDS };
+
+// (a) the inverse of bd_insert_kernel, a piece of the slots at a time: flag[i] = slot i of the piece holds an item, i <= m (flag[m] = 0)
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_flag_kernel(const unsigned long long* __restrict__ slots, uint64_t m, uint64_t P, uint32_t* __restrict__ flag,
+                                                                  uint32_t* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (i > m) return;
+    uint32_t f = 0;
+    if (i < m) {
+        const uint32_t val = (uint32_t)(slots[i] >> 32);
+        f = val != 0x7fffffffu ? 1u : 0u;
+        if (f && (val == 0 || val >= P)) bad[BD_BAD_VALUE] = 1;        // (every writer stores the same value)
+    }
+    flag[i] = f;
+}
+// the item of slot slot0 + i goes to place base + fscan[i]: k-mer = its bucket (the last b with boff[b] <= slot) << 32 | key, pid = val
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_compact_kernel(const unsigned long long* __restrict__ slots, const uint32_t* __restrict__ flag,
+                                                                     const uint32_t* __restrict__ fscan, uint64_t m, uint64_t slot0,
+                                                                     const unsigned long long* __restrict__ boff, uint64_t nb, uint64_t base, uint64_t nD,
+                                                                     uint64_t* __restrict__ K, uint32_t* __restrict__ pid) {
+    const uint64_t i = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (i >= m || !flag[i]) return;
+    const uint64_t at = base + fscan[i], s = slot0 + i;
+    if (at >= nD) return;                              // (more items than the patterns count: the host compares the totals)
+    uint64_t lo = 0, hi = nb;                          // boff[0] = 0 <= s < boff[nb]
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) / 2; if (boff[mid] <= s) lo = mid; else hi = mid; }
+    const unsigned long long item = slots[i];
+    K[at] = (lo << 32) | (item & 0xffffffffull);
+    pid[at] = (uint32_t)(item >> 32);
+}
+
+// (b) is_parent is not in a stored database: a pattern is a parent iff some pattern names it (pattern.h:106-114).  isp is zeroed before.
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_isp_kernel(const long long* __restrict__ parent, uint64_t P, uint32_t* __restrict__ isp, uint32_t* __restrict__ bad) {
+    const uint64_t p = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (p >= P) return;
+    const long long q = parent[p];
+    if (q < -1 || q >= (long long)p) { bad[BD_BAD_PARENT] = 1; return; }
+    if (q >= 0) isp[q] = 1;
+}
+
+// (d) the sorted dictionary: strictly ascending, inside kbits; hist[p] = k-mers whose pattern is p
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_dict_check_kernel(const uint64_t* __restrict__ D, const uint32_t* __restrict__ cur, uint64_t nD, uint32_t kbits,
+                                                                        uint64_t P, uint32_t* __restrict__ hist, uint32_t* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (i >= nD) return;
+    const uint64_t x = D[i];
+    if (i && D[i - 1] >= x) bad[BD_BAD_TWICE] = 1;
+    if (kbits < 64 && (x >> kbits)) bad[BD_BAD_WIDE] = 1;
+    const uint32_t c = cur[i];
+    if (c && c < P) atomicAdd(&hist[c], 1u);           // (0 and >= P were flagged where the slots were read)
+}
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_count_check_kernel(const uint32_t* __restrict__ hist, const long long* __restrict__ here, uint64_t P,
+                                                                         uint32_t* __restrict__ bad) {
+    const uint64_t p = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (p < P && (long long)hist[p] != here[p]) bad[BD_BAD_COUNT] = 1;
+}
+
+// 64 bits of a pattern's stream from bit `pos` on, MSB first; words past the pattern's own read as zeros
+__device__ __forceinline__ uint64_t bd_seed_window(const uint64_t* __restrict__ s, uint64_t words, uint64_t pos) {
+    const uint64_t w = pos >> 6;
+    const uint32_t sh = (uint32_t)pos & 63u;
+    const uint64_t c0 = w < words ? s[w] : 0ull, c1 = w + 1 < words ? s[w + 1] : 0ull;
+    return sh ? (c0 << sh) | (c1 >> (64u - sh)) : c0;
+}
+// (c) one thread per pattern: its num_local - 1 codes (what bd_write_codes_kernel writes) back into its stretch of the events, ascending.
+// The deltas' running sums go down first; once their total is known, id[0] = last_sample_id - total is added to each.
+__global__ __launch_bounds__(BD_THREADS) void bd_seed_decode_kernel(const uint32_t* __restrict__ num_local, const uint32_t* __restrict__ estart,
+                                                                    const uint32_t* __restrict__ last_id, const uint32_t* __restrict__ num_bits,
+                                                                    const unsigned long long* __restrict__ data_offset, const uint64_t* __restrict__ data,
+                                                                    uint64_t n_words, uint64_t P, uint64_t E, uint64_t n_samples, uint32_t* __restrict__ ev_pid,
+                                                                    uint32_t* __restrict__ ev_sid, uint32_t* __restrict__ bad) {
+    const uint64_t p = (uint64_t)blockIdx.x * BD_THREADS + threadIdx.x;
+    if (p >= P) return;
+    const uint32_t n = num_local[p], bits = num_bits[p];
+    if (!n) { if (bits) bad[BD_BAD_STREAM] = 1; return; }
+    const uint64_t e0 = estart[p], off = data_offset[p], words = bits ? (((uint64_t)bits + 127ull) / 128ull) * 2ull : 0ull;
+    if (e0 + n > E) { bad[BD_BAD_STREAM] = 1; return; }                        // (cannot happen: E is the sum of num_local)
+    if (off > n_words || words > n_words - off) { bad[BD_BAD_WORDS] = 1; return; }
+    const uint32_t last = last_id[p];
+    if (last >= n_samples) { bad[BD_BAD_IDS] = 1; return; }
+    const uint64_t* __restrict__ s = data + off;
+    uint64_t pos = 0, total = 0;
+    ev_pid[e0] = (uint32_t)p;
+    ev_sid[e0] = 0;
+    for (uint32_t i = 1; i < n; ++i) {
+        if (pos >= bits) { bad[BD_BAD_STREAM] = 1; return; }
+        const uint64_t win = bd_seed_window(s, words, pos);
+        const uint32_t ones = ~win ? (uint32_t)__clzll((long long)~win) : 64u;
+        if (ones > 31u) { bad[BD_BAD_STREAM] = 1; return; }                    // a delta is 32 bits wide: at most 31 leading ones
+        const uint32_t delta = (uint32_t)((win << ones) >> (63u - ones)) | (1u << ones);
+        pos += 2u * ones + 1u;
+        total += delta;
+        if (pos > bits) { bad[BD_BAD_STREAM] = 1; return; }
+        if (total > last) { bad[BD_BAD_IDS] = 1; return; }                     // the first id would be negative
+        ev_pid[e0 + i] = (uint32_t)p;
+        ev_sid[e0 + i] = (uint32_t)total;
+    }
+    if (pos != bits) { bad[BD_BAD_STREAM] = 1; return; }
+    const uint32_t first = last - (uint32_t)total;
+    for (uint32_t i = 0; i < n; ++i) ev_sid[e0 + i] += first;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 struct Acct {
     uint64_t live = 0, peak = 0, limit = 0;            // limit: KMDB_BUILD_DEVICE_BYTES, 0 = what the device has
@@ -365,6 +470,7 @@ struct kmdb_builder {
     uint64_t E = 0, cap_e = 0;
     BBuf overflow;                 // one flag
     kmdb_build_stats stats{};
+    kmdb_build_seed_stats seed{};  // zeros unless the builder was seeded
     std::vector<hipEvent_t> events;
     ~kmdb_builder() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
 };
@@ -550,8 +656,14 @@ int bd_usable(kmdb_builder* b, const char* who) {
     return 0;
 }
 
-int bd_begin(uint32_t k, double fraction, double start_fraction, int32_t alphabet, const kmdb_opts* opts, kmdb_builder** out) {
-    const char* who = "kmdb_build_begin";
+struct BdSeedPlan {                // what the host reads off a kmdbh_db before any device work
+    const kmdbh_db* db;
+    const kmdb_db_view* v;
+    uint64_t nD, E, n_slots;       // sum of num_kmers, sum of num_local, bucket_offset[n_buckets]
+};
+int bd_seed(kmdb_builder* b, const BdSeedPlan& plan, const char* who);
+
+int bd_begin(const char* who, uint32_t k, double fraction, double start_fraction, int32_t alphabet, const kmdb_opts* opts, const BdSeedPlan* seed, kmdb_builder** out) {
     if (!out) return kmdb_set_error(std::string(who) + ": null argument");
     *out = nullptr;
     if (opts && opts->abi_version && !kmdb_abi_compatible(opts->abi_version)) return kmdb_set_error(std::string(who) + ": kmdb_opts.abi_version is not served by this library");
@@ -573,6 +685,12 @@ int bd_begin(uint32_t k, double fraction, double start_fraction, int32_t alphabe
     if (const char* e = getenv("KMDB_BUILD_DEVICE_BYTES")) b->acct.limit = strtoull(e, nullptr, 10);
     BD_DO(b->overflow.alloc(b->acct, 4, "a flag"));
     BD_TRY(hipMemsetAsync(b->overflow.p, 0, 4, b->st));
+    if (seed) {
+        BD_DO(bd_seed(b, *seed, who));
+        hold.b = nullptr;
+        *out = b;
+        return 0;
+    }
     BD_DO(bd_reserve(b, 1u << 16, 1u << 16));
     // pattern 0 = the empty pattern (prefix_kmer_db.cpp:24; pattern_t(): parent -1, everything else 0)
     const long long zero64 = 0, minus1 = -1;
@@ -585,6 +703,191 @@ int bd_begin(uint32_t k, double fraction, double start_fraction, int32_t alphabe
     hold.b = nullptr;
     *out = b;
     return 0;
+}
+
+// The seed (replaces db->deserialize + the filter and alphabet taken from the database, console_build.cpp:48-57): the arrays of a kmdbh_db
+// become the state a builder would hold after the database's samples, so that the add and finish paths go on from it unchanged.
+//   (a) the slots go up a piece at a time (KMDB_BUILD_SEED_SLOTS_PER_PIECE, default 2^27: the whole table is never resident); flag, scan,
+//       compact to (k-mer, pattern id); the pieces' buffers are released before the sort's are allocated; sort_pairs over kbits -> D, cur
+//   (b) here / nsam / parent are the stored num_kmers / num_samples / parent_id; isp is recomputed from parent
+//   (d) D strictly ascending and inside kbits, the k-mers per pattern against num_kmers
+//   (c) a scan of num_local gives every pattern its stretch of the events; one thread per pattern decodes its stream into it
+// Held at the peak of (a): 12 bytes per distinct k-mer twice over (the pairs before and after the sort) plus the sort's storage; afterwards
+// the builder's own 12 per k-mer, 24 per pattern and 8 per event, and while (c) runs 28 per pattern and the streams.
+int bd_seed(kmdb_builder* b, const BdSeedPlan& plan, const char* who) {
+    const kmdb_db_view* v = plan.v;
+    const uint64_t P = v->n_patterns, N = v->n_samples, nb = v->n_buckets, n_words = v->n_data_words, nD = plan.nD, E = plan.E, n_slots = plan.n_slots;
+    hipStream_t st = b->st;
+    kmdb_build_seed_stats& ss = b->seed;
+    ss.slots = n_slots;
+    BBuf bad;
+    BD_DO(bad.alloc(b->acct, 8 * 4, "the seed's flags"));
+    BD_TRY(hipMemsetAsync(bad.p, 0, 8 * 4, st));
+    uint32_t* d_bad = bad.as<uint32_t>();
+    auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t { ss.h2d_bytes += bytes; return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
+    // ---- (a) the dictionary from the tables
+    {
+        BBuf Kin, Pin;
+        BD_DO(Kin.alloc(b->acct, nD * 8, "the tables' k-mers"));
+        BD_DO(Pin.alloc(b->acct, nD * 4, "the tables' pattern ids"));
+        uint64_t found = 0;
+        {
+            uint64_t piece = 1ull << 27;
+            if (const char* e = getenv("KMDB_BUILD_SEED_SLOTS_PER_PIECE")) piece = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), 1ull << 30);
+            piece = std::min(piece, std::max<uint64_t>(n_slots, 1));
+            BBuf boff, chunk, flag, fscan, tmp;
+            BD_DO(boff.alloc(b->acct, (nb + 1) * 8, "bucket_offset"));
+            BD_DO(chunk.alloc(b->acct, piece * 8, "a piece of the hashtables' slots"));
+            BD_DO(flag.alloc(b->acct, (piece + 1) * 4, "the slots' flags"));
+            BD_DO(fscan.alloc(b->acct, (piece + 1) * 4, "the slots' ranks"));
+            size_t tb = 0;
+            BD_TRY(prim::exclusive_sum(nullptr, tb, flag.as<uint32_t>(), fscan.as<uint32_t>(), piece + 1, st));
+            BD_DO(tmp.alloc(b->acct, tb, "the scan's temporary storage"));
+            BD_MARK(0);
+            BD_TRY(h2d(boff.p, v->bucket_offset, (nb + 1) * 8));
+            BD_MARK(1);
+            BD_TRY(hipStreamSynchronize(st));
+            ss.upload_ms += bd_ms(b, 0, 1);
+            for (uint64_t s0 = 0; s0 < n_slots; s0 += piece) {
+                const uint64_t m = std::min(piece, n_slots - s0);
+                size_t need = 0;
+                BD_TRY(prim::exclusive_sum(nullptr, need, flag.as<uint32_t>(), fscan.as<uint32_t>(), m + 1, st));
+                if (need > tmp.bytes) BD_DO(tmp.alloc(b->acct, need, "the scan's temporary storage"));
+                BD_MARK(0);
+                BD_TRY(h2d(chunk.p, v->slots + s0, m * 8));
+                BD_MARK(1);
+                hipLaunchKernelGGL(bd_seed_flag_kernel, dim3(bd_blocks(m + 1)), dim3(BD_THREADS), 0, st, chunk.as<unsigned long long>(), m, P, flag.as<uint32_t>(), d_bad);
+                BD_TRY(prim::exclusive_sum(tmp.p, need, flag.as<uint32_t>(), fscan.as<uint32_t>(), m + 1, st));
+                hipLaunchKernelGGL(bd_seed_compact_kernel, dim3(bd_blocks(m)), dim3(BD_THREADS), 0, st, chunk.as<unsigned long long>(), flag.as<uint32_t>(), fscan.as<uint32_t>(), m, s0,
+                                   boff.as<unsigned long long>(), nb, found, nD, Kin.as<uint64_t>(), Pin.as<uint32_t>());
+                BD_TRY(hipGetLastError());
+                BD_MARK(2);
+                uint32_t cnt = 0;
+                BD_TRY(hipMemcpyAsync(&cnt, fscan.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, st));
+                BD_TRY(hipStreamSynchronize(st));
+                found += cnt;
+                ss.upload_ms += bd_ms(b, 0, 1);
+                ss.dict_ms += bd_ms(b, 1, 2);
+            }
+        }
+        if (found != nD)
+            return kmdb_set_error(std::string(who) + ": the database's tables hold " + std::to_string(found) + " k-mers, the num_kmers of its patterns add up to " + std::to_string(nD));
+        BD_DO(b->D.alloc(b->acct, nD * 8, "the dictionary"));
+        BD_DO(b->cur.alloc(b->acct, nD * 4, "the k-mers' pattern ids"));
+        if (nD) {
+            BBuf tmp;
+            size_t tb = 0;
+            BD_TRY(prim::sort_pairs(nullptr, tb, Kin.as<uint64_t>(), b->D.as<uint64_t>(), Pin.as<uint32_t>(), b->cur.as<uint32_t>(), nD, 0, b->kbits, st));
+            BD_DO(tmp.alloc(b->acct, tb, "the sort's temporary storage"));
+            BD_MARK(0);
+            BD_TRY(prim::sort_pairs(tmp.p, tb, Kin.as<uint64_t>(), b->D.as<uint64_t>(), Pin.as<uint32_t>(), b->cur.as<uint32_t>(), nD, 0, b->kbits, st));
+            BD_MARK(1);
+            BD_TRY(hipStreamSynchronize(st));
+            ss.dict_ms += bd_ms(b, 0, 1);
+        }
+        b->nD = nD;
+    }
+    // ---- (b) the tree.  b->P is still 1 and b->E 0: bd_reserve allocates, there is nothing to keep
+    BD_DO(bd_reserve(b, (P - 1) + (1u << 16), E + (1u << 16)));
+    BD_MARK(0);
+    BD_TRY(h2d(b->here.p, v->num_kmers, P * 8));
+    BD_TRY(h2d(b->parent.p, v->parent_id, P * 8));
+    BD_TRY(h2d(b->nsam.p, v->num_samples, P * 4));
+    BD_MARK(1);
+    BD_TRY(hipMemsetAsync(b->isp.p, 0, P * 4, st));
+    hipLaunchKernelGGL(bd_seed_isp_kernel, dim3(bd_blocks(P)), dim3(BD_THREADS), 0, st, b->parent.as<long long>(), P, b->isp.as<uint32_t>(), d_bad);
+    BD_TRY(hipGetLastError());
+    BD_MARK(2);
+    // ---- (d) the dictionary against the tree
+    {
+        BBuf hist;
+        BD_DO(hist.alloc(b->acct, P * 4, "the patterns' k-mer counters"));
+        BD_TRY(hipMemsetAsync(hist.p, 0, P * 4, st));
+        if (nD) hipLaunchKernelGGL(bd_seed_dict_check_kernel, dim3(bd_blocks(nD)), dim3(BD_THREADS), 0, st, b->D.as<uint64_t>(), b->cur.as<uint32_t>(), nD, b->kbits, P, hist.as<uint32_t>(), d_bad);
+        hipLaunchKernelGGL(bd_seed_count_check_kernel, dim3(bd_blocks(P)), dim3(BD_THREADS), 0, st, hist.as<uint32_t>(), b->here.as<long long>(), P, d_bad);
+        BD_TRY(hipGetLastError());
+        BD_MARK(3);
+        BD_TRY(hipStreamSynchronize(st));
+    }
+    ss.upload_ms += bd_ms(b, 0, 1);
+    ss.tree_ms = bd_ms(b, 1, 2);
+    ss.check_ms = bd_ms(b, 2, 3);
+    // ---- (c) the events from the gamma streams
+    uint32_t flags[8] = {0};
+    {
+        BBuf num_local, estart, last_id, num_bits, data_off, data, tmp;
+        BD_DO(num_local.alloc(b->acct, (P + 1) * 4, "num_local"));
+        BD_DO(estart.alloc(b->acct, (P + 1) * 4, "the patterns' first events"));
+        BD_DO(last_id.alloc(b->acct, P * 4, "last_sample_id"));
+        BD_DO(num_bits.alloc(b->acct, P * 4, "num_bits"));
+        BD_DO(data_off.alloc(b->acct, P * 8, "data_offset"));
+        BD_DO(data.alloc(b->acct, n_words * 8, "the gamma streams"));
+        size_t tb = 0;
+        BD_TRY(prim::exclusive_sum(nullptr, tb, num_local.as<uint32_t>(), estart.as<uint32_t>(), P + 1, st));
+        BD_DO(tmp.alloc(b->acct, tb, "the scan's temporary storage"));
+        BD_MARK(0);
+        BD_TRY(hipMemsetAsync(num_local.as<uint32_t>() + P, 0, 4, st));
+        BD_TRY(h2d(num_local.p, v->num_local, P * 4));
+        BD_TRY(h2d(last_id.p, v->last_sample_id, P * 4));
+        BD_TRY(h2d(num_bits.p, v->num_bits, P * 4));
+        BD_TRY(h2d(data_off.p, v->data_offset, P * 8));
+        if (n_words) BD_TRY(h2d(data.p, v->data, n_words * 8));
+        BD_MARK(1);
+        BD_TRY(prim::exclusive_sum(tmp.p, tb, num_local.as<uint32_t>(), estart.as<uint32_t>(), P + 1, st));
+        hipLaunchKernelGGL(bd_seed_decode_kernel, dim3(bd_blocks(P)), dim3(BD_THREADS), 0, st, num_local.as<uint32_t>(), estart.as<uint32_t>(), last_id.as<uint32_t>(), num_bits.as<uint32_t>(),
+                           data_off.as<unsigned long long>(), data.as<uint64_t>(), n_words, P, E, N, b->ev_pid.as<uint32_t>(), b->ev_sid.as<uint32_t>(), d_bad);
+        BD_TRY(hipGetLastError());
+        BD_MARK(2);
+        BD_TRY(hipMemcpyAsync(flags, bad.p, sizeof flags, hipMemcpyDeviceToHost, st));
+        BD_TRY(hipStreamSynchronize(st));
+        ss.upload_ms += bd_ms(b, 0, 1);
+        ss.decode_ms = bd_ms(b, 1, 2);
+    }
+    static const char* const why[8] = {"a value of its tables is 0 or no pattern id", "a k-mer is stored twice in its tables", "a k-mer of its tables is wider than k symbols",
+                                       "the k-mers its tables give a pattern differ from the pattern's num_kmers", "a pattern's stream does not end at its num_bits",
+                                       "a pattern's sample ids are not strictly ascending below the number of samples", "a pattern's parent_id is not below its own id",
+                                       "a pattern's stream lies outside the stream words"};
+    for (int i = 0; i < 8; ++i)
+        if (flags[i]) return kmdb_set_error(std::string(who) + ": the database cannot seed a builder: " + why[i]);
+    b->P = P;
+    b->E = E;
+    for (uint64_t i = 0; i < N; ++i) { b->names.emplace_back(kmdbh_db_sample_name(plan.db, i)); b->counts.push_back(kmdbh_db_sample_kmers(plan.db, i)); }
+    ss.samples = N; ss.distinct_kmers = nD; ss.patterns = P; ss.events = E;
+    return 0;
+}
+
+// what can be refused before any device work
+int bd_begin_from_db(const kmdbh_db* db, const kmdb_opts* opts, kmdb_builder** out) {
+    const char* who = "kmdb_build_begin_from_db";
+    if (!out) return kmdb_set_error(std::string(who) + ": null argument");
+    *out = nullptr;
+    if (!db) return kmdb_set_error(std::string(who) + ": null argument");
+    BdSeedPlan plan{db, kmdbh_db_view(db), 0, 0, 0};
+    const kmdb_db_view* v = plan.v;
+    if (!v->n_buckets || !v->bucket_offset || !v->slots)
+        return kmdb_set_error(std::string(who) + ": the database holds no hashtables (it was loaded with SkipHashtables): the k-mers of its patterns are in them");
+    const uint64_t P = v->n_patterns;
+    if (!P) return kmdb_set_error(std::string(who) + ": the database holds no pattern, not even the empty one");
+    if (v->n_samples >= 0xFFFFFFFFull) return kmdb_set_error(std::string(who) + ": 2^32 samples or more");
+    if (P >= 0x7FFFFFFFull) return kmdb_set_error(std::string(who) + ": 2^31 patterns or more: pattern ids are 31 bits wide (hashmap_lp.h:78)");
+    for (uint64_t p = 0; p < P; ++p) {
+        if (v->num_kmers[p] < 0) return kmdb_set_error(std::string(who) + ": a pattern with a negative num_kmers");
+        plan.nD += (uint64_t)v->num_kmers[p];
+        plan.E += v->num_local[p];
+        if (plan.nD >= 0x7FFFFFFFull) return kmdb_set_error(std::string(who) + ": 2^31 distinct k-mers or more: the seed's sort takes 31-bit sizes");
+        if (plan.E >= 0x7FFFFFFFull) return kmdb_set_error(std::string(who) + ": 2^31 (pattern, sample) events or more: the sort at finish takes 31-bit sizes");
+    }
+    plan.n_slots = v->bucket_offset[v->n_buckets];
+    const uint32_t k = kmdbh_db_kmer_length(db);
+    const int32_t alphabet = kmdbh_db_alphabet(db);
+    int8_t map[256];
+    uint32_t size = 0, bits = 0;
+    if (alphabet >= 0 && alphabet < KMDB_ALPHABET_COUNT && !kmdbh_alphabet_table(alphabet, map, &size, &bits, nullptr)) {
+        const uint64_t want = 1ull << std::max(8, (int)(bits * k) - 32);                  // prefix_kmer_db.cpp:54-62
+        if (v->n_buckets != want)
+            return kmdb_set_error(std::string(who) + ": the database has " + std::to_string(v->n_buckets) + " prefix buckets, k = " + std::to_string(k) + " takes " + std::to_string(want));
+    }                                                                                      // (an unknown alphabet is refused by bd_begin)
+    return bd_begin(who, k, kmdbh_db_fraction(db), kmdbh_db_start_fraction(db), alphabet, opts, &plan, out);
 }
 
 // the pieces of a call: [s0, s1) with at most BD_PIECE_KMERS k-mers (a longer sample alone) and BD_PIECE_SAMPLES non-empty samples
@@ -827,7 +1130,15 @@ int bd_finish(kmdb_builder* b, kmdbh_db** out) {
     }
 
 extern "C" int kmdb_build_begin(uint32_t kmer_length, double fraction, double start_fraction, int32_t alphabet, const kmdb_opts* opts, kmdb_builder** out) {
-    BD_GUARD("kmdb_build_begin", bd_begin(kmer_length, fraction, start_fraction, alphabet, opts, out))
+    BD_GUARD("kmdb_build_begin", bd_begin("kmdb_build_begin", kmer_length, fraction, start_fraction, alphabet, opts, nullptr, out))
+}
+extern "C" int kmdb_build_begin_from_db(const kmdbh_db* db, const kmdb_opts* opts, kmdb_builder** out) {
+    BD_GUARD("kmdb_build_begin_from_db", bd_begin_from_db(db, opts, out))
+}
+extern "C" int kmdb_build_seed_stats_get(const kmdb_builder* b, kmdb_build_seed_stats* out) {
+    if (!b || !out) return kmdb_set_error("kmdb_build_seed_stats_get: null argument");
+    *out = b->seed;
+    return 0;
 }
 extern "C" int kmdb_build_add_kmers(kmdb_builder* b, const char* const* names, const uint64_t* const* kmers, const size_t* counts, size_t n_samples) {
     BD_GUARD("kmdb_build_add_kmers", bd_add_kmers(b, names, kmers, counts, n_samples))

@@ -8,6 +8,7 @@
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
 //     kmer-db-amd minhash    [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] <samples>
 //     kmer-db-amd build      [-k <kmer-length>] [-f <fraction>] [-alphabet <name>] [-multisample-fasta | -from-minhash] <samples> <db>
+//     kmer-db-amd build      -extend-from <old.db> [-multisample-fasta | -from-minhash] <samples> <db>
 // mirroring the reference consoles (reference src/console_all2all.cpp, console_all2all_sparse.cpp,
 // console_new2all.cpp) around the calls that the C ABI replaces.  Options that only tune the
 // reference's CPU engine (-t, -rt, -buffer, -bubble-size) are accepted; -t also sizes the
@@ -916,8 +917,15 @@ int run_build(std::vector<std::string>& args, Common& c) {
     uint32_t k = 18;
     int32_t alphabet = KMDB_ALPHABET_NT;
     bool multi = false;
-    std::string v;
-    if (!from_minhash) {
+    std::string v, seed_path;
+    // -extend-from <old.db>: the builder starts from a stored database (console_build.cpp:48-57).  k, fraction, start fraction and alphabet are
+    // the database's own; -k, -f, -f-start, -alphabet and -preserve-strand are accepted and ignored, as the reference's -extend does
+    const bool extend = take_option(args, "-extend-from", seed_path);
+    if (extend) {
+        take_option(args, "-f", v); take_option(args, "-f-start", v); take_option(args, "-alphabet", v); take_option(args, "-k", v);
+        take_switch(args, "-preserve-strand");
+        multi = take_switch(args, "-multisample-fasta");
+    } else if (!from_minhash) {
         if (take_option(args, "-f", v)) { std::istringstream iss(v); if (!(iss >> fraction)) throw std::runtime_error("Unable to parse the fraction: " + v); }
         if (take_option(args, "-f-start", v)) { std::istringstream iss(v); if (!(iss >> fstart)) throw std::runtime_error("Unable to parse the start fraction: " + v); }
         multi = take_switch(args, "-multisample-fasta");
@@ -939,6 +947,12 @@ int run_build(std::vector<std::string>& args, Common& c) {
     }
     if (args.size() != 2) throw usage_error("build");
     std::cerr << "Building database (from " << (from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
+    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } built, old;
+    if (extend) {                                                  // read with its tables, before anything else is opened and before any device is touched
+        std::cerr << "Loading k-mer database " << seed_path << "..." << std::endl;
+        if (kmdbh_db_load(seed_path.c_str(), 0, &old.h)) throw std::runtime_error("Cannot open k-mer database " + seed_path);
+        k = kmdbh_db_kmer_length(old.h); fraction = kmdbh_db_fraction(old.h); fstart = kmdbh_db_start_fraction(old.h); alphabet = kmdbh_db_alphabet(old.h);
+    }
     // LoaderEx::configure (loader_ex.cpp:87-122): a FASTA file is one input file, anything else a list of them
     std::vector<std::string> entries;
     bool is_fasta = false;
@@ -958,7 +972,16 @@ int run_build(std::vector<std::string>& args, Common& c) {
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
     const int nthreads = c.threads > 0 ? c.threads : (int)std::max(1u, std::thread::hardware_concurrency());
     struct Builder { kmdb_builder* b = nullptr; ~Builder() { kmdb_build_free(b); } } bld;
-    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } built;
+    if (extend) {
+        check(kmdb_build_begin_from_db(old.h, &o, &bld.b));
+        kmdbh_db_free(old.h);                                      // the builder holds the state now
+        old.h = nullptr;
+        kmdb_build_seed_stats ss{};
+        if (std::getenv("KMDB_VERBOSE") && !kmdb_build_seed_stats_get(bld.b, &ss))
+            std::cerr << "[kmdb] build: seeded from " << ss.samples << " samples, " << ss.distinct_kmers << " distinct k-mers, " << ss.patterns << " patterns, " << ss.events
+                      << " events, " << ss.slots << " slots, " << ss.h2d_bytes << " bytes to the device; upload " << ss.upload_ms << " dictionary " << ss.dict_ms << " tree "
+                      << ss.tree_ms << " decode " << ss.decode_ms << " checks " << ss.check_ms << " ms" << std::endl;
+    }
     struct Sample { std::string name, text; std::vector<uint64_t> kmers; bool on_host = false; };
     struct File { std::string entry; std::vector<Sample> samples; bool ok = false; uint32_t k = 0; double fraction = 0; };
     size_t added = 0;
@@ -1025,7 +1048,7 @@ int run_build(std::vector<std::string>& args, Common& c) {
         for (File& f : files) {
             if (!f.ok) { std::cerr << "failed:" << f.entry << std::endl; continue; }
             if (from_minhash) {
-                if (!bld.b) { k = f.k; fraction = f.fraction; }
+                if (!bld.b) { k = f.k; fraction = f.fraction; }                // (a seeded builder is there already: the files must match the database)
                 // AbstractKmerDb::addKmers (kmer_db.h:116-121)
                 if (f.k != k) throw std::runtime_error("Error in AbstractKmerDb::addKmers(): adding kmers of different length");
                 if (f.fraction != fraction) throw std::runtime_error("Error in AbstractKmerDb::addKmers(): adding kmers of different minhash fraction");
@@ -1530,6 +1553,7 @@ void usage() {
                  "    kmer-db-amd minhash [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] [-preserve-strand] [-host-extract] <samples>\n"
                  "    kmer-db-amd build [-k <kmer-length>] [-f <fraction>] [-f-start <v>] [-alphabet <name>] [-preserve-strand] [-multisample-fasta] [-host-extract] <sample_list | fasta> <database>\n"
                  "    kmer-db-amd build -from-minhash <sample_list> <database>\n"
+                 "    kmer-db-amd build -extend-from <old.db> [-from-minhash] [-multisample-fasta] [-host-extract] <sample_list | fasta> <database>\n"
                  "    kmer-db-amd all2all-parts [-min ...] [-max ...] <db_list> <common_table>\n"
                  "    kmer-db-amd distance [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* <measure> <common_table> <output>\n"
                  "Common options: -t <threads>, -gpu <device>\n"
@@ -1543,7 +1567,8 @@ void usage() {
                  "minhash: <samples> is a list of FASTA files (or one FASTA file); <sample>.minhash = its k-mers that pass the filter (-f, default 0.01),\n"
                  "                   sorted and unique, extracted on the GPU; -host-extract extracts them on the host and needs no GPU\n"
                  "build: the database is grown on the GPU from the samples in input order and written in the reference's format; -from-minhash takes\n"
-                 "                   <sample>.minhash files (k and fraction from the files); -extend and -from-kmers are refused\n"
+                 "                   <sample>.minhash files (k and fraction from the files); -extend-from <old.db> starts from a stored database (its k,\n"
+                 "                   fraction and alphabet; <database> may be <old.db>); -extend and -from-kmers are refused\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
