@@ -44,6 +44,30 @@
 #include <cstdlib>
 #include <cstring>
 
+// counters of the block-record pipeline, zeroed at the start of every call and read back at its end
+enum : uint32_t {
+    KCTR_CHUNKS = 0,        // record chunks opened
+    KCTR_POOL_OVERFLOW,     // != 0: the chunk pool was too small (results invalid; the call is repeated with a larger pool)
+    KCTR_PAIR_OVERFLOW,     // != 0: the pool of extra (block, mask) pairs was too small
+    KCTR_NWIDE,             // nodes whose full list touches more than two blocks
+    KCTR_LIST_OVERFLOW,     // != 0: a wide node's path did not fit the per-wave entry pool
+    KCTR_RAW = 5,           // chunks of the wide pool in use (upper bound: busiest sub-pool x sub-pools)
+    KCTR_RECORDS = 6,       // low word of the number of block records written (64-bit atomic: even index)
+    KCTR_RECORDS_HI = 7,
+    KCTR_SLOW = 8,          // wide nodes that took the climbing path
+    KCTR_WIDE_OVERFLOW = 9, // != 0: the wide record pool was too small
+    KCTR_WIDE_RECORDS = 10, // records written to the wide pool
+    KCTR_ROWJOBS = 11,      // row mode: workgroups of the sort inside the block rows
+    KCTR_L2_OVERFLOW = 12,  // != 0: the second level's node indices or entries ran out (results invalid; repeated with larger arrays)
+    KCTR_L2_NODES = 13,     // nodes that went to the second level
+    KCTR_POOL_USED = 15,    // chunks of the chunk pool in use (upper bound: busiest sub-pool x sub-pools)
+    KCTR_K2JOBS = 14,       // row mode: jobs of the apply kernel over the sorted records (one stream, or one part of a long stream, each)
+    KCTR_DIRECT = 16,       // first-block records the narrow kernel applied where it emitted them (never written: k1n_kernel<true>)
+    KCTR_COUNT = 17
+};
+constexpr uint32_t KMDB_PAIR_REGIONS = 4096;   // sub-pools of the extra-pair pool (one allocation cursor each)
+constexpr uint32_t KMDB_SUBPOOLS = 256;      // sub-pools of the record chunk pool (one allocation cursor each)
+
 namespace {
 
 __host__ __device__ __forceinline__ uint32_t tri32(uint32_t x) { return x * (x + 1u) / 2u; }
@@ -2845,14 +2869,122 @@ __global__ void v1_arrays_kernel(const uint2* __restrict__ k0in, const uint32_t*
 
 // weight digit bits of the wide pool's key word: what the stream bits and the two digit-index bits leave (four digits cover 32 bits)
 inline uint32_t wide_digit_bits(int key_bits) { return (uint32_t)(32 - key_bits - 2); }
-PoolView pool_view(const kmdb_db* db, bool dense) {
-    return PoolView{db->counters, db->chunk_key, db->chunk_fill, db->rec, db->recw, db->sub_cursor, (uint32_t)(db->pool_cap / KMDB_SUBPOOLS),
-                    (uint32_t)db->pool_cap, db->wkey, (WideRec*)db->wrec, db->wsub_cursor, (uint32_t)(db->wide_pool_cap / KMDB_SUBPOOLS), dense ? 1u : 0u,
-                    (uint32_t)db->key_bits, wide_digit_bits(db->key_bits), db->row_mode ? 1u : 0u, db->n_states, db->rec_pshift};
-}
+}  // namespace
 
-void free_and_null(void** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
-#define FREE_NULL(x) free_and_null((void**)&(x))
+// ------------------------------------------------------------------------------------------
+// The pipeline's state: the working set of a handle (contents rebuilt by every call) and what a call remembers for the next.  The handle
+// (kmdb_db.blocks) owns it; every device array is a DevBuf, so that destroying the state is all there is to releasing it.
+// ------------------------------------------------------------------------------------------
+struct BlocksState {
+    uint32_t NB = 0, n_states = 0;  // blocks, (bucket, weight class) streams
+    DevBuf<unsigned long long> p0_mask;      // [P] first (block, mask) pair of every node's local list
+    DevBuf<uint32_t> p0_info;       // [P] block | npairs << 16
+    DevBuf<uint32_t> pair_ofs;      // [P] first extra pair (valid when npairs > 1)
+    DevBuf<uint16_t> pair_blk;      // extra pairs, KMDB_PAIR_REGIONS sub-pools
+    DevBuf<unsigned long long> pair_mask;
+    uint64_t pair_cap = 0;          // entries in total
+    DevBuf<uint32_t> pair_cursor;           // [KMDB_PAIR_REGIONS * 16] one cursor per region, a cache line apart
+    DevBuf<ulonglong2> fn_mask;     // [P] for a node with more than two blocks whose parent has at most two: the parent's (F0, F1)
+    DevBuf<uint32_t> fn_blk;        // [P] and its blocks: first | second << 16 (0xFFFF: none)
+    DevBuf<unsigned long long> widebits;     // [ceil(P / 64)] nodes with more than two blocks
+    DevBuf<uint32_t> wide_cnt;      // [words + 1] popcounts / their exclusive scan
+    DevBuf<uint32_t> wide_base;
+    DevBuf<uint32_t> widx;          // [wide_cap] the wide nodes, DFS order
+    DevBuf<uint32_t> wrun_anc;      // [runs][chain_cap] root path of the first node of every run of the wide-node kernel (built by every call)
+    DevBuf<uint32_t> wrun_anc_n;
+    uint64_t wide_cap = 0;
+    DevBuf<uint32_t> chunk_key;     // [pool_cap] stream of every chunk (n_states: never opened)
+    DevBuf<uint32_t> chunk_fill;    // [pool_cap] records in the chunk
+    DevBuf<uint32_t> sorted_key;    // the chunk table sorted by stream
+    DevBuf<uint32_t> sorted_id;
+    DevBuf<void> sort_tmp;
+    size_t sort_tmp_bytes = 0;
+    int key_bits = 1;
+    DevBuf<unsigned char> rec;      // [pool_cap * 64] 16-byte record slots ({rows, cols}; diagonal streams pack 8-byte rows)
+    DevBuf<uint32_t> recw;          // [pool_cap * 64] weights of the classes with w > 1
+    uint64_t pool_cap = 0;          // chunks of 64 records, KMDB_SUBPOOLS interleaved sub-pools
+    DevBuf<uint32_t> sub_cursor;    // [KMDB_SUBPOOLS * 16]
+    // wide pool: records in arrival order + a device-wide sort by stream (the wide kernel always; the narrow kernel if its
+    // per-stream chunks do not work out)
+    bool dense_wide = false, dense_narrow = false;
+    // the narrow kernel's first-block records (X, X): 0 stream chunks + k2_apply_kernel (round 5), 1 applied inside the narrow kernel (tile in its
+    // registers, nothing written), 2 compacted per slice in DFS order + k2d_kernel on the side stream (default).  1 and 2: what they cannot take
+    // (weights of 128 and more) goes the dense_narrow way, nothing uses stream chunks
+    int k1n_mode = 2;
+    DevBuf<unsigned long long> dmask;       // mode 2: [n_nsegs * nseg_nodes] F0 of the slice's records
+    DevBuf<uint32_t> dwx;                   //         w | X << 8
+    DevBuf<uint32_t> slice_cnt;             //         [n_nsegs] records of every slice
+    DevBuf<uint32_t> direct_ctr;    // [KMDB_SUBPOOLS * 16] records applied directly, counted per wave on spread addresses
+    uint64_t last_n_direct = 0;
+    DevBuf<uint32_t> wkey, swkey;     // wide pool: stream of every record slot (0xFFFFFFFF = never written), and sorted
+    DevBuf<WideRec> wrec, swrec;       // wide pool: 16-byte records {rows, cols} (weight digit in the key word), and sorted by stream
+    uint64_t wide_pool_cap = 0;     // chunks of 64 records
+    DevBuf<uint32_t> wsub_cursor;
+    DevBuf<uint32_t> run_ctr;       // wide-node kernel: next run of every class
+    // many streams ("row mode"): the wide records go to per-block-row chunks of the chunk pool; the chunk table grouped by key, then a
+    // counting sort inside every row
+    bool row_mode = false;
+    uint32_t rec_pshift = 0;        // many streams, block width <= 54: the weight digit of a block record lives in the spare bits of its column mask (from
+                                    // this bit on) and the record travels as 16 bytes; 0: 16 bytes of masks + the 4-byte key word
+    uint32_t n_ckeys = 0;                              // keys of the chunk table: streams (+ block rows in row mode); n_ckeys = never opened
+    DevBuf<uint32_t> ct_hist, ct_offs, ct_cursor;   // [n_ckeys + 2]
+    DevBuf<void> ct_tmp;
+    size_t ct_tmp_bytes = 0;
+    DevBuf<uint32_t> rg_hist, rg_offs;   // row chunks grouped by row: [NB][rg_blocks] counts / offsets (+ total)
+    DevBuf<uint32_t> row_ids;                          // the row chunks' ids, grouped by row
+    uint32_t rg_blocks = 0;
+    DevBuf<void> rg_tmp;
+    size_t rg_tmp_bytes = 0;
+    DevBuf<uint32_t> rs_rows;                          // [2][NB + 1] first job / first table entry of every row
+    DevBuf<uint32_t> rs_hist, rs_offs;   // [rs_entries] per row [stream][job] counts / offsets
+    uint64_t rs_entries = 0;
+    DevBuf<void> rs_tmp;
+    size_t rs_tmp_bytes = 0;
+    uint64_t sorted_cap = 0;                           // records the sorted arrays (swkey / swrec) hold
+    uint32_t last_n_rowjobs = 0, last_n_sorted = 0, last_n_k2jobs = 0, k1w_waves = 0, k1w_slots = 0;   // (k1w_waves: most the pools are sized for; k1w_slots: waves the chip holds at once)
+    const void* k1w_slots_fn = nullptr;                // the wide kernel's instantiation k1w_slots was asked for
+    DevBuf<uint32_t> cs_hist, cs_offs;   // counting sort of the wide pool: [stream][block] counts / offsets (+ total)
+    DevBuf<void> cs_tmp;
+    size_t cs_tmp_bytes = 0;
+    DevBuf<uint32_t> counters;      // [KCTR_COUNT]
+    uint32_t* h_counters = nullptr; // pinned host copy
+    // ---- second level above the block records (a2a_blocks.hip, L2View): the nodes with many blocks write (node, block, mask) entries instead of
+    // their c (c + 1) / 2 records; a tile job joins two blocks' lists and applies the matches.  Row mode with few enough blocks only.
+    bool l2_on = false;
+    uint32_t l2_min_blocks = 24, l2_node_cap = 0, l2_ent_cap = 0, last_l2_nodes = 0;
+    DevBuf<uint32_t> l2_cursors;                       // [32 * 16]
+    DevBuf<unsigned long long> l2_bitmap;              // [NB][l2_node_cap / 64]
+    DevBuf<uint32_t> l2_rank, l2_len, l2_loff;   // [NB][W] rank directory, [NB] list lengths, [NB + 1] list offsets
+    DevBuf<uint32_t> l2_ent_g, l2_node_w, l2_list_w;
+    DevBuf<uint16_t> l2_ent_blk;
+    DevBuf<unsigned long long> l2_ent_mask, l2_list_mask;
+    uint64_t est_records = 0;       // sampled estimate for the chosen width
+    // what the previous call found (the pipeline is deterministic per database: grid sizes of the next call)
+    bool have_counts = false;
+    uint32_t last_n_wide = 0, last_n_chunks = 0, last_n_raw = 0, last_n_slow = 0;
+    uint64_t last_records = 0;
+    uint32_t n_slices = 1;          // passes over the pattern stream per call (a database whose records do not fit one)
+    struct SliceCounts { bool valid = false; uint32_t lo = 0, hi = 0, n_wide = 0, n_chunks = 0, n_raw = 0, n_rowjobs = 0, n_sorted = 0, n_k2jobs = 0; };
+    std::vector<SliceCounts> slice_counts;   // what the previous call found, per slice of the pattern stream
+    DevBuf<void> scan_tmp;
+    size_t scan_tmp_bytes = 0;
+    DevBuf<unsigned char> tile_touched;      // [n_states] != 0: the last call's apply kernels added something to the tile of that block pair (the sparse
+                                             // entry point scans only those tiles)
+    DevBuf<uint32_t> k2j_start;     // [n_states + 1] many streams: where every stream starts in the sorted arrays
+    DevBuf<uint2> k2j_jobs;         // [k2j_cap] jobs of the apply kernel: {stream, part of K2J_REC records}
+    uint64_t k2j_cap = 0;
+
+    ~BlocksState() { if (h_counters) (void)hipHostFree(h_counters); }
+};
+void BlocksStateDelete::operator()(BlocksState* b) const { delete b; }
+
+namespace {
+
+PoolView pool_view(const BlocksState& b, bool dense) {
+    return PoolView{b.counters, b.chunk_key, b.chunk_fill, b.rec, b.recw, b.sub_cursor, (uint32_t)(b.pool_cap / KMDB_SUBPOOLS),
+                    (uint32_t)b.pool_cap, b.wkey, b.wrec, b.wsub_cursor, (uint32_t)(b.wide_pool_cap / KMDB_SUBPOOLS), dense ? 1u : 0u,
+                    (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), b.row_mode ? 1u : 0u, b.n_states, b.rec_pshift};
+}
 
 // ---- the emit kernels' instantiations: ONE place maps a handle's record path to the function that is configured, queried and launched
 struct K1nPick { void (*fn)(const NParams); const char* name; };
@@ -2876,85 +3008,84 @@ struct ValidKey { uint32_t n_states, kmask; __host__ __device__ uint32_t operato
 // Record slots a pool can index.  Slot numbers are 32-bit; the few-streams path hands slot counts to rocPRIM as int (2^31).  The many-streams
 // path (row mode) is the engine's own kernels throughout: 2^32 minus a margin (the slot after the last chunk must not wrap to the
 // "no open chunk" value 0 of the row tables, and the windows of the apply kernel round the record count up).
-inline uint64_t pool_slot_limit(const kmdb_db* db) { return db->row_mode ? (1ull << 32) - (1ull << 20) : (1ull << 31); }
+inline uint64_t pool_slot_limit(const BlocksState& b) { return b.row_mode ? (1ull << 32) - (1ull << 20) : (1ull << 31); }
 
-int alloc_record_pool(kmdb_db* db, uint64_t chunks) {
-    FREE_NULL(db->chunk_key); FREE_NULL(db->chunk_fill); FREE_NULL(db->sorted_key); FREE_NULL(db->sorted_id);
-    FREE_NULL(db->rec); FREE_NULL(db->recw); FREE_NULL(db->sort_tmp); FREE_NULL(db->rs_hist); FREE_NULL(db->rs_offs); FREE_NULL(db->rs_tmp);
-    db->pool_cap = 0;
+int alloc_record_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
+    // (all the old arrays go before the first new one comes)
+    dev_reset(b.chunk_key, b.chunk_fill, b.sorted_key, b.sorted_id, b.rec, b.recw, b.sort_tmp, b.rs_hist, b.rs_offs, b.rs_tmp);
+    b.pool_cap = 0;
     chunks = (chunks + (uint64_t)KMDB_SUBPOOLS * ARENA_GRAB - 1) / ((uint64_t)KMDB_SUBPOOLS * ARENA_GRAB) * ((uint64_t)KMDB_SUBPOOLS * ARENA_GRAB);
-    if (chunks >= pool_slot_limit(db) >> CH_SHIFT) return kmdb_set_error("kmdb: record pool would exceed its " + std::to_string(pool_slot_limit(db)) + " record slots");
-    HIP_TRY(hipMalloc((void**)&db->chunk_key, chunks * 4));
-    HIP_TRY(hipMalloc((void**)&db->chunk_fill, chunks * 4));
-    HIP_TRY(hipMalloc((void**)&db->sorted_key, chunks * 4));
-    HIP_TRY(hipMalloc((void**)&db->sorted_id, chunks * 4));
-    HIP_TRY(hipMalloc((void**)&db->rec, (chunks << CH_SHIFT) * 16));
-    HIP_TRY(hipMalloc((void**)&db->recw, (chunks << CH_SHIFT) * 4));
+    if (chunks >= pool_slot_limit(b) >> CH_SHIFT) return kmdb_set_error("kmdb: record pool would exceed its " + std::to_string(pool_slot_limit(b)) + " record slots");
+    DEV_ALLOC(b.chunk_key, chunks);
+    DEV_ALLOC(b.chunk_fill, chunks);
+    DEV_ALLOC(b.sorted_key, chunks);
+    DEV_ALLOC(b.sorted_id, chunks);
+    DEV_ALLOC(b.rec, (chunks << CH_SHIFT) * 16);
+    DEV_ALLOC(b.recw, chunks << CH_SHIFT);
     {
-        rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(db->chunk_fill, U32toU64());
-        HIP_TRY(prim::sum(nullptr, db->sort_tmp_bytes, it, (unsigned long long*)nullptr, (int)chunks, db->stream));
+        rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(b.chunk_fill, U32toU64());
+        HIP_TRY(prim::sum(nullptr, b.sort_tmp_bytes, it, (unsigned long long*)nullptr, (int)chunks, st));
     }
-    HIP_TRY(hipMalloc(&db->sort_tmp, std::max<size_t>(db->sort_tmp_bytes, 16)));
-    if (db->row_mode) {
+    DEV_ALLOC(b.sort_tmp, std::max<size_t>(b.sort_tmp_bytes, 16));
+    if (b.row_mode) {
         // the row chunks grouped by row: [row][workgroup of RG_THREADS chunk ids] counts / offsets, the grouped ids
-        FREE_NULL(db->rg_hist); FREE_NULL(db->rg_offs); FREE_NULL(db->rg_tmp); FREE_NULL(db->row_ids);
-        db->rg_blocks = (uint32_t)((chunks + RG_THREADS - 1) / RG_THREADS);
-        const size_t rg_ne = (size_t)db->NB * db->rg_blocks + 1;
-        HIP_TRY(hipMalloc((void**)&db->rg_hist, rg_ne * 4));
-        HIP_TRY(hipMalloc((void**)&db->rg_offs, rg_ne * 4));
-        HIP_TRY(hipMalloc((void**)&db->row_ids, chunks * 4));
-        HIP_TRY(prim::exclusive_sum(nullptr, db->rg_tmp_bytes, db->rg_hist, db->rg_offs, (int)rg_ne, db->stream));
-        HIP_TRY(hipMalloc(&db->rg_tmp, std::max<size_t>(db->rg_tmp_bytes, 16)));
+        dev_reset(b.rg_hist, b.rg_offs, b.rg_tmp, b.row_ids);
+        b.rg_blocks = (uint32_t)((chunks + RG_THREADS - 1) / RG_THREADS);
+        const size_t rg_ne = (size_t)b.NB * b.rg_blocks + 1;
+        DEV_ALLOC(b.rg_hist, rg_ne);
+        DEV_ALLOC(b.rg_offs, rg_ne);
+        DEV_ALLOC(b.row_ids, chunks);
+        HIP_TRY(prim::exclusive_sum(nullptr, b.rg_tmp_bytes, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
+        DEV_ALLOC(b.rg_tmp, std::max<size_t>(b.rg_tmp_bytes, 16));
         // the sort inside the rows: at most chunks / RS_JOB_CHUNKS + NB jobs, every one with at most NB bins
-        db->rs_entries = (chunks / RS_JOB_CHUNKS + db->NB + 1) * (uint64_t)db->NB + 1;
-        if (db->rs_entries >= (1ull << 31)) return kmdb_set_error("kmdb: the table of the sort inside the block rows would exceed 2^31 entries");
-        HIP_TRY(hipMalloc((void**)&db->rs_hist, db->rs_entries * 4));
-        HIP_TRY(hipMalloc((void**)&db->rs_offs, db->rs_entries * 4));
-        HIP_TRY(prim::exclusive_sum(nullptr, db->rs_tmp_bytes, db->rs_hist, db->rs_offs, (int)db->rs_entries, db->stream));
-        HIP_TRY(hipMalloc(&db->rs_tmp, std::max<size_t>(db->rs_tmp_bytes, 16)));
+        b.rs_entries = (chunks / RS_JOB_CHUNKS + b.NB + 1) * (uint64_t)b.NB + 1;
+        if (b.rs_entries >= (1ull << 31)) return kmdb_set_error("kmdb: the table of the sort inside the block rows would exceed 2^31 entries");
+        DEV_ALLOC(b.rs_hist, b.rs_entries);
+        DEV_ALLOC(b.rs_offs, b.rs_entries);
+        HIP_TRY(prim::exclusive_sum(nullptr, b.rs_tmp_bytes, b.rs_hist.get(), b.rs_offs.get(), (int)b.rs_entries, st));
+        DEV_ALLOC(b.rs_tmp, std::max<size_t>(b.rs_tmp_bytes, 16));
     }
-    db->pool_cap = chunks;
+    b.pool_cap = chunks;
     return 0;
 }
 // few streams: the wide pool (records in arrival order + their stream keys) and the sorted copies; many streams (row mode): the
 // sorted arrays only — the wide records travel through row chunks of the chunk pool
-int alloc_wide_pool(kmdb_db* db, uint64_t chunks) {
-    FREE_NULL(db->wkey); FREE_NULL(db->wrec); FREE_NULL(db->swkey); FREE_NULL(db->swrec); FREE_NULL(db->sort2_tmp);
-    db->wide_pool_cap = 0; db->sorted_cap = 0;
+int alloc_wide_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
+    dev_reset(b.wkey, b.wrec, b.swkey, b.swrec);
+    b.wide_pool_cap = 0; b.sorted_cap = 0;
     chunks = (chunks + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB - 1) / ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) * ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB);
     const uint64_t slots = chunks << WCH_SHIFT;
-    if (slots >= pool_slot_limit(db)) return kmdb_set_error("kmdb: wide record pool would exceed its " + std::to_string(pool_slot_limit(db)) + " record slots");
-    HIP_TRY(hipMalloc((void**)&db->swkey, slots * 4));
-    HIP_TRY(hipMalloc(&db->swrec, slots * sizeof(WideRec)));
-    db->sorted_cap = slots;
+    if (slots >= pool_slot_limit(b)) return kmdb_set_error("kmdb: wide record pool would exceed its " + std::to_string(pool_slot_limit(b)) + " record slots");
+    DEV_ALLOC(b.swkey, slots);
+    DEV_ALLOC(b.swrec, slots);
+    b.sorted_cap = slots;
     // jobs of the apply kernel: every stream at least one, a long one a job per K2J_REC records
-    FREE_NULL(db->k2j_jobs);
-    db->k2j_cap = slots / K2J_REC + db->n_states + 1;
-    HIP_TRY(hipMalloc((void**)&db->k2j_jobs, db->k2j_cap * sizeof(uint2)));
-    if (db->row_mode) {
-        db->wide_pool_cap = chunks;
+    b.k2j_cap = slots / K2J_REC + b.n_states + 1;
+    DEV_ALLOC(b.k2j_jobs, b.k2j_cap);
+    if (b.row_mode) {
+        b.wide_pool_cap = chunks;
         return 0;
     }
-    HIP_TRY(hipMalloc((void**)&db->wkey, slots * 4));
-    HIP_TRY(hipMalloc(&db->wrec, slots * sizeof(WideRec)));
-    if (!db->cs_hist) {
+    DEV_ALLOC(b.wkey, slots);
+    DEV_ALLOC(b.wrec, slots);
+    if (!b.cs_hist) {
         // one pass: [stream][workgroup]
-        const size_t ne = (size_t)db->n_states * CS_BLOCKS_ONE + 1;
-        HIP_TRY(hipMalloc((void**)&db->cs_hist, ne * 4));
-        HIP_TRY(hipMalloc((void**)&db->cs_offs, ne * 4));
-        HIP_TRY(prim::exclusive_sum(nullptr, db->cs_tmp_bytes, db->cs_hist, db->cs_offs, (int)ne, db->stream));
-        HIP_TRY(hipMalloc(&db->cs_tmp, std::max<size_t>(db->cs_tmp_bytes, 16)));
+        const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
+        DEV_ALLOC(b.cs_hist, ne);
+        DEV_ALLOC(b.cs_offs, ne);
+        HIP_TRY(prim::exclusive_sum(nullptr, b.cs_tmp_bytes, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
+        DEV_ALLOC(b.cs_tmp, std::max<size_t>(b.cs_tmp_bytes, 16));
     }
-    db->wide_pool_cap = chunks;
+    b.wide_pool_cap = chunks;
     return 0;
 }
-int alloc_pair_pool(kmdb_db* db, uint64_t entries) {
-    FREE_NULL(db->pair_blk); FREE_NULL(db->pair_mask);
+int alloc_pair_pool(BlocksState& b, uint64_t entries) {
+    dev_reset(b.pair_blk, b.pair_mask);
     entries = (entries + KMDB_PAIR_REGIONS - 1) / KMDB_PAIR_REGIONS * KMDB_PAIR_REGIONS;
     if (entries >= (1ull << 32)) return kmdb_set_error("kmdb: pair pool would exceed 2^32 entries");
-    HIP_TRY(hipMalloc((void**)&db->pair_blk, entries * 2 + 64));
-    HIP_TRY(hipMalloc((void**)&db->pair_mask, entries * 8 + 64));
-    db->pair_cap = entries;
+    DEV_ALLOC(b.pair_blk, entries + 32);            // (64 bytes beyond the entries, as for the masks)
+    DEV_ALLOC(b.pair_mask, entries + 8);
+    b.pair_cap = entries;
     return 0;
 }
 
@@ -2994,8 +3125,7 @@ int kmdb_ensure_v1_arrays(kmdb_db* db) {
     if (db->v1_ready) return 0;
     if (ensure_v1_impl(db)) {
         // nothing half made is left behind: the next call starts over
-        for (void** p : {(void**)&db->meta, (void**)&db->bitpos, (void**)&db->wprefix, (void**)&db->v1_counters, (void**)&db->segs, (void**)&db->v1_scan_tmp,
-                         (void**)&db->ck_ofs, (void**)&db->ck_bit, (void**)&db->ck_id}) free_and_null(p);
+        dev_reset(db->meta, db->bitpos, db->wprefix, db->v1_counters, db->segs, db->v1_scan_tmp, db->ck_ofs, db->ck_bit, db->ck_id);
         return 1;
     }
     db->v1_ready = true;
@@ -3003,10 +3133,10 @@ int kmdb_ensure_v1_arrays(kmdb_db* db) {
 }
 static int ensure_v1_impl(kmdb_db* db) {
     const uint64_t P = db->P;
-    HIP_TRY(hipMalloc((void**)&db->meta, std::max<uint64_t>(P, 1) * sizeof(uint4)));
-    HIP_TRY(hipMalloc((void**)&db->bitpos, std::max<uint64_t>(P, 1) * 8));
-    HIP_TRY(hipMalloc((void**)&db->wprefix, (P + 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->v1_counters, 8 * sizeof(unsigned long long)));
+    DEV_ALLOC(db->meta, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->bitpos, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->wprefix, P + 1);
+    DEV_ALLOC(db->v1_counters, 8);
     HIP_TRY(hipMemset(db->v1_counters, 0, 8 * sizeof(unsigned long long)));
     if (P) hipLaunchKernelGGL(v1_arrays_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, db->stream, db->k0in, db->bitrel, db->blkbase, db->nl,
                               (uint32_t)P, db->meta, db->bitpos);
@@ -3015,28 +3145,28 @@ static int ensure_v1_impl(kmdb_db* db) {
     const uint64_t step = 2048;
     for (uint64_t f = 0; f < P; f += step) segs.push_back(Segment{(uint32_t)f, (uint32_t)std::min<uint64_t>(P, f + step)});
     while (segs.size() % WAVES_PER_BLOCK) segs.push_back(Segment{(uint32_t)P, (uint32_t)P});
-    HIP_TRY(hipMalloc((void**)&db->segs, std::max<size_t>(segs.size(), 1) * sizeof(Segment)));
+    DEV_ALLOC(db->segs, std::max<size_t>(segs.size(), 1));
     if (!segs.empty()) HIP_TRY(hipMemcpy(db->segs, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice));
     db->n_segs = (uint32_t)segs.size();
-    HIP_TRY(prim::exclusive_sum(nullptr, db->v1_scan_tmp_bytes, db->w, db->wprefix, (int)(P + 1)));
-    HIP_TRY(hipMalloc(&db->v1_scan_tmp, std::max<size_t>(db->v1_scan_tmp_bytes, 16)));
+    HIP_TRY(prim::exclusive_sum(nullptr, db->v1_scan_tmp_bytes, db->w.get(), db->wprefix.get(), (int)(P + 1)));
+    DEV_ALLOC(db->v1_scan_tmp, std::max<size_t>(db->v1_scan_tmp_bytes, 16));
     {
         const uint64_t P1 = P + 1;
-        uint32_t* cnt = nullptr;
-        void* tmp = nullptr;
+        DevBuf<uint32_t> cnt;
+        DevBuf<void> tmp;
         size_t tb = 0;
-        HIP_TRY(hipMalloc((void**)&cnt, P1 * 4));
-        HIP_TRY(hipMalloc((void**)&db->ck_ofs, P1 * 4));
+        DEV_ALLOC(cnt, P1);
+        DEV_ALLOC(db->ck_ofs, P1);
         hipLaunchKernelGGL(ck_count_kernel, dim3((unsigned)((P1 + 255) / 256)), dim3(256), 0, db->stream, db->k0in, (uint32_t)P, cnt);
-        HIP_TRY(prim::exclusive_sum(nullptr, tb, cnt, db->ck_ofs, (int)P1, db->stream));
-        HIP_TRY(hipMalloc(&tmp, std::max<size_t>(tb, 16)));
-        HIP_TRY(prim::exclusive_sum(tmp, tb, cnt, db->ck_ofs, (int)P1, db->stream));
+        HIP_TRY(prim::exclusive_sum(nullptr, tb, cnt.get(), db->ck_ofs.get(), (int)P1, db->stream));
+        DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
+        HIP_TRY(prim::exclusive_sum(tmp, tb, cnt.get(), db->ck_ofs.get(), (int)P1, db->stream));
         uint32_t n_ck = 0;
         HIP_TRY(hipMemcpyAsync(&n_ck, db->ck_ofs + P, 4, hipMemcpyDeviceToHost, db->stream));
         HIP_TRY(hipStreamSynchronize(db->stream));
-        (void)hipFree(cnt); (void)hipFree(tmp);
-        HIP_TRY(hipMalloc((void**)&db->ck_bit, std::max<uint64_t>(n_ck, 1) * 8));
-        HIP_TRY(hipMalloc((void**)&db->ck_id, std::max<uint64_t>(n_ck, 1) * 4));
+        cnt.reset(); tmp.reset();
+        DEV_ALLOC(db->ck_bit, std::max<uint64_t>(n_ck, 1));
+        DEV_ALLOC(db->ck_id, std::max<uint64_t>(n_ck, 1));
         if (P) hipLaunchKernelGGL(ck_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, db->stream, db->k0in, db->bitrel, db->blkbase, db->bits,
                                   (uint32_t)P, db->ck_ofs, db->ck_bit, db->ck_id);
         HIP_TRY(hipGetLastError());
@@ -3052,51 +3182,49 @@ int kmdb_rect_sort_apply(hipStream_t st, uint32_t* wkey, void* wrec, uint32_t ns
                          uint32_t n_cols) {
     if (!nslots) return 0;
     const uint32_t n_states = nbr * nbc, kmask = (1u << key_bits) - 1u;
-    uint32_t *swkey = nullptr, *hist = nullptr, *offs = nullptr;
-    WideRec* swrec = nullptr;
-    void* tmp = nullptr;
-    auto cleanup = [&]() { for (void* p : {(void*)swkey, (void*)swrec, (void*)hist, (void*)offs, tmp}) if (p) (void)hipFree(p); };
-#define RS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    RS_TRY(hipMalloc((void**)&swkey, (size_t)nslots * 4));
-    RS_TRY(hipMalloc((void**)&swrec, (size_t)nslots * sizeof(WideRec)));
+    DevBuf<uint32_t> swkey, hist, offs;
+    DevBuf<WideRec> swrec;
+    DevBuf<void> tmp;
+    DEV_ALLOC(swkey, (size_t)nslots);
+    DEV_ALLOC(swrec, (size_t)nslots);
     const uint32_t* total_ptr = nullptr;
     if (n_states <= CS_MAX_KEYS) {
         const size_t ne = (size_t)n_states * CS_BLOCKS_ONE + 1;
         size_t tb = 0;
-        RS_TRY(hipMalloc((void**)&hist, ne * 4));
-        RS_TRY(hipMalloc((void**)&offs, ne * 4));
-        RS_TRY(prim::exclusive_sum(nullptr, tb, hist, offs, (int)ne, st));
-        RS_TRY(hipMalloc(&tmp, std::max<size_t>(tb, 16)));
+        DEV_ALLOC(hist, ne);
+        DEV_ALLOC(offs, ne);
+        HIP_TRY(prim::exclusive_sum(nullptr, tb, hist.get(), offs.get(), (int)ne, st));
+        DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
         const CsRows no_rows{};
         hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), n_states * 4, st, wkey, nslots, n_states, n_states, (int)CS_BY_STREAM, no_rows, kmask, hist);
-        RS_TRY(prim::exclusive_sum(tmp, tb, hist, offs, (int)ne, st));
-        RS_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(n_states, false)));
+        HIP_TRY(prim::exclusive_sum(tmp, tb, hist.get(), offs.get(), (int)ne, st));
+        HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(n_states, false)));
         hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(n_states, false), st, wkey, (const WideRec*)wrec, nslots, n_states, n_states,
                            (int)CS_BY_STREAM, no_rows, kmask, offs, swkey, swrec, 0u);
         total_ptr = offs + (ne - 1);
     } else {
         size_t tb = 0;
-        RS_TRY(prim::sort_pairs(nullptr, tb, wkey, swkey, (WideRec*)wrec, swrec, (int)nslots, 0, key_bits, st));
-        RS_TRY(hipMalloc(&tmp, std::max<size_t>(tb, 16)));
-        RS_TRY(prim::sort_pairs(tmp, tb, wkey, swkey, (WideRec*)wrec, swrec, (int)nslots, 0, key_bits, st));
+        HIP_TRY(prim::sort_pairs(nullptr, tb, wkey, swkey.get(), (WideRec*)wrec, swrec.get(), (int)nslots, 0, key_bits, st));
+        DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
+        HIP_TRY(prim::sort_pairs(tmp, tb, wkey, swkey.get(), (WideRec*)wrec, swrec.get(), (int)nslots, 0, key_bits, st));
     }
     hipLaunchKernelGGL(k2_sorted_kernel, dim3((nslots + K2S_WIN - 1) / K2S_WIN), dim3(256), 0, st, swkey, (const WideRec*)swrec, nslots, total_ptr, (const uint32_t*)nullptr,
                        n_states, (uint32_t)key_bits, wide_digit_bits(key_bits), M, n_rows, 64u, nbc, n_cols, (unsigned char*)nullptr);
-    RS_TRY(hipGetLastError());
-    RS_TRY(hipStreamSynchronize(st));
-#undef RS_TRY
-    cleanup();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
 static int blocks_prepare_impl(kmdb_db* db);
 // (the flag is set only when every allocation succeeded: a failed lazy preparation inside a call leaves nothing half made behind)
 int kmdb_blocks_prepare(kmdb_db* db) {
+    db->blocks.reset(new BlocksState());
     if (blocks_prepare_impl(db)) { kmdb_blocks_release(db); return 1; }
     db->blocks_prepared = true;
     return 0;
 }
 static int blocks_prepare_impl(kmdb_db* db) {
+    BlocksState& b = *db->blocks;
     const uint64_t N = db->N, P = db->P;
     db->fallback_reason.clear();
     if (N < 2 || P == 0) { db->fallback_reason = "fewer than two samples"; return 0; }
@@ -3127,7 +3255,9 @@ static int blocks_prepare_impl(kmdb_db* db) {
         q.P = (uint32_t)P; q.stride = stride;
         for (int c = 0; c < EST_NW; ++c) { q.widths[c] = cands[c]; q.magics[c] = (uint32_t)((1ull << 32) / cands[c]) + 1u; }
         q.l2_min = getenv("KMDB_L2_MIN") ? std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(getenv("KMDB_L2_MIN"))) : L2_MIN_BLOCKS;
-        HIP_TRY(hipMalloc((void**)&q.out, (3 * EST_NW + 1) * 8));
+        DevBuf<unsigned long long> d_out;
+        DEV_ALLOC(d_out, 3 * EST_NW + 1);
+        q.out = d_out;
         HIP_TRY(hipMemsetAsync(q.out, 0, (3 * EST_NW + 1) * 8, db->stream));
         const uint64_t nthreads = (P + stride - 1) / stride;
         hipLaunchKernelGGL(width_estimate_kernel, dim3((unsigned)((nthreads + 63) / 64)), dim3(64), 0, db->stream, q);
@@ -3135,7 +3265,6 @@ static int blocks_prepare_impl(kmdb_db* db) {
         unsigned long long h[3 * EST_NW + 1];
         HIP_TRY(hipMemcpyAsync(h, q.out, sizeof h, hipMemcpyDeviceToHost, db->stream));
         HIP_TRY(hipStreamSynchronize(db->stream));
-        (void)hipFree(q.out);
         int best = 0;
         for (int c = 1; c < EST_NW; ++c) if (h[c] + h[EST_NW + c] < h[best] + h[EST_NW + best]) best = c;
         if (forced >= 32 && forced <= 64) {
@@ -3144,44 +3273,44 @@ static int blocks_prepare_impl(kmdb_db* db) {
             for (int c = 0; c < EST_NW; ++c) if (cands[c] >= forced) best = c;
         } else db->width = cands[best];
         est_n = h[best] * stride; est_g = h[EST_NW + best] * stride; est_l2 = h[2 * EST_NW + 1 + best] * stride;
-        db->est_records = est_n + est_g;
+        b.est_records = est_n + est_g;
         if (verbose) {
             fprintf(stderr, "[kmdb] width estimate (1 node in %u, %llu sampled):", stride, h[2 * EST_NW]);
             for (int c = 0; c < EST_NW; ++c) fprintf(stderr, " %u:%llu", cands[c], (h[c] + h[EST_NW + c]) * stride);
             fprintf(stderr, " -> width %u\n", db->width);
         }
     }
-    db->NB = (uint32_t)((N + db->width - 1) / db->width);
-    const uint64_t n_states = (uint64_t)db->NB * (db->NB + 1) / 2;          // streams = block pairs
+    b.NB = (uint32_t)((N + db->width - 1) / db->width);
+    const uint64_t n_states = (uint64_t)b.NB * (b.NB + 1) / 2;          // streams = block pairs
     if (n_states + 1 >= (1ull << 22)) { db->fallback_reason = "too many block pairs"; return 0; }          // 22 stream bits + 8-bit weight digits in a key word
     static_assert((1ull << 22) < (uint64_t)BNONE * (BNONE + 1ull) / 2ull, "fewer than 2^22 block pairs keep the block index (< 2897) below BNONE and inside pair_blk's 16 bits");
-    db->n_states = (uint32_t)n_states;
-    if (k1w_wave_bytes(std::max<uint32_t>(K1W_ARENA_MIN, (db->NB + 2u + 63u) & ~63u), (db->NB + 2u + 3u) & ~3u, db->chain_cap, db->NB) > (size_t)(152u << 10)) {
-        db->fallback_reason = "the lists of the wide-node kernel do not fit the LDS (" + std::to_string(db->NB) + " blocks, root paths of up to " +
+    b.n_states = (uint32_t)n_states;
+    if (k1w_wave_bytes(std::max<uint32_t>(K1W_ARENA_MIN, (b.NB + 2u + 63u) & ~63u), (b.NB + 2u + 3u) & ~3u, db->chain_cap, b.NB) > (size_t)(152u << 10)) {
+        db->fallback_reason = "the lists of the wide-node kernel do not fit the LDS (" + std::to_string(b.NB) + " blocks, root paths of up to " +
                               std::to_string(db->max_depth) + " nodes)";
         return 0;
     }
     phase("block width estimate");
     // ---- working set
-    HIP_TRY(hipMalloc((void**)&db->p0_mask, P * 8));
-    HIP_TRY(hipMalloc((void**)&db->p0_info, P * 4));
-    HIP_TRY(hipMalloc((void**)&db->pair_ofs, P * 4));
-    HIP_TRY(hipMalloc((void**)&db->pair_cursor, (KMDB_PAIR_REGIONS + 1) * 16 * 4));
-    HIP_TRY(hipMalloc((void**)&db->fn_mask, P * 16));
-    HIP_TRY(hipMalloc((void**)&db->fn_blk, P * 4));
+    DEV_ALLOC(b.p0_mask, P);
+    DEV_ALLOC(b.p0_info, P);
+    DEV_ALLOC(b.pair_ofs, P);
+    DEV_ALLOC(b.pair_cursor, (KMDB_PAIR_REGIONS + 1) * 16);
+    DEV_ALLOC(b.fn_mask, P);
+    DEV_ALLOC(b.fn_blk, P);
     const uint64_t n_words = (P + 63) / 64;
-    HIP_TRY(hipMalloc((void**)&db->widebits, n_words * 8));
-    HIP_TRY(hipMalloc((void**)&db->wide_cnt, (n_words + 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->wide_base, (n_words + 1) * 4));
-    HIP_TRY(prim::exclusive_sum(nullptr, db->scan_tmp_bytes, db->wide_cnt, db->wide_base, (int)(n_words + 1)));
-    HIP_TRY(hipMalloc(&db->scan_tmp, std::max<size_t>(db->scan_tmp_bytes, 16)));
-    HIP_TRY(hipMalloc((void**)&db->counters, KCTR_COUNT * 4));
-    HIP_TRY(hipHostMalloc((void**)&db->h_counters, KCTR_COUNT * 4));
+    DEV_ALLOC(b.widebits, n_words);
+    DEV_ALLOC(b.wide_cnt, n_words + 1);
+    DEV_ALLOC(b.wide_base, n_words + 1);
+    HIP_TRY(prim::exclusive_sum(nullptr, b.scan_tmp_bytes, b.wide_cnt.get(), b.wide_base.get(), (int)(n_words + 1)));
+    DEV_ALLOC(b.scan_tmp, std::max<size_t>(b.scan_tmp_bytes, 16));
+    DEV_ALLOC(b.counters, KCTR_COUNT);
+    HIP_TRY(hipHostMalloc((void**)&b.h_counters, KCTR_COUNT * 4));
     phase("per-node arrays (hipMalloc)");
     {
         // extra pairs: sampled with the chosen width (K0 reserves min(l - 1, blocks spanned) per list that is not a single short run)
-        unsigned long long* d_need = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_need, 8));
+        DevBuf<unsigned long long> d_need;
+        DEV_ALLOC(d_need, 1);
         HIP_TRY(hipMemsetAsync(d_need, 0, 8, db->stream));
         const BlockMap bm{db->width, (uint32_t)((1ull << 32) / db->width) + 1u};
         const uint64_t nthreads = (P + stride - 1) / stride;
@@ -3190,19 +3319,19 @@ static int blocks_prepare_impl(kmdb_db* db) {
         unsigned long long h_need = 0;
         HIP_TRY(hipMemcpyAsync(&h_need, d_need, 8, hipMemcpyDeviceToHost, db->stream));
         HIP_TRY(hipStreamSynchronize(db->stream));
-        (void)hipFree(d_need);
+        d_need.reset();
         const uint64_t est_pairs = h_need * stride;
         if (verbose) fprintf(stderr, "[kmdb] extra (block, mask) pairs, sampled: %llu\n", (unsigned long long)est_pairs);
         // (twice the estimate: three quarters of the pool are wave-private sub-pools, and a sub-pool that runs out sends its waves to the shared
         // rest behind ONE cursor — with 1.25 x the estimate the sub-pools were nearly full and the decode launches took 3.9 instead of 2.2 ms at C2,
         // profiles/r06_j6: same-address device atomics)
-        if (alloc_pair_pool(db, std::max<uint64_t>(est_pairs * 2 + P / 4, (uint64_t)KMDB_PAIR_REGIONS * 64))) return 1;
+        if (alloc_pair_pool(b, std::max<uint64_t>(est_pairs * 2 + P / 4, (uint64_t)KMDB_PAIR_REGIONS * 64))) return 1;
     }
     phase("pair estimate + pair pool");
-    HIP_TRY(hipMalloc((void**)&db->sub_cursor, KMDB_SUBPOOLS * 16 * 4));
-    HIP_TRY(hipMalloc((void**)&db->wsub_cursor, KMDB_SUBPOOLS * 16 * 4));
-    HIP_TRY(hipMalloc((void**)&db->run_ctr, K1W_CTRS * 16 * 4));
-    HIP_TRY(hipMalloc((void**)&db->direct_ctr, KMDB_SUBPOOLS * 16 * 4));
+    DEV_ALLOC(b.sub_cursor, KMDB_SUBPOOLS * 16);
+    DEV_ALLOC(b.wsub_cursor, KMDB_SUBPOOLS * 16);
+    DEV_ALLOC(b.run_ctr, K1W_CTRS * 16);
+    DEV_ALLOC(b.direct_ctr, KMDB_SUBPOOLS * 16);
     // Where the records go.  The narrow kernel's first-block diagonal records follow the clustering of the DFS stream: per-stream
     // chunks (an open chunk per block and wave), applied straight from the grouped chunk table.  The other records spread over
     // many streams, a few per stream and wave:
@@ -3214,64 +3343,64 @@ static int blocks_prepare_impl(kmdb_db* db) {
     //                                  grouping by row in a pass of its own cost another 7.5 ms).
     // With more streams than the narrow kernel's open-chunk table holds it sends its diagonal records the same way, if its chunks turn
     // out to be evicted nearly empty.
-    db->dense_wide = true;
-    db->dense_narrow = false;
-    if (const char* e = getenv("KMDB_DENSE")) db->dense_narrow = atoi(e) >= 2;
-    // Round 6: the narrow kernel's first-block records no longer travel through stream chunks (engine_state.h: k1n_mode; KMDB_K1N_MODE=0 / 1 / 2
+    b.dense_wide = true;
+    b.dense_narrow = false;
+    if (const char* e = getenv("KMDB_DENSE")) b.dense_narrow = atoi(e) >= 2;
+    // Round 6: the narrow kernel's first-block records no longer travel through stream chunks (BlocksState: k1n_mode; KMDB_K1N_MODE=0 / 1 / 2
     // for the A/B): compacted per slice and applied by k2d_kernel beside the wide kernel (2, default), or applied inside the narrow kernel (1).
-    db->k1n_mode = 2;
-    if (const char* e = getenv("KMDB_K1N_MODE")) if (*e) db->k1n_mode = std::max(0, std::min(2, atoi(e)));
-    if (db->k1n_mode) db->dense_narrow = true;
-    if (db->k1n_mode == 2) {
+    b.k1n_mode = 2;
+    if (const char* e = getenv("KMDB_K1N_MODE")) if (*e) b.k1n_mode = std::max(0, std::min(2, atoi(e)));
+    if (b.k1n_mode) b.dense_narrow = true;
+    if (b.k1n_mode == 2) {
         const size_t slots = (size_t)db->n_nsegs * db->nseg_nodes;
-        HIP_TRY(hipMalloc((void**)&db->dmask, std::max<size_t>(slots, 1) * 8));
-        HIP_TRY(hipMalloc((void**)&db->dwx, std::max<size_t>(slots, 1) * 4));
-        HIP_TRY(hipMalloc((void**)&db->slice_cnt, std::max<size_t>(db->n_nsegs, 1) * 4));
+        DEV_ALLOC(b.dmask, std::max<size_t>(slots, 1));
+        DEV_ALLOC(b.dwx, std::max<size_t>(slots, 1));
+        DEV_ALLOC(b.slice_cnt, std::max<size_t>(db->n_nsegs, 1));
     }
-    db->row_mode = db->n_states > CS_MAX_KEYS;
-    if (const char* e = getenv("KMDB_ROW_MODE")) if (*e) db->row_mode = atoi(e) != 0;          // (tests: small databases through the many-streams path)
+    b.row_mode = b.n_states > CS_MAX_KEYS;
+    if (const char* e = getenv("KMDB_ROW_MODE")) if (*e) b.row_mode = atoi(e) != 0;          // (tests: small databases through the many-streams path)
     // packed records: a block width of at most 54 leaves the column mask 10 spare bits and more — an 8-bit weight digit at least and the digit's
     // index — so the records of the many-streams path travel as 16 bytes through the sort and the apply step (KMDB_REC_PACKED=0: 16 + 4, A/B)
     // (round 5, later: the few-streams path as well — its one-pass sort moves 16 bytes per record and leaves the key words behind)
-    db->rec_pshift = (db->width <= 54u && !(getenv("KMDB_REC_PACKED") && getenv("KMDB_REC_PACKED")[0] == '0')) ? db->width : 0u;
+    b.rec_pshift = (db->width <= 54u && !(getenv("KMDB_REC_PACKED") && getenv("KMDB_REC_PACKED")[0] == '0')) ? db->width : 0u;
     // The second level (many streams, <= 256 blocks: see blocks_attempt) writes no records for the nodes with L2_MIN_BLOCKS blocks or more — 52 % of the
     // estimate at 10 000 samples.  Round 5 sized the pools from the estimate before it: 110 GB for 616 M records of 16 bytes.
     {
         const char* l2_env = getenv("KMDB_L2");
-        if (db->row_mode && db->NB <= 256u && !(l2_env && l2_env[0] == '0')) {
+        if (b.row_mode && b.NB <= 256u && !(l2_env && l2_env[0] == '0')) {
             if (verbose) fprintf(stderr, "[kmdb] block records estimated: %llu, of them %llu from nodes the second level joins per tile instead\n",
                                  (unsigned long long)(est_n + est_g), (unsigned long long)est_l2);
             est_g -= std::min(est_g, est_l2);
         }
     }
-    db->n_ckeys = db->n_states;                                  // keys of the grouped chunk table = the streams (row chunks sit in their rows' lists)
+    b.n_ckeys = b.n_states;                                  // keys of the grouped chunk table = the streams (row chunks sit in their rows' lists)
     {
         int key_bits = 1;
-        while ((1ull << key_bits) <= (uint64_t)db->n_states + 1) ++key_bits;          // streams; all-ones = never written
-        db->key_bits = key_bits;
+        while ((1ull << key_bits) <= (uint64_t)b.n_states + 1) ++key_bits;          // streams; all-ones = never written
+        b.key_bits = key_bits;
     }
-    HIP_TRY(hipMalloc((void**)&db->tile_touched, (size_t)db->n_states + 1));
-    HIP_TRY(hipMalloc((void**)&db->ct_hist, ((size_t)db->n_ckeys + 2) * 4));
-    HIP_TRY(hipMalloc((void**)&db->ct_offs, ((size_t)db->n_ckeys + 2) * 4));
-    HIP_TRY(hipMalloc((void**)&db->ct_cursor, ((size_t)db->n_ckeys + 2) * 4));
-    HIP_TRY(prim::exclusive_sum(nullptr, db->ct_tmp_bytes, db->ct_hist, db->ct_offs, (int)(db->n_ckeys + 1), db->stream));
-    HIP_TRY(hipMalloc(&db->ct_tmp, std::max<size_t>(db->ct_tmp_bytes, 16)));
+    DEV_ALLOC(b.tile_touched, (size_t)b.n_states + 1);
+    DEV_ALLOC(b.ct_hist, (size_t)b.n_ckeys + 2);
+    DEV_ALLOC(b.ct_offs, (size_t)b.n_ckeys + 2);
+    DEV_ALLOC(b.ct_cursor, (size_t)b.n_ckeys + 2);
+    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist.get(), b.ct_offs.get(), (int)(b.n_ckeys + 1), db->stream));
+    DEV_ALLOC(b.ct_tmp, std::max<size_t>(b.ct_tmp_bytes, 16));
     // A database whose records do not fit one pass (2^31 record slots, or the memory left) is taken in SLICES of the pattern stream:
     // every slice emits the records of its own patterns only, the partial matrices add up in place (the engine's own version of
     // kmdb_opts.shard_index / shard_count; the reference blocks by `-buffer` the same way, similarity_calculator.cpp:290-325).
     {
         uint64_t slices = 1;
         const uint64_t slots = (est_n + est_g) * 3 / 2;
-        const uint64_t usable = pool_slot_limit(db) / 4 * 3;                                            // three quarters of the slots a pool can index
+        const uint64_t usable = pool_slot_limit(b) / 4 * 3;                                            // three quarters of the slots a pool can index
         slices = std::max<uint64_t>(slices, (slots + usable - 1) / usable);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
             slices = std::max<uint64_t>(slices, (slots * 44 + free_b / 2) / std::max<size_t>(free_b * 6 / 10, 1));     // pool + sorted copy: 44 B per slot, 60 % of what is free
         if (const char* e = getenv("KMDB_SLICES")) if (*e) slices = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-        db->n_slices = (uint32_t)std::min<uint64_t>(slices, 1u << 16);
-        if (verbose && db->n_slices > 1) fprintf(stderr, "[kmdb] %llu block records estimated: %u slices of the pattern stream per call\n",
-                                                 (unsigned long long)(est_n + est_g), db->n_slices);
-        est_n = est_n / db->n_slices + 1; est_g = est_g / db->n_slices + 1;
+        b.n_slices = (uint32_t)std::min<uint64_t>(slices, 1u << 16);
+        if (verbose && b.n_slices > 1) fprintf(stderr, "[kmdb] %llu block records estimated: %u slices of the pattern stream per call\n",
+                                                 (unsigned long long)(est_n + est_g), b.n_slices);
+        est_n = est_n / b.n_slices + 1; est_g = est_g / b.n_slices + 1;
     }
     if (const char* e = getenv("KMDB_POOL_PERCENT")) if (*e) {
         // (tests: pools far too small, so that the first call takes the enlarge-and-repeat path on every one of them)
@@ -3279,85 +3408,74 @@ static int blocks_prepare_impl(kmdb_db* db) {
         est_n = est_n * pct / 100 + 1; est_g = est_g * pct / 100 + 1;
     }
     // waves of the wide-node kernel: in row mode every wave may end with an open chunk per block row
-    db->k1w_waves = K1W_MAX_WAVES;
-    if (db->row_mode) {
-        db->k1w_waves = std::min<uint32_t>(db->k1w_waves, std::max<uint32_t>(256u, std::min<uint32_t>(4096u, (1u << 21) / std::max<uint32_t>(db->NB, 1u))));
-        HIP_TRY(hipMalloc((void**)&db->rs_rows, (size_t)2 * (db->NB + 1) * 4));
+    b.k1w_waves = K1W_MAX_WAVES;
+    if (b.row_mode) {
+        b.k1w_waves = std::min<uint32_t>(b.k1w_waves, std::max<uint32_t>(256u, std::min<uint32_t>(4096u, (1u << 21) / std::max<uint32_t>(b.NB, 1u))));
+        DEV_ALLOC(b.rs_rows, (size_t)2 * (b.NB + 1));
     }
-    HIP_TRY(hipMalloc((void**)&db->k2j_start, ((size_t)db->n_states + 2) * 4));
+    DEV_ALLOC(b.k2j_start, (size_t)b.n_states + 2);
     // stream chunks: the narrow estimate at two thirds average fill, plus what the waves hold when they end (open chunks, an
     // unfinished grab); wide records: the wide estimate at two thirds (+ a grab / the open row chunks per wave)
     // (modes 1 and 2: of the narrow kernel's first-block records only the stragglers go to the pools — weights of 128 and more, in mode 1 also a
     // slice's nodes outside its tile: a sixteenth of the estimate is generous, and a pool that is too small is enlarged as ever)
-    if (db->k1n_mode) { est_g += est_n / 16 + 1; est_n = 0; }
-    if (db->row_mode) {
+    if (b.k1n_mode) { est_g += est_n / 16 + 1; est_n = 0; }
+    if (b.row_mode) {
         // the estimate (one node in `stride`, exact per node) plus a quarter, plus what the waves hold when they end (open chunks, unfinished grabs); the
         // sorted copy holds the records themselves: the estimate plus an eighth.  A pool that turns out too small is enlarged and the call repeated.
         // (chunks, not records, are what runs out: every wave keeps an open chunk per block row it writes to — the wide kernel's waves all rows, a
         // slice of the narrow kernel the rows of its nodes' second blocks, up to 48 counted here — and leaves it partly filled.  Round 5's pools hid
         // that behind the records the second level no longer writes; with the estimate after the second level and 12 chunks per slice the first
         // call at 10 000 samples ran out and doubled its pool: profiles/r06_close_bench.err)
-        if (alloc_record_pool(db, (est_n + est_g) * 5 / 4 / CH_REC + (uint64_t)db->n_nsegs * std::min<uint32_t>(db->NB, 48u) + (uint64_t)db->k1w_waves * (db->NB + ARENA_GRAB) + 4096)) return 1;
-        if (alloc_wide_pool(db, (est_n + est_g) * 9 / 8 / WCH_REC + 4096)) return 1;
+        if (alloc_record_pool(b, db->stream, (est_n + est_g) * 5 / 4 / CH_REC + (uint64_t)db->n_nsegs * std::min<uint32_t>(b.NB, 48u) + (uint64_t)b.k1w_waves * (b.NB + ARENA_GRAB) + 4096)) return 1;
+        if (alloc_wide_pool(b, db->stream, (est_n + est_g) * 9 / 8 / WCH_REC + 4096)) return 1;
     } else {
-        if (alloc_record_pool(db, est_n * 3 / 2 / CH_REC + (db->dense_narrow ? 0u : (uint64_t)db->n_nsegs * 8) + 4096)) return 1;
-        if (alloc_wide_pool(db, est_g * 3 / 2 / WCH_REC + (uint64_t)(K1W_MAX_WAVES + 64) * (WIDE_GRAB + 2) + (uint64_t)db->n_nsegs * (WIDE_GRAB / 2) + 1024)) return 1;
+        if (alloc_record_pool(b, db->stream, est_n * 3 / 2 / CH_REC + (b.dense_narrow ? 0u : (uint64_t)db->n_nsegs * 8) + 4096)) return 1;
+        if (alloc_wide_pool(b, db->stream, est_g * 3 / 2 / WCH_REC + (uint64_t)(K1W_MAX_WAVES + 64) * (WIDE_GRAB + 2) + (uint64_t)db->n_nsegs * (WIDE_GRAB / 2) + 1024)) return 1;
     }
     if (verbose) fprintf(stderr, "[kmdb] prepare: record pools %.2f GB\n", kmdb_blocks_device_bytes(db) / 1e9);
     phase("record pools (hipMalloc)");
     return 0;
 }
 
-void kmdb_blocks_release(kmdb_db* db) {
-    FREE_NULL(db->p0_mask); FREE_NULL(db->p0_info); FREE_NULL(db->pair_ofs); FREE_NULL(db->pair_blk); FREE_NULL(db->pair_mask);
-    FREE_NULL(db->pair_cursor); FREE_NULL(db->fn_mask); FREE_NULL(db->fn_blk); FREE_NULL(db->widebits); FREE_NULL(db->wide_cnt);
-    FREE_NULL(db->wide_base); FREE_NULL(db->widx); FREE_NULL(db->wrun_anc); FREE_NULL(db->wrun_anc_n); FREE_NULL(db->chunk_key); FREE_NULL(db->chunk_fill); FREE_NULL(db->sorted_key);
-    FREE_NULL(db->sorted_id); FREE_NULL(db->chunk_iota); FREE_NULL(db->sort_tmp);
-    FREE_NULL(db->wkey); FREE_NULL(db->wrec); FREE_NULL(db->swkey); FREE_NULL(db->swrec); FREE_NULL(db->sort2_tmp); FREE_NULL(db->wsub_cursor); FREE_NULL(db->cs_hist); FREE_NULL(db->cs_offs); FREE_NULL(db->cs_rows); FREE_NULL(db->cs_tmp);
-    FREE_NULL(db->rec); FREE_NULL(db->recw); FREE_NULL(db->counters); FREE_NULL(db->scan_tmp); FREE_NULL(db->sub_cursor);
-    FREE_NULL(db->ct_hist); FREE_NULL(db->ct_offs); FREE_NULL(db->ct_cursor); FREE_NULL(db->ct_tmp); FREE_NULL(db->rs_rows); FREE_NULL(db->rs_hist); FREE_NULL(db->rs_offs);
-    FREE_NULL(db->run_ctr); FREE_NULL(db->direct_ctr); FREE_NULL(db->dmask); FREE_NULL(db->dwx); FREE_NULL(db->slice_cnt); FREE_NULL(db->rs_tmp); FREE_NULL(db->rg_hist); FREE_NULL(db->rg_offs); FREE_NULL(db->rg_tmp); FREE_NULL(db->row_ids); FREE_NULL(db->k2j_start); FREE_NULL(db->k2j_jobs); FREE_NULL(db->tile_touched);
-    FREE_NULL(db->l2_cursors); FREE_NULL(db->l2_bitmap); FREE_NULL(db->l2_rank); FREE_NULL(db->l2_len); FREE_NULL(db->l2_loff); FREE_NULL(db->l2_ent_g);
-    FREE_NULL(db->l2_node_w); FREE_NULL(db->l2_list_w); FREE_NULL(db->l2_ent_blk); FREE_NULL(db->l2_ent_mask); FREE_NULL(db->l2_list_mask);
-    db->l2_node_cap = 0; db->l2_ent_cap = 0;
-    if (db->h_counters) { (void)hipHostFree(db->h_counters); db->h_counters = nullptr; }
-    db->pool_cap = 0; db->pair_cap = 0; db->wide_cap = 0;
-}
+// the state's destructor frees every array it holds
+void kmdb_blocks_release(kmdb_db* db) { db->blocks.reset(); }
 
 uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
-    if (!db->counters) return 0;
-    return db->P * (8 + 4 + 4 + 16 + 4) + (db->dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + db->pair_cap * 10 + ((db->pool_cap << CH_SHIFT) * 20) + db->pool_cap * 16 + db->wide_cap * 4 + (db->P / 64) * 16 +
-           (db->wide_pool_cap << WCH_SHIFT) * (db->row_mode ? 20 : 40) + db->rs_entries * 8 + (uint64_t)db->n_ckeys * 12 +
-           (uint64_t)db->NB * (db->l2_node_cap / 64u) * 12 + (uint64_t)db->l2_ent_cap * 26 + (uint64_t)db->l2_node_cap * 4;
+    if (!db->blocks || !db->blocks->counters) return 0;
+    const BlocksState& b = *db->blocks;
+    return db->P * (8 + 4 + 4 + 16 + 4) + (b.dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + b.pair_cap * 10 + ((b.pool_cap << CH_SHIFT) * 20) + b.pool_cap * 16 + b.wide_cap * 4 + (db->P / 64) * 16 +
+           (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.n_ckeys * 12 +
+           (uint64_t)b.NB * (b.l2_node_cap / 64u) * 12 + (uint64_t)b.l2_ent_cap * 26 + (uint64_t)b.l2_node_cap * 4;
 }
 
 namespace {
 
 // second level (L2View): arrays for node_cap node indices and ent_cap entries; frees what was there
-int alloc_l2(kmdb_db* db, uint32_t node_cap, uint32_t ent_cap) {
-    FREE_NULL(db->l2_cursors); FREE_NULL(db->l2_bitmap); FREE_NULL(db->l2_rank); FREE_NULL(db->l2_len); FREE_NULL(db->l2_loff); FREE_NULL(db->l2_ent_g);
-    FREE_NULL(db->l2_node_w); FREE_NULL(db->l2_list_w); FREE_NULL(db->l2_ent_blk); FREE_NULL(db->l2_ent_mask); FREE_NULL(db->l2_list_mask);
+int alloc_l2(BlocksState& b, uint32_t node_cap, uint32_t ent_cap) {
+    dev_reset(b.l2_cursors, b.l2_bitmap, b.l2_rank, b.l2_len, b.l2_loff, b.l2_ent_g, b.l2_node_w, b.l2_list_w, b.l2_ent_blk, b.l2_ent_mask, b.l2_list_mask);
+    b.l2_node_cap = 0; b.l2_ent_cap = 0;
     node_cap = (node_cap + 64u * L2_SUB - 1u) / (64u * L2_SUB) * (64u * L2_SUB);
     ent_cap = (ent_cap + L2_ENT_GRAB * L2_SUB - 1u) / (L2_ENT_GRAB * L2_SUB) * (L2_ENT_GRAB * L2_SUB);
-    const size_t W = node_cap / 64u, NB = db->NB;
-    HIP_TRY(hipMalloc((void**)&db->l2_cursors, 2 * L2_SUB * 16 * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_bitmap, NB * W * 8));
-    HIP_TRY(hipMalloc((void**)&db->l2_rank, NB * W * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_len, NB * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_loff, (NB + 2) * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_ent_g, (size_t)ent_cap * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_ent_blk, (size_t)ent_cap * 2));
-    HIP_TRY(hipMalloc((void**)&db->l2_ent_mask, (size_t)ent_cap * 8));
-    HIP_TRY(hipMalloc((void**)&db->l2_list_mask, (size_t)ent_cap * 8));
-    HIP_TRY(hipMalloc((void**)&db->l2_list_w, (size_t)ent_cap * 4));
-    HIP_TRY(hipMalloc((void**)&db->l2_node_w, (size_t)node_cap * 4));
-    db->l2_node_cap = node_cap; db->l2_ent_cap = ent_cap;
+    const size_t W = node_cap / 64u, NB = b.NB;
+    DEV_ALLOC(b.l2_cursors, 2 * L2_SUB * 16);
+    DEV_ALLOC(b.l2_bitmap, NB * W);
+    DEV_ALLOC(b.l2_rank, NB * W);
+    DEV_ALLOC(b.l2_len, NB);
+    DEV_ALLOC(b.l2_loff, NB + 2);
+    DEV_ALLOC(b.l2_ent_g, (size_t)ent_cap);
+    DEV_ALLOC(b.l2_ent_blk, (size_t)ent_cap);
+    DEV_ALLOC(b.l2_ent_mask, (size_t)ent_cap);
+    DEV_ALLOC(b.l2_list_mask, (size_t)ent_cap);
+    DEV_ALLOC(b.l2_list_w, (size_t)ent_cap);
+    DEV_ALLOC(b.l2_node_w, (size_t)node_cap);
+    b.l2_node_cap = node_cap; b.l2_ent_cap = ent_cap;
     return 0;
 }
 
 // one attempt of the whole pipeline; *retry is set when a pool was too small (it has been enlarged)
 // decode: run K0 (the first slice of a call does; what it leaves — the local (block, mask) pairs of every node — serves all slices)
 int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry) {
+    BlocksState& b = *db->blocks;
     *retry = false;
     // KMDB_SYNC_DEBUG: wait after every stage and name the one that failed (debugging aid, no effect on results)
     static const bool sync_debug = getenv("KMDB_SYNC_DEBUG") != nullptr;
@@ -3370,42 +3488,42 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     const uint32_t P = (uint32_t)db->P;
     const BlockMap bm{db->width, (uint32_t)((1ull << 32) / db->width) + 1u};
     const uint32_t n_words = (P + 63) / 64;
-    const uint32_t pool_cap = (uint32_t)db->pool_cap;
-    const bool row_mode = db->row_mode;
-    const uint32_t n_ckeys = db->n_ckeys;
-    HIP_TRY(hipMemsetAsync(db->counters, 0, KCTR_COUNT * 4, st));
-    if (decode) HIP_TRY(hipMemsetAsync(db->pair_cursor, 0, (KMDB_PAIR_REGIONS + 1) * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(db->sub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(db->wsub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(db->run_ctr, 0, K1W_CTRS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(db->direct_ctr, 0, KMDB_SUBPOOLS * 16 * 4, st));
+    const uint32_t pool_cap = (uint32_t)b.pool_cap;
+    const bool row_mode = b.row_mode;
+    const uint32_t n_ckeys = b.n_ckeys;
+    HIP_TRY(hipMemsetAsync(b.counters, 0, KCTR_COUNT * 4, st));
+    if (decode) HIP_TRY(hipMemsetAsync(b.pair_cursor, 0, (KMDB_PAIR_REGIONS + 1) * 16 * 4, st));
+    HIP_TRY(hipMemsetAsync(b.sub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
+    HIP_TRY(hipMemsetAsync(b.wsub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
+    HIP_TRY(hipMemsetAsync(b.run_ctr, 0, K1W_CTRS * 16 * 4, st));
+    HIP_TRY(hipMemsetAsync(b.direct_ctr, 0, KMDB_SUBPOOLS * 16 * 4, st));
     // Sizes of the launches: measured by the previous call on this handle.  What the narrow kernel produces repeats exactly; where
     // the wide kernel's records land depends on which wave took which run, so the chunk counts behind it vary a little from call
     // to call: those launches get some slack, every kernel takes the true counts from device memory, and the call is repeated with
     // upper bounds if a true count exceeded its launch (checked at the end).
     auto with_slack = [](uint32_t v) -> uint32_t { return v + v / 8u + 1024u; };
-    const uint32_t raw_launch = db->have_counts ? (uint32_t)std::min<uint64_t>(with_slack(db->last_n_raw), row_mode ? 0xFFFFFFFFull : db->wide_pool_cap) : 0u;
+    const uint32_t raw_launch = b.have_counts ? (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), row_mode ? 0xFFFFFFFFull : b.wide_pool_cap) : 0u;
     if (!row_mode) {
         // never-written slots of the wide pool sort last; only the part the previous call used has to be reset
-        const uint64_t wslots = db->have_counts ? (uint64_t)raw_launch << WCH_SHIFT : db->wide_pool_cap << WCH_SHIFT;
-        HIP_TRY(hipMemsetAsync(db->wkey, 0xFF, wslots * 4, st));
+        const uint64_t wslots = b.have_counts ? (uint64_t)raw_launch << WCH_SHIFT : b.wide_pool_cap << WCH_SHIFT;
+        HIP_TRY(hipMemsetAsync(b.wkey, 0xFF, wslots * 4, st));
     }
-    HIP_TRY(hipMemsetAsync(db->chunk_fill, 0, (size_t)pool_cap * 4, st));
-    HIP_TRY(hipMemsetAsync(db->ct_hist, 0, ((size_t)n_ckeys + 2) * 4, st));
-    hipLaunchKernelGGL(fill_u32_kernel, dim3((pool_cap + 255) / 256), dim3(256), 0, st, db->chunk_key, pool_cap, 0xFFFFFFFFu);      // never opened
+    HIP_TRY(hipMemsetAsync(b.chunk_fill, 0, (size_t)pool_cap * 4, st));
+    HIP_TRY(hipMemsetAsync(b.ct_hist, 0, ((size_t)n_ckeys + 2) * 4, st));
+    hipLaunchKernelGGL(fill_u32_kernel, dim3((pool_cap + 255) / 256), dim3(256), 0, st, b.chunk_key, pool_cap, 0xFFFFFFFFu);      // never opened
     if (stage("init")) return 1;
     // ---- K0  (the two launches one after the other: both are bound by instruction issue, side by side on two streams they take
     // exactly as long — measured, profiles/r03_k0side_ab.sh)
     if (decode) {
         K0Params q{};
         q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.perm = nullptr; q.P = P; q.short_ids = db->short_max_ids; q.bm = bm;
-        q.p0_mask = db->p0_mask; q.p0_info = db->p0_info; q.pair_ofs = db->pair_ofs; q.pair_blk = db->pair_blk; q.pair_mask = db->pair_mask;
+        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
         // sub-pools of the pair pool: enough of them that their cursors are not hot, few enough that one wave's need fits a share
         uint32_t nreg = 1;
         while (nreg < KMDB_PAIR_REGIONS && (uint64_t)nreg * 16384 < P) nreg <<= 1;
         // three quarters of the pool in sub-pools, the rest shared
-        q.pair_cursor = db->pair_cursor; q.n_regions = nreg; q.region_cap = (uint32_t)(db->pair_cap * 3 / 4 / nreg);
-        q.spill_cap = (uint32_t)(db->pair_cap - (uint64_t)q.region_cap * nreg); q.counters = db->counters;
+        q.pair_cursor = b.pair_cursor; q.n_regions = nreg; q.region_cap = (uint32_t)(b.pair_cap * 3 / 4 / nreg);
+        q.spill_cap = (uint32_t)(b.pair_cap - (uint64_t)q.region_cap * nreg); q.counters = b.counters;
         hipLaunchKernelGGL((k0_decode_kernel<false>), dim3((P + 255) / 256), dim3(256), 0, st, q);
         if (db->n_long) {
             q.perm = db->long_nodes; q.P = db->n_long;
@@ -3419,27 +3537,27 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     {
         NParams q{};
         q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.dflag = db->dflag; q.seg_anc = db->nseg_anc; q.seg_anc_n = db->nseg_anc_n;
-        q.p0_mask = db->p0_mask; q.p0_info = db->p0_info; q.pair_ofs = db->pair_ofs; q.pair_blk = db->pair_blk; q.pair_mask = db->pair_mask;
-        q.fn_mask = db->fn_mask; q.fn_blk = db->fn_blk; q.widebits = db->widebits;
+        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
+        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits;
         q.P = P; q.nseg_nodes = db->nseg_nodes; q.n_segs = db->n_nsegs; q.chain_cap = db->chain_cap;
-        q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = db->dense_narrow ? 0u : arena_table_bits(db->NB); q.n_keys = db->NB;
-        q.all_wide = db->dense_narrow ? 1u : 0u;
-        q.pool = pool_view(db, db->dense_narrow);
+        q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.NB); q.n_keys = b.NB;
+        q.all_wide = b.dense_narrow ? 1u : 0u;
+        q.pool = pool_view(b, b.dense_narrow);
         // a wave's chain table grows with the depth of the tree: as many waves per workgroup as 144 KB of LDS hold
-        const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, row_mode ? db->NB : 0u);
+        const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, row_mode ? b.NB : 0u);
         const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(K1N_WAVES, (144u << 10) / wave_lds));
         const size_t lds = wave_lds * waves;
         q.dbg = getenv("KMDB_K1N_DBG") ? (uint32_t)atoi(getenv("KMDB_K1N_DBG")) : 0u;
-        q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = db->tile_touched; q.direct_ctr = db->direct_ctr;
-        q.dmask = db->dmask; q.dwx = db->dwx; q.slice_cnt = db->slice_cnt;
+        q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = b.tile_touched; q.direct_ctr = b.direct_ctr;
+        q.dmask = b.dmask; q.dwx = b.dwx; q.slice_cnt = b.slice_cnt;
         // (mode 1 holds 48 accumulator registers beside the narrow kernel's 95: three waves per SIMD without spills, or four with 84 bytes of
         // scratch per lane — KMDB_K1N_MINW=4, A/B)
         static const int minw = getenv("KMDB_K1N_MINW") ? atoi(getenv("KMDB_K1N_MINW")) : 3;
         // the instantiation of the call's record path: the attribute and the launch take the same function
-        const K1nPick pick = k1n_pick(db->k1n_mode, minw, row_mode);
+        const K1nPick pick = k1n_pick(b.k1n_mode, minw, row_mode);
         HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const dim3 grid((q.n_segs + waves - 1) / waves), block(WAVE * waves);
-        if (!db->have_counts && getenv("KMDB_VERBOSE"))
+        if (!b.have_counts && getenv("KMDB_VERBOSE"))
             fprintf(stderr, "[kmdb] narrow kernel: %u slices, %zu B of LDS per wave, %u per workgroup, instantiation %s\n", q.n_segs, wave_lds, waves, pick.name);
         hipLaunchKernelGGL(pick.fn, grid, block, lds, st, q);
         HIP_TRY(hipGetLastError());
@@ -3451,23 +3569,23 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     // next to the wide kernel (which writes no chunks).  Many streams: after the wide kernel (it writes the row chunks), next to
     // the sort inside the rows.
     auto group_and_apply_chunks = [&](hipStream_t cs) -> int {
-        hipLaunchKernelGGL(ct_hist_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, db->chunk_key, pool_cap, n_ckeys, db->ct_hist);
-        size_t tb = db->ct_tmp_bytes;
-        HIP_TRY(prim::exclusive_sum(db->ct_tmp, tb, db->ct_hist, db->ct_offs, (int)(n_ckeys + 1), cs));
-        HIP_TRY(hipMemcpyAsync(db->ct_cursor, db->ct_offs, ((size_t)n_ckeys + 1) * 4, hipMemcpyDeviceToDevice, cs));
-        hipLaunchKernelGGL(ct_scatter_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, db->chunk_key, pool_cap, n_ckeys, db->ct_cursor, db->sorted_key, db->sorted_id);
-        hipLaunchKernelGGL(ct_count_kernel, dim3(1), dim3(1), 0, cs, db->ct_offs, db->n_states, db->counters);
+        hipLaunchKernelGGL(ct_hist_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_hist);
+        size_t tb = b.ct_tmp_bytes;
+        HIP_TRY(prim::exclusive_sum(b.ct_tmp, tb, b.ct_hist.get(), b.ct_offs.get(), (int)(n_ckeys + 1), cs));
+        HIP_TRY(hipMemcpyAsync(b.ct_cursor, b.ct_offs, ((size_t)n_ckeys + 1) * 4, hipMemcpyDeviceToDevice, cs));
+        hipLaunchKernelGGL(ct_scatter_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_cursor, b.sorted_key, b.sorted_id);
+        hipLaunchKernelGGL(ct_count_kernel, dim3(1), dim3(1), 0, cs, b.ct_offs, b.n_states, b.counters);
         if (cs != s2) { HIP_TRY(hipEventRecord(db->ev_side[0], cs)); HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0)); }
         {
-            rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(db->chunk_fill, U32toU64());
-            HIP_TRY(prim::sum(db->sort_tmp, db->sort_tmp_bytes, it, (unsigned long long*)(db->counters + KCTR_RECORDS), (int)pool_cap, s2));
+            rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(b.chunk_fill, U32toU64());
+            HIP_TRY(prim::sum(b.sort_tmp, b.sort_tmp_bytes, it, (unsigned long long*)(b.counters + KCTR_RECORDS), (int)pool_cap, s2));
         }
-        const uint32_t win = db->n_states <= CS_MAX_KEYS ? 16u : 32u;      // (8 / 32 / 64 chunks at few streams: within the boxes' noise, profiles/r05_j5)
+        const uint32_t win = b.n_states <= CS_MAX_KEYS ? 16u : 32u;      // (8 / 32 / 64 chunks at few streams: within the boxes' noise, profiles/r05_j5)
         uint32_t grid = (pool_cap + win - 1) / win;
-        if (db->have_counts) grid = std::min(grid, (db->last_n_chunks + win - 1) / win);
+        if (b.have_counts) grid = std::min(grid, (b.last_n_chunks + win - 1) / win);
         if (grid)
-            hipLaunchKernelGGL(k2_apply_kernel, dim3(grid), dim3(256), 0, s2, db->rec, db->recw, db->sorted_key, db->sorted_id, db->chunk_fill, db->n_states,
-                               db->ct_offs + db->n_states, M, (uint32_t)db->N, db->width, win, db->tile_touched);
+            hipLaunchKernelGGL(k2_apply_kernel, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
+                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(db->ev_side[1], s2));
         if (sync_debug) { const hipError_t e = hipStreamSynchronize(s2); fprintf(stderr, "[kmdb] stage %-14s %s\n", "chunk apply", e == hipSuccess ? "ok" : hipGetErrorString(e)); }
@@ -3478,9 +3596,9 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         HIP_TRY(hipEventRecord(db->ev_side[0], st));
         HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
         DParams d{};
-        d.dmask = db->dmask; d.dwx = db->dwx; d.slice_cnt = db->slice_cnt; d.n_segs = db->n_nsegs; d.nseg_nodes = db->nseg_nodes;
+        d.dmask = b.dmask; d.dwx = b.dwx; d.slice_cnt = b.slice_cnt; d.n_segs = db->n_nsegs; d.nseg_nodes = db->nseg_nodes;
         static const uint32_t sl = getenv("KMDB_K2D_SLICES") ? (uint32_t)std::max(1, atoi(getenv("KMDB_K2D_SLICES"))) : K2D_SLICES;
-        d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = db->tile_touched;
+        d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = b.tile_touched;
         const uint32_t waves = (db->n_nsegs + sl - 1u) / sl;
         if (waves) hipLaunchKernelGGL(k2d_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d);
         HIP_TRY(hipGetLastError());
@@ -3492,309 +3610,310 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     // which then take 0.28 ms at C2 instead of their own 0.05.  KMDB_K2D_EARLY=0 starts it with the wide kernel: the wide stage gains 0.1 ms, the
     // sort beside which the kernel then ends loses them — profiles/r06_j13: 6.70 / 6.98 against 6.86 / 6.93 ms at C2, 18.45 against 19.11 at 10 000 samples)
     static const bool k2d_early = !(getenv("KMDB_K2D_EARLY") && getenv("KMDB_K2D_EARLY")[0] == '0');
-    if (db->k1n_mode == 2 && k2d_early && apply_slices()) return 1;
+    if (b.k1n_mode == 2 && k2d_early && apply_slices()) return 1;
     if (!row_mode) {
-        if (!db->dense_narrow) {
+        if (!b.dense_narrow) {
             HIP_TRY(hipEventRecord(db->ev_side[0], st));
             HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
             if (group_and_apply_chunks(s2)) return 1;
         } else HIP_TRY(hipEventRecord(db->ev_side[1], s2));        // (no stream chunk is ever opened: nothing to group; the side stream holds the slices' apply kernel or nothing)
     }
     // ---- wide list
-    hipLaunchKernelGGL(wide_count_kernel, dim3((n_words + 1 + 255) / 256), dim3(256), 0, st, db->widebits, n_words, db->wide_cnt);
-    HIP_TRY(prim::exclusive_sum(db->scan_tmp, db->scan_tmp_bytes, db->wide_cnt, db->wide_base, (int)(n_words + 1), st));
+    hipLaunchKernelGGL(wide_count_kernel, dim3((n_words + 1 + 255) / 256), dim3(256), 0, st, b.widebits, n_words, b.wide_cnt);
+    HIP_TRY(prim::exclusive_sum(b.scan_tmp, b.scan_tmp_bytes, b.wide_cnt.get(), b.wide_base.get(), (int)(n_words + 1), st));
     uint32_t n_wide;
-    if (db->have_counts && db->wide_cap >= db->last_n_wide) n_wide = db->last_n_wide;     // deterministic per database; checked at the end of the call
+    if (b.have_counts && b.wide_cap >= b.last_n_wide) n_wide = b.last_n_wide;     // deterministic per database; checked at the end of the call
     else {
-        HIP_TRY(hipMemcpyAsync(db->h_counters, db->wide_base + n_words, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(b.h_counters, b.wide_base + n_words, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        n_wide = db->h_counters[0];
-        if (n_wide > db->wide_cap) {
-            FREE_NULL(db->widx); FREE_NULL(db->wrun_anc); FREE_NULL(db->wrun_anc_n);
-            HIP_TRY(hipMalloc((void**)&db->widx, (size_t)n_wide * 4));
-            HIP_TRY(hipMalloc((void**)&db->wrun_anc, ((size_t)n_wide / 64 + 1) * db->chain_cap * 4));
-            HIP_TRY(hipMalloc((void**)&db->wrun_anc_n, ((size_t)n_wide / 64 + 1) * 4));
-            db->wide_cap = n_wide;
+        n_wide = b.h_counters[0];
+        if (n_wide > b.wide_cap) {
+            dev_reset(b.widx, b.wrun_anc, b.wrun_anc_n);
+            b.wide_cap = 0;
+            DEV_ALLOC(b.widx, (size_t)n_wide);
+            DEV_ALLOC(b.wrun_anc, ((size_t)n_wide / 64 + 1) * db->chain_cap);
+            DEV_ALLOC(b.wrun_anc_n, (size_t)n_wide / 64 + 1);
+            b.wide_cap = n_wide;
         }
     }
-    if (!db->widx) { HIP_TRY(hipMalloc((void**)&db->widx, 4)); db->wide_cap = std::max<uint64_t>(db->wide_cap, 1); }
-    hipLaunchKernelGGL(wide_expand_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, db->widebits, db->wide_base, n_words, db->widx,
-                       (uint32_t)db->wide_cap, db->counters);
-    if (db->k1n_mode == 2 && !k2d_early && apply_slices()) return 1;
+    if (!b.widx) { DEV_ALLOC(b.widx, 1); b.wide_cap = std::max<uint64_t>(b.wide_cap, 1); }
+    hipLaunchKernelGGL(wide_expand_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, b.widebits, b.wide_base, n_words, b.widx,
+                       (uint32_t)b.wide_cap, b.counters);
+    if (b.k1n_mode == 2 && !k2d_early && apply_slices()) return 1;
     // ---- K1w
     if (n_wide) {
         WParams q{};
-        q.widx = db->widx; q.n_wide = n_wide; q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.widebits = db->widebits;
-        q.dflag = db->dflag; q.wide_base = db->wide_base;
-        q.p0_mask = db->p0_mask; q.p0_info = db->p0_info; q.pair_ofs = db->pair_ofs; q.pair_blk = db->pair_blk; q.pair_mask = db->pair_mask;
-        q.fn_mask = db->fn_mask; q.fn_blk = db->fn_blk; q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.pool = pool_view(db, db->dense_wide);
+        q.widx = b.widx; q.n_wide = n_wide; q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.widebits = b.widebits;
+        q.dflag = db->dflag; q.wide_base = b.wide_base;
+        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
+        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.pool = pool_view(b, b.dense_wide);
             // ---- second level: many streams, few enough blocks that a tile job's bitmap scan stays small (tiles x nodes: quadratic in the
         // blocks), KMDB_L2=0 switches it off, KMDB_L2_MIN=c moves the threshold
         {
             const char* l2_env = getenv("KMDB_L2");
             const char* l2_min_env = getenv("KMDB_L2_MIN");
-            db->l2_on = row_mode && db->NB <= 256u && !(l2_env && l2_env[0] == '0');
-            db->l2_min_blocks = l2_min_env ? std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(l2_min_env)) : L2_MIN_BLOCKS;
-            if (db->l2_on && !db->l2_bitmap) {
+            b.l2_on = row_mode && b.NB <= 256u && !(l2_env && l2_env[0] == '0');
+            b.l2_min_blocks = l2_min_env ? std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(l2_min_env)) : L2_MIN_BLOCKS;
+            if (b.l2_on && !b.l2_bitmap) {
                 // a first guess from the wide list (at 10 000 samples 2 % of the wide nodes have 24 blocks or more); a call that runs out doubles both
                 // (KMDB_POOL_PERCENT, tests: the smallest arrays there are, so that the doubling path runs)
                 const bool tiny = getenv("KMDB_POOL_PERCENT") != nullptr;
-                if (alloc_l2(db, tiny ? 1u : std::max<uint32_t>(64u * L2_SUB * 4u, n_wide / 16u), tiny ? 1u : std::max<uint32_t>(L2_ENT_GRAB * L2_SUB * 4u, n_wide / 16u * 48u))) return 1;
+                if (alloc_l2(b, tiny ? 1u : std::max<uint32_t>(64u * L2_SUB * 4u, n_wide / 16u), tiny ? 1u : std::max<uint32_t>(L2_ENT_GRAB * L2_SUB * 4u, n_wide / 16u * 48u))) return 1;
             }
             q.l2 = L2View{};
-            if (db->l2_on) {
-                q.l2.on = 1u; q.l2.min_blocks = db->l2_min_blocks; q.l2.node_cap = db->l2_node_cap; q.l2.W = db->l2_node_cap / 64u; q.l2.ent_cap = db->l2_ent_cap;
-                q.l2.cursors = db->l2_cursors; q.l2.bitmap = db->l2_bitmap; q.l2.ent_g = db->l2_ent_g; q.l2.ent_blk = db->l2_ent_blk; q.l2.ent_mask = db->l2_ent_mask;
-                q.l2.node_w = db->l2_node_w;
-                HIP_TRY(hipMemsetAsync(db->l2_cursors, 0, 2 * L2_SUB * 16 * 4, st));
-                HIP_TRY(hipMemsetAsync(db->l2_bitmap, 0, (size_t)db->NB * q.l2.W * 8, st));
-                HIP_TRY(hipMemsetAsync(db->l2_ent_blk, 0xFF, (size_t)db->l2_ent_cap * 2, st));
+            if (b.l2_on) {
+                q.l2.on = 1u; q.l2.min_blocks = b.l2_min_blocks; q.l2.node_cap = b.l2_node_cap; q.l2.W = b.l2_node_cap / 64u; q.l2.ent_cap = b.l2_ent_cap;
+                q.l2.cursors = b.l2_cursors; q.l2.bitmap = b.l2_bitmap; q.l2.ent_g = b.l2_ent_g; q.l2.ent_blk = b.l2_ent_blk; q.l2.ent_mask = b.l2_ent_mask;
+                q.l2.node_w = b.l2_node_w;
+                HIP_TRY(hipMemsetAsync(b.l2_cursors, 0, 2 * L2_SUB * 16 * 4, st));
+                HIP_TRY(hipMemsetAsync(b.l2_bitmap, 0, (size_t)b.NB * q.l2.W * 8, st));
+                HIP_TRY(hipMemsetAsync(b.l2_ent_blk, 0xFF, (size_t)b.l2_ent_cap * 2, st));
             }
         }
         q.run_nodes = K1W_RUN_NODES;
         if (const char* e = getenv("KMDB_K1W_RUN")) q.run_nodes = std::max<uint32_t>(64u, (uint32_t)atoi(e) / 64u * 64u);
         q.n_runs = (n_wide + q.run_nodes - 1) / q.run_nodes;
         // root paths of the runs' first nodes (the table is sized with the wide list, for runs of 64 nodes at least)
-        hipLaunchKernelGGL(wrun_anc_kernel, dim3((q.n_runs + 63) / 64), dim3(64), 0, st, db->widx, n_wide, q.run_nodes, db->parent, db->dflag, db->chain_cap,
-                           db->wrun_anc, db->wrun_anc_n);
-        q.seg_anc = db->wrun_anc; q.seg_anc_n = db->wrun_anc_n;
+        hipLaunchKernelGGL(wrun_anc_kernel, dim3((q.n_runs + 63) / 64), dim3(64), 0, st, b.widx, n_wide, q.run_nodes, db->parent, db->dflag, db->chain_cap,
+                           b.wrun_anc, b.wrun_anc_n);
+        q.seg_anc = b.wrun_anc; q.seg_anc_n = b.wrun_anc_n;
         
         // LDS of a wave: rows of a batch (at least one full list: as many entries as there are blocks), the chain list, the chain
-        q.chain_cap = db->chain_cap; q.e_cap = (db->NB + 2u + 3u) & ~3u; q.arena_cap = std::max<uint32_t>(K1W_ARENA_MIN, (db->NB + 2u + 63u) & ~63u);
-        q.n_rows = row_mode ? db->NB : 0u;
+        q.chain_cap = db->chain_cap; q.e_cap = (b.NB + 2u + 3u) & ~3u; q.arena_cap = std::max<uint32_t>(K1W_ARENA_MIN, (b.NB + 2u + 63u) & ~63u);
+        q.n_rows = row_mode ? b.NB : 0u;
         const size_t wave_lds = k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows);
         const uint32_t waves = wave_lds * K1W_WAVES <= (size_t)(64u << 10) ? (uint32_t)K1W_WAVES : 1u;
         // the instantiation of the call's record path: the attribute, the occupancy query and the launch take the same function
-        const K1wPick pick = k1w_pick(row_mode, db->l2_on);
+        const K1wPick pick = k1w_pick(row_mode, b.l2_on);
         HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
         // As many waves as the chip holds at once, each with an equal share of the runs (dealt round-robin): with more, the waves
         // beyond the first round start when the first ones end, and all take equally long — 1.6 rounds cost 2 (measured at 10 000
         // samples: 4096 waves at 10 per CU took 8.8 ms, of which every wave ran 4.4).
         // (the count is kept on the handle with the instantiation it was asked for: KMDB_L2 may change between the calls of a handle)
-        if (!db->k1w_slots || db->k1w_slots_fn != (const void*)pick.fn) {
+        if (!b.k1w_slots || b.k1w_slots_fn != (const void*)pick.fn) {
             int per_cu = 0, dev = 0;
             hipDeviceProp_t prop;
-            db->k1w_slots = 0; db->k1w_slots_fn = (const void*)pick.fn;
+            b.k1w_slots = 0; b.k1w_slots_fn = (const void*)pick.fn;
             HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pick.fn, (int)(WAVE * waves), wave_lds * waves));
             HIP_TRY(hipGetDevice(&dev));
             HIP_TRY(hipGetDeviceProperties(&prop, dev));
-            db->k1w_slots = (uint32_t)std::max(1, per_cu) * waves * (uint32_t)std::max(1, prop.multiProcessorCount);
+            b.k1w_slots = (uint32_t)std::max(1, per_cu) * waves * (uint32_t)std::max(1, prop.multiProcessorCount);
         }
-        q.n_waves = std::min<uint32_t>(std::min<uint32_t>(db->k1w_slots, db->k1w_waves), q.n_runs);
-        q.run_ctr = db->run_ctr;
-        if (const char* e = getenv("KMDB_K1W_WAVES")) q.n_waves = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(db->k1w_waves, q.n_runs), (uint32_t)atoi(e)));
-        if (!db->have_counts && getenv("KMDB_VERBOSE"))
+        q.n_waves = std::min<uint32_t>(std::min<uint32_t>(b.k1w_slots, b.k1w_waves), q.n_runs);
+        q.run_ctr = b.run_ctr;
+        if (const char* e = getenv("KMDB_K1W_WAVES")) q.n_waves = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(b.k1w_waves, q.n_runs), (uint32_t)atoi(e)));
+        if (!b.have_counts && getenv("KMDB_VERBOSE"))
             fprintf(stderr, "[kmdb] wide kernel: %u wide nodes in %u runs, %u waves (%u fit the chip, %zu B of LDS per wave, %u per workgroup), instantiation %s\n", n_wide,
-                    q.n_runs, q.n_waves, db->k1w_slots, wave_lds, waves, pick.name);
+                    q.n_runs, q.n_waves, b.k1w_slots, wave_lds, waves, pick.name);
         hipLaunchKernelGGL(pick.fn, dim3((q.n_waves + waves - 1) / waves), dim3(WAVE * waves), wave_lds * waves, st, q);
-        if (db->l2_on) {
+        if (b.l2_on) {
             // rank directories, list offsets, lists, and the tile joins adding into M (a tile whose blocks have no list leaves at once)
-            const uint32_t NB = db->NB, W = db->l2_node_cap / 64u;
-            hipLaunchKernelGGL(l2_ranks_kernel, dim3(NB), dim3(256), 0, st, db->l2_bitmap, W, db->l2_rank, db->l2_len);
-            hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, db->l2_len, NB, db->l2_cursors, W, db->l2_loff);
-            hipLaunchKernelGGL(l2_lists_kernel, dim3((db->l2_ent_cap + 255u) / 256u), dim3(256), 0, st, db->l2_ent_g, db->l2_ent_blk, db->l2_ent_mask, db->l2_node_w,
-                               db->l2_ent_cap, W, db->l2_bitmap, db->l2_rank, db->l2_loff, db->l2_list_mask, db->l2_list_w, db->l2_cursors);
-            hipLaunchKernelGGL(l2_join_apply_kernel, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, db->l2_bitmap, db->l2_rank, db->l2_list_mask, db->l2_list_w,
-                               db->l2_loff, W, NB, M, (uint32_t)db->N, db->width, db->tile_touched);
+            const uint32_t NB = b.NB, W = b.l2_node_cap / 64u;
+            hipLaunchKernelGGL(l2_ranks_kernel, dim3(NB), dim3(256), 0, st, b.l2_bitmap, W, b.l2_rank, b.l2_len);
+            hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, b.l2_len, NB, b.l2_cursors, W, b.l2_loff);
+            hipLaunchKernelGGL(l2_lists_kernel, dim3((b.l2_ent_cap + 255u) / 256u), dim3(256), 0, st, b.l2_ent_g, b.l2_ent_blk, b.l2_ent_mask, b.l2_node_w,
+                               b.l2_ent_cap, W, b.l2_bitmap, b.l2_rank, b.l2_loff, b.l2_list_mask, b.l2_list_w, b.l2_cursors);
+            hipLaunchKernelGGL(l2_join_apply_kernel, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
+                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched);
         }
     }
     HIP_TRY(hipGetLastError());
     if (stage("wide emit")) return 1;
     HIP_TRY(hipEventRecord(db->ev_k[2], st));
-    const uint32_t kmask = (1u << db->key_bits) - 1u;
+    const uint32_t kmask = (1u << b.key_bits) - 1u;
     uint32_t jobs_launched = 0, k2jobs_launched = 0;
     if (row_mode) {
         // ---- many streams: chunk table grouped (stream chunks -> side stream), then the sort inside the block rows and its apply
         if (group_and_apply_chunks(st)) return 1;
-        const uint32_t NB = db->NB;
-        uint32_t* row_job = db->rs_rows, *row_tab = db->rs_rows + (NB + 1);
+        const uint32_t NB = b.NB;
+        uint32_t* row_job = b.rs_rows, *row_tab = b.rs_rows + (NB + 1);
         {
             // the row chunks grouped by row
-            const size_t rg_ne = (size_t)NB * db->rg_blocks + 1;
-            hipLaunchKernelGGL(rg_hist_kernel, dim3(db->rg_blocks), dim3(RG_THREADS), NB * 4, st, db->chunk_key, pool_cap, db->n_states, NB, db->rg_hist);
-            size_t tbg = db->rg_tmp_bytes;
-            HIP_TRY(prim::exclusive_sum(db->rg_tmp, tbg, db->rg_hist, db->rg_offs, (int)rg_ne, st));
-            hipLaunchKernelGGL(rg_scatter_kernel, dim3(db->rg_blocks), dim3(RG_THREADS), NB * 4, st, db->chunk_key, pool_cap, db->n_states, NB, db->rg_offs, db->row_ids);
+            const size_t rg_ne = (size_t)NB * b.rg_blocks + 1;
+            hipLaunchKernelGGL(rg_hist_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_hist);
+            size_t tbg = b.rg_tmp_bytes;
+            HIP_TRY(prim::exclusive_sum(b.rg_tmp, tbg, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
+            hipLaunchKernelGGL(rg_scatter_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_offs, b.row_ids);
         }
-        hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, db->rg_offs, db->rg_blocks, NB, row_job, row_tab, db->counters);
-        const RsRows R{db->rg_offs, db->row_ids, db->rg_blocks, NB, row_job, row_tab};
+        hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters);
+        const RsRows R{b.rg_offs, b.row_ids, b.rg_blocks, NB, row_job, row_tab};
         // jobs and table entries: measured by the previous call, else their upper bounds (workgroups beyond the last job leave at once)
         const uint32_t jobs_bound = (uint32_t)(pool_cap / RS_JOB_CHUNKS + NB + 1);
-        const uint32_t jobs = db->have_counts ? std::min<uint32_t>(jobs_bound, with_slack(db->last_n_rowjobs)) : jobs_bound;
+        const uint32_t jobs = b.have_counts ? std::min<uint32_t>(jobs_bound, with_slack(b.last_n_rowjobs)) : jobs_bound;
         jobs_launched = jobs;
-        const size_t ne = std::min<size_t>(db->rs_entries, (size_t)jobs * NB + 1);
-        HIP_TRY(hipMemsetAsync(db->rs_hist, 0, ne * 4, st));
+        const size_t ne = std::min<size_t>(b.rs_entries, (size_t)jobs * NB + 1);
+        HIP_TRY(hipMemsetAsync(b.rs_hist, 0, ne * 4, st));
         {
             // (4, round 4's, against 8 / 16 at 10 000 samples: apply step 6.08 / 5.88 / 5.85 ms, profiles/r05_j14 — the kernel waits for its loads)
             const char* ue = getenv("KMDB_RSH_UNROLL");
             const int u = ue ? atoi(ue) : 16;
-            if (u == 16) hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), NB * 4, st, R, db->chunk_fill, db->recw, kmask, db->rs_hist);
-            else if (u == 8) hipLaunchKernelGGL(rs_hist_kernel<8>, dim3(jobs), dim3(256), NB * 4, st, R, db->chunk_fill, db->recw, kmask, db->rs_hist);
-            else hipLaunchKernelGGL(rs_hist_kernel<4>, dim3(jobs), dim3(256), NB * 4, st, R, db->chunk_fill, db->recw, kmask, db->rs_hist);
+            if (u == 16) hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
+            else if (u == 8) hipLaunchKernelGGL(rs_hist_kernel<8>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
+            else hipLaunchKernelGGL(rs_hist_kernel<4>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
         }
-        size_t tb = db->rs_tmp_bytes;
-        HIP_TRY(prim::exclusive_sum(db->rs_tmp, tb, db->rs_hist, db->rs_offs, (int)ne, st));
-        const uint32_t* total_ptr = db->rs_offs + (ne - 1);
-        HIP_TRY(hipMemcpyAsync(db->counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
+        size_t tb = b.rs_tmp_bytes;
+        HIP_TRY(prim::exclusive_sum(b.rs_tmp, tb, b.rs_hist.get(), b.rs_offs.get(), (int)ne, st));
+        const uint32_t* total_ptr = b.rs_offs + (ne - 1);
+        HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
         // (Sorting and applying bands of block rows side by side on two streams was measured at 10 000 samples: 2 / 4 / 8 bands 18.4 / 17.0 /
         // 18.7 ms against 16.5 for one — the two kernels do not complement each other.)
-        HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(NB, db->rec_pshift != 0)));
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(NB, db->rec_pshift != 0), st, R, db->chunk_fill, db->recw, (const WideRec*)db->rec, kmask,
-                           db->rs_offs, (uint32_t)db->sorted_cap, db->swkey, (WideRec*)db->swrec, db->counters, db->rec_pshift ? 1u : 0u);
+        HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(NB, b.rec_pshift != 0)));
+        hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(NB, b.rec_pshift != 0), st, R, b.chunk_fill, b.recw, (const WideRec*)b.rec.get(), kmask,
+                           b.rs_offs, (uint32_t)b.sorted_cap, b.swkey, (WideRec*)b.swrec, b.counters, b.rec_pshift ? 1u : 0u);
         // the sorted records applied stream by stream (a long stream in parts of K2J_REC records): one write-back of a tile per job
-        hipLaunchKernelGGL(k2j_starts_kernel, dim3((db->n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, db->rs_offs, db->n_states, db->k2j_start);
-        hipLaunchKernelGGL(k2j_build_kernel, dim3((db->n_states + 1023u) / 1024u), dim3(1024), 0, st, db->k2j_start, db->n_states, db->k2j_jobs, (uint32_t)db->k2j_cap, db->counters);
-        k2jobs_launched = db->have_counts ? db->last_n_k2jobs : (uint32_t)db->k2j_cap;       // (the streams' lengths repeat exactly from call to call)
+        hipLaunchKernelGGL(k2j_starts_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
+        hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
+        k2jobs_launched = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;       // (the streams' lengths repeat exactly from call to call)
         if (k2jobs_launched)
-            hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, db->swkey, (const WideRec*)db->swrec, db->k2j_start, db->k2j_jobs, db->counters + KCTR_K2JOBS,
-                               (uint32_t)db->k2j_cap, (uint32_t)db->sorted_cap, db->rec_pshift, (uint32_t)db->key_bits, wide_digit_bits(db->key_bits), M, (uint32_t)db->N, db->width, db->tile_touched);
+            hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
+                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
         HIP_TRY(hipGetLastError());
         if (stage("row sort+apply")) return 1;
     } else {
-        hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(1), 0, st, db->wsub_cursor, db->counters);
+        hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(1), 0, st, b.wsub_cursor, b.counters);
         // the wide pool: records sorted by stream (the sort moves the 16-byte records with their key words), one tile per run
         uint32_t n_raw;
-        if (db->have_counts) n_raw = raw_launch;
+        if (b.have_counts) n_raw = raw_launch;
         else {
-            HIP_TRY(hipMemcpyAsync(db->h_counters, db->counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            n_raw = std::min<uint32_t>(db->h_counters[KCTR_RAW], (uint32_t)db->wide_pool_cap);
+            n_raw = std::min<uint32_t>(b.h_counters[KCTR_RAW], (uint32_t)b.wide_pool_cap);
         }
         if (n_raw) {
             const uint32_t nslots = (uint32_t)((uint64_t)n_raw << WCH_SHIFT);
             const CsRows no_rows{};
-            const size_t ne = (size_t)db->n_states * CS_BLOCKS_ONE + 1;
-            hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), db->n_states * 4, st, db->wkey, nslots, db->n_states, db->n_states, (int)CS_BY_STREAM,
-                               no_rows, kmask, db->cs_hist);
-            size_t tb = db->cs_tmp_bytes;
-            HIP_TRY(prim::exclusive_sum(db->cs_tmp, tb, db->cs_hist, db->cs_offs, (int)ne, st));
-            const bool packed = db->rec_pshift != 0;
-            HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(db->n_states, packed)));
-            hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(db->n_states, packed), st, db->wkey, (const WideRec*)db->wrec, nslots,
-                               db->n_states, db->n_states, (int)CS_BY_STREAM, no_rows, kmask, db->cs_offs, db->swkey, (WideRec*)db->swrec, packed ? 1u : 0u);
-            const uint32_t* total_ptr = db->cs_offs + (ne - 1);
-            HIP_TRY(hipMemcpyAsync(db->counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
+            const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
+            hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), b.n_states * 4, st, b.wkey, nslots, b.n_states, b.n_states, (int)CS_BY_STREAM,
+                               no_rows, kmask, b.cs_hist);
+            size_t tb = b.cs_tmp_bytes;
+            HIP_TRY(prim::exclusive_sum(b.cs_tmp, tb, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
+            const bool packed = b.rec_pshift != 0;
+            HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(b.n_states, packed)));
+            hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(b.n_states, packed), st, b.wkey, (const WideRec*)b.wrec, nslots,
+                               b.n_states, b.n_states, (int)CS_BY_STREAM, no_rows, kmask, b.cs_offs, b.swkey, (WideRec*)b.swrec, packed ? 1u : 0u);
+            const uint32_t* total_ptr = b.cs_offs + (ne - 1);
+            HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
             if (getenv("KMDB_K2_WINDOWS") && !packed) {
                 // (A/B: round 4's apply step over windows of 4096 sorted positions, run boundaries searched in the key words)
                 const uint32_t g2 = (nslots + K2S_WIN - 1) / K2S_WIN;
-                hipLaunchKernelGGL(k2_sorted_kernel, dim3(g2), dim3(256), 0, st, db->swkey, (const WideRec*)db->swrec, nslots, total_ptr, (const uint32_t*)nullptr,
-                                   db->n_states, (uint32_t)db->key_bits, wide_digit_bits(db->key_bits), M, (uint32_t)db->N, db->width, 0u, 0u, db->tile_touched);
+                hipLaunchKernelGGL(k2_sorted_kernel, dim3(g2), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, nslots, total_ptr, (const uint32_t*)nullptr,
+                                   b.n_states, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, 0u, 0u, b.tile_touched);
             } else {
                 // the sorted records applied stream by stream, as on the many-streams path: the streams start where the sort's offsets say (no run
                 // boundaries searched, no key word read for packed records), a tile is written back once per K2J_REC records of its stream
-                hipLaunchKernelGGL(k2j_starts_flat_kernel, dim3((db->n_states + 1u + 255u) / 256u), dim3(256), 0, st, db->cs_offs, db->n_states, CS_BLOCKS_ONE, db->k2j_start);
-                hipLaunchKernelGGL(k2j_build_kernel, dim3((db->n_states + 1023u) / 1024u), dim3(1024), 0, st, db->k2j_start, db->n_states, db->k2j_jobs, (uint32_t)db->k2j_cap, db->counters);
-                k2jobs_launched = db->have_counts ? db->last_n_k2jobs : (uint32_t)db->k2j_cap;
+                hipLaunchKernelGGL(k2j_starts_flat_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, b.cs_offs, b.n_states, CS_BLOCKS_ONE, b.k2j_start);
+                hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
+                k2jobs_launched = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;
                 if (k2jobs_launched)
-                    hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, db->swkey, (const WideRec*)db->swrec, db->k2j_start, db->k2j_jobs, db->counters + KCTR_K2JOBS,
-                                       (uint32_t)db->k2j_cap, (uint32_t)db->sorted_cap, db->rec_pshift, (uint32_t)db->key_bits, wide_digit_bits(db->key_bits), M, (uint32_t)db->N, db->width, db->tile_touched);
+                    hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
+                                       (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
             }
             HIP_TRY(hipGetLastError());
         }
         if (stage("sorted apply")) return 1;
     }
     HIP_TRY(hipStreamWaitEvent(st, db->ev_side[1], 0));          // the side stream's tiles are in the matrix too
-    hipLaunchKernelGGL(pool_used_kernel, dim3(1), dim3(64), 0, st, db->sub_cursor, db->direct_ctr, db->counters);
+    hipLaunchKernelGGL(pool_used_kernel, dim3(1), dim3(64), 0, st, b.sub_cursor, b.direct_ctr, b.counters);
     HIP_TRY(hipEventRecord(db->ev_k[3], st));
     // ---- what the call found
-    HIP_TRY(hipMemcpyAsync(db->h_counters, db->counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t* c = db->h_counters;
+    const uint32_t* c = b.h_counters;
     if (c[KCTR_LIST_OVERFLOW] || c[KCTR_SLOW]) {
         db->fallback_reason = "internal: the wide-node kernel lost a list (chain miss " + std::to_string(c[KCTR_SLOW]) + ", arena overflow " + std::to_string(c[KCTR_LIST_OVERFLOW]) + ")";
         return 0;
     }
     if (c[KCTR_L2_OVERFLOW]) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] second level out of node indices or entries (%u / %u): doubling\n", db->l2_node_cap, db->l2_ent_cap);
-        if (alloc_l2(db, db->l2_node_cap * 2u, db->l2_ent_cap * 2u)) return 1;
-        db->have_counts = false; *retry = true;
+        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] second level out of node indices or entries (%u / %u): doubling\n", b.l2_node_cap, b.l2_ent_cap);
+        if (alloc_l2(b, b.l2_node_cap * 2u, b.l2_ent_cap * 2u)) return 1;
+        b.have_counts = false; *retry = true;
         return 0;
     }
     if (c[KCTR_PAIR_OVERFLOW] || c[KCTR_POOL_OVERFLOW] || c[KCTR_WIDE_OVERFLOW]) {
         const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
         if (c[KCTR_PAIR_OVERFLOW]) {
-            if (verbose) fprintf(stderr, "[kmdb] pair pool too small (%llu entries): doubling\n", (unsigned long long)db->pair_cap);
-            if (alloc_pair_pool(db, db->pair_cap * 2)) return 1;
+            if (verbose) fprintf(stderr, "[kmdb] pair pool too small (%llu entries): doubling\n", (unsigned long long)b.pair_cap);
+            if (alloc_pair_pool(b, b.pair_cap * 2)) return 1;
         }
         if (c[KCTR_WIDE_OVERFLOW]) {
-            const uint64_t want = db->wide_pool_cap * 2;
-            if ((want << WCH_SHIFT) >= pool_slot_limit(db)) {
-                if (db->n_slices >= (1u << 16)) { db->fallback_reason = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
-                db->n_slices *= 2;                                  // the pools stay as they are: half as many patterns per pass
-                if (verbose) fprintf(stderr, "[kmdb] wide record pool at its limit: %u slices of the pattern stream per call\n", db->n_slices);
-                db->have_counts = false; *retry = true;
+            const uint64_t want = b.wide_pool_cap * 2;
+            if ((want << WCH_SHIFT) >= pool_slot_limit(b)) {
+                if (b.n_slices >= (1u << 16)) { db->fallback_reason = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
+                b.n_slices *= 2;                                  // the pools stay as they are: half as many patterns per pass
+                if (verbose) fprintf(stderr, "[kmdb] wide record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
+                b.have_counts = false; *retry = true;
                 return 0;
             }
-            if (verbose) fprintf(stderr, "[kmdb] wide record pool too small (%llu chunks): doubling\n", (unsigned long long)db->wide_pool_cap);
-            if (alloc_wide_pool(db, want)) return 1;
+            if (verbose) fprintf(stderr, "[kmdb] wide record pool too small (%llu chunks): doubling\n", (unsigned long long)b.wide_pool_cap);
+            if (alloc_wide_pool(b, db->stream, want)) return 1;
         }
         if (c[KCTR_POOL_OVERFLOW]) {
-            uint64_t want = db->pool_cap * 2;
-            if (!row_mode && !db->dense_narrow && db->n_states > (1u << ST_MAX_BITS) && (db->pool_cap << CH_SHIFT) > 8 * (db->est_records + (1u << 22))) {
+            uint64_t want = b.pool_cap * 2;
+            if (!row_mode && !b.dense_narrow && b.n_states > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
                 // the estimate is long covered: the narrow kernel's chunks are being evicted nearly empty.  Wide pool for it as well.
-                db->dense_narrow = true;
+                b.dense_narrow = true;
                 if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the sort too\n");
-                if (alloc_wide_pool(db, db->wide_pool_cap + db->est_records * 5 / 4 / WCH_REC + (uint64_t)db->n_nsegs * (WIDE_GRAB + 2))) return 1;
+                if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC + (uint64_t)db->n_nsegs * (WIDE_GRAB + 2))) return 1;
                 want = 0;
-            } else if (row_mode && !db->dense_narrow && db->NB > (1u << ST_MAX_BITS) && (db->pool_cap << CH_SHIFT) > 8 * (db->est_records + (1u << 22))) {
+            } else if (row_mode && !b.dense_narrow && b.NB > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
                 // the same with row chunks: the diagonal records join the rows
-                db->dense_narrow = true;
+                b.dense_narrow = true;
                 if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the row chunks too\n");
-                if (alloc_wide_pool(db, db->wide_pool_cap + db->est_records * 5 / 4 / WCH_REC)) return 1;
+                if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC)) return 1;
                 want = 0;
-            } else if ((want << CH_SHIFT) >= pool_slot_limit(db)) {
-                if (db->n_slices >= (1u << 16)) {
-                    db->fallback_reason = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(db->n_states) + " streams, " + std::to_string(db->pool_cap) + " chunks were not enough)";
+            } else if ((want << CH_SHIFT) >= pool_slot_limit(b)) {
+                if (b.n_slices >= (1u << 16)) {
+                    db->fallback_reason = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(b.n_states) + " streams, " + std::to_string(b.pool_cap) + " chunks were not enough)";
                     return 0;
                 }
-                db->n_slices *= 2;
-                if (verbose) fprintf(stderr, "[kmdb] record pool at its limit: %u slices of the pattern stream per call\n", db->n_slices);
-                db->have_counts = false; *retry = true;
+                b.n_slices *= 2;
+                if (verbose) fprintf(stderr, "[kmdb] record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
+                b.have_counts = false; *retry = true;
                 return 0;
             }
             if (want) {
-                if (verbose) fprintf(stderr, "[kmdb] record pool too small (%llu chunks): %llu\n", (unsigned long long)db->pool_cap, (unsigned long long)want);
-                if (alloc_record_pool(db, want)) return 1;
+                if (verbose) fprintf(stderr, "[kmdb] record pool too small (%llu chunks): %llu\n", (unsigned long long)b.pool_cap, (unsigned long long)want);
+                if (alloc_record_pool(b, db->stream, want)) return 1;
             }
         }
-        db->have_counts = false; *retry = true;
+        b.have_counts = false; *retry = true;
         return 0;
     }
-    if (db->have_counts && (c[KCTR_NWIDE] != db->last_n_wide || c[KCTR_CHUNKS] != db->last_n_chunks ||
-                            (row_mode ? (c[KCTR_ROWJOBS] > jobs_launched || c[KCTR_WIDE_RECORDS] != db->last_n_sorted || c[KCTR_K2JOBS] > k2jobs_launched)
+    if (b.have_counts && (c[KCTR_NWIDE] != b.last_n_wide || c[KCTR_CHUNKS] != b.last_n_chunks ||
+                            (row_mode ? (c[KCTR_ROWJOBS] > jobs_launched || c[KCTR_WIDE_RECORDS] != b.last_n_sorted || c[KCTR_K2JOBS] > k2jobs_launched)
                                       : (c[KCTR_RAW] > raw_launch || c[KCTR_K2JOBS] > k2jobs_launched)))) {
         // the exact counts cannot differ for an unchanged database and emit range, and the varying ones stay inside their slack in
         // practice; if not: redo the call with upper bounds
         if (getenv("KMDB_VERBOSE"))
             fprintf(stderr, "[kmdb] a launch was sized too small (wide nodes %u / %u, chunks %u / %u, row jobs %u / %u, sorted %u / %u, apply jobs %u / %u, raw %u / %u): the call is repeated\n",
-                    c[KCTR_NWIDE], db->last_n_wide, c[KCTR_CHUNKS], db->last_n_chunks, c[KCTR_ROWJOBS], jobs_launched, c[KCTR_WIDE_RECORDS], db->last_n_sorted, c[KCTR_K2JOBS],
+                    c[KCTR_NWIDE], b.last_n_wide, c[KCTR_CHUNKS], b.last_n_chunks, c[KCTR_ROWJOBS], jobs_launched, c[KCTR_WIDE_RECORDS], b.last_n_sorted, c[KCTR_K2JOBS],
                     k2jobs_launched, c[KCTR_RAW], raw_launch);
-        db->have_counts = false; *retry = true;
+        b.have_counts = false; *retry = true;
         return 0;
     }
     // Headroom: where the wide kernel's records land depends on which wave took which run, so a pool that was just large enough this time may
     // be too small next time (a warm call would then take the enlarge-and-repeat path: seen once in the tests with pools of 1 %).  A pool
     // more than 85 % in use grows by a quarter now, while nothing runs.
-    if ((uint64_t)c[KCTR_POOL_USED] * 100 > db->pool_cap * 85) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_POOL_USED], (unsigned long long)db->pool_cap);
-        const uint64_t want = db->pool_cap + db->pool_cap / 4;
-        if (((want + (uint64_t)KMDB_SUBPOOLS * ARENA_GRAB) << CH_SHIFT) < pool_slot_limit(db) && alloc_record_pool(db, want)) return 1;
+    if ((uint64_t)c[KCTR_POOL_USED] * 100 > b.pool_cap * 85) {
+        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_POOL_USED], (unsigned long long)b.pool_cap);
+        const uint64_t want = b.pool_cap + b.pool_cap / 4;
+        if (((want + (uint64_t)KMDB_SUBPOOLS * ARENA_GRAB) << CH_SHIFT) < pool_slot_limit(b) && alloc_record_pool(b, db->stream, want)) return 1;
     }
-    if (!row_mode && (uint64_t)c[KCTR_RAW] * 100 > db->wide_pool_cap * 85) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] wide record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_RAW], (unsigned long long)db->wide_pool_cap);
-        const uint64_t want = db->wide_pool_cap + db->wide_pool_cap / 4;
-        if (((want + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) << WCH_SHIFT) < pool_slot_limit(db) && alloc_wide_pool(db, want)) return 1;
+    if (!row_mode && (uint64_t)c[KCTR_RAW] * 100 > b.wide_pool_cap * 85) {
+        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] wide record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_RAW], (unsigned long long)b.wide_pool_cap);
+        const uint64_t want = b.wide_pool_cap + b.wide_pool_cap / 4;
+        if (((want + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) << WCH_SHIFT) < pool_slot_limit(b) && alloc_wide_pool(b, db->stream, want)) return 1;
     }
-    if (!db->have_counts && getenv("KMDB_VERBOSE"))
+    if (!b.have_counts && getenv("KMDB_VERBOSE"))
         fprintf(stderr, "[kmdb] record pool: %u of %llu chunks in use (busiest sub-pool x sub-pools); wide pool / sorted arrays: %llu slots\n", c[KCTR_POOL_USED],
-                (unsigned long long)db->pool_cap, (unsigned long long)db->sorted_cap);
-    db->last_n_wide = c[KCTR_NWIDE]; db->last_n_chunks = c[KCTR_CHUNKS]; db->last_n_raw = c[KCTR_RAW]; db->last_n_slow = c[KCTR_SLOW];
-    db->last_n_rowjobs = c[KCTR_ROWJOBS]; db->last_n_sorted = c[KCTR_WIDE_RECORDS]; db->last_l2_nodes = c[KCTR_L2_NODES]; db->last_n_k2jobs = c[KCTR_K2JOBS];
-    if (db->l2_on && !db->have_counts && getenv("KMDB_VERBOSE"))
-        fprintf(stderr, "[kmdb] second level: %u nodes with %u blocks or more joined per tile (indices for %u, entries for %u)\n", c[KCTR_L2_NODES], db->l2_min_blocks,
-                db->l2_node_cap, db->l2_ent_cap);
-    db->last_records = ((uint64_t)c[KCTR_RECORDS] | ((uint64_t)c[KCTR_RECORDS_HI] << 32)) + (row_mode ? 0u : c[KCTR_WIDE_RECORDS]);
-    db->last_n_direct = c[KCTR_DIRECT];
+                (unsigned long long)b.pool_cap, (unsigned long long)b.sorted_cap);
+    b.last_n_wide = c[KCTR_NWIDE]; b.last_n_chunks = c[KCTR_CHUNKS]; b.last_n_raw = c[KCTR_RAW]; b.last_n_slow = c[KCTR_SLOW];
+    b.last_n_rowjobs = c[KCTR_ROWJOBS]; b.last_n_sorted = c[KCTR_WIDE_RECORDS]; b.last_l2_nodes = c[KCTR_L2_NODES]; b.last_n_k2jobs = c[KCTR_K2JOBS];
+    if (b.l2_on && !b.have_counts && getenv("KMDB_VERBOSE"))
+        fprintf(stderr, "[kmdb] second level: %u nodes with %u blocks or more joined per tile (indices for %u, entries for %u)\n", c[KCTR_L2_NODES], b.l2_min_blocks,
+                b.l2_node_cap, b.l2_ent_cap);
+    b.last_records = ((uint64_t)c[KCTR_RECORDS] | ((uint64_t)c[KCTR_RECORDS_HI] << 32)) + (row_mode ? 0u : c[KCTR_WIDE_RECORDS]);
+    b.last_n_direct = c[KCTR_DIRECT];
     return 0;
 }
 
@@ -3806,39 +3925,46 @@ static void blocks_join_side_streams(kmdb_db* db) {
 }
 
 int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st) {
+    BlocksState& b = *db->blocks;
     const uint64_t cells = db->N * (db->N - 1) / 2;
     for (int round = 0; round < 64; ++round) {
-        if (db->tile_touched) HIP_TRY(hipMemsetAsync(db->tile_touched, 0, (size_t)db->n_states + 1, st));      // the tiles this call adds to (all its slices)
+        if (b.tile_touched) HIP_TRY(hipMemsetAsync(b.tile_touched, 0, (size_t)b.n_states + 1, st));      // the tiles this call adds to (all its slices)
         // the slices of [emit_lo, emit_hi) one after the other, adding into the same matrix; a pass that had to enlarge a pool (or
         // asked for more slices) leaves a partial sum behind: everything again from a zeroed matrix
-        const uint32_t S = std::max<uint32_t>(1u, db->n_slices);
+        const uint32_t S = std::max<uint32_t>(1u, b.n_slices);
         bool again = false;
         uint64_t records = 0, direct = 0;
         // the launch sizes a call measures belong to one emit range: kept per slice, so that a sliced database reaches the warm path too
-        if (db->slice_counts.size() != S) db->slice_counts.assign(S, kmdb_db::SliceCounts{});
+        if (b.slice_counts.size() != S) b.slice_counts.assign(S, BlocksState::SliceCounts{});
         bool decoded = false;
         db->last_call_sized = false;
         for (uint32_t k = 0; k < S && !again; ++k) {
             const uint32_t lo = emit_lo + (uint32_t)((uint64_t)(emit_hi - emit_lo) * k / S), hi = emit_lo + (uint32_t)((uint64_t)(emit_hi - emit_lo) * (k + 1) / S);
             if (lo == hi) continue;
-            kmdb_db::SliceCounts& sc = db->slice_counts[k];
-            db->have_counts = sc.valid && sc.lo == lo && sc.hi == hi;
-            if (db->have_counts) { db->last_n_wide = sc.n_wide; db->last_n_chunks = sc.n_chunks; db->last_n_raw = sc.n_raw; db->last_n_rowjobs = sc.n_rowjobs; db->last_n_sorted = sc.n_sorted; db->last_n_k2jobs = sc.n_k2jobs; }
-            db->last_emit_lo = lo; db->last_emit_hi = hi;
-            if (!db->have_counts) db->last_call_sized = true;
+            BlocksState::SliceCounts& sc = b.slice_counts[k];
+            b.have_counts = sc.valid && sc.lo == lo && sc.hi == hi;
+            if (b.have_counts) { b.last_n_wide = sc.n_wide; b.last_n_chunks = sc.n_chunks; b.last_n_raw = sc.n_raw; b.last_n_rowjobs = sc.n_rowjobs; b.last_n_sorted = sc.n_sorted; b.last_n_k2jobs = sc.n_k2jobs; }
+            if (!b.have_counts) db->last_call_sized = true;
             bool retry = false;
             if (blocks_attempt(db, M, lo, hi, !decoded, st, &retry)) { blocks_join_side_streams(db); return 1; }
             decoded = true;
             if (!db->fallback_reason.empty()) return 0;
-            if (retry) { again = true; for (auto& c : db->slice_counts) c.valid = false; }
+            if (retry) { again = true; for (auto& c : b.slice_counts) c.valid = false; }
             else {
-                sc = kmdb_db::SliceCounts{true, lo, hi, db->last_n_wide, db->last_n_chunks, db->last_n_raw, db->last_n_rowjobs, db->last_n_sorted, db->last_n_k2jobs};
-                records += db->last_records;
-                direct += db->last_n_direct;
+                sc = BlocksState::SliceCounts{true, lo, hi, b.last_n_wide, b.last_n_chunks, b.last_n_raw, b.last_n_rowjobs, b.last_n_sorted, b.last_n_k2jobs};
+                records += b.last_records;
+                direct += b.last_n_direct;
             }
         }
-        if (!again) { db->last_records = records; db->last_n_direct = direct; db->have_counts = true; return 0; }
+        if (!again) { b.last_records = records; b.last_n_direct = direct; b.have_counts = true; return 0; }
         HIP_TRY(hipMemsetAsync(M, 0, cells * 4, st));
     }
     return kmdb_set_error("kmdb_blocks_run: the record pools did not converge");
 }
+
+// ---- what the other translation units read of the last call (engine_state.h)
+kmdb_blocks_counts kmdb_blocks_last_counts(const kmdb_db* db) {
+    const BlocksState& b = *db->blocks;
+    return kmdb_blocks_counts{b.last_records, b.last_n_direct, b.last_n_wide, b.last_n_chunks, b.l2_on ? b.last_l2_nodes : 0u};
+}
+const unsigned char* kmdb_blocks_tile_touched(const kmdb_db* db) { return db->blocks ? db->blocks->tile_touched.get() : nullptr; }

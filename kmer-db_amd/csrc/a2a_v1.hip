@@ -327,9 +327,8 @@ int kmdb_v1_run(kmdb_db* db, uint32_t* M, uint32_t seg_begin, uint32_t seg_end, 
         const size_t stride = (N + 63) / 64 * 64;
         const size_t words = (size_t)blocks * WAVES_PER_BLOCK * stride;
         if (db->stack_scratch_words < words) {
-            if (db->stack_scratch) (void)hipFree(db->stack_scratch);
-            db->stack_scratch = nullptr; db->stack_scratch_words = 0;
-            HIP_TRY(hipMalloc((void**)&db->stack_scratch, words * 4));
+            db->stack_scratch_words = 0;
+            DEV_ALLOC(db->stack_scratch, words);
             db->stack_scratch_words = words;
         }
         p.stack_scratch = db->stack_scratch;

@@ -320,13 +320,6 @@ __global__ __launch_bounds__(64) void d2_row_tiles_kernel(const uint32_t* __rest
     if (!COMPACT && lane == 0) row_nnz[row] = count;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <class T> T* as() { return (T*)p; }
-};
-
 D2Db view_of(const kmdb_engine_view& e) {
     return D2Db{e.n_buckets, e.bucket_offset, e.slots, e.pid2dfs, e.meta, e.bitpos, e.parent, e.bits};
 }
@@ -349,10 +342,10 @@ const unsigned long long* d2_list_store(const kmdb_engine_view& e, hipStream_t s
             return nullptr;
         }
     }
-    unsigned long long* sets = nullptr;
-    uint32_t* done = nullptr;
-    if (hipMalloc((void**)&sets, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipMalloc((void**)&done, (e.P + 1) * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(sets); return nullptr; }
+    // (built in a local: the handle gets the store when it is complete, anything less frees itself)
+    DevBuf<unsigned long long> sets;
+    DevBuf<uint32_t> done;
+    if (sets.alloc(e.P * nb) || done.alloc(e.P + 1)) { (void)hipGetLastError(); return nullptr; }
     bool ok = hipMemsetAsync(done, 0, (e.P + 1) * 4, st) == hipSuccess;
     const D2Db v = view_of(e);
     uint32_t filled = 0, round = 0;
@@ -363,21 +356,14 @@ const unsigned long long* d2_list_store(const kmdb_engine_view& e, hipStream_t s
             hipLaunchKernelGGL(d2_sets_round_kernel, dim3((unsigned)((e.P + 255) / 256)), dim3(256), 0, st, v, (uint32_t)e.P, nb, round, done, sets, done + e.P);
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&filled, done + e.P, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
     }
-    (void)hipFree(done);
-    if (!ok || filled != e.P) { (void)hipGetLastError(); (void)hipFree(sets); return nullptr; }
+    done.reset();
+    if (!ok || filled != e.P) { (void)hipGetLastError(); return nullptr; }
     if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] db2db: list store of %llu patterns x %u words (%.2f GB) filled in %u rounds\n", (unsigned long long)e.P, nb, bytes / 1e9, round);
-    *e.list_sets = sets; *e.list_sets_nb = nb; *e.device_bytes += bytes;
-    return sets;
+    *e.list_sets = std::move(sets); *e.list_sets_nb = nb; *e.device_bytes += bytes;
+    return *e.list_sets;
 }
 
 }  // namespace
-
-#define D2_TRY(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
 
 // what the sparse entry asks of the call (nullptr: the dense entry)
 struct D2Sparse {
@@ -401,9 +387,9 @@ static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_
         for (kmdb_engine_view* e : {&er, &ec})
             if (*e->list_sets) {
                 (void)hipSetDevice(e->device);
-                (void)hipFree(*e->list_sets);
+                e->list_sets->reset();
                 *e->device_bytes -= (uint64_t)e->P * *e->list_sets_nb * 8;
-                *e->list_sets = nullptr; *e->list_sets_nb = 0; *e->list_sets_tried = true;
+                *e->list_sets_nb = 0; *e->list_sets_tried = true;
                 freed = true;
             }
         (void)hipGetLastError();
@@ -446,29 +432,29 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     if (er.device != ec.device) return kmdb_set_error(who + ": the databases live on different devices");
     // (sample ids take 20 bits here as everywhere: round 4's limit of 65 535 samples per part — a 16-bit block index array of fixed size in the
     // pair kernel — is gone; what bounds a part now is the pair kernel's LDS and the 2^22 block pairs of the stream keys, checked below)
-    D2_TRY(hipSetDevice(er.device));
+    HIP_TRY(hipSetDevice(er.device));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)er.stream;
     const uint64_t nr = er.N, nc = ec.N;
     uint64_t n_slots = 0;
-    D2_TRY(hipMemcpy(&n_slots, ec.bucket_offset + ec.n_buckets, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_slots, ec.bucket_offset + ec.n_buckets, 8, hipMemcpyDeviceToHost));
     if (n_slots >= (1ull << 31)) return kmdb_set_error(who + ": column database has more than 2^31 hashtable slots");
-    DevBuf d_keys, d_keys2, d_uniq, d_cnt, d_nruns, d_out, d_tmp, d_flag;
-    D2_TRY(d_keys.alloc(n_slots * 8)); D2_TRY(d_keys2.alloc(n_slots * 8)); D2_TRY(d_uniq.alloc((n_slots + 1) * 8));
-    D2_TRY(d_cnt.alloc((n_slots + 1) * 4)); D2_TRY(d_nruns.alloc(16)); D2_TRY(d_out.alloc(nr * nc * 4)); D2_TRY(d_flag.alloc(16));
-    D2_TRY(hipMemsetAsync(d_out.p, 0, std::max<uint64_t>(nr * nc * 4, 4), st));
-    D2_TRY(hipMemsetAsync(d_flag.p, 0, 16, st));
+    DevBuf<void> d_keys, d_keys2, d_uniq, d_cnt, d_nruns, d_out, d_tmp, d_flag;
+    DEV_ALLOC_BYTES(d_keys, n_slots * 8); DEV_ALLOC_BYTES(d_keys2, n_slots * 8); DEV_ALLOC_BYTES(d_uniq, (n_slots + 1) * 8);
+    DEV_ALLOC_BYTES(d_cnt, (n_slots + 1) * 4); DEV_ALLOC_BYTES(d_nruns, 16); DEV_ALLOC_BYTES(d_out, nr * nc * 4); DEV_ALLOC_BYTES(d_flag, 16);
+    HIP_TRY(hipMemsetAsync(d_out.get(), 0, std::max<uint64_t>(nr * nc * 4, 4), st));
+    HIP_TRY(hipMemsetAsync(d_flag.get(), 0, 16, st));
     // the cell in tiles of 64 x 64; sparse entry: one flag byte per tile (KMDB_SP_ALL_TILES=1: every tile counts as touched, as for all2all-sp — A/B)
     const uint32_t nbr = (uint32_t)((nr + 63) / 64), nbc = (uint32_t)((nc + 63) / 64);
     const uint64_t n_tiles = (uint64_t)nbr * nbc;
     const bool all_tiles = sp && getenv("KMDB_SP_ALL_TILES");
     bool any_records = false, flags_timed = false;
-    DevBuf d_tiles;
+    DevBuf<void> d_tiles;
     if (sp) {
-        D2_TRY(d_tiles.alloc(n_tiles));
-        D2_TRY(hipMemsetAsync(d_tiles.p, all_tiles ? 1 : 0, std::max<uint64_t>(n_tiles, 1), st));
+        DEV_ALLOC_BYTES(d_tiles, n_tiles);
+        HIP_TRY(hipMemsetAsync(d_tiles.get(), all_tiles ? 1 : 0, std::max<uint64_t>(n_tiles, 1), st));
     }
     hipEvent_t ev0 = (hipEvent_t)er.ev[0], ev1 = (hipEvent_t)er.ev[1], ev2 = (hipEvent_t)er.ev[2], ev3 = (hipEvent_t)er.ev[3];
-    D2_TRY(hipEventRecord(ev0, st));
+    HIP_TRY(hipEventRecord(ev0, st));
     const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
     auto t_mark = std::chrono::steady_clock::now();
     auto phase = [&](const char* what) {                          // KMDB_VERBOSE: host-side wall time of the call's steps (each one waited for)
@@ -486,22 +472,22 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     const unsigned key_end = std::min<unsigned>(64u, cbits + rbits);
     if (n_slots && nr && nc) {
         size_t tb_sort = 0, tb_rle = 0;
-        D2_TRY(prim::sort_keys(nullptr, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
+        HIP_TRY(prim::sort_keys(nullptr, tb_sort, static_cast<unsigned long long*>(d_keys.get()), static_cast<unsigned long long*>(d_keys2.get()),
                                                  (int)n_slots, 0, key_end, st));
-        D2_TRY(prim::run_length_encode(nullptr, tb_rle, d_keys2.as<unsigned long long>(), d_uniq.as<unsigned long long>(),
-                                                     d_cnt.as<uint32_t>(), d_nruns.as<uint32_t>(), (int)n_slots, st));
-        D2_TRY(d_tmp.alloc(std::max(tb_sort, tb_rle)));
+        HIP_TRY(prim::run_length_encode(nullptr, tb_rle, static_cast<unsigned long long*>(d_keys2.get()), static_cast<unsigned long long*>(d_uniq.get()),
+                                                     static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_nruns.get()), (int)n_slots, st));
+        DEV_ALLOC_BYTES(d_tmp, std::max(tb_sort, tb_rle));
         const D2Db vr = view_of(er), vc = view_of(ec);
         hipLaunchKernelGGL(d2_probe_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, vr, vc, n_slots, cbits,
-                           d_keys.as<unsigned long long>());
-        D2_TRY(hipGetLastError());
-        D2_TRY(prim::sort_keys(d_tmp.p, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
+                           static_cast<unsigned long long*>(d_keys.get()));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(prim::sort_keys(d_tmp.get(), tb_sort, static_cast<unsigned long long*>(d_keys.get()), static_cast<unsigned long long*>(d_keys2.get()),
                                                  (int)n_slots, 0, key_end, st));
-        D2_TRY(prim::run_length_encode(d_tmp.p, tb_rle, d_keys2.as<unsigned long long>(), d_uniq.as<unsigned long long>(),
-                                                     d_cnt.as<uint32_t>(), d_nruns.as<uint32_t>(), (int)n_slots, st));
+        HIP_TRY(prim::run_length_encode(d_tmp.get(), tb_rle, static_cast<unsigned long long*>(d_keys2.get()), static_cast<unsigned long long*>(d_uniq.get()),
+                                                     static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_nruns.get()), (int)n_slots, st));
         uint32_t nruns = 0;
-        D2_TRY(hipMemcpyAsync(&nruns, d_nruns.p, 4, hipMemcpyDeviceToHost, st));
-        D2_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&nruns, d_nruns.get(), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         phase("probe + sort + run lengths");
         if (nruns) {
             // pairs -> block records -> sorted by block pair -> accumulated on the matrix cores (a2a_blocks.hip)
@@ -521,33 +507,33 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
             const unsigned long long* csets = rsets ? (db_col == db_row ? rsets : d2_list_store(ec, st, reserve)) : nullptr;
             const bool store = rsets && csets;
             phase("list stores");
-            DevBuf d_nrec, d_cursor;
-            D2_TRY(d_nrec.alloc(64 * 8 * 8)); D2_TRY(d_cursor.alloc(D2_CURSORS * 16 * 4));
-            D2_TRY(hipMemsetAsync(d_nrec.p, 0, 64 * 8 * 8, st));
-            D2_TRY(hipMemsetAsync(d_cursor.p, 0, D2_CURSORS * 16 * 4, st));
-            D2Pool pool{nullptr, nullptr, d_cursor.as<uint32_t>(), 0u, (uint32_t)key_bits, dbits, d_flag.as<uint32_t>() + 1};
-            D2_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            D2_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            D2_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            D2_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            DevBuf<void> d_nrec, d_cursor;
+            DEV_ALLOC_BYTES(d_nrec, 64 * 8 * 8); DEV_ALLOC_BYTES(d_cursor, D2_CURSORS * 16 * 4);
+            HIP_TRY(hipMemsetAsync(d_nrec.get(), 0, 64 * 8 * 8, st));
+            HIP_TRY(hipMemsetAsync(d_cursor.get(), 0, D2_CURSORS * 16 * 4, st));
+            D2Pool pool{nullptr, nullptr, static_cast<uint32_t*>(d_cursor.get()), 0u, (uint32_t)key_bits, dbits, static_cast<uint32_t*>(d_flag.get()) + 1};
+            HIP_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)d2_emit_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             // the pool: sized for six records per pair first; if that overflows, the
             // records are counted and the pool is made to measure
-            DevBuf d_wkey, d_wrec;
+            DevBuf<void> d_wkey, d_wrec;
             uint64_t slots = 0;
             for (int attempt = 0; attempt < 2; ++attempt) {
                 unsigned long long total = 6ull * nruns;
                 if (attempt) {
-                    D2_TRY(hipMemsetAsync(d_nrec.p, 0, 64 * 8 * 8, st));
+                    HIP_TRY(hipMemsetAsync(d_nrec.get(), 0, 64 * 8 * 8, st));
                     if (store)
-                        hipLaunchKernelGGL((d2_emit_kernel<true, true>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, d_uniq.as<unsigned long long>(), d_cnt.as<uint32_t>(),
-                                           nruns, nbr, nbc, cbits, pool, d_nrec.as<unsigned long long>());
+                        hipLaunchKernelGGL((d2_emit_kernel<true, true>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, static_cast<unsigned long long*>(d_uniq.get()), static_cast<uint32_t*>(d_cnt.get()),
+                                           nruns, nbr, nbc, cbits, pool, static_cast<unsigned long long*>(d_nrec.get()));
                     else
-                        hipLaunchKernelGGL((d2_emit_kernel<true, false>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, d_uniq.as<unsigned long long>(), d_cnt.as<uint32_t>(),
-                                           nruns, nbr, nbc, cbits, pool, d_nrec.as<unsigned long long>());
-                    D2_TRY(hipGetLastError());
+                        hipLaunchKernelGGL((d2_emit_kernel<true, false>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, static_cast<unsigned long long*>(d_uniq.get()), static_cast<uint32_t*>(d_cnt.get()),
+                                           nruns, nbr, nbc, cbits, pool, static_cast<unsigned long long*>(d_nrec.get()));
+                    HIP_TRY(hipGetLastError());
                     unsigned long long h_nrec[64 * 8];
-                    D2_TRY(hipMemcpyAsync(h_nrec, d_nrec.p, sizeof h_nrec, hipMemcpyDeviceToHost, st));
-                    D2_TRY(hipStreamSynchronize(st));
+                    HIP_TRY(hipMemcpyAsync(h_nrec, d_nrec.get(), sizeof h_nrec, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipStreamSynchronize(st));
                     total = 0;
                     for (int q = 0; q < 64; ++q) total += h_nrec[q * 8];
                 }
@@ -557,22 +543,22 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
                 const uint64_t region = grabs * D2_GRAB;
                 slots = region * D2_CURSORS;
                 if (slots >= (1ull << 31)) return kmdb_set_error(who + ": more than 2^31 block records");
-                if (d_wkey.p) { (void)hipFree(d_wkey.p); d_wkey.p = nullptr; (void)hipFree(d_wrec.p); d_wrec.p = nullptr; }
-                D2_TRY(d_wkey.alloc(slots * 4)); D2_TRY(d_wrec.alloc(slots * 16));
-                D2_TRY(hipMemsetAsync(d_wkey.p, 0xFF, slots * 4, st));
-                D2_TRY(hipMemsetAsync(d_cursor.p, 0, D2_CURSORS * 16 * 4, st));
-                D2_TRY(hipMemsetAsync(d_flag.as<uint32_t>() + 1, 0, 4, st));
-                pool.wkey = d_wkey.as<uint32_t>(); pool.wrec = d_wrec.as<ulonglong2>(); pool.region = (uint32_t)region;
+                dev_reset(d_wkey, d_wrec);                      // (a second round: the old pool goes before the larger one comes)
+                DEV_ALLOC_BYTES(d_wkey, slots * 4); DEV_ALLOC_BYTES(d_wrec, slots * 16);
+                HIP_TRY(hipMemsetAsync(d_wkey.get(), 0xFF, slots * 4, st));
+                HIP_TRY(hipMemsetAsync(d_cursor.get(), 0, D2_CURSORS * 16 * 4, st));
+                HIP_TRY(hipMemsetAsync(static_cast<uint32_t*>(d_flag.get()) + 1, 0, 4, st));
+                pool.wkey = static_cast<uint32_t*>(d_wkey.get()); pool.wrec = static_cast<ulonglong2*>(d_wrec.get()); pool.region = (uint32_t)region;
                 if (store)
-                    hipLaunchKernelGGL((d2_emit_kernel<false, true>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, d_uniq.as<unsigned long long>(), d_cnt.as<uint32_t>(),
-                                       nruns, nbr, nbc, cbits, pool, d_nrec.as<unsigned long long>());
+                    hipLaunchKernelGGL((d2_emit_kernel<false, true>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, static_cast<unsigned long long*>(d_uniq.get()), static_cast<uint32_t*>(d_cnt.get()),
+                                       nruns, nbr, nbc, cbits, pool, static_cast<unsigned long long*>(d_nrec.get()));
                 else
-                    hipLaunchKernelGGL((d2_emit_kernel<false, false>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, d_uniq.as<unsigned long long>(), d_cnt.as<uint32_t>(),
-                                       nruns, nbr, nbc, cbits, pool, d_nrec.as<unsigned long long>());
-                D2_TRY(hipGetLastError());
+                    hipLaunchKernelGGL((d2_emit_kernel<false, false>), dim3(grid), dim3(64 * wpb), lds, st, vr, vc, rsets, csets, static_cast<unsigned long long*>(d_uniq.get()), static_cast<uint32_t*>(d_cnt.get()),
+                                       nruns, nbr, nbc, cbits, pool, static_cast<unsigned long long*>(d_nrec.get()));
+                HIP_TRY(hipGetLastError());
                 uint32_t ovf = 0;
-                D2_TRY(hipMemcpyAsync(&ovf, d_flag.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, st));
-                D2_TRY(hipStreamSynchronize(st));
+                HIP_TRY(hipMemcpyAsync(&ovf, static_cast<uint32_t*>(d_flag.get()) + 1, 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
                 if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] db2db: %u pattern pairs, pool for %llu records (%s)%s\n", nruns, total, attempt ? "counted" : "estimate", ovf ? ": too small" : "");
                 if (!ovf) break;
                 if (attempt) return kmdb_set_error(who + ": internal error (record pool overflow)");
@@ -581,14 +567,14 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
             any_records = true;
             if (sp && !all_tiles) {
                 // the tiles this call adds to, from the pool's key words (before the sort takes the pool)
-                D2_TRY(hipEventRecord(ev1, st));
-                hipLaunchKernelGGL(d2_tile_flags_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_wkey.as<uint32_t>(), (uint32_t)slots,
-                                   (1u << key_bits) - 1u, (uint32_t)n_tiles, d_tiles.as<unsigned char>());
-                D2_TRY(hipGetLastError());
-                D2_TRY(hipEventRecord(ev2, st));
+                HIP_TRY(hipEventRecord(ev1, st));
+                hipLaunchKernelGGL(d2_tile_flags_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, static_cast<uint32_t*>(d_wkey.get()), (uint32_t)slots,
+                                   (1u << key_bits) - 1u, (uint32_t)n_tiles, static_cast<unsigned char*>(d_tiles.get()));
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(ev2, st));
                 flags_timed = true;
             }
-            if (kmdb_rect_sort_apply(st, d_wkey.as<uint32_t>(), d_wrec.p, (uint32_t)slots, nbr, nbc, key_bits, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc)) return 1;
+            if (kmdb_rect_sort_apply(st, static_cast<uint32_t*>(d_wkey.get()), d_wrec.get(), (uint32_t)slots, nbr, nbc, key_bits, static_cast<uint32_t*>(d_out.get()), (uint32_t)nr, (uint32_t)nc)) return 1;
             phase("sort + apply");
         }
     }
@@ -596,68 +582,68 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     ds = kmdb_db2db_stats{};
     ds.tiles = n_tiles;
     if (!sp) {
-        D2_TRY(hipEventRecord(ev3, st));
-        D2_TRY(hipEventSynchronize(ev3));
+        HIP_TRY(hipEventRecord(ev3, st));
+        HIP_TRY(hipEventSynchronize(ev3));
         float ms = 0;
-        D2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev3));
         kmdb_engine_set_times(db_row, ms, ms);
         uint32_t too_long = 0;
-        D2_TRY(hipMemcpy(&too_long, d_flag.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&too_long, d_flag.get(), 4, hipMemcpyDeviceToHost));
         if (too_long) return kmdb_set_error(who + ": internal error");
-        if (nr * nc) D2_TRY(hipMemcpy(out, d_out.p, nr * nc * 4, hipMemcpyDeviceToHost));
+        if (nr * nc) HIP_TRY(hipMemcpy(out, d_out.get(), nr * nc * 4, hipMemcpyDeviceToHost));
         ds.d2h_bytes = nr * nc * 4;
         return 0;
     }
     // ---- the sparse entry: the cell stays in d_out and is compacted there (count per row, exclusive sum, (col, val) in ascending columns)
-    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } c0, c1;
-    D2_TRY(hipEventCreate(&c0.e)); D2_TRY(hipEventCreate(&c1.e));
-    DevBuf d_nnz, d_ptr, d_col, d_val, d_rk, d_ck, d_scan;
+    DevEvent c0, c1;
+    if (c0.create()) return 1; if (c1.create()) return 1;
+    DevBuf<void> d_nnz, d_ptr, d_col, d_val, d_rk, d_ck, d_scan;
     DevFilter df{};
     if (sp->n_filters) {
-        D2_TRY(d_rk.alloc(nr * 4)); D2_TRY(d_ck.alloc(nc * 4));
-        if (nr) D2_TRY(hipMemcpyAsync(d_rk.p, sp->row_kmers, nr * 4, hipMemcpyHostToDevice, st));
-        if (nc) D2_TRY(hipMemcpyAsync(d_ck.p, sp->col_kmers, nc * 4, hipMemcpyHostToDevice, st));
-        df.n = (int)sp->n_filters; df.counts = d_rk.as<uint32_t>();
+        DEV_ALLOC_BYTES(d_rk, nr * 4); DEV_ALLOC_BYTES(d_ck, nc * 4);
+        if (nr) HIP_TRY(hipMemcpyAsync(d_rk.get(), sp->row_kmers, nr * 4, hipMemcpyHostToDevice, st));
+        if (nc) HIP_TRY(hipMemcpyAsync(d_ck.get(), sp->col_kmers, nc * 4, hipMemcpyHostToDevice, st));
+        df.n = (int)sp->n_filters; df.counts = static_cast<uint32_t*>(d_rk.get());
         kmdb_dev_bounds(sp->filters, sp->n_filters, (int)er.kmer_length, df.kind, df.lo, df.hi);
     }
-    D2_TRY(d_nnz.alloc((nr + 1) * 8)); D2_TRY(d_ptr.alloc((nr + 1) * 8));
+    DEV_ALLOC_BYTES(d_nnz, (nr + 1) * 8); DEV_ALLOC_BYTES(d_ptr, (nr + 1) * 8);
     // (a cell without a single block record has no tile to read: its counts stay zero)
     const bool scan = nr && nc && (any_records || all_tiles);
-    D2_TRY(hipEventRecord(c0.e, st));
-    D2_TRY(hipMemsetAsync(d_nnz.p, 0, (nr + 1) * 8, st));
+    HIP_TRY(hipEventRecord(c0, st));
+    HIP_TRY(hipMemsetAsync(d_nnz.get(), 0, (nr + 1) * 8, st));
     if (scan) {
-        hipLaunchKernelGGL((d2_row_tiles_kernel<false>), dim3((unsigned)nr), dim3(64), 0, st, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc, nbc,
-                           d_tiles.as<unsigned char>(), d_nnz.as<unsigned long long>(), (const unsigned long long*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, df, d_ck.as<uint32_t>());
-        D2_TRY(hipGetLastError());
+        hipLaunchKernelGGL((d2_row_tiles_kernel<false>), dim3((unsigned)nr), dim3(64), 0, st, static_cast<uint32_t*>(d_out.get()), (uint32_t)nr, (uint32_t)nc, nbc,
+                           static_cast<unsigned char*>(d_tiles.get()), static_cast<unsigned long long*>(d_nnz.get()), (const unsigned long long*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, df, static_cast<uint32_t*>(d_ck.get()));
+        HIP_TRY(hipGetLastError());
     }
     size_t scan_bytes = 0;
-    D2_TRY(prim::exclusive_sum(nullptr, scan_bytes, d_nnz.as<unsigned long long>(), d_ptr.as<unsigned long long>(), (size_t)(nr + 1), st));
-    D2_TRY(d_scan.alloc(scan_bytes));
-    D2_TRY(prim::exclusive_sum(d_scan.p, scan_bytes, d_nnz.as<unsigned long long>(), d_ptr.as<unsigned long long>(), (size_t)(nr + 1), st));
+    HIP_TRY(prim::exclusive_sum(nullptr, scan_bytes, static_cast<unsigned long long*>(d_nnz.get()), static_cast<unsigned long long*>(d_ptr.get()), (size_t)(nr + 1), st));
+    DEV_ALLOC_BYTES(d_scan, scan_bytes);
+    HIP_TRY(prim::exclusive_sum(d_scan.get(), scan_bytes, static_cast<unsigned long long*>(d_nnz.get()), static_cast<unsigned long long*>(d_ptr.get()), (size_t)(nr + 1), st));
     std::vector<unsigned long long> h_ptr(nr + 1, 0);
     std::vector<unsigned char> h_tiles(n_tiles, 0);
-    D2_TRY(hipMemcpyAsync(h_ptr.data(), d_ptr.p, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (n_tiles) D2_TRY(hipMemcpyAsync(h_tiles.data(), d_tiles.p, n_tiles, hipMemcpyDeviceToHost, st));
-    D2_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h_ptr.data(), d_ptr.get(), (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(h_tiles.data(), d_tiles.get(), n_tiles, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint64_t nnz_dev = h_ptr[nr];
-    D2_TRY(d_col.alloc(nnz_dev * 4)); D2_TRY(d_val.alloc(nnz_dev * 4));
+    DEV_ALLOC_BYTES(d_col, nnz_dev * 4); DEV_ALLOC_BYTES(d_val, nnz_dev * 4);
     if (scan && nnz_dev) {
-        hipLaunchKernelGGL((d2_row_tiles_kernel<true>), dim3((unsigned)nr), dim3(64), 0, st, d_out.as<uint32_t>(), (uint32_t)nr, (uint32_t)nc, nbc,
-                           d_tiles.as<unsigned char>(), (unsigned long long*)nullptr, d_ptr.as<unsigned long long>(), d_col.as<uint32_t>(),
-                           d_val.as<uint32_t>(), df, d_ck.as<uint32_t>());
-        D2_TRY(hipGetLastError());
+        hipLaunchKernelGGL((d2_row_tiles_kernel<true>), dim3((unsigned)nr), dim3(64), 0, st, static_cast<uint32_t*>(d_out.get()), (uint32_t)nr, (uint32_t)nc, nbc,
+                           static_cast<unsigned char*>(d_tiles.get()), (unsigned long long*)nullptr, static_cast<unsigned long long*>(d_ptr.get()), static_cast<uint32_t*>(d_col.get()),
+                           static_cast<uint32_t*>(d_val.get()), df, static_cast<uint32_t*>(d_ck.get()));
+        HIP_TRY(hipGetLastError());
     }
-    D2_TRY(hipEventRecord(c1.e, st));
-    D2_TRY(hipEventRecord(ev3, st));
-    D2_TRY(hipEventSynchronize(ev3));
+    HIP_TRY(hipEventRecord(c1, st));
+    HIP_TRY(hipEventRecord(ev3, st));
+    HIP_TRY(hipEventSynchronize(ev3));
     float ms = 0, ms_flags = 0, ms_compact = 0;
-    D2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
-    D2_TRY(hipEventElapsedTime(&ms_compact, c0.e, c1.e));
-    if (flags_timed) D2_TRY(hipEventElapsedTime(&ms_flags, ev1, ev2));
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+    HIP_TRY(hipEventElapsedTime(&ms_compact, c0, c1));
+    if (flags_timed) HIP_TRY(hipEventElapsedTime(&ms_flags, ev1, ev2));
     kmdb_engine_set_times(db_row, ms, ms);
     uint32_t too_long = 0;
-    D2_TRY(hipMemcpy(&too_long, d_flag.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&too_long, d_flag.get(), 4, hipMemcpyDeviceToHost));
     if (too_long) return kmdb_set_error(who + ": internal error");
     kmdb_sparse_rows* o = sp->out;
     o->n_rows = nr;
@@ -668,8 +654,8 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     if (!o->row_ptr || !o->col || !o->val) return kmdb_set_error(who + ": out of host memory for the result");
     for (uint64_t i = 0; i <= nr; ++i) o->row_ptr[i] = h_ptr[i];
     if (nnz_dev) {
-        D2_TRY(hipMemcpy(o->col, d_col.p, nnz_dev * 4, hipMemcpyDeviceToHost));
-        D2_TRY(hipMemcpy(o->val, d_val.p, nnz_dev * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(o->col, d_col.get(), nnz_dev * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(o->val, d_val.get(), nnz_dev * 4, hipMemcpyDeviceToHost));
     }
     for (unsigned char t : h_tiles) ds.tiles_touched += t != 0;
     ds.nnz_device = nnz_dev;

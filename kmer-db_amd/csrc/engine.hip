@@ -197,10 +197,10 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
     db->one_shot = opts && (opts->flags & KMDB_FLAG_ONE_SHOT);
     auto fail = [&]() { kmdb_db_free(db); return 1; };
     if (hipStreamCreate(&db->stream) != hipSuccess) { kmdb_set_error("hipStreamCreate failed"); return fail(); }
-    for (auto& e : db->ev) if (hipEventCreate(&e) != hipSuccess) { kmdb_set_error("hipEventCreate failed"); return fail(); }
-    for (auto& e : db->ev_k) if (hipEventCreate(&e) != hipSuccess) { kmdb_set_error("hipEventCreate failed"); return fail(); }
+    for (auto& e : db->ev) if (e.create()) return fail();
+    for (auto& e : db->ev_k) if (e.create()) return fail();
     if (hipStreamCreate(&db->stream2) != hipSuccess) { kmdb_set_error("hipStreamCreate failed"); return fail(); }
-    for (auto& e : db->ev_side) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { kmdb_set_error("hipEventCreate failed"); return fail(); }
+    for (auto& e : db->ev_side) if (e.create(hipEventDisableTiming)) return fail();
     // KMDB_VERBOSE: the four parts of the upload as wholes (the layout and the preparation print their own phases; what those
     // leave out — the release of their temporaries, the first use of the device by the process — shows up here)
     const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
@@ -301,14 +301,8 @@ extern "C" void kmdb_db_free(kmdb_db* db) {
     if (db->staging_thread.joinable()) db->staging_thread.join();
     for (const auto& r : db->staging_kept) (void)munmap(r.first, r.second);      // a one-shot handle's regions: pages long dropped, the mappings go now
     db->staging_kept.clear();
-    kmdb_blocks_release(db);
-    void* ptrs[] = {db->k0in, db->bitrel, db->blkbase, db->bits, db->nl, db->parent, db->w, db->dflag, db->sub_end, db->long_nodes, db->nseg_anc,
-                    db->nseg_anc_n, db->meta, db->bitpos, db->ck_ofs, db->ck_bit, db->ck_id, db->wprefix, db->segs, db->v1_scan_tmp, db->stack_scratch, db->v1_counters,
-                    db->bucket_offset, db->slots, db->pid2dfs, db->list_sets, db->rl_ofs, db->rl_runs, db->rl_node};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& e : db->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : db->ev_k) if (e) (void)hipEventDestroy(e);
-    for (auto& e : db->ev_side) if (e) (void)hipEventDestroy(e);
+    // The streams go first; the pipeline's state, the device arrays and the events are members and go with the handle below, while its device
+    // is still current (set above).  The order does not matter: a destroyed stream finishes its work, and hipFree waits for the device.
     if (db->stream2) (void)hipStreamDestroy(db->stream2);
     if (db->stream) (void)hipStreamDestroy(db->stream);
     delete db;
@@ -404,7 +398,7 @@ int run_dense(kmdb_db* db, uint32_t* M, const kmdb_opts* opts, hipStream_t st) {
     // with their 16-bit ids are only ever chosen up to 4096 samples, kmdb_v1_run)
     if (kmdb_ensure_v1_arrays(db)) return 1;
     HIP_TRY(hipMemsetAsync(db->v1_counters, 0, 8 * sizeof(unsigned long long), st));
-    HIP_TRY(prim::exclusive_sum(db->v1_scan_tmp, db->v1_scan_tmp_bytes, db->w, db->wprefix, (int)(P + 1), st));
+    HIP_TRY(prim::exclusive_sum(db->v1_scan_tmp, db->v1_scan_tmp_bytes, db->w.get(), db->wprefix.get(), (int)(P + 1), st));
     HIP_TRY(hipEventRecord(db->ev[1], st));
     const uint32_t seg_begin = (uint32_t)((uint64_t)db->n_segs * shard_index / shard_count) / WAVES_PER_BLOCK * WAVES_PER_BLOCK;
     const uint32_t seg_end = shard_index + 1 == shard_count ? db->n_segs : (uint32_t)((uint64_t)db->n_segs * (shard_index + 1) / shard_count) / WAVES_PER_BLOCK * WAVES_PER_BLOCK;
@@ -428,9 +422,10 @@ int finish_stats(kmdb_db* db, hipStream_t st) {
         HIP_TRY(hipEventElapsedTime(&k1g, db->ev_k[1], db->ev_k[2]));
         HIP_TRY(hipEventElapsedTime(&k2, db->ev_k[2], db->ev_k[3]));
         db->stats.k0_ms = k0; db->stats.k1n_ms = k1n; db->stats.k1g_ms = k1g; db->stats.k1_ms = k1n + k1g; db->stats.k2_ms = k2;
-        db->stats.n_records = db->last_records; db->stats.n_wide = db->last_n_wide; db->stats.n_chunks = db->last_n_chunks;
-        db->stats.n_joined = db->l2_on ? db->last_l2_nodes : 0u;
-        db->stats.n_direct = db->last_n_direct;
+        const kmdb_blocks_counts last = kmdb_blocks_last_counts(db);
+        db->stats.n_records = last.records; db->stats.n_wide = last.wide; db->stats.n_chunks = last.chunks;
+        db->stats.n_joined = last.joined;
+        db->stats.n_direct = last.direct;
         // the pipeline's arrays grow inside calls (second-level arrays on the first call, pools enlarged by a quarter or doubled): what is
         // resident NOW, not what the preparation allocated
         const uint64_t now = kmdb_blocks_device_bytes(db);
@@ -460,14 +455,14 @@ extern "C" int kmdb_all2all_dense(kmdb_db* db, uint32_t* out, const kmdb_opts* o
     if (!db || (!out && db->N > 1)) return kmdb_set_error("kmdb_all2all_dense: null argument");
     HIP_TRY(hipSetDevice(db->device));
     const uint64_t cells = db->N ? db->N * (db->N - 1) / 2 : 0;
-    uint32_t* M = nullptr;
-    HIP_TRY(hipMalloc((void**)&M, std::max<uint64_t>(cells, 1) * 4));
+    DevBuf<uint32_t> M;
+    DEV_ALLOC(M, std::max<uint64_t>(cells, 1));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
     int rc = run_dense(db, M, opts, st);
     if (!rc) rc = finish_stats(db, st);
     if (!rc && cells && hipMemcpy(out, M, cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
         rc = kmdb_set_error("kmdb_all2all_dense: copy back failed");
-    (void)hipFree(M);
+    M.reset();
     kmdb_release_staging(db);
     return rc;
 }
@@ -612,22 +607,19 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
     HIP_TRY(hipSetDevice(db->device));
     const uint64_t N = db->N;
     const uint64_t cells = N ? N * (N - 1) / 2 : 0;
-    uint32_t* M = nullptr;
-    unsigned long long *row_nnz = nullptr, *row_ptr = nullptr;
-    uint32_t *col = nullptr, *val = nullptr, *d_counts = nullptr;
-    void* tmp = nullptr;
+    DevBuf<uint32_t> M, col, val, d_counts;
+    DevBuf<unsigned long long> row_nnz, row_ptr;
+    DevBuf<void> tmp;
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
     int rc = 0;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)M, (void*)row_nnz, (void*)row_ptr, (void*)col, (void*)val, (void*)d_counts, tmp}) if (p) (void)hipFree(p);
-    };
     DevFilter df{};
-#define SP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); kmdb_sparse_free(out); return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    if (!from_cells) SP_TRY(hipMalloc((void**)&M, std::max<uint64_t>(cells, 1) * 4));
-    SP_TRY(hipMalloc((void**)&row_nnz, (N + 1) * 8));
-    SP_TRY(hipMalloc((void**)&row_ptr, (N + 1) * 8));
+#define SP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { kmdb_sparse_free(out); return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+#define SP_ALLOC(buf, n) do { if ((buf).alloc((n), #buf)) { kmdb_sparse_free(out); return 1; } } while (0)
+    if (!from_cells) SP_ALLOC(M, std::max<uint64_t>(cells, 1));
+    SP_ALLOC(row_nnz, N + 1);
+    SP_ALLOC(row_ptr, N + 1);
     if (n_filters) {
-        SP_TRY(hipMalloc((void**)&d_counts, std::max<uint64_t>(N, 1) * 4));
+        SP_ALLOC(d_counts, std::max<uint64_t>(N, 1));
         SP_TRY(hipMemcpyAsync(d_counts, sample_kmers, N * 4, hipMemcpyHostToDevice, st));
         df.n = (int)n_filters; df.counts = d_counts;
         kmdb_dev_bounds(filters, n_filters, (int)db->kmer_length, df.kind, df.lo, df.hi);
@@ -635,7 +627,7 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
     const uint32_t* cellsp = (const uint32_t*)dense_dev;
     if (!from_cells) {
         rc = run_dense(db, M, opts, st);
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
         cellsp = M; cell_lo = 0; cell_hi = cells;
     } else {
         SP_TRY(hipEventRecord(db->ev[0], st)); SP_TRY(hipEventRecord(db->ev[1], st)); SP_TRY(hipEventRecord(db->ev[2], st));
@@ -649,40 +641,41 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
     }
     SP_TRY(hipMemsetAsync(row_nnz, 0, (N + 1) * 8, st));
     // the block-record pipeline just told which tiles it added to: only those are scanned (KMDB_SP_ALL_TILES=1: every cell, as before — A/B)
-    const bool skip = !from_cells && db->stats.path == KMDB_PATH_RECORDS && db->tile_touched && N > 1 && !getenv("KMDB_SP_ALL_TILES");
-    const TileSkip ts{db->tile_touched, db->width};
+    const unsigned char* touched = kmdb_blocks_tile_touched(db);
+    const bool skip = !from_cells && db->stats.path == KMDB_PATH_RECORDS && touched && N > 1 && !getenv("KMDB_SP_ALL_TILES");
+    const TileSkip ts{touched, db->width};
     if (skip) hipLaunchKernelGGL((row_tiles_kernel<false>), dim3((unsigned)N), dim3(64), 0, st, cellsp, N, ts, row_nnz, (const unsigned long long*)nullptr, (uint32_t*)nullptr,
                                  (uint32_t*)nullptr, df);
     else
     if (row_hi > row_lo) hipLaunchKernelGGL(row_nnz_kernel, dim3((unsigned)(row_hi - row_lo)), dim3(256), 0, st, cellsp, row_lo, cell_lo, cell_hi, row_nnz, df);
     size_t tmp_bytes = 0;
-    SP_TRY(prim::exclusive_sum(nullptr, tmp_bytes, row_nnz, row_ptr, (int)(N + 1), st));
-    SP_TRY(hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    SP_TRY(prim::exclusive_sum(tmp, tmp_bytes, row_nnz, row_ptr, (int)(N + 1), st));
+    SP_TRY(prim::exclusive_sum(nullptr, tmp_bytes, row_nnz.get(), row_ptr.get(), (int)(N + 1), st));
+    SP_ALLOC(tmp, std::max<size_t>(tmp_bytes, 16));
+    SP_TRY(prim::exclusive_sum(tmp, tmp_bytes, row_nnz.get(), row_ptr.get(), (int)(N + 1), st));
     std::vector<unsigned long long> h_ptr(N + 1, 0);
     SP_TRY(hipMemcpyAsync(h_ptr.data(), row_ptr, (N + 1) * 8, hipMemcpyDeviceToHost, st));
     SP_TRY(hipStreamSynchronize(st));
     const uint64_t nnz = h_ptr[N];
-    SP_TRY(hipMalloc((void**)&col, std::max<uint64_t>(nnz, 1) * 4));
-    SP_TRY(hipMalloc((void**)&val, std::max<uint64_t>(nnz, 1) * 4));
+    SP_ALLOC(col, std::max<uint64_t>(nnz, 1));
+    SP_ALLOC(val, std::max<uint64_t>(nnz, 1));
     if (skip) hipLaunchKernelGGL((row_tiles_kernel<true>), dim3((unsigned)N), dim3(64), 0, st, cellsp, N, ts, (unsigned long long*)nullptr, row_ptr, col, val, df);
     else
     if (row_hi > row_lo) hipLaunchKernelGGL(row_compact_kernel, dim3((unsigned)(row_hi - row_lo)), dim3(256), 0, st, cellsp, row_lo, cell_lo, cell_hi, row_ptr, col, val, df);
     rc = finish_stats(db, st);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     out->n_rows = N;
     out->nnz = nnz;
     out->row_ptr = (uint64_t*)std::malloc((N + 1) * 8);
     out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
     out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
-    if (!out->row_ptr || !out->col || !out->val) { cleanup(); kmdb_sparse_free(out); return kmdb_set_error("kmdb_all2all_sparse: out of host memory for the result"); }
+    if (!out->row_ptr || !out->col || !out->val) { kmdb_sparse_free(out); return kmdb_set_error("kmdb_all2all_sparse: out of host memory for the result"); }
     for (uint64_t i = 0; i <= N; ++i) out->row_ptr[i] = h_ptr[i];
     if (nnz) {
         SP_TRY(hipMemcpy(out->col, col, nnz * 4, hipMemcpyDeviceToHost));
         SP_TRY(hipMemcpy(out->val, val, nnz * 4, hipMemcpyDeviceToHost));
     }
 #undef SP_TRY
-    cleanup();
+#undef SP_ALLOC
     kmdb_release_staging(db);
     if (n_filters || measure >= 0) return kmdb_sparse_decide("kmdb_all2all_sparse", out, filters, n_filters, sample_kmers, sample_kmers, measure, (int)db->kmer_length);
     return 0;
@@ -727,10 +720,6 @@ int check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n
     if (!sample_kmers) return kmdb_set_error(std::string(who) + ": sample_kmers is NULL");
     return kmdb_check_filters(who, filters, n_filters, sample_kmers, -1);
 }
-struct DevFree {
-    std::vector<void*> p;
-    ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
-};
 
 // The candidates of the symmetric rows of the cells [cell_lo, cell_hi) — complete: every row holds its `count` best cells by the exact decision
 // among the cells of the range (rows the margin band could not settle are fetched again whole).
@@ -741,11 +730,9 @@ int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dens
     const uint64_t N = db->N;
     const uint64_t cells = N ? N * (N - 1) / 2 : 0;
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
-    DevFree dev;
-    uint32_t *M = nullptr, *d_counts = nullptr;
-    if (!from_cells) { HIP_TRY(hipMalloc((void**)&M, std::max<uint64_t>(cells, 1) * 4)); dev.p.push_back(M); }
-    HIP_TRY(hipMalloc((void**)&d_counts, std::max<uint64_t>(N, 1) * 4));
-    dev.p.push_back(d_counts);
+    DevBuf<uint32_t> M, d_counts;
+    if (!from_cells) DEV_ALLOC(M, std::max<uint64_t>(cells, 1));
+    DEV_ALLOC(d_counts, std::max<uint64_t>(N, 1));
     HIP_TRY(hipMemcpyAsync(d_counts, sample_kmers, N * 4, hipMemcpyHostToDevice, st));
     const int k = (int)db->kmer_length;
     const Proxy px = proxy_of(criterion);
@@ -759,7 +746,8 @@ int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dens
         if (run_dense(db, M, opts, st)) return 1;
         job.cells = M; job.cell_lo = 0; job.cell_hi = cells;
         // the block-record pipeline just told which tiles it added to: only those are read (KMDB_SP_ALL_TILES=1: every tile — A/B)
-        if (db->stats.path == KMDB_PATH_RECORDS && db->tile_touched && N > 1 && !getenv("KMDB_SP_ALL_TILES")) { job.touched = db->tile_touched; job.width = db->width; }
+        const unsigned char* touched = kmdb_blocks_tile_touched(db);
+        if (db->stats.path == KMDB_PATH_RECORDS && touched && N > 1 && !getenv("KMDB_SP_ALL_TILES")) { job.touched = touched; job.width = db->width; }
     } else {
         HIP_TRY(hipEventRecord(db->ev[0], st)); HIP_TRY(hipEventRecord(db->ev[1], st)); HIP_TRY(hipEventRecord(db->ev[2], st));
         db->stats.path = KMDB_PATH_NONE;

@@ -1,6 +1,8 @@
 // engine_internal.h — lets the other translation units of libkmdb_amd.so (new2all.hip) reach
 // the HBM-resident database that engine.hip owns.  Not installed.
 #pragma once
+#include "dev_mem.h"
+
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -29,14 +31,14 @@ struct kmdb_engine_view {
     uint32_t qs_index, qs_count;   // query shard: qs_count > 1, the tables hold the buckets b % qs_count == qs_index at b / qs_count and DFS indices as values; pid2dfs is null
     uint32_t max_depth;            // nodes on the longest root path
     // list store of db2db.hip, kept with the handle: the full sample list of every pattern as a bit set of list_sets_nb words
-    // (built on the first db2db call that can afford it, freed by kmdb_db_free)
-    unsigned long long** list_sets;
+    // (built on the first db2db call that can afford it; the handle owns it)
+    DevBuf<unsigned long long>* list_sets;
     uint32_t* list_sets_nb;
     bool* list_sets_tried;
     // run index of new2all.hip, kept with the handle: node i's local ids as runs rl_runs[rl_ofs[i] .. rl_ofs[i + 1]) (start | length << rs, n2a_run_shift)
-    uint32_t** rl_ofs;
-    uint32_t** rl_runs;
-    uint4** rl_node;               // and the walk's 16-byte node records {subtree end, parent, first run or the only id, min(l, 65535) | min(runs, 65535) << 16}
+    DevBuf<uint32_t>* rl_ofs;
+    DevBuf<uint32_t>* rl_runs;
+    DevBuf<uint4>* rl_node;              // and the walk's 16-byte node records {subtree end, parent, first run or the only id, min(l, 65535) | min(runs, 65535) << 16}
     bool* rl_tried;
     uint64_t* device_bytes;
     struct kmdb_db2db_stats* d2_stats;   // the last db2db call with this handle as the row database (kmdb_db2db_stats_get)

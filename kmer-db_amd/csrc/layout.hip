@@ -230,14 +230,6 @@ struct HostBuf {
     HostBuf& operator=(const HostBuf&) = delete;
 };
 
-template <class T>
-struct DevTmp {
-    T* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { HIP_TRY(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return 0; }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; }
-};
-
 }  // namespace
 
 void kmdb_release_staging(kmdb_db* db) {
@@ -402,25 +394,25 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     phase("host: narrow fields + pack streams");
 
     // ---- H2D
-    DevTmp<int32_t> d_parent;
-    DevTmp<uint32_t> d_ll, d_last, d_n, d_nbits, d_w;
-    DevTmp<uint64_t> d_src;
-    if (d_parent.alloc(P) || d_ll.alloc(P) || d_last.alloc(P) || d_n.alloc(P) || d_nbits.alloc(P) || d_w.alloc(P) || d_src.alloc(n_bit_words)) return 1;
-    HIP_TRY(hipMemcpyAsync(d_parent.p, h_parent.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ll.p, h_ll.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_last.p, h_last.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_n.p, h_n.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_nbits.p, h_nbits.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_w.p, h_w.p, P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_src.p, h_bits.p, n_bit_words * 8, hipMemcpyHostToDevice, st));
+    DevBuf<int32_t> d_parent;
+    DevBuf<uint32_t> d_ll, d_last, d_n, d_nbits, d_w;
+    DevBuf<uint64_t> d_src;
+    if (d_parent.alloc(std::max<size_t>(P, 1)) || d_ll.alloc(std::max<size_t>(P, 1)) || d_last.alloc(std::max<size_t>(P, 1)) || d_n.alloc(std::max<size_t>(P, 1)) || d_nbits.alloc(std::max<size_t>(P, 1)) || d_w.alloc(std::max<size_t>(P, 1)) || d_src.alloc(std::max<size_t>(n_bit_words, 1))) return 1;
+    HIP_TRY(hipMemcpyAsync(d_parent.get(), h_parent.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_ll.get(), h_ll.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_last.get(), h_last.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_n.get(), h_n.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_nbits.get(), h_nbits.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_w.get(), h_w.p, P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_src.get(), h_bits.p, n_bit_words * 8, hipMemcpyHostToDevice, st));
     h2d_bytes += P * 24 + n_bit_words * 8;
-    DevTmp<unsigned long long> d_wfull;                       // sum_pairs uses the untruncated counts
+    DevBuf<unsigned long long> d_wfull;                       // sum_pairs uses the untruncated counts
     uint64_t dev_ht_bytes = 0;
     if (qshard) {
         // only the shard's own bucket table: no slot of a foreign bucket crosses PCIe, and no pid2dfs array is made (the slots hold DFS indices)
         db->n_buckets = qs_buckets; db->qs_index = sel->qs_index; db->qs_count = sel->qs_count;
-        HIP_TRY(hipMalloc((void**)&db->bucket_offset, (qs_buckets + 1) * 8));
-        HIP_TRY(hipMalloc((void**)&db->slots, std::max<uint64_t>(qs_slots, 1) * 8));
+        DEV_ALLOC(db->bucket_offset, qs_buckets + 1);
+        DEV_ALLOC(db->slots, std::max<uint64_t>(qs_slots, 1));
         HIP_TRY(hipMemcpyAsync(db->bucket_offset, h_qoff.p, (qs_buckets + 1) * 8, hipMemcpyHostToDevice, st));
         if (qs_slots) HIP_TRY(hipMemcpyAsync(db->slots, h_qslots.p, qs_slots * 8, hipMemcpyHostToDevice, st));
         h2d_bytes += (qs_buckets + 1) * 8 + qs_slots * 8;
@@ -428,8 +420,8 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     } else if (with_hashtables && v->n_buckets) {
         const uint64_t n_slots = v->bucket_offset[v->n_buckets];
         db->n_buckets = v->n_buckets;
-        HIP_TRY(hipMalloc((void**)&db->bucket_offset, (v->n_buckets + 1) * 8));
-        HIP_TRY(hipMalloc((void**)&db->slots, std::max<uint64_t>(n_slots, 1) * 8));
+        DEV_ALLOC(db->bucket_offset, v->n_buckets + 1);
+        DEV_ALLOC(db->slots, std::max<uint64_t>(n_slots, 1));
         HIP_TRY(hipMemcpyAsync(db->bucket_offset, v->bucket_offset, (v->n_buckets + 1) * 8, hipMemcpyHostToDevice, st));
         if (n_slots) HIP_TRY(hipMemcpyAsync(db->slots, v->slots, n_slots * 8, hipMemcpyHostToDevice, st));
         h2d_bytes += (v->n_buckets + 1) * 8 + n_slots * 8;
@@ -448,45 +440,45 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         if (r.p) db->staging.emplace_back(r.p, r.bytes);
 
     // ---- device: DFS pre-order
-    DevTmp<uint32_t> cnt, cstart, size, keys, vals, skeys, schild, ssz, S, acc[2], dep[2], order, flags;
-    DevTmp<int32_t> anc[2];
-    if (cnt.alloc(P + 2) || cstart.alloc(P + 2) || size.alloc(P) || flags.alloc(4)) return 1;
+    DevBuf<uint32_t> cnt, cstart, size, keys, vals, skeys, schild, ssz, S, acc[2], dep[2], order, flags;
+    DevBuf<int32_t> anc[2];
+    if (cnt.alloc(P + 2) || cstart.alloc(P + 2) || size.alloc(std::max<size_t>(P, 1)) || flags.alloc(4)) return 1;
     phase("  first device temporaries");
-    HIP_TRY(hipMemsetAsync(cnt.p, 0, (P + 2) * 4, st));
-    HIP_TRY(hipMemsetAsync(cstart.p, 0, (P + 2) * 4, st));
-    HIP_TRY(hipMemsetAsync(flags.p, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(cnt.get(), 0, (P + 2) * 4, st));
+    HIP_TRY(hipMemsetAsync(cstart.get(), 0, (P + 2) * 4, st));
+    HIP_TRY(hipMemsetAsync(flags.get(), 0, 16, st));
     // children grouped by parent, pid order inside a family
-    if (keys.alloc(P) || vals.alloc(P) || skeys.alloc(P) || schild.alloc(P)) return 1;
+    if (keys.alloc(std::max<size_t>(P, 1)) || vals.alloc(std::max<size_t>(P, 1)) || skeys.alloc(std::max<size_t>(P, 1)) || schild.alloc(std::max<size_t>(P, 1))) return 1;
     HIP_TRY(hipStreamSynchronize(st));
     phase("  temporaries (hipMalloc)");
-    hipLaunchKernelGGL(lay_keys_kernel, dim3(G), dim3(B), 0, st, d_parent.p, (uint32_t)P, keys.p, vals.p);
+    hipLaunchKernelGGL(lay_keys_kernel, dim3(G), dim3(B), 0, st, d_parent.get(), (uint32_t)P, keys.get(), vals.get());
     {
         int end_bit = 1;
         while ((1ull << end_bit) <= P) ++end_bit;
         size_t tb = 0;
-        HIP_TRY(prim::sort_pairs(nullptr, tb, keys.p, skeys.p, vals.p, schild.p, (int)P, 0, end_bit, st));
-        DevTmp<unsigned char> tmp;
-        if (tmp.alloc(tb)) return 1;
+        HIP_TRY(prim::sort_pairs(nullptr, tb, keys.get(), skeys.get(), vals.get(), schild.get(), (int)P, 0, end_bit, st));
+        DevBuf<unsigned char> tmp;
+        if (tmp.alloc(std::max<size_t>(tb, 1))) return 1;
         HIP_TRY(hipStreamSynchronize(st));
         phase("  keys + sort temporaries");
-        HIP_TRY(prim::sort_pairs(tmp.p, tb, keys.p, skeys.p, vals.p, schild.p, (int)P, 0, end_bit, st));
+        HIP_TRY(prim::sort_pairs(tmp.get(), tb, keys.get(), skeys.get(), vals.get(), schild.get(), (int)P, 0, end_bit, st));
         HIP_TRY(hipStreamSynchronize(st));
         phase("  radix sort");
     }
     keys.reset(); vals.reset();
-    hipLaunchKernelGGL(lay_child_runs_kernel, dim3(G), dim3(B), 0, st, skeys.p, (uint32_t)P, cstart.p, cnt.p);
-    hipLaunchKernelGGL(lay_child_len_kernel, dim3(G1), dim3(B), 0, st, cstart.p, (uint32_t)(P + 1), cnt.p);
+    hipLaunchKernelGGL(lay_child_runs_kernel, dim3(G), dim3(B), 0, st, skeys.get(), (uint32_t)P, cstart.get(), cnt.get());
+    hipLaunchKernelGGL(lay_child_len_kernel, dim3(G1), dim3(B), 0, st, cstart.get(), (uint32_t)(P + 1), cnt.get());
     phase("  sort by parent");
     // depth of every node: pointer doubling along the parent links (ping-pong buffers)
-    for (int k = 0; k < 2; ++k) if (acc[k].alloc(P) || dep[k].alloc(P) || anc[k].alloc(P)) return 1;
-    auto jump_all = [&](DevTmp<uint32_t>* val, int* cur_out) -> int {
+    for (int k = 0; k < 2; ++k) if (acc[k].alloc(std::max<size_t>(P, 1)) || dep[k].alloc(std::max<size_t>(P, 1)) || anc[k].alloc(std::max<size_t>(P, 1))) return 1;
+    auto jump_all = [&](DevBuf<uint32_t>* val, int* cur_out) -> int {
         int cur = 0;
-        HIP_TRY(hipMemcpyAsync(anc[0].p, d_parent.p, P * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(anc[0].get(), d_parent.get(), P * 4, hipMemcpyDeviceToDevice, st));
         for (int round = 0; round < 40; ++round) {
-            HIP_TRY(hipMemsetAsync(flags.p, 0, 4, st));
-            hipLaunchKernelGGL(lay_jump_kernel, dim3(G), dim3(B), 0, st, val[cur].p, anc[cur].p, (uint32_t)P, val[cur ^ 1].p, anc[cur ^ 1].p, flags.p);
+            HIP_TRY(hipMemsetAsync(flags.get(), 0, 4, st));
+            hipLaunchKernelGGL(lay_jump_kernel, dim3(G), dim3(B), 0, st, val[cur].get(), anc[cur].get(), (uint32_t)P, val[cur ^ 1].get(), anc[cur ^ 1].get(), flags.get());
             uint32_t active = 0;
-            HIP_TRY(hipMemcpyAsync(&active, flags.p, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&active, flags.get(), 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             cur ^= 1;
             if (!active) break;
@@ -495,84 +487,84 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         return 0;
     };
     int dcur = 0;
-    hipLaunchKernelGGL(lay_fill_kernel, dim3(G), dim3(B), 0, st, dep[0].p, (uint32_t)P, 1u);
+    hipLaunchKernelGGL(lay_fill_kernel, dim3(G), dim3(B), 0, st, dep[0].get(), (uint32_t)P, 1u);
     if (jump_all(dep, &dcur)) return 1;
     dep[dcur ^ 1].reset();
     uint32_t max_depth = 0;
     {
-        DevTmp<uint32_t> dmax;
+        DevBuf<uint32_t> dmax;
         if (dmax.alloc(1)) return 1;
         size_t tb = 0;
-        HIP_TRY(prim::max(nullptr, tb, dep[dcur].p, dmax.p, (int)P, st));
-        DevTmp<unsigned char> tmp;
-        if (tmp.alloc(tb)) return 1;
-        HIP_TRY(prim::max(tmp.p, tb, dep[dcur].p, dmax.p, (int)P, st));
-        HIP_TRY(hipMemcpyAsync(&max_depth, dmax.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(prim::max(nullptr, tb, dep[dcur].get(), dmax.get(), (int)P, st));
+        DevBuf<unsigned char> tmp;
+        if (tmp.alloc(std::max<size_t>(tb, 1))) return 1;
+        HIP_TRY(prim::max(tmp.get(), tb, dep[dcur].get(), dmax.get(), (int)P, st));
+        HIP_TRY(hipMemcpyAsync(&max_depth, dmax.get(), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     phase("  depth");
     for (uint32_t level = max_depth; level >= 1; --level)
-        hipLaunchKernelGGL(lay_sizes_level_kernel, dim3(G), dim3(B), 0, st, dep[dcur].p, level, cstart.p, cnt.p, schild.p, (uint32_t)P, size.p);
+        hipLaunchKernelGGL(lay_sizes_level_kernel, dim3(G), dim3(B), 0, st, dep[dcur].get(), level, cstart.get(), cnt.get(), schild.get(), (uint32_t)P, size.get());
     HIP_TRY(hipGetLastError());
     phase("  subtree sizes");
     // pre-order offsets among siblings, then their sums along the root paths
-    if (ssz.alloc(P) || S.alloc(P + 1)) return 1;
-    hipLaunchKernelGGL(lay_gather_u32_kernel, dim3(G), dim3(B), 0, st, size.p, schild.p, (uint32_t)P, ssz.p);
+    if (ssz.alloc(std::max<size_t>(P, 1)) || S.alloc(P + 1)) return 1;
+    hipLaunchKernelGGL(lay_gather_u32_kernel, dim3(G), dim3(B), 0, st, size.get(), schild.get(), (uint32_t)P, ssz.get());
     {
         size_t tb1 = 0;
-        HIP_TRY(prim::exclusive_sum(nullptr, tb1, ssz.p, S.p, (int)P, st));
-        DevTmp<unsigned char> tmp;
-        if (tmp.alloc(tb1)) return 1;
-        HIP_TRY(prim::exclusive_sum(tmp.p, tb1, ssz.p, S.p, (int)P, st));
+        HIP_TRY(prim::exclusive_sum(nullptr, tb1, ssz.get(), S.get(), (int)P, st));
+        DevBuf<unsigned char> tmp;
+        if (tmp.alloc(std::max<size_t>(tb1, 1))) return 1;
+        HIP_TRY(prim::exclusive_sum(tmp.get(), tb1, ssz.get(), S.get(), (int)P, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     ssz.reset();
-    hipLaunchKernelGGL(lay_rel_kernel, dim3(G), dim3(B), 0, st, skeys.p, schild.p, S.p, cstart.p, (uint32_t)P, acc[0].p);
+    hipLaunchKernelGGL(lay_rel_kernel, dim3(G), dim3(B), 0, st, skeys.get(), schild.get(), S.get(), cstart.get(), (uint32_t)P, acc[0].get());
     HIP_TRY(hipGetLastError());
     int cur = 0;
     if (jump_all(acc, &cur)) return 1;
     skeys.reset(); schild.reset(); S.reset(); cstart.reset();
     anc[0].reset(); anc[1].reset(); acc[cur ^ 1].reset();
-    if (order.alloc(P)) return 1;
-    HIP_TRY(hipMemsetAsync(order.p, 0xFF, P * 4, st));
-    hipLaunchKernelGGL(lay_order_kernel, dim3(G), dim3(B), 0, st, acc[cur].p, (uint32_t)P, order.p, flags.p + 1);
+    if (order.alloc(std::max<size_t>(P, 1))) return 1;
+    HIP_TRY(hipMemsetAsync(order.get(), 0xFF, P * 4, st));
+    hipLaunchKernelGGL(lay_order_kernel, dim3(G), dim3(B), 0, st, acc[cur].get(), (uint32_t)P, order.get(), flags.get() + 1);
     phase("device: DFS pre-order");
 
     // ---- DFS-ordered node arrays
-    HIP_TRY(hipMalloc((void**)&db->k0in, std::max<uint64_t>(P, 1) * 8));
-    HIP_TRY(hipMalloc((void**)&db->nl, std::max<uint64_t>(P, 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->parent, std::max<uint64_t>(P, 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->w, (P + 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->dflag, std::max<uint64_t>(P, 1) * 2));
-    HIP_TRY(hipMalloc((void**)&db->sub_end, std::max<uint64_t>(P, 1) * 4));
-    DevTmp<LayStats> d_stats;
+    DEV_ALLOC(db->k0in, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->nl, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->parent, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->w, P + 1);
+    DEV_ALLOC(db->dflag, std::max<uint64_t>(P, 1));
+    DEV_ALLOC(db->sub_end, std::max<uint64_t>(P, 1));
+    DevBuf<LayStats> d_stats;
     if (d_stats.alloc(1)) return 1;
-    HIP_TRY(hipMemsetAsync(d_stats.p, 0, sizeof(LayStats), st));
+    HIP_TRY(hipMemsetAsync(d_stats.get(), 0, sizeof(LayStats), st));
     if (!sel) {
         // the checksum sum_p w_p C(n_p, 2) is defined on the full 64-bit counts
-        if (d_wfull.alloc(P)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_wfull.p, v->num_kmers, P * 8, hipMemcpyHostToDevice, st));
+        if (d_wfull.alloc(std::max<size_t>(P, 1))) return 1;
+        HIP_TRY(hipMemcpyAsync(d_wfull.get(), v->num_kmers, P * 8, hipMemcpyHostToDevice, st));
         h2d_bytes += P * 8;
     }
-    hipLaunchKernelGGL(lay_gather_kernel, dim3(std::min<unsigned>(G1, 2048u)), dim3(B), 0, st, order.p, acc[cur].p, dep[dcur].p, cnt.p, size.p, d_parent.p, d_ll.p, d_last.p, d_n.p, d_nbits.p, d_w.p,
-                       d_wfull.p, (uint32_t)P, db->short_max_ids, db->k0in, db->nl, db->parent, db->w, db->dflag, db->sub_end, d_stats.p);
+    hipLaunchKernelGGL(lay_gather_kernel, dim3(std::min<unsigned>(G1, 2048u)), dim3(B), 0, st, order.get(), acc[cur].get(), dep[dcur].get(), cnt.get(), size.get(), d_parent.get(), d_ll.get(), d_last.get(), d_n.get(), d_nbits.get(), d_w.get(),
+                       d_wfull.get(), (uint32_t)P, db->short_max_ids, db->k0in, db->nl, db->parent, db->w, db->dflag, db->sub_end, d_stats.get());
     HIP_TRY(hipGetLastError());
     LayStats hs{};
     uint32_t hflags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(&hs, d_stats.p, sizeof hs, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hflags, flags.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hs, d_stats.get(), sizeof hs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hflags, flags.get(), 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (hflags[1]) return kmdb_set_error("kmdb_db_upload: pattern tree is not a forest");
     if (qshard) {
         if (qs_slots) {
-            hipLaunchKernelGGL(lay_slots_to_dfs_kernel, dim3((unsigned)std::min<uint64_t>((qs_slots + 255) / 256, 8192)), dim3(256), 0, st, db->slots, qs_slots, acc[cur].p, (uint32_t)P);
+            hipLaunchKernelGGL(lay_slots_to_dfs_kernel, dim3((unsigned)std::min<uint64_t>((qs_slots + 255) / 256, 8192)), dim3(256), 0, st, db->slots, qs_slots, acc[cur].get(), (uint32_t)P);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(st));
         }
     } else if (with_hashtables && v->n_buckets) {
         // pid -> DFS index for the hash lookups of new2all
-        HIP_TRY(hipMalloc((void**)&db->pid2dfs, std::max<uint64_t>(P, 1) * 4));
-        hipLaunchKernelGGL(lay_pid2dfs_kernel, dim3(G), dim3(B), 0, st, acc[cur].p, (uint32_t)P, db->pid2dfs);
+        DEV_ALLOC(db->pid2dfs, std::max<uint64_t>(P, 1));
+        hipLaunchKernelGGL(lay_pid2dfs_kernel, dim3(G), dim3(B), 0, st, acc[cur].get(), (uint32_t)P, db->pid2dfs);
         HIP_TRY(hipStreamSynchronize(st));
     }
     d_wfull.reset(); d_ll.reset(); d_last.reset(); d_n.reset(); d_w.reset(); size.reset(); cnt.reset(); dep[dcur].reset(); d_parent.reset();
@@ -580,25 +572,25 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
 
     // ---- streams re-packed in DFS order
     {
-        DevTmp<uint32_t> nb_dfs;
-        DevTmp<uint64_t> srcpos, dstpos;
-        if (nb_dfs.alloc(P) || srcpos.alloc(P + 1) || dstpos.alloc(P + 1)) return 1;
-        hipLaunchKernelGGL(lay_nbits_dfs_kernel, dim3(G), dim3(B), 0, st, db->k0in, (uint32_t)P, nb_dfs.p);
-        rocprim::transform_iterator<uint32_t*, U32toU64, uint64_t> it_src(d_nbits.p, U32toU64()), it_dst(nb_dfs.p, U32toU64());
+        DevBuf<uint32_t> nb_dfs;
+        DevBuf<uint64_t> srcpos, dstpos;
+        if (nb_dfs.alloc(std::max<size_t>(P, 1)) || srcpos.alloc(P + 1) || dstpos.alloc(P + 1)) return 1;
+        hipLaunchKernelGGL(lay_nbits_dfs_kernel, dim3(G), dim3(B), 0, st, db->k0in, (uint32_t)P, nb_dfs.get());
+        rocprim::transform_iterator<uint32_t*, U32toU64, uint64_t> it_src(d_nbits.get(), U32toU64()), it_dst(nb_dfs.get(), U32toU64());
         size_t tb = 0;
-        HIP_TRY(prim::exclusive_sum(nullptr, tb, it_src, srcpos.p, (int)P, st));
-        DevTmp<unsigned char> tmp;
-        if (tmp.alloc(tb)) return 1;
-        HIP_TRY(prim::exclusive_sum(tmp.p, tb, it_src, srcpos.p, (int)P, st));
-        HIP_TRY(prim::exclusive_sum(tmp.p, tb, it_dst, dstpos.p, (int)P, st));
-        HIP_TRY(hipMalloc((void**)&db->bits, n_bit_words * 8));
+        HIP_TRY(prim::exclusive_sum(nullptr, tb, it_src, srcpos.get(), (int)P, st));
+        DevBuf<unsigned char> tmp;
+        if (tmp.alloc(std::max<size_t>(tb, 1))) return 1;
+        HIP_TRY(prim::exclusive_sum(tmp.get(), tb, it_src, srcpos.get(), (int)P, st));
+        HIP_TRY(prim::exclusive_sum(tmp.get(), tb, it_dst, dstpos.get(), (int)P, st));
+        DEV_ALLOC(db->bits, n_bit_words);
         HIP_TRY(hipMemsetAsync(db->bits, 0, n_bit_words * 8, st));
         db->n_bit_words = n_bit_words;
-        HIP_TRY(hipMalloc((void**)&db->blkbase, ((P + 255) / 256 + 1) * 8));
-        HIP_TRY(hipMalloc((void**)&db->bitrel, std::max<uint64_t>(P, 1) * 4));
-        hipLaunchKernelGGL(lay_blkbase_kernel, dim3(G), dim3(B), 0, st, dstpos.p, (uint32_t)P, db->blkbase, db->bitrel);
-        hipLaunchKernelGGL(lay_copy_bits_kernel, dim3(G), dim3(B), 0, st, order.p, srcpos.p, dstpos.p, db->k0in, d_src.p, (uint32_t)P,
-                           (unsigned long long*)db->bits);
+        DEV_ALLOC(db->blkbase, (P + 255) / 256 + 1);
+        DEV_ALLOC(db->bitrel, std::max<uint64_t>(P, 1));
+        hipLaunchKernelGGL(lay_blkbase_kernel, dim3(G), dim3(B), 0, st, dstpos.get(), (uint32_t)P, db->blkbase, db->bitrel);
+        hipLaunchKernelGGL(lay_copy_bits_kernel, dim3(G), dim3(B), 0, st, order.get(), srcpos.get(), dstpos.get(), db->k0in, d_src.get(), (uint32_t)P,
+                           (unsigned long long*)db->bits.get());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -616,29 +608,29 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     db->nseg_nodes = 2048;
     if (const char* e = getenv("KMDB_NSEG")) if (*e) db->nseg_nodes = (uint32_t)std::max<uint64_t>(64, strtoull(e, nullptr, 10) / 64 * 64);
     db->n_nsegs = (uint32_t)((P + db->nseg_nodes - 1) / db->nseg_nodes);
-    HIP_TRY(hipMalloc((void**)&db->nseg_anc, std::max<size_t>((size_t)db->n_nsegs * db->chain_cap, 1) * 4));
-    HIP_TRY(hipMalloc((void**)&db->nseg_anc_n, std::max<size_t>(db->n_nsegs, 1) * 4));
+    DEV_ALLOC(db->nseg_anc, std::max<size_t>((size_t)db->n_nsegs * db->chain_cap, 1));
+    DEV_ALLOC(db->nseg_anc_n, std::max<size_t>(db->n_nsegs, 1));
     if (db->n_nsegs)
         hipLaunchKernelGGL(lay_seg_anc_kernel, dim3((db->n_nsegs + 63) / 64), dim3(64), 0, st, db->parent, db->dflag, (uint32_t)P, db->nseg_nodes, db->n_nsegs,
                            db->chain_cap, db->nseg_anc, db->nseg_anc_n);
     db->n_long = hs.n_long;
     if (hs.n_long) {
-        DevTmp<uint32_t> sel, lk, lk2, nsel;
-        if (sel.alloc(hs.n_long + 1) || lk.alloc(hs.n_long) || lk2.alloc(hs.n_long) || nsel.alloc(1)) return 1;
-        HIP_TRY(hipMalloc((void**)&db->long_nodes, (size_t)hs.n_long * 4));
+        DevBuf<uint32_t> sel, lk, lk2, nsel;
+        if (sel.alloc(hs.n_long + 1) || lk.alloc(std::max<size_t>(hs.n_long, 1)) || lk2.alloc(std::max<size_t>(hs.n_long, 1)) || nsel.alloc(1)) return 1;
+        DEV_ALLOC(db->long_nodes, (size_t)hs.n_long);
         rocprim::counting_iterator<uint32_t> first(0u);
         size_t tb = 0;
-        HIP_TRY(prim::select_if(nullptr, tb, first, sel.p, nsel.p, (int)P, LongNodePred{db->k0in, db->short_max_ids}, st));
-        DevTmp<unsigned char> tmp;
-        if (tmp.alloc(tb)) return 1;
-        HIP_TRY(prim::select_if(tmp.p, tb, first, sel.p, nsel.p, (int)P, LongNodePred{db->k0in, db->short_max_ids}, st));
-        hipLaunchKernelGGL(lay_long_keys_kernel, dim3((hs.n_long + 255) / 256), dim3(256), 0, st, db->k0in, sel.p, hs.n_long, lk.p);
+        HIP_TRY(prim::select_if(nullptr, tb, first, sel.get(), nsel.get(), (int)P, LongNodePred{db->k0in, db->short_max_ids}, st));
+        DevBuf<unsigned char> tmp;
+        if (tmp.alloc(std::max<size_t>(tb, 1))) return 1;
+        HIP_TRY(prim::select_if(tmp.get(), tb, first, sel.get(), nsel.get(), (int)P, LongNodePred{db->k0in, db->short_max_ids}, st));
+        hipLaunchKernelGGL(lay_long_keys_kernel, dim3((hs.n_long + 255) / 256), dim3(256), 0, st, db->k0in, sel.get(), hs.n_long, lk.get());
         // most work first; the sort is stable, so equal work keeps ascending DFS order
         size_t tb2 = 0;
-        HIP_TRY(prim::sort_pairs_desc(nullptr, tb2, lk.p, lk2.p, sel.p, db->long_nodes, (int)hs.n_long, 0, 32, st));
-        DevTmp<unsigned char> tmp2;
-        if (tmp2.alloc(tb2)) return 1;
-        HIP_TRY(prim::sort_pairs_desc(tmp2.p, tb2, lk.p, lk2.p, sel.p, db->long_nodes, (int)hs.n_long, 0, 32, st));
+        HIP_TRY(prim::sort_pairs_desc(nullptr, tb2, lk.get(), lk2.get(), sel.get(), db->long_nodes.get(), (int)hs.n_long, 0, 32, st));
+        DevBuf<unsigned char> tmp2;
+        if (tmp2.alloc(std::max<size_t>(tb2, 1))) return 1;
+        HIP_TRY(prim::sort_pairs_desc(tmp2.get(), tb2, lk.get(), lk2.get(), sel.get(), db->long_nodes.get(), (int)hs.n_long, 0, 32, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     HIP_TRY(hipStreamSynchronize(st));

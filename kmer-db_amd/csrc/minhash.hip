@@ -21,6 +21,7 @@
 //            words sample by sample, and the per-sample offsets.
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
+#include "dev_mem.h"
 
 #include <hip/hip_runtime.h>
 #include "prim.h"
@@ -179,33 +180,10 @@ __global__ void mh_sample_offsets_kernel(const uint32_t* __restrict__ sid, const
     off[s] = hscan[lo];                            // hscan has n + 1 entries
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    hipError_t alloc(size_t b, uint64_t* account) {
-        bytes = std::max<size_t>(b, 16);
-        if (account) *account += bytes;
-        return hipMalloc(&p, bytes);
-    }
-    template <class T> T* as() { return (T*)p; }
-};
-struct Ev {
-    hipEvent_t e = nullptr;
-    ~Ev() { if (e) (void)hipEventDestroy(e); }
-};
 
 thread_local kmdb_minhash_stats g_stats;
 
 }  // namespace
-
-#define MH_TRY(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
 
 // bases per piece (one longer sample still goes alone).  At fraction 1 the device holds about 42 bytes per base, and the kept
 // words of a piece — at most its bases — stay below 2^31, the size rocPRIM's sorts are given as an int here.
@@ -241,102 +219,102 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
     const uint64_t L = soff[n];
     const uint64_t n_tiles = (L + MH_T - 1) / MH_T;
     uint64_t scratch = 0;
-    DevBuf d_text, d_soff, d_cnt, d_off, d_kA, d_kB, d_sA, d_sB, d_head, d_hscan, d_uniq, d_uoff, d_tmp;
-    Ev ev[7];
-    for (auto& e : ev) MH_TRY(hipEventCreate(&e.e));
-    MH_TRY(hipEventRecord(ev[0].e, st));
+    DevBuf<void> d_text, d_soff, d_cnt, d_off, d_kA, d_kB, d_sA, d_sB, d_head, d_hscan, d_uniq, d_uoff, d_tmp;
+    DevEvent ev[7];
+    for (auto& e : ev) if (e.create()) return 1;
+    HIP_TRY(hipEventRecord(ev[0], st));
     const size_t text_bytes = MH_PAD + n_tiles * MH_T;
-    MH_TRY(d_text.alloc(text_bytes, &scratch));
-    MH_TRY(d_soff.alloc((n + 1) * 8, &scratch));
-    MH_TRY(d_cnt.alloc((n_tiles + 1) * 4, &scratch));
-    MH_TRY(d_off.alloc((n_tiles + 1) * 4, &scratch));
-    MH_TRY(d_uoff.alloc((n + 1) * 8, &scratch));
-    MH_TRY(hipMemsetAsync(d_text.p, '\n', text_bytes, st));
+    DEV_ALLOC_BYTES(d_text, text_bytes); scratch += d_text.bytes();
+    DEV_ALLOC_BYTES(d_soff, (n + 1) * 8); scratch += d_soff.bytes();
+    DEV_ALLOC_BYTES(d_cnt, (n_tiles + 1) * 4); scratch += d_cnt.bytes();
+    DEV_ALLOC_BYTES(d_off, (n_tiles + 1) * 4); scratch += d_off.bytes();
+    DEV_ALLOC_BYTES(d_uoff, (n + 1) * 8); scratch += d_uoff.bytes();
+    HIP_TRY(hipMemsetAsync(d_text.get(), '\n', text_bytes, st));
     for (size_t s = 0; s < n; ++s)
-        if (seq_lens[s]) MH_TRY(hipMemcpyAsync(d_text.as<char>() + MH_PAD + soff[s], seqs[s], seq_lens[s], hipMemcpyHostToDevice, st));
-    MH_TRY(hipMemcpyAsync(d_soff.p, soff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    MH_TRY(hipMemsetAsync(d_cnt.p, 0, (n_tiles + 1) * 4, st));
-    MH_TRY(hipEventRecord(ev[1].e, st));
+        if (seq_lens[s]) HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_text.get()) + MH_PAD + soff[s], seqs[s], seq_lens[s], hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_soff.get(), soff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_cnt.get(), 0, (n_tiles + 1) * 4, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
     MhParams p = proto;
-    p.text = d_text.as<unsigned char>(); p.map = d_map; p.soff = d_soff.as<uint64_t>(); p.n_samples = (uint32_t)n;
+    p.text = static_cast<unsigned char*>(d_text.get()); p.map = d_map; p.soff = static_cast<uint64_t*>(d_soff.get()); p.n_samples = (uint32_t)n;
     // pass 1: the tiles' counts; their scan: every tile's offset and, in the entry behind the last tile, the total
-    hipLaunchKernelGGL(mh_extract_kernel<false>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, d_cnt.as<uint32_t>(), (const uint32_t*)nullptr,
+    hipLaunchKernelGGL(mh_extract_kernel<false>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, static_cast<uint32_t*>(d_cnt.get()), (const uint32_t*)nullptr,
                        (unsigned long long*)nullptr, (uint32_t*)nullptr);
-    MH_TRY(hipGetLastError());
-    MH_TRY(hipEventRecord(ev[2].e, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[2], st));
     size_t tb0 = 0;
-    MH_TRY(prim::exclusive_sum(nullptr, tb0, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n_tiles + 1, st));
-    MH_TRY(d_tmp.alloc(tb0, &scratch));
-    MH_TRY(prim::exclusive_sum(d_tmp.p, tb0, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n_tiles + 1, st));
+    HIP_TRY(prim::exclusive_sum(nullptr, tb0, static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_off.get()), n_tiles + 1, st));
+    DEV_ALLOC_BYTES(d_tmp, tb0); scratch += d_tmp.bytes();
+    HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb0, static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_off.get()), n_tiles + 1, st));
     uint32_t kept32 = 0;
-    MH_TRY(hipMemcpyAsync(&kept32, d_off.as<uint32_t>() + n_tiles, 4, hipMemcpyDeviceToHost, st));
-    MH_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&kept32, static_cast<uint32_t*>(d_off.get()) + n_tiles, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint64_t kept = kept32;
     if (kept > L) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (more kept words than positions)");
-    MH_TRY(hipEventRecord(ev[3].e, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
     uint64_t n_unique = 0;
     std::vector<uint64_t> uoff(n + 1, 0);
     if (kept) {
-        MH_TRY(d_kA.alloc(kept * 8, &scratch)); MH_TRY(d_kB.alloc(kept * 8, &scratch));
-        MH_TRY(d_sA.alloc(kept * 4, &scratch)); MH_TRY(d_sB.alloc(kept * 4, &scratch));
-        MH_TRY(d_head.alloc((kept + 1) * 4, &scratch)); MH_TRY(d_hscan.alloc((kept + 1) * 4, &scratch));
-        unsigned long long *kA = d_kA.as<unsigned long long>(), *kB = d_kB.as<unsigned long long>();
-        uint32_t *sA = d_sA.as<uint32_t>(), *sB = d_sB.as<uint32_t>();
+        DEV_ALLOC_BYTES(d_kA, kept * 8); scratch += d_kA.bytes(); DEV_ALLOC_BYTES(d_kB, kept * 8); scratch += d_kB.bytes();
+        DEV_ALLOC_BYTES(d_sA, kept * 4); scratch += d_sA.bytes(); DEV_ALLOC_BYTES(d_sB, kept * 4); scratch += d_sB.bytes();
+        DEV_ALLOC_BYTES(d_head, (kept + 1) * 4); scratch += d_head.bytes(); DEV_ALLOC_BYTES(d_hscan, (kept + 1) * 4); scratch += d_hscan.bytes();
+        unsigned long long *kA = static_cast<unsigned long long*>(d_kA.get()), *kB = static_cast<unsigned long long*>(d_kB.get());
+        uint32_t *sA = static_cast<uint32_t*>(d_sA.get()), *sB = static_cast<uint32_t*>(d_sB.get());
         // pass 2: the same extraction, the kept words written at tile offset + rank
-        hipLaunchKernelGGL(mh_extract_kernel<true>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, (uint32_t*)nullptr, (const uint32_t*)d_off.as<uint32_t>(), kA, sA);
-        MH_TRY(hipGetLastError());
-        MH_TRY(hipEventRecord(ev[4].e, st));
+        hipLaunchKernelGGL(mh_extract_kernel<true>, dim3((unsigned)n_tiles), dim3(MH_THREADS), 0, st, p, (uint32_t*)nullptr, (const uint32_t*)static_cast<uint32_t*>(d_off.get()), kA, sA);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[4], st));
         const unsigned blocks = (unsigned)((kept + 255) / 256);
         const int kbits = (int)std::min<uint32_t>(64u, p.bits * p.k + p.widen);
         int sbits = 1;
         while (sbits < 32 && (1ull << sbits) < n) ++sbits;          // the sample ids in use: only those bits are sorted
         size_t tb1 = 0, tb2 = 0, tb3 = 0;
-        MH_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
-        MH_TRY(prim::sort_pairs(nullptr, tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));
-        MH_TRY(prim::exclusive_sum(nullptr, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(kept + 1), st));
-        DevBuf d_tmp2;
-        MH_TRY(d_tmp2.alloc(std::max(tb1, std::max(tb2, tb3)), &scratch));
-        MH_TRY(prim::sort_pairs(d_tmp2.p, tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
-        MH_TRY(prim::sort_pairs(d_tmp2.p, tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));     // stable: the words stay ascending inside a sample
-        MH_TRY(hipEventRecord(ev[5].e, st));
-        MH_TRY(hipMemsetAsync(d_head.p, 0, (kept + 1) * 4, st));
-        hipLaunchKernelGGL(mh_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, sA, kept, d_head.as<uint32_t>());
-        MH_TRY(prim::exclusive_sum(d_tmp2.p, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(kept + 1), st));
+        HIP_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
+        HIP_TRY(prim::sort_pairs(nullptr, tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));
+        HIP_TRY(prim::exclusive_sum(nullptr, tb3, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), (int)(kept + 1), st));
+        DevBuf<void> d_tmp2;
+        DEV_ALLOC_BYTES(d_tmp2, std::max(tb1, std::max(tb2, tb3))); scratch += d_tmp2.bytes();
+        HIP_TRY(prim::sort_pairs(d_tmp2.get(), tb1, kA, kB, sA, sB, (int)kept, 0, kbits, st));
+        HIP_TRY(prim::sort_pairs(d_tmp2.get(), tb2, sB, sA, kB, kA, (int)kept, 0, sbits, st));     // stable: the words stay ascending inside a sample
+        HIP_TRY(hipEventRecord(ev[5], st));
+        HIP_TRY(hipMemsetAsync(d_head.get(), 0, (kept + 1) * 4, st));
+        hipLaunchKernelGGL(mh_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, sA, kept, static_cast<uint32_t*>(d_head.get()));
+        HIP_TRY(prim::exclusive_sum(d_tmp2.get(), tb3, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), (int)(kept + 1), st));
         uint32_t nu32 = 0;
-        MH_TRY(hipMemcpyAsync(&nu32, d_hscan.as<uint32_t>() + kept, 4, hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(mh_sample_offsets_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, sA, d_hscan.as<uint32_t>(), kept, (uint32_t)n,
-                           d_uoff.as<uint64_t>());
-        MH_TRY(hipGetLastError());
-        MH_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(&nu32, static_cast<uint32_t*>(d_hscan.get()) + kept, 4, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(mh_sample_offsets_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, sA, static_cast<uint32_t*>(d_hscan.get()), kept, (uint32_t)n,
+                           static_cast<uint64_t*>(d_uoff.get()));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
         n_unique = nu32;
         if (n_unique > kept) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (more unique words than kept words)");
-        MH_TRY(d_uniq.alloc(n_unique * 8, &scratch));
-        hipLaunchKernelGGL(mh_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), kept, d_uniq.as<uint64_t>());
-        MH_TRY(hipGetLastError());
-        MH_TRY(hipMemcpyAsync(uoff.data(), d_uoff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        DEV_ALLOC_BYTES(d_uniq, n_unique * 8); scratch += d_uniq.bytes();
+        hipLaunchKernelGGL(mh_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), kept, static_cast<uint64_t*>(d_uniq.get()));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(uoff.data(), d_uoff.get(), (n + 1) * 8, hipMemcpyDeviceToHost, st));
         if (!sink) {
             uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_unique) * 8);
             if (!grown) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: out of host memory");
             *kmers = grown;
-            if (n_unique) MH_TRY(hipMemcpyAsync(grown + *total, d_uniq.p, n_unique * 8, hipMemcpyDeviceToHost, st));
+            if (n_unique) HIP_TRY(hipMemcpyAsync(grown + *total, d_uniq.get(), n_unique * 8, hipMemcpyDeviceToHost, st));
         }
-        MH_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (uoff[n] != n_unique) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: internal error (the sample offsets do not end at the unique count)");
     } else {
-        MH_TRY(hipEventRecord(ev[4].e, st));
-        MH_TRY(hipEventRecord(ev[5].e, st));
+        HIP_TRY(hipEventRecord(ev[4], st));
+        HIP_TRY(hipEventRecord(ev[5], st));
     }
-    MH_TRY(hipEventRecord(ev[6].e, st));
-    MH_TRY(hipEventSynchronize(ev[6].e));
+    HIP_TRY(hipEventRecord(ev[6], st));
+    HIP_TRY(hipEventSynchronize(ev[6]));
     if (sink) {
         // the sorts' double buffers and the flags are done with: the sink's own work gets their memory
-        for (DevBuf* b : {&d_kA, &d_kB, &d_sA, &d_sB, &d_head, &d_hscan, &d_text, &d_cnt, &d_off}) b->release();
-        if (const int rc = (*sink)(d_uniq.as<uint64_t>(), uoff.data(), n, (void*)st)) return rc;
+        dev_reset(d_kA, d_kB, d_sA, d_sB, d_head, d_hscan, d_text, d_cnt, d_off);
+        if (const int rc = (*sink)(static_cast<uint64_t*>(d_uniq.get()), uoff.data(), n, (void*)st)) return rc;
     }
     for (size_t s = 0; s < n; ++s) off[s + 1] = *total + uoff[s + 1];
     *total += n_unique;
     float ms[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 6; ++i) MH_TRY(hipEventElapsedTime(&ms[i], ev[i].e, ev[i + 1].e));
+    for (int i = 0; i < 6; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
     g_stats.pieces += 1; g_stats.bases += L - n; g_stats.kept += kept; g_stats.unique += n_unique;
     g_stats.scratch_bytes = std::max<uint64_t>(g_stats.scratch_bytes, scratch);
     g_stats.h2d_ms += ms[0]; g_stats.count_ms += ms[1]; g_stats.scan_ms += ms[2]; g_stats.write_ms += ms[3]; g_stats.sort_ms += ms[4]; g_stats.unique_ms += ms[5];
@@ -374,19 +352,19 @@ static int mh_batch(const char* who, const char* const* seqs, const size_t* seq_
         kmdbh_minhash_window(fraction, start_fraction, &p.lo, &p.hi);               // src/filter.h:38-51; the host's one definition (host_kmers.cpp)
         p.seed = 42ull ^ (uint64_t)std::ceil((double)k / 4.0);
         p.word_mask = (1ull << (p.bits * k)) - 1ull;                                // (bits * k <= 63)
-        MH_TRY(hipSetDevice(opts ? opts->device : 0));
+        HIP_TRY(hipSetDevice(opts ? opts->device : 0));
         hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t) nullptr;
-        DevBuf d_map;
-        MH_TRY(d_map.alloc(256, nullptr));
-        MH_TRY(hipMemcpyAsync(d_map.p, map, 256, hipMemcpyHostToDevice, st));
-        MH_TRY(hipStreamSynchronize(st));                                           // (`map` lives on this frame)
+        DevBuf<void> d_map;
+        DEV_ALLOC_BYTES(d_map, 256);
+        HIP_TRY(hipMemcpyAsync(d_map.get(), map, 256, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));                                           // (`map` lives on this frame)
         // samples are independent: cut the batch where the accumulated bases pass the budget
         const uint64_t budget = mh_budget();
         for (size_t s0 = 0; s0 < n_samples;) {
             size_t s1 = s0;
             uint64_t bases = 0;
             do { bases += seq_lens[s1] + 1; ++s1; } while (s1 < n_samples && bases + seq_lens[s1] + 1 <= budget && bases + seq_lens[s1] + 1 < (1ull << 31) - 2);
-            if (const int rc = mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, d_map.as<int8_t>(), st, &kmers, &total, offsets + s0, sink)) return rc;
+            if (const int rc = mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, static_cast<int8_t*>(d_map.get()), st, &kmers, &total, offsets + s0, sink)) return rc;
             s0 = s1;
         }
     }

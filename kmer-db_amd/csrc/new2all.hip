@@ -439,70 +439,58 @@ __global__ __launch_bounds__(N2_THREADS) void n2a_walk_kernel(const unsigned lon
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <class T> T* as() { return (T*)p; }
-};
 
 }  // namespace
 
-#define N2_TRY(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
-
 struct N2aU32toU64 { __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; } };
 // the handle's run index (false: this handle does without one — no memory for it — and the walk decodes the gamma streams as before)
-static bool n2a_run_index(const kmdb_engine_view& e, hipStream_t st) {
-    if (*e.rl_ofs && *e.rl_runs && *e.rl_node) return true;
-    if (*e.rl_tried || !e.P || getenv("KMDB_N2A_NO_RUNS")) return false;
-    *e.rl_tried = true;
+static bool n2a_build_run_index(const kmdb_engine_view& e, hipStream_t st) {
     const uint32_t P = (uint32_t)e.P;
-    uint32_t *cnt = nullptr, *ofs = nullptr, *runs = nullptr;
-    void* tmp = nullptr;
-    auto fail = [&]() { (void)hipGetLastError(); for (void* p : {(void*)cnt, (void*)ofs, (void*)runs, tmp}) if (p) (void)hipFree(p); return false; };
-    if (hipMalloc((void**)&cnt, ((size_t)P + 1) * 4) != hipSuccess || hipMalloc((void**)&ofs, ((size_t)P + 1) * 4) != hipSuccess) return fail();
+    // (built in locals: the handle gets the index when it is complete, anything less frees itself)
+    DevBuf<uint32_t> cnt, ofs, runs;
+    DevBuf<uint4> nodes;
+    DevBuf<void> tmp;
+    if (cnt.alloc((size_t)P + 1) || ofs.alloc((size_t)P + 1)) return false;
     hipLaunchKernelGGL((n2a_runs_kernel<false>), dim3((P + 1 + 255) / 256), dim3(256), 0, st, e.meta, e.bitpos, e.bits, P, (uint32_t)e.N, cnt, (const uint32_t*)nullptr, (uint32_t*)nullptr);
     size_t tb = 0;
-    if (prim::exclusive_sum(nullptr, tb, cnt, ofs, (int)(P + 1), st) != hipSuccess || hipMalloc(&tmp, std::max<size_t>(tb, 16)) != hipSuccess) return fail();
-    if (prim::exclusive_sum(tmp, tb, cnt, ofs, (int)(P + 1), st) != hipSuccess) return fail();
+    if (prim::exclusive_sum(nullptr, tb, cnt.get(), ofs.get(), (int)(P + 1), st) != hipSuccess || tmp.alloc(std::max<size_t>(tb, 16))) return false;
+    if (prim::exclusive_sum(tmp, tb, cnt.get(), ofs.get(), (int)(P + 1), st) != hipSuccess) return false;
     // the offsets are 32 bits wide, and the number of runs is bounded by the sum of the local lists' lengths over up to 2^31 patterns, not
     // by the sample count: the counts are summed in 64 bits first, and a database with 2^32 runs or more does without the index
     // (a wrapped total would have under-allocated `runs`)
     {
-        unsigned long long* d_sum = nullptr;
-        void* tmp2 = nullptr;
+        DevBuf<unsigned long long> d_sum;
+        DevBuf<void> tmp2;
         size_t tb2 = 0;
         rocprim::transform_iterator<uint32_t*, N2aU32toU64, unsigned long long> it(cnt, N2aU32toU64());
         unsigned long long h_sum = 0;
-        bool ok = hipMalloc((void**)&d_sum, 8) == hipSuccess && prim::sum(nullptr, tb2, it, d_sum, (int)(P + 1), st) == hipSuccess &&
-                  hipMalloc(&tmp2, std::max<size_t>(tb2, 16)) == hipSuccess && prim::sum(tmp2, tb2, it, d_sum, (int)(P + 1), st) == hipSuccess &&
-                  hipMemcpyAsync(&h_sum, d_sum, 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-        if (d_sum) (void)hipFree(d_sum);
-        if (tmp2) (void)hipFree(tmp2);
-        if (!ok || h_sum >= (1ull << 32)) return fail();
+        const bool ok = !d_sum.alloc(1) && prim::sum(nullptr, tb2, it, d_sum.get(), (int)(P + 1), st) == hipSuccess &&
+                        !tmp2.alloc(std::max<size_t>(tb2, 16)) && prim::sum(tmp2, tb2, it, d_sum.get(), (int)(P + 1), st) == hipSuccess &&
+                        hipMemcpyAsync(&h_sum, d_sum, 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+        if (!ok || h_sum >= (1ull << 32)) return false;
     }
     uint32_t total = 0;
-    if (hipMemcpyAsync(&total, ofs + P, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail();
+    if (hipMemcpyAsync(&total, ofs + P, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)total * 4 + (size_t)P * sizeof(uint4) + (1ull << 30) > free_b / 2) return fail();
-    if (hipMalloc((void**)&runs, std::max<size_t>((size_t)total, 1) * 4) != hipSuccess) return fail();
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)total * 4 + (size_t)P * sizeof(uint4) + (1ull << 30) > free_b / 2) return false;
+    if (runs.alloc(std::max<size_t>((size_t)total, 1))) return false;
     hipLaunchKernelGGL((n2a_runs_kernel<true>), dim3((P + 1 + 255) / 256), dim3(256), 0, st, e.meta, e.bitpos, e.bits, P, (uint32_t)e.N, (uint32_t*)nullptr, (const uint32_t*)ofs, runs);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail();
-    uint4* nodes = nullptr;
-    if (hipMalloc((void**)&nodes, (size_t)P * sizeof(uint4)) != hipSuccess) return fail();
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
+    if (nodes.alloc((size_t)P)) return false;
     hipLaunchKernelGGL(n2a_nodes_kernel, dim3((P + 255) / 256), dim3(256), 0, st, e.meta, e.parent, e.sub_end, (const uint32_t*)ofs, P, nodes);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(nodes); return fail(); }
-    (void)hipFree(cnt); (void)hipFree(tmp);
-    *e.rl_ofs = ofs; *e.rl_runs = runs; *e.rl_node = nodes;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
+    *e.rl_ofs = std::move(ofs); *e.rl_runs = std::move(runs); *e.rl_node = std::move(nodes);
     *e.device_bytes += ((uint64_t)P + 1) * 4 + (uint64_t)total * 4 + (uint64_t)P * sizeof(uint4);
     if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] new2all: run index of %u nodes, %u runs (%.2f GB)\n", P, total, (((double)P + 1) * 4 + (double)total * 4) / 1e9);
     return true;
+}
+static bool n2a_run_index(const kmdb_engine_view& e, hipStream_t st) {
+    if (*e.rl_ofs && *e.rl_runs && *e.rl_node) return true;
+    if (*e.rl_tried || !e.P || getenv("KMDB_N2A_NO_RUNS")) return false;
+    *e.rl_tried = true;
+    if (n2a_build_run_index(e, st)) return true;
+    (void)hipGetLastError();
+    return false;
 }
 
 // probe / sort / count / walk over a batch whose k-mers (sorted and unique per query, query by query) and
@@ -512,29 +500,29 @@ static bool n2a_run_index(const kmdb_engine_view& e, hipStream_t st) {
 static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, const uint64_t* d_kmers, const uint64_t* d_qoff_p,
                    size_t total, size_t nq, uint32_t* out_dense, uint32_t* out_dev = nullptr) {
     const uint64_t N = e.N;
-    DevBuf d_keys, d_keys2, d_uniq, d_cnt, d_csum, d_nruns, d_qstart, d_sim, d_tmp;
-    N2_TRY(d_keys.alloc(total * 8));
-    N2_TRY(d_keys2.alloc(total * 8));
-    N2_TRY(d_uniq.alloc((total + 1) * 8));
-    N2_TRY(d_cnt.alloc((total + 2) * 4));
-    N2_TRY(d_csum.alloc((total + 2) * 4));
-    N2_TRY(d_nruns.alloc(16));
-    N2_TRY(d_qstart.alloc((nq + 2) * 4));
-    if (!out_dev) N2_TRY(d_sim.alloc(nq * N * 4));
-    uint32_t* const sim = out_dev ? out_dev : d_sim.as<uint32_t>();
+    DevBuf<void> d_keys, d_keys2, d_uniq, d_cnt, d_csum, d_nruns, d_qstart, d_sim, d_tmp;
+    DEV_ALLOC_BYTES(d_keys, total * 8);
+    DEV_ALLOC_BYTES(d_keys2, total * 8);
+    DEV_ALLOC_BYTES(d_uniq, (total + 1) * 8);
+    DEV_ALLOC_BYTES(d_cnt, (total + 2) * 4);
+    DEV_ALLOC_BYTES(d_csum, (total + 2) * 4);
+    DEV_ALLOC_BYTES(d_nruns, 16);
+    DEV_ALLOC_BYTES(d_qstart, (nq + 2) * 4);
+    if (!out_dev) DEV_ALLOC_BYTES(d_sim, nq * N * 4);
+    uint32_t* const sim = out_dev ? out_dev : static_cast<uint32_t*>(d_sim.get());
     size_t tb_sort = 0, tb_rle = 0, tb_scan = 0;
-    N2_TRY(prim::sort_keys(nullptr, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
+    HIP_TRY(prim::sort_keys(nullptr, tb_sort, static_cast<unsigned long long*>(d_keys.get()), static_cast<unsigned long long*>(d_keys2.get()),
                                              (int)total, 0, 64, st));
-    N2_TRY(prim::run_length_encode(nullptr, tb_rle, d_keys2.as<unsigned long long>(), d_uniq.as<unsigned long long>(),
-                                                 d_cnt.as<uint32_t>(), d_nruns.as<uint32_t>(), (int)total, st));
-    N2_TRY(prim::exclusive_sum(nullptr, tb_scan, d_cnt.as<uint32_t>(), d_csum.as<uint32_t>(), (int)(total + 1), st));
-    N2_TRY(d_tmp.alloc(std::max(tb_sort, std::max(tb_rle, tb_scan))));
-    if (!out_dev) N2_TRY(hipMemsetAsync(d_sim.p, 0, std::max<uint64_t>(nq * N * 4, 4), st));
+    HIP_TRY(prim::run_length_encode(nullptr, tb_rle, static_cast<unsigned long long*>(d_keys2.get()), static_cast<unsigned long long*>(d_uniq.get()),
+                                                 static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_nruns.get()), (int)total, st));
+    HIP_TRY(prim::exclusive_sum(nullptr, tb_scan, static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_csum.get()), (int)(total + 1), st));
+    DEV_ALLOC_BYTES(d_tmp, std::max(tb_sort, std::max(tb_rle, tb_scan)));
+    if (!out_dev) HIP_TRY(hipMemsetAsync(d_sim.get(), 0, std::max<uint64_t>(nq * N * 4, 4), st));
 
     // the run index of the handle: made on its first new2all call (outside the call's device time, inside its wall time)
     const bool runidx = n2a_run_index(e, st);
     hipEvent_t ev0 = (hipEvent_t)e.ev[0], ev3 = (hipEvent_t)e.ev[3];
-    N2_TRY(hipEventRecord(ev0, st));
+    HIP_TRY(hipEventRecord(ev0, st));
     uint32_t nruns = 0;
     if (total) {
         const unsigned blocks = (unsigned)std::min<size_t>(65535, (total + 255) / 256);
@@ -546,21 +534,21 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
         while ((1ull << qbits) < nq) ++qbits;
         if (e.qs_count > 1)
             hipLaunchKernelGGL(n2a_probe_kernel<true>, dim3(blocks), dim3(256), 0, st, d_kmers, d_qoff_p, (uint32_t)nq, total, e.n_buckets, e.bucket_offset, e.slots,
-                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, e.qs_index, e.qs_count, d_keys.as<unsigned long long>());
+                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, e.qs_index, e.qs_count, static_cast<unsigned long long*>(d_keys.get()));
         else
             hipLaunchKernelGGL(n2a_probe_kernel<false>, dim3(blocks), dim3(256), 0, st, d_kmers, d_qoff_p, (uint32_t)nq, total, e.n_buckets, e.bucket_offset, e.slots,
-                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, 0u, 1u, d_keys.as<unsigned long long>());
-        N2_TRY(hipGetLastError());
-        N2_TRY(prim::sort_keys(d_tmp.p, tb_sort, d_keys.as<unsigned long long>(), d_keys2.as<unsigned long long>(),
+                               e.pid2dfs, e.w, pbits, (uint32_t)e.P, 0u, 1u, static_cast<unsigned long long*>(d_keys.get()));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(prim::sort_keys(d_tmp.get(), tb_sort, static_cast<unsigned long long*>(d_keys.get()), static_cast<unsigned long long*>(d_keys2.get()),
                                                  (int)total, 0, std::min(64u, pbits + qbits), st));
-        N2_TRY(hipMemsetAsync(d_cnt.p, 0, (total + 2) * 4, st));
-        N2_TRY(prim::run_length_encode(d_tmp.p, tb_rle, d_keys2.as<unsigned long long>(), d_uniq.as<unsigned long long>(),
-                                                     d_cnt.as<uint32_t>(), d_nruns.as<uint32_t>(), (int)total, st));
-        N2_TRY(hipMemcpyAsync(&nruns, d_nruns.p, 4, hipMemcpyDeviceToHost, st));
-        N2_TRY(hipStreamSynchronize(st));
-        N2_TRY(prim::exclusive_sum(d_tmp.p, tb_scan, d_cnt.as<uint32_t>(), d_csum.as<uint32_t>(), (int)(nruns + 1), st));
+        HIP_TRY(hipMemsetAsync(d_cnt.get(), 0, (total + 2) * 4, st));
+        HIP_TRY(prim::run_length_encode(d_tmp.get(), tb_rle, static_cast<unsigned long long*>(d_keys2.get()), static_cast<unsigned long long*>(d_uniq.get()),
+                                                     static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_nruns.get()), (int)total, st));
+        HIP_TRY(hipMemcpyAsync(&nruns, d_nruns.get(), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb_scan, static_cast<uint32_t*>(d_cnt.get()), static_cast<uint32_t*>(d_csum.get()), (int)(nruns + 1), st));
         hipLaunchKernelGGL(n2a_query_ranges_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st,
-                           d_uniq.as<unsigned long long>(), nruns, (uint32_t)nq, pbits, d_qstart.as<uint32_t>());
+                           static_cast<unsigned long long*>(d_uniq.get()), nruns, (uint32_t)nq, pbits, static_cast<uint32_t*>(d_qstart.get()));
         if (nruns) {
             // LDS of a workgroup: the per-query histogram (4 B per sample) + the queue of long lists (16 B per entry) + 12 B per thread
             // (scan scratch, the workgroup's stretch of the hit list)
@@ -573,8 +561,8 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
             const bool packed_nodes = getenv("KMDB_N2A_NO_NODES") == nullptr;        // (A/B: the climb reads the engine's arrays, five loads per node)
             const unsigned wblocks = (nruns + threads - 1) / threads;
 #define N2A_WALK(H, T, Q, R)                                                                                                             \
-    hipLaunchKernelGGL((n2a_walk_kernel<H, T, Q, R>), dim3(wblocks), dim3(T), (H) ? N * 4 : 0, st, d_uniq.as<unsigned long long>(),      \
-                       d_csum.as<uint32_t>(), d_qstart.as<uint32_t>(), nruns, (uint32_t)nq, e.meta, e.bitpos, e.parent, e.sub_end,       \
+    hipLaunchKernelGGL((n2a_walk_kernel<H, T, Q, R>), dim3(wblocks), dim3(T), (H) ? N * 4 : 0, st, static_cast<unsigned long long*>(d_uniq.get()),      \
+                       static_cast<uint32_t*>(d_csum.get()), static_cast<uint32_t*>(d_qstart.get()), nruns, (uint32_t)nq, e.meta, e.bitpos, e.parent, e.sub_end,       \
                        e.bits, e.ck_ofs, e.ck_bit, e.ck_id, (const uint32_t*)*e.rl_ofs, (const uint32_t*)*e.rl_runs, packed_nodes ? (const uint4*)*e.rl_node : (const uint4*)nullptr, (uint32_t)N, pbits, sim)
             if (runidx) {
                 if (threads == 1024) { if (lds_hist) N2A_WALK(true, 1024, 1024, true); else N2A_WALK(false, 1024, 1024, true); }
@@ -585,14 +573,14 @@ static int n2a_run(kmdb_db* dbh, const kmdb_engine_view& e, hipStream_t st, cons
             }
 #undef N2A_WALK
         }
-        N2_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    N2_TRY(hipEventRecord(ev3, st));
-    N2_TRY(hipEventSynchronize(ev3));
+    HIP_TRY(hipEventRecord(ev3, st));
+    HIP_TRY(hipEventSynchronize(ev3));
     float ms = 0;
-    N2_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev3));
     kmdb_engine_set_times(dbh, ms, ms);
-    if (!out_dev && nq * N) N2_TRY(hipMemcpy(out_dense, d_sim.p, nq * N * 4, hipMemcpyDeviceToHost));
+    if (!out_dev && nq * N) HIP_TRY(hipMemcpy(out_dense, d_sim.get(), nq * N * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -627,20 +615,20 @@ static int new2all_once(kmdb_db* dbh, const uint64_t* const* kmers, const size_t
     // (a query shard may own no bucket at all — more shards than buckets: its tables are empty, not missing, and every k-mer is a miss)
     if ((!e.n_buckets && e.qs_count <= 1) || !e.slots) return kmdb_set_error("kmdb_new2all_batch: database was uploaded without hashtables");
     if (nq >= (1ull << 31)) return kmdb_set_error("kmdb_new2all_batch: too many queries in one batch");
-    N2_TRY(hipSetDevice(e.device));
+    HIP_TRY(hipSetDevice(e.device));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)e.stream;
     std::vector<uint64_t> qoff(nq + 1, 0);
     for (size_t q = 0; q < nq; ++q) qoff[q + 1] = qoff[q] + counts[q];
     const size_t total = qoff[nq];
     if (total >= (1ull << 32) - 2) return kmdb_set_error("kmdb_new2all_batch: a single query of 2^32 k-mers or more is not supported");
     if (!nq) return 0;
-    DevBuf d_k, d_qoff;
-    N2_TRY(d_k.alloc(total * 8));
-    N2_TRY(d_qoff.alloc((nq + 1) * 8));
+    DevBuf<void> d_k, d_qoff;
+    DEV_ALLOC_BYTES(d_k, total * 8);
+    DEV_ALLOC_BYTES(d_qoff, (nq + 1) * 8);
     for (size_t q = 0; q < nq; ++q)
-        if (counts[q]) N2_TRY(hipMemcpyAsync(d_k.as<uint64_t>() + qoff[q], kmers[q], counts[q] * 8, hipMemcpyHostToDevice, st));
-    N2_TRY(hipMemcpyAsync(d_qoff.p, qoff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, st));
-    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
+        if (counts[q]) HIP_TRY(hipMemcpyAsync(static_cast<uint64_t*>(d_k.get()) + qoff[q], kmers[q], counts[q] * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_qoff.get(), qoff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, st));
+    return n2a_run(dbh, e, st, static_cast<uint64_t*>(d_k.get()), static_cast<uint64_t*>(d_qoff.get()), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -840,49 +828,49 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
     if (kmdbh_alphabet_table(alphabet, p.map, &p.size, &p.bits, &preserve_strand)) return kmdb_set_error("kmdb_new2all_batch_seq: unknown alphabet");
     if (k == 0 || k > 64u / p.bits - 1u) return kmdb_set_error("kmdb_new2all_batch_seq: k-mer length must be 1.." + std::to_string(64u / p.bits - 1u) + " for this alphabet (alphabet.h:37)");
     if (!nq) return 0;
-    N2_TRY(hipSetDevice(e.device));
+    HIP_TRY(hipSetDevice(e.device));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)e.stream;
     std::vector<uint64_t> soff(nq + 1, 0);
     for (size_t q = 0; q < nq; ++q) soff[q + 1] = soff[q] + seq_lens[q];
     const uint64_t L = soff[nq];
     if (L >= (1ull << 31) - 2) return kmdb_set_error("kmdb_new2all_batch_seq: a single query of 2^31 bases or more; extract its k-mers on the host (kmdbh_extract_kmers) and use kmdb_new2all_batch");
     if (nq >= (1ull << 31)) return kmdb_set_error("kmdb_new2all_batch_seq: too many queries in one batch");
-    DevBuf d_seq, d_soff, d_kmer, d_kmer2, d_qid, d_qid2, d_head, d_hscan, d_k, d_qoff, d_tmp;
-    N2_TRY(d_seq.alloc(L + 32));
-    N2_TRY(d_soff.alloc((nq + 1) * 8));
-    N2_TRY(d_kmer.alloc(L * 8)); N2_TRY(d_kmer2.alloc(L * 8));
-    N2_TRY(d_qid.alloc(L * 4)); N2_TRY(d_qid2.alloc(L * 4));
-    N2_TRY(d_qoff.alloc((nq + 1) * 8));
+    DevBuf<void> d_seq, d_soff, d_kmer, d_kmer2, d_qid, d_qid2, d_head, d_hscan, d_k, d_qoff, d_tmp;
+    DEV_ALLOC_BYTES(d_seq, L + 32);
+    DEV_ALLOC_BYTES(d_soff, (nq + 1) * 8);
+    DEV_ALLOC_BYTES(d_kmer, L * 8); DEV_ALLOC_BYTES(d_kmer2, L * 8);
+    DEV_ALLOC_BYTES(d_qid, L * 4); DEV_ALLOC_BYTES(d_qid2, L * 4);
+    DEV_ALLOC_BYTES(d_qoff, (nq + 1) * 8);
     for (size_t q = 0; q < nq; ++q)
-        if (seq_lens[q]) N2_TRY(hipMemcpyAsync(d_seq.as<char>() + soff[q], seqs[q], seq_lens[q], hipMemcpyHostToDevice, st));
-    N2_TRY(hipMemcpyAsync(d_soff.p, soff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, st));
+        if (seq_lens[q]) HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_seq.get()) + soff[q], seqs[q], seq_lens[q], hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_soff.get(), soff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> qoff(nq + 1, 0);
     size_t total = 0;
     if (L) {
         const int prefix_bits = (int)(p.bits * k) - 32;
-        p.seq = d_seq.as<char>(); p.soff = d_soff.as<uint64_t>(); p.nq = (uint32_t)nq; p.total_len = L; p.k = k;
+        p.seq = static_cast<char*>(d_seq.get()); p.soff = static_cast<uint64_t*>(d_soff.get()); p.nq = (uint32_t)nq; p.total_len = L; p.k = k;
         p.widen = prefix_bits < 8 ? (uint32_t)(8 - prefix_bits) : 0u;
         p.preserve = preserve_strand; p.subsample = fraction < 1.0;
         kmdbh_minhash_window(fraction, start_fraction, &p.lo, &p.hi);                 // src/filter.h:38-51; the host's one definition (host_kmers.cpp)
         p.quarter_len = (uint64_t)std::ceil((double)k / 4.0);
-        p.kmer = d_kmer.as<unsigned long long>(); p.qid = d_qid.as<uint32_t>();
+        p.kmer = static_cast<unsigned long long*>(d_kmer.get()); p.qid = static_cast<uint32_t*>(d_qid.get());
         hipLaunchKernelGGL(n2a_extract_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, p);
-        N2_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // the sorts ping-pong between two buffer pairs: (kA, qA) holds the positions, (kB, qB) is the other side
-        unsigned long long *kA = d_kmer.as<unsigned long long>(), *kB = d_kmer2.as<unsigned long long>();
-        uint32_t *qA = d_qid.as<uint32_t>(), *qB = d_qid2.as<uint32_t>();
+        unsigned long long *kA = static_cast<unsigned long long*>(d_kmer.get()), *kB = static_cast<unsigned long long*>(d_kmer2.get());
+        uint32_t *qA = static_cast<uint32_t*>(d_qid.get()), *qB = static_cast<uint32_t*>(d_qid2.get());
         uint64_t n = L;                                          // positions that go through the sorts
         if (e.qs_count > 1) {
             // a query shard: only the positions whose k-mer it owns (n2a_own_positions_kernel), BEFORE the sorts
-            DevBuf d_own;
-            N2_TRY(d_own.alloc(8));
-            N2_TRY(hipMemsetAsync(d_own.p, 0, 8, st));
+            DevBuf<void> d_own;
+            DEV_ALLOC_BYTES(d_own, 8);
+            HIP_TRY(hipMemsetAsync(d_own.get(), 0, 8, st));
             hipLaunchKernelGGL(n2a_own_positions_kernel, dim3((unsigned)((L + 256u * N2_OWN_ITEMS - 1) / (256u * N2_OWN_ITEMS))), dim3(256), 0, st, kA, qA, L,
-                               e.qs_index, e.qs_count, kB, qB, d_own.as<unsigned long long>());
-            N2_TRY(hipGetLastError());
+                               e.qs_index, e.qs_count, kB, qB, static_cast<unsigned long long*>(d_own.get()));
+            HIP_TRY(hipGetLastError());
             unsigned long long own = 0;
-            N2_TRY(hipMemcpyAsync(&own, d_own.p, 8, hipMemcpyDeviceToHost, st));
-            N2_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(&own, d_own.get(), 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             if (own > L) return kmdb_set_error("kmdb_new2all_batch_seq: internal error (more own positions than positions)");
             n = own;
             std::swap(kA, kB); std::swap(qA, qB);
@@ -890,43 +878,43 @@ static int new2all_seq_once(kmdb_db* dbh, const char* const* seqs, const size_t*
         if (n) {
             // (sized by the positions that go on: on a query shard the two L-sized buffer pairs above are still needed — the compaction writes
             // into the second pair, whose length is not known before it ran — but everything from here on is about 1 / qs_count of that)
-            N2_TRY(d_head.alloc((n + 1) * 4)); N2_TRY(d_hscan.alloc((n + 1) * 4));
+            DEV_ALLOC_BYTES(d_head, (n + 1) * 4); DEV_ALLOC_BYTES(d_hscan, (n + 1) * 4);
             const unsigned blocks = (unsigned)((n + 255) / 256);
             const int kbits = (int)std::min<uint32_t>(64u, p.bits * k + p.widen);
             size_t tb1 = 0, tb2 = 0, tb3 = 0;
-            N2_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
-            N2_TRY(prim::sort_pairs(nullptr, tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
-            N2_TRY(prim::exclusive_sum(nullptr, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(n + 1), st));
-            N2_TRY(d_tmp.alloc(std::max(tb1, std::max(tb2, tb3))));
-            N2_TRY(prim::sort_pairs(d_tmp.p, tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
+            HIP_TRY(prim::sort_pairs(nullptr, tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
+            HIP_TRY(prim::sort_pairs(nullptr, tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
+            HIP_TRY(prim::exclusive_sum(nullptr, tb3, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), (int)(n + 1), st));
+            DEV_ALLOC_BYTES(d_tmp, std::max(tb1, std::max(tb2, tb3)));
+            HIP_TRY(prim::sort_pairs(d_tmp.get(), tb1, kA, kB, qA, qB, (int)n, 0, kbits, st));
             // dropped positions carry query ~0: all 32 bits take part so that they sort behind every query
-            N2_TRY(prim::sort_pairs(d_tmp.p, tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
-            N2_TRY(hipMemsetAsync(d_head.p, 0, (n + 1) * 4, st));
-            hipLaunchKernelGGL(n2a_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, qA, n, d_head.as<uint32_t>());
-            N2_TRY(prim::exclusive_sum(d_tmp.p, tb3, d_head.as<uint32_t>(), d_hscan.as<uint32_t>(), (int)(n + 1), st));
+            HIP_TRY(prim::sort_pairs(d_tmp.get(), tb2, qB, qA, kB, kA, (int)n, 0, 32, st));
+            HIP_TRY(hipMemsetAsync(d_head.get(), 0, (n + 1) * 4, st));
+            hipLaunchKernelGGL(n2a_heads_kernel, dim3(blocks), dim3(256), 0, st, kA, qA, n, static_cast<uint32_t*>(d_head.get()));
+            HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb3, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), (int)(n + 1), st));
             uint32_t n_unique = 0;
-            N2_TRY(hipMemcpyAsync(&n_unique, d_hscan.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&n_unique, static_cast<uint32_t*>(d_hscan.get()) + n, 4, hipMemcpyDeviceToHost, st));
             hipLaunchKernelGGL(n2a_query_offsets_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st, qA,
-                               d_hscan.as<uint32_t>(), n, (uint32_t)nq, d_qoff.as<uint64_t>());
-            N2_TRY(hipGetLastError());
-            N2_TRY(hipStreamSynchronize(st));
+                               static_cast<uint32_t*>(d_hscan.get()), n, (uint32_t)nq, static_cast<uint64_t*>(d_qoff.get()));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));
             total = n_unique;
-            N2_TRY(d_k.alloc(total * 8));
-            hipLaunchKernelGGL(n2a_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, d_head.as<uint32_t>(),
-                               d_hscan.as<uint32_t>(), n, d_k.as<uint64_t>());
-            N2_TRY(hipGetLastError());
-            N2_TRY(hipMemcpyAsync(qoff.data(), d_qoff.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-            N2_TRY(hipStreamSynchronize(st));
+            DEV_ALLOC_BYTES(d_k, total * 8);
+            hipLaunchKernelGGL(n2a_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, static_cast<uint32_t*>(d_head.get()),
+                               static_cast<uint32_t*>(d_hscan.get()), n, static_cast<uint64_t*>(d_k.get()));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(qoff.data(), d_qoff.get(), (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
         } else {                                                 // (a shard that owns none of the batch's k-mers)
-            N2_TRY(d_k.alloc(16));
-            N2_TRY(hipMemsetAsync(d_qoff.p, 0, (nq + 1) * 8, st));
+            DEV_ALLOC_BYTES(d_k, 16);
+            HIP_TRY(hipMemsetAsync(d_qoff.get(), 0, (nq + 1) * 8, st));
         }
     } else {
-        N2_TRY(d_k.alloc(16));
-        N2_TRY(hipMemsetAsync(d_qoff.p, 0, (nq + 1) * 8, st));
+        DEV_ALLOC_BYTES(d_k, 16);
+        HIP_TRY(hipMemsetAsync(d_qoff.get(), 0, (nq + 1) * 8, st));
     }
     for (size_t q = 0; q < nq; ++q) out_kmer_counts[q] = qoff[q + 1] - qoff[q];
     // the sort buffers are not needed any more: release them before the probe pipeline allocates its own
     d_kmer.reset(); d_kmer2.reset(); d_qid2.reset(); d_head.reset(); d_hscan.reset(); d_qid.reset();
-    return n2a_run(dbh, e, st, d_k.as<uint64_t>(), d_qoff.as<uint64_t>(), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
+    return n2a_run(dbh, e, st, static_cast<uint64_t*>(d_k.get()), static_cast<uint64_t*>(d_qoff.get()), total, nq, out_is_dev ? nullptr : out, out_is_dev ? out : nullptr);
 }

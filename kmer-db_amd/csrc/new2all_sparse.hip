@@ -74,24 +74,10 @@ __global__ void n2s_row_ptr_kernel(const unsigned long long* __restrict__ seg_pt
     if (q <= nq) row_ptr[q] = seg_ptr[q * nseg];
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <class T> T* as() { return (T*)p; }
-};
-struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } };
 
 hipStream_t stream_of(const kmdb_engine_view& e, const kmdb_opts* opts) { return (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)e.stream; }
 
 }  // namespace
-
-#define N2S_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
 
 // what every entry refuses on its arguments alone, before the handle is looked at
 static int n2s_check_args(const char* who, const void* handle, const kmdb_sparse_rows* out, const kmdb_cell_filter* filters, size_t n_filters,
@@ -114,60 +100,60 @@ int kmdb_n2a_rows_compact(const char* who_, kmdb_db* db, const uint32_t* cells_d
     if (!cells_dev && cell_hi > cell_lo) return kmdb_set_error(who + ": null rows");
     if (n_filters && !query_kmers && nq) return kmdb_set_error(who + ": null argument");
     if (nq >= (1ull << 31)) return kmdb_set_error(who + ": too many queries in one batch");
-    N2S_TRY(hipSetDevice(e.device));
+    HIP_TRY(hipSetDevice(e.device));
     hipStream_t st = stream_of(e, opts);
     const uint32_t nseg = (uint32_t)std::max<uint64_t>(1, (N + N2S_SEG - 1) / N2S_SEG);
     const uint64_t n_segs = (uint64_t)nq * nseg;
-    Ev c0, c1, c2, c3;
-    N2S_TRY(hipEventCreate(&c0.e)); N2S_TRY(hipEventCreate(&c1.e)); N2S_TRY(hipEventCreate(&c2.e)); N2S_TRY(hipEventCreate(&c3.e));
-    DevBuf d_cnt, d_scan, d_ptr, d_tmp, d_col, d_val, d_qk, d_sk;
+    DevEvent c0, c1, c2, c3;
+    if (c0.create()) return 1; if (c1.create()) return 1; if (c2.create()) return 1; if (c3.create()) return 1;
+    DevBuf<void> d_cnt, d_scan, d_ptr, d_tmp, d_col, d_val, d_qk, d_sk;
     DevFilter df{};
     if (n_filters) {
-        N2S_TRY(d_qk.alloc(nq * 4)); N2S_TRY(d_sk.alloc(N * 4));
-        if (nq) N2S_TRY(hipMemcpyAsync(d_qk.p, query_kmers, nq * 4, hipMemcpyHostToDevice, st));
-        if (N) N2S_TRY(hipMemcpyAsync(d_sk.p, sample_kmers, N * 4, hipMemcpyHostToDevice, st));
-        df.n = (int)n_filters; df.counts = d_qk.as<uint32_t>();
+        DEV_ALLOC_BYTES(d_qk, nq * 4); DEV_ALLOC_BYTES(d_sk, N * 4);
+        if (nq) HIP_TRY(hipMemcpyAsync(d_qk.get(), query_kmers, nq * 4, hipMemcpyHostToDevice, st));
+        if (N) HIP_TRY(hipMemcpyAsync(d_sk.get(), sample_kmers, N * 4, hipMemcpyHostToDevice, st));
+        df.n = (int)n_filters; df.counts = static_cast<uint32_t*>(d_qk.get());
         kmdb_dev_bounds(filters, n_filters, (int)e.kmer_length, df.kind, df.lo, df.hi);
     }
-    N2S_TRY(d_cnt.alloc((n_segs + 1) * 8)); N2S_TRY(d_scan.alloc((n_segs + 1) * 8)); N2S_TRY(d_ptr.alloc((nq + 1) * 8));
+    DEV_ALLOC_BYTES(d_cnt, (n_segs + 1) * 8); DEV_ALLOC_BYTES(d_scan, (n_segs + 1) * 8); DEV_ALLOC_BYTES(d_ptr, (nq + 1) * 8);
     size_t scan_bytes = 0;
-    N2S_TRY(prim::exclusive_sum(nullptr, scan_bytes, d_cnt.as<unsigned long long>(), d_scan.as<unsigned long long>(), (size_t)(n_segs + 1), st));
-    N2S_TRY(d_tmp.alloc(scan_bytes));
+    HIP_TRY(prim::exclusive_sum(nullptr, scan_bytes, static_cast<unsigned long long*>(d_cnt.get()), static_cast<unsigned long long*>(d_scan.get()), (size_t)(n_segs + 1), st));
+    DEV_ALLOC_BYTES(d_tmp, scan_bytes);
     // the segments of the rows that meet the range (the others keep a count of zero)
     uint64_t seg_lo = 0, seg_hi = 0;
     if (cell_hi > cell_lo && N) { seg_lo = cell_lo / N * nseg; seg_hi = ((cell_hi - 1) / N + 1) * nseg; }
     constexpr uint64_t GRID_MAX = 1ull << 30;                    // segments per launch
-    N2S_TRY(hipEventRecord(c0.e, st));
-    N2S_TRY(hipMemsetAsync(d_cnt.p, 0, (n_segs + 1) * 8, st));
+    HIP_TRY(hipEventRecord(c0, st));
+    HIP_TRY(hipMemsetAsync(d_cnt.get(), 0, (n_segs + 1) * 8, st));
     for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += GRID_MAX) {
         hipLaunchKernelGGL((n2s_segments_kernel<false>), dim3((unsigned)std::min(GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
-                           cell_lo, cell_hi, d_cnt.as<unsigned long long>(), (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, df,
-                           d_sk.as<uint32_t>());
-        N2S_TRY(hipGetLastError());
+                           cell_lo, cell_hi, static_cast<unsigned long long*>(d_cnt.get()), (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, df,
+                           static_cast<uint32_t*>(d_sk.get()));
+        HIP_TRY(hipGetLastError());
     }
-    N2S_TRY(hipEventRecord(c1.e, st));
-    N2S_TRY(prim::exclusive_sum(d_tmp.p, scan_bytes, d_cnt.as<unsigned long long>(), d_scan.as<unsigned long long>(), (size_t)(n_segs + 1), st));
-    hipLaunchKernelGGL(n2s_row_ptr_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st, d_scan.as<unsigned long long>(), nseg, (uint64_t)nq,
-                       d_ptr.as<unsigned long long>());
-    N2S_TRY(hipGetLastError());
-    N2S_TRY(hipEventRecord(c2.e, st));
+    HIP_TRY(hipEventRecord(c1, st));
+    HIP_TRY(prim::exclusive_sum(d_tmp.get(), scan_bytes, static_cast<unsigned long long*>(d_cnt.get()), static_cast<unsigned long long*>(d_scan.get()), (size_t)(n_segs + 1), st));
+    hipLaunchKernelGGL(n2s_row_ptr_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, st, static_cast<unsigned long long*>(d_scan.get()), nseg, (uint64_t)nq,
+                       static_cast<unsigned long long*>(d_ptr.get()));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c2, st));
     std::vector<unsigned long long> h_ptr(nq + 1, 0);
-    N2S_TRY(hipMemcpyAsync(h_ptr.data(), d_ptr.p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    N2S_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h_ptr.data(), d_ptr.get(), (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint64_t nnz_dev = h_ptr[nq];
     if (nnz_dev > cell_hi - cell_lo) return kmdb_set_error(who + ": internal error (more kept cells than cells)");
-    N2S_TRY(d_col.alloc(nnz_dev * 4)); N2S_TRY(d_val.alloc(nnz_dev * 4));
+    DEV_ALLOC_BYTES(d_col, nnz_dev * 4); DEV_ALLOC_BYTES(d_val, nnz_dev * 4);
     if (nnz_dev)
         for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += GRID_MAX) {
             hipLaunchKernelGGL((n2s_segments_kernel<true>), dim3((unsigned)std::min(GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
-                               cell_lo, cell_hi, (unsigned long long*)nullptr, d_scan.as<unsigned long long>(), d_col.as<uint32_t>(), d_val.as<uint32_t>(), df,
-                               d_sk.as<uint32_t>());
-            N2S_TRY(hipGetLastError());
+                               cell_lo, cell_hi, (unsigned long long*)nullptr, static_cast<unsigned long long*>(d_scan.get()), static_cast<uint32_t*>(d_col.get()), static_cast<uint32_t*>(d_val.get()), df,
+                               static_cast<uint32_t*>(d_sk.get()));
+            HIP_TRY(hipGetLastError());
         }
-    N2S_TRY(hipEventRecord(c3.e, st));
-    N2S_TRY(hipEventSynchronize(c3.e));
+    HIP_TRY(hipEventRecord(c3, st));
+    HIP_TRY(hipEventSynchronize(c3));
     float ms = 0;
-    N2S_TRY(hipEventElapsedTime(&ms, c0.e, c3.e));
+    HIP_TRY(hipEventElapsedTime(&ms, c0, c3));
     out->n_rows = nq;
     out->nnz = nnz_dev;
     out->row_ptr = (uint64_t*)std::malloc((nq + 1) * 8);
@@ -176,8 +162,8 @@ int kmdb_n2a_rows_compact(const char* who_, kmdb_db* db, const uint32_t* cells_d
     if (!out->row_ptr || !out->col || !out->val) { kmdb_sparse_free(out); return kmdb_set_error(who + ": out of host memory for the result"); }
     for (uint64_t i = 0; i <= nq; ++i) out->row_ptr[i] = h_ptr[i];
     if (nnz_dev) {
-        hipError_t rc = hipMemcpyAsync(out->col, d_col.p, nnz_dev * 4, hipMemcpyDeviceToHost, st);
-        if (rc == hipSuccess) rc = hipMemcpyAsync(out->val, d_val.p, nnz_dev * 4, hipMemcpyDeviceToHost, st);
+        hipError_t rc = hipMemcpyAsync(out->col, d_col.get(), nnz_dev * 4, hipMemcpyDeviceToHost, st);
+        if (rc == hipSuccess) rc = hipMemcpyAsync(out->val, d_val.get(), nnz_dev * 4, hipMemcpyDeviceToHost, st);
         if (rc == hipSuccess) rc = hipStreamSynchronize(st);
         if (rc != hipSuccess) { kmdb_sparse_free(out); return kmdb_set_error(who + ": copy of the compacted rows: " + hipGetErrorString(rc)); }
     }
@@ -201,22 +187,22 @@ static int n2s_batch(const char* who_, kmdb_db* db, size_t nq, const kmdb_cell_f
     if (e.qs_count > 1 && !allow_query_shard)
         return kmdb_set_error(who + ": a query shard holds partial sums and partial k-mer counts (compact the summed rows with kmdb_new2all_rows_sparse_device, or use kmdb_node_new2all_batch_sparse_filtered)");
     if (nq >= (1ull << 31)) return kmdb_set_error(who + ": too many queries in one batch");
-    N2S_TRY(hipSetDevice(e.device));
+    HIP_TRY(hipSetDevice(e.device));
     hipStream_t st = stream_of(e, opts);
     const uint64_t cells = (uint64_t)nq * e.N;
-    DevBuf rows;
-    N2S_TRY(rows.alloc(cells * 4));
-    if (cells) N2S_TRY(hipMemsetAsync(rows.p, 0, cells * 4, st));
+    DevBuf<void> rows;
+    DEV_ALLOC_BYTES(rows, cells * 4);
+    if (cells) HIP_TRY(hipMemsetAsync(rows.get(), 0, cells * 4, st));
     kmdb_opts o{};
     if (opts) o = *opts; else { o.abi_version = KMDB_ABI_VERSION; o.device = e.device; o.shard_count = 1; }
     o.stream = st;
     std::vector<uint32_t> qk;
     try { qk.assign(std::max<size_t>(nq, 1), 0); } catch (const std::exception&) { return kmdb_set_error(who + ": out of host memory"); }
-    if (fill(rows.as<uint32_t>(), &o, qk.data())) return 1;
+    if (fill(static_cast<uint32_t*>(rows.get()), &o, qk.data())) return 1;
     kmdb_stats before{};
     (void)kmdb_db_stats(db, &before);
     kmdb_new2all_sparse_stats ns{};
-    if (kmdb_n2a_rows_compact(who_, db, rows.as<uint32_t>(), nq, 0, cells, qk.data(), filters, n_filters, sample_kmers, out, &o, &ns)) return 1;
+    if (kmdb_n2a_rows_compact(who_, db, static_cast<uint32_t*>(rows.get()), nq, 0, cells, qk.data(), filters, n_filters, sample_kmers, out, &o, &ns)) return 1;
     kmdb_engine_set_times(db, before.kernel_ms + ns.compact_ms, before.kernel_ms + ns.compact_ms);
     if ((n_filters || measure >= 0) && kmdb_sparse_decide(who_, out, filters, n_filters, qk.data(), sample_kmers, measure, (int)e.kmer_length)) return 1;
     ns.nnz = out->nnz;

@@ -9,7 +9,7 @@
 struct kmdb_sample_job {
     const uint32_t* cells = nullptr;        // device: cell `cell_lo` of the lower triangle
     uint64_t N = 0, cell_lo = 0, cell_hi = 0;
-    const unsigned char* touched = nullptr; // device, or nullptr: the tile flags of the block-record pipeline (kmdb_db.tile_touched) ...
+    const unsigned char* touched = nullptr; // device, or nullptr: the tile flags of the block-record pipeline (kmdb_blocks_tile_touched) ...
     uint32_t width = 64;                    // ... and the block width they were made for
     const uint32_t* counts_dev = nullptr;   // device: [N] k-mer counts of the samples
     size_t n_bounds = 0;                    // the widened bounds of the filters on their plain ratios (RATIO_* of cell_filter.h)

@@ -225,18 +225,6 @@ __global__ __launch_bounds__(64) void sr_sort_rows_kernel(const unsigned long lo
     }
 }
 
-struct Bufs {
-    std::vector<void*> p;
-    ~Bufs() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <class T> hipError_t get(T** out, uint64_t n) {
-        void* x = nullptr;
-        const hipError_t e = hipMalloc(&x, std::max<uint64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(x);
-        *out = (T*)x;
-        return e;
-    }
-};
-
 }  // namespace
 
 int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
@@ -254,20 +242,17 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
     q.kind = j.kind; q.flip = j.flip; q.count = j.count;
     const uint64_t B = (N + q.W - 1) / q.W, tiles = B * (B + 1) / 2;
     if (tiles >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many tiles");
-    Bufs bufs;
-    uint32_t *hist = nullptr, *thr = nullptr, *cursor = nullptr, *tcol = nullptr, *tval = nullptr, *col = nullptr, *val = nullptr;
-    SrState* state = nullptr;
-    unsigned long long *len = nullptr, *row_ptr = nullptr, *ntr = nullptr;
-    char* tmp = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return kmdb_set_error("hipEventCreate failed"); }
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } guard{e0, e1};
-    HIP_TRY(bufs.get(&thr, N));
-    HIP_TRY(bufs.get(&len, N + 1));
-    HIP_TRY(bufs.get(&row_ptr, N + 1));
-    HIP_TRY(bufs.get(&cursor, N));
-    HIP_TRY(bufs.get(&ntr, 1));
+    DevBuf<uint32_t> hist, thr, cursor, tcol, tval, col, val;
+    DevBuf<SrState> state;
+    DevBuf<unsigned long long> len, row_ptr, ntr;
+    DevBuf<char> tmp;
+    DevEvent e0, e1;
+    if (e0.create() || e1.create()) return 1;
+    DEV_ALLOC(thr, std::max<uint64_t>(N, 1));
+    DEV_ALLOC(len, N + 1);
+    DEV_ALLOC(row_ptr, N + 1);
+    DEV_ALLOC(cursor, std::max<uint64_t>(N, 1));
+    DEV_ALLOC(ntr, 1);
     HIP_TRY(hipEventRecord(e0, st));
     HIP_TRY(hipMemsetAsync(len, 0, (N + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(cursor, 0, N * 4, st));
@@ -280,8 +265,8 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
         HIP_TRY(hipMemcpyAsync(thr, h_thr.data(), N * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     } else {
-        HIP_TRY(bufs.get(&hist, N * 256));
-        HIP_TRY(bufs.get(&state, N));
+        DEV_ALLOC(hist, std::max<uint64_t>(N * 256, 1));
+        DEV_ALLOC(state, std::max<uint64_t>(N, 1));
         HIP_TRY(hipMemsetAsync(hist, 0, N * 256 * 4, st));
         HIP_TRY(hipMemsetAsync(state, 0, N * sizeof(SrState), st));
         HIP_TRY(hipMemsetAsync(thr, 0, N * 4, st));
@@ -298,19 +283,19 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
     ++out->passes;
     if (!only_rows) hipLaunchKernelGGL(sr_truncated_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, state, len, N, ntr);
     size_t tmp_bytes = 0;
-    HIP_TRY(prim::exclusive_sum(nullptr, tmp_bytes, len, row_ptr, (int)(N + 1), st));
-    HIP_TRY(bufs.get(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    HIP_TRY(prim::exclusive_sum(tmp, tmp_bytes, len, row_ptr, (int)(N + 1), st));
+    HIP_TRY(prim::exclusive_sum(nullptr, tmp_bytes, len.get(), row_ptr.get(), (int)(N + 1), st));
+    DEV_ALLOC(tmp, std::max<size_t>(tmp_bytes, 16));
+    HIP_TRY(prim::exclusive_sum(tmp, tmp_bytes, len.get(), row_ptr.get(), (int)(N + 1), st));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "row pointers are copied as they are");
     HIP_TRY(hipMemcpyAsync(out->row_ptr.data(), row_ptr, (N + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     out->d2h_bytes += (N + 1) * 8;
     const uint64_t nnz = out->row_ptr[N];
     if (nnz) {
-        HIP_TRY(bufs.get(&tcol, nnz));
-        HIP_TRY(bufs.get(&tval, nnz));
-        HIP_TRY(bufs.get(&col, nnz));
-        HIP_TRY(bufs.get(&val, nnz));
+        DEV_ALLOC(tcol, std::max<uint64_t>(nnz, 1));
+        DEV_ALLOC(tval, std::max<uint64_t>(nnz, 1));
+        DEV_ALLOC(col, std::max<uint64_t>(nnz, 1));
+        DEV_ALLOC(val, std::max<uint64_t>(nnz, 1));
         hipLaunchKernelGGL((sr_tile_kernel<SR_EMIT>), grid, block, 0, st, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, (unsigned long long*)nullptr, row_ptr, cursor,
                            tcol, tval);
         ++out->passes;
