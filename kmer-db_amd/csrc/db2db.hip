@@ -488,6 +488,11 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
         uint32_t nruns = 0;
         HIP_TRY(hipMemcpyAsync(&nruns, d_nruns.get(), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
+        if (nruns) {                                              // the slots without a hit are ONE run, the last (~0 sorts behind every key in use): no pattern pair
+            unsigned long long last_key = 0;
+            HIP_TRY(hipMemcpy(&last_key, static_cast<unsigned long long*>(d_uniq.get()) + (nruns - 1), 8, hipMemcpyDeviceToHost));
+            if (last_key == D2_INVALID) --nruns;
+        }
         phase("probe + sort + run lengths");
         if (nruns) {
             // pairs -> block records -> sorted by block pair -> accumulated on the matrix cores (a2a_blocks.hip)
