@@ -42,6 +42,9 @@ extern "C" {
 /* And the seed of the build mode: a builder that starts from a stored database (kmdb_build_begin_from_db, kmdb_build_seed_stats_get): two more
  * entry points and one struct of their own, the version stays 8. */
 #define KMDB_HAS_BUILD_SEED 1
+/* And the distance mode on the device: the table of common k-mer counts parsed, measured and formatted in HBM (kmdb_distance_*), and the one
+ * definition of a measure's text (kmdbh_format_measure): six more entry points and three structs of their own, the version stays 8. */
+#define KMDB_HAS_DISTANCE 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -714,6 +717,69 @@ int  kmdb_build_stats_get(const kmdb_builder* b, kmdb_build_stats* out);
  * every pattern header, zeros into bytes 36..39 (the reference leaves those four unwritten: pattern.cpp:35-37).  Any kmdbh_db that holds its
  * tables (kmdbh_db_load mode 0, kmdb_build_finish) can be stored; no GPU. */
 int  kmdbh_db_store(const kmdbh_db* db, const char* path);
+
+/* ---------------------------------------------------------------------------------------
+ * The distance mode (console_distance.cpp:7-213): the body of a table of common k-mer counts in, the table of one measure out, text to text.
+ * Additive in ABI 8 (KMDB_HAS_DISTANCE).  The device classifies the bytes, parses every field, computes the measure of every cell and writes
+ * the text; a cell whose six decimals or whose bounds the device's arithmetic cannot settle (kmdb_distance_stats.host_cells, about 2e-6 of
+ * the cells) takes no bytes there and is computed with kmdbh_metric, formatted with kmdbh_format_measure and spliced in on the host.
+ * ------------------------------------------------------------------------------------- */
+#define KMDB_DISTANCE_SPARSE_OUT 1u  /* -sparse: "column:value," of the non-zero counts that pass the bounds */
+#define KMDB_DISTANCE_SPARSE_IN  2u  /* the rows hold "column:count" pairs (sparse input always gives sparse output) */
+#define KMDB_DISTANCE_TRIANGLE   4u  /* dense rows: row i keeps min(i, n) values (decided by the caller from row 0, console_distance.cpp:149-152) */
+#define KMDB_DISTANCE_PHYLIP     8u  /* -phylip-out: blanks as separators, no bounds; dense input only */
+#define KMDB_DISTANCE_FLAGS_ALL  15u
+#define KMDB_DISTANCE_MAX_FILTERS 12 /* the device filter's capacity: one bound pair per criterion and a few repeats */
+/* status of kmdb_distance_rows besides 0 and 1: the text is one the device path does not take; kmdb_last_error() says why, nothing was
+ * written, the handle stays usable.  The caller runs the host loop instead. */
+#define KMDB_DISTANCE_DECLINED 2
+typedef struct kmdb_distance kmdb_distance;
+typedef struct kmdb_distance_opts {
+    uint32_t abi_version;          /* KMDB_ABI_VERSION */
+    int32_t  device;               /* HIP device ordinal */
+    int32_t  measure;              /* KMDB_METRIC_* */
+    uint32_t kmer_length;
+    const uint32_t* counts;        /* [n] the table's total-kmers row (copied) */
+    uint64_t n;                    /* columns of the table */
+    const kmdb_cell_filter* filters;   /* [n_filters] bounds, the num-kmers bounds among them (KMDB_METRIC_NUM_KMERS); copied */
+    uint64_t n_filters;            /* at most KMDB_DISTANCE_MAX_FILTERS */
+    uint32_t flags;                /* KMDB_DISTANCE_* */
+    uint32_t reserved;
+    void*    stream;               /* hipStream_t to run on, NULL = the default stream */
+} kmdb_distance_opts;
+typedef struct kmdb_distance_out {
+    char*    text;                 /* library-allocated, free with kmdb_distance_out_free */
+    size_t   len;
+    uint64_t rows;                 /* rows the call took */
+} kmdb_distance_out;
+typedef struct kmdb_distance_stats {   /* the whole life of the handle */
+    uint64_t calls;
+    uint64_t rows;
+    uint64_t cells_read;           /* cells of the input the row rules read */
+    uint64_t cells_written;        /* values in the output, the host's included */
+    uint64_t host_cells;           /* cells the device left to the host (rounding boundary, bound margin, not finite) */
+    uint64_t bytes_in, bytes_out;
+    uint64_t device_bytes;         /* most device memory one call held */
+    double   parse_ms;             /* HIP events: classification, compactions, digits */
+    double   measure_ms;           /* ... the measures, the text lengths, their scans */
+    double   format_ms;            /* ... names, separators, digits written */
+    double   copy_ms;              /* ... text to the device, text and the host's cells back */
+} kmdb_distance_stats;
+/* Replaces the setup of DistanceConsole::run (console_distance.cpp:58-72, 93-98).  Refused: an unknown measure or criterion, more than
+ * KMDB_DISTANCE_MAX_FILTERS bounds, unknown flags, no usable device. */
+int  kmdb_distance_begin(const kmdb_distance_opts* opts, kmdb_distance** out);
+/* Replaces the row loop (console_distance.cpp:75-204) for a run of WHOLE rows: `lines` = len bytes of table text in host memory, the rows
+ * first_row, first_row + 1, ... of the body; only the last row may lack its '\n'.  out->text = byte for byte what the loop writes for them
+ * ('\n' for endl).  Every read is clamped to the piece: damaged text is declined or parsed as the host loop parses it, never a fault.
+ * Declined (KMDB_DISTANCE_DECLINED): a line without a comma; a field of more than 10 digits or with a byte that is neither a digit nor a
+ * separator; "a:b:c"; a pair without SPARSE_IN or a plain cell with it (so: rows that mix the two); PHYLIP with SPARSE_IN; 2^32 - 64 bytes or more. */
+int  kmdb_distance_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t first_row, kmdb_distance_out* out);
+void kmdb_distance_out_free(kmdb_distance_out* out);
+void kmdb_distance_free(kmdb_distance* d);
+int  kmdb_distance_stats_get(const kmdb_distance* d, kmdb_distance_stats* out);
+/* Double2PChar with six decimals as the distance console prints a measure (conversion.h:167-219, 262-268): 0 and -0.0 are "0"; anything else
+ * is the sign, then x = (uint64)(|v| * 1e6 + 0.5) as x / 10^6 '.' x % 10^6 in six digits.  Returns the length; no terminator; out holds 40 bytes. */
+size_t kmdbh_format_measure(double v, char* out);
 
 /* CSV text (console_all2all.cpp:40-78, console_new2all.cpp:99-160, conversion.h:246-298).
  * Each returns bytes written to `out` (caller sizes it: 10000 + 100*N like the reference). */

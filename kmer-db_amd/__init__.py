@@ -12,6 +12,7 @@ from .capi import (  # noqa: F401
     ABI_VERSION,
     Builder,
     DeviceDB,
+    Distance,
     HostDB,
     KmdbError,
     NodeDB,
@@ -22,6 +23,7 @@ from .capi import (  # noqa: F401
     extract_kmers_alphabet,
     format_dense_row,
     format_header,
+    format_measure,
     format_sparse_row,
     lib,
     lib_path,

@@ -101,6 +101,22 @@ class _BuildSeedStats(C.Structure):
                 ("check_ms", C.c_double)]
 
 
+class _DistanceOpts(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("measure", C.c_int32), ("kmer_length", C.c_uint32), ("counts", C.c_void_p),
+                ("n", C.c_uint64), ("filters", C.c_void_p), ("n_filters", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
+class _DistanceOut(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("len", C.c_size_t), ("rows", C.c_uint64)]
+
+
+class _DistanceStats(C.Structure):
+    _fields_ = [("calls", C.c_uint64), ("rows", C.c_uint64), ("cells_read", C.c_uint64), ("cells_written", C.c_uint64), ("host_cells", C.c_uint64),
+                ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("device_bytes", C.c_uint64), ("parse_ms", C.c_double), ("measure_ms", C.c_double),
+                ("format_ms", C.c_double), ("copy_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -110,6 +126,8 @@ FLAG_FORCE_DIRECT = 2
 FLAG_FORCE_TILE = 4
 FLAG_NO_FALLBACK = 8
 FLAG_ONE_SHOT = 16
+DISTANCE_SPARSE_OUT, DISTANCE_SPARSE_IN, DISTANCE_TRIANGLE, DISTANCE_PHYLIP = 1, 2, 4, 8
+DISTANCE_DECLINED = 2
 PATH_NONE, PATH_RECORDS, PATH_TILE, PATH_GLOBAL = 0, 1, 2, 3
 PARTITIONS = ("prefix", "range", "prefix-tables")      # KMDB_PARTITION_*
 
@@ -131,6 +149,7 @@ EXPORTS = [
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
     "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
     "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
+    "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
 ]
 
 
@@ -265,6 +284,15 @@ def lib():
     L.kmdb_build_begin_from_db.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.kmdb_build_seed_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildSeedStats)]
     L.kmdbh_db_store.argtypes = [C.c_void_p, C.c_char_p]
+    L.kmdb_distance_begin.argtypes = [C.POINTER(_DistanceOpts), C.POINTER(C.c_void_p)]
+    L.kmdb_distance_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_out_free.restype = None
+    L.kmdb_distance_out_free.argtypes = [C.POINTER(_DistanceOut)]
+    L.kmdb_distance_free.restype = None
+    L.kmdb_distance_free.argtypes = [C.c_void_p]
+    L.kmdb_distance_stats_get.argtypes = [C.c_void_p, C.POINTER(_DistanceStats)]
+    L.kmdbh_format_measure.restype = C.c_size_t
+    L.kmdbh_format_measure.argtypes = [C.c_double, C.c_char_p]
     L.kmdbh_format_header.restype = C.c_size_t
     L.kmdbh_format_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.kmdbh_format_dense_row.restype = C.c_size_t
@@ -1076,6 +1104,61 @@ class Builder:
             self.close()
         except Exception:
             pass
+
+
+class Distance:
+    """kmdb_distance_*: the rows of a table of common k-mer counts -> the rows of one measure, parsed, measured and formatted on the device.
+    counts: the table's total-kmers row; filters: [(criterion name, lo, hi)], None = unbounded, "num-kmers" among them."""
+
+    def __init__(self, measure, k, counts, filters=(), sparse_out=False, sparse_in=False, triangle=False, phylip=False, device=0, stream=None):
+        self._d = C.c_void_p()
+        cnt = np.ascontiguousarray(counts, np.uint32)
+        fs = _filters(filters)
+        o = _DistanceOpts()
+        o.abi_version, o.device, o.measure, o.kmer_length = ABI_VERSION, int(device), _criterion(measure), int(k)
+        o.counts, o.n = cnt.ctypes.data, cnt.size
+        o.filters, o.n_filters = C.cast(fs, C.c_void_p), len(filters)
+        o.flags = (DISTANCE_SPARSE_OUT if sparse_out else 0) | (DISTANCE_SPARSE_IN if sparse_in else 0) | (DISTANCE_TRIANGLE if triangle else 0) \
+            | (DISTANCE_PHYLIP if phylip else 0)
+        o.stream = stream
+        _check(lib().kmdb_distance_begin(C.byref(o), C.byref(self._d)))
+
+    def rows(self, text, first_row=0):
+        """a run of whole rows -> (their output text, 0), or (b"", DISTANCE_DECLINED) with the reason in .declined"""
+        text = bytes(text)
+        out = _DistanceOut()
+        rc = lib().kmdb_distance_rows(self._d, text, len(text), int(first_row), C.byref(out))
+        if rc == DISTANCE_DECLINED:
+            self.declined = lib().kmdb_last_error().decode(errors="replace")
+            return b"", rc
+        _check(rc)
+        try:
+            return C.string_at(out.text, out.len), 0
+        finally:
+            lib().kmdb_distance_out_free(C.byref(out))
+
+    def stats(self):
+        st = _DistanceStats()
+        _check(lib().kmdb_distance_stats_get(self._d, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _DistanceStats._fields_}
+
+    def close(self):
+        if self._d:
+            lib().kmdb_distance_free(self._d)
+            self._d = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_measure(v):
+    """kmdbh_format_measure: a measure as the distance mode prints it"""
+    buf = C.create_string_buffer(48)
+    n = lib().kmdbh_format_measure(float(v), buf)
+    return buf.raw[:n]
 
 
 def sort_unique(kmers):

@@ -1,0 +1,680 @@
+// distance.hip — the distance mode on the device (console_distance.cpp:75-204): a run of whole table rows, text in and text out.
+//
+//   classify  a lane per byte, a wave per 64-byte window: ballots of '\n' and of the separators, the windows' counts scanned (prim.h).  The
+//             rows come out of the '\n' count, a row's first comma (the end of its name) out of one atomicMin per window and row, the
+//             fields ("tokens": what follows a ',' or ':' behind the name) out of the separator count.  Nothing walks a row.
+//   parse     a lane per token: at most 10 digits into 64 bits, truncated to uint32 as the host loop truncates; the row rules' flags.
+//   measure   a lane per OUTPUT cell (dense: n or min(row, n) per row whatever the row holds; otherwise one per token): kmdbh_metric's
+//             expressions in double with contraction off, the bounds, the text length.  A cell the device's arithmetic cannot settle
+//             (dev_code) takes no bytes and is listed for the host.
+//   format    one scan of the lengths, the output allocated to its size, a lane per cell writes its digits, a wave per row its name.
+//
+// Every position is below the piece's length by construction and clamped to it again where it is used: damaged text is declined
+// (KMDB_DISTANCE_DECLINED) or parsed as the host loop parses it, and never read or written outside the buffers.
+#include "kmdb_amd.h"
+#include "dev_mem.h"
+#include "prim.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+// hipcc contracts v * 1e6 + 0.5 into an fma by default; the host compiler of the reference does not
+#pragma clang fp contract(off)
+
+static_assert(KMDB_DISTANCE_MAX_FILTERS == 12, "cell_filter.h's DEV_FILTER_MAX");
+
+namespace {
+
+constexpr int DT = 256;                         // threads per workgroup, four windows
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+enum { MODE_DENSE = 0, MODE_SPARSE_OUT, MODE_SPARSE_IN, MODE_PHYLIP };
+// why a piece is declined (the largest code wins: any will do)
+enum { DECL_NONE = 0, DECL_NO_COMMA, DECL_DIGITS, DECL_CHAR, DECL_COLONS, DECL_PAIR, DECL_PLAIN };
+// token flags
+enum : uint8_t { TF_OPEN_COLON = 1, TF_TERM_COLON = 2, TF_READ = 4, TF_OVER32 = 8 };
+// cell codes: bits 0..59 x = (uint64)(|v| * 1e6 + 0.5)
+constexpr uint64_t C_ZERO = 1ull << 60, C_NEG = 1ull << 61, C_HOST = 1ull << 62, C_SKIP = 1ull << 63, C_X = (1ull << 60) - 1;
+
+struct DistParams {
+    const unsigned char* text;
+    uint32_t L;                 // bytes
+    uint32_t R;                 // rows
+    uint32_t M;                 // tokens
+    uint32_t n;                 // columns
+    const uint32_t* counts;     // [n]
+    int mode, measure, k, triangle;
+    uint64_t first_row;
+    int n_filters;
+    int f_metric[KMDB_DISTANCE_MAX_FILTERS];
+    double f_lo[KMDB_DISTANCE_MAX_FILTERS], f_hi[KMDB_DISTANCE_MAX_FILTERS];
+    // classification
+    const uint32_t* weol;       // [NW + 1] '\n' before the window
+    const uint32_t* wsep;       // [NW + 1] separators before the window
+    uint32_t* fc;               // [R] first comma of the row, NONE: none
+    uint32_t* row_end;          // [R] the row's '\n', L for a last row without one
+    uint32_t* row_first;        // [R + 1] the row's first token (its own k-mer count); [R] = M
+    uint32_t* sep_pos;          // [M] the separator in front of the token
+    uint32_t* sep_row;          // [M]
+    uint32_t* tok_val;          // [M]
+    uint8_t* tok_flags;         // [M]
+    // rows and cells
+    uint64_t* oc;               // [R + 1] output cells of the row, scanned in place: the first cell of the row, [R] = all
+    uint64_t* rowfix;           // [R + 1] name + separator + '\n', scanned in place
+    uint64_t n_cells;
+    uint64_t* code;             // [n_cells]
+    uint8_t* len;               // [n_cells]
+    uint64_t* off;              // [n_cells + 1] scanned lengths
+    unsigned int* decline;
+    unsigned long long* counters;   // [0] cells read [1] cells the device wrote [2] cells for the host [3] entries appended
+};
+
+// a cell the host decides: where its text goes, and what it is
+struct HostCell {
+    uint64_t ci;                // output cell index: the order of the text
+    uint64_t off;               // byte offset in the device's text
+    uint32_t col;               // 0-based column
+    uint32_t count, a;
+    uint32_t pad;
+};
+
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1; }
+
+// ---- classify ---------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DT) dist_eol_count_kernel(const unsigned char* text, uint32_t L, uint32_t* wcnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    const bool eol = i < L && text[i] == '\n';
+    const uint64_t m = __ballot(eol);
+    if ((threadIdx.x & 63) == 0 && i < L) wcnt[i >> 6] = (uint32_t)__popcll(m);
+}
+
+// the rows' ends and first commas: one atomicMin per window and row (the first comma of the row inside the window)
+__global__ void __launch_bounds__(DT) dist_rows_kernel(DistParams p) {
+    const uint64_t i = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    const bool in = i < p.L;
+    const unsigned char ch = in ? p.text[i] : 0;
+    const uint64_t eols = __ballot(in && ch == '\n'), commas = __ballot(in && ch == ',');
+    if (!in) return;
+    const uint64_t below = lanes_below();
+    const uint32_t row = p.weol[i >> 6] + (uint32_t)__popcll(eols & below);
+    if (row >= p.R) return;                                     // (cannot happen: R counts the '\n' and a last row without one)
+    if (ch == '\n') p.row_end[row] = (uint32_t)i;
+    else if (ch == ',') {
+        const uint64_t e = eols & below;
+        const uint64_t since = e ? ~((2ull << (63 - __clzll(e))) - 1) : ~0ull;      // the lanes behind the last '\n' in front of this one
+        if (!(commas & below & since)) atomicMin(&p.fc[row], (uint32_t)i);
+    }
+}
+
+__device__ __forceinline__ bool dist_is_sep(const DistParams& p, uint64_t i, bool in, unsigned char ch, uint64_t eols, uint32_t* row_out) {
+    if (!in) return false;
+    const uint32_t row = p.weol[i >> 6] + (uint32_t)__popcll(eols & lanes_below());
+    *row_out = row;
+    return (ch == ',' || ch == ':') && row < p.R && i >= p.fc[row];
+}
+
+__global__ void __launch_bounds__(DT) dist_sep_count_kernel(DistParams p, uint32_t* wcnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    const bool in = i < p.L;
+    const unsigned char ch = in ? p.text[i] : 0;
+    const uint64_t eols = __ballot(in && ch == '\n');
+    uint32_t row = 0;
+    const uint64_t seps = __ballot(dist_is_sep(p, i, in, ch, eols, &row));
+    if ((threadIdx.x & 63) == 0 && in) wcnt[i >> 6] = (uint32_t)__popcll(seps);
+}
+
+__global__ void __launch_bounds__(DT) dist_sep_write_kernel(DistParams p) {
+    const uint64_t i = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    const bool in = i < p.L;
+    const unsigned char ch = in ? p.text[i] : 0;
+    const uint64_t eols = __ballot(in && ch == '\n');
+    uint32_t row = 0;
+    const bool sep = dist_is_sep(p, i, in, ch, eols, &row);
+    const uint64_t seps = __ballot(sep);
+    if (!sep) return;
+    const uint32_t j = p.wsep[i >> 6] + (uint32_t)__popcll(seps & lanes_below());
+    if (j >= p.M) return;
+    p.sep_pos[j] = (uint32_t)i;
+    p.sep_row[j] = row;
+    if (i == p.fc[row]) p.row_first[row] = j;
+}
+
+// ---- parse ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dist_decline(const DistParams& p, unsigned int why) { atomicMax(p.decline, why); }
+
+__global__ void __launch_bounds__(DT) dist_parse_kernel(DistParams p) {
+    const uint64_t j = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    bool counted = false;
+    if (j < p.M) {
+        const uint32_t pos = min(p.sep_pos[j], p.L - 1), r = min(p.sep_row[j], p.R - 1);
+        const uint32_t rend = min(p.row_end[r], p.L);
+        const bool more = j + 1 < p.M && p.sep_row[j + 1] == r;
+        const uint32_t start = min(pos + 1, rend);
+        const uint32_t stop = more ? max(start, min(p.sep_pos[j + 1], rend)) : rend;
+        uint8_t fl = 0;
+        if (p.text[pos] == ':') fl |= TF_OPEN_COLON;
+        if (more && p.text[min(p.sep_pos[j + 1], p.L - 1)] == ':') fl |= TF_TERM_COLON;
+        if (rend - start > 1) fl |= TF_READ;                    // console_distance.cpp:100: a cell is read while end - p > 1
+        const uint32_t len = stop - start;
+        if (len > 10) dist_decline(p, DECL_DIGITS);
+        unsigned long long v = 0;
+        for (uint32_t q = 0; q < min(len, 10u); ++q) {
+            const unsigned char ch = p.text[start + q];
+            if (ch < '0' || ch > '9') { dist_decline(p, DECL_CHAR); break; }
+            v = v * 10 + (unsigned)(ch - '0');
+        }
+        if (v >> 32) fl |= TF_OVER32;
+        p.tok_val[j] = (uint32_t)v;
+        p.tok_flags[j] = fl;
+        const uint32_t first = p.row_first[r];
+        if ((fl & TF_TERM_COLON) && (j == first || (fl & TF_OPEN_COLON))) dist_decline(p, DECL_COLONS);     // "count:x", "a:b:c"
+        if (j != first && !(fl & TF_OPEN_COLON) && (fl & TF_READ)) {                                         // a cell the row rules read
+            counted = true;
+            const bool pair = fl & TF_TERM_COLON;
+            if (pair && p.mode != MODE_SPARSE_IN) dist_decline(p, DECL_PAIR);
+            if (!pair && p.mode == MODE_SPARSE_IN) dist_decline(p, DECL_PLAIN);
+        }
+    }
+    const uint64_t m = __ballot(counted);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.counters[0], (unsigned long long)__popcll(m));
+}
+
+// a lane per row: a row without a comma is declined; the output cells of the row and the bytes around them
+__global__ void __launch_bounds__(DT) dist_row_sizes_kernel(DistParams p) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r >= p.R) return;
+    const uint32_t fc = p.fc[r];
+    if (fc == NONE) { dist_decline(p, DECL_NO_COMMA); p.oc[r] = 0; p.rowfix[r] = 0; return; }
+    const uint32_t start = r ? min(p.row_end[r - 1] + 1, p.L) : 0;
+    const uint32_t tb = p.row_first[r], te = p.row_first[r + 1];
+    uint64_t cells;
+    if (p.mode == MODE_DENSE) cells = p.triangle ? min((uint64_t)p.n, p.first_row + r) : (uint64_t)p.n;
+    else cells = te > tb ? te - tb - 1 : 0;
+    p.oc[r] = cells;
+    p.rowfix[r] = (uint64_t)(fc >= start ? fc - start : 0) + 2;
+}
+
+// ---- measure ----------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double dev_mash(double j, int k) { return j == 0 ? 1.0 : (-1.0 / k) * log((2 * j) / (j + 1)); }
+
+// kmdbh_metric's expressions (host_metrics.cpp).  *exact: the value is the host's bit for bit (correctly rounded operations only);
+// *zero_ok: a result of 0 is one the host computes as 0 too.
+__device__ double dev_metric(int metric, uint32_t c, uint32_t a, uint32_t b, int k, bool* exact, bool* zero_ok) {
+    *exact = true; *zero_ok = true;
+    switch (metric) {
+    case KMDB_METRIC_JACCARD:     return (double)c / (double)(uint32_t)(a + b - c);
+    case KMDB_METRIC_MIN:         return (double)c / (double)(a < b ? a : b);
+    case KMDB_METRIC_MAX:         return (double)c / (double)(a > b ? a : b);
+    case KMDB_METRIC_COSINE:      *exact = false; return (double)c / sqrt((double)(uint32_t)(a * b));
+    case KMDB_METRIC_MASH:        *exact = false; return dev_mash((double)c / (double)(uint32_t)(a + b - c), k);     // 0 only where the log's argument is 1
+    case KMDB_METRIC_ANI:         { *exact = false; const double j = (double)c / (double)(uint32_t)(a + b - c); *zero_ok = j == 0; return 1.0 - dev_mash(j, k); }
+    case KMDB_METRIC_ANI_SHORTER: { *exact = false; const double j = (double)c / (double)(a < b ? a : b); *zero_ok = j == 0; return 1.0 - dev_mash(j, k); }
+    case KMDB_METRIC_MASH_QUERY:  *exact = false; return dev_mash((double)c / (double)a, k);
+    default:                      return (double)c;
+    }
+}
+
+// The text of a value, or C_HOST where the device's few ulp could change it: t = |v| * 1e6 + 0.5 within 2^-20 of an integer — for a log /
+// sqrt measure within t * 2^-44 where that is more: a few hundred ulp of t, whatever its size — v not finite or of 10^12 and more, a
+// value below 10^-9 that is not an exact zero (its sign and its being zero are not settled here).
+__device__ uint64_t dev_code(double v, bool exact, bool zero_ok) {
+    if (v == 0) return zero_ok ? C_ZERO : C_HOST;
+    const double m = fabs(v);
+    if (!(m < 1e12)) return C_HOST;                             // NaN and infinities too
+    if (!exact && m < 1e-9) return C_HOST;
+    const double t = m * 1000000.0 + 0.5;
+    if (fabs(t - rint(t)) <= (exact ? 0x1p-20 : fmax(0x1p-20, t * 0x1p-44))) return C_HOST;
+    return (uint64_t)t | (v < 0 ? C_NEG : 0);
+}
+
+__device__ __forceinline__ uint32_t dev_digits(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 10) { v /= 10; ++n; }
+    return n;
+}
+
+// 0: the bounds drop the cell; 1: they keep it; 2: a bound lies within 1e-9 * max(1, |bound|) of the device's value: the host decides
+__device__ int dev_bounds(const DistParams& p, uint32_t c, uint32_t a, uint32_t b) {
+    int verdict = 1;
+    for (int i = 0; i < p.n_filters; ++i) {
+        bool exact, zero_ok;
+        const double x = dev_metric(p.f_metric[i], c, a, b, p.k, &exact, &zero_ok), lo = p.f_lo[i], hi = p.f_hi[i];
+        if (p.f_metric[i] == KMDB_METRIC_NUM_KMERS) { if (!(x >= lo && x <= hi)) return 0; continue; }      // an integer: nothing to settle
+        if (!(fabs(x) <= 1.7e308)) { verdict = 2; continue; }
+        if (fabs(x - lo) <= 1e-9 * fmax(1.0, fabs(lo)) || fabs(x - hi) <= 1e-9 * fmax(1.0, fabs(hi))) { verdict = 2; continue; }
+        if (!(x >= lo && x <= hi)) return 0;                    // clear of every margin: dropped whatever the undecided bounds say
+    }
+    return verdict;
+}
+
+struct Cell {
+    uint32_t row, col, count, a;
+    uint32_t prefix;            // the column printed in front of the value, 0: none
+    bool emit;                  // the row rules write it (bounds aside)
+    bool zero;                  // phylip: a value beyond the row's processed count
+};
+
+// the row of an output cell: the last row whose first cell is at or below it (rows without cells share their successor's)
+__device__ __forceinline__ uint32_t dev_row_of(const uint64_t* base, uint32_t R, uint64_t ci) {
+    uint32_t lo = 0, hi = R;                                    // base[lo] <= ci < base[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (base[mid] <= ci) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ Cell dev_cell(const DistParams& p, uint64_t ci) {
+    Cell x{};
+    const uint32_t r = dev_row_of(p.oc, p.R, ci);
+    const uint64_t c = ci - p.oc[r];
+    const uint32_t tb = min(p.row_first[r], p.M - 1), te = min(p.row_first[r + 1], p.M);
+    const uint64_t j = (uint64_t)tb + 1 + c;
+    const bool has = j < te && (p.tok_flags[j] & TF_READ);
+    x.row = r;
+    x.a = p.tok_val[tb];
+    switch (p.mode) {
+    case MODE_DENSE:                                            // every cell of the row's processed count, 0 where the row holds none
+        x.col = (uint32_t)c; x.count = has ? p.tok_val[j] : 0; x.emit = c < p.n;
+        break;
+    case MODE_PHYLIP: {                                         // min(n_read, n) values; 0 beyond the processed count
+        const uint64_t n_proc = p.triangle ? min((uint64_t)p.n, p.first_row + r) : (uint64_t)p.n;
+        x.col = (uint32_t)c; x.emit = has && c < p.n; x.count = has ? p.tok_val[j] : 0; x.zero = c >= n_proc;
+        break;
+    }
+    case MODE_SPARSE_OUT:
+        // (the loop tests v > 0 on the 64 bits it read and keeps the 32 it stores: 2^32 is a cell of count 0)
+        x.col = (uint32_t)c; x.count = has ? p.tok_val[j] : 0; x.emit = has && c < p.n && (x.count > 0 || (p.tok_flags[j] & TF_OVER32)); x.prefix = (uint32_t)c + 1;
+        break;
+    default: {                                                  // pairs: the column token (opened by ','), its count in the next one
+        const bool pair = has && !(p.tok_flags[j] & TF_OPEN_COLON) && (p.tok_flags[j] & TF_TERM_COLON) && j + 1 < te;
+        const uint32_t col = pair ? p.tok_val[j] : 0;
+        const bool ok = pair && !(p.tok_flags[j] & TF_OVER32) && col >= 1 && col <= p.n;
+        x.count = ok ? p.tok_val[j + 1] : 0; x.col = ok ? col - 1 : 0; x.prefix = col; x.emit = ok && x.count > 0;
+        break;
+    }
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(DT) dist_measure_kernel(DistParams p) {
+    const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    bool wrote = false, host = false;
+    if (ci < p.n_cells) {
+        const Cell x = dev_cell(p, ci);
+        uint64_t code = C_SKIP;
+        uint32_t len = 0;
+        if (x.emit) {
+            const uint32_t b = p.counts[min(x.col, p.n - 1)];
+            const int keep = x.prefix ? dev_bounds(p, x.count, x.a, b) : 1;         // the bounds belong to the sparse forms
+            if (keep == 2) code = C_HOST;
+            else if (keep == 1) {
+                bool exact = true, zero_ok = true;
+                const double v = x.zero ? 0.0 : dev_metric(p.measure, x.count, x.a, b, p.k, &exact, &zero_ok);
+                code = dev_code(v, exact, zero_ok);
+            }
+            if (code == C_HOST) host = true;
+            else if (code != C_SKIP) {
+                wrote = true;
+                len = (code & C_ZERO) ? 1 : ((code & C_NEG) ? 1 : 0) + dev_digits((code & C_X) / 1000000ull) + 7;
+                if (x.prefix) len += dev_digits(x.prefix) + 1;
+                len += 1;                                       // the separator behind the value
+            }
+        }
+        p.code[ci] = code;
+        p.len[ci] = (uint8_t)len;
+    }
+    const uint64_t mw = __ballot(wrote), mh = __ballot(host);
+    if ((threadIdx.x & 63) == 0) {
+        if (mw) atomicAdd(&p.counters[1], (unsigned long long)__popcll(mw));
+        if (mh) atomicAdd(&p.counters[2], (unsigned long long)__popcll(mh));
+    }
+}
+
+// ---- format -----------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned char* dev_put_uint(unsigned char* o, uint64_t v) {
+    const uint32_t n = dev_digits(v);
+    for (uint32_t i = n; i-- > 0;) { o[i] = (unsigned char)('0' + v % 10); v /= 10; }
+    return o + n;
+}
+
+// where the cells of row r begin in the output: its name and the separator behind it in front of them
+__device__ __forceinline__ uint64_t dev_cells_at(const DistParams& p, uint32_t r) { return p.rowfix[r] + (p.rowfix[r + 1] - p.rowfix[r] - 1); }
+
+__global__ void __launch_bounds__(DT) dist_write_kernel(DistParams p, unsigned char* out, uint64_t out_bytes, HostCell* host, uint64_t host_cap) {
+    const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (ci >= p.n_cells) return;
+    const uint64_t code = p.code[ci];
+    if (code == C_SKIP) return;
+    const Cell x = dev_cell(p, ci);
+    const uint64_t at = dev_cells_at(p, x.row) + p.off[ci];
+    if (code == C_HOST) {
+        const unsigned long long e = atomicAdd(&p.counters[3], 1ull);
+        if (e < host_cap) host[e] = HostCell{ci, at, x.col, x.count, x.a, 0};
+        return;
+    }
+    const uint32_t len = p.len[ci];
+    if (at + len > out_bytes) return;                           // (cannot happen: the buffer has the scanned size)
+    unsigned char* o = out + at;
+    if (x.prefix) { o = dev_put_uint(o, x.prefix); *o++ = ':'; }
+    if (code & C_ZERO) *o++ = '0';
+    else {
+        if (code & C_NEG) *o++ = '-';
+        const uint64_t v = code & C_X;
+        o = dev_put_uint(o, v / 1000000ull);
+        *o++ = '.';
+        uint32_t f = (uint32_t)(v % 1000000ull);
+        for (int i = 5; i >= 0; --i) { o[i] = (unsigned char)('0' + f % 10u); f /= 10u; }
+        o += 6;
+    }
+    *o = p.mode == MODE_PHYLIP ? ' ' : ',';
+}
+
+// a wave per row: the name, the separator behind it, the '\n' behind the row's cells
+__global__ void __launch_bounds__(DT) dist_names_kernel(DistParams p, unsigned char* out, uint64_t out_bytes) {
+    const uint64_t r = ((uint64_t)blockIdx.x * DT + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= p.R) return;
+    const uint32_t start = r ? min(p.row_end[r - 1] + 1, p.L) : 0;
+    const uint32_t fc = min(p.fc[r], p.L);
+    const uint32_t nlen = fc >= start ? fc - start : 0;
+    const uint64_t at = p.rowfix[r] + p.off[p.oc[r]];           // the row's first byte: the fixed bytes and the cells of the rows before
+    const uint64_t nl = p.rowfix[r + 1] - 1 + p.off[p.oc[r + 1]];
+    if (at + nlen + 1 > out_bytes || nl >= out_bytes) return;
+    for (uint32_t q = lane; q < nlen; q += 64) out[at + q] = p.text[start + q];
+    if (lane == 0) { out[at + nlen] = p.mode == MODE_PHYLIP ? ' ' : ','; out[nl] = '\n'; }
+}
+
+template <class T>
+__global__ void dist_fill_kernel(T* a, uint64_t n, T v) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
+const char* decline_text(unsigned int why) {
+    switch (why) {
+    case DECL_NO_COMMA: return "a line has no comma";
+    case DECL_DIGITS:   return "a field has more than 10 digits";
+    case DECL_CHAR:     return "a field holds a byte that is neither a digit nor a separator";
+    case DECL_COLONS:   return "a ':' where the row rules know no pair";
+    case DECL_PAIR:     return "a column:count pair in a table taken for dense";
+    case DECL_PLAIN:    return "a plain cell in a table taken for sparse";
+    default:            return "unknown";
+    }
+}
+
+inline unsigned blocks_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, (n + DT - 1) / DT); }
+
+}  // namespace
+
+struct kmdb_distance {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int measure = 0, k = 0, mode = MODE_DENSE, triangle = 0;
+    uint32_t flags = 0;
+    std::vector<uint32_t> counts;
+    std::vector<kmdb_cell_filter> filters;
+    DevBuf<uint32_t> d_counts;
+    kmdb_distance_stats st{};
+};
+
+extern "C" int kmdb_distance_begin(const kmdb_distance_opts* opts, kmdb_distance** out) {
+    const char* who = "kmdb_distance_begin: ";
+    if (!opts || !out) return kmdb_set_error(std::string(who) + "null argument");
+    *out = nullptr;
+    if (opts->abi_version && !kmdb_abi_compatible(opts->abi_version)) return kmdb_set_error(std::string(who) + "kmdb_distance_opts.abi_version is not served by this library");
+    if (opts->measure < 0 || opts->measure >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + "unknown measure " + std::to_string(opts->measure));
+    if (opts->flags & ~KMDB_DISTANCE_FLAGS_ALL) return kmdb_set_error(std::string(who) + "unknown flags");
+    if (opts->n_filters > KMDB_DISTANCE_MAX_FILTERS) return kmdb_set_error(std::string(who) + "more than " + std::to_string(KMDB_DISTANCE_MAX_FILTERS) + " bounds");
+    if ((opts->n && !opts->counts) || (opts->n_filters && !opts->filters)) return kmdb_set_error(std::string(who) + "null argument");
+    if (opts->n >= 0xFFFFFFFFull) return kmdb_set_error(std::string(who) + "2^32 - 1 columns or more");
+    for (uint64_t i = 0; i < opts->n_filters; ++i)
+        if (opts->filters[i].metric < 0 || opts->filters[i].metric >= KMDB_METRIC_COUNT) return kmdb_set_error(std::string(who) + "unknown criterion " + std::to_string(opts->filters[i].metric));
+    if (kmdb_device_count() <= 0) return kmdb_set_error(std::string(who) + "no usable gfx950 device");
+    kmdb_distance* d = new (std::nothrow) kmdb_distance;
+    if (!d) return kmdb_set_error(std::string(who) + "out of host memory");
+    int rc = 0;
+    try {
+        d->device = opts->device; d->stream = (hipStream_t)opts->stream; d->measure = opts->measure; d->k = (int)opts->kmer_length; d->flags = opts->flags;
+        d->triangle = (opts->flags & KMDB_DISTANCE_TRIANGLE) ? 1 : 0;
+        d->mode = (opts->flags & KMDB_DISTANCE_PHYLIP) ? MODE_PHYLIP : (opts->flags & KMDB_DISTANCE_SPARSE_IN) ? MODE_SPARSE_IN
+                : (opts->flags & KMDB_DISTANCE_SPARSE_OUT) ? MODE_SPARSE_OUT : MODE_DENSE;
+        d->counts.assign(opts->counts, opts->counts + opts->n);
+        d->filters.assign(opts->filters, opts->filters + opts->n_filters);
+        rc = [&]() -> int {
+            HIP_TRY(hipSetDevice(d->device));
+            DEV_ALLOC(d->d_counts, d->counts.size());
+            if (!d->counts.empty()) HIP_TRY(hipMemcpy(d->d_counts.get(), d->counts.data(), d->counts.size() * 4, hipMemcpyHostToDevice));
+            return 0;
+        }();
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string(who) + e.what());
+    }
+    if (rc) { delete d; return rc; }
+    *out = d;
+    return 0;
+}
+
+extern "C" void kmdb_distance_free(kmdb_distance* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    delete d;
+}
+
+extern "C" void kmdb_distance_out_free(kmdb_distance_out* out) {
+    if (!out) return;
+    free(out->text);
+    out->text = nullptr; out->len = 0; out->rows = 0;
+}
+
+extern "C" int kmdb_distance_stats_get(const kmdb_distance* d, kmdb_distance_stats* out) {
+    if (!d || !out) return kmdb_set_error("kmdb_distance_stats_get: null argument");
+    *out = d->st;
+    return 0;
+}
+
+// the cells the device left open, in the order of the text: computed, bounded and formatted as the host loop does it, spliced in
+static int dist_splice(kmdb_distance* d, std::vector<HostCell>& cells, const char* dev_text, size_t dev_len, kmdb_distance_out* out, uint64_t* written) {
+    std::sort(cells.begin(), cells.end(), [](const HostCell& x, const HostCell& y) { return x.ci < y.ci; });
+    char* text = (char*)malloc(std::max<size_t>(1, dev_len + cells.size() * 64));
+    if (!text) return kmdb_set_error("kmdb_distance_rows: out of host memory");
+    size_t o = 0, from = 0;
+    const bool bounded = d->mode == MODE_SPARSE_OUT || d->mode == MODE_SPARSE_IN;
+    for (const HostCell& c : cells) {
+        const size_t at = (size_t)std::min<uint64_t>(c.off, dev_len);
+        if (at > from) { std::memcpy(text + o, dev_text + from, at - from); o += at - from; from = at; }
+        const uint32_t b = d->counts[c.col];
+        bool keep = true;
+        if (bounded)
+            for (const kmdb_cell_filter& f : d->filters) {
+                const double x = kmdbh_metric(f.metric, c.count, c.a, b, d->k);
+                if (!(x >= f.lo && x <= f.hi)) { keep = false; break; }
+            }
+        if (!keep) continue;
+        if (bounded) { o += (size_t)std::snprintf(text + o, 24, "%llu", (unsigned long long)c.col + 1); text[o++] = ':'; }
+        o += kmdbh_format_measure(kmdbh_metric(d->measure, c.count, c.a, b, d->k), text + o);
+        text[o++] = d->mode == MODE_PHYLIP ? ' ' : ',';
+        ++*written;
+    }
+    std::memcpy(text + o, dev_text + from, dev_len - from);
+    o += dev_len - from;
+    out->text = text; out->len = o;
+    return 0;
+}
+
+static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t first_row, kmdb_distance_out* out) {
+    const char* who = "kmdb_distance_rows: ";
+    if (d->mode == MODE_PHYLIP && (d->flags & KMDB_DISTANCE_SPARSE_IN)) { kmdb_set_error(std::string(who) + "declined: phylip output from sparse input"); return KMDB_DISTANCE_DECLINED; }
+    if (len >= 0xFFFFFFFFull - 64) { kmdb_set_error(std::string(who) + "declined: a piece of 2^32 - 64 bytes or more"); return KMDB_DISTANCE_DECLINED; }
+    d->st.calls += 1;
+    if (len == 0) {
+        out->text = (char*)malloc(1);
+        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    const uint32_t L = (uint32_t)len;
+    const uint64_t NW = ((uint64_t)L + 63) / 64;
+    uint64_t held = 0;
+    DevEvent ev[6];
+    for (auto& e : ev) if (e.create()) return 1;
+    DevBuf<unsigned char> d_text;
+    DevBuf<uint32_t> d_wcnt, d_weol, d_wsep, d_fc, d_row_end, d_row_first, d_sep_pos, d_sep_row, d_tok_val;
+    DevBuf<uint8_t> d_tok_flags, d_len;
+    DevBuf<uint64_t> d_oc, d_rowfix, d_code, d_off;
+    DevBuf<unsigned int> d_decline;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<void> d_tmp;
+    DevBuf<unsigned char> d_out;
+    DevBuf<HostCell> d_host;
+    auto scan = [&](auto* in, auto* outp, size_t n) -> int {      // exclusive sum with the library's temporary storage
+        size_t tb = 0;
+        HIP_TRY(prim::exclusive_sum(nullptr, tb, in, outp, n, st));
+        if (tb > d_tmp.bytes()) { held += tb; DEV_ALLOC_BYTES(d_tmp, tb); }
+        HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb, in, outp, n, st));
+        return 0;
+    };
+
+    HIP_TRY(hipEventRecord(ev[0], st));
+    DEV_ALLOC(d_text, (size_t)L); DEV_ALLOC(d_wcnt, NW + 1); DEV_ALLOC(d_weol, NW + 1); DEV_ALLOC(d_wsep, NW + 1); DEV_ALLOC(d_decline, 1); DEV_ALLOC(d_counters, 4);
+    held += L + 3 * (NW + 1) * 4;
+    HIP_TRY(hipMemcpyAsync(d_text.get(), lines, L, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_decline.get(), 0, 4, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
+    HIP_TRY(hipMemsetAsync(d_wcnt.get(), 0, (NW + 1) * 4, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
+
+    // classify: rows
+    DistParams p{};
+    p.text = d_text; p.L = L; p.n = (uint32_t)d->counts.size(); p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k;
+    p.triangle = d->triangle; p.first_row = first_row; p.n_filters = (int)d->filters.size();
+    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
+    p.decline = d_decline; p.counters = d_counters;
+    hipLaunchKernelGGL(dist_eol_count_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, (const unsigned char*)d_text.get(), L, d_wcnt.get());
+    HIP_TRY(hipGetLastError());
+    if (scan(d_wcnt.get(), d_weol.get(), NW + 1)) return 1;
+    uint32_t n_eol = 0;
+    HIP_TRY(hipMemcpyAsync(&n_eol, d_weol.get() + NW, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_eol > L) return kmdb_set_error(std::string(who) + "internal error (more line ends than bytes)");
+    const uint32_t R = n_eol + (lines[len - 1] != '\n' ? 1u : 0u);
+    p.R = R; p.weol = d_weol;
+    DEV_ALLOC(d_fc, (size_t)R); DEV_ALLOC(d_row_end, (size_t)R); DEV_ALLOC(d_row_first, (size_t)R + 1); DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1);
+    held += (uint64_t)R * 28;
+    p.fc = d_fc; p.row_end = d_row_end; p.row_first = d_row_first; p.oc = d_oc; p.rowfix = d_rowfix;
+    hipLaunchKernelGGL(dist_fill_kernel<uint32_t>, dim3(blocks_for(R)), dim3(DT), 0, st, d_fc.get(), (uint64_t)R, NONE);
+    hipLaunchKernelGGL(dist_fill_kernel<uint32_t>, dim3(blocks_for(R)), dim3(DT), 0, st, d_row_end.get(), (uint64_t)R, L);
+    hipLaunchKernelGGL(dist_rows_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    // classify: tokens
+    HIP_TRY(hipMemsetAsync(d_wcnt.get(), 0, (NW + 1) * 4, st));
+    hipLaunchKernelGGL(dist_sep_count_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, p, d_wcnt.get());
+    HIP_TRY(hipGetLastError());
+    if (scan(d_wcnt.get(), d_wsep.get(), NW + 1)) return 1;
+    uint32_t M = 0;
+    HIP_TRY(hipMemcpyAsync(&M, d_wsep.get() + NW, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (M > L) return kmdb_set_error(std::string(who) + "internal error (more separators than bytes)");
+    p.M = M; p.wsep = d_wsep;
+    const auto declined = [&](unsigned int why) {
+        kmdb_set_error(std::string(who) + "declined: " + decline_text(why));
+        return KMDB_DISTANCE_DECLINED;
+    };
+    if (M == 0) return declined(DECL_NO_COMMA);                 // (R >= 1 here: no row has a comma)
+    DEV_ALLOC(d_sep_pos, (size_t)M); DEV_ALLOC(d_sep_row, (size_t)M); DEV_ALLOC(d_tok_val, (size_t)M); DEV_ALLOC(d_tok_flags, (size_t)M);
+    held += (uint64_t)M * 13;
+    p.sep_pos = d_sep_pos; p.sep_row = d_sep_row; p.tok_val = d_tok_val; p.tok_flags = d_tok_flags;
+    hipLaunchKernelGGL(dist_fill_kernel<uint32_t>, dim3(blocks_for((uint64_t)R + 1)), dim3(DT), 0, st, d_row_first.get(), (uint64_t)R + 1, M);
+    hipLaunchKernelGGL(dist_sep_write_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    // parse
+    hipLaunchKernelGGL(dist_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
+    hipLaunchKernelGGL(dist_parse_kernel, dim3(blocks_for(M)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
+    if (scan(d_oc.get(), d_oc.get(), (size_t)R + 1)) return 1;
+    if (scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1)) return 1;
+    unsigned int why = 0;
+    uint64_t n_cells = 0, fix_bytes = 0;
+    HIP_TRY(hipMemcpyAsync(&why, d_decline.get(), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_cells, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev[2], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (why) return declined(why);
+    if (fix_bytes > (uint64_t)L + 2ull * R) return kmdb_set_error(std::string(who) + "internal error (names longer than the text)");
+
+    // measure
+    p.n_cells = n_cells;
+    DEV_ALLOC(d_code, (size_t)n_cells); DEV_ALLOC(d_len, (size_t)n_cells + 1); DEV_ALLOC(d_off, (size_t)n_cells + 1);
+    held += n_cells * 17;
+    p.code = d_code; p.len = d_len; p.off = d_off;
+    if (n_cells) {
+        hipLaunchKernelGGL(dist_measure_kernel, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(d_len.get() + n_cells, 0, 1, st));
+    if (scan(d_len.get(), d_off.get(), (size_t)n_cells + 1)) return 1;
+    uint64_t cell_bytes = 0;
+    unsigned long long counters[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(&cell_bytes, d_off.get() + n_cells, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counters, d_counters.get(), 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (cell_bytes > n_cells * 64 || counters[2] > n_cells) return kmdb_set_error(std::string(who) + "internal error (the cells' text is longer than they can write)");
+
+    // format
+    const uint64_t out_bytes = fix_bytes + cell_bytes, n_host = counters[2];
+    DEV_ALLOC(d_out, (size_t)out_bytes); DEV_ALLOC(d_host, (size_t)n_host);
+    held += out_bytes + n_host * sizeof(HostCell);
+    if (n_cells) hipLaunchKernelGGL(dist_write_kernel, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p, d_out.get(), out_bytes, d_host.get(), n_host);
+    hipLaunchKernelGGL(dist_names_kernel, dim3(blocks_for((uint64_t)R * 64)), dim3(DT), 0, st, p, d_out.get(), out_bytes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[4], st));
+    char* text = (char*)malloc(std::max<uint64_t>(1, out_bytes));
+    if (!text) return kmdb_set_error(std::string(who) + "out of host memory");
+    std::vector<HostCell> cells;
+    int rc = [&]() -> int {
+        try { cells.resize(n_host); } catch (const std::exception&) { return kmdb_set_error(std::string(who) + "out of host memory"); }
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(text, d_out.get(), out_bytes, hipMemcpyDeviceToHost, st));
+        if (n_host) HIP_TRY(hipMemcpyAsync(cells.data(), d_host.get(), n_host * sizeof(HostCell), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ev[5], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    }();
+    uint64_t written = counters[1];
+    if (!rc) {
+        if (n_host) {
+            rc = dist_splice(d, cells, text, out_bytes, out, &written);
+            free(text);
+        } else { out->text = text; out->len = out_bytes; }
+    } else free(text);
+    if (rc) return rc;
+    out->rows = R;
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    d->st.rows += R; d->st.cells_read += counters[0]; d->st.cells_written += written; d->st.host_cells += n_host;
+    d->st.bytes_in += len; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
+    d->st.copy_ms += ms[0] + ms[4]; d->st.parse_ms += ms[1]; d->st.measure_ms += ms[2]; d->st.format_ms += ms[3];
+    return 0;
+}
+
+extern "C" int kmdb_distance_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t first_row, kmdb_distance_out* out) {
+    if (!d || !out || (len && !lines)) return kmdb_set_error("kmdb_distance_rows: null argument");
+    out->text = nullptr; out->len = 0; out->rows = 0;
+    int rc;
+    try {
+        rc = dist_rows(d, lines, len, first_row, out);
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string("kmdb_distance_rows: ") + e.what());
+    }
+    if (rc) kmdb_distance_out_free(out);
+    return rc;
+}

@@ -101,3 +101,18 @@ extern "C" size_t kmdbh_format_sparse_row(const char* name, uint64_t kmers, cons
     *p++ = '\n';
     return (size_t)(p - out);
 }
+
+// A measure in the distance console's notation (conversion.h:167-219 called with six decimals, :262-268): exactly 0 (and -0.0) is "0",
+// everything else the sign, the integer part and six decimals of the magnitude rounded half up.  The one definition: the device writes
+// the same digits for the cells it decides (distance.hip), the host's cells go through here.
+extern "C" size_t kmdbh_format_measure(double v, char* out) {
+    if (v == 0) { *out = '0'; return 1; }
+    char* p = out;
+    if (v < 0) { *p++ = '-'; v = -v; }
+    const unsigned long long x = (unsigned long long)(v * 1000000.0 + 0.5);
+    p += put_u64(x / 1000000ull, p);
+    *p++ = '.';
+    uint32_t f = (uint32_t)(x % 1000000ull);
+    for (int i = 5; i >= 0; --i) { p[i] = (char)('0' + f % 10u); f /= 10u; }
+    return (size_t)(p + 6 - out);
+}

@@ -1405,6 +1405,12 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
 // measure per cell.  Same row semantics as the reference: a dense triangle (first row named like the first sample, no counts
 // in it) keeps i values in row i, any other dense table whole rows; sparse input or -sparse give "column:value" pairs of the
 // non-zero counts that pass the filters; a bound without a criterion filters the chosen measure.
+// Two paths write the same bytes.  The host loop below takes one line at a time.  The device path (distance_on_device, kmdb_distance_*)
+// parses, measures and formats whole pieces of the table in HBM; the header lines, the names, the counts, the bounds and the triangle test
+// stay here.  KMDB_DISTANCE_DEVICE=1 forces the device path (no usable device: an error), KMDB_DISTANCE_DEVICE=0 or -host the host loop.
+// Otherwise the host loop runs, unless KMDB_DISTANCE_MIN_BYTES is set: then the device path takes a table of at least that many bytes when a
+// device is usable (the threshold has not been measured, so none is built in; no usable device: the host loop, silently).  A table the device
+// path declines (kmdb_amd.h) is announced on stderr and written by the host loop from the start, the output file reopened.
 
 // a measure in the reference's fixed notation (conversion.h:167-219, 262-268): exactly 0 is "0", everything else has six
 // decimals, rounded half up on the magnitude
@@ -1418,7 +1424,200 @@ size_t put_measure(double v, char* out) {
 }
 size_t put_uint(unsigned long long v, char* out) { return (size_t)std::snprintf(out, 24, "%llu", v); }
 
-int run_distance(std::vector<std::string>& args) {
+// ---- distance on the device (kmdb_distance_*) -----------------------------------------------------------------------------------------------
+// The body of the table goes through the device in pieces of whole lines (KMDB_DISTANCE_BYTES_PER_PIECE, default 256 MiB: a size chosen for
+// memory, not tuned; a longer line goes alone): a reader thread fills piece n + 1 and a writer thread writes piece n - 1 while piece n is
+// on the device.  What the host loop decides from the rows it has seen is decided here from the first piece: the triangle from row 0, sparse
+// input from the first row that has cells.  Rows in front of that row hold no cells and are written as the host loop writes them — as DENSE
+// rows when -sparse was not given (the loop turns to sparse output only at the first pair it meets), through a handle of their own.
+template <class T>
+class Channel {                                  // a bounded queue between two threads; close() from either side ends both
+public:
+    bool push(T&& v) {
+        std::unique_lock<std::mutex> l(m_);
+        cv_.wait(l, [&] { return closed_ || q_.size() < 2; });
+        if (closed_) return false;
+        q_.push_back(std::move(v));
+        cv_.notify_all();
+        return true;
+    }
+    bool pop(T& v) {
+        std::unique_lock<std::mutex> l(m_);
+        cv_.wait(l, [&] { return done_ || closed_ || !q_.empty(); });
+        if (closed_ || q_.empty()) return false;
+        v = std::move(q_.front());
+        q_.erase(q_.begin());
+        cv_.notify_all();
+        return true;
+    }
+    void finish() { std::lock_guard<std::mutex> l(m_); done_ = true; cv_.notify_all(); }      // the producer has no more
+    void close() { std::lock_guard<std::mutex> l(m_); closed_ = true; cv_.notify_all(); }      // give up: nobody waits any longer
+    template <class F> void drain(F&& f) { std::lock_guard<std::mutex> l(m_); for (auto& v : q_) f(v); q_.clear(); }   // what nobody took
+private:
+    std::mutex m_;
+    std::condition_variable cv_;
+    std::vector<T> q_;
+    bool done_ = false, closed_ = false;
+};
+
+struct DistanceSetup {
+    int device = 0, measure = 0;
+    uint32_t k = 0;
+    std::vector<uint32_t> counts;
+    std::vector<kmdb_cell_filter> filters;
+    bool sparse_out = false, phylip = false;
+    std::string first_name;                      // of the header's sample names; empty: none
+    bool has_names = false;
+};
+
+struct DistanceHandle {
+    kmdb_distance* d = nullptr;
+    ~DistanceHandle() { if (d) kmdb_distance_free(d); }
+    void begin(const DistanceSetup& s, uint32_t flags) {
+        kmdb_distance_opts o{};
+        o.abi_version = KMDB_ABI_VERSION; o.device = s.device; o.measure = s.measure; o.kmer_length = s.k;
+        o.counts = s.counts.data(); o.n = s.counts.size(); o.filters = s.filters.data(); o.n_filters = s.filters.size(); o.flags = flags;
+        check(kmdb_distance_begin(&o, &d));
+    }
+};
+
+// true: the output is written; false: the device path declined (why), the caller starts over with the host loop
+bool distance_on_device(const std::string& path, long long body, std::ostream& out, const DistanceSetup& s, std::string& why) {
+    size_t piece_bytes = 256ull << 20;
+    if (const char* e = std::getenv("KMDB_DISTANCE_BYTES_PER_PIECE")) piece_bytes = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    piece_bytes = std::min<size_t>(piece_bytes, 3ull << 30);
+    struct Piece { std::string text; bool last = false; };
+    struct Text { kmdb_distance_out o{}; };
+    Channel<Piece> pieces;
+    Channel<Text> texts;
+    std::string read_error;
+    std::thread reader([&]() {
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f || fseeko(f, (off_t)body, SEEK_SET)) { read_error = "Cannot open common k-mers table: " + path; if (f) std::fclose(f); pieces.close(); return; }
+        std::string buf;
+        size_t pos = 0;                                            // buf[pos ..): read and not yet handed on
+        bool eof = false;
+        for (bool last = false; !last;) {
+            size_t cut = std::string::npos;
+            for (;;) {
+                const size_t have = buf.size() - pos;
+                if (have >= piece_bytes || eof) {                   // the last line end inside the piece; none: the line goes alone, whatever its length
+                    const size_t lim = pos + std::min(have, piece_bytes);
+                    size_t nl = lim > pos ? buf.rfind('\n', lim - 1) : std::string::npos;
+                    if (nl == std::string::npos || nl < pos) nl = buf.find('\n', lim > pos ? lim - 1 : pos);
+                    if (nl != std::string::npos) { cut = nl + 1; break; }
+                    if (eof) { cut = buf.size(); break; }
+                }
+                buf.erase(0, pos);
+                pos = 0;
+                const size_t old = buf.size(), want = std::max<size_t>(old < piece_bytes ? piece_bytes - old : 0, 1 << 16);
+                buf.resize(old + want);
+                const size_t got = std::fread(&buf[old], 1, want, f);
+                buf.resize(old + got);
+                if (got < want) eof = true;
+            }
+            Piece p;
+            p.text.assign(buf, pos, cut - pos);
+            pos = cut;
+            last = p.last = eof && pos == buf.size();
+            if (!pieces.push(std::move(p))) break;
+        }
+        std::fclose(f);
+        pieces.finish();
+    });
+    bool write_failed = false;
+    std::thread writer([&]() {
+        Text t;
+        while (texts.pop(t)) {
+            if (t.o.len) out.write(t.o.text, (std::streamsize)t.o.len);
+            kmdb_distance_out_free(&t.o);
+            if (!out) { write_failed = true; texts.close(); pieces.close(); break; }
+        }
+    });
+    auto stop = [&]() { pieces.close(); texts.close(); reader.join(); writer.join(); texts.drain([](Text& t) { kmdb_distance_out_free(&t.o); }); };
+    DistanceHandle lead, body_handle;
+    uint64_t row = 0, lead_rows = 0;
+    bool decided = false, declined = false, triangle = false;
+    std::string pending;                                           // the rows seen before the first row with cells (they hold none), and that row's piece
+    size_t scanned = 0;
+    std::string error;
+    try {
+        Piece p;
+        while (pieces.pop(p)) {
+            const char* text = p.text.data();
+            size_t len = p.text.size();
+            if (!decided) {
+                // row 0: the triangle; the first row with cells: sparse or dense input
+                if (pending.empty()) pending = std::move(p.text); else pending += p.text;
+                bool sparse_in = false, found = false;
+                size_t at = scanned;
+                while (at < pending.size() && !found) {
+                    const char* b = pending.data() + at;
+                    const char* nl = (const char*)std::memchr(b, '\n', pending.size() - at);
+                    const char* end = nl ? nl : pending.data() + pending.size();
+                    const char* comma = std::find(b, end, ',');
+                    const char* q = comma < end ? comma + 1 : end;
+                    while (q < end && *q >= '0' && *q <= '9') ++q;
+                    if (q < end) ++q;
+                    unsigned long long v = 0;
+                    bool pair = false;
+                    if (end - q > 1) {
+                        found = true;
+                        while (q < end && *q >= '0' && *q <= '9') v = v * 10 + (unsigned)(*q++ - '0');
+                        pair = q < end && *q == ':';
+                        sparse_in = pair;
+                    }
+                    if (at == 0)
+                        triangle = !s.sparse_out && s.has_names && std::string(b, comma) == s.first_name && (s.counts.empty() || pair || (uint32_t)v == 0);
+                    if (!found) { ++lead_rows; at = (size_t)(end - pending.data()) + (nl ? 1 : 0); }
+                }
+                scanned = at;
+                if (!found && !p.last) continue;
+                decided = true;
+                text = pending.data();
+                len = pending.size();
+                const uint32_t tri = triangle ? KMDB_DISTANCE_TRIANGLE : 0u;
+                body_handle.begin(s, tri | (s.sparse_out ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (sparse_in ? KMDB_DISTANCE_SPARSE_IN : 0u) | (s.phylip ? KMDB_DISTANCE_PHYLIP : 0u));
+                if (sparse_in && !s.sparse_out && !s.phylip && lead_rows) {
+                    lead.begin(s, tri);
+                    Text t;
+                    const int rc = kmdb_distance_rows(lead.d, text, scanned, 0, &t.o);
+                    if (rc == KMDB_DISTANCE_DECLINED) { why = kmdb_last_error(); declined = true; break; }
+                    check(rc);
+                    if (!texts.push(std::move(t))) { kmdb_distance_out_free(&t.o); break; }
+                    row = lead_rows; text += scanned; len -= scanned;
+                }
+            }
+            Text t;
+            const int rc = kmdb_distance_rows(body_handle.d, text, len, row, &t.o);
+            if (rc == KMDB_DISTANCE_DECLINED) { why = kmdb_last_error(); declined = true; break; }
+            check(rc);
+            row += t.o.rows;
+            if (!texts.push(std::move(t))) { kmdb_distance_out_free(&t.o); break; }
+        }
+    } catch (std::exception& e) {
+        error = e.what();
+    }
+    if (declined || !error.empty()) { stop(); if (!error.empty()) throw std::runtime_error(error); return false; }
+    texts.finish();
+    reader.join();
+    writer.join();
+    if (!read_error.empty()) throw std::runtime_error(read_error);
+    if (write_failed) throw std::runtime_error("Cannot write the output table");
+    if (std::getenv("KMDB_VERBOSE"))
+        for (const DistanceHandle* h : {&lead, &body_handle}) {
+            kmdb_distance_stats st{};
+            if (!h->d || kmdb_distance_stats_get(h->d, &st)) continue;
+            std::cerr << "[kmdb] distance on the device: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
+                      << ", host cells " << st.host_cells << ", bytes in " << st.bytes_in << ", bytes out " << st.bytes_out << ", parse " << st.parse_ms
+                      << " ms, measure " << st.measure_ms << " ms, format " << st.format_ms << " ms, copies " << st.copy_ms << " ms" << std::endl;
+        }
+    return true;
+}
+
+
+int run_distance(std::vector<std::string>& args, const Common& c) {
+    const bool host_only = take_switch(args, "-host");
     bool sparse_out = take_switch(args, "-sparse");
     const bool phylip = take_switch(args, "-phylip-out");
     if (phylip) sparse_out = false;
@@ -1463,6 +1662,7 @@ int run_distance(std::vector<std::string>& args) {
     in >> tok >> k >> tok >> fraction >> tok;                  // "kmer-length: K fraction: F db-samples"
     std::getline(in, rest);                                    // ",name,name,..."
     if (!phylip) out << "kmer-length: " << k << " fraction: " << fraction << rest << std::endl;
+    const std::string header_rest = rest;
     std::vector<std::string> sample_names;
     {
         std::string t = rest;
@@ -1480,6 +1680,38 @@ int run_distance(std::vector<std::string>& args) {
     }
     const size_t n = db_counts.size();
     if (phylip) out << n << std::endl;
+
+    {
+        const char* forced = std::getenv("KMDB_DISTANCE_DEVICE");
+        const char* min_bytes = std::getenv("KMDB_DISTANCE_MIN_BYTES");
+        bool on_device = false;
+        if (host_only || (forced && forced[0] == '0')) on_device = false;
+        else if (forced && forced[0] == '1') {
+            if (kmdb_device_count() <= c.device) throw std::runtime_error("KMDB_DISTANCE_DEVICE=1: no usable GPU (device " + std::to_string(c.device) + ")");
+            on_device = true;
+        } else if (min_bytes) {
+            std::ifstream sz(args[0], std::ios::binary | std::ios::ate);
+            on_device = sz && (unsigned long long)sz.tellg() >= std::strtoull(min_bytes, nullptr, 10) && kmdb_device_count() > c.device;
+        }
+        const long long body = (long long)in.tellg();
+        if (on_device && body >= 0) {
+            DistanceSetup s;
+            s.device = c.device; s.measure = kmdbh_metric_id(measure_name.c_str()); s.k = k; s.counts = db_counts; s.sparse_out = sparse_out; s.phylip = phylip;
+            s.has_names = !sample_names.empty();
+            if (s.has_names) s.first_name = sample_names[0];
+            for (auto& kv : bounds) s.filters.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+            if (kmer_lo != 0 || kmer_hi != (long)std::numeric_limits<uint32_t>::max())
+                s.filters.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)kmer_lo, (double)kmer_hi});
+            std::string why;
+            out.flush();
+            if (distance_on_device(args[0], body, out, s, why)) { out.flush(); return 0; }
+            std::cerr << "WARNING: distance: the device path declined this table (" << why << "); the host loop runs" << std::endl;
+            out.close();
+            out.open(args[1]);                                     // from the start: the header lines again, then every row
+            if (!phylip) out << "kmer-length: " << k << " fraction: " << fraction << header_rest << std::endl;
+            else out << n << std::endl;
+        }
+    }
 
     auto pass = [&](uint32_t common, uint32_t qcnt, size_t col) {
         for (auto& kv : bounds) {
@@ -1555,7 +1787,7 @@ void usage() {
                  "    kmer-db-amd build -from-minhash <sample_list> <database>\n"
                  "    kmer-db-amd build -extend-from <old.db> [-from-minhash] [-multisample-fasta] [-host-extract] <sample_list | fasta> <database>\n"
                  "    kmer-db-amd all2all-parts [-min ...] [-max ...] <db_list> <common_table>\n"
-                 "    kmer-db-amd distance [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* <measure> <common_table> <output>\n"
+                 "    kmer-db-amd distance [-sparse] [-phylip-out] [-host] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* <measure> <common_table> <output>\n"
                  "Common options: -t <threads>, -gpu <device>\n"
                  "all2all / all2all-sp: -gpus <N>  the k-mer space in N prefix-bucket shards over the node's GPUs (from -gpu on), partial matrices\n"
                  "                                  summed by one RCCL reduce-scatter; more shards than devices: a device runs its shards in turn\n"
@@ -1569,6 +1801,8 @@ void usage() {
                  "build: the database is grown on the GPU from the samples in input order and written in the reference's format; -from-minhash takes\n"
                  "                   <sample>.minhash files (k and fraction from the files); -extend-from <old.db> starts from a stored database (its k,\n"
                  "                   fraction and alphabet; <database> may be <old.db>); -extend and -from-kmers are refused\n"
+                 "distance: KMDB_DISTANCE_DEVICE=1 parses, measures and formats the table on the GPU (-gpu <device>; same bytes); -host and\n"
+                 "                   KMDB_DISTANCE_DEVICE=0 keep it on the host, which is also what runs when neither is given\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
 }
 
@@ -1606,7 +1840,7 @@ int main(int argc, char** argv) {
         if (mode == "new2all") return run_new2all(args, c);
         if (mode == "one2all") return run_one2all(args, c);
         if (mode == "all2all-parts") return run_all2all_parts(args, c);
-        if (mode == "distance") return run_distance(args);
+        if (mode == "distance") return run_distance(args, c);
         if (mode == "minhash") return run_minhash(args, c);
         if (mode == "build") return run_build(args, c);
         usage();
