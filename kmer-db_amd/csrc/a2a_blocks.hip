@@ -18,7 +18,7 @@
 //                            lanes, earlier ones from a chain table in LDS (one slot per depth).  Emits the records of those
 //                            nodes (first-block diagonal records into per-block stream chunks, the others into the wide pool),
 //                            flags the nodes with more blocks and leaves them their parent's summary.
-//       wide list            the flagged nodes, compacted (popcount + scan + expand)
+//       wide list            the flagged nodes, compacted: the narrow kernel counts them per word and slice, one workgroup scans the slices, expand
 //   K1g k1g_kernel           one lane per wide node: list = parent's list (row in LDS, chain table, or a climb) + own pairs;
 //                            the records of a batch are numbered by a prefix sum and emitted one per lane from a descriptor
 //                            queue into the wide pool, in arrival order; heavy nodes by the whole wave.
@@ -263,11 +263,19 @@ __device__ __forceinline__ Resv arena_reserve(WaveArena& A, const PoolView& pv, 
     return r;
 }
 template <class PV> __device__ __forceinline__ void arena_finish(const WaveArena& A, const PV& pv, uint32_t lane) {
-    if (A.tmask == 0) return;                                   // no stream table (never-written slots of the wide pool keep their 0xFFFFFFFF key)
+    if (A.tmask == 0) return;                                   // no stream table
     for (uint32_t e = lane; e <= A.tmask; e += WAVE) {
         const uint32_t v = A.t_slot[e];
         if (v != KEY_NONE && (A.direct || A.t_key[e] != KEY_NONE)) pool_cold(pv)->chunk_fill[v >> CH_SHIFT] = v & (CH_REC - 1u);
     }
+}
+// Few streams: the key array of the wide pool is NOT filled before a call.  A slot holds a record of this call iff its chunk was handed out (its index
+// inside its sub-pool lies below the sub-pool's cursor: the sort tests that, cs_chunks_handed) and the wave that took the chunk wrote the slot.  What a
+// wave took and did not write — the tail of its one open chunk and the chunks left of its last grab — gets the "never written" key here: at most
+// WIDE_GRAB stores per wave.  Every kernel instantiation that reserves slots of the wide pool ends with this call.
+template <class PV> __device__ __forceinline__ void arena_finish_wide(const WaveArena& A, const PV& pv, uint32_t lane) {
+    if (A.dopen && lane < WCH_REC - (A.dslot & (WCH_REC - 1u))) pv.wkey[A.dslot + lane] = KEY_NONE;
+    for (uint32_t k = 0; k < A.wstock; ++k) pv.wkey[(((A.wnext + k) * KMDB_SUBPOOLS + A.wsub) << WCH_SHIFT) + lane] = KEY_NONE;
 }
 
 // diagonal streams (X == Y, cols == rows) pack 8-byte rows into the first half of their chunks
@@ -397,9 +405,14 @@ __device__ __forceinline__ void rec_store_diag(const PoolView& pv, uint32_t slot
     pv.recw[slot] = w;
 }
 
-__global__ void fill_u32_kernel(uint32_t* __restrict__ p, uint32_t n, uint32_t v) {
+// the start of a call in ONE launch: the first n_state words of the per-call state (BlocksState::call_state) cleared, every chunk of the chunk table
+// empty and never opened, and — the first attempt of a call — no tile flagged as touched
+__global__ void call_prologue_kernel(uint32_t* __restrict__ state, uint32_t n_state, uint32_t* __restrict__ chunk_fill, uint32_t* __restrict__ chunk_key,
+                                     uint32_t pool_cap, unsigned char* __restrict__ touched, uint32_t n_touched) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
+    if (i < n_state) state[i] = 0u;
+    if (i < pool_cap) { chunk_fill[i] = 0u; chunk_key[i] = 0xFFFFFFFFu; }
+    if (i < n_touched) touched[i] = 0;
 }
 __global__ void iota_u32_kernel(uint32_t* __restrict__ p, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -761,6 +774,8 @@ struct NParams {
     ulonglong2* fn_mask;           // written for the nodes with more than two blocks whose parent has at most two:
     uint32_t* fn_blk;              // the parent's (blocks, masks)
     unsigned long long* widebits;
+    uint32_t* wide_base;           // [ceil(P / 64)] flagged nodes of the SLICE before every 64-node word (wide_expand_kernel adds the slices before it)
+    uint32_t* wide_slice_cnt;      // [n_segs] flagged nodes of every slice
     uint32_t P, nseg_nodes, n_segs, chain_cap;
     uint32_t emit_lo, emit_hi;
     uint32_t tbits, n_keys;        // log2 of the open-chunk table, blocks
@@ -899,6 +914,7 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
     k2_v16i c00 = {}, c10 = {}, c11 = {};
     uint32_t curX = BNONE, n_direct = 0;
     uint32_t flat_n = 0;                                             // flat mode: records of the slice so far (wave-uniform)
+    uint32_t n_flagged = 0;                                          // nodes with more than two blocks in the slice so far (wave-uniform)
     auto dflush = [&]() {
         // one HBM atomic per non-zero cell (D layout of the MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)).  Cell (rb + r, rb + c)
         // of the triangle sits at tri64(rb) + rb + [rb r + r (r - 1) / 2 + c]: a wave-uniform base and a 32-bit offset per lane
@@ -947,8 +963,10 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
         const uint32_t w0 = S.bw & 0x7FFFu, w1 = (S.bw >> 15) & 0x7FFFu;
         const unsigned long long F0 = S.m0, F1 = w1 != BNONE ? S.m1 : 0ull;
         {
+            // (the wide list's prefix sums start here: the flagged nodes of the slice so far, wave-uniform, beside the bits)
             const unsigned long long wb = __ballot(wide);
-            if (lane == 0) q.widebits[base >> 6] = wb;
+            if (lane == 0) { q.widebits[base >> 6] = wb; q.wide_base[base >> 6] = n_flagged; }
+            n_flagged += (uint32_t)__popcll(wb);
         }
         if (__ballot(wide)) {
             // a node with more blocks whose parent still has at most two takes the parent's (blocks, masks) along: the wide
@@ -1071,8 +1089,10 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
     KARG(NParams) qe = kernarg_reread<NParams>();                        // (the slice's end)
     if (DIRECT && lane == 0 && n_direct) atomicAdd(&qe->direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], n_direct);
     if (FLAT && lane == 0) { qe->slice_cnt[seg] = flat_n; if (flat_n) atomicAdd(&qe->direct_ctr[(seg % KMDB_SUBPOOLS) * 16u], flat_n); }
+    if (lane == 0) qe->wide_slice_cnt[seg] = n_flagged;
     if constexpr (MODE == 0) arena_finish(A, q.pool, lane);               // (the other modes open no stream chunk)
     if constexpr (ROWS) rowtab_finish(RT, pv, lane);
+    else arena_finish_wide(A, pv, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1203,23 +1223,83 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // ------------------------------------------------------------------------------------------
 // wide list: compaction of the flagged nodes
 // ------------------------------------------------------------------------------------------
-__global__ void wide_count_kernel(const unsigned long long* __restrict__ bits, uint32_t n_words, uint32_t* __restrict__ cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_words) cnt[i] = (uint32_t)__popcll(bits[i]);
-    else if (i == n_words) cnt[i] = 0;
+// The narrow kernel leaves, beside the bits, the flagged nodes of the slice before every word (wide_base) and the slice's total (slice_cnt): what is
+// left of the prefix sums is the scan of the slice totals — some 50 000 numbers at C2 — in ONE workgroup: every wave takes a contiguous share, sums
+// it (coalesced, eight loads under way: the kernel is one workgroup waiting for its loads), the 16 wave totals are scanned, and the wave goes over its share again with a wave scan per 64 totals.
+// slice_base[s] = flagged nodes before slice s, slice_base[n_segs] = KCTR_NWIDE = wide_base[n_words] = all of them.
+constexpr uint32_t WSL_THREADS = 1024;
+__global__ __launch_bounds__(WSL_THREADS) void wide_slices_kernel(const uint32_t* __restrict__ slice_cnt, uint32_t n_segs, uint32_t* __restrict__ slice_base,
+                                                                   uint32_t* __restrict__ wide_base, uint32_t n_words, uint32_t* __restrict__ counters) {
+    __shared__ uint32_t wtot[WSL_THREADS / WAVE];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t NW = WSL_THREADS / WAVE;
+    const uint32_t share = ((n_segs + NW - 1u) / NW + 63u) & ~63u;          // a multiple of 64 per wave
+    const uint32_t lo = wave * share < n_segs ? wave * share : n_segs;
+    const uint32_t hi = n_segs - lo < share ? n_segs : lo + share;
+    constexpr uint32_t U = 8;
+    uint32_t sum = 0;
+    for (uint32_t i0 = lo; i0 < hi; i0 += U * WAVE) {
+        uint32_t v[U];
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) { const uint32_t i = i0 + j * WAVE + lane; v[j] = i < hi ? slice_cnt[i] : 0u; }
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) sum += v[j];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, WAVE);
+    if (lane == 0) wtot[wave] = sum;
+    __syncthreads();
+    uint32_t run = 0, total = 0;
+    for (uint32_t k = 0; k < NW; ++k) { const uint32_t t = wtot[k]; if (k < wave) run += t; total += t; }
+    for (uint32_t i0 = lo; i0 < hi; i0 += U * WAVE) {
+        uint32_t v[U];
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) { const uint32_t i = i0 + j * WAVE + lane; v[j] = i < hi ? slice_cnt[i] : 0u; }
+#pragma unroll
+        for (uint32_t j = 0; j < U; ++j) {
+            const uint32_t i = i0 + j * WAVE + lane;
+            const uint32_t incl = wave_incl_scan(v[j], lane);
+            if (i < hi) slice_base[i] = run + incl - v[j];
+            run += bcast(incl, WAVE - 1u);
+        }
+    }
+    if (threadIdx.x == 0) { slice_base[n_segs] = total; wide_base[n_words] = total; counters[KCTR_NWIDE] = total; }
 }
-__global__ void wide_expand_kernel(const unsigned long long* __restrict__ bits, const uint32_t* __restrict__ base, uint32_t n_words,
-                                   uint32_t* __restrict__ widx, uint32_t cap, uint32_t* __restrict__ counters) {
+// The wide list itself: word i's flagged nodes go to widx[slice_base[its slice] + wide_base[i] ...], and wide_base[i] becomes the absolute prefix the
+// wide kernel reads.  SERIAL (the default): a thread per word walks its bits.  Otherwise (KMDB_WIDE_EXPAND=wave, A/B) one wave per 64 words: the words that
+// have a flagged node are taken one after the other by the whole wave, lane k writes node k at its rank among the word's bits, so the stores of a word are
+// contiguous — at C2, where most words hold a few flagged nodes, that is 64 turns of a wave for 64 words against half a dozen per thread, and it measured
+// slower beside k2d_kernel.  slice_shift: log2 of the words per slice (0xFFFFFFFF: not a power of two, divide).
+template <bool SERIAL>
+__global__ __launch_bounds__(256) void wide_expand_kernel(const unsigned long long* __restrict__ bits, uint32_t* __restrict__ base, const uint32_t* __restrict__ slice_base,
+                                                          uint32_t words_per_slice, uint32_t slice_shift, uint32_t n_words, uint32_t* __restrict__ widx, uint32_t cap) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) counters[KCTR_NWIDE] = base[n_words];
-    if (i >= n_words) return;
-    unsigned long long b = bits[i];
-    uint32_t o = base[i];
-    while (b) {
-        const uint32_t k = (uint32_t)__builtin_ctzll(b);
-        b &= b - 1;
-        if (o < cap) widx[o] = i * 64u + k;
-        ++o;
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long b = 0;
+    uint32_t o = 0;
+    if (i < n_words) {
+        b = bits[i];
+        o = slice_base[slice_shift != 0xFFFFFFFFu ? i >> slice_shift : i / words_per_slice] + base[i];
+        base[i] = o;
+    }
+    if (SERIAL) {
+        while (b) {
+            const uint32_t k = (uint32_t)__builtin_ctzll(b);
+            b &= b - 1;
+            if (o < cap) widx[o] = i * 64u + k;
+            ++o;
+        }
+        return;
+    }
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    unsigned long long todo = __ballot(b != 0ull);
+    const uint32_t w0 = i - lane;
+    while (todo) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        const unsigned long long bj = ((unsigned long long)bcast((uint32_t)(b >> 32), j) << 32) | bcast((uint32_t)b, j);
+        const uint32_t p = bcast(o, j) + (uint32_t)__popcll(bj & lt_mask);
+        if (((bj >> lane) & 1ull) && p < cap) widx[p] = (w0 + j) * 64u + lane;
     }
 }
 
@@ -1753,6 +1833,7 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
     }
     arena_finish(A, pv, lane);
     if constexpr (ROWS) rowtab_finish(RT, pv, lane);
+    else arena_finish_wide(A, pv, lane);
     if (lane == 0 && n_miss) atomicAdd(&pool_cold(pv)->counters[KCTR_SLOW], n_miss);
     if constexpr (L2) if (lane == 0 && l2_nodes) atomicAdd(&pool_cold(pv)->counters[KCTR_L2_NODES], l2_nodes);
 }
@@ -2195,7 +2276,6 @@ __global__ void count_chunks_kernel(const uint32_t* __restrict__ sorted_key, uin
     while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (sorted_key[mid] < n_states) lo = mid + 1; else hi = mid; }
     counters[KCTR_CHUNKS] = lo;
 }
-// slots of the wide pool in use = the busiest sub-pool's share of all
 // chunks of the chunk pool in use = the busiest sub-pool's share of all (one wave: a maximum over the 256 cursors)
 __global__ void pool_used_kernel(const uint32_t* __restrict__ sub_cursor, const uint32_t* __restrict__ direct_ctr, uint32_t* __restrict__ counters) {
     uint32_t mx = 0, nd = 0;
@@ -2204,10 +2284,14 @@ __global__ void pool_used_kernel(const uint32_t* __restrict__ sub_cursor, const 
     for (int d = 32; d >= 1; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, WAVE)); nd += (uint32_t)__shfl_xor((int)nd, d, WAVE); }
     if (threadIdx.x == 0) { counters[KCTR_POOL_USED] = mx * KMDB_SUBPOOLS; counters[KCTR_DIRECT] = nd; }
 }
-__global__ void count_raw_kernel(const uint32_t* __restrict__ wsub_cursor, uint32_t* __restrict__ counters) {
+// chunks of the wide pool in use, the same way (one wave) — and the 256 cursors side by side, clamped to the chunks a sub-pool holds, for the sort
+// (cs_chunks_handed)
+__global__ void count_raw_kernel(const uint32_t* __restrict__ wsub_cursor, uint32_t wsub_cap, uint32_t* __restrict__ counters, uint32_t* __restrict__ handed) {
     uint32_t mx = 0;
-    for (uint32_t p = 0; p < KMDB_SUBPOOLS; ++p) mx = max(mx, wsub_cursor[p * 16u]);
-    counters[KCTR_RAW] = mx * KMDB_SUBPOOLS;                    // chunk ids below this bound cover every written record
+    for (uint32_t p = threadIdx.x; p < KMDB_SUBPOOLS; p += 64u) { const uint32_t c = wsub_cursor[p * 16u]; mx = max(mx, c); handed[p] = c < wsub_cap ? c : wsub_cap; }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, WAVE));
+    if (threadIdx.x == 0) counters[KCTR_RAW] = mx * KMDB_SUBPOOLS;                    // chunk ids below this bound cover every written record
 }
 
 // Counting sort of the wide pool by stream: per-workgroup histograms in LDS (no device atomics), one exclusive scan over the
@@ -2279,19 +2363,39 @@ __global__ void cs_rows_kernel(const uint32_t* __restrict__ O1, uint32_t NB, uin
         row_blk[NB] = blk; row_tab[NB] = tab;
     }
 }
+// The all2all call's wide pool (wcur != nullptr: the chunks handed out by each of its 256 sub-pools, count_raw_kernel) comes WITHOUT pre-filled key
+// words: a slot counts only if its chunk was handed out — chunk c is number c / KMDB_SUBPOOLS of sub-pool c % KMDB_SUBPOOLS (arena_take_wide), handed out
+// iff that number lies below the sub-pool's cursor; what a wave took and did not write holds KEY_NONE (arena_finish_wide).  The cursors are loaded
+// into LDS once per workgroup; per 2048 slots — 32 chunks, the workgroups' shares start at multiples of 1024 slots — one LDS read and a ballot give the
+// wave a 32-bit mask, the test of a thread's slot is a bit of it (the four waves of a pass of 256 slots hold one chunk each).
+__device__ __forceinline__ void cs_load_cursors(uint32_t* cur, const uint32_t* __restrict__ wcur) {
+    if (!wcur) return;
+    for (uint32_t k = threadIdx.x; k < KMDB_SUBPOOLS; k += blockDim.x) cur[k] = wcur[k];
+    __syncthreads();
+}
+__device__ __forceinline__ uint32_t cs_chunks_handed(const uint32_t* cur, bool masked, uint32_t t0) {
+    if (!masked) return 0xFFFFFFFFu;
+    const uint32_t c = (t0 >> WCH_SHIFT) + (threadIdx.x & 31u);
+    return (uint32_t)__ballot(c / KMDB_SUBPOOLS < cur[c % KMDB_SUBPOOLS]);
+}
+static_assert(WCH_REC == 64, "cs_chunks_handed: a wave's 64 consecutive slots are one chunk of the wide pool");
 __global__ __launch_bounds__(256) void cs_hist_kernel(const uint32_t* __restrict__ wkey, uint32_t n, uint32_t n_valid, uint32_t n_keys, int mode, const CsRows rows,
-                                                     uint32_t kmask, uint32_t* __restrict__ H) {
+                                                     uint32_t kmask, uint32_t* __restrict__ H, const uint32_t* __restrict__ wcur) {
     extern __shared__ uint32_t cs_lds[];
+    __shared__ uint32_t cs_cur[KMDB_SUBPOOLS];
     const CsJob job = cs_job(mode, n, n_keys, rows);
+    cs_load_cursors(cs_cur, wcur);
     for (uint32_t k = threadIdx.x; k < job.n_bins; k += blockDim.x) cs_lds[k] = 0;
     __syncthreads();
+    const uint32_t wv = threadIdx.x >> 6;
     // eight key words per thread requested together (the loop used to wait for one load per iteration)
     for (uint32_t i0 = job.lo; i0 < job.hi; i0 += 8u * blockDim.x) {
+        const uint32_t handed = cs_chunks_handed(cs_cur, wcur != nullptr, i0);
         uint32_t kw[8];
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j) {
             const uint32_t i = i0 + j * blockDim.x + threadIdx.x;
-            kw[j] = i < job.hi ? wkey[i] : 0xFFFFFFFFu;
+            kw[j] = (i < job.hi && ((handed >> (4u * j + wv)) & 1u)) ? wkey[i] : 0xFFFFFFFFu;
         }
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j) {
@@ -2310,8 +2414,10 @@ constexpr uint32_t CS_TILE = 2048, CS_THREADS = 256;
 __host__ __device__ inline size_t cs_scatter_lds(uint32_t n_keys, bool packed) { return (size_t)CS_TILE * (sizeof(WideRec) + (packed ? 4 : 8)) + (size_t)n_keys * 12 + CS_THREADS * 4 + 64; }
 __global__ __launch_bounds__(CS_THREADS) void cs_scatter_kernel(const uint32_t* __restrict__ wkey, const WideRec* __restrict__ wrec, uint32_t n, uint32_t n_valid,
                                                          uint32_t n_keys, int mode, const CsRows rows, uint32_t kmask, const uint32_t* __restrict__ O,
-                                                         uint32_t* __restrict__ swkey, WideRec* __restrict__ swrec, uint32_t packed) {
+                                                         uint32_t* __restrict__ swkey, WideRec* __restrict__ swrec, uint32_t packed,
+                                                         const uint32_t* __restrict__ wcur) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
+    __shared__ uint32_t cs_cur[KMDB_SUBPOOLS];                            // (wcur: see cs_hist_kernel)
     WideRec* st_rec = (WideRec*)cs_raw;                                   // [CS_TILE]
     uint32_t* st_dst = (uint32_t*)(st_rec + CS_TILE);                     // [CS_TILE] global destination
     uint32_t* st_key = st_dst + CS_TILE;                                  // [CS_TILE]; not there for packed records: their key words (the stream only) stay behind
@@ -2327,14 +2433,18 @@ __global__ __launch_bounds__(CS_THREADS) void cs_scatter_kernel(const uint32_t* 
     // keys and records are fetched together, and the next tile's before this one is staged (one round trip per tile, under way early)
     uint32_t nkw[PER];
     WideRec nrec[PER];
+    const uint32_t wv = threadIdx.x >> 6;
     auto fetch = [&](uint32_t t0) {
+        const uint32_t handed = cs_chunks_handed(cs_cur, wcur != nullptr, t0);
 #pragma unroll
         for (uint32_t j = 0; j < PER; ++j) {
             const uint32_t i = t0 + j * CS_THREADS + threadIdx.x;
             nkw[j] = 0xFFFFFFFFu; nrec[j] = WideRec{0ull, 0ull};
-            if (i < hi) { nkw[j] = wkey[i]; nrec[j] = wrec[i]; }
+            if (i < hi && ((handed >> (4u * j + wv)) & 1u)) { nkw[j] = wkey[i]; nrec[j] = wrec[i]; }
         }
     };
+    static_assert(PER * (CS_THREADS / 64u) == 32u, "cs_chunks_handed covers the 32 chunks of a tile");
+    cs_load_cursors(cs_cur, wcur);
     if (lo < hi) fetch(lo);
     for (uint32_t t0 = lo; t0 < hi; t0 += CS_TILE) {
         for (uint32_t k = threadIdx.x; k < nb; k += CS_THREADS) hist[k] = 0;
@@ -2883,12 +2993,12 @@ struct BlocksState {
     DevBuf<uint16_t> pair_blk;      // extra pairs, KMDB_PAIR_REGIONS sub-pools
     DevBuf<unsigned long long> pair_mask;
     uint64_t pair_cap = 0;          // entries in total
-    DevBuf<uint32_t> pair_cursor;           // [KMDB_PAIR_REGIONS * 16] one cursor per region, a cache line apart
+    uint32_t* pair_cursor = nullptr;        // [(KMDB_PAIR_REGIONS + 1) * 16] one cursor per region, a cache line apart (in call_state)
     DevBuf<ulonglong2> fn_mask;     // [P] for a node with more than two blocks whose parent has at most two: the parent's (F0, F1)
     DevBuf<uint32_t> fn_blk;        // [P] and its blocks: first | second << 16 (0xFFFF: none)
     DevBuf<unsigned long long> widebits;     // [ceil(P / 64)] nodes with more than two blocks
-    DevBuf<uint32_t> wide_cnt;      // [words + 1] popcounts / their exclusive scan
-    DevBuf<uint32_t> wide_base;
+    DevBuf<uint32_t> wide_base;     // [words + 1] wide nodes before every word: the narrow kernel writes them per slice, wide_expand_kernel makes them absolute
+    DevBuf<uint32_t> wide_slice_cnt, wide_slice_base;   // [n_nsegs] wide nodes of every slice of the narrow kernel, [n_nsegs + 1] their exclusive scan
     DevBuf<uint32_t> widx;          // [wide_cap] the wide nodes, DFS order
     DevBuf<uint32_t> wrun_anc;      // [runs][chain_cap] root path of the first node of every run of the wide-node kernel (built by every call)
     DevBuf<uint32_t> wrun_anc_n;
@@ -2903,7 +3013,7 @@ struct BlocksState {
     DevBuf<unsigned char> rec;      // [pool_cap * 64] 16-byte record slots ({rows, cols}; diagonal streams pack 8-byte rows)
     DevBuf<uint32_t> recw;          // [pool_cap * 64] weights of the classes with w > 1
     uint64_t pool_cap = 0;          // chunks of 64 records, KMDB_SUBPOOLS interleaved sub-pools
-    DevBuf<uint32_t> sub_cursor;    // [KMDB_SUBPOOLS * 16]
+    uint32_t* sub_cursor = nullptr; // [KMDB_SUBPOOLS * 16] (in call_state)
     // wide pool: records in arrival order + a device-wide sort by stream (the wide kernel always; the narrow kernel if its
     // per-stream chunks do not work out)
     bool dense_wide = false, dense_narrow = false;
@@ -2914,20 +3024,22 @@ struct BlocksState {
     DevBuf<unsigned long long> dmask;       // mode 2: [n_nsegs * nseg_nodes] F0 of the slice's records
     DevBuf<uint32_t> dwx;                   //         w | X << 8
     DevBuf<uint32_t> slice_cnt;             //         [n_nsegs] records of every slice
-    DevBuf<uint32_t> direct_ctr;    // [KMDB_SUBPOOLS * 16] records applied directly, counted per wave on spread addresses
+    uint32_t* direct_ctr = nullptr; // [KMDB_SUBPOOLS * 16] records applied directly, counted per wave on spread addresses (in call_state)
     uint64_t last_n_direct = 0;
     DevBuf<uint32_t> wkey, swkey;     // wide pool: stream of every record slot (0xFFFFFFFF = never written), and sorted
     DevBuf<WideRec> wrec, swrec;       // wide pool: 16-byte records {rows, cols} (weight digit in the key word), and sorted by stream
     uint64_t wide_pool_cap = 0;     // chunks of 64 records
-    DevBuf<uint32_t> wsub_cursor;
-    DevBuf<uint32_t> run_ctr;       // wide-node kernel: next run of every class
+    uint32_t* wsub_cursor = nullptr;                   // (in call_state)
+    DevBuf<uint32_t> wide_handed;     // [KMDB_SUBPOOLS] chunks every sub-pool of the wide pool handed out in this call (count_raw_kernel, for the sort)
+    uint32_t* run_ctr = nullptr;    // wide-node kernel: next run of every class (in call_state)
     // many streams ("row mode"): the wide records go to per-block-row chunks of the chunk pool; the chunk table grouped by key, then a
     // counting sort inside every row
     bool row_mode = false;
     uint32_t rec_pshift = 0;        // many streams, block width <= 54: the weight digit of a block record lives in the spare bits of its column mask (from
                                     // this bit on) and the record travels as 16 bytes; 0: 16 bytes of masks + the 4-byte key word
     uint32_t n_ckeys = 0;                              // keys of the chunk table: streams (+ block rows in row mode); n_ckeys = never opened
-    DevBuf<uint32_t> ct_hist, ct_offs, ct_cursor;   // [n_ckeys + 2]
+    uint32_t* ct_hist = nullptr;                       // [n_ckeys + 2] (in call_state)
+    DevBuf<uint32_t> ct_offs, ct_cursor;            // [n_ckeys + 2]
     DevBuf<void> ct_tmp;
     size_t ct_tmp_bytes = 0;
     DevBuf<uint32_t> rg_hist, rg_offs;   // row chunks grouped by row: [NB][rg_blocks] counts / offsets (+ total)
@@ -2946,7 +3058,11 @@ struct BlocksState {
     DevBuf<uint32_t> cs_hist, cs_offs;   // counting sort of the wide pool: [stream][block] counts / offsets (+ total)
     DevBuf<void> cs_tmp;
     size_t cs_tmp_bytes = 0;
-    DevBuf<uint32_t> counters;      // [KCTR_COUNT]
+    // What every call starts from zero lies in ONE array, cleared by the call's first launch (call_prologue_kernel): the counters, the cursors of the
+    // sub-pools, the run and direct counters, the chunk table's histogram and — last, cleared only by a call that decodes — the pair pool's cursors.
+    DevBuf<uint32_t> call_state;
+    uint32_t call_state_n = 0, call_state_n_decode = 0;    // words a call clears: without / with the pair cursors
+    uint32_t* counters = nullptr;   // [KCTR_COUNT] (in call_state)
     uint32_t* h_counters = nullptr; // pinned host copy
     // ---- second level above the block records (a2a_blocks.hip, L2View): the nodes with many blocks write (node, block, mask) entries instead of
     // their c (c + 1) / 2 records; a tile job joins two blocks' lists and applies the matches.  Row mode with few enough blocks only.
@@ -2966,8 +3082,6 @@ struct BlocksState {
     uint32_t n_slices = 1;          // passes over the pattern stream per call (a database whose records do not fit one)
     struct SliceCounts { bool valid = false; uint32_t lo = 0, hi = 0, n_wide = 0, n_chunks = 0, n_raw = 0, n_rowjobs = 0, n_sorted = 0, n_k2jobs = 0; };
     std::vector<SliceCounts> slice_counts;   // what the previous call found, per slice of the pattern stream
-    DevBuf<void> scan_tmp;
-    size_t scan_tmp_bytes = 0;
     DevBuf<unsigned char> tile_touched;      // [n_states] != 0: the last call's apply kernels added something to the tile of that block pair (the sparse
                                              // entry point scans only those tiles)
     DevBuf<uint32_t> k2j_start;     // [n_states + 1] many streams: where every stream starts in the sorted arrays
@@ -3196,11 +3310,12 @@ int kmdb_rect_sort_apply(hipStream_t st, uint32_t* wkey, void* wrec, uint32_t ns
         HIP_TRY(prim::exclusive_sum(nullptr, tb, hist.get(), offs.get(), (int)ne, st));
         DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
         const CsRows no_rows{};
-        hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), n_states * 4, st, wkey, nslots, n_states, n_states, (int)CS_BY_STREAM, no_rows, kmask, hist);
+        hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), n_states * 4, st, wkey, nslots, n_states, n_states, (int)CS_BY_STREAM, no_rows, kmask, hist,
+                           (const uint32_t*)nullptr);              // (this pool's key words are filled by its owner)
         HIP_TRY(prim::exclusive_sum(tmp, tb, hist.get(), offs.get(), (int)ne, st));
         HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(n_states, false)));
         hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(n_states, false), st, wkey, (const WideRec*)wrec, nslots, n_states, n_states,
-                           (int)CS_BY_STREAM, no_rows, kmask, offs, swkey, swrec, 0u);
+                           (int)CS_BY_STREAM, no_rows, kmask, offs, swkey, swrec, 0u, (const uint32_t*)nullptr);
         total_ptr = offs + (ne - 1);
     } else {
         size_t tb = 0;
@@ -3295,16 +3410,28 @@ static int blocks_prepare_impl(kmdb_db* db) {
     DEV_ALLOC(b.p0_mask, P);
     DEV_ALLOC(b.p0_info, P);
     DEV_ALLOC(b.pair_ofs, P);
-    DEV_ALLOC(b.pair_cursor, (KMDB_PAIR_REGIONS + 1) * 16);
     DEV_ALLOC(b.fn_mask, P);
     DEV_ALLOC(b.fn_blk, P);
     const uint64_t n_words = (P + 63) / 64;
     DEV_ALLOC(b.widebits, n_words);
-    DEV_ALLOC(b.wide_cnt, n_words + 1);
     DEV_ALLOC(b.wide_base, n_words + 1);
-    HIP_TRY(prim::exclusive_sum(nullptr, b.scan_tmp_bytes, b.wide_cnt.get(), b.wide_base.get(), (int)(n_words + 1)));
-    DEV_ALLOC(b.scan_tmp, std::max<size_t>(b.scan_tmp_bytes, 16));
-    DEV_ALLOC(b.counters, KCTR_COUNT);
+    DEV_ALLOC(b.wide_slice_cnt, std::max<size_t>(db->n_nsegs, 1));
+    DEV_ALLOC(b.wide_slice_base, (size_t)db->n_nsegs + 1);
+    DEV_ALLOC(b.wide_handed, KMDB_SUBPOOLS);
+    {
+        // the per-call state at fixed offsets (the chunk table's keys are the streams: b.n_ckeys below)
+        uint32_t o = 0;
+        auto take = [&](uint32_t n) { const uint32_t at = o; o += (n + 15u) & ~15u; return at; };
+        const uint32_t o_ctr = take(KCTR_COUNT), o_sub = take(KMDB_SUBPOOLS * 16), o_wsub = take(KMDB_SUBPOOLS * 16), o_run = take(K1W_CTRS * 16),
+                       o_dir = take(KMDB_SUBPOOLS * 16), o_cth = take(b.n_states + 2);
+        b.call_state_n = o;
+        const uint32_t o_pair = take((KMDB_PAIR_REGIONS + 1) * 16);
+        b.call_state_n_decode = o;
+        DEV_ALLOC(b.call_state, o);
+        uint32_t* s = b.call_state;
+        b.counters = s + o_ctr; b.sub_cursor = s + o_sub; b.wsub_cursor = s + o_wsub; b.run_ctr = s + o_run; b.direct_ctr = s + o_dir; b.ct_hist = s + o_cth;
+        b.pair_cursor = s + o_pair;
+    }
     HIP_TRY(hipHostMalloc((void**)&b.h_counters, KCTR_COUNT * 4));
     phase("per-node arrays (hipMalloc)");
     {
@@ -3328,10 +3455,6 @@ static int blocks_prepare_impl(kmdb_db* db) {
         if (alloc_pair_pool(b, std::max<uint64_t>(est_pairs * 2 + P / 4, (uint64_t)KMDB_PAIR_REGIONS * 64))) return 1;
     }
     phase("pair estimate + pair pool");
-    DEV_ALLOC(b.sub_cursor, KMDB_SUBPOOLS * 16);
-    DEV_ALLOC(b.wsub_cursor, KMDB_SUBPOOLS * 16);
-    DEV_ALLOC(b.run_ctr, K1W_CTRS * 16);
-    DEV_ALLOC(b.direct_ctr, KMDB_SUBPOOLS * 16);
     // Where the records go.  The narrow kernel's first-block diagonal records follow the clustering of the DFS stream: per-stream
     // chunks (an open chunk per block and wave), applied straight from the grouped chunk table.  The other records spread over
     // many streams, a few per stream and wave:
@@ -3380,10 +3503,9 @@ static int blocks_prepare_impl(kmdb_db* db) {
         b.key_bits = key_bits;
     }
     DEV_ALLOC(b.tile_touched, (size_t)b.n_states + 1);
-    DEV_ALLOC(b.ct_hist, (size_t)b.n_ckeys + 2);
     DEV_ALLOC(b.ct_offs, (size_t)b.n_ckeys + 2);
     DEV_ALLOC(b.ct_cursor, (size_t)b.n_ckeys + 2);
-    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist.get(), b.ct_offs.get(), (int)(b.n_ckeys + 1), db->stream));
+    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist, b.ct_offs.get(), (int)(b.n_ckeys + 1), db->stream));
     DEV_ALLOC(b.ct_tmp, std::max<size_t>(b.ct_tmp_bytes, 16));
     // A database whose records do not fit one pass (2^31 record slots, or the memory left) is taken in SLICES of the pattern stream:
     // every slice emits the records of its own patterns only, the partial matrices add up in place (the engine's own version of
@@ -3443,7 +3565,8 @@ void kmdb_blocks_release(kmdb_db* db) { db->blocks.reset(); }
 uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
     if (!db->blocks || !db->blocks->counters) return 0;
     const BlocksState& b = *db->blocks;
-    return db->P * (8 + 4 + 4 + 16 + 4) + (b.dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + b.pair_cap * 10 + ((b.pool_cap << CH_SHIFT) * 20) + b.pool_cap * 16 + b.wide_cap * 4 + (db->P / 64) * 16 +
+    return db->P * (8 + 4 + 4 + 16 + 4) + (b.dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + b.pair_cap * 10 + ((b.pool_cap << CH_SHIFT) * 20) + b.pool_cap * 16 + b.wide_cap * 4 + (db->P / 64) * 12 + (uint64_t)db->n_nsegs * 8 +
+           (uint64_t)b.call_state_n_decode * 4 +
            (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.n_ckeys * 12 +
            (uint64_t)b.NB * (b.l2_node_cap / 64u) * 12 + (uint64_t)b.l2_ent_cap * 26 + (uint64_t)b.l2_node_cap * 4;
 }
@@ -3491,26 +3614,22 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     const uint32_t pool_cap = (uint32_t)b.pool_cap;
     const bool row_mode = b.row_mode;
     const uint32_t n_ckeys = b.n_ckeys;
-    HIP_TRY(hipMemsetAsync(b.counters, 0, KCTR_COUNT * 4, st));
-    if (decode) HIP_TRY(hipMemsetAsync(b.pair_cursor, 0, (KMDB_PAIR_REGIONS + 1) * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(b.sub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(b.wsub_cursor, 0, KMDB_SUBPOOLS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(b.run_ctr, 0, K1W_CTRS * 16 * 4, st));
-    HIP_TRY(hipMemsetAsync(b.direct_ctr, 0, KMDB_SUBPOOLS * 16 * 4, st));
     // Sizes of the launches: measured by the previous call on this handle.  What the narrow kernel produces repeats exactly; where
     // the wide kernel's records land depends on which wave took which run, so the chunk counts behind it vary a little from call
     // to call: those launches get some slack, every kernel takes the true counts from device memory, and the call is repeated with
     // upper bounds if a true count exceeded its launch (checked at the end).
     auto with_slack = [](uint32_t v) -> uint32_t { return v + v / 8u + 1024u; };
     const uint32_t raw_launch = b.have_counts ? (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), row_mode ? 0xFFFFFFFFull : b.wide_pool_cap) : 0u;
-    if (!row_mode) {
-        // never-written slots of the wide pool sort last; only the part the previous call used has to be reset
-        const uint64_t wslots = b.have_counts ? (uint64_t)raw_launch << WCH_SHIFT : b.wide_pool_cap << WCH_SHIFT;
-        HIP_TRY(hipMemsetAsync(b.wkey, 0xFF, wslots * 4, st));
+    // ---- the call's state in one launch: counters, cursors and the chunk table's histogram cleared (the pair pool's cursors with them when this
+    // attempt decodes: later slices of a call reuse the decode), every chunk empty and never opened.  The host is not ahead of the queue yet: every
+    // further submission here is a gap on the device (profiles/prologue_c2_timeline_*.md).  The wide pool's key words are not touched: which slots
+    // hold a record of this call follows from the sub-pools' cursors (cs_chunks_handed, arena_finish_wide).
+    {
+        // (the attempt that decodes is the first of its call: the tiles the call adds to, all its slices, are flagged from here on)
+        const uint32_t n_state = decode ? b.call_state_n_decode : b.call_state_n, n_touched = decode && b.tile_touched ? b.n_states + 1u : 0u;
+        hipLaunchKernelGGL(call_prologue_kernel, dim3((std::max(std::max(n_state, pool_cap), n_touched) + 255u) / 256u), dim3(256), 0, st, b.call_state.get(), n_state,
+                           b.chunk_fill.get(), b.chunk_key.get(), pool_cap, b.tile_touched.get(), n_touched);
     }
-    HIP_TRY(hipMemsetAsync(b.chunk_fill, 0, (size_t)pool_cap * 4, st));
-    HIP_TRY(hipMemsetAsync(b.ct_hist, 0, ((size_t)n_ckeys + 2) * 4, st));
-    hipLaunchKernelGGL(fill_u32_kernel, dim3((pool_cap + 255) / 256), dim3(256), 0, st, b.chunk_key, pool_cap, 0xFFFFFFFFu);      // never opened
     if (stage("init")) return 1;
     // ---- K0  (the two launches one after the other: both are bound by instruction issue, side by side on two streams they take
     // exactly as long — measured, profiles/r03_k0side_ab.sh)
@@ -3538,7 +3657,7 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         NParams q{};
         q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.dflag = db->dflag; q.seg_anc = db->nseg_anc; q.seg_anc_n = db->nseg_anc_n;
         q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
-        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits;
+        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits; q.wide_base = b.wide_base; q.wide_slice_cnt = b.wide_slice_cnt;
         q.P = P; q.nseg_nodes = db->nseg_nodes; q.n_segs = db->n_nsegs; q.chain_cap = db->chain_cap;
         q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.NB); q.n_keys = b.NB;
         q.all_wide = b.dense_narrow ? 1u : 0u;
@@ -3571,7 +3690,7 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     auto group_and_apply_chunks = [&](hipStream_t cs) -> int {
         hipLaunchKernelGGL(ct_hist_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_hist);
         size_t tb = b.ct_tmp_bytes;
-        HIP_TRY(prim::exclusive_sum(b.ct_tmp, tb, b.ct_hist.get(), b.ct_offs.get(), (int)(n_ckeys + 1), cs));
+        HIP_TRY(prim::exclusive_sum(b.ct_tmp, tb, b.ct_hist, b.ct_offs.get(), (int)(n_ckeys + 1), cs));
         HIP_TRY(hipMemcpyAsync(b.ct_cursor, b.ct_offs, ((size_t)n_ckeys + 1) * 4, hipMemcpyDeviceToDevice, cs));
         hipLaunchKernelGGL(ct_scatter_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_cursor, b.sorted_key, b.sorted_id);
         hipLaunchKernelGGL(ct_count_kernel, dim3(1), dim3(1), 0, cs, b.ct_offs, b.n_states, b.counters);
@@ -3619,12 +3738,13 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         } else HIP_TRY(hipEventRecord(db->ev_side[1], s2));        // (no stream chunk is ever opened: nothing to group; the side stream holds the slices' apply kernel or nothing)
     }
     // ---- wide list
-    hipLaunchKernelGGL(wide_count_kernel, dim3((n_words + 1 + 255) / 256), dim3(256), 0, st, b.widebits, n_words, b.wide_cnt);
-    HIP_TRY(prim::exclusive_sum(b.scan_tmp, b.scan_tmp_bytes, b.wide_cnt.get(), b.wide_base.get(), (int)(n_words + 1), st));
+    // (the narrow kernel counted the flagged nodes per word and slice: one workgroup scans the slices' totals, no device-wide scan)
+    hipLaunchKernelGGL(wide_slices_kernel, dim3(1), dim3(WSL_THREADS), 0, st, b.wide_slice_cnt.get(), db->n_nsegs, b.wide_slice_base.get(), b.wide_base.get(), n_words,
+                       b.counters);
     uint32_t n_wide;
     if (b.have_counts && b.wide_cap >= b.last_n_wide) n_wide = b.last_n_wide;     // deterministic per database; checked at the end of the call
     else {
-        HIP_TRY(hipMemcpyAsync(b.h_counters, b.wide_base + n_words, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters + KCTR_NWIDE, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         n_wide = b.h_counters[0];
         if (n_wide > b.wide_cap) {
@@ -3637,8 +3757,12 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         }
     }
     if (!b.widx) { DEV_ALLOC(b.widx, 1); b.wide_cap = std::max<uint64_t>(b.wide_cap, 1); }
-    hipLaunchKernelGGL(wide_expand_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, b.widebits, b.wide_base, n_words, b.widx,
-                       (uint32_t)b.wide_cap, b.counters);
+    {
+        static const bool wave_form = getenv("KMDB_WIDE_EXPAND") && !strcmp(getenv("KMDB_WIDE_EXPAND"), "wave");
+        const uint32_t wps = db->nseg_nodes / 64u;
+        hipLaunchKernelGGL(wave_form ? wide_expand_kernel<false> : wide_expand_kernel<true>, dim3((n_words + 255) / 256), dim3(256), 0, st, b.widebits.get(), b.wide_base.get(),
+                           b.wide_slice_base.get(), wps, (wps & (wps - 1u)) ? 0xFFFFFFFFu : (uint32_t)__builtin_ctz(wps), n_words, b.widx.get(), (uint32_t)b.wide_cap);
+    }
     if (b.k1n_mode == 2 && !k2d_early && apply_slices()) return 1;
     // ---- K1w
     if (n_wide) {
@@ -3770,7 +3894,7 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         HIP_TRY(hipGetLastError());
         if (stage("row sort+apply")) return 1;
     } else {
-        hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(1), 0, st, b.wsub_cursor, b.counters);
+        hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(64), 0, st, b.wsub_cursor, (uint32_t)(b.wide_pool_cap / KMDB_SUBPOOLS), b.counters, b.wide_handed.get());
         // the wide pool: records sorted by stream (the sort moves the 16-byte records with their key words), one tile per run
         uint32_t n_raw;
         if (b.have_counts) n_raw = raw_launch;
@@ -3784,13 +3908,13 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
             const CsRows no_rows{};
             const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
             hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), b.n_states * 4, st, b.wkey, nslots, b.n_states, b.n_states, (int)CS_BY_STREAM,
-                               no_rows, kmask, b.cs_hist);
+                               no_rows, kmask, b.cs_hist, b.wide_handed.get());
             size_t tb = b.cs_tmp_bytes;
             HIP_TRY(prim::exclusive_sum(b.cs_tmp, tb, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
             const bool packed = b.rec_pshift != 0;
             HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(b.n_states, packed)));
             hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(b.n_states, packed), st, b.wkey, (const WideRec*)b.wrec, nslots,
-                               b.n_states, b.n_states, (int)CS_BY_STREAM, no_rows, kmask, b.cs_offs, b.swkey, (WideRec*)b.swrec, packed ? 1u : 0u);
+                               b.n_states, b.n_states, (int)CS_BY_STREAM, no_rows, kmask, b.cs_offs, b.swkey, (WideRec*)b.swrec, packed ? 1u : 0u, b.wide_handed.get());
             const uint32_t* total_ptr = b.cs_offs + (ne - 1);
             HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
             if (getenv("KMDB_K2_WINDOWS") && !packed) {
@@ -3928,7 +4052,7 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
     BlocksState& b = *db->blocks;
     const uint64_t cells = db->N * (db->N - 1) / 2;
     for (int round = 0; round < 64; ++round) {
-        if (b.tile_touched) HIP_TRY(hipMemsetAsync(b.tile_touched, 0, (size_t)b.n_states + 1, st));      // the tiles this call adds to (all its slices)
+        // (the tiles this call adds to, all its slices: tile_touched is cleared by the prologue of the round's first attempt, the one that decodes)
         // the slices of [emit_lo, emit_hi) one after the other, adding into the same matrix; a pass that had to enlarge a pool (or
         // asked for more slices) leaves a partial sum behind: everything again from a zeroed matrix
         const uint32_t S = std::max<uint32_t>(1u, b.n_slices);
