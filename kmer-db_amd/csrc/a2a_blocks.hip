@@ -18,16 +18,22 @@
 //                            lanes, earlier ones from a chain table in LDS (one slot per depth).  Emits the records of those
 //                            nodes (first-block diagonal records into per-block stream chunks, the others into the wide pool),
 //                            flags the nodes with more blocks and leaves them their parent's summary.
-//       wide list            the flagged nodes, compacted: the narrow kernel counts them per word and slice, one workgroup scans the slices, expand
-//   K1g k1g_kernel           one lane per wide node: list = parent's list (row in LDS, chain table, or a climb) + own pairs;
-//                            the records of a batch are numbered by a prefix sum and emitted one per lane from a descriptor
-//                            queue into the wide pool, in arrival order; heavy nodes by the whole wave.
-//   sort cs_hist / cs_scatter  the wide pool (16-byte records + a key word: stream | weight digit) grouped by stream: counting
-//                            sort with per-workgroup LDS histograms and staged tiles, one pass (<= 2048 streams) or two
-//                            (by block row, then inside the rows); rocprim radix sort beyond 512 block rows.
-//   K2  k2_apply_kernel      stream chunks (side stream, next to K1g), k2_sorted_kernel: the sorted wide pool.  64 records per
-//                            wave step as bit matrices, int8 MFMA into a 64 x 64 LDS tile (weights >= 128 as base-128 digit
-//                            passes), one HBM atomic per non-zero cell.
+//                            The first-block records (X, X) of a slice: compacted per slice and applied by k2d_kernel on the side
+//                            stream (KMDB_K1N_MODE=2, default), applied inside the kernel (1), or written to stream chunks (0).
+//       wide list            the flagged nodes, compacted: the narrow kernel counts them per word and slice, wide_slices_kernel (one
+//                            workgroup) scans the slices, wide_expand_kernel writes the list
+//   K1w k1w_kernel           the wide nodes in runs of 256 (root paths of the runs' first nodes: wrun_anc_kernel): list = parent's
+//                            list + own pairs, records into the wide pool (few streams) or per-block-row chunks (many streams);
+//                            many streams with at most 256 blocks: the nodes with many blocks go to the second level instead
+//                            (l2_ranks / l2_offsets / l2_lists / l2_join_apply_kernel join two blocks' lists per tile)
+//   sort few streams (<= 2048): cs_hist / cs_scatter_kernel, ONE counting-sort pass over the wide pool by stream (per-workgroup
+//                            LDS histograms, staged tiles).  Many streams: the chunk table grouped by key (ct_hist / ct_scatter), the
+//                            row chunks grouped by row (rg_hist / rg_scatter), then a counting sort inside every block row
+//                            (rs_rows / rs_hist / rs_scatter_kernel).
+//   K2  k2_apply_kernel      stream chunks (side stream, next to K1w); k2j_starts[_flat] / k2j_build / k2_jobs_kernel: the sorted
+//                            records stream by stream.  64 records per wave step as bit matrices, int8 MFMA into a 64 x 64 LDS tile
+//                            (weights >= 128 as base-128 digit passes), one HBM atomic per non-zero cell.
+// db2db (kmdb_rect_sort_apply) shares cs_hist / cs_scatter and applies its sorted records with k2_sorted_kernel.
 // Records are placed WITHOUT a counting pass and WITHOUT hot global atomics (same-address device atomics run at a few million
 // per second on this part: measured, profiles/README.md): waves take chunks from 256 sub-pool cursors a few at a time, keep
 // their open stream chunks in an LDS table indexed by block, and reserve slots for a group of lanes with a ballot.  The pools are
@@ -414,10 +420,6 @@ __global__ void call_prologue_kernel(uint32_t* __restrict__ state, uint32_t n_st
     if (i < pool_cap) { chunk_fill[i] = 0u; chunk_key[i] = 0xFFFFFFFFu; }
     if (i < n_touched) touched[i] = 0;
 }
-__global__ void iota_u32_kernel(uint32_t* __restrict__ p, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = i;
-}
 
 // ------------------------------------------------------------------------------------------
 // K0: gamma streams -> local (block, mask) pairs
@@ -790,7 +792,8 @@ struct NParams {
     unsigned long long* dmask;     // [n_segs * nseg_nodes] F0
     uint32_t* dwx;                 // [n_segs * nseg_nodes] w | X << 8
     uint32_t* slice_cnt;           // [n_segs]
-    uint32_t dbg;                  // experiments (KMDB_K1N_DBG; results are WRONG with any bit set): 1 no write-back, 2 no matrix-core step
+    uint32_t dbg;                  // always 0 (no switch sets it).  The two tests of it in k1n_kernel<1, *> stay: without them k1n_kernel<1, 4, rows> is compiled with
+                                   // 108 instead of 76 bytes of scratch per lane and measured 9.42 against 8.42 ms at C2 (profiles/a2a_cleanup_ab.json)
 };
 constexpr int K1N_WAVES = 4;
 __host__ __device__ inline size_t k1n_wave_bytes(uint32_t chain_cap, uint32_t tbits, uint32_t n_states, uint32_t n_rows) {
@@ -1266,15 +1269,12 @@ __global__ __launch_bounds__(WSL_THREADS) void wide_slices_kernel(const uint32_t
     if (threadIdx.x == 0) { slice_base[n_segs] = total; wide_base[n_words] = total; counters[KCTR_NWIDE] = total; }
 }
 // The wide list itself: word i's flagged nodes go to widx[slice_base[its slice] + wide_base[i] ...], and wide_base[i] becomes the absolute prefix the
-// wide kernel reads.  SERIAL (the default): a thread per word walks its bits.  Otherwise (KMDB_WIDE_EXPAND=wave, A/B) one wave per 64 words: the words that
-// have a flagged node are taken one after the other by the whole wave, lane k writes node k at its rank among the word's bits, so the stores of a word are
-// contiguous — at C2, where most words hold a few flagged nodes, that is 64 turns of a wave for 64 words against half a dozen per thread, and it measured
-// slower beside k2d_kernel.  slice_shift: log2 of the words per slice (0xFFFFFFFF: not a power of two, divide).
-template <bool SERIAL>
+// wide kernel reads.  A thread per word walks its bits.  (One wave per 64 words, lane k writing node k at its rank among the word's bits so that the stores
+// of a word are contiguous, is 64 turns of a wave for 64 words against half a dozen per thread at C2, where most words hold a few flagged nodes: it measured
+// slower beside k2d_kernel)  slice_shift: log2 of the words per slice (0xFFFFFFFF: not a power of two, divide).
 __global__ __launch_bounds__(256) void wide_expand_kernel(const unsigned long long* __restrict__ bits, uint32_t* __restrict__ base, const uint32_t* __restrict__ slice_base,
                                                           uint32_t words_per_slice, uint32_t slice_shift, uint32_t n_words, uint32_t* __restrict__ widx, uint32_t cap) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
     unsigned long long b = 0;
     uint32_t o = 0;
     if (i < n_words) {
@@ -1282,24 +1282,11 @@ __global__ __launch_bounds__(256) void wide_expand_kernel(const unsigned long lo
         o = slice_base[slice_shift != 0xFFFFFFFFu ? i >> slice_shift : i / words_per_slice] + base[i];
         base[i] = o;
     }
-    if (SERIAL) {
-        while (b) {
-            const uint32_t k = (uint32_t)__builtin_ctzll(b);
-            b &= b - 1;
-            if (o < cap) widx[o] = i * 64u + k;
-            ++o;
-        }
-        return;
-    }
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    unsigned long long todo = __ballot(b != 0ull);
-    const uint32_t w0 = i - lane;
-    while (todo) {
-        const uint32_t j = (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
-        const unsigned long long bj = ((unsigned long long)bcast((uint32_t)(b >> 32), j) << 32) | bcast((uint32_t)b, j);
-        const uint32_t p = bcast(o, j) + (uint32_t)__popcll(bj & lt_mask);
-        if (((bj >> lane) & 1ull) && p < cap) widx[p] = (w0 + j) * 64u + lane;
+    while (b) {
+        const uint32_t k = (uint32_t)__builtin_ctzll(b);
+        b &= b - 1;
+        if (o < cap) widx[o] = i * 64u + k;
+        ++o;
     }
 }
 
@@ -2270,12 +2257,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2A_MIN_WAV
     }
 }
 
-// opened chunks = the head of the sorted chunk table
-__global__ void count_chunks_kernel(const uint32_t* __restrict__ sorted_key, uint32_t pool_cap, uint32_t n_states, uint32_t* __restrict__ counters) {
-    uint32_t lo = 0, hi = pool_cap;
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (sorted_key[mid] < n_states) lo = mid + 1; else hi = mid; }
-    counters[KCTR_CHUNKS] = lo;
-}
 // chunks of the chunk pool in use = the busiest sub-pool's share of all (one wave: a maximum over the 256 cursors)
 __global__ void pool_used_kernel(const uint32_t* __restrict__ sub_cursor, const uint32_t* __restrict__ direct_ctr, uint32_t* __restrict__ counters) {
     uint32_t mx = 0, nd = 0;
@@ -2297,14 +2278,12 @@ __global__ void count_raw_kernel(const uint32_t* __restrict__ wsub_cursor, uint3
 // Counting sort of the wide pool by stream: per-workgroup histograms in LDS (no device atomics), one exclusive scan over the
 // table of counts, then every workgroup moves its records to its own range of every stream.  The order inside a stream is
 // arbitrary (uint32 adds commute).  Two reads of the keys, one read and one write of the records per pass.
-// Up to CS_MAX_KEYS streams: one pass, bins = streams.  More (10 000 samples at width 50 are 20 100 streams): two passes —
-// first by block row X (bins = rows), then every row by itself, cut into chunks of whole tiles, bins = the row's X + 1 streams.
-// A scatter straight to 20 100 destinations is bound by the number of write requests (measured: 25.8 ms for 495 M records, a
-// tile holds less than one record per stream); the two staged passes write bursts (6.3 ms + the same again).
-// More than CS_MAX_ROWS block rows (25 600 samples at width 50): rocprim's radix sort — a tile of 1024 records then holds about one
-// record per bin of its row, the staged passes stop writing bursts (measured at 782 rows: 27.7 ms against 22.6 with rocprim).
-constexpr uint32_t CS_MAX_KEYS = 2048, CS_BLOCKS = 2048, CS_MAX_ROWS = 512;
-constexpr uint32_t CS_BLOCKS_ONE = 3072;   // workgroups of the one-pass sort (two full rounds on the chip measured better than 2048; the two-pass sort keeps 2048)
+// One pass, bins = streams, for up to CS_MAX_KEYS of them: with more (10 000 samples at width 50 are 20 100 streams) a tile holds
+// less than one record per stream and a scatter straight to that many destinations is bound by the number of write requests
+// (measured: 25.8 ms for 495 M records).  The all2all call then takes the many-streams path (row chunks, rg_* and rs_* below);
+// db2db (kmdb_rect_sort_apply) keeps rocPRIM's radix sort for more than CS_MAX_KEYS streams.
+constexpr uint32_t CS_MAX_KEYS = 2048;
+constexpr uint32_t CS_BLOCKS_ONE = 3072;   // workgroups of the sort (two full rounds on the chip measured better than 2048)
 // block row X of stream s = tri32(X) + Y
 __device__ __forceinline__ uint32_t stream_row(uint32_t s) {
     uint32_t X = (uint32_t)((__fsqrt_rn(8.0f * (float)s + 1.0f) - 1.0f) * 0.5f);
@@ -2312,57 +2291,18 @@ __device__ __forceinline__ uint32_t stream_row(uint32_t s) {
     while (tri32(X + 1u) <= s) ++X;
     return X;
 }
-// the second pass's view of the row-sorted records: where every row starts, its first workgroup, its first table entry
-struct CsRows {
-    const uint32_t* row_start;      // [NB + 1]
-    const uint32_t* row_blk;        // [NB + 1] workgroups before the row (a row of n records has ceil(n / chunk))
-    const uint32_t* row_tab;        // [NB + 1] table entries before the row (its (X + 1) streams x its workgroups)
-    uint32_t NB, chunk;
-};
-enum { CS_BY_STREAM = 0, CS_BY_ROW = 1, CS_IN_ROW = 2 };
-// what one workgroup sorts: records [lo, hi), bin of a key = row(key) or key - sub, count / offset of bin k at table[tab + k * stride]
-struct CsJob { uint32_t lo, hi, n_bins, sub, tab, stride; };
-__device__ __forceinline__ CsJob cs_job(int mode, uint32_t n, uint32_t n_keys, const CsRows& rows) {
-    CsJob j{0u, 0u, n_keys, 0u, blockIdx.x, gridDim.x};
-    if (mode != CS_IN_ROW) {
-        // equal shares of whole 1024-record tiles; the shares in XCD-contiguous order (the grids are multiples of 8)
-        const uint32_t vb = (gridDim.x & 7u) ? blockIdx.x : xcd_contiguous(blockIdx.x, gridDim.x);
-        j.tab = vb;
-        const uint32_t per_block = ((n + gridDim.x - 1u) / gridDim.x + 1023u) / 1024u * 1024u;
-        const uint32_t lo = vb * per_block;
-        if (lo < n) { j.lo = lo; j.hi = n - lo < per_block ? n : lo + per_block; }
-        return j;
-    }
-    j.n_bins = 0;
-    if (blockIdx.x >= rows.row_blk[rows.NB]) return j;
-    uint32_t a = 0, b = rows.NB;                             // last row whose first workgroup is <= this one and that has workgroups
-    while (b - a > 1u) { const uint32_t mid = (a + b) >> 1; if (rows.row_blk[mid] <= blockIdx.x) a = mid; else b = mid; }
-    const uint32_t X = a, c = blockIdx.x - rows.row_blk[X];
-    j.lo = rows.row_start[X] + c * rows.chunk;
-    j.hi = rows.row_start[X + 1];
-    if (j.hi - j.lo > rows.chunk) j.hi = j.lo + rows.chunk;
-    j.n_bins = X + 1u; j.sub = tri32(X); j.tab = rows.row_tab[X] + c; j.stride = rows.row_blk[X + 1] - rows.row_blk[X];
+// what one workgroup sorts: records [lo, hi); count / offset of bin (= stream) k at table[tab + k * gridDim.x]
+struct CsJob { uint32_t lo, hi, tab; };
+__device__ __forceinline__ CsJob cs_job(uint32_t n) {
+    // equal shares of whole 1024-record tiles; the shares in XCD-contiguous order (the grids are multiples of 8)
+    const uint32_t vb = (gridDim.x & 7u) ? blockIdx.x : xcd_contiguous(blockIdx.x, gridDim.x);
+    CsJob j{0u, 0u, vb};
+    const uint32_t per_block = ((n + gridDim.x - 1u) / gridDim.x + 1023u) / 1024u * 1024u;
+    const uint32_t lo = vb * per_block;
+    if (lo < n) { j.lo = lo; j.hi = n - lo < per_block ? n : lo + per_block; }
     return j;
 }
-__device__ __forceinline__ uint32_t cs_bin(int mode, uint32_t key, uint32_t n_valid, uint32_t sub) {
-    if (key >= n_valid) return 0xFFFFFFFFu;
-    return mode == CS_BY_ROW ? stream_row(key) : key - sub;
-}
-// row tables of the second pass from the first pass's offsets O1[row][workgroup] (+ total)
-__global__ void cs_rows_kernel(const uint32_t* __restrict__ O1, uint32_t NB, uint32_t chunk, uint32_t* __restrict__ row_start, uint32_t* __restrict__ row_blk,
-                               uint32_t* __restrict__ row_tab) {
-    for (uint32_t X = threadIdx.x; X <= NB; X += blockDim.x) row_start[X] = O1[(size_t)X * CS_BLOCKS];      // entry [NB][0] is the total
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t blk = 0, tab = 0;
-        for (uint32_t X = 0; X < NB; ++X) {
-            row_blk[X] = blk; row_tab[X] = tab;
-            const uint32_t nch = (row_start[X + 1] - row_start[X] + chunk - 1u) / chunk;
-            blk += nch; tab += nch * (X + 1u);
-        }
-        row_blk[NB] = blk; row_tab[NB] = tab;
-    }
-}
+__device__ __forceinline__ uint32_t cs_bin(uint32_t key, uint32_t n_valid) { return key < n_valid ? key : 0xFFFFFFFFu; }
 // The all2all call's wide pool (wcur != nullptr: the chunks handed out by each of its 256 sub-pools, count_raw_kernel) comes WITHOUT pre-filled key
 // words: a slot counts only if its chunk was handed out — chunk c is number c / KMDB_SUBPOOLS of sub-pool c % KMDB_SUBPOOLS (arena_take_wide), handed out
 // iff that number lies below the sub-pool's cursor; what a wave took and did not write holds KEY_NONE (arena_finish_wide).  The cursors are loaded
@@ -2379,13 +2319,13 @@ __device__ __forceinline__ uint32_t cs_chunks_handed(const uint32_t* cur, bool m
     return (uint32_t)__ballot(c / KMDB_SUBPOOLS < cur[c % KMDB_SUBPOOLS]);
 }
 static_assert(WCH_REC == 64, "cs_chunks_handed: a wave's 64 consecutive slots are one chunk of the wide pool");
-__global__ __launch_bounds__(256) void cs_hist_kernel(const uint32_t* __restrict__ wkey, uint32_t n, uint32_t n_valid, uint32_t n_keys, int mode, const CsRows rows,
+__global__ __launch_bounds__(256) void cs_hist_kernel(const uint32_t* __restrict__ wkey, uint32_t n, uint32_t n_valid, uint32_t n_keys,
                                                      uint32_t kmask, uint32_t* __restrict__ H, const uint32_t* __restrict__ wcur) {
     extern __shared__ uint32_t cs_lds[];
     __shared__ uint32_t cs_cur[KMDB_SUBPOOLS];
-    const CsJob job = cs_job(mode, n, n_keys, rows);
+    const CsJob job = cs_job(n);
     cs_load_cursors(cs_cur, wcur);
-    for (uint32_t k = threadIdx.x; k < job.n_bins; k += blockDim.x) cs_lds[k] = 0;
+    for (uint32_t k = threadIdx.x; k < n_keys; k += blockDim.x) cs_lds[k] = 0;
     __syncthreads();
     const uint32_t wv = threadIdx.x >> 6;
     // eight key words per thread requested together (the loop used to wait for one load per iteration)
@@ -2399,13 +2339,13 @@ __global__ __launch_bounds__(256) void cs_hist_kernel(const uint32_t* __restrict
         }
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t bin = kw[j] == 0xFFFFFFFFu ? 0xFFFFFFFFu : cs_bin(mode, kw[j] & kmask, n_valid, job.sub);
-            if (bin < job.n_bins) atomicAdd(&cs_lds[bin], 1u);
+            const uint32_t bin = kw[j] == 0xFFFFFFFFu ? 0xFFFFFFFFu : cs_bin(kw[j] & kmask, n_valid);
+            if (bin < n_keys) atomicAdd(&cs_lds[bin], 1u);
         }
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < job.n_bins; k += blockDim.x) H[(size_t)job.tab + (size_t)k * job.stride] = cs_lds[k];
-    if (mode != CS_IN_ROW && blockIdx.x == 0 && threadIdx.x == 0) H[(size_t)n_keys * gridDim.x] = 0;          // the scan leaves the total here
+    for (uint32_t k = threadIdx.x; k < n_keys; k += blockDim.x) H[(size_t)job.tab + (size_t)k * gridDim.x] = cs_lds[k];
+    if (blockIdx.x == 0 && threadIdx.x == 0) H[(size_t)n_keys * gridDim.x] = 0;          // the scan leaves the total here
 }
 // The scatter stages tiles of CS_TILE records in LDS sorted by bin, so that the records of one stream leave the tile as one
 // contiguous burst.  LDS: the staged records, their destinations, and three per-bin arrays (tile histogram = rank source,
@@ -2413,7 +2353,7 @@ __global__ __launch_bounds__(256) void cs_hist_kernel(const uint32_t* __restrict
 constexpr uint32_t CS_TILE = 2048, CS_THREADS = 256;
 __host__ __device__ inline size_t cs_scatter_lds(uint32_t n_keys, bool packed) { return (size_t)CS_TILE * (sizeof(WideRec) + (packed ? 4 : 8)) + (size_t)n_keys * 12 + CS_THREADS * 4 + 64; }
 __global__ __launch_bounds__(CS_THREADS) void cs_scatter_kernel(const uint32_t* __restrict__ wkey, const WideRec* __restrict__ wrec, uint32_t n, uint32_t n_valid,
-                                                         uint32_t n_keys, int mode, const CsRows rows, uint32_t kmask, const uint32_t* __restrict__ O,
+                                                         uint32_t n_keys, uint32_t kmask, const uint32_t* __restrict__ O,
                                                          uint32_t* __restrict__ swkey, WideRec* __restrict__ swrec, uint32_t packed,
                                                          const uint32_t* __restrict__ wcur) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_raw[];
@@ -2425,9 +2365,9 @@ __global__ __launch_bounds__(CS_THREADS) void cs_scatter_kernel(const uint32_t* 
     uint32_t* toff = hist + n_keys;                                       // [n_keys] first staging position of the bin
     uint32_t* cursor = toff + n_keys;                                     // [n_keys] next global position of the bin for this workgroup
     uint32_t* part = cursor + n_keys;                                     // [CS_THREADS] scan scratch
-    const CsJob job = cs_job(mode, n, n_keys, rows);
-    const uint32_t nb = job.n_bins, lo = job.lo, hi = job.hi;
-    for (uint32_t k = threadIdx.x; k < nb; k += CS_THREADS) cursor[k] = O[(size_t)job.tab + (size_t)k * job.stride];
+    const CsJob job = cs_job(n);
+    const uint32_t nb = n_keys, lo = job.lo, hi = job.hi;
+    for (uint32_t k = threadIdx.x; k < nb; k += CS_THREADS) cursor[k] = O[(size_t)job.tab + (size_t)k * gridDim.x];
     constexpr uint32_t PER = CS_TILE / CS_THREADS;
     const uint32_t kper = (nb + CS_THREADS - 1u) / CS_THREADS;                              // bins per thread in the scan
     // keys and records are fetched together, and the next tile's before this one is staged (one round trip per tile, under way early)
@@ -2454,7 +2394,7 @@ __global__ __launch_bounds__(CS_THREADS) void cs_scatter_kernel(const uint32_t* 
 #pragma unroll
         for (uint32_t j = 0; j < PER; ++j) {
             kw[j] = nkw[j]; rc[j] = nrec[j];
-            key[j] = cs_bin(mode, kw[j] & kmask, n_valid, job.sub);
+            key[j] = cs_bin(kw[j] & kmask, n_valid);
             rank[j] = key[j] < nb ? atomicAdd(&hist[key[j]], 1u) : 0u;
         }
         if (t0 + CS_TILE < hi) fetch(t0 + CS_TILE);
@@ -2574,7 +2514,7 @@ __global__ __launch_bounds__(RG_THREADS) void rg_scatter_kernel(const uint32_t* 
 // ---- many streams: the sort inside the block rows.  Row X's records sit in the chunks of its part of row_ids, cut into jobs of
 // RS_JOB_CHUNKS chunks, one workgroup each; bins = the row's X + 1 streams.  Counting sort as above (LDS histograms per job, one
 // scan over [row][stream][job], LDS-staged scatter), reading through the chunk list, writing the dense sorted arrays
-// k2_sorted_kernel walks.
+// k2_jobs_kernel walks.
 constexpr uint32_t RS_JOB_CHUNKS = 64;
 struct RsRows { const uint32_t* O; const uint32_t* row_ids; uint32_t G, NB; const uint32_t* row_job; const uint32_t* row_tab; };
 __global__ void rs_rows_kernel(const uint32_t* __restrict__ O, uint32_t G, uint32_t NB, uint32_t* __restrict__ row_job, uint32_t* __restrict__ row_tab,
@@ -2730,13 +2670,14 @@ __global__ __launch_bounds__(CS_THREADS) void rs_scatter_kernel(const RsRows R, 
 }
 __host__ __device__ inline size_t rs_scatter_lds(uint32_t NB, bool packed) { return (size_t)CS_TILE * (sizeof(WideRec) + (packed ? 4 : 8)) + (size_t)NB * 12 + CS_THREADS * 4 + 64; }
 
-// K2 over records sorted by stream (dense mode): a window of K2S_WIN sorted positions, one 64 x 64 tile per run of equal streams
+// K2 over db2db's records sorted by stream (kmdb_rect_sort_apply; stream = row block x rect_nbc + column block): a window of K2S_WIN sorted
+// positions, run boundaries searched in the key words, one 64 x 64 tile per run of equal streams
 constexpr uint32_t K2S_WIN = 4096;
 constexpr int K2S_MIN_WAVES = 3;           // waves per SIMD the compiler must leave room for (4: 128 VGPRs and 104 B of scratch per lane; 3: no scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAVES, 8))) void k2_sorted_kernel(const uint32_t* __restrict__ swkey, const WideRec* __restrict__ swrec,
-                                                        uint32_t limit, const uint32_t* __restrict__ total_ptr, const uint32_t* __restrict__ lo_ptr,
+                                                        uint32_t limit, const uint32_t* __restrict__ total_ptr,
                                                         uint32_t n_states, uint32_t kbits, uint32_t dbits, uint32_t* __restrict__ M, uint32_t N,
-                                                        uint32_t bwidth, uint32_t rect_nbc, uint32_t rect_cols, unsigned char* __restrict__ touched) {
+                                                        uint32_t bwidth, uint32_t rect_nbc, uint32_t rect_cols) {
     __shared__ uint32_t acc[64 * 64];
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[4][64];
     __shared__ unsigned long long lut_ff[256], lut_01[256];
@@ -2744,7 +2685,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
     __shared__ uint32_t wor_sh;
     __shared__ uint32_t tcount[256];
     const uint32_t total = total_ptr ? (*total_ptr < limit ? *total_ptr : limit) : limit;      // counting sort: the valid records; radix sort: all slots
-    const uint32_t p0 = (lo_ptr ? *lo_ptr : 0u) + blockIdx.x * K2S_WIN;                        // (a band of block rows: [*lo_ptr, *total_ptr))
+    const uint32_t p0 = blockIdx.x * K2S_WIN;
     const uint32_t kmask = (1u << kbits) - 1u;
     if (p0 >= total || (swkey[p0] & kmask) >= n_states) return;
     const uint32_t wend = total - p0 < K2S_WIN ? total - p0 : K2S_WIN;
@@ -2794,12 +2735,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
         K2Item it;
         {
             const uint32_t bucket = key;
-            if (rect_nbc) { it.X = bucket / rect_nbc; it.Y = bucket - it.X * rect_nbc; }      // db2db: stream = row block x column blocks + column block
-            else { it.X = stream_row(bucket); it.Y = bucket - tri32(it.X); }
+            it.X = bucket / rect_nbc; it.Y = bucket - it.X * rect_nbc;
             it.rect_cols = rect_cols; it.pshift = 0;
             it.n_rec = b - a; it.count = (it.n_rec + 63u) / 64u; it.ids = nullptr; it.fills = nullptr; it.srec = swrec + p0 + a; it.skey = swkey + p0 + a; it.kbits = kbits; it.dbits = dbits; it.rec = nullptr; it.recw = nullptr;
         }
-        k2_run<true>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched);
+        k2_run<true>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, nullptr);      // (a rectangle: no tile flags)
     }
 }
 
@@ -2966,19 +2906,52 @@ __global__ void pair_estimate_kernel(const uint2* __restrict__ k0in, const uint3
     if (lane == 0 && need) atomicAdd(out, need);
 }
 
-// v1 / new2all node arrays from the compact layout
-__global__ void v1_arrays_kernel(const uint2* __restrict__ k0in, const uint32_t* __restrict__ bitrel, const uint64_t* __restrict__ blkbase,
-                                 const uint32_t* __restrict__ nl, uint32_t P, uint4* __restrict__ meta, uint64_t* __restrict__ bitpos) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P) return;
-    const uint2 km = k0in[i];
-    const uint32_t v = nl[i];
-    meta[i] = make_uint4(v, kmdb_k0_l(km), kmdb_k0_last(km), kmdb_k0_bits(km));
-    bitpos[i] = blkbase[i >> 8] + bitrel[i];
-}
-
 // weight digit bits of the wide pool's key word: what the stream bits and the two digit-index bits leave (four digits cover 32 bits)
 inline uint32_t wide_digit_bits(int key_bits) { return (uint32_t)(32 - key_bits - 2); }
+
+// ------------------------------------------------------------------------------------------
+// The pipeline's switches (README.md, the table of environment switches): environment variables read ONCE per handle, when its pipeline state is made
+// (blocks_read_knobs at the top of blocks_prepare_impl).  An empty value counts as unset.
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t K1W_RUN_NODES = 256;     // wide nodes per run of a wave (round-robin: heavy nodes sit together in the DFS order)
+struct BlocksKnobs {
+    uint32_t block_width = 0;               // KMDB_BLOCK_WIDTH: 32…64 (anything else is ignored); 0: from the sampled estimate
+    bool dense_narrow = false;              // KMDB_DENSE >= 2
+    int k1n_mode = 2;                       // KMDB_K1N_MODE, clamped to 0…2 (BlocksState::k1n_mode)
+    int k1n_minw = 3;                       // KMDB_K1N_MINW: mode 1 at four waves per SIMD when >= 4
+    int row_mode = -1;                      // KMDB_ROW_MODE: 0 / 1; -1: by the number of streams
+    bool rec_packed = true;                 // KMDB_REC_PACKED=0 clears it
+    bool l2 = true;                         // KMDB_L2=0 clears it
+    uint32_t l2_min = L2_MIN_BLOCKS;        // KMDB_L2_MIN, at least K1W_HEAVY
+    uint64_t slices = 0;                    // KMDB_SLICES, at least 1; 0: from the record estimate
+    uint64_t pool_percent = 0;              // KMDB_POOL_PERCENT, at least 1; 0: unset
+    uint32_t k2d_slices = K2D_SLICES;       // KMDB_K2D_SLICES, at least 1
+    bool k2d_early = true;                  // KMDB_K2D_EARLY=0 clears it
+    uint32_t k1w_run = K1W_RUN_NODES;       // KMDB_K1W_RUN: a multiple of 64, at least 64
+    uint32_t k1w_waves = 0;                 // KMDB_K1W_WAVES, at least 1; 0: as many as the chip holds
+};
+BlocksKnobs blocks_read_knobs() {
+    BlocksKnobs k;
+    auto env = [](const char* name) -> const char* { const char* e = getenv(name); return e && *e ? e : nullptr; };
+    if (const char* e = env("KMDB_BLOCK_WIDTH")) { const uint32_t w = (uint32_t)strtoul(e, nullptr, 10); if (w >= 32 && w <= 64) k.block_width = w; }
+    if (const char* e = env("KMDB_DENSE")) k.dense_narrow = atoi(e) >= 2;
+    if (const char* e = env("KMDB_K1N_MODE")) k.k1n_mode = std::max(0, std::min(2, atoi(e)));
+    if (const char* e = env("KMDB_K1N_MINW")) k.k1n_minw = atoi(e);
+    if (const char* e = env("KMDB_ROW_MODE")) k.row_mode = atoi(e) != 0;          // (tests: small databases through the many-streams path)
+    if (const char* e = env("KMDB_REC_PACKED")) k.rec_packed = e[0] != '0';
+    if (const char* e = env("KMDB_L2")) k.l2 = e[0] != '0';
+    if (const char* e = env("KMDB_L2_MIN")) k.l2_min = std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(e));
+    if (const char* e = env("KMDB_SLICES")) k.slices = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    if (const char* e = env("KMDB_POOL_PERCENT")) k.pool_percent = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    if (const char* e = env("KMDB_K2D_SLICES")) k.k2d_slices = (uint32_t)std::max(1, atoi(e));
+    if (const char* e = env("KMDB_K2D_EARLY")) k.k2d_early = e[0] != '0';
+    if (const char* e = env("KMDB_K1W_RUN")) k.k1w_run = std::max<uint32_t>(64u, (uint32_t)atoi(e) / 64u * 64u);
+    if (const char* e = env("KMDB_K1W_WAVES")) k.k1w_waves = std::max<uint32_t>(1u, (uint32_t)atoi(e));
+    return k;
+}
+// the two diagnostics are read where they are used: they may be set and unset between the calls of a process
+bool kmdb_verbose() { return getenv("KMDB_VERBOSE") != nullptr; }
+bool kmdb_sync_debug() { return getenv("KMDB_SYNC_DEBUG") != nullptr; }      // wait after every stage and name the one that failed (no effect on results)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -2986,6 +2959,7 @@ inline uint32_t wide_digit_bits(int key_bits) { return (uint32_t)(32 - key_bits 
 // (kmdb_db.blocks) owns it; every device array is a DevBuf, so that destroying the state is all there is to releasing it.
 // ------------------------------------------------------------------------------------------
 struct BlocksState {
+    BlocksKnobs knobs;              // the switches as they stood when the state was made
     uint32_t NB = 0, n_states = 0;  // blocks, (bucket, weight class) streams
     DevBuf<unsigned long long> p0_mask;      // [P] first (block, mask) pair of every node's local list
     DevBuf<uint32_t> p0_info;       // [P] block | npairs << 16
@@ -3016,7 +2990,7 @@ struct BlocksState {
     uint32_t* sub_cursor = nullptr; // [KMDB_SUBPOOLS * 16] (in call_state)
     // wide pool: records in arrival order + a device-wide sort by stream (the wide kernel always; the narrow kernel if its
     // per-stream chunks do not work out)
-    bool dense_wide = false, dense_narrow = false;
+    bool dense_narrow = false;
     // the narrow kernel's first-block records (X, X): 0 stream chunks + k2_apply_kernel (round 5), 1 applied inside the narrow kernel (tile in its
     // registers, nothing written), 2 compacted per slice in DFS order + k2d_kernel on the side stream (default).  1 and 2: what they cannot take
     // (weights of 128 and more) goes the dense_narrow way, nothing uses stream chunks
@@ -3037,9 +3011,9 @@ struct BlocksState {
     bool row_mode = false;
     uint32_t rec_pshift = 0;        // many streams, block width <= 54: the weight digit of a block record lives in the spare bits of its column mask (from
                                     // this bit on) and the record travels as 16 bytes; 0: 16 bytes of masks + the 4-byte key word
-    uint32_t n_ckeys = 0;                              // keys of the chunk table: streams (+ block rows in row mode); n_ckeys = never opened
-    uint32_t* ct_hist = nullptr;                       // [n_ckeys + 2] (in call_state)
-    DevBuf<uint32_t> ct_offs, ct_cursor;            // [n_ckeys + 2]
+    // the chunk table grouped by key: the keys are the streams (row chunks, keyed n_states + row, sit in their rows' lists: rg_*); n_states = never opened
+    uint32_t* ct_hist = nullptr;                       // [n_states + 2] (in call_state)
+    DevBuf<uint32_t> ct_offs, ct_cursor;            // [n_states + 2]
     DevBuf<void> ct_tmp;
     size_t ct_tmp_bytes = 0;
     DevBuf<uint32_t> rg_hist, rg_offs;   // row chunks grouped by row: [NB][rg_blocks] counts / offsets (+ total)
@@ -3054,7 +3028,6 @@ struct BlocksState {
     size_t rs_tmp_bytes = 0;
     uint64_t sorted_cap = 0;                           // records the sorted arrays (swkey / swrec) hold
     uint32_t last_n_rowjobs = 0, last_n_sorted = 0, last_n_k2jobs = 0, k1w_waves = 0, k1w_slots = 0;   // (k1w_waves: most the pools are sized for; k1w_slots: waves the chip holds at once)
-    const void* k1w_slots_fn = nullptr;                // the wide kernel's instantiation k1w_slots was asked for
     DevBuf<uint32_t> cs_hist, cs_offs;   // counting sort of the wide pool: [stream][block] counts / offsets (+ total)
     DevBuf<void> cs_tmp;
     size_t cs_tmp_bytes = 0;
@@ -3077,7 +3050,7 @@ struct BlocksState {
     uint64_t est_records = 0;       // sampled estimate for the chosen width
     // what the previous call found (the pipeline is deterministic per database: grid sizes of the next call)
     bool have_counts = false;
-    uint32_t last_n_wide = 0, last_n_chunks = 0, last_n_raw = 0, last_n_slow = 0;
+    uint32_t last_n_wide = 0, last_n_chunks = 0, last_n_raw = 0;
     uint64_t last_records = 0;
     uint32_t n_slices = 1;          // passes over the pattern stream per call (a database whose records do not fit one)
     struct SliceCounts { bool valid = false; uint32_t lo = 0, hi = 0, n_wide = 0, n_chunks = 0, n_raw = 0, n_rowjobs = 0, n_sorted = 0, n_k2jobs = 0; };
@@ -3115,7 +3088,6 @@ K1wPick k1w_pick(bool rows, bool l2) {
 }
 
 constexpr uint32_t K1W_MAX_WAVES = 8192;
-constexpr uint32_t K1W_RUN_NODES = 256;     // wide nodes per run of a wave (round-robin: heavy nodes sit together in the DFS order)
 struct U32toU64 { __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; } };
 struct ValidKey { uint32_t n_states, kmask; __host__ __device__ uint32_t operator()(uint32_t k) const { return (k & kmask) < n_states ? 1u : 0u; } };
 
@@ -3208,87 +3180,6 @@ int alloc_pair_pool(BlocksState& b, uint64_t entries) {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// list index for new2all / db2db (engine_state.h): checkpoints of the long local lists
-__global__ void ck_count_kernel(const uint2* __restrict__ k0in, uint32_t P, uint32_t* __restrict__ cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > P) return;
-    const uint32_t l = i < P ? kmdb_k0_l(k0in[i]) : 0u;
-    cnt[i] = l > KMDB_CK_IDS ? (l + KMDB_CK_IDS - 1u) / KMDB_CK_IDS : 0u;
-}
-__global__ void ck_fill_kernel(const uint2* __restrict__ k0in, const uint32_t* __restrict__ bitrel, const uint64_t* __restrict__ blkbase,
-                               const uint64_t* __restrict__ bits, uint32_t P, const uint32_t* __restrict__ ck_ofs, uint64_t* __restrict__ ck_bit,
-                               uint32_t* __restrict__ ck_id) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P) return;
-    const uint2 km = k0in[i];
-    const uint32_t l = kmdb_k0_l(km), last = kmdb_k0_last(km);
-    if (l <= KMDB_CK_IDS) return;
-    const uint64_t pos = blkbase[i >> 8] + bitrel[i];
-    uint32_t sum = 0;
-    { BitCursor c(bits, pos); for (uint32_t t = 0; t + 1 < l; ++t) sum += c.next(); }
-    BitCursor c(bits, pos);
-    uint32_t id = last - sum, o = ck_ofs[i];
-    for (uint32_t t = 0; t < l; ++t) {
-        if (t % KMDB_CK_IDS == 0) { ck_id[o] = id; ck_bit[o] = c.wi * 64u + c.s; ++o; }      // element t and the position of the code after it
-        if (t + 1 < l) id += c.next();
-    }
-}
-
-static int ensure_v1_impl(kmdb_db* db);
-int kmdb_ensure_v1_arrays(kmdb_db* db) {
-    if (db->v1_ready) return 0;
-    if (ensure_v1_impl(db)) {
-        // nothing half made is left behind: the next call starts over
-        dev_reset(db->meta, db->bitpos, db->wprefix, db->v1_counters, db->segs, db->v1_scan_tmp, db->ck_ofs, db->ck_bit, db->ck_id);
-        return 1;
-    }
-    db->v1_ready = true;
-    return 0;
-}
-static int ensure_v1_impl(kmdb_db* db) {
-    const uint64_t P = db->P;
-    DEV_ALLOC(db->meta, std::max<uint64_t>(P, 1));
-    DEV_ALLOC(db->bitpos, std::max<uint64_t>(P, 1));
-    DEV_ALLOC(db->wprefix, P + 1);
-    DEV_ALLOC(db->v1_counters, 8);
-    HIP_TRY(hipMemset(db->v1_counters, 0, 8 * sizeof(unsigned long long)));
-    if (P) hipLaunchKernelGGL(v1_arrays_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, db->stream, db->k0in, db->bitrel, db->blkbase, db->nl,
-                              (uint32_t)P, db->meta, db->bitpos);
-    HIP_TRY(hipGetLastError());
-    std::vector<Segment> segs;
-    const uint64_t step = 2048;
-    for (uint64_t f = 0; f < P; f += step) segs.push_back(Segment{(uint32_t)f, (uint32_t)std::min<uint64_t>(P, f + step)});
-    while (segs.size() % WAVES_PER_BLOCK) segs.push_back(Segment{(uint32_t)P, (uint32_t)P});
-    DEV_ALLOC(db->segs, std::max<size_t>(segs.size(), 1));
-    if (!segs.empty()) HIP_TRY(hipMemcpy(db->segs, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice));
-    db->n_segs = (uint32_t)segs.size();
-    HIP_TRY(prim::exclusive_sum(nullptr, db->v1_scan_tmp_bytes, db->w.get(), db->wprefix.get(), (int)(P + 1)));
-    DEV_ALLOC(db->v1_scan_tmp, std::max<size_t>(db->v1_scan_tmp_bytes, 16));
-    {
-        const uint64_t P1 = P + 1;
-        DevBuf<uint32_t> cnt;
-        DevBuf<void> tmp;
-        size_t tb = 0;
-        DEV_ALLOC(cnt, P1);
-        DEV_ALLOC(db->ck_ofs, P1);
-        hipLaunchKernelGGL(ck_count_kernel, dim3((unsigned)((P1 + 255) / 256)), dim3(256), 0, db->stream, db->k0in, (uint32_t)P, cnt);
-        HIP_TRY(prim::exclusive_sum(nullptr, tb, cnt.get(), db->ck_ofs.get(), (int)P1, db->stream));
-        DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
-        HIP_TRY(prim::exclusive_sum(tmp, tb, cnt.get(), db->ck_ofs.get(), (int)P1, db->stream));
-        uint32_t n_ck = 0;
-        HIP_TRY(hipMemcpyAsync(&n_ck, db->ck_ofs + P, 4, hipMemcpyDeviceToHost, db->stream));
-        HIP_TRY(hipStreamSynchronize(db->stream));
-        cnt.reset(); tmp.reset();
-        DEV_ALLOC(db->ck_bit, std::max<uint64_t>(n_ck, 1));
-        DEV_ALLOC(db->ck_id, std::max<uint64_t>(n_ck, 1));
-        if (P) hipLaunchKernelGGL(ck_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, db->stream, db->k0in, db->bitrel, db->blkbase, db->bits,
-                                  (uint32_t)P, db->ck_ofs, db->ck_bit, db->ck_id);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(db->stream));
-    return 0;
-}
-
 // db2db (csrc/db2db.hip): records (row block, column block, row mask, column mask, weight digit in the key word) of the pairs of
 // patterns that share k-mers, in arrival order in [0, nslots) with never-written slots keyed all-ones -> sorted by stream and
 // accumulated into the dense n_rows x n_cols matrix M by the same sort and matrix-core kernels as the all2all's wide pool.
@@ -3309,13 +3200,12 @@ int kmdb_rect_sort_apply(hipStream_t st, uint32_t* wkey, void* wrec, uint32_t ns
         DEV_ALLOC(offs, ne);
         HIP_TRY(prim::exclusive_sum(nullptr, tb, hist.get(), offs.get(), (int)ne, st));
         DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
-        const CsRows no_rows{};
-        hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), n_states * 4, st, wkey, nslots, n_states, n_states, (int)CS_BY_STREAM, no_rows, kmask, hist,
+        hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), n_states * 4, st, wkey, nslots, n_states, n_states, kmask, hist,
                            (const uint32_t*)nullptr);              // (this pool's key words are filled by its owner)
         HIP_TRY(prim::exclusive_sum(tmp, tb, hist.get(), offs.get(), (int)ne, st));
         HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(n_states, false)));
         hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(n_states, false), st, wkey, (const WideRec*)wrec, nslots, n_states, n_states,
-                           (int)CS_BY_STREAM, no_rows, kmask, offs, swkey, swrec, 0u, (const uint32_t*)nullptr);
+                           kmask, offs, swkey, swrec, 0u, (const uint32_t*)nullptr);
         total_ptr = offs + (ne - 1);
     } else {
         size_t tb = 0;
@@ -3323,8 +3213,8 @@ int kmdb_rect_sort_apply(hipStream_t st, uint32_t* wkey, void* wrec, uint32_t ns
         DEV_ALLOC(tmp, std::max<size_t>(tb, 16));
         HIP_TRY(prim::sort_pairs(tmp, tb, wkey, swkey.get(), (WideRec*)wrec, swrec.get(), (int)nslots, 0, key_bits, st));
     }
-    hipLaunchKernelGGL(k2_sorted_kernel, dim3((nslots + K2S_WIN - 1) / K2S_WIN), dim3(256), 0, st, swkey, (const WideRec*)swrec, nslots, total_ptr, (const uint32_t*)nullptr,
-                       n_states, (uint32_t)key_bits, wide_digit_bits(key_bits), M, n_rows, 64u, nbc, n_cols, (unsigned char*)nullptr);
+    hipLaunchKernelGGL(k2_sorted_kernel, dim3((nslots + K2S_WIN - 1) / K2S_WIN), dim3(256), 0, st, swkey, (const WideRec*)swrec, nslots, total_ptr,
+                       n_states, (uint32_t)key_bits, wide_digit_bits(key_bits), M, n_rows, 64u, nbc, n_cols);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -3340,6 +3230,8 @@ int kmdb_blocks_prepare(kmdb_db* db) {
 }
 static int blocks_prepare_impl(kmdb_db* db) {
     BlocksState& b = *db->blocks;
+    b.knobs = blocks_read_knobs();
+    const BlocksKnobs& knobs = b.knobs;
     const uint64_t N = db->N, P = db->P;
     db->fallback_reason.clear();
     if (N < 2 || P == 0) { db->fallback_reason = "fewer than two samples"; return 0; }
@@ -3347,7 +3239,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
         db->fallback_reason = "a root path of " + std::to_string(db->max_depth) + " nodes exceeds the chain table (" + std::to_string(KMDB_CHAIN_MAX) + ")";
         return 0;
     }
-    const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
+    const bool verbose = kmdb_verbose();
     auto t_mark = std::chrono::steady_clock::now();
     auto phase = [&](const char* what) {                        // where the preparation's time goes (hipMalloc of tens of GB is not free)
         if (!verbose) return;
@@ -3360,8 +3252,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
     // ranges that a 64-id grid would cut in two.  One node in `stride` is decoded along its whole root path and its
     // blocks are counted for every candidate at once; the candidate with the fewest records wins.
     const uint32_t cands[EST_NW] = {64, 60, 56, 52, 50, 48, 44, 40, 36, 32};
-    uint32_t forced = 0;
-    if (const char* e = getenv("KMDB_BLOCK_WIDTH")) forced = (uint32_t)strtoul(e, nullptr, 10);
+    const uint32_t forced = knobs.block_width;
     const uint32_t stride = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, P / 65536));
     uint64_t est_n = 0, est_g = 0, est_l2 = 0;                  // records of the nodes with <= 2 blocks, of the others, and of those the part the second level replaces
     {
@@ -3369,7 +3260,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
         q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.parent = db->parent; q.nl = db->nl; q.w = db->w;
         q.P = (uint32_t)P; q.stride = stride;
         for (int c = 0; c < EST_NW; ++c) { q.widths[c] = cands[c]; q.magics[c] = (uint32_t)((1ull << 32) / cands[c]) + 1u; }
-        q.l2_min = getenv("KMDB_L2_MIN") ? std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(getenv("KMDB_L2_MIN"))) : L2_MIN_BLOCKS;
+        q.l2_min = knobs.l2_min;
         DevBuf<unsigned long long> d_out;
         DEV_ALLOC(d_out, 3 * EST_NW + 1);
         q.out = d_out;
@@ -3382,7 +3273,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
         HIP_TRY(hipStreamSynchronize(db->stream));
         int best = 0;
         for (int c = 1; c < EST_NW; ++c) if (h[c] + h[EST_NW + c] < h[best] + h[EST_NW + best]) best = c;
-        if (forced >= 32 && forced <= 64) {
+        if (forced) {
             db->width = forced;
             best = 0;
             for (int c = 0; c < EST_NW; ++c) if (cands[c] >= forced) best = c;
@@ -3419,7 +3310,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
     DEV_ALLOC(b.wide_slice_base, (size_t)db->n_nsegs + 1);
     DEV_ALLOC(b.wide_handed, KMDB_SUBPOOLS);
     {
-        // the per-call state at fixed offsets (the chunk table's keys are the streams: b.n_ckeys below)
+        // the per-call state at fixed offsets (the chunk table's keys are the streams)
         uint32_t o = 0;
         auto take = [&](uint32_t n) { const uint32_t at = o; o += (n + 15u) & ~15u; return at; };
         const uint32_t o_ctr = take(KCTR_COUNT), o_sub = take(KMDB_SUBPOOLS * 16), o_wsub = take(KMDB_SUBPOOLS * 16), o_run = take(K1W_CTRS * 16),
@@ -3466,13 +3357,10 @@ static int blocks_prepare_impl(kmdb_db* db) {
     //                                  grouping by row in a pass of its own cost another 7.5 ms).
     // With more streams than the narrow kernel's open-chunk table holds it sends its diagonal records the same way, if its chunks turn
     // out to be evicted nearly empty.
-    b.dense_wide = true;
-    b.dense_narrow = false;
-    if (const char* e = getenv("KMDB_DENSE")) b.dense_narrow = atoi(e) >= 2;
+    b.dense_narrow = knobs.dense_narrow;
     // Round 6: the narrow kernel's first-block records no longer travel through stream chunks (BlocksState: k1n_mode; KMDB_K1N_MODE=0 / 1 / 2
     // for the A/B): compacted per slice and applied by k2d_kernel beside the wide kernel (2, default), or applied inside the narrow kernel (1).
-    b.k1n_mode = 2;
-    if (const char* e = getenv("KMDB_K1N_MODE")) if (*e) b.k1n_mode = std::max(0, std::min(2, atoi(e)));
+    b.k1n_mode = knobs.k1n_mode;
     if (b.k1n_mode) b.dense_narrow = true;
     if (b.k1n_mode == 2) {
         const size_t slots = (size_t)db->n_nsegs * db->nseg_nodes;
@@ -3481,31 +3369,30 @@ static int blocks_prepare_impl(kmdb_db* db) {
         DEV_ALLOC(b.slice_cnt, std::max<size_t>(db->n_nsegs, 1));
     }
     b.row_mode = b.n_states > CS_MAX_KEYS;
-    if (const char* e = getenv("KMDB_ROW_MODE")) if (*e) b.row_mode = atoi(e) != 0;          // (tests: small databases through the many-streams path)
+    if (knobs.row_mode >= 0) b.row_mode = knobs.row_mode != 0;
     // packed records: a block width of at most 54 leaves the column mask 10 spare bits and more — an 8-bit weight digit at least and the digit's
     // index — so the records of the many-streams path travel as 16 bytes through the sort and the apply step (KMDB_REC_PACKED=0: 16 + 4, A/B)
     // (round 5, later: the few-streams path as well — its one-pass sort moves 16 bytes per record and leaves the key words behind)
-    b.rec_pshift = (db->width <= 54u && !(getenv("KMDB_REC_PACKED") && getenv("KMDB_REC_PACKED")[0] == '0')) ? db->width : 0u;
-    // The second level (many streams, <= 256 blocks: see blocks_attempt) writes no records for the nodes with L2_MIN_BLOCKS blocks or more — 52 % of the
+    b.rec_pshift = (db->width <= 54u && knobs.rec_packed) ? db->width : 0u;
+    // The second level: many streams, few enough blocks that a tile job's bitmap scan stays small (tiles x nodes: quadratic in the blocks);
+    // KMDB_L2=0 switches it off, KMDB_L2_MIN=c moves the threshold.  It writes no records for the nodes with L2_MIN_BLOCKS blocks or more — 52 % of the
     // estimate at 10 000 samples.  Round 5 sized the pools from the estimate before it: 110 GB for 616 M records of 16 bytes.
-    {
-        const char* l2_env = getenv("KMDB_L2");
-        if (b.row_mode && b.NB <= 256u && !(l2_env && l2_env[0] == '0')) {
-            if (verbose) fprintf(stderr, "[kmdb] block records estimated: %llu, of them %llu from nodes the second level joins per tile instead\n",
-                                 (unsigned long long)(est_n + est_g), (unsigned long long)est_l2);
-            est_g -= std::min(est_g, est_l2);
-        }
+    b.l2_on = b.row_mode && b.NB <= 256u && knobs.l2;
+    b.l2_min_blocks = knobs.l2_min;
+    if (b.l2_on) {
+        if (verbose) fprintf(stderr, "[kmdb] block records estimated: %llu, of them %llu from nodes the second level joins per tile instead\n",
+                             (unsigned long long)(est_n + est_g), (unsigned long long)est_l2);
+        est_g -= std::min(est_g, est_l2);
     }
-    b.n_ckeys = b.n_states;                                  // keys of the grouped chunk table = the streams (row chunks sit in their rows' lists)
     {
         int key_bits = 1;
         while ((1ull << key_bits) <= (uint64_t)b.n_states + 1) ++key_bits;          // streams; all-ones = never written
         b.key_bits = key_bits;
     }
     DEV_ALLOC(b.tile_touched, (size_t)b.n_states + 1);
-    DEV_ALLOC(b.ct_offs, (size_t)b.n_ckeys + 2);
-    DEV_ALLOC(b.ct_cursor, (size_t)b.n_ckeys + 2);
-    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist, b.ct_offs.get(), (int)(b.n_ckeys + 1), db->stream));
+    DEV_ALLOC(b.ct_offs, (size_t)b.n_states + 2);
+    DEV_ALLOC(b.ct_cursor, (size_t)b.n_states + 2);
+    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist, b.ct_offs.get(), (int)(b.n_states + 1), db->stream));
     DEV_ALLOC(b.ct_tmp, std::max<size_t>(b.ct_tmp_bytes, 16));
     // A database whose records do not fit one pass (2^31 record slots, or the memory left) is taken in SLICES of the pattern stream:
     // every slice emits the records of its own patterns only, the partial matrices add up in place (the engine's own version of
@@ -3518,15 +3405,15 @@ static int blocks_prepare_impl(kmdb_db* db) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
             slices = std::max<uint64_t>(slices, (slots * 44 + free_b / 2) / std::max<size_t>(free_b * 6 / 10, 1));     // pool + sorted copy: 44 B per slot, 60 % of what is free
-        if (const char* e = getenv("KMDB_SLICES")) if (*e) slices = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+        if (knobs.slices) slices = knobs.slices;
         b.n_slices = (uint32_t)std::min<uint64_t>(slices, 1u << 16);
         if (verbose && b.n_slices > 1) fprintf(stderr, "[kmdb] %llu block records estimated: %u slices of the pattern stream per call\n",
                                                  (unsigned long long)(est_n + est_g), b.n_slices);
         est_n = est_n / b.n_slices + 1; est_g = est_g / b.n_slices + 1;
     }
-    if (const char* e = getenv("KMDB_POOL_PERCENT")) if (*e) {
+    if (knobs.pool_percent) {
         // (tests: pools far too small, so that the first call takes the enlarge-and-repeat path on every one of them)
-        const uint64_t pct = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+        const uint64_t pct = knobs.pool_percent;
         est_n = est_n * pct / 100 + 1; est_g = est_g * pct / 100 + 1;
     }
     // waves of the wide-node kernel: in row mode every wave may end with an open chunk per block row
@@ -3567,7 +3454,7 @@ uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
     const BlocksState& b = *db->blocks;
     return db->P * (8 + 4 + 4 + 16 + 4) + (b.dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + b.pair_cap * 10 + ((b.pool_cap << CH_SHIFT) * 20) + b.pool_cap * 16 + b.wide_cap * 4 + (db->P / 64) * 12 + (uint64_t)db->n_nsegs * 8 +
            (uint64_t)b.call_state_n_decode * 4 +
-           (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.n_ckeys * 12 +
+           (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.n_states * 12 +
            (uint64_t)b.NB * (b.l2_node_cap / 64u) * 12 + (uint64_t)b.l2_ent_cap * 26 + (uint64_t)b.l2_node_cap * 4;
 }
 
@@ -3595,154 +3482,135 @@ int alloc_l2(BlocksState& b, uint32_t node_cap, uint32_t ent_cap) {
     return 0;
 }
 
-// one attempt of the whole pipeline; *retry is set when a pool was too small (it has been enlarged)
-// decode: run K0 (the first slice of a call does; what it leaves — the local (block, mask) pairs of every node — serves all slices)
-int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry) {
-    BlocksState& b = *db->blocks;
-    *retry = false;
-    // KMDB_SYNC_DEBUG: wait after every stage and name the one that failed (debugging aid, no effect on results)
-    static const bool sync_debug = getenv("KMDB_SYNC_DEBUG") != nullptr;
-    auto stage = [&](const char* name) -> int {
-        if (!sync_debug) return 0;
-        const hipError_t e = hipStreamSynchronize(st);
-        fprintf(stderr, "[kmdb] stage %-14s %s\n", name, e == hipSuccess ? "ok" : hipGetErrorString(e));
-        return e == hipSuccess ? 0 : kmdb_set_error(std::string("stage ") + name + ": " + hipGetErrorString(e));
-    };
-    const uint32_t P = (uint32_t)db->P;
-    const BlockMap bm{db->width, (uint32_t)((1ull << 32) / db->width) + 1u};
-    const uint32_t n_words = (P + 63) / 64;
+// ---- One attempt of the whole pipeline (blocks_attempt, below) as its stages, in the order the call runs them.
+// Sizes of the launches: measured by the previous call on this handle.  What the narrow kernel produces repeats exactly; where
+// the wide kernel's records land depends on which wave took which run, so the chunk counts behind it vary a little from call
+// to call: those launches get some slack, every kernel takes the true counts from device memory, and the call is repeated with
+// upper bounds if a true count exceeded its launch (checked at the end).
+struct Launched { uint32_t raw = 0, rowjobs = 0, k2jobs = 0; };
+inline uint32_t with_slack(uint32_t v) { return v + v / 8u + 1024u; }
+// KMDB_SYNC_DEBUG: wait after every stage and name the one that failed (debugging aid, no effect on results)
+int stage_done(hipStream_t s, const char* name) {
+    if (!kmdb_sync_debug()) return 0;
+    const hipError_t e = hipStreamSynchronize(s);
+    fprintf(stderr, "[kmdb] stage %-14s %s\n", name, e == hipSuccess ? "ok" : hipGetErrorString(e));
+    return e == hipSuccess ? 0 : kmdb_set_error(std::string("stage ") + name + ": " + hipGetErrorString(e));
+}
+// ---- 1. the call's state in one launch: counters, cursors and the chunk table's histogram cleared (the pair pool's cursors with them when this
+// attempt decodes: later slices of a call reuse the decode), every chunk empty and never opened.  The host is not ahead of the queue yet: every
+// further submission here is a gap on the device (profiles/prologue_c2_timeline_*.md).  The wide pool's key words are not touched: which slots
+// hold a record of this call follows from the sub-pools' cursors (cs_chunks_handed, arena_finish_wide).
+void a2a_prologue(BlocksState& b, hipStream_t st, bool decode) {
+    // (the attempt that decodes is the first of its call: the tiles the call adds to, all its slices, are flagged from here on)
     const uint32_t pool_cap = (uint32_t)b.pool_cap;
-    const bool row_mode = b.row_mode;
-    const uint32_t n_ckeys = b.n_ckeys;
-    // Sizes of the launches: measured by the previous call on this handle.  What the narrow kernel produces repeats exactly; where
-    // the wide kernel's records land depends on which wave took which run, so the chunk counts behind it vary a little from call
-    // to call: those launches get some slack, every kernel takes the true counts from device memory, and the call is repeated with
-    // upper bounds if a true count exceeded its launch (checked at the end).
-    auto with_slack = [](uint32_t v) -> uint32_t { return v + v / 8u + 1024u; };
-    const uint32_t raw_launch = b.have_counts ? (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), row_mode ? 0xFFFFFFFFull : b.wide_pool_cap) : 0u;
-    // ---- the call's state in one launch: counters, cursors and the chunk table's histogram cleared (the pair pool's cursors with them when this
-    // attempt decodes: later slices of a call reuse the decode), every chunk empty and never opened.  The host is not ahead of the queue yet: every
-    // further submission here is a gap on the device (profiles/prologue_c2_timeline_*.md).  The wide pool's key words are not touched: which slots
-    // hold a record of this call follows from the sub-pools' cursors (cs_chunks_handed, arena_finish_wide).
+    const uint32_t n_state = decode ? b.call_state_n_decode : b.call_state_n, n_touched = decode && b.tile_touched ? b.n_states + 1u : 0u;
+    hipLaunchKernelGGL(call_prologue_kernel, dim3((std::max(std::max(n_state, pool_cap), n_touched) + 255u) / 256u), dim3(256), 0, st, b.call_state.get(), n_state,
+                       b.chunk_fill.get(), b.chunk_key.get(), pool_cap, b.tile_touched.get(), n_touched);
+}
+// ---- 2. K0  (the two launches one after the other: both are bound by instruction issue, side by side on two streams they take
+// exactly as long — measured, profiles/r03_k0side_ab.sh)
+int a2a_decode(kmdb_db* db, BlocksState& b, hipStream_t st) {
+    const uint32_t P = (uint32_t)db->P;
+    K0Params q{};
+    q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.perm = nullptr; q.P = P; q.short_ids = db->short_max_ids;
+    q.bm = BlockMap{db->width, (uint32_t)((1ull << 32) / db->width) + 1u};
+    q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
+    // sub-pools of the pair pool: enough of them that their cursors are not hot, few enough that one wave's need fits a share
+    uint32_t nreg = 1;
+    while (nreg < KMDB_PAIR_REGIONS && (uint64_t)nreg * 16384 < P) nreg <<= 1;
+    // three quarters of the pool in sub-pools, the rest shared
+    q.pair_cursor = b.pair_cursor; q.n_regions = nreg; q.region_cap = (uint32_t)(b.pair_cap * 3 / 4 / nreg);
+    q.spill_cap = (uint32_t)(b.pair_cap - (uint64_t)q.region_cap * nreg); q.counters = b.counters;
+    hipLaunchKernelGGL((k0_decode_kernel<false>), dim3((P + 255) / 256), dim3(256), 0, st, q);
+    if (db->n_long) {
+        q.perm = db->long_nodes; q.P = db->n_long;
+        hipLaunchKernelGGL((k0_decode_kernel<true>), dim3((db->n_long + 255) / 256), dim3(256), 0, st, q);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ---- 3. K1n
+int a2a_narrow_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st) {
+    NParams q{};
+    q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.dflag = db->dflag; q.seg_anc = db->nseg_anc; q.seg_anc_n = db->nseg_anc_n;
+    q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
+    q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits; q.wide_base = b.wide_base; q.wide_slice_cnt = b.wide_slice_cnt;
+    q.P = (uint32_t)db->P; q.nseg_nodes = db->nseg_nodes; q.n_segs = db->n_nsegs; q.chain_cap = db->chain_cap;
+    q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.NB); q.n_keys = b.NB;
+    q.all_wide = b.dense_narrow ? 1u : 0u;
+    q.pool = pool_view(b, b.dense_narrow);
+    // a wave's chain table grows with the depth of the tree: as many waves per workgroup as 144 KB of LDS hold
+    const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, b.row_mode ? b.NB : 0u);
+    const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(K1N_WAVES, (144u << 10) / wave_lds));
+    const size_t lds = wave_lds * waves;
+    q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = b.tile_touched; q.direct_ctr = b.direct_ctr;
+    q.dmask = b.dmask; q.dwx = b.dwx; q.slice_cnt = b.slice_cnt;
+    // (mode 1 holds 48 accumulator registers beside the narrow kernel's 95: three waves per SIMD without spills, or four with 72 bytes of
+    // scratch per lane, 76 in row mode — KMDB_K1N_MINW=4, A/B)
+    // the instantiation of the call's record path: the attribute and the launch take the same function
+    const K1nPick pick = k1n_pick(b.k1n_mode, b.knobs.k1n_minw, b.row_mode);
+    HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((q.n_segs + waves - 1) / waves), block(WAVE * waves);
+    if (!b.have_counts && kmdb_verbose())
+        fprintf(stderr, "[kmdb] narrow kernel: %u slices, %zu B of LDS per wave, %u per workgroup, instantiation %s\n", q.n_segs, wave_lds, waves, pick.name);
+    hipLaunchKernelGGL(pick.fn, grid, block, lds, st, q);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ---- 4. mode 2: the slices' first-block records through k2d_kernel, on the side stream beside the wide kernel
+// (It starts right behind the narrow kernel, beside the wide list's small kernels — scan, expand, root paths of the runs, which then take
+// 0.28 ms at C2 instead of their own 0.05.  KMDB_K2D_EARLY=0 starts it with the wide kernel: the wide stage gains 0.1 ms, the sort beside which
+// the kernel then ends loses them — profiles/r06_j13: 6.70 / 6.98 against 6.86 / 6.93 ms at C2, 18.45 against 19.11 at 10 000 samples)
+int a2a_slice_apply(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hipStream_t s2) {
+    HIP_TRY(hipEventRecord(db->ev_side[0], st));
+    HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
+    DParams d{};
+    d.dmask = b.dmask; d.dwx = b.dwx; d.slice_cnt = b.slice_cnt; d.n_segs = db->n_nsegs; d.nseg_nodes = db->nseg_nodes;
+    const uint32_t sl = b.knobs.k2d_slices;
+    d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = b.tile_touched;
+    const uint32_t waves = (db->n_nsegs + sl - 1u) / sl;
+    if (waves) hipLaunchKernelGGL(k2d_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(db->ev_side[1], s2));               // (the call's end waits for the side stream; many streams: recorded again behind the chunk table's work)
+    (void)stage_done(s2, "slice apply");
+    return 0;
+}
+// ---- 5. The chunk table grouped by key (on stream `cs`), then on the side stream the stream chunks applied.  Few streams: right behind the
+// narrow kernel, next to the wide kernel (which writes no chunks).  Many streams: after the wide kernel (it writes the row chunks), next to
+// the sort inside the rows.
+int a2a_group_and_apply_chunks(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t cs, hipStream_t s2) {
+    const uint32_t pool_cap = (uint32_t)b.pool_cap;
+    hipLaunchKernelGGL(ct_hist_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, b.n_states, b.ct_hist);
+    size_t tb = b.ct_tmp_bytes;
+    HIP_TRY(prim::exclusive_sum(b.ct_tmp, tb, b.ct_hist, b.ct_offs.get(), (int)(b.n_states + 1), cs));
+    HIP_TRY(hipMemcpyAsync(b.ct_cursor, b.ct_offs, ((size_t)b.n_states + 1) * 4, hipMemcpyDeviceToDevice, cs));
+    hipLaunchKernelGGL(ct_scatter_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, b.n_states, b.ct_cursor, b.sorted_key, b.sorted_id);
+    hipLaunchKernelGGL(ct_count_kernel, dim3(1), dim3(1), 0, cs, b.ct_offs, b.n_states, b.counters);
+    if (cs != s2) { HIP_TRY(hipEventRecord(db->ev_side[0], cs)); HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0)); }
     {
-        // (the attempt that decodes is the first of its call: the tiles the call adds to, all its slices, are flagged from here on)
-        const uint32_t n_state = decode ? b.call_state_n_decode : b.call_state_n, n_touched = decode && b.tile_touched ? b.n_states + 1u : 0u;
-        hipLaunchKernelGGL(call_prologue_kernel, dim3((std::max(std::max(n_state, pool_cap), n_touched) + 255u) / 256u), dim3(256), 0, st, b.call_state.get(), n_state,
-                           b.chunk_fill.get(), b.chunk_key.get(), pool_cap, b.tile_touched.get(), n_touched);
+        rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(b.chunk_fill, U32toU64());
+        HIP_TRY(prim::sum(b.sort_tmp, b.sort_tmp_bytes, it, (unsigned long long*)(b.counters + KCTR_RECORDS), (int)pool_cap, s2));
     }
-    if (stage("init")) return 1;
-    // ---- K0  (the two launches one after the other: both are bound by instruction issue, side by side on two streams they take
-    // exactly as long — measured, profiles/r03_k0side_ab.sh)
-    if (decode) {
-        K0Params q{};
-        q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.perm = nullptr; q.P = P; q.short_ids = db->short_max_ids; q.bm = bm;
-        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
-        // sub-pools of the pair pool: enough of them that their cursors are not hot, few enough that one wave's need fits a share
-        uint32_t nreg = 1;
-        while (nreg < KMDB_PAIR_REGIONS && (uint64_t)nreg * 16384 < P) nreg <<= 1;
-        // three quarters of the pool in sub-pools, the rest shared
-        q.pair_cursor = b.pair_cursor; q.n_regions = nreg; q.region_cap = (uint32_t)(b.pair_cap * 3 / 4 / nreg);
-        q.spill_cap = (uint32_t)(b.pair_cap - (uint64_t)q.region_cap * nreg); q.counters = b.counters;
-        hipLaunchKernelGGL((k0_decode_kernel<false>), dim3((P + 255) / 256), dim3(256), 0, st, q);
-        if (db->n_long) {
-            q.perm = db->long_nodes; q.P = db->n_long;
-            hipLaunchKernelGGL((k0_decode_kernel<true>), dim3((db->n_long + 255) / 256), dim3(256), 0, st, q);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (stage("decode")) return 1;
-    HIP_TRY(hipEventRecord(db->ev_k[0], st));
-    // ---- K1n
-    {
-        NParams q{};
-        q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.dflag = db->dflag; q.seg_anc = db->nseg_anc; q.seg_anc_n = db->nseg_anc_n;
-        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
-        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits; q.wide_base = b.wide_base; q.wide_slice_cnt = b.wide_slice_cnt;
-        q.P = P; q.nseg_nodes = db->nseg_nodes; q.n_segs = db->n_nsegs; q.chain_cap = db->chain_cap;
-        q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.NB); q.n_keys = b.NB;
-        q.all_wide = b.dense_narrow ? 1u : 0u;
-        q.pool = pool_view(b, b.dense_narrow);
-        // a wave's chain table grows with the depth of the tree: as many waves per workgroup as 144 KB of LDS hold
-        const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, row_mode ? b.NB : 0u);
-        const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(K1N_WAVES, (144u << 10) / wave_lds));
-        const size_t lds = wave_lds * waves;
-        q.dbg = getenv("KMDB_K1N_DBG") ? (uint32_t)atoi(getenv("KMDB_K1N_DBG")) : 0u;
-        q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = b.tile_touched; q.direct_ctr = b.direct_ctr;
-        q.dmask = b.dmask; q.dwx = b.dwx; q.slice_cnt = b.slice_cnt;
-        // (mode 1 holds 48 accumulator registers beside the narrow kernel's 95: three waves per SIMD without spills, or four with 84 bytes of
-        // scratch per lane — KMDB_K1N_MINW=4, A/B)
-        static const int minw = getenv("KMDB_K1N_MINW") ? atoi(getenv("KMDB_K1N_MINW")) : 3;
-        // the instantiation of the call's record path: the attribute and the launch take the same function
-        const K1nPick pick = k1n_pick(b.k1n_mode, minw, row_mode);
-        HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const dim3 grid((q.n_segs + waves - 1) / waves), block(WAVE * waves);
-        if (!b.have_counts && getenv("KMDB_VERBOSE"))
-            fprintf(stderr, "[kmdb] narrow kernel: %u slices, %zu B of LDS per wave, %u per workgroup, instantiation %s\n", q.n_segs, wave_lds, waves, pick.name);
-        hipLaunchKernelGGL(pick.fn, grid, block, lds, st, q);
-        HIP_TRY(hipGetLastError());
-    }
-    if (stage("narrow emit")) return 1;
-    HIP_TRY(hipEventRecord(db->ev_k[1], st));
-    hipStream_t s2 = db->stream2;
-    // The chunk table grouped by key (on stream `cs`), then on the side stream the stream chunks applied.  Few streams: right here,
-    // next to the wide kernel (which writes no chunks).  Many streams: after the wide kernel (it writes the row chunks), next to
-    // the sort inside the rows.
-    auto group_and_apply_chunks = [&](hipStream_t cs) -> int {
-        hipLaunchKernelGGL(ct_hist_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_hist);
-        size_t tb = b.ct_tmp_bytes;
-        HIP_TRY(prim::exclusive_sum(b.ct_tmp, tb, b.ct_hist, b.ct_offs.get(), (int)(n_ckeys + 1), cs));
-        HIP_TRY(hipMemcpyAsync(b.ct_cursor, b.ct_offs, ((size_t)n_ckeys + 1) * 4, hipMemcpyDeviceToDevice, cs));
-        hipLaunchKernelGGL(ct_scatter_kernel, dim3((pool_cap + CT_THREADS - 1) / CT_THREADS), dim3(CT_THREADS), 0, cs, b.chunk_key, pool_cap, n_ckeys, b.ct_cursor, b.sorted_key, b.sorted_id);
-        hipLaunchKernelGGL(ct_count_kernel, dim3(1), dim3(1), 0, cs, b.ct_offs, b.n_states, b.counters);
-        if (cs != s2) { HIP_TRY(hipEventRecord(db->ev_side[0], cs)); HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0)); }
-        {
-            rocprim::transform_iterator<uint32_t*, U32toU64, unsigned long long> it(b.chunk_fill, U32toU64());
-            HIP_TRY(prim::sum(b.sort_tmp, b.sort_tmp_bytes, it, (unsigned long long*)(b.counters + KCTR_RECORDS), (int)pool_cap, s2));
-        }
-        const uint32_t win = b.n_states <= CS_MAX_KEYS ? 16u : 32u;      // (8 / 32 / 64 chunks at few streams: within the boxes' noise, profiles/r05_j5)
-        uint32_t grid = (pool_cap + win - 1) / win;
-        if (b.have_counts) grid = std::min(grid, (b.last_n_chunks + win - 1) / win);
-        if (grid)
-            hipLaunchKernelGGL(k2_apply_kernel, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
-                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(db->ev_side[1], s2));
-        if (sync_debug) { const hipError_t e = hipStreamSynchronize(s2); fprintf(stderr, "[kmdb] stage %-14s %s\n", "chunk apply", e == hipSuccess ? "ok" : hipGetErrorString(e)); }
-        return 0;
-    };
-    auto apply_slices = [&]() -> int {
-        // mode 2: the slices' first-block records through k2d_kernel, on the side stream beside the wide kernel
-        HIP_TRY(hipEventRecord(db->ev_side[0], st));
-        HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
-        DParams d{};
-        d.dmask = b.dmask; d.dwx = b.dwx; d.slice_cnt = b.slice_cnt; d.n_segs = db->n_nsegs; d.nseg_nodes = db->nseg_nodes;
-        static const uint32_t sl = getenv("KMDB_K2D_SLICES") ? (uint32_t)std::max(1, atoi(getenv("KMDB_K2D_SLICES"))) : K2D_SLICES;
-        d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = b.tile_touched;
-        const uint32_t waves = (db->n_nsegs + sl - 1u) / sl;
-        if (waves) hipLaunchKernelGGL(k2d_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(db->ev_side[1], s2));               // (the call's end waits for the side stream; many streams: recorded again behind the chunk table's work)
-        if (sync_debug) { const hipError_t e = hipStreamSynchronize(s2); fprintf(stderr, "[kmdb] stage %-14s %s\n", "slice apply", e == hipSuccess ? "ok" : hipGetErrorString(e)); }
-        return 0;
-    };
-    // (the slices' apply kernel starts right behind the narrow kernel, beside the wide list's small kernels — scan, expand, root paths of the runs,
-    // which then take 0.28 ms at C2 instead of their own 0.05.  KMDB_K2D_EARLY=0 starts it with the wide kernel: the wide stage gains 0.1 ms, the
-    // sort beside which the kernel then ends loses them — profiles/r06_j13: 6.70 / 6.98 against 6.86 / 6.93 ms at C2, 18.45 against 19.11 at 10 000 samples)
-    static const bool k2d_early = !(getenv("KMDB_K2D_EARLY") && getenv("KMDB_K2D_EARLY")[0] == '0');
-    if (b.k1n_mode == 2 && k2d_early && apply_slices()) return 1;
-    if (!row_mode) {
-        if (!b.dense_narrow) {
-            HIP_TRY(hipEventRecord(db->ev_side[0], st));
-            HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
-            if (group_and_apply_chunks(s2)) return 1;
-        } else HIP_TRY(hipEventRecord(db->ev_side[1], s2));        // (no stream chunk is ever opened: nothing to group; the side stream holds the slices' apply kernel or nothing)
-    }
-    // ---- wide list
-    // (the narrow kernel counted the flagged nodes per word and slice: one workgroup scans the slices' totals, no device-wide scan)
+    const uint32_t win = b.n_states <= CS_MAX_KEYS ? 16u : 32u;      // (8 / 32 / 64 chunks at few streams: within the boxes' noise, profiles/r05_j5)
+    uint32_t grid = (pool_cap + win - 1) / win;
+    if (b.have_counts) grid = std::min(grid, (b.last_n_chunks + win - 1) / win);
+    if (grid)
+        hipLaunchKernelGGL(k2_apply_kernel, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
+                           b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(db->ev_side[1], s2));
+    (void)stage_done(s2, "chunk apply");
+    return 0;
+}
+// ---- 6. wide list: the flagged nodes, compacted.  The narrow kernel counted them per word and slice: one workgroup scans the slices' totals, no
+// device-wide scan.  A handle's first call (or one whose list outgrew its arrays) waits for the device here and reads the number of wide nodes, as
+// the few-streams sort of such a call reads the chunks in use; later calls take the previous call's counts (checked at the end of the call).
+int a2a_wide_list(kmdb_db* db, BlocksState& b, hipStream_t st, uint32_t* n_wide_out) {
+    const uint32_t n_words = ((uint32_t)db->P + 63) / 64;
     hipLaunchKernelGGL(wide_slices_kernel, dim3(1), dim3(WSL_THREADS), 0, st, b.wide_slice_cnt.get(), db->n_nsegs, b.wide_slice_base.get(), b.wide_base.get(), n_words,
                        b.counters);
     uint32_t n_wide;
-    if (b.have_counts && b.wide_cap >= b.last_n_wide) n_wide = b.last_n_wide;     // deterministic per database; checked at the end of the call
+    if (b.have_counts && b.wide_cap >= b.last_n_wide) n_wide = b.last_n_wide;
     else {
         HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters + KCTR_NWIDE, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -3757,189 +3625,207 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         }
     }
     if (!b.widx) { DEV_ALLOC(b.widx, 1); b.wide_cap = std::max<uint64_t>(b.wide_cap, 1); }
+    const uint32_t wps = db->nseg_nodes / 64u;
+    hipLaunchKernelGGL(wide_expand_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, b.widebits.get(), b.wide_base.get(),
+                       b.wide_slice_base.get(), wps, (wps & (wps - 1u)) ? 0xFFFFFFFFu : (uint32_t)__builtin_ctz(wps), n_words, b.widx.get(), (uint32_t)b.wide_cap);
+    *n_wide_out = n_wide;
+    return 0;
+}
+// ---- 7. K1w, and behind it the second level (BlocksState::l2_on)
+int a2a_wide_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, uint32_t n_wide, hipStream_t st) {
+    WParams q{};
+    q.widx = b.widx; q.n_wide = n_wide; q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.widebits = b.widebits;
+    q.dflag = db->dflag; q.wide_base = b.wide_base;
+    q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
+    q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.pool = pool_view(b, true);
+    if (b.l2_on && !b.l2_bitmap) {
+        // a first guess from the wide list (at 10 000 samples 2 % of the wide nodes have 24 blocks or more); a call that runs out doubles both
+        // (KMDB_POOL_PERCENT, tests: the smallest arrays there are, so that the doubling path runs)
+        const bool tiny = b.knobs.pool_percent != 0;
+        if (alloc_l2(b, tiny ? 1u : std::max<uint32_t>(64u * L2_SUB * 4u, n_wide / 16u), tiny ? 1u : std::max<uint32_t>(L2_ENT_GRAB * L2_SUB * 4u, n_wide / 16u * 48u))) return 1;
+    }
+    q.l2 = L2View{};
+    if (b.l2_on) {
+        q.l2.on = 1u; q.l2.min_blocks = b.l2_min_blocks; q.l2.node_cap = b.l2_node_cap; q.l2.W = b.l2_node_cap / 64u; q.l2.ent_cap = b.l2_ent_cap;
+        q.l2.cursors = b.l2_cursors; q.l2.bitmap = b.l2_bitmap; q.l2.ent_g = b.l2_ent_g; q.l2.ent_blk = b.l2_ent_blk; q.l2.ent_mask = b.l2_ent_mask;
+        q.l2.node_w = b.l2_node_w;
+        HIP_TRY(hipMemsetAsync(b.l2_cursors, 0, 2 * L2_SUB * 16 * 4, st));
+        HIP_TRY(hipMemsetAsync(b.l2_bitmap, 0, (size_t)b.NB * q.l2.W * 8, st));
+        HIP_TRY(hipMemsetAsync(b.l2_ent_blk, 0xFF, (size_t)b.l2_ent_cap * 2, st));
+    }
+    q.run_nodes = b.knobs.k1w_run;
+    q.n_runs = (n_wide + q.run_nodes - 1) / q.run_nodes;
+    // root paths of the runs' first nodes (the table is sized with the wide list, for runs of 64 nodes at least)
+    hipLaunchKernelGGL(wrun_anc_kernel, dim3((q.n_runs + 63) / 64), dim3(64), 0, st, b.widx, n_wide, q.run_nodes, db->parent, db->dflag, db->chain_cap,
+                       b.wrun_anc, b.wrun_anc_n);
+    q.seg_anc = b.wrun_anc; q.seg_anc_n = b.wrun_anc_n;
+    // LDS of a wave: rows of a batch (at least one full list: as many entries as there are blocks), the chain list, the chain
+    q.chain_cap = db->chain_cap; q.e_cap = (b.NB + 2u + 3u) & ~3u; q.arena_cap = std::max<uint32_t>(K1W_ARENA_MIN, (b.NB + 2u + 63u) & ~63u);
+    q.n_rows = b.row_mode ? b.NB : 0u;
+    const size_t wave_lds = k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows);
+    const uint32_t waves = wave_lds * K1W_WAVES <= (size_t)(64u << 10) ? (uint32_t)K1W_WAVES : 1u;
+    // the instantiation of the call's record path: the attribute, the occupancy query and the launch take the same function
+    const K1wPick pick = k1w_pick(b.row_mode, b.l2_on);
+    HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
+    // As many waves as the chip holds at once, each with an equal share of the runs (dealt round-robin): with more, the waves
+    // beyond the first round start when the first ones end, and all take equally long — 1.6 rounds cost 2 (measured at 10 000
+    // samples: 4096 waves at 10 per CU took 8.8 ms, of which every wave ran 4.4).
+    // (the count is kept on the handle: its instantiation and its LDS do not change between the calls)
+    if (!b.k1w_slots) {
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t prop;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pick.fn, (int)(WAVE * waves), wave_lds * waves));
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        b.k1w_slots = (uint32_t)std::max(1, per_cu) * waves * (uint32_t)std::max(1, prop.multiProcessorCount);
+    }
+    q.n_waves = std::min<uint32_t>(std::min<uint32_t>(b.k1w_slots, b.k1w_waves), q.n_runs);
+    q.run_ctr = b.run_ctr;
+    if (b.knobs.k1w_waves) q.n_waves = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(b.k1w_waves, q.n_runs), b.knobs.k1w_waves));
+    if (!b.have_counts && kmdb_verbose())
+        fprintf(stderr, "[kmdb] wide kernel: %u wide nodes in %u runs, %u waves (%u fit the chip, %zu B of LDS per wave, %u per workgroup), instantiation %s\n", n_wide,
+                q.n_runs, q.n_waves, b.k1w_slots, wave_lds, waves, pick.name);
+    hipLaunchKernelGGL(pick.fn, dim3((q.n_waves + waves - 1) / waves), dim3(WAVE * waves), wave_lds * waves, st, q);
+    if (b.l2_on) {
+        // rank directories, list offsets, lists, and the tile joins adding into M (a tile whose blocks have no list leaves at once)
+        const uint32_t NB = b.NB, W = b.l2_node_cap / 64u;
+        hipLaunchKernelGGL(l2_ranks_kernel, dim3(NB), dim3(256), 0, st, b.l2_bitmap, W, b.l2_rank, b.l2_len);
+        hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, b.l2_len, NB, b.l2_cursors, W, b.l2_loff);
+        hipLaunchKernelGGL(l2_lists_kernel, dim3((b.l2_ent_cap + 255u) / 256u), dim3(256), 0, st, b.l2_ent_g, b.l2_ent_blk, b.l2_ent_mask, b.l2_node_w,
+                           b.l2_ent_cap, W, b.l2_bitmap, b.l2_rank, b.l2_loff, b.l2_list_mask, b.l2_list_w, b.l2_cursors);
+        hipLaunchKernelGGL(l2_join_apply_kernel, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
+                           b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched);
+    }
+    return 0;
+}
+// the sorted records applied stream by stream (a long stream in parts of K2J_REC records): one write-back of a tile per job.  k2j_start holds where
+// the streams start (from the sort's offsets: no run boundaries searched, no key word read for packed records)
+void a2a_apply_stream_jobs(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, Launched& L) {
+    hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
+    L.k2jobs = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;       // (the streams' lengths repeat exactly from call to call)
+    if (L.k2jobs)
+        hipLaunchKernelGGL(k2_jobs_kernel, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
+                           (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
+}
+// ---- 8. many streams: chunk table grouped (stream chunks -> side stream), then the sort inside the block rows and its apply
+int a2a_sort_apply_rows(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hipStream_t s2, Launched& L) {
+    if (a2a_group_and_apply_chunks(db, b, M, st, s2)) return 1;
+    const uint32_t NB = b.NB, pool_cap = (uint32_t)b.pool_cap, kmask = (1u << b.key_bits) - 1u;
+    uint32_t* row_job = b.rs_rows, *row_tab = b.rs_rows + (NB + 1);
     {
-        static const bool wave_form = getenv("KMDB_WIDE_EXPAND") && !strcmp(getenv("KMDB_WIDE_EXPAND"), "wave");
-        const uint32_t wps = db->nseg_nodes / 64u;
-        hipLaunchKernelGGL(wave_form ? wide_expand_kernel<false> : wide_expand_kernel<true>, dim3((n_words + 255) / 256), dim3(256), 0, st, b.widebits.get(), b.wide_base.get(),
-                           b.wide_slice_base.get(), wps, (wps & (wps - 1u)) ? 0xFFFFFFFFu : (uint32_t)__builtin_ctz(wps), n_words, b.widx.get(), (uint32_t)b.wide_cap);
+        // the row chunks grouped by row
+        const size_t rg_ne = (size_t)NB * b.rg_blocks + 1;
+        hipLaunchKernelGGL(rg_hist_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_hist);
+        size_t tbg = b.rg_tmp_bytes;
+        HIP_TRY(prim::exclusive_sum(b.rg_tmp, tbg, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
+        hipLaunchKernelGGL(rg_scatter_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_offs, b.row_ids);
     }
-    if (b.k1n_mode == 2 && !k2d_early && apply_slices()) return 1;
-    // ---- K1w
-    if (n_wide) {
-        WParams q{};
-        q.widx = b.widx; q.n_wide = n_wide; q.nl = db->nl; q.parent = db->parent; q.w = db->w; q.widebits = b.widebits;
-        q.dflag = db->dflag; q.wide_base = b.wide_base;
-        q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
-        q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.pool = pool_view(b, b.dense_wide);
-            // ---- second level: many streams, few enough blocks that a tile job's bitmap scan stays small (tiles x nodes: quadratic in the
-        // blocks), KMDB_L2=0 switches it off, KMDB_L2_MIN=c moves the threshold
-        {
-            const char* l2_env = getenv("KMDB_L2");
-            const char* l2_min_env = getenv("KMDB_L2_MIN");
-            b.l2_on = row_mode && b.NB <= 256u && !(l2_env && l2_env[0] == '0');
-            b.l2_min_blocks = l2_min_env ? std::max<uint32_t>(K1W_HEAVY, (uint32_t)atoi(l2_min_env)) : L2_MIN_BLOCKS;
-            if (b.l2_on && !b.l2_bitmap) {
-                // a first guess from the wide list (at 10 000 samples 2 % of the wide nodes have 24 blocks or more); a call that runs out doubles both
-                // (KMDB_POOL_PERCENT, tests: the smallest arrays there are, so that the doubling path runs)
-                const bool tiny = getenv("KMDB_POOL_PERCENT") != nullptr;
-                if (alloc_l2(b, tiny ? 1u : std::max<uint32_t>(64u * L2_SUB * 4u, n_wide / 16u), tiny ? 1u : std::max<uint32_t>(L2_ENT_GRAB * L2_SUB * 4u, n_wide / 16u * 48u))) return 1;
-            }
-            q.l2 = L2View{};
-            if (b.l2_on) {
-                q.l2.on = 1u; q.l2.min_blocks = b.l2_min_blocks; q.l2.node_cap = b.l2_node_cap; q.l2.W = b.l2_node_cap / 64u; q.l2.ent_cap = b.l2_ent_cap;
-                q.l2.cursors = b.l2_cursors; q.l2.bitmap = b.l2_bitmap; q.l2.ent_g = b.l2_ent_g; q.l2.ent_blk = b.l2_ent_blk; q.l2.ent_mask = b.l2_ent_mask;
-                q.l2.node_w = b.l2_node_w;
-                HIP_TRY(hipMemsetAsync(b.l2_cursors, 0, 2 * L2_SUB * 16 * 4, st));
-                HIP_TRY(hipMemsetAsync(b.l2_bitmap, 0, (size_t)b.NB * q.l2.W * 8, st));
-                HIP_TRY(hipMemsetAsync(b.l2_ent_blk, 0xFF, (size_t)b.l2_ent_cap * 2, st));
-            }
-        }
-        q.run_nodes = K1W_RUN_NODES;
-        if (const char* e = getenv("KMDB_K1W_RUN")) q.run_nodes = std::max<uint32_t>(64u, (uint32_t)atoi(e) / 64u * 64u);
-        q.n_runs = (n_wide + q.run_nodes - 1) / q.run_nodes;
-        // root paths of the runs' first nodes (the table is sized with the wide list, for runs of 64 nodes at least)
-        hipLaunchKernelGGL(wrun_anc_kernel, dim3((q.n_runs + 63) / 64), dim3(64), 0, st, b.widx, n_wide, q.run_nodes, db->parent, db->dflag, db->chain_cap,
-                           b.wrun_anc, b.wrun_anc_n);
-        q.seg_anc = b.wrun_anc; q.seg_anc_n = b.wrun_anc_n;
-        
-        // LDS of a wave: rows of a batch (at least one full list: as many entries as there are blocks), the chain list, the chain
-        q.chain_cap = db->chain_cap; q.e_cap = (b.NB + 2u + 3u) & ~3u; q.arena_cap = std::max<uint32_t>(K1W_ARENA_MIN, (b.NB + 2u + 63u) & ~63u);
-        q.n_rows = row_mode ? b.NB : 0u;
-        const size_t wave_lds = k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows);
-        const uint32_t waves = wave_lds * K1W_WAVES <= (size_t)(64u << 10) ? (uint32_t)K1W_WAVES : 1u;
-        // the instantiation of the call's record path: the attribute, the occupancy query and the launch take the same function
-        const K1wPick pick = k1w_pick(row_mode, b.l2_on);
-        HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
-        // As many waves as the chip holds at once, each with an equal share of the runs (dealt round-robin): with more, the waves
-        // beyond the first round start when the first ones end, and all take equally long — 1.6 rounds cost 2 (measured at 10 000
-        // samples: 4096 waves at 10 per CU took 8.8 ms, of which every wave ran 4.4).
-        // (the count is kept on the handle with the instantiation it was asked for: KMDB_L2 may change between the calls of a handle)
-        if (!b.k1w_slots || b.k1w_slots_fn != (const void*)pick.fn) {
-            int per_cu = 0, dev = 0;
-            hipDeviceProp_t prop;
-            b.k1w_slots = 0; b.k1w_slots_fn = (const void*)pick.fn;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pick.fn, (int)(WAVE * waves), wave_lds * waves));
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipGetDeviceProperties(&prop, dev));
-            b.k1w_slots = (uint32_t)std::max(1, per_cu) * waves * (uint32_t)std::max(1, prop.multiProcessorCount);
-        }
-        q.n_waves = std::min<uint32_t>(std::min<uint32_t>(b.k1w_slots, b.k1w_waves), q.n_runs);
-        q.run_ctr = b.run_ctr;
-        if (const char* e = getenv("KMDB_K1W_WAVES")) q.n_waves = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(b.k1w_waves, q.n_runs), (uint32_t)atoi(e)));
-        if (!b.have_counts && getenv("KMDB_VERBOSE"))
-            fprintf(stderr, "[kmdb] wide kernel: %u wide nodes in %u runs, %u waves (%u fit the chip, %zu B of LDS per wave, %u per workgroup), instantiation %s\n", n_wide,
-                    q.n_runs, q.n_waves, b.k1w_slots, wave_lds, waves, pick.name);
-        hipLaunchKernelGGL(pick.fn, dim3((q.n_waves + waves - 1) / waves), dim3(WAVE * waves), wave_lds * waves, st, q);
-        if (b.l2_on) {
-            // rank directories, list offsets, lists, and the tile joins adding into M (a tile whose blocks have no list leaves at once)
-            const uint32_t NB = b.NB, W = b.l2_node_cap / 64u;
-            hipLaunchKernelGGL(l2_ranks_kernel, dim3(NB), dim3(256), 0, st, b.l2_bitmap, W, b.l2_rank, b.l2_len);
-            hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, b.l2_len, NB, b.l2_cursors, W, b.l2_loff);
-            hipLaunchKernelGGL(l2_lists_kernel, dim3((b.l2_ent_cap + 255u) / 256u), dim3(256), 0, st, b.l2_ent_g, b.l2_ent_blk, b.l2_ent_mask, b.l2_node_w,
-                               b.l2_ent_cap, W, b.l2_bitmap, b.l2_rank, b.l2_loff, b.l2_list_mask, b.l2_list_w, b.l2_cursors);
-            hipLaunchKernelGGL(l2_join_apply_kernel, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
-                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched);
-        }
-    }
+    hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters);
+    const RsRows R{b.rg_offs, b.row_ids, b.rg_blocks, NB, row_job, row_tab};
+    // jobs and table entries: measured by the previous call, else their upper bounds (workgroups beyond the last job leave at once)
+    const uint32_t jobs_bound = (uint32_t)(pool_cap / RS_JOB_CHUNKS + NB + 1);
+    const uint32_t jobs = b.have_counts ? std::min<uint32_t>(jobs_bound, with_slack(b.last_n_rowjobs)) : jobs_bound;
+    L.rowjobs = jobs;
+    const size_t ne = std::min<size_t>(b.rs_entries, (size_t)jobs * NB + 1);
+    HIP_TRY(hipMemsetAsync(b.rs_hist, 0, ne * 4, st));
+    // (16 chunks' key words requested together; 4, round 4's, and 8 at 10 000 samples: apply step 6.08 / 5.88 against 5.85 ms, profiles/r05_j14 — the
+    // kernel waits for its loads)
+    hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
+    size_t tb = b.rs_tmp_bytes;
+    HIP_TRY(prim::exclusive_sum(b.rs_tmp, tb, b.rs_hist.get(), b.rs_offs.get(), (int)ne, st));
+    const uint32_t* total_ptr = b.rs_offs + (ne - 1);
+    HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
+    // (Sorting and applying bands of block rows side by side on two streams was measured at 10 000 samples: 2 / 4 / 8 bands 18.4 / 17.0 /
+    // 18.7 ms against 16.5 for one — the two kernels do not complement each other.)
+    HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(NB, b.rec_pshift != 0)));
+    hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(NB, b.rec_pshift != 0), st, R, b.chunk_fill, b.recw, (const WideRec*)b.rec.get(), kmask,
+                       b.rs_offs, (uint32_t)b.sorted_cap, b.swkey, (WideRec*)b.swrec, b.counters, b.rec_pshift ? 1u : 0u);
+    hipLaunchKernelGGL(k2j_starts_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
+    a2a_apply_stream_jobs(db, b, M, st, L);
     HIP_TRY(hipGetLastError());
-    if (stage("wide emit")) return 1;
-    HIP_TRY(hipEventRecord(db->ev_k[2], st));
-    const uint32_t kmask = (1u << b.key_bits) - 1u;
-    uint32_t jobs_launched = 0, k2jobs_launched = 0;
-    if (row_mode) {
-        // ---- many streams: chunk table grouped (stream chunks -> side stream), then the sort inside the block rows and its apply
-        if (group_and_apply_chunks(st)) return 1;
-        const uint32_t NB = b.NB;
-        uint32_t* row_job = b.rs_rows, *row_tab = b.rs_rows + (NB + 1);
-        {
-            // the row chunks grouped by row
-            const size_t rg_ne = (size_t)NB * b.rg_blocks + 1;
-            hipLaunchKernelGGL(rg_hist_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_hist);
-            size_t tbg = b.rg_tmp_bytes;
-            HIP_TRY(prim::exclusive_sum(b.rg_tmp, tbg, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
-            hipLaunchKernelGGL(rg_scatter_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_offs, b.row_ids);
-        }
-        hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters);
-        const RsRows R{b.rg_offs, b.row_ids, b.rg_blocks, NB, row_job, row_tab};
-        // jobs and table entries: measured by the previous call, else their upper bounds (workgroups beyond the last job leave at once)
-        const uint32_t jobs_bound = (uint32_t)(pool_cap / RS_JOB_CHUNKS + NB + 1);
-        const uint32_t jobs = b.have_counts ? std::min<uint32_t>(jobs_bound, with_slack(b.last_n_rowjobs)) : jobs_bound;
-        jobs_launched = jobs;
-        const size_t ne = std::min<size_t>(b.rs_entries, (size_t)jobs * NB + 1);
-        HIP_TRY(hipMemsetAsync(b.rs_hist, 0, ne * 4, st));
-        {
-            // (4, round 4's, against 8 / 16 at 10 000 samples: apply step 6.08 / 5.88 / 5.85 ms, profiles/r05_j14 — the kernel waits for its loads)
-            const char* ue = getenv("KMDB_RSH_UNROLL");
-            const int u = ue ? atoi(ue) : 16;
-            if (u == 16) hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
-            else if (u == 8) hipLaunchKernelGGL(rs_hist_kernel<8>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
-            else hipLaunchKernelGGL(rs_hist_kernel<4>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
-        }
-        size_t tb = b.rs_tmp_bytes;
-        HIP_TRY(prim::exclusive_sum(b.rs_tmp, tb, b.rs_hist.get(), b.rs_offs.get(), (int)ne, st));
-        const uint32_t* total_ptr = b.rs_offs + (ne - 1);
-        HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
-        // (Sorting and applying bands of block rows side by side on two streams was measured at 10 000 samples: 2 / 4 / 8 bands 18.4 / 17.0 /
-        // 18.7 ms against 16.5 for one — the two kernels do not complement each other.)
-        HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(NB, b.rec_pshift != 0)));
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(NB, b.rec_pshift != 0), st, R, b.chunk_fill, b.recw, (const WideRec*)b.rec.get(), kmask,
-                           b.rs_offs, (uint32_t)b.sorted_cap, b.swkey, (WideRec*)b.swrec, b.counters, b.rec_pshift ? 1u : 0u);
-        // the sorted records applied stream by stream (a long stream in parts of K2J_REC records): one write-back of a tile per job
-        hipLaunchKernelGGL(k2j_starts_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
-        hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
-        k2jobs_launched = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;       // (the streams' lengths repeat exactly from call to call)
-        if (k2jobs_launched)
-            hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
-                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
-        HIP_TRY(hipGetLastError());
-        if (stage("row sort+apply")) return 1;
-    } else {
-        hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(64), 0, st, b.wsub_cursor, (uint32_t)(b.wide_pool_cap / KMDB_SUBPOOLS), b.counters, b.wide_handed.get());
-        // the wide pool: records sorted by stream (the sort moves the 16-byte records with their key words), one tile per run
-        uint32_t n_raw;
-        if (b.have_counts) n_raw = raw_launch;
-        else {
-            HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            n_raw = std::min<uint32_t>(b.h_counters[KCTR_RAW], (uint32_t)b.wide_pool_cap);
-        }
-        if (n_raw) {
-            const uint32_t nslots = (uint32_t)((uint64_t)n_raw << WCH_SHIFT);
-            const CsRows no_rows{};
-            const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
-            hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), b.n_states * 4, st, b.wkey, nslots, b.n_states, b.n_states, (int)CS_BY_STREAM,
-                               no_rows, kmask, b.cs_hist, b.wide_handed.get());
-            size_t tb = b.cs_tmp_bytes;
-            HIP_TRY(prim::exclusive_sum(b.cs_tmp, tb, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
-            const bool packed = b.rec_pshift != 0;
-            HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(b.n_states, packed)));
-            hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(b.n_states, packed), st, b.wkey, (const WideRec*)b.wrec, nslots,
-                               b.n_states, b.n_states, (int)CS_BY_STREAM, no_rows, kmask, b.cs_offs, b.swkey, (WideRec*)b.swrec, packed ? 1u : 0u, b.wide_handed.get());
-            const uint32_t* total_ptr = b.cs_offs + (ne - 1);
-            HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
-            if (getenv("KMDB_K2_WINDOWS") && !packed) {
-                // (A/B: round 4's apply step over windows of 4096 sorted positions, run boundaries searched in the key words)
-                const uint32_t g2 = (nslots + K2S_WIN - 1) / K2S_WIN;
-                hipLaunchKernelGGL(k2_sorted_kernel, dim3(g2), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, nslots, total_ptr, (const uint32_t*)nullptr,
-                                   b.n_states, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, 0u, 0u, b.tile_touched);
-            } else {
-                // the sorted records applied stream by stream, as on the many-streams path: the streams start where the sort's offsets say (no run
-                // boundaries searched, no key word read for packed records), a tile is written back once per K2J_REC records of its stream
-                hipLaunchKernelGGL(k2j_starts_flat_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, b.cs_offs, b.n_states, CS_BLOCKS_ONE, b.k2j_start);
-                hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
-                k2jobs_launched = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;
-                if (k2jobs_launched)
-                    hipLaunchKernelGGL(k2_jobs_kernel, dim3(k2jobs_launched), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
-                                       (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        if (stage("sorted apply")) return 1;
+    return 0;
+}
+// ---- 9. few streams: the wide pool sorted by stream in one counting-sort pass (the sort moves the 16-byte records, with their key words unless
+// they are packed), then applied stream by stream as on the many-streams path
+int a2a_sort_apply_flat(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, Launched& L) {
+    hipLaunchKernelGGL(count_raw_kernel, dim3(1), dim3(64), 0, st, b.wsub_cursor, (uint32_t)(b.wide_pool_cap / KMDB_SUBPOOLS), b.counters, b.wide_handed.get());
+    uint32_t n_raw;
+    if (b.have_counts) n_raw = L.raw;
+    else {
+        HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_raw = std::min<uint32_t>(b.h_counters[KCTR_RAW], (uint32_t)b.wide_pool_cap);
     }
-    HIP_TRY(hipStreamWaitEvent(st, db->ev_side[1], 0));          // the side stream's tiles are in the matrix too
-    hipLaunchKernelGGL(pool_used_kernel, dim3(1), dim3(64), 0, st, b.sub_cursor, b.direct_ctr, b.counters);
-    HIP_TRY(hipEventRecord(db->ev_k[3], st));
-    // ---- what the call found
+    if (!n_raw) return 0;
+    const uint32_t nslots = (uint32_t)((uint64_t)n_raw << WCH_SHIFT), kmask = (1u << b.key_bits) - 1u;
+    const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
+    hipLaunchKernelGGL(cs_hist_kernel, dim3(CS_BLOCKS_ONE), dim3(256), b.n_states * 4, st, b.wkey, nslots, b.n_states, b.n_states, kmask, b.cs_hist, b.wide_handed.get());
+    size_t tb = b.cs_tmp_bytes;
+    HIP_TRY(prim::exclusive_sum(b.cs_tmp, tb, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
+    const bool packed = b.rec_pshift != 0;
+    HIP_TRY(hipFuncSetAttribute((const void*)cs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cs_scatter_lds(b.n_states, packed)));
+    hipLaunchKernelGGL(cs_scatter_kernel, dim3(CS_BLOCKS_ONE), dim3(CS_THREADS), cs_scatter_lds(b.n_states, packed), st, b.wkey, (const WideRec*)b.wrec, nslots,
+                       b.n_states, b.n_states, kmask, b.cs_offs, b.swkey, (WideRec*)b.swrec, packed ? 1u : 0u, b.wide_handed.get());
+    const uint32_t* total_ptr = b.cs_offs + (ne - 1);
+    HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k2j_starts_flat_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, b.cs_offs, b.n_states, CS_BLOCKS_ONE, b.k2j_start);
+    a2a_apply_stream_jobs(db, b, M, st, L);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// a pool ran over (results invalid): it is enlarged — or, at the limit of what a pool can index, the call takes more slices of the pattern stream —
+// and the call repeated.  Leaves db->fallback_reason when neither is possible.
+int a2a_enlarge_pools(kmdb_db* db, BlocksState& b, const uint32_t* c) {
+    const bool verbose = kmdb_verbose();
+    if (c[KCTR_PAIR_OVERFLOW]) {
+        if (verbose) fprintf(stderr, "[kmdb] pair pool too small (%llu entries): doubling\n", (unsigned long long)b.pair_cap);
+        if (alloc_pair_pool(b, b.pair_cap * 2)) return 1;
+    }
+    if (c[KCTR_WIDE_OVERFLOW]) {
+        const uint64_t want = b.wide_pool_cap * 2;
+        if ((want << WCH_SHIFT) >= pool_slot_limit(b)) {
+            if (b.n_slices >= (1u << 16)) { db->fallback_reason = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
+            b.n_slices *= 2;                                  // the pools stay as they are: half as many patterns per pass
+            if (verbose) fprintf(stderr, "[kmdb] wide record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
+            return 0;
+        }
+        if (verbose) fprintf(stderr, "[kmdb] wide record pool too small (%llu chunks): doubling\n", (unsigned long long)b.wide_pool_cap);
+        if (alloc_wide_pool(b, db->stream, want)) return 1;
+    }
+    if (c[KCTR_POOL_OVERFLOW]) {
+        uint64_t want = b.pool_cap * 2;
+        if (!b.row_mode && !b.dense_narrow && b.n_states > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
+            // the estimate is long covered: the narrow kernel's chunks are being evicted nearly empty.  Wide pool for it as well.
+            b.dense_narrow = true;
+            if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the sort too\n");
+            if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC + (uint64_t)db->n_nsegs * (WIDE_GRAB + 2))) return 1;
+            want = 0;
+        } else if (b.row_mode && !b.dense_narrow && b.NB > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
+            // the same with row chunks: the diagonal records join the rows
+            b.dense_narrow = true;
+            if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the row chunks too\n");
+            if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC)) return 1;
+            want = 0;
+        } else if ((want << CH_SHIFT) >= pool_slot_limit(b)) {
+            if (b.n_slices >= (1u << 16)) {
+                db->fallback_reason = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(b.n_states) + " streams, " + std::to_string(b.pool_cap) + " chunks were not enough)";
+                return 0;
+            }
+            b.n_slices *= 2;
+            if (verbose) fprintf(stderr, "[kmdb] record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
+            return 0;
+        }
+        if (want) {
+            if (verbose) fprintf(stderr, "[kmdb] record pool too small (%llu chunks): %llu\n", (unsigned long long)b.pool_cap, (unsigned long long)want);
+            if (alloc_record_pool(b, db->stream, want)) return 1;
+        }
+    }
+    return 0;
+}
+// ---- 10. what the call found: the counters read back (the call's end), then — a pool or the second level ran over: enlarged (or more slices), retry;
+// a launch sized too small: retry with upper bounds; headroom growth; what the next call remembers.  *retry: the attempt's results are invalid.
+int a2a_settle(kmdb_db* db, BlocksState& b, hipStream_t st, const Launched& L, bool* retry) {
+    const bool row_mode = b.row_mode;
     HIP_TRY(hipMemcpyAsync(b.h_counters, b.counters, KCTR_COUNT * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t* c = b.h_counters;
@@ -3948,70 +3834,25 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
         return 0;
     }
     if (c[KCTR_L2_OVERFLOW]) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] second level out of node indices or entries (%u / %u): doubling\n", b.l2_node_cap, b.l2_ent_cap);
+        if (kmdb_verbose()) fprintf(stderr, "[kmdb] second level out of node indices or entries (%u / %u): doubling\n", b.l2_node_cap, b.l2_ent_cap);
         if (alloc_l2(b, b.l2_node_cap * 2u, b.l2_ent_cap * 2u)) return 1;
         b.have_counts = false; *retry = true;
         return 0;
     }
     if (c[KCTR_PAIR_OVERFLOW] || c[KCTR_POOL_OVERFLOW] || c[KCTR_WIDE_OVERFLOW]) {
-        const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
-        if (c[KCTR_PAIR_OVERFLOW]) {
-            if (verbose) fprintf(stderr, "[kmdb] pair pool too small (%llu entries): doubling\n", (unsigned long long)b.pair_cap);
-            if (alloc_pair_pool(b, b.pair_cap * 2)) return 1;
-        }
-        if (c[KCTR_WIDE_OVERFLOW]) {
-            const uint64_t want = b.wide_pool_cap * 2;
-            if ((want << WCH_SHIFT) >= pool_slot_limit(b)) {
-                if (b.n_slices >= (1u << 16)) { db->fallback_reason = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
-                b.n_slices *= 2;                                  // the pools stay as they are: half as many patterns per pass
-                if (verbose) fprintf(stderr, "[kmdb] wide record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
-                b.have_counts = false; *retry = true;
-                return 0;
-            }
-            if (verbose) fprintf(stderr, "[kmdb] wide record pool too small (%llu chunks): doubling\n", (unsigned long long)b.wide_pool_cap);
-            if (alloc_wide_pool(b, db->stream, want)) return 1;
-        }
-        if (c[KCTR_POOL_OVERFLOW]) {
-            uint64_t want = b.pool_cap * 2;
-            if (!row_mode && !b.dense_narrow && b.n_states > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
-                // the estimate is long covered: the narrow kernel's chunks are being evicted nearly empty.  Wide pool for it as well.
-                b.dense_narrow = true;
-                if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the sort too\n");
-                if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC + (uint64_t)db->n_nsegs * (WIDE_GRAB + 2))) return 1;
-                want = 0;
-            } else if (row_mode && !b.dense_narrow && b.NB > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
-                // the same with row chunks: the diagonal records join the rows
-                b.dense_narrow = true;
-                if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the row chunks too\n");
-                if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC)) return 1;
-                want = 0;
-            } else if ((want << CH_SHIFT) >= pool_slot_limit(b)) {
-                if (b.n_slices >= (1u << 16)) {
-                    db->fallback_reason = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(b.n_states) + " streams, " + std::to_string(b.pool_cap) + " chunks were not enough)";
-                    return 0;
-                }
-                b.n_slices *= 2;
-                if (verbose) fprintf(stderr, "[kmdb] record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
-                b.have_counts = false; *retry = true;
-                return 0;
-            }
-            if (want) {
-                if (verbose) fprintf(stderr, "[kmdb] record pool too small (%llu chunks): %llu\n", (unsigned long long)b.pool_cap, (unsigned long long)want);
-                if (alloc_record_pool(b, db->stream, want)) return 1;
-            }
-        }
-        b.have_counts = false; *retry = true;
+        if (a2a_enlarge_pools(db, b, c)) return 1;
+        if (db->fallback_reason.empty()) { b.have_counts = false; *retry = true; }
         return 0;
     }
     if (b.have_counts && (c[KCTR_NWIDE] != b.last_n_wide || c[KCTR_CHUNKS] != b.last_n_chunks ||
-                            (row_mode ? (c[KCTR_ROWJOBS] > jobs_launched || c[KCTR_WIDE_RECORDS] != b.last_n_sorted || c[KCTR_K2JOBS] > k2jobs_launched)
-                                      : (c[KCTR_RAW] > raw_launch || c[KCTR_K2JOBS] > k2jobs_launched)))) {
+                            (row_mode ? (c[KCTR_ROWJOBS] > L.rowjobs || c[KCTR_WIDE_RECORDS] != b.last_n_sorted || c[KCTR_K2JOBS] > L.k2jobs)
+                                      : (c[KCTR_RAW] > L.raw || c[KCTR_K2JOBS] > L.k2jobs)))) {
         // the exact counts cannot differ for an unchanged database and emit range, and the varying ones stay inside their slack in
         // practice; if not: redo the call with upper bounds
-        if (getenv("KMDB_VERBOSE"))
+        if (kmdb_verbose())
             fprintf(stderr, "[kmdb] a launch was sized too small (wide nodes %u / %u, chunks %u / %u, row jobs %u / %u, sorted %u / %u, apply jobs %u / %u, raw %u / %u): the call is repeated\n",
-                    c[KCTR_NWIDE], b.last_n_wide, c[KCTR_CHUNKS], b.last_n_chunks, c[KCTR_ROWJOBS], jobs_launched, c[KCTR_WIDE_RECORDS], b.last_n_sorted, c[KCTR_K2JOBS],
-                    k2jobs_launched, c[KCTR_RAW], raw_launch);
+                    c[KCTR_NWIDE], b.last_n_wide, c[KCTR_CHUNKS], b.last_n_chunks, c[KCTR_ROWJOBS], L.rowjobs, c[KCTR_WIDE_RECORDS], b.last_n_sorted, c[KCTR_K2JOBS],
+                    L.k2jobs, c[KCTR_RAW], L.raw);
         b.have_counts = false; *retry = true;
         return 0;
     }
@@ -4019,26 +3860,64 @@ int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi,
     // be too small next time (a warm call would then take the enlarge-and-repeat path: seen once in the tests with pools of 1 %).  A pool
     // more than 85 % in use grows by a quarter now, while nothing runs.
     if ((uint64_t)c[KCTR_POOL_USED] * 100 > b.pool_cap * 85) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_POOL_USED], (unsigned long long)b.pool_cap);
+        if (kmdb_verbose()) fprintf(stderr, "[kmdb] record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_POOL_USED], (unsigned long long)b.pool_cap);
         const uint64_t want = b.pool_cap + b.pool_cap / 4;
         if (((want + (uint64_t)KMDB_SUBPOOLS * ARENA_GRAB) << CH_SHIFT) < pool_slot_limit(b) && alloc_record_pool(b, db->stream, want)) return 1;
     }
     if (!row_mode && (uint64_t)c[KCTR_RAW] * 100 > b.wide_pool_cap * 85) {
-        if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] wide record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_RAW], (unsigned long long)b.wide_pool_cap);
+        if (kmdb_verbose()) fprintf(stderr, "[kmdb] wide record pool %u of %llu chunks in use: enlarged by a quarter\n", c[KCTR_RAW], (unsigned long long)b.wide_pool_cap);
         const uint64_t want = b.wide_pool_cap + b.wide_pool_cap / 4;
         if (((want + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) << WCH_SHIFT) < pool_slot_limit(b) && alloc_wide_pool(b, db->stream, want)) return 1;
     }
-    if (!b.have_counts && getenv("KMDB_VERBOSE"))
+    if (!b.have_counts && kmdb_verbose())
         fprintf(stderr, "[kmdb] record pool: %u of %llu chunks in use (busiest sub-pool x sub-pools); wide pool / sorted arrays: %llu slots\n", c[KCTR_POOL_USED],
                 (unsigned long long)b.pool_cap, (unsigned long long)b.sorted_cap);
-    b.last_n_wide = c[KCTR_NWIDE]; b.last_n_chunks = c[KCTR_CHUNKS]; b.last_n_raw = c[KCTR_RAW]; b.last_n_slow = c[KCTR_SLOW];
+    b.last_n_wide = c[KCTR_NWIDE]; b.last_n_chunks = c[KCTR_CHUNKS]; b.last_n_raw = c[KCTR_RAW];
     b.last_n_rowjobs = c[KCTR_ROWJOBS]; b.last_n_sorted = c[KCTR_WIDE_RECORDS]; b.last_l2_nodes = c[KCTR_L2_NODES]; b.last_n_k2jobs = c[KCTR_K2JOBS];
-    if (b.l2_on && !b.have_counts && getenv("KMDB_VERBOSE"))
+    if (b.l2_on && !b.have_counts && kmdb_verbose())
         fprintf(stderr, "[kmdb] second level: %u nodes with %u blocks or more joined per tile (indices for %u, entries for %u)\n", c[KCTR_L2_NODES], b.l2_min_blocks,
                 b.l2_node_cap, b.l2_ent_cap);
     b.last_records = ((uint64_t)c[KCTR_RECORDS] | ((uint64_t)c[KCTR_RECORDS_HI] << 32)) + (row_mode ? 0u : c[KCTR_WIDE_RECORDS]);
     b.last_n_direct = c[KCTR_DIRECT];
     return 0;
+}
+// one attempt of the whole pipeline; *retry is set when a pool was too small (it has been enlarged)
+// decode: run K0 (the first slice of a call does; what it leaves — the local (block, mask) pairs of every node — serves all slices)
+int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry) {
+    BlocksState& b = *db->blocks;
+    hipStream_t s2 = db->stream2;
+    *retry = false;
+    Launched L;
+    if (b.have_counts) L.raw = (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), b.row_mode ? 0xFFFFFFFFull : b.wide_pool_cap);
+    a2a_prologue(b, st, decode);
+    if (stage_done(st, "init")) return 1;
+    if (decode && a2a_decode(db, b, st)) return 1;
+    if (stage_done(st, "decode")) return 1;
+    HIP_TRY(hipEventRecord(db->ev_k[0], st));
+    if (a2a_narrow_emit(db, b, M, emit_lo, emit_hi, st)) return 1;
+    if (stage_done(st, "narrow emit")) return 1;
+    HIP_TRY(hipEventRecord(db->ev_k[1], st));
+    if (b.k1n_mode == 2 && b.knobs.k2d_early && a2a_slice_apply(db, b, M, st, s2)) return 1;
+    if (!b.row_mode) {
+        if (!b.dense_narrow) {
+            HIP_TRY(hipEventRecord(db->ev_side[0], st));
+            HIP_TRY(hipStreamWaitEvent(s2, db->ev_side[0], 0));
+            if (a2a_group_and_apply_chunks(db, b, M, s2, s2)) return 1;
+        } else HIP_TRY(hipEventRecord(db->ev_side[1], s2));        // (no stream chunk is ever opened: nothing to group; the side stream holds the slices' apply kernel or nothing)
+    }
+    uint32_t n_wide = 0;
+    if (a2a_wide_list(db, b, st, &n_wide)) return 1;
+    if (b.k1n_mode == 2 && !b.knobs.k2d_early && a2a_slice_apply(db, b, M, st, s2)) return 1;
+    if (n_wide && a2a_wide_emit(db, b, M, emit_lo, emit_hi, n_wide, st)) return 1;
+    HIP_TRY(hipGetLastError());
+    if (stage_done(st, "wide emit")) return 1;
+    HIP_TRY(hipEventRecord(db->ev_k[2], st));
+    if (b.row_mode ? a2a_sort_apply_rows(db, b, M, st, s2, L) : a2a_sort_apply_flat(db, b, M, st, L)) return 1;
+    if (stage_done(st, b.row_mode ? "row sort+apply" : "sorted apply")) return 1;
+    HIP_TRY(hipStreamWaitEvent(st, db->ev_side[1], 0));          // the side stream's tiles are in the matrix too
+    hipLaunchKernelGGL(pool_used_kernel, dim3(1), dim3(64), 0, st, b.sub_cursor, b.direct_ctr, b.counters);
+    HIP_TRY(hipEventRecord(db->ev_k[3], st));
+    return a2a_settle(db, b, st, L, retry);
 }
 
 }  // namespace

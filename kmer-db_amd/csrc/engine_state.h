@@ -1,5 +1,6 @@
 // engine_state.h — the HBM-resident database shared by the translation units of libkmdb_amd.so
-// (engine.hip: layout / entry points, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline).
+// (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, node_arrays.hip: the node
+// arrays of the v1 kernels and of new2all).
 #pragma once
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
@@ -152,7 +153,7 @@ uint64_t kmdb_blocks_device_bytes(const kmdb_db* db);
 struct kmdb_blocks_counts { uint64_t records, direct; uint32_t wide, chunks, joined; };
 kmdb_blocks_counts kmdb_blocks_last_counts(const kmdb_db* db);
 const unsigned char* kmdb_blocks_tile_touched(const kmdb_db* db);
-// v1 / new2all node arrays, derived on the device from the compact layout
+// ---- node_arrays.hip: v1 / new2all node arrays, derived on the device from the compact layout
 int kmdb_ensure_v1_arrays(kmdb_db* db);
 
 // layout.hip: unmap db->staging piece by piece on a detached thread

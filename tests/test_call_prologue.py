@@ -84,11 +84,11 @@ def test_wide_list_from_the_narrow_kernels_counts(K, dev, env, width, N, name, a
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("extra", [{"KMDB_NSEG": "64"}, {"KMDB_NSEG": "64", "KMDB_K1N_MODE": "0"}, {"KMDB_NSEG": "192", "KMDB_WIDE_EXPAND": "wave"}],
+@pytest.mark.parametrize("extra", [{"KMDB_NSEG": "64"}, {"KMDB_NSEG": "64", "KMDB_K1N_MODE": "0"}, {"KMDB_NSEG": "192"}],
                          ids=lambda x: ",".join("%s=%s" % kv for kv in sorted(x.items())))
 def test_wide_list_with_slices_of_64_nodes(dev, extra):
     """The same forests with slices of 64 nodes (one word of wide bits per slice: every slice total is one word's count, a hundred slices are all
-    wide), and — slices of 192 nodes, three words each: no power of two — with the expand kernel's wave form."""
+    wide), and with slices of 192 nodes, three words each: no power of two, the expand kernel divides instead of shifting."""
     _child(extra, ["wide"])
 
 

@@ -1333,17 +1333,16 @@ def test_patterns_that_touch_every_block_of_many(K, O, dev):
     d.close()
 
 
-@pytest.mark.parametrize("form", ["packed", "unpacked", "windows"])
+@pytest.mark.parametrize("form", ["packed", "unpacked"])
 def test_few_streams_record_forms(K, O, dev, tmp_path, form):
-    """The few-streams path (at most 2048 block pairs: BASELINE configs[1]) moves its block records in one of three forms: packed (block
+    """The few-streams path (at most 2048 block pairs: BASELINE configs[1]) moves its block records in one of two forms: packed (block
     width <= 54: 16 bytes, the weight digit in the column word's spare bits, the key words stay behind in the one-pass sort, apply step by
-    stream jobs), unpacked (KMDB_REC_PACKED=0, or any width above 54: 16 + 4 bytes, stream jobs) and round 4's (windows of 4096 sorted
-    positions, KMDB_K2_WINDOWS).  Random forests with weights of up to 32 bits (one to four digits of 8 - 16 bits) at widths 32 / 50 / 54 /
+    stream jobs) and unpacked (KMDB_REC_PACKED=0, or any width above 54: 16 + 4 bytes, stream jobs).  Random forests with weights of up to 32 bits (one to four digits of 8 - 16 bits) at widths 32 / 50 / 54 /
     64 against the oracle: whole call, warm call, slices of the pattern stream (reference src/similarity_calculator.cpp:42-438)."""
     import importlib
     S = importlib.import_module("kmerdb_amd.synth")
-    env = {"packed": {}, "unpacked": {"KMDB_REC_PACKED": "0"}, "windows": {"KMDB_REC_PACKED": "0", "KMDB_K2_WINDOWS": "1"}}[form]
-    keys = ("KMDB_REC_PACKED", "KMDB_K2_WINDOWS", "KMDB_BLOCK_WIDTH", "KMDB_ROW_MODE")
+    env = {"packed": {}, "unpacked": {"KMDB_REC_PACKED": "0"}}[form]
+    keys = ("KMDB_REC_PACKED", "KMDB_BLOCK_WIDTH", "KMDB_ROW_MODE")
     saved = {k: os.environ.get(k) for k in keys}
     try:
         for k in keys:

@@ -1,8 +1,8 @@
 """Every kernel variant of all2all and new2all that a switch of the engine selects, not only the ones the default configuration launches:
 the three ways of the narrow kernel's first-block records (KMDB_K1N_MODE 0 / 1 / 2: stream chunks and k2_apply_kernel, the matrix-core
-step inside k1n_kernel<1, *>, compacted slices and k2d_kernel), few and many streams under each, the switches read once per process
-(KMDB_K1N_MINW, KMDB_K2D_SLICES, KMDB_K2D_EARLY, KMDB_SYNC_DEBUG: child processes), the two launches of the decode kernel either side of
-KMDB_SHORT_IDS, rs_hist_kernel<4 / 8>, and the eight instantiations of new2all's walk.  The inputs (tests/variant_cases.py) hold the edges
+step inside k1n_kernel<1, *>, compacted slices and k2d_kernel), few and many streams under each, KMDB_K1N_MINW, KMDB_K2D_SLICES, KMDB_K2D_EARLY and
+KMDB_SYNC_DEBUG in child processes, the two launches of the decode kernel either side of
+KMDB_SHORT_IDS, the sort inside the block rows on a random forest and a clade collection, and the eight instantiations of new2all's walk.  The inputs (tests/variant_cases.py) hold the edges
 of these kernels on purpose — the int8 operand limit, the 32 / 32 split of the matrix-core tile, partial last blocks, changes of the first
 block inside a slice — and a census on the host proves it before anything runs on a device.  All comparisons are exact (uint32 sums)."""
 import functools
@@ -20,8 +20,8 @@ from conftest import ROOT
 from test_gpu_parity import _random_forest
 
 SWITCHES = ("KMDB_K1N_MODE", "KMDB_ROW_MODE", "KMDB_BLOCK_WIDTH", "KMDB_NSEG", "KMDB_DENSE", "KMDB_SLICES", "KMDB_L2_MIN", "KMDB_L2", "KMDB_POOL_PERCENT",
-            "KMDB_SHORT_IDS", "KMDB_RSH_UNROLL", "KMDB_REC_PACKED", "KMDB_K2_WINDOWS", "KMDB_N2A_NO_RUNS", "KMDB_N2A_NO_NODES", "KMDB_N2A_THREADS",
-            "KMDB_K1N_MINW", "KMDB_K2D_SLICES", "KMDB_K2D_EARLY", "KMDB_SYNC_DEBUG", "KMDB_K1N_DBG", "KMDB_SP_ALL_TILES")
+            "KMDB_SHORT_IDS", "KMDB_REC_PACKED", "KMDB_N2A_NO_RUNS", "KMDB_N2A_NO_NODES", "KMDB_N2A_THREADS",
+            "KMDB_K1N_MINW", "KMDB_K2D_SLICES", "KMDB_K2D_EARLY", "KMDB_SYNC_DEBUG", "KMDB_SP_ALL_TILES")
 
 
 @pytest.fixture(scope="module")
@@ -388,15 +388,14 @@ def test_decode_launches_either_side_of_the_short_list_boundary(K, dev, env, sho
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("unroll", [4, 8])
-def test_row_histogram_unrolls(K, O, dev, env, clade, unroll):
-    """rs_hist_kernel<4> and <8> (the default launches <16>) on the many-streams path: a random forest and a clade collection"""
+def test_row_histogram_on_random_and_clade_inputs(K, O, dev, env, clade):
+    """rs_hist_kernel<16> and the rest of the many-streams path in the default mode of the narrow kernel: a random forest and a clade collection"""
     seed, N, P, max_local, chain = RANDOM[1]
     pat, exp = _random_case(seed, N, P, max_local, chain)
     _, view = V.make_view(K, _S(), pat, N)
-    env(KMDB_RSH_UNROLL=unroll, KMDB_ROW_MODE=1)
-    _against_oracle(K, dev, view, exp, N, "unroll %d seed %d" % (unroll, seed), O)
-    _against_oracle(K, dev, _clade_view(K, clade), clade[3], clade[0], "unroll %d clades" % unroll, O)
+    env(KMDB_ROW_MODE=1)
+    _against_oracle(K, dev, view, exp, N, "row mode seed %d" % seed, O)
+    _against_oracle(K, dev, _clade_view(K, clade), clade[3], clade[0], "row mode clades", O)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
