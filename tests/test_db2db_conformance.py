@@ -17,7 +17,8 @@ for P; test_references_agree holds the two against each other on every case the 
 Out of reach, on purpose: counts of three and four digits through db2db need dbits <= 10 with counts >= 2^20, cells of 8 GB and more;
 the shifts of wide_weight for j >= 2 are shared with all2all, where test_few_streams_record_forms goes up to four digits, and db2db's
 own code is the generic j loop that two digits exercise.  The refusals "more than 2^22 block pairs" and "do not fit the LDS" come after
-dense allocations of tens of GB; the scalar branch of kmdb_probe needs tables of a capacity below 4, which no .db file holds."""
+dense allocations of tens of GB; the scalar branch of kmdb_probe needs tables of a capacity below 4 or at an odd offset, which the
+fabricated tables of test_new2all_conformance.py hold (test_probe_tables_through_db2db runs them through this path)."""
 import os
 import re
 
