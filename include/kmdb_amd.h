@@ -45,6 +45,10 @@ extern "C" {
 /* And the distance mode on the device: the table of common k-mer counts parsed, measured and formatted in HBM (kmdb_distance_*), and the one
  * definition of a measure's text (kmdbh_format_measure): six more entry points and three structs of their own, the version stays 8. */
 #define KMDB_HAS_DISTANCE 1
+/* And a second source of cells for the distance handle: a lower triangle of counts that is in HBM already — the one kmdb_all2all_dense_device
+ * computes, or one the caller accumulated — measured and formatted without ever being text (kmdb_distance_take_all2all,
+ * kmdb_distance_take_cells_device, kmdb_distance_matrix_rows, kmdb_distance_cells_device): four more entry points, no struct changed, the version stays 8. */
+#define KMDB_HAS_DISTANCE_MATRIX 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -774,6 +778,34 @@ int  kmdb_distance_begin(const kmdb_distance_opts* opts, kmdb_distance** out);
  * Declined (KMDB_DISTANCE_DECLINED): a line without a comma; a field of more than 10 digits or with a byte that is neither a digit nor a
  * separator; "a:b:c"; a pair without SPARSE_IN or a plain cell with it (so: rows that mix the two); PHYLIP with SPARSE_IN; 2^32 - 64 bytes or more. */
 int  kmdb_distance_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t first_row, kmdb_distance_out* out);
+/* The same table from a matrix in HBM (KMDB_HAS_DISTANCE_MATRIX): `all2all` followed by `distance` without the table of counts in between.
+ * The handle is begun with the samples' k-mer counts as `counts` (n = N: they are the rows' counts and the columns'), with
+ * KMDB_DISTANCE_TRIANGLE and without KMDB_DISTANCE_SPARSE_IN — any other handle is refused by the three calls below.  What
+ * kmdb_distance_matrix_rows returns for rows [row_lo, row_hi) is byte for byte what kmdb_distance_rows returns for those rows of the DENSE
+ * table of counts of the matrix ("<name>,<count>,<cell>,...,\n", row i with its i cells): "<name>," and i values; with SPARSE_OUT
+ * "<column + 1>:<value>," of the non-zero cells that pass the bounds (a = the row sample's count, b = the column's); with PHYLIP blanks and
+ * no bounds.  The cells the device cannot settle go to the host as they do there (kmdb_distance_stats.host_cells).
+ *
+ * take_all2all: runs kmdb_all2all_dense_device of `db` (opts as there, NULL: the whole database; a null opts->stream means the handle's)
+ *   into a triangle of N (N - 1) / 2 uint32 the HANDLE allocates and owns, freed with the handle or at the next take.  Refused: a database
+ *   on another device than the handle's, or of another N than the handle's n.
+ * take_cells_device: borrows cells the CALLER accumulated (a sum over shards, a tensor).  cells_dev points at the FIRST CELL OF ROW row_lo,
+ *   cell row_lo (row_lo - 1) / 2 of the triangle, and holds every cell from there to the end of the triangle or of the last row asked for:
+ *   a few late rows of a large matrix can be handed over without the rows in front of them (the cell_lo convention of
+ *   kmdb_sparse_from_dense_device, whose stream note applies: the cells must be complete on the handle's stream).  A null pointer is taken
+ *   when the rows asked for later hold no cells (row 0; N = 1).  Refused: row_lo > n.
+ * Both copy `names` (n C strings) to the device once, as a blob and its offsets.
+ * matrix_rows: out as with kmdb_distance_rows (kmdb_distance_out_free); row_lo == row_hi gives empty text and 0 rows.  Refused: no matrix
+ *   taken; row_lo > row_hi; row_hi > n; rows in front of a borrowed pointer's row_lo; cells and a null pointer; a piece of 2^31 cells or
+ *   more, or one whose working arrays (17 B a cell) do not fit the device's free memory — the message gives the bytes; ask for fewer rows.
+ * kmdb_distance_stats counts these calls in its fields: cells_read = the cells of the rows, bytes_in = four times that, parse_ms stays 0. */
+int  kmdb_distance_take_all2all(kmdb_distance* d, kmdb_db* db, const char* const* names, const kmdb_opts* opts);
+int  kmdb_distance_take_cells_device(kmdb_distance* d, const void* cells_dev, uint64_t row_lo, const char* const* names);
+int  kmdb_distance_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out);
+/* The cells the handle reads: the first cell of the row it was taken from (row 0 after take_all2all); null before a take.  A second handle of
+ * the same n — another measure, other bounds — borrows them with kmdb_distance_take_cells_device while the first one lives: one all2all
+ * run serves several tables. */
+const void* kmdb_distance_cells_device(const kmdb_distance* d);
 void kmdb_distance_out_free(kmdb_distance_out* out);
 void kmdb_distance_free(kmdb_distance* d);
 int  kmdb_distance_stats_get(const kmdb_distance* d, kmdb_distance_stats* out);

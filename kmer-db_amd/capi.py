@@ -150,6 +150,7 @@ EXPORTS = [
     "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
     "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
     "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
+    "kmdb_distance_take_all2all", "kmdb_distance_take_cells_device", "kmdb_distance_matrix_rows", "kmdb_distance_cells_device",
 ]
 
 
@@ -286,6 +287,11 @@ def lib():
     L.kmdbh_db_store.argtypes = [C.c_void_p, C.c_char_p]
     L.kmdb_distance_begin.argtypes = [C.POINTER(_DistanceOpts), C.POINTER(C.c_void_p)]
     L.kmdb_distance_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_take_all2all.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(_Opts)]
+    L.kmdb_distance_take_cells_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)]
+    L.kmdb_distance_matrix_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_cells_device.restype = C.c_void_p
+    L.kmdb_distance_cells_device.argtypes = [C.c_void_p]
     L.kmdb_distance_out_free.restype = None
     L.kmdb_distance_out_free.argtypes = [C.POINTER(_DistanceOut)]
     L.kmdb_distance_free.restype = None
@@ -1134,6 +1140,33 @@ class Distance:
         _check(rc)
         try:
             return C.string_at(out.text, out.len), 0
+        finally:
+            lib().kmdb_distance_out_free(C.byref(out))
+
+    @staticmethod
+    def _names(names):
+        names = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+        return (C.c_char_p * max(1, len(names)))(*names)
+
+    def take_all2all(self, db, names):
+        """kmdb_distance_take_all2all: the all2all triangle of a DeviceDB, computed into memory the handle owns, becomes the source of cells"""
+        _check(lib().kmdb_distance_take_all2all(self._d, db._d, self._names(names), None))
+
+    def take_cells(self, dev_ptr, row_lo, names):
+        """kmdb_distance_take_cells_device: dev_ptr (e.g. a torch tensor's .data_ptr(), or None) = the first cell of row row_lo of a lower triangle
+        of uint32 the caller keeps alive"""
+        _check(lib().kmdb_distance_take_cells_device(self._d, C.c_void_p(dev_ptr), int(row_lo), self._names(names)))
+
+    def cells_ptr(self):
+        """kmdb_distance_cells_device: the device address of the cells taken (None before a take), for a second handle's take_cells"""
+        return lib().kmdb_distance_cells_device(self._d)
+
+    def matrix_rows(self, lo, hi):
+        """kmdb_distance_matrix_rows: the text of rows [lo, hi) of the measure's table of the matrix taken"""
+        out = _DistanceOut()
+        _check(lib().kmdb_distance_matrix_rows(self._d, int(lo), int(hi), C.byref(out)))
+        try:
+            return C.string_at(out.text, out.len)
         finally:
             lib().kmdb_distance_out_free(C.byref(out))
 

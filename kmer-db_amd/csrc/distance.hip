@@ -9,10 +9,15 @@
 //             (dev_code) takes no bytes and is listed for the host.
 //   format    one scan of the lengths, the output allocated to its size, a lane per cell writes its digits, a wave per row its name.
 //
+// The cells have two sources behind the same measure and format stages: the tokens parsed from text (TextCells), and a lower triangle of
+// counts that is in HBM already (TriangleCells: kmdb_distance_take_* and kmdb_distance_matrix_rows) — output cell ci of a piece of rows IS
+// matrix cell piece_lo + ci, consecutive lanes read consecutive uint32, nothing is classified or parsed and the names come from a blob.
+//
 // Every position is below the piece's length by construction and clamped to it again where it is used: damaged text is declined
 // (KMDB_DISTANCE_DECLINED) or parsed as the host loop parses it, and never read or written outside the buffers.
 #include "kmdb_amd.h"
 #include "dev_mem.h"
+#include "engine_state.h"
 #include "prim.h"
 
 #include <algorithm>
@@ -72,6 +77,12 @@ struct DistParams {
     uint64_t* off;              // [n_cells + 1] scanned lengths
     unsigned int* decline;
     unsigned long long* counters;   // [0] cells read [1] cells the device wrote [2] cells for the host [3] entries appended
+    // the triangle as the source of cells (TriangleCells): row i of the matrix at i (i - 1) / 2, the piece's rows first_row .. first_row + R
+    const uint32_t* tri;            // matrix cell tri_lo and what follows it
+    uint64_t tri_lo, tri_cells;     // the first matrix cell behind tri, and how many there are
+    uint64_t piece_lo;              // the matrix cell of the piece's output cell 0: first_row (first_row - 1) / 2
+    const unsigned char* names;     // the samples' names back to back
+    const uint64_t* name_off;       // [n + 1] where a sample's name begins
 };
 
 // a cell the host decides: where its text goes, and what it is
@@ -269,7 +280,18 @@ __device__ __forceinline__ uint32_t dev_row_of(const uint64_t* base, uint32_t R,
     return lo;
 }
 
-__device__ Cell dev_cell(const DistParams& p, uint64_t ci) {
+// ---- the sources of cells: what output cell ci is, and where the name of row r lies -------------------------------------------------------
+struct TextCells {
+    static __device__ Cell at(const DistParams& p, uint64_t ci);
+    static __device__ __forceinline__ const unsigned char* name(const DistParams& p, uint32_t r, uint32_t* nlen) {
+        const uint32_t start = r ? min(p.row_end[r - 1] + 1, p.L) : 0;
+        const uint32_t fc = min(p.fc[r], p.L);
+        *nlen = fc >= start ? fc - start : 0;
+        return p.text + start;
+    }
+};
+
+__device__ Cell TextCells::at(const DistParams& p, uint64_t ci) {
     Cell x{};
     const uint32_t r = dev_row_of(p.oc, p.R, ci);
     const uint64_t c = ci - p.oc[r];
@@ -302,11 +324,53 @@ __device__ Cell dev_cell(const DistParams& p, uint64_t ci) {
     return x;
 }
 
+// the row i of the triangle that holds matrix cell g: i (i - 1) / 2 <= g < i (i + 1) / 2 (i >= 1; 64 bits: i (i - 1) passes 2^32 from row 65 537 on)
+__device__ __forceinline__ uint64_t dev_tri_row(uint64_t g) {
+    uint64_t i = (uint64_t)((1.0 + sqrt(1.0 + 8.0 * (double)g)) * 0.5);
+    if (i < 1) i = 1;
+    while (i > 1 && i * (i - 1) / 2 > g) --i;                   // (the square root of a number of 2^40 and more is a unit or so off)
+    while (i * (i + 1) / 2 <= g) ++i;
+    return i;
+}
+
+struct TriangleCells {
+    // every cell of the piece is a cell of the matrix: the count is read where it lies, the row's own count is a = counts[row]
+    static __device__ Cell at(const DistParams& p, uint64_t ci) {
+        Cell x{};
+        const uint64_t g = p.piece_lo + ci;
+        uint64_t i = dev_tri_row(g);
+        i = min(max(i, p.first_row), p.first_row + p.R - 1);    // clamped to the piece
+        const uint64_t c = min(g - min(g, i * (i - 1) / 2), (uint64_t)p.n - 1);
+        x.row = (uint32_t)(i - p.first_row);
+        x.col = (uint32_t)c;
+        x.a = p.counts[min(i, (uint64_t)p.n - 1)];
+        x.count = p.tri[min(g - p.tri_lo, p.tri_cells - 1)];
+        x.emit = p.mode != MODE_SPARSE_OUT || x.count > 0;
+        x.prefix = p.mode == MODE_SPARSE_OUT ? (uint32_t)c + 1 : 0;
+        return x;
+    }
+    static __device__ __forceinline__ const unsigned char* name(const DistParams& p, uint32_t r, uint32_t* nlen) {
+        const uint64_t s = min(p.first_row + r, (uint64_t)p.n - 1);
+        *nlen = (uint32_t)(p.name_off[s + 1] - p.name_off[s]);
+        return p.names + p.name_off[s];
+    }
+};
+
+// a lane per row of a piece of the triangle: its output cells, and the bytes of its name, the separator behind it and the '\n'
+__global__ void __launch_bounds__(DT) dist_tri_row_sizes_kernel(DistParams p) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r >= p.R) return;
+    const uint64_t s = min(p.first_row + r, (uint64_t)p.n - 1);
+    p.oc[r] = min(p.first_row + r, (uint64_t)p.n);
+    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
+}
+
+template <class Source>
 __global__ void __launch_bounds__(DT) dist_measure_kernel(DistParams p) {
     const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
     bool wrote = false, host = false;
     if (ci < p.n_cells) {
-        const Cell x = dev_cell(p, ci);
+        const Cell x = Source::at(p, ci);
         uint64_t code = C_SKIP;
         uint32_t len = 0;
         if (x.emit) {
@@ -346,12 +410,13 @@ __device__ __forceinline__ unsigned char* dev_put_uint(unsigned char* o, uint64_
 // where the cells of row r begin in the output: its name and the separator behind it in front of them
 __device__ __forceinline__ uint64_t dev_cells_at(const DistParams& p, uint32_t r) { return p.rowfix[r] + (p.rowfix[r + 1] - p.rowfix[r] - 1); }
 
+template <class Source>
 __global__ void __launch_bounds__(DT) dist_write_kernel(DistParams p, unsigned char* out, uint64_t out_bytes, HostCell* host, uint64_t host_cap) {
     const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
     if (ci >= p.n_cells) return;
     const uint64_t code = p.code[ci];
     if (code == C_SKIP) return;
-    const Cell x = dev_cell(p, ci);
+    const Cell x = Source::at(p, ci);
     const uint64_t at = dev_cells_at(p, x.row) + p.off[ci];
     if (code == C_HOST) {
         const unsigned long long e = atomicAdd(&p.counters[3], 1ull);
@@ -376,17 +441,17 @@ __global__ void __launch_bounds__(DT) dist_write_kernel(DistParams p, unsigned c
 }
 
 // a wave per row: the name, the separator behind it, the '\n' behind the row's cells
+template <class Source>
 __global__ void __launch_bounds__(DT) dist_names_kernel(DistParams p, unsigned char* out, uint64_t out_bytes) {
     const uint64_t r = ((uint64_t)blockIdx.x * DT + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63;
     if (r >= p.R) return;
-    const uint32_t start = r ? min(p.row_end[r - 1] + 1, p.L) : 0;
-    const uint32_t fc = min(p.fc[r], p.L);
-    const uint32_t nlen = fc >= start ? fc - start : 0;
+    uint32_t nlen = 0;
+    const unsigned char* name = Source::name(p, (uint32_t)r, &nlen);
     const uint64_t at = p.rowfix[r] + p.off[p.oc[r]];           // the row's first byte: the fixed bytes and the cells of the rows before
     const uint64_t nl = p.rowfix[r + 1] - 1 + p.off[p.oc[r + 1]];
     if (at + nlen + 1 > out_bytes || nl >= out_bytes) return;
-    for (uint32_t q = lane; q < nlen; q += 64) out[at + q] = p.text[start + q];
+    for (uint32_t q = lane; q < nlen; q += 64) out[at + q] = name[q];
     if (lane == 0) { out[at + nlen] = p.mode == MODE_PHYLIP ? ' ' : ','; out[nl] = '\n'; }
 }
 
@@ -420,8 +485,104 @@ struct kmdb_distance {
     std::vector<uint32_t> counts;
     std::vector<kmdb_cell_filter> filters;
     DevBuf<uint32_t> d_counts;
+    // the triangle taken as the source of cells (kmdb_distance_take_*): the handle's own (take_all2all) or the caller's (take_cells_device)
+    bool taken = false;
+    DevBuf<uint32_t> own_tri;
+    const uint32_t* tri = nullptr;      // the first cell of row tri_row_lo; may be null when no row asked for holds a cell
+    uint64_t tri_row_lo = 0;
+    DevBuf<unsigned char> d_names;
+    DevBuf<uint64_t> d_name_off;
     kmdb_distance_stats st{};
 };
+
+static int dist_splice(kmdb_distance* d, std::vector<HostCell>& cells, const char* dev_text, size_t dev_len, kmdb_distance_out* out, uint64_t* written);
+
+namespace {
+
+// exclusive sum with the library's temporary storage
+template <class In, class Out>
+int dist_scan(In* in, Out* outp, size_t n, DevBuf<void>& d_tmp, uint64_t& held, hipStream_t st) {
+    size_t tb = 0;
+    HIP_TRY(prim::exclusive_sum(nullptr, tb, in, outp, n, st));
+    if (tb > d_tmp.bytes()) { held += tb; DEV_ALLOC_BYTES(d_tmp, tb); }
+    HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb, in, outp, n, st));
+    return 0;
+}
+
+struct DistTail {
+    unsigned long long counters[4];
+    uint64_t written, n_host;
+    float measure_ms, format_ms, copy_ms;
+};
+
+// The measure and format stages of a piece whose rows and cells are laid out (p.R, p.oc and p.rowfix scanned, p.n_cells, fix_bytes): whatever
+// the source of the cells.  `begun` was recorded on the stream where the stages begin.  out->text and out->len are set.
+template <class Source>
+int dist_measure_format(kmdb_distance* d, const char* who, DistParams& p, uint64_t fix_bytes, DevBuf<void>& d_tmp, uint64_t& held, hipEvent_t begun,
+                        kmdb_distance_out* out, DistTail* tail) {
+    hipStream_t st = d->stream;
+    const uint32_t R = p.R;
+    const uint64_t n_cells = p.n_cells;
+    DevEvent ev[3];
+    for (auto& e : ev) if (e.create()) return 1;
+    DevBuf<uint8_t> d_len;
+    DevBuf<uint64_t> d_code, d_off;
+    DevBuf<unsigned char> d_out;
+    DevBuf<HostCell> d_host;
+
+    // measure
+    DEV_ALLOC(d_code, (size_t)n_cells); DEV_ALLOC(d_len, (size_t)n_cells + 1); DEV_ALLOC(d_off, (size_t)n_cells + 1);
+    held += n_cells * 17;
+    p.code = d_code; p.len = d_len; p.off = d_off;
+    if (n_cells) {
+        hipLaunchKernelGGL(dist_measure_kernel<Source>, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(d_len.get() + n_cells, 0, 1, st));
+    if (dist_scan(d_len.get(), d_off.get(), (size_t)n_cells + 1, d_tmp, held, st)) return 1;
+    uint64_t cell_bytes = 0;
+    unsigned long long* counters = tail->counters;
+    HIP_TRY(hipMemcpyAsync(&cell_bytes, d_off.get() + n_cells, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counters, p.counters, 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (cell_bytes > n_cells * 64 || counters[2] > n_cells) return kmdb_set_error(std::string(who) + "internal error (the cells' text is longer than they can write)");
+
+    // format
+    const uint64_t out_bytes = fix_bytes + cell_bytes, n_host = counters[2];
+    DEV_ALLOC(d_out, (size_t)out_bytes); DEV_ALLOC(d_host, (size_t)n_host);
+    held += out_bytes + n_host * sizeof(HostCell);
+    if (n_cells) hipLaunchKernelGGL(dist_write_kernel<Source>, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p, d_out.get(), out_bytes, d_host.get(), n_host);
+    hipLaunchKernelGGL(dist_names_kernel<Source>, dim3(blocks_for((uint64_t)R * 64)), dim3(DT), 0, st, p, d_out.get(), out_bytes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], st));
+    char* text = (char*)malloc(std::max<uint64_t>(1, out_bytes));
+    if (!text) return kmdb_set_error(std::string(who) + "out of host memory");
+    std::vector<HostCell> cells;
+    int rc = [&]() -> int {
+        try { cells.resize(n_host); } catch (const std::exception&) { return kmdb_set_error(std::string(who) + "out of host memory"); }
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(text, d_out.get(), out_bytes, hipMemcpyDeviceToHost, st));
+        if (n_host) HIP_TRY(hipMemcpyAsync(cells.data(), d_host.get(), n_host * sizeof(HostCell), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    }();
+    tail->written = counters[1];
+    tail->n_host = n_host;
+    if (!rc) {
+        if (n_host) {
+            rc = dist_splice(d, cells, text, out_bytes, out, &tail->written);
+            free(text);
+        } else { out->text = text; out->len = out_bytes; }
+    } else free(text);
+    if (rc) return rc;
+    HIP_TRY(hipEventElapsedTime(&tail->measure_ms, begun, ev[0]));
+    HIP_TRY(hipEventElapsedTime(&tail->format_ms, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&tail->copy_ms, ev[1], ev[2]));
+    return 0;
+}
+
+}  // namespace
 
 extern "C" int kmdb_distance_begin(const kmdb_distance_opts* opts, kmdb_distance** out) {
     const char* who = "kmdb_distance_begin: ";
@@ -522,24 +683,16 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     const uint32_t L = (uint32_t)len;
     const uint64_t NW = ((uint64_t)L + 63) / 64;
     uint64_t held = 0;
-    DevEvent ev[6];
+    DevEvent ev[3];
     for (auto& e : ev) if (e.create()) return 1;
     DevBuf<unsigned char> d_text;
     DevBuf<uint32_t> d_wcnt, d_weol, d_wsep, d_fc, d_row_end, d_row_first, d_sep_pos, d_sep_row, d_tok_val;
-    DevBuf<uint8_t> d_tok_flags, d_len;
-    DevBuf<uint64_t> d_oc, d_rowfix, d_code, d_off;
+    DevBuf<uint8_t> d_tok_flags;
+    DevBuf<uint64_t> d_oc, d_rowfix;
     DevBuf<unsigned int> d_decline;
     DevBuf<unsigned long long> d_counters;
     DevBuf<void> d_tmp;
-    DevBuf<unsigned char> d_out;
-    DevBuf<HostCell> d_host;
-    auto scan = [&](auto* in, auto* outp, size_t n) -> int {      // exclusive sum with the library's temporary storage
-        size_t tb = 0;
-        HIP_TRY(prim::exclusive_sum(nullptr, tb, in, outp, n, st));
-        if (tb > d_tmp.bytes()) { held += tb; DEV_ALLOC_BYTES(d_tmp, tb); }
-        HIP_TRY(prim::exclusive_sum(d_tmp.get(), tb, in, outp, n, st));
-        return 0;
-    };
+    auto scan = [&](auto* in, auto* outp, size_t n) -> int { return dist_scan(in, outp, n, d_tmp, held, st); };
 
     HIP_TRY(hipEventRecord(ev[0], st));
     DEV_ALLOC(d_text, (size_t)L); DEV_ALLOC(d_wcnt, NW + 1); DEV_ALLOC(d_weol, NW + 1); DEV_ALLOC(d_wsep, NW + 1); DEV_ALLOC(d_decline, 1); DEV_ALLOC(d_counters, 4);
@@ -611,58 +764,16 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     if (why) return declined(why);
     if (fix_bytes > (uint64_t)L + 2ull * R) return kmdb_set_error(std::string(who) + "internal error (names longer than the text)");
 
-    // measure
+    // measure and format
     p.n_cells = n_cells;
-    DEV_ALLOC(d_code, (size_t)n_cells); DEV_ALLOC(d_len, (size_t)n_cells + 1); DEV_ALLOC(d_off, (size_t)n_cells + 1);
-    held += n_cells * 17;
-    p.code = d_code; p.len = d_len; p.off = d_off;
-    if (n_cells) {
-        hipLaunchKernelGGL(dist_measure_kernel, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync(d_len.get() + n_cells, 0, 1, st));
-    if (scan(d_len.get(), d_off.get(), (size_t)n_cells + 1)) return 1;
-    uint64_t cell_bytes = 0;
-    unsigned long long counters[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(&cell_bytes, d_off.get() + n_cells, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(counters, d_counters.get(), 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ev[3], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (cell_bytes > n_cells * 64 || counters[2] > n_cells) return kmdb_set_error(std::string(who) + "internal error (the cells' text is longer than they can write)");
-
-    // format
-    const uint64_t out_bytes = fix_bytes + cell_bytes, n_host = counters[2];
-    DEV_ALLOC(d_out, (size_t)out_bytes); DEV_ALLOC(d_host, (size_t)n_host);
-    held += out_bytes + n_host * sizeof(HostCell);
-    if (n_cells) hipLaunchKernelGGL(dist_write_kernel, dim3(blocks_for(n_cells)), dim3(DT), 0, st, p, d_out.get(), out_bytes, d_host.get(), n_host);
-    hipLaunchKernelGGL(dist_names_kernel, dim3(blocks_for((uint64_t)R * 64)), dim3(DT), 0, st, p, d_out.get(), out_bytes);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[4], st));
-    char* text = (char*)malloc(std::max<uint64_t>(1, out_bytes));
-    if (!text) return kmdb_set_error(std::string(who) + "out of host memory");
-    std::vector<HostCell> cells;
-    int rc = [&]() -> int {
-        try { cells.resize(n_host); } catch (const std::exception&) { return kmdb_set_error(std::string(who) + "out of host memory"); }
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(text, d_out.get(), out_bytes, hipMemcpyDeviceToHost, st));
-        if (n_host) HIP_TRY(hipMemcpyAsync(cells.data(), d_host.get(), n_host * sizeof(HostCell), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(ev[5], st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return 0;
-    }();
-    uint64_t written = counters[1];
-    if (!rc) {
-        if (n_host) {
-            rc = dist_splice(d, cells, text, out_bytes, out, &written);
-            free(text);
-        } else { out->text = text; out->len = out_bytes; }
-    } else free(text);
-    if (rc) return rc;
+    DistTail t{};
+    if (dist_measure_format<TextCells>(d, who, p, fix_bytes, d_tmp, held, ev[2], out, &t)) return 1;
     out->rows = R;
-    float ms[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-    d->st.rows += R; d->st.cells_read += counters[0]; d->st.cells_written += written; d->st.host_cells += n_host;
+    float ms[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    d->st.rows += R; d->st.cells_read += t.counters[0]; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
     d->st.bytes_in += len; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
-    d->st.copy_ms += ms[0] + ms[4]; d->st.parse_ms += ms[1]; d->st.measure_ms += ms[2]; d->st.format_ms += ms[3];
+    d->st.copy_ms += ms[0] + t.copy_ms; d->st.parse_ms += ms[1]; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
     return 0;
 }
 
@@ -674,6 +785,151 @@ extern "C" int kmdb_distance_rows(kmdb_distance* d, const char* lines, size_t le
         rc = dist_rows(d, lines, len, first_row, out);
     } catch (const std::exception& e) {
         rc = kmdb_set_error(std::string("kmdb_distance_rows: ") + e.what());
+    }
+    if (rc) kmdb_distance_out_free(out);
+    return rc;
+}
+
+// ---- the triangle as the source of cells -------------------------------------------------------------------------------------------------
+static inline uint64_t tri_cells_before(uint64_t row) { return row ? row * (row - 1) / 2 : 0; }
+
+static int dist_take_check(const kmdb_distance* d, const std::string& who) {
+    if (!(d->flags & KMDB_DISTANCE_TRIANGLE)) return kmdb_set_error(who + "the handle was not begun with KMDB_DISTANCE_TRIANGLE: a matrix is a lower triangle");
+    if (d->flags & KMDB_DISTANCE_SPARSE_IN) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_SPARSE_IN: a matrix holds no column:count pairs");
+    return 0;
+}
+
+// the names to the device once: a blob and the offsets of its n + 1 ends
+static int dist_take_names(kmdb_distance* d, const char* const* names, const std::string& who) {
+    const size_t n = d->counts.size();
+    std::vector<uint64_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (!names[i]) return kmdb_set_error(who + "null name");
+        off[i + 1] = off[i] + std::strlen(names[i]);
+    }
+    std::string blob;
+    blob.reserve((size_t)off[n]);
+    for (size_t i = 0; i < n; ++i) blob.append(names[i]);
+    HIP_TRY(hipSetDevice(d->device));
+    DEV_ALLOC(d->d_names, blob.size()); DEV_ALLOC(d->d_name_off, n + 1);
+    if (!blob.empty()) HIP_TRY(hipMemcpy(d->d_names.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->d_name_off.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int kmdb_distance_take_all2all(kmdb_distance* d, kmdb_db* db, const char* const* names, const kmdb_opts* opts) {
+    const std::string who = "kmdb_distance_take_all2all: ";
+    if (!d || !db || (!names && !d->counts.empty())) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_take_check(d, who)) return 1;
+        if (db->device != d->device) return kmdb_set_error(who + "the database lives on device " + std::to_string(db->device) + ", the handle on device " + std::to_string(d->device));
+        if (db->N != d->counts.size()) return kmdb_set_error(who + "the database holds " + std::to_string(db->N) + " samples, the handle was begun with " + std::to_string(d->counts.size()));
+        d->taken = false; d->tri = nullptr; d->tri_row_lo = 0;
+        d->own_tri.reset();                                     // the triangle of the take before goes first
+        if (dist_take_names(d, names, who)) return 1;
+        DEV_ALLOC(d->own_tri, (size_t)std::max<uint64_t>(1, tri_cells_before(db->N)));
+        kmdb_opts o{};
+        if (opts) o = *opts;
+        else { o.abi_version = KMDB_ABI_VERSION; o.shard_count = 1; }
+        o.device = d->device;
+        if (!o.stream) o.stream = d->stream;                    // (null still: the database's own stream, complete when the call returns)
+        if (kmdb_all2all_dense_device(db, d->own_tri.get(), &o)) return 1;
+        if (o.stream != (void*)d->stream) HIP_TRY(hipStreamSynchronize((hipStream_t)o.stream));
+        d->tri = d->own_tri.get(); d->taken = true;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_take_cells_device(kmdb_distance* d, const void* cells_dev, uint64_t row_lo, const char* const* names) {
+    const std::string who = "kmdb_distance_take_cells_device: ";
+    if (!d || (!names && !d->counts.empty())) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_take_check(d, who)) return 1;
+        if (row_lo > d->counts.size()) return kmdb_set_error(who + "row_lo " + std::to_string(row_lo) + " lies behind the " + std::to_string(d->counts.size()) + " rows");
+        d->taken = false; d->tri = nullptr; d->tri_row_lo = 0;
+        d->own_tri.reset();
+        if (dist_take_names(d, names, who)) return 1;
+        d->tri = (const uint32_t*)cells_dev; d->tri_row_lo = row_lo; d->taken = true;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" const void* kmdb_distance_cells_device(const kmdb_distance* d) { return d && d->taken ? d->tri : nullptr; }
+
+static int dist_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    const char* who = "kmdb_distance_matrix_rows: ";
+    const uint64_t n = d->counts.size();
+    if (dist_take_check(d, who)) return 1;
+    if (!d->taken) return kmdb_set_error(std::string(who) + "no matrix was taken (kmdb_distance_take_all2all, kmdb_distance_take_cells_device)");
+    if (row_lo > row_hi) return kmdb_set_error(std::string(who) + "row_lo > row_hi");
+    if (row_hi > n) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(n) + " rows");
+    if (row_lo < row_hi && row_lo < d->tri_row_lo) return kmdb_set_error(std::string(who) + "row " + std::to_string(row_lo) + " lies in front of the cells taken (from row " + std::to_string(d->tri_row_lo) + " on)");
+    d->st.calls += 1;
+    if (row_lo == row_hi) {
+        out->text = (char*)malloc(1);
+        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
+        return 0;
+    }
+    const uint32_t R = (uint32_t)(row_hi - row_lo);
+    const uint64_t n_cells = tri_cells_before(row_hi) - tri_cells_before(row_lo);
+    if (n_cells && !d->tri) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " cells and a null pointer was taken");
+    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
+    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
+    size_t mem_free = 0, mem_total = 0;
+    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
+                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
+    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
+    DevEvent begun;
+    if (begun.create()) return 1;
+    DevBuf<uint64_t> d_oc, d_rowfix;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<void> d_tmp;
+    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
+    HIP_TRY(hipEventRecord(begun, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
+    DistParams p{};
+    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 1; p.first_row = row_lo;
+    p.n_filters = (int)d->filters.size();
+    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
+    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
+    p.tri = d->tri; p.tri_lo = tri_cells_before(d->tri_row_lo); p.tri_cells = tri_cells_before(n) - p.tri_lo; p.piece_lo = tri_cells_before(row_lo);
+    p.names = d->d_names; p.name_off = d->d_name_off; p.n_cells = n_cells;
+    hipLaunchKernelGGL(dist_tri_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
+    if (dist_scan(d_oc.get(), d_oc.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
+    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
+    uint64_t oc_all = 0, fix_bytes = 0;
+    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
+    DistTail t{};
+    if (dist_measure_format<TriangleCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
+    out->rows = R;
+    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
+    d->st.bytes_in += n_cells * 4; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
+    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+    return 0;
+}
+
+extern "C" int kmdb_distance_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    if (!d || !out) return kmdb_set_error("kmdb_distance_matrix_rows: null argument");
+    out->text = nullptr; out->len = 0; out->rows = 0;
+    int rc;
+    try {
+        rc = dist_matrix_rows(d, row_lo, row_hi, out);
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string("kmdb_distance_matrix_rows: ") + e.what());
     }
     if (rc) kmdb_distance_out_free(out);
     return rc;

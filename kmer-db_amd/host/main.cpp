@@ -3,6 +3,7 @@
 // Drop-in for the three kmer-db modes on the hot path:
 //     kmer-db-amd all2all    [-sparse [-min [m:]v] [-max [m:]v]] <db> <out.csv>
 //     kmer-db-amd all2all-sp [-min [m:]v] [-max [m:]v]           <db> <out.csv>
+//     kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <out>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
@@ -285,11 +286,21 @@ void write_header(const Db& db, std::ofstream& ofs) {
     ofs.write(buf.data(), (std::streamsize)len);
 }
 
+// all2all / all2all-sp -distance <measure> (below, with the distance mode): every "-distance <measure>" taken from the arguments
+std::vector<std::string> take_distance_measures(std::vector<std::string>& args) {
+    std::vector<std::string> measures;
+    for (std::string v; take_option(args, "-distance", v);) measures.push_back(v);
+    return measures;
+}
+int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures, bool sparse_forced, const char* mode);
+
 // ---- all2all (console_all2all.cpp:7-89) -----------------------------------------------------------
 int run_all2all(std::vector<std::string>& args, Common& c) {
     std::string v;
     take_option(args, "-buffer", v);
     take_option(args, "-bubble-size", v);
+    const std::vector<std::string> measures = take_distance_measures(args);
+    if (!measures.empty()) return run_all2all_distance(args, c, measures, false, "all2all");
     c.sparse = take_switch(args, "-sparse");
     if (c.sparse) c.filters.parse(args);
     if (args.size() != 2) throw usage_error("all2all");
@@ -385,6 +396,8 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     take_option(args, "-buffer", v);
     uint32_t bubble = 8000;
     if (take_option(args, "-bubble-size", v)) bubble = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+    const std::vector<std::string> measures = take_distance_measures(args);
+    if (!measures.empty()) return run_all2all_distance(args, c, measures, true, "all2all-sp");
     take_switch(args, "-sparse");
     c.filters.parse(args);
     c.sampler.parse(args);
@@ -1616,15 +1629,9 @@ bool distance_on_device(const std::string& path, long long body, std::ostream& o
 }
 
 
-int run_distance(std::vector<std::string>& args, const Common& c) {
-    const bool host_only = take_switch(args, "-host");
-    bool sparse_out = take_switch(args, "-sparse");
-    const bool phylip = take_switch(args, "-phylip-out");
-    if (phylip) sparse_out = false;
-    auto avail = metrics();
-    struct Bound { metric_fn fn; double lo = std::numeric_limits<double>::lowest(), hi = std::numeric_limits<double>::max(); };
-    std::map<std::string, Bound> bounds;
-    long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+// the -min / -max list as the distance mode reads it (params.cpp:603-668): a bare bound ("?") belongs to the chosen measure, num-kmers: is the count
+struct DistanceBound { metric_fn fn; double lo = std::numeric_limits<double>::lowest(), hi = std::numeric_limits<double>::max(); };
+void take_distance_bounds(std::vector<std::string>& args, std::map<std::string, metric_fn>& avail, std::map<std::string, DistanceBound>& bounds, long& kmer_lo, long& kmer_hi) {
     const char* names[2] = {"-min", "-max"};
     for (int which = 0; which < 2; ++which) {
         std::string v;
@@ -1640,6 +1647,151 @@ int run_distance(std::vector<std::string>& args, const Common& c) {
             else throw std::runtime_error("Filtering error - unknown metric: " + crit);
         }
     }
+}
+// the bounds of one run as the library takes them
+std::vector<kmdb_cell_filter> distance_filters(const std::map<std::string, DistanceBound>& bounds, long kmer_lo, long kmer_hi) {
+    std::vector<kmdb_cell_filter> fl;
+    for (auto& kv : bounds) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+    if (kmer_lo != 0 || kmer_hi != (long)std::numeric_limits<uint32_t>::max())
+        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)kmer_lo, (double)kmer_hi});
+    return fl;
+}
+
+// ---- all2all -distance <measure>: the measure's table straight from the matrix in HBM ---------------------------------------------------------
+// `all2all D T` followed by `distance O <measure> T out`, byte for byte, without T: the library computes the triangle into memory the first
+// measure's handle owns (kmdb_distance_take_all2all), every further measure borrows it, and the rows come back as text in pieces cut by a
+// budget of cells (KMDB_DISTANCE_CELLS_PER_PIECE, default 2^25: chosen for memory — 17 B of working arrays a cell and the text —, not tuned).
+// The writer thread writes piece n - 1 while piece n is on the device.  The header lines come from the host, as run_distance writes them
+// for a triangle table: no ",db-samples", no total-kmers line.  The -min / -max list is read by the DISTANCE mode's rule.
+int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures, bool sparse_forced, const char* mode) {
+    auto avail = metrics();
+    for (auto& m : measures)
+        if (!avail.count(m)) throw std::runtime_error("unknown measure: " + m);
+    if (c.gpus > 0) throw std::runtime_error(std::string("-distance does not go with -gpus <N>: the node's shards keep their triangle to themselves (run ") + mode + " and distance)");
+    for (auto& a : args)
+        if (a == "-sample-rows") throw std::runtime_error("-distance does not go with -sample-rows: sampled rows are no rows of the triangle");
+    bool sparse = take_switch(args, "-sparse") || sparse_forced;
+    const bool phylip = take_switch(args, "-phylip-out");
+    if (phylip) sparse = false;
+    std::map<std::string, DistanceBound> bounds;
+    long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+    take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
+    if (args.size() != 2) throw usage_error(mode);
+    uint64_t budget = 1ull << 25;
+    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+
+    std::cerr << "All versus all comparison, " << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
+    Db db;
+    std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
+    kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1; o.flags = KMDB_FLAG_ONE_SHOT;
+    {
+        const auto tl = clk::now();
+        std::thread warm([&]() { (void)kmdb_device_prepare(c.device); });      // the device's first use, next to the read of the file (an error shows at the upload)
+        const int load_rc = kmdbh_db_load(args[0].c_str(), 2, &db.h);
+        const std::string load_err = load_rc ? kmdb_last_error() : "";
+        warm.join();
+        if (load_rc) throw std::runtime_error(load_err);
+        const double load_s = since(tl);
+        const auto tu = clk::now();
+        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 0, &db.d));
+        std::cerr << "Database loaded in " << load_s << " s, uploaded in " << since(tu) << " s" << std::endl;
+    }
+    const uint64_t n = kmdbh_db_n_samples(db.h);
+    DistanceSetup s;
+    s.device = c.device; s.k = kmdbh_db_kmer_length(db.h); s.sparse_out = sparse; s.phylip = phylip;
+    s.counts.resize(n);
+    std::vector<const char*> names(std::max<uint64_t>(n, 1), "");
+    for (uint64_t i = 0; i < n; ++i) { s.counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i); names[i] = kmdbh_db_sample_name(db.h, i); }
+    const uint32_t flags = KMDB_DISTANCE_TRIANGLE | (sparse ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (phylip ? KMDB_DISTANCE_PHYLIP : 0u);
+
+    DistanceHandle owner;                                          // the first measure's handle holds the triangle for all of them
+    std::ofstream ofs;
+    std::string path;
+    for (size_t mi = 0; mi < measures.size(); ++mi) {
+        const std::string& measure = measures[mi];
+        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
+        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measure] = b; }
+        s.measure = kmdbh_metric_id(measure.c_str());
+        s.filters = distance_filters(own, kmer_lo, kmer_hi);
+        DistanceHandle borrower;
+        DistanceHandle& h = mi == 0 ? owner : borrower;
+        h.begin(s, flags);
+        if (mi == 0) {
+            std::cerr << "Calculating matrix of common k-mers..." << std::endl;
+            const auto t0 = clk::now();
+            check(kmdb_distance_take_all2all(h.d, db.d, names.data(), &o));
+            kmdb_stats st{};
+            if (!kmdb_db_stats(db.d, &st) && st.path == KMDB_PATH_GLOBAL)
+                std::cerr << "WARNING: the fast pipeline could not take this database (" << kmdb_db_fallback_reason(db.d) << "); the slow HBM-atomics kernel ran" << std::endl;
+            std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+            db.uploaded();
+        } else check(kmdb_distance_take_cells_device(h.d, kmdb_distance_cells_device(owner.d), 0, names.data()));
+
+        path = measures.size() == 1 ? args[1] : args[1] + "." + measure;
+        std::cerr << "Storing the " << measure << " table in " << path << "...";
+        const auto t0 = clk::now();
+        ofs.open(path, std::ios::binary);
+        if (!phylip) {
+            ofs << "kmer-length: " << s.k << " fraction: " << kmdbh_db_fraction(db.h) << " ,";
+            for (uint64_t i = 0; i < n; ++i) ofs << names[i] << ',';
+            ofs << std::endl;
+        } else ofs << n << std::endl;
+        struct Text { kmdb_distance_out o{}; };
+        Channel<Text> texts;
+        bool write_failed = false;
+        std::thread writer([&]() {
+            Text t;
+            while (texts.pop(t)) {
+                if (t.o.len) ofs.write(t.o.text, (std::streamsize)t.o.len);
+                kmdb_distance_out_free(&t.o);
+                if (!ofs) { write_failed = true; texts.close(); break; }
+            }
+        });
+        std::string error;
+        try {
+            for (uint64_t i0 = 0; i0 < n;) {
+                uint64_t i1 = i0, cells = 0;
+                while (i1 < n && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+                Text t;
+                check(kmdb_distance_matrix_rows(h.d, i0, i1, &t.o));
+                if (!texts.push(std::move(t))) { kmdb_distance_out_free(&t.o); break; }
+                i0 = i1;
+            }
+        } catch (std::exception& e) {
+            error = e.what();
+        }
+        if (error.empty()) texts.finish(); else texts.close();
+        writer.join();
+        texts.drain([](Text& t) { kmdb_distance_out_free(&t.o); });
+        if (!error.empty()) throw std::runtime_error(error);
+        if (write_failed) throw std::runtime_error("Cannot write the output file " + path);
+        std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+        if (std::getenv("KMDB_VERBOSE")) {
+            kmdb_distance_stats st{};
+            if (!kmdb_distance_stats_get(h.d, &st))
+                std::cerr << "[kmdb] distance from the matrix: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
+                          << ", host cells " << st.host_cells << ", bytes out " << st.bytes_out << ", measure " << st.measure_ms << " ms, format " << st.format_ms
+                          << " ms, copies " << st.copy_ms << " ms" << std::endl;
+        }
+        if (mi + 1 < measures.size()) {
+            ofs.close();
+            if (!ofs) throw std::runtime_error("Cannot write the output file " + path);
+        }
+    }
+    return finish(db, ofs, path);
+}
+
+int run_distance(std::vector<std::string>& args, const Common& c) {
+    const bool host_only = take_switch(args, "-host");
+    bool sparse_out = take_switch(args, "-sparse");
+    const bool phylip = take_switch(args, "-phylip-out");
+    if (phylip) sparse_out = false;
+    auto avail = metrics();
+    using Bound = DistanceBound;
+    std::map<std::string, Bound> bounds;
+    long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+    take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
     if (args.empty()) throw std::runtime_error("No distance/similarity metric specified");
     const std::string measure_name = args.front();
     args.erase(args.begin());
@@ -1699,9 +1851,7 @@ int run_distance(std::vector<std::string>& args, const Common& c) {
             s.device = c.device; s.measure = kmdbh_metric_id(measure_name.c_str()); s.k = k; s.counts = db_counts; s.sparse_out = sparse_out; s.phylip = phylip;
             s.has_names = !sample_names.empty();
             if (s.has_names) s.first_name = sample_names[0];
-            for (auto& kv : bounds) s.filters.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-            if (kmer_lo != 0 || kmer_hi != (long)std::numeric_limits<uint32_t>::max())
-                s.filters.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)kmer_lo, (double)kmer_hi});
+            s.filters = distance_filters(bounds, kmer_lo, kmer_hi);
             std::string why;
             out.flush();
             if (distance_on_device(args[0], body, out, s, why)) { out.flush(); return 0; }
@@ -1803,7 +1953,13 @@ void usage() {
                  "                   fraction and alphabet; <database> may be <old.db>); -extend and -from-kmers are refused\n"
                  "distance: KMDB_DISTANCE_DEVICE=1 parses, measures and formats the table on the GPU (-gpu <device>; same bytes); -host and\n"
                  "                   KMDB_DISTANCE_DEVICE=0 keep it on the host, which is also what runs when neither is given\n"
-                 "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n";
+                 "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n"
+                 "    kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* -distance <measure> [-distance <measure>]* <database> <output>\n"
+                 "all2all / all2all-sp -distance:  the table of <measure> straight from the matrix on the GPU: the file `all2all` followed by `distance`\n"
+                 "                                  writes, without the table of counts in between; all2all-sp forces -sparse.  Several -distance: one all2all\n"
+                 "                                  run, a file <output>.<measure> each.  -min / -max are read as the DISTANCE mode reads them here: a bare\n"
+                 "                                  bound belongs to <measure> (NOT to num-kmers as in all2all -sparse), num-kmers:<v> bounds the count.\n"
+                 "                                  Refused with -gpus <N> and with -sample-rows.\n";
 }
 
 }  // namespace
