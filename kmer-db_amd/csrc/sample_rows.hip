@@ -9,6 +9,11 @@
 // filters (1e-6 relative) plus the float rounding (2^-22): ties and the margin band come out, a row with fewer than `count` cells comes out whole.
 // The host decides (host_sampler.cpp) with the reference's double arithmetic.
 //
+// A cell whose proxy is infinite or NaN (a sample k-mer count of 0 beside a non-zero cell, a + b - c wrapping to 0) has no rank the device can
+// know: the host scores it +inf under jaccard / min / max / cosine and NaN — below every number — under the four log measures.  A row that
+// holds ANY such cell therefore comes out whole (a flag per sample, set in the first histogram pass and read at digit 0), so that the host
+// still sees a superset of the row's true best `count` whichever way it ranks the cell.
+//
 // Every pass reads the triangle in row order, one workgroup per tile of width x width cells: the tile's keys go to LDS once and every one of
 // its 2 x width samples — `width` row samples, `width` column samples — reads its own line of the tile from there (a wave per sample, the
 // column lines through a padded stride), so no pass walks a column of the triangle.  Passes: 4 histogram, 1 count, 1 emit = 6 reads of the
@@ -42,7 +47,7 @@ struct SrJob {
 };
 struct SrState { uint32_t prefix, k, done, total; };   // done: 1 the row comes out whole, 2 cut at T_s; total: cells of the row that pass the widened filters
 
-// order-preserving key of the proxy: 0 is kept for "no cell", SR_KEY_BEST for a NaN or infinite proxy (the host decides those)
+// order-preserving key of the proxy: 0 is kept for "no cell", SR_KEY_BEST for a NaN or infinite proxy (its whole row goes to the host)
 __device__ __forceinline__ uint32_t sr_key(const SrJob& q, uint32_t c, uint32_t row, uint32_t col) {
     double x = dev_ratio(q.kind, c, q.f.counts[row], q.f.counts[col]);
     if (q.flip) x = -x;
@@ -72,14 +77,15 @@ __host__ __device__ inline uint32_t sr_float_key(float f) {
 }
 
 // One workgroup (4 waves) per tile (X, Y), Y <= X, tile index X (X + 1) / 2 + Y as in kmdb_db.tile_touched.
-//   SR_HIST : digit `digit` (0 = top 8 bits) of the keys that share the sample's prefix goes to hist[s][256]
+//   SR_HIST : digit `digit` (0 = top 8 bits) of the keys that share the sample's prefix goes to hist[s][256]; at digit 0 a line that holds
+//             an SR_KEY_BEST key sets unrankable[s]
 //   SR_COUNT: len[s] += cells with key >= thr[s]            (thr 0: the sample is skipped)
 //   SR_EMIT : those cells appended at row_ptr[s] + cursor[s]++
 template <int MODE>
 __global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t digit, const SrState* __restrict__ state, uint32_t* __restrict__ hist,
                                                       const uint32_t* __restrict__ thr, unsigned long long* __restrict__ len,
                                                       const unsigned long long* __restrict__ row_ptr, uint32_t* __restrict__ cursor,
-                                                      uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
+                                                      uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval, uint32_t* __restrict__ unrankable) {
     __shared__ uint32_t s_key[SR_W][SR_W + 1];
     __shared__ uint32_t s_val[SR_W][SR_W + 1];
     const uint32_t t = blockIdx.x;
@@ -127,6 +133,7 @@ __global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t di
         if (MODE == SR_HIST) {
             const SrState st = state[s];
             if (st.done) continue;
+            if (digit == 0 && __ballot(key == SR_KEY_BEST) && lane == 0) unrankable[s] = 1u;
             bool on = key != 0 && (digit == 0 || (key >> (32 - 8 * digit)) == st.prefix);
             const uint32_t bin = (key >> (24 - 8 * digit)) & 255u;
             unsigned long long m = __ballot(on);
@@ -161,7 +168,8 @@ __global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t di
 
 // After histogram pass `digit`: the bin that holds the sample's k-th largest key extends its prefix; the histogram is zeroed for the next pass.
 // After the last digit the prefix IS the key of T_s, and thr[s] the key of T_s narrowed by the margin.
-__global__ void sr_select_kernel(uint32_t* __restrict__ hist, SrState* __restrict__ state, uint32_t* __restrict__ thr, uint64_t N, uint32_t digit, uint32_t count) {
+__global__ void sr_select_kernel(uint32_t* __restrict__ hist, SrState* __restrict__ state, uint32_t* __restrict__ thr, const uint32_t* __restrict__ unrankable,
+                                 uint64_t N, uint32_t digit, uint32_t count) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= N) return;
     SrState st = state[s];
@@ -171,7 +179,8 @@ __global__ void sr_select_kernel(uint32_t* __restrict__ hist, SrState* __restric
         unsigned long long total = 0;
         for (int b = 0; b < 256; ++b) total += h[b];
         st.total = (uint32_t)total;
-        if (total < count) { st.done = 1; state[s] = st; thr[s] = total ? 1u : 0u; return; }       // fewer than `count` cells: everything is kept
+        // fewer than `count` cells, or a cell the device cannot rank: everything is kept
+        if (total < count || unrankable[s]) { st.done = 1; state[s] = st; thr[s] = total ? 1u : 0u; return; }
         st.k = count; st.prefix = 0;
     }
     uint32_t acc = 0;
@@ -181,18 +190,15 @@ __global__ void sr_select_kernel(uint32_t* __restrict__ hist, SrState* __restric
         if (st.k && acc + c >= st.k) { st.prefix = (st.prefix << 8) | (uint32_t)b; st.k -= acc; acc = 0; for (int z = b - 1; z >= 0; --z) h[z] = 0; break; }
         acc += c;
     }
-    if (digit == 3) {
-        if (st.prefix == SR_KEY_BEST) { st.done = 1; thr[s] = 1u; }       // `count` cells the device cannot rank: the whole row goes to the host
-        else {
-            const double T = (double)sr_key_float(st.prefix);
-            const double narrowed = T - fabs(T) * (1e-6 + 2.384185791015625e-07);
-            float f = (float)narrowed;
-            if ((double)f > narrowed) f = nextafterf(f, -INFINITY);
-            uint32_t key = sr_float_key(f);
-            if (key == 0) key = 1;
-            thr[s] = key;
-            st.done = 2;
-        }
+    if (digit == 3) {                                                     // (the keys of a row that reaches this are all finite floats)
+        const double T = (double)sr_key_float(st.prefix);
+        const double narrowed = T - fabs(T) * (1e-6 + 2.384185791015625e-07);
+        float f = (float)narrowed;
+        if ((double)f > narrowed) f = nextafterf(f, -INFINITY);
+        uint32_t key = sr_float_key(f);
+        if (key == 0) key = 1;
+        thr[s] = key;
+        st.done = 2;
     }
     state[s] = st;
 }
@@ -242,7 +248,7 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
     q.kind = j.kind; q.flip = j.flip; q.count = j.count;
     const uint64_t B = (N + q.W - 1) / q.W, tiles = B * (B + 1) / 2;
     if (tiles >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many tiles");
-    DevBuf<uint32_t> hist, thr, cursor, tcol, tval, col, val;
+    DevBuf<uint32_t> hist, thr, cursor, tcol, tval, col, val, unrankable;
     DevBuf<SrState> state;
     DevBuf<unsigned long long> len, row_ptr, ntr;
     DevBuf<char> tmp;
@@ -270,16 +276,18 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
         HIP_TRY(hipMemsetAsync(hist, 0, N * 256 * 4, st));
         HIP_TRY(hipMemsetAsync(state, 0, N * sizeof(SrState), st));
         HIP_TRY(hipMemsetAsync(thr, 0, N * 4, st));
+        DEV_ALLOC(unrankable, std::max<uint64_t>(N, 1));
+        HIP_TRY(hipMemsetAsync(unrankable, 0, N * 4, st));
         for (uint32_t d = 0; d < 4; ++d) {
             hipLaunchKernelGGL((sr_tile_kernel<SR_HIST>), grid, block, 0, st, q, d, state, hist, (const uint32_t*)nullptr, (unsigned long long*)nullptr,
-                               (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(sr_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, hist, state, thr, N, d, q.count);
+                               (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, unrankable.get());
+            hipLaunchKernelGGL(sr_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, hist, state, thr, (const uint32_t*)unrankable.get(), N, d, q.count);
             ++out->passes;
         }
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL((sr_tile_kernel<SR_COUNT>), grid, block, 0, st, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, len, (const unsigned long long*)nullptr,
-                       (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     ++out->passes;
     if (!only_rows) hipLaunchKernelGGL(sr_truncated_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, state, len, N, ntr);
     size_t tmp_bytes = 0;
@@ -297,7 +305,7 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
         DEV_ALLOC(col, std::max<uint64_t>(nnz, 1));
         DEV_ALLOC(val, std::max<uint64_t>(nnz, 1));
         hipLaunchKernelGGL((sr_tile_kernel<SR_EMIT>), grid, block, 0, st, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, (unsigned long long*)nullptr, row_ptr, cursor,
-                           tcol, tval);
+                           tcol, tval, (uint32_t*)nullptr);
         ++out->passes;
         hipLaunchKernelGGL(sr_sort_rows_kernel, dim3((unsigned)N), dim3(64), 0, st, row_ptr, tcol, tval, col, val);
         HIP_TRY(hipGetLastError());

@@ -67,16 +67,18 @@ def passing(K, i, j, c, kmers, k, filters):
 
 def expected_rows(K, tri, N, kmers, k, criterion, count, filters=()):
     """the sampler's rows from the full matrix: every passing pair offered to both its samples with one score (the triangle's row sample first),
-    the `count` best by (score descending, id ascending), written in ascending id"""
+    the `count` best by (score descending, id ascending), written in ascending id.  A NaN score ranks below every number and among NaN scores
+    the smaller id wins: host_sampler.cpp's own rule (the reference's comparison is no order there)"""
     i, j, c = pairs_of(tri, N)
     ok = passing(K, i, j, c, kmers, k, filters)
     i, j, c = i[ok], j[ok], c[ok]
     sc = metric_of(K, criterion, c, kmers[i], kmers[j], k)
     per = [[] for _ in range(N)]
     for a, b, v, s in zip(i.tolist(), j.tolist(), c.tolist(), sc.tolist()):
-        per[a].append((-s, b, v))
-        per[b].append((-s, a, v))
-    return [sorted((o, v) for _, o, v in sorted(r)[:count]) for r in per]
+        nan = s != s
+        per[a].append((nan, 0.0 if nan else -s, b, v))
+        per[b].append((nan, 0.0 if nan else -s, a, v))
+    return [sorted((o, v) for _, _, o, v in sorted(r)[:count]) for r in per]
 
 
 def full_part(tri, N):
