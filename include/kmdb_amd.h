@@ -49,6 +49,10 @@ extern "C" {
  * computes, or one the caller accumulated — measured and formatted without ever being text (kmdb_distance_take_all2all,
  * kmdb_distance_take_cells_device, kmdb_distance_matrix_rows, kmdb_distance_cells_device): four more entry points, no struct changed, the version stays 8. */
 #define KMDB_HAS_DISTANCE_MATRIX 1
+/* And the distance mode fed from the rows of a batch of new2all queries in HBM — computed into a rectangle the handle owns, or one the caller
+ * accumulated (kmdb_distance_take_new2all_batch, kmdb_distance_take_new2all_batch_seq_alphabet, kmdb_distance_take_rows_device,
+ * kmdb_distance_query_rows): four more entry points, no struct changed, the version stays 8. */
+#define KMDB_HAS_DISTANCE_QUERY_ROWS 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -806,6 +810,40 @@ int  kmdb_distance_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_h
  * the same n — another measure, other bounds — borrows them with kmdb_distance_take_cells_device while the first one lives: one all2all
  * run serves several tables. */
 const void* kmdb_distance_cells_device(const kmdb_distance* d);
+/* The same table from the rows of a batch of queries in HBM (KMDB_HAS_DISTANCE_QUERY_ROWS): `new2all` followed by `distance` without the table
+ * of counts in between.  The handle is begun with the DATABASE samples' k-mer counts as `counts` (n = N: the columns' counts), WITHOUT
+ * KMDB_DISTANCE_TRIANGLE and without KMDB_DISTANCE_SPARSE_IN — any other handle is refused by the four calls below.  What
+ * kmdb_distance_query_rows returns for rows [row_lo, row_hi) of the batch is byte for byte what kmdb_distance_rows returns for those rows of
+ * the DENSE table of counts new2all writes ("<query name>,<query count>,<N cells>,\n"): "<query name>," and N values; with SPARSE_OUT
+ * "<column + 1>:<value>," of the non-zero cells that pass the bounds; with PHYLIP blanks and no bounds.  In every measure and bound a = the
+ * QUERY's own k-mer count truncated to uint32, b = counts[column]: mash-query tells the two apart.  The cells the device cannot settle go to
+ * the host as they do for text (kmdb_distance_stats.host_cells).  The triangle rule of the distance mode (row 0 named like the first sample
+ * with a first cell of 0) is the CALLER's to decide: these calls always write whole rows.
+ *
+ * take_new2all_batch: the HANDLE owns an nq x N rectangle of uint32, kept between takes and grown only for a larger batch; the call zeroes
+ *   it on the handle's stream, runs kmdb_new2all_batch_device of `db` into it (kmers, counts, nq, opts as there; NULL opts: the defaults; a
+ *   null opts->stream means the handle's) and keeps a[q] = (uint32_t)counts[q] and the nq `names` (C strings) on the device.
+ * take_new2all_batch_seq_alphabet: the same through kmdb_new2all_batch_seq_alphabet_device; a[q] = the device extractor's unique count, also
+ *   returned in out_kmer_counts.
+ *   Both refuse: a database on another device than the handle's, or of another N than the handle's n; a handle without hashtables; a QUERY
+ *   SHARD handle (kmdb_db_upload_query_shard) — its rows are partial sums and so are its counts: sum the shards' rows and hand them over
+ *   with take_rows_device.
+ * take_rows_device: borrows rows the CALLER accumulated (a sum over shards, a tensor, another handle's rows): rows_dev = cell 0 of a
+ *   row-major nq x N rectangle of uint32 in device memory, complete on the handle's stream and alive while rows are asked for; query_kmers
+ *   = the nq queries' counts in host memory.  A null pointer is taken when the rows asked for later hold no cells.  A second handle of the
+ *   same n — another measure, other bounds — borrows the first one's rows: kmdb_distance_cells_device returns the address of the rows taken.
+ * query_rows: out as with kmdb_distance_rows (kmdb_distance_out_free); row_lo == row_hi gives empty text and 0 rows.  Refused: nothing
+ *   taken; row_lo > row_hi; row_hi > nq; cells and a null pointer; a piece of 2^31 cells or more, or one whose working arrays (17 B a cell)
+ *   do not fit the device's free memory — the message gives the bytes; ask for fewer rows.
+ * kmdb_distance_stats counts these calls in its fields: cells_read = the cells of the rows, bytes_in = four times that, parse_ms stays 0. */
+int  kmdb_distance_take_new2all_batch(kmdb_distance* d, kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq,
+                                      const char* const* names, const kmdb_opts* opts);
+int  kmdb_distance_take_new2all_batch_seq_alphabet(kmdb_distance* d, kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq,
+                                                   double fraction, double start_fraction, int32_t alphabet, const char* const* names,
+                                                   uint64_t* out_kmer_counts, const kmdb_opts* opts);
+int  kmdb_distance_take_rows_device(kmdb_distance* d, const void* rows_dev, size_t nq, const uint32_t* query_kmers /* [nq], host */,
+                                    const char* const* names);
+int  kmdb_distance_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out);
 void kmdb_distance_out_free(kmdb_distance_out* out);
 void kmdb_distance_free(kmdb_distance* d);
 int  kmdb_distance_stats_get(const kmdb_distance* d, kmdb_distance_stats* out);

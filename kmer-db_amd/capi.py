@@ -151,6 +151,7 @@ EXPORTS = [
     "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
     "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
     "kmdb_distance_take_all2all", "kmdb_distance_take_cells_device", "kmdb_distance_matrix_rows", "kmdb_distance_cells_device",
+    "kmdb_distance_take_new2all_batch", "kmdb_distance_take_new2all_batch_seq_alphabet", "kmdb_distance_take_rows_device", "kmdb_distance_query_rows",
 ]
 
 
@@ -290,6 +291,11 @@ def lib():
     L.kmdb_distance_take_all2all.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(_Opts)]
     L.kmdb_distance_take_cells_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)]
     L.kmdb_distance_matrix_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_take_new2all_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(_Opts)]
+    L.kmdb_distance_take_new2all_batch_seq_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                                                C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_distance_take_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]
+    L.kmdb_distance_query_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_DistanceOut)]
     L.kmdb_distance_cells_device.restype = C.c_void_p
     L.kmdb_distance_cells_device.argtypes = [C.c_void_p]
     L.kmdb_distance_out_free.restype = None
@@ -1165,6 +1171,37 @@ class Distance:
         """kmdb_distance_matrix_rows: the text of rows [lo, hi) of the measure's table of the matrix taken"""
         out = _DistanceOut()
         _check(lib().kmdb_distance_matrix_rows(self._d, int(lo), int(hi), C.byref(out)))
+        try:
+            return C.string_at(out.text, out.len)
+        finally:
+            lib().kmdb_distance_out_free(C.byref(out))
+
+    def take_new2all(self, db, kmer_lists, names):
+        """kmdb_distance_take_new2all_batch: the new2all rows of a batch of queries (sorted unique k-mer arrays) against a DeviceDB, computed into a
+        rectangle the handle owns, become the source of cells; a = the length of each list"""
+        keep, ptrs, cnts, nq = _kmer_queries(kmer_lists)
+        _check(lib().kmdb_distance_take_new2all_batch(self._d, db._d, ptrs, cnts, nq, self._names(names), None))
+
+    def take_new2all_seqs(self, db, seqs, names, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        """kmdb_distance_take_new2all_batch_seq_alphabet: the same with the queries given as sequence text; returns the unique k-mer count per query"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        keep, ptrs, lens, nq = _text_queries(seqs)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        _check(lib().kmdb_distance_take_new2all_batch_seq_alphabet(self._d, db._d, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet),
+                                                                   self._names(names), cnt.ctypes.data, None))
+        return cnt[:nq]
+
+    def take_rows(self, dev_ptr, nq, query_kmers, names):
+        """kmdb_distance_take_rows_device: dev_ptr (e.g. a torch tensor's .data_ptr(), or None) = cell 0 of a row-major nq x N rectangle of uint32
+        the caller keeps alive; query_kmers: the queries' own k-mer counts"""
+        qk = np.ascontiguousarray(np.asarray(query_kmers, np.uint64) & 0xFFFFFFFF, np.uint32)
+        _check(lib().kmdb_distance_take_rows_device(self._d, C.c_void_p(dev_ptr), int(nq), qk.ctypes.data, self._names(names)))
+
+    def query_rows(self, lo, hi):
+        """kmdb_distance_query_rows: the text of rows [lo, hi) of the measure's table of the batch taken"""
+        out = _DistanceOut()
+        _check(lib().kmdb_distance_query_rows(self._d, int(lo), int(hi), C.byref(out)))
         try:
             return C.string_at(out.text, out.len)
         finally:

@@ -12,11 +12,15 @@
 // The cells have two sources behind the same measure and format stages: the tokens parsed from text (TextCells), and a lower triangle of
 // counts that is in HBM already (TriangleCells: kmdb_distance_take_* and kmdb_distance_matrix_rows) — output cell ci of a piece of rows IS
 // matrix cell piece_lo + ci, consecutive lanes read consecutive uint32, nothing is classified or parsed and the names come from a blob.
+// A third source is the row-major nq x N rectangle of a batch of new2all queries (RowCells: kmdb_distance_take_new2all_batch*,
+// kmdb_distance_take_rows_device and kmdb_distance_query_rows) — the same, with whole rows of N cells, a = the QUERY's own count and the
+// names of the queries.
 //
 // Every position is below the piece's length by construction and clamped to it again where it is used: damaged text is declined
 // (KMDB_DISTANCE_DECLINED) or parsed as the host loop parses it, and never read or written outside the buffers.
 #include "kmdb_amd.h"
 #include "dev_mem.h"
+#include "engine_internal.h"
 #include "engine_state.h"
 #include "prim.h"
 
@@ -83,6 +87,10 @@ struct DistParams {
     uint64_t piece_lo;              // the matrix cell of the piece's output cell 0: first_row (first_row - 1) / 2
     const unsigned char* names;     // the samples' names back to back
     const uint64_t* name_off;       // [n + 1] where a sample's name begins
+    // the rows of a batch of queries as the source of cells (RowCells): tri = cell 0 of the nq x n rectangle, tri_cells = nq n, piece_lo =
+    // first_row n; names / name_off are the QUERIES' ([rows_nq + 1])
+    const uint32_t* row_counts;     // [rows_nq] the queries' own k-mer counts
+    uint64_t rows_nq;
 };
 
 // a cell the host decides: where its text goes, and what it is
@@ -365,6 +373,38 @@ __global__ void __launch_bounds__(DT) dist_tri_row_sizes_kernel(DistParams p) {
     p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
 }
 
+struct RowCells {
+    // every cell of the piece is a cell of the rectangle: row = ci / n in 32 bits (a piece holds fewer than 2^31 cells; a 64-bit divide is a
+    // long software sequence), the row's own count is a = row_counts[first_row + row], b = counts[col] as everywhere
+    static __device__ Cell at(const DistParams& p, uint64_t ci) {
+        Cell x{};
+        const uint32_t c32 = (uint32_t)ci;
+        const uint32_t row = min(c32 / p.n, p.R - 1);           // clamped to the piece
+        const uint32_t col = min(c32 - row * p.n, p.n - 1);
+        x.row = row;
+        x.col = col;
+        x.a = p.row_counts[min(p.first_row + row, p.rows_nq - 1)];
+        x.count = p.tri[min(p.piece_lo + ci, p.tri_cells - 1)];
+        x.emit = p.mode != MODE_SPARSE_OUT || x.count > 0;
+        x.prefix = p.mode == MODE_SPARSE_OUT ? col + 1 : 0;
+        return x;
+    }
+    static __device__ __forceinline__ const unsigned char* name(const DistParams& p, uint32_t r, uint32_t* nlen) {
+        const uint64_t s = min(p.first_row + r, p.rows_nq - 1);
+        *nlen = (uint32_t)(p.name_off[s + 1] - p.name_off[s]);
+        return p.names + p.name_off[s];
+    }
+};
+
+// a lane per row of a piece of the rectangle: n output cells, and the bytes of the query's name, the separator behind it and the '\n'
+__global__ void __launch_bounds__(DT) dist_query_row_sizes_kernel(DistParams p) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r >= p.R) return;
+    const uint64_t s = min(p.first_row + r, p.rows_nq - 1);
+    p.oc[r] = p.n;
+    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
+}
+
 template <class Source>
 __global__ void __launch_bounds__(DT) dist_measure_kernel(DistParams p) {
     const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
@@ -492,6 +532,15 @@ struct kmdb_distance {
     uint64_t tri_row_lo = 0;
     DevBuf<unsigned char> d_names;
     DevBuf<uint64_t> d_name_off;
+    // the rows of a batch of queries taken as the source of cells (kmdb_distance_take_new2all_batch*: the handle's own buffer, kept between
+    // takes and grown only for a larger batch; kmdb_distance_take_rows_device: the caller's)
+    bool rows_taken = false;
+    DevBuf<uint32_t> own_rows;
+    const uint32_t* rows = nullptr;     // cell 0 of the nq x n rectangle; may be null when it holds no cell
+    uint64_t rows_nq = 0;
+    DevBuf<uint32_t> d_row_counts;      // [rows_nq] the queries' own counts
+    DevBuf<unsigned char> d_qnames;
+    DevBuf<uint64_t> d_qname_off;
     kmdb_distance_stats st{};
 };
 
@@ -800,8 +849,7 @@ static int dist_take_check(const kmdb_distance* d, const std::string& who) {
 }
 
 // the names to the device once: a blob and the offsets of its n + 1 ends
-static int dist_take_names(kmdb_distance* d, const char* const* names, const std::string& who) {
-    const size_t n = d->counts.size();
+static int dist_names_to_device(kmdb_distance* d, const char* const* names, size_t n, DevBuf<unsigned char>& d_blob, DevBuf<uint64_t>& d_off, const std::string& who) {
     std::vector<uint64_t> off(n + 1, 0);
     for (size_t i = 0; i < n; ++i) {
         if (!names[i]) return kmdb_set_error(who + "null name");
@@ -811,10 +859,13 @@ static int dist_take_names(kmdb_distance* d, const char* const* names, const std
     blob.reserve((size_t)off[n]);
     for (size_t i = 0; i < n; ++i) blob.append(names[i]);
     HIP_TRY(hipSetDevice(d->device));
-    DEV_ALLOC(d->d_names, blob.size()); DEV_ALLOC(d->d_name_off, n + 1);
-    if (!blob.empty()) HIP_TRY(hipMemcpy(d->d_names.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->d_name_off.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    DEV_ALLOC(d_blob, blob.size()); DEV_ALLOC(d_off, n + 1);
+    if (!blob.empty()) HIP_TRY(hipMemcpy(d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_off.get(), off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
     return 0;
+}
+static int dist_take_names(kmdb_distance* d, const char* const* names, const std::string& who) {
+    return dist_names_to_device(d, names, d->counts.size(), d->d_names, d->d_name_off, who);
 }
 
 extern "C" int kmdb_distance_take_all2all(kmdb_distance* d, kmdb_db* db, const char* const* names, const kmdb_opts* opts) {
@@ -858,7 +909,7 @@ extern "C" int kmdb_distance_take_cells_device(kmdb_distance* d, const void* cel
     }
 }
 
-extern "C" const void* kmdb_distance_cells_device(const kmdb_distance* d) { return d && d->taken ? d->tri : nullptr; }
+extern "C" const void* kmdb_distance_cells_device(const kmdb_distance* d) { return !d ? nullptr : d->taken ? d->tri : d->rows_taken ? d->rows : nullptr; }
 
 static int dist_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
     const char* who = "kmdb_distance_matrix_rows: ";
@@ -930,6 +981,174 @@ extern "C" int kmdb_distance_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint
         rc = dist_matrix_rows(d, row_lo, row_hi, out);
     } catch (const std::exception& e) {
         rc = kmdb_set_error(std::string("kmdb_distance_matrix_rows: ") + e.what());
+    }
+    if (rc) kmdb_distance_out_free(out);
+    return rc;
+}
+
+// ---- the rows of a batch of queries as the source of cells -------------------------------------------------------------------------------
+static int dist_rows_check(const kmdb_distance* d, const std::string& who) {
+    if (d->flags & KMDB_DISTANCE_TRIANGLE) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_TRIANGLE: the rows of queries are whole rows");
+    if (d->flags & KMDB_DISTANCE_SPARSE_IN) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_SPARSE_IN: the rows of queries hold no column:count pairs");
+    return 0;
+}
+
+// what a take keeps besides the cells: the queries' own counts and their names
+static int dist_take_queries(kmdb_distance* d, const uint32_t* a, size_t nq, const char* const* names, const std::string& who) {
+    if (dist_names_to_device(d, names, nq, d->d_qnames, d->d_qname_off, who)) return 1;
+    DEV_ALLOC(d->d_row_counts, nq);
+    if (nq) HIP_TRY(hipMemcpy(d->d_row_counts.get(), a, nq * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// One batch into the handle's own rectangle: zeroed on the handle's stream, filled by `fill` (kmdb_new2all_batch*_device, which returns when
+// its last kernel has ended), a[q] = what fill reports as the query's count.
+template <class Fill>
+static int dist_take_batch(kmdb_distance* d, kmdb_db* db, size_t nq, const char* const* names, const kmdb_opts* opts, const std::string& who, Fill&& fill) {
+    if (dist_rows_check(d, who)) return 1;
+    kmdb_engine_view e;
+    if (kmdb_engine_get(db, &e)) return 1;
+    if (e.device != d->device) return kmdb_set_error(who + "the database lives on device " + std::to_string(e.device) + ", the handle on device " + std::to_string(d->device));
+    if (e.N != d->counts.size()) return kmdb_set_error(who + "the database holds " + std::to_string(e.N) + " samples, the handle was begun with " + std::to_string(d->counts.size()));
+    if (e.qs_count > 1) return kmdb_set_error(who + "a query shard holds partial sums and partial k-mer counts (sum the shards' rows with kmdb_new2all_batch_device and hand them to kmdb_distance_take_rows_device)");
+    if (!e.n_buckets || !e.slots) return kmdb_set_error(who + "database was uploaded without hashtables");
+    if (nq >= (1ull << 31)) return kmdb_set_error(who + "too many queries in one batch");
+    d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0;
+    HIP_TRY(hipSetDevice(d->device));
+    const uint64_t cells = (uint64_t)nq * e.N;
+    if (d->own_rows.bytes() < cells * 4 || !d->own_rows) DEV_ALLOC(d->own_rows, (size_t)std::max<uint64_t>(1, cells));
+    if (cells) HIP_TRY(hipMemsetAsync(d->own_rows.get(), 0, cells * 4, d->stream));
+    kmdb_opts o{};
+    if (opts) o = *opts;
+    else { o.abi_version = KMDB_ABI_VERSION; o.shard_count = 1; }
+    o.device = d->device;
+    if (!o.stream) o.stream = d->stream;                        // (null still: the database's own stream)
+    const hipStream_t runs_on = o.stream ? (hipStream_t)o.stream : (hipStream_t)e.stream;
+    if (runs_on != d->stream) HIP_TRY(hipStreamSynchronize(d->stream));     // the zeros first
+    std::vector<uint32_t> a(std::max<size_t>(nq, 1), 0);
+    if (fill(d->own_rows.get(), &o, a.data())) return 1;
+    if (dist_take_queries(d, a.data(), nq, names, who)) return 1;
+    d->rows = d->own_rows.get(); d->rows_nq = nq; d->rows_taken = true;
+    return 0;
+}
+
+extern "C" int kmdb_distance_take_new2all_batch(kmdb_distance* d, kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq,
+                                                const char* const* names, const kmdb_opts* opts) {
+    const std::string who = "kmdb_distance_take_new2all_batch: ";
+    if (!d || !db || (nq && (!kmers || !counts || !names))) return kmdb_set_error(who + "null argument");
+    try {
+        return dist_take_batch(d, db, nq, names, opts, who, [&](uint32_t* rows, const kmdb_opts* o, uint32_t* a) -> int {
+            for (size_t q = 0; q < nq; ++q) a[q] = (uint32_t)counts[q];
+            return kmdb_new2all_batch_device(db, kmers, counts, nq, rows, o);
+        });
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_take_new2all_batch_seq_alphabet(kmdb_distance* d, kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq,
+                                                             double fraction, double start_fraction, int32_t alphabet, const char* const* names,
+                                                             uint64_t* out_kmer_counts, const kmdb_opts* opts) {
+    const std::string who = "kmdb_distance_take_new2all_batch_seq_alphabet: ";
+    if (!d || !db || (nq && (!seqs || !seq_lens || !names || !out_kmer_counts))) return kmdb_set_error(who + "null argument");
+    if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error(who + "unknown alphabet " + std::to_string(alphabet));
+    try {
+        return dist_take_batch(d, db, nq, names, opts, who, [&](uint32_t* rows, const kmdb_opts* o, uint32_t* a) -> int {
+            // the query counts are the device extractor's unique counts
+            if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, out_kmer_counts, o)) return 1;
+            for (size_t q = 0; q < nq; ++q) a[q] = (uint32_t)out_kmer_counts[q];
+            return 0;
+        });
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_take_rows_device(kmdb_distance* d, const void* rows_dev, size_t nq, const uint32_t* query_kmers, const char* const* names) {
+    const std::string who = "kmdb_distance_take_rows_device: ";
+    if (!d || (nq && (!query_kmers || !names))) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_rows_check(d, who)) return 1;
+        if (nq >= (1ull << 31)) return kmdb_set_error(who + "too many queries in one batch");
+        d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0;
+        HIP_TRY(hipSetDevice(d->device));
+        if (dist_take_queries(d, query_kmers, nq, names, who)) return 1;
+        d->rows = (const uint32_t*)rows_dev; d->rows_nq = nq; d->rows_taken = true;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+static int dist_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    const char* who = "kmdb_distance_query_rows: ";
+    const uint64_t n = d->counts.size();
+    if (dist_rows_check(d, who)) return 1;
+    if (!d->rows_taken) return kmdb_set_error(std::string(who) + "no rows were taken (kmdb_distance_take_new2all_batch, kmdb_distance_take_new2all_batch_seq_alphabet, kmdb_distance_take_rows_device)");
+    if (row_lo > row_hi) return kmdb_set_error(std::string(who) + "row_lo > row_hi");
+    if (row_hi > d->rows_nq) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(d->rows_nq) + " rows");
+    d->st.calls += 1;
+    if (row_lo == row_hi) {
+        out->text = (char*)malloc(1);
+        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
+        return 0;
+    }
+    const uint32_t R = (uint32_t)(row_hi - row_lo);
+    const uint64_t n_cells = (uint64_t)R * n;
+    if (n_cells && !d->rows) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " cells and a null pointer was taken");
+    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
+    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
+    size_t mem_free = 0, mem_total = 0;
+    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
+                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
+    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
+    DevEvent begun;
+    if (begun.create()) return 1;
+    DevBuf<uint64_t> d_oc, d_rowfix;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<void> d_tmp;
+    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
+    HIP_TRY(hipEventRecord(begun, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
+    DistParams p{};
+    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 0; p.first_row = row_lo;
+    p.n_filters = (int)d->filters.size();
+    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
+    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
+    p.tri = d->rows; p.tri_lo = 0; p.tri_cells = d->rows_nq * n; p.piece_lo = row_lo * n;
+    p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->rows_nq; p.n_cells = n_cells;
+    hipLaunchKernelGGL(dist_query_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
+    if (dist_scan(d_oc.get(), d_oc.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
+    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
+    uint64_t oc_all = 0, fix_bytes = 0;
+    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
+    DistTail t{};
+    if (dist_measure_format<RowCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
+    out->rows = R;
+    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
+    d->st.bytes_in += n_cells * 4; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
+    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+    return 0;
+}
+
+extern "C" int kmdb_distance_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    if (!d || !out) return kmdb_set_error("kmdb_distance_query_rows: null argument");
+    out->text = nullptr; out->len = 0; out->rows = 0;
+    int rc;
+    try {
+        rc = dist_query_rows(d, row_lo, row_hi, out);
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string("kmdb_distance_query_rows: ") + e.what());
     }
     if (rc) kmdb_distance_out_free(out);
     return rc;

@@ -5,6 +5,7 @@
 //     kmer-db-amd all2all-sp [-min [m:]v] [-max [m:]v]           <db> <out.csv>
 //     kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <out>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
+//     kmer-db-amd new2all    [-multisample-fasta] [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <sample-list> <out>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
 //     kmer-db-amd minhash    [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] <samples>
@@ -293,6 +294,7 @@ std::vector<std::string> take_distance_measures(std::vector<std::string>& args) 
     return measures;
 }
 int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures, bool sparse_forced, const char* mode);
+int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures);
 
 // ---- all2all (console_all2all.cpp:7-89) -----------------------------------------------------------
 int run_all2all(std::vector<std::string>& args, Common& c) {
@@ -1110,9 +1112,104 @@ int run_build(std::vector<std::string>& args, Common& c) {
     return 0;
 }
 
+// The queries of a new2all run (console_new2all.cpp:64-74): read, extracted and handed on in input order, in batches of 64 queries — flushed by
+// size as well as by count: the engine's scratch grows with the bases.  flush() takes what `batch` holds and clears it.  A list entry that
+// cannot be read is announced as "failed:<path>" and left out.
+struct QuerySource {
+    bool from_minhash, multi, host_extract;
+    uint32_t k;
+    int32_t alphabet;
+    double fraction, fstart;
+    int nthreads;
+};
+template <class Flush>
+void new2all_queries(const std::vector<std::string>& entries, const QuerySource& s, std::vector<Query>& batch, Flush&& flush) {
+    const bool from_minhash = s.from_minhash, multi = s.multi, host_extract = s.host_extract;
+    const uint32_t k = s.k;
+    const int32_t alphabet = s.alphabet;
+    const double fraction = s.fraction, fstart = s.fstart;
+    const int nthreads = s.nthreads;
+    size_t batch_bases = 0;
+    auto make_query = [&](const std::string& name, const std::vector<const std::string*>& seqs) {
+        Query q;
+        q.name = name;
+        size_t bytes = 0;
+        for (auto* s : seqs) bytes += s->size() + 1;
+        q.from_kmers = host_extract || bytes >= LONG_QUERY_BASES;
+        if (!q.from_kmers) {
+            q.text.reserve(bytes);
+            for (auto* s : seqs) { q.text += *s; q.text += '\n'; }
+            return q;
+        }
+        size_t total = 0;
+        for (auto* s : seqs) total += s->size();
+        q.kmers.resize(total + 1);
+        size_t cnt = 0;
+        for (auto* s : seqs) cnt += kmdbh_extract_kmers_alphabet(s->data(), s->size(), k, alphabet, fraction, fstart, q.kmers.data() + cnt);
+        cnt = kmdbh_sort_unique(q.kmers.data(), cnt);              // KmerHelper::unique (console_new2all.cpp:73)
+        q.kmers.resize(cnt);
+        return q;
+    };
+
+    const size_t BATCH = 64, BATCH_BASES = 512u << 20;
+    auto add = [&](Query&& q) {
+        batch_bases += q.text.size() + q.kmers.size();
+        batch.push_back(std::move(q));
+        if (batch.size() == BATCH || batch_bases >= BATCH_BASES) { flush(); batch_bases = 0; }
+    };
+    if (multi) {
+        for (auto& e : entries) {
+            std::string data;
+            if (!slurp(e, data)) { std::cerr << "failed:" << e << std::endl; continue; }
+            std::vector<Record> recs;
+            split_fasta(data, recs);
+            for (auto& r : recs) {
+                add(make_query(r.header, {&r.seq}));
+            }
+        }
+    } else {
+        for (size_t base = 0; base < entries.size(); base += BATCH) {
+            size_t cntq = std::min(BATCH, entries.size() - base);
+            std::vector<Query> qs(cntq);
+            std::vector<char> okv(cntq, 0);
+            std::atomic<size_t> next{0};
+            auto worker = [&]() {
+                for (size_t i; (i = next.fetch_add(1)) < cntq;) {
+                    if (from_minhash) {
+                        uint32_t fk = 0;
+                        if (!load_minhash(entries[base + i], qs[i].kmers, fk)) continue;      // (cannot be opened, or damaged)
+                        qs[i].name = basename_of(entries[base + i]);
+                        qs[i].from_kmers = true;
+                        okv[i] = 1;
+                        continue;
+                    }
+                    std::string data;
+                    if (!slurp(entries[base + i], data)) continue;
+                    std::vector<Record> recs;
+                    split_fasta(data, recs);
+                    std::vector<const std::string*> seqs;
+                    for (auto& r : recs) seqs.push_back(&r.seq);
+                    qs[i] = make_query(basename_of(entries[base + i]), seqs);
+                    okv[i] = 1;
+                }
+            };
+            std::vector<std::thread> pool;
+            for (int t = 0; t < std::min<int>(nthreads, (int)cntq); ++t) pool.emplace_back(worker);
+            for (auto& t : pool) t.join();
+            for (size_t i = 0; i < cntq; ++i) {
+                if (!okv[i]) { std::cerr << "failed:" << entries[base + i] << std::endl; continue; }
+                add(std::move(qs[i]));
+            }
+        }
+    }
+    flush();
+}
+
 // ---- new2all (console_new2all.cpp:12-174) ---------------------------------------------------------
 int run_new2all(std::vector<std::string>& args, Common& c) {
     if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    const std::vector<std::string> measures = take_distance_measures(args);
+    if (!measures.empty()) return run_new2all_distance(args, c, measures);
     // -from-minhash: every list entry names <entry>.minhash; its words go to the k-mer entries AS STORED — the database's filter is not applied
     // again (MihashedInputFile::load, minhashed_input_file.h:88-105)
     const bool from_minhash = take_switch(args, "-from-minhash");
@@ -1157,7 +1254,6 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     // queries are produced in input order; similarities are computed in batches on the GPU and rows
     // written in the same order (the reference re-orders through a priority queue, :60,114-117)
     std::vector<Query> batch;
-    size_t batch_bases = 0;                    // flushed by size as well as by count: the engine's scratch grows with the bases
     // -sparse: the rows are compacted and the -min / -max bounds applied on the device (kmdb_new2all_batch*_sparse_filtered: one2all_sp + the row's
     // CombinedFilter, console_new2all.cpp:76-78, 130-148); KMDB_N2A_DENSE_ROWS=1 keeps the dense rows and the host's filter (A/B, same bytes)
     const bool sparse_on_device = c.sparse && !std::getenv("KMDB_N2A_DENSE_ROWS");
@@ -1172,7 +1268,6 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     }
     auto flush = [&]() {
         if (batch.empty()) return;
-        batch_bases = 0;
         std::vector<size_t> cnts(batch.size());
         std::vector<uint32_t> out(sparse_on_device ? 1 : batch.size() * n + 1);
         // a query is either sequence text (loader + KmerHelper::unique + one2all on the device, kmdb_new2all_batch_seq) or,
@@ -1257,79 +1352,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
         batch.clear();
     };
 
-    auto make_query = [&](const std::string& name, const std::vector<const std::string*>& seqs) {
-        Query q;
-        q.name = name;
-        size_t bytes = 0;
-        for (auto* s : seqs) bytes += s->size() + 1;
-        q.from_kmers = host_extract || bytes >= LONG_QUERY_BASES;
-        if (!q.from_kmers) {
-            q.text.reserve(bytes);
-            for (auto* s : seqs) { q.text += *s; q.text += '\n'; }
-            return q;
-        }
-        size_t total = 0;
-        for (auto* s : seqs) total += s->size();
-        q.kmers.resize(total + 1);
-        size_t cnt = 0;
-        for (auto* s : seqs) cnt += kmdbh_extract_kmers_alphabet(s->data(), s->size(), k, alphabet, fraction, fstart, q.kmers.data() + cnt);
-        cnt = kmdbh_sort_unique(q.kmers.data(), cnt);              // KmerHelper::unique (console_new2all.cpp:73)
-        q.kmers.resize(cnt);
-        return q;
-    };
-
-    const size_t BATCH = 64, BATCH_BASES = 512u << 20;
-    auto add = [&](Query&& q) {
-        batch_bases += q.text.size() + q.kmers.size();
-        batch.push_back(std::move(q));
-        if (batch.size() == BATCH || batch_bases >= BATCH_BASES) flush();
-    };
-    if (multi) {
-        for (auto& e : entries) {
-            std::string data;
-            if (!slurp(e, data)) { std::cerr << "failed:" << e << std::endl; continue; }
-            std::vector<Record> recs;
-            split_fasta(data, recs);
-            for (auto& r : recs) {
-                add(make_query(r.header, {&r.seq}));
-            }
-        }
-    } else {
-        for (size_t base = 0; base < entries.size(); base += BATCH) {
-            size_t cntq = std::min(BATCH, entries.size() - base);
-            std::vector<Query> qs(cntq);
-            std::vector<char> okv(cntq, 0);
-            std::atomic<size_t> next{0};
-            auto worker = [&]() {
-                for (size_t i; (i = next.fetch_add(1)) < cntq;) {
-                    if (from_minhash) {
-                        uint32_t fk = 0;
-                        if (!load_minhash(entries[base + i], qs[i].kmers, fk)) continue;      // (cannot be opened, or damaged)
-                        qs[i].name = basename_of(entries[base + i]);
-                        qs[i].from_kmers = true;
-                        okv[i] = 1;
-                        continue;
-                    }
-                    std::string data;
-                    if (!slurp(entries[base + i], data)) continue;
-                    std::vector<Record> recs;
-                    split_fasta(data, recs);
-                    std::vector<const std::string*> seqs;
-                    for (auto& r : recs) seqs.push_back(&r.seq);
-                    qs[i] = make_query(basename_of(entries[base + i]), seqs);
-                    okv[i] = 1;
-                }
-            };
-            std::vector<std::thread> pool;
-            for (int t = 0; t < std::min<int>(nthreads, (int)cntq); ++t) pool.emplace_back(worker);
-            for (auto& t : pool) t.join();
-            for (size_t i = 0; i < cntq; ++i) {
-                if (!okv[i]) { std::cerr << "failed:" << entries[base + i] << std::endl; continue; }
-                add(std::move(qs[i]));
-            }
-        }
-    }
-    flush();
+    new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads}, batch, flush);
     if (db.node) node_report(db);                                  // (the last batch's call)
     std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
     return 0;
@@ -1340,6 +1363,8 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
 // command line and the file does not end with a newline (console_one2all.cpp:88-93).
 int run_one2all(std::vector<std::string>& args, Common& c) {
     if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    // (the table one2all writes has no final newline, and the distance loop then drops a one-digit last cell: not reproduced here)
+    if (!take_distance_measures(args).empty()) throw std::runtime_error("one2all does not take -distance: run one2all and distance");
     const bool from_minhash = take_switch(args, "-from-minhash");      // the sample argument names <sample>.minhash (console_one2all.cpp:55-58)
     if (from_minhash && take_switch(args, "-multisample-fasta")) throw usage_error("one2all");
     if (args.size() != 3) throw usage_error("one2all");
@@ -1782,6 +1807,226 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
     return finish(db, ofs, path);
 }
 
+// ---- new2all -distance <measure>: the measure's table straight from the query rows in HBM ------------------------------------------------------
+// `new2all D Q T` followed by `distance -host <measure> T out`, byte for byte, without T (T the DENSE table of counts, whatever -sparse says
+// about the output).  The queries are read, extracted and batched as in new2all.  Per batch the rows are computed once, into a rectangle the
+// first measure's handle owns (kmdb_distance_take_new2all_batch*: the k-mer half and the text half of a batch are two takes); every further
+// measure borrows them (kmdb_distance_take_rows_device).  The rows come back as text in pieces cut at row ends by a budget of cells
+// (KMDB_DISTANCE_CELLS_PER_PIECE, as for the matrix) and are written in input order by a writer thread per measure, while the device has the
+// next batch.  The header lines are the ones run_distance writes for such a table: no ",db-samples", no total-kmers line.  The -min / -max
+// list is read by the DISTANCE mode's rule.
+// The triangle rule (run_distance: row 0 named like the first sample with a first cell of 0 makes row i keep min(i, N) values) would cut the
+// rows of such a table; it is decided here from query 0 of the first batch before any output file exists, and where it would fire the run is
+// refused.  In the sparse form the rule changes no byte, so nothing is decided.
+int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures) {
+    auto avail = metrics();
+    for (auto& m : measures)
+        if (!avail.count(m)) throw std::runtime_error("unknown measure: " + m);
+    if (c.gpus > 0) throw std::runtime_error("-distance does not go with -gpus <N>: the node's query rows live in the chunks of a reduce-scatter (run new2all and distance)");
+    const bool from_minhash = take_switch(args, "-from-minhash");
+    const bool multi = take_switch(args, "-multisample-fasta");
+    if (multi && from_minhash) throw usage_error("new2all");
+    const bool host_extract = take_switch(args, "-host-extract");
+    bool sparse = take_switch(args, "-sparse");
+    const bool phylip = take_switch(args, "-phylip-out");
+    if (phylip) sparse = false;
+    std::map<std::string, DistanceBound> bounds;
+    long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+    take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
+    if (args.size() != 3) throw usage_error("new2all");
+    uint64_t budget = 1ull << 25;
+    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+
+    std::cerr << "Set of new samples  (from " << (from_minhash ? "minhashed k-mers" : "genomes") << ") versus entire database comparison, "
+              << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
+    Db db;
+    std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
+    auto t0 = clk::now();
+    kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
+    check(kmdbh_db_load(args[0].c_str(), 0, &db.h));
+    check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 1, &db.d));
+    std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+    const uint64_t n = kmdbh_db_n_samples(db.h);
+    const uint32_t k = kmdbh_db_kmer_length(db.h);
+    const double fraction = kmdbh_db_fraction(db.h), fstart = kmdbh_db_start_fraction(db.h);
+    const int32_t alphabet = kmdbh_db_alphabet(db.h);
+    if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) throw std::runtime_error("Invalid alphabet type");
+
+    std::ifstream lst(args[1]);
+    if (!lst) throw std::runtime_error("Unable to open sample list " + args[1]);
+    std::vector<std::string> entries;
+    for (std::string ln; std::getline(lst, ln);) {
+        while (!ln.empty() && (ln.back() == '\r' || ln.back() == ' ')) ln.pop_back();
+        if (!ln.empty()) entries.push_back(ln);
+    }
+    const int nthreads = c.threads > 0 ? c.threads : (int)std::max(1u, std::thread::hardware_concurrency());
+
+    DistanceSetup s;
+    s.device = c.device; s.k = k; s.sparse_out = sparse; s.phylip = phylip;
+    s.counts.resize(n);
+    std::vector<std::string> sample_names(n);
+    for (uint64_t i = 0; i < n; ++i) { s.counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i); sample_names[i] = kmdbh_db_sample_name(db.h, i); }
+    const uint32_t flags = (sparse ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (phylip ? KMDB_DISTANCE_PHYLIP : 0u);
+
+    // one handle, one output file and one writer thread per measure; handle 0 owns the rows of the batch
+    struct Text { kmdb_distance_out o{}; };
+    struct Table {
+        std::string measure, path;
+        DistanceHandle h;
+        std::ofstream ofs;
+        Channel<Text> texts;
+        std::thread writer;
+        bool write_failed = false;
+    };
+    std::vector<std::unique_ptr<Table>> tables;
+    for (auto& measure : measures) {
+        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
+        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measure] = b; }
+        s.measure = kmdbh_metric_id(measure.c_str());
+        s.filters = distance_filters(own, kmer_lo, kmer_hi);
+        tables.emplace_back(new Table);
+        Table& t = *tables.back();
+        t.measure = measure;
+        t.path = measures.size() == 1 ? args[2] : args[2] + "." + measure;
+        t.h.begin(s, flags);
+    }
+    bool opened = false;
+    auto open_tables = [&]() {
+        if (opened) return;
+        opened = true;
+        for (auto& tp : tables) {
+            Table& t = *tp;
+            t.ofs.open(t.path, std::ios::binary);
+            if (!phylip) {
+                t.ofs << "kmer-length: " << k << " fraction: " << fraction << " ,";
+                for (uint64_t i = 0; i < n; ++i) t.ofs << sample_names[i] << ',';
+                t.ofs << std::endl;
+            } else t.ofs << n << std::endl;
+            t.writer = std::thread([&t]() {
+                Text x;
+                while (t.texts.pop(x)) {
+                    if (x.o.len) t.ofs.write(x.o.text, (std::streamsize)x.o.len);
+                    kmdb_distance_out_free(&x.o);
+                    if (!t.ofs) { t.write_failed = true; t.texts.close(); break; }
+                }
+            });
+        }
+    };
+    auto stop_tables = [&](bool ok) {
+        for (auto& tp : tables) {
+            if (ok) tp->texts.finish(); else tp->texts.close();
+            if (tp->writer.joinable()) tp->writer.join();
+            tp->texts.drain([](Text& x) { kmdb_distance_out_free(&x.o); });
+        }
+    };
+
+    // the first cell of the first row taken, through a probe of its own: num-kmers is the count itself, and only a count of 0 is written "0"
+    auto first_cell_is_zero = [&](const uint32_t* a, const char* const* names) {
+        if (n == 0) return true;
+        DistanceSetup ps = s;
+        ps.measure = KMDB_METRIC_NUM_KMERS; ps.filters.clear();
+        DistanceHandle probe;
+        probe.begin(ps, 0);
+        check(kmdb_distance_take_rows_device(probe.d, kmdb_distance_cells_device(tables[0]->h.d), 1, a, names));
+        Text x;
+        check(kmdb_distance_query_rows(probe.d, 0, 1, &x.o));
+        const size_t at = std::strlen(names[0]) + 1;
+        const bool zero = x.o.len > at + 1 && x.o.text[at] == '0' && x.o.text[at + 1] == ',';
+        kmdb_distance_out_free(&x.o);
+        return zero;
+    };
+
+    std::cerr << "Processing queries..." << std::endl;
+    auto total0 = clk::now();
+    std::vector<Query> batch;
+    bool first_take = true;
+    uint64_t n_queries = 0;
+    auto flush = [&]() {
+        if (batch.empty()) return;
+        std::vector<size_t> halves[2];                             // [0] k-mer lists (-host-extract, -from-minhash, long genomes), [1] sequence text
+        for (size_t q = 0; q < batch.size(); ++q) halves[batch[q].from_kmers ? 0 : 1].push_back(q);
+        // the text of every table, as pieces of consecutive queries keyed by the first one's place in the batch
+        std::vector<std::map<size_t, Text>> pieces(tables.size());
+        try {
+            for (int half = 0; half < 2; ++half) {
+                const std::vector<size_t>& idx = halves[half];
+                if (idx.empty()) continue;
+                const size_t nq = idx.size();
+                std::vector<const char*> names(nq);
+                std::vector<uint32_t> a(nq);
+                for (size_t t = 0; t < nq; ++t) names[t] = batch[idx[t]].name.c_str();
+                if (half == 0) {
+                    std::vector<const uint64_t*> ptrs(nq);
+                    std::vector<size_t> kc(nq);
+                    for (size_t t = 0; t < nq; ++t) { ptrs[t] = batch[idx[t]].kmers.data(); kc[t] = batch[idx[t]].kmers.size(); a[t] = (uint32_t)kc[t]; }
+                    check(kmdb_distance_take_new2all_batch(tables[0]->h.d, db.d, ptrs.data(), kc.data(), nq, names.data(), &o));
+                } else {
+                    std::vector<const char*> ptrs(nq);
+                    std::vector<size_t> lens(nq);
+                    std::vector<uint64_t> uniq(nq);
+                    for (size_t t = 0; t < nq; ++t) { ptrs[t] = batch[idx[t]].text.data(); lens[t] = batch[idx[t]].text.size(); }
+                    check(kmdb_distance_take_new2all_batch_seq_alphabet(tables[0]->h.d, db.d, ptrs.data(), lens.data(), nq, fraction, fstart, alphabet, names.data(), uniq.data(), &o));
+                    for (size_t t = 0; t < nq; ++t) a[t] = (uint32_t)uniq[t];
+                }
+                // the triangle rule, from query 0 of the run (dense and phylip forms only)
+                if (first_take && idx[0] == 0 && !sparse && n > 0 && batch[0].name == sample_names[0] && first_cell_is_zero(a.data(), names.data()))
+                    throw std::runtime_error("new2all -distance: the first query, " + batch[0].name + ", is named like the first sample of the database, " + sample_names[0]
+                                             + ", and shares no k-mer with it: the distance mode takes such a table for a triangle and cuts its rows; run new2all and distance");
+                for (size_t ti = 0; ti < tables.size(); ++ti) {
+                    kmdb_distance* h = tables[ti]->h.d;
+                    if (ti) check(kmdb_distance_take_rows_device(h, kmdb_distance_cells_device(tables[0]->h.d), nq, a.data(), names.data()));
+                    // pieces: rows of the half that follow each other in the batch, within the budget of cells
+                    const uint64_t rows_max = std::max<uint64_t>(1, budget / std::max<uint64_t>(n, 1));
+                    for (size_t r0 = 0; r0 < nq;) {
+                        size_t r1 = r0 + 1;
+                        while (r1 < nq && idx[r1] == idx[r1 - 1] + 1 && r1 - r0 < rows_max) ++r1;
+                        Text x;
+                        check(kmdb_distance_query_rows(h, r0, r1, &x.o));
+                        pieces[ti][idx[r0]] = x;
+                        r0 = r1;
+                    }
+                }
+            }
+        } catch (...) {
+            for (auto& m : pieces) for (auto& kv : m) kmdb_distance_out_free(&kv.second.o);
+            throw;
+        }
+        first_take = false;
+        open_tables();
+        for (size_t ti = 0; ti < tables.size(); ++ti)
+            for (auto& kv : pieces[ti]) {
+                Text x = kv.second;
+                kv.second.o = kmdb_distance_out{};
+                if (!tables[ti]->texts.push(std::move(x))) kmdb_distance_out_free(&x.o);
+            }
+        n_queries += batch.size();
+        batch.clear();
+    };
+    try {
+        new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads}, batch, flush);
+        open_tables();                                             // (no query at all: the header lines alone, as the two commands write them)
+    } catch (...) {
+        stop_tables(false);
+        throw;
+    }
+    stop_tables(true);
+    for (auto& tp : tables) {
+        tp->ofs.close();
+        if (tp->write_failed || !tp->ofs) throw std::runtime_error("Cannot write the output file " + tp->path);
+        std::cerr << "Stored the " << tp->measure << " table of " << n_queries << " queries in " << tp->path << std::endl;
+        if (std::getenv("KMDB_VERBOSE")) {
+            kmdb_distance_stats st{};
+            if (!kmdb_distance_stats_get(tp->h.d, &st))
+                std::cerr << "[kmdb] distance from the query rows: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
+                          << ", host cells " << st.host_cells << ", bytes out " << st.bytes_out << ", measure " << st.measure_ms << " ms, format " << st.format_ms
+                          << " ms, copies " << st.copy_ms << " ms" << std::endl;
+        }
+    }
+    std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
+    return 0;
+}
+
 int run_distance(std::vector<std::string>& args, const Common& c) {
     const bool host_only = take_switch(args, "-host");
     bool sparse_out = take_switch(args, "-sparse");
@@ -1959,7 +2204,12 @@ void usage() {
                  "                                  writes, without the table of counts in between; all2all-sp forces -sparse.  Several -distance: one all2all\n"
                  "                                  run, a file <output>.<measure> each.  -min / -max are read as the DISTANCE mode reads them here: a bare\n"
                  "                                  bound belongs to <measure> (NOT to num-kmers as in all2all -sparse), num-kmers:<v> bounds the count.\n"
-                 "                                  Refused with -gpus <N> and with -sample-rows.\n";
+                 "                                  Refused with -gpus <N> and with -sample-rows.\n"
+                 "    kmer-db-amd new2all [-sparse] [-phylip-out] [-min ...]* [-max ...]* [-multisample-fasta | -from-minhash] [-host-extract] -distance <measure> [-distance <measure>]* <database> <sample_list> <output>\n"
+                 "new2all -distance:               the table of <measure> straight from the query rows on the GPU: the file `new2all` followed by `distance`\n"
+                 "                                  writes, without the table of counts in between; several -distance and the -min / -max list as above.\n"
+                 "                                  Refused with -gpus <N>, and where the distance mode would take the table for a triangle (the first query\n"
+                 "                                  named like the first sample and sharing no k-mer with it; -sparse is not affected).\n";
 }
 
 }  // namespace
