@@ -53,6 +53,10 @@ extern "C" {
  * accumulated (kmdb_distance_take_new2all_batch, kmdb_distance_take_new2all_batch_seq_alphabet, kmdb_distance_take_rows_device,
  * kmdb_distance_query_rows): four more entry points, no struct changed, the version stays 8. */
 #define KMDB_HAS_DISTANCE_QUERY_ROWS 1
+/* And the -sample-rows selection on an off-diagonal cell of the all2all-parts grid: the candidates of a rectangle of two sample sets chosen in
+ * HBM (kmdb_db2db_sampled, kmdb_sampled_from_rect_device, kmdb_db2db_sample_stats_get): three more entry points, no struct changed, the version
+ * stays 8. */
+#define KMDB_HAS_DB2DB_SAMPLED 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -427,6 +431,34 @@ typedef struct kmdb_db2db_stats {  /* the LAST kmdb_db2db_* call with this handl
     double   compact_ms;           /* HIP events around flags + count + scan + compact (kmdb_stats.kernel_ms holds the whole call) */
 } kmdb_db2db_stats;
 int  kmdb_db2db_stats_get(const kmdb_db* db_row, kmdb_db2db_stats* out);
+/* Replaces db2db_sp + SparseMatrix::compact2(filter) + SparseMatrix::add_to_sampler for an off-diagonal cell of the all2all-parts grid under
+ * -sample-rows <criterion>:<count> (console_all2all_parts.cpp:179-195 and 225-241: db2db_sp at :180 / :226, compact2(filter) and add_to_sampler
+ * right after it; array.h:391-446, 450-540; sampler.h).  The cell is accumulated in HBM as for kmdb_db2db_dense, its tile flags are made as for
+ * kmdb_db2db_sparse_filtered (KMDB_SP_ALL_TILES=1 reads every tile), and the radix select of kmdb_all2all_sampled runs on the flagged tiles of the
+ * rectangle: neither the cell nor anything proportional to its non-zeros reaches the host.
+ * A pair (r, c) has ONE score, with a = row_sample_kmers[r], the ROW sample's k-mer count, and b = col_sample_kmers[c], the COLUMN sample's, and
+ * is offered to row sample r and to column sample c (mash-query tells the two apart; the bounds use the same a and b).
+ * out_row_candidates: n_samples(db_row) rows, cols local to db_col; out_col_candidates: n_samples(db_col) rows, cols local to db_row.  Both as
+ * kmdb_sampled_from_dense_device gives them: ascending columns, val = common k-mers, no measures — per sample a superset of its `count` best
+ * cells of this cell by the exact decision, filters included (rows the margin cannot settle are fetched again whole inside the call).  A sample's
+ * best `count` within a cell is a superset of its share of the global best `count`, so the candidates of all cells of a grid — with their local
+ * ids shifted to global ones — go to kmdbh_sample_rows_select, or to any exact sampler, together.
+ * Refused before any device work: NULL handles / outs, count 0, an unknown criterion, a missing count array (both are required), an unknown
+ * metric in a filter, more than 12 bounds; everything kmdb_db2db_dense refuses (no hashtables, a query shard, different k-mer lengths or
+ * devices, its size limits); and 2^31 - 2 samples in the two sets or 2^31 tiles of 64 x 64 cells, the select's 31-bit sizes. */
+int  kmdb_db2db_sampled(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters,
+                        const uint32_t* row_sample_kmers /* [nr] */, const uint32_t* col_sample_kmers /* [nc] */, int criterion, uint32_t count,
+                        kmdb_sparse_rows* out_row_candidates, kmdb_sparse_rows* out_col_candidates, const kmdb_opts* opts);
+/* The same on a rectangle the CALLER accumulated: cells_dev = nr x nc uint32 in device memory, row-major (cell (r, c) at r * nc + c), every tile
+ * read.  db gives the device, the stream and the k-mer length, as in kmdb_sampled_from_dense_device, and the stream note of
+ * kmdb_sparse_from_dense_device applies: the cells must be complete on opts->stream (the handle's own when NULL) before the call. */
+int  kmdb_sampled_from_rect_device(kmdb_db* db, const void* cells_dev, uint64_t nr, uint64_t nc, const kmdb_cell_filter* filters, size_t n_filters,
+                                   const uint32_t* row_sample_kmers, const uint32_t* col_sample_kmers, int criterion, uint32_t count,
+                                   kmdb_sparse_rows* out_row_candidates, kmdb_sparse_rows* out_col_candidates, const kmdb_opts* opts);
+/* The LAST kmdb_db2db_sampled call with this handle as the ROW database (or kmdb_sampled_from_rect_device call on it): the fields of
+ * kmdb_sample_stats over the nr + nc lines of the cell — candidates of both outputs, rows truncated / re-fetched on either side, triangle_reads =
+ * passes over the cell's touched tiles.  The tile counts of that call are in kmdb_db2db_stats_get (tiles, tiles_touched). */
+int  kmdb_db2db_sample_stats_get(const kmdb_db* db_row, kmdb_sample_stats* out);
 
 /* ---------------------------------------------------------------------------------------
  * One database over the GPUs of a node (north_star: prefix buckets sharded across the GPUs, one RCCL reduce of the

@@ -144,6 +144,7 @@ EXPORTS = [
     "kmdbh_format_header", "kmdbh_format_dense_row", "kmdbh_format_sparse_row",
     "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
     "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
+    "kmdb_db2db_sampled", "kmdb_sampled_from_rect_device", "kmdb_db2db_sample_stats_get",
     "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
@@ -221,6 +222,11 @@ def lib():
     L.kmdb_db2db_sparse_filtered.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Sparse),
                                              C.POINTER(_Opts)]
     L.kmdb_db2db_stats_get.argtypes = [C.c_void_p, C.POINTER(_Db2dbStats)]
+    L.kmdb_db2db_sampled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse),
+                                     C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_sampled_from_rect_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_db2db_sample_stats_get.argtypes = [C.c_void_p, C.POINTER(_SampleStats)]
     for name in ("kmdb_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_sparse_filtered"):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
                                      C.POINTER(_Sparse), C.POINTER(_Opts)]
@@ -722,6 +728,43 @@ class DeviceDB:
         s = _Db2dbStats()
         _check(lib().kmdb_db2db_stats_get(self._d, C.byref(s)))
         return {f: getattr(s, f) for f, _ in _Db2dbStats._fields_}
+
+    def db2db_sampled(self, col, criterion, count, row_kmers, col_kmers, filters=()):
+        """kmdb_db2db_sampled: the -sample-rows candidates of the cell (this database's samples = rows, `col`'s = columns), selected on the device.
+        Returns (row candidates: self.N rows with ids local to `col`, column candidates: col.N rows with ids local to this database) — no
+        measures; a = the row sample's k-mer count, b = the column sample's."""
+        rows, cols = _Sparse(), _Sparse()
+        o = _opts(self.device)
+        rk = None if row_kmers is None else np.ascontiguousarray(row_kmers, np.uint32)
+        ck = None if col_kmers is None else np.ascontiguousarray(col_kmers, np.uint32)
+        _check(lib().kmdb_db2db_sampled(self._d, col._d, _filters(filters), len(filters), None if rk is None else rk.ctypes.data,
+                                        None if ck is None else ck.ctypes.data, _criterion(criterion), int(count), C.byref(rows), C.byref(cols), C.byref(o)))
+        try:
+            return SparseRows(rows), SparseRows(cols)
+        finally:
+            lib().kmdb_sparse_free(C.byref(rows))
+            lib().kmdb_sparse_free(C.byref(cols))
+
+    def sampled_from_rect_device(self, dev_ptr, nr, nc, criterion, count, row_kmers, col_kmers, filters=(), stream=None):
+        """kmdb_sampled_from_rect_device: the same on a caller-accumulated row-major nr x nc uint32 rectangle in device memory at dev_ptr."""
+        rows, cols = _Sparse(), _Sparse()
+        o = _opts(self.device, stream=stream)
+        rk = None if row_kmers is None else np.ascontiguousarray(row_kmers, np.uint32)
+        ck = None if col_kmers is None else np.ascontiguousarray(col_kmers, np.uint32)
+        _check(lib().kmdb_sampled_from_rect_device(self._d, C.c_void_p(dev_ptr), int(nr), int(nc), _filters(filters), len(filters),
+                                                   None if rk is None else rk.ctypes.data, None if ck is None else ck.ctypes.data, _criterion(criterion),
+                                                   int(count), C.byref(rows), C.byref(cols), C.byref(o)))
+        try:
+            return SparseRows(rows), SparseRows(cols)
+        finally:
+            lib().kmdb_sparse_free(C.byref(rows))
+            lib().kmdb_sparse_free(C.byref(cols))
+
+    def db2db_sample_stats(self):
+        """kmdb_db2db_sample_stats_get: the last sampled db2db (or rectangle) call with this handle as the row database"""
+        s = _SampleStats()
+        _check(lib().kmdb_db2db_sample_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
 
     def new2all_seq(self, seqs, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
         """queries given as sequence text (bytes / str); k-mer extraction, minhash filter, sort + unique on the device.

@@ -22,6 +22,11 @@
 //   flags    one byte per 64 x 64 tile of the cell, set from the key words of the emit pool: the tiles that received a block record
 //   compact  one wave per row over the flagged tiles of its row block: widened bounds (cell_filter.h), per-row counts, exclusive sum,
 //            (col, val) in ascending columns; the exact decision is the host's (kmdb_sparse_decide, engine.hip)
+// kmdb_db2db_sampled (db2db_sp + compact2(filter) + SparseMatrix::add_to_sampler of an off-diagonal cell with -sample-rows <criterion>:<count>,
+// src/console_all2all_parts.cpp:179-195, 225-241; src/array.h:450-540) keeps the cell in HBM as well and selects there:
+//   flags    as above
+//   select   the radix select of sample_rows.hip on the flagged tiles of the rectangle: per row sample and per column sample a superset of its
+//            `count` best cells of this cell (kmdb_sample_rect, engine.hip: selection, completeness rule, re-fetch)
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
 #include "engine_internal.h"
@@ -373,11 +378,20 @@ struct D2Sparse {
     int measure;
     kmdb_sparse_rows* out;
 };
-static int db2db_impl(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts, bool allow_store);
+// what the sampled entry asks of the call (nullptr: one of the other two)
+struct D2Sampled {
+    const kmdb_cell_filter* filters;
+    size_t n_filters;
+    const uint32_t *row_kmers, *col_kmers;
+    int criterion;
+    uint32_t count;
+    kmdb_sparse_rows *out_row, *out_col;
+};
+static int db2db_impl(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const D2Sampled* sm, const kmdb_opts* opts, bool allow_store);
 
 // the call, and once more without the handles' list stores when it ran out of HBM
-static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts) {
-    int rc = db2db_impl(who, db_row, db_col, out, sp, opts, true);
+static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const D2Sampled* sm, const kmdb_opts* opts) {
+    int rc = db2db_impl(who, db_row, db_col, out, sp, sm, opts, true);
     if (rc && std::strstr(kmdb_last_error(), hipGetErrorString(hipErrorOutOfMemory))) {
         // out of HBM inside the call: the handles' list stores (up to 8 GB each) are the part that can go — the pairs' lists are then built
         // by climbing, as on handles that never had a store — and the call is tried once more
@@ -395,7 +409,7 @@ static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_
         (void)hipGetLastError();
         if (freed) {
             if (getenv("KMDB_VERBOSE")) fprintf(stderr, "[kmdb] db2db: out of device memory; list stores dropped, the call is repeated on the climbing path\n");
-            rc = db2db_impl(who, db_row, db_col, out, sp, opts, false);
+            rc = db2db_impl(who, db_row, db_col, out, sp, sm, opts, false);
         }
     }
     return rc;
@@ -403,7 +417,7 @@ static int db2db_call(const char* who, kmdb_db* db_row, kmdb_db* db_col, uint32_
 
 extern "C" int kmdb_db2db_dense(kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const kmdb_opts* opts) {
     if (!db_row || !db_col || !out) return kmdb_set_error("kmdb_db2db_dense: null argument");
-    return db2db_call("kmdb_db2db_dense", db_row, db_col, out, nullptr, opts);
+    return db2db_call("kmdb_db2db_dense", db_row, db_col, out, nullptr, nullptr, opts);
 }
 
 extern "C" int kmdb_db2db_sparse_filtered(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters,
@@ -415,12 +429,27 @@ extern "C" int kmdb_db2db_sparse_filtered(kmdb_db* db_row, kmdb_db* db_col, cons
     if (kmdb_check_filters(who, filters, n_filters, row_sample_kmers && col_sample_kmers ? row_sample_kmers : nullptr, measure)) return 1;
     std::memset(out, 0, sizeof *out);
     const D2Sparse sp{filters, n_filters, row_sample_kmers, col_sample_kmers, measure, out};
-    const int rc = db2db_call(who, db_row, db_col, nullptr, &sp, opts);
+    const int rc = db2db_call(who, db_row, db_col, nullptr, &sp, nullptr, opts);
     if (rc) kmdb_sparse_free(out);
     return rc;
 }
 
-static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const kmdb_opts* opts, bool allow_store) {
+extern "C" int kmdb_db2db_sampled(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_sample_kmers,
+                                  const uint32_t* col_sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out_row_candidates,
+                                  kmdb_sparse_rows* out_col_candidates, const kmdb_opts* opts) {
+    const char* who = "kmdb_db2db_sampled";
+    if (!db_row || !db_col || !out_row_candidates || !out_col_candidates) return kmdb_set_error(std::string(who) + ": null argument");
+    // (the proxy and the bounds need the k-mer counts of both sides: a = the row sample's, b = the column sample's)
+    if (kmdb_check_sample_args(who, filters, n_filters, row_sample_kmers && col_sample_kmers ? row_sample_kmers : nullptr, criterion, count)) return 1;
+    std::memset(out_row_candidates, 0, sizeof *out_row_candidates);
+    std::memset(out_col_candidates, 0, sizeof *out_col_candidates);
+    const D2Sampled sm{filters, n_filters, row_sample_kmers, col_sample_kmers, criterion, count, out_row_candidates, out_col_candidates};
+    const int rc = db2db_call(who, db_row, db_col, nullptr, nullptr, &sm, opts);
+    if (rc) { kmdb_sparse_free(out_row_candidates); kmdb_sparse_free(out_col_candidates); }
+    return rc;
+}
+
+static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32_t* out, const D2Sparse* sp, const D2Sampled* sm, const kmdb_opts* opts, bool allow_store) {
     const std::string who(who_);
     kmdb_engine_view er, ec;
     if (kmdb_engine_get(db_row, &er)) return 1;
@@ -435,6 +464,7 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     HIP_TRY(hipSetDevice(er.device));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : (hipStream_t)er.stream;
     const uint64_t nr = er.N, nc = ec.N;
+    if (sm && kmdb_sample_rect_check(who_, nr, nc)) return 1;
     uint64_t n_slots = 0;
     HIP_TRY(hipMemcpy(&n_slots, ec.bucket_offset + ec.n_buckets, 8, hipMemcpyDeviceToHost));
     if (n_slots >= (1ull << 31)) return kmdb_set_error(who + ": column database has more than 2^31 hashtable slots");
@@ -443,13 +473,14 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     DEV_ALLOC_BYTES(d_cnt, (n_slots + 1) * 4); DEV_ALLOC_BYTES(d_nruns, 16); DEV_ALLOC_BYTES(d_out, nr * nc * 4); DEV_ALLOC_BYTES(d_flag, 16);
     HIP_TRY(hipMemsetAsync(d_out.get(), 0, std::max<uint64_t>(nr * nc * 4, 4), st));
     HIP_TRY(hipMemsetAsync(d_flag.get(), 0, 16, st));
-    // the cell in tiles of 64 x 64; sparse entry: one flag byte per tile (KMDB_SP_ALL_TILES=1: every tile counts as touched, as for all2all-sp — A/B)
+    // the cell in tiles of 64 x 64; sparse and sampled entries: one flag byte per tile (KMDB_SP_ALL_TILES=1: every tile counts as touched, as for all2all-sp — A/B)
     const uint32_t nbr = (uint32_t)((nr + 63) / 64), nbc = (uint32_t)((nc + 63) / 64);
     const uint64_t n_tiles = (uint64_t)nbr * nbc;
-    const bool all_tiles = sp && getenv("KMDB_SP_ALL_TILES");
+    const bool tile_flags = sp || sm;
+    const bool all_tiles = tile_flags && getenv("KMDB_SP_ALL_TILES");
     bool any_records = false, flags_timed = false;
     DevBuf<void> d_tiles;
-    if (sp) {
+    if (tile_flags) {
         DEV_ALLOC_BYTES(d_tiles, n_tiles);
         HIP_TRY(hipMemsetAsync(d_tiles.get(), all_tiles ? 1 : 0, std::max<uint64_t>(n_tiles, 1), st));
     }
@@ -570,7 +601,7 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
             }
             phase("pool + emit");
             any_records = true;
-            if (sp && !all_tiles) {
+            if (tile_flags && !all_tiles) {
                 // the tiles this call adds to, from the pool's key words (before the sort takes the pool)
                 HIP_TRY(hipEventRecord(ev1, st));
                 hipLaunchKernelGGL(d2_tile_flags_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, static_cast<uint32_t*>(d_wkey.get()), (uint32_t)slots,
@@ -586,6 +617,32 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     kmdb_db2db_stats& ds = *er.d2_stats;
     ds = kmdb_db2db_stats{};
     ds.tiles = n_tiles;
+    if (sm) {
+        // ---- the sampled entry: the cell stays in d_out and the select reads its flagged tiles there (a cell without a single block record has
+        // no flagged tile: every line comes out empty)
+        std::vector<unsigned char> h_tiles(n_tiles, 0);
+        if (n_tiles) HIP_TRY(hipMemcpyAsync(h_tiles.data(), d_tiles.get(), n_tiles, hipMemcpyDeviceToHost, st));
+        kmdb_sample_stats ss{};
+        *er.d2_sample_stats = ss;
+        if (kmdb_sample_rect(who_, st, (int)er.kmer_length, static_cast<uint32_t*>(d_out.get()), nr, nc, static_cast<unsigned char*>(d_tiles.get()), sm->filters,
+                             sm->n_filters, sm->row_kmers, sm->col_kmers, sm->criterion, sm->count, sm->out_row, sm->out_col, &ss)) return 1;
+        HIP_TRY(hipEventRecord(ev3, st));
+        HIP_TRY(hipEventSynchronize(ev3));
+        float ms = 0, ms_flags = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev3));
+        if (flags_timed) HIP_TRY(hipEventElapsedTime(&ms_flags, ev1, ev2));
+        kmdb_engine_set_times(db_row, ms, ms);
+        uint32_t too_long = 0;
+        HIP_TRY(hipMemcpy(&too_long, d_flag.get(), 4, hipMemcpyDeviceToHost));
+        if (too_long) return kmdb_set_error(who + ": internal error");
+        for (unsigned char t : h_tiles) ds.tiles_touched += t != 0;
+        ss.select_ms += (double)ms_flags;
+        ds.nnz_device = ds.nnz = ss.candidates;
+        ds.d2h_bytes = ss.d2h_bytes;
+        ds.compact_ms = ss.select_ms;
+        *er.d2_sample_stats = ss;
+        return 0;
+    }
     if (!sp) {
         HIP_TRY(hipEventRecord(ev3, st));
         HIP_TRY(hipEventSynchronize(ev3));

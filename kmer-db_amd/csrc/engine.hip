@@ -318,7 +318,7 @@ int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* o) {
     o->pid2dfs = db->pid2dfs; o->qs_index = db->qs_index; o->qs_count = db->qs_count; o->stream = db->stream;
     o->max_depth = db->max_depth; o->list_sets = &db->list_sets; o->list_sets_nb = &db->list_sets_nb; o->list_sets_tried = &db->list_sets_tried;
     o->rl_ofs = &db->rl_ofs; o->rl_runs = &db->rl_runs; o->rl_node = &db->rl_node; o->rl_tried = &db->rl_tried;
-    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats; o->n2s_stats = &db->n2s_stats;
+    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats; o->d2_sample_stats = &db->d2_sample_stats; o->n2s_stats = &db->n2s_stats;
     for (int i = 0; i < 4; ++i) o->ev[i] = db->ev[i];
     return 0;
 }
@@ -721,6 +721,98 @@ int check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n
     return kmdb_check_filters(who, filters, n_filters, sample_kmers, -1);
 }
 
+// The selection and its completeness rule over the lines of a job's slots (the symmetric rows of a triangle; the row and column lines of a
+// rectangle): sel.res holds every line, sel.whole the lines of sel.again (ascending slots) fetched again whole.  ab(s, o, a, b): the k-mer counts
+// of the ROW sample (a) and the COLUMN sample (b) of the cell that line s lists under the id o.
+struct SampleSelection { kmdb_sample_result res, whole; std::vector<uint32_t> again; };
+template <class AB>
+int select_complete(hipStream_t st, const kmdb_sample_job& job, uint64_t n_slots, Proxy px, uint32_t count, int k, const kmdb_cell_filter* filters, size_t n_filters,
+                    AB&& ab, kmdb_sample_stats& ss, SampleSelection& sel) {
+    kmdb_sample_result& res = sel.res;
+    if (kmdb_sample_candidates(st, job, nullptr, 0, &res)) return 1;
+    ss.rows_truncated = res.rows_truncated; ss.d2h_bytes = res.d2h_bytes; ss.select_ms = res.select_ms; ss.triangle_reads = res.passes;
+    // Completeness.  A row that came out whole is decided.  A truncated row holds every cell whose key is >= the key of T_s, its count-th best
+    // proxy, less the margin: when `count` of its candidates at or above T_s pass the EXACT filters, no cell the device held back can be among
+    // the row's best.  T_s is recomputed here from the candidates (they include all cells at or above it).  A row of fewer than `count`
+    // candidates was not truncated; without filters every candidate passes.
+    std::vector<uint32_t>& again = sel.again;
+    if (n_filters) {
+        std::vector<uint32_t> keys;
+        for (uint64_t s = 0; s < n_slots; ++s) {
+            const uint64_t b = res.row_ptr[s], e = res.row_ptr[s + 1];
+            if (e - b < count) continue;
+            keys.clear();
+            for (uint64_t x = b; x < e; ++x) {
+                uint32_t ca, cb;
+                ab(s, res.col[x], ca, cb);
+                keys.push_back(kmdb_sample_proxy_key(host_proxy(px, res.val[x], ca, cb)));
+            }
+            std::vector<uint32_t> sorted(keys);
+            std::nth_element(sorted.begin(), sorted.begin() + (count - 1), sorted.end(), std::greater<uint32_t>());
+            const uint32_t T = sorted[count - 1];
+            uint64_t ok = 0;
+            for (uint64_t x = b; x < e && ok < count; ++x) {
+                if (keys[x - b] < T) continue;
+                uint32_t ca, cb;
+                ab(s, res.col[x], ca, cb);
+                bool pass = true;
+                for (size_t q = 0; q < n_filters && pass; ++q) {
+                    const double v = kmdbh_metric(filters[q].metric, res.val[x], ca, cb, k);
+                    pass = v >= filters[q].lo && v <= filters[q].hi;
+                }
+                ok += pass ? 1 : 0;
+            }
+            if (ok < count) again.push_back((uint32_t)s);
+        }
+    }
+    if (!again.empty()) {
+        if (kmdb_sample_candidates(st, job, again.data(), again.size(), &sel.whole)) return 1;
+        ss.rows_refetched = again.size(); ss.d2h_bytes += sel.whole.d2h_bytes; ss.select_ms += sel.whole.select_ms; ss.triangle_reads += sel.whole.passes;
+    }
+    return 0;
+}
+// the lines of the slots [s_lo, s_hi) as the rows of `out`, a re-fetched line in place of its first form
+int pack_slots(const char* who, const SampleSelection& sel, uint64_t s_lo, uint64_t s_hi, kmdb_sparse_rows* out) {
+    const std::vector<uint32_t>& again = sel.again;
+    const size_t a_lo = (size_t)(std::lower_bound(again.begin(), again.end(), s_lo) - again.begin());
+    const uint64_t n = s_hi - s_lo;
+    uint64_t nnz = 0;
+    {
+        size_t a = a_lo;
+        for (uint64_t s = s_lo; s < s_hi; ++s) {
+            const bool re = a < again.size() && again[a] == s;
+            if (re) ++a;
+            const kmdb_sample_result& r = re ? sel.whole : sel.res;
+            nnz += r.row_ptr[s + 1] - r.row_ptr[s];
+        }
+    }
+    out->n_rows = n; out->nnz = nnz;
+    out->row_ptr = (uint64_t*)std::malloc((n + 1) * 8);
+    out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+    out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
+    if (!out->row_ptr || !out->col || !out->val) { kmdb_sparse_free(out); return kmdb_set_error(std::string(who) + ": out of host memory for the result"); }
+    uint64_t w = 0;
+    size_t a = a_lo;
+    for (uint64_t s = s_lo; s < s_hi; ++s) {
+        out->row_ptr[s - s_lo] = w;
+        const bool re = a < again.size() && again[a] == s;
+        if (re) ++a;
+        const kmdb_sample_result& r = re ? sel.whole : sel.res;
+        const uint64_t b = r.row_ptr[s], m = r.row_ptr[s + 1] - b;
+        if (m) { std::memcpy(out->col + w, r.col.data() + b, m * 4); std::memcpy(out->val + w, r.val.data() + b, m * 4); }
+        w += m;
+    }
+    out->row_ptr[n] = w;
+    return 0;
+}
+void job_bounds(kmdb_sample_job& job, const kmdb_cell_filter* filters, size_t n_filters, int k) {
+    job.n_bounds = n_filters;
+    for (size_t i = 0; i < n_filters; ++i) {
+        const RatioBound rb = ratio_bound(filters[i], k);
+        job.bound_kind[i] = rb.kind; job.bound_lo[i] = rb.lo; job.bound_hi[i] = rb.hi;
+    }
+}
+
 // The candidates of the symmetric rows of the cells [cell_lo, cell_hi) — complete: every row holds its `count` best cells by the exact decision
 // among the cells of the range (rows the margin band could not settle are fetched again whole).
 int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dense_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
@@ -737,11 +829,8 @@ int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dens
     const int k = (int)db->kmer_length;
     const Proxy px = proxy_of(criterion);
     kmdb_sample_job job;
-    job.N = N; job.counts_dev = d_counts; job.kind = px.kind; job.flip = px.flip; job.count = count; job.n_bounds = n_filters;
-    for (size_t i = 0; i < n_filters; ++i) {
-        const RatioBound rb = ratio_bound(filters[i], k);
-        job.bound_kind[i] = rb.kind; job.bound_lo[i] = rb.lo; job.bound_hi[i] = rb.hi;
-    }
+    job.N = N; job.counts_dev = d_counts; job.kind = px.kind; job.flip = px.flip; job.count = count;
+    job_bounds(job, filters, n_filters, k);
     if (!from_cells) {
         if (run_dense(db, M, opts, st)) return 1;
         job.cells = M; job.cell_lo = 0; job.cell_hi = cells;
@@ -756,76 +845,14 @@ int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dens
     kmdb_sample_stats& ss = db->sample_stats;
     ss = kmdb_sample_stats{};
     try {
-        kmdb_sample_result res;
-        if (kmdb_sample_candidates(st, job, nullptr, 0, &res)) return 1;
-        ss.rows_truncated = res.rows_truncated; ss.d2h_bytes = res.d2h_bytes; ss.select_ms = res.select_ms; ss.triangle_reads = res.passes;
-        // Completeness.  A row that came out whole is decided.  A truncated row holds every cell whose key is >= the key of T_s, its count-th best
-        // proxy, less the margin: when `count` of its candidates at or above T_s pass the EXACT filters, no cell the device held back can be among
-        // the row's best.  T_s is recomputed here from the candidates (they include all cells at or above it).  A row of fewer than `count`
-        // candidates was not truncated; without filters every candidate passes.
-        std::vector<uint32_t> again;
-        if (n_filters) {
-            std::vector<uint32_t> keys;
-            for (uint64_t s = 0; s < N; ++s) {
-                const uint64_t b = res.row_ptr[s], e = res.row_ptr[s + 1];
-                if (e - b < count) continue;
-                keys.clear();
-                for (uint64_t x = b; x < e; ++x) {
-                    const uint32_t o = res.col[x];
-                    keys.push_back(kmdb_sample_proxy_key(host_proxy(px, res.val[x], sample_kmers[std::max<uint64_t>(s, o)], sample_kmers[std::min<uint64_t>(s, o)])));
-                }
-                std::vector<uint32_t> sorted(keys);
-                std::nth_element(sorted.begin(), sorted.begin() + (count - 1), sorted.end(), std::greater<uint32_t>());
-                const uint32_t T = sorted[count - 1];
-                uint64_t ok = 0;
-                for (uint64_t x = b; x < e && ok < count; ++x) {
-                    if (keys[x - b] < T) continue;
-                    const uint32_t o = res.col[x], a = sample_kmers[std::max<uint64_t>(s, o)], bb = sample_kmers[std::min<uint64_t>(s, o)];
-                    bool pass = true;
-                    for (size_t q = 0; q < n_filters && pass; ++q) {
-                        const double v = kmdbh_metric(filters[q].metric, res.val[x], a, bb, k);
-                        pass = v >= filters[q].lo && v <= filters[q].hi;
-                    }
-                    ok += pass ? 1 : 0;
-                }
-                if (ok < count) again.push_back((uint32_t)s);
-            }
-        }
-        kmdb_sample_result whole;
-        if (!again.empty()) {
-            if (kmdb_sample_candidates(st, job, again.data(), again.size(), &whole)) return 1;
-            ss.rows_refetched = again.size(); ss.d2h_bytes += whole.d2h_bytes; ss.select_ms += whole.select_ms; ss.triangle_reads += whole.passes;
-        }
+        SampleSelection sel;
+        // (the pair's one score has the triangle's row, the larger id, as the row sample)
+        auto ab = [&](uint64_t s, uint32_t o, uint32_t& a, uint32_t& b) { a = sample_kmers[std::max<uint64_t>(s, o)]; b = sample_kmers[std::min<uint64_t>(s, o)]; };
+        if (select_complete(st, job, N, px, count, k, filters, n_filters, ab, ss, sel)) return 1;
         if (finish_stats(db, st)) return 1;
         kmdb_release_staging(db);
-        uint64_t nnz = 0;
-        {
-            size_t a = 0;
-            for (uint64_t s = 0; s < N; ++s) {
-                const bool re = a < again.size() && again[a] == s;
-                if (re) ++a;
-                const kmdb_sample_result& r = re ? whole : res;
-                nnz += r.row_ptr[s + 1] - r.row_ptr[s];
-            }
-        }
-        out->n_rows = N; out->nnz = nnz;
-        out->row_ptr = (uint64_t*)std::malloc((N + 1) * 8);
-        out->col = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
-        out->val = (uint32_t*)std::malloc(std::max<uint64_t>(nnz, 1) * 4);
-        if (!out->row_ptr || !out->col || !out->val) { kmdb_sparse_free(out); return kmdb_set_error(std::string(who) + ": out of host memory for the result"); }
-        uint64_t w = 0;
-        size_t a = 0;
-        for (uint64_t s = 0; s < N; ++s) {
-            out->row_ptr[s] = w;
-            const bool re = a < again.size() && again[a] == s;
-            if (re) ++a;
-            const kmdb_sample_result& r = re ? whole : res;
-            const uint64_t b = r.row_ptr[s], n = r.row_ptr[s + 1] - b;
-            if (n) { std::memcpy(out->col + w, r.col.data() + b, n * 4); std::memcpy(out->val + w, r.val.data() + b, n * 4); }
-            w += n;
-        }
-        out->row_ptr[N] = w;
-        ss.candidates = nnz;
+        if (pack_slots(who, sel, 0, N, out)) return 1;
+        ss.candidates = out->nnz;
         return 0;
     } catch (const std::exception& e) {
         kmdb_sparse_free(out);
@@ -833,6 +860,80 @@ int sampled_impl(const char* who, kmdb_db* db, bool from_cells, const void* dens
     }
 }
 }  // namespace
+
+// The same on a row-major nr x nc rectangle of two sample sets in HBM (engine_internal.h): the lines of the nr row samples into out_row (columns
+// local to the column set), those of the nc column samples into out_col (columns local to the row set).  a = the row sample's count, b = the
+// column sample's, on either line.
+int kmdb_sample_rect(const char* who, hipStream_t st, int kmer_length, const uint32_t* cells_dev, uint64_t nr, uint64_t nc, const unsigned char* touched,
+                     const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers, const uint32_t* col_kmers, int criterion, uint32_t count,
+                     kmdb_sparse_rows* out_row, kmdb_sparse_rows* out_col, kmdb_sample_stats* stats) {
+    std::memset(out_row, 0, sizeof *out_row);
+    std::memset(out_col, 0, sizeof *out_col);
+    DevBuf<uint32_t> d_rk, d_ck;
+    DEV_ALLOC(d_rk, std::max<uint64_t>(nr, 1));
+    DEV_ALLOC(d_ck, std::max<uint64_t>(nc, 1));
+    if (nr) HIP_TRY(hipMemcpyAsync(d_rk, row_kmers, nr * 4, hipMemcpyHostToDevice, st));
+    if (nc) HIP_TRY(hipMemcpyAsync(d_ck, col_kmers, nc * 4, hipMemcpyHostToDevice, st));
+    const Proxy px = proxy_of(criterion);
+    kmdb_sample_job job;
+    job.rect = true; job.cells = cells_dev; job.nr = nr; job.nc = nc; job.touched = touched;
+    job.counts_dev = d_rk; job.col_counts_dev = d_ck; job.kind = px.kind; job.flip = px.flip; job.count = count;
+    job_bounds(job, filters, n_filters, kmer_length);
+    kmdb_sample_stats ss{};
+    try {
+        SampleSelection sel;
+        auto ab = [&](uint64_t s, uint32_t o, uint32_t& a, uint32_t& b) {
+            if (s < nr) { a = row_kmers[s]; b = col_kmers[o]; } else { a = row_kmers[o]; b = col_kmers[s - nr]; }
+        };
+        if (select_complete(st, job, nr + nc, px, count, kmer_length, filters, n_filters, ab, ss, sel)) return 1;
+        if (pack_slots(who, sel, 0, nr, out_row)) return 1;
+        if (pack_slots(who, sel, nr, nr + nc, out_col)) { kmdb_sparse_free(out_row); return 1; }
+        ss.candidates = out_row->nnz + out_col->nnz;
+        if (stats) *stats = ss;
+        return 0;
+    } catch (const std::exception& e) {
+        kmdb_sparse_free(out_row); kmdb_sparse_free(out_col);
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+
+// the limits of the select's 31-bit sizes (slots + 1 and tiles of 64 x 64), before any device work
+int kmdb_sample_rect_check(const char* who, uint64_t nr, uint64_t nc) {
+    if (nr >= (1ull << 31) || nc >= (1ull << 31) || nr + nc + 1 >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": more than 2^31 - 2 samples in the two sets");
+    if (((nr + 63) / 64) * ((nc + 63) / 64) >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": more than 2^31 tiles of 64 x 64 cells");
+    return 0;
+}
+
+extern "C" int kmdb_sampled_from_rect_device(kmdb_db* db, const void* cells_dev, uint64_t nr, uint64_t nc, const kmdb_cell_filter* filters, size_t n_filters,
+                                             const uint32_t* row_sample_kmers, const uint32_t* col_sample_kmers, int criterion, uint32_t count,
+                                             kmdb_sparse_rows* out_row_candidates, kmdb_sparse_rows* out_col_candidates, const kmdb_opts* opts) {
+    const char* who = "kmdb_sampled_from_rect_device";
+    if (!db || !out_row_candidates || !out_col_candidates) return kmdb_set_error(std::string(who) + ": null argument");
+    if (check_sample_args(who, filters, n_filters, row_sample_kmers && col_sample_kmers ? row_sample_kmers : nullptr, criterion, count)) return 1;
+    if (kmdb_sample_rect_check(who, nr, nc)) return 1;
+    if (!cells_dev && nr && nc) return kmdb_set_error(std::string(who) + ": null matrix");
+    HIP_TRY(hipSetDevice(db->device));
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
+    HIP_TRY(hipEventRecord(db->ev[0], st)); HIP_TRY(hipEventRecord(db->ev[1], st)); HIP_TRY(hipEventRecord(db->ev[2], st));
+    db->stats.path = KMDB_PATH_NONE;
+    db->d2_sample_stats = kmdb_sample_stats{};
+    if (kmdb_sample_rect(who, st, (int)db->kmer_length, (const uint32_t*)cells_dev, nr, nc, nullptr, filters, n_filters, row_sample_kmers, col_sample_kmers, criterion,
+                         count, out_row_candidates, out_col_candidates, &db->d2_sample_stats)) return 1;
+    if (finish_stats(db, st)) { kmdb_sparse_free(out_row_candidates); kmdb_sparse_free(out_col_candidates); return 1; }
+    kmdb_release_staging(db);
+    return 0;
+}
+
+extern "C" int kmdb_db2db_sample_stats_get(const kmdb_db* db_row, kmdb_sample_stats* out) {
+    if (!db_row || !out) return kmdb_set_error("kmdb_db2db_sample_stats_get: null argument");
+    *out = db_row->d2_sample_stats;
+    return 0;
+}
+
+// the argument checks of kmdb_db2db_sampled that need no handle (db2db.hip makes the others)
+int kmdb_check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count) {
+    return check_sample_args(who, filters, n_filters, sample_kmers, criterion, count);
+}
 
 extern "C" int kmdb_sampled_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters,
                                               size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out_candidates,

@@ -42,6 +42,7 @@ struct kmdb_engine_view {
     bool* rl_tried;
     uint64_t* device_bytes;
     struct kmdb_db2db_stats* d2_stats;   // the last db2db call with this handle as the row database (kmdb_db2db_stats_get)
+    struct kmdb_sample_stats* d2_sample_stats;   // the last sampled db2db call with this handle as the row database (kmdb_db2db_sample_stats_get)
     struct kmdb_new2all_sparse_stats* n2s_stats;   // the last sparse new2all call on the handle (kmdb_new2all_sparse_stats_get)
     void* stream;
     void* ev[4];
@@ -72,6 +73,19 @@ void kmdb_dev_bounds(const kmdb_cell_filter* filters, size_t n_filters, int kmer
 // against the bounds, the rows are compacted in place and, with measure >= 0, out->measure is filled.  0, or 1 with the error set (out freed).
 int kmdb_sparse_decide(const char* who, kmdb_sparse_rows* out, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers,
                        const uint32_t* col_kmers, int measure, int kmer_length);
+
+// ---- the -sample-rows selection on a rectangle of two sample sets (engine.hip over sample_rows.hip; db2db.hip selects its cell with it)
+struct kmdb_sample_stats;
+// argument checks of a sampled call, before any device work (sample_kmers: null when the caller lacks one of the count arrays)
+int kmdb_check_sample_args(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count);
+// nr + nc and the tile count against the select's 31-bit sizes
+int kmdb_sample_rect_check(const char* who, uint64_t nr, uint64_t nc);
+// The complete candidates (selection, completeness rule, re-fetch) of a row-major nr x nc rectangle in HBM, complete on `st`; touched: one flag
+// per 64 x 64 tile at row block * ceil(nc / 64) + column block, or null.  out_row: nr rows, columns local to the column set; out_col: nc rows,
+// columns local to the row set; ascending columns, val = common k-mers.  stats (may be null) is filled.  0, or 1 with the error set (outs freed).
+int kmdb_sample_rect(const char* who, hipStream_t st, int kmer_length, const uint32_t* cells_dev, uint64_t nr, uint64_t nc, const unsigned char* touched,
+                     const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers, const uint32_t* col_kmers, int criterion, uint32_t count,
+                     kmdb_sparse_rows* out_row, kmdb_sparse_rows* out_col, kmdb_sample_stats* stats);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

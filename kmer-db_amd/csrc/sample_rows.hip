@@ -18,6 +18,11 @@
 // its 2 x width samples — `width` row samples, `width` column samples — reads its own line of the tile from there (a wave per sample, the
 // column lines through a padded stride), so no pass walks a column of the triangle.  Passes: 4 histogram, 1 count, 1 emit = 6 reads of the
 // (touched tiles of the) triangle.  The emit appends through one cursor per sample; a rank sort inside every row then gives ascending columns.
+//
+// The same passes select on a RECTANGLE of two sample sets, the off-diagonal cell of the all2all-parts grid (db2db_sp + compact2(filter) +
+// add_to_sampler, reference src/console_all2all_parts.cpp:179-195, 225-241): the tile kernel is a template over the source of its cells
+// (TriSamples / RectSamples below) and everything else works on SLOTS — the N samples of a triangle, the nr row samples followed by the nc
+// column samples of a rectangle.  A pair of a rectangle has one score with the cell's row as the row sample, on either of its two lines.
 #include "device_common.h"
 #include "cell_filter.h"
 #include "sample_rows.h"
@@ -36,20 +41,69 @@ constexpr uint32_t SR_W = 64;           // widest tile: a lane per column
 constexpr uint32_t SR_KEY_BEST = 0xFFFFFFFFu;
 enum { SR_HIST = 0, SR_COUNT, SR_EMIT };
 
-struct SrJob {
+struct SrJob {                          // what every source of cells shares
+    const unsigned char* touched;       // [tiles] or nullptr: only flagged tiles are read
+    DevFilter f;                        // widened bounds (f.counts is not read here: the k-mer counts come from the source)
+    int kind, flip;                     // RATIO_* of the criterion; 1: the measure falls with its ratio
+    uint32_t count;
+};
+// The source of the cells — the one thing of a pass that knows a geometry (as distance.hip's TextCells / TriangleCells / RowCells): which tile is
+// where, which cell a lane loads, whose k-mer counts a and b are, and which slot of hist / state / thr / len / cursor / row_ptr a line belongs to.
+// TriSamples: the lower triangle of N samples, flat cells [cell_lo, cell_hi); tile (X, Y), Y <= X, has the index X (X + 1) / 2 + Y as in
+// kmdb_db.tile_touched; the slot of a row line and of a column line is the sample itself.
+struct TriSamples {
     const uint32_t* M;                  // cell `cell_lo` of the lower triangle
     uint64_t N, cell_lo, cell_hi;
     uint32_t W;                         // tile width (the block width of the handle when its tile flags are used, else SR_W)
-    const unsigned char* touched;       // [tiles] or nullptr: only flagged tiles are read
-    DevFilter f;                        // widened bounds; f.counts is always set (the proxy needs the k-mer counts)
-    int kind, flip;                     // RATIO_* of the criterion; 1: the measure falls with its ratio
-    uint32_t count;
+    const uint32_t* counts;             // [N] k-mer counts of the samples
+    __device__ __forceinline__ uint32_t width() const { return W; }
+    __device__ __forceinline__ bool tile(uint32_t t, uint64_t& i0, uint64_t& j0) const {       // false: no cell of the tile is in the range
+        uint32_t X = (uint32_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+        while ((uint64_t)X * (X + 1) / 2 > t) --X;
+        while ((uint64_t)(X + 1) * (X + 2) / 2 <= t) ++X;
+        const uint32_t Y = t - (uint32_t)((uint64_t)X * (X + 1) / 2);
+        i0 = (uint64_t)X * W; j0 = (uint64_t)Y * W;
+        if (i0 >= N) return false;
+        // the tile's rows against the flat range: rows [i0, i1], cells tri(i0) + j0 .. tri(i1) + i1 - 1
+        const uint64_t i1 = (i0 + W < N ? i0 + W : N) - 1;
+        return !(tri64(i1) + i1 <= cell_lo || tri64(i0 ? i0 : 1) + j0 >= cell_hi);
+    }
+    __device__ __forceinline__ uint32_t load(uint64_t i, uint64_t j, uint32_t lane) const {
+        if (lane < W && i < N && j < i) {
+            const uint64_t flat = tri64(i) + j;
+            if (flat >= cell_lo && flat < cell_hi) return M[flat - cell_lo];
+        }
+        return 0u;
+    }
+    __device__ __forceinline__ uint32_t a(uint64_t i) const { return counts[i]; }
+    __device__ __forceinline__ uint32_t b(uint64_t j) const { return counts[j]; }
+    __device__ __forceinline__ bool row_slot(uint64_t i, uint64_t& s) const { s = i; return i < N; }
+    __device__ __forceinline__ bool col_slot(uint64_t j, uint64_t& s) const { s = j; return j < N; }
+};
+// RectSamples: a row-major nr x nc rectangle of two sample sets, cell (r, c) at r * nc + c (64-bit: 66 000 x 66 000 cells exceed 2^32).  Tile t is
+// (t / nbc, t % nbc), the stream numbering of db2db.hip's d2_emit_kernel / d2_tile_flags_kernel, always 64 wide.  Slots [0, nr) are the row
+// samples, [nr, nr + nc) the column samples; a is ALWAYS the row sample's count and b the column sample's, whichever line ranks the cell.
+struct RectSamples {
+    const uint32_t* M;
+    uint32_t nr, nc, nbc;
+    const uint32_t *row_counts, *col_counts;
+    __device__ __forceinline__ uint32_t width() const { return SR_W; }
+    __device__ __forceinline__ bool tile(uint32_t t, uint64_t& i0, uint64_t& j0) const {
+        i0 = (uint64_t)(t / nbc) * SR_W; j0 = (uint64_t)(t % nbc) * SR_W;
+        return i0 < nr;
+    }
+    // (a lane whose column is >= nc loads nothing: in a row-major rectangle that address is a cell of the NEXT row — d2_row_tiles_kernel)
+    __device__ __forceinline__ uint32_t load(uint64_t i, uint64_t j, uint32_t) const { return i < nr && j < nc ? M[i * nc + j] : 0u; }
+    __device__ __forceinline__ uint32_t a(uint64_t i) const { return row_counts[i]; }
+    __device__ __forceinline__ uint32_t b(uint64_t j) const { return col_counts[j]; }
+    __device__ __forceinline__ bool row_slot(uint64_t i, uint64_t& s) const { s = i; return i < nr; }
+    __device__ __forceinline__ bool col_slot(uint64_t j, uint64_t& s) const { s = (uint64_t)nr + j; return j < nc; }
 };
 struct SrState { uint32_t prefix, k, done, total; };   // done: 1 the row comes out whole, 2 cut at T_s; total: cells of the row that pass the widened filters
 
 // order-preserving key of the proxy: 0 is kept for "no cell", SR_KEY_BEST for a NaN or infinite proxy (its whole row goes to the host)
-__device__ __forceinline__ uint32_t sr_key(const SrJob& q, uint32_t c, uint32_t row, uint32_t col) {
-    double x = dev_ratio(q.kind, c, q.f.counts[row], q.f.counts[col]);
+__device__ __forceinline__ uint32_t sr_key(const SrJob& q, uint32_t c, uint32_t a, uint32_t b) {
+    double x = dev_ratio(q.kind, c, a, b);
     if (q.flip) x = -x;
     if (!(fabs(x) <= 1.7976931348623157e308)) return SR_KEY_BEST;
     const uint32_t u = __float_as_uint((float)x);
@@ -76,13 +130,13 @@ __host__ __device__ inline uint32_t sr_float_key(float f) {
     return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 
-// One workgroup (4 waves) per tile (X, Y), Y <= X, tile index X (X + 1) / 2 + Y as in kmdb_db.tile_touched.
+// One workgroup (4 waves) per tile of the source.
 //   SR_HIST : digit `digit` (0 = top 8 bits) of the keys that share the sample's prefix goes to hist[s][256]; at digit 0 a line that holds
 //             an SR_KEY_BEST key sets unrankable[s]
 //   SR_COUNT: len[s] += cells with key >= thr[s]            (thr 0: the sample is skipped)
-//   SR_EMIT : those cells appended at row_ptr[s] + cursor[s]++
-template <int MODE>
-__global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t digit, const SrState* __restrict__ state, uint32_t* __restrict__ hist,
+//   SR_EMIT : those cells appended at row_ptr[s] + cursor[s]++ (a row line carries the column's id, a column line the row's)
+template <int MODE, class Cells>
+__global__ __launch_bounds__(256) void sr_tile_kernel(const Cells src, const SrJob q, uint32_t digit, const SrState* __restrict__ state, uint32_t* __restrict__ hist,
                                                       const uint32_t* __restrict__ thr, unsigned long long* __restrict__ len,
                                                       const unsigned long long* __restrict__ row_ptr, uint32_t* __restrict__ cursor,
                                                       uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval, uint32_t* __restrict__ unrankable) {
@@ -90,28 +144,17 @@ __global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t di
     __shared__ uint32_t s_val[SR_W][SR_W + 1];
     const uint32_t t = blockIdx.x;
     if (q.touched && !q.touched[t]) return;
-    uint32_t X = (uint32_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((uint64_t)X * (X + 1) / 2 > t) --X;
-    while ((uint64_t)(X + 1) * (X + 2) / 2 <= t) ++X;
-    const uint32_t Y = t - (uint32_t)((uint64_t)X * (X + 1) / 2);
-    const uint32_t W = q.W, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t i0 = (uint64_t)X * W, j0 = (uint64_t)Y * W;
-    if (i0 >= q.N) return;
-    {
-        // the tile's rows against the flat range: rows [i0, i1], cells tri(i0) + j0 .. tri(i1) + i1 - 1
-        const uint64_t i1 = (i0 + W < q.N ? i0 + W : q.N) - 1;
-        if (tri64(i1) + i1 <= q.cell_lo || tri64(i0 ? i0 : 1) + j0 >= q.cell_hi) return;
-    }
+    const uint32_t W = src.width(), lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t i0, j0;
+    if (!src.tile(t, i0, j0)) return;
     uint32_t any = 0;
     for (uint32_t r = wave; r < W; r += 4) {
         const uint64_t i = i0 + r, j = j0 + lane;
-        uint32_t v = 0, key = 0;
-        if (lane < W && i < q.N && j < i) {
-            const uint64_t flat = tri64(i) + j;
-            if (flat >= q.cell_lo && flat < q.cell_hi) {
-                v = q.M[flat - q.cell_lo];
-                if (dev_keep(q.f, v, (uint32_t)i, (uint32_t)j)) key = sr_key(q, v, (uint32_t)i, (uint32_t)j);
-            }
+        const uint32_t v = src.load(i, j, lane);
+        uint32_t key = 0;
+        if (v) {
+            const uint32_t a = src.a(i), b = src.b(j);
+            if (q.f.n == 0 || dev_keep_ab(q.f, v, a, b)) key = sr_key(q, v, a, b);
         }
         s_key[r][lane] = key;
         s_val[r][lane] = v;
@@ -122,8 +165,8 @@ __global__ __launch_bounds__(256) void sr_tile_kernel(const SrJob q, uint32_t di
     for (uint32_t slot = wave; slot < 2 * W; slot += 4) {
         const bool isrow = slot < W;
         const uint32_t a = isrow ? slot : slot - W;
-        const uint64_t s = isrow ? i0 + a : j0 + a;
-        if (s >= q.N) continue;
+        uint64_t s;
+        if (!(isrow ? src.row_slot(i0 + a, s) : src.col_slot(j0 + a, s))) continue;
         uint32_t key = 0, v = 0;
         if (lane < W) {
             key = isrow ? s_key[a][lane] : s_key[lane][a];
@@ -231,23 +274,9 @@ __global__ __launch_bounds__(64) void sr_sort_rows_kernel(const unsigned long lo
     }
 }
 
-}  // namespace
-
-int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
-    const uint64_t N = j.N;
-    out->row_ptr.assign(N + 1, 0);
-    out->col.clear(); out->val.clear();
-    out->rows_truncated = 0; out->d2h_bytes = 0; out->select_ms = 0; out->passes = 0;
-    if (N < 2 || j.cell_hi <= j.cell_lo) return 0;
-    SrJob q{};
-    q.M = j.cells; q.N = N; q.cell_lo = j.cell_lo; q.cell_hi = j.cell_hi;
-    q.W = j.touched ? j.width : SR_W; q.touched = j.touched;
-    if (q.W == 0 || q.W > SR_W) return kmdb_set_error("kmdb_sample_candidates: tile width out of range");
-    q.f.n = (int)j.n_bounds; q.f.counts = j.counts_dev;
-    for (size_t i = 0; i < j.n_bounds; ++i) { q.f.kind[i] = j.bound_kind[i]; q.f.lo[i] = j.bound_lo[i]; q.f.hi[i] = j.bound_hi[i]; }
-    q.kind = j.kind; q.flip = j.flip; q.count = j.count;
-    const uint64_t B = (N + q.W - 1) / q.W, tiles = B * (B + 1) / 2;
-    if (tiles >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many tiles");
+// the passes over one source of cells: N slots (out->row_ptr is sized and zeroed), `tiles` workgroups per pass
+template <class Cells>
+int sr_run(hipStream_t st, const Cells& src, const SrJob& q, uint64_t N, uint64_t tiles, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
     DevBuf<uint32_t> hist, thr, cursor, tcol, tval, col, val, unrankable;
     DevBuf<SrState> state;
     DevBuf<unsigned long long> len, row_ptr, ntr;
@@ -279,14 +308,14 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
         DEV_ALLOC(unrankable, std::max<uint64_t>(N, 1));
         HIP_TRY(hipMemsetAsync(unrankable, 0, N * 4, st));
         for (uint32_t d = 0; d < 4; ++d) {
-            hipLaunchKernelGGL((sr_tile_kernel<SR_HIST>), grid, block, 0, st, q, d, state, hist, (const uint32_t*)nullptr, (unsigned long long*)nullptr,
+            hipLaunchKernelGGL((sr_tile_kernel<SR_HIST, Cells>), grid, block, 0, st, src, q, d, state, hist, (const uint32_t*)nullptr, (unsigned long long*)nullptr,
                                (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, unrankable.get());
             hipLaunchKernelGGL(sr_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, hist, state, thr, (const uint32_t*)unrankable.get(), N, d, q.count);
             ++out->passes;
         }
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL((sr_tile_kernel<SR_COUNT>), grid, block, 0, st, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, len, (const unsigned long long*)nullptr,
+    hipLaunchKernelGGL((sr_tile_kernel<SR_COUNT, Cells>), grid, block, 0, st, src, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, len, (const unsigned long long*)nullptr,
                        (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     ++out->passes;
     if (!only_rows) hipLaunchKernelGGL(sr_truncated_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, state, len, N, ntr);
@@ -304,7 +333,7 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
         DEV_ALLOC(tval, std::max<uint64_t>(nnz, 1));
         DEV_ALLOC(col, std::max<uint64_t>(nnz, 1));
         DEV_ALLOC(val, std::max<uint64_t>(nnz, 1));
-        hipLaunchKernelGGL((sr_tile_kernel<SR_EMIT>), grid, block, 0, st, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, (unsigned long long*)nullptr, row_ptr, cursor,
+        hipLaunchKernelGGL((sr_tile_kernel<SR_EMIT, Cells>), grid, block, 0, st, src, q, 0u, (const SrState*)nullptr, (uint32_t*)nullptr, thr, (unsigned long long*)nullptr, row_ptr, cursor,
                            tcol, tval, (uint32_t*)nullptr);
         ++out->passes;
         hipLaunchKernelGGL(sr_sort_rows_kernel, dim3((unsigned)N), dim3(64), 0, st, row_ptr, tcol, tval, col, val);
@@ -329,6 +358,36 @@ int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint3
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     out->select_ms = ms;
     return 0;
+}
+
+}  // namespace
+
+int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
+    const bool rect = j.rect;
+    const uint64_t N = rect ? j.nr + j.nc : j.N;
+    out->row_ptr.assign(N + 1, 0);
+    out->col.clear(); out->val.clear();
+    out->rows_truncated = 0; out->d2h_bytes = 0; out->select_ms = 0; out->passes = 0;
+    if (rect ? (j.nr == 0 || j.nc == 0) : (N < 2 || j.cell_hi <= j.cell_lo)) return 0;
+    if (N + 1 >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many samples");
+    SrJob q{};
+    q.touched = j.touched;
+    q.f.n = (int)j.n_bounds; q.f.counts = j.counts_dev;
+    for (size_t i = 0; i < j.n_bounds; ++i) { q.f.kind[i] = j.bound_kind[i]; q.f.lo[i] = j.bound_lo[i]; q.f.hi[i] = j.bound_hi[i]; }
+    q.kind = j.kind; q.flip = j.flip; q.count = j.count;
+    if (rect) {
+        if (j.nr >= (1ull << 32) || j.nc >= (1ull << 32)) return kmdb_set_error("kmdb_sample_candidates: too many samples");
+        const uint64_t nbr = (j.nr + SR_W - 1) / SR_W, nbc = (j.nc + SR_W - 1) / SR_W, tiles = nbr * nbc;
+        if (tiles >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many tiles");
+        const RectSamples src{j.cells, (uint32_t)j.nr, (uint32_t)j.nc, (uint32_t)nbc, j.counts_dev, j.col_counts_dev};
+        return sr_run(st, src, q, N, tiles, only_rows, n_only, out);
+    }
+    const uint32_t W = j.touched ? j.width : SR_W;
+    if (W == 0 || W > SR_W) return kmdb_set_error("kmdb_sample_candidates: tile width out of range");
+    const uint64_t B = (N + W - 1) / W, tiles = B * (B + 1) / 2;
+    if (tiles >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many tiles");
+    const TriSamples src{j.cells, N, j.cell_lo, j.cell_hi, W, j.counts_dev};
+    return sr_run(st, src, q, N, tiles, only_rows, n_only, out);
 }
 
 // the key the device ranks by, from the host's own proxy: what the completeness rule of the entry points compares (engine.hip)

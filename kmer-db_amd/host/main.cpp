@@ -82,6 +82,7 @@ struct Filters {
     struct Bound { metric_fn fn; double lo = std::numeric_limits<double>::lowest(), hi = std::numeric_limits<double>::max(); };
     std::map<std::string, Bound> metric;
     uint32_t kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+    size_t given = 0;                        // -min / -max options read: never fewer than the bounds they fold into (one lo / hi pair per measure)
 
     void parse(std::vector<std::string>& args) {
         auto avail = metrics();
@@ -95,6 +96,7 @@ struct Filters {
                 std::istringstream iss(num);
                 double value;
                 if (!(iss >> value)) throw std::runtime_error("Filtering error - unable to parse numerical value: " + v);
+                ++given;
                 if (metric_name == "num-kmers") {
                     (which == 0 ? kmer_lo : kmer_hi) = (uint32_t)std::lrint(value);
                 } else if (avail.count(metric_name)) {
@@ -124,8 +126,11 @@ struct Filters {
 // order in which its hash tables happen to list a row): here the same draws, over the pairs in ascending order of the other sample — the same
 // kind of subset, not the same bytes.
 // all2all-sp with a criterion never fills this sampler: the candidates are selected on the device and decided by the library
-// (kmdb_all2all_sampled / kmdb_node_all2all_sampled).  all2all-parts does — its cells come from kmdb_db2db_dense in host memory —, from several
-// workers at once: add() takes the lock of the sample's stripe, and with a criterion a row is pruned to its `cap` best whenever it reaches
+// (kmdb_all2all_sampled / kmdb_node_all2all_sampled).  all2all-parts does, from several workers at once.  With a criterion it is given the
+// CANDIDATES of every cell only — per sample a superset of its `count` best of that cell, selected on the device (kmdb_db2db_sampled; the diagonal
+// cells by kmdb_all2all_sampled), each side of a pair where it was selected — and finish_row, exact on any superset, decides.  Every kept pair of
+// every cell goes through it only on the host path: the random strategy, KMDB_PARTS_DENSE_CELLS=1, KMDB_PARTS_HOST_SAMPLER=1 or more than 12
+// bounds.  add() takes the lock of the sample's stripe, and with a criterion a row is pruned to its `cap` best whenever it reaches
 // 2 * cap items (the order is total, so what is left at the end is the same: never more than 2 * cap items per sample, as the reference's heap
 // never holds more than cap + 1).
 struct RowSampler {
@@ -576,9 +581,18 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
     for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
     if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
         fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+    const std::vector<kmdb_cell_filter> fl_all = fl;              // every bound: what a sampled call takes (a selection without a bound is no superset)
     if (fl.size() > 8) fl.clear();                                // (the rows are checked with every bound below anyway)
     std::vector<uint32_t> counts32(counts.begin(), counts.end());
     const bool dense_cells = std::getenv("KMDB_PARTS_DENSE_CELLS") != nullptr;
+    // -sample-rows <criterion>:<count>: every cell's candidates are selected on the device (kmdb_db2db_sampled, kmdb_all2all_sampled on the
+    // diagonal) and only those reach the sampler.  The random strategy, KMDB_PARTS_DENSE_CELLS=1, more bounds than the device takes and
+    // KMDB_PARTS_HOST_SAMPLER=1 (A/B) keep the host path: every kept pair of every cell goes through the sampler.  The bytes written are the same.
+    // (The device takes 12 bounds.  Every -min / -max given counts as one here, before a measure's two fold into one lo / hi pair — the cautious
+    // reading: the folded list, at most one pair per measure, could never exceed 12 by itself.)
+    const bool device_sampler = c.sampler.on() && c.sampler.best && !dense_cells && c.filters.given <= 12 && fl_all.size() <= 12 &&
+                                std::getenv("KMDB_PARTS_HOST_SAMPLER") == nullptr;
+    const bool verbose = std::getenv("KMDB_VERBOSE") != nullptr;
     auto block_row = [&](Worker& wk, size_t i) {
         auto get = [&](size_t p, size_t keep) -> Db& {
             if (wk.resident[p]) return *wk.resident[p];
@@ -599,6 +613,66 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
         const uint64_t row_shift = row_start[i];
         Db& drow = get(i, i);
         const uint64_t nr = part_n[i];
+        if (device_sampler) {
+            // (console_all2all_parts.cpp:179-195, 225-241 with a sampler: db2db_sp, compact2(filter), add_to_sampler.)  A sample's best `count` of
+            // one cell is a superset of its share of its best `count` overall, and finish_row is exact on any superset.  A pair has one score, the
+            // later part's sample being the row sample; each side of a pair is added only where the device selected it for that side.
+            const uint32_t cap = (uint32_t)std::min<size_t>(c.sampler.cap, 0xFFFFFFFFu);
+            const uint32_t* row_counts = counts32.data() + row_shift;
+            for (size_t j = 0; j < i; ++j) {
+                { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << j + 1 << ")" << std::endl; }
+                Db& dcol = get(j, i);
+                const uint64_t shift_j = row_start[j], nc = part_n[j];
+                const uint32_t* col_counts = counts32.data() + shift_j;
+                std::vector<kmdb_sparse_rows> cand(2, kmdb_sparse_rows{});      // [0]: the row samples' candidates, [1]: the column samples'
+                struct FreeRows { std::vector<kmdb_sparse_rows>& v; ~FreeRows() { for (auto& x : v) kmdb_sparse_free(&x); } } free_cand{cand};
+                auto sampled = [&]() {
+                    return kmdb_db2db_sampled(drow.d, dcol.d, fl_all.data(), fl_all.size(), row_counts, col_counts, c.sampler.criterion_id, cap, &cand[0], &cand[1], &wk.o);
+                };
+                if (sampled()) {
+                    for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i && q != j) wk.resident[q].reset();
+                    check(sampled());
+                }
+                for (uint64_t r = 0; r < nr; ++r)
+                    for (uint64_t e = cand[0].row_ptr[r]; e < cand[0].row_ptr[r + 1]; ++e) {
+                        const uint32_t col = cand[0].col[e], v = cand[0].val[e], a = row_counts[r], b = col_counts[col];
+                        if (c.filters.pass(v, a, b, (int)k)) c.sampler.add(row_shift + r, (uint32_t)(shift_j + col), v, c.sampler.score(v, a, b, (int)k));
+                    }
+                for (uint64_t cs = 0; cs < nc; ++cs)
+                    for (uint64_t e = cand[1].row_ptr[cs]; e < cand[1].row_ptr[cs + 1]; ++e) {
+                        const uint32_t rw = cand[1].col[e], v = cand[1].val[e], a = row_counts[rw], b = col_counts[cs];
+                        if (c.filters.pass(v, a, b, (int)k)) c.sampler.add(shift_j + cs, (uint32_t)(row_shift + rw), v, c.sampler.score(v, a, b, (int)k));
+                    }
+                if (verbose) {
+                    kmdb_sample_stats ss{};
+                    kmdb_db2db_stats ds{};
+                    if (!kmdb_db2db_sample_stats_get(drow.d, &ss) && !kmdb_db2db_stats_get(drow.d, &ds)) {
+                        std::lock_guard<std::mutex> g(mu);
+                        std::fprintf(stderr, "[kmdb] all2all-parts: sampled cell (%zu,%zu): %llu of %llu tiles touched, %llu candidates, %llu rows truncated, %llu re-fetched, selection %.3f ms\n",
+                                     i + 1, j + 1, (unsigned long long)ds.tiles_touched, (unsigned long long)ds.tiles, (unsigned long long)ss.candidates,
+                                     (unsigned long long)ss.rows_truncated, (unsigned long long)ss.rows_refetched, ss.select_ms);
+                    }
+                }
+            }
+            { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << i + 1 << ")" << std::endl; }
+            // the diagonal cell: the part's own symmetric rows, selected and decided by the library
+            kmdb_sparse_rows sp{};
+            auto diagonal = [&]() { return kmdb_all2all_sampled(drow.d, fl_all.data(), fl_all.size(), row_counts, c.sampler.criterion_id, cap, &sp, &wk.o); };
+            if (diagonal()) {
+                for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i) wk.resident[q].reset();
+                check(diagonal());
+            }
+            for (uint64_t s = 0; s < nr; ++s)
+                for (uint64_t e = sp.row_ptr[s]; e < sp.row_ptr[s + 1]; ++e) {
+                    const uint32_t o = sp.col[e], v = sp.val[e], a = row_counts[std::max<uint64_t>(s, o)], b = row_counts[std::min<uint64_t>(s, o)];
+                    if (c.filters.pass(v, a, b, (int)k)) c.sampler.add(row_shift + s, (uint32_t)(row_shift + o), v, c.sampler.score(v, a, b, (int)k));
+                }
+            kmdb_sparse_free(&sp);
+            std::lock_guard<std::mutex> g(mu);
+            block_text[i].clear(); block_saved[i] = 0; block_done[i] = 1;
+            cv.notify_all();
+            return;
+        }
         // A cell is kept as the reference keeps it (:179-195, 225-241: db2db_sp, then compact2 with the -min / -max filter): compacted and filtered
         // on the device, a CSR per earlier part of the block row.  KMDB_PARTS_DENSE_CELLS=1: the dense rectangles of kmdb_db2db_dense, scanned on the
         // host (the previous path, for A/B); the bytes written are the same.
@@ -2199,6 +2273,8 @@ void usage() {
                  "distance: KMDB_DISTANCE_DEVICE=1 parses, measures and formats the table on the GPU (-gpu <device>; same bytes); -host and\n"
                  "                   KMDB_DISTANCE_DEVICE=0 keep it on the host, which is also what runs when neither is given\n"
                  "all2all-parts: -gpus <W>         the block rows of the grid dealt to W workers over the node's GPUs (parts resident per device)\n"
+                 "               -sample-rows <criterion>:<count>  every cell's candidates are selected on the GPU (same bytes); KMDB_PARTS_HOST_SAMPLER=1,\n"
+                 "                                  KMDB_PARTS_DENSE_CELLS=1, more than 12 bounds and -sample-rows <count> (random) keep the sampler on the host\n"
                  "    kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min [<criterion>:]<v>]* [-max [<criterion>:]<v>]* -distance <measure> [-distance <measure>]* <database> <output>\n"
                  "all2all / all2all-sp -distance:  the table of <measure> straight from the matrix on the GPU: the file `all2all` followed by `distance`\n"
                  "                                  writes, without the table of counts in between; all2all-sp forces -sparse.  Several -distance: one all2all\n"
