@@ -53,6 +53,11 @@ extern "C" {
  * accumulated (kmdb_distance_take_new2all_batch, kmdb_distance_take_new2all_batch_seq_alphabet, kmdb_distance_take_rows_device,
  * kmdb_distance_query_rows): four more entry points, no struct changed, the version stays 8. */
 #define KMDB_HAS_DISTANCE_QUERY_ROWS 1
+/* And the distance mode fed from a CSR in HBM over a run of rows — a block row of the all2all-parts grid gathered on the device from its cells'
+ * CSRs, or one the caller built (kmdb_distance_parts_begin_rows, kmdb_distance_parts_add_db2db, kmdb_distance_parts_add_all2all,
+ * kmdb_distance_parts_add_csr_device, kmdb_distance_take_csr_device, kmdb_distance_csr_rows, kmdb_distance_csr_device, kmdb_distance_csr_row_ptr,
+ * kmdb_distance_parts_stats_get): nine more entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_DISTANCE_PARTS 1
 /* And the -sample-rows selection on an off-diagonal cell of the all2all-parts grid: the candidates of a rectangle of two sample sets chosen in
  * HBM (kmdb_db2db_sampled, kmdb_sampled_from_rect_device, kmdb_db2db_sample_stats_get): three more entry points, no struct changed, the version
  * stays 8. */
@@ -876,6 +881,52 @@ int  kmdb_distance_take_new2all_batch_seq_alphabet(kmdb_distance* d, kmdb_db* db
 int  kmdb_distance_take_rows_device(kmdb_distance* d, const void* rows_dev, size_t nq, const uint32_t* query_kmers /* [nq], host */,
                                     const char* const* names);
 int  kmdb_distance_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out);
+/* The same table from a CSR in HBM (KMDB_HAS_DISTANCE_PARTS): `all2all-parts` followed by `distance -sparse` without the table of counts in
+ * between.  The handle must have been begun with KMDB_DISTANCE_SPARSE_OUT, without KMDB_DISTANCE_TRIANGLE, KMDB_DISTANCE_SPARSE_IN and
+ * KMDB_DISTANCE_PHYLIP, and with `counts` = the k-mer counts of the WHOLE collection (n = all samples of all parts) — any other handle is
+ * refused by every call below.  The source is a CSR over nr rows, the samples of one block row of the grid: row_ptr uint64[nr + 1] ascending
+ * from 0, col uint32 0-based GLOBAL columns (already shifted by the samples of the earlier parts) ascending within a row, val uint32 > 0.
+ * What kmdb_distance_csr_rows returns for rows [row_lo, row_hi) is byte for byte what kmdb_distance_rows of a KMDB_DISTANCE_SPARSE_IN handle
+ * returns for the "name,count,col:val,..." text of those rows: a = the ROW sample's own count, b = counts[col], the bounds and the host cells
+ * as everywhere (kmdb_distance_stats.host_cells).
+ *   parts_begin_rows: starts a block row of nr row samples (their k-mer counts, truncated to 32 bits as the text path truncates them, and their
+ *     names) and drops the previous one.
+ *   parts_add_db2db: the cell (db_row, db_col) computed as kmdb_db2db_sparse_filtered computes it, without bounds, its CSR kept in HBM; col_shift
+ *     = the samples of the parts before db_col's.  Out of device memory it retries once without the list stores and then returns the library's
+ *     usual out-of-memory error: the caller may evict resident parts and repeat.  The cells are kept UNFILTERED: the handle's bounds are
+ *     applied cell by cell when the rows are written, so that a handle with other bounds can borrow the same CSR.
+ *   parts_add_all2all: the diagonal cell, the lower triangle of `db` as kmdb_all2all_sparse computes it.
+ *   parts_add_csr_device: a cell the caller computed — a CSR in HBM over the nr rows of the block row, its n_cols columns LOCAL to the cell —
+ *     checked and COPIED into the block row (the caller's arrays may go when the call returns).
+ *   take_csr_device: BORROWS a CSR the caller built and keeps alive (a tensor, another handle's gathered CSR).
+ *   csr_rows: out as with kmdb_distance_rows (kmdb_distance_out_free); row_lo == row_hi gives empty text and 0 rows.  The first call after the
+ *     adds gathers the cells into ONE CSR on the device (merged row_ptr = the sum of the cells' row_ptr; every entry copied to its place with
+ *     its column shifted) and frees the cells' own.
+ *   csr_device / csr_row_ptr: the gathered (or taken) CSR's device addresses, for a second handle to borrow, and its row_ptr on the host
+ *     ([nr + 1]: what a caller cuts its pieces by); both gather first where cells are waiting.
+ * Refused by name: null arguments; a handle of another kind; row_lo > row_hi or row_hi > nr; rows asked before anything was taken; entries
+ * behind a null pointer; a row_ptr that does not ascend from 0, or a column >= n (both found on the device when the CSR is taken and reported
+ * with a message, never as a fault); a database on another device; a query-shard handle; a part whose samples do not fit the columns; a piece of
+ * 2^31 cells or more, or beyond the free device memory (with the bytes).  The offsets of entries are 64-bit throughout. */
+typedef struct kmdb_distance_parts_stats {   /* the whole life of the handle */
+    uint64_t block_rows;           /* kmdb_distance_parts_begin_rows calls */
+    uint64_t grid_cells;           /* cells added */
+    uint64_t cells_in;             /* entries of the cells added */
+    uint64_t cells_written;        /* entries whose text the device wrote */
+    uint64_t host_cells;           /* entries the host decided */
+    uint64_t peak_bytes;           /* the most a block row held on the device: its cells' CSRs, the gathered CSR, a piece's working arrays */
+    double   gather_ms;
+} kmdb_distance_parts_stats;
+int  kmdb_distance_parts_begin_rows(kmdb_distance* d, size_t nr, const uint32_t* row_kmers /* [nr], host */, const char* const* names /* [nr] */);
+int  kmdb_distance_parts_add_db2db(kmdb_distance* d, kmdb_db* db_row, kmdb_db* db_col, uint64_t col_shift, const kmdb_opts* opts);
+int  kmdb_distance_parts_add_all2all(kmdb_distance* d, kmdb_db* db, uint64_t col_shift, const kmdb_opts* opts);
+int  kmdb_distance_parts_add_csr_device(kmdb_distance* d, const void* row_ptr_dev, const void* col_dev, const void* val_dev, uint64_t n_cols, uint64_t col_shift);
+int  kmdb_distance_take_csr_device(kmdb_distance* d, const void* row_ptr_dev, const void* col_dev, const void* val_dev, size_t nr,
+                                   const uint32_t* row_kmers /* [nr], host */, const char* const* names /* [nr] */);
+int  kmdb_distance_csr_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out);
+int  kmdb_distance_csr_device(kmdb_distance* d, const void** row_ptr_dev, const void** col_dev, const void** val_dev, uint64_t* nr);
+int  kmdb_distance_csr_row_ptr(kmdb_distance* d, uint64_t* out /* [nr + 1], host */);
+int  kmdb_distance_parts_stats_get(const kmdb_distance* d, kmdb_distance_parts_stats* out);
 void kmdb_distance_out_free(kmdb_distance_out* out);
 void kmdb_distance_free(kmdb_distance* d);
 int  kmdb_distance_stats_get(const kmdb_distance* d, kmdb_distance_stats* out);

@@ -117,6 +117,11 @@ class _DistanceStats(C.Structure):
                 ("format_ms", C.c_double), ("copy_ms", C.c_double)]
 
 
+class _DistancePartsStats(C.Structure):
+    _fields_ = [("block_rows", C.c_uint64), ("grid_cells", C.c_uint64), ("cells_in", C.c_uint64), ("cells_written", C.c_uint64), ("host_cells", C.c_uint64),
+                ("peak_bytes", C.c_uint64), ("gather_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -153,6 +158,8 @@ EXPORTS = [
     "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
     "kmdb_distance_take_all2all", "kmdb_distance_take_cells_device", "kmdb_distance_matrix_rows", "kmdb_distance_cells_device",
     "kmdb_distance_take_new2all_batch", "kmdb_distance_take_new2all_batch_seq_alphabet", "kmdb_distance_take_rows_device", "kmdb_distance_query_rows",
+    "kmdb_distance_parts_begin_rows", "kmdb_distance_parts_add_db2db", "kmdb_distance_parts_add_all2all", "kmdb_distance_parts_add_csr_device", "kmdb_distance_take_csr_device", "kmdb_distance_csr_rows",
+    "kmdb_distance_csr_device", "kmdb_distance_csr_row_ptr", "kmdb_distance_parts_stats_get",
 ]
 
 
@@ -302,6 +309,15 @@ def lib():
                                                                 C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_distance_take_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]
     L.kmdb_distance_query_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_parts_begin_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]
+    L.kmdb_distance_parts_add_db2db.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(_Opts)]
+    L.kmdb_distance_parts_add_all2all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(_Opts)]
+    L.kmdb_distance_parts_add_csr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
+    L.kmdb_distance_take_csr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]
+    L.kmdb_distance_csr_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_DistanceOut)]
+    L.kmdb_distance_csr_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.kmdb_distance_csr_row_ptr.argtypes = [C.c_void_p, C.c_void_p]
+    L.kmdb_distance_parts_stats_get.argtypes = [C.c_void_p, C.POINTER(_DistancePartsStats)]
     L.kmdb_distance_cells_device.restype = C.c_void_p
     L.kmdb_distance_cells_device.argtypes = [C.c_void_p]
     L.kmdb_distance_out_free.restype = None
@@ -1249,6 +1265,57 @@ class Distance:
             return C.string_at(out.text, out.len)
         finally:
             lib().kmdb_distance_out_free(C.byref(out))
+
+    def parts_begin(self, row_kmers, names):
+        """kmdb_distance_parts_begin_rows: a block row of the all2all-parts grid — the row samples' own k-mer counts and names; drops the one before"""
+        rk = np.ascontiguousarray(np.asarray(row_kmers, np.uint64) & 0xFFFFFFFF, np.uint32)
+        self._nr = rk.size
+        _check(lib().kmdb_distance_parts_begin_rows(self._d, rk.size, rk.ctypes.data, self._names(names)))
+
+    def parts_add_db2db(self, db_row, db_col, col_shift):
+        """kmdb_distance_parts_add_db2db: the cell (db_row, db_col) of two DeviceDBs, its CSR kept in HBM; col_shift = the samples of the earlier parts"""
+        _check(lib().kmdb_distance_parts_add_db2db(self._d, db_row._d, db_col._d, int(col_shift), None))
+
+    def parts_add_all2all(self, db, col_shift):
+        """kmdb_distance_parts_add_all2all: the diagonal cell, the lower triangle of a DeviceDB"""
+        _check(lib().kmdb_distance_parts_add_all2all(self._d, db._d, int(col_shift), None))
+
+    def parts_add_csr(self, row_ptr, col, val, n_cols, col_shift):
+        """kmdb_distance_parts_add_csr_device: a cell the caller computed (device addresses; columns local to the cell's n_cols), copied in"""
+        _check(lib().kmdb_distance_parts_add_csr_device(self._d, C.c_void_p(row_ptr), C.c_void_p(col), C.c_void_p(val), int(n_cols), int(col_shift)))
+
+    def take_csr(self, row_ptr, col, val, nr, row_kmers, names):
+        """kmdb_distance_take_csr_device: device addresses (e.g. torch tensors' .data_ptr(), or None) of a CSR the caller keeps alive — row_ptr
+        uint64[nr + 1], col uint32 global 0-based ascending within a row, val uint32 > 0; row_kmers: the row samples' own k-mer counts"""
+        rk = np.ascontiguousarray(np.asarray(row_kmers, np.uint64) & 0xFFFFFFFF, np.uint32)
+        self._nr = int(nr)
+        _check(lib().kmdb_distance_take_csr_device(self._d, C.c_void_p(row_ptr), C.c_void_p(col), C.c_void_p(val), int(nr), rk.ctypes.data, self._names(names)))
+
+    def csr_rows(self, lo, hi):
+        """kmdb_distance_csr_rows: the text of rows [lo, hi) of the measure's table of the CSR taken (the first call after the adds gathers)"""
+        out = _DistanceOut()
+        _check(lib().kmdb_distance_csr_rows(self._d, int(lo), int(hi), C.byref(out)))
+        try:
+            return C.string_at(out.text, out.len)
+        finally:
+            lib().kmdb_distance_out_free(C.byref(out))
+
+    def csr_ptrs(self):
+        """kmdb_distance_csr_device: (row_ptr, col, val, nr) — the device addresses of the gathered or taken CSR, for a second handle's take_csr"""
+        rp, co, va, nr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(lib().kmdb_distance_csr_device(self._d, C.byref(rp), C.byref(co), C.byref(va), C.byref(nr)))
+        return rp.value, co.value, va.value, nr.value
+
+    def csr_row_ptr(self):
+        """kmdb_distance_csr_row_ptr: the row_ptr of the gathered or taken CSR on the host"""
+        out = np.zeros(getattr(self, "_nr", 0) + 1, np.uint64)
+        _check(lib().kmdb_distance_csr_row_ptr(self._d, out.ctypes.data))
+        return out
+
+    def parts_stats(self):
+        st = _DistancePartsStats()
+        _check(lib().kmdb_distance_parts_stats_get(self._d, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _DistancePartsStats._fields_}
 
     def stats(self):
         st = _DistanceStats()

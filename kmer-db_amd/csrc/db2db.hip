@@ -22,6 +22,8 @@
 //   flags    one byte per 64 x 64 tile of the cell, set from the key words of the emit pool: the tiles that received a block record
 //   compact  one wave per row over the flagged tiles of its row block: widened bounds (cell_filter.h), per-row counts, exclusive sum,
 //            (col, val) in ascending columns; the exact decision is the host's (kmdb_sparse_decide, engine.hip)
+// kmdb_db2db_csr_device (engine_internal.h; the cells of `all2all-parts -distance`, distance.hip) is the same compaction without bounds whose
+// three buffers stay in HBM: nothing is copied to the host and nothing is decided here.
 // kmdb_db2db_sampled (db2db_sp + compact2(filter) + SparseMatrix::add_to_sampler of an off-diagonal cell with -sample-rows <criterion>:<count>,
 // src/console_all2all_parts.cpp:179-195, 225-241; src/array.h:450-540) keeps the cell in HBM as well and selects there:
 //   flags    as above
@@ -377,6 +379,7 @@ struct D2Sparse {
     const uint32_t *row_kmers, *col_kmers;
     int measure;
     kmdb_sparse_rows* out;
+    kmdb_csr_dev* keep;          // not null: the CSR stays in HBM (kmdb_db2db_csr_device), `out` is not filled and nothing is decided
 };
 // what the sampled entry asks of the call (nullptr: one of the other two)
 struct D2Sampled {
@@ -428,10 +431,16 @@ extern "C" int kmdb_db2db_sparse_filtered(kmdb_db* db_row, kmdb_db* db_col, cons
     // (bounds and measures need the k-mer counts of both sides: a = the row sample's, b = the column sample's)
     if (kmdb_check_filters(who, filters, n_filters, row_sample_kmers && col_sample_kmers ? row_sample_kmers : nullptr, measure)) return 1;
     std::memset(out, 0, sizeof *out);
-    const D2Sparse sp{filters, n_filters, row_sample_kmers, col_sample_kmers, measure, out};
+    const D2Sparse sp{filters, n_filters, row_sample_kmers, col_sample_kmers, measure, out, nullptr};
     const int rc = db2db_call(who, db_row, db_col, nullptr, &sp, nullptr, opts);
     if (rc) kmdb_sparse_free(out);
     return rc;
+}
+
+int kmdb_db2db_csr_device(const char* who, kmdb_db* db_row, kmdb_db* db_col, kmdb_csr_dev* keep, const kmdb_opts* opts) {
+    if (!db_row || !db_col || !keep) return kmdb_set_error(std::string(who) + ": null argument");
+    const D2Sparse sp{nullptr, 0, nullptr, nullptr, -1, nullptr, keep};
+    return db2db_call(who, db_row, db_col, nullptr, &sp, nullptr, opts);
 }
 
 extern "C" int kmdb_db2db_sampled(kmdb_db* db_row, kmdb_db* db_col, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_sample_kmers,
@@ -707,6 +716,15 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
     uint32_t too_long = 0;
     HIP_TRY(hipMemcpy(&too_long, d_flag.get(), 4, hipMemcpyDeviceToHost));
     if (too_long) return kmdb_set_error(who + ": internal error");
+    for (unsigned char t : h_tiles) ds.tiles_touched += t != 0;
+    ds.nnz_device = nnz_dev;
+    ds.compact_ms = (double)ms_flags + (double)ms_compact;
+    if (sp->keep) {                                               // the CSR stays where it is: nothing crosses, nothing is decided here
+        sp->keep->row_ptr = std::move(d_ptr); sp->keep->col = std::move(d_col); sp->keep->val = std::move(d_val);
+        sp->keep->n_rows = nr; sp->keep->nnz = nnz_dev;
+        ds.nnz = nnz_dev;
+        return 0;
+    }
     kmdb_sparse_rows* o = sp->out;
     o->n_rows = nr;
     o->nnz = nnz_dev;
@@ -719,10 +737,7 @@ static int db2db_impl(const char* who_, kmdb_db* db_row, kmdb_db* db_col, uint32
         HIP_TRY(hipMemcpy(o->col, d_col.get(), nnz_dev * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(o->val, d_val.get(), nnz_dev * 4, hipMemcpyDeviceToHost));
     }
-    for (unsigned char t : h_tiles) ds.tiles_touched += t != 0;
-    ds.nnz_device = nnz_dev;
     ds.d2h_bytes = (nr + 1) * 8 + nnz_dev * 8;
-    ds.compact_ms = (double)ms_flags + (double)ms_compact;
     // the exact decision: every cell the widened bounds let through, by the reference's arithmetic (a = row sample, b = column sample)
     if ((sp->n_filters || sp->measure >= 0) &&
         kmdb_sparse_decide(who_, o, sp->filters, sp->n_filters, sp->row_kmers, sp->col_kmers, sp->measure, (int)er.kmer_length)) return 1;

@@ -41,6 +41,9 @@ public:
         return 0;
     }
     void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; bytes_ = 0; }
+    // the array of a buffer of another element type becomes this one's (what this one held goes first); `o` is left empty
+    template <class U> void take(DevBuf<U>& o) { reset(); bytes_ = o.bytes(); p_ = (T*)o.release(); }
+    T* release() { bytes_ = 0; return std::exchange(p_, nullptr); }
     T* get() const { return p_; }
     size_t bytes() const { return bytes_; }
     operator T*() const { return p_; }

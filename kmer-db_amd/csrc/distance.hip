@@ -14,7 +14,9 @@
 // matrix cell piece_lo + ci, consecutive lanes read consecutive uint32, nothing is classified or parsed and the names come from a blob.
 // A third source is the row-major nq x N rectangle of a batch of new2all queries (RowCells: kmdb_distance_take_new2all_batch*,
 // kmdb_distance_take_rows_device and kmdb_distance_query_rows) — the same, with whole rows of N cells, a = the QUERY's own count and the
-// names of the queries.
+// names of the queries.  A fourth is a CSR in HBM over a run of rows (CsrCells: kmdb_distance_parts_*, kmdb_distance_take_csr_device and
+// kmdb_distance_csr_rows) — a block row of the all2all-parts grid, gathered from its cells' CSRs by the two kernels at the end of this file:
+// output cell ci IS entry piece_lo + ci, its row found in the rebased row_ptr, a = the ROW sample's own count.
 //
 // Every position is below the piece's length by construction and clamped to it again where it is used: damaged text is declined
 // (KMDB_DISTANCE_DECLINED) or parsed as the host loop parses it, and never read or written outside the buffers.
@@ -91,6 +93,11 @@ struct DistParams {
     // first_row n; names / name_off are the QUERIES' ([rows_nq + 1])
     const uint32_t* row_counts;     // [rows_nq] the queries' own k-mer counts
     uint64_t rows_nq;
+    // a CSR as the source of cells (CsrCells): entry piece_lo + ci of csr_col / csr_val, oc = the piece's row_ptr rebased; names / name_off /
+    // row_counts / rows_nq are the ROW samples' as for RowCells
+    const uint32_t* csr_col;        // 0-based global columns, ascending within a row
+    const uint32_t* csr_val;
+    uint64_t csr_nnz;
 };
 
 // a cell the host decides: where its text goes, and what it is
@@ -405,6 +412,80 @@ __global__ void __launch_bounds__(DT) dist_query_row_sizes_kernel(DistParams p) 
     p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
 }
 
+struct CsrCells {
+    // every cell of the piece is an entry of the CSR: consecutive lanes read consecutive col / val; the row is the last one whose first entry is
+    // at or below ci (64-bit offsets throughout: row_ptr, piece_lo and the entry index)
+    static __device__ Cell at(const DistParams& p, uint64_t ci) {
+        Cell x{};
+        const uint64_t e = min(p.piece_lo + ci, p.csr_nnz - 1);   // clamped to the entries
+        const uint32_t row = dev_row_of(p.oc, p.R, ci);
+        const uint32_t col = min(p.csr_col[e], p.n - 1);            // (a column >= n is refused when the CSR is taken)
+        x.row = row;
+        x.col = col;
+        x.a = p.row_counts[min(p.first_row + row, p.rows_nq - 1)];
+        x.count = p.csr_val[e];
+        x.emit = x.count > 0;                                       // (a stored zero is the pair "col:0" of the text: not written)
+        x.prefix = col + 1;
+        return x;
+    }
+    static __device__ __forceinline__ const unsigned char* name(const DistParams& p, uint32_t r, uint32_t* nlen) { return RowCells::name(p, r, nlen); }
+};
+
+// a lane per row of a piece of the CSR (and one for the end): the first output cell of the row = row_ptr rebased to the piece — no scan —, and
+// the bytes of the row sample's name, the separator behind it and the '\n'
+__global__ void __launch_bounds__(DT) dist_csr_row_sizes_kernel(DistParams p, const uint64_t* row_ptr) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r > p.R) return;
+    const uint64_t base = row_ptr[p.first_row];
+    const uint64_t at = row_ptr[p.first_row + r];
+    p.oc[r] = at >= base ? at - base : 0;
+    if (r == p.R) { p.rowfix[r] = 0; return; }
+    const uint64_t s = min(p.first_row + r, p.rows_nq - 1);
+    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
+}
+
+// what a CSR must be to be read without a fault: row_ptr ascending from 0 (a lane per row), every column below n (a lane per entry)
+enum : unsigned int { CSR_BAD_PTR = 1, CSR_BAD_COL = 2 };
+__global__ void __launch_bounds__(DT) dist_csr_check_kernel(const uint64_t* row_ptr, uint64_t nr, const uint32_t* col, uint64_t nnz, uint32_t n, unsigned int* bad,
+                                                            unsigned int* bad_col) {
+    const uint64_t i = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (i < nr && row_ptr[i] > row_ptr[i + 1]) atomicOr(bad, CSR_BAD_PTR);
+    if (i == 0 && (row_ptr[0] != 0 || row_ptr[nr] != nnz)) atomicOr(bad, CSR_BAD_PTR);
+    if (i < nnz && col[i] >= n) { atomicOr(bad, CSR_BAD_COL); atomicMax(bad_col, col[i]); }
+}
+
+// ---- the gather: the CSRs of the cells of a block row -> ONE CSR --------------------------------------------------------------------------
+// merged row_ptr[r] = the sum over the cells of their row_ptr[r] (a sum of exclusive sums is the exclusive sum of the sums): a lane per row
+__global__ void __launch_bounds__(DT) dist_gather_ptr_kernel(const uint64_t* const* cell_ptr, uint32_t n_cells, uint64_t nr, uint64_t* merged, uint64_t* base) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r > nr) return;
+    uint64_t sum = 0;
+    for (uint32_t c = 0; c < n_cells; ++c) sum += cell_ptr[c][r];
+    merged[r] = sum;
+    base[r] = sum;
+}
+
+// One cell into its place, a lane per ENTRY of the cell: its row by search of the cell's row_ptr (a row of 10^5 entries is 10^5 lanes, 10^5
+// rows without entries are never visited), its place = where the cells before this one left the row (base[row]) + its rank in the cell's row,
+// its column shifted by the samples of the earlier parts.  Consecutive lanes read and — inside a row — write consecutive words.
+__global__ void __launch_bounds__(DT) dist_gather_copy_kernel(const uint64_t* ptr, const uint32_t* col, const uint32_t* val, uint64_t nr, uint64_t nnz, uint32_t shift,
+                                                              const uint64_t* base, uint32_t* out_col, uint32_t* out_val, uint64_t out_nnz) {
+    const uint64_t e = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (e >= nnz) return;
+    const uint32_t r = dev_row_of(ptr, (uint32_t)nr, e);
+    const uint64_t first = ptr[r];
+    const uint64_t at = base[r] + (e >= first ? e - first : 0);
+    if (at >= out_nnz) return;                                  // (cannot happen: the merged row_ptr is the sum of the cells')
+    out_col[at] = col[e] + shift;
+    out_val[at] = val[e];
+}
+
+// ... and the rows' places move behind it: a lane per row
+__global__ void __launch_bounds__(DT) dist_gather_advance_kernel(const uint64_t* ptr, uint64_t nr, uint64_t* base) {
+    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
+    if (r < nr) base[r] += ptr[r + 1] - ptr[r];
+}
+
 template <class Source>
 __global__ void __launch_bounds__(DT) dist_measure_kernel(DistParams p) {
     const uint64_t ci = (uint64_t)blockIdx.x * DT + threadIdx.x;
@@ -541,10 +622,25 @@ struct kmdb_distance {
     DevBuf<uint32_t> d_row_counts;      // [rows_nq] the queries' own counts
     DevBuf<unsigned char> d_qnames;
     DevBuf<uint64_t> d_qname_off;
+    // a CSR taken as the source of cells: the caller's (kmdb_distance_take_csr_device) or the handle's own, gathered from the cells of a block row
+    // (kmdb_distance_parts_*).  The row samples' counts and names share d_row_counts / d_qnames / d_qname_off with the query rows.
+    bool csr_taken = false;
+    bool parts_open = false;            // a block row was begun and its cells are not gathered yet
+    const uint64_t* csr_ptr = nullptr;
+    const uint32_t *csr_col = nullptr, *csr_val = nullptr;
+    uint64_t csr_nr = 0, csr_nnz = 0;
+    std::vector<uint64_t> csr_host_ptr; // [csr_nr + 1] the row_ptr on the host: the pieces' sizes
+    DevBuf<uint64_t> own_ptr;
+    DevBuf<uint32_t> own_col, own_val;
+    struct PartCell { kmdb_csr_dev csr; uint32_t shift = 0; };
+    std::vector<PartCell> parts;
+    uint64_t parts_bytes = 0;           // the cells' CSRs held now
     kmdb_distance_stats st{};
+    kmdb_distance_parts_stats pst{};
 };
 
 static int dist_splice(kmdb_distance* d, std::vector<HostCell>& cells, const char* dev_text, size_t dev_len, kmdb_distance_out* out, uint64_t* written);
+static void dist_csr_drop(kmdb_distance* d);       // a take of another source drops the CSR: the row samples' arrays are shared
 
 namespace {
 
@@ -1013,7 +1109,7 @@ static int dist_take_batch(kmdb_distance* d, kmdb_db* db, size_t nq, const char*
     if (e.qs_count > 1) return kmdb_set_error(who + "a query shard holds partial sums and partial k-mer counts (sum the shards' rows with kmdb_new2all_batch_device and hand them to kmdb_distance_take_rows_device)");
     if (!e.n_buckets || !e.slots) return kmdb_set_error(who + "database was uploaded without hashtables");
     if (nq >= (1ull << 31)) return kmdb_set_error(who + "too many queries in one batch");
-    d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0;
+    d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0; dist_csr_drop(d);
     HIP_TRY(hipSetDevice(d->device));
     const uint64_t cells = (uint64_t)nq * e.N;
     if (d->own_rows.bytes() < cells * 4 || !d->own_rows) DEV_ALLOC(d->own_rows, (size_t)std::max<uint64_t>(1, cells));
@@ -1070,7 +1166,7 @@ extern "C" int kmdb_distance_take_rows_device(kmdb_distance* d, const void* rows
     try {
         if (dist_rows_check(d, who)) return 1;
         if (nq >= (1ull << 31)) return kmdb_set_error(who + "too many queries in one batch");
-        d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0;
+        d->rows_taken = false; d->rows = nullptr; d->rows_nq = 0; dist_csr_drop(d);
         HIP_TRY(hipSetDevice(d->device));
         if (dist_take_queries(d, query_kmers, nq, names, who)) return 1;
         d->rows = (const uint32_t*)rows_dev; d->rows_nq = nq; d->rows_taken = true;
@@ -1149,6 +1245,350 @@ extern "C" int kmdb_distance_query_rows(kmdb_distance* d, uint64_t row_lo, uint6
         rc = dist_query_rows(d, row_lo, row_hi, out);
     } catch (const std::exception& e) {
         rc = kmdb_set_error(std::string("kmdb_distance_query_rows: ") + e.what());
+    }
+    if (rc) kmdb_distance_out_free(out);
+    return rc;
+}
+
+// ---- a CSR as the source of cells: a block row of the all2all-parts grid -----------------------------------------------------------------
+static int dist_csr_check(const kmdb_distance* d, const std::string& who) {
+    if (!(d->flags & KMDB_DISTANCE_SPARSE_OUT)) return kmdb_set_error(who + "the handle was not begun with KMDB_DISTANCE_SPARSE_OUT: the entries of a CSR are written as column:value pairs");
+    if (d->flags & KMDB_DISTANCE_TRIANGLE) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_TRIANGLE: a CSR holds the entries it holds");
+    if (d->flags & KMDB_DISTANCE_SPARSE_IN) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_SPARSE_IN: a CSR is no text of column:count pairs");
+    if (d->flags & KMDB_DISTANCE_PHYLIP) return kmdb_set_error(who + "the handle was begun with KMDB_DISTANCE_PHYLIP: phylip output from sparse input is declined");
+    return 0;
+}
+
+static void dist_csr_drop(kmdb_distance* d) {
+    d->csr_taken = false; d->parts_open = false;
+    d->csr_ptr = nullptr; d->csr_col = nullptr; d->csr_val = nullptr; d->csr_nr = 0; d->csr_nnz = 0;
+    d->csr_host_ptr.clear();
+    d->parts.clear(); d->parts_bytes = 0;
+    dev_reset(d->own_ptr, d->own_col, d->own_val);
+}
+
+// the CSR at (row_ptr, col, val) becomes the source of cells once the device found it sound: row_ptr ascending from 0 to nnz, every column < n
+static int dist_csr_adopt(kmdb_distance* d, const uint64_t* row_ptr, const uint32_t* col, const uint32_t* val, uint64_t nr, const std::string& who) {
+    hipStream_t st = d->stream;
+    const uint64_t n = d->counts.size();
+    std::vector<uint64_t> h_ptr(nr + 1, 0);
+    if (nr) {
+        if (!row_ptr) return kmdb_set_error(who + std::to_string(nr) + " rows and a null row_ptr");
+        HIP_TRY(hipMemcpyAsync(h_ptr.data(), row_ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const uint64_t nnz = h_ptr[nr];
+    if (nnz && (!col || !val)) return kmdb_set_error(who + "the rows hold " + std::to_string(nnz) + " entries and a null pointer was taken");
+    if (nr) {
+        DevBuf<unsigned int> d_bad;
+        DEV_ALLOC(d_bad, 2);
+        HIP_TRY(hipMemsetAsync(d_bad.get(), 0, 8, st));
+        hipLaunchKernelGGL(dist_csr_check_kernel, dim3(blocks_for(std::max(nr, nnz))), dim3(DT), 0, st, row_ptr, nr, col, nnz, (uint32_t)n, d_bad.get(), d_bad.get() + 1);
+        HIP_TRY(hipGetLastError());
+        unsigned int bad[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(bad, d_bad.get(), 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad[0] & CSR_BAD_PTR) return kmdb_set_error(who + "row_ptr does not ascend from 0 to its last value");
+        if (bad[0] & CSR_BAD_COL) return kmdb_set_error(who + "a column of the CSR (" + std::to_string(bad[1]) + ") is not below the " + std::to_string(n) + " columns the handle was begun with");
+    }
+    d->csr_ptr = row_ptr; d->csr_col = col; d->csr_val = val; d->csr_nr = nr; d->csr_nnz = nnz;
+    d->csr_host_ptr = std::move(h_ptr);
+    d->csr_taken = true;
+    return 0;
+}
+
+extern "C" int kmdb_distance_parts_begin_rows(kmdb_distance* d, size_t nr, const uint32_t* row_kmers, const char* const* names) {
+    const std::string who = "kmdb_distance_parts_begin_rows: ";
+    if (!d || (nr && (!row_kmers || !names))) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_csr_check(d, who)) return 1;
+        if (nr >= (1ull << 31)) return kmdb_set_error(who + "too many rows in one block row");
+        HIP_TRY(hipSetDevice(d->device));
+        dist_csr_drop(d);                                       // the block row before goes first
+        if (dist_take_queries(d, row_kmers, nr, names, who)) return 1;
+        d->rows_taken = false; d->rows = nullptr;               // (the row samples' arrays are shared with the query rows: one source at a time)
+        d->rows_nq = nr; d->csr_nr = nr; d->parts_open = true;
+        d->pst.block_rows += 1;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+// what both adds ask of the handle and of a database
+static int dist_parts_add_check(kmdb_distance* d, kmdb_db* db, uint64_t col_shift, const std::string& who, bool rows_side) {
+    if (dist_csr_check(d, who)) return 1;
+    if (!d->parts_open) return kmdb_set_error(who + "no block row is open (kmdb_distance_parts_begin_rows; the rows asked for close it)");
+    kmdb_engine_view e;
+    if (kmdb_engine_get(db, &e)) return 1;
+    if (e.device != d->device) return kmdb_set_error(who + "the database lives on device " + std::to_string(e.device) + ", the handle on device " + std::to_string(d->device));
+    if (e.qs_count > 1) return kmdb_set_error(who + "a query shard holds only its own buckets (upload the parts with kmdb_db_upload)");
+    if (rows_side && e.N != d->csr_nr) return kmdb_set_error(who + "the row database holds " + std::to_string(e.N) + " samples, the block row was begun with " + std::to_string(d->csr_nr));
+    if (!rows_side && col_shift + e.N > d->counts.size())
+        return kmdb_set_error(who + "col_shift " + std::to_string(col_shift) + " + " + std::to_string(e.N) + " samples lie behind the " + std::to_string(d->counts.size()) + " columns the handle was begun with");
+    return 0;
+}
+
+static int dist_parts_keep(kmdb_distance* d, kmdb_distance::PartCell&& cell) {
+    const uint64_t bytes = (cell.csr.n_rows + 1) * 8 + cell.csr.nnz * 8;
+    d->parts_bytes += bytes;
+    d->pst.cells_in += cell.csr.nnz; d->pst.grid_cells += 1;
+    d->pst.peak_bytes = std::max<uint64_t>(d->pst.peak_bytes, d->parts_bytes);
+    d->parts.push_back(std::move(cell));
+    return 0;
+}
+
+extern "C" int kmdb_distance_parts_add_db2db(kmdb_distance* d, kmdb_db* db_row, kmdb_db* db_col, uint64_t col_shift, const kmdb_opts* opts) {
+    const std::string who = "kmdb_distance_parts_add_db2db: ";
+    if (!d || !db_row || !db_col) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_parts_add_check(d, db_row, 0, who, true) || dist_parts_add_check(d, db_col, col_shift, who, false)) return 1;
+        kmdb_opts o{};
+        if (opts) o = *opts;
+        else { o.abi_version = KMDB_ABI_VERSION; o.shard_count = 1; }
+        o.device = d->device;
+        kmdb_distance::PartCell cell;
+        cell.shift = (uint32_t)col_shift;
+        // (the library's out-of-memory error passes through: the caller evicts resident parts and repeats)
+        if (kmdb_db2db_csr_device("kmdb_distance_parts_add_db2db", db_row, db_col, &cell.csr, &o)) return 1;
+        return dist_parts_keep(d, std::move(cell));
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_parts_add_all2all(kmdb_distance* d, kmdb_db* db, uint64_t col_shift, const kmdb_opts* opts) {
+    const std::string who = "kmdb_distance_parts_add_all2all: ";
+    if (!d || !db) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_parts_add_check(d, db, 0, who, true) || dist_parts_add_check(d, db, col_shift, who, false)) return 1;
+        kmdb_opts o{};
+        if (opts) o = *opts;
+        else { o.abi_version = KMDB_ABI_VERSION; o.shard_count = 1; }
+        o.device = d->device;
+        kmdb_distance::PartCell cell;
+        cell.shift = (uint32_t)col_shift;
+        if (kmdb_all2all_csr_device("kmdb_distance_parts_add_all2all", db, &cell.csr, &o)) return 1;
+        return dist_parts_keep(d, std::move(cell));
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_parts_add_csr_device(kmdb_distance* d, const void* row_ptr_dev, const void* col_dev, const void* val_dev, uint64_t n_cols, uint64_t col_shift) {
+    const std::string who = "kmdb_distance_parts_add_csr_device: ";
+    if (!d) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_csr_check(d, who)) return 1;
+        if (!d->parts_open) return kmdb_set_error(who + "no block row is open (kmdb_distance_parts_begin_rows; the rows asked for close it)");
+        if (col_shift + n_cols > d->counts.size())
+            return kmdb_set_error(who + "col_shift " + std::to_string(col_shift) + " + " + std::to_string(n_cols) + " columns lie behind the " + std::to_string(d->counts.size()) + " columns the handle was begun with");
+        HIP_TRY(hipSetDevice(d->device));
+        hipStream_t st = d->stream;
+        const uint64_t nr = d->csr_nr;
+        if (nr && !row_ptr_dev) return kmdb_set_error(who + std::to_string(nr) + " rows and a null row_ptr");
+        kmdb_distance::PartCell cell;
+        cell.shift = (uint32_t)col_shift;
+        cell.csr.n_rows = nr;
+        DEV_ALLOC_BYTES(cell.csr.row_ptr, (nr + 1) * 8);
+        if (nr) HIP_TRY(hipMemcpyAsync(cell.csr.row_ptr.get(), row_ptr_dev, (nr + 1) * 8, hipMemcpyDeviceToDevice, st));
+        else HIP_TRY(hipMemsetAsync(cell.csr.row_ptr.get(), 0, 8, st));
+        uint64_t nnz = 0;
+        HIP_TRY(hipMemcpyAsync(&nnz, (const uint64_t*)cell.csr.row_ptr.get() + nr, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (nnz && (!col_dev || !val_dev)) return kmdb_set_error(who + "the rows hold " + std::to_string(nnz) + " entries and a null pointer was given");
+        if (nnz >= (1ull << 40)) return kmdb_set_error(who + "row_ptr does not ascend from 0 to its last value");
+        // the cell is checked where it was given (row_ptr ascending from 0, every column below n_cols) and then copied
+        DevBuf<unsigned int> d_bad;
+        DEV_ALLOC(d_bad, 2);
+        HIP_TRY(hipMemsetAsync(d_bad.get(), 0, 8, st));
+        if (nr) hipLaunchKernelGGL(dist_csr_check_kernel, dim3(blocks_for(std::max(nr, nnz))), dim3(DT), 0, st, (const uint64_t*)row_ptr_dev, nr, (const uint32_t*)col_dev, nnz,
+                                   (uint32_t)n_cols, d_bad.get(), d_bad.get() + 1);
+        HIP_TRY(hipGetLastError());
+        unsigned int bad[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(bad, d_bad.get(), 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad[0] & CSR_BAD_PTR) return kmdb_set_error(who + "row_ptr does not ascend from 0 to its last value");
+        if (bad[0] & CSR_BAD_COL) return kmdb_set_error(who + "a column of the cell (" + std::to_string(bad[1]) + ") is not below its " + std::to_string(n_cols) + " columns");
+        cell.csr.nnz = nnz;
+        DEV_ALLOC_BYTES(cell.csr.col, nnz * 4); DEV_ALLOC_BYTES(cell.csr.val, nnz * 4);
+        if (nnz) {
+            HIP_TRY(hipMemcpyAsync(cell.csr.col.get(), col_dev, nnz * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(cell.csr.val.get(), val_dev, nnz * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return dist_parts_keep(d, std::move(cell));
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+// the cells of the open block row -> the handle's own CSR; the cells' CSRs are freed
+static int dist_parts_gather(kmdb_distance* d, const std::string& who) {
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    const uint64_t nr = d->csr_nr;
+    const uint32_t nc = (uint32_t)d->parts.size();
+    uint64_t nnz = 0;
+    for (auto& c : d->parts) {
+        if (c.csr.n_rows != nr) return kmdb_set_error(who + "internal error (a cell of " + std::to_string(c.csr.n_rows) + " rows in a block row of " + std::to_string(nr) + ")");
+        nnz += c.csr.nnz;
+    }
+    DevEvent g0, g1;
+    if (g0.create() || g1.create()) return 1;
+    DevBuf<uint64_t> d_base;
+    DevBuf<const uint64_t*> d_tab;
+    DEV_ALLOC(d->own_ptr, (size_t)nr + 1); DEV_ALLOC(d->own_col, (size_t)nnz); DEV_ALLOC(d->own_val, (size_t)nnz);
+    DEV_ALLOC(d_base, (size_t)nr + 1); DEV_ALLOC(d_tab, (size_t)std::max<uint32_t>(nc, 1));
+    d->pst.peak_bytes = std::max<uint64_t>(d->pst.peak_bytes, d->parts_bytes + (nr + 1) * 16 + nnz * 8);
+    std::vector<const uint64_t*> tab(std::max<uint32_t>(nc, 1), nullptr);
+    for (uint32_t c = 0; c < nc; ++c) tab[c] = (const uint64_t*)d->parts[c].csr.row_ptr.get();
+    HIP_TRY(hipEventRecord(g0, st));
+    HIP_TRY(hipMemcpyAsync(d_tab.get(), tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dist_gather_ptr_kernel, dim3(blocks_for(nr + 1)), dim3(DT), 0, st, (const uint64_t* const*)d_tab.get(), nc, nr, d->own_ptr.get(), d_base.get());
+    for (uint32_t c = 0; c < nc; ++c) {
+        const kmdb_csr_dev& x = d->parts[c].csr;
+        if (!x.nnz) continue;
+        hipLaunchKernelGGL(dist_gather_copy_kernel, dim3(blocks_for(x.nnz)), dim3(DT), 0, st, (const uint64_t*)x.row_ptr.get(), (const uint32_t*)x.col.get(),
+                           (const uint32_t*)x.val.get(), nr, x.nnz, d->parts[c].shift, (const uint64_t*)d_base.get(), d->own_col.get(), d->own_val.get(), nnz);
+        if (c + 1 < nc) hipLaunchKernelGGL(dist_gather_advance_kernel, dim3(blocks_for(nr)), dim3(DT), 0, st, (const uint64_t*)x.row_ptr.get(), nr, d_base.get());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g1, st));
+    HIP_TRY(hipStreamSynchronize(st));                          // (tab and the cells live until here)
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, g0, g1));
+    d->pst.gather_ms += ms;
+    d->parts.clear(); d->parts_bytes = 0; d->parts_open = false;
+    if (dist_csr_adopt(d, d->own_ptr.get(), d->own_col.get(), d->own_val.get(), nr, who)) return 1;
+    if (d->csr_nnz != nnz) { d->csr_taken = false; return kmdb_set_error(who + "internal error (the gathered rows do not add up to the cells)"); }
+    return 0;
+}
+
+extern "C" int kmdb_distance_take_csr_device(kmdb_distance* d, const void* row_ptr_dev, const void* col_dev, const void* val_dev, size_t nr, const uint32_t* row_kmers,
+                                             const char* const* names) {
+    const std::string who = "kmdb_distance_take_csr_device: ";
+    if (!d || (nr && (!row_kmers || !names))) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_csr_check(d, who)) return 1;
+        if (nr >= (1ull << 31)) return kmdb_set_error(who + "too many rows in one block row");
+        HIP_TRY(hipSetDevice(d->device));
+        dist_csr_drop(d);
+        if (dist_take_queries(d, row_kmers, nr, names, who)) return 1;
+        d->rows_taken = false; d->rows = nullptr; d->rows_nq = nr;
+        return dist_csr_adopt(d, (const uint64_t*)row_ptr_dev, (const uint32_t*)col_dev, (const uint32_t*)val_dev, nr, who);
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+// the source is there: taken, or gathered now from the cells of the open block row
+static int dist_csr_ready(kmdb_distance* d, const std::string& who) {
+    if (dist_csr_check(d, who)) return 1;
+    if (d->parts_open) return dist_parts_gather(d, who);
+    if (!d->csr_taken) return kmdb_set_error(who + "no CSR was taken (kmdb_distance_parts_begin_rows and its adds, kmdb_distance_take_csr_device)");
+    return 0;
+}
+
+extern "C" int kmdb_distance_csr_device(kmdb_distance* d, const void** row_ptr_dev, const void** col_dev, const void** val_dev, uint64_t* nr) {
+    const std::string who = "kmdb_distance_csr_device: ";
+    if (!d || !row_ptr_dev || !col_dev || !val_dev || !nr) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_csr_ready(d, who)) return 1;
+        *row_ptr_dev = d->csr_ptr; *col_dev = d->csr_col; *val_dev = d->csr_val; *nr = d->csr_nr;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_csr_row_ptr(kmdb_distance* d, uint64_t* out) {
+    const std::string who = "kmdb_distance_csr_row_ptr: ";
+    if (!d || !out) return kmdb_set_error(who + "null argument");
+    try {
+        if (dist_csr_ready(d, who)) return 1;
+        std::copy(d->csr_host_ptr.begin(), d->csr_host_ptr.end(), out);
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(who + e.what());
+    }
+}
+
+extern "C" int kmdb_distance_parts_stats_get(const kmdb_distance* d, kmdb_distance_parts_stats* out) {
+    if (!d || !out) return kmdb_set_error("kmdb_distance_parts_stats_get: null argument");
+    *out = d->pst;
+    return 0;
+}
+
+static int dist_csr_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    const char* who = "kmdb_distance_csr_rows: ";
+    const uint64_t n = d->counts.size();
+    if (dist_csr_check(d, who)) return 1;
+    if (row_lo > row_hi) return kmdb_set_error(std::string(who) + "row_lo > row_hi");
+    if (!d->parts_open && !d->csr_taken) return kmdb_set_error(std::string(who) + "no CSR was taken (kmdb_distance_parts_begin_rows and its adds, kmdb_distance_take_csr_device)");
+    if (row_hi > d->csr_nr) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(d->csr_nr) + " rows");
+    if (dist_csr_ready(d, who)) return 1;
+    d->st.calls += 1;
+    if (row_lo == row_hi) {
+        out->text = (char*)malloc(1);
+        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
+        return 0;
+    }
+    const uint32_t R = (uint32_t)(row_hi - row_lo);
+    const uint64_t piece_lo = d->csr_host_ptr[row_lo], n_cells = d->csr_host_ptr[row_hi] - piece_lo;    // 64-bit offsets, as row_ptr holds them
+    if (n_cells && n == 0) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " entries and the handle was begun with no column");
+    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
+    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
+    size_t mem_free = 0, mem_total = 0;
+    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
+                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
+    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
+    DevEvent begun;
+    if (begun.create()) return 1;
+    DevBuf<uint64_t> d_oc, d_rowfix;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<void> d_tmp;
+    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
+    HIP_TRY(hipEventRecord(begun, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
+    DistParams p{};
+    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 0; p.first_row = row_lo;
+    p.n_filters = (int)d->filters.size();
+    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
+    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
+    p.csr_col = d->csr_col; p.csr_val = d->csr_val; p.csr_nnz = d->csr_nnz; p.piece_lo = piece_lo;
+    p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->csr_nr; p.n_cells = n_cells;
+    hipLaunchKernelGGL(dist_csr_row_sizes_kernel, dim3(blocks_for((uint64_t)R + 1)), dim3(DT), 0, st, p, d->csr_ptr);
+    HIP_TRY(hipGetLastError());
+    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
+    uint64_t oc_all = 0, fix_bytes = 0;
+    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
+    DistTail t{};
+    if (dist_measure_format<CsrCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
+    out->rows = R;
+    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
+    d->st.bytes_in += n_cells * 8; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
+    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+    d->pst.cells_written += t.counters[1]; d->pst.host_cells += t.n_host;
+    d->pst.peak_bytes = std::max<uint64_t>(d->pst.peak_bytes, (d->csr_ptr == d->own_ptr.get() ? (d->csr_nr + 1) * 8 + d->csr_nnz * 8 : 0) + held);
+    return 0;
+}
+
+extern "C" int kmdb_distance_csr_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
+    if (!d || !out) return kmdb_set_error("kmdb_distance_csr_rows: null argument");
+    out->text = nullptr; out->len = 0; out->rows = 0;
+    int rc;
+    try {
+        rc = dist_csr_rows(d, row_lo, row_hi, out);
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string("kmdb_distance_csr_rows: ") + e.what());
     }
     if (rc) kmdb_distance_out_free(out);
     return rc;

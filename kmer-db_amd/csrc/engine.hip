@@ -517,7 +517,7 @@ void kmdb_dev_bounds(const kmdb_cell_filter* filters, size_t n_filters, int kmer
 }
 
 static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters, size_t n_filters,
-                       const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
+                       const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts, kmdb_csr_dev* keep = nullptr);
 
 int kmdb_check_filters(const char* who, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure) {
     if ((n_filters && !filters) || ((n_filters || measure >= 0) && !sample_kmers)) return kmdb_set_error(std::string(who) + ": null argument");
@@ -530,6 +530,12 @@ int kmdb_check_filters(const char* who, const kmdb_cell_filter* filters, size_t 
 
 extern "C" int kmdb_all2all_sparse(kmdb_db* db, kmdb_sparse_rows* out, const kmdb_opts* opts) {
     return sparse_impl(db, false, nullptr, 0, ~0ull, nullptr, 0, nullptr, -1, out, opts);
+}
+
+int kmdb_all2all_csr_device(const char* who, kmdb_db* db, kmdb_csr_dev* keep, const kmdb_opts* opts) {
+    if (!db || !keep) return kmdb_set_error(std::string(who) + ": null argument");
+    kmdb_sparse_rows none{};
+    return sparse_impl(db, false, nullptr, 0, ~0ull, nullptr, 0, nullptr, -1, &none, opts, keep);
 }
 
 extern "C" int kmdb_all2all_sparse_filtered(kmdb_db* db, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
@@ -601,7 +607,7 @@ int kmdb_sparse_decide(const char* who, kmdb_sparse_rows* out, const kmdb_cell_f
 
 // from_cells: compact the caller's cells [cell_lo, cell_hi) (dense_dev points at cell_lo); else accumulate the whole triangle first
 static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint64_t cell_lo, uint64_t cell_hi, const kmdb_cell_filter* filters, size_t n_filters,
-                       const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+                       const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts, kmdb_csr_dev* keep) {
     if (!db || !out) return kmdb_set_error("kmdb_all2all_sparse: null argument");
     std::memset(out, 0, sizeof *out);
     HIP_TRY(hipSetDevice(db->device));
@@ -663,6 +669,12 @@ static int sparse_impl(kmdb_db* db, bool from_cells, const void* dense_dev, uint
     if (row_hi > row_lo) hipLaunchKernelGGL(row_compact_kernel, dim3((unsigned)(row_hi - row_lo)), dim3(256), 0, st, cellsp, row_lo, cell_lo, cell_hi, row_ptr, col, val, df);
     rc = finish_stats(db, st);
     if (rc) return rc;
+    if (keep) {                                                   // the CSR stays in HBM (kmdb_all2all_csr_device)
+        keep->row_ptr.take(row_ptr); keep->col.take(col); keep->val.take(val);
+        keep->n_rows = N; keep->nnz = nnz;
+        kmdb_release_staging(db);
+        return 0;
+    }
     out->n_rows = N;
     out->nnz = nnz;
     out->row_ptr = (uint64_t*)std::malloc((N + 1) * 8);

@@ -74,6 +74,18 @@ void kmdb_dev_bounds(const kmdb_cell_filter* filters, size_t n_filters, int kmer
 int kmdb_sparse_decide(const char* who, kmdb_sparse_rows* out, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers,
                        const uint32_t* col_kmers, int measure, int kmer_length);
 
+// ---- a cell's CSR kept in HBM (distance.hip gathers the cells of a block row of the all2all-parts grid from these)
+struct kmdb_csr_dev {
+    DevBuf<void> row_ptr;          // uint64[n_rows + 1]
+    DevBuf<void> col, val;         // uint32[nnz]: columns local to the cell, ascending within a row; counts > 0
+    uint64_t n_rows = 0, nnz = 0;
+};
+// kmdb_db2db_sparse_filtered without bounds and without the copy to the host: the cell (db_row, db_col) compacted where it is, complete when
+// the call returns.  Retries once without the list stores on out-of-memory, as every db2db entry.  0, or 1 with the error set.
+int kmdb_db2db_csr_device(const char* who, kmdb_db* db_row, kmdb_db* db_col, kmdb_csr_dev* keep, const kmdb_opts* opts);
+// kmdb_all2all_sparse the same way: the lower triangle of one database
+int kmdb_all2all_csr_device(const char* who, kmdb_db* db, kmdb_csr_dev* keep, const kmdb_opts* opts);
+
 // ---- the -sample-rows selection on a rectangle of two sample sets (engine.hip over sample_rows.hip; db2db.hip selects its cell with it)
 struct kmdb_sample_stats;
 // argument checks of a sampled call, before any device work (sample_kmers: null when the caller lacks one of the count arrays)

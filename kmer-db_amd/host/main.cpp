@@ -8,6 +8,7 @@
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <sample-list> <out>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
 //     kmer-db-amd all2all-parts [-min ...] [-max ...] <db-list> <out.csv>
+//     kmer-db-amd all2all-parts [-min ...] [-max ...] [-gpus W] -distance <measure> <db-list> <out>
 //     kmer-db-amd minhash    [-f <fraction>] [-k <kmer-length>] [-alphabet <name>] <samples>
 //     kmer-db-amd build      [-k <kmer-length>] [-f <fraction>] [-alphabet <name>] [-multisample-fasta | -from-minhash] <samples> <db>
 //     kmer-db-amd build      -extend-from <old.db> [-multisample-fasta | -from-minhash] <samples> <db>
@@ -506,7 +507,41 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
 // db2db_sp + compact2 of two (similarity_calculator.cpp:1225-1540, console_all2all_parts.cpp:179-195 -> kmdb_db2db_sparse_filtered).  Row k of row part i is written as the
 // concatenation of its cells' sparse rows with the column index shifted by the samples of the earlier parts
 // (:292-310), which is the sparse lower-triangular matrix of the whole collection.
+// the list of database files and what every mode over the grid needs of the whole collection (console_all2all_parts.cpp:60-100): every database
+// is read once up front for its names and k-mer counts
+struct PartsCollection {
+    std::vector<std::string> files, names;
+    std::vector<uint64_t> counts, part_n;
+    uint32_t k = 0;
+    double fraction = 0;
+};
+PartsCollection read_parts_collection(const std::string& list) {
+    PartsCollection pc;
+    std::ifstream lst(list);
+    if (!lst) throw std::runtime_error("Cannot open file with list of database files " + list);
+    for (std::string ln; std::getline(lst, ln);) {
+        while (!ln.empty() && (ln.back() == '\r' || ln.back() == ' ')) ln.pop_back();
+        if (!ln.empty()) pc.files.push_back(ln);
+    }
+    if (pc.files.empty()) throw std::runtime_error("Empty list of database files");
+    for (size_t i = 0; i < pc.files.size(); ++i) {
+        Db d;
+        if (kmdbh_db_load(pc.files[i].c_str(), 2, &d.h)) throw std::runtime_error("Cannot open k-mer database " + pc.files[i]);
+        if (i == 0) { pc.k = kmdbh_db_kmer_length(d.h); pc.fraction = kmdbh_db_fraction(d.h); }
+        else if (pc.k != kmdbh_db_kmer_length(d.h) || pc.fraction != kmdbh_db_fraction(d.h))
+            throw std::runtime_error("Databases have different k-mer lengths or fractions");
+        const uint64_t n = kmdbh_db_n_samples(d.h);
+        pc.part_n.push_back(n);
+        for (uint64_t s = 0; s < n; ++s) { pc.names.push_back(kmdbh_db_sample_name(d.h, s)); pc.counts.push_back(kmdbh_db_sample_kmers(d.h, s)); }
+    }
+    return pc;
+}
+
+int run_all2all_parts_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures);
+
 int run_all2all_parts(std::vector<std::string>& args, Common& c) {
+    const std::vector<std::string> measures = take_distance_measures(args);
+    if (!measures.empty()) return run_all2all_parts_distance(args, c, measures);
     std::string v;
     take_option(args, "-buffer", v);
     take_option(args, "-bubble-size", v);
@@ -515,30 +550,13 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
     c.sampler.parse(args);
     if (args.size() != 2) throw usage_error("all2all-parts");
     std::cerr << "All versus all comparison (parts)" << std::endl;
-    std::ifstream lst(args[0]);
-    if (!lst) throw std::runtime_error("Cannot open file with list of database files " + args[0]);
-    std::vector<std::string> files;
-    for (std::string ln; std::getline(lst, ln);) {
-        while (!ln.empty() && (ln.back() == '\r' || ln.back() == ' ')) ln.pop_back();
-        if (!ln.empty()) files.push_back(ln);
-    }
-    if (files.empty()) throw std::runtime_error("Empty list of database files");
+    PartsCollection pc = read_parts_collection(args[0]);
+    const std::vector<std::string>& files = pc.files;
+    const std::vector<std::string>& names = pc.names;
+    const std::vector<uint64_t>&counts = pc.counts, &part_n = pc.part_n;
+    const uint32_t k = pc.k;
+    const double fraction = pc.fraction;
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
-    // names and k-mer counts of the whole collection (:60-100): every database is read once up front
-    std::vector<std::string> names;
-    std::vector<uint64_t> counts, part_n;
-    uint32_t k = 0;
-    double fraction = 0;
-    for (size_t i = 0; i < files.size(); ++i) {
-        Db d;
-        if (kmdbh_db_load(files[i].c_str(), 2, &d.h)) throw std::runtime_error("Cannot open k-mer database " + files[i]);
-        if (i == 0) { k = kmdbh_db_kmer_length(d.h); fraction = kmdbh_db_fraction(d.h); }
-        else if (k != kmdbh_db_kmer_length(d.h) || fraction != kmdbh_db_fraction(d.h))
-            throw std::runtime_error("Databases have different k-mer lengths or fractions");
-        const uint64_t n = kmdbh_db_n_samples(d.h);
-        part_n.push_back(n);
-        for (uint64_t s = 0; s < n; ++s) { names.push_back(kmdbh_db_sample_name(d.h, s)); counts.push_back(kmdbh_db_sample_kmers(d.h, s)); }
-    }
     std::ofstream ofs(args[1], std::ios::binary);
     {
         char head[128];
@@ -2101,6 +2119,205 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
     return 0;
 }
 
+// ---- all2all-parts -distance <measure>: the measure's table straight from the block rows' CSRs in HBM ------------------------------------------
+// `all2all-parts L T` followed by `distance -sparse <bounds> <measure> T out`, byte for byte, without T.  Every cell of a block row leaves its CSR
+// in HBM (kmdb_distance_parts_add_db2db, kmdb_distance_parts_add_all2all), the first measure's handle gathers them into one CSR there, every
+// further measure borrows it (kmdb_distance_csr_device, kmdb_distance_take_csr_device), and the rows come back as text in pieces cut at row ends
+// by a budget of cells (KMDB_DISTANCE_CELLS_PER_PIECE, default 2^25, as for the other two -distance forms).  The cells are computed WITHOUT
+// bounds — the table T of the pair of commands is written without any — and the -min / -max list is read by the DISTANCE mode's rule.  The header
+// is the one run_distance writes for such a table: no ",db-samples", no total-kmers line.  The output is always the sparse form: the rows in
+// front of the table's first pair, which the distance loop writes as dense rows when -sparse is not given, are not reproduced.
+// -gpus W as in all2all-parts: the block rows dealt to W workers, every worker with its own handles on its device; this thread is the writer: it
+// takes the block rows in order and writes a piece while the device has the next one.
+int run_all2all_parts_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures) {
+    auto avail = metrics();
+    for (auto& m : measures)
+        if (!avail.count(m)) throw std::runtime_error("unknown measure: " + m);
+    for (auto& a : args) {
+        if (a == "-sample-rows") throw std::runtime_error("-distance does not go with -sample-rows: sampled rows are no rows of the grid's table");
+        if (a == "-phylip-out") throw std::runtime_error("-distance does not go with -phylip-out under all2all-parts: phylip output from sparse input is declined");
+    }
+    std::string v;
+    take_option(args, "-buffer", v);
+    take_option(args, "-bubble-size", v);
+    take_switch(args, "-sparse");
+    std::map<std::string, DistanceBound> bounds;
+    long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
+    take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
+    if (args.size() != 2) throw usage_error("all2all-parts");
+    uint64_t budget = 1ull << 25;
+    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+
+    std::cerr << "All versus all comparison (parts), " << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
+    const PartsCollection pc = read_parts_collection(args[0]);
+    const size_t n_parts = pc.files.size(), M = measures.size();
+    std::vector<uint64_t> row_start(n_parts + 1, 0);
+    for (size_t i = 0; i < n_parts; ++i) row_start[i + 1] = row_start[i] + pc.part_n[i];
+    const std::vector<uint32_t> counts32(pc.counts.begin(), pc.counts.end());
+    std::vector<const char*> name_ptrs(std::max<size_t>(pc.names.size(), 1), "");
+    for (size_t i = 0; i < pc.names.size(); ++i) name_ptrs[i] = pc.names[i].c_str();
+    std::vector<DistanceSetup> setups(M);
+    for (size_t mi = 0; mi < M; ++mi) {
+        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
+        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measures[mi]] = b; }
+        setups[mi].k = pc.k; setups[mi].sparse_out = true; setups[mi].counts = counts32;
+        setups[mi].measure = kmdbh_metric_id(measures[mi].c_str());
+        setups[mi].filters = distance_filters(own, kmer_lo, kmer_hi);
+    }
+    std::vector<std::ofstream> ofs(M);
+    std::vector<std::string> paths(M);
+    for (size_t mi = 0; mi < M; ++mi) {
+        paths[mi] = M == 1 ? args[1] : args[1] + "." + measures[mi];
+        ofs[mi].open(paths[mi], std::ios::binary);
+        ofs[mi] << "kmer-length: " << pc.k << " fraction: " << pc.fraction << " ,";
+        for (auto& nm : pc.names) ofs[mi] << nm << ',';
+        ofs[mi] << std::endl;
+    }
+
+    const int have = std::max(1, kmdb_device_count());
+    const size_t W = c.gpus > 0 ? std::min<size_t>((size_t)c.gpus, n_parts) : 1;
+    struct Worker {
+        kmdb_opts o{};
+        std::vector<std::unique_ptr<Db>> resident;
+        std::vector<std::unique_ptr<DistanceHandle>> h;            // one per measure, on the worker's device; [0] gathers, the others borrow
+    };
+    std::vector<Worker> workers(W);
+    for (size_t t = 0; t < W; ++t) {
+        workers[t].o.abi_version = KMDB_ABI_VERSION; workers[t].o.shard_count = 1;
+        workers[t].o.device = c.device + (int)(t % (size_t)std::max(1, have - c.device));
+        workers[t].resident.resize(n_parts);
+    }
+    if (W > 1) std::cerr << "Block rows of the grid dealt to " << W << " workers on " << std::min<size_t>(W, (size_t)std::max(1, have - c.device)) << " GPU(s)" << std::endl;
+    // the text of a block row: per measure the pieces the writer has not taken yet, in order (under mu)
+    struct BlockOut {
+        std::vector<std::vector<kmdb_distance_out>> pieces;
+        bool done = false;
+        ~BlockOut() { for (auto& m : pieces) for (auto& o : m) kmdb_distance_out_free(&o); }
+    };
+    std::vector<BlockOut> block_out(n_parts);
+    for (auto& b : block_out) b.pieces.resize(M);
+    std::mutex mu;
+    std::condition_variable cv;
+    std::exception_ptr failure;
+    const bool verbose = std::getenv("KMDB_VERBOSE") != nullptr;
+    auto block_row = [&](Worker& wk, size_t i) {
+        auto get = [&](size_t p, size_t keep) -> Db& {
+            if (wk.resident[p]) return *wk.resident[p];
+            auto d = std::make_unique<Db>();
+            check(kmdbh_db_load(pc.files[p].c_str(), 0, &d->h));
+            if (kmdb_db_upload(kmdbh_db_view(d->h), &wk.o, 1, &d->d)) {
+                for (size_t j = 0; j < wk.resident.size(); ++j) if (j != keep) wk.resident[j].reset();
+                check(kmdb_db_upload(kmdbh_db_view(d->h), &wk.o, 1, &d->d));
+            }
+            kmdbh_db_free(d->h); d->h = nullptr;                   // the host copy is not needed once the part is in HBM
+            wk.resident[p] = std::move(d);
+            return *wk.resident[p];
+        };
+        if (wk.h.empty())
+            for (size_t mi = 0; mi < M; ++mi) {
+                DistanceSetup s = setups[mi];
+                s.device = wk.o.device;
+                wk.h.push_back(std::make_unique<DistanceHandle>());
+                wk.h.back()->begin(s, KMDB_DISTANCE_SPARSE_OUT);
+            }
+        kmdb_distance* h0 = wk.h[0]->d;
+        const uint64_t row_shift = row_start[i], nr = pc.part_n[i];
+        const uint32_t* row_counts = counts32.data() + row_shift;
+        const char* const* row_names = name_ptrs.data() + row_shift;
+        Db& drow = get(i, i);
+        check(kmdb_distance_parts_begin_rows(h0, nr, row_counts, row_names));
+        for (size_t j = 0; j < i; ++j) {
+            { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << j + 1 << ")" << std::endl; }
+            Db& dcol = get(j, i);
+            if (kmdb_distance_parts_add_db2db(h0, drow.d, dcol.d, row_start[j], &wk.o)) {
+                // out of HBM inside the call: the other resident parts go, one more try
+                for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i && q != j) wk.resident[q].reset();
+                check(kmdb_distance_parts_add_db2db(h0, drow.d, dcol.d, row_start[j], &wk.o));
+            }
+        }
+        { std::lock_guard<std::mutex> g(mu); std::cerr << "Processing cell (" << i + 1 << "," << i + 1 << ")" << std::endl; }
+        if (kmdb_distance_parts_add_all2all(h0, drow.d, row_shift, &wk.o)) {
+            for (size_t q = 0; q < wk.resident.size(); ++q) if (q != i) wk.resident[q].reset();
+            check(kmdb_distance_parts_add_all2all(h0, drow.d, row_shift, &wk.o));
+        }
+        std::vector<uint64_t> ptr(nr + 1, 0);
+        check(kmdb_distance_csr_row_ptr(h0, ptr.data()));          // (gathers)
+        for (size_t mi = 0; mi < M; ++mi) {
+            kmdb_distance* h = wk.h[mi]->d;
+            if (mi) {
+                const void *rp = nullptr, *co = nullptr, *va = nullptr;
+                uint64_t rows = 0;
+                check(kmdb_distance_csr_device(h0, &rp, &co, &va, &rows));
+                check(kmdb_distance_take_csr_device(h, rp, co, va, (size_t)rows, row_counts, row_names));
+            }
+            for (uint64_t r0 = 0; r0 < nr;) {
+                uint64_t r1 = r0 + 1;
+                while (r1 < nr && ptr[r1 + 1] - ptr[r0] <= budget) ++r1;
+                kmdb_distance_out piece{};
+                check(kmdb_distance_csr_rows(h, r0, r1, &piece));
+                { std::lock_guard<std::mutex> g(mu); block_out[i].pieces[mi].push_back(piece); }
+                cv.notify_all();                                   // the writer takes the piece while the device has the next
+                r0 = r1;
+            }
+        }
+        std::lock_guard<std::mutex> g(mu);
+        block_out[i].done = true;
+        cv.notify_all();
+    };
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < W; ++t)
+        pool.emplace_back([&, t]() {
+            try {
+                for (size_t i = t; i < n_parts; i += W) {
+                    { std::lock_guard<std::mutex> g(mu); if (failure) return; }
+                    block_row(workers[t], i);
+                }
+            } catch (...) {
+                std::lock_guard<std::mutex> g(mu);
+                if (!failure) failure = std::current_exception();
+                cv.notify_all();
+            }
+        });
+    bool write_failed = false;
+    for (size_t i = 0; i < n_parts && !write_failed;) {
+        std::unique_lock<std::mutex> g(mu);
+        BlockOut& b = block_out[i];
+        auto any = [&] { for (auto& m : b.pieces) if (!m.empty()) return true; return false; };
+        cv.wait(g, [&] { return any() || b.done || failure; });
+        if (!any() && !b.done) break;                              // (a failure: nothing more comes)
+        std::vector<std::vector<kmdb_distance_out>> take(M);
+        for (size_t mi = 0; mi < M; ++mi) take[mi].swap(b.pieces[mi]);
+        const bool last = b.done;
+        g.unlock();
+        for (size_t mi = 0; mi < M; ++mi) {
+            for (auto& o : take[mi]) {
+                if (o.len) ofs[mi].write(o.text, (std::streamsize)o.len);
+                kmdb_distance_out_free(&o);
+            }
+            if (!ofs[mi]) write_failed = true;
+        }
+        if (last) ++i;
+    }
+    if (write_failed) { std::lock_guard<std::mutex> g(mu); if (!failure) failure = std::make_exception_ptr(std::runtime_error("Cannot write the output file " + args[1])); }
+    for (auto& th : pool) th.join();
+    if (verbose && !failure)
+        for (size_t t = 0; t < W; ++t) {
+            kmdb_distance_parts_stats ps{};
+            if (workers[t].h.empty() || kmdb_distance_parts_stats_get(workers[t].h[0]->d, &ps)) continue;
+            std::cerr << "[kmdb] distance from the grid, worker " << t << ": block rows " << ps.block_rows << ", cells " << ps.grid_cells << ", entries in " << ps.cells_in
+                      << ", written by the device " << ps.cells_written << ", host cells " << ps.host_cells << ", gather " << ps.gather_ms << " ms, peak "
+                      << ps.peak_bytes << " B" << std::endl;
+        }
+    workers.clear();                                              // (the handles and the parts go before the process ends)
+    if (failure) std::rethrow_exception(failure);
+    for (size_t mi = 0; mi < M; ++mi) {
+        ofs[mi].close();
+        if (!ofs[mi]) throw std::runtime_error("Cannot write the output file " + paths[mi]);
+    }
+    return 0;
+}
+
 int run_distance(std::vector<std::string>& args, const Common& c) {
     const bool host_only = take_switch(args, "-host");
     bool sparse_out = take_switch(args, "-sparse");
@@ -2285,7 +2502,12 @@ void usage() {
                  "new2all -distance:               the table of <measure> straight from the query rows on the GPU: the file `new2all` followed by `distance`\n"
                  "                                  writes, without the table of counts in between; several -distance and the -min / -max list as above.\n"
                  "                                  Refused with -gpus <N>, and where the distance mode would take the table for a triangle (the first query\n"
-                 "                                  named like the first sample and sharing no k-mer with it; -sparse is not affected).\n";
+                 "                                  named like the first sample and sharing no k-mer with it; -sparse is not affected).\n"
+                 "    kmer-db-amd all2all-parts [-min ...]* [-max ...]* [-gpus <W>] -distance <measure> [-distance <measure>]* <db_list> <output>\n"
+                 "all2all-parts -distance:         the table of <measure> straight from the block rows of the grid on the GPU: the file `all2all-parts`\n"
+                 "                                  followed by `distance -sparse` writes, without the table of counts in between; always the sparse form\n"
+                 "                                  (-sparse changes nothing).  Several -distance and the -min / -max list as above; -gpus <W> as in\n"
+                 "                                  all2all-parts.  Refused with -sample-rows and with -phylip-out.\n";
 }
 
 }  // namespace
