@@ -17,6 +17,8 @@
 // names of the queries.  A fourth is a CSR in HBM over a run of rows (CsrCells: kmdb_distance_parts_*, kmdb_distance_take_csr_device and
 // kmdb_distance_csr_rows) — a block row of the all2all-parts grid, gathered from its cells' CSRs by the two kernels at the end of this file:
 // output cell ci IS entry piece_lo + ci, its row found in the rebased row_ptr, a = the ROW sample's own count.
+// The three sources in HBM share their host side too (dist_piece): a source is a struct that says what a cell is (at), where a row's name
+// lies (name) and how many cells a row has (row_cells), and a lambda of its entry point that sets the fields of DistParams these read.
 //
 // Every position is below the piece's length by construction and clamped to it again where it is used: damaged text is declined
 // (KMDB_DISTANCE_DECLINED) or parsed as the host loop parses it, and never read or written outside the buffers.
@@ -83,18 +85,17 @@ struct DistParams {
     uint64_t* off;              // [n_cells + 1] scanned lengths
     unsigned int* decline;
     unsigned long long* counters;   // [0] cells read [1] cells the device wrote [2] cells for the host [3] entries appended
-    // the triangle as the source of cells (TriangleCells): row i of the matrix at i (i - 1) / 2, the piece's rows first_row .. first_row + R
-    const uint32_t* tri;            // matrix cell tri_lo and what follows it
-    uint64_t tri_lo, tri_cells;     // the first matrix cell behind tri, and how many there are
-    uint64_t piece_lo;              // the matrix cell of the piece's output cell 0: first_row (first_row - 1) / 2
-    const unsigned char* names;     // the samples' names back to back
-    const uint64_t* name_off;       // [n + 1] where a sample's name begins
-    // the rows of a batch of queries as the source of cells (RowCells): tri = cell 0 of the nq x n rectangle, tri_cells = nq n, piece_lo =
-    // first_row n; names / name_off are the QUERIES' ([rows_nq + 1])
-    const uint32_t* row_counts;     // [rows_nq] the queries' own k-mer counts
+    // counts that lie in HBM as the source of cells.  TriangleCells: the lower triangle, row i at cell i (i - 1) / 2; RowCells: the row-major
+    // nq x n rectangle of a batch of queries.  The piece's rows are first_row .. first_row + R of either.
+    const uint32_t* cells;          // source cell cells_lo and what follows it
+    uint64_t cells_lo, cells_len;   // the first source cell behind `cells` (the rectangle: 0), and how many there are
+    uint64_t piece_lo;              // the source cell (CsrCells: the entry) of the piece's output cell 0
+    const unsigned char* names;     // the rows' names back to back: the samples' (TriangleCells), the queries' or the row samples' (RowCells, CsrCells)
+    const uint64_t* name_off;       // [n + 1] or [rows_nq + 1] where a name begins
+    const uint32_t* row_counts;     // [rows_nq] RowCells, CsrCells: the rows' own k-mer counts
     uint64_t rows_nq;
-    // a CSR as the source of cells (CsrCells): entry piece_lo + ci of csr_col / csr_val, oc = the piece's row_ptr rebased; names / name_off /
-    // row_counts / rows_nq are the ROW samples' as for RowCells
+    // a CSR as the source of cells (CsrCells): entry piece_lo + ci of csr_col / csr_val
+    const uint64_t* csr_ptr;        // [rows_nq + 1] row_ptr, ascending from 0 to csr_nnz (dist_csr_adopt has seen to it)
     const uint32_t* csr_col;        // 0-based global columns, ascending within a row
     const uint32_t* csr_val;
     uint64_t csr_nnz;
@@ -210,8 +211,8 @@ __global__ void __launch_bounds__(DT) dist_parse_kernel(DistParams p) {
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.counters[0], (unsigned long long)__popcll(m));
 }
 
-// a lane per row: a row without a comma is declined; the output cells of the row and the bytes around them
-__global__ void __launch_bounds__(DT) dist_row_sizes_kernel(DistParams p) {
+// a lane per row of the text: a row without a comma is declined; the output cells of the row and the bytes around them
+__global__ void __launch_bounds__(DT) dist_text_row_sizes_kernel(DistParams p) {
     const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
     if (r >= p.R) return;
     const uint32_t fc = p.fc[r];
@@ -359,7 +360,7 @@ struct TriangleCells {
         x.row = (uint32_t)(i - p.first_row);
         x.col = (uint32_t)c;
         x.a = p.counts[min(i, (uint64_t)p.n - 1)];
-        x.count = p.tri[min(g - p.tri_lo, p.tri_cells - 1)];
+        x.count = p.cells[min(g - p.cells_lo, p.cells_len - 1)];
         x.emit = p.mode != MODE_SPARSE_OUT || x.count > 0;
         x.prefix = p.mode == MODE_SPARSE_OUT ? (uint32_t)c + 1 : 0;
         return x;
@@ -369,16 +370,8 @@ struct TriangleCells {
         *nlen = (uint32_t)(p.name_off[s + 1] - p.name_off[s]);
         return p.names + p.name_off[s];
     }
+    static __device__ __forceinline__ uint64_t row_cells(const DistParams& p, uint32_t r) { return min(p.first_row + r, (uint64_t)p.n); }
 };
-
-// a lane per row of a piece of the triangle: its output cells, and the bytes of its name, the separator behind it and the '\n'
-__global__ void __launch_bounds__(DT) dist_tri_row_sizes_kernel(DistParams p) {
-    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
-    if (r >= p.R) return;
-    const uint64_t s = min(p.first_row + r, (uint64_t)p.n - 1);
-    p.oc[r] = min(p.first_row + r, (uint64_t)p.n);
-    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
-}
 
 struct RowCells {
     // every cell of the piece is a cell of the rectangle: row = ci / n in 32 bits (a piece holds fewer than 2^31 cells; a 64-bit divide is a
@@ -391,7 +384,7 @@ struct RowCells {
         x.row = row;
         x.col = col;
         x.a = p.row_counts[min(p.first_row + row, p.rows_nq - 1)];
-        x.count = p.tri[min(p.piece_lo + ci, p.tri_cells - 1)];
+        x.count = p.cells[min(p.piece_lo + ci, p.cells_len - 1)];
         x.emit = p.mode != MODE_SPARSE_OUT || x.count > 0;
         x.prefix = p.mode == MODE_SPARSE_OUT ? col + 1 : 0;
         return x;
@@ -401,16 +394,8 @@ struct RowCells {
         *nlen = (uint32_t)(p.name_off[s + 1] - p.name_off[s]);
         return p.names + p.name_off[s];
     }
+    static __device__ __forceinline__ uint64_t row_cells(const DistParams& p, uint32_t) { return p.n; }
 };
-
-// a lane per row of a piece of the rectangle: n output cells, and the bytes of the query's name, the separator behind it and the '\n'
-__global__ void __launch_bounds__(DT) dist_query_row_sizes_kernel(DistParams p) {
-    const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
-    if (r >= p.R) return;
-    const uint64_t s = min(p.first_row + r, p.rows_nq - 1);
-    p.oc[r] = p.n;
-    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
-}
 
 struct CsrCells {
     // every cell of the piece is an entry of the CSR: consecutive lanes read consecutive col / val; the row is the last one whose first entry is
@@ -429,19 +414,22 @@ struct CsrCells {
         return x;
     }
     static __device__ __forceinline__ const unsigned char* name(const DistParams& p, uint32_t r, uint32_t* nlen) { return RowCells::name(p, r, nlen); }
+    static __device__ __forceinline__ uint64_t row_cells(const DistParams& p, uint32_t r) {
+        const uint64_t s = min(p.first_row + r, p.rows_nq - 1);     // clamped to the rows: row_ptr holds rows_nq + 1 values
+        return p.csr_ptr[s + 1] - p.csr_ptr[s];
+    }
 };
 
-// a lane per row of a piece of the CSR (and one for the end): the first output cell of the row = row_ptr rebased to the piece — no scan —, and
-// the bytes of the row sample's name, the separator behind it and the '\n'
-__global__ void __launch_bounds__(DT) dist_csr_row_sizes_kernel(DistParams p, const uint64_t* row_ptr) {
+// A lane per row of a piece whose cells lie in HBM, whatever the source: the row's output cells, and the bytes of its name, the separator
+// behind it and the '\n'.  The host closes both arrays with a 0 and scans them in place.
+template <class Source>
+__global__ void __launch_bounds__(DT) dist_row_sizes_kernel(DistParams p) {
     const uint64_t r = (uint64_t)blockIdx.x * DT + threadIdx.x;
-    if (r > p.R) return;
-    const uint64_t base = row_ptr[p.first_row];
-    const uint64_t at = row_ptr[p.first_row + r];
-    p.oc[r] = at >= base ? at - base : 0;
-    if (r == p.R) { p.rowfix[r] = 0; return; }
-    const uint64_t s = min(p.first_row + r, p.rows_nq - 1);
-    p.rowfix[r] = p.name_off[s + 1] - p.name_off[s] + 2;
+    if (r >= p.R) return;
+    p.oc[r] = Source::row_cells(p, (uint32_t)r);
+    uint32_t nlen = 0;
+    (void)Source::name(p, (uint32_t)r, &nlen);
+    p.rowfix[r] = (uint64_t)nlen + 2;
 }
 
 // what a CSR must be to be read without a fault: row_ptr ascending from 0 (a lane per row), every column below n (a lane per entry)
@@ -657,8 +645,61 @@ int dist_scan(In* in, Out* outp, size_t n, DevBuf<void>& d_tmp, uint64_t& held, 
 struct DistTail {
     unsigned long long counters[4];
     uint64_t written, n_host;
+    uint64_t held;              // dist_piece: the device bytes of the call
     float measure_ms, format_ms, copy_ms;
 };
+
+// what every piece takes from the handle, whatever the source of its cells: the columns and their counts, the form, the measure and the bounds
+DistParams dist_params(const kmdb_distance* d, uint64_t first_row) {
+    DistParams p{};
+    p.n = (uint32_t)d->counts.size(); p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = d->triangle; p.first_row = first_row;
+    p.n_filters = (int)d->filters.size();
+    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
+    return p;
+}
+
+// The rows' sizes (p.oc and p.rowfix, a value per row) become their places: both closed with a 0 and scanned in place, the two totals back on
+// the host.  `done` (may be null) is recorded behind the copies; the stream is synchronised once.
+int dist_scan_rows(const DistParams& p, DevBuf<void>& d_tmp, uint64_t& held, hipStream_t st, hipEvent_t done, uint64_t* n_cells, uint64_t* fix_bytes) {
+    HIP_TRY(hipMemsetAsync(p.oc + p.R, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(p.rowfix + p.R, 0, 8, st));
+    if (dist_scan(p.oc, p.oc, (size_t)p.R + 1, d_tmp, held, st)) return 1;
+    if (dist_scan(p.rowfix, p.rowfix, (size_t)p.R + 1, d_tmp, held, st)) return 1;
+    HIP_TRY(hipMemcpyAsync(n_cells, p.oc + p.R, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(fix_bytes, p.rowfix + p.R, 8, hipMemcpyDeviceToHost, st));
+    if (done) HIP_TRY(hipEventRecord(done, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// a call without rows returns a text of no bytes
+int dist_empty_piece(const char* who, kmdb_distance_out* out) {
+    out->text = (char*)malloc(1);
+    if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
+    return 0;
+}
+
+// a piece into the handle's statistics (the call itself is counted where it begins)
+void dist_account(kmdb_distance* d, uint32_t R, uint64_t cells_read, uint64_t bytes_in, uint64_t held, const DistTail& t, const kmdb_distance_out* out) {
+    d->st.rows += R; d->st.cells_read += cells_read; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
+    d->st.bytes_in += bytes_in; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
+    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+}
+
+// what the four *_rows entry points do around their work: the arguments, an `out` that is empty until the call succeeds, no exception outside
+template <class Body>
+int dist_rows_entry(const char* who, bool args_ok, kmdb_distance_out* out, Body&& body) {
+    if (!args_ok) return kmdb_set_error(std::string(who) + "null argument");
+    out->text = nullptr; out->len = 0; out->rows = 0;
+    int rc;
+    try {
+        rc = body();
+    } catch (const std::exception& e) {
+        rc = kmdb_set_error(std::string(who) + e.what());
+    }
+    if (rc) kmdb_distance_out_free(out);
+    return rc;
+}
 
 // The measure and format stages of a piece whose rows and cells are laid out (p.R, p.oc and p.rowfix scanned, p.n_cells, fix_bytes): whatever
 // the source of the cells.  `begun` was recorded on the stream where the stages begin.  out->text and out->len are set.
@@ -724,6 +765,44 @@ int dist_measure_format(kmdb_distance* d, const char* who, DistParams& p, uint64
     HIP_TRY(hipEventElapsedTime(&tail->measure_ms, begun, ev[0]));
     HIP_TRY(hipEventElapsedTime(&tail->format_ms, ev[0], ev[1]));
     HIP_TRY(hipEventElapsedTime(&tail->copy_ms, ev[1], ev[2]));
+    return 0;
+}
+
+// One piece of R >= 1 rows (row_lo and what follows) whose n_cells cells lie in HBM, from the check of its size to the handle's statistics.
+// A Source says what the cells, the names and the rows' sizes are (at, name, row_cells); `fill` sets the fields of DistParams the Source reads.
+// bytes_per_cell: what a cell counts for in the statistics' bytes_in.
+template <class Source, class Fill>
+int dist_piece(kmdb_distance* d, const char* who, uint64_t row_lo, uint32_t R, uint64_t n_cells, uint64_t bytes_per_cell, Fill&& fill, kmdb_distance_out* out, DistTail* tail) {
+    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
+    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
+    size_t mem_free = 0, mem_total = 0;
+    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
+                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
+    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
+    DevEvent begun;
+    if (begun.create()) return 1;
+    DevBuf<uint64_t> d_oc, d_rowfix;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<void> d_tmp;
+    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
+    HIP_TRY(hipEventRecord(begun, st));
+    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
+    DistParams p = dist_params(d, row_lo);
+    p.R = R; p.n_cells = n_cells; p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
+    fill(p);
+    hipLaunchKernelGGL(dist_row_sizes_kernel<Source>, dim3(blocks_for(R)), dim3(DT), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    uint64_t oc_all = 0, fix_bytes = 0;
+    if (dist_scan_rows(p, d_tmp, held, st, nullptr, &oc_all, &fix_bytes)) return 1;
+    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
+    if (dist_measure_format<Source>(d, who, p, fix_bytes, d_tmp, held, begun, out, tail)) return 1;
+    out->rows = R;
+    tail->held = held;
+    dist_account(d, R, n_cells, n_cells * bytes_per_cell, held, *tail, out);
     return 0;
 }
 
@@ -818,11 +897,7 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     if (d->mode == MODE_PHYLIP && (d->flags & KMDB_DISTANCE_SPARSE_IN)) { kmdb_set_error(std::string(who) + "declined: phylip output from sparse input"); return KMDB_DISTANCE_DECLINED; }
     if (len >= 0xFFFFFFFFull - 64) { kmdb_set_error(std::string(who) + "declined: a piece of 2^32 - 64 bytes or more"); return KMDB_DISTANCE_DECLINED; }
     d->st.calls += 1;
-    if (len == 0) {
-        out->text = (char*)malloc(1);
-        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
-        return 0;
-    }
+    if (len == 0) return dist_empty_piece(who, out);
     HIP_TRY(hipSetDevice(d->device));
     hipStream_t st = d->stream;
     const uint32_t L = (uint32_t)len;
@@ -849,11 +924,8 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     HIP_TRY(hipEventRecord(ev[1], st));
 
     // classify: rows
-    DistParams p{};
-    p.text = d_text; p.L = L; p.n = (uint32_t)d->counts.size(); p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k;
-    p.triangle = d->triangle; p.first_row = first_row; p.n_filters = (int)d->filters.size();
-    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
-    p.decline = d_decline; p.counters = d_counters;
+    DistParams p = dist_params(d, first_row);
+    p.text = d_text; p.L = L; p.decline = d_decline; p.counters = d_counters;
     hipLaunchKernelGGL(dist_eol_count_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, (const unsigned char*)d_text.get(), L, d_wcnt.get());
     HIP_TRY(hipGetLastError());
     if (scan(d_wcnt.get(), d_weol.get(), NW + 1)) return 1;
@@ -892,20 +964,13 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     hipLaunchKernelGGL(dist_sep_write_kernel, dim3(blocks_for(L)), dim3(DT), 0, st, p);
     HIP_TRY(hipGetLastError());
     // parse
-    hipLaunchKernelGGL(dist_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
+    hipLaunchKernelGGL(dist_text_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
     hipLaunchKernelGGL(dist_parse_kernel, dim3(blocks_for(M)), dim3(DT), 0, st, p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
-    if (scan(d_oc.get(), d_oc.get(), (size_t)R + 1)) return 1;
-    if (scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1)) return 1;
     unsigned int why = 0;
     uint64_t n_cells = 0, fix_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&why, d_decline.get(), 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&n_cells, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ev[2], st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&why, d_decline.get(), 4, hipMemcpyDeviceToHost, st));      // (the two kernels that decline are on the stream)
+    if (dist_scan_rows(p, d_tmp, held, st, ev[2], &n_cells, &fix_bytes)) return 1;
     if (why) return declined(why);
     if (fix_bytes > (uint64_t)L + 2ull * R) return kmdb_set_error(std::string(who) + "internal error (names longer than the text)");
 
@@ -916,23 +981,13 @@ static int dist_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t f
     out->rows = R;
     float ms[2] = {0, 0};
     for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-    d->st.rows += R; d->st.cells_read += t.counters[0]; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
-    d->st.bytes_in += len; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
-    d->st.copy_ms += ms[0] + t.copy_ms; d->st.parse_ms += ms[1]; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+    dist_account(d, R, t.counters[0], len, held, t, out);
+    d->st.copy_ms += ms[0]; d->st.parse_ms += ms[1];           // the text's way to the device, and its classify and parse stages
     return 0;
 }
 
 extern "C" int kmdb_distance_rows(kmdb_distance* d, const char* lines, size_t len, uint64_t first_row, kmdb_distance_out* out) {
-    if (!d || !out || (len && !lines)) return kmdb_set_error("kmdb_distance_rows: null argument");
-    out->text = nullptr; out->len = 0; out->rows = 0;
-    int rc;
-    try {
-        rc = dist_rows(d, lines, len, first_row, out);
-    } catch (const std::exception& e) {
-        rc = kmdb_set_error(std::string("kmdb_distance_rows: ") + e.what());
-    }
-    if (rc) kmdb_distance_out_free(out);
-    return rc;
+    return dist_rows_entry("kmdb_distance_rows: ", d && out && (!len || lines), out, [&] { return dist_rows(d, lines, len, first_row, out); });
 }
 
 // ---- the triangle as the source of cells -------------------------------------------------------------------------------------------------
@@ -1016,70 +1071,18 @@ static int dist_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, 
     if (row_hi > n) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(n) + " rows");
     if (row_lo < row_hi && row_lo < d->tri_row_lo) return kmdb_set_error(std::string(who) + "row " + std::to_string(row_lo) + " lies in front of the cells taken (from row " + std::to_string(d->tri_row_lo) + " on)");
     d->st.calls += 1;
-    if (row_lo == row_hi) {
-        out->text = (char*)malloc(1);
-        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
-        return 0;
-    }
-    const uint32_t R = (uint32_t)(row_hi - row_lo);
+    if (row_lo == row_hi) return dist_empty_piece(who, out);
     const uint64_t n_cells = tri_cells_before(row_hi) - tri_cells_before(row_lo);
     if (n_cells && !d->tri) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " cells and a null pointer was taken");
-    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
-    HIP_TRY(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
-    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
-    size_t mem_free = 0, mem_total = 0;
-    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
-                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
-    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
-    DevEvent begun;
-    if (begun.create()) return 1;
-    DevBuf<uint64_t> d_oc, d_rowfix;
-    DevBuf<unsigned long long> d_counters;
-    DevBuf<void> d_tmp;
-    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
-    HIP_TRY(hipEventRecord(begun, st));
-    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
-    DistParams p{};
-    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 1; p.first_row = row_lo;
-    p.n_filters = (int)d->filters.size();
-    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
-    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
-    p.tri = d->tri; p.tri_lo = tri_cells_before(d->tri_row_lo); p.tri_cells = tri_cells_before(n) - p.tri_lo; p.piece_lo = tri_cells_before(row_lo);
-    p.names = d->d_names; p.name_off = d->d_name_off; p.n_cells = n_cells;
-    hipLaunchKernelGGL(dist_tri_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
-    if (dist_scan(d_oc.get(), d_oc.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
-    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
-    uint64_t oc_all = 0, fix_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
     DistTail t{};
-    if (dist_measure_format<TriangleCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
-    out->rows = R;
-    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
-    d->st.bytes_in += n_cells * 4; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
-    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
-    return 0;
+    return dist_piece<TriangleCells>(d, who, row_lo, (uint32_t)(row_hi - row_lo), n_cells, 4, [&](DistParams& p) {
+        p.cells = d->tri; p.cells_lo = tri_cells_before(d->tri_row_lo); p.cells_len = tri_cells_before(n) - p.cells_lo; p.piece_lo = tri_cells_before(row_lo);
+        p.names = d->d_names; p.name_off = d->d_name_off;
+    }, out, &t);
 }
 
 extern "C" int kmdb_distance_matrix_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
-    if (!d || !out) return kmdb_set_error("kmdb_distance_matrix_rows: null argument");
-    out->text = nullptr; out->len = 0; out->rows = 0;
-    int rc;
-    try {
-        rc = dist_matrix_rows(d, row_lo, row_hi, out);
-    } catch (const std::exception& e) {
-        rc = kmdb_set_error(std::string("kmdb_distance_matrix_rows: ") + e.what());
-    }
-    if (rc) kmdb_distance_out_free(out);
-    return rc;
+    return dist_rows_entry("kmdb_distance_matrix_rows: ", d && out, out, [&] { return dist_matrix_rows(d, row_lo, row_hi, out); });
 }
 
 // ---- the rows of a batch of queries as the source of cells -------------------------------------------------------------------------------
@@ -1184,70 +1187,19 @@ static int dist_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, k
     if (row_lo > row_hi) return kmdb_set_error(std::string(who) + "row_lo > row_hi");
     if (row_hi > d->rows_nq) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(d->rows_nq) + " rows");
     d->st.calls += 1;
-    if (row_lo == row_hi) {
-        out->text = (char*)malloc(1);
-        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
-        return 0;
-    }
+    if (row_lo == row_hi) return dist_empty_piece(who, out);
     const uint32_t R = (uint32_t)(row_hi - row_lo);
     const uint64_t n_cells = (uint64_t)R * n;
     if (n_cells && !d->rows) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " cells and a null pointer was taken");
-    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
-    HIP_TRY(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
-    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
-    size_t mem_free = 0, mem_total = 0;
-    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
-                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
-    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
-    DevEvent begun;
-    if (begun.create()) return 1;
-    DevBuf<uint64_t> d_oc, d_rowfix;
-    DevBuf<unsigned long long> d_counters;
-    DevBuf<void> d_tmp;
-    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
-    HIP_TRY(hipEventRecord(begun, st));
-    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
-    DistParams p{};
-    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 0; p.first_row = row_lo;
-    p.n_filters = (int)d->filters.size();
-    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
-    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
-    p.tri = d->rows; p.tri_lo = 0; p.tri_cells = d->rows_nq * n; p.piece_lo = row_lo * n;
-    p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->rows_nq; p.n_cells = n_cells;
-    hipLaunchKernelGGL(dist_query_row_sizes_kernel, dim3(blocks_for(R)), dim3(DT), 0, st, p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(d_oc.get() + R, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_rowfix.get() + R, 0, 8, st));
-    if (dist_scan(d_oc.get(), d_oc.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
-    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
-    uint64_t oc_all = 0, fix_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
     DistTail t{};
-    if (dist_measure_format<RowCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
-    out->rows = R;
-    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
-    d->st.bytes_in += n_cells * 4; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
-    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
-    return 0;
+    return dist_piece<RowCells>(d, who, row_lo, R, n_cells, 4, [&](DistParams& p) {
+        p.cells = d->rows; p.cells_lo = 0; p.cells_len = d->rows_nq * n; p.piece_lo = row_lo * n;
+        p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->rows_nq;
+    }, out, &t);
 }
 
 extern "C" int kmdb_distance_query_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
-    if (!d || !out) return kmdb_set_error("kmdb_distance_query_rows: null argument");
-    out->text = nullptr; out->len = 0; out->rows = 0;
-    int rc;
-    try {
-        rc = dist_query_rows(d, row_lo, row_hi, out);
-    } catch (const std::exception& e) {
-        rc = kmdb_set_error(std::string("kmdb_distance_query_rows: ") + e.what());
-    }
-    if (rc) kmdb_distance_out_free(out);
-    return rc;
+    return dist_rows_entry("kmdb_distance_query_rows: ", d && out, out, [&] { return dist_query_rows(d, row_lo, row_hi, out); });
 }
 
 // ---- a CSR as the source of cells: a block row of the all2all-parts grid -----------------------------------------------------------------
@@ -1529,67 +1481,19 @@ static int dist_csr_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmd
     if (row_hi > d->csr_nr) return kmdb_set_error(std::string(who) + "row_hi " + std::to_string(row_hi) + " > " + std::to_string(d->csr_nr) + " rows");
     if (dist_csr_ready(d, who)) return 1;
     d->st.calls += 1;
-    if (row_lo == row_hi) {
-        out->text = (char*)malloc(1);
-        if (!out->text) return kmdb_set_error(std::string(who) + "out of host memory");
-        return 0;
-    }
-    const uint32_t R = (uint32_t)(row_hi - row_lo);
+    if (row_lo == row_hi) return dist_empty_piece(who, out);
     const uint64_t piece_lo = d->csr_host_ptr[row_lo], n_cells = d->csr_host_ptr[row_hi] - piece_lo;    // 64-bit offsets, as row_ptr holds them
     if (n_cells && n == 0) return kmdb_set_error(std::string(who) + "the rows hold " + std::to_string(n_cells) + " entries and the handle was begun with no column");
-    if (n_cells >= (1ull << 31)) return kmdb_set_error(std::string(who) + "a piece of 2^31 cells or more (" + std::to_string(n_cells) + "): ask for fewer rows a call");
-    HIP_TRY(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    // the working arrays: code, length and offset of every cell, two sums per row; the text comes on top (DevBuf refuses with its own size)
-    const uint64_t need = n_cells * 17 + 9 + ((uint64_t)R + 1) * 16 + 64;
-    size_t mem_free = 0, mem_total = 0;
-    HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-    if (need > mem_free) return kmdb_set_error(std::string(who) + "a piece of " + std::to_string(n_cells) + " cells needs " + std::to_string(need) + " B of working arrays on the device, "
-                                              + std::to_string(mem_free) + " B are free: ask for fewer rows a call");
-    uint64_t held = ((uint64_t)R + 1) * 16 + 32;                // (the cells' arrays and the text are counted where they are allocated)
-    DevEvent begun;
-    if (begun.create()) return 1;
-    DevBuf<uint64_t> d_oc, d_rowfix;
-    DevBuf<unsigned long long> d_counters;
-    DevBuf<void> d_tmp;
-    DEV_ALLOC(d_oc, (size_t)R + 1); DEV_ALLOC(d_rowfix, (size_t)R + 1); DEV_ALLOC(d_counters, 4);
-    HIP_TRY(hipEventRecord(begun, st));
-    HIP_TRY(hipMemsetAsync(d_counters.get(), 0, 32, st));
-    DistParams p{};
-    p.R = R; p.n = (uint32_t)n; p.counts = d->d_counts; p.mode = d->mode; p.measure = d->measure; p.k = d->k; p.triangle = 0; p.first_row = row_lo;
-    p.n_filters = (int)d->filters.size();
-    for (int i = 0; i < p.n_filters; ++i) { p.f_metric[i] = d->filters[i].metric; p.f_lo[i] = d->filters[i].lo; p.f_hi[i] = d->filters[i].hi; }
-    p.counters = d_counters; p.oc = d_oc; p.rowfix = d_rowfix;
-    p.csr_col = d->csr_col; p.csr_val = d->csr_val; p.csr_nnz = d->csr_nnz; p.piece_lo = piece_lo;
-    p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->csr_nr; p.n_cells = n_cells;
-    hipLaunchKernelGGL(dist_csr_row_sizes_kernel, dim3(blocks_for((uint64_t)R + 1)), dim3(DT), 0, st, p, d->csr_ptr);
-    HIP_TRY(hipGetLastError());
-    if (dist_scan(d_rowfix.get(), d_rowfix.get(), (size_t)R + 1, d_tmp, held, st)) return 1;
-    uint64_t oc_all = 0, fix_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&oc_all, d_oc.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&fix_bytes, d_rowfix.get() + R, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (oc_all != n_cells) return kmdb_set_error(std::string(who) + "internal error (the rows' cells do not add up to the piece)");
     DistTail t{};
-    if (dist_measure_format<CsrCells>(d, who, p, fix_bytes, d_tmp, held, begun, out, &t)) return 1;
-    out->rows = R;
-    d->st.rows += R; d->st.cells_read += n_cells; d->st.cells_written += t.written; d->st.host_cells += t.n_host;
-    d->st.bytes_in += n_cells * 8; d->st.bytes_out += out->len; d->st.device_bytes = std::max<uint64_t>(d->st.device_bytes, held);
-    d->st.copy_ms += t.copy_ms; d->st.measure_ms += t.measure_ms; d->st.format_ms += t.format_ms;
+    if (dist_piece<CsrCells>(d, who, row_lo, (uint32_t)(row_hi - row_lo), n_cells, 8, [&](DistParams& p) {
+            p.csr_ptr = d->csr_ptr; p.csr_col = d->csr_col; p.csr_val = d->csr_val; p.csr_nnz = d->csr_nnz; p.piece_lo = piece_lo;
+            p.names = d->d_qnames; p.name_off = d->d_qname_off; p.row_counts = d->d_row_counts; p.rows_nq = d->csr_nr;
+        }, out, &t)) return 1;
     d->pst.cells_written += t.counters[1]; d->pst.host_cells += t.n_host;
-    d->pst.peak_bytes = std::max<uint64_t>(d->pst.peak_bytes, (d->csr_ptr == d->own_ptr.get() ? (d->csr_nr + 1) * 8 + d->csr_nnz * 8 : 0) + held);
+    d->pst.peak_bytes = std::max<uint64_t>(d->pst.peak_bytes, (d->csr_ptr == d->own_ptr.get() ? (d->csr_nr + 1) * 8 + d->csr_nnz * 8 : 0) + t.held);
     return 0;
 }
 
 extern "C" int kmdb_distance_csr_rows(kmdb_distance* d, uint64_t row_lo, uint64_t row_hi, kmdb_distance_out* out) {
-    if (!d || !out) return kmdb_set_error("kmdb_distance_csr_rows: null argument");
-    out->text = nullptr; out->len = 0; out->rows = 0;
-    int rc;
-    try {
-        rc = dist_csr_rows(d, row_lo, row_hi, out);
-    } catch (const std::exception& e) {
-        rc = kmdb_set_error(std::string("kmdb_distance_csr_rows: ") + e.what());
-    }
-    if (rc) kmdb_distance_out_free(out);
-    return rc;
+    return dist_rows_entry("kmdb_distance_csr_rows: ", d && out, out, [&] { return dist_csr_rows(d, row_lo, row_hi, out); });
 }

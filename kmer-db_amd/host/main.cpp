@@ -1611,13 +1611,81 @@ struct DistanceHandle {
     }
 };
 
+// ---- what the three -distance forms (all2all, new2all, all2all-parts) share ------------------------------------------------------------------
+// the pieces' budget of cells: KMDB_DISTANCE_CELLS_PER_PIECE, default 2^25 (chosen for memory — 17 B of working arrays a cell and the text —,
+// not tuned), at least 1 and below the 2^31 cells the library takes in one call
+uint64_t distance_cell_budget() {
+    uint64_t budget = 1ull << 25;
+    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    return std::min<uint64_t>(budget, (1ull << 31) - 1);
+}
+
+// the header of a measure's table as run_distance writes it for a table without ",db-samples" and total-kmers line
+template <class Names>
+void write_distance_header(std::ostream& os, bool phylip, uint32_t k, double fraction, const Names& names, uint64_t n) {
+    if (!phylip) {
+        os << "kmer-length: " << k << " fraction: " << fraction << " ,";
+        for (uint64_t i = 0; i < n; ++i) os << names[i] << ',';
+        os << std::endl;
+    } else os << n << std::endl;
+}
+
+// One output file and the thread that writes it: piece n - 1 goes to the file while piece n is on the device.  A text pushed belongs to the
+// writer; stop() ends the thread (ok: everything pushed is written first; otherwise at once) and frees what nobody wrote.
+struct Text { kmdb_distance_out o{}; };
+struct TableWriter {
+    std::ofstream ofs;
+    Channel<Text> texts;
+    std::thread thread;
+    bool write_failed = false;
+    ~TableWriter() { stop(false); }
+    std::ofstream& open(const std::string& path) {              // (the caller writes the header lines before start())
+        ofs.open(path, std::ios::binary);
+        return ofs;
+    }
+    void start() {
+        thread = std::thread([this]() {
+            Text t;
+            while (texts.pop(t)) {
+                if (t.o.len) ofs.write(t.o.text, (std::streamsize)t.o.len);
+                kmdb_distance_out_free(&t.o);
+                if (!ofs) { write_failed = true; texts.close(); break; }
+            }
+        });
+    }
+    bool push(kmdb_distance_out& o) {                           // false: the writer has given up
+        Text t;
+        t.o = o;
+        o = kmdb_distance_out{};
+        if (texts.push(std::move(t))) return true;
+        kmdb_distance_out_free(&t.o);
+        return false;
+    }
+    void stop(bool ok) {
+        if (ok) texts.finish(); else texts.close();
+        if (thread.joinable()) thread.join();
+        texts.drain([](Text& t) { kmdb_distance_out_free(&t.o); });
+    }
+};
+
+// the KMDB_VERBOSE line of a handle's statistics; from_text: the fields of the text source too
+void report_distance_stats(const char* lead_in, const kmdb_distance* d, bool from_text) {
+    kmdb_distance_stats st{};
+    if (!std::getenv("KMDB_VERBOSE") || !d || kmdb_distance_stats_get(d, &st)) return;
+    std::cerr << "[kmdb] " << lead_in << ": calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
+              << ", host cells " << st.host_cells;
+    if (from_text) std::cerr << ", bytes in " << st.bytes_in;
+    std::cerr << ", bytes out " << st.bytes_out;
+    if (from_text) std::cerr << ", parse " << st.parse_ms << " ms";
+    std::cerr << ", measure " << st.measure_ms << " ms, format " << st.format_ms << " ms, copies " << st.copy_ms << " ms" << std::endl;
+}
+
 // true: the output is written; false: the device path declined (why), the caller starts over with the host loop
 bool distance_on_device(const std::string& path, long long body, std::ostream& out, const DistanceSetup& s, std::string& why) {
     size_t piece_bytes = 256ull << 20;
     if (const char* e = std::getenv("KMDB_DISTANCE_BYTES_PER_PIECE")) piece_bytes = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
     piece_bytes = std::min<size_t>(piece_bytes, 3ull << 30);
     struct Piece { std::string text; bool last = false; };
-    struct Text { kmdb_distance_out o{}; };
     Channel<Piece> pieces;
     Channel<Text> texts;
     std::string read_error;
@@ -1734,14 +1802,7 @@ bool distance_on_device(const std::string& path, long long body, std::ostream& o
     writer.join();
     if (!read_error.empty()) throw std::runtime_error(read_error);
     if (write_failed) throw std::runtime_error("Cannot write the output table");
-    if (std::getenv("KMDB_VERBOSE"))
-        for (const DistanceHandle* h : {&lead, &body_handle}) {
-            kmdb_distance_stats st{};
-            if (!h->d || kmdb_distance_stats_get(h->d, &st)) continue;
-            std::cerr << "[kmdb] distance on the device: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
-                      << ", host cells " << st.host_cells << ", bytes in " << st.bytes_in << ", bytes out " << st.bytes_out << ", parse " << st.parse_ms
-                      << " ms, measure " << st.measure_ms << " ms, format " << st.format_ms << " ms, copies " << st.copy_ms << " ms" << std::endl;
-        }
+    for (const DistanceHandle* h : {&lead, &body_handle}) report_distance_stats("distance on the device", h->d, true);
     return true;
 }
 
@@ -1765,6 +1826,13 @@ void take_distance_bounds(std::vector<std::string>& args, std::map<std::string, 
         }
     }
 }
+// a bare bound belongs to the measure of the run
+void own_bare_bound(std::map<std::string, DistanceBound>& bounds, const std::string& measure) {
+    if (!bounds.count("?")) return;
+    const DistanceBound b = bounds["?"];
+    bounds.erase("?");
+    bounds[measure] = b;
+}
 // the bounds of one run as the library takes them
 std::vector<kmdb_cell_filter> distance_filters(const std::map<std::string, DistanceBound>& bounds, long kmer_lo, long kmer_hi) {
     std::vector<kmdb_cell_filter> fl;
@@ -1772,6 +1840,11 @@ std::vector<kmdb_cell_filter> distance_filters(const std::map<std::string, Dista
     if (kmer_lo != 0 || kmer_hi != (long)std::numeric_limits<uint32_t>::max())
         fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)kmer_lo, (double)kmer_hi});
     return fl;
+}
+// ... of the run of one measure out of several over the same -min / -max list
+std::vector<kmdb_cell_filter> distance_filters(std::map<std::string, DistanceBound> bounds, const std::string& measure, long kmer_lo, long kmer_hi) {
+    own_bare_bound(bounds, measure);
+    return distance_filters(bounds, kmer_lo, kmer_hi);
 }
 
 // ---- all2all -distance <measure>: the measure's table straight from the matrix in HBM ---------------------------------------------------------
@@ -1794,9 +1867,7 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
     long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
     take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
     if (args.size() != 2) throw usage_error(mode);
-    uint64_t budget = 1ull << 25;
-    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
-    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+    const uint64_t budget = distance_cell_budget();
 
     std::cerr << "All versus all comparison, " << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
     Db db;
@@ -1823,14 +1894,12 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
     const uint32_t flags = KMDB_DISTANCE_TRIANGLE | (sparse ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (phylip ? KMDB_DISTANCE_PHYLIP : 0u);
 
     DistanceHandle owner;                                          // the first measure's handle holds the triangle for all of them
-    std::ofstream ofs;
+    std::unique_ptr<TableWriter> w;                                // one per measure in turn
     std::string path;
     for (size_t mi = 0; mi < measures.size(); ++mi) {
         const std::string& measure = measures[mi];
-        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
-        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measure] = b; }
         s.measure = kmdbh_metric_id(measure.c_str());
-        s.filters = distance_filters(own, kmer_lo, kmer_hi);
+        s.filters = distance_filters(bounds, measure, kmer_lo, kmer_hi);
         DistanceHandle borrower;
         DistanceHandle& h = mi == 0 ? owner : borrower;
         h.begin(s, flags);
@@ -1848,55 +1917,34 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
         path = measures.size() == 1 ? args[1] : args[1] + "." + measure;
         std::cerr << "Storing the " << measure << " table in " << path << "...";
         const auto t0 = clk::now();
-        ofs.open(path, std::ios::binary);
-        if (!phylip) {
-            ofs << "kmer-length: " << s.k << " fraction: " << kmdbh_db_fraction(db.h) << " ,";
-            for (uint64_t i = 0; i < n; ++i) ofs << names[i] << ',';
-            ofs << std::endl;
-        } else ofs << n << std::endl;
-        struct Text { kmdb_distance_out o{}; };
-        Channel<Text> texts;
-        bool write_failed = false;
-        std::thread writer([&]() {
-            Text t;
-            while (texts.pop(t)) {
-                if (t.o.len) ofs.write(t.o.text, (std::streamsize)t.o.len);
-                kmdb_distance_out_free(&t.o);
-                if (!ofs) { write_failed = true; texts.close(); break; }
-            }
-        });
+        w.reset(new TableWriter);
+        write_distance_header(w->open(path), phylip, s.k, kmdbh_db_fraction(db.h), names, n);
+        w->start();
         std::string error;
         try {
             for (uint64_t i0 = 0; i0 < n;) {
                 uint64_t i1 = i0, cells = 0;
                 while (i1 < n && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
-                Text t;
-                check(kmdb_distance_matrix_rows(h.d, i0, i1, &t.o));
-                if (!texts.push(std::move(t))) { kmdb_distance_out_free(&t.o); break; }
+                kmdb_distance_out piece{};
+                check(kmdb_distance_matrix_rows(h.d, i0, i1, &piece));
+                if (!w->push(piece)) break;
                 i0 = i1;
             }
         } catch (std::exception& e) {
             error = e.what();
         }
-        if (error.empty()) texts.finish(); else texts.close();
-        writer.join();
-        texts.drain([](Text& t) { kmdb_distance_out_free(&t.o); });
+        w->stop(error.empty());
         if (!error.empty()) throw std::runtime_error(error);
-        if (write_failed) throw std::runtime_error("Cannot write the output file " + path);
+        if (w->write_failed) throw std::runtime_error("Cannot write the output file " + path);
         std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
-        if (std::getenv("KMDB_VERBOSE")) {
-            kmdb_distance_stats st{};
-            if (!kmdb_distance_stats_get(h.d, &st))
-                std::cerr << "[kmdb] distance from the matrix: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
-                          << ", host cells " << st.host_cells << ", bytes out " << st.bytes_out << ", measure " << st.measure_ms << " ms, format " << st.format_ms
-                          << " ms, copies " << st.copy_ms << " ms" << std::endl;
-        }
+        report_distance_stats("distance from the matrix", h.d, false);
         if (mi + 1 < measures.size()) {
-            ofs.close();
-            if (!ofs) throw std::runtime_error("Cannot write the output file " + path);
+            w->ofs.close();
+            if (!w->ofs) throw std::runtime_error("Cannot write the output file " + path);
         }
     }
-    return finish(db, ofs, path);
+    if (!w) throw usage_error(mode);                               // (no measure: the callers give one at least)
+    return finish(db, w->ofs, path);
 }
 
 // ---- new2all -distance <measure>: the measure's table straight from the query rows in HBM ------------------------------------------------------
@@ -1926,9 +1974,7 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
     long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
     take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
     if (args.size() != 3) throw usage_error("new2all");
-    uint64_t budget = 1ull << 25;
-    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
-    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+    const uint64_t budget = distance_cell_budget();
 
     std::cerr << "Set of new samples  (from " << (from_minhash ? "minhashed k-mers" : "genomes") << ") versus entire database comparison, "
               << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
@@ -1962,21 +2008,15 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
     const uint32_t flags = (sparse ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (phylip ? KMDB_DISTANCE_PHYLIP : 0u);
 
     // one handle, one output file and one writer thread per measure; handle 0 owns the rows of the batch
-    struct Text { kmdb_distance_out o{}; };
     struct Table {
         std::string measure, path;
         DistanceHandle h;
-        std::ofstream ofs;
-        Channel<Text> texts;
-        std::thread writer;
-        bool write_failed = false;
+        TableWriter w;
     };
     std::vector<std::unique_ptr<Table>> tables;
     for (auto& measure : measures) {
-        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
-        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measure] = b; }
         s.measure = kmdbh_metric_id(measure.c_str());
-        s.filters = distance_filters(own, kmer_lo, kmer_hi);
+        s.filters = distance_filters(bounds, measure, kmer_lo, kmer_hi);
         tables.emplace_back(new Table);
         Table& t = *tables.back();
         t.measure = measure;
@@ -1988,29 +2028,12 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
         if (opened) return;
         opened = true;
         for (auto& tp : tables) {
-            Table& t = *tp;
-            t.ofs.open(t.path, std::ios::binary);
-            if (!phylip) {
-                t.ofs << "kmer-length: " << k << " fraction: " << fraction << " ,";
-                for (uint64_t i = 0; i < n; ++i) t.ofs << sample_names[i] << ',';
-                t.ofs << std::endl;
-            } else t.ofs << n << std::endl;
-            t.writer = std::thread([&t]() {
-                Text x;
-                while (t.texts.pop(x)) {
-                    if (x.o.len) t.ofs.write(x.o.text, (std::streamsize)x.o.len);
-                    kmdb_distance_out_free(&x.o);
-                    if (!t.ofs) { t.write_failed = true; t.texts.close(); break; }
-                }
-            });
+            write_distance_header(tp->w.open(tp->path), phylip, k, fraction, sample_names, n);
+            tp->w.start();
         }
     };
     auto stop_tables = [&](bool ok) {
-        for (auto& tp : tables) {
-            if (ok) tp->texts.finish(); else tp->texts.close();
-            if (tp->writer.joinable()) tp->writer.join();
-            tp->texts.drain([](Text& x) { kmdb_distance_out_free(&x.o); });
-        }
+        for (auto& tp : tables) tp->w.stop(ok);
     };
 
     // the first cell of the first row taken, through a probe of its own: num-kmers is the count itself, and only a count of 0 is written "0"
@@ -2087,11 +2110,7 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
         first_take = false;
         open_tables();
         for (size_t ti = 0; ti < tables.size(); ++ti)
-            for (auto& kv : pieces[ti]) {
-                Text x = kv.second;
-                kv.second.o = kmdb_distance_out{};
-                if (!tables[ti]->texts.push(std::move(x))) kmdb_distance_out_free(&x.o);
-            }
+            for (auto& kv : pieces[ti]) (void)tables[ti]->w.push(kv.second.o);
         n_queries += batch.size();
         batch.clear();
     };
@@ -2104,16 +2123,10 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
     }
     stop_tables(true);
     for (auto& tp : tables) {
-        tp->ofs.close();
-        if (tp->write_failed || !tp->ofs) throw std::runtime_error("Cannot write the output file " + tp->path);
+        tp->w.ofs.close();
+        if (tp->w.write_failed || !tp->w.ofs) throw std::runtime_error("Cannot write the output file " + tp->path);
         std::cerr << "Stored the " << tp->measure << " table of " << n_queries << " queries in " << tp->path << std::endl;
-        if (std::getenv("KMDB_VERBOSE")) {
-            kmdb_distance_stats st{};
-            if (!kmdb_distance_stats_get(tp->h.d, &st))
-                std::cerr << "[kmdb] distance from the query rows: calls " << st.calls << ", rows " << st.rows << ", cells read " << st.cells_read << ", cells written " << st.cells_written
-                          << ", host cells " << st.host_cells << ", bytes out " << st.bytes_out << ", measure " << st.measure_ms << " ms, format " << st.format_ms
-                          << " ms, copies " << st.copy_ms << " ms" << std::endl;
-        }
+        report_distance_stats("distance from the query rows", tp->h.d, false);
     }
     std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
     return 0;
@@ -2145,9 +2158,7 @@ int run_all2all_parts_distance(std::vector<std::string>& args, Common& c, const 
     long kmer_lo = 0, kmer_hi = std::numeric_limits<uint32_t>::max();
     take_distance_bounds(args, avail, bounds, kmer_lo, kmer_hi);
     if (args.size() != 2) throw usage_error("all2all-parts");
-    uint64_t budget = 1ull << 25;
-    if (const char* e = std::getenv("KMDB_DISTANCE_CELLS_PER_PIECE")) budget = std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
-    budget = std::min<uint64_t>(budget, (1ull << 31) - 1);
+    const uint64_t budget = distance_cell_budget();
 
     std::cerr << "All versus all comparison (parts), " << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
     const PartsCollection pc = read_parts_collection(args[0]);
@@ -2159,20 +2170,16 @@ int run_all2all_parts_distance(std::vector<std::string>& args, Common& c, const 
     for (size_t i = 0; i < pc.names.size(); ++i) name_ptrs[i] = pc.names[i].c_str();
     std::vector<DistanceSetup> setups(M);
     for (size_t mi = 0; mi < M; ++mi) {
-        std::map<std::string, DistanceBound> own = bounds;         // a bare bound belongs to the measure of the run
-        if (own.count("?")) { const DistanceBound b = own["?"]; own.erase("?"); own[measures[mi]] = b; }
         setups[mi].k = pc.k; setups[mi].sparse_out = true; setups[mi].counts = counts32;
         setups[mi].measure = kmdbh_metric_id(measures[mi].c_str());
-        setups[mi].filters = distance_filters(own, kmer_lo, kmer_hi);
+        setups[mi].filters = distance_filters(bounds, measures[mi], kmer_lo, kmer_hi);
     }
     std::vector<std::ofstream> ofs(M);
     std::vector<std::string> paths(M);
     for (size_t mi = 0; mi < M; ++mi) {
         paths[mi] = M == 1 ? args[1] : args[1] + "." + measures[mi];
         ofs[mi].open(paths[mi], std::ios::binary);
-        ofs[mi] << "kmer-length: " << pc.k << " fraction: " << pc.fraction << " ,";
-        for (auto& nm : pc.names) ofs[mi] << nm << ',';
-        ofs[mi] << std::endl;
+        write_distance_header(ofs[mi], false, pc.k, pc.fraction, pc.names, pc.names.size());
     }
 
     const int have = std::max(1, kmdb_device_count());
@@ -2333,11 +2340,7 @@ int run_distance(std::vector<std::string>& args, const Common& c) {
     args.erase(args.begin());
     if (args.size() < 2) throw usage_error("distance");
     if (!avail.count(measure_name)) throw std::runtime_error("unknown measure: " + measure_name);
-    if (bounds.count("?")) {                                   // a bare bound belongs to the chosen measure
-        const Bound b = bounds["?"];
-        bounds.erase("?");
-        bounds[measure_name] = b;
-    }
+    own_bare_bound(bounds, measure_name);
     for (auto& kv : bounds) kv.second.fn = avail[kv.first];
     const metric_fn measure = avail[measure_name];
 
