@@ -2847,14 +2847,14 @@ __global__ void width_estimate_kernel(const EstParams q) {
         const uint32_t l = kmdb_k0_l(km), last = kmdb_k0_last(km);
         if (l) {
             const uint64_t pos = q.blkbase[(uint32_t)y >> 8] + q.bitrel[y];
-            uint32_t sum = 0;
-            if (l > 1) { BitCursor c(q.bits, pos); for (uint32_t k = 0; k + 1 < l; ++k) sum += c.next(); }
+            uint32_t sum = 0;                                   // (gamma_first_id, written out here and in pair_estimate_kernel: see profiles/gamma_reader_codeobject.md)
+            if (l > 1) { GammaCursor<2> c(q.bits, pos); for (uint32_t k = 0; k + 1 < l; ++k) sum += c.next(); }
             uint32_t id = last - sum;
             uint32_t fb[EST_NW], cb[EST_NW];
 #pragma unroll
             for (int c = 0; c < EST_NW; ++c) { fb[c] = __umulhi(id, q.magics[c]); cb[c] = fb[c]; nblk[c] += 1; }
             if (l > 1) {
-                BitCursor c2(q.bits, pos);
+                GammaCursor<2> c2(q.bits, pos);
                 for (uint32_t k = 0; k + 1 < l; ++k) {
                     id += c2.next();
 #pragma unroll
@@ -2893,7 +2893,7 @@ __global__ void pair_estimate_kernel(const uint2* __restrict__ k0in, const uint3
         const uint2 km = k0in[i0];
         const uint32_t l = kmdb_k0_l(km), last = kmdb_k0_last(km);
         if (l > 1) {
-            BitCursor c(bits, blkbase[(uint32_t)i0 >> 8] + bitrel[i0]);
+            GammaCursor<2> c(bits, blkbase[(uint32_t)i0 >> 8] + bitrel[i0]);
             uint32_t span = 0;
             for (uint32_t k = 0; k + 1 < l; ++k) span += c.next();
             const uint32_t nb = bm.blk(last) - bm.blk(last - span);

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include "hash_probe.h"
 #include "prim.h"
+#include "device_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -385,11 +386,10 @@ __global__ __launch_bounds__(BD_THREADS) void bd_seed_decode_kernel(const uint32
     for (uint32_t i = 1; i < n; ++i) {
         if (pos >= bits) { bad[BD_BAD_STREAM] = 1; return; }
         const uint64_t win = bd_seed_window(s, words, pos);
-        const uint32_t ones = ~win ? (uint32_t)__clzll((long long)~win) : 64u;
-        if (ones > 31u) { bad[BD_BAD_STREAM] = 1; return; }                    // a delta is 32 bits wide: at most 31 leading ones
-        const uint32_t delta = (uint32_t)((win << ones) >> (63u - ones)) | (1u << ones);
-        pos += 2u * ones + 1u;
-        total += delta;
+        if ((uint32_t)(win >> 32) == ~0u) { bad[BD_BAD_STREAM] = 1; return; }  // a delta is 32 bits wide: at most 31 leading ones, never clamped here
+        const GammaCode g = gamma_code(win);
+        pos += g.len();
+        total += g.value();
         if (pos > bits) { bad[BD_BAD_STREAM] = 1; return; }
         if (total > last) { bad[BD_BAD_IDS] = 1; return; }                     // the first id would be negative
         ev_pid[e0 + i] = (uint32_t)p;

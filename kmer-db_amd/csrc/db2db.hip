@@ -37,6 +37,7 @@
 #include "prim.h"
 #include "hash_probe.h"
 #include "cell_filter.h"
+#include "device_common.h"
 
 #include <algorithm>
 #include <cstring>
@@ -88,24 +89,6 @@ __global__ void d2_probe_kernel(D2Db row, D2Db col, uint64_t n_col_slots, uint32
     keys[i] = key;
 }
 
-struct D2Cursor {                               // gamma stream reader (src/elias_gamma.h:104-128)
-    const uint64_t* __restrict__ bits;
-    uint64_t wi, c0, c1;
-    uint32_t s;
-    __device__ __forceinline__ D2Cursor(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
-        wi = pos >> 6; s = (uint32_t)pos & 63u; c0 = bits[wi]; c1 = bits[wi + 1];
-    }
-    __device__ __forceinline__ uint32_t next() {
-        const uint64_t win = s ? ((c0 << s) | (c1 >> (64u - s))) : c0;
-        uint32_t ones = (uint32_t)__clzll((long long)~win);
-        ones = ones > 31u ? 31u : ones;
-        const uint32_t low = (uint32_t)((win << ones) >> (63u - ones));
-        s += 2u * ones + 1u;
-        if (s >= 64u) { s -= 64u; ++wi; c0 = c1; c1 = bits[wi + 1]; }
-        return low | (1u << ones);
-    }
-};
-
 // full list of the pattern with DFS index `node` as a bit set over the sample ids (64 per word): lane d decodes the d-th
 // node of the root path and ORs its local ids in (pattern_t::decodeSamples, src/pattern.cpp:99-109: first id = last - sum of the deltas)
 __device__ __forceinline__ void d2_list_bits(const D2Db& db, uint32_t node, unsigned long long* set, uint32_t lane) {
@@ -118,11 +101,12 @@ __device__ __forceinline__ void d2_list_bits(const D2Db& db, uint32_t node, unsi
             if (l) {
                 uint32_t id = m.z;
                 if (l > 1) {
-                    D2Cursor c1(db.bits, db.bitpos[r]);
+                    // (gamma_first_id, written out: through the helper the second loop kept a test of l — 2 % of the call, profiles/gamma_reader_ab.json)
+                    GammaCursor<1> c1(db.bits, db.bitpos[r]);
                     uint32_t sum = 0;
                     for (uint32_t t = 0; t + 1 < l; ++t) sum += c1.next();
                     id = m.z - sum;
-                    D2Cursor c2(db.bits, db.bitpos[r]);
+                    GammaCursor<1> c2(db.bits, db.bitpos[r]);
                     for (uint32_t t = 0; t + 1 < l; ++t) { atomicOr(&set[id >> 6], 1ull << (id & 63u)); id += c2.next(); }
                 }
                 atomicOr(&set[id >> 6], 1ull << (id & 63u));
@@ -157,11 +141,8 @@ __global__ __launch_bounds__(256) void d2_sets_round_kernel(D2Db db, uint32_t P,
         if (l) {
             uint32_t id = m.z;
             if (l > 1) {
-                D2Cursor c1(db.bits, db.bitpos[i]);
-                uint32_t sum = 0;
-                for (uint32_t t = 0; t + 1 < l; ++t) sum += c1.next();
-                id = m.z - sum;
-                D2Cursor c2(db.bits, db.bitpos[i]);
+                id = gamma_first_id<1, false>(db.bits, db.bitpos[i], l, m.z);
+                GammaCursor<1> c2(db.bits, db.bitpos[i]);
                 uint32_t cw = id >> 6;
                 unsigned long long acc = 0;
                 for (uint32_t t = 0; t + 1 < l; ++t) {                    // ids ascend: one read-modify-write per word

@@ -1,5 +1,5 @@
 // device_common.h — device-side helpers shared by the kernels of libkmdb_amd.so: wave-level primitives,
-// the Elias-gamma stream reader, node decoding, block mapping.  Everything is internal to each
+// the Elias-gamma stream readers (one code, the 64-bit cursor, first id and runs of a list), node decoding, block mapping.  Everything is internal to each
 // translation unit (anonymous namespace).
 #pragma once
 #include "engine_state.h"
@@ -47,35 +47,99 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
 }
 
 // Gamma streams are MSB-first in little-endian uint64 words (reference src/elias_gamma.h:113-125).
-// BitCursor keeps three consecutive words in registers: a code (<= 63 bits) is extracted from
-// c0:c1 with shifts only, and the word two ahead is fetched when the cursor crosses a word
-// boundary, so the decode loop has no load on its dependency chain.  The bit array carries four
-// padding words.
-struct BitCursor {
+// One Elias-gamma code at the head of a 64-bit window: (L-1) ones, a zero, (L-1) low bits (reference src/elias_gamma.h:104-128).
+// A valid code has at most 31 leading ones (a delta is 32 bits wide), so every code fits the window.  THE definition: every 64-bit
+// reader takes value and length from here.  (low and ones apart: a cursor asks for the value after it has advanced by the length,
+// as every reader did — put together before the advance, the v1 kernels came out with other code.)
+struct GammaCode {
+    uint32_t low, ones;                            // the bits behind the zero; the leading ones
+    __device__ __forceinline__ uint32_t value() const { return low | (1u << ones); }
+    __device__ __forceinline__ uint32_t len() const { return 2u * ones + 1u; }
+};
+__device__ __forceinline__ GammaCode gamma_code(uint64_t win) {
+    uint32_t ones = (uint32_t)__clzll((long long)~win);
+    ones = ones > 31u ? 31u : ones;
+    return GammaCode{(uint32_t)((win << ones) >> (63u - ones)), ones};
+}
+
+// The 64-bit reader.  It keeps AHEAD + 1 consecutive words in registers: a code is extracted from c[0]:c[1] with shifts only.
+// AHEAD = 2: the word two ahead is fetched when the cursor crosses a word boundary, so the decode loop has no load on its dependency
+// chain.  AHEAD = 1: a register pair less, the load of a crossing feeds the next window.  The bit array carries four padding words.
+template <int AHEAD>
+struct GammaCursor {
+    static_assert(AHEAD == 1 || AHEAD == 2, "GammaCursor: one or two words ahead");
     const uint64_t* __restrict__ bits;
     uint64_t wi;
-    uint64_t c0, c1, c2;
-    uint32_t s;                                    // bit offset inside c0
-    __device__ __forceinline__ BitCursor(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
+    uint64_t c[AHEAD + 1];
+    uint32_t s;                                    // bit offset inside c[0]
+    __device__ __forceinline__ GammaCursor(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
         wi = pos >> 6;
         s = (uint32_t)pos & 63u;
-        c0 = bits[wi]; c1 = bits[wi + 1]; c2 = bits[wi + 2];
+#pragma unroll
+        for (int k = 0; k <= AHEAD; ++k) c[k] = bits[wi + k];
     }
-    // one Elias-gamma value: (L-1) ones, a zero, (L-1) low bits (reference src/elias_gamma.h:104-128)
-    __device__ __forceinline__ uint32_t next() {
-        const uint64_t win = s ? ((c0 << s) | (c1 >> (64u - s))) : c0;
-        uint32_t ones = (uint32_t)__clzll((long long)~win);
-        ones = ones > 31u ? 31u : ones;             // a valid code has at most 31 leading ones
-        const uint32_t low = (uint32_t)((win << ones) >> (63u - ones));
-        s += 2u * ones + 1u;
+    __device__ __forceinline__ uint64_t pos() const { return wi * 64u + s; }
+    __device__ __forceinline__ uint64_t window() const { return s ? ((c[0] << s) | (c[1] >> (64u - s))) : c[0]; }
+    __device__ __forceinline__ void advance(uint32_t n) {          // n <= 64
+        s += n;
         if (s >= 64u) {
             s -= 64u;
             ++wi;
-            c0 = c1; c1 = c2; c2 = bits[wi + 2];
+#pragma unroll
+            for (int k = 0; k < AHEAD; ++k) c[k] = c[k + 1];
+            c[AHEAD] = bits[wi + AHEAD];
         }
-        return low | (1u << ones);
+    }
+    __device__ __forceinline__ uint32_t next() {
+        const GammaCode g = gamma_code(window());
+        advance(g.len());
+        return g.value();
+    }
+    // the "0" codes (deltas of 1) at the cursor, at most `limit` of them: taken in one step
+    __device__ __forceinline__ uint32_t zeros(uint32_t limit) {
+        const uint64_t win = window();
+        uint32_t z = win ? (uint32_t)__clzll((long long)win) : 64u;
+        z = z < limit ? z : limit;
+        advance(z);
+        return z;
     }
 };
+
+// A local list of l >= 1 ids is l-1 gamma-coded deltas in append order, the last id explicit (pattern_t::decodeSamples, reference
+// src/pattern.cpp:99-109).  Its first id = last - sum of the deltas at `pos`: what a consumer needs before it decodes the deltas again from
+// `pos`.  RUNS: runs of deltas of 1 in one step each.  (l = 1: the last id, after the cursor's loads at `pos`.)
+template <int AHEAD, bool RUNS>
+__device__ __forceinline__ uint32_t gamma_first_id(const uint64_t* bits, uint64_t pos, uint32_t l, uint32_t last) {
+    GammaCursor<AHEAD> c(bits, pos);
+    uint32_t sum = 0;
+    if (RUNS) {
+        for (uint32_t rem = l - 1u; rem;) {
+            const uint32_t z = c.zeros(rem);
+            sum += z; rem -= z;
+            if (rem) { sum += c.next(); --rem; }
+        }
+    } else {
+        for (uint32_t t = 0; t + 1 < l; ++t) sum += c.next();
+    }
+    return last - sum;
+}
+
+// The `count` >= 1 ids from `start` on, deltas at the cursor, as maximal runs of consecutive ids: run(start, len) for each, in order.
+template <int AHEAD, class F>
+__device__ __forceinline__ void gamma_runs(GammaCursor<AHEAD>& c, uint32_t start, uint32_t count, F&& run) {
+    uint32_t len = 1;
+    for (uint32_t rem = count - 1u; rem;) {
+        const uint32_t z = c.zeros(rem);
+        len += z; rem -= z;
+        if (rem) {
+            const uint32_t d = c.next();
+            --rem;
+            if (d == 1u) ++len;
+            else { run(start, len); start += len - 1u + d; len = 1; }
+        }
+    }
+    run(start, len);
+}
 
 // Run-aware reader of the same streams on 32-bit units.  Most deltas of a local list are 1 (code "0": the samples of a cluster are
 // consecutive ids), so the decoder consumes a whole run of "0" codes with one count-leading-zeros and only walks code by code through
@@ -143,6 +207,7 @@ struct RunCursor32 {
                 // through a 64-bit window over three units.  (Round 5 clamped the count of leading ones to 15 here: such a delta — rare, it
                 // needs a list that jumps over 65 536 ids at once — was decoded wrongly.)  Behind zeros the code waits for the next step, which
                 // starts at it.
+                // (restates gamma_code() above, the definition of this arithmetic, on this cursor's units)
                 const unsigned long long w64 = (((unsigned long long)c[0] << 32) | c[1]) << s | (s ? (unsigned long long)(c[2] >> (32u - s)) : 0ull);
                 uint32_t o64 = (uint32_t)__clzll((long long)~w64);
                 o64 = o64 > 31u ? 31u : o64;
@@ -161,7 +226,7 @@ template <class T>
 __device__ __forceinline__ void decode_node(const uint64_t* __restrict__ bits, uint64_t pos, uint32_t l, uint32_t last, T* out) {
     if (l == 0) return;
     if (l > 1) {
-        BitCursor cur(bits, pos);
+        GammaCursor<2> cur(bits, pos);
         uint32_t sum = 0;
         for (uint32_t i = 0; i + 1 < l; ++i) {
             const uint32_t d = cur.next();
@@ -194,35 +259,6 @@ struct BlockMap {
 };
 
 static_assert((uint64_t)KMDB_MAX_SAMPLES * 64u <= (1ull << 32), "BlockMap::blk: the magic division is exact only for ids below 2^32 / width");
-
-// decode_node plus, per id, the running bit mask of the ids of the same block seen so far
-// in this node ("cum"): the block-record kernel needs it per stack position.
-__device__ __forceinline__ void decode_node_cum(const uint64_t* __restrict__ bits, uint64_t pos, uint32_t l, uint32_t last,
-                                                uint16_t* out, unsigned long long* cum, const BlockMap bm) {
-    if (l == 0) return;
-    uint32_t id = last;
-    if (l > 1) {
-        BitCursor cur(bits, pos);
-        uint32_t sum = 0;
-        for (uint32_t i = 0; i + 1 < l; ++i) {
-            const uint32_t d = cur.next();
-            out[i] = (uint16_t)d;
-            sum += d;
-        }
-        id = last - sum;
-    }
-    uint32_t curblk = 0xFFFFFFFFu;
-    unsigned long long acc = 0;
-    for (uint32_t i = 0; i < l; ++i) {
-        const uint32_t d = (i + 1 < l) ? (uint32_t)out[i] : 0u;
-        const uint32_t blk = bm.blk(id);
-        if (blk != curblk) { curblk = blk; acc = 0; }
-        acc |= 1ull << bm.bit(id, blk);
-        out[i] = (uint16_t)id;
-        cum[i] = acc;
-        id += d;
-    }
-}
 
 __device__ __forceinline__ uint64_t tri64(uint64_t a) { return a * (a - 1) / 2; }
 

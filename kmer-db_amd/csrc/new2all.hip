@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include "prim.h"
 #include "hash_probe.h"
+#include "device_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -103,33 +104,6 @@ __global__ void n2a_query_ranges_kernel(const unsigned long long* __restrict__ u
     qstart[q] = lo;
 }
 
-struct N2Cursor {                                                 // gamma stream reader (see BitCursor in device_common.h)
-    const uint64_t* __restrict__ bits;
-    uint64_t wi, c0, c1;
-    uint32_t s;
-    __device__ __forceinline__ N2Cursor(const uint64_t* __restrict__ b, uint64_t pos) : bits(b) {
-        wi = pos >> 6; s = (uint32_t)pos & 63u; c0 = bits[wi]; c1 = bits[wi + 1];
-    }
-    __device__ __forceinline__ uint32_t next() {                  // (L-1) ones, a zero, (L-1) low bits (src/elias_gamma.h:104-128)
-        const uint64_t win = s ? ((c0 << s) | (c1 >> (64u - s))) : c0;
-        uint32_t ones = (uint32_t)__clzll((long long)~win);
-        ones = ones > 31u ? 31u : ones;
-        const uint32_t low = (uint32_t)((win << ones) >> (63u - ones));
-        s += 2u * ones + 1u;
-        if (s >= 64u) { s -= 64u; ++wi; c0 = c1; c1 = bits[wi + 1]; }
-        return low | (1u << ones);
-    }
-    // the "0" codes (deltas of 1) at the cursor, at most `limit` of them: taken in one step
-    __device__ __forceinline__ uint32_t zeros(uint32_t limit) {
-        const uint64_t win = s ? ((c0 << s) | (c1 >> (64u - s))) : c0;
-        uint32_t z = win ? (uint32_t)__clzll((long long)win) : 64u;
-        z = z < limit ? z : limit;
-        s += z;
-        if (s >= 64u) { s -= 64u; ++wi; c0 = c1; c1 = bits[wi + 1]; }
-        return z;
-    }
-};
-
 // (4) walk: one thread per distinct (query, hit pattern).  A thread climbs from its hit towards the root until it meets the
 // previous hit's path, so every node on the union of the root paths is visited once per query; the node's local ids get H =
 // the number of hit k-mers below it.  Local lists of up to KMDB_CK_IDS ids are decoded by the visiting thread; longer ones
@@ -154,20 +128,8 @@ __global__ void n2a_runs_kernel(const uint4* __restrict__ meta, const uint64_t* 
         const uint4 m = meta[i];
         const uint32_t l = m.y;
         if (l) {
-            uint32_t id = m.z;
-            if (l > 1) {
-                N2Cursor c1(bits, bitpos[i]);
-                uint32_t sum = 0;
-                for (uint32_t rem = l - 1u; rem;) {
-                    const uint32_t z = c1.zeros(rem);
-                    sum += z; rem -= z;
-                    if (rem) { sum += c1.next(); --rem; }
-                }
-                id = m.z - sum;
-            }
-            uint32_t o = FILL ? ofs[i] : 0u, start = id, len = 1;
-            auto put = [&]() {                                       // the run [start, start + len)
-                uint32_t s0 = start, left = len;
+            uint32_t o = FILL ? ofs[i] : 0u;
+            auto put = [&](uint32_t s0, uint32_t left) {             // the run [s0, s0 + left)
                 while (left) {
                     const uint32_t take = left < max_len ? left : max_len;
                     if (FILL) runs[o] = s0 | (take << rs);
@@ -175,19 +137,10 @@ __global__ void n2a_runs_kernel(const uint4* __restrict__ meta, const uint64_t* 
                 }
             };
             if (l > 1) {
-                N2Cursor c2(bits, bitpos[i]);
-                for (uint32_t rem = l - 1u; rem;) {
-                    const uint32_t z = c2.zeros(rem);
-                    len += z; rem -= z;
-                    if (rem) {
-                        const uint32_t d = c2.next();
-                        --rem;
-                        if (d == 1u) ++len;
-                        else { put(); start += len - 1u + d; len = 1; }
-                    }
-                }
-            }
-            put();
+                const uint32_t first = gamma_first_id<1, true>(bits, bitpos[i], l, m.z);
+                GammaCursor<1> c(bits, bitpos[i]);
+                gamma_runs(c, first, l, put);
+            } else put(m.z, 1u);
         }
     }
     if (!FILL) cnt[i] = n;
@@ -310,16 +263,9 @@ __global__ __launch_bounds__(N2_THREADS) void n2a_walk_kernel(const unsigned lon
                     uint32_t id = m.z;
                     if (l > 1) {
                         // pattern_t::decodeSamples (src/pattern.cpp:99-109): first id = last - sum of the deltas
-                        N2Cursor c1(bits, bp);
-                        uint32_t sum = 0;
+                        id = gamma_first_id<1, true>(bits, bp, l, m.z);
+                        GammaCursor<1> c2(bits, bp);
                         for (uint32_t rem = l - 1u; rem;) {                 // runs of deltas of 1 in one step each
-                            const uint32_t z = c1.zeros(rem);
-                            sum += z; rem -= z;
-                            if (rem) { sum += c1.next(); --rem; }
-                        }
-                        id = m.z - sum;
-                        N2Cursor c2(bits, bp);
-                        for (uint32_t rem = l - 1u; rem;) {
                             const uint32_t z = c2.zeros(rem);
                             for (uint32_t t = 0; t < z; ++t) { atomicAdd(&acc[id], H); ++id; }
                             rem -= z;
@@ -387,25 +333,12 @@ __global__ __launch_bounds__(N2_THREADS) void n2a_walk_kernel(const unsigned lon
                 const uint32_t o = q_node[lo] + piece;
                 uint32_t id = ck_id[o];
                 const uint32_t left = l - piece * KMDB_CK_IDS, cnt = left < KMDB_CK_IDS ? left : KMDB_CK_IDS;
-                N2Cursor c(bits, ck_bit[o]);
+                GammaCursor<1> c(bits, ck_bit[o]);
                 if (LDS_HIST) {
-                    uint32_t start = id, len = 1, rem = cnt - 1u;          // the run [start, start + len) under construction
-                    while (rem) {
-                        const uint32_t z = c.zeros(rem);
-                        len += z; rem -= z;
-                        if (rem) {
-                            const uint32_t d = c.next();
-                            --rem;
-                            if (d == 1u) ++len;
-                            else {
-                                atomicAdd(&hist[start], H);
-                                if (start + len < N) atomicAdd(&hist[start + len], 0u - H);
-                                start += len - 1u + d; len = 1;
-                            }
-                        }
-                    }
-                    atomicAdd(&hist[start], H);
-                    if (start + len < N) atomicAdd(&hist[start + len], 0u - H);
+                    gamma_runs(c, id, cnt, [&](uint32_t start, uint32_t len) {
+                        atomicAdd(&hist[start], H);
+                        if (start + len < N) atomicAdd(&hist[start + len], 0u - H);
+                    });
                 } else {
                     atomicAdd(&acc[id], H);
                     for (uint32_t t = 1; t < cnt; ++t) { id += c.next(); atomicAdd(&acc[id], H); }

@@ -38,12 +38,10 @@ __global__ void ck_fill_kernel(const uint2* __restrict__ k0in, const uint32_t* _
     const uint32_t l = kmdb_k0_l(km), last = kmdb_k0_last(km);
     if (l <= KMDB_CK_IDS) return;
     const uint64_t pos = blkbase[i >> 8] + bitrel[i];
-    uint32_t sum = 0;
-    { BitCursor c(bits, pos); for (uint32_t t = 0; t + 1 < l; ++t) sum += c.next(); }
-    BitCursor c(bits, pos);
-    uint32_t id = last - sum, o = ck_ofs[i];
+    uint32_t id = gamma_first_id<2, false>(bits, pos, l, last), o = ck_ofs[i];
+    GammaCursor<2> c(bits, pos);
     for (uint32_t t = 0; t < l; ++t) {
-        if (t % KMDB_CK_IDS == 0) { ck_id[o] = id; ck_bit[o] = c.wi * 64u + c.s; ++o; }      // element t and the position of the code after it
+        if (t % KMDB_CK_IDS == 0) { ck_id[o] = id; ck_bit[o] = c.pos(); ++o; }      // element t and the position of the code after it
         if (t + 1 < l) id += c.next();
     }
 }

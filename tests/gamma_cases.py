@@ -1,9 +1,9 @@
 """Inputs and references of test_gamma_conformance.py: an Elias-gamma coder of its own, the case families that put every code length at
 every bit offset in front of the engine's stream readers, and a census that proves on the host what the families hold.  Host only.
 
-The engine has four gamma readers ("The stream readers"): RunCursor32 (32-bit units, all2all's decode kernel, two launches),
-BitCursor (64 bit, three words: the v1 kernels, the upload's estimates, new2all's checkpoints), N2Cursor (new2all: run index, walk, queued
-lists) and D2Cursor (db2db: list store and root-path climb).  A reader that is one bit off at one alignment must fail here.
+The engine has two gamma readers ("The stream readers"): RunCursor32 (32-bit units, all2all's decode kernel, two launches) and
+GammaCursor, 64 bit — <2>, three words: the v1 kernels, the upload's estimates, new2all's checkpoints; <1>, two words: new2all (run index,
+walk, queued lists) and db2db (list store and root-path climb).  A reader that is one bit off at one alignment must fail here.
 
 The coder (encode / decode) is plain Python on big integers: a stream is ONE int, most significant bit first, cut into uint64 words of
 which the first holds the first 64 bits (reference src/elias_gamma.h:104-128); a value d of L bits is L - 1 ones, a zero and the L - 1 low
@@ -16,7 +16,7 @@ not matter, over t = 0 .. 63 the code under test meets every bit offset of a 64-
 
 Limits of the coverage, stated rather than pretended:
   * RunCursor32 reads codes of up to 39 bits, all2all serves at most 2^17 samples' worth of matrix in memory (131 072 samples are a
-    34 GB matrix): deltas of 2^17 and more — codes of 35 to 39 bits — reach N2Cursor, D2Cursor and BitCursor (collection D), never
+    34 GB matrix): deltas of 2^17 and more — codes of 35 to 39 bits — reach GammaCursor<1> and GammaCursor<2> (collection D), never
     RunCursor32.  Its 64-bit side path is exercised by the 33-bit codes of collection C only.
   * A delta cannot exceed N - 1: the last value of the longest code length of a collection, 2^(j + 1) - 1, is lowered to what the id range
     leaves behind the prefix and the tail (it keeps its code length), and the tail's 2^j is halved until it fits.  One list without a

@@ -1,13 +1,13 @@
 """Gamma-stream decode conformance: every stream reader of the engine — RunCursor32 (all2all's decode kernel, short and long launch),
-BitCursor (the v1 kernels, the upload's estimates, new2all's checkpoints), N2Cursor (new2all's run index, walk and queued lists) and
-D2Cursor (db2db's list store and root-path climb) — meets every code length at every bit offset, lists either side of the 128-bit bound
+GammaCursor<2> (the v1 kernels, the upload's estimates, new2all's checkpoints) and GammaCursor<1> (new2all's run index, walk and queued
+lists; db2db's list store and root-path climb) — meets every code length at every bit offset, lists either side of the 128-bit bound
 of the short launch, of every 32nd id (new2all's checkpoints), of the longest run the run index stores, and of 65 536 ids (31 / 33-bit
 codes).  The inputs are tests/gamma_cases.py's; a census on the host proves what they hold before a device runs.  The references are the
 decoded lists themselves (variant_cases.definition, its sparse form, one2all_from_lists, db2db_from_lists) and the CPU oracle, never a
 second run of the engine; all comparisons are exact uint32 equality.
 
 What cannot be reached: codes of 35 to 39 bits in RunCursor32 (all2all would need more than 131 072 samples: a 34 GB matrix); they are
-decoded by N2Cursor, D2Cursor and BitCursor in collection D (526 336 samples).  A change to any reader must pass this file."""
+decoded by GammaCursor<1> and GammaCursor<2> in collection D (526 336 samples).  A change to any reader must pass this file."""
 import functools
 import os
 
@@ -221,7 +221,7 @@ A2A_VARIANTS = [{}] + [{"KMDB_SHORT_IDS": s} for s in (1, 47, 48, 64)] + [{"KMDB
 def test_all2all_collection_a(K, dev, env, variant):
     """RunCursor32 at every code length of up to 23 bits and every offset: the whole matrix of collection A == the definition, on the
     block-record pipeline (FLAG_NO_FALLBACK; stats().path says so) with the short launch taking lists of up to 1, 47, 48 and 64 ids and
-    under every first-block and row mode; in the default configuration also BitCursor in the three v1 kernels"""
+    under every first-block and row mode; in the default configuration also GammaCursor<2> in the three v1 kernels"""
     pat, N, exp = _case_A()
     lap = _Lap("all2all_collection_a %s" % variant)
     _, view = V.make_view(K, _S(), pat, N)
@@ -309,7 +309,7 @@ def test_more_than_65535_samples_gamma_collection_b(K, dev, env):
 def test_more_than_65535_samples_gamma_collection_c(K, dev, env):
     """Deltas 65 535 (31 bits: the last code of the 32-bit window) and 65 536, 65 537, 65 590 (33 bits: the 64-bit side path of
     RunCursor32::step) side by side, 65 600 samples: the block-record pipeline, two slices of the pattern stream summed, and the
-    HBM-atomics kernel (BitCursor, 32-bit ids)."""
+    HBM-atomics kernel (GammaCursor<2>, 32-bit ids)."""
     import torch
 
     def calls(d, M, check):
@@ -338,7 +338,7 @@ N2A_VARIANTS = ({}, {"KMDB_N2A_NO_RUNS": 1}, {"KMDB_N2A_NO_NODES": 1}, {"KMDB_N2
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,N", [("A", 4096), ("A", 10000), ("C", 65600), ("R16", 65536), ("D", G.SIZES["D"])])
 def test_new2all_on_the_collections(K, O, dev, env, dbs, name, N):
-    """N2Cursor (next and zeros) and BitCursor in ck_fill_kernel: with the run index (n2a_runs_kernel; 16-bit starts and runs of up to
+    """GammaCursor<1> (next and zeros) and GammaCursor<2> in ck_fill_kernel: with the run index (n2a_runs_kernel; 16-bit starts and runs of up to
     65 535 ids at 65 536 samples, 20-bit starts and runs of up to 4095 above), without it (the inline decode of the walk, the queued long
     lists from a checkpoint: a long code directly before, on and behind every 32nd id), over the engine's arrays, and with 1024 threads.
     The per-query histogram is in LDS for A at 4096 samples, for A at 10 000 with 512 threads only, in memory for C, R16 and D.  The
@@ -381,7 +381,7 @@ def _csr(dense):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,N", [("A", 4096), ("A", 4097), ("D", G.SIZES["D"])])
 def test_db2db_on_the_collections(K, O, dev, env, dbs, name, N):
-    """D2Cursor: the list store (a part of 4096 samples) and the root-path climb (4097 samples, and D: codes of up to 39 bits), the case
+    """GammaCursor<1>, next only (db2db): the list store (a part of 4096 samples) and the root-path climb (4097 samples, and D: codes of up to 39 bits), the case
     collection as the row part and as the column part of a cell with a 64-sample part that shares every k-mer with it.  The dense cell ==
     the oracle's db2db (== the lists: test_references_agree), the rows of db2db_sparse == its non-zeros."""
     lap = _Lap("db2db %s %d" % (name, N))
