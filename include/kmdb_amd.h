@@ -62,6 +62,11 @@ extern "C" {
  * HBM (kmdb_db2db_sampled, kmdb_sampled_from_rect_device, kmdb_db2db_sample_stats_get): three more entry points, no struct changed, the version
  * stays 8. */
 #define KMDB_HAS_DB2DB_SAMPLED 1
+/* And the -sample-rows selection on the query rows of new2all: every query's best database samples chosen in HBM (kmdb_new2all_batch_sampled,
+ * kmdb_new2all_batch_seq_alphabet_sampled, kmdb_sampled_from_rows_device, kmdbh_query_rows_select, kmdb_new2all_sample_stats_get, and over
+ * the GPUs of a node kmdb_node_new2all_batch_sampled, kmdb_node_new2all_batch_seq_alphabet_sampled, kmdb_node_new2all_sample_stats_get): eight
+ * more entry points, no struct changed, the version stays 8. */
+#define KMDB_HAS_NEW2ALL_SAMPLED 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -402,6 +407,53 @@ typedef struct kmdb_new2all_sparse_stats {   /* the LAST sparse new2all call on 
 } kmdb_new2all_sparse_stats;
 int  kmdb_new2all_sparse_stats_get(const kmdb_db* db, kmdb_new2all_sparse_stats* out);
 
+/* ---------------------------------------------------------------------------------------
+ * new2all -sample-rows <criterion>:<count>: a search.  Every QUERY keeps its `count` best database samples; the database samples collect nothing.
+ * The reference has no such option for new2all; the rule is the one its Sampler applies to a sparse row everywhere else (sampler.h:44-67) over the
+ * row new2all -sparse writes (console_new2all.cpp:130-148).  For query q with a = its own unique k-mer count truncated to uint32 and database
+ * sample s with b = sample_kmers[s]: the cell c = rows[q][s] is a candidate when c > 0 and it passes every bound (a = the QUERY's count, b = the
+ * sample's, as in kmdb_new2all_batch_sparse_filtered); its score is kmdbh_metric(criterion, c, a, b, k); row q keeps the `count` candidates with
+ * the largest score, ties towards the smaller sample id, listed in ascending sample id; a row of fewer candidates comes out whole.
+ * The device selects on the criterion's plain ratio by the radix select of kmdb_all2all_sampled, here over per-row segments of 2048 columns, a
+ * wave each; the host decides with kmdbh_metric; rows the margin cannot settle are fetched again whole inside the call.
+ * ------------------------------------------------------------------------------------- */
+/* Stands for T calls of one2all_sp + CombinedFilter (console_new2all.cpp:76-78, 130-148) followed by Sampler::saveRowSparse (sampler.h:123-139):
+ * the rows accumulated in HBM as for kmdb_new2all_batch_device, then selection, exact decision and re-fetch inside the call.  out: row q = the
+ * kept samples of query q in ascending id, val = common k-mers, measure = the score (as kmdb_all2all_sampled gives it).  criterion:
+ * KMDB_METRIC_*; count >= 1; sample_kmers [N] is required.  Needs the hashtables; a query-shard handle is refused, as
+ * kmdb_new2all_batch_sparse_filtered refuses it. */
+int  kmdb_new2all_batch_sampled(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                size_t n_filters, const uint32_t* sample_kmers /* [N] */, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                const kmdb_opts* opts);
+/* The same with the queries given as sequence text (the second call site of a batch, console_new2all.cpp:60-75 with the device extractor);
+ * out_kmer_counts [nq]: the unique k-mer count of every query, whose low 32 bits are a. */
+int  kmdb_new2all_batch_seq_alphabet_sampled(kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                             double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                             const uint32_t* sample_kmers /* [N] */, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                             uint64_t* out_kmer_counts, const kmdb_opts* opts);
+/* The candidates of a flat range [cell_lo, cell_hi) of a row-major nq x n_cols rectangle of query rows the CALLER accumulated (the multi-GPU form
+ * of the call site above: a device's reduce-scatter chunk as it is; rows_dev = device address of cell cell_lo, as in
+ * kmdb_new2all_rows_sparse_device).  db gives the device, the stream and the k-mer length, as in kmdb_sampled_from_rect_device; n_cols is
+ * explicit (1 .. 2^32 - 1) and need not be the handle's sample count.  query_kmers [nq] and sample_kmers [n_cols] are host arrays.
+ * out_candidates: all nq rows, ascending sample ids, val = common k-mers, no measures; rows outside the range are empty and a row cut by a range
+ * end lists only its cells inside.  Per row a superset of its `count` best cells among the cells of the range (exact filters included: the
+ * re-fetch happens here); a row's best `count` within a range is a superset of its share of the global best `count`, so the candidates of
+ * several ranges go to kmdbh_query_rows_select together.  The stream note of kmdb_sparse_from_dense_device applies. */
+int  kmdb_sampled_from_rows_device(kmdb_db* db, const void* rows_dev, size_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi,
+                                   const uint32_t* query_kmers /* [nq] */, const kmdb_cell_filter* filters, size_t n_filters,
+                                   const uint32_t* sample_kmers /* [n_cols] */, int criterion, uint32_t count, kmdb_sparse_rows* out_candidates,
+                                   const kmdb_opts* opts);
+/* The exact one-sided decision (Sampler with strategy best, sampler.h:44-67, 123-139; no GPU): any number of candidate parts of nq rows each in,
+ * per query the `count` best cells that pass the filters out — ascending id, val = common k-mers, measure = score.  Does not depend on the order
+ * of the candidates within or across parts; a pair listed twice counts once.  Every candidate's column must be an index into sample_kmers. */
+int  kmdbh_query_rows_select(int criterion, uint32_t count, int kmer_length, const uint32_t* query_kmers /* [nq] */, size_t nq,
+                             const uint32_t* sample_kmers, const kmdb_cell_filter* filters, size_t n_filters, const kmdb_sparse_rows* const* parts,
+                             size_t n_parts, kmdb_sparse_rows* out);
+/* The LAST sampled new2all call on the handle (or kmdb_sampled_from_rows_device call on it): the fields of kmdb_sample_stats over the rows that
+ * meet the range; triangle_reads = passes over the rows: 4 histogram, 1 count, 1 emit; 2 more for a re-fetch.  d2h_bytes: 8 per row that meets
+ * the range plus 8, 8 per candidate, one counter — the working arrays are sized by those rows, not by nq. */
+int  kmdb_new2all_sample_stats_get(const kmdb_db* db, kmdb_sample_stats* out);
+
 /* Replaces SimilarityCalculator::db2db_sp(db_row, db_col, SparseMatrix&, bubbles) (similarity_calculator.cpp:1225-1540),
  * the off-diagonal cell of the all2all-parts grid (call sites console_all2all_parts.cpp:180,226): both databases
  * resident with hashtables on the same device.  out: n_samples(db_row) x n_samples(db_col) uint32, row-major, host
@@ -557,6 +609,21 @@ int  kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(kmdb_node* node, const
                                                           uint64_t* out_kmer_counts, const kmdb_opts* opts);
 /* the last sparse new2all call on the node: cells, nnz_device and d2h_bytes summed over the devices, the slowest device's compact_ms */
 int  kmdb_node_new2all_sparse_stats_get(const kmdb_node* node, kmdb_new2all_sparse_stats* out);
+/* = kmdb_new2all_batch_sampled over the query shards of the node (console_new2all.cpp:76-78, 130-148 + sampler.h:123-139 made multi-GPU): after
+ * the reduce-scatter every device selects the candidates of ITS chunk of the summed rows on its own stream (kmdb_sampled_from_rows_device's
+ * select), the host decides once (kmdbh_query_rows_select).  A node of another partition than KMDB_PARTITION_PREFIX_TABLES is refused;
+ * argument errors are raised before any device thread starts. */
+int  kmdb_node_new2all_batch_sampled(kmdb_node* node, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                     size_t n_filters, const uint32_t* sample_kmers /* [N] */, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                     const kmdb_opts* opts);
+/* The text entry (kmdb_new2all_batch_seq_alphabet_sampled over the node): a query's count is complete only when every device has reported, so the
+ * select is a second pass over the devices with the chunks still resident, as in kmdb_node_new2all_batch_seq_alphabet_sparse_filtered. */
+int  kmdb_node_new2all_batch_seq_alphabet_sampled(kmdb_node* node, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                  double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                  const uint32_t* sample_kmers /* [N] */, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                                  uint64_t* out_kmer_counts, const kmdb_opts* opts);
+/* the last sampled new2all call on the node: the fields of kmdb_sample_stats summed over the devices, the slowest device's select_ms */
+int  kmdb_node_new2all_sample_stats_get(const kmdb_node* node, kmdb_sample_stats* out);
 
 /* ---------------------------------------------------------------------------------------
  * Host-side helpers of the front-end (no GPU needed).  They mirror the reference's loader

@@ -28,11 +28,13 @@ from .capi import (  # noqa: F401
     lib,
     lib_path,
     make_view,
+    metric,
     minhash_batch,
     minhash_geometry,
     minhash_load,
     minhash_stats,
     minhash_store,
+    query_rows_select,
     range_plan,
     sample_rows_select,
     sort_unique,

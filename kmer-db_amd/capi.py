@@ -150,6 +150,8 @@ EXPORTS = [
     "kmdb_all2all_sampled", "kmdb_sampled_from_dense_device", "kmdb_node_all2all_sampled", "kmdb_db_sample_stats", "kmdbh_sample_rows_select",
     "kmdb_db2db_sparse_filtered", "kmdb_db2db_stats_get",
     "kmdb_db2db_sampled", "kmdb_sampled_from_rect_device", "kmdb_db2db_sample_stats_get",
+    "kmdb_new2all_batch_sampled", "kmdb_new2all_batch_seq_alphabet_sampled", "kmdb_sampled_from_rows_device", "kmdbh_query_rows_select", "kmdb_new2all_sample_stats_get",
+    "kmdb_node_new2all_batch_sampled", "kmdb_node_new2all_batch_seq_alphabet_sampled", "kmdb_node_new2all_sample_stats_get",
     "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
@@ -234,6 +236,22 @@ def lib():
     L.kmdb_sampled_from_rect_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_db2db_sample_stats_get.argtypes = [C.c_void_p, C.POINTER(_SampleStats)]
+    L.kmdb_node_new2all_batch_sampled.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p,
+                                                  C.c_int, C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_node_new2all_batch_seq_alphabet_sampled.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                                               C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse), C.c_void_p,
+                                                               C.POINTER(_Opts)]
+    L.kmdb_node_new2all_sample_stats_get.argtypes = [C.c_void_p, C.POINTER(_SampleStats)]
+    L.kmdb_new2all_batch_sampled.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
+                                             C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_new2all_batch_seq_alphabet_sampled.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                                          C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse), C.c_void_p,
+                                                          C.POINTER(_Opts)]
+    L.kmdb_sampled_from_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t,
+                                                C.c_void_p, C.c_int, C.c_uint32, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdbh_query_rows_select.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(_CellFilter), C.c_size_t,
+                                          C.POINTER(C.POINTER(_Sparse)), C.c_size_t, C.POINTER(_Sparse)]
+    L.kmdb_new2all_sample_stats_get.argtypes = [C.c_void_p, C.POINTER(_SampleStats)]
     for name in ("kmdb_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_sparse_filtered"):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
                                      C.POINTER(_Sparse), C.POINTER(_Opts)]
@@ -845,6 +863,44 @@ class DeviceDB:
                                                      C.byref(raw), C.byref(o)))
         return _rows_out(raw)
 
+    def new2all_sampled(self, queries, criterion, count, sample_kmers, filters=()):
+        """kmdb_new2all_batch_sampled: per query (a sorted unique k-mer array) its `count` best database samples by `criterion` (new2all -sample-rows
+        criterion:count) — ascending ids, val = common k-mers, measure = the score.  The candidates are selected on the device, the decision is the
+        host's; a = the query's own k-mer count, b = sample_kmers[sample]."""
+        keep, ptrs, cnts, nq = _kmer_queries(queries)
+        raw, o, sk = _Sparse(), _opts(self.device), _u32(sample_kmers)
+        _check(lib().kmdb_new2all_batch_sampled(self._d, ptrs, cnts, nq, _filters(filters), len(filters), _ptr(sk), _criterion(criterion), int(count), C.byref(raw),
+                                                C.byref(o)))
+        return _rows_out(raw)
+
+    def new2all_seq_sampled(self, seqs, criterion, count, sample_kmers, filters=(), fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        """kmdb_new2all_batch_seq_alphabet_sampled: as new2all_sampled with the queries given as sequence text; returns (SparseRows, unique k-mer count
+        per query)"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        keep, ptrs, lens, nq = _text_queries(seqs)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        raw, o, sk = _Sparse(), _opts(self.device), _u32(sample_kmers)
+        _check(lib().kmdb_new2all_batch_seq_alphabet_sampled(self._d, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet), _filters(filters),
+                                                             len(filters), _ptr(sk), _criterion(criterion), int(count), C.byref(raw), cnt.ctypes.data, C.byref(o)))
+        return _rows_out(raw), cnt[:nq]
+
+    def sampled_from_rows_device(self, dev_ptr, nq, n_cols, criterion, count, query_kmers, sample_kmers, cell_lo=0, cell_hi=None, filters=(), stream=None):
+        """kmdb_sampled_from_rows_device: the candidates (no measures) of the cells [cell_lo, cell_hi) of a row-major nq x n_cols uint32 buffer of query
+        rows the caller accumulated; dev_ptr = device address of cell_lo.  All nq rows come back, those outside the range empty; the candidates of
+        several ranges go to query_rows_select together."""
+        raw, o = _Sparse(), _opts(self.device, stream=stream)
+        qk, sk = _u32(query_kmers), _u32(sample_kmers)
+        _check(lib().kmdb_sampled_from_rows_device(self._d, C.c_void_p(dev_ptr), int(nq), int(n_cols), int(cell_lo), int(nq) * int(n_cols) if cell_hi is None else int(cell_hi),
+                                                   _ptr(qk), _filters(filters), len(filters), _ptr(sk), _criterion(criterion), int(count), C.byref(raw), C.byref(o)))
+        return _rows_out(raw)
+
+    def new2all_sample_stats(self):
+        """kmdb_new2all_sample_stats_get: the last sampled new2all (or query-rows) call on the handle"""
+        s = _SampleStats()
+        _check(lib().kmdb_new2all_sample_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+
     def new2all_sparse_stats(self):
         """kmdb_new2all_sparse_stats_get: the last sparse new2all call on the handle"""
         s = _New2allSparseStats()
@@ -968,6 +1024,32 @@ class NodeDB:
                                                                           C.byref(raw), cnt.ctypes.data, None))
         return _rows_out(raw), cnt[:nq]
 
+    def new2all_sampled(self, queries, criterion, count, sample_kmers, filters=()):
+        """kmdb_node_new2all_batch_sampled: DeviceDB.new2all_sampled over the query shards of the node — every device selects on its own chunk of
+        the summed rows, the host decides once"""
+        keep, ptrs, cnts, nq = _kmer_queries(queries)
+        raw, sk = _Sparse(), _u32(sample_kmers)
+        _check(lib().kmdb_node_new2all_batch_sampled(self._n, ptrs, cnts, nq, _filters(filters), len(filters), _ptr(sk), _criterion(criterion), int(count),
+                                                     C.byref(raw), None))
+        return _rows_out(raw)
+
+    def new2all_seq_sampled(self, seqs, criterion, count, sample_kmers, filters=(), fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
+        """kmdb_node_new2all_batch_seq_alphabet_sampled: (SparseRows, unique k-mer count per query)"""
+        if alphabet is None:
+            alphabet = 1 if preserve_strand else 0
+        keep, ptrs, lens, nq = _text_queries(seqs)
+        cnt = np.zeros(max(nq, 1), dtype=np.uint64)
+        raw, sk = _Sparse(), _u32(sample_kmers)
+        _check(lib().kmdb_node_new2all_batch_seq_alphabet_sampled(self._n, ptrs, lens, nq, float(fraction), float(start_fraction), int(alphabet), _filters(filters),
+                                                                  len(filters), _ptr(sk), _criterion(criterion), int(count), C.byref(raw), cnt.ctypes.data, None))
+        return _rows_out(raw), cnt[:nq]
+
+    def new2all_sample_stats(self):
+        """kmdb_node_new2all_sample_stats_get: the last sampled new2all call on the node (sums over the devices, the slowest select_ms)"""
+        s = _SampleStats()
+        _check(lib().kmdb_node_new2all_sample_stats_get(self._n, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+
     def new2all_sparse_stats(self):
         """kmdb_node_new2all_sparse_stats_get: the last sparse new2all call on the node (sums over the devices, the slowest compact_ms)"""
         s = _New2allSparseStats()
@@ -1032,6 +1114,28 @@ def sample_rows_select(criterion, count, kmer_length, sample_kmers, parts, filte
         return SparseRows(out)
     finally:
         lib().kmdb_sparse_free(C.byref(out))
+
+
+def metric(criterion, common, cnt_row, cnt_col, kmer_length):
+    """kmdbh_metric (no GPU): the measure of one cell — uint32 wrap-around integer parts, double arithmetic"""
+    return float(lib().kmdbh_metric(_criterion(criterion), int(common), int(cnt_row), int(cnt_col), int(kmer_length)))
+
+
+def query_rows_select(criterion, count, kmer_length, query_kmers, sample_kmers, parts, filters=()):
+    """kmdbh_query_rows_select (no GPU): parts = candidate rows of the same nq queries, each a SparseRows or a (row_ptr, col, val) triple -> SparseRows
+    of the `count` best database samples per query that pass the filters: ascending ids, val = common k-mers, measure = the score"""
+    raws, keep = [], []
+    for p in parts:
+        rp, col, val = (p.row_ptr, p.col, p.val) if isinstance(p, SparseRows) else p
+        r, k = _raw_rows(len(rp) - 1, rp, col, val)
+        raws.append(r)
+        keep.append(k)
+    arr = (C.POINTER(_Sparse) * max(1, len(raws)))(*[C.pointer(r) for r in raws])
+    qk, sk = _u32(query_kmers), _u32(sample_kmers)
+    out = _Sparse()
+    _check(lib().kmdbh_query_rows_select(_criterion(criterion), int(count), int(kmer_length), _ptr(qk), 0 if query_kmers is None else len(query_kmers),
+                                         _ptr(sk), _filters(filters), len(filters), arr, len(raws), C.byref(out)))
+    return _rows_out(out)
 
 
 def extract_kmers(seq, k, fraction=1.0, start_fraction=0.0, preserve_strand=False):

@@ -49,4 +49,9 @@ __device__ __forceinline__ double dev_ratio(int kind, uint32_t c, uint32_t a, ui
     default:            return (double)c;
     }
 }
+// Query rows (new2all) are cut into segments of this many columns, a wave each, by the compaction of new2all_sparse.hip and by the row select
+// of sample_rows.hip: a row of 10 000 samples is 5 waves, a row of a million 489 — enough waves per row to fill the chip with a handful of
+// queries, few enough counts (8 B each) that the scan stays small against the rows
+constexpr uint32_t N2S_SEG = 2048;
+constexpr uint64_t N2S_GRID_MAX = 1ull << 30;           // segments per launch of either: more go out in several launches
 }  // namespace

@@ -318,7 +318,7 @@ int kmdb_engine_get(kmdb_db* db, kmdb_engine_view* o) {
     o->pid2dfs = db->pid2dfs; o->qs_index = db->qs_index; o->qs_count = db->qs_count; o->stream = db->stream;
     o->max_depth = db->max_depth; o->list_sets = &db->list_sets; o->list_sets_nb = &db->list_sets_nb; o->list_sets_tried = &db->list_sets_tried;
     o->rl_ofs = &db->rl_ofs; o->rl_runs = &db->rl_runs; o->rl_node = &db->rl_node; o->rl_tried = &db->rl_tried;
-    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats; o->d2_sample_stats = &db->d2_sample_stats; o->n2s_stats = &db->n2s_stats;
+    o->device_bytes = &db->stats.device_bytes; o->d2_stats = &db->d2_stats; o->d2_sample_stats = &db->d2_sample_stats; o->n2s_stats = &db->n2s_stats; o->n2a_sample_stats = &db->n2a_sample_stats;
     for (int i = 0; i < 4; ++i) o->ev[i] = db->ev[i];
     return 0;
 }
@@ -933,6 +933,79 @@ extern "C" int kmdb_sampled_from_rect_device(kmdb_db* db, const void* cells_dev,
                          count, out_row_candidates, out_col_candidates, &db->d2_sample_stats)) return 1;
     if (finish_stats(db, st)) { kmdb_sparse_free(out_row_candidates); kmdb_sparse_free(out_col_candidates); return 1; }
     kmdb_release_staging(db);
+    return 0;
+}
+
+// The same on the QUERY ROWS of new2all (engine_internal.h): the flat cells [cell_lo, cell_hi) of a row-major nq x n_cols rectangle in HBM.
+// One-sided: the slots are the rows that meet the range, a = the query's count, b = the sample's.  out has all nq rows.
+int kmdb_sample_query_rows_check(const char* who, uint64_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi) {
+    if (n_cols == 0 || n_cols >= (1ull << 32)) return kmdb_set_error(std::string(who) + ": n_cols must be between 1 and 2^32 - 1");
+    if (nq >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": too many queries in one batch");
+    if (cell_lo > cell_hi) return kmdb_set_error(std::string(who) + ": cell_lo > cell_hi");
+    if (cell_hi > nq * n_cols) return kmdb_set_error(std::string(who) + ": cell_hi beyond the nq x n_cols cells of the batch");
+    return 0;
+}
+int kmdb_sample_query_rows(const char* who, hipStream_t st, int kmer_length, const uint32_t* cells_dev, uint64_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi,
+                           const uint32_t* query_kmers, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count,
+                           kmdb_sparse_rows* out, kmdb_sample_stats* stats) {
+    std::memset(out, 0, sizeof *out);
+    const uint64_t q_lo = cell_hi > cell_lo ? cell_lo / n_cols : 0, n_slots = cell_hi > cell_lo ? (cell_hi - 1) / n_cols + 1 - q_lo : 0;
+    DevBuf<uint32_t> d_qk, d_sk;
+    DEV_ALLOC(d_qk, std::max<uint64_t>(n_slots, 1));
+    DEV_ALLOC(d_sk, n_cols);
+    if (n_slots) HIP_TRY(hipMemcpyAsync(d_qk, query_kmers + q_lo, n_slots * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_sk, sample_kmers, n_cols * 4, hipMemcpyHostToDevice, st));
+    const Proxy px = proxy_of(criterion);
+    kmdb_sample_job job;
+    job.query_rows = true; job.cells = cells_dev; job.nr = nq; job.nc = n_cols; job.cell_lo = cell_lo; job.cell_hi = cell_hi;
+    job.counts_dev = d_qk; job.col_counts_dev = d_sk; job.kind = px.kind; job.flip = px.flip; job.count = count;
+    job_bounds(job, filters, n_filters, kmer_length);
+    kmdb_sample_stats ss{};
+    try {
+        SampleSelection sel;
+        auto ab = [&](uint64_t s, uint32_t o, uint32_t& a, uint32_t& b) { a = query_kmers[q_lo + s]; b = sample_kmers[o]; };
+        if (select_complete(st, job, n_slots, px, count, kmer_length, filters, n_filters, ab, ss, sel)) return 1;
+        kmdb_sparse_rows part{};
+        if (pack_slots(who, sel, 0, n_slots, &part)) return 1;
+        // the rows outside the range are empty
+        uint64_t* ptr = (uint64_t*)std::malloc((nq + 1) * 8);
+        if (!ptr) { kmdb_sparse_free(&part); return kmdb_set_error(std::string(who) + ": out of host memory for the result"); }
+        for (uint64_t q = 0; q <= nq; ++q) ptr[q] = q < q_lo ? 0 : q - q_lo <= n_slots ? part.row_ptr[q - q_lo] : part.nnz;
+        std::free(part.row_ptr);
+        part.row_ptr = ptr; part.n_rows = nq;
+        *out = part;
+        ss.candidates = out->nnz;
+        if (stats) *stats = ss;
+        return 0;
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+
+extern "C" int kmdb_sampled_from_rows_device(kmdb_db* db, const void* rows_dev, size_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi,
+                                             const uint32_t* query_kmers, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers,
+                                             int criterion, uint32_t count, kmdb_sparse_rows* out_candidates, const kmdb_opts* opts) {
+    const char* who = "kmdb_sampled_from_rows_device";
+    if (!db || !out_candidates) return kmdb_set_error(std::string(who) + ": null argument");
+    if (check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    if (nq && !query_kmers) return kmdb_set_error(std::string(who) + ": query_kmers is NULL");
+    if (kmdb_sample_query_rows_check(who, nq, n_cols, cell_lo, cell_hi)) return 1;
+    if (!rows_dev && cell_hi > cell_lo) return kmdb_set_error(std::string(who) + ": null rows");
+    HIP_TRY(hipSetDevice(db->device));
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
+    HIP_TRY(hipEventRecord(db->ev[0], st)); HIP_TRY(hipEventRecord(db->ev[1], st)); HIP_TRY(hipEventRecord(db->ev[2], st));
+    db->stats.path = KMDB_PATH_NONE;
+    db->n2a_sample_stats = kmdb_sample_stats{};
+    if (kmdb_sample_query_rows(who, st, (int)db->kmer_length, (const uint32_t*)rows_dev, nq, n_cols, cell_lo, cell_hi, query_kmers, filters, n_filters, sample_kmers,
+                               criterion, count, out_candidates, &db->n2a_sample_stats)) return 1;
+    if (finish_stats(db, st)) { kmdb_sparse_free(out_candidates); return 1; }
+    kmdb_release_staging(db);
+    return 0;
+}
+
+extern "C" int kmdb_new2all_sample_stats_get(const kmdb_db* db, kmdb_sample_stats* out) {
+    if (!db || !out) return kmdb_set_error("kmdb_new2all_sample_stats_get: null argument");
+    *out = db->n2a_sample_stats;
     return 0;
 }
 

@@ -44,6 +44,7 @@ struct kmdb_engine_view {
     struct kmdb_db2db_stats* d2_stats;   // the last db2db call with this handle as the row database (kmdb_db2db_stats_get)
     struct kmdb_sample_stats* d2_sample_stats;   // the last sampled db2db call with this handle as the row database (kmdb_db2db_sample_stats_get)
     struct kmdb_new2all_sparse_stats* n2s_stats;   // the last sparse new2all call on the handle (kmdb_new2all_sparse_stats_get)
+    struct kmdb_sample_stats* n2a_sample_stats;   // the last sampled new2all call on the handle (kmdb_new2all_sample_stats_get)
     void* stream;
     void* ev[4];
 };
@@ -98,6 +99,16 @@ int kmdb_sample_rect_check(const char* who, uint64_t nr, uint64_t nc);
 int kmdb_sample_rect(const char* who, hipStream_t st, int kmer_length, const uint32_t* cells_dev, uint64_t nr, uint64_t nc, const unsigned char* touched,
                      const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* row_kmers, const uint32_t* col_kmers, int criterion, uint32_t count,
                      kmdb_sparse_rows* out_row, kmdb_sparse_rows* out_col, kmdb_sample_stats* stats);
+
+// ---- the same selection on the query rows of new2all (engine.hip over sample_rows.hip; new2all_sparse.hip selects a batch's rows with it)
+// n_cols in [1, 2^32), nq < 2^31, cell_lo <= cell_hi <= nq * n_cols — before any device work
+int kmdb_sample_query_rows_check(const char* who, uint64_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi);
+// The complete candidates of the flat cells [cell_lo, cell_hi) of a row-major nq x n_cols rectangle of query rows (cells_dev points at cell_lo,
+// complete on `st`): all nq rows in `out`, the rows outside the range empty, ascending sample ids, val = common k-mers, no measures.  One-sided:
+// a = query_kmers[row], b = sample_kmers[col].  stats (may be null) is filled.  0, or 1 with the error set (out freed).
+int kmdb_sample_query_rows(const char* who, hipStream_t st, int kmer_length, const uint32_t* cells_dev, uint64_t nq, uint64_t n_cols, uint64_t cell_lo, uint64_t cell_hi,
+                           const uint32_t* query_kmers, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count,
+                           kmdb_sparse_rows* out, kmdb_sample_stats* stats);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

@@ -105,6 +105,7 @@ struct kmdb_db {
     kmdb_new2all_sparse_stats n2s_stats{};   // the last sparse new2all call on the handle (kmdb_new2all_sparse_stats_get)
     kmdb_sample_stats sample_stats{};   // the last sampled call on the handle (kmdb_db_sample_stats)
     kmdb_sample_stats d2_sample_stats{};   // the last sampled db2db / rectangle call with this handle as the row database (kmdb_db2db_sample_stats_get)
+    kmdb_sample_stats n2a_sample_stats{};   // the last sampled new2all / query-rows call on the handle (kmdb_new2all_sample_stats_get)
     bool blocks_prepared = false;   // width estimate + working set of the block-record pipeline exist (made at upload for all2all
                                     // uploads, on the first all2all call for uploads that carry hashtables: new2all / db2db use)
     std::string fallback_reason;    // why the block-record pipeline cannot take this database ("" = it can)

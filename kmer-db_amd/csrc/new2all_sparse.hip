@@ -27,9 +27,7 @@
 
 namespace {
 
-// columns per segment: a row of 10 000 samples is 5 waves, a row of a million 489 — enough waves per row to fill the chip with a handful
-// of queries, few enough counts (8 B each) that the scan stays small against the rows
-constexpr uint32_t N2S_SEG = 2048;
+// (N2S_SEG, the columns per segment, lives in cell_filter.h: the row select of sample_rows.hip cuts the same rows the same way)
 
 // One wave per segment `seg0 + blockIdx.x` = row * nseg + s: the columns [s * N2S_SEG, min(N, (s + 1) * N2S_SEG)) of query `row`.  `cells`
 // points at cell cell_lo.  A lane whose column is beyond the row, or whose cell lies outside [cell_lo, cell_hi), loads nothing: that address
@@ -122,11 +120,10 @@ int kmdb_n2a_rows_compact(const char* who_, kmdb_db* db, const uint32_t* cells_d
     // the segments of the rows that meet the range (the others keep a count of zero)
     uint64_t seg_lo = 0, seg_hi = 0;
     if (cell_hi > cell_lo && N) { seg_lo = cell_lo / N * nseg; seg_hi = ((cell_hi - 1) / N + 1) * nseg; }
-    constexpr uint64_t GRID_MAX = 1ull << 30;                    // segments per launch
     HIP_TRY(hipEventRecord(c0, st));
     HIP_TRY(hipMemsetAsync(d_cnt.get(), 0, (n_segs + 1) * 8, st));
-    for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += GRID_MAX) {
-        hipLaunchKernelGGL((n2s_segments_kernel<false>), dim3((unsigned)std::min(GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
+    for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += N2S_GRID_MAX) {
+        hipLaunchKernelGGL((n2s_segments_kernel<false>), dim3((unsigned)std::min(N2S_GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
                            cell_lo, cell_hi, static_cast<unsigned long long*>(d_cnt.get()), (const unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, df,
                            static_cast<uint32_t*>(d_sk.get()));
         HIP_TRY(hipGetLastError());
@@ -144,8 +141,8 @@ int kmdb_n2a_rows_compact(const char* who_, kmdb_db* db, const uint32_t* cells_d
     if (nnz_dev > cell_hi - cell_lo) return kmdb_set_error(who + ": internal error (more kept cells than cells)");
     DEV_ALLOC_BYTES(d_col, nnz_dev * 4); DEV_ALLOC_BYTES(d_val, nnz_dev * 4);
     if (nnz_dev)
-        for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += GRID_MAX) {
-            hipLaunchKernelGGL((n2s_segments_kernel<true>), dim3((unsigned)std::min(GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
+        for (uint64_t s0 = seg_lo; s0 < seg_hi; s0 += N2S_GRID_MAX) {
+            hipLaunchKernelGGL((n2s_segments_kernel<true>), dim3((unsigned)std::min(N2S_GRID_MAX, seg_hi - s0)), dim3(64), 0, st, cells_dev, (uint32_t)N, nseg, s0, seg_hi,
                                cell_lo, cell_hi, (unsigned long long*)nullptr, static_cast<unsigned long long*>(d_scan.get()), static_cast<uint32_t*>(d_col.get()), static_cast<uint32_t*>(d_val.get()), df,
                                static_cast<uint32_t*>(d_sk.get()));
             HIP_TRY(hipGetLastError());
@@ -239,6 +236,83 @@ extern "C" int kmdb_new2all_batch_seq_alphabet_sparse_filtered(kmdb_db* db, cons
     if (nq && (!seqs || !seq_lens || !out_kmer_counts)) return kmdb_set_error(std::string(who) + ": null argument");
     if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error(std::string(who) + ": unknown alphabet " + std::to_string(alphabet));
     return n2s_batch(who, db, nq, filters, n_filters, sample_kmers, measure, out, opts, false, [&](uint32_t* rows, const kmdb_opts* o, uint32_t* qk) -> int {
+        // the query counts are the device extractor's unique counts
+        if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, out_kmer_counts, o)) return 1;
+        for (size_t q = 0; q < nq; ++q) qk[q] = (uint32_t)out_kmer_counts[q];
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// new2all -sample-rows <criterion>:<count>: every query keeps its `count` best database samples (the rule of Sampler, reference
+// src/sampler.h:44-67, applied to the sparse row console_new2all.cpp:130-148 writes).  The rows of a batch are accumulated as above, the
+// candidates selected where they are (kmdb_sample_query_rows: sample_rows.hip, the completeness rule and the re-fetch of engine.hip), the
+// decision is the host's (kmdbh_query_rows_select).  Only the candidates leave HBM.
+// ------------------------------------------------------------------------------------------
+template <class Fill>
+static int n2s_batch_sampled(const char* who_, kmdb_db* db, size_t nq, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion,
+                             uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts, Fill&& fill) {
+    const std::string who(who_);
+    std::memset(out, 0, sizeof *out);
+    kmdb_engine_view e;
+    if (kmdb_engine_get(db, &e)) return 1;
+    if ((!e.n_buckets && e.qs_count <= 1) || !e.slots) return kmdb_set_error(who + ": database was uploaded without hashtables");
+    if (e.qs_count > 1)
+        return kmdb_set_error(who + ": a query shard holds partial sums and partial k-mer counts (select on the summed rows with kmdb_sampled_from_rows_device)");
+    if (e.N == 0) return kmdb_set_error(who + ": the database holds no samples");
+    if (kmdb_sample_query_rows_check(who_, nq, e.N, 0, (uint64_t)nq * e.N)) return 1;
+    HIP_TRY(hipSetDevice(e.device));
+    hipStream_t st = stream_of(e, opts);
+    const uint64_t cells = (uint64_t)nq * e.N;
+    DevBuf<void> rows;
+    DEV_ALLOC_BYTES(rows, cells * 4);
+    if (cells) HIP_TRY(hipMemsetAsync(rows.get(), 0, cells * 4, st));
+    kmdb_opts o{};
+    if (opts) o = *opts; else { o.abi_version = KMDB_ABI_VERSION; o.device = e.device; o.shard_count = 1; }
+    o.stream = st;
+    std::vector<uint32_t> qk;
+    try { qk.assign(std::max<size_t>(nq, 1), 0); } catch (const std::exception&) { return kmdb_set_error(who + ": out of host memory"); }
+    if (fill(static_cast<uint32_t*>(rows.get()), &o, qk.data())) return 1;
+    kmdb_stats before{};
+    if (kmdb_db_stats(db, &before)) return 1;                    // (kernel_ms of the accumulation that has just ended)
+    kmdb_sample_stats ss{};
+    kmdb_sparse_rows cand;
+    if (kmdb_sample_query_rows(who_, st, (int)e.kmer_length, static_cast<uint32_t*>(rows.get()), nq, e.N, 0, cells, qk.data(), filters, n_filters, sample_kmers, criterion,
+                               count, &cand, &ss)) return 1;
+    // kernel_ms of the call = accumulation + selection.  (kmdb_engine_set_times keeps no second figure any more: its dominant_ms argument is
+    // not read, and every caller passes the call's total for it, as n2s_batch does.)
+    const double call_ms = before.kernel_ms + ss.select_ms;
+    kmdb_engine_set_times(db, call_ms, call_ms);
+    *e.n2a_sample_stats = ss;
+    const kmdb_sparse_rows* parts[1] = {&cand};
+    const int rc = kmdbh_query_rows_select(criterion, count, (int)e.kmer_length, qk.data(), nq, sample_kmers, filters, n_filters, parts, 1, out);
+    kmdb_sparse_free(&cand);
+    return rc;
+}
+
+extern "C" int kmdb_new2all_batch_sampled(kmdb_db* db, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                          size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                          const kmdb_opts* opts) {
+    const char* who = "kmdb_new2all_batch_sampled";
+    if (!db || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    if (nq && (!kmers || !counts)) return kmdb_set_error(std::string(who) + ": null argument");
+    return n2s_batch_sampled(who, db, nq, filters, n_filters, sample_kmers, criterion, count, out, opts, [&](uint32_t* rows, const kmdb_opts* o, uint32_t* qk) -> int {
+        for (size_t q = 0; q < nq; ++q) qk[q] = (uint32_t)counts[q];
+        return kmdb_new2all_batch_device(db, kmers, counts, nq, rows, o);
+    });
+}
+
+extern "C" int kmdb_new2all_batch_seq_alphabet_sampled(kmdb_db* db, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                       double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                       const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                                       uint64_t* out_kmer_counts, const kmdb_opts* opts) {
+    const char* who = "kmdb_new2all_batch_seq_alphabet_sampled";
+    if (!db || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    if (nq && (!seqs || !seq_lens || !out_kmer_counts)) return kmdb_set_error(std::string(who) + ": null argument");
+    if (alphabet < 0 || alphabet >= KMDB_ALPHABET_COUNT) return kmdb_set_error(std::string(who) + ": unknown alphabet " + std::to_string(alphabet));
+    return n2s_batch_sampled(who, db, nq, filters, n_filters, sample_kmers, criterion, count, out, opts, [&](uint32_t* rows, const kmdb_opts* o, uint32_t* qk) -> int {
         // the query counts are the device extractor's unique counts
         if (kmdb_new2all_batch_seq_alphabet_device(db, seqs, seq_lens, nq, fraction, start_fraction, alphabet, rows, out_kmer_counts, o)) return 1;
         for (size_t q = 0; q < nq; ++q) qk[q] = (uint32_t)out_kmer_counts[q];

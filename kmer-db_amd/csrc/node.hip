@@ -123,6 +123,7 @@ struct kmdb_node {
     int partition = KMDB_PARTITION_PREFIX;
     kmdb_node_stats stats{};
     kmdb_new2all_sparse_stats n2s_stats{};                   // the last sparse new2all call (kmdb_node_new2all_sparse_stats_get)
+    kmdb_sample_stats n2a_sample_stats{};                    // the last sampled new2all call (kmdb_node_new2all_sample_stats_get)
     Rendezvous meet;
     std::atomic<bool> aborted{false};                        // a collective failed after the rendezvous: the communicators are gone
 };
@@ -680,6 +681,36 @@ namespace {
 // counts_known: the queries' counts are known before the rows are (k-mer entry): the compaction is queued behind the collective.  Else (text
 // entry) they are complete only once every device has reported: query_counts() is called after the first pass and the compaction is a second
 // pass over the devices, the chunks still resident.
+// The passes of a call that works on every device's chunk of the summed rows: on_chunk(d, chunk, lo, hi) runs on the device's thread and stream.
+template <class Run, class Counts, class OnChunk>
+int node_new2all_on_chunks(kmdb_node* nd, const char* who, size_t nq, const kmdb_opts* opts, bool counts_known, Run& run, Counts&& query_counts,
+                           std::vector<uint32_t>& qk, OnChunk&& on_chunk) {
+    if (counts_known) {
+        query_counts(qk);
+        return node_new2all_call(nd, who, nq, opts, run, on_chunk);
+    }
+    int rc = node_new2all_call(nd, who, nq, opts, run, [](size_t, const uint32_t*, uint64_t, uint64_t) -> int { return 0; });
+    if (rc) return rc;
+    query_counts(qk);
+    const uint64_t cells = (uint64_t)nq * nd->N, per = node_rows_per(nd, cells);
+    rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
+        if (!dev_ok) return 1;
+        DevSlot& s = nd->dev[d];
+        const uint32_t* p; uint64_t lo, hi;
+        node_rows_chunk(nd, d, cells, per, p, lo, hi);
+        NODE_TRY(hipEventRecord(s.ev[2], s.stream));
+        if (on_chunk(d, p, lo, hi)) return 1;
+        NODE_TRY(hipEventRecord(s.ev[3], s.stream));
+        NODE_TRY(hipStreamSynchronize(s.stream));
+        float c = 0;
+        NODE_TRY(hipEventElapsedTime(&c, s.ev[2], s.ev[3]));
+        s.d2h_ms = c;
+        return 0;
+    });
+    node_fill_stats(nd);
+    return rc;
+}
+
 template <class Run, class Counts>
 int node_new2all_sparse(kmdb_node* nd, const char* who, size_t nq, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int measure,
                         kmdb_sparse_rows* out, const kmdb_opts* opts, bool counts_known, Run& run, Counts&& query_counts) {
@@ -694,32 +725,7 @@ int node_new2all_sparse(kmdb_node* nd, const char* who, size_t nq, const kmdb_ce
         kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = s.device; o.shard_count = 1; o.stream = s.stream;
         return kmdb_n2a_rows_compact(who, s.shards[0], p, nq, lo, hi, qk.data(), filters, n_filters, sample_kmers, &part[d], &o, &pst[d]);
     };
-    int rc;
-    if (counts_known) {
-        query_counts(qk);
-        rc = node_new2all_call(nd, who, nq, opts, run, compact);
-    } else {
-        rc = node_new2all_call(nd, who, nq, opts, run, [](size_t, const uint32_t*, uint64_t, uint64_t) -> int { return 0; });
-        if (!rc) {
-            query_counts(qk);
-            const uint64_t cells = (uint64_t)nq * nd->N, per = node_rows_per(nd, cells);
-            rc = on_devices(nd, [&](size_t d, bool dev_ok) -> int {
-                if (!dev_ok) return 1;
-                DevSlot& s = nd->dev[d];
-                const uint32_t* p; uint64_t lo, hi;
-                node_rows_chunk(nd, d, cells, per, p, lo, hi);
-                NODE_TRY(hipEventRecord(s.ev[2], s.stream));
-                if (compact(d, p, lo, hi)) return 1;
-                NODE_TRY(hipEventRecord(s.ev[3], s.stream));
-                NODE_TRY(hipStreamSynchronize(s.stream));
-                float c = 0;
-                NODE_TRY(hipEventElapsedTime(&c, s.ev[2], s.ev[3]));
-                s.d2h_ms = c;
-                return 0;
-            });
-            node_fill_stats(nd);
-        }
-    }
+    int rc = node_new2all_on_chunks(nd, who, nq, opts, counts_known, run, query_counts, qk, compact);
     kmdb_new2all_sparse_stats ns{};
     if (!rc) {
         uint64_t nnz = 0;
@@ -804,6 +810,91 @@ extern "C" int kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(kmdb_node* n
     } catch (const std::exception& e) {
         return kmdb_set_error(std::string(who) + ": " + e.what());
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// new2all -sample-rows over the node: the summed rows stay where the reduce-scatter left them and every device selects the candidates of ITS
+// chunk on its own stream (kmdb_sample_query_rows: the row-segment select of sample_rows.hip, complete by the exact decision within the chunk);
+// a row's best `count` within a chunk is a superset of its share of the global best `count`, so the host decides once over the devices'
+// parts (kmdbh_query_rows_select).
+// ------------------------------------------------------------------------------------------
+namespace {
+template <class Run, class Counts>
+int node_new2all_sampled(kmdb_node* nd, const char* who, size_t nq, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion,
+                         uint32_t count, kmdb_sparse_rows* out, const kmdb_opts* opts, bool counts_known, Run& run, Counts&& query_counts) {
+    std::memset(out, 0, sizeof *out);
+    if (nd->partition == KMDB_PARTITION_PREFIX_TABLES && kmdb_sample_query_rows_check(who, nq, nd->N, 0, (uint64_t)nq * nd->N)) return 1;
+    const size_t D = nd->dev.size();
+    std::vector<kmdb_sparse_rows> part(D);
+    for (auto& p : part) std::memset(&p, 0, sizeof p);
+    std::vector<kmdb_sample_stats> pst(D);
+    std::vector<uint32_t> qk;
+    auto select = [&](size_t d, const uint32_t* p, uint64_t lo, uint64_t hi) -> int {
+        return kmdb_sample_query_rows(who, nd->dev[d].stream, (int)nd->kmer_length, p, nq, nd->N, lo, hi, qk.data(), filters, n_filters, sample_kmers, criterion,
+                                      count, &part[d], &pst[d]);
+    };
+    int rc = node_new2all_on_chunks(nd, who, nq, opts, counts_known, run, query_counts, qk, select);
+    if (!rc) {
+        kmdb_sample_stats ss{};
+        std::vector<const kmdb_sparse_rows*> ptrs;
+        for (size_t d = 0; d < D; ++d) {
+            ptrs.push_back(&part[d]);
+            ss.candidates += pst[d].candidates; ss.rows_truncated += pst[d].rows_truncated; ss.rows_refetched += pst[d].rows_refetched;
+            ss.d2h_bytes += pst[d].d2h_bytes; ss.triangle_reads += pst[d].triangle_reads; ss.select_ms = std::max(ss.select_ms, pst[d].select_ms);
+        }
+        nd->n2a_sample_stats = ss;
+        rc = kmdbh_query_rows_select(criterion, count, (int)nd->kmer_length, qk.data(), nq, sample_kmers, filters, n_filters, ptrs.data(), ptrs.size(), out);
+    }
+    const std::string msg = rc ? kmdb_last_error() : "";
+    for (auto& p : part) kmdb_sparse_free(&p);
+    return rc ? kmdb_set_error(msg) : 0;
+}
+}  // namespace
+
+extern "C" int kmdb_node_new2all_batch_sampled(kmdb_node* nd, const uint64_t* const* kmers, const size_t* counts, size_t nq, const kmdb_cell_filter* filters,
+                                               size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                               const kmdb_opts* opts) {
+    const char* who = "kmdb_node_new2all_batch_sampled";
+    // (argument errors before any device thread starts: a refusal must not leave a rank waiting at the rendezvous)
+    if (!nd || !out || (nq && (!kmers || !counts))) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    try {
+        KmerRun run{nd, who, kmers, counts, nq, {}};
+        run.split.resize(nd->dev.size());
+        return node_new2all_sampled(nd, who, nq, filters, n_filters, sample_kmers, criterion, count, out, opts, true, run, [&](std::vector<uint32_t>& qk) {
+            qk.assign(std::max<size_t>(nq, 1), 0);
+            for (size_t q = 0; q < nq; ++q) qk[q] = (uint32_t)counts[q];
+        });
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+
+// The text entry: a query's count is complete only when every device has reported, so the select is a second pass over the devices with the
+// chunks still resident, as in kmdb_node_new2all_batch_seq_alphabet_sparse_filtered.
+extern "C" int kmdb_node_new2all_batch_seq_alphabet_sampled(kmdb_node* nd, const char* const* seqs, const size_t* seq_lens, size_t nq, double fraction,
+                                                            double start_fraction, int32_t alphabet, const kmdb_cell_filter* filters, size_t n_filters,
+                                                            const uint32_t* sample_kmers, int criterion, uint32_t count, kmdb_sparse_rows* out,
+                                                            uint64_t* out_kmer_counts, const kmdb_opts* opts) {
+    const char* who = "kmdb_node_new2all_batch_seq_alphabet_sampled";
+    if (!nd || !out || (nq && (!seqs || !seq_lens || !out_kmer_counts))) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_check_sample_args(who, filters, n_filters, sample_kmers, criterion, count)) return 1;
+    try {
+        SeqRun run{who, seqs, seq_lens, nq, fraction, start_fraction, alphabet, {}};
+        run.per_dev.assign(nd->dev.size(), std::vector<uint64_t>(nq, 0));
+        return node_new2all_sampled(nd, who, nq, filters, n_filters, sample_kmers, criterion, count, out, opts, false, run, [&](std::vector<uint32_t>& qk) {
+            qk.assign(std::max<size_t>(nq, 1), 0);
+            for (size_t q = 0; q < nq; ++q) { out_kmer_counts[q] = run.count(q); qk[q] = (uint32_t)out_kmer_counts[q]; }
+        });
+    } catch (const std::exception& e) {
+        return kmdb_set_error(std::string(who) + ": " + e.what());
+    }
+}
+
+extern "C" int kmdb_node_new2all_sample_stats_get(const kmdb_node* nd, kmdb_sample_stats* out) {
+    if (!nd || !out) return kmdb_set_error("kmdb_node_new2all_sample_stats_get: null argument");
+    *out = nd->n2a_sample_stats;
+    return 0;
 }
 
 extern "C" int kmdb_node_new2all_sparse_stats_get(const kmdb_node* nd, kmdb_new2all_sparse_stats* out) {

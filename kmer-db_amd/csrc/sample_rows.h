@@ -19,6 +19,11 @@ struct kmdb_sample_job {
     bool rect = false;
     uint64_t nr = 0, nc = 0;
     const uint32_t* col_counts_dev = nullptr;
+    // The third geometry: the QUERY ROWS of new2all — the flat cells [cell_lo, cell_hi) of a row-major nr x nc rectangle (nr queries, nc database
+    // samples; cells = cell `cell_lo`; N, touched, width and rect are not read).  One-sided: the slots are the rows that meet the range, slot s =
+    // query cell_lo / nc + s, whose line lists sample ids; the samples collect nothing.  counts_dev: [slots] the k-mer counts of THOSE queries (a);
+    // col_counts_dev: [nc] of the samples (b).
+    bool query_rows = false;
     size_t n_bounds = 0;                    // the widened bounds of the filters on their plain ratios (RATIO_* of cell_filter.h)
     int bound_kind[12] = {};
     double bound_lo[12] = {}, bound_hi[12] = {};
@@ -26,7 +31,7 @@ struct kmdb_sample_job {
     uint32_t count = 0;
 };
 struct kmdb_sample_result {
-    std::vector<uint64_t> row_ptr;          // [N + 1] symmetric rows ([nr + nc + 1] lines of the slots of a rectangle), ascending columns
+    std::vector<uint64_t> row_ptr;          // [N + 1] symmetric rows ([nr + nc + 1] lines of the slots of a rectangle; [slots + 1] query rows), ascending columns
     std::vector<uint32_t> col, val;
     uint64_t rows_truncated = 0, d2h_bytes = 0;
     double select_ms = 0;                   // HIP events around the passes

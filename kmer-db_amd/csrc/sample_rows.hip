@@ -23,6 +23,13 @@
 // add_to_sampler, reference src/console_all2all_parts.cpp:179-195, 225-241): the tile kernel is a template over the source of its cells
 // (TriSamples / RectSamples below) and everything else works on SLOTS — the N samples of a triangle, the nr row samples followed by the nc
 // column samples of a rectangle.  A pair of a rectangle has one score with the cell's row as the row sample, on either of its two lines.
+//
+// The QUERY ROWS of new2all (RowSegs, sr_segment_kernel) are the third source, and the one-sided one: a query keeps its best database samples,
+// the database samples collect nothing.  A row has no column line, so the tile transpose buys nothing; the rows are cut as new2all_sparse.hip
+// cuts them — a wave per segment of N2S_SEG columns of one row — and the same six passes run over the segments.  The histogram pass folds the
+// 32 lines of a segment into the wave's own 256 bins in LDS and adds the non-zero bins to the row's global histogram once per segment; the
+// count pass writes one count per segment, a scan over the segments gives the emit its places, and columns come out ascending by construction:
+// no per-row cursor and no rank sort (a query row that comes out whole can hold 10^5 entries, and the rank sort is quadratic in a row).
 #include "device_common.h"
 #include "cell_filter.h"
 #include "sample_rows.h"
@@ -274,6 +281,201 @@ __global__ __launch_bounds__(64) void sr_sort_rows_kernel(const unsigned long lo
     }
 }
 
+// RowSegs: the flat cells [cell_lo, cell_hi) of a row-major nq x N rectangle of QUERY rows (cell q * N + s = query q, database sample s; M points
+// at cell cell_lo — the convention of kmdb_new2all_rows_sparse_device).  The slots are the rows that meet the range: slot = q - q_lo.  Segment
+// slot * nseg + s holds the columns [s * N2S_SEG, min(N, (s + 1) * N2S_SEG)) of its row.  a = the QUERY's k-mer count, b = the sample's.
+struct RowSegs {
+    const uint32_t* M;
+    uint32_t N, nseg;
+    uint64_t q_lo, cell_lo, cell_hi;
+    const uint32_t* query_counts;       // [slots] the k-mer counts of the queries q_lo ...
+    const uint32_t* counts;             // [N] of the database samples
+};
+
+// One wave (a workgroup of its own) per segment `seg0 + blockIdx.x`: 32 lines of 64 consecutive cells.  A lane whose column is beyond the row,
+// or whose cell lies outside [cell_lo, cell_hi), loads nothing (that address is a cell of the next row, of another device's chunk, or of
+// nothing at all); cell offsets are 64-bit.
+//   SR_HIST : the ballot loop of sr_tile_kernel folds every line into s_hist, the wave's OWN 256 bins: the leading lane of a bin does a plain
+//             add — within a line every bin is added to once, and the barrier after the line (the workgroup IS the wave: no other wave waits
+//             on it, it only orders the wave's LDS accesses) puts the next line's reads of a bin behind this line's write, whichever lane
+//             made it.  The segment ends with one global atomicAdd per non-zero bin: up to 32 times fewer than one per line.
+//   SR_COUNT: seg_len[seg] = cells with key >= thr[slot]   (seg_len is zeroed: a skipped slot writes nothing; no atomics)
+//   SR_EMIT : those cells from seg_ptr[seg] on, line after line at the running ballot prefix: ascending columns by construction
+template <int MODE>
+__global__ __launch_bounds__(64) void sr_segment_kernel(const RowSegs src, const SrJob q, uint32_t digit, uint64_t seg0, uint64_t seg_end,
+                                                        const SrState* __restrict__ state, uint32_t* __restrict__ hist, const uint32_t* __restrict__ thr,
+                                                        unsigned long long* __restrict__ seg_len, const unsigned long long* __restrict__ seg_ptr,
+                                                        uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval, uint32_t* __restrict__ unrankable) {
+    __shared__ uint32_t s_hist[256];
+    const uint64_t seg = seg0 + blockIdx.x;
+    if (seg >= seg_end) return;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t slot = seg / src.nseg;
+    const uint32_t s = (uint32_t)(seg - slot * src.nseg);
+    const uint32_t c0 = s * N2S_SEG, c1 = src.N - c0 < N2S_SEG ? src.N : c0 + N2S_SEG;      // (s < nseg: c0 < N)
+    const uint64_t base = (src.q_lo + slot) * (uint64_t)src.N;
+    SrState st{};
+    uint32_t th = 0;
+    if (MODE == SR_HIST) {
+        st = state[slot];
+        if (st.done) return;
+        for (uint32_t b = lane; b < 256u; b += 64u) s_hist[b] = 0u;
+        __syncthreads();
+    } else {
+        th = thr[slot];
+        if (th == 0) return;
+    }
+    const uint32_t a = src.query_counts[slot];                   // once per wave
+    unsigned long long out = MODE == SR_EMIT ? seg_ptr[seg] : 0ull;
+    uint32_t count = 0;
+    bool best = false, any = false;
+    for (uint32_t j0 = c0; j0 < c1; j0 += 64u) {
+        const uint32_t j = j0 + lane;
+        const uint64_t cell = base + j;
+        uint32_t v = 0;
+        if (j < c1 && cell >= src.cell_lo && cell < src.cell_hi) v = src.M[cell - src.cell_lo];
+        if (!__ballot(v != 0)) continue;                         // (most lines of a sparse row)
+        uint32_t key = 0;
+        if (v) {
+            const uint32_t b = src.counts[j];
+            if (q.f.n == 0 || dev_keep_ab(q.f, v, a, b)) key = sr_key(q, v, a, b);
+        }
+        if (MODE == SR_HIST) {
+            best |= key == SR_KEY_BEST;
+            const bool on = key != 0 && (digit == 0 || (key >> (32 - 8 * digit)) == st.prefix);
+            const uint32_t bin = (key >> (24 - 8 * digit)) & 255u;
+            unsigned long long m = __ballot(on);
+            if (!m) continue;
+            any = true;
+            while (m) {                                          // one step per distinct bin of the line
+                const int lead = __builtin_ctzll(m);
+                const uint32_t lb = (uint32_t)__shfl((int)bin, lead, 64);
+                const unsigned long long same = __ballot(on && bin == lb);
+                if ((int)lane == lead) s_hist[lb] += (uint32_t)__popcll(same);
+                m &= ~same;
+            }
+            __syncthreads();
+        } else {
+            const bool on = key >= th;                           // (th >= 1: a key of 0 is no cell)
+            const unsigned long long m = __ballot(on);
+            if (MODE == SR_EMIT) {
+                if (on) { const unsigned long long o = out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); ocol[o] = j; oval[o] = v; }
+                out += (uint32_t)__popcll(m);
+            } else count += (uint32_t)__popcll(m);
+        }
+    }
+    if (MODE == SR_HIST) {
+        if (digit == 0 && __ballot(best) && lane == 0) unrankable[slot] = 1u;
+        if (any)                                                 // (wave-uniform; the last line's barrier stands before these reads)
+            for (uint32_t b = lane; b < 256u; b += 64u) {
+                const uint32_t n = s_hist[b];
+                if (n) atomicAdd(&hist[slot * 256 + b], n);
+            }
+    } else if (MODE == SR_COUNT) {
+        if (lane == 0) seg_len[seg] = count;
+    }
+}
+
+// row_ptr[slot] = the scan at the first segment of the slot's row (row_ptr[N] = the scan's last entry, the total), len[slot] = the row's cells
+__global__ void sr_seg_row_ptr_kernel(const unsigned long long* __restrict__ seg_ptr, uint32_t nseg, uint64_t N, unsigned long long* __restrict__ row_ptr,
+                                      unsigned long long* __restrict__ len) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > N) return;
+    const unsigned long long b = seg_ptr[s * nseg];
+    row_ptr[s] = b;
+    if (s < N) len[s] = seg_ptr[(s + 1) * nseg] - b;
+}
+
+// The passes over the query rows: N slots (out->row_ptr is sized and zeroed), N * nseg segments per pass, at most N2S_GRID_MAX per launch.
+template <int MODE>
+int sr_segments_launch(hipStream_t st, const RowSegs& src, const SrJob& q, uint32_t digit, uint64_t n_segs, const SrState* state, uint32_t* hist, const uint32_t* thr,
+                       unsigned long long* seg_len, const unsigned long long* seg_ptr, uint32_t* ocol, uint32_t* oval, uint32_t* unrankable) {
+    for (uint64_t s0 = 0; s0 < n_segs; s0 += N2S_GRID_MAX) {
+        hipLaunchKernelGGL((sr_segment_kernel<MODE>), dim3((unsigned)std::min(N2S_GRID_MAX, n_segs - s0)), dim3(64), 0, st, src, q, digit, s0, n_segs, state, hist, thr,
+                           seg_len, seg_ptr, ocol, oval, unrankable);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+int sr_run_rows(hipStream_t st, const RowSegs& src, const SrJob& q, uint64_t N, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
+    const uint64_t n_segs = N * src.nseg;
+    DevBuf<uint32_t> hist, thr, col, val, unrankable;
+    DevBuf<SrState> state;
+    DevBuf<unsigned long long> seg_len, seg_ptr, len, row_ptr, ntr;
+    DevBuf<char> tmp;
+    DevEvent e0, e1;
+    if (e0.create() || e1.create()) return 1;
+    DEV_ALLOC(thr, N);
+    DEV_ALLOC(seg_len, n_segs + 1);
+    DEV_ALLOC(seg_ptr, n_segs + 1);
+    DEV_ALLOC(len, N);
+    DEV_ALLOC(row_ptr, N + 1);
+    DEV_ALLOC(ntr, 1);
+    HIP_TRY(hipEventRecord(e0, st));
+    HIP_TRY(hipMemsetAsync(seg_len, 0, (n_segs + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(ntr, 0, 8, st));
+    if (only_rows) {
+        // the re-fetch: the listed rows whole, every other row skipped
+        std::vector<uint32_t> h_thr(N, 0);
+        for (size_t i = 0; i < n_only; ++i) h_thr[only_rows[i]] = 1u;
+        HIP_TRY(hipMemcpyAsync(thr, h_thr.data(), N * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        DEV_ALLOC(hist, N * 256);
+        DEV_ALLOC(state, N);
+        DEV_ALLOC(unrankable, N);
+        HIP_TRY(hipMemsetAsync(hist, 0, N * 256 * 4, st));
+        HIP_TRY(hipMemsetAsync(state, 0, N * sizeof(SrState), st));
+        HIP_TRY(hipMemsetAsync(thr, 0, N * 4, st));
+        HIP_TRY(hipMemsetAsync(unrankable, 0, N * 4, st));
+        for (uint32_t d = 0; d < 4; ++d) {
+            if (sr_segments_launch<SR_HIST>(st, src, q, d, n_segs, state, hist, nullptr, nullptr, nullptr, nullptr, nullptr, unrankable)) return 1;
+            hipLaunchKernelGGL(sr_select_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, hist, state, thr, (const uint32_t*)unrankable.get(), N, d, q.count);
+            HIP_TRY(hipGetLastError());
+            ++out->passes;
+        }
+    }
+    if (sr_segments_launch<SR_COUNT>(st, src, q, 0u, n_segs, nullptr, nullptr, thr, seg_len, nullptr, nullptr, nullptr, nullptr)) return 1;
+    ++out->passes;
+    size_t tmp_bytes = 0;
+    HIP_TRY(prim::exclusive_sum(nullptr, tmp_bytes, seg_len.get(), seg_ptr.get(), (size_t)(n_segs + 1), st));
+    DEV_ALLOC(tmp, std::max<size_t>(tmp_bytes, 16));
+    HIP_TRY(prim::exclusive_sum(tmp, tmp_bytes, seg_len.get(), seg_ptr.get(), (size_t)(n_segs + 1), st));
+    hipLaunchKernelGGL(sr_seg_row_ptr_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)seg_ptr.get(), src.nseg, N, row_ptr.get(), len.get());
+    if (!only_rows) hipLaunchKernelGGL(sr_truncated_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, state, (const unsigned long long*)len.get(), N, ntr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out->row_ptr.data(), row_ptr, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->d2h_bytes += (N + 1) * 8;
+    const uint64_t nnz = out->row_ptr[N];
+    if (nnz > src.cell_hi - src.cell_lo) return kmdb_set_error("kmdb_sample_candidates: internal error (more candidates than cells)");
+    if (nnz) {
+        DEV_ALLOC(col, nnz);
+        DEV_ALLOC(val, nnz);
+        if (sr_segments_launch<SR_EMIT>(st, src, q, 0u, n_segs, nullptr, nullptr, thr, nullptr, seg_ptr, col, val, nullptr)) return 1;
+        ++out->passes;
+    }
+    HIP_TRY(hipEventRecord(e1, st));
+    if (nnz) {
+        out->col.resize(nnz); out->val.resize(nnz);
+        HIP_TRY(hipMemcpyAsync(out->col.data(), col, nnz * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out->val.data(), val, nnz * 4, hipMemcpyDeviceToHost, st));
+        out->d2h_bytes += nnz * 8;
+        if (!only_rows) {
+            unsigned long long h_ntr = 0;
+            HIP_TRY(hipMemcpyAsync(&h_ntr, ntr, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            out->rows_truncated = h_ntr;
+            out->d2h_bytes += 8;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    out->select_ms = ms;
+    return 0;
+}
+
 // the passes over one source of cells: N slots (out->row_ptr is sized and zeroed), `tiles` workgroups per pass
 template <class Cells>
 int sr_run(hipStream_t st, const Cells& src, const SrJob& q, uint64_t N, uint64_t tiles, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
@@ -363,18 +565,26 @@ int sr_run(hipStream_t st, const Cells& src, const SrJob& q, uint64_t N, uint64_
 }  // namespace
 
 int kmdb_sample_candidates(hipStream_t st, const kmdb_sample_job& j, const uint32_t* only_rows, size_t n_only, kmdb_sample_result* out) {
-    const bool rect = j.rect;
-    const uint64_t N = rect ? j.nr + j.nc : j.N;
+    const bool rect = j.rect, rows = j.query_rows;
+    // (query rows: the slots are the rows that meet the range)
+    const uint64_t q_lo = rows && j.cell_hi > j.cell_lo && j.nc ? j.cell_lo / j.nc : 0;
+    const uint64_t N = rows ? (j.cell_hi > j.cell_lo && j.nc ? (j.cell_hi - 1) / j.nc + 1 - q_lo : 0) : rect ? j.nr + j.nc : j.N;
     out->row_ptr.assign(N + 1, 0);
     out->col.clear(); out->val.clear();
     out->rows_truncated = 0; out->d2h_bytes = 0; out->select_ms = 0; out->passes = 0;
-    if (rect ? (j.nr == 0 || j.nc == 0) : (N < 2 || j.cell_hi <= j.cell_lo)) return 0;
+    if (rows ? N == 0 : rect ? (j.nr == 0 || j.nc == 0) : (N < 2 || j.cell_hi <= j.cell_lo)) return 0;
     if (N + 1 >= (1ull << 31)) return kmdb_set_error("kmdb_sample_candidates: too many samples");
     SrJob q{};
     q.touched = j.touched;
     q.f.n = (int)j.n_bounds; q.f.counts = j.counts_dev;
     for (size_t i = 0; i < j.n_bounds; ++i) { q.f.kind[i] = j.bound_kind[i]; q.f.lo[i] = j.bound_lo[i]; q.f.hi[i] = j.bound_hi[i]; }
     q.kind = j.kind; q.flip = j.flip; q.count = j.count;
+    if (rows) {
+        if (j.nc >= (1ull << 32)) return kmdb_set_error("kmdb_sample_candidates: too many samples");
+        const uint32_t nseg = (uint32_t)((j.nc + N2S_SEG - 1) / N2S_SEG);
+        const RowSegs src{j.cells, (uint32_t)j.nc, nseg, q_lo, j.cell_lo, j.cell_hi, j.counts_dev, j.col_counts_dev};
+        return sr_run_rows(st, src, q, N, only_rows, n_only, out);
+    }
     if (rect) {
         if (j.nr >= (1ull << 32) || j.nc >= (1ull << 32)) return kmdb_set_error("kmdb_sample_candidates: too many samples");
         const uint64_t nbr = (j.nr + SR_W - 1) / SR_W, nbc = (j.nc + SR_W - 1) / SR_W, tiles = nbr * nbc;

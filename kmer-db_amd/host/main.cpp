@@ -1300,15 +1300,22 @@ void new2all_queries(const std::vector<std::string>& entries, const QuerySource&
 // ---- new2all (console_new2all.cpp:12-174) ---------------------------------------------------------
 int run_new2all(std::vector<std::string>& args, Common& c) {
     if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
+    const bool sample_rows = std::find(args.begin(), args.end(), "-sample-rows") != args.end();
     const std::vector<std::string> measures = take_distance_measures(args);
+    if (!measures.empty() && sample_rows) throw std::runtime_error("new2all: -sample-rows does not go with -distance: sampled rows are no rows of the table");
     if (!measures.empty()) return run_new2all_distance(args, c, measures);
+    // -sample-rows <criterion>:<count>: a search — every query keeps its `count` best database samples (the rule of sampler.h:44-67 on the sparse
+    // row; the database samples collect nothing).  The output is always the sparse form.
+    c.sampler.parse(args);
+    if (sample_rows && !c.sampler.best)
+        throw std::runtime_error("new2all: -sample-rows needs <criterion>:<count>: the random strategy (a count alone) has no meaning for a search");
     // -from-minhash: every list entry names <entry>.minhash; its words go to the k-mer entries AS STORED — the database's filter is not applied
     // again (MihashedInputFile::load, minhashed_input_file.h:88-105)
     const bool from_minhash = take_switch(args, "-from-minhash");
     const bool multi = take_switch(args, "-multisample-fasta");
     if (multi && from_minhash) throw usage_error("new2all");
     const bool host_extract = take_switch(args, "-host-extract");   // k-mer extraction on the host instead of the device
-    c.sparse = take_switch(args, "-sparse");
+    c.sparse = take_switch(args, "-sparse") || c.sampler.on();
     if (c.sparse) c.filters.parse(args);
     if (args.size() != 3) throw usage_error("new2all");
     std::cerr << "Set of new samples  (from " << (from_minhash ? "minhashed k-mers" : "genomes") << ") versus entire database comparison" << std::endl;
@@ -1348,7 +1355,11 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     std::vector<Query> batch;
     // -sparse: the rows are compacted and the -min / -max bounds applied on the device (kmdb_new2all_batch*_sparse_filtered: one2all_sp + the row's
     // CombinedFilter, console_new2all.cpp:76-78, 130-148); KMDB_N2A_DENSE_ROWS=1 keeps the dense rows and the host's filter (A/B, same bytes)
-    const bool sparse_on_device = c.sparse && !std::getenv("KMDB_N2A_DENSE_ROWS");
+    // -sample-rows: the candidates of every query are selected on the device and decided by the library (kmdb_new2all_batch*_sampled);
+    // KMDB_N2A_HOST_SAMPLER=1 takes the filtered sparse rows to the host's RowSampler instead (A/B, same bytes)
+    const bool sampled_on_device = c.sampler.on() && !std::getenv("KMDB_N2A_HOST_SAMPLER");
+    const uint32_t sample_cap = (uint32_t)std::min<size_t>(c.sampler.cap, 0xFFFFFFFFu);
+    const bool sparse_on_device = c.sparse && (c.sampler.on() || !std::getenv("KMDB_N2A_DENSE_ROWS"));
     const bool verbose = std::getenv("KMDB_VERBOSE") != nullptr;
     std::vector<kmdb_cell_filter> fl;
     std::vector<uint32_t> sample_counts(n);
@@ -1370,7 +1381,15 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
         struct Rows { kmdb_sparse_rows r{}; ~Rows() { kmdb_sparse_free(&r); } } sp[2];
         std::vector<std::pair<int, size_t>> where(batch.size());
         kmdb_new2all_sparse_stats tot{};
+        kmdb_sample_stats stot{};
         auto account = [&]() {
+            if (sampled_on_device) {
+                kmdb_sample_stats st{};
+                if (db.node ? kmdb_node_new2all_sample_stats_get(db.node, &st) : kmdb_new2all_sample_stats_get(db.d, &st)) return;
+                stot.candidates += st.candidates; stot.rows_truncated += st.rows_truncated; stot.rows_refetched += st.rows_refetched;
+                stot.d2h_bytes += st.d2h_bytes; stot.select_ms += st.select_ms;
+                return;
+            }
             kmdb_new2all_sparse_stats st{};
             if (db.node ? kmdb_node_new2all_sparse_stats_get(db.node, &st) : kmdb_new2all_sparse_stats_get(db.d, &st)) return;
             tot.cells += st.cells; tot.nnz_device += st.nnz_device; tot.nnz += st.nnz; tot.d2h_bytes += st.d2h_bytes; tot.compact_ms += st.compact_ms;
@@ -1380,7 +1399,15 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             std::vector<size_t> kc(by_kmers.size());
             for (size_t t = 0; t < by_kmers.size(); ++t) { ptrs[t] = batch[by_kmers[t]].kmers.data(); kc[t] = batch[by_kmers[t]].kmers.size(); }
             if (sparse_on_device) {
-                if (db.node) check(kmdb_node_new2all_batch_sparse_filtered(db.node, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(), -1, &sp[0].r, nullptr));
+                if (sampled_on_device) {
+                    if (db.node)
+                        check(kmdb_node_new2all_batch_sampled(db.node, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(),
+                                                              c.sampler.criterion_id, sample_cap, &sp[0].r, nullptr));
+                    else
+                        check(kmdb_new2all_batch_sampled(db.d, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(),
+                                                         c.sampler.criterion_id, sample_cap, &sp[0].r, &o));
+                }
+                else if (db.node) check(kmdb_node_new2all_batch_sparse_filtered(db.node, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(), -1, &sp[0].r, nullptr));
                 else check(kmdb_new2all_batch_sparse_filtered(db.d, ptrs.data(), kc.data(), by_kmers.size(), fl.data(), fl.size(), sample_counts.data(), -1, &sp[0].r, &o));
                 account();
                 for (size_t t = 0; t < by_kmers.size(); ++t) { cnts[by_kmers[t]] = kc[t]; where[by_kmers[t]] = {0, t}; }
@@ -1400,7 +1427,16 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             std::vector<uint64_t> uniq(by_text.size());
             for (size_t t = 0; t < by_text.size(); ++t) { ptrs[t] = batch[by_text[t]].text.data(); lens[t] = batch[by_text[t]].text.size(); }
             if (sparse_on_device) {
-                if (db.node) check(kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(), sample_counts.data(), -1, &sp[1].r, uniq.data(), nullptr));
+                if (sampled_on_device) {
+                    if (db.node)
+                        check(kmdb_node_new2all_batch_seq_alphabet_sampled(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(),
+                                                                           fl.size(), sample_counts.data(), c.sampler.criterion_id, sample_cap, &sp[1].r, uniq.data(),
+                                                                           nullptr));
+                    else
+                        check(kmdb_new2all_batch_seq_alphabet_sampled(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(),
+                                                                      sample_counts.data(), c.sampler.criterion_id, sample_cap, &sp[1].r, uniq.data(), &o));
+                }
+                else if (db.node) check(kmdb_node_new2all_batch_seq_alphabet_sparse_filtered(db.node, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(), sample_counts.data(), -1, &sp[1].r, uniq.data(), nullptr));
                 else check(kmdb_new2all_batch_seq_alphabet_sparse_filtered(db.d, ptrs.data(), lens.data(), by_text.size(), fraction, fstart, alphabet, fl.data(), fl.size(), sample_counts.data(), -1, &sp[1].r, uniq.data(), &o));
                 account();
                 for (size_t t = 0; t < by_text.size(); ++t) { cnts[by_text[t]] = (size_t)uniq[t]; where[by_text[t]] = {1, t}; }
@@ -1414,6 +1450,11 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
             }
             }
         }
+        if (sampled_on_device && verbose)
+            std::cerr << "[kmdb] new2all: sampled batch of " << batch.size() << " queries: " << stot.candidates << " candidates, " << stot.rows_truncated
+                      << " rows truncated, " << stot.rows_refetched << " fetched again, select " << stot.select_ms << " ms, " << stot.d2h_bytes
+                      << " bytes to the host" << std::endl;
+        else
         if (sparse_on_device && verbose)
             std::cerr << "[kmdb] new2all: sparse batch of " << batch.size() << " queries: " << tot.cells << " cells, " << tot.nnz_device << " left the device, "
                       << tot.nnz << " kept, compaction " << tot.compact_ms << " ms, " << tot.d2h_bytes << " bytes to the host" << std::endl;
@@ -1427,6 +1468,12 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
                 cols.clear(); vals.clear();
                 for (uint64_t e = r.row_ptr[where[q].second]; e < r.row_ptr[where[q].second + 1]; ++e)
                     if (c.filters.pass(r.val[e], (uint32_t)cnts[q], sample_counts[r.col[e]], (int)k)) { cols.push_back(r.col[e]); vals.push_back(r.val[e]); }
+                if (c.sampler.on() && !sampled_on_device) {
+                    // the host's sampler on the filtered row: the query's row alone collects (a = the query's count, b = the sample's)
+                    c.sampler.init(1);
+                    for (size_t e = 0; e < cols.size(); ++e) c.sampler.add(0, cols[e], vals[e], c.sampler.score(vals[e], (uint32_t)cnts[q], sample_counts[cols[e]], (int)k));
+                    c.sampler.finish_row(0, cols, vals);
+                }
                 len = kmdbh_format_sparse_row(batch[q].name.c_str(), cnts[q], cols.data(), vals.data(), cols.size(), row.data());
             } else if (c.sparse) {
                 const uint32_t* r = out.data() + q * n;
@@ -2485,6 +2532,10 @@ void usage() {
                  "new2all / one2all: -gpus <N>     the database in N query shards over the node's GPUs (from -gpu on): a shard holds the tree and the\n"
                  "                                  hashtable slots of its own prefix buckets; the rows of the shards are summed by one RCCL reduce-scatter\n"
                  "                   -from-minhash the samples are <sample>.minhash files (written by the minhash mode): their k-mers are used as stored\n"
+                 "new2all: -sample-rows <criterion>:<count>  a search: every query keeps its <count> best database samples by <criterion> among the cells\n"
+                 "                                  that pass -min / -max (sparse output; ties towards the smaller sample id), selected on the GPU;\n"
+                 "                                  KMDB_N2A_HOST_SAMPLER=1 keeps the sampler on the host (same bytes).  With -gpus <N> every GPU selects\n"
+                 "                                  on its share of the rows.  Refused with -distance and without a criterion.\n"
                  "minhash: <samples> is a list of FASTA files (or one FASTA file); <sample>.minhash = its k-mers that pass the filter (-f, default 0.01),\n"
                  "                   sorted and unique, extracted on the GPU; -host-extract extracts them on the host and needs no GPU\n"
                  "build: the database is grown on the GPU from the samples in input order and written in the reference's format; -from-minhash takes\n"
