@@ -67,6 +67,10 @@ extern "C" {
  * the GPUs of a node kmdb_node_new2all_batch_sampled, kmdb_node_new2all_batch_seq_alphabet_sampled, kmdb_node_new2all_sample_stats_get): eight
  * more entry points, no struct changed, the version stays 8. */
 #define KMDB_HAS_NEW2ALL_SAMPLED 1
+/* And long samples in the minhash extractor: a sample beyond a threshold is extracted in sections whose sorted unique lists are joined on the
+ * device by a merge-union of two ascending arrays (kmdb_sorted_union_device, kmdb_sorted_union_geometry, kmdb_minhash_long_stats_get): three
+ * more entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_LONG_SAMPLES 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -717,8 +721,12 @@ typedef struct kmdb_kmer_lists {
  * seqs[s]: the text of sample s, its records joined by '\n' (the form kmdb_new2all_batch_seq_alphabet takes); '\n' and every byte outside the
  * alphabet end a window.  The device (opts->device) and the stream (opts->stream, NULL: the default stream) come from opts; opts may be NULL
  * (device 0).  The words are filtered BEFORE they are stored (count, scan, write), so device memory beyond the text grows with what is kept.
- * A batch is cut into pieces at sample boundaries (KMDB_MINHASH_BASES_PER_PIECE bases, default 2^29).  Refused: an unknown alphabet, a k the
- * alphabet cannot hold (alphabet.h:37), a single sample of 2^31 - 2 bases or more (extract it on the host). */
+ * A batch is cut into pieces at sample boundaries (KMDB_MINHASH_BASES_PER_PIECE bases, default 2^29); a sample longer than that goes alone, up
+ * to KMDB_MINHASH_MAX_SAMPLE_BASES bytes of text (default 2^30; both are read at every call).  A longer sample — of any length, 2^31 bases and
+ * beyond — is extracted in consecutive sections of at most the piece budget, cut wherever the budget falls: a section owns the k-mers whose last
+ * symbol lies in it and is shown the symbols in front of it; its sorted unique list stays on the device and is joined into the sample's
+ * running list by kmdb_sorted_union_device's kernels, so device memory is bounded by one section's scratch beside the sample's own list.
+ * The words are those of the sample extracted whole.  Refused: an unknown alphabet, a k the alphabet cannot hold (alphabet.h:37). */
 int  kmdb_minhash_batch_seq_alphabet(const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length,
                                      double fraction, double start_fraction, int32_t alphabet, kmdb_kmer_lists* out, const kmdb_opts* opts);
 void kmdb_kmer_lists_free(kmdb_kmer_lists* lists);
@@ -738,7 +746,26 @@ typedef struct kmdb_minhash_stats {   /* the LAST kmdb_minhash_batch_seq_alphabe
     double   sort_ms;              /* the two radix sorts */
     double   unique_ms;            /* head flags, scan, compaction, the lists to the host */
 } kmdb_minhash_stats;
-int  kmdb_minhash_stats_get(kmdb_minhash_stats* out);
+int  kmdb_minhash_stats_get(kmdb_minhash_stats* out);   /* (a section of a long sample counts as a piece; `unique` counts a long sample's final list) */
+typedef struct kmdb_minhash_long_stats {   /* the long samples of the same call (all zero when it had none) */
+    uint64_t long_samples;         /* samples extracted in sections */
+    uint64_t sections;             /* their sections */
+    uint64_t union_words_in;       /* words that went into the merge-unions (both sides, summed over the unions) */
+    uint64_t union_words_out;      /* words they wrote */
+    uint64_t union_bytes;          /* device memory traffic of the unions by construction: both inputs read twice (count, write), the union written once */
+    uint64_t peak_bytes;           /* most device memory held at once: the running list + a section's scratch, or + a section's list, the union and its tables */
+    double   union_ms;             /* HIP events around the unions */
+} kmdb_minhash_long_stats;
+int  kmdb_minhash_long_stats_get(kmdb_minhash_long_stats* out);
+/* out_dev[0 .. *n_out) = the union of a_dev[0 .. na) and b_dev[0 .. nb), two STRICTLY ascending arrays of 64-bit words in device memory (compared
+ * unsigned), strictly ascending: a merge — merge-path partition into tiles, per-tile counts, a 64-bit scan, a write pass — not a sort, with every
+ * index 64 bits wide.  out_dev must not overlap the inputs.  The device and the stream come from opts (NULL: device 0, the default stream); the
+ * call returns when the union is written.  Refused under the entry's name: out_cap < na + nb (whatever the arrays have in common), a null array
+ * with a size that is not 0.  Arrays that do not ascend give an unspecified order of words and never a fault: every index is clamped to its array. */
+int  kmdb_sorted_union_device(const void* a_dev, uint64_t na, const void* b_dev, uint64_t nb, void* out_dev, uint64_t out_cap, uint64_t* n_out,
+                              const kmdb_opts* opts);
+/* The union's geometry: a thread merges *words_per_thread words of the merged order, a workgroup a tile of *words_per_tile (tests place their edges by these). */
+void kmdb_sorted_union_geometry(uint32_t* words_per_thread, uint32_t* words_per_tile);
 /* Replaces MihashedInputFile::store (minhashed_input_file.h:109-118, call site console_minhash.cpp:47), byte for byte: u32 0xfedcba98, u64 count,
  * count x u64 words, u32 k, f64 fraction; little-endian, no padding.  `path` is the full file name: the caller appends ".minhash" (no GPU). */
 int  kmdbh_minhash_store(const char* path, const uint64_t* kmers, size_t count, uint32_t kmer_length, double fraction);
@@ -816,7 +843,7 @@ int  kmdb_build_seed_stats_get(const kmdb_builder* b, kmdb_build_seed_stats* out
 int  kmdb_build_add_kmers(kmdb_builder* b, const char* const* names, const uint64_t* const* kmers, const size_t* counts, size_t n_samples);
 /* The same from text (console_build.cpp:111 with the loader in front of it, genome_input_file.h): seqs[s] = the sample's records joined by '\n',
  * the form kmdb_minhash_batch_seq_alphabet takes.  Extracted, filtered with the builder's window, sorted and made unique on the device with
- * that entry's own kernels; the lists never visit the host. */
+ * that entry's own kernels — a long sample in sections, as there; the lists never visit the host.  A sample of 2^31 k-mers or more is refused. */
 int  kmdb_build_add_seq_alphabet(kmdb_builder* b, const char* const* names, const char* const* seqs, const size_t* seq_lens, size_t n_samples);
 /* Replaces what PrefixKmerDb::serialize reads out of the live object (console_build.cpp:149; prefix_kmer_db.cpp:438-574): gamma streams, tables,
  * everything copied into a kmdbh_db — free it with kmdbh_db_free; upload it (kmdb_db_upload(kmdbh_db_view(h), ...)) or store it.  The

@@ -32,10 +32,13 @@ from .capi import (  # noqa: F401
     minhash_batch,
     minhash_geometry,
     minhash_load,
+    minhash_long_stats,
     minhash_stats,
     minhash_store,
     query_rows_select,
     range_plan,
     sample_rows_select,
     sort_unique,
+    sorted_union_device,
+    sorted_union_geometry,
 )

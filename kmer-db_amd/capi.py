@@ -89,6 +89,11 @@ class _MinhashStats(C.Structure):
                 ("unique_ms", C.c_double)]
 
 
+class _MinhashLongStats(C.Structure):
+    _fields_ = [("long_samples", C.c_uint64), ("sections", C.c_uint64), ("union_words_in", C.c_uint64), ("union_words_out", C.c_uint64),
+                ("union_bytes", C.c_uint64), ("peak_bytes", C.c_uint64), ("union_ms", C.c_double)]
+
+
 class _BuildStats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("kmers_added", C.c_uint64), ("distinct_kmers", C.c_uint64), ("patterns", C.c_uint64), ("events", C.c_uint64),
                 ("peak_device_bytes", C.c_uint64), ("merge_ms", C.c_double), ("lookup_ms", C.c_double), ("sort_ms", C.c_double), ("group_ms", C.c_double),
@@ -155,6 +160,7 @@ EXPORTS = [
     "kmdb_new2all_batch_sparse_filtered", "kmdb_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_new2all_rows_sparse_device", "kmdb_new2all_sparse_stats_get",
     "kmdb_node_new2all_batch_sparse_filtered", "kmdb_node_new2all_batch_seq_alphabet_sparse_filtered", "kmdb_node_new2all_sparse_stats_get",
     "kmdb_minhash_batch_seq_alphabet", "kmdb_kmer_lists_free", "kmdb_minhash_geometry", "kmdb_minhash_stats_get", "kmdbh_minhash_store", "kmdbh_minhash_load", "kmdbh_minhash_free",
+    "kmdb_minhash_long_stats_get", "kmdb_sorted_union_device", "kmdb_sorted_union_geometry",
     "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
     "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
     "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
@@ -303,6 +309,10 @@ def lib():
     L.kmdb_minhash_geometry.restype = None
     L.kmdb_minhash_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.kmdb_minhash_stats_get.argtypes = [C.POINTER(_MinhashStats)]
+    L.kmdb_minhash_long_stats_get.argtypes = [C.POINTER(_MinhashLongStats)]
+    L.kmdb_sorted_union_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+    L.kmdb_sorted_union_geometry.restype = None
+    L.kmdb_sorted_union_geometry.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.kmdbh_minhash_store.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_double]
     L.kmdbh_minhash_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     L.kmdbh_minhash_free.restype = None
@@ -546,6 +556,26 @@ def _text_queries(seqs):
     bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
     nq = len(bs)
     return bs, (C.c_char_p * max(nq, 1))(*bs), (C.c_size_t * max(nq, 1))(*[len(b) for b in bs]), nq
+
+
+def _sample_texts(seqs):
+    """the texts of minhash_batch / Builder.add_seqs -> (keepalive, pointer array, length array, n).  bytes are passed as they are; a bytearray,
+    a memoryview or a uint8 array — a text of gigabytes — is passed by its address, without a copy"""
+    keep, ptrs, lens = [], [], []
+    for s in seqs:
+        if isinstance(s, str):
+            s = s.encode()
+        if isinstance(s, bytes):
+            keep.append(s)
+            ptrs.append(C.cast(C.c_char_p(s), C.c_void_p).value or 0)
+            lens.append(len(s))
+        else:
+            a = np.frombuffer(s, np.uint8) if not isinstance(s, np.ndarray) else np.ascontiguousarray(s).view(np.uint8).reshape(-1)
+            keep.append((s, a))
+            ptrs.append(a.ctypes.data if a.size else 0)
+            lens.append(a.size)
+    n = len(keep)
+    return keep, (C.c_void_p * max(n, 1))(*ptrs), (C.c_size_t * max(n, 1))(*lens), n
 
 
 def _rows_out(raw):
@@ -1177,7 +1207,7 @@ def minhash_batch(seqs, k, alphabet="nt", fraction=1.0, start_fraction=0.0, devi
     """kmdb_minhash_batch_seq_alphabet: the sorted unique k-mer words of every sample (its records joined by '\n'), extracted and filtered on the
     device — a list of uint64 arrays.  alphabet = index into ALPHABETS or its name."""
     a = ALPHABETS.index(alphabet) if isinstance(alphabet, str) else int(alphabet)
-    keep, ptrs, lens, n = _text_queries(seqs)
+    keep, ptrs, lens, n = _sample_texts(seqs)
     out = _KmerLists()
     o = _opts(device, stream=stream)
     _check(lib().kmdb_minhash_batch_seq_alphabet(ptrs, lens, n, int(k), float(fraction), float(start_fraction), a, C.byref(out), C.byref(o)))
@@ -1196,6 +1226,30 @@ def minhash_stats():
     st = _MinhashStats()
     _check(lib().kmdb_minhash_stats_get(C.byref(st)))
     return {f: getattr(st, f) for f, _ in _MinhashStats._fields_}
+
+
+def minhash_long_stats():
+    """kmdb_minhash_long_stats_get: the long samples of the last minhash_batch call of this thread as a dict (samples cut into sections, their
+    sections, words into and out of the merge-unions, the unions' ms from HIP events and bytes, peak device bytes)"""
+    st = _MinhashLongStats()
+    _check(lib().kmdb_minhash_long_stats_get(C.byref(st)))
+    return {f: getattr(st, f) for f, _ in _MinhashLongStats._fields_}
+
+
+def sorted_union_geometry():
+    """kmdb_sorted_union_geometry: (merged words per thread, merged words per tile) of the merge-union"""
+    r, t = C.c_uint32(), C.c_uint32()
+    lib().kmdb_sorted_union_geometry(C.byref(r), C.byref(t))
+    return int(r.value), int(t.value)
+
+
+def sorted_union_device(a_ptr, na, b_ptr, nb, out_ptr, cap, device=0, stream=None):
+    """kmdb_sorted_union_device: the union of two strictly ascending uint64 arrays in device memory (addresses, e.g. a torch tensor's
+    .data_ptr(), or None) written to out_ptr (room for `cap` >= na + nb words) -> the number of words written"""
+    n = C.c_uint64()
+    o = _opts(device, stream=stream)
+    _check(lib().kmdb_sorted_union_device(C.c_void_p(a_ptr), int(na), C.c_void_p(b_ptr), int(nb), C.c_void_p(out_ptr), int(cap), C.byref(n), C.byref(o)))
+    return int(n.value)
 
 
 def minhash_store(path, kmers, k, fraction):
@@ -1255,7 +1309,7 @@ class Builder:
     def add_seqs(self, names, seqs):
         """texts, records joined by '\n', extracted on the device with the builder's k / fraction / alphabet (kmdb_build_add_seq_alphabet)"""
         keep_n, nptr = self._names(names)
-        keep, ptrs, lens, n = _text_queries(seqs)
+        keep, ptrs, lens, n = _sample_texts(seqs)
         assert n == len(keep_n)
         _check(lib().kmdb_build_add_seq_alphabet(self._b, nptr, ptrs, lens, n))
 

@@ -44,6 +44,11 @@ struct kmdb_opts;
 int kmdb_minhash_device_lists(const char* who, const char* const* seqs, const size_t* seq_lens, size_t n_samples, uint32_t kmer_length, double fraction,
                               double start_fraction, int32_t alphabet, const kmdb_opts* opts, const kmdb_device_lists_sink& sink);
 
+// ---- sorted_union.hip: what kmdb_sorted_union_device does once its arguments are checked and the device is set — out (room for na + nb words)
+// = a ∪ b, *n_out its length; returns after the last kernel has ended.  *scratch_bytes (may be null): device bytes of the call's own tables.
+int kmdb_sorted_union_on_stream(const char* who, const uint64_t* a, uint64_t na, const uint64_t* b, uint64_t nb, uint64_t* out, uint64_t* n_out, void* stream,
+                                uint64_t* scratch_bytes);
+
 // ---- host_shards.cpp: the prefix shards of one database, planned on the host in ONE pass over its hashtables and ONE sweep over its
 // tree, for all shards at once (bucket = kmer >> 32, reference src/types.h:25-27; items src/hashmap_lp.h:71-78).
 // Shard s owns the k-mers of the buckets b with b % n_shards == s.  w[s][p] = k-mers of pattern p in shard s; a node is kept by shard s

@@ -182,15 +182,23 @@ __global__ void mh_sample_offsets_kernel(const uint32_t* __restrict__ sid, const
 
 
 thread_local kmdb_minhash_stats g_stats;
+thread_local kmdb_minhash_long_stats g_long;
 
 }  // namespace
 
-// bases per piece (one longer sample still goes alone).  At fraction 1 the device holds about 42 bytes per base, and the kept
-// words of a piece — at most its bases — stay below 2^31, the size rocPRIM's sorts are given as an int here.
+// bases per piece (one longer sample still goes alone, up to mh_max_sample()).  At fraction 1 the device holds about 42 bytes per base
+// (DESIGN 4), and the kept words of a piece — at most its bases — stay below 2^31, the size rocPRIM's sorts are given as an int here.
 static uint64_t mh_budget() {
     if (const char* e = getenv("KMDB_MINHASH_BASES_PER_PIECE")) return std::max<uint64_t>(1, strtoull(e, nullptr, 10));
     return 512ull << 20;
 }
+// a sample with more bytes of text than this is extracted in sections of at most the budget (mh_long_sample)
+static uint64_t mh_max_sample() {
+    if (const char* e = getenv("KMDB_MINHASH_MAX_SAMPLE_BASES")) return std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    return 1ull << 30;
+}
+// the most a piece can hold: its text and the '\n' behind it stay below the 2^31 - 2 positions the 32-bit counts of a piece are good for
+constexpr uint64_t MH_PIECE_LIMIT = (1ull << 31) - 2;
 
 extern "C" void kmdb_minhash_geometry(uint32_t* positions_per_thread, uint32_t* positions_per_tile) {
     if (positions_per_thread) *positions_per_thread = MH_R;
@@ -210,10 +218,19 @@ extern "C" int kmdb_minhash_stats_get(kmdb_minhash_stats* out) {
     return 0;
 }
 
+extern "C" int kmdb_minhash_long_stats_get(kmdb_minhash_long_stats* out) {
+    if (!out) return kmdb_set_error("kmdb_minhash_long_stats_get: null argument");
+    *out = g_long;
+    return 0;
+}
+
 // one piece: the samples [0, n) of the arguments; their unique words are appended to `kmers` (`total` words so far) and off[s + 1] is set
-// (with a sink the words stay on the device: the sink reads them there and nothing of the piece's lists is copied to the host)
+// (with a sink the words stay on the device: the sink reads them there and nothing of the piece's lists is copied to the host).
+// A section of a long sample is a piece of one sample (n = 1) with `section` set: the `front_len` <= MH_PAD bytes of the sample in front of
+// it go into the pad, so that the warm-up of its first runs sees them; its list goes to section->list, not to the host, the sink or `off`.
+struct MhSection { const char* front; size_t front_len; DevBuf<void> list; uint64_t count = 0, scratch = 0; };
 static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, const MhParams& proto, const int8_t* d_map, hipStream_t st,
-                   uint64_t** kmers, uint64_t* total, uint64_t* off, const kmdb_device_lists_sink* sink) {
+                   uint64_t** kmers, uint64_t* total, uint64_t* off, const kmdb_device_lists_sink* sink, MhSection* section = nullptr) {
     std::vector<uint64_t> soff(n + 1, 0);
     for (size_t s = 0; s < n; ++s) soff[s + 1] = soff[s] + seq_lens[s] + 1;        // (the '\n' behind every sample)
     const uint64_t L = soff[n];
@@ -230,6 +247,8 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
     DEV_ALLOC_BYTES(d_off, (n_tiles + 1) * 4); scratch += d_off.bytes();
     DEV_ALLOC_BYTES(d_uoff, (n + 1) * 8); scratch += d_uoff.bytes();
     HIP_TRY(hipMemsetAsync(d_text.get(), '\n', text_bytes, st));
+    if (section && section->front_len)             // (front_len <= MH_PAD: the bytes end where position 0 begins)
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_text.get()) + MH_PAD - section->front_len, section->front, section->front_len, hipMemcpyHostToDevice, st));
     for (size_t s = 0; s < n; ++s)
         if (seq_lens[s]) HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_text.get()) + MH_PAD + soff[s], seqs[s], seq_lens[s], hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_soff.get(), soff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
@@ -292,7 +311,7 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
         hipLaunchKernelGGL(mh_compact_kernel, dim3(blocks), dim3(256), 0, st, kA, static_cast<uint32_t*>(d_head.get()), static_cast<uint32_t*>(d_hscan.get()), kept, static_cast<uint64_t*>(d_uniq.get()));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(uoff.data(), d_uoff.get(), (n + 1) * 8, hipMemcpyDeviceToHost, st));
-        if (!sink) {
+        if (!sink && !section) {
             uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_unique) * 8);
             if (!grown) return kmdb_set_error("kmdb_minhash_batch_seq_alphabet: out of host memory");
             *kmers = grown;
@@ -306,18 +325,82 @@ static int mh_once(const char* const* seqs, const size_t* seq_lens, size_t n, co
     }
     HIP_TRY(hipEventRecord(ev[6], st));
     HIP_TRY(hipEventSynchronize(ev[6]));
-    if (sink) {
+    if (section) {
+        section->list.take(d_uniq);
+        section->count = n_unique;
+        section->scratch = scratch;
+    } else if (sink) {
         // the sorts' double buffers and the flags are done with: the sink's own work gets their memory
         dev_reset(d_kA, d_kB, d_sA, d_sB, d_head, d_hscan, d_text, d_cnt, d_off);
         if (const int rc = (*sink)(static_cast<uint64_t*>(d_uniq.get()), uoff.data(), n, (void*)st)) return rc;
     }
-    for (size_t s = 0; s < n; ++s) off[s + 1] = *total + uoff[s + 1];
-    *total += n_unique;
+    if (!section) {
+        for (size_t s = 0; s < n; ++s) off[s + 1] = *total + uoff[s + 1];
+        *total += n_unique;
+        g_stats.unique += n_unique;
+    }
     float ms[6] = {0, 0, 0, 0, 0, 0};
     for (int i = 0; i < 6; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-    g_stats.pieces += 1; g_stats.bases += L - n; g_stats.kept += kept; g_stats.unique += n_unique;
+    g_stats.pieces += 1; g_stats.bases += L - n; g_stats.kept += kept;
     g_stats.scratch_bytes = std::max<uint64_t>(g_stats.scratch_bytes, scratch);
     g_stats.h2d_ms += ms[0]; g_stats.count_ms += ms[1]; g_stats.scan_ms += ms[2]; g_stats.write_ms += ms[3]; g_stats.sort_ms += ms[4]; g_stats.unique_ms += ms[5];
+    return 0;
+}
+
+// One sample in consecutive sections of at most the budget, cut wherever the budget falls.  A section owns the k-mers whose LAST symbol lies in
+// it — every window of the sample is counted once by its position — and sees the k - 1 symbols in front of its first position in the pad.
+// Its sorted unique list stays on the device and is joined into the sample's running list by the merge-union (sorted_union.hip): the words of
+// the whole sample are counted with 64 bits, those of a section with 32.  After the last section the list goes where a piece's lists go.
+static int mh_long_sample(const char* who, const char* seq, size_t len, const MhParams& proto, const int8_t* d_map, hipStream_t st, uint64_t** kmers,
+                          uint64_t* total, uint64_t* off, const kmdb_device_lists_sink* sink) {
+    const uint64_t step = std::min<uint64_t>(mh_budget(), MH_PIECE_LIMIT - 1);
+    DevBuf<void> d_run;                            // the running list: the union of the sections so far
+    uint64_t n_run = 0;
+    DevEvent ev[2];
+    for (auto& e : ev) if (e.create()) return 1;
+    auto peak = [&](uint64_t bytes) { g_long.peak_bytes = std::max<uint64_t>(g_long.peak_bytes, bytes); };
+    g_long.long_samples += 1;
+    for (uint64_t at = 0; at < len; at += step) {
+        MhSection sec;
+        const size_t sec_len = (size_t)std::min<uint64_t>(step, len - at);
+        const char* text = seq + at;
+        sec.front_len = (size_t)std::min<uint64_t>(MH_PAD, at);
+        sec.front = text - sec.front_len;
+        if (const int rc = mh_once(&text, &sec_len, 1, proto, d_map, st, nullptr, nullptr, nullptr, nullptr, &sec)) return rc;
+        g_long.sections += 1;
+        peak(d_run.bytes() + sec.scratch);
+        if (!n_run) { d_run.take(sec.list); n_run = sec.count; continue; }        // (the first list, or the first that holds a word)
+        if (!sec.count) continue;
+        DevBuf<void> d_join;
+        DEV_ALLOC_BYTES(d_join, (n_run + sec.count) * 8);
+        uint64_t n_join = 0, tables = 0;
+        HIP_TRY(hipEventRecord(ev[0], st));
+        if (const int rc = kmdb_sorted_union_on_stream(who, static_cast<const uint64_t*>(d_run.get()), n_run, static_cast<const uint64_t*>(sec.list.get()), sec.count,
+                                                       static_cast<uint64_t*>(d_join.get()), &n_join, (void*)st, &tables)) return rc;
+        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipEventSynchronize(ev[1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        g_long.union_ms += ms;
+        g_long.union_words_in += n_run + sec.count; g_long.union_words_out += n_join;
+        g_long.union_bytes += (2 * (n_run + sec.count) + n_join) * 8;               // both inputs read by the count pass and by the write pass, the union written
+        peak(d_run.bytes() + sec.list.bytes() + d_join.bytes() + tables);
+        d_run.take(d_join);
+        n_run = n_join;
+    }
+    if (sink) {
+        const uint64_t one[2] = {0, n_run};
+        if (const int rc = (*sink)(static_cast<const uint64_t*>(d_run.get()), one, 1, (void*)st)) return rc;
+    } else {
+        uint64_t* grown = (uint64_t*)realloc(*kmers, std::max<uint64_t>(1, *total + n_run) * 8);
+        if (!grown) return kmdb_set_error(std::string(who) + ": out of host memory");
+        *kmers = grown;
+        if (n_run) HIP_TRY(hipMemcpyAsync(grown + *total, d_run.get(), n_run * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    off[1] = *total + n_run;
+    *total += n_run;
+    g_stats.unique += n_run;
     return 0;
 }
 
@@ -336,9 +419,9 @@ static int mh_batch(const char* who, const char* const* seqs, const size_t* seq_
     if (n_samples >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": too many samples in one batch");
     for (size_t s = 0; s < n_samples; ++s) {
         if (seq_lens[s] && !seqs[s]) return kmdb_set_error(std::string(who) + ": null argument");
-        if (seq_lens[s] >= (1ull << 31) - 2) return kmdb_set_error(std::string(who) + ": a single sample of 2^31 bases or more; extract its k-mers on the host (kmdbh_extract_kmers_alphabet, kmdbh_sort_unique)");
     }
     g_stats = kmdb_minhash_stats{};
+    g_long = kmdb_minhash_long_stats{};
     uint64_t* offsets = (uint64_t*)calloc(n_samples + 1, 8);
     if (!offsets) return kmdb_set_error(std::string(who) + ": out of host memory");
     uint64_t* kmers = nullptr;
@@ -358,12 +441,19 @@ static int mh_batch(const char* who, const char* const* seqs, const size_t* seq_
         DEV_ALLOC_BYTES(d_map, 256);
         HIP_TRY(hipMemcpyAsync(d_map.get(), map, 256, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                                           // (`map` lives on this frame)
-        // samples are independent: cut the batch where the accumulated bases pass the budget
-        const uint64_t budget = mh_budget();
+        // samples are independent: cut the batch where the accumulated bases pass the budget; a long sample is cut itself, the pieces around it
+        // are made as if it were a batch's end
+        const uint64_t budget = mh_budget(), max_sample = mh_max_sample();
+        auto is_long = [&](size_t s) { return seq_lens[s] > max_sample || seq_lens[s] >= MH_PIECE_LIMIT; };
         for (size_t s0 = 0; s0 < n_samples;) {
+            if (is_long(s0)) {
+                if (const int rc = mh_long_sample(who, seqs[s0], seq_lens[s0], p, static_cast<int8_t*>(d_map.get()), st, &kmers, &total, offsets + s0, sink)) return rc;
+                ++s0;
+                continue;
+            }
             size_t s1 = s0;
             uint64_t bases = 0;
-            do { bases += seq_lens[s1] + 1; ++s1; } while (s1 < n_samples && bases + seq_lens[s1] + 1 <= budget && bases + seq_lens[s1] + 1 < (1ull << 31) - 2);
+            do { bases += seq_lens[s1] + 1; ++s1; } while (s1 < n_samples && !is_long(s1) && bases + seq_lens[s1] + 1 <= budget && bases + seq_lens[s1] + 1 < MH_PIECE_LIMIT);
             if (const int rc = mh_once(seqs + s0, seq_lens + s0, s1 - s0, p, static_cast<int8_t*>(d_map.get()), st, &kmers, &total, offsets + s0, sink)) return rc;
             s0 = s1;
         }

@@ -863,12 +863,38 @@ void split_fasta(const std::string& data, std::vector<Record>& recs) {
 
 struct Query {
     std::string name;
-    std::vector<uint64_t> kmers;             // from_kmers: sorted unique k-mers from the host loader
+    std::vector<uint64_t> kmers;             // from_kmers: sorted unique k-mers (the host loader; a long query: the stand-alone device extractor)
     std::string text;                        // else: records joined by '\n' (device-side extraction)
     bool from_kmers = false;
+    std::string error;                       // a device extraction that failed on a reader thread: thrown where the query is handed on
 };
-// the device loader indexes positions with 32 bits: longer genomes go through the host loader
+// the loader inside the new2all call indexes positions with 32 bits: the k-mers of a longer query are extracted by the stand-alone extractor
+// (kmdb_minhash_batch_seq_alphabet: in sections, on the device) and enter as a k-mer list.  KMDB_LONG_QUERY_BASES lowers the threshold (tests).
 constexpr size_t LONG_QUERY_BASES = 1800u << 20;
+// KMDB_VERBOSE: what the last extractor call of this thread did with its long samples
+void report_long_samples(const char* mode) {
+    kmdb_minhash_long_stats ls{};
+    if (!std::getenv("KMDB_VERBOSE") || kmdb_minhash_long_stats_get(&ls) || !ls.long_samples) return;
+    std::cerr << "[kmdb] " << mode << ": " << ls.long_samples << " long samples in " << ls.sections << " sections; unions " << ls.union_words_in << " words in, "
+              << ls.union_words_out << " out, " << ls.union_ms << " ms; peak " << ls.peak_bytes << " device bytes" << std::endl;
+}
+size_t long_query_bases() {
+    if (const char* e = std::getenv("KMDB_LONG_QUERY_BASES")) return (size_t)std::max<unsigned long long>(1, std::strtoull(e, nullptr, 10));
+    return LONG_QUERY_BASES;
+}
+// the sorted unique k-mers of one long query, by the device extractor with the database's own k, window and alphabet
+void extract_long_query(const std::string& text, uint32_t k, int32_t alphabet, double fraction, double fstart, int device, std::vector<uint64_t>& kmers) {
+    static std::mutex one_at_a_time;         // (the reader threads: one long text on the device at a time)
+    std::lock_guard<std::mutex> lock(one_at_a_time);
+    kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = device; o.shard_count = 1;
+    const char* tp = text.data();
+    const size_t tl = text.size();
+    kmdb_kmer_lists lists{};
+    check(kmdb_minhash_batch_seq_alphabet(&tp, &tl, 1, k, fraction, fstart, alphabet, &lists, &o));
+    report_long_samples("long query");
+    struct FreeLists { kmdb_kmer_lists& l; ~FreeLists() { kmdb_kmer_lists_free(&l); } } free_lists{lists};
+    kmers.assign(lists.kmers, lists.kmers + lists.offsets[1]);
+}
 
 std::string basename_of(const std::string& p) {
     size_t s = p.find_last_of('/');
@@ -890,7 +916,7 @@ bool load_minhash(const std::string& entry, std::vector<uint64_t>& kmers, uint32
 
 // ---- minhash (console_minhash.cpp:7-52, params.cpp:674-716): every sample's filtered, sorted, unique k-mers into <sample>.minhash --------
 // The loader + KmerHelper::sortAndUnique run on the device for a batch of samples at a time (kmdb_minhash_batch_seq_alphabet);
-// -host-extract — and a sample beyond the device loader's 32-bit positions — takes kmdbh_extract_kmers_alphabet + kmdbh_sort_unique and
+// a sample of any length goes there (a long one in sections); -host-extract takes kmdbh_extract_kmers_alphabet + kmdbh_sort_unique and
 // never touches a device.  The files are MihashedInputFile::store's, byte for byte (kmdbh_minhash_store).
 int run_minhash(std::vector<std::string>& args, Common& c) {
     if (take_switch(args, "-from-kmers")) throw std::runtime_error(KMC_REFUSAL);
@@ -961,7 +987,7 @@ int run_minhash(std::vector<std::string>& args, Common& c) {
                     split_fasta(data, recs);
                     size_t bytes = 0, total = 0;
                     for (auto& r : recs) { bytes += r.seq.size() + 1; total += r.seq.size(); }
-                    s.on_host = host_extract || bytes >= LONG_QUERY_BASES;
+                    s.on_host = host_extract;
                     if (s.on_host) {
                         s.kmers.resize(total + 1);
                         size_t n = 0;
@@ -979,7 +1005,7 @@ int run_minhash(std::vector<std::string>& args, Common& c) {
         for (int t = 0; t < std::min<int>(nthreads, (int)cnt); ++t) pool.emplace_back(worker);
         for (auto& t : pool) t.join();
         if (failed) throw std::runtime_error("out of memory while reading the samples");
-        // device calls over stretches of the batch of at most BATCH_BASES bases
+        // device calls over stretches of the batch of at most BATCH_BASES bases (a longer sample is a stretch of its own)
         for (size_t i0 = 0; i0 < cnt;) {
             std::vector<size_t> idx;
             size_t bases = 0, i1 = i0;
@@ -991,6 +1017,7 @@ int run_minhash(std::vector<std::string>& args, Common& c) {
                 std::vector<size_t> lens(idx.size());
                 for (size_t t = 0; t < idx.size(); ++t) { ptrs[t] = ss[idx[t]].text.data(); lens[t] = ss[idx[t]].text.size(); }
                 check(kmdb_minhash_batch_seq_alphabet(ptrs.data(), lens.data(), idx.size(), k, fraction, 0.0, alphabet, &lists, &o));
+                report_long_samples("minhash");
             }
             struct FreeLists { kmdb_kmer_lists& l; ~FreeLists() { kmdb_kmer_lists_free(&l); } } free_lists{lists};
             size_t t = 0;
@@ -1129,7 +1156,7 @@ int run_build(std::vector<std::string>& args, Common& c) {
                         s.name = multi ? recs[r0].header : basename_of(f.entry);
                         size_t bytes = 0, total = 0;
                         for (size_t r = r0; r < r1; ++r) { bytes += recs[r].seq.size() + 1; total += recs[r].seq.size(); }
-                        s.on_host = host_extract || bytes >= LONG_QUERY_BASES;
+                        s.on_host = host_extract;
                         if (s.on_host) {
                             s.kmers.resize(total + 1);
                             size_t n = 0;
@@ -1182,6 +1209,7 @@ int run_build(std::vector<std::string>& args, Common& c) {
                 std::vector<size_t> lens(m);
                 for (size_t t = 0; t < m; ++t) { ptrs[t] = ss[i0 + t]->text.data(); lens[t] = ss[i0 + t]->text.size(); }
                 check(kmdb_build_add_seq_alphabet(bld.b, names.data(), ptrs.data(), lens.data(), m));
+                report_long_samples("build");
             }
             added += m;
             i0 = i1;
@@ -1213,6 +1241,7 @@ struct QuerySource {
     int32_t alphabet;
     double fraction, fstart;
     int nthreads;
+    int device;                              // where a long query's k-mers are extracted
 };
 template <class Flush>
 void new2all_queries(const std::vector<std::string>& entries, const QuerySource& s, std::vector<Query>& batch, Flush&& flush) {
@@ -1227,10 +1256,15 @@ void new2all_queries(const std::vector<std::string>& entries, const QuerySource&
         q.name = name;
         size_t bytes = 0;
         for (auto* s : seqs) bytes += s->size() + 1;
-        q.from_kmers = host_extract || bytes >= LONG_QUERY_BASES;
-        if (!q.from_kmers) {
+        const bool long_query = bytes >= long_query_bases();
+        q.from_kmers = host_extract || long_query;
+        if (!host_extract) {
             q.text.reserve(bytes);
             for (auto* s : seqs) { q.text += *s; q.text += '\n'; }
+            if (!long_query) return q;
+            // the same window, k and alphabet as the call's own loader; the query enters as the k-mer list a long query always entered as
+            try { extract_long_query(q.text, k, alphabet, fraction, fstart, s.device, q.kmers); } catch (const std::exception& e) { q.error = e.what(); }
+            std::string().swap(q.text);
             return q;
         }
         size_t total = 0;
@@ -1245,6 +1279,7 @@ void new2all_queries(const std::vector<std::string>& entries, const QuerySource&
 
     const size_t BATCH = 64, BATCH_BASES = 512u << 20;
     auto add = [&](Query&& q) {
+        if (!q.error.empty()) throw std::runtime_error(q.error);
         batch_bases += q.text.size() + q.kmers.size();
         batch.push_back(std::move(q));
         if (batch.size() == BATCH || batch_bases >= BATCH_BASES) { flush(); batch_bases = 0; }
@@ -1374,7 +1409,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
         std::vector<size_t> cnts(batch.size());
         std::vector<uint32_t> out(sparse_on_device ? 1 : batch.size() * n + 1);
         // a query is either sequence text (loader + KmerHelper::unique + one2all on the device, kmdb_new2all_batch_seq) or,
-        // with -host-extract and for genomes beyond the device loader's 2^31 positions, a k-mer list (kmdb_new2all_batch)
+        // with -host-extract and for genomes beyond the call's own loader (2^31 positions; extracted on the device beforehand), a k-mer list (kmdb_new2all_batch)
         std::vector<size_t> by_text, by_kmers;
         for (size_t q = 0; q < batch.size(); ++q) (batch[q].from_kmers ? by_kmers : by_text).push_back(q);
         // sparse rows of the two halves, and where query q's row is: {half, row}
@@ -1491,7 +1526,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
         batch.clear();
     };
 
-    new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads}, batch, flush);
+    new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads, c.device}, batch, flush);
     if (db.node) node_report(db);                                  // (the last batch's call)
     std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl;
     return 0;
@@ -1532,8 +1567,8 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
     } else if (!slurp(args[1], data)) throw std::runtime_error("Cannot open sample file: " + args[1]);
     std::vector<Record> recs;
     split_fasta(data, recs);
-    // loader (kmer_extract.h, filter.h), KmerHelper::sortAndUnique (console_one2all.cpp:64-66) and one2all on the device;
-    // genomes beyond the device loader's 32-bit positions take the host loader
+    // loader (kmer_extract.h, filter.h), KmerHelper::sortAndUnique (console_one2all.cpp:64-66) and one2all on the device; a genome beyond
+    // the call's own loader (32-bit positions) is extracted by the stand-alone extractor first, on the device too, and enters as a k-mer list
     size_t bases = 0;
     for (auto& r : recs) bases += r.seq.size() + 1;
     uint64_t cnt = 0;
@@ -1546,7 +1581,7 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
         if (db.node) check(kmdb_node_new2all_batch(db.node, &kp, &kc, 1, sims.data(), nullptr));
         else check(kmdb_new2all_batch(db.d, &kp, &kc, 1, sims.data(), &o));
         cnt = kc;
-    } else if (bases < LONG_QUERY_BASES) {
+    } else if (bases < long_query_bases()) {
         std::string text;
         text.reserve(bases);
         for (auto& r : recs) { text += r.seq; text += '\n'; }
@@ -1555,11 +1590,12 @@ int run_one2all(std::vector<std::string>& args, Common& c) {
         if (db.node) check(kmdb_node_new2all_batch_seq_alphabet(db.node, &tp, &tl, 1, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), alphabet, sims.data(), &cnt, nullptr));
         else check(kmdb_new2all_batch_seq_alphabet(db.d, &tp, &tl, 1, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), alphabet, sims.data(), &cnt, &o));
     } else {
-        std::vector<uint64_t> kmers(bases + 1);
-        size_t kc = 0;
-        for (auto& r : recs)
-            kc += kmdbh_extract_kmers_alphabet(r.seq.data(), r.seq.size(), k, alphabet, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), kmers.data() + kc);
-        kc = kmdbh_sort_unique(kmers.data(), kc);
+        std::string text;
+        text.reserve(bases);
+        for (auto& r : recs) { text += r.seq; text += '\n'; }
+        std::vector<uint64_t> kmers;
+        extract_long_query(text, k, alphabet, kmdbh_db_fraction(db.h), kmdbh_db_start_fraction(db.h), c.device, kmers);
+        size_t kc = kmers.size();
         const uint64_t* kp = kmers.data();
         if (db.node) check(kmdb_node_new2all_batch(db.node, &kp, &kc, 1, sims.data(), nullptr));
         else check(kmdb_new2all_batch(db.d, &kp, &kc, 1, sims.data(), &o));
@@ -2162,7 +2198,7 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
         batch.clear();
     };
     try {
-        new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads}, batch, flush);
+        new2all_queries(entries, QuerySource{from_minhash, multi, host_extract, k, alphabet, fraction, fstart, nthreads, c.device}, batch, flush);
         open_tables();                                             // (no query at all: the header lines alone, as the two commands write them)
     } catch (...) {
         stop_tables(false);
