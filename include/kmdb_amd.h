@@ -42,6 +42,9 @@ extern "C" {
 /* And the seed of the build mode: a builder that starts from a stored database (kmdb_build_begin_from_db, kmdb_build_seed_stats_get): two more
  * entry points and one struct of their own, the version stays 8. */
 #define KMDB_HAS_BUILD_SEED 1
+/* And the hand-off of a finished builder to the engine in HBM (kmdb_build_finish_device, kmdb_build_handoff_stats_get; kmdbh_db_header_only):
+ * three more entry points, same version number, no struct changed. */
+#define KMDB_HAS_BUILD_HANDOFF 1
 /* And the distance mode on the device: the table of common k-mer counts parsed, measured and formatted in HBM (kmdb_distance_*), and the one
  * definition of a measure's text (kmdbh_format_measure): six more entry points and three structs of their own, the version stays 8. */
 #define KMDB_HAS_DISTANCE 1
@@ -851,6 +854,41 @@ int  kmdb_build_add_seq_alphabet(kmdb_builder* b, const char* const* names, cons
 int  kmdb_build_finish(kmdb_builder* b, kmdbh_db** out);
 void kmdb_build_free(kmdb_builder* b);
 int  kmdb_build_stats_get(const kmdb_builder* b, kmdb_build_stats* out);
+/* The hand-off (KMDB_HAS_BUILD_HANDOFF): kmdb_build_finish followed by kmdb_db_upload(kmdbh_db_view(h), opts, with_hashtables, ...) without the
+ * host in between.  *out_db is, in every respect, the handle that pair returns — that equivalence defines the result, the upload's refusals
+ * with the upload's messages included (2^31 patterns or more, KMDB_MAX_SAMPLES samples or more, unknown bits in opts->flags, its tree and
+ * header checks) — but no pattern field, stream word or table slot visits the host: one kernel narrows the builder's fields, the streams are
+ * re-packed from their word-aligned pid-order places, the tables go device to device.  kmdb_stats.h2d_bytes of the handle is 0, upload_ms is
+ * the time of the layout and the preparation.  opts->device must be the builder's device; another one is refused.  The refusals that need no
+ * device work (flags, counts, device) leave the builder as it was; everything later ends it exactly as kmdb_build_finish does (a later add or
+ * finish is refused, a failure leaves it dead), and kmdb_build_free stays the caller's job.
+ * with_hashtables = 0 and host_image = 0 skips the tables altogether (bucket starts, capacities, insert), and the all2all working set is
+ * prepared as for an all2all upload.  out_host may be NULL.  host_image = 1: *out_host is the image kmdb_build_finish returns (kmdbh_db_store
+ * of it gives the same bytes; the tables are made whatever with_hashtables says).  host_image = 0: *out_host is a HEADER-ONLY image — names,
+ * per-sample k-mer counts, k, fraction, start fraction, alphabet, kmers_count; its view has n_patterns == 0, which no stored database has
+ * (pattern 0 always exists), and kmdbh_db_store and every kmdb_db_upload* refuse it with a message.
+ * The builder's arrays are released as soon as their last reader has run: the unsorted events after the sort, the dictionary before the
+ * layout, the tree and the per-pattern fields after the fields kernel, the tables after their copy, the pid-order stream words after the
+ * re-pack (a full host image keeps all but the dictionary until it is copied). */
+int  kmdb_build_finish_device(kmdb_builder* b, const kmdb_opts* opts, int with_hashtables, int host_image, kmdb_db** out_db, kmdbh_db** out_host);
+typedef struct kmdb_build_handoff_stats {   /* what kmdb_build_finish_device did (zeros before it) */
+    uint64_t patterns, samples;
+    uint64_t peak_device_bytes;    /* most device memory builder and handle held together during the call */
+    uint64_t handle_device_bytes;  /* kmdb_stats.device_bytes of the handle */
+    uint64_t d2h_bytes;            /* bytes of the host image copied back (0 for a header-only image) */
+    uint32_t with_hashtables, host_image;   /* as asked */
+    double   encode_ms;            /* HIP events: events grouped by pattern, gamma streams */
+    double   tables_ms;            /* ... the prefix-bucket hashtables (0 when they were skipped) */
+    double   fields_ms;            /* wall clock: the fields kernel, the tables copied device to device */
+    double   layout_ms;            /* ... DFS pre-order, node arrays, stream re-pack, slices and long nodes */
+    double   prepare_ms;           /* ... the all2all working set (0 with hashtables: made by the first all2all call) */
+    double   copy_back_ms;         /* HIP events: the full host image (0 otherwise) */
+    double   total_ms;             /* wall clock of the call */
+} kmdb_build_handoff_stats;
+int  kmdb_build_handoff_stats_get(const kmdb_builder* b, kmdb_build_handoff_stats* out);
+/* The header-only image of a database, as kmdb_build_finish_device returns it with host_image = 0 (names, counts, k, fractions, alphabet);
+ * free it with kmdbh_db_free.  No GPU. */
+int  kmdbh_db_header_only(const kmdbh_db* db, kmdbh_db** out);
 /* PrefixKmerDb::serialize(file, true) (prefix_kmer_db.cpp:438-574; call site console_build.cpp:149): header fields :449-457, samples, raw tables
  * (hashmap_lp.h:481-528), patterns in blocks of at most 64 MB cut by the reference's own rule (:545-569).  is_parent goes into bytes 32..35 of
  * every pattern header, zeros into bytes 36..39 (the reference leaves those four unwritten: pattern.cpp:35-37).  Any kmdbh_db that holds its

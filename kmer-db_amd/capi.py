@@ -106,6 +106,12 @@ class _BuildSeedStats(C.Structure):
                 ("check_ms", C.c_double)]
 
 
+class _BuildHandoffStats(C.Structure):
+    _fields_ = [("patterns", C.c_uint64), ("samples", C.c_uint64), ("peak_device_bytes", C.c_uint64), ("handle_device_bytes", C.c_uint64),
+                ("d2h_bytes", C.c_uint64), ("with_hashtables", C.c_uint32), ("host_image", C.c_uint32), ("encode_ms", C.c_double), ("tables_ms", C.c_double),
+                ("fields_ms", C.c_double), ("layout_ms", C.c_double), ("prepare_ms", C.c_double), ("copy_back_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class _DistanceOpts(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("measure", C.c_int32), ("kmer_length", C.c_uint32), ("counts", C.c_void_p),
                 ("n", C.c_uint64), ("filters", C.c_void_p), ("n_filters", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
@@ -163,6 +169,7 @@ EXPORTS = [
     "kmdb_minhash_long_stats_get", "kmdb_sorted_union_device", "kmdb_sorted_union_geometry",
     "kmdb_build_begin", "kmdb_build_add_kmers", "kmdb_build_add_seq_alphabet", "kmdb_build_finish", "kmdb_build_free", "kmdb_build_stats_get", "kmdbh_db_store",
     "kmdb_build_begin_from_db", "kmdb_build_seed_stats_get",
+    "kmdb_build_finish_device", "kmdb_build_handoff_stats_get", "kmdbh_db_header_only",
     "kmdb_distance_begin", "kmdb_distance_rows", "kmdb_distance_out_free", "kmdb_distance_free", "kmdb_distance_stats_get", "kmdbh_format_measure",
     "kmdb_distance_take_all2all", "kmdb_distance_take_cells_device", "kmdb_distance_matrix_rows", "kmdb_distance_cells_device",
     "kmdb_distance_take_new2all_batch", "kmdb_distance_take_new2all_batch_seq_alphabet", "kmdb_distance_take_rows_device", "kmdb_distance_query_rows",
@@ -321,6 +328,9 @@ def lib():
     L.kmdb_build_add_kmers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.kmdb_build_add_seq_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.kmdb_build_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.kmdb_build_finish_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.kmdb_build_handoff_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildHandoffStats)]
+    L.kmdbh_db_header_only.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.kmdb_build_free.restype = None
     L.kmdb_build_free.argtypes = [C.c_void_p]
     L.kmdb_build_stats_get.argtypes = [C.c_void_p, C.POINTER(_BuildStats)]
@@ -454,6 +464,12 @@ class HostDB:
             out["bucket_offset"] = arr(v.bucket_offset, int(v.n_buckets) + 1, np.uint64)
             out["slots"] = arr(v.slots, int(out["bucket_offset"][-1]), np.uint64)
         return out
+
+    def header_only(self):
+        """kmdbh_db_header_only: names, counts, k, fractions and alphabet alone — the image Builder.finish_device returns without host_image"""
+        h = C.c_void_p()
+        _check(lib().kmdbh_db_header_only(self._h, C.byref(h)))
+        return HostDB(None, _handle=h)
 
     def store(self, path):
         """kmdbh_db_store: the file PrefixKmerDb::serialize(file, true) writes; the database must hold its tables"""
@@ -635,6 +651,14 @@ class DeviceDB:
                                               C.byref(self._d)))
         self.N = int(view.contents.n_samples)
         self.P = int(view.contents.n_patterns)
+
+    @classmethod
+    def _wrap(cls, handle, device, n_samples, keep=None):
+        """a DeviceDB around a kmdb_db handle made elsewhere (Builder.finish_device); the object owns the handle"""
+        self = cls.__new__(cls)
+        self._keep, self.device, self._d, self.N = keep, device, handle, int(n_samples)
+        self.P = int(self.stats()["n_patterns"])
+        return self
 
     def tri_size(self):
         return self.N * (self.N - 1) // 2 if self.N else 0
@@ -1276,6 +1300,7 @@ class Builder:
     def __init__(self, k, fraction=1.0, start_fraction=0.0, alphabet="nt", device=0, stream=None):
         a = ALPHABETS.index(alphabet) if isinstance(alphabet, str) else int(alphabet)
         self._b = C.c_void_p()
+        self.device = device
         o = _opts(device, stream=stream)
         _check(lib().kmdb_build_begin(int(k), float(fraction), float(start_fraction), a, C.byref(o), C.byref(self._b)))
 
@@ -1285,6 +1310,7 @@ class Builder:
         counts are the database's, new samples are numbered from hostdb.N on"""
         self = cls.__new__(cls)
         self._b = C.c_void_p()
+        self.device = device
         o = _opts(device, stream=stream)
         _check(lib().kmdb_build_begin_from_db(hostdb._h, C.byref(o), C.byref(self._b)))
         return self
@@ -1317,6 +1343,21 @@ class Builder:
         h = C.c_void_p()
         _check(lib().kmdb_build_finish(self._b, C.byref(h)))
         return HostDB(None, _handle=h)
+
+    def finish_device(self, with_hashtables=False, host_image=False, flags=0, device=None):
+        """kmdb_build_finish_device: the database handed to the engine in HBM -> (DeviceDB, HostDB).  The HostDB is the image finish()
+        returns with host_image, else a header-only image (names, counts, k, fractions, alphabet).  device: the builder's (another is refused)"""
+        dev = self.device if device is None else device
+        d, h = C.c_void_p(), C.c_void_p()
+        o = _opts(dev, (0, 1), flags)
+        _check(lib().kmdb_build_finish_device(self._b, C.byref(o), int(bool(with_hashtables)), int(bool(host_image)), C.byref(d), C.byref(h)))
+        host = HostDB(None, _handle=h)
+        return DeviceDB._wrap(d, dev, host.N), host
+
+    def handoff_stats(self):
+        st = _BuildHandoffStats()
+        _check(lib().kmdb_build_handoff_stats_get(self._b, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _BuildHandoffStats._fields_}
 
     def stats(self):
         st = _BuildStats()

@@ -23,6 +23,8 @@
 //                >= 16 that keeps the fill at or below 0.8 (hashmap_lp.h:420-437); home slot and probing as csrc/hash_probe.h reads them;
 //                placement by 64-bit atomic minimum: linear probing with priorities, one table whatever the order of arrival
 //            (e) everything copied into a kmdbh_db
+//   hand-off     kmdb_build_finish_device: (c), (d) only if somebody reads the tables, then the engine's layout straight from these arrays
+//                (kmdb_db_from_device -> kmdb_layout_from_device, layout.hip), (e) only for a full host image
 //   seed     (f) kmdb_build_begin_from_db: the reverse of (c) - (e), a stored database loaded into the state above (bd_seed, further down)
 // Wave-64, 256 threads per block, one element per thread; every kernel checks its own bounds and no kernel uses scratch (the compile's
 // resource remarks are read by tests/test_build.py).
@@ -33,8 +35,11 @@
 #include "hash_probe.h"
 #include "prim.h"
 #include "device_common.h"
+#include "dev_mem.h"
+#include "engine_internal.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -414,7 +419,7 @@ struct BBuf {
     BBuf& operator=(const BBuf&) = delete;
     ~BBuf() { release(); }
     void release() {
-        if (p) { (void)hipFree(p); a->live -= bytes; }
+        if (p) { (void)hipFree(p); a->live -= bytes; if (dev_mem_meter) dev_mem_meter->sub(bytes); }
         p = nullptr; bytes = 0;
     }
     void swap(BBuf& o) { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(a, o.a); }
@@ -434,6 +439,7 @@ struct BBuf {
         bytes = b; a = &acct;
         acct.live += b;
         acct.peak = std::max(acct.peak, acct.live);
+        if (dev_mem_meter) dev_mem_meter->add(b);
         return 0;
     }
     template <class T> T* as() const { return (T*)p; }
@@ -471,6 +477,7 @@ struct kmdb_builder {
     BBuf overflow;                 // one flag
     kmdb_build_stats stats{};
     kmdb_build_seed_stats seed{};  // zeros unless the builder was seeded
+    kmdb_build_handoff_stats handoff{};   // zeros unless the builder ended in kmdb_build_finish_device
     std::vector<hipEvent_t> events;
     ~kmdb_builder() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
 };
@@ -991,19 +998,23 @@ int bd_add_seq(kmdb_builder* b, const char* const* names, const char* const* seq
     return rc;
 }
 
-int bd_finish(kmdb_builder* b, kmdbh_db** out) {
-    const char* who = "kmdb_build_finish";
-    if (!out) return kmdb_set_error(std::string(who) + ": null argument");
-    *out = nullptr;
-    BD_DO(bd_usable(b, who));
-    BD_TRY(hipSetDevice(b->device));
+// what the finish stages (c) and (d) leave in HBM: the rest of a stored database next to the builder's own here / parent / nsam
+struct BdFinish {
+    BBuf flag;                     // [0] a stream of 2^32 bits or more, [1] a k-mer outside the prefix buckets
+    BBuf num_local, last_id, num_bits, data_off, data;
+    uint64_t n_words = 0;
+    BBuf boff, slots;
+    uint64_t nb = 0, n_slots = 0;  // nb == 0: stage (d) has not run
+};
+
+// (c); HIP events e0, e0 + 1 around it
+int bd_finish_encode(kmdb_builder* b, const char* who, BdFinish& f, size_t e0) {
     hipStream_t st = b->st;
-    b->finished = true;
-    struct Dead { kmdb_builder* b; bool armed = true; ~Dead() { if (armed) b->dead = true; } } dead{b};
-    const uint64_t P = b->P, E = b->E, nD = b->nD;
-    BD_MARK(0);
+    const uint64_t P = b->P, E = b->E;
+    BD_MARK(e0);
     // ---- (c) the gamma streams
-    BBuf spid, ssid, clen, bitpos, num_local, last_id, num_bits, words, pbit0, data_off, data, flag;
+    BBuf spid, ssid, clen, bitpos, words, pbit0;
+    BBuf &num_local = f.num_local, &last_id = f.last_id, &num_bits = f.num_bits, &data_off = f.data_off, &data = f.data, &flag = f.flag;
     BD_DO(flag.alloc(b->acct, 8, "two flags"));
     BD_TRY(hipMemsetAsync(flag.p, 0, 8, st));
     BD_DO(spid.alloc(b->acct, (E + 1) * 4, "the sorted events' patterns"));
@@ -1040,7 +1051,7 @@ int bd_finish(kmdb_builder* b, kmdbh_db** out) {
     hipLaunchKernelGGL(bd_pattern_fields_kernel, dim3(bd_blocks(P + 1)), dim3(BD_THREADS), 0, st, spid.as<uint32_t>(), ssid.as<uint32_t>(), E, bitpos.as<unsigned long long>(), P,
                        num_local.as<uint32_t>(), last_id.as<uint32_t>(), num_bits.as<uint32_t>(), words.as<unsigned long long>(), pbit0.as<unsigned long long>(), flag.as<uint32_t>());
     BD_TRY(hipGetLastError());
-    uint64_t n_words = 0;
+    uint64_t& n_words = f.n_words;
     {
         BBuf tmp;
         size_t tb = 0;
@@ -1058,20 +1069,29 @@ int bd_finish(kmdb_builder* b, kmdbh_db** out) {
     if (E) hipLaunchKernelGGL(bd_write_codes_kernel, dim3(bd_blocks(E)), dim3(BD_THREADS), 0, st, spid.as<uint32_t>(), ssid.as<uint32_t>(), E, bitpos.as<unsigned long long>(),
                               pbit0.as<unsigned long long>(), data_off.as<unsigned long long>(), data.as<unsigned long long>(), n_words);
     BD_TRY(hipGetLastError());
-    BD_MARK(1);
+    BD_MARK(e0 + 1);
     BD_TRY(hipStreamSynchronize(st));
     spid.release(); ssid.release(); bitpos.release(); words.release(); pbit0.release();
+    return 0;
+}
+
+// (d); HIP events e0, e0 + 1 around it
+int bd_finish_tables(kmdb_builder* b, const char* who, BdFinish& f, size_t e0) {
+    hipStream_t st = b->st;
+    const uint64_t nD = b->nD;
+    BD_MARK(e0);
     // ---- (d) the tables
     const int prefix_bits = std::max(8, (int)(b->bits * b->k) - 32);                      // prefix_kmer_db.cpp:54-62
-    const uint64_t nb = 1ull << prefix_bits;
-    BBuf bstart, caps, boff, slots;
+    const uint64_t nb = f.nb = 1ull << prefix_bits;
+    BBuf bstart, caps;
+    BBuf &boff = f.boff, &slots = f.slots, &flag = f.flag;
     BD_DO(bstart.alloc(b->acct, (nb + 1) * 8, "the buckets' first k-mers"));
     BD_DO(caps.alloc(b->acct, (nb + 1) * 8, "the buckets' capacities"));
     BD_DO(boff.alloc(b->acct, (nb + 1) * 8, "bucket_offset"));
     hipLaunchKernelGGL(bd_bucket_starts_kernel, dim3(bd_blocks(nb + 1)), dim3(BD_THREADS), 0, st, b->D.as<uint64_t>(), nD, nb, bstart.as<unsigned long long>());
     hipLaunchKernelGGL(bd_bucket_caps_kernel, dim3(bd_blocks(nb + 1)), dim3(BD_THREADS), 0, st, bstart.as<unsigned long long>(), nb, caps.as<unsigned long long>());
     BD_TRY(hipGetLastError());
-    uint64_t n_slots = 0;
+    uint64_t& n_slots = f.n_slots;
     {
         BBuf tmp;
         size_t tb = 0;
@@ -1087,11 +1107,20 @@ int bd_finish(kmdb_builder* b, kmdbh_db** out) {
     if (nD) hipLaunchKernelGGL(bd_insert_kernel, dim3(bd_blocks(nD)), dim3(BD_THREADS), 0, st, b->D.as<uint64_t>(), b->cur.as<uint32_t>(), nD, nb, boff.as<unsigned long long>(),
                                slots.as<unsigned long long>(), flag.as<uint32_t>() + 1);
     BD_TRY(hipGetLastError());
-    BD_MARK(2);
+    BD_MARK(e0 + 1);
     uint32_t failed = 0;
     BD_TRY(hipMemcpyAsync(&failed, flag.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, st));
     BD_TRY(hipStreamSynchronize(st));
     if (failed) return kmdb_set_error(std::string(who) + ": a k-mer does not fit the prefix buckets of k = " + std::to_string(b->k) + " (the lists were made with another k or alphabet)");
+    return 0;
+}
+
+// (e); HIP events e0, e0 + 1 around it.  *out is the caller's to free.
+int bd_finish_copy_back(kmdb_builder* b, BdFinish& f, size_t e0, kmdbh_db** out) {
+    hipStream_t st = b->st;
+    const uint64_t P = b->P, nD = b->nD, n_words = f.n_words, nb = f.nb, n_slots = f.n_slots;
+    BBuf &num_local = f.num_local, &last_id = f.last_id, &num_bits = f.num_bits, &data_off = f.data_off, &data = f.data, &boff = f.boff, &slots = f.slots;
+    BD_MARK(e0);
     // ---- (e) to the host
     kmdbh_db_arrays a{};
     std::vector<std::string> names = b->names;
@@ -1109,14 +1138,110 @@ int bd_finish(kmdb_builder* b, kmdbh_db** out) {
     BD_TRY(hipMemcpyAsync(a.data, data.p, (n_words + 2) * 8, hipMemcpyDeviceToHost, st));
     BD_TRY(hipMemcpyAsync(a.bucket_offset, boff.p, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     if (n_slots) BD_TRY(hipMemcpyAsync(a.slots, slots.p, n_slots * 8, hipMemcpyDeviceToHost, st));
-    BD_MARK(3);
+    BD_MARK(e0 + 1);
     BD_TRY(hipStreamSynchronize(st));
-    b->stats.encode_ms = bd_ms(b, 0, 1);
-    b->stats.tables_ms = bd_ms(b, 1, 2);
-    b->stats.copy_back_ms = bd_ms(b, 2, 3);
-    dead.armed = false;
     hold.h = nullptr;
     *out = h;
+    return 0;
+}
+
+int bd_finish(kmdb_builder* b, kmdbh_db** out) {
+    const char* who = "kmdb_build_finish";
+    if (!out) return kmdb_set_error(std::string(who) + ": null argument");
+    *out = nullptr;
+    BD_DO(bd_usable(b, who));
+    BD_TRY(hipSetDevice(b->device));
+    b->finished = true;
+    struct Dead { kmdb_builder* b; bool armed = true; ~Dead() { if (armed) b->dead = true; } } dead{b};
+    BdFinish f;
+    BD_DO(bd_finish_encode(b, who, f, 0));
+    BD_DO(bd_finish_tables(b, who, f, 2));
+    BD_DO(bd_finish_copy_back(b, f, 4, out));
+    b->stats.encode_ms = bd_ms(b, 0, 1);
+    b->stats.tables_ms = bd_ms(b, 2, 3);
+    b->stats.copy_back_ms = bd_ms(b, 4, 5);
+    dead.armed = false;
+    return 0;
+}
+
+// kmdb_build_finish_device: stages (c) and, when somebody reads the tables, (d); then the engine's layout straight from the builder's arrays
+// (kmdb_db_from_device); then, for a full host image, (e).  Every array of the builder goes as soon as its last reader has run.
+int bd_finish_device(kmdb_builder* b, const kmdb_opts* opts, int with_hashtables, int host_image, kmdb_db** out_db, kmdbh_db** out_host) {
+    const char* who = "kmdb_build_finish_device";
+    if (out_host) *out_host = nullptr;
+    if (!out_db) return kmdb_set_error(std::string(who) + ": null argument");
+    *out_db = nullptr;
+    BD_DO(bd_usable(b, who));
+    // what kmdb_db_upload refuses of the finished database, with its messages, and a foreign device: found before the state is touched, the
+    // builder stays as it was (kmdb_build_finish still serves it)
+    if (opts && opts->abi_version && !kmdb_abi_compatible(opts->abi_version)) return kmdb_set_error(std::string(who) + ": kmdb_opts.abi_version is not served by this library");
+    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
+    if (b->P >= (1ull << 31)) return kmdb_set_error("kmdb_db_upload: more than 2^31 patterns");
+    if (b->names.size() >= KMDB_MAX_SAMPLES)
+        return kmdb_set_error("kmdb_db_upload: " + std::to_string(KMDB_MAX_SAMPLES) + " samples or more are not supported (sample ids take " + std::to_string(KMDB_ID_BITS) + " bits in the device layout)");
+    if ((opts ? opts->device : 0) != b->device)
+        return kmdb_set_error(std::string(who) + ": kmdb_opts.device is " + std::to_string(opts ? opts->device : 0) + ", the builder lives on device " + std::to_string(b->device) +
+                              " (the hand-off moves nothing between devices)");
+    BD_TRY(hipSetDevice(b->device));
+    hipStream_t st = b->st;
+    b->finished = true;
+    struct Dead { kmdb_builder* b; bool armed = true; ~Dead() { if (armed) b->dead = true; } } dead{b};
+    DevMemMeter meter;
+    meter.live = meter.peak = (long long)b->acct.live;
+    struct Metered { DevMemMeter* was; explicit Metered(DevMemMeter* m) : was(dev_mem_meter) { dev_mem_meter = m; } ~Metered() { dev_mem_meter = was; } } metered{&meter};
+    const auto t0 = std::chrono::steady_clock::now();
+    kmdb_build_handoff_stats& hs = b->handoff;
+    hs = kmdb_build_handoff_stats{};
+    hs.with_hashtables = with_hashtables ? 1 : 0; hs.host_image = host_image ? 1 : 0;
+    const bool tables = with_hashtables || host_image;
+    BdFinish f;
+    BD_DO(bd_finish_encode(b, who, f, 0));
+    if (tables) BD_DO(bd_finish_tables(b, who, f, 2));
+    b->D.release();                                    // the dictionary and its pattern ids: read by stage (d) only
+    b->cur.release();
+    BD_TRY(hipStreamSynchronize(st));
+    kmdb_layout_device_source src;
+    src.n_patterns = b->P; src.n_samples = b->names.size(); src.kmer_length = b->k;
+    src.num_kmers = b->here.as<long long>(); src.parent_id = b->parent.as<long long>(); src.num_samples = b->nsam.as<uint32_t>();
+    src.num_local = f.num_local.as<uint32_t>(); src.last_sample_id = f.last_id.as<uint32_t>(); src.num_bits = f.num_bits.as<uint32_t>();
+    src.data_offset = f.data_off.as<unsigned long long>(); src.data = f.data.as<uint64_t>(); src.n_data_words = f.n_words;
+    if (with_hashtables) { src.n_buckets = f.nb; src.n_slots = f.n_slots; src.bucket_offset = f.boff.as<uint64_t>(); src.slots = f.slots.as<uint64_t>(); }
+    if (!host_image) {
+        src.tables_done = [&] { f.boff.release(); f.slots.release(); };
+        src.fields_done = [&] { b->here.release(); b->parent.release(); b->nsam.release(); b->isp.release(); f.num_local.release(); f.last_id.release(); f.num_bits.release(); f.data_off.release(); };
+        src.streams_done = [&] { f.data.release(); };
+    }
+    kmdb_db* db = nullptr;
+    BD_DO(kmdb_db_from_device(&src, opts, with_hashtables, &db));
+    struct HoldHandle { kmdb_db* db; ~HoldHandle() { if (db) kmdb_db_free(db); } } hold_db{db};
+    kmdbh_db* h = nullptr;
+    if (host_image) {
+        BD_DO(bd_finish_copy_back(b, f, 4, &h));
+        hs.copy_back_ms = bd_ms(b, 4, 5);
+        hs.d2h_bytes = b->P * 40 + (f.n_words + 2) * 8 + (f.nb + 1) * 8 + f.n_slots * 8;
+    } else if (out_host) {
+        kmdbh_db_arrays a{};
+        std::vector<std::string> names = b->names;
+        std::vector<uint64_t> counts = b->counts;
+        h = kmdbh_db_make(b->k, b->fraction, b->start_fraction, b->alphabet, b->nD, std::move(names), std::move(counts), 0, 0, 0, 0, &a);
+        if (!h) return 1;
+    }
+    hs.patterns = b->P; hs.samples = b->names.size();
+    hs.encode_ms = bd_ms(b, 0, 1);
+    hs.tables_ms = tables ? bd_ms(b, 2, 3) : 0.0;
+    hs.fields_ms = src.fields_ms;
+    hs.layout_ms = src.layout_ms - src.fields_ms;
+    hs.prepare_ms = src.prepare_ms;
+    hs.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    hs.peak_device_bytes = (uint64_t)meter.peak;
+    kmdb_stats ds{};
+    if (!kmdb_db_stats(db, &ds)) hs.handle_device_bytes = ds.device_bytes;
+    b->stats.encode_ms = hs.encode_ms; b->stats.tables_ms = hs.tables_ms; b->stats.copy_back_ms = hs.copy_back_ms;
+    dead.armed = false;
+    hold_db.db = nullptr;
+    *out_db = db;
+    if (out_host) *out_host = h;
+    else if (h) kmdbh_db_free(h);
     return 0;
 }
 
@@ -1149,6 +1274,14 @@ extern "C" int kmdb_build_add_seq_alphabet(kmdb_builder* b, const char* const* n
 extern "C" int kmdb_build_finish(kmdb_builder* b, kmdbh_db** out) {
     BD_GUARD("kmdb_build_finish", bd_finish(b, out))
 }
+extern "C" int kmdb_build_finish_device(kmdb_builder* b, const kmdb_opts* opts, int with_hashtables, int host_image, kmdb_db** out_db, kmdbh_db** out_host) {
+    BD_GUARD("kmdb_build_finish_device", bd_finish_device(b, opts, with_hashtables, host_image, out_db, out_host))
+}
+extern "C" int kmdb_build_handoff_stats_get(const kmdb_builder* b, kmdb_build_handoff_stats* out) {
+    if (!b || !out) return kmdb_set_error("kmdb_build_handoff_stats_get: null argument");
+    *out = b->handoff;
+    return 0;
+}
 extern "C" void kmdb_build_free(kmdb_builder* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
@@ -1161,6 +1294,6 @@ extern "C" int kmdb_build_stats_get(const kmdb_builder* b, kmdb_build_stats* out
     out->distinct_kmers = b->nD;
     out->patterns = b->P;
     out->events = b->E;
-    out->peak_device_bytes = b->acct.peak;
+    out->peak_device_bytes = std::max<uint64_t>(b->acct.peak, b->handoff.peak_device_bytes);
     return 0;
 }

@@ -18,6 +18,16 @@
             return kmdb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// A meter of the device bytes the calling thread holds through DevBuf (and build.hip's BBuf) while it is installed: kmdb_build_finish_device
+// reports the peak of builder plus handle with it.  Null (the default): nothing is counted.  A buffer made before the meter was installed and
+// released under it would count as negative: the hand-off installs it before the handle exists and takes it off before it returns.
+struct DevMemMeter {
+    long long live = 0, peak = 0;
+    void add(size_t b) { live += (long long)b; if (live > peak) peak = live; }
+    void sub(size_t b) { live -= (long long)b; }
+};
+inline thread_local DevMemMeter* dev_mem_meter = nullptr;
+
 // Reads as the T* it replaces: a kernel argument, `q.field = buf`, `buf + n` and `if (!buf)` go through the conversion.  (A function template
 // that deduces its argument takes buf.get(): a DevBuf cannot be copied.)
 template <class T>
@@ -38,9 +48,13 @@ public:
         const hipError_t e = hipMalloc((void**)&p_, want);
         if (e != hipSuccess) { p_ = nullptr; return kmdb_set_error(std::string(what) + ": hipMalloc of " + std::to_string(want) + " B: " + hipGetErrorString(e)); }
         bytes_ = want;
+        if (dev_mem_meter) dev_mem_meter->add(want);
         return 0;
     }
-    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; bytes_ = 0; }
+    void reset() {
+        if (p_) { (void)hipFree(p_); if (dev_mem_meter) dev_mem_meter->sub(bytes_); }
+        p_ = nullptr; bytes_ = 0;
+    }
     // the array of a buffer of another element type becomes this one's (what this one held goes first); `o` is left empty
     template <class U> void take(DevBuf<U>& o) { reset(); bytes_ = o.bytes(); p_ = (T*)o.release(); }
     T* release() { bytes_ = 0; return std::exchange(p_, nullptr); }

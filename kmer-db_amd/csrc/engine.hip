@@ -167,33 +167,13 @@ __global__ __launch_bounds__(64) void row_tiles_kernel(const uint32_t* __restric
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// plan / rplan: the part of the database this handle holds — shard `shard_index` of `shard_count` prefix-bucket shards (plan == nullptr: planned
-// here), or range `shard_index` of rplan's tree ranges; neither (shard_count 1): the whole database
-int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
-                const kmdb_range_plan* rplan, kmdb_db** out, bool query_shard = false) {
-    *out = nullptr;
-    if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload: bad view / ABI version");
-    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
-    const uint64_t P = v->n_patterns, N = v->n_samples;
-    if (P >= (1ull << 31)) return kmdb_set_error("kmdb_db_upload: more than 2^31 patterns");
-    if (N >= KMDB_MAX_SAMPLES) return kmdb_set_error("kmdb_db_upload: " + std::to_string(KMDB_MAX_SAMPLES) + " samples or more are not supported (sample ids take " + std::to_string(KMDB_ID_BITS) + " bits in the device layout)");
-    if (shard_count == 0 || shard_index >= shard_count) return kmdb_set_error("kmdb_db_upload_shard: shard_index >= shard_count");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        (void)hipGetLastError();
-        return kmdb_set_error("kmdb_db_upload: no HIP device available (the engine has no CPU fallback)");
-    }
-    const int device = opts ? opts->device : 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(device));
-    // a prefix shard uploaded by itself plans itself: its k-mer counts from its own buckets, its nodes by one sweep (host_shards.cpp)
-    kmdb_shard_plan own_plan;
-    if (shard_count > 1 && !plan && !rplan) {
-        if (kmdb_shard_plan_build(v, shard_count, std::vector<uint32_t>{shard_index}, &own_plan)) return 1;
-        plan = &own_plan;
-    }
+// The handle of a database on `device`: streams and events, the layout (layout(db): kmdb_layout_upload, or kmdb_layout_from_device), the
+// working set of all2all for a handle without hashtables, the stats.  prepare_ms (may be null): wall clock of kmdb_blocks_prepare.
+template <class Layout>
+int handle_make(uint64_t N, uint64_t P, uint32_t kmer_length, int device, const kmdb_opts* opts, int with_hashtables, std::chrono::steady_clock::time_point t0,
+                Layout&& layout, kmdb_db** out, double* prepare_ms = nullptr) {
     auto* db = new kmdb_db();
-    db->device = device; db->N = N; db->P = P; db->kmer_length = v->kmer_length;
+    db->device = device; db->N = N; db->P = P; db->kmer_length = kmer_length;
     db->one_shot = opts && (opts->flags & KMDB_FLAG_ONE_SHOT);
     auto fail = [&]() { kmdb_db_free(db); return 1; };
     if (hipStreamCreate(&db->stream) != hipSuccess) { kmdb_set_error("hipStreamCreate failed"); return fail(); }
@@ -212,22 +192,15 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
         t_mark = now;
     };
     part("streams + events (first use of the device)");
-    {
-        kmdb_kept_nodes sel;
-        if (rplan) sel = kmdb_kept_of_range(*rplan, shard_index);
-        else if (plan && shard_count > 1) sel = kmdb_kept_of_shard(*plan, shard_index);
-        if (query_shard && plan && shard_count > 1) { sel.what = "query shard"; sel.qs_index = shard_index; sel.qs_count = shard_count; }
-        const bool part_of_db = rplan || (plan && shard_count > 1);
-        const int rc = kmdb_layout_upload(db, v, with_hashtables, part_of_db ? &sel : nullptr);
-        if (plan && shard_count > 1) plan->release_weights(shard_index);      // the shard's P counters go back
-        if (rc) return fail();
-    }
+    if (layout(db)) return fail();
     part("layout incl. release of its temporaries");
     // the working set of all2all: now for an all2all upload, on the first all2all call for a new2all / db2db upload
+    const auto t_prep = std::chrono::steady_clock::now();
     if (!with_hashtables && kmdb_blocks_prepare(db)) return fail();
     part("preparation of the all2all working set");
     if (hipStreamSynchronize(db->stream) != hipSuccess) { kmdb_set_error("kmdb_db_upload: device error"); return fail(); }
     part("final wait");
+    if (prepare_ms) *prepare_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep).count();
     db->blocks_bytes_counted = kmdb_blocks_device_bytes(db);
     db->stats.device_bytes += db->blocks_bytes_counted;
     db->stats.width = db->width;
@@ -236,6 +209,44 @@ int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtable
                                         (unsigned long long)P, (unsigned long long)N);
     *out = db;
     return 0;
+}
+
+// plan / rplan: the part of the database this handle holds — shard `shard_index` of `shard_count` prefix-bucket shards (plan == nullptr: planned
+// here), or range `shard_index` of rplan's tree ranges; neither (shard_count 1): the whole database
+int upload_impl(const kmdb_db_view* v, const kmdb_opts* opts, int with_hashtables, uint32_t shard_index, uint32_t shard_count, kmdb_shard_plan* plan,
+                const kmdb_range_plan* rplan, kmdb_db** out, bool query_shard = false) {
+    *out = nullptr;
+    if (!v || !kmdb_abi_compatible(v->abi_version)) return kmdb_set_error("kmdb_db_upload: bad view / ABI version");
+    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
+    const uint64_t P = v->n_patterns, N = v->n_samples;
+    if (!P) return kmdb_set_error("kmdb_db_upload: the view holds no pattern, not even the empty one (a header-only image of kmdb_build_finish_device carries names and counts only)");
+    if (P >= (1ull << 31)) return kmdb_set_error("kmdb_db_upload: more than 2^31 patterns");
+    if (N >= KMDB_MAX_SAMPLES) return kmdb_set_error("kmdb_db_upload: " + std::to_string(KMDB_MAX_SAMPLES) + " samples or more are not supported (sample ids take " + std::to_string(KMDB_ID_BITS) + " bits in the device layout)");
+    if (shard_count == 0 || shard_index >= shard_count) return kmdb_set_error("kmdb_db_upload_shard: shard_index >= shard_count");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        (void)hipGetLastError();
+        return kmdb_set_error("kmdb_db_upload: no HIP device available (the engine has no CPU fallback)");
+    }
+    const int device = opts ? opts->device : 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(device));
+    // a prefix shard uploaded by itself plans itself: its k-mer counts from its own buckets, its nodes by one sweep (host_shards.cpp)
+    kmdb_shard_plan own_plan;
+    if (shard_count > 1 && !plan && !rplan) {
+        if (kmdb_shard_plan_build(v, shard_count, std::vector<uint32_t>{shard_index}, &own_plan)) return 1;
+        plan = &own_plan;
+    }
+    return handle_make(N, P, v->kmer_length, device, opts, with_hashtables, t0, [&](kmdb_db* db) {
+        kmdb_kept_nodes sel;
+        if (rplan) sel = kmdb_kept_of_range(*rplan, shard_index);
+        else if (plan && shard_count > 1) sel = kmdb_kept_of_shard(*plan, shard_index);
+        if (query_shard && plan && shard_count > 1) { sel.what = "query shard"; sel.qs_index = shard_index; sel.qs_count = shard_count; }
+        const bool part_of_db = rplan || (plan && shard_count > 1);
+        const int rc = kmdb_layout_upload(db, v, with_hashtables, part_of_db ? &sel : nullptr);
+        if (plan && shard_count > 1) plan->release_weights(shard_index);      // the shard's P counters go back
+        return rc;
+    }, out);
 }
 
 }  // namespace
@@ -255,6 +266,7 @@ int kmdb_db_upload_query_planned(const kmdb_db_view* v, const kmdb_opts* opts, u
     if (shard_count == 0 || shard_count > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_db_upload_query_shard: shard_count must be between 1 and " + std::to_string(KMDB_MAX_SHARDS));
     if (shard_index >= shard_count) return kmdb_set_error("kmdb_db_upload_query_shard: shard_index >= shard_count");
     if (shard_count == 1) return kmdb_db_upload(v, opts, 1, out);
+    if (!v->n_patterns) return kmdb_set_error("kmdb_db_upload_query_shard: the view holds no pattern, not even the empty one (a header-only image of kmdb_build_finish_device carries names and counts only)");
     if (!v->n_buckets) return kmdb_set_error("kmdb_db_upload_query_shard: the view carries no hashtables (load the database with mode Everything)");
     return upload_impl(v, opts, 1, shard_index, shard_count, plan, nullptr, out, true);
 }
@@ -268,6 +280,7 @@ extern "C" int kmdb_db_upload_range(const kmdb_db_view* v, const kmdb_opts* opts
     if (range_count == 0 || range_count > KMDB_MAX_SHARDS) return kmdb_set_error("kmdb_db_upload_range: range_count must be between 1 and " + std::to_string(KMDB_MAX_SHARDS));
     if (range_index >= range_count) return kmdb_set_error("kmdb_db_upload_range: range_index >= range_count");
     if (range_count == 1) return kmdb_db_upload(v, opts, 0, out);
+    if (!v->n_patterns) return kmdb_set_error("kmdb_db_upload_range: the view holds no pattern, not even the empty one (a header-only image of kmdb_build_finish_device carries names and counts only)");
     // a range uploaded by itself plans all ranges (two sweeps over parent_id and num_samples, host_ranges.cpp): the cuts are a pure function
     // of the view and the count, so processes that each upload one range of the same database agree
     try {
@@ -287,6 +300,24 @@ int kmdb_db_upload_planned(const kmdb_db_view* v, const kmdb_opts* opts, int wit
                            kmdb_db** out) {
     if (!out) return kmdb_set_error("kmdb_db_upload_shard: null argument");
     return upload_impl(v, opts, with_hashtables, shard_index, shard_count, plan, nullptr, out);
+}
+
+// the hand-off of a finished builder (build.hip): the refusals are those of upload_impl, with its messages
+int kmdb_db_from_device(kmdb_layout_device_source* src, const kmdb_opts* opts, int with_hashtables, kmdb_db** out) {
+    *out = nullptr;
+    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error("kmdb_db_upload: unknown bits in kmdb_opts.flags");
+    const uint64_t P = src->n_patterns, N = src->n_samples;
+    if (!P) return kmdb_set_error("kmdb_db_upload: the view holds no pattern, not even the empty one");
+    if (P >= (1ull << 31)) return kmdb_set_error("kmdb_db_upload: more than 2^31 patterns");
+    if (N >= KMDB_MAX_SAMPLES) return kmdb_set_error("kmdb_db_upload: " + std::to_string(KMDB_MAX_SAMPLES) + " samples or more are not supported (sample ids take " + std::to_string(KMDB_ID_BITS) + " bits in the device layout)");
+    const int device = opts ? opts->device : 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(device));
+    return handle_make(N, P, src->kmer_length, device, opts, with_hashtables, t0, [&](kmdb_db* db) {
+        const int rc = kmdb_layout_from_device(db, src, with_hashtables);
+        src->layout_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    }, out, &src->prepare_ms);
 }
 
 extern "C" void kmdb_db_settle(kmdb_db* db) {

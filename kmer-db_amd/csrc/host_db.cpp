@@ -407,6 +407,15 @@ kmdbh_db* kmdbh_db_make(uint32_t kmer_length, double fraction, double start_frac
     return db;
 }
 
+extern "C" int kmdbh_db_header_only(const kmdbh_db* db, kmdbh_db** out) {
+    if (!db || !out) return kmdb_set_error("kmdbh_db_header_only: null argument");
+    kmdbh_db_arrays a{};
+    std::vector<std::string> names = db->names;
+    std::vector<uint64_t> counts = db->sample_kmers;
+    *out = kmdbh_db_make(db->kmer_length, db->fraction, db->start_fraction, db->alphabet, db->kmers_count, std::move(names), std::move(counts), 0, 0, 0, 0, &a);
+    return *out ? 0 : 1;
+}
+
 // ---- PrefixKmerDb::serialize(file, true) (prefix_kmer_db.cpp:438-574) ---------------------------------------------------------------
 namespace {
 struct Out {
@@ -422,6 +431,8 @@ constexpr size_t SIZEOF_PATTERN_T = 48;                // the reference's split 
 
 static int db_store_impl(const kmdbh_db* db, const char* path) {
     const kmdb_db_view& v = db->view;
+    if (!v.n_patterns)
+        return kmdb_set_error("kmdbh_db_store: a header-only image holds names and counts, no pattern and no table (kmdb_build_finish_device with host_image = 0): nothing to store");
     if (!v.n_buckets || !v.bucket_offset || !v.slots)
         return kmdb_set_error("kmdbh_db_store: the database holds no hashtables (it was loaded with SkipHashtables)");
     Out o;

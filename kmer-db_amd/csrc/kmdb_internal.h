@@ -35,6 +35,37 @@ kmdbh_db* kmdbh_db_make(uint32_t kmer_length, double fraction, double start_frac
                         std::vector<std::string>&& names, std::vector<uint64_t>&& sample_kmers, uint64_t n_patterns, uint64_t n_data_words,
                         uint64_t n_buckets, uint64_t n_slots, kmdbh_db_arrays* arrays);
 
+// ---- the hand-off of a finished builder to the engine (kmdb_build_finish_device, build.hip -> engine.hip -> layout.hip): the database as
+// the builder holds it in HBM at the end of its finish stages (c) and (d).  Every pointer is device memory of the handle's device, every
+// array in pattern-id order; the streams are word-aligned (pattern p from word data_offset[p] on, MSB first, zero behind num_bits).
+// The callbacks (any may be empty) tell the builder that the last reader of a group of its arrays has run, so that it can release them:
+// the tables once they are copied, the tree and the stage (c) fields once the node arrays exist, the stream words once they are re-packed.
+struct kmdb_db;
+struct kmdb_layout_device_source {
+    uint64_t n_patterns = 0, n_samples = 0;
+    uint32_t kmer_length = 0;
+    const long long* num_kmers = nullptr;            // the builder's tree
+    const long long* parent_id = nullptr;
+    const uint32_t* num_samples = nullptr;
+    const uint32_t* num_local = nullptr;             // stage (c)
+    const uint32_t* last_sample_id = nullptr;
+    const uint32_t* num_bits = nullptr;
+    const unsigned long long* data_offset = nullptr;
+    const uint64_t* data = nullptr;
+    uint64_t n_data_words = 0;
+    uint64_t n_buckets = 0, n_slots = 0;             // stage (d); 0 buckets: no tables were made
+    const uint64_t* bucket_offset = nullptr;
+    const uint64_t* slots = nullptr;
+    std::function<void()> tables_done, fields_done, streams_done;
+    mutable double fields_ms = 0;                    // out: wall clock of the fields kernel and the table copies
+    double layout_ms = 0, prepare_ms = 0;            // out: wall clock of the whole layout (fields included) and of kmdb_blocks_prepare
+};
+// layout.hip: fills the handle's structural arrays and stats from the source (the device stage kmdb_db_upload ends in); 0, or 1 with the error set
+int kmdb_layout_from_device(kmdb_db* db, const kmdb_layout_device_source* src, int with_hashtables);
+// engine.hip: the handle kmdb_db_upload would return for the same database, made from the source; opts as for kmdb_db_upload
+struct kmdb_opts;
+int kmdb_db_from_device(kmdb_layout_device_source* src, const kmdb_opts* opts, int with_hashtables, kmdb_db** out);
+
 // ---- minhash.hip: the extractor behind kmdb_minhash_batch_seq_alphabet with the lists LEFT ON THE DEVICE (build.hip adds them to its
 // tree from there).  The batch is cut into pieces as for the public entry; for every piece `sink` is called once, after the piece's last
 // kernel has ended: d_kmers = the sorted unique words of the piece's n samples, sample s at [off[s], off[s + 1]) (off in host memory,

@@ -8,6 +8,8 @@
 //                     every node by pointer doubling along the parent links, then one gather into DFS order and a
 //                     bit-exact re-pack of the streams
 // parent_id[p] < p (patterns are appended, reference src/prefix_kmer_db.cpp:219,357); children keep pid order.
+// The device half (lay_device_stage) has a second source: kmdb_layout_from_device hands it a finished builder's arrays where they lie in
+// HBM (kmdb_build_finish_device, build.hip) — lay_fields_kernel does what the host's narrowing loop does, and nothing visits the host.
 #include "device_common.h"
 #include "engine_internal.h"
 
@@ -230,6 +232,76 @@ struct HostBuf {
     HostBuf& operator=(const HostBuf&) = delete;
 };
 
+// KMDB_VERBOSE: the time since the last phase, after everything on the device has ended
+struct LayPhase {
+    const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!verbose) return;
+        (void)hipDeviceSynchronize();
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[kmdb] upload: %-34s %.3f s\n", what, std::chrono::duration<double>(now - t0).count());
+        t0 = now;
+    }
+};
+
+// What the device stage reads, all of it in HBM and in pid order.  The buffers are the stage's to release as soon as their last reader has run.
+struct LayIn {
+    uint64_t P = 0, N = 0;
+    DevBuf<int32_t> parent;                  // -1 for roots
+    DevBuf<uint32_t> ll, last, n, nbits, w;  // num_local, last id (0 where num_local is 0), num_samples, num_bits, weight (32 bits)
+    DevBuf<unsigned long long> wfull;        // the untruncated weights, or empty (a part of a database: the plan's weights are the whole truth)
+    const int64_t* wfull_host = nullptr;     // ... or still on the host: P counts the stage copies up when it needs them
+    DevBuf<uint64_t> src_own;                // the stream words when the stage owns them
+    const uint64_t* src = nullptr;           // the stream words: MSB first, stream p from bit srcpos[p] on
+    DevBuf<uint64_t> srcpos;                 // empty: the streams lie back to back (the scan of nbits)
+    uint64_t n_bit_words = 0;                // words of the DFS-order streams, the look-ahead padding included
+    bool tables = false;                     // db->bucket_offset / db->slots hold the whole database's tables: pid2dfs is made
+    bool qshard = false;                     // ... one query shard's, values = indices among the kept nodes
+    uint64_t qs_slots = 0;
+    uint64_t h2d_bytes = 0, dev_ht_bytes = 0;
+    std::function<void()> streams_done;      // the source's own words behind `src` have had their last reader
+};
+int lay_device_stage(kmdb_db* db, LayIn& in, LayPhase& phase);
+
+// The host loop of kmdb_layout_upload for a source that lies in HBM (kmdb_layout_from_device): one lane per pattern narrows the fields of the
+// builder's state and of its finish stage (c), with the same checks — bad[0]: parent_id >= pattern id, bad[1]: inconsistent header (the
+// stream's words inside the data words included: lay_copy_bits_kernel reads ceil(num_bits / 64) words from 64 * data_offset on).  The
+// streams are word-aligned in pid order, so their source positions need no scan; the sum of num_bits (64 bits) sizes the DFS-order words.
+__global__ __launch_bounds__(256) void lay_fields_kernel(const long long* __restrict__ num_kmers, const long long* __restrict__ parent_id, const uint32_t* __restrict__ num_samples,
+                                                         const uint32_t* __restrict__ num_local, const uint32_t* __restrict__ last_id, const uint32_t* __restrict__ num_bits,
+                                                         const unsigned long long* __restrict__ data_offset, uint64_t n_data_words, uint32_t P, uint32_t N,
+                                                         int32_t* __restrict__ parent, uint32_t* __restrict__ ll, uint32_t* __restrict__ last, uint32_t* __restrict__ n_out,
+                                                         uint32_t* __restrict__ nbits, uint32_t* __restrict__ w, unsigned long long* __restrict__ wfull,
+                                                         uint64_t* __restrict__ srcpos, unsigned long long* __restrict__ total_bits, uint32_t* __restrict__ bad) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long bits = 0;
+    if (p < P) {
+        const long long par = parent_id[p], nk = num_kmers[p];
+        const uint32_t n = num_samples[p], l = num_local[p], nb = num_bits[p], lst = last_id[p];
+        const unsigned long long off = data_offset[p], words = ((unsigned long long)nb + 63ull) / 64ull;
+        if (par >= (long long)p) bad[0] = 1;
+        if (l > n || n > N || (l && lst >= N) || nb >= KMDB_MAX_STREAM_BITS || off > n_data_words || words > n_data_words - off) bad[1] = 1;
+        parent[p] = par < 0 ? -1 : (int32_t)par;
+        ll[p] = l;
+        last[p] = l ? lst : 0u;
+        n_out[p] = n;
+        nbits[p] = nb;
+        w[p] = (uint32_t)nk;                   // truncated exactly like the reference's to_add (similarity_calculator.cpp:222)
+        wfull[p] = (unsigned long long)nk;
+        srcpos[p] = 64ull * off;
+        bits = nb;
+    }
+    __shared__ unsigned long long s_bits[256];
+    s_bits[threadIdx.x] = bits;
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) s_bits[threadIdx.x] += s_bits[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && s_bits[0]) atomicAdd(total_bits, s_bits[0]);
+}
+
 }  // namespace
 
 void kmdb_release_staging(kmdb_db* db) {
@@ -261,19 +333,9 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     uint64_t P = pruned ? sel->kept : P_view;                  // nodes laid out
     uint64_t h2d_bytes = 0;
     const uint64_t N = v->n_samples;
-    const bool verbose = getenv("KMDB_VERBOSE") != nullptr;
-    auto tphase0 = std::chrono::steady_clock::now();
-    auto phase = [&](const char* what) {
-        if (!verbose) return;
-        (void)hipDeviceSynchronize();
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[kmdb] upload: %-34s %.3f s\n", what, std::chrono::duration<double>(now - tphase0).count());
-        tphase0 = now;
-    };
+    LayPhase phase;
+    const bool verbose = phase.verbose;
     hipStream_t st = db->stream;
-    if (const char* e = getenv("KMDB_SHORT_IDS")) if (*e) db->short_max_ids = (uint32_t)std::max(1, std::min(64, atoi(e)));     // (experiment, round 5)
-    const unsigned B = 256;
-    unsigned G = (unsigned)((P + B - 1) / B), G1 = (unsigned)((P + 1 + B - 1) / B);
 
     // ---- host: narrow + validate the header fields, pack the streams in pid order
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
@@ -394,9 +456,10 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     phase("host: narrow fields + pack streams");
 
     // ---- H2D
-    DevBuf<int32_t> d_parent;
-    DevBuf<uint32_t> d_ll, d_last, d_n, d_nbits, d_w;
-    DevBuf<uint64_t> d_src;
+    LayIn in;
+    DevBuf<int32_t>& d_parent = in.parent;
+    DevBuf<uint32_t>&d_ll = in.ll, &d_last = in.last, &d_n = in.n, &d_nbits = in.nbits, &d_w = in.w;
+    DevBuf<uint64_t>& d_src = in.src_own;
     if (d_parent.alloc(std::max<size_t>(P, 1)) || d_ll.alloc(std::max<size_t>(P, 1)) || d_last.alloc(std::max<size_t>(P, 1)) || d_n.alloc(std::max<size_t>(P, 1)) || d_nbits.alloc(std::max<size_t>(P, 1)) || d_w.alloc(std::max<size_t>(P, 1)) || d_src.alloc(std::max<size_t>(n_bit_words, 1))) return 1;
     HIP_TRY(hipMemcpyAsync(d_parent.get(), h_parent.p, P * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_ll.get(), h_ll.p, P * 4, hipMemcpyHostToDevice, st));
@@ -406,7 +469,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     HIP_TRY(hipMemcpyAsync(d_w.get(), h_w.p, P * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_src.get(), h_bits.p, n_bit_words * 8, hipMemcpyHostToDevice, st));
     h2d_bytes += P * 24 + n_bit_words * 8;
-    DevBuf<unsigned long long> d_wfull;                       // sum_pairs uses the untruncated counts
+    DevBuf<unsigned long long>& d_wfull = in.wfull;           // sum_pairs uses the untruncated counts
     uint64_t dev_ht_bytes = 0;
     if (qshard) {
         // only the shard's own bucket table: no slot of a foreign bucket crosses PCIe, and no pid2dfs array is made (the slots hold DFS indices)
@@ -439,6 +502,27 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     for (HostRegion r : {h_parent.release(), h_ll.release(), h_last.release(), h_n.release(), h_nbits.release(), h_w.release(), h_bits.release(), h_qoff.release(), h_qslots.release()})
         if (r.p) db->staging.emplace_back(r.p, r.bytes);
 
+    if (!sel) in.wfull_host = v->num_kmers;                   // (copied up by the device stage, where the node arrays are made)
+    in.P = P; in.N = N; in.src = d_src.get(); in.n_bit_words = n_bit_words;
+    in.qshard = qshard; in.qs_slots = qs_slots; in.tables = !qshard && with_hashtables && v->n_buckets;
+    in.h2d_bytes = h2d_bytes; in.dev_ht_bytes = dev_ht_bytes;
+    return lay_device_stage(db, in, phase);
+}
+
+// The device stage: from the pid-order arrays of `in` (all in HBM) to the handle's DFS-ordered layout.  Both sources end here: the host
+// stage above (a view, narrowed and packed on the host, copied up) and kmdb_layout_from_device below (a builder's state, never off the device).
+namespace {
+int lay_device_stage(kmdb_db* db, LayIn& in, LayPhase& phase) {
+    const uint64_t P = in.P, N = in.N, n_bit_words = in.n_bit_words;
+    hipStream_t st = db->stream;
+    if (const char* e = getenv("KMDB_SHORT_IDS")) if (*e) db->short_max_ids = (uint32_t)std::max(1, std::min(64, atoi(e)));     // (experiment, round 5)
+    const unsigned B = 256;
+    const unsigned G = (unsigned)((P + B - 1) / B), G1 = (unsigned)((P + 1 + B - 1) / B);
+    DevBuf<int32_t>& d_parent = in.parent;
+    DevBuf<uint32_t>&d_ll = in.ll, &d_last = in.last, &d_n = in.n, &d_nbits = in.nbits, &d_w = in.w;
+    DevBuf<unsigned long long>& d_wfull = in.wfull;
+    const bool qshard = in.qshard;
+    const uint64_t qs_slots = in.qs_slots;
     // ---- device: DFS pre-order
     DevBuf<uint32_t> cnt, cstart, size, keys, vals, skeys, schild, ssz, S, acc[2], dep[2], order, flags;
     DevBuf<int32_t> anc[2];
@@ -540,11 +624,11 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     DevBuf<LayStats> d_stats;
     if (d_stats.alloc(1)) return 1;
     HIP_TRY(hipMemsetAsync(d_stats.get(), 0, sizeof(LayStats), st));
-    if (!sel) {
+    if (in.wfull_host) {
         // the checksum sum_p w_p C(n_p, 2) is defined on the full 64-bit counts
         if (d_wfull.alloc(std::max<size_t>(P, 1))) return 1;
-        HIP_TRY(hipMemcpyAsync(d_wfull.get(), v->num_kmers, P * 8, hipMemcpyHostToDevice, st));
-        h2d_bytes += P * 8;
+        HIP_TRY(hipMemcpyAsync(d_wfull.get(), in.wfull_host, P * 8, hipMemcpyHostToDevice, st));
+        in.h2d_bytes += P * 8;
     }
     hipLaunchKernelGGL(lay_gather_kernel, dim3(std::min<unsigned>(G1, 2048u)), dim3(B), 0, st, order.get(), acc[cur].get(), dep[dcur].get(), cnt.get(), size.get(), d_parent.get(), d_ll.get(), d_last.get(), d_n.get(), d_nbits.get(), d_w.get(),
                        d_wfull.get(), (uint32_t)P, db->short_max_ids, db->k0in, db->nl, db->parent, db->w, db->dflag, db->sub_end, d_stats.get());
@@ -561,7 +645,7 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(st));
         }
-    } else if (with_hashtables && v->n_buckets) {
+    } else if (in.tables) {
         // pid -> DFS index for the hash lookups of new2all
         DEV_ALLOC(db->pid2dfs, std::max<uint64_t>(P, 1));
         hipLaunchKernelGGL(lay_pid2dfs_kernel, dim3(G), dim3(B), 0, st, acc[cur].get(), (uint32_t)P, db->pid2dfs);
@@ -573,15 +657,18 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     // ---- streams re-packed in DFS order
     {
         DevBuf<uint32_t> nb_dfs;
-        DevBuf<uint64_t> srcpos, dstpos;
-        if (nb_dfs.alloc(std::max<size_t>(P, 1)) || srcpos.alloc(P + 1) || dstpos.alloc(P + 1)) return 1;
+        // (a source that names its own stream positions has filled in.srcpos; the host stage packs back to back: the scan of num_bits)
+        const bool packed = !in.srcpos;
+        DevBuf<uint64_t>& srcpos = in.srcpos;
+        DevBuf<uint64_t> dstpos;
+        if (nb_dfs.alloc(std::max<size_t>(P, 1)) || (packed && srcpos.alloc(P + 1)) || dstpos.alloc(P + 1)) return 1;
         hipLaunchKernelGGL(lay_nbits_dfs_kernel, dim3(G), dim3(B), 0, st, db->k0in, (uint32_t)P, nb_dfs.get());
         rocprim::transform_iterator<uint32_t*, U32toU64, uint64_t> it_src(d_nbits.get(), U32toU64()), it_dst(nb_dfs.get(), U32toU64());
         size_t tb = 0;
         HIP_TRY(prim::exclusive_sum(nullptr, tb, it_src, srcpos.get(), (int)P, st));
         DevBuf<unsigned char> tmp;
         if (tmp.alloc(std::max<size_t>(tb, 1))) return 1;
-        HIP_TRY(prim::exclusive_sum(tmp.get(), tb, it_src, srcpos.get(), (int)P, st));
+        if (packed) HIP_TRY(prim::exclusive_sum(tmp.get(), tb, it_src, srcpos.get(), (int)P, st));
         HIP_TRY(prim::exclusive_sum(tmp.get(), tb, it_dst, dstpos.get(), (int)P, st));
         DEV_ALLOC(db->bits, n_bit_words);
         HIP_TRY(hipMemsetAsync(db->bits, 0, n_bit_words * 8, st));
@@ -589,12 +676,13 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
         DEV_ALLOC(db->blkbase, (P + 255) / 256 + 1);
         DEV_ALLOC(db->bitrel, std::max<uint64_t>(P, 1));
         hipLaunchKernelGGL(lay_blkbase_kernel, dim3(G), dim3(B), 0, st, dstpos.get(), (uint32_t)P, db->blkbase, db->bitrel);
-        hipLaunchKernelGGL(lay_copy_bits_kernel, dim3(G), dim3(B), 0, st, order.get(), srcpos.get(), dstpos.get(), db->k0in, d_src.get(), (uint32_t)P,
+        hipLaunchKernelGGL(lay_copy_bits_kernel, dim3(G), dim3(B), 0, st, order.get(), srcpos.get(), dstpos.get(), db->k0in, in.src, (uint32_t)P,
                            (unsigned long long*)db->bits.get());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
-    d_src.reset(); d_nbits.reset(); order.reset();
+    in.srcpos.reset(); in.src_own.reset(); in.src = nullptr; d_nbits.reset(); order.reset();
+    if (in.streams_done) in.streams_done();
     phase("device: stream re-pack");
 
     // ---- per-slice root paths, long nodes
@@ -641,7 +729,56 @@ int kmdb_layout_upload(kmdb_db* db, const kmdb_db_view* v, int with_hashtables, 
     db->stats.sum_pairs = hs.pairs;
     db->stats.n_segments = db->n_nsegs;
     db->stats.n_patterns = P;
-    db->stats.h2d_bytes = h2d_bytes;
-    db->stats.device_bytes = P * (8 + 4 + 4 + 4 + 4 + 2 + 4) + n_bit_words * 8 + (uint64_t)db->n_nsegs * db->chain_cap * 4 + dev_ht_bytes;
+    db->stats.h2d_bytes = in.h2d_bytes;
+    db->stats.device_bytes = P * (8 + 4 + 4 + 4 + 4 + 2 + 4) + n_bit_words * 8 + (uint64_t)db->n_nsegs * db->chain_cap * 4 + in.dev_ht_bytes;
     return 0;
+}
+}  // namespace
+
+// The second source of the device stage: a builder's state at the end of its finish stages (c) and (d) (build.hip), read where it lies.
+// No pattern field, stream word or table slot visits the host: one kernel narrows the fields, the tables go device to device, and the
+// streams are re-packed from their word-aligned pid-order places (srcpos = 64 * data_offset; lay_copy_bits_kernel's tail mask drops the
+// padding, and with an aligned source it never reads the word behind a stream).
+int kmdb_layout_from_device(kmdb_db* db, const kmdb_layout_device_source* s, int with_hashtables) {
+    const uint64_t P = s->n_patterns, N = s->n_samples;
+    const auto t0 = std::chrono::steady_clock::now();
+    LayPhase phase;
+    hipStream_t st = db->stream;
+    LayIn in;
+    in.P = P; in.N = N;
+    DevBuf<unsigned long long> total;
+    DevBuf<uint32_t> bad;
+    if (in.parent.alloc(P) || in.ll.alloc(P) || in.last.alloc(P) || in.n.alloc(P) || in.nbits.alloc(P) || in.w.alloc(P) || in.wfull.alloc(P) || in.srcpos.alloc(P + 1) ||
+        total.alloc(1) || bad.alloc(2)) return 1;
+    HIP_TRY(hipMemsetAsync(total.get(), 0, 8, st));
+    HIP_TRY(hipMemsetAsync(bad.get(), 0, 8, st));
+    hipLaunchKernelGGL(lay_fields_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, s->num_kmers, s->parent_id, s->num_samples, s->num_local, s->last_sample_id,
+                       s->num_bits, s->data_offset, s->n_data_words, (uint32_t)P, (uint32_t)N, in.parent.get(), in.ll.get(), in.last.get(), in.n.get(), in.nbits.get(), in.w.get(),
+                       in.wfull.get(), in.srcpos.get(), total.get(), bad.get());
+    HIP_TRY(hipGetLastError());
+    unsigned long long total_bits = 0;
+    uint32_t hbad[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&total_bits, total.get(), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hbad, bad.get(), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (hbad[0]) return kmdb_set_error("kmdb_db_upload: parent_id >= pattern id");
+    if (hbad[1]) return kmdb_set_error("kmdb_db_upload: inconsistent pattern header");
+    if (s->fields_done) s->fields_done();                     // (the kernel has ended: nothing reads the source's fields again)
+    in.n_bit_words = (total_bits + 63) / 64 + 16;             // zero padding words for the cursors' look-ahead
+    in.src = s->data;
+    if (with_hashtables && s->n_buckets) {
+        db->n_buckets = s->n_buckets;
+        DEV_ALLOC(db->bucket_offset, s->n_buckets + 1);
+        DEV_ALLOC(db->slots, std::max<uint64_t>(s->n_slots, 1));
+        HIP_TRY(hipMemcpyAsync(db->bucket_offset, s->bucket_offset, (s->n_buckets + 1) * 8, hipMemcpyDeviceToDevice, st));
+        if (s->n_slots) HIP_TRY(hipMemcpyAsync(db->slots, s->slots, s->n_slots * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        in.tables = true;
+        in.dev_ht_bytes = (s->n_buckets + 1) * 8 + s->n_slots * 8 + P * 4;
+    }
+    if (s->tables_done) s->tables_done();
+    in.streams_done = s->streams_done;
+    s->fields_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    phase("device: narrow fields");
+    return lay_device_stage(db, in, phase);
 }

@@ -202,7 +202,10 @@ struct Db {
     ~Db() { if (dropper.joinable()) dropper.join(); if (node) kmdb_node_free(node); if (d) kmdb_db_free(d); if (h) kmdbh_db_free(h); }
 };
 
+struct BuildInput;
 struct Common {
+    std::shared_ptr<BuildInput> from_samples;     // all2all | all2all-sp -from-samples: build's input switches; the "database" argument is the sample list
+    std::string keep_db;                     // -keep-db <database>: the file `build` would have written, stored next to the table
     int threads = 0;
     int device = 0;
     int gpus = 0;                            // -gpus N: N prefix-bucket shards over the node's devices (0: one device, no sharding)
@@ -302,6 +305,10 @@ std::vector<std::string> take_distance_measures(std::vector<std::string>& args) 
 int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures, bool sparse_forced, const char* mode);
 int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::vector<std::string>& measures);
 
+// The opening of all2all, all2all-sp and their -distance form (further down, behind build): `db` holds the database on the device and what the
+// rest of the run reads of it on the host — names, k-mer counts, k, fraction
+void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts& o);
+
 // ---- all2all (console_all2all.cpp:7-89) -----------------------------------------------------------
 int run_all2all(std::vector<std::string>& args, Common& c) {
     std::string v;
@@ -314,22 +321,9 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     if (args.size() != 2) throw usage_error("all2all");
     std::cerr << "All versus all comparison" << std::endl;
     Db db;
-    std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
     std::ofstream ofs(args[1]);
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1; o.flags = KMDB_FLAG_ONE_SHOT;
-    if (c.gpus > 0) node_upload(db, args[0], c);
-    else {
-        const auto tl = clk::now();
-        std::thread warm([&]() { (void)kmdb_device_prepare(c.device); });      // the device's first use, next to the read of the file (an error shows at the upload)
-        const int load_rc = kmdbh_db_load(args[0].c_str(), 2, &db.h);
-        const std::string load_err = load_rc ? kmdb_last_error() : "";
-        warm.join();
-        if (load_rc) throw std::runtime_error(load_err);
-        const double load_s = since(tl);
-        const auto tu = clk::now();
-        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 0, &db.d));
-        std::cerr << "Database loaded in " << load_s << " s, uploaded in " << since(tu) << " s" << std::endl;
-    }
+    open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
     std::cerr << "Calculating matrix of common k-mers..." << std::endl;
@@ -412,22 +406,9 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     if (args.size() != 2) throw usage_error("all2all-sp");
     std::cerr << "All versus all comparison (sparse computation)" << std::endl;
     Db db;
-    std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
     std::ofstream ofs(args[1], std::ios::binary);
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1; o.bubble_size = bubble; o.flags = KMDB_FLAG_ONE_SHOT;
-    if (c.gpus > 0) node_upload(db, args[0], c);
-    else {
-        const auto tl = clk::now();
-        std::thread warm([&]() { (void)kmdb_device_prepare(c.device); });      // the device's first use, next to the read of the file (an error shows at the upload)
-        const int load_rc = kmdbh_db_load(args[0].c_str(), 2, &db.h);
-        const std::string load_err = load_rc ? kmdb_last_error() : "";
-        warm.join();
-        if (load_rc) throw std::runtime_error(load_err);
-        const double load_s = since(tl);
-        const auto tu = clk::now();
-        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 0, &db.d));
-        std::cerr << "Database loaded in " << load_s << " s, uploaded in " << since(tu) << " s" << std::endl;
-    }
+    open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
     std::cerr << "Calculating matrix of common k-mers...";
@@ -1041,20 +1022,26 @@ int run_minhash(std::vector<std::string>& args, Common& c) {
 // ---- build (console_build.cpp:33-158, params.cpp:459-513, loader_ex.cpp:86-124, 165-168): genomes (or <sample>.minhash files) in, a database out ----
 // db.addKmers per sample (:111) is kmdb_build_add_seq_alphabet / kmdb_build_add_kmers for a batch of samples, serialize (:149) is
 // kmdb_build_finish + kmdbh_db_store.  The samples take their ids in input order; a file that cannot be opened prints "failed:<path>" and takes none.
-int run_build(std::vector<std::string>& args, Common& c) {
-    const bool from_kmers = take_switch(args, "-from-kmers"), from_minhash = take_switch(args, "-from-minhash");
-    if (from_kmers && from_minhash) throw std::runtime_error("-from-kmers and -from-minhash switches exclude one another.");      // params.cpp:499-502
-    if (from_kmers) throw std::runtime_error(KMC_REFUSAL);
-    if (take_switch(args, "-extend")) throw std::runtime_error("build -extend is not supported: rebuild from the sample list");
-    const bool host_extract = take_switch(args, "-host-extract");
+// build's input switches (params.cpp:459-513), with build's defaults, checks and messages: `build` and `all2all | all2all-sp -from-samples` read them
+struct BuildInput {
+    bool from_minhash = false, host_extract = false, multi = false, extend = false;
     double fraction = 1.0, fstart = 0.0;
     uint32_t k = 18;
     int32_t alphabet = KMDB_ALPHABET_NT;
-    bool multi = false;
-    std::string v, seed_path;
+    std::string seed_path;
+    void parse(std::vector<std::string>& args);
+};
+void BuildInput::parse(std::vector<std::string>& args) {
+    const bool from_kmers = take_switch(args, "-from-kmers");
+    from_minhash = take_switch(args, "-from-minhash");
+    if (from_kmers && from_minhash) throw std::runtime_error("-from-kmers and -from-minhash switches exclude one another.");      // params.cpp:499-502
+    if (from_kmers) throw std::runtime_error(KMC_REFUSAL);
+    if (take_switch(args, "-extend")) throw std::runtime_error("build -extend is not supported: rebuild from the sample list");
+    host_extract = take_switch(args, "-host-extract");
+    std::string v;
     // -extend-from <old.db>: the builder starts from a stored database (console_build.cpp:48-57).  k, fraction, start fraction and alphabet are
     // the database's own; -k, -f, -f-start, -alphabet and -preserve-strand are accepted and ignored, as the reference's -extend does
-    const bool extend = take_option(args, "-extend-from", seed_path);
+    extend = take_option(args, "-extend-from", seed_path);
     if (extend) {
         take_option(args, "-f", v); take_option(args, "-f-start", v); take_option(args, "-alphabet", v); take_option(args, "-k", v);
         take_switch(args, "-preserve-strand");
@@ -1079,9 +1066,19 @@ int run_build(std::vector<std::string>& args, Common& c) {
         kmdbh_alphabet_table(alphabet, map, &size, &bits, nullptr);
         if (k == 0 || k > 64u / bits - 1u) throw std::runtime_error("K-mer length for the given alphabet cannot exceed " + std::to_string(64u / bits - 1u));
     }
-    if (args.size() != 2) throw usage_error("build");
-    std::cerr << "Building database (from " << (from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
-    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } built, old;
+}
+
+struct BuilderHold { kmdb_builder* b = nullptr; ~BuilderHold() { kmdb_build_free(b); } };
+
+// The sample-feeding loop of build: the seed (-extend-from) is loaded, the list read, every sample extracted and added in input order; bld.b
+// is the fed builder, not yet finished.  k, fraction and alphabet of `in` end as the builder's (a seed's, a .minhash file's).
+void build_feed(BuildInput& in, const std::string& input, Common& c, BuilderHold& bld) {
+    const bool from_minhash = in.from_minhash, host_extract = in.host_extract, multi = in.multi, extend = in.extend;
+    double &fraction = in.fraction, &fstart = in.fstart;
+    uint32_t& k = in.k;
+    int32_t& alphabet = in.alphabet;
+    const std::string& seed_path = in.seed_path;
+    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } old;
     if (extend) {                                                  // read with its tables, before anything else is opened and before any device is touched
         std::cerr << "Loading k-mer database " << seed_path << "..." << std::endl;
         if (kmdbh_db_load(seed_path.c_str(), 0, &old.h)) throw std::runtime_error("Cannot open k-mer database " + seed_path);
@@ -1092,12 +1089,12 @@ int run_build(std::vector<std::string>& args, Common& c) {
     bool is_fasta = false;
     for (const char* ext : {".fa", ".fna", ".fasta", ".fastq", ".gz", ".fa.gz", ".fna.gz", ".fasta.gz", ".fastq.gz"}) {
         const size_t n = std::strlen(ext);
-        if (args[0].size() >= n && args[0].compare(args[0].size() - n, n, ext) == 0) is_fasta = true;
+        if (input.size() >= n && input.compare(input.size() - n, n, ext) == 0) is_fasta = true;
     }
-    if (is_fasta) entries.push_back(args[0]);
+    if (is_fasta) entries.push_back(input);
     else {
-        std::ifstream lst(args[0]);
-        if (!lst) throw std::runtime_error("Unable to open input file " + args[0]);
+        std::ifstream lst(input);
+        if (!lst) throw std::runtime_error("Unable to open input file " + input);
         for (std::string e; lst >> e;) entries.push_back(e);
     }
     std::cerr << "Processing samples..." << std::endl;
@@ -1105,7 +1102,6 @@ int run_build(std::vector<std::string>& args, Common& c) {
     double extract_s = 0, update_s = 0;
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1;
     const int nthreads = c.threads > 0 ? c.threads : (int)std::max(1u, std::thread::hardware_concurrency());
-    struct Builder { kmdb_builder* b = nullptr; ~Builder() { kmdb_build_free(b); } } bld;
     if (extend) {
         check(kmdb_build_begin_from_db(old.h, &o, &bld.b));
         kmdbh_db_free(old.h);                                      // the builder holds the state now
@@ -1221,6 +1217,16 @@ int run_build(std::vector<std::string>& args, Common& c) {
     if (!bld.b) throw std::runtime_error("no sample could be read: the database would be empty");
     std::cerr << std::endl << std::endl << "EXECUTION TIMES" << std::endl << "Total: " << since(total0) << std::endl
               << "Kmer sorting/unique time: " << extract_s << std::endl << "Database update time:" << update_s << std::endl;
+}
+
+int run_build(std::vector<std::string>& args, Common& c) {
+    BuildInput in;
+    in.parse(args);
+    if (args.size() != 2) throw usage_error("build");
+    std::cerr << "Building database (from " << (in.from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
+    struct HostDb { kmdbh_db* h = nullptr; ~HostDb() { if (h) kmdbh_db_free(h); } } built;
+    BuilderHold bld;
+    build_feed(in, args[0], c, bld);
     check(kmdb_build_finish(bld.b, &built.h));
     kmdb_build_stats st{};
     if (std::getenv("KMDB_VERBOSE") && !kmdb_build_stats_get(bld.b, &st))
@@ -1230,6 +1236,44 @@ int run_build(std::vector<std::string>& args, Common& c) {
     std::cerr << "Serializing database..." << std::endl;
     check(kmdbh_db_store(built.h, args[1].c_str()));
     return 0;
+}
+
+void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts& o) {
+    if (c.from_samples) {
+        // -from-samples: `source` is build's sample list.  The builder is fed as by `build`, then handed to the engine where it lies
+        // (kmdb_build_finish_device): db.h is the header-only image, or with -keep-db the full one, stored at once — finish() leaves through _Exit
+        BuildInput& in = *c.from_samples;
+        std::cerr << "Building database (from " << (in.from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
+        BuilderHold bld;
+        build_feed(in, source, c, bld);
+        const auto tu = clk::now();
+        const bool keep = !c.keep_db.empty();
+        check(kmdb_build_finish_device(bld.b, &o, 0, keep ? 1 : 0, &db.d, &db.h));
+        std::cerr << "Database handed to the engine in " << since(tu) << " s" << std::endl;
+        kmdb_build_handoff_stats hs{};
+        if (std::getenv("KMDB_VERBOSE") && !kmdb_build_handoff_stats_get(bld.b, &hs))
+            std::cerr << "[kmdb] hand-off: " << hs.samples << " samples, " << hs.patterns << " patterns, peak " << hs.peak_device_bytes << " device bytes (handle "
+                      << hs.handle_device_bytes << "), " << hs.d2h_bytes << " bytes to the host; encode " << hs.encode_ms << " tables " << hs.tables_ms << " fields "
+                      << hs.fields_ms << " layout " << hs.layout_ms << " prepare " << hs.prepare_ms << " copy-back " << hs.copy_back_ms << " total " << hs.total_ms << " ms"
+                      << std::endl;
+        if (keep) {
+            std::cerr << "Serializing database..." << std::endl;
+            check(kmdbh_db_store(db.h, c.keep_db.c_str()));
+        }
+        return;
+    }
+    std::cerr << "Loading k-mer database " << source << "..." << std::endl;
+    if (c.gpus > 0) { node_upload(db, source, c); return; }
+    const auto tl = clk::now();
+    std::thread warm([&]() { (void)kmdb_device_prepare(c.device); });      // the device's first use, next to the read of the file (an error shows at the upload)
+    const int load_rc = kmdbh_db_load(source.c_str(), 2, &db.h);
+    const std::string load_err = load_rc ? kmdb_last_error() : "";
+    warm.join();
+    if (load_rc) throw std::runtime_error(load_err);
+    const double load_s = since(tl);
+    const auto tu = clk::now();
+    check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 0, &db.d));
+    std::cerr << "Database loaded in " << load_s << " s, uploaded in " << since(tu) << " s" << std::endl;
 }
 
 // The queries of a new2all run (console_new2all.cpp:64-74): read, extracted and handed on in input order, in batches of 64 queries — flushed by
@@ -1954,20 +1998,8 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
 
     std::cerr << "All versus all comparison, " << (measures.size() == 1 ? "measure " + measures[0] : std::to_string(measures.size()) + " measures") << std::endl;
     Db db;
-    std::cerr << "Loading k-mer database " << args[0] << "..." << std::endl;
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1; o.flags = KMDB_FLAG_ONE_SHOT;
-    {
-        const auto tl = clk::now();
-        std::thread warm([&]() { (void)kmdb_device_prepare(c.device); });      // the device's first use, next to the read of the file (an error shows at the upload)
-        const int load_rc = kmdbh_db_load(args[0].c_str(), 2, &db.h);
-        const std::string load_err = load_rc ? kmdb_last_error() : "";
-        warm.join();
-        if (load_rc) throw std::runtime_error(load_err);
-        const double load_s = since(tl);
-        const auto tu = clk::now();
-        check(kmdb_db_upload(kmdbh_db_view(db.h), &o, 0, &db.d));
-        std::cerr << "Database loaded in " << load_s << " s, uploaded in " << since(tu) << " s" << std::endl;
-    }
+    open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     DistanceSetup s;
     s.device = c.device; s.k = kmdbh_db_kmer_length(db.h); s.sparse_out = sparse; s.phylip = phylip;
@@ -2597,7 +2629,14 @@ void usage() {
                  "all2all-parts -distance:         the table of <measure> straight from the block rows of the grid on the GPU: the file `all2all-parts`\n"
                  "                                  followed by `distance -sparse` writes, without the table of counts in between; always the sparse form\n"
                  "                                  (-sparse changes nothing).  Several -distance and the -min / -max list as above; -gpus <W> as in\n"
-                 "                                  all2all-parts.  Refused with -sample-rows and with -phylip-out.\n";
+                 "                                  all2all-parts.  Refused with -sample-rows and with -phylip-out.\n"
+                 "    kmer-db-amd all2all | all2all-sp -from-samples [build's input switches] [-keep-db <database>] [the mode's own switches] <sample_list | fasta> <output>\n"
+                 "all2all / all2all-sp -from-samples: the samples in, the table out: the database is grown on the GPU as by build and handed to the engine in\n"
+                 "                                  HBM, no .db in between; <output> holds what build followed by the mode writes.  Build's input switches:\n"
+                 "                                  -k -f -f-start -alphabet -preserve-strand -multisample-fasta -from-minhash -host-extract -extend-from <old.db>;\n"
+                 "                                  the mode's own, -distance <measure> included, as on one GPU.  -keep-db <database> also stores the file\n"
+                 "                                  build would have written.  Refused with -gpus <N>, -from-kmers and -extend; -keep-db needs -from-samples.\n"
+                 "                                  Not offered: new2all / one2all -from-samples, all2all-parts, any -gpus.\n";
 }
 
 }  // namespace
@@ -2629,6 +2668,17 @@ int main(int argc, char** argv) {
         }
         take_switch(args, "-v");
         take_switch(args, "-vv");
+        // all2all | all2all-sp -from-samples: refused by name here, before any file is read or any device touched
+        const bool keep_db = take_option(args, "-keep-db", c.keep_db);
+        if ((mode == "all2all" || mode == "all2all-sp") && take_switch(args, "-from-samples")) {
+            if (c.gpus > 0) throw std::runtime_error("-from-samples does not go with -gpus <N>: the builder hands its database to the engine on its own device (run build, then " + mode + " -gpus)");
+            for (auto& a : args) {
+                if (a == "-from-kmers") throw std::runtime_error(KMC_REFUSAL);
+                if (a == "-extend") throw std::runtime_error("-from-samples does not go with -extend: start from a stored database with -extend-from <old.db>");
+            }
+            c.from_samples = std::make_shared<BuildInput>();
+            c.from_samples->parse(args);
+        } else if (keep_db) throw std::runtime_error("-keep-db <database> goes with all2all | all2all-sp -from-samples only: it names the file build would have written");
         if (mode == "all2all") return run_all2all(args, c);
         if (mode == "all2all-sp") return run_all2all_sp(args, c);
         if (mode == "new2all") return run_new2all(args, c);
