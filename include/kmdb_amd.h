@@ -74,6 +74,10 @@ extern "C" {
  * device by a merge-union of two ascending arrays (kmdb_sorted_union_device, kmdb_sorted_union_geometry, kmdb_minhash_long_stats_get): three
  * more entry points and one struct of their own, the version stays 8. */
 #define KMDB_HAS_LONG_SAMPLES 1
+/* And a band of the all2all matrix's rows computed alone: the cells of rows [row_lo, row_hi) and nothing else of the triangle in HBM
+ * (kmdb_all2all_rows_device, kmdb_all2all_rows, kmdb_all2all_rows_stats_get; kmdb_device_buffer_alloc, kmdb_device_buffer_free for a caller
+ * without HIP of its own): five more entry points and one struct of their own, the version stays 8. */
+#define KMDB_HAS_ALL2ALL_ROWS 1
 
 /* ---------------------------------------------------------------------------------------
  * Host-side view of a loaded database = what the reference hands to SimilarityCalculator:
@@ -264,6 +268,39 @@ int  kmdb_all2all_dense(kmdb_db* db, uint32_t* out_lower_tri, const kmdb_opts* o
 /* Same, result left in DEVICE memory (caller-owned, N(N-1)/2 uint32, need not be zeroed)
  * so that per-GPU partial matrices can be reduced with RCCL without a host round trip. */
 int  kmdb_all2all_dense_device(kmdb_db* db, void* out_lower_tri_dev, const kmdb_opts* opts);
+
+/* A band of that matrix: rows [row_lo, row_hi) alone (KMDB_HAS_ALL2ALL_ROWS).  The reference adds, for every local id of a pattern, the
+ * pattern's subtree weight to the cells of all ids in front of it on the root path (similarity_calculator.cpp:213-233): a row of the matrix is
+ * written only by the patterns that hold its sample as a LOCAL id.  The band call selects those patterns from the node arrays, rebuilds their root
+ * paths and adds their rows inside the band; no cell outside it exists anywhere.  What it serves: the new rows after a collection was extended
+ * (build -extend-from: rows [old N, N)), and a part of a matrix whose triangle does not fit.
+ * out_cells holds tri(row_hi) - tri(row_lo) uint32, tri(i) = i (i - 1) / 2 in 64 bits: cell tri(row_lo) of the lower triangle onwards — the
+ * layout kmdb_sparse_from_dense_device, kmdb_sampled_from_dense_device (cell_lo = tri(row_lo), cell_hi = tri(row_hi)) and
+ * kmdb_distance_take_cells_device (row_lo) take.  Caller-owned, need not be zeroed, written on opts->stream (the handle's own when NULL); the call
+ * returns when the cells are complete.  DEFINITION: exactly the cells [tri(row_lo), tri(row_hi)) of what kmdb_all2all_dense_device writes for the
+ * same handle (uint32, wrap-around; adds commute, so bit-exact) — a prefix shard or a tree range gives its partial band.
+ * Refused with a message: null arguments, row_lo > row_hi, row_hi > N, kmdb_opts.shard_count > 1 (a band takes the whole pattern stream), unknown
+ * flag bits (the KMDB_FLAG_FORCE_* bits are accepted and mean nothing here: there is one path), a query-shard handle, and a band of 2^32 cells
+ * or more whose bytes exceed the device's memory (kmdb_all2all_rows, which allocates the band: its free memory); the message names the bytes.
+ * An empty band (row_lo == row_hi, or row_hi <= 1) succeeds and writes nothing.
+ * Limits: a node is applied by one wave however long its list is (no node splitting); one device (a node handle has no band call). */
+typedef struct kmdb_all2all_rows_stats {   /* the LAST band call on the handle */
+    uint64_t nodes_selected;       /* nodes the select launch listed: a superset, chosen without decoding a list */
+    uint64_t nodes_applied;        /* of those, the nodes that had a local id inside the band */
+    uint64_t updates;              /* cell additions issued */
+    uint64_t band_cells;           /* tri(row_hi) - tri(row_lo) */
+    uint64_t scratch_bytes;        /* the call's working memory on the handle: node list, counters, per-wave id stacks */
+    double   select_ms;            /* HIP events around the select launch ... */
+    double   apply_ms;             /* ... and the apply launch (kmdb_stats.kernel_ms holds the whole call) */
+} kmdb_all2all_rows_stats;
+int  kmdb_all2all_rows_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts);
+/* the same with the band copied to HOST memory (the device buffer lives for the call) */
+int  kmdb_all2all_rows(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts);
+int  kmdb_all2all_rows_stats_get(const kmdb_db* db, kmdb_all2all_rows_stats* out);
+/* `bytes` of device memory on `device` for a caller that links no HIP runtime (the command-line front-end holds the band of -rows in it between
+ * kmdb_all2all_rows_device and the calls that read it); not zeroed; freed with kmdb_device_buffer_free (a null pointer is ignored). */
+int  kmdb_device_buffer_alloc(int32_t device, uint64_t bytes, void** out);
+void kmdb_device_buffer_free(int32_t device, void* p);
 
 /* Replaces SimilarityCalculator::all2all_sp(db, SparseMatrix&, CBubbleHelper&) followed by
  * SparseMatrix::compact2 with pass-all filters (similarity_calculator.cpp:442-657,

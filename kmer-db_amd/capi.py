@@ -133,6 +133,11 @@ class _DistancePartsStats(C.Structure):
                 ("peak_bytes", C.c_uint64), ("gather_ms", C.c_double)]
 
 
+class _All2allRowsStats(C.Structure):
+    _fields_ = [("nodes_selected", C.c_uint64), ("nodes_applied", C.c_uint64), ("updates", C.c_uint64), ("band_cells", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("select_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -175,6 +180,7 @@ EXPORTS = [
     "kmdb_distance_take_new2all_batch", "kmdb_distance_take_new2all_batch_seq_alphabet", "kmdb_distance_take_rows_device", "kmdb_distance_query_rows",
     "kmdb_distance_parts_begin_rows", "kmdb_distance_parts_add_db2db", "kmdb_distance_parts_add_all2all", "kmdb_distance_parts_add_csr_device", "kmdb_distance_take_csr_device", "kmdb_distance_csr_rows",
     "kmdb_distance_csr_device", "kmdb_distance_csr_row_ptr", "kmdb_distance_parts_stats_get",
+    "kmdb_all2all_rows_device", "kmdb_all2all_rows", "kmdb_all2all_rows_stats_get", "kmdb_device_buffer_alloc", "kmdb_device_buffer_free",
 ]
 
 
@@ -223,6 +229,12 @@ def lib():
     L.kmdb_node_all2all_sparse.argtypes = [C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_all2all_dense.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_all2all_dense_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsStats)]
+    L.kmdb_device_buffer_alloc.argtypes = [C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.kmdb_device_buffer_free.restype = None
+    L.kmdb_device_buffer_free.argtypes = [C.c_int32, C.c_void_p]
     L.kmdb_all2all_sparse.argtypes = [C.c_void_p, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_all2all_sparse_filtered.argtypes = [C.c_void_p, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_sparse_from_dense_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int,
@@ -673,6 +685,28 @@ class DeviceDB:
         """Result stays in device memory at dev_ptr (e.g. torch tensor .data_ptr())."""
         o = _opts(self.device, shard, flags, stream)
         _check(lib().kmdb_all2all_dense_device(self._d, C.c_void_p(dev_ptr), C.byref(o)))
+
+    def all2all_rows(self, row_lo, row_hi, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows: rows [row_lo, row_hi) of the matrix alone — the cells tri(row_lo) .. tri(row_hi) of the lower triangle, tri(i) =
+        i (i - 1) / 2, as a numpy uint32 array; nothing else of the triangle is computed or held anywhere"""
+        lo, hi = int(row_lo), int(row_hi)
+        cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
+        out = np.zeros(max(1, cells), dtype=np.uint32)
+        o = _opts(self.device, shard, flags)
+        _check(lib().kmdb_all2all_rows(self._d, lo, hi, out.ctypes.data, C.byref(o)))
+        return out[:cells]
+
+    def all2all_rows_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows_device: the same band left in device memory at dev_ptr (e.g. a torch tensor's .data_ptr()): the layout
+        sparse_from_dense_device (cell_lo = tri(row_lo), cell_hi = tri(row_hi)) and Distance.take_cells (row_lo) take"""
+        o = _opts(self.device, shard, flags, stream)
+        _check(lib().kmdb_all2all_rows_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+
+    def all2all_rows_stats(self):
+        """kmdb_all2all_rows_stats_get: the last band call on the handle"""
+        s = _All2allRowsStats()
+        _check(lib().kmdb_all2all_rows_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allRowsStats._fields_}
 
     def all2all_sparse(self, shard=(0, 1)):
         raw = _Sparse()

@@ -110,6 +110,11 @@ int kmdb_sample_query_rows(const char* who, hipStream_t st, int kmer_length, con
                            const uint32_t* query_kmers, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers, int criterion, uint32_t count,
                            kmdb_sparse_rows* out, kmdb_sample_stats* stats);
 
+// ---- a band of the matrix's rows (a2a_rows.hip: kmdb_all2all_rows_device / kmdb_all2all_rows / kmdb_all2all_rows_stats_get of include/kmdb_amd.h).
+// Tree form on the node arrays of kmdb_ensure_v1_arrays: a select launch (a lane per node) and an apply launch (a fixed grid of waves over the
+// selected nodes) that add the cells [tri(row_lo), tri(row_hi)) and no other; the id stacks are the handle's stack_scratch, shared with a2a_v1.hip.
+constexpr int KMDB_ROWS_LDS_CAP = 1024;   // a full list of up to this many ids is rebuilt on the wave's LDS stack, a longer one in global scratch
+
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},
 // d = 32 - key_bits - 2; slots never written carry the key 0xFFFFFFFF.

@@ -1,6 +1,6 @@
 // engine_state.h — the HBM-resident database shared by the translation units of libkmdb_amd.so
-// (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, node_arrays.hip: the node
-// arrays of the v1 kernels and of new2all).
+// (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, a2a_rows.hip: a band of
+// the matrix's rows, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
 #pragma once
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
@@ -88,6 +88,11 @@ struct kmdb_db {
     DevBuf<uint32_t> stack_scratch;     // global kernel: per-wave id stacks
     size_t stack_scratch_words = 0;
     DevBuf<unsigned long long> v1_counters;      // [0] tile flushes
+    // ---- a band of rows (a2a_rows.hip): made on the first band call of the handle; the id stacks are stack_scratch above
+    DevBuf<uint32_t> rows_sel;          // [P] the nodes selected by the last band call
+    DevBuf<unsigned long long> rows_counters;    // [0] nodes selected, [1] nodes with a band row, [2] cell additions
+    uint64_t rows_bytes_counted = 0;    // the two arrays' share of stats.device_bytes as last counted
+    kmdb_all2all_rows_stats rows_stats{};        // the last band call on the handle (kmdb_all2all_rows_stats_get)
     // hashtables (new2all)
     uint64_t n_buckets = 0;
     DevBuf<uint64_t> bucket_offset;

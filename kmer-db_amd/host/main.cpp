@@ -4,6 +4,7 @@
 //     kmer-db-amd all2all    [-sparse [-min [m:]v] [-max [m:]v]] <db> <out.csv>
 //     kmer-db-amd all2all-sp [-min [m:]v] [-max [m:]v]           <db> <out.csv>
 //     kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <out>
+//     kmer-db-amd all2all | all2all-sp -rows <lo>:<hi> | new [the forms above] <db> <out>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <sample-list> <out>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
@@ -202,8 +203,57 @@ struct Db {
     ~Db() { if (dropper.joinable()) dropper.join(); if (node) kmdb_node_free(node); if (d) kmdb_db_free(d); if (h) kmdbh_db_free(h); }
 };
 
+// -rows <lo>:<hi> | new (all2all, all2all-sp): only the lines of samples lo .. hi - 1 of the table, from a band of the matrix computed alone
+// (kmdb_all2all_rows_device; reference similarity_calculator.cpp:213-233 adds a row only from the patterns that hold its sample as a local id).
+// 0-based sample indices, either side may be empty; `new` (with -from-samples -extend-from <old.db>): from the sample count of <old.db> to N.
+struct RowBand {
+    bool on = false, is_new = false, lo_open = false, hi_open = false;
+    uint64_t lo = 0, hi = 0;
+    void parse(const std::string& v) {
+        on = true;
+        if (v == "new") { is_new = true; return; }
+        const std::string what = "-rows expects <lo>:<hi> (0-based sample indices, either side may be empty) or new: " + v;
+        const size_t sep = v.find(':');
+        if (sep == std::string::npos || v.find(':', sep + 1) != std::string::npos) throw std::runtime_error(what);
+        auto side = [&](const std::string& t, bool& open, uint64_t& x) {
+            open = t.empty();
+            if (t.size() > 18 || t.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error(what);
+            if (!open) x = std::strtoull(t.c_str(), nullptr, 10);
+        };
+        side(v.substr(0, sep), lo_open, lo);
+        side(v.substr(sep + 1), hi_open, hi);
+        if (!lo_open && !hi_open && lo > hi) throw std::runtime_error("-rows " + v + ": lo > hi");
+    }
+    // the band of a collection of n samples (seed_samples: those of -extend-from's database); refused: hi > n
+    void resolve(uint64_t n, uint64_t seed_samples, uint64_t& r_lo, uint64_t& r_hi) const {
+        r_lo = is_new ? seed_samples : lo_open ? 0 : lo;
+        r_hi = is_new || hi_open ? n : hi;
+        if (r_hi > n) throw std::runtime_error("-rows: " + std::to_string(r_hi) + " is beyond the " + std::to_string(n) + " samples of the database");
+        if (r_lo > r_hi) throw std::runtime_error("-rows: lo > hi (" + std::to_string(r_lo) + " > " + std::to_string(r_hi) + ") with the " + std::to_string(n) + " samples of the database");
+    }
+};
+uint64_t tri(uint64_t i) { return i ? i * (i - 1) / 2 : 0; }
+// the band in device memory, for the calls that read it there
+struct DeviceBand {
+    int device = 0;
+    void* p = nullptr;
+    DeviceBand(int dev, uint64_t cells) : device(dev) { if (kmdb_device_buffer_alloc(dev, std::max<uint64_t>(cells, 1) * 4, &p)) throw std::runtime_error(kmdb_last_error()); }
+    ~DeviceBand() { if (p) kmdb_device_buffer_free(device, p); }
+    DeviceBand(const DeviceBand&) = delete;
+    DeviceBand& operator=(const DeviceBand&) = delete;
+};
+// KMDB_VERBOSE: what the last band call on the handle did
+void report_rows_stats(const kmdb_db* d) {
+    kmdb_all2all_rows_stats rs{};
+    if (!std::getenv("KMDB_VERBOSE") || kmdb_all2all_rows_stats_get(d, &rs)) return;
+    std::cerr << "[kmdb] all2all rows: " << rs.band_cells << " cells, nodes selected / applied / updates " << rs.nodes_selected << " / " << rs.nodes_applied << " / "
+              << rs.updates << ", select " << rs.select_ms << " ms, apply " << rs.apply_ms << " ms, " << rs.scratch_bytes << " bytes of scratch" << std::endl;
+}
+
 struct BuildInput;
 struct Common {
+    RowBand rows;                            // all2all | all2all-sp -rows
+    uint64_t seed_samples = 0;               // -from-samples -extend-from <old.db>: the samples of <old.db> (set by open_database)
     std::shared_ptr<BuildInput> from_samples;     // all2all | all2all-sp -from-samples: build's input switches; the "database" argument is the sample list
     std::string keep_db;                     // -keep-db <database>: the file `build` would have written, stored next to the table
     int threads = 0;
@@ -309,6 +359,54 @@ int run_new2all_distance(std::vector<std::string>& args, Common& c, const std::v
 // rest of the run reads of it on the host — names, k-mer counts, k, fraction
 void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts& o);
 
+// all2all -sparse | all2all-sp with -rows: the band is accumulated and compacted where it lies (kmdb_all2all_rows_device, then
+// kmdb_sparse_from_dense_device on the cells [tri(lo), tri(hi))), the host applies every bound again as the full run does, and the header and the
+// lines of samples lo .. hi - 1 are written.  Neither the triangle nor the band exists on the host.
+int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs, const std::string& path, uint64_t lo, uint64_t hi) {
+    const uint64_t n = kmdbh_db_n_samples(db.h);
+    const int k = (int)kmdbh_db_kmer_length(db.h);
+    std::cerr << "Calculating rows " << lo << " to " << hi << " of the matrix of common k-mers...";
+    auto t0 = clk::now();
+    kmdb_sparse_rows sp{};
+    {
+        std::vector<kmdb_cell_filter> fl;
+        for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+        if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
+            fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+        if (fl.size() > 8) fl.clear();                          // (the host-side pass below applies every bound anyway)
+        std::vector<uint32_t> counts(std::max<uint64_t>(n, 1));
+        for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
+        DeviceBand band(c.device, tri(hi) - tri(lo));
+        check(kmdb_all2all_rows_device(db.d, lo, hi, band.p, &o));
+        report_rows_stats(db.d);
+        check(kmdb_sparse_from_dense_device(db.d, band.p, tri(lo), tri(hi), fl.data(), fl.size(), counts.data(), -1, &sp, &o));
+    }
+    std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+    db.uploaded();
+    std::cerr << "Storing rows of the matrix of common k-mers in " << path << "...";
+    t0 = clk::now();
+    write_header(db, ofs);
+    std::vector<char> row(10000 + n * 100);
+    std::vector<uint32_t> cols, vals;
+    size_t saved = 0;
+    for (uint64_t i = lo; i < hi; ++i) {
+        cols.clear(); vals.clear();
+        for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
+            if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
+                cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
+            }
+        const char* name = kmdbh_db_sample_name(db.h, i);
+        if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
+        size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
+        ofs.write(row.data(), (std::streamsize)len);
+        saved += cols.size();
+    }
+    kmdb_sparse_free(&sp);
+    std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+    std::cerr << "No. saved pairs: " << saved << std::endl;
+    return finish(db, ofs, path);
+}
+
 // ---- all2all (console_all2all.cpp:7-89) -----------------------------------------------------------
 int run_all2all(std::vector<std::string>& args, Common& c) {
     std::string v;
@@ -326,11 +424,18 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
+    uint64_t r_lo = 0, r_hi = n;                                 // the rows written: all of them, or the band of -rows
+    if (c.rows.on) c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
+    if (c.rows.on && c.sparse) return write_sparse_band(db, c, o, ofs, args[1], r_lo, r_hi);
+    const uint64_t cell_lo = tri(r_lo);                          // m holds the cells from here on
     std::cerr << "Calculating matrix of common k-mers..." << std::endl;
     auto t0 = clk::now();
-    std::vector<uint32_t> m(n ? n * (n - 1) / 2 + 1 : 1);
+    std::vector<uint32_t> m(tri(r_hi) - cell_lo + 1);
     if (db.node) { check(kmdb_node_all2all_dense(db.node, m.data(), nullptr)); node_report(db); }
-    else {
+    else if (c.rows.on) {
+        check(kmdb_all2all_rows(db.d, r_lo, r_hi, m.data(), &o));
+        report_rows_stats(db.d);
+    } else {
         check(kmdb_all2all_dense(db.d, m.data(), &o));
         kmdb_stats st{};
         if (!kmdb_db_stats(db.d, &st) && st.path == KMDB_PATH_GLOBAL)
@@ -346,9 +451,9 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     const int nthr = (int)std::max<size_t>(1, std::min<size_t>(c.threads > 0 ? (size_t)c.threads : 16, std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 1));
     size_t name_max = 0;
     for (uint64_t i = 0; i < n; ++i) name_max = std::max(name_max, std::strlen(kmdbh_db_sample_name(db.h, i)));
-    for (uint64_t i0 = 0; i0 < n;) {
+    for (uint64_t i0 = r_lo; i0 < r_hi;) {
         uint64_t i1 = i0, cells_in = 0;
-        while (i1 < n && (i1 == i0 || cells_in + i1 <= (32u << 20))) { cells_in += i1; ++i1; }
+        while (i1 < r_hi && (i1 == i0 || cells_in + i1 <= (32u << 20))) { cells_in += i1; ++i1; }
         std::vector<std::vector<char>> text(nthr);
         std::atomic<int> failed{0};
         auto work = [&](int t) {
@@ -363,7 +468,7 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
             std::vector<uint32_t> cols, vals;
             size_t used = 0;
             for (uint64_t i = a; i < b; ++i) {
-                const uint32_t* r = m.data() + i * (i - 1) / 2;
+                const uint32_t* r = m.data() + (tri(i) - cell_lo);
                 const char* name = kmdbh_db_sample_name(db.h, i);
                 const size_t need = 64 + name_max + i * (c.sparse ? 22 : 11);
                 if (out.size() < used + need) out.resize(std::max(out.size() * 2, used + need));
@@ -411,6 +516,11 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
+    if (c.rows.on) {
+        uint64_t r_lo = 0, r_hi = n;
+        c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
+        return write_sparse_band(db, c, o, ofs, args[1], r_lo, r_hi);
+    }
     std::cerr << "Calculating matrix of common k-mers...";
     auto t0 = clk::now();
     kmdb_sparse_rows sp{};
@@ -1246,6 +1356,8 @@ void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts
         std::cerr << "Building database (from " << (in.from_minhash ? "minhashed k-mers" : "fasta genomes") << ")" << std::endl;
         BuilderHold bld;
         build_feed(in, source, c, bld);
+        kmdb_build_seed_stats seed{};
+        if (in.extend && !kmdb_build_seed_stats_get(bld.b, &seed)) c.seed_samples = seed.samples;      // (-rows new starts here)
         const auto tu = clk::now();
         const bool keep = !c.keep_db.empty();
         check(kmdb_build_finish_device(bld.b, &o, 0, keep ? 1 : 0, &db.d, &db.h));
@@ -2001,6 +2113,10 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
     kmdb_opts o{}; o.abi_version = KMDB_ABI_VERSION; o.device = c.device; o.shard_count = 1; o.flags = KMDB_FLAG_ONE_SHOT;
     open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
+    // -rows: the band is computed once into memory this run holds, every measure's handle borrows it from its first row on and only its rows are asked for
+    uint64_t r_lo = 0, r_hi = n;
+    if (c.rows.on) c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
+    std::unique_ptr<DeviceBand> band;
     DistanceSetup s;
     s.device = c.device; s.k = kmdbh_db_kmer_length(db.h); s.sparse_out = sparse; s.phylip = phylip;
     s.counts.resize(n);
@@ -2018,7 +2134,18 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
         DistanceHandle borrower;
         DistanceHandle& h = mi == 0 ? owner : borrower;
         h.begin(s, flags);
-        if (mi == 0) {
+        if (c.rows.on) {
+            if (!band) {
+                std::cerr << "Calculating rows " << r_lo << " to " << r_hi << " of the matrix of common k-mers..." << std::endl;
+                const auto t0 = clk::now();
+                band.reset(new DeviceBand(c.device, tri(r_hi) - tri(r_lo)));
+                check(kmdb_all2all_rows_device(db.d, r_lo, r_hi, band->p, &o));
+                report_rows_stats(db.d);
+                std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+                db.uploaded();
+            }
+            check(kmdb_distance_take_cells_device(h.d, band->p, r_lo, names.data()));
+        } else if (mi == 0) {
             std::cerr << "Calculating matrix of common k-mers..." << std::endl;
             const auto t0 = clk::now();
             check(kmdb_distance_take_all2all(h.d, db.d, names.data(), &o));
@@ -2037,9 +2164,9 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
         w->start();
         std::string error;
         try {
-            for (uint64_t i0 = 0; i0 < n;) {
+            for (uint64_t i0 = r_lo; i0 < r_hi;) {
                 uint64_t i1 = i0, cells = 0;
-                while (i1 < n && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+                while (i1 < r_hi && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
                 kmdb_distance_out piece{};
                 check(kmdb_distance_matrix_rows(h.d, i0, i1, &piece));
                 if (!w->push(piece)) break;
@@ -2636,7 +2763,14 @@ void usage() {
                  "                                  -k -f -f-start -alphabet -preserve-strand -multisample-fasta -from-minhash -host-extract -extend-from <old.db>;\n"
                  "                                  the mode's own, -distance <measure> included, as on one GPU.  -keep-db <database> also stores the file\n"
                  "                                  build would have written.  Refused with -gpus <N>, -from-kmers and -extend; -keep-db needs -from-samples.\n"
-                 "                                  Not offered: new2all / one2all -from-samples, all2all-parts, any -gpus.\n";
+                 "                                  Not offered: new2all / one2all -from-samples, all2all-parts, any -gpus.\n"
+                 "    kmer-db-amd all2all | all2all-sp -rows <lo>:<hi> [the mode's own switches] <database> <output>\n"
+                 "all2all / all2all-sp -rows <lo>:<hi>: only the rows of samples lo .. hi - 1 (0-based, either side may be empty: 100: is 100 to N) are computed,\n"
+                 "                                  as a band of the matrix of its own on the GPU; <output> holds the header lines of the full run and exactly\n"
+                 "                                  its lines of those samples.  Dense, -sparse / all2all-sp with the -min / -max list, and -distance <measure>.\n"
+                 "                                  -rows new (with -from-samples -extend-from <old.db>): the rows of the samples added to <old.db>.\n"
+                 "                                  Refused with -gpus <N>, -sample-rows and -phylip-out, and when hi exceeds the sample count.  Not offered:\n"
+                 "                                  a whole run walked in bands (-band-rows), a long pattern split over several waves.\n";
 }
 
 }  // namespace
@@ -2679,6 +2813,18 @@ int main(int argc, char** argv) {
             c.from_samples = std::make_shared<BuildInput>();
             c.from_samples->parse(args);
         } else if (keep_db) throw std::runtime_error("-keep-db <database> goes with all2all | all2all-sp -from-samples only: it names the file build would have written");
+        // -rows <lo>:<hi> | new: what it does not go with is refused by name here, before any file is read or any device touched
+        if (take_option(args, "-rows", v)) {
+            if (mode != "all2all" && mode != "all2all-sp") throw std::runtime_error("-rows applies to all2all and all2all-sp");
+            if (c.gpus > 0) throw std::runtime_error("-rows does not go with -gpus <N>: a band is computed on one device from the whole pattern tree");
+            for (auto& a : args) {
+                if (a == "-sample-rows") throw std::runtime_error("-rows does not go with -sample-rows: a pair is offered to both its samples, so a band of rows does not hold a sample's candidates");
+                if (a == "-phylip-out") throw std::runtime_error("-rows does not go with -phylip-out: a phylip table is a whole triangle");
+            }
+            c.rows.parse(v);
+            if (c.rows.is_new && !(c.from_samples && c.from_samples->extend))
+                throw std::runtime_error("-rows new goes with -from-samples -extend-from <old.db> only: it means the rows of the samples added to <old.db>");
+        }
         if (mode == "all2all") return run_all2all(args, c);
         if (mode == "all2all-sp") return run_all2all_sp(args, c);
         if (mode == "new2all") return run_new2all(args, c);
