@@ -302,6 +302,34 @@ int  kmdb_all2all_rows_stats_get(const kmdb_db* db, kmdb_all2all_rows_stats* out
 int  kmdb_device_buffer_alloc(int32_t device, uint64_t bytes, void** out);
 void kmdb_device_buffer_free(int32_t device, void* p);
 
+/* The same band, its rows summed in LDS tiles (KMDB_HAS_ALL2ALL_ROWS_TILED; a2a_band.hip).  DEFINITION: bit for bit what kmdb_all2all_rows_device
+ * writes for the same arguments.  Row r is written only by the nodes that hold r as a local id; such a node (a "hit" of row r) adds its subtree
+ * weight W to column c for every id c < r of its root path.  A job is (row r, a tile of KMDB_ROWS_TILE_COLS columns in front of r, a share of at
+ * most KMDB_ROWS_TILE_HITS of the row's hits): one workgroup holds the tile as uint32 words in LDS, enters every run of consecutive ids [s, s + len)
+ * of the hits' root paths as +W at s and -W (modulo 2^32) at s + len, takes one inclusive prefix sum over the tile and adds every non-zero cell to
+ * the band once.  Both switches are read at every call: KMDB_ROWS_TILE_COLS a multiple of 64 from 64 to 40896 (160 KiB of LDS less the scan's
+ * words), KMDB_ROWS_TILE_HITS 1 or more; anything else is refused.  Refusals as for kmdb_all2all_rows_device / kmdb_all2all_rows, under these names;
+ * an empty band succeeds and writes nothing.
+ * Limits: the list of one node is decoded by one lane per hit however long it is (no wave-cooperative decode); one device. */
+#define KMDB_HAS_ALL2ALL_ROWS_TILED 1
+typedef struct kmdb_all2all_rows_tiled_stats {   /* the LAST tiled band call on the handle */
+    uint64_t nodes_selected;       /* nodes the select launch listed: the superset rule of the band call above */
+    uint64_t nodes_applied;        /* of those, the nodes that had a local id inside the band */
+    uint64_t hits;                 /* (row, node) records: local ids inside the band of the nodes selected */
+    uint64_t jobs;                 /* workgroups of the apply launch: (row, column tile, share of the row's hits) */
+    uint64_t runs;                 /* runs entered into a tile, clipped to it and to the row: a pair of LDS adds each (the closing one may be left out) */
+    uint64_t updates;              /* cell additions the runs stand for: equal to kmdb_all2all_rows_stats.updates of the same band */
+    uint64_t tile_cols;            /* columns of a tile at this call */
+    uint64_t band_cells;           /* tri(row_hi) - tri(row_lo) */
+    double   select_ms;            /* HIP events around the select launch, ... */
+    double   hits_ms;              /* ... the hit passes and the job table (two host round trips inside), ... */
+    double   apply_ms;             /* ... and the apply launch (kmdb_stats.kernel_ms holds the whole call) */
+    uint64_t scratch_bytes;        /* the call's working memory on the handle: node list, counters, per-row tables, hit records, job table */
+} kmdb_all2all_rows_tiled_stats;
+int  kmdb_all2all_rows_tiled_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts);
+int  kmdb_all2all_rows_tiled(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts);
+int  kmdb_all2all_rows_tiled_stats_get(const kmdb_db* db, kmdb_all2all_rows_tiled_stats* out);
+
 /* Replaces SimilarityCalculator::all2all_sp(db, SparseMatrix&, CBubbleHelper&) followed by
  * SparseMatrix::compact2 with pass-all filters (similarity_calculator.cpp:442-657,
  * array.h:391-446; call sites console_all2all_sparse.cpp:44,79). */
@@ -330,6 +358,21 @@ int  kmdb_sparse_from_dense_device(kmdb_db* db, const void* cells_dev, uint64_t 
 /* NOTE on streams: the call reads cells_dev on opts->stream (the handle's own stream when NULL) and does NOT order itself after
  * the caller's producer: the cells must be complete on that stream (or the device idle) before the call — after an RCCL collective
  * on another stream, wait for it first (hipStreamWaitEvent / hipStreamSynchronize). */
+/* kmdb_all2all_sparse_filtered walked in bands of band_rows rows (KMDB_HAS_ALL2ALL_ROWS_TILED): for every band [k R, min((k + 1) R, N)) one band
+ * buffer — the largest band's, made once — is filled by the tiled band call and compacted where it lies (kmdb_sparse_from_dense_device on the cells
+ * [tri(lo), tri(hi))); its rows are appended to the result.  Only one band is ever resident: the way of one device to a collection whose triangle
+ * does not fit (300 000 samples are 180 GB).  DEFINITION: row_ptr, col, val and measure equal to kmdb_all2all_sparse_filtered's for the same
+ * arguments.  Refused: band_rows == 0, and everything the two composed calls refuse. */
+typedef struct kmdb_all2all_banded_stats {   /* the LAST banded call on the handle */
+    uint64_t bands;
+    uint64_t max_band_bytes;       /* the band buffer: the largest band's cells, 4 bytes each */
+    uint64_t peak_device_bytes;    /* the largest kmdb_stats.device_bytes + band buffer + tiled scratch over the bands */
+    uint64_t hits, runs, updates;  /* sums over the bands of kmdb_all2all_rows_tiled_stats */
+    double   select_ms, hits_ms, apply_ms;
+} kmdb_all2all_banded_stats;
+int  kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_rows, const kmdb_cell_filter* filters, size_t n_filters,
+                                         const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
+int  kmdb_all2all_banded_stats_get(const kmdb_db* db, kmdb_all2all_banded_stats* out);
 /* ---------------------------------------------------------------------------------------
  * all2all-sp -sample-rows <criterion>:<count> (params.cpp:533-557): every sample keeps its `count` best neighbours.  A pair (i, j), i > j, with
  * a non-zero cell that passes the filters has ONE score, metric(cell, kmers[i], kmers[j], k) with the triangle's row i as the row sample, and is

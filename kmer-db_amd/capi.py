@@ -138,6 +138,17 @@ class _All2allRowsStats(C.Structure):
                 ("scratch_bytes", C.c_uint64), ("select_ms", C.c_double), ("apply_ms", C.c_double)]
 
 
+class _All2allRowsTiledStats(C.Structure):
+    _fields_ = [("nodes_selected", C.c_uint64), ("nodes_applied", C.c_uint64), ("hits", C.c_uint64), ("jobs", C.c_uint64), ("runs", C.c_uint64),
+                ("updates", C.c_uint64), ("tile_cols", C.c_uint64), ("band_cells", C.c_uint64), ("select_ms", C.c_double), ("hits_ms", C.c_double),
+                ("apply_ms", C.c_double), ("scratch_bytes", C.c_uint64)]
+
+
+class _All2allBandedStats(C.Structure):
+    _fields_ = [("bands", C.c_uint64), ("max_band_bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64), ("hits", C.c_uint64), ("runs", C.c_uint64),
+                ("updates", C.c_uint64), ("select_ms", C.c_double), ("hits_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -181,6 +192,7 @@ EXPORTS = [
     "kmdb_distance_parts_begin_rows", "kmdb_distance_parts_add_db2db", "kmdb_distance_parts_add_all2all", "kmdb_distance_parts_add_csr_device", "kmdb_distance_take_csr_device", "kmdb_distance_csr_rows",
     "kmdb_distance_csr_device", "kmdb_distance_csr_row_ptr", "kmdb_distance_parts_stats_get",
     "kmdb_all2all_rows_device", "kmdb_all2all_rows", "kmdb_all2all_rows_stats_get", "kmdb_device_buffer_alloc", "kmdb_device_buffer_free",
+    "kmdb_all2all_rows_tiled_device", "kmdb_all2all_rows_tiled", "kmdb_all2all_rows_tiled_stats_get", "kmdb_all2all_sparse_filtered_banded", "kmdb_all2all_banded_stats_get",
 ]
 
 
@@ -232,6 +244,11 @@ def lib():
     L.kmdb_all2all_rows_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_all2all_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
     L.kmdb_all2all_rows_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsStats)]
+    L.kmdb_all2all_rows_tiled_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_tiled.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_tiled_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsTiledStats)]
+    L.kmdb_all2all_sparse_filtered_banded.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
+    L.kmdb_all2all_banded_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allBandedStats)]
     L.kmdb_device_buffer_alloc.argtypes = [C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
     L.kmdb_device_buffer_free.restype = None
     L.kmdb_device_buffer_free.argtypes = [C.c_int32, C.c_void_p]
@@ -707,6 +724,50 @@ class DeviceDB:
         s = _All2allRowsStats()
         _check(lib().kmdb_all2all_rows_stats_get(self._d, C.byref(s)))
         return {f: getattr(s, f) for f, _ in _All2allRowsStats._fields_}
+
+    def all2all_rows_tiled(self, row_lo, row_hi, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows_tiled: the band of all2all_rows, bit for bit, its rows summed in LDS tiles (KMDB_ROWS_TILE_COLS, KMDB_ROWS_TILE_HITS)"""
+        lo, hi = int(row_lo), int(row_hi)
+        cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
+        out = np.zeros(max(1, cells), dtype=np.uint32)
+        o = _opts(self.device, shard, flags)
+        _check(lib().kmdb_all2all_rows_tiled(self._d, lo, hi, out.ctypes.data, C.byref(o)))
+        return out[:cells]
+
+    def all2all_rows_tiled_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows_tiled_device: the same band left in device memory at dev_ptr, the layout of all2all_rows_device"""
+        o = _opts(self.device, shard, flags, stream)
+        _check(lib().kmdb_all2all_rows_tiled_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+
+    def all2all_rows_tiled_stats(self):
+        """kmdb_all2all_rows_tiled_stats_get: the last tiled band call on the handle"""
+        s = _All2allRowsTiledStats()
+        _check(lib().kmdb_all2all_rows_tiled_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allRowsTiledStats._fields_}
+
+    def all2all_sparse_filtered_banded(self, band_rows, filters, sample_kmers, measure=None, shard=(0, 1)):
+        """kmdb_all2all_sparse_filtered_banded: all2all_sparse_filtered walked in bands of band_rows rows — one band resident at a time, the same
+        SparseRows"""
+        raw = _Sparse()
+        o = _opts(self.device, shard)
+        fs = (_CellFilter * max(1, len(filters)))()
+        for i, (name, lo, hi) in enumerate(filters):
+            fs[i].metric = METRICS.index(name)
+            fs[i].lo = -np.finfo(np.float64).max if lo is None else lo
+            fs[i].hi = np.finfo(np.float64).max if hi is None else hi
+        cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
+        _check(lib().kmdb_all2all_sparse_filtered_banded(self._d, int(band_rows), fs, len(filters), None if cnt is None else cnt.ctypes.data,
+                                                         -1 if measure is None else METRICS.index(measure), C.byref(raw), C.byref(o)))
+        try:
+            return SparseRows(raw)
+        finally:
+            lib().kmdb_sparse_free(C.byref(raw))
+
+    def all2all_banded_stats(self):
+        """kmdb_all2all_banded_stats_get: the last banded call on the handle"""
+        s = _All2allBandedStats()
+        _check(lib().kmdb_all2all_banded_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allBandedStats._fields_}
 
     def all2all_sparse(self, shard=(0, 1)):
         raw = _Sparse()

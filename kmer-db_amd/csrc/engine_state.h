@@ -1,6 +1,6 @@
 // engine_state.h — the HBM-resident database shared by the translation units of libkmdb_amd.so
 // (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, a2a_rows.hip: a band of
-// the matrix's rows, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
+// the matrix's rows, a2a_band.hip: the same band summed in LDS tiles and a run walked in bands, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
 #pragma once
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
@@ -93,6 +93,21 @@ struct kmdb_db {
     DevBuf<unsigned long long> rows_counters;    // [0] nodes selected, [1] nodes with a band row, [2] cell additions
     uint64_t rows_bytes_counted = 0;    // the two arrays' share of stats.device_bytes as last counted
     kmdb_all2all_rows_stats rows_stats{};        // the last band call on the handle (kmdb_all2all_rows_stats_get)
+    // ---- the tiled band call (a2a_band.hip): made on the first tiled call of the handle, grown when a call needs more
+    DevBuf<uint32_t> band_sel;          // [P] the nodes selected by the last tiled call
+    DevBuf<unsigned long long> band_counters;    // [0] nodes selected, [1] nodes with a hit, [2] hits, [3] runs, [4] cell additions
+    DevBuf<uint32_t> band_rows;         // [3][rows + 1] per row of the band: hit count, its exclusive sum, the write cursor
+    uint64_t band_rows_cap = 0;         // rows + 1 the three tables hold
+    DevBuf<uint32_t> band_hits;         // [hits] the node of every hit, grouped by row
+    uint64_t band_hits_cap = 0;
+    DevBuf<uint4> band_jobs;            // [jobs] {row, first column of the tile, first hit, hits}
+    uint64_t band_jobs_cap = 0;
+    DevBuf<void> band_scan_tmp;         // rocPRIM's temporary storage for the scan of the hit counts
+    size_t band_scan_tmp_bytes = 0;
+    DevEvent band_ev;                   // between the hit passes and the apply launch (ev[0 .. 3] are the call's other marks)
+    uint64_t band_bytes_counted = 0;    // these arrays' share of stats.device_bytes as last counted
+    kmdb_all2all_rows_tiled_stats band_stats{};  // the last tiled call on the handle (kmdb_all2all_rows_tiled_stats_get)
+    kmdb_all2all_banded_stats banded_stats{};    // the last banded call on the handle (kmdb_all2all_banded_stats_get)
     // hashtables (new2all)
     uint64_t n_buckets = 0;
     DevBuf<uint64_t> bucket_offset;

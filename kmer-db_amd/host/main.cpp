@@ -5,6 +5,7 @@
 //     kmer-db-amd all2all-sp [-min [m:]v] [-max [m:]v]           <db> <out.csv>
 //     kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <out>
 //     kmer-db-amd all2all | all2all-sp -rows <lo>:<hi> | new [the forms above] <db> <out>
+//     kmer-db-amd all2all | all2all-sp -band-rows <R> [the forms above] <db> <out>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <sample-list> <out>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
@@ -250,9 +251,43 @@ void report_rows_stats(const kmdb_db* d) {
               << rs.updates << ", select " << rs.select_ms << " ms, apply " << rs.apply_ms << " ms, " << rs.scratch_bytes << " bytes of scratch" << std::endl;
 }
 
+// the same for the tiled band call
+void report_rows_tiled_stats(const kmdb_db* d, uint64_t lo, uint64_t hi) {
+    kmdb_all2all_rows_tiled_stats bs{};
+    if (!std::getenv("KMDB_VERBOSE") || kmdb_all2all_rows_tiled_stats_get(d, &bs)) return;
+    std::cerr << "[kmdb] all2all rows tiled: rows " << lo << " to " << hi << ", " << bs.band_cells << " cells, nodes selected / applied " << bs.nodes_selected << " / "
+              << bs.nodes_applied << ", hits / jobs / runs / updates " << bs.hits << " / " << bs.jobs << " / " << bs.runs << " / " << bs.updates << ", tiles of "
+              << bs.tile_cols << " columns, select " << bs.select_ms << " ms, hits " << bs.hits_ms << " ms, apply " << bs.apply_ms << " ms, " << bs.scratch_bytes
+              << " bytes of scratch" << std::endl;
+}
+// -band-rows <R>: a number of rows, 1 or more
+uint64_t parse_band_rows(const std::string& v) {
+    if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos || std::strtoull(v.c_str(), nullptr, 10) == 0)
+        throw std::runtime_error("-band-rows expects <R>, a number of rows of 1 or more: " + v);
+    return std::strtoull(v.c_str(), nullptr, 10);
+}
+// the largest band of [lo, hi) walked R rows at a time, in cells
+uint64_t largest_band_cells(uint64_t lo, uint64_t hi, uint64_t R) {
+    uint64_t cells = 0;
+    for (uint64_t b = lo; b < hi; b += std::min(R, hi - b)) cells = std::max(cells, tri(b + std::min(R, hi - b)) - tri(b));
+    return cells;
+}
+
 struct BuildInput;
 struct Common {
     RowBand rows;                            // all2all | all2all-sp -rows
+    uint64_t band_rows = 0;                  // all2all | all2all-sp -band-rows <R>: the rows are walked in bands of R, one band resident at a time (0: off)
+    // the tiled band call: every band of -band-rows; with KMDB_ROWS_TILED=1 also the band of plain -rows (A/B with the same bytes)
+    bool tiled() const { const char* e = std::getenv("KMDB_ROWS_TILED"); return band_rows != 0 || (e && e[0] == '1'); }
+    // the band [lo, hi) into device memory at `dev` by the call this run takes
+    void band_to_device(kmdb_db* d, uint64_t lo, uint64_t hi, void* dev, const kmdb_opts& o) const {
+        if (tiled()) { check(kmdb_all2all_rows_tiled_device(d, lo, hi, dev, &o)); report_rows_tiled_stats(d, lo, hi); }
+        else { check(kmdb_all2all_rows_device(d, lo, hi, dev, &o)); report_rows_stats(d); }
+    }
+    void band_to_host(kmdb_db* d, uint64_t lo, uint64_t hi, uint32_t* host, const kmdb_opts& o) const {
+        if (tiled()) { check(kmdb_all2all_rows_tiled(d, lo, hi, host, &o)); report_rows_tiled_stats(d, lo, hi); }
+        else { check(kmdb_all2all_rows(d, lo, hi, host, &o)); report_rows_stats(d); }
+    }
     uint64_t seed_samples = 0;               // -from-samples -extend-from <old.db>: the samples of <old.db> (set by open_database)
     std::shared_ptr<BuildInput> from_samples;     // all2all | all2all-sp -from-samples: build's input switches; the "database" argument is the sample list
     std::string keep_db;                     // -keep-db <database>: the file `build` would have written, stored next to the table
@@ -365,43 +400,56 @@ void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts
 int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs, const std::string& path, uint64_t lo, uint64_t hi) {
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
-    std::cerr << "Calculating rows " << lo << " to " << hi << " of the matrix of common k-mers...";
+    // -band-rows <R>: the same for every band of R rows in turn — one band buffer on the device, the header once, the bands' lines one after another
+    const bool banded = c.band_rows != 0;
+    const uint64_t R = banded ? c.band_rows : std::max<uint64_t>(hi - lo, 1);
+    std::cerr << "Calculating rows " << lo << " to " << hi << " of the matrix of common k-mers";
+    if (banded) std::cerr << " in bands of " << R << " rows, storing them in " << path;
+    std::cerr << "...";
     auto t0 = clk::now();
-    kmdb_sparse_rows sp{};
-    {
-        std::vector<kmdb_cell_filter> fl;
-        for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-        if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
-            fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
-        if (fl.size() > 8) fl.clear();                          // (the host-side pass below applies every bound anyway)
-        std::vector<uint32_t> counts(std::max<uint64_t>(n, 1));
-        for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
-        DeviceBand band(c.device, tri(hi) - tri(lo));
-        check(kmdb_all2all_rows_device(db.d, lo, hi, band.p, &o));
-        report_rows_stats(db.d);
-        check(kmdb_sparse_from_dense_device(db.d, band.p, tri(lo), tri(hi), fl.data(), fl.size(), counts.data(), -1, &sp, &o));
-    }
-    std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
-    db.uploaded();
-    std::cerr << "Storing rows of the matrix of common k-mers in " << path << "...";
-    t0 = clk::now();
-    write_header(db, ofs);
+    std::vector<kmdb_cell_filter> fl;
+    for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+    if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
+        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+    if (fl.size() > 8) fl.clear();                              // (the host-side pass below applies every bound anyway)
+    std::vector<uint32_t> counts(std::max<uint64_t>(n, 1));
+    for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
     std::vector<char> row(10000 + n * 100);
     std::vector<uint32_t> cols, vals;
     size_t saved = 0;
-    for (uint64_t i = lo; i < hi; ++i) {
-        cols.clear(); vals.clear();
-        for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
-            if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
-                cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
+    {
+        DeviceBand band(c.device, largest_band_cells(lo, hi, R));
+        for (uint64_t b_lo = lo;;) {                            // (an empty range: one empty band, so that the header is written)
+            const uint64_t b_hi = b_lo + std::min(R, hi - b_lo);
+            kmdb_sparse_rows sp{};
+            c.band_to_device(db.d, b_lo, b_hi, band.p, o);
+            check(kmdb_sparse_from_dense_device(db.d, band.p, tri(b_lo), tri(b_hi), fl.data(), fl.size(), counts.data(), -1, &sp, &o));
+            if (b_lo == lo) {
+                if (!banded) {
+                    std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+                    std::cerr << "Storing rows of the matrix of common k-mers in " << path << "...";
+                    t0 = clk::now();
+                }
+                db.uploaded();
+                write_header(db, ofs);
             }
-        const char* name = kmdbh_db_sample_name(db.h, i);
-        if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
-        size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
-        ofs.write(row.data(), (std::streamsize)len);
-        saved += cols.size();
+            for (uint64_t i = b_lo; i < b_hi; ++i) {
+                cols.clear(); vals.clear();
+                for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
+                    if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
+                        cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
+                    }
+                const char* name = kmdbh_db_sample_name(db.h, i);
+                if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
+                size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
+                ofs.write(row.data(), (std::streamsize)len);
+                saved += cols.size();
+            }
+            kmdb_sparse_free(&sp);
+            b_lo = b_hi;
+            if (b_lo >= hi) break;
+        }
     }
-    kmdb_sparse_free(&sp);
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     std::cerr << "No. saved pairs: " << saved << std::endl;
     return finish(db, ofs, path);
@@ -426,16 +474,17 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     const int k = (int)kmdbh_db_kmer_length(db.h);
     uint64_t r_lo = 0, r_hi = n;                                 // the rows written: all of them, or the band of -rows
     if (c.rows.on) c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
-    if (c.rows.on && c.sparse) return write_sparse_band(db, c, o, ofs, args[1], r_lo, r_hi);
-    const uint64_t cell_lo = tri(r_lo);                          // m holds the cells from here on
+    if ((c.rows.on || c.band_rows) && c.sparse) return write_sparse_band(db, c, o, ofs, args[1], r_lo, r_hi);
+    // -band-rows <R>: the rows are computed and written R at a time; m holds one band (the largest one's cells) and is used again for the next
+    const uint64_t R = c.band_rows ? c.band_rows : std::max<uint64_t>(r_hi - r_lo, 1);
+    uint64_t cell_lo = tri(r_lo);                                // m holds the cells from here on
     std::cerr << "Calculating matrix of common k-mers..." << std::endl;
     auto t0 = clk::now();
-    std::vector<uint32_t> m(tri(r_hi) - cell_lo + 1);
+    std::vector<uint32_t> m(largest_band_cells(r_lo, r_hi, R) + 1);
     if (db.node) { check(kmdb_node_all2all_dense(db.node, m.data(), nullptr)); node_report(db); }
-    else if (c.rows.on) {
-        check(kmdb_all2all_rows(db.d, r_lo, r_hi, m.data(), &o));
-        report_rows_stats(db.d);
-    } else {
+    else if (c.band_rows) c.band_to_host(db.d, r_lo, r_lo + std::min(R, r_hi - r_lo), m.data(), o);      // (the first band; the others as the rows are written)
+    else if (c.rows.on) c.band_to_host(db.d, r_lo, r_hi, m.data(), o);
+    else {
         check(kmdb_all2all_dense(db.d, m.data(), &o));
         kmdb_stats st{};
         if (!kmdb_db_stats(db.d, &st) && st.path == KMDB_PATH_GLOBAL)
@@ -451,9 +500,13 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     const int nthr = (int)std::max<size_t>(1, std::min<size_t>(c.threads > 0 ? (size_t)c.threads : 16, std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 1));
     size_t name_max = 0;
     for (uint64_t i = 0; i < n; ++i) name_max = std::max(name_max, std::strlen(kmdbh_db_sample_name(db.h, i)));
-    for (uint64_t i0 = r_lo; i0 < r_hi;) {
+    for (uint64_t b_lo = r_lo; b_lo < r_hi;) {
+    const uint64_t b_hi = b_lo + std::min(R, r_hi - b_lo);     // (one band: the whole range unless -band-rows cuts it)
+    if (b_lo != r_lo) c.band_to_host(db.d, b_lo, b_hi, m.data(), o);
+    cell_lo = tri(b_lo);
+    for (uint64_t i0 = b_lo; i0 < b_hi;) {
         uint64_t i1 = i0, cells_in = 0;
-        while (i1 < r_hi && (i1 == i0 || cells_in + i1 <= (32u << 20))) { cells_in += i1; ++i1; }
+        while (i1 < b_hi && (i1 == i0 || cells_in + i1 <= (32u << 20))) { cells_in += i1; ++i1; }
         std::vector<std::vector<char>> text(nthr);
         std::atomic<int> failed{0};
         auto work = [&](int t) {
@@ -493,6 +546,8 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
         for (auto& tx : text) ofs.write(tx.data(), (std::streamsize)tx.size());
         i0 = i1;
     }
+    b_lo = b_hi;
+    }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     return finish(db, ofs, args[1]);
 }
@@ -516,9 +571,9 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     open_database(db, args[0], c, o);
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
-    if (c.rows.on) {
+    if (c.rows.on || c.band_rows) {
         uint64_t r_lo = 0, r_hi = n;
-        c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
+        if (c.rows.on) c.rows.resolve(n, c.seed_samples, r_lo, r_hi);
         return write_sparse_band(db, c, o, ofs, args[1], r_lo, r_hi);
     }
     std::cerr << "Calculating matrix of common k-mers...";
@@ -2124,6 +2179,64 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
     for (uint64_t i = 0; i < n; ++i) { s.counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i); names[i] = kmdbh_db_sample_name(db.h, i); }
     const uint32_t flags = KMDB_DISTANCE_TRIANGLE | (sparse ? KMDB_DISTANCE_SPARSE_OUT : 0u) | (phylip ? KMDB_DISTANCE_PHYLIP : 0u);
 
+    // -band-rows <R>: every measure's table is open at once; a band is computed once, every measure's handle borrows it in turn and its rows go to
+    // that measure's writer — one band buffer for the whole run
+    if (c.band_rows) {
+        const uint64_t R = c.band_rows;
+        const size_t nm = measures.size();
+        if (!nm) throw usage_error(mode);
+        std::vector<DistanceSetup> setups(nm, s);
+        std::vector<DistanceHandle> hs(nm);
+        std::vector<std::unique_ptr<TableWriter>> ws(nm);
+        std::vector<std::string> paths(nm);
+        for (size_t mi = 0; mi < nm; ++mi) {
+            setups[mi].measure = kmdbh_metric_id(measures[mi].c_str());
+            setups[mi].filters = distance_filters(bounds, measures[mi], kmer_lo, kmer_hi);
+            hs[mi].begin(setups[mi], flags);
+            paths[mi] = nm == 1 ? args[1] : args[1] + "." + measures[mi];
+            ws[mi].reset(new TableWriter);
+            write_distance_header(ws[mi]->open(paths[mi]), phylip, s.k, kmdbh_db_fraction(db.h), names, n);
+            ws[mi]->start();
+        }
+        std::cerr << "Calculating rows " << r_lo << " to " << r_hi << " of the matrix of common k-mers in bands of " << R << " rows, storing "
+                  << (nm == 1 ? "the " + measures[0] + " table" : std::to_string(nm) + " tables") << " in " << args[1] << (nm == 1 ? "" : ".<measure>") << "...";
+        const auto t0 = clk::now();
+        band.reset(new DeviceBand(c.device, largest_band_cells(r_lo, r_hi, R)));
+        std::string error;
+        try {
+            for (uint64_t b_lo = r_lo; b_lo < r_hi;) {
+                const uint64_t b_hi = b_lo + std::min(R, r_hi - b_lo);
+                c.band_to_device(db.d, b_lo, b_hi, band->p, o);
+                if (b_lo == r_lo) db.uploaded();
+                for (size_t mi = 0; mi < nm; ++mi) {
+                    check(kmdb_distance_take_cells_device(hs[mi].d, band->p, b_lo, names.data()));
+                    for (uint64_t i0 = b_lo; i0 < b_hi;) {
+                        uint64_t i1 = i0, cells = 0;
+                        while (i1 < b_hi && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+                        kmdb_distance_out piece{};
+                        check(kmdb_distance_matrix_rows(hs[mi].d, i0, i1, &piece));
+                        if (!ws[mi]->push(piece)) throw std::runtime_error("Cannot write the output file " + paths[mi]);
+                        i0 = i1;
+                    }
+                }
+                b_lo = b_hi;
+            }
+        } catch (std::exception& e) {
+            error = e.what();
+        }
+        for (auto& w : ws) w->stop(error.empty());
+        if (!error.empty()) throw std::runtime_error(error);
+        for (size_t mi = 0; mi < nm; ++mi)
+            if (ws[mi]->write_failed) throw std::runtime_error("Cannot write the output file " + paths[mi]);
+        std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
+        for (size_t mi = 0; mi < nm; ++mi) report_distance_stats("distance from the matrix", hs[mi].d, false);
+        for (size_t mi = 0; mi + 1 < nm; ++mi) {
+            ws[mi]->ofs.close();
+            if (!ws[mi]->ofs) throw std::runtime_error("Cannot write the output file " + paths[mi]);
+        }
+        return finish(db, ws[nm - 1]->ofs, paths[nm - 1]);
+    }
+
     DistanceHandle owner;                                          // the first measure's handle holds the triangle for all of them
     std::unique_ptr<TableWriter> w;                                // one per measure in turn
     std::string path;
@@ -2139,8 +2252,7 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
                 std::cerr << "Calculating rows " << r_lo << " to " << r_hi << " of the matrix of common k-mers..." << std::endl;
                 const auto t0 = clk::now();
                 band.reset(new DeviceBand(c.device, tri(r_hi) - tri(r_lo)));
-                check(kmdb_all2all_rows_device(db.d, r_lo, r_hi, band->p, &o));
-                report_rows_stats(db.d);
+                c.band_to_device(db.d, r_lo, r_hi, band->p, o);
                 std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
                 db.uploaded();
             }
@@ -2769,8 +2881,16 @@ void usage() {
                  "                                  as a band of the matrix of its own on the GPU; <output> holds the header lines of the full run and exactly\n"
                  "                                  its lines of those samples.  Dense, -sparse / all2all-sp with the -min / -max list, and -distance <measure>.\n"
                  "                                  -rows new (with -from-samples -extend-from <old.db>): the rows of the samples added to <old.db>.\n"
-                 "                                  Refused with -gpus <N>, -sample-rows and -phylip-out, and when hi exceeds the sample count.  Not offered:\n"
-                 "                                  a whole run walked in bands (-band-rows), a long pattern split over several waves.\n";
+                 "                                  Refused with -gpus <N>, -sample-rows and -phylip-out, and when hi exceeds the sample count.\n"
+                 "    kmer-db-amd all2all | all2all-sp -band-rows <R> [the mode's own switches] <database> <output>\n"
+                 "all2all / all2all-sp -band-rows <R>: the whole run walked in bands of R rows — one band of the matrix is resident at a time, its rows summed\n"
+                 "                                  in LDS tiles on the GPU; <output> holds, byte for byte, what the same command without -band-rows writes:\n"
+                 "                                  the way of one GPU to a collection whose triangle does not fit its memory.  Dense, -sparse / all2all-sp\n"
+                 "                                  with the -min / -max list, and -distance <measure> (repeated too).  With -rows <lo>:<hi> | new that range\n"
+                 "                                  is walked in bands; with -from-samples [-extend-from <old.db>] as well.  Refused with -gpus <N>, -sample-rows\n"
+                 "                                  and -phylip-out, and when R is 0 or no number.  KMDB_ROWS_TILE_COLS / KMDB_ROWS_TILE_HITS: a tile's columns\n"
+                 "                                  and the hits of a share; KMDB_ROWS_TILED=1: plain -rows takes the tiled call too.  Not offered: a long\n"
+                 "                                  pattern's list decoded by several lanes.\n";
 }
 
 }  // namespace
@@ -2824,6 +2944,17 @@ int main(int argc, char** argv) {
             c.rows.parse(v);
             if (c.rows.is_new && !(c.from_samples && c.from_samples->extend))
                 throw std::runtime_error("-rows new goes with -from-samples -extend-from <old.db> only: it means the rows of the samples added to <old.db>");
+        }
+        // -band-rows <R>: the same
+        if (std::find(args.begin(), args.end(), "-band-rows") != args.end()) {
+            if (mode != "all2all" && mode != "all2all-sp") throw std::runtime_error("-band-rows applies to all2all and all2all-sp");
+            if (c.gpus > 0) throw std::runtime_error("-band-rows does not go with -gpus <N>: a band is computed on one device from the whole pattern tree");
+            for (auto& a : args) {
+                if (a == "-sample-rows") throw std::runtime_error("-band-rows does not go with -sample-rows: a pair is offered to both its samples, so a band of rows does not hold a sample's candidates");
+                if (a == "-phylip-out") throw std::runtime_error("-band-rows does not go with -phylip-out: a phylip table is a whole triangle");
+            }
+            if (!take_option(args, "-band-rows", v)) throw std::runtime_error("-band-rows expects <R>, a number of rows of 1 or more");
+            c.band_rows = parse_band_rows(v);
         }
         if (mode == "all2all") return run_all2all(args, c);
         if (mode == "all2all-sp") return run_all2all_sp(args, c);
