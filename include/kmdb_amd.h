@@ -373,6 +373,60 @@ typedef struct kmdb_all2all_banded_stats {   /* the LAST banded call on the hand
 int  kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_rows, const kmdb_cell_filter* filters, size_t n_filters,
                                          const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
 int  kmdb_all2all_banded_stats_get(const kmdb_db* db, kmdb_all2all_banded_stats* out);
+
+/* The same band through the block-record pipeline (KMDB_HAS_ALL2ALL_ROWS_RECORDS; a2a_rows_records.hip, a2a_blocks.hip).  DEFINITION: bit for bit
+ * what kmdb_all2all_rows_device writes for the same arguments — the cells [tri(row_lo), tri(row_hi)) of kmdb_all2all_dense_device, tri(i) =
+ * i (i - 1) / 2, in the out_cells layout of the two band calls above; the band is zeroed by the call and added into, the host variant allocates it.
+ * Decode, emit and the sorts run as in a whole-matrix call (same records, same launch sizes: a band call and a whole call share one warm handle);
+ * the apply stage works on the block rows Xlo = row_lo / width .. Xhi = (row_hi - 1) / width alone: a stream job, a window run of stream chunks, a
+ * slice's tile of first-block records or a second-level tile of another block row does no matrix-core step and no write-back, and a cell is written
+ * iff row_lo <= row < row_hi, at tri(row) - tri(row_lo) + col.  The handle's working set is the whole call's less the triangle: the band is the only
+ * output.  A database the pipeline cannot take (kmdb_db_fallback_reason) is served by kmdb_all2all_rows_device, and the stats say so; with
+ * KMDB_FLAG_NO_FALLBACK the call fails with the reason.
+ * Refused with a message, under these names: null arguments, row_lo > row_hi, row_hi > N, kmdb_opts.shard_count > 1, unknown flag bits, a
+ * query-shard handle, a band whose bytes exceed the device's memory, and a handle made under KMDB_K1N_MODE=1 (its narrow kernel writes the matrix
+ * itself).  A refused call leaves out_cells untouched.  An empty band succeeds and writes nothing.
+ * kmdb_stats after a band call: kernel_ms and device_bytes are the band call's; path, n_records, sized_call, the stage times and the other counts
+ * stay those of the last whole-matrix call on the handle — the band call's own are in kmdb_all2all_rows_records_stats.
+ * Limit: the pipeline's 2^22 block pairs (about 185 000 samples at width 64); beyond it the two tree forms above are the only route. */
+#define KMDB_HAS_ALL2ALL_ROWS_RECORDS 1
+#define KMDB_ROWS_RECORDS_PATH_NONE     0u   /* an empty band: nothing ran */
+#define KMDB_ROWS_RECORDS_PATH_RECORDS  1u   /* the block-record pipeline */
+#define KMDB_ROWS_RECORDS_PATH_TREE     2u   /* fallback: kmdb_all2all_rows_device ran */
+typedef struct kmdb_all2all_rows_records_stats {   /* the LAST such call on the handle */
+    uint32_t path;                 /* KMDB_ROWS_RECORDS_PATH_* */
+    uint32_t width;                /* sample ids per block */
+    uint32_t x_lo, x_hi;           /* block rows the band meets */
+    uint32_t sized_call;           /* kmdb_stats.sized_call of this call */
+    uint32_t slices;               /* passes over the pattern stream */
+    uint64_t band_cells;           /* tri(row_hi) - tri(row_lo) */
+    uint64_t records;              /* block records emitted: kmdb_stats.n_records of a whole call on the handle */
+    uint64_t units_total;          /* apply units the call met: the sum of the four kinds below ... */
+    uint64_t units_run;            /* ... and those inside the band's block rows, which ran */
+    uint64_t jobs_total, jobs_run;         /* stream jobs over the sorted records */
+    uint64_t runs_total, runs_run;         /* window runs of stream chunks */
+    uint64_t slices_total, slices_run;     /* tiles of the slices' first-block records */
+    uint64_t tiles_total, tiles_run;       /* second-level tiles with both lists non-empty */
+    double   k0_ms, k1n_ms, k1g_ms, k2_ms, kernel_ms;   /* the stage times of kmdb_stats for this call */
+    uint64_t peak_device_bytes;    /* kmdb_stats.device_bytes after the call + the band's bytes */
+} kmdb_all2all_rows_records_stats;
+int  kmdb_all2all_rows_records_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts);
+int  kmdb_all2all_rows_records(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts);
+int  kmdb_all2all_rows_records_stats_get(const kmdb_db* db, kmdb_all2all_rows_records_stats* out);
+/* kmdb_all2all_sparse_filtered_banded with the band call chosen: KMDB_BAND_PATH_TILED is that call itself, _TREE takes kmdb_all2all_rows_device,
+ * _RECORDS kmdb_all2all_rows_records_device.  Same DEFINITION, same refusals (and an unknown path); kmdb_all2all_banded_stats is filled by every
+ * path (its hit / run / update sums by _TILED only), the records path's own sums are in kmdb_all2all_banded_records_stats. */
+#define KMDB_BAND_PATH_TILED   0
+#define KMDB_BAND_PATH_TREE    1
+#define KMDB_BAND_PATH_RECORDS 2
+typedef struct kmdb_all2all_banded_records_stats {   /* the LAST banded call with KMDB_BAND_PATH_RECORDS on the handle */
+    uint64_t bands;
+    uint64_t units_total, units_run;   /* sums over the bands of kmdb_all2all_rows_records_stats */
+    double   ms;                       /* sum of the bands' kernel_ms */
+} kmdb_all2all_banded_records_stats;
+int  kmdb_all2all_sparse_filtered_banded_path(kmdb_db* db, uint64_t band_rows, int path, const kmdb_cell_filter* filters, size_t n_filters,
+                                              const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
+int  kmdb_all2all_banded_records_stats_get(const kmdb_db* db, kmdb_all2all_banded_records_stats* out);
 /* ---------------------------------------------------------------------------------------
  * all2all-sp -sample-rows <criterion>:<count> (params.cpp:533-557): every sample keeps its `count` best neighbours.  A pair (i, j), i > j, with
  * a non-zero cell that passes the filters has ONE score, metric(cell, kmers[i], kmers[j], k) with the triangle's row i as the row sample, and is

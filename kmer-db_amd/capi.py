@@ -149,6 +149,19 @@ class _All2allBandedStats(C.Structure):
                 ("updates", C.c_uint64), ("select_ms", C.c_double), ("hits_ms", C.c_double), ("apply_ms", C.c_double)]
 
 
+class _All2allRowsRecordsStats(C.Structure):
+    _fields_ = [("path", C.c_uint32), ("width", C.c_uint32), ("x_lo", C.c_uint32), ("x_hi", C.c_uint32), ("sized_call", C.c_uint32), ("slices", C.c_uint32),
+                ("band_cells", C.c_uint64), ("records", C.c_uint64), ("units_total", C.c_uint64), ("units_run", C.c_uint64),
+                ("jobs_total", C.c_uint64), ("jobs_run", C.c_uint64), ("runs_total", C.c_uint64), ("runs_run", C.c_uint64),
+                ("slices_total", C.c_uint64), ("slices_run", C.c_uint64), ("tiles_total", C.c_uint64), ("tiles_run", C.c_uint64),
+                ("k0_ms", C.c_double), ("k1n_ms", C.c_double), ("k1g_ms", C.c_double), ("k2_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("peak_device_bytes", C.c_uint64)]
+
+
+class _All2allBandedRecordsStats(C.Structure):
+    _fields_ = [("bands", C.c_uint64), ("units_total", C.c_uint64), ("units_run", C.c_uint64), ("ms", C.c_double)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -161,6 +174,8 @@ FLAG_ONE_SHOT = 16
 DISTANCE_SPARSE_OUT, DISTANCE_SPARSE_IN, DISTANCE_TRIANGLE, DISTANCE_PHYLIP = 1, 2, 4, 8
 DISTANCE_DECLINED = 2
 PATH_NONE, PATH_RECORDS, PATH_TILE, PATH_GLOBAL = 0, 1, 2, 3
+ROWS_RECORDS_PATH_NONE, ROWS_RECORDS_PATH_RECORDS, ROWS_RECORDS_PATH_TREE = 0, 1, 2      # kmdb_all2all_rows_records_stats.path
+BAND_PATHS = ("tiled", "tree", "records")              # KMDB_BAND_PATH_*
 PARTITIONS = ("prefix", "range", "prefix-tables")      # KMDB_PARTITION_*
 
 # every symbol include/kmdb_amd.h declares
@@ -193,6 +208,8 @@ EXPORTS = [
     "kmdb_distance_csr_device", "kmdb_distance_csr_row_ptr", "kmdb_distance_parts_stats_get",
     "kmdb_all2all_rows_device", "kmdb_all2all_rows", "kmdb_all2all_rows_stats_get", "kmdb_device_buffer_alloc", "kmdb_device_buffer_free",
     "kmdb_all2all_rows_tiled_device", "kmdb_all2all_rows_tiled", "kmdb_all2all_rows_tiled_stats_get", "kmdb_all2all_sparse_filtered_banded", "kmdb_all2all_banded_stats_get",
+    "kmdb_all2all_rows_records_device", "kmdb_all2all_rows_records", "kmdb_all2all_rows_records_stats_get", "kmdb_all2all_sparse_filtered_banded_path",
+    "kmdb_all2all_banded_records_stats_get",
 ]
 
 
@@ -249,6 +266,12 @@ def lib():
     L.kmdb_all2all_rows_tiled_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsTiledStats)]
     L.kmdb_all2all_sparse_filtered_banded.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse), C.POINTER(_Opts)]
     L.kmdb_all2all_banded_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allBandedStats)]
+    L.kmdb_all2all_rows_records_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_records.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(_Opts)]
+    L.kmdb_all2all_rows_records_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsRecordsStats)]
+    L.kmdb_all2all_sparse_filtered_banded_path.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse),
+                                                           C.POINTER(_Opts)]
+    L.kmdb_all2all_banded_records_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allBandedRecordsStats)]
     L.kmdb_device_buffer_alloc.argtypes = [C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
     L.kmdb_device_buffer_free.restype = None
     L.kmdb_device_buffer_free.argtypes = [C.c_int32, C.c_void_p]
@@ -745,9 +768,37 @@ class DeviceDB:
         _check(lib().kmdb_all2all_rows_tiled_stats_get(self._d, C.byref(s)))
         return {f: getattr(s, f) for f, _ in _All2allRowsTiledStats._fields_}
 
-    def all2all_sparse_filtered_banded(self, band_rows, filters, sample_kmers, measure=None, shard=(0, 1)):
+    def all2all_rows_records(self, row_lo, row_hi, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows_records: the band of all2all_rows, bit for bit, through the block-record pipeline (decode, emit, sort whole; the apply
+        stage on the band's block rows alone)"""
+        lo, hi = int(row_lo), int(row_hi)
+        cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
+        out = np.zeros(max(1, cells), dtype=np.uint32)
+        o = _opts(self.device, shard, flags)
+        _check(lib().kmdb_all2all_rows_records(self._d, lo, hi, out.ctypes.data, C.byref(o)))
+        return out[:cells]
+
+    def all2all_rows_records_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows_records_device: the same band left in device memory at dev_ptr, the layout of all2all_rows_device"""
+        o = _opts(self.device, shard, flags, stream)
+        _check(lib().kmdb_all2all_rows_records_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+
+    def all2all_rows_records_stats(self):
+        """kmdb_all2all_rows_records_stats_get: the last band call through the block-record pipeline on the handle"""
+        s = _All2allRowsRecordsStats()
+        _check(lib().kmdb_all2all_rows_records_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allRowsRecordsStats._fields_}
+
+    def all2all_banded_records_stats(self):
+        """kmdb_all2all_banded_records_stats_get: the last banded call with path="records" on the handle"""
+        s = _All2allBandedRecordsStats()
+        _check(lib().kmdb_all2all_banded_records_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allBandedRecordsStats._fields_}
+
+    def all2all_sparse_filtered_banded(self, band_rows, filters, sample_kmers, measure=None, shard=(0, 1), path=None):
         """kmdb_all2all_sparse_filtered_banded: all2all_sparse_filtered walked in bands of band_rows rows — one band resident at a time, the same
-        SparseRows"""
+        SparseRows.  path: None (the tiled band call, kmdb_all2all_sparse_filtered_banded itself), or one of BAND_PATHS / its index
+        (kmdb_all2all_sparse_filtered_banded_path)"""
         raw = _Sparse()
         o = _opts(self.device, shard)
         fs = (_CellFilter * max(1, len(filters)))()
@@ -756,8 +807,13 @@ class DeviceDB:
             fs[i].lo = -np.finfo(np.float64).max if lo is None else lo
             fs[i].hi = np.finfo(np.float64).max if hi is None else hi
         cnt = None if sample_kmers is None else np.ascontiguousarray(sample_kmers, np.uint32)
-        _check(lib().kmdb_all2all_sparse_filtered_banded(self._d, int(band_rows), fs, len(filters), None if cnt is None else cnt.ctypes.data,
-                                                         -1 if measure is None else METRICS.index(measure), C.byref(raw), C.byref(o)))
+        if path is None:
+            _check(lib().kmdb_all2all_sparse_filtered_banded(self._d, int(band_rows), fs, len(filters), None if cnt is None else cnt.ctypes.data,
+                                                             -1 if measure is None else METRICS.index(measure), C.byref(raw), C.byref(o)))
+        else:
+            _check(lib().kmdb_all2all_sparse_filtered_banded_path(self._d, int(band_rows), BAND_PATHS.index(path) if isinstance(path, str) else int(path), fs,
+                                                                  len(filters), None if cnt is None else cnt.ctypes.data,
+                                                                  -1 if measure is None else METRICS.index(measure), C.byref(raw), C.byref(o)))
         try:
             return SparseRows(raw)
         finally:

@@ -227,27 +227,6 @@ uint64_t band_device_bytes(const kmdb_db* db) {
     return db->band_sel.bytes() + db->band_counters.bytes() + db->band_rows.bytes() + db->band_hits.bytes() + db->band_jobs.bytes() + db->band_scan_tmp.bytes();
 }
 
-// the argument checks of rows_check / rows_check_bytes (a2a_rows.hip), the same cases in the same words; 0, or 1 with the error set
-int band_check(const char* who, const kmdb_db* db, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts) {
-    const std::string w(who);
-    if (row_lo > row_hi) return kmdb_set_error(w + ": row_lo > row_hi (" + std::to_string(row_lo) + " > " + std::to_string(row_hi) + ")");
-    if (row_hi > db->N) return kmdb_set_error(w + ": row_hi " + std::to_string(row_hi) + " > the " + std::to_string(db->N) + " samples of the database");
-    if (opts && opts->shard_count > 1) return kmdb_set_error(w + ": a band needs the whole pattern stream (shard_count must be 1)");
-    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error(w + ": unknown bits in kmdb_opts.flags");
-    if (db->qs_count > 1) return kmdb_set_error(w + ": not on a query shard (kmdb_db_upload_query_shard): its tree holds one shard's k-mers only");
-    return 0;
-}
-int band_check_bytes(const char* who, uint64_t band_cells, bool against_free) {
-    if (band_cells < (1ull << 32)) return 0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t limit = against_free ? free_b : total_b;
-    if (band_cells > limit / 4)
-        return kmdb_set_error(std::string(who) + ": the band is " + std::to_string(band_cells) + " cells, " + std::to_string(band_cells * 4) + " bytes, beyond the " +
-                              std::to_string(limit) + " bytes of " + (against_free ? "free device memory" : "device memory"));
-    return 0;
-}
-
 // KMDB_ROWS_TILE_COLS / KMDB_ROWS_TILE_HITS, read at every call (tests and A/B)
 int band_switches(const char* who, uint32_t& tile_cols, uint32_t& tile_hits) {
     tile_cols = BAND_TILE_COLS_DEFAULT;
@@ -404,11 +383,11 @@ int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint6
 extern "C" int kmdb_all2all_rows_tiled_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts) {
     const char* who = "kmdb_all2all_rows_tiled_device";
     if (!db) return kmdb_set_error(std::string(who) + ": null argument");
-    if (band_check(who, db, row_lo, row_hi, opts)) return 1;
+    if (kmdb_band_check(who, db, row_lo, row_hi, opts)) return 1;
     const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
     if (!out_cells_dev && band_cells) return kmdb_set_error(std::string(who) + ": null argument");
     HIP_TRY(hipSetDevice(db->device));
-    if (band_check_bytes(who, band_cells, false)) return 1;
+    if (kmdb_band_check_bytes(who, band_cells, false)) return 1;
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
     const int rc = band_run(who, db, (uint32_t*)out_cells_dev, row_lo, row_hi, st);
     kmdb_release_staging(db);
@@ -418,11 +397,11 @@ extern "C" int kmdb_all2all_rows_tiled_device(kmdb_db* db, uint64_t row_lo, uint
 extern "C" int kmdb_all2all_rows_tiled(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts) {
     const char* who = "kmdb_all2all_rows_tiled";
     if (!db) return kmdb_set_error(std::string(who) + ": null argument");
-    if (band_check(who, db, row_lo, row_hi, opts)) return 1;
+    if (kmdb_band_check(who, db, row_lo, row_hi, opts)) return 1;
     const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
     if (!out_cells_host && band_cells) return kmdb_set_error(std::string(who) + ": null argument");
     HIP_TRY(hipSetDevice(db->device));
-    if (band_check_bytes(who, band_cells, true)) return 1;
+    if (kmdb_band_check_bytes(who, band_cells, true)) return 1;
     DevBuf<uint32_t> band;
     DEV_ALLOC(band, std::max<uint64_t>(band_cells, 1));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
@@ -440,23 +419,26 @@ extern "C" int kmdb_all2all_rows_tiled_stats_get(const kmdb_db* db, kmdb_all2all
     return 0;
 }
 
-// kmdb_all2all_sparse_filtered walked in bands: one band buffer, the tiled call, the compaction of the cells where they lie, the rows appended
-extern "C" int kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_rows, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers,
-                                                   int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
-    const char* who = "kmdb_all2all_sparse_filtered_banded";
+// kmdb_all2all_sparse_filtered walked in bands: one band buffer, the band call of `path` (KMDB_BAND_PATH_*: the tiled call here, the tree call of
+// a2a_rows.hip, the block-record pipeline's of a2a_rows_records.hip), the compaction of the cells where they lie, the rows appended
+static int banded_run(const char* who, kmdb_db* db, uint64_t band_rows, int path, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers,
+                      int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
     if (!db || !out) return kmdb_set_error(std::string(who) + ": null argument");
+    if (path != KMDB_BAND_PATH_TILED && path != KMDB_BAND_PATH_TREE && path != KMDB_BAND_PATH_RECORDS)
+        return kmdb_set_error(std::string(who) + ": unknown path " + std::to_string(path) + " (KMDB_BAND_PATH_TILED, _TREE or _RECORDS)");
     if (band_rows == 0) return kmdb_set_error(std::string(who) + ": band_rows is 0 (a band holds one row at least)");
     if (kmdb_check_filters(who, filters, n_filters, sample_kmers, measure)) return 1;
     const uint64_t N = db->N;
-    if (band_check(who, db, 0, N, opts)) return 1;
+    if (kmdb_band_check(who, db, 0, N, opts)) return 1;
     HIP_TRY(hipSetDevice(db->device));
     uint64_t max_cells = 0;
     for (uint64_t lo = 0; lo < N; lo += std::min<uint64_t>(band_rows, N - lo)) {
         const uint64_t hi = lo + std::min<uint64_t>(band_rows, N - lo);
         max_cells = std::max(max_cells, tri_h(hi) - tri_h(lo));
     }
-    if (band_check_bytes(who, max_cells, true)) return 1;
+    if (kmdb_band_check_bytes(who, max_cells, true)) return 1;
     kmdb_all2all_banded_stats bt{};
+    kmdb_all2all_banded_records_stats br{};
     bt.max_band_bytes = max_cells * 4;
     DevBuf<uint32_t> band;
     DEV_ALLOC(band, std::max<uint64_t>(max_cells, 1));
@@ -467,12 +449,20 @@ extern "C" int kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_ro
     int rc = 0;
     for (uint64_t lo = 0; lo < N && !rc;) {
         const uint64_t hi = lo + std::min<uint64_t>(band_rows, N - lo);
-        rc = band_run(who, db, band, lo, hi, st);
+        if (path == KMDB_BAND_PATH_TILED) rc = band_run(who, db, band, lo, hi, st);
+        else if (path == KMDB_BAND_PATH_TREE) rc = kmdb_all2all_rows_device(db, lo, hi, band, opts);
+        else rc = kmdb_all2all_rows_records_device(db, lo, hi, band, opts);
         if (rc) break;
-        const kmdb_all2all_rows_tiled_stats& bs = db->band_stats;
         ++bt.bands;
-        bt.hits += bs.hits; bt.runs += bs.runs; bt.updates += bs.updates;
-        bt.select_ms += bs.select_ms; bt.hits_ms += bs.hits_ms; bt.apply_ms += bs.apply_ms;
+        if (path == KMDB_BAND_PATH_TILED) {
+            const kmdb_all2all_rows_tiled_stats& bs = db->band_stats;
+            bt.hits += bs.hits; bt.runs += bs.runs; bt.updates += bs.updates;
+            bt.select_ms += bs.select_ms; bt.hits_ms += bs.hits_ms; bt.apply_ms += bs.apply_ms;
+        } else if (path == KMDB_BAND_PATH_TREE) {
+            bt.updates += db->rows_stats.updates; bt.select_ms += db->rows_stats.select_ms; bt.apply_ms += db->rows_stats.apply_ms;
+        } else {
+            ++br.bands; br.units_total += db->rr_stats.units_total; br.units_run += db->rr_stats.units_run; br.ms += db->rr_stats.kernel_ms;
+        }
         bt.peak_device_bytes = std::max<uint64_t>(bt.peak_device_bytes, db->stats.device_bytes + band.bytes());
         kmdb_sparse_rows part{};
         rc = kmdb_sparse_from_dense_device(db, band, tri_h(lo), tri_h(hi), filters, n_filters, sample_kmers, measure, &part, opts);
@@ -487,6 +477,7 @@ extern "C" int kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_ro
     }
     band.reset();
     db->banded_stats = bt;
+    if (path == KMDB_BAND_PATH_RECORDS) db->banded_rr_stats = br;
     kmdb_release_staging(db);
     if (rc) return 1;
     const uint64_t nnz = col.size();
@@ -506,6 +497,20 @@ extern "C" int kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_ro
         std::memcpy(out->val, val.data(), nnz * sizeof(uint32_t));
         if (measure >= 0) std::memcpy(out->measure, meas.data(), nnz * sizeof(double));
     }
+    return 0;
+}
+
+extern "C" int kmdb_all2all_sparse_filtered_banded(kmdb_db* db, uint64_t band_rows, const kmdb_cell_filter* filters, size_t n_filters, const uint32_t* sample_kmers,
+                                                   int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    return banded_run("kmdb_all2all_sparse_filtered_banded", db, band_rows, KMDB_BAND_PATH_TILED, filters, n_filters, sample_kmers, measure, out, opts);
+}
+extern "C" int kmdb_all2all_sparse_filtered_banded_path(kmdb_db* db, uint64_t band_rows, int path, const kmdb_cell_filter* filters, size_t n_filters,
+                                                        const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts) {
+    return banded_run("kmdb_all2all_sparse_filtered_banded_path", db, band_rows, path, filters, n_filters, sample_kmers, measure, out, opts);
+}
+extern "C" int kmdb_all2all_banded_records_stats_get(const kmdb_db* db, kmdb_all2all_banded_records_stats* out) {
+    if (!db || !out) return kmdb_set_error("kmdb_all2all_banded_records_stats_get: null argument");
+    *out = db->banded_rr_stats;
     return 0;
 }
 

@@ -33,6 +33,9 @@
 //   K2  k2_apply_kernel      stream chunks (side stream, next to K1w); k2j_starts[_flat] / k2j_build / k2_jobs_kernel: the sorted
 //                            records stream by stream.  64 records per wave step as bit matrices, int8 MFMA into a 64 x 64 LDS tile
 //                            (weights >= 128 as base-128 digit passes), one HBM atomic per non-zero cell.
+// A band of rows (kmdb_blocks_run with a kmdb_band_desc; a2a_rows_records.hip): K0, K1n, K1w and the sorts run as above, the K2 stage takes its
+//                            BAND instantiations (k2d_band_kernel, k2_apply_kernel<true>, k2_jobs_kernel<true>, l2_join_apply_kernel<true>): the units
+//                            of block rows outside the band are culled, the write-back is windowed to the band's rows and based on its first cell.
 // db2db (kmdb_rect_sort_apply) shares cs_hist / cs_scatter and applies its sorted records with k2_sorted_kernel.
 // Records are placed WITHOUT a counting pass and WITHOUT hot global atomics (same-address device atomics run at a few million
 // per second on this part: measured, profiles/README.md): waves take chunks from 256 sub-pool cursors a few at a time, keep
@@ -77,6 +80,24 @@ constexpr uint32_t KMDB_SUBPOOLS = 256;      // sub-pools of the record chunk po
 namespace {
 
 __host__ __device__ __forceinline__ uint32_t tri32(uint32_t x) { return x * (x + 1u) / 2u; }
+
+// A band of the matrix's rows as the write-back sites of the apply stage see it (kmdb_all2all_rows_records_device): M then points at cell
+// tri64(row_lo) of the triangle, the band's first, and holds the rows [row_lo, row_hi) only.  [Xlo, Xhi] are the block rows the band meets: a
+// stream job, a window run, a slice's tile or a second-level tile of another block row is culled (no matrix-core step, no write-back), and a cell
+// of a block row that lies half inside is written iff its row is one of the band's, at tri64(row) - cell_lo + col.  units: 64 slots of BAND_UNIT_WORDS
+// words, a slot per workgroup (mod 64) so that no counter is hot: BU_* of every apply unit the call met and of those it ran (the call's statistics).
+// The whole-matrix instantiations (BAND = false) take BandArg<false>, which is empty: nothing of this reaches them.
+struct BandWin { uint32_t row_lo, row_hi, Xlo, Xhi; uint64_t cell_lo; uint32_t* units; };
+template <bool BAND> struct BandArg {};
+template <> struct BandArg<true> { BandWin w; };
+enum : uint32_t { BU_JOBS = 0, BU_JOBS_RUN, BU_RUNS, BU_RUNS_RUN, BU_SLICES, BU_SLICES_RUN, BU_TILES, BU_TILES_RUN, BU_COUNT };
+constexpr uint32_t BAND_UNIT_SLOTS = 64, BAND_UNIT_WORDS = 32;      // (a slot is one 128-byte line)
+__device__ __forceinline__ bool band_culls(const BandWin& w, uint32_t X) { return X < w.Xlo || X > w.Xhi; }
+__device__ __forceinline__ void band_unit(const BandWin& w, uint32_t slot, uint32_t kind, bool ran) {
+    uint32_t* c = w.units + (size_t)(slot & (BAND_UNIT_SLOTS - 1u)) * BAND_UNIT_WORDS;
+    atomicAdd(c + kind, 1u);
+    if (ran) atomicAdd(c + kind + 1u, 1u);
+}
 
 // Workgroups are dealt to the eight XCDs round-robin (workgroup b runs on XCD b % 8), and every XCD has its own L2.  Where neighbouring
 // work items write neighbouring memory (the sort kernels: consecutive jobs fill adjacent stretches of every stream, the cache lines at
@@ -1119,7 +1140,9 @@ struct DParams {
     uint32_t N, bwidth;
     unsigned char* touched;
 };
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k2d_kernel(const DParams q) {
+// (the kernel's body: BAND = false is k2d_kernel as it always was; BAND = true culls the tiles of block rows outside the band and windows the write-back)
+template <bool BAND>
+__device__ __forceinline__ void k2d_body(const DParams& q, const BandArg<BAND>& band) {
     __shared__ unsigned long long lut_ff[256], lut_01[256];       // byte b -> its 8 bits spread over 8 bytes (0xFF / 0x01 where set)
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[4][64];
     {
@@ -1171,12 +1194,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         while (!pend && next_step()) {}
         if (!pend) break;
         const uint32_t X0 = bcast(wx >> 8, (uint32_t)__builtin_ctzll(pend));
+        bool culled = false;                                     // (wave-uniform) band: the tile's block row lies outside it — its records are passed over
+        if constexpr (BAND) {
+            culled = band_culls(band.w, X0);
+            if (lane == 0) band_unit(band.w, blockIdx.x * 4u + wave, BU_SLICES, !culled);
+        }
         k2_v16i c00 = {}, c10 = {}, c11 = {};
         for (;;) {
             const bool mine = ((pend >> lane) & 1ull) && (wx >> 8) == X0;
             const unsigned long long bm = __ballot(mine);
             if (!bm) break;                                      // the step's next record belongs to another tile
             pend &= ~bm;
+            if constexpr (BAND) if (culled) { if (pend || !next_step()) break; continue; }
             const unsigned long long Rt = transpose64(mine ? m : 0ull, trc);        // lane r: bit k <=> record k of the step has id r of the block
             unsigned long long ra0, ra1;
             {
@@ -1203,9 +1232,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         }
         // write-back: one HBM atomic per non-zero cell (D layout of the MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)).  Cell (rb + r, rb + c)
         // of the triangle sits at tri64(rb) + rb + [rb r + r (r - 1) / 2 + c]: a wave-uniform base and a 32-bit offset per lane
+        if constexpr (BAND) if (culled) continue;
         const uint32_t rb = X0 * q.bwidth;
-        uint32_t* const Mb = q.M + (tri64((uint64_t)rb) + rb);
-        const uint32_t lim = q.N - rb;                                  // rows of the block inside the matrix (masks never hold an id beyond N: belt and braces)
+        // (band: the base is relative to the band's first cell — it may lie in front of the buffer where the band starts inside this block; the row
+        // window below is tested before any address made from it is used)
+        uint32_t* Mb;
+        if constexpr (BAND) Mb = q.M + ((int64_t)(tri64((uint64_t)rb) + rb) - (int64_t)band.w.cell_lo);
+        else Mb = q.M + (tri64((uint64_t)rb) + rb);
+        uint32_t lim = q.N - rb;                                        // rows of the block inside the matrix (masks never hold an id beyond N: belt and braces)
+        uint32_t first = 0;                                             // band: the block's rows [first, lim) are the band's
+        if constexpr (BAND) {
+            first = band.w.row_lo > rb ? band.w.row_lo - rb : 0u;
+            lim = band.w.row_hi - rb < lim ? band.w.row_hi - rb : lim;  // (row_hi > rb: the tile is not culled)
+        }
         // (the lane's part of the 48 offsets and conditions does not depend on the tile: seen through, it is computed once before the loop and kept — some
         // hundred registers beside the 48 accumulators.  Behind the empty asm it is a few instructions per atomic, computed where it is used.)
         uint32_t h4 = 4u * half, lc = l31;
@@ -1215,13 +1254,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             const uint32_t row0 = (uint32_t)((r & 3) + 8 * (r >> 2)) + h4, row1 = row0 + 32u;
             const uint32_t o0 = rb * row0 + row0 * (row0 - 1u) / 2u + lc, o1 = rb * row1 + row1 * (row1 - 1u) / 2u + lc;
             const uint32_t v00 = (uint32_t)c00[r], v10 = (uint32_t)c10[r], v11 = (uint32_t)c11[r];
-            if (v00 && lc < row0 && row0 < lim) atomicAdd(Mb + o0, v00);
-            if (v10 && row1 < lim) atomicAdd(Mb + o1, v10);
-            if (v11 && lc < row0 && row1 < lim) atomicAdd(Mb + o1 + 32u, v11);
+            if constexpr (BAND) {
+                const bool in0 = row0 >= first && row0 < lim, in1 = row1 >= first && row1 < lim;
+                if (v00 && lc < row0 && in0) atomicAdd(Mb + o0, v00);
+                if (v10 && in1) atomicAdd(Mb + o1, v10);
+                if (v11 && lc < row0 && in1) atomicAdd(Mb + o1 + 32u, v11);
+            } else {
+                if (v00 && lc < row0 && row0 < lim) atomicAdd(Mb + o0, v00);
+                if (v10 && row1 < lim) atomicAdd(Mb + o1, v10);
+                if (v11 && lc < row0 && row1 < lim) atomicAdd(Mb + o1 + 32u, v11);
+            }
         }
         if (lane == 0 && q.touched) q.touched[tri32(X0) + X0] = 1;      // (all2all-sp scans only the tiles a call added to)
     }
 }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k2d_kernel(const DParams q) { k2d_body<false>(q, BandArg<false>{}); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k2d_band_kernel(const DParams q, const BandArg<true> band) { k2d_body<true>(q, band); }
 
 // ------------------------------------------------------------------------------------------
 // wide list: compaction of the flagged nodes
@@ -1962,10 +2010,12 @@ __device__ __forceinline__ uint32_t k2_apply_mfma(const K2Item& it, uint32_t dig
 }
 
 // one run (the records of one block pair inside a window): accumulate, once per weight digit that occurs, and flush the tile
-template <bool SORTED>
+// (BAND: M is the band's buffer and a cell is written iff its row is one of the band's — BandWin; the callers cull the runs of other block rows before they get here)
+template <bool SORTED, bool BAND = false>
 __device__ __forceinline__ void k2_run(const K2Item& it, uint32_t* acc, uint32_t* wor_sh,
                                        unsigned char (*wbuf)[64], const unsigned long long* lut_ff, const unsigned long long* lut_01,
-                                       uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, unsigned char* __restrict__ touched) {
+                                       uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, unsigned char* __restrict__ touched,
+                                       const BandArg<BAND>& band = BandArg<BAND>{}) {
     for (uint32_t k = threadIdx.x; k < 64 * 64; k += 256) acc[k] = 0;
     if (threadIdx.x == 0) { *wor_sh = 0; if (touched && !it.rect_cols) touched[tri32(it.X) + it.Y] = 1; }      // (the tile gets something: all2all-sp scans only such tiles)
     __syncthreads();
@@ -1983,6 +2033,8 @@ __device__ __forceinline__ void k2_run(const K2Item& it, uint32_t* acc, uint32_t
         const uint32_t v = acc[k];
         if (!v) continue;
         const uint64_t row = (uint64_t)it.X * bwidth + (k >> 6), col = (uint64_t)it.Y * bwidth + (k & 63u);
+        if constexpr (BAND) { if (row >= band.w.row_lo && row < band.w.row_hi && row < N && col < row) atomicAdd(&M[tri64(row) - band.w.cell_lo + col], v); }
+        else
         if (it.rect_cols) { if (row < N && col < it.rect_cols) atomicAdd(&M[row * it.rect_cols + col], v); }
         else if (row < N && col < row) atomicAdd(&M[tri64(row) + col], v);
     }
@@ -2046,11 +2098,15 @@ __global__ void l2_lists_kernel(const uint32_t* __restrict__ ent_g, const uint16
 // masks and the weight gathered (the next step's while this one is applied), two bit transposes, byte spreading, eight MFMAs, as
 // k2_apply_mfma does for 64 sorted records.  The queue's tail is drained by a last, empty round of the same loop (one call site of the step:
 // inlined twice, the kernel ran at two waves per SIMD).  Weights of 128 and more: one join per base-128 digit that occurs.
+// BAND (BandWin): a tile of a block row outside the band leaves before it reads a bitmap word or a list, and the write-back is windowed.
 constexpr uint32_t L2_WAVES = 4, L2_QCAP = 576;
-__global__ __launch_bounds__(64 * L2_WAVES) __attribute__((amdgpu_waves_per_eu(3, 8)))
+// (The whole-matrix form keeps its three waves per SIMD and the 11 registers in scratch it has there.  The band form asks for two: with the window's
+// operands beside the join it would spill as well, and a band call runs the tiles of a few block rows — room per wave counts for more than waves.)
+template <bool BAND>
+__global__ __launch_bounds__(64 * L2_WAVES) __attribute__((amdgpu_waves_per_eu(BAND ? 2 : 3, 8)))
 void l2_join_apply_kernel(const unsigned long long* __restrict__ B, const uint32_t* __restrict__ R, const unsigned long long* __restrict__ L, const uint32_t* __restrict__ Wt,
                           const uint32_t* __restrict__ loff, uint32_t w_stride, uint32_t nb_blocks, uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth,
-                          unsigned char* __restrict__ touched) {
+                          unsigned char* __restrict__ touched, const BandArg<BAND> band) {
     uint32_t W;
     __shared__ uint32_t q[L2_WAVES][L2_QCAP];
     __shared__ uint32_t q2[L2_WAVES][L2_QCAP];
@@ -2061,6 +2117,11 @@ void l2_join_apply_kernel(const unsigned long long* __restrict__ B, const uint32
     const uint32_t t = blockIdx.x;
     const uint32_t X = stream_row(t), Y = t - tri32(X);
     if (loff[X + 1] == loff[X] || loff[Y + 1] == loff[Y]) return;       // (uniform over the workgroup)
+    if constexpr (BAND) {
+        const bool culled = band_culls(band.w, X);
+        if (threadIdx.x == 0) band_unit(band.w, t, BU_TILES, !culled);
+        if (culled) return;
+    }
     W = loff[nb_blocks + 1u];                       // the bitmap words in use (l2_offsets_kernel); rows of the bitmaps stay w_stride apart
     const bool diag = X == Y;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -2207,16 +2268,20 @@ void l2_join_apply_kernel(const unsigned long long* __restrict__ B, const uint32
         const uint32_t v = acc[k];
         if (!v) continue;
         const uint64_t row = (uint64_t)X * bwidth + (k >> 6), col = (uint64_t)Y * bwidth + (k & 63u);
-        if (row < N && col < row) atomicAdd(&M[tri64(row) + col], v);
+        if constexpr (BAND) { if (row >= band.w.row_lo && row < band.w.row_hi && row < N && col < row) atomicAdd(&M[tri64(row) - band.w.cell_lo + col], v); }
+        else if (row < N && col < row) atomicAdd(&M[tri64(row) + col], v);
     }
 }
 
 constexpr uint32_t K2_WIN = 32;            // sorted chunks per workgroup at most; the launch picks 16 (few streams: measured better) or 32
 constexpr int K2A_MIN_WAVES = 3;
+// (BAND, BandWin: a run of the window whose key names a block row outside the band is passed over before one of its records is read)
+template <bool BAND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2A_MIN_WAVES, 8))) void k2_apply_kernel(const unsigned char* __restrict__ rec, const uint32_t* __restrict__ recw,
                                                        const uint32_t* __restrict__ sorted_key, const uint32_t* __restrict__ sorted_id,
                                                        const uint32_t* __restrict__ chunk_fill, uint32_t n_states, const uint32_t* __restrict__ n_chunks_ptr,
-                                                       uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, uint32_t win, unsigned char* __restrict__ touched) {
+                                                       uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, uint32_t win, unsigned char* __restrict__ touched,
+                                                       const BandArg<BAND> band) {
     __shared__ uint32_t acc[64 * 64];
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[4][64];
     __shared__ unsigned long long lut_ff[256], lut_01[256];       // byte b -> its 8 bits spread over 8 bytes (0xFF / 0x01 where set)
@@ -2252,7 +2317,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2A_MIN_WAV
             it.X = X; it.Y = bucket - tri32(X);
             it.count = (b - a) * CH_STEPS; it.ids = s_id + a; it.fills = s_fill + a; it.srec = nullptr; it.n_rec = 0; it.rec = rec; it.recw = recw; it.rect_cols = 0; it.pshift = 0;
         }
-        k2_run<false>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched);
+        if constexpr (BAND) {
+            const bool culled = band_culls(band.w, it.X);
+            if (threadIdx.x == 0) band_unit(band.w, blockIdx.x, BU_RUNS, !culled);
+            if (culled) { a = b; continue; }
+        }
+        k2_run<false, BAND>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched, band);
         a = b;
     }
 }
@@ -2781,9 +2851,12 @@ __global__ __launch_bounds__(1024) void k2j_build_kernel(const uint32_t* __restr
     uint32_t o = base_sh + wsum[wave] + incl - nj;
     for (uint32_t part = 0; part < nj; ++part, ++o) if (o < cap) jobs[o] = make_uint2(s, part);
 }
+// (BAND, BandWin: a job whose stream lies in a block row outside the band leaves with its job word read and nothing else)
+template <bool BAND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAVES, 8))) void k2_jobs_kernel(const uint32_t* __restrict__ swkey, const WideRec* __restrict__ swrec,
                                                         const uint32_t* __restrict__ start, const uint2* __restrict__ jobs, const uint32_t* __restrict__ n_jobs, uint32_t cap,
-                                                        uint32_t limit, uint32_t pshift, uint32_t kbits, uint32_t dbits, uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, unsigned char* __restrict__ touched) {
+                                                        uint32_t limit, uint32_t pshift, uint32_t kbits, uint32_t dbits, uint32_t* __restrict__ M, uint32_t N, uint32_t bwidth, unsigned char* __restrict__ touched,
+                                                        const BandArg<BAND> band) {
     __shared__ uint32_t acc[64 * 64];
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[4][64];
     __shared__ unsigned long long lut_ff[256], lut_01[256];
@@ -2791,6 +2864,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
     const uint32_t nj = *n_jobs < cap ? *n_jobs : cap;
     if (blockIdx.x >= nj) return;
     const uint2 job = jobs[blockIdx.x];
+    if constexpr (BAND) {
+        const bool culled = band_culls(band.w, stream_row(job.x));
+        if (threadIdx.x == 0) band_unit(band.w, blockIdx.x, BU_JOBS, !culled);
+        if (culled) return;
+    }
     {
         unsigned long long v = 0;
 #pragma unroll
@@ -2809,7 +2887,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
     it.X = stream_row(job.x); it.Y = job.x - tri32(it.X); it.rect_cols = 0; it.pshift = pshift;
     it.n_rec = b - a; it.count = (it.n_rec + 63u) / 64u; it.ids = nullptr; it.fills = nullptr; it.srec = swrec + a; it.skey = swkey + a; it.kbits = kbits; it.dbits = dbits;
     it.rec = nullptr; it.recw = nullptr;
-    k2_run<true>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched);
+    k2_run<true, BAND>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched, band);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3060,6 +3138,12 @@ struct BlocksState {
     DevBuf<uint32_t> k2j_start;     // [n_states + 1] many streams: where every stream starts in the sorted arrays
     DevBuf<uint2> k2j_jobs;         // [k2j_cap] jobs of the apply kernel: {stream, part of K2J_REC records}
     uint64_t k2j_cap = 0;
+    // ---- a call for a band of rows (kmdb_blocks_run with a kmdb_band_desc): the band as the apply kernels take it, for the call's duration, and the
+    // units they counted (BandWin::units; made on the handle's first band call)
+    bool band_on = false;
+    BandWin band{};
+    DevBuf<uint32_t> band_units;    // [BAND_UNIT_SLOTS * BAND_UNIT_WORDS]
+    kmdb_blocks_band_units last_band_units{};
 
     ~BlocksState() { if (h_counters) (void)hipHostFree(h_counters); }
 };
@@ -3569,7 +3653,10 @@ int a2a_slice_apply(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hi
     const uint32_t sl = b.knobs.k2d_slices;
     d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = b.tile_touched;
     const uint32_t waves = (db->n_nsegs + sl - 1u) / sl;
-    if (waves) hipLaunchKernelGGL(k2d_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d);
+    if (waves) {
+        if (b.band_on) hipLaunchKernelGGL(k2d_band_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d, BandArg<true>{b.band});
+        else hipLaunchKernelGGL(k2d_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(db->ev_side[1], s2));               // (the call's end waits for the side stream; many streams: recorded again behind the chunk table's work)
     (void)stage_done(s2, "slice apply");
@@ -3594,9 +3681,14 @@ int a2a_group_and_apply_chunks(kmdb_db* db, BlocksState& b, uint32_t* M, hipStre
     const uint32_t win = b.n_states <= CS_MAX_KEYS ? 16u : 32u;      // (8 / 32 / 64 chunks at few streams: within the boxes' noise, profiles/r05_j5)
     uint32_t grid = (pool_cap + win - 1) / win;
     if (b.have_counts) grid = std::min(grid, (b.last_n_chunks + win - 1) / win);
-    if (grid)
-        hipLaunchKernelGGL(k2_apply_kernel, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
-                           b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched);
+    if (grid) {
+        if (b.band_on)
+            hipLaunchKernelGGL(k2_apply_kernel<true>, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
+                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched, BandArg<true>{b.band});
+        else
+            hipLaunchKernelGGL(k2_apply_kernel<false>, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
+                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched, BandArg<false>{});
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(db->ev_side[1], s2));
     (void)stage_done(s2, "chunk apply");
@@ -3693,8 +3785,12 @@ int a2a_wide_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, ui
         hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, b.l2_len, NB, b.l2_cursors, W, b.l2_loff);
         hipLaunchKernelGGL(l2_lists_kernel, dim3((b.l2_ent_cap + 255u) / 256u), dim3(256), 0, st, b.l2_ent_g, b.l2_ent_blk, b.l2_ent_mask, b.l2_node_w,
                            b.l2_ent_cap, W, b.l2_bitmap, b.l2_rank, b.l2_loff, b.l2_list_mask, b.l2_list_w, b.l2_cursors);
-        hipLaunchKernelGGL(l2_join_apply_kernel, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
-                           b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched);
+        if (b.band_on)
+            hipLaunchKernelGGL(l2_join_apply_kernel<true>, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
+                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched, BandArg<true>{b.band});
+        else
+            hipLaunchKernelGGL(l2_join_apply_kernel<false>, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
+                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched, BandArg<false>{});
     }
     return 0;
 }
@@ -3703,9 +3799,16 @@ int a2a_wide_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, ui
 void a2a_apply_stream_jobs(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, Launched& L) {
     hipLaunchKernelGGL(k2j_build_kernel, dim3((b.n_states + 1023u) / 1024u), dim3(1024), 0, st, b.k2j_start, b.n_states, b.k2j_jobs, (uint32_t)b.k2j_cap, b.counters);
     L.k2jobs = b.have_counts ? b.last_n_k2jobs : (uint32_t)b.k2j_cap;       // (the streams' lengths repeat exactly from call to call)
-    if (L.k2jobs)
-        hipLaunchKernelGGL(k2_jobs_kernel, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
-                           (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width, b.tile_touched);
+    if (L.k2jobs) {
+        if (b.band_on)
+            hipLaunchKernelGGL(k2_jobs_kernel<true>, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
+                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width,
+                               b.tile_touched, BandArg<true>{b.band});
+        else
+            hipLaunchKernelGGL(k2_jobs_kernel<false>, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
+                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width,
+                               b.tile_touched, BandArg<false>{});
+    }
 }
 // ---- 8. many streams: chunk table grouped (stream chunks -> side stream), then the sort inside the block rows and its apply
 int a2a_sort_apply_rows(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hipStream_t s2, Launched& L) {
@@ -3883,10 +3986,17 @@ int a2a_settle(kmdb_db* db, BlocksState& b, hipStream_t st, const Launched& L, b
 }
 // one attempt of the whole pipeline; *retry is set when a pool was too small (it has been enlarged)
 // decode: run K0 (the first slice of a call does; what it leaves — the local (block, mask) pairs of every node — serves all slices)
-int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry) {
+// band (may be null): M holds that band of rows only — the emit stages run as ever, every apply launch takes its BAND instantiation
+int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry, const kmdb_band_desc* band) {
     BlocksState& b = *db->blocks;
     hipStream_t s2 = db->stream2;
     *retry = false;
+    b.band_on = band != nullptr;
+    if (band) {
+        // (row_lo < row_hi <= N: the caller's checks; an empty band never gets here)
+        b.band = BandWin{(uint32_t)band->row_lo, (uint32_t)band->row_hi, (uint32_t)(band->row_lo / db->width), (uint32_t)((band->row_hi - 1) / db->width), band->cell_lo,
+                         b.band_units.get()};
+    }
     Launched L;
     if (b.have_counts) L.raw = (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), b.row_mode ? 0xFFFFFFFFull : b.wide_pool_cap);
     a2a_prologue(b, st, decode);
@@ -3927,10 +4037,25 @@ static void blocks_join_side_streams(kmdb_db* db) {
     if (db->stream2) (void)hipStreamSynchronize(db->stream2);
 }
 
-int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st) {
+// the band call's unit counters, summed over their slots
+static int blocks_read_band_units(BlocksState& b, hipStream_t st) {
+    std::vector<uint32_t> h((size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS);
+    HIP_TRY(hipMemcpyAsync(h.data(), b.band_units, h.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t c[BU_COUNT] = {};
+    for (uint32_t s = 0; s < BAND_UNIT_SLOTS; ++s) for (uint32_t k = 0; k < BU_COUNT; ++k) c[k] += h[(size_t)s * BAND_UNIT_WORDS + k];
+    b.last_band_units = kmdb_blocks_band_units{c[BU_JOBS], c[BU_JOBS_RUN], c[BU_RUNS], c[BU_RUNS_RUN], c[BU_SLICES], c[BU_SLICES_RUN], c[BU_TILES], c[BU_TILES_RUN]};
+    return 0;
+}
+
+int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band) {
     BlocksState& b = *db->blocks;
-    const uint64_t cells = db->N * (db->N - 1) / 2;
+    // what a repeated round zeroes: the words of M — the whole triangle, or the band's cells only
+    const uint64_t cells = band ? band->cells : db->N * (db->N - 1) / 2;
+    if (band && !b.band_units) DEV_ALLOC(b.band_units, (size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS);
+    struct BandOff { BlocksState& b; ~BandOff() { b.band_on = false; } } band_off{b};      // (the state never names a band beyond its call)
     for (int round = 0; round < 64; ++round) {
+        if (band) HIP_TRY(hipMemsetAsync(b.band_units, 0, (size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS * 4, st));
         // (the tiles this call adds to, all its slices: tile_touched is cleared by the prologue of the round's first attempt, the one that decodes)
         // the slices of [emit_lo, emit_hi) one after the other, adding into the same matrix; a pass that had to enlarge a pool (or
         // asked for more slices) leaves a partial sum behind: everything again from a zeroed matrix
@@ -3949,7 +4074,7 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
             if (b.have_counts) { b.last_n_wide = sc.n_wide; b.last_n_chunks = sc.n_chunks; b.last_n_raw = sc.n_raw; b.last_n_rowjobs = sc.n_rowjobs; b.last_n_sorted = sc.n_sorted; b.last_n_k2jobs = sc.n_k2jobs; }
             if (!b.have_counts) db->last_call_sized = true;
             bool retry = false;
-            if (blocks_attempt(db, M, lo, hi, !decoded, st, &retry)) { blocks_join_side_streams(db); return 1; }
+            if (blocks_attempt(db, M, lo, hi, !decoded, st, &retry, band)) { blocks_join_side_streams(db); return 1; }
             decoded = true;
             if (!db->fallback_reason.empty()) return 0;
             if (retry) { again = true; for (auto& c : b.slice_counts) c.valid = false; }
@@ -3959,8 +4084,11 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
                 direct += b.last_n_direct;
             }
         }
-        if (!again) { b.last_records = records; b.last_n_direct = direct; b.have_counts = true; return 0; }
-        HIP_TRY(hipMemsetAsync(M, 0, cells * 4, st));
+        if (!again) {
+            b.last_records = records; b.last_n_direct = direct; b.have_counts = true;
+            return band ? blocks_read_band_units(b, st) : 0;
+        }
+        if (cells) HIP_TRY(hipMemsetAsync(M, 0, cells * 4, st));
     }
     return kmdb_set_error("kmdb_blocks_run: the record pools did not converge");
 }
@@ -3971,3 +4099,6 @@ kmdb_blocks_counts kmdb_blocks_last_counts(const kmdb_db* db) {
     return kmdb_blocks_counts{b.last_records, b.last_n_direct, b.last_n_wide, b.last_n_chunks, b.l2_on ? b.last_l2_nodes : 0u};
 }
 const unsigned char* kmdb_blocks_tile_touched(const kmdb_db* db) { return db->blocks ? db->blocks->tile_touched.get() : nullptr; }
+kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db) { return db->blocks ? db->blocks->last_band_units : kmdb_blocks_band_units{}; }
+int kmdb_blocks_k1n_mode(const kmdb_db* db) { return db->blocks ? db->blocks->k1n_mode : -1; }
+uint32_t kmdb_blocks_n_slices(const kmdb_db* db) { return db->blocks ? std::max<uint32_t>(1u, db->blocks->n_slices) : 1u; }

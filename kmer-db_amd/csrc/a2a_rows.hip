@@ -133,29 +133,6 @@ uint64_t tri_h(uint64_t i) { return i ? i * (i - 1) / 2 : 0; }
 // what the band path keeps on the handle between calls
 uint64_t rows_device_bytes(const kmdb_db* db) { return db->rows_sel.bytes() + db->rows_counters.bytes(); }
 
-// argument checks shared by the two entry points; 0, or 1 with the error set
-int rows_check(const char* who, const kmdb_db* db, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts) {
-    const std::string w(who);
-    if (row_lo > row_hi) return kmdb_set_error(w + ": row_lo > row_hi (" + std::to_string(row_lo) + " > " + std::to_string(row_hi) + ")");
-    if (row_hi > db->N) return kmdb_set_error(w + ": row_hi " + std::to_string(row_hi) + " > the " + std::to_string(db->N) + " samples of the database");
-    if (opts && opts->shard_count > 1) return kmdb_set_error(w + ": a band needs the whole pattern stream (shard_count must be 1)");
-    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error(w + ": unknown bits in kmdb_opts.flags");
-    if (db->qs_count > 1) return kmdb_set_error(w + ": not on a query shard (kmdb_db_upload_query_shard): its tree holds one shard's k-mers only");
-    return 0;
-}
-
-// a band too large to exist: from 2^32 cells on, its bytes against `limit` bytes of device memory
-int rows_check_bytes(const char* who, uint64_t band_cells, bool against_free) {
-    if (band_cells < (1ull << 32)) return 0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t limit = against_free ? free_b : total_b;
-    if (band_cells > limit / 4)
-        return kmdb_set_error(std::string(who) + ": the band is " + std::to_string(band_cells) + " cells, " + std::to_string(band_cells * 4) + " bytes, beyond the " +
-                              std::to_string(limit) + " bytes of " + (against_free ? "free device memory" : "device memory"));
-    return 0;
-}
-
 int rows_run(kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipStream_t st) {
     const uint64_t N = db->N, P = db->P;
     const uint64_t cell_lo = tri_h(row_lo), band_cells = tri_h(row_hi) - cell_lo;
@@ -220,13 +197,36 @@ int rows_run(kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipSt
 
 }  // namespace
 
+// argument checks shared by every band call (engine_internal.h); 0, or 1 with the error set
+int kmdb_band_check(const char* who, const kmdb_db* db, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts) {
+    const std::string w(who);
+    if (row_lo > row_hi) return kmdb_set_error(w + ": row_lo > row_hi (" + std::to_string(row_lo) + " > " + std::to_string(row_hi) + ")");
+    if (row_hi > db->N) return kmdb_set_error(w + ": row_hi " + std::to_string(row_hi) + " > the " + std::to_string(db->N) + " samples of the database");
+    if (opts && opts->shard_count > 1) return kmdb_set_error(w + ": a band needs the whole pattern stream (shard_count must be 1)");
+    if (opts && (opts->flags & ~KMDB_FLAG_ALL)) return kmdb_set_error(w + ": unknown bits in kmdb_opts.flags");
+    if (db->qs_count > 1) return kmdb_set_error(w + ": not on a query shard (kmdb_db_upload_query_shard): its tree holds one shard's k-mers only");
+    return 0;
+}
+
+// a band too large to exist: from 2^32 cells on, its bytes against `limit` bytes of device memory
+int kmdb_band_check_bytes(const char* who, uint64_t band_cells, bool against_free) {
+    if (band_cells < (1ull << 32)) return 0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t limit = against_free ? free_b : total_b;
+    if (band_cells > limit / 4)
+        return kmdb_set_error(std::string(who) + ": the band is " + std::to_string(band_cells) + " cells, " + std::to_string(band_cells * 4) + " bytes, beyond the " +
+                              std::to_string(limit) + " bytes of " + (against_free ? "free device memory" : "device memory"));
+    return 0;
+}
+
 extern "C" int kmdb_all2all_rows_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts) {
     if (!db) return kmdb_set_error("kmdb_all2all_rows_device: null argument");
-    if (rows_check("kmdb_all2all_rows_device", db, row_lo, row_hi, opts)) return 1;
+    if (kmdb_band_check("kmdb_all2all_rows_device", db, row_lo, row_hi, opts)) return 1;
     const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
     if (!out_cells_dev && band_cells) return kmdb_set_error("kmdb_all2all_rows_device: null argument");
     HIP_TRY(hipSetDevice(db->device));
-    if (rows_check_bytes("kmdb_all2all_rows_device", band_cells, false)) return 1;
+    if (kmdb_band_check_bytes("kmdb_all2all_rows_device", band_cells, false)) return 1;
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
     const int rc = rows_run(db, (uint32_t*)out_cells_dev, row_lo, row_hi, st);
     kmdb_release_staging(db);
@@ -235,11 +235,11 @@ extern "C" int kmdb_all2all_rows_device(kmdb_db* db, uint64_t row_lo, uint64_t r
 
 extern "C" int kmdb_all2all_rows(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts) {
     if (!db) return kmdb_set_error("kmdb_all2all_rows: null argument");
-    if (rows_check("kmdb_all2all_rows", db, row_lo, row_hi, opts)) return 1;
+    if (kmdb_band_check("kmdb_all2all_rows", db, row_lo, row_hi, opts)) return 1;
     const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
     if (!out_cells_host && band_cells) return kmdb_set_error("kmdb_all2all_rows: null argument");
     HIP_TRY(hipSetDevice(db->device));
-    if (rows_check_bytes("kmdb_all2all_rows", band_cells, true)) return 1;
+    if (kmdb_band_check_bytes("kmdb_all2all_rows", band_cells, true)) return 1;
     DevBuf<uint32_t> band;
     DEV_ALLOC(band, std::max<uint64_t>(band_cells, 1));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;

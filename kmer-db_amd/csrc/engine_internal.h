@@ -114,6 +114,11 @@ int kmdb_sample_query_rows(const char* who, hipStream_t st, int kmer_length, con
 // Tree form on the node arrays of kmdb_ensure_v1_arrays: a select launch (a lane per node) and an apply launch (a fixed grid of waves over the
 // selected nodes) that add the cells [tri(row_lo), tri(row_hi)) and no other; the id stacks are the handle's stack_scratch, shared with a2a_v1.hip.
 constexpr int KMDB_ROWS_LDS_CAP = 1024;   // a full list of up to this many ids is rebuilt on the wave's LDS stack, a longer one in global scratch
+// The argument checks every band call shares (a2a_rows.hip; a2a_band.hip and a2a_rows_records.hip refuse the same cases in the same words under their
+// own names): row_lo <= row_hi <= N, shard_count 1, known flag bits, no query shard; and a band of 2^32 cells or more against the device's memory
+// (against_free: its free memory — the call allocates the band itself).  0, or 1 with the error set.
+int kmdb_band_check(const char* who, const kmdb_db* db, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts);
+int kmdb_band_check_bytes(const char* who, uint64_t band_cells, bool against_free);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

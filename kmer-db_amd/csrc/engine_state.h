@@ -1,6 +1,7 @@
 // engine_state.h — the HBM-resident database shared by the translation units of libkmdb_amd.so
 // (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, a2a_rows.hip: a band of
-// the matrix's rows, a2a_band.hip: the same band summed in LDS tiles and a run walked in bands, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
+// the matrix's rows, a2a_band.hip: the same band summed in LDS tiles and a run walked in bands, a2a_rows_records.hip: the same band through the
+// block-record pipeline, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
 #pragma once
 #include "kmdb_amd.h"
 #include "kmdb_internal.h"
@@ -108,6 +109,9 @@ struct kmdb_db {
     uint64_t band_bytes_counted = 0;    // these arrays' share of stats.device_bytes as last counted
     kmdb_all2all_rows_tiled_stats band_stats{};  // the last tiled call on the handle (kmdb_all2all_rows_tiled_stats_get)
     kmdb_all2all_banded_stats banded_stats{};    // the last banded call on the handle (kmdb_all2all_banded_stats_get)
+    // ---- the band call through the block-record pipeline (a2a_rows_records.hip; its device state is the pipeline's own)
+    kmdb_all2all_rows_records_stats rr_stats{};  // the last such call on the handle (kmdb_all2all_rows_records_stats_get)
+    kmdb_all2all_banded_records_stats banded_rr_stats{};   // the last banded call on the records path (kmdb_all2all_banded_records_stats_get)
     // hashtables (new2all)
     uint64_t n_buckets = 0;
     DevBuf<uint64_t> bucket_offset;
@@ -168,7 +172,16 @@ int kmdb_v1_run(kmdb_db* db, uint32_t* M, uint32_t seg_begin, uint32_t seg_end, 
 // upload-time: block width from a sampled estimate, working-set allocation
 int kmdb_blocks_prepare(kmdb_db* db);
 // per call: decode, narrow / wide emit, apply — everything that depends on a sample id happens here
-int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st);
+// band == nullptr: M is the whole triangle.  Else M holds the rows [row_lo, row_hi) only — `cells` words, the first of them cell `cell_lo` = tri(row_lo) of
+// the triangle: decode, emit and sort run whole, the apply stage culls the block rows outside the band and windows its write-back (a2a_rows_records.hip)
+struct kmdb_band_desc { uint64_t row_lo, row_hi, cell_lo, cells; };
+int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band = nullptr);
+// the apply units of the last band call: stream jobs, window runs of stream chunks, slices' tiles of first-block records, second-level tiles
+struct kmdb_blocks_band_units { uint64_t jobs, jobs_run, runs, runs_run, slices, slices_run, tiles, tiles_run; };
+kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db);
+// what a band caller asks before it runs: the narrow kernel's mode (KMDB_K1N_MODE; 1 writes the matrix itself), passes over the pattern stream per call
+int kmdb_blocks_k1n_mode(const kmdb_db* db);
+uint32_t kmdb_blocks_n_slices(const kmdb_db* db);
 void kmdb_blocks_release(kmdb_db* db);
 uint64_t kmdb_blocks_device_bytes(const kmdb_db* db);
 // what the last kmdb_blocks_run found (the statistics of the call), and the tiles it added to: [block pairs] != 0, or null without a working set

@@ -6,6 +6,7 @@
 //     kmer-db-amd all2all | all2all-sp [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <out>
 //     kmer-db-amd all2all | all2all-sp -rows <lo>:<hi> | new [the forms above] <db> <out>
 //     kmer-db-amd all2all | all2all-sp -band-rows <R> [the forms above] <db> <out>
+//     kmer-db-amd all2all | all2all-sp -rows ... | -band-rows <R> -band-path <tree|tiled|records> [the forms above] <db> <out>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse ...]  <db> <sample-list> <out.csv>
 //     kmer-db-amd new2all    [-multisample-fasta] [-sparse] [-phylip-out] [-min ...] [-max ...] -distance <measure> <db> <sample-list> <out>
 //     kmer-db-amd one2all    <db> <sample> <out.csv>
@@ -260,6 +261,24 @@ void report_rows_tiled_stats(const kmdb_db* d, uint64_t lo, uint64_t hi) {
               << bs.tile_cols << " columns, select " << bs.select_ms << " ms, hits " << bs.hits_ms << " ms, apply " << bs.apply_ms << " ms, " << bs.scratch_bytes
               << " bytes of scratch" << std::endl;
 }
+// the same for the band call through the block-record pipeline (-band-path records)
+void report_rows_records_stats(const kmdb_db* d, uint64_t lo, uint64_t hi) {
+    kmdb_all2all_rows_records_stats rs{};
+    if (!std::getenv("KMDB_VERBOSE") || kmdb_all2all_rows_records_stats_get(d, &rs)) return;
+    std::cerr << "[kmdb] all2all rows records: rows " << lo << " to " << hi << ", " << rs.band_cells << " cells, "
+              << (rs.path == KMDB_ROWS_RECORDS_PATH_RECORDS ? "block records" : rs.path == KMDB_ROWS_RECORDS_PATH_TREE ? "tree fallback" : "nothing to do")
+              << ", block rows " << rs.x_lo << " to " << rs.x_hi << " of width " << rs.width << ", " << rs.records << " records, apply units run / total " << rs.units_run
+              << " / " << rs.units_total << ", " << rs.slices << " slices, sized call " << rs.sized_call << ", decode " << rs.k0_ms << " ms, narrow " << rs.k1n_ms
+              << " ms, wide " << rs.k1g_ms << " ms, apply " << rs.k2_ms << " ms, call " << rs.kernel_ms << " ms, peak " << rs.peak_device_bytes << " bytes" << std::endl;
+}
+// -band-path <tree|tiled|records>: the band call of -rows / -band-rows
+enum class BandPath { unset, tree, tiled, records };
+BandPath parse_band_path(const std::string& v) {
+    if (v == "tree") return BandPath::tree;
+    if (v == "tiled") return BandPath::tiled;
+    if (v == "records") return BandPath::records;
+    throw std::runtime_error("-band-path expects tree, tiled or records: " + v);
+}
 // -band-rows <R>: a number of rows, 1 or more
 uint64_t parse_band_rows(const std::string& v) {
     if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos || std::strtoull(v.c_str(), nullptr, 10) == 0)
@@ -278,14 +297,22 @@ struct Common {
     RowBand rows;                            // all2all | all2all-sp -rows
     uint64_t band_rows = 0;                  // all2all | all2all-sp -band-rows <R>: the rows are walked in bands of R, one band resident at a time (0: off)
     // the tiled band call: every band of -band-rows; with KMDB_ROWS_TILED=1 also the band of plain -rows (A/B with the same bytes)
-    bool tiled() const { const char* e = std::getenv("KMDB_ROWS_TILED"); return band_rows != 0 || (e && e[0] == '1'); }
+    // -band-path <tree|tiled|records> names the call instead (unset: the defaults above)
+    BandPath band_path = BandPath::unset;
+    bool tiled() const {
+        if (band_path != BandPath::unset) return band_path == BandPath::tiled;
+        const char* e = std::getenv("KMDB_ROWS_TILED");
+        return band_rows != 0 || (e && e[0] == '1');
+    }
     // the band [lo, hi) into device memory at `dev` by the call this run takes
     void band_to_device(kmdb_db* d, uint64_t lo, uint64_t hi, void* dev, const kmdb_opts& o) const {
-        if (tiled()) { check(kmdb_all2all_rows_tiled_device(d, lo, hi, dev, &o)); report_rows_tiled_stats(d, lo, hi); }
+        if (band_path == BandPath::records) { check(kmdb_all2all_rows_records_device(d, lo, hi, dev, &o)); report_rows_records_stats(d, lo, hi); }
+        else if (tiled()) { check(kmdb_all2all_rows_tiled_device(d, lo, hi, dev, &o)); report_rows_tiled_stats(d, lo, hi); }
         else { check(kmdb_all2all_rows_device(d, lo, hi, dev, &o)); report_rows_stats(d); }
     }
     void band_to_host(kmdb_db* d, uint64_t lo, uint64_t hi, uint32_t* host, const kmdb_opts& o) const {
-        if (tiled()) { check(kmdb_all2all_rows_tiled(d, lo, hi, host, &o)); report_rows_tiled_stats(d, lo, hi); }
+        if (band_path == BandPath::records) { check(kmdb_all2all_rows_records(d, lo, hi, host, &o)); report_rows_records_stats(d, lo, hi); }
+        else if (tiled()) { check(kmdb_all2all_rows_tiled(d, lo, hi, host, &o)); report_rows_tiled_stats(d, lo, hi); }
         else { check(kmdb_all2all_rows(d, lo, hi, host, &o)); report_rows_stats(d); }
     }
     uint64_t seed_samples = 0;               // -from-samples -extend-from <old.db>: the samples of <old.db> (set by open_database)
@@ -2890,7 +2917,14 @@ void usage() {
                  "                                  is walked in bands; with -from-samples [-extend-from <old.db>] as well.  Refused with -gpus <N>, -sample-rows\n"
                  "                                  and -phylip-out, and when R is 0 or no number.  KMDB_ROWS_TILE_COLS / KMDB_ROWS_TILE_HITS: a tile's columns\n"
                  "                                  and the hits of a share; KMDB_ROWS_TILED=1: plain -rows takes the tiled call too.  Not offered: a long\n"
-                 "                                  pattern's list decoded by several lanes.\n";
+                 "                                  pattern's list decoded by several lanes.\n"
+                 "    kmer-db-amd all2all | all2all-sp -rows <lo>:<hi> | -band-rows <R> -band-path <tree|tiled|records> [...] <database> <output>\n"
+                 "all2all / all2all-sp -band-path <tree|tiled|records>: the call every band of -rows / -band-rows comes from — tree: the pattern tree walked,\n"
+                 "                                  rows added cell by cell (the default of -rows); tiled: rows summed in LDS tiles (the default of\n"
+                 "                                  -band-rows); records: the block-record pipeline of the whole-matrix call (decode, emit and sort run whole,\n"
+                 "                                  the matrix-core apply on the band's block rows alone).  <output> holds the same bytes in all three.\n"
+                 "                                  Refused without -rows / -band-rows, with any other value and in any other mode; up to about 185 000\n"
+                 "                                  samples (2^22 block pairs), KMDB_K1N_MODE=1 is refused.  KMDB_VERBOSE: one line per band.\n";
 }
 
 }  // namespace
@@ -2955,6 +2989,13 @@ int main(int argc, char** argv) {
             }
             if (!take_option(args, "-band-rows", v)) throw std::runtime_error("-band-rows expects <R>, a number of rows of 1 or more");
             c.band_rows = parse_band_rows(v);
+        }
+        // -band-path <tree|tiled|records>: the band call of the two switches above, refused by name without them
+        if (std::find(args.begin(), args.end(), "-band-path") != args.end()) {
+            if (mode != "all2all" && mode != "all2all-sp") throw std::runtime_error("-band-path applies to all2all and all2all-sp");
+            if (!take_option(args, "-band-path", v)) throw std::runtime_error("-band-path expects tree, tiled or records");
+            c.band_path = parse_band_path(v);
+            if (!c.rows.on && !c.band_rows) throw std::runtime_error("-band-path goes with -rows <lo>:<hi> | new and / or -band-rows <R> only: it names the call a band of rows comes from");
         }
         if (mode == "all2all") return run_all2all(args, c);
         if (mode == "all2all-sp") return run_all2all_sp(args, c);
