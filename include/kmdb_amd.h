@@ -388,7 +388,8 @@ int  kmdb_all2all_banded_stats_get(const kmdb_db* db, kmdb_all2all_banded_stats*
  * itself).  A refused call leaves out_cells untouched.  An empty band succeeds and writes nothing.
  * kmdb_stats after a band call: kernel_ms and device_bytes are the band call's; path, n_records, sized_call, the stage times and the other counts
  * stay those of the last whole-matrix call on the handle — the band call's own are in kmdb_all2all_rows_records_stats.
- * Limit: the pipeline's 2^22 block pairs (about 185 000 samples at width 64); beyond it the two tree forms above are the only route. */
+ * Limit of this form: the pipeline's 2^22 block pairs (about 185 000 samples at width 64, 92 640 at width 32).  Beyond it the call takes band emit
+ * (KMDB_HAS_ALL2ALL_BAND_EMIT, below), whose limit is 2^22 streams per BAND. */
 #define KMDB_HAS_ALL2ALL_ROWS_RECORDS 1
 #define KMDB_ROWS_RECORDS_PATH_NONE     0u   /* an empty band: nothing ran */
 #define KMDB_ROWS_RECORDS_PATH_RECORDS  1u   /* the block-record pipeline */
@@ -427,6 +428,49 @@ typedef struct kmdb_all2all_banded_records_stats {   /* the LAST banded call wit
 int  kmdb_all2all_sparse_filtered_banded_path(kmdb_db* db, uint64_t band_rows, int path, const kmdb_cell_filter* filters, size_t n_filters,
                                               const uint32_t* sample_kmers, int measure, kmdb_sparse_rows* out, const kmdb_opts* opts);
 int  kmdb_all2all_banded_records_stats_get(const kmdb_db* db, kmdb_all2all_banded_records_stats* out);
+/* Band emit (KMDB_HAS_ALL2ALL_BAND_EMIT; a2a_blocks.hip): the second form of the records band call, additive in ABI 8.  The emit kernels write the block
+ * records of the band's block rows Xlo .. Xhi alone — a record (X, Y) outside them never exists — keyed RELATIVE to the band: tri32(X) - tri32(Xlo) + Y,
+ * tri32(x) = x (x + 1) / 2, with n_streams = tri32(Xhi + 1) - tri32(Xlo) keys; the sorts, the stream jobs and the second-level tiles run over the band's
+ * streams, every array indexed by block row holds Xhi - Xlo + 1 rows.  The call runs on a state of its own per handle, made at the first such call and
+ * made anew when a later band needs more streams or rows; its pools follow the band's share of the estimate.  The whole-matrix state is not touched:
+ * whole calls before and after give the same matrix and the same counts in kmdb_stats; kmdb_stats.device_bytes counts both states.
+ * Same DEFINITION, refusals and output rule as above.  Which form kmdb_all2all_rows_records[_device] takes — KMDB_BAND_EMIT, read at the handle's first
+ * records band call: unset — band emit only where the whole-matrix pipeline refused the database for "too many block pairs" and nothing else (everywhere
+ * else the call above, with its records, units and stats); 1 — every records band call the pipeline can take; 0 — never.
+ * A band is refused by band emit when its n_streams + 1 >= min(2^22, KMDB_BAND_MAX_STREAMS) (a test switch) or when the wide kernel's lists — as many
+ * entries as the collection has blocks — do not fit the LDS: the band then comes from kmdb_all2all_rows_device (path = TREE), with
+ * KMDB_FLAG_NO_FALLBACK the call fails with a message that names the streams or the bytes.  kmdb_db_fallback_reason stays the whole matrix's.
+ * Limits: a band of fewer than 2^22 streams (at 9 375 blocks, 300 000 samples at width 32, that is some 440 block rows: 14 000 rows per band) and a
+ * collection whose blocks the wide kernel's lists hold in LDS: some 7 500 blocks, 240 000 samples at width 32, 480 000 at width 64.  Beyond either the
+ * two tree forms above are the only route. */
+#define KMDB_HAS_ALL2ALL_BAND_EMIT 1
+#define KMDB_BAND_EMIT_FORM_NONE   0u   /* an empty band, a tree fallback or a failed call: no records path ran */
+#define KMDB_BAND_EMIT_FORM_WHOLE  1u   /* decode, emit and the sorts ran whole, the apply stage culled (the call above) */
+#define KMDB_BAND_EMIT_FORM_BAND   2u   /* band emit */
+typedef struct kmdb_band_geometry {
+    uint32_t x_lo, x_hi;           /* block rows the band meets: row_lo / width, (row_hi - 1) / width; 0, 0 for an empty band */
+    uint32_t n_rows;               /* x_hi - x_lo + 1; 0 for an empty band */
+    uint32_t fits;                 /* 1: n_streams + 1 < 2^22 */
+    uint64_t n_streams;            /* tri32(x_hi + 1) - tri32(x_lo); 0 for an empty band */
+    uint64_t stream_base;          /* tri32(x_lo) */
+} kmdb_band_geometry;
+/* host only, no GPU: the geometry of the band [row_lo, row_hi) of n_samples samples at block width `width` — the function the library itself calls.
+ * Refused with a message: a null out, a width outside 32 .. 64, row_lo > row_hi, row_hi > n_samples. */
+int  kmdbh_band_streams(uint64_t n_samples, uint32_t width, uint64_t row_lo, uint64_t row_hi, kmdb_band_geometry* out);
+typedef struct kmdb_all2all_rows_band_emit_stats {   /* the LAST records band call on the handle */
+    uint32_t form;                 /* KMDB_BAND_EMIT_FORM_* */
+    uint32_t x_lo, x_hi, n_rows;   /* kmdb_band_geometry of the band at the handle's width */
+    uint32_t key_bits;             /* stream bits of a key word: the band's under band emit, the whole matrix's otherwise */
+    uint32_t row_mode;             /* 1: the many-streams record path */
+    uint32_t l2_on;                /* 1: the second level is on */
+    uint32_t attempts;             /* 1 + the repeats of the call (pools enlarged, launches sized anew) */
+    uint64_t n_streams, stream_base;
+    uint64_t records;              /* block records emitted: the band's under band emit */
+    uint64_t est_records;          /* the estimate the state's pools were sized from */
+    uint64_t state_bytes;          /* device bytes of the band-emit state (0: the handle has none) */
+    uint64_t whole_state_bytes;    /* device bytes of the whole-matrix state, 0 where none exists */
+} kmdb_all2all_rows_band_emit_stats;
+int  kmdb_all2all_rows_band_emit_stats_get(const kmdb_db* db, kmdb_all2all_rows_band_emit_stats* out);
 /* ---------------------------------------------------------------------------------------
  * all2all-sp -sample-rows <criterion>:<count> (params.cpp:533-557): every sample keeps its `count` best neighbours.  A pair (i, j), i > j, with
  * a non-zero cell that passes the filters has ONE score, metric(cell, kmers[i], kmers[j], k) with the triangle's row i as the row sample, and is

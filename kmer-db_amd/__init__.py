@@ -19,6 +19,7 @@ from .capi import (  # noqa: F401
     SparseRows,
     device_count,
     ALPHABETS,
+    band_streams,
     extract_kmers,
     extract_kmers_alphabet,
     format_dense_row,

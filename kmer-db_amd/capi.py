@@ -162,6 +162,16 @@ class _All2allBandedRecordsStats(C.Structure):
     _fields_ = [("bands", C.c_uint64), ("units_total", C.c_uint64), ("units_run", C.c_uint64), ("ms", C.c_double)]
 
 
+class _BandGeometry(C.Structure):
+    _fields_ = [("x_lo", C.c_uint32), ("x_hi", C.c_uint32), ("n_rows", C.c_uint32), ("fits", C.c_uint32), ("n_streams", C.c_uint64), ("stream_base", C.c_uint64)]
+
+
+class _All2allRowsBandEmitStats(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("x_lo", C.c_uint32), ("x_hi", C.c_uint32), ("n_rows", C.c_uint32), ("key_bits", C.c_uint32), ("row_mode", C.c_uint32),
+                ("l2_on", C.c_uint32), ("attempts", C.c_uint32), ("n_streams", C.c_uint64), ("stream_base", C.c_uint64), ("records", C.c_uint64),
+                ("est_records", C.c_uint64), ("state_bytes", C.c_uint64), ("whole_state_bytes", C.c_uint64)]
+
+
 class _New2allSparseStats(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("nnz_device", C.c_uint64), ("nnz", C.c_uint64), ("d2h_bytes", C.c_uint64), ("compact_ms", C.c_double)]
 
@@ -176,6 +186,7 @@ DISTANCE_DECLINED = 2
 PATH_NONE, PATH_RECORDS, PATH_TILE, PATH_GLOBAL = 0, 1, 2, 3
 ROWS_RECORDS_PATH_NONE, ROWS_RECORDS_PATH_RECORDS, ROWS_RECORDS_PATH_TREE = 0, 1, 2      # kmdb_all2all_rows_records_stats.path
 BAND_PATHS = ("tiled", "tree", "records")              # KMDB_BAND_PATH_*
+BAND_EMIT_FORM_NONE, BAND_EMIT_FORM_WHOLE, BAND_EMIT_FORM_BAND = 0, 1, 2      # kmdb_all2all_rows_band_emit_stats.form
 PARTITIONS = ("prefix", "range", "prefix-tables")      # KMDB_PARTITION_*
 
 # every symbol include/kmdb_amd.h declares
@@ -210,6 +221,7 @@ EXPORTS = [
     "kmdb_all2all_rows_tiled_device", "kmdb_all2all_rows_tiled", "kmdb_all2all_rows_tiled_stats_get", "kmdb_all2all_sparse_filtered_banded", "kmdb_all2all_banded_stats_get",
     "kmdb_all2all_rows_records_device", "kmdb_all2all_rows_records", "kmdb_all2all_rows_records_stats_get", "kmdb_all2all_sparse_filtered_banded_path",
     "kmdb_all2all_banded_records_stats_get",
+    "kmdb_all2all_rows_band_emit_stats_get", "kmdbh_band_streams",
 ]
 
 
@@ -272,6 +284,8 @@ def lib():
     L.kmdb_all2all_sparse_filtered_banded_path.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(_CellFilter), C.c_size_t, C.c_void_p, C.c_int, C.POINTER(_Sparse),
                                                            C.POINTER(_Opts)]
     L.kmdb_all2all_banded_records_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allBandedRecordsStats)]
+    L.kmdb_all2all_rows_band_emit_stats_get.argtypes = [C.c_void_p, C.POINTER(_All2allRowsBandEmitStats)]
+    L.kmdbh_band_streams.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(_BandGeometry)]
     L.kmdb_device_buffer_alloc.argtypes = [C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
     L.kmdb_device_buffer_free.restype = None
     L.kmdb_device_buffer_free.argtypes = [C.c_int32, C.c_void_p]
@@ -667,6 +681,14 @@ class SparseRows:
         return self.col[a:b], self.val[a:b]
 
 
+def band_streams(n_samples, width, row_lo, row_hi):
+    """kmdbh_band_streams (host only, no GPU): the geometry of the band [row_lo, row_hi) in the block-record pipeline's streams at block width `width`
+    as a dict of kmdb_band_geometry's fields"""
+    g = _BandGeometry()
+    _check(lib().kmdbh_band_streams(int(n_samples), int(width), int(row_lo), int(row_hi), C.byref(g)))
+    return {f: getattr(g, f) for f, _ in _BandGeometry._fields_}
+
+
 class DeviceDB:
     """A database resident in HBM (kmdb_db_upload)."""
 
@@ -788,6 +810,17 @@ class DeviceDB:
         s = _All2allRowsRecordsStats()
         _check(lib().kmdb_all2all_rows_records_stats_get(self._d, C.byref(s)))
         return {f: getattr(s, f) for f, _ in _All2allRowsRecordsStats._fields_}
+
+    def all2all_rows_band_emit_stats(self):
+        """kmdb_all2all_rows_band_emit_stats_get: the form the last records band call on the handle took (BAND_EMIT_FORM_*), its band's geometry in the
+        pipeline's streams, and the band-emit state"""
+        s = _All2allRowsBandEmitStats()
+        _check(lib().kmdb_all2all_rows_band_emit_stats_get(self._d, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in _All2allRowsBandEmitStats._fields_}
+
+    def band_streams(self, row_lo, row_hi, width=None):
+        """kmdbh_band_streams for this handle's samples; width: the handle's block width (known after its first all2all or band call) unless given"""
+        return band_streams(self.N, self.stats()["width"] if width is None else width, row_lo, row_hi)
 
     def all2all_banded_records_stats(self):
         """kmdb_all2all_banded_records_stats_get: the last banded call with path="records" on the handle"""

@@ -1,4 +1,5 @@
-// a2a_blocks.hip — the block-record pipeline of the dense all2all path (up to about 185 000 samples: 2^22 block pairs).
+// a2a_blocks.hip — the block-record pipeline of the dense all2all path (the whole matrix: up to about 185 000 samples, 2^22 block pairs;
+// a band of rows under band emit: fewer than 2^22 streams per BAND, keyed relative to it).
 //
 // Replaces SimilarityCalculator::all2all (reference src/similarity_calculator.cpp:42-438, inner loop row_add
 // src/simd/row_add_avx2.cpp:30-124) with a design for gfx950.  The N x N matrix is cut into blocks (X, Y), X >= Y,
@@ -36,6 +37,10 @@
 // A band of rows (kmdb_blocks_run with a kmdb_band_desc; a2a_rows_records.hip): K0, K1n, K1w and the sorts run as above, the K2 stage takes its
 //                            BAND instantiations (k2d_band_kernel, k2_apply_kernel<true>, k2_jobs_kernel<true>, l2_join_apply_kernel<true>): the units
 //                            of block rows outside the band are culled, the write-back is windowed to the band's rows and based on its first cell.
+// Band emit (kmdb_band_desc::emit; the handle's second state, kmdb_blocks_band_prepare): K1n and K1w take their BAND instantiations (k1n_band_kernel,
+//                            k1w_band_kernel) and emit the records of the band's block rows [Xlo, Xhi] alone, keyed tri32(X) - tri32(Xlo) + Y; the sorts, the stream
+//                            jobs and the second level's tiles run over the band's tri32(Xhi + 1) - tri32(Xlo) streams, everything indexed by block row holds
+//                            Xhi - Xlo + 1 rows, and every consumer that turns a key back into (X, Y) adds the base first (band_stream, RsRows::sbase).
 // db2db (kmdb_rect_sort_apply) shares cs_hist / cs_scatter and applies its sorted records with k2_sorted_kernel.
 // Records are placed WITHOUT a counting pass and WITHOUT hot global atomics (same-address device atomics run at a few million
 // per second on this part: measured, profiles/README.md): waves take chunks from 256 sub-pool cursors a few at a time, keep
@@ -52,6 +57,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
+#include <string>
 
 // counters of the block-record pipeline, zeroed at the start of every call and read back at its end
 enum : uint32_t {
@@ -87,12 +95,15 @@ __host__ __device__ __forceinline__ uint32_t tri32(uint32_t x) { return x * (x +
 // of a block row that lies half inside is written iff its row is one of the band's, at tri64(row) - cell_lo + col.  units: 64 slots of BAND_UNIT_WORDS
 // words, a slot per workgroup (mod 64) so that no counter is hot: BU_* of every apply unit the call met and of those it ran (the call's statistics).
 // The whole-matrix instantiations (BAND = false) take BandArg<false>, which is empty: nothing of this reaches them.
-struct BandWin { uint32_t row_lo, row_hi, Xlo, Xhi; uint64_t cell_lo; uint32_t* units; };
+struct BandWin { uint32_t row_lo, row_hi, Xlo, Xhi; uint64_t cell_lo; uint32_t* units; uint32_t sbase; };
 template <bool BAND> struct BandArg {};
 template <> struct BandArg<true> { BandWin w; };
 enum : uint32_t { BU_JOBS = 0, BU_JOBS_RUN, BU_RUNS, BU_RUNS_RUN, BU_SLICES, BU_SLICES_RUN, BU_TILES, BU_TILES_RUN, BU_COUNT };
 constexpr uint32_t BAND_UNIT_SLOTS = 64, BAND_UNIT_WORDS = 32;      // (a slot is one 128-byte line)
 __device__ __forceinline__ bool band_culls(const BandWin& w, uint32_t X) { return X < w.Xlo || X > w.Xhi; }
+// the stream a key names: band emit (kmdb_band_desc::emit) keys its records relative to the band's first stream, sbase = tri32(Xlo); every other call: 0
+__device__ __forceinline__ uint32_t band_stream(const BandArg<false>&, uint32_t key) { return key; }
+__device__ __forceinline__ uint32_t band_stream(const BandArg<true>& b, uint32_t key) { return key + b.w.sbase; }
 __device__ __forceinline__ void band_unit(const BandWin& w, uint32_t slot, uint32_t kind, bool ran) {
     uint32_t* c = w.units + (size_t)(slot & (BAND_UNIT_SLOTS - 1u)) * BAND_UNIT_WORDS;
     atomicAdd(c + kind, 1u);
@@ -815,6 +826,10 @@ struct NParams {
     uint32_t* slice_cnt;           // [n_segs]
     uint32_t dbg;                  // always 0 (no switch sets it).  The two tests of it in k1n_kernel<1, *> stay: without them k1n_kernel<1, 4, rows> is compiled with
                                    // 108 instead of 76 bytes of scratch per lane and measured 9.42 against 8.42 ms at C2 (profiles/a2a_cleanup_ab.json)
+    // band emit (k1n_band_kernel; no other instantiation reads these): the band's block rows [band_xlo, band_xhi] and its first stream, tri32(band_xlo).
+    // A record is emitted iff its block row X lies in the band, keyed tri32(X) - band_sbase + Y; n_keys then counts the band's block rows, and the open-chunk
+    // table and the row tables are indexed by X - band_xlo
+    uint32_t band_xlo, band_xhi, band_sbase;
 };
 constexpr int K1N_WAVES = 4;
 __host__ __device__ inline size_t k1n_wave_bytes(uint32_t chain_cap, uint32_t tbits, uint32_t n_states, uint32_t n_rows) {
@@ -836,9 +851,16 @@ __host__ __device__ inline size_t k1n_wave_bytes(uint32_t chain_cap, uint32_t tb
 // wide kernel).  The rare others — a lane whose first block is not the wave's current one, a weight of 128 or more — take the
 // records' way through the wide pool / the row chunks as in all_wide mode.
 // (NParams must stay the kernel's ONLY argument: kernarg_reread<NParams>() and PoolRef::k read it at offset 0 of the kernarg segment)
-template <int MODE, int MINW, bool ROWS>
-__global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_eu(MINW, 8))) void k1n_kernel(const NParams q) {
+// The kernel's body.  BAND = false is k1n_kernel as it always was.  BAND = true (k1n_band_kernel, modes 0 and 2) is the emit filter of a band call: the
+// walk — summaries, chain slots, the wide list's bits and counts, fn_* — is the whole tree's, a record (w0, w0), (w1, w0) or (w1, w1) is emitted iff its block
+// row lies in [band_xlo, band_xhi], keyed relative to the band's first stream; mode 0's diagonal chunks and mode 2's per-slice compaction take the same
+// filter (a slot outside the band is dropped, not culled later).
+template <int MODE, bool ROWS, bool BAND>
+__device__ __forceinline__ void k1n_body(const NParams& q) {
+    static_assert(!BAND || MODE != 1, "mode 1 writes the whole matrix from the narrow kernel: it has no band form");
     constexpr bool DIRECT = MODE == 1, FLAT = MODE == 2;
+    const uint32_t bxlo = BAND ? q.band_xlo : 0u, bsbase = BAND ? q.band_sbase : 0u;
+    auto in_band = [&](uint32_t X) -> bool { if constexpr (BAND) return X >= q.band_xlo && X <= q.band_xhi; else return true; };
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ unsigned long long lut_ff[DIRECT ? 256 : 1], lut_01[DIRECT ? 256 : 1];       // byte b -> its 8 bits spread over 8 bytes (0xFF / 0x01 where set)
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[DIRECT ? K1N_WAVES : 1][64];
@@ -1010,7 +1032,7 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
         auto first_block_records = [&]() {
             // (w0, w0, F0): the lanes of a batch mostly share the block — one reservation per block in that block's open chunk.
             // (In wide mode, q.all_wide, these records take the wide pool as well.)
-            bool d0 = act && __popcll(F0) >= 2;
+            bool d0 = act && __popcll(F0) >= 2 && in_band(w0);
             if (FLAT) {
                 // the slice's first-block records, compacted in DFS order: two coalesced stores, no reservation, no chunk table
                 const bool dd = d0 && w < 128u;                          // (an int8 operand holds a weight below 128; the others take the sort)
@@ -1074,22 +1096,22 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
                     const uint32_t X0 = bcast(w0, (uint32_t)__builtin_ctzll(pend));
                     const bool mine = d0 && w0 == X0;
                     const unsigned long long bc = __ballot(mine);
-                    const Resv r = arena_reserve(A, q.pool, X0, tri32(X0) + X0, (uint32_t)__popcll(bc), lane);
+                    const Resv r = arena_reserve(A, q.pool, X0 - bxlo, tri32(X0) + X0 - bsbase, (uint32_t)__popcll(bc), lane);
                     if (mine) rec_store_diag(q.pool, resv_slot(r, (uint32_t)__popcll(bc & lt_mask)), F0, w);
                     pend &= ~bc;
                 }
             } else {
-                rec_emit<ROWS>(A, pv, RT, d0, w0, F0, F0, w, tri32(w0) + w0, lane, lt_mask);
+                rec_emit<ROWS>(A, pv, RT, d0, w0 - bxlo, F0, F0, w, tri32(w0) + w0 - bsbase, lane, lt_mask);
             }
         };
         if (!DIRECT) first_block_records();
         // second blocks, (w1, w0, F1, F0) and (w1, w1, F1): the pairs differ from lane to lane, so these records go to the wide
         // pool in arrival order (one reservation for all lanes) and are grouped by the sort
         {
-            const bool act2 = act && F1 != 0;
+            const bool act2 = act && F1 != 0 && in_band(w1);
             if (__ballot(act2)) {
-                rec_emit<ROWS>(A, pv, RT, act2, w1, F1, F0, w, tri32(w1) + w0, lane, lt_mask);
-                rec_emit<ROWS>(A, pv, RT, act2 && __popcll(F1) >= 2, w1, F1, F1, w, tri32(w1) + w1, lane, lt_mask);
+                rec_emit<ROWS>(A, pv, RT, act2, w1 - bxlo, F1, F0, w, tri32(w1) + w0 - bsbase, lane, lt_mask);
+                rec_emit<ROWS>(A, pv, RT, act2 && __popcll(F1) >= 2, w1 - bxlo, F1, F1, w, tri32(w1) + w1 - bsbase, lane, lt_mask);
             }
         }
         // ---- chain slots for the next batch: the nodes on the root path of this batch's last node, i.e. the
@@ -1118,6 +1140,11 @@ __global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_e
     if constexpr (ROWS) rowtab_finish(RT, pv, lane);
     else arena_finish_wide(A, pv, lane);
 }
+template <int MODE, int MINW, bool ROWS>
+__global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_eu(MINW, 8))) void k1n_kernel(const NParams q) { k1n_body<MODE, ROWS, false>(q); }
+// the band-emit instantiations (modes 0 and 2; compiled for four waves per SIMD as their counterparts are)
+template <int MODE, bool ROWS>
+__global__ __launch_bounds__(WAVE * K1N_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k1n_band_kernel(const NParams q) { k1n_body<MODE, ROWS, true>(q); }
 
 // ------------------------------------------------------------------------------------------
 // K2d: the narrow kernel's first-block records, slice by slice
@@ -1410,6 +1437,8 @@ struct WParams {
     uint32_t emit_lo, emit_hi;
     PoolView pool;
     L2View l2;
+    // band emit (k1w_band_kernel; no other instantiation reads these): as in NParams.  n_rows then counts the band's block rows.
+    uint32_t band_xlo, band_xhi, band_sbase;
 };
 constexpr int K1W_WAVES = 2;
 constexpr int K1W_MINW_FEW = 5;            // waves per SIMD the few-streams instantiation is compiled for (4 / 5 / 6 measured: DESIGN §8; 6 needs 52 bytes of scratch per lane)
@@ -1495,9 +1524,14 @@ __global__ void wrun_anc_kernel(const uint32_t* __restrict__ widx, uint32_t n_wi
 // neither the code nor the registers of the paths it does not take.
 // (WParams must stay the kernel's ONLY argument: kernarg_reread<WParams>() and PoolRef::k read it at offset 0 of the kernarg segment)
 // (few streams: pinned at five waves per SIMD — left to itself the allocator lands on either side of the 96 registers that five waves allow)
-template <bool ROWS, bool L2>
-__global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_eu(ROWS ? 4 : K1W_MINW_FEW, 8))) void k1w_kernel(const WParams q) {
+// The kernel's body.  BAND = false is k1w_kernel as it always was.  BAND = true (k1w_band_kernel) is the emit filter of a band call: the walk (chains, arenas,
+// fn_*) is unchanged; a node's list is ascending in blocks, so its entries inside the band's block rows are ONE run [a_lo, a_hi) and its records are the
+// pair indices t in [tri32(a_lo), tri32(a_hi)) of the triangular enumeration — the heavy form runs over that range, the record-parallel form takes its
+// prefix sums over tri32(a_hi) - tri32(a_lo); a node with no entry in the band emits nothing.  The second level's entries are written as ever.
+template <bool ROWS, bool L2, bool BAND>
+__device__ __forceinline__ void k1w_body(const WParams& q) {
     static_assert(ROWS || !L2, "the second level runs in row mode only");
+    const uint32_t bxlo = BAND ? q.band_xlo : 0u, bsbase = BAND ? q.band_sbase : 0u;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const uint32_t lane = lane_id();
     const uint32_t wave = threadIdx.x >> 6;
@@ -1570,8 +1604,19 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
                     ++l2_nodes;
                     continue;
                 }
-                const uint32_t Tj = mj * (mj + 1u) / 2u;
-                for (uint32_t t0 = 0; t0 < Tj; t0 += WAVE) {
+                uint32_t T0 = 0, Tj = mj * (mj + 1u) / 2u;
+                if constexpr (BAND) {
+                    // the run of the node's entries inside the band's block rows (blocks ascend): entries below Xlo, entries up to Xhi
+                    uint32_t a_lo = 0, a_hi = 0;
+                    for (uint32_t e0 = 0; e0 < mj; e0 += WAVE) {
+                        const uint32_t e = e0 + lane;
+                        const uint32_t blk = e < mj ? cblk(e) : 0xFFFFFFFFu;
+                        a_lo += (uint32_t)__popcll(__ballot(blk < q.band_xlo));
+                        a_hi += (uint32_t)__popcll(__ballot(blk <= q.band_xhi));
+                    }
+                    T0 = tri32(a_lo); Tj = tri32(a_hi);
+                }
+                for (uint32_t t0 = T0; t0 < Tj; t0 += WAVE) {
                     const uint32_t t = t0 + lane;
                     bool rec_on = false;
                     uint32_t stream = 0, X = 0;
@@ -1586,9 +1631,9 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
                         const uint32_t Y = cblk(b);
                         rec_on = a != b || __popcll(FX) >= 2;
                         if (a == b) FY = FX;
-                        stream = tri32(X) + Y;
+                        stream = tri32(X) + Y - bsbase;
                     }
-                    rec_emit<ROWS>(A, pv, RT, rec_on, X, FX, FY, wj, stream, lane, lt_mask);
+                    rec_emit<ROWS>(A, pv, RT, rec_on, X - bxlo, FX, FY, wj, stream, lane, lt_mask);
                 }
             }
             on = on && m < K1W_HEAVY;
@@ -1597,10 +1642,25 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
         // the owner of record t by a binary search in the prefix sums (LDS) and the pair (a, b) from the record's index inside the node.
         // (A queue of descriptors pushed by the owners cost a loop of up to 55 iterations per owner: 2/3 of the kernel's VALU work at
         // 10 000 samples.)
-        const uint32_t myrec = on ? m * (m + 1u) / 2u : 0u;
+        uint32_t myrec = on ? m * (m + 1u) / 2u : 0u;
+        uint32_t roff = 0;                                  // band: the node's first pair index inside the band, tri32(a_lo) <= 55
+        if constexpr (BAND) {
+            uint32_t a_lo = 0, a_hi = 0;
+            if (on) {
+                const uint32_t st = L.st_start[lane], pre = L.st_pre[lane];
+                for (uint32_t e = 0; e < m; ++e) {
+                    const uint32_t blk = e < pre ? (uint32_t)L.e_blk[e] : (uint32_t)L.ent_blk[st + e - pre];
+                    a_lo += blk < q.band_xlo ? 1u : 0u;
+                    a_hi += blk <= q.band_xhi ? 1u : 0u;
+                }
+            }
+            roff = tri32(a_lo); myrec = tri32(a_hi) - roff;
+        }
         const uint32_t rincl = wave_incl_scan(myrec, lane);
         const uint32_t T = bcast(rincl, WAVE - 1);
-        L.queue[lane] = rincl;
+        // (band: the lane's first pair index rides in the upper half of its queue word — a batch holds fewer than 64 * 55 records)
+        L.queue[lane] = BAND ? rincl | (roff << 16) : rincl;
+        auto qcount = [&](uint32_t i) -> uint32_t { const uint32_t v = L.queue[i]; if constexpr (BAND) return v & 0xFFFFu; else return v; };
         L.st_w[lane] = wv;
         lds_sync();
         for (uint32_t t0 = 0; t0 < T; t0 += WAVE) {
@@ -1611,8 +1671,9 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
             if (t < T) {
                 uint32_t own = 0;                               // the first lane whose inclusive sum exceeds t
 #pragma unroll
-                for (uint32_t sft = 32; sft >= 1u; sft >>= 1) if (L.queue[own + sft - 1u] <= t) own += sft;
-                const uint32_t r0 = t - (own ? L.queue[own - 1u] : 0u);
+                for (uint32_t sft = 32; sft >= 1u; sft >>= 1) if (qcount(own + sft - 1u) <= t) own += sft;
+                uint32_t r0 = t - (own ? qcount(own - 1u) : 0u);
+                if constexpr (BAND) r0 += L.queue[own] >> 16;
                 uint32_t a = (uint32_t)((__fsqrt_rn(8.0f * (float)r0 + 1.0f) - 1.0f) * 0.5f);
                 while (tri32(a) > r0) --a;
                 while (tri32(a + 1u) <= r0) ++a;
@@ -1624,11 +1685,11 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
                 ww = L.st_w[own];
                 diag = a == b;
                 rec_on = !diag || __popcll(FX) >= 2;               // a diagonal record needs two ids to have a pair
-                stream = tri32(X) + Y;
+                stream = tri32(X) + Y - bsbase;
             }
             // few streams: the step's records go to the wide pool in arrival order (one reservation for all lanes); many: to
             // the chunks of their block rows
-            rec_emit<ROWS>(A, pv, RT, rec_on, X, FX, diag ? FX : FY, ww, stream, lane, lt_mask);
+            rec_emit<ROWS>(A, pv, RT, rec_on, X - bxlo, FX, diag ? FX : FY, ww, stream, lane, lt_mask);
         }
         lds_sync();
     };
@@ -1872,6 +1933,11 @@ __global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_e
     if (lane == 0 && n_miss) atomicAdd(&pool_cold(pv)->counters[KCTR_SLOW], n_miss);
     if constexpr (L2) if (lane == 0 && l2_nodes) atomicAdd(&pool_cold(pv)->counters[KCTR_L2_NODES], l2_nodes);
 }
+template <bool ROWS, bool L2>
+__global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_eu(ROWS ? 4 : K1W_MINW_FEW, 8))) void k1w_kernel(const WParams q) { k1w_body<ROWS, L2, false>(q); }
+// the band-emit instantiations, compiled for the waves per SIMD of their counterparts
+template <bool ROWS, bool L2>
+__global__ __launch_bounds__(WAVE * K1W_WAVES) __attribute__((amdgpu_waves_per_eu(ROWS ? 4 : K1W_MINW_FEW, 8))) void k1w_band_kernel(const WParams q) { k1w_body<ROWS, L2, true>(q); }
 
 // ------------------------------------------------------------------------------------------
 // K2: records -> matrix
@@ -2114,7 +2180,7 @@ void l2_join_apply_kernel(const unsigned long long* __restrict__ B, const uint32
     __shared__ uint32_t acc[64 * 64];
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[L2_WAVES][64];
     __shared__ uint32_t wor_sh;
-    const uint32_t t = blockIdx.x;
+    const uint32_t t = band_stream(band, blockIdx.x);           // (band emit launches the band's tiles only, counted from its first stream)
     const uint32_t X = stream_row(t), Y = t - tri32(X);
     if (loff[X + 1] == loff[X] || loff[Y + 1] == loff[Y]) return;       // (uniform over the workgroup)
     if constexpr (BAND) {
@@ -2310,7 +2376,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2A_MIN_WAV
         while (b < win && s_key[b] == key) ++b;
         K2Item it;
         {
-            const uint32_t bucket = key;
+            const uint32_t bucket = band_stream(band, key);
             uint32_t X = (uint32_t)((__fsqrt_rn(8.0f * (float)bucket + 1.0f) - 1.0f) * 0.5f);
             while (tri32(X) > bucket) --X;
             while (tri32(X + 1u) <= bucket) ++X;
@@ -2586,9 +2652,14 @@ __global__ __launch_bounds__(RG_THREADS) void rg_scatter_kernel(const uint32_t* 
 // scan over [row][stream][job], LDS-staged scatter), reading through the chunk list, writing the dense sorted arrays
 // k2_jobs_kernel walks.
 constexpr uint32_t RS_JOB_CHUNKS = 64;
-struct RsRows { const uint32_t* O; const uint32_t* row_ids; uint32_t G, NB; const uint32_t* row_job; const uint32_t* row_tab; };
-__global__ void rs_rows_kernel(const uint32_t* __restrict__ O, uint32_t G, uint32_t NB, uint32_t* __restrict__ row_job, uint32_t* __restrict__ row_tab,
-                               uint32_t* __restrict__ counters) {
+// (NB: the block rows the tables hold.  The whole matrix: all of them, Xlo = sbase = 0, bins = NB.  Band emit: the band's rows, row r of the tables is block row
+// Xlo + r with Xlo + r + 1 streams, keyed from sbase = tri32(Xlo) on; bins = Xhi + 1, the streams of its last row)
+struct RsRows { const uint32_t* O; const uint32_t* row_ids; uint32_t G, NB; const uint32_t* row_job; const uint32_t* row_tab; uint32_t Xlo, sbase, bins; };
+// (the kernel's body: BAND = false is rs_rows_kernel as it always was, Xlo folded to 0)
+template <bool BAND>
+__device__ __forceinline__ void rs_rows_body(const uint32_t* __restrict__ O, uint32_t G, uint32_t NB, uint32_t* __restrict__ row_job, uint32_t* __restrict__ row_tab,
+                                             uint32_t* __restrict__ counters, uint32_t Xlo_arg) {
+    const uint32_t Xlo = BAND ? Xlo_arg : 0u;
     __shared__ uint32_t s_job[1024], s_tab[1024];
     // jobs and table entries of every row, then block-wide exclusive scans (NB may be a few thousand)
     uint32_t cj = 0, ct = 0;
@@ -2596,7 +2667,7 @@ __global__ void rs_rows_kernel(const uint32_t* __restrict__ O, uint32_t G, uint3
         const uint32_t X = base + threadIdx.x;
         uint32_t nj = 0;
         if (X < NB) nj = (O[(size_t)(X + 1u) * G] - O[(size_t)X * G] + RS_JOB_CHUNKS - 1u) / RS_JOB_CHUNKS;
-        s_job[threadIdx.x] = nj; s_tab[threadIdx.x] = X < NB ? nj * (X + 1u) : 0u;
+        s_job[threadIdx.x] = nj; s_tab[threadIdx.x] = X < NB ? nj * (X + Xlo + 1u) : 0u;
         __syncthreads();
         for (uint32_t d = 1; d < 1024; d <<= 1) {
             const uint32_t a = threadIdx.x >= d ? s_job[threadIdx.x - d] : 0u, b = threadIdx.x >= d ? s_tab[threadIdx.x - d] : 0u;
@@ -2604,12 +2675,16 @@ __global__ void rs_rows_kernel(const uint32_t* __restrict__ O, uint32_t G, uint3
             s_job[threadIdx.x] += a; s_tab[threadIdx.x] += b;
             __syncthreads();
         }
-        if (X < NB) { row_job[X] = cj + s_job[threadIdx.x] - nj; row_tab[X] = ct + s_tab[threadIdx.x] - nj * (X + 1u); }
+        if (X < NB) { row_job[X] = cj + s_job[threadIdx.x] - nj; row_tab[X] = ct + s_tab[threadIdx.x] - nj * (X + Xlo + 1u); }
         cj += s_job[1023]; ct += s_tab[1023];
         __syncthreads();
     }
     if (threadIdx.x == 0) { row_job[NB] = cj; row_tab[NB] = ct; counters[KCTR_ROWJOBS] = cj; counters[KCTR_RAW] = O[(size_t)NB * G]; }
 }
+__global__ void rs_rows_kernel(const uint32_t* __restrict__ O, uint32_t G, uint32_t NB, uint32_t* __restrict__ row_job, uint32_t* __restrict__ row_tab,
+                               uint32_t* __restrict__ counters) { rs_rows_body<false>(O, G, NB, row_job, row_tab, counters, 0u); }
+__global__ void rs_rows_band_kernel(const uint32_t* __restrict__ O, uint32_t G, uint32_t NB, uint32_t* __restrict__ row_job, uint32_t* __restrict__ row_tab,
+                                    uint32_t* __restrict__ counters, uint32_t Xlo) { rs_rows_body<true>(O, G, NB, row_job, row_tab, counters, Xlo); }
 struct RsJob { uint32_t X, nj, cb, ce, tab; const uint32_t* ids; };
 
 __device__ __forceinline__ bool rs_job(const RsRows& R, uint32_t job, uint32_t job_end, RsJob& j) {
@@ -2633,7 +2708,7 @@ __global__ __launch_bounds__(256) void rs_hist_kernel(const RsRows R, const uint
     __shared__ uint32_t s_id[RS_JOB_CHUNKS], s_fill[RS_JOB_CHUNKS];
     RsJob j;
     if (!rs_job(R, blockIdx.x, 0xFFFFFFFFu, j)) return;
-    const uint32_t nb = j.X + 1u, sub = tri32(j.X), nch = j.ce - j.cb;
+    const uint32_t nb = j.X + R.Xlo + 1u, sub = tri32(j.X + R.Xlo) - R.sbase, nch = j.ce - j.cb;
     for (uint32_t k = threadIdx.x; k < nb; k += blockDim.x) cs_lds[k] = 0;
     // the job's chunk ids and fills first (one round trip), then the key words of four chunks at a time
     if (threadIdx.x < nch) { const uint32_t id = j.ids[j.cb + threadIdx.x]; s_id[threadIdx.x] = id; s_fill[threadIdx.x] = chunk_fill[id]; }
@@ -2667,8 +2742,8 @@ __global__ __launch_bounds__(CS_THREADS) void rs_scatter_kernel(const RsRows R, 
     // consecutive jobs write neighbouring stretches of every stream of their row (the lines at the seams are shared): workgroups are dealt
     // to the eight XCDs round-robin, so job = f(blockIdx) keeps every XCD on ONE contiguous range of jobs and the seams in one L2
     if (!rs_job(R, xcd_contiguous(blockIdx.x, gridDim.x), 0xFFFFFFFFu, job)) return;
-    const uint32_t NB = R.NB;
-    const uint32_t nb = job.X + 1u, sub = tri32(job.X), nch = job.ce - job.cb;
+    const uint32_t NB = R.bins;
+    const uint32_t nb = job.X + R.Xlo + 1u, sub = tri32(job.X + R.Xlo) - R.sbase, nch = job.ce - job.cb;
     WideRec* st_rec = (WideRec*)cs_raw;                                   // [CS_TILE]
     uint32_t* st_dst = (uint32_t*)(st_rec + CS_TILE);                     // [CS_TILE] global destination
     uint32_t* st_key = st_dst + CS_TILE;                                  // [CS_TILE]; not there for packed records (their key words stay behind: 8 KB
@@ -2819,14 +2894,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
 // 10 000 samples.  Where a stream starts is known from the counting sort's offsets: no run boundaries are searched.
 constexpr uint32_t K2J_REC = 16384;
 // (O = the sort's offsets [row][stream of the row][job of the row], exclusive sums: entry (X, Y, job 0) is where stream (X, Y) starts)
-__global__ void k2j_starts_kernel(const RsRows R, const uint32_t* __restrict__ O, uint32_t n_states, uint32_t* __restrict__ start) {
+// (BAND = false is k2j_starts_kernel as it always was; BAND: stream s of the band is stream s + sbase of the matrix, its block row counted from Xlo)
+template <bool BAND>
+__device__ __forceinline__ void k2j_starts_body(const RsRows& R, const uint32_t* __restrict__ O, uint32_t n_states, uint32_t* __restrict__ start) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s > n_states) return;
     if (s == n_states) { start[s] = O[R.row_tab[R.NB]]; return; }                         // all sorted records
-    const uint32_t X = stream_row(s), Y = s - tri32(X);
+    const uint32_t sa = BAND ? s + R.sbase : s;
+    const uint32_t Xa = stream_row(sa), Y = sa - tri32(Xa), X = BAND ? Xa - R.Xlo : Xa;
     const uint32_t nj = R.row_job[X + 1] - R.row_job[X];                                   // a row without records has no jobs: its streams start where the next row does
     start[s] = O[(size_t)R.row_tab[X] + (size_t)Y * nj];
 }
+__global__ void k2j_starts_kernel(const RsRows R, const uint32_t* __restrict__ O, uint32_t n_states, uint32_t* __restrict__ start) { k2j_starts_body<false>(R, O, n_states, start); }
+__global__ void k2j_starts_band_kernel(const RsRows R, const uint32_t* __restrict__ O, uint32_t n_states, uint32_t* __restrict__ start) { k2j_starts_body<true>(R, O, n_states, start); }
 // few streams: O = the one-pass sort's offsets [stream][workgroup share] (+ the total): share 0 of a stream is where the stream starts
 __global__ void k2j_starts_flat_kernel(const uint32_t* __restrict__ O, uint32_t n_states, uint32_t shares, uint32_t* __restrict__ start) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2865,7 +2945,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
     if (blockIdx.x >= nj) return;
     const uint2 job = jobs[blockIdx.x];
     if constexpr (BAND) {
-        const bool culled = band_culls(band.w, stream_row(job.x));
+        const bool culled = band_culls(band.w, stream_row(band_stream(band, job.x)));
         if (threadIdx.x == 0) band_unit(band.w, blockIdx.x, BU_JOBS, !culled);
         if (culled) return;
     }
@@ -2884,7 +2964,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2S_MIN_WAV
     const uint32_t b = e - a > K2J_REC ? a + K2J_REC : e;
     if (a == b) return;
     K2Item it;
-    it.X = stream_row(job.x); it.Y = job.x - tri32(it.X); it.rect_cols = 0; it.pshift = pshift;
+    const uint32_t stream = band_stream(band, job.x);
+    it.X = stream_row(stream); it.Y = stream - tri32(it.X); it.rect_cols = 0; it.pshift = pshift;
     it.n_rec = b - a; it.count = (it.n_rec + 63u) / 64u; it.ids = nullptr; it.fills = nullptr; it.srec = swrec + a; it.skey = swkey + a; it.kbits = kbits; it.dbits = dbits;
     it.rec = nullptr; it.recw = nullptr;
     k2_run<true, BAND>(it, acc, &wor_sh, wbuf, lut_ff, lut_01, M, N, bwidth, touched, band);
@@ -3144,6 +3225,19 @@ struct BlocksState {
     BandWin band{};
     DevBuf<uint32_t> band_units;    // [BAND_UNIT_SLOTS * BAND_UNIT_WORDS]
     kmdb_blocks_band_units last_band_units{};
+    // ---- the geometry the stream-sized and row-sized arrays follow.  The handle's whole-matrix state (kmdb_db.blocks): g_rows = g_bins = NB, g_xlo =
+    // g_sbase = 0 and the capacities equal n_states / NB, for good.  The band-emit state (kmdb_db.band_blocks, emit_band): the block rows [g_xlo, g_xhi] of the
+    // call's band — n_states = its streams tri32(g_xhi + 1) - g_sbase, g_sbase = tri32(g_xlo), g_rows = g_xhi - g_xlo + 1, g_bins = g_xhi + 1 (the streams of its
+    // last row) — set per call inside the capacities the state was made for; a band that needs more gets a new state (kmdb_blocks_band_prepare).
+    // NB stays the blocks of the whole collection in both: the lists of the wide kernel and the second level are indexed by block.
+    bool emit_band = false;
+    uint32_t g_rows = 0, g_bins = 0, g_xlo = 0, g_xhi = 0, g_sbase = 0;
+    uint32_t cap_states = 0, cap_rows = 0, cap_bins = 0;
+    uint32_t digit_bits = 0;        // != 0: the weight digit bits of an unpacked key word (band emit: the whole call's, so that a weight makes as many records); 0: wide_digit_bits(key_bits)
+    uint64_t est_n0 = 0, est_g0 = 0, est_l20 = 0;   // the sampled estimate as the width estimate left it: narrow, wide, and the part the second level replaces
+    uint32_t est_stride = 1;
+    uint32_t attempts = 0;          // attempts of the last call (1 + repeats)
+    int forced_row_mode = -1;       // band emit: the record path kmdb_blocks_band_prepare chose for the state (0 / 1); -1: by the streams and KMDB_ROW_MODE
 
     ~BlocksState() { if (h_counters) (void)hipHostFree(h_counters); }
 };
@@ -3151,10 +3245,16 @@ void BlocksStateDelete::operator()(BlocksState* b) const { delete b; }
 
 namespace {
 
+inline uint32_t state_digit_bits(const BlocksState& b) { return b.digit_bits ? b.digit_bits : wide_digit_bits(b.key_bits); }
 PoolView pool_view(const BlocksState& b, bool dense) {
     return PoolView{b.counters, b.chunk_key, b.chunk_fill, b.rec, b.recw, b.sub_cursor, (uint32_t)(b.pool_cap / KMDB_SUBPOOLS),
                     (uint32_t)b.pool_cap, b.wkey, b.wrec, b.wsub_cursor, (uint32_t)(b.wide_pool_cap / KMDB_SUBPOOLS), dense ? 1u : 0u,
-                    (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), b.row_mode ? 1u : 0u, b.n_states, b.rec_pshift};
+                    (uint32_t)b.key_bits, state_digit_bits(b), b.row_mode ? 1u : 0u, b.n_states, b.rec_pshift};
+}
+// the tile flags as the apply kernels index them, by absolute stream tri32(X) + Y: the band-emit state holds the flags of the band's streams only, from its
+// first stream on (the kernels it launches touch no tile outside the band)
+inline unsigned char* touched_view(const BlocksState& b) {
+    return b.tile_touched ? (unsigned char*)((uintptr_t)b.tile_touched.get() - (uintptr_t)b.g_sbase) : nullptr;
 }
 
 // ---- the emit kernels' instantiations: ONE place maps a handle's record path to the function that is configured, queried and launched
@@ -3169,6 +3269,15 @@ struct K1wPick { void (*fn)(const WParams); const char* name; };
 K1wPick k1w_pick(bool rows, bool l2) {
     if (!rows) return K1wPick{k1w_kernel<false, false>, "k1w<no rows, no L2>"};
     return l2 ? K1wPick{k1w_kernel<true, true>, "k1w<rows, L2>"} : K1wPick{k1w_kernel<true, false>, "k1w<rows, no L2>"};
+}
+// the band-emit instantiations (the state's k1n_mode is 0 or 2: kmdb_blocks_band_prepare)
+K1nPick k1n_band_pick(int mode, bool rows) {
+    if (mode == 2) return rows ? K1nPick{k1n_band_kernel<2, true>, "k1n band<2, rows>"} : K1nPick{k1n_band_kernel<2, false>, "k1n band<2, no rows>"};
+    return rows ? K1nPick{k1n_band_kernel<0, true>, "k1n band<0, rows>"} : K1nPick{k1n_band_kernel<0, false>, "k1n band<0, no rows>"};
+}
+K1wPick k1w_band_pick(bool rows, bool l2) {
+    if (!rows) return K1wPick{k1w_band_kernel<false, false>, "k1w band<no rows, no L2>"};
+    return l2 ? K1wPick{k1w_band_kernel<true, true>, "k1w band<rows, L2>"} : K1wPick{k1w_band_kernel<true, false>, "k1w band<rows, no L2>"};
 }
 
 constexpr uint32_t K1W_MAX_WAVES = 8192;
@@ -3201,14 +3310,14 @@ int alloc_record_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
         // the row chunks grouped by row: [row][workgroup of RG_THREADS chunk ids] counts / offsets, the grouped ids
         dev_reset(b.rg_hist, b.rg_offs, b.rg_tmp, b.row_ids);
         b.rg_blocks = (uint32_t)((chunks + RG_THREADS - 1) / RG_THREADS);
-        const size_t rg_ne = (size_t)b.NB * b.rg_blocks + 1;
+        const size_t rg_ne = (size_t)b.cap_rows * b.rg_blocks + 1;
         DEV_ALLOC(b.rg_hist, rg_ne);
         DEV_ALLOC(b.rg_offs, rg_ne);
         DEV_ALLOC(b.row_ids, chunks);
         HIP_TRY(prim::exclusive_sum(nullptr, b.rg_tmp_bytes, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
         DEV_ALLOC(b.rg_tmp, std::max<size_t>(b.rg_tmp_bytes, 16));
-        // the sort inside the rows: at most chunks / RS_JOB_CHUNKS + NB jobs, every one with at most NB bins
-        b.rs_entries = (chunks / RS_JOB_CHUNKS + b.NB + 1) * (uint64_t)b.NB + 1;
+        // the sort inside the rows: at most chunks / RS_JOB_CHUNKS + NB jobs, every one with at most NB bins (band emit: the band's rows, the bins of its last row)
+        b.rs_entries = (chunks / RS_JOB_CHUNKS + b.cap_rows + 1) * (uint64_t)b.cap_bins + 1;
         if (b.rs_entries >= (1ull << 31)) return kmdb_set_error("kmdb: the table of the sort inside the block rows would exceed 2^31 entries");
         DEV_ALLOC(b.rs_hist, b.rs_entries);
         DEV_ALLOC(b.rs_offs, b.rs_entries);
@@ -3223,14 +3332,18 @@ int alloc_record_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
 int alloc_wide_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
     dev_reset(b.wkey, b.wrec, b.swkey, b.swrec);
     b.wide_pool_cap = 0; b.sorted_cap = 0;
-    chunks = (chunks + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB - 1) / ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) * ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB);
+    // (a pool handed out through the 256 sub-pools holds a whole grab of each.  The band-emit state on the many-streams path has no such pool: its wide records
+    // travel through row chunks, what is allocated here are the sorted arrays alone, and those are sized for the band's records to the chunk)
+    if (!(b.emit_band && b.row_mode))
+        chunks = (chunks + (uint64_t)KMDB_SUBPOOLS * WIDE_GRAB - 1) / ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB) * ((uint64_t)KMDB_SUBPOOLS * WIDE_GRAB);
+    chunks = std::max<uint64_t>(chunks, 1);
     const uint64_t slots = chunks << WCH_SHIFT;
     if (slots >= pool_slot_limit(b)) return kmdb_set_error("kmdb: wide record pool would exceed its " + std::to_string(pool_slot_limit(b)) + " record slots");
     DEV_ALLOC(b.swkey, slots);
     DEV_ALLOC(b.swrec, slots);
     b.sorted_cap = slots;
     // jobs of the apply kernel: every stream at least one, a long one a job per K2J_REC records
-    b.k2j_cap = slots / K2J_REC + b.n_states + 1;
+    b.k2j_cap = slots / K2J_REC + b.cap_states + 1;
     DEV_ALLOC(b.k2j_jobs, b.k2j_cap);
     if (b.row_mode) {
         b.wide_pool_cap = chunks;
@@ -3240,7 +3353,7 @@ int alloc_wide_pool(BlocksState& b, hipStream_t st, uint64_t chunks) {
     DEV_ALLOC(b.wrec, slots);
     if (!b.cs_hist) {
         // one pass: [stream][workgroup]
-        const size_t ne = (size_t)b.n_states * CS_BLOCKS_ONE + 1;
+        const size_t ne = (size_t)b.cap_states * CS_BLOCKS_ONE + 1;
         DEV_ALLOC(b.cs_hist, ne);
         DEV_ALLOC(b.cs_offs, ne);
         HIP_TRY(prim::exclusive_sum(nullptr, b.cs_tmp_bytes, b.cs_hist.get(), b.cs_offs.get(), (int)ne, st));
@@ -3305,6 +3418,9 @@ int kmdb_rect_sort_apply(hipStream_t st, uint32_t* wkey, void* wrec, uint32_t ns
 }
 
 static int blocks_prepare_impl(kmdb_db* db);
+static uint64_t state_device_bytes(const kmdb_db* db, const BlocksState& b);
+static int blocks_alloc_working_set(kmdb_db* db, BlocksState& b, uint64_t est_n, uint64_t est_g, uint64_t est_l2, uint32_t stride,
+                                    const std::function<void(const char*)>& phase);
 // (the flag is set only when every allocation succeeded: a failed lazy preparation inside a call leaves nothing half made behind)
 int kmdb_blocks_prepare(kmdb_db* db) {
     db->blocks.reset(new BlocksState());
@@ -3364,6 +3480,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
         } else db->width = cands[best];
         est_n = h[best] * stride; est_g = h[EST_NW + best] * stride; est_l2 = h[2 * EST_NW + 1 + best] * stride;
         b.est_records = est_n + est_g;
+        b.est_n0 = est_n; b.est_g0 = est_g; b.est_l20 = est_l2; b.est_stride = stride;      // (kept for the band-emit state, which scales them to its band)
         if (verbose) {
             fprintf(stderr, "[kmdb] width estimate (1 node in %u, %llu sampled):", stride, h[2 * EST_NW]);
             for (int c = 0; c < EST_NW; ++c) fprintf(stderr, " %u:%llu", cands[c], (h[c] + h[EST_NW + c]) * stride);
@@ -3381,6 +3498,18 @@ static int blocks_prepare_impl(kmdb_db* db) {
         return 0;
     }
     phase("block width estimate");
+    // (the whole matrix: every block row, every stream, for good)
+    b.cap_states = b.n_states; b.g_rows = b.g_bins = b.cap_rows = b.cap_bins = b.NB; b.g_xlo = 0; b.g_xhi = b.NB - 1u; b.g_sbase = 0;
+    return blocks_alloc_working_set(db, b, est_n, est_g, est_l2, stride, phase);
+}
+// The working set of a state whose geometry is set (NB, n_states, the g_* and cap_* of BlocksState) from the sampled estimate of ITS records: the per-node
+// arrays, the per-call state, the pair pool, the record paths chosen, the arrays sized by streams and rows, the pools.  The whole-matrix state and the
+// band-emit state are both made here.
+static int blocks_alloc_working_set(kmdb_db* db, BlocksState& b, uint64_t est_n, uint64_t est_g, uint64_t est_l2, uint32_t stride,
+                                    const std::function<void(const char*)>& phase) {
+    const BlocksKnobs& knobs = b.knobs;
+    const uint64_t P = db->P;
+    const bool verbose = kmdb_verbose();
     // ---- working set
     DEV_ALLOC(b.p0_mask, P);
     DEV_ALLOC(b.p0_info, P);
@@ -3398,7 +3527,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
         uint32_t o = 0;
         auto take = [&](uint32_t n) { const uint32_t at = o; o += (n + 15u) & ~15u; return at; };
         const uint32_t o_ctr = take(KCTR_COUNT), o_sub = take(KMDB_SUBPOOLS * 16), o_wsub = take(KMDB_SUBPOOLS * 16), o_run = take(K1W_CTRS * 16),
-                       o_dir = take(KMDB_SUBPOOLS * 16), o_cth = take(b.n_states + 2);
+                       o_dir = take(KMDB_SUBPOOLS * 16), o_cth = take(b.cap_states + 2);
         b.call_state_n = o;
         const uint32_t o_pair = take((KMDB_PAIR_REGIONS + 1) * 16);
         b.call_state_n_decode = o;
@@ -3454,6 +3583,7 @@ static int blocks_prepare_impl(kmdb_db* db) {
     }
     b.row_mode = b.n_states > CS_MAX_KEYS;
     if (knobs.row_mode >= 0) b.row_mode = knobs.row_mode != 0;
+    if (b.forced_row_mode >= 0) b.row_mode = b.forced_row_mode != 0;          // (the band-emit state: decided with the one-pass sort's LDS in view)
     // packed records: a block width of at most 54 leaves the column mask 10 spare bits and more — an 8-bit weight digit at least and the digit's
     // index — so the records of the many-streams path travel as 16 bytes through the sort and the apply step (KMDB_REC_PACKED=0: 16 + 4, A/B)
     // (round 5, later: the few-streams path as well — its one-pass sort moves 16 bytes per record and leaves the key words behind)
@@ -3473,10 +3603,10 @@ static int blocks_prepare_impl(kmdb_db* db) {
         while ((1ull << key_bits) <= (uint64_t)b.n_states + 1) ++key_bits;          // streams; all-ones = never written
         b.key_bits = key_bits;
     }
-    DEV_ALLOC(b.tile_touched, (size_t)b.n_states + 1);
-    DEV_ALLOC(b.ct_offs, (size_t)b.n_states + 2);
-    DEV_ALLOC(b.ct_cursor, (size_t)b.n_states + 2);
-    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist, b.ct_offs.get(), (int)(b.n_states + 1), db->stream));
+    DEV_ALLOC(b.tile_touched, (size_t)b.cap_states + 1);
+    DEV_ALLOC(b.ct_offs, (size_t)b.cap_states + 2);
+    DEV_ALLOC(b.ct_cursor, (size_t)b.cap_states + 2);
+    HIP_TRY(prim::exclusive_sum(nullptr, b.ct_tmp_bytes, b.ct_hist, b.ct_offs.get(), (int)(b.cap_states + 1), db->stream));
     DEV_ALLOC(b.ct_tmp, std::max<size_t>(b.ct_tmp_bytes, 16));
     // A database whose records do not fit one pass (2^31 record slots, or the memory left) is taken in SLICES of the pattern stream:
     // every slice emits the records of its own patterns only, the partial matrices add up in place (the engine's own version of
@@ -3503,10 +3633,10 @@ static int blocks_prepare_impl(kmdb_db* db) {
     // waves of the wide-node kernel: in row mode every wave may end with an open chunk per block row
     b.k1w_waves = K1W_MAX_WAVES;
     if (b.row_mode) {
-        b.k1w_waves = std::min<uint32_t>(b.k1w_waves, std::max<uint32_t>(256u, std::min<uint32_t>(4096u, (1u << 21) / std::max<uint32_t>(b.NB, 1u))));
-        DEV_ALLOC(b.rs_rows, (size_t)2 * (b.NB + 1));
+        b.k1w_waves = std::min<uint32_t>(b.k1w_waves, std::max<uint32_t>(256u, std::min<uint32_t>(4096u, (1u << 21) / std::max<uint32_t>(b.cap_rows, 1u))));
+        DEV_ALLOC(b.rs_rows, (size_t)2 * (b.cap_rows + 1));
     }
-    DEV_ALLOC(b.k2j_start, (size_t)b.n_states + 2);
+    DEV_ALLOC(b.k2j_start, (size_t)b.cap_states + 2);
     // stream chunks: the narrow estimate at two thirds average fill, plus what the waves hold when they end (open chunks, an
     // unfinished grab); wide records: the wide estimate at two thirds (+ a grab / the open row chunks per wave)
     // (modes 1 and 2: of the narrow kernel's first-block records only the stragglers go to the pools — weights of 128 and more, in mode 1 also a
@@ -3519,13 +3649,17 @@ static int blocks_prepare_impl(kmdb_db* db) {
         // slice of the narrow kernel the rows of its nodes' second blocks, up to 48 counted here — and leaves it partly filled.  Round 5's pools hid
         // that behind the records the second level no longer writes; with the estimate after the second level and 12 chunks per slice the first
         // call at 10 000 samples ran out and doubled its pool: profiles/r06_close_bench.err)
-        if (alloc_record_pool(b, db->stream, (est_n + est_g) * 5 / 4 / CH_REC + (uint64_t)db->n_nsegs * std::min<uint32_t>(b.NB, 48u) + (uint64_t)b.k1w_waves * (b.NB + ARENA_GRAB) + 4096)) return 1;
-        if (alloc_wide_pool(b, db->stream, (est_n + est_g) * 9 / 8 / WCH_REC + 4096)) return 1;
+        if (alloc_record_pool(b, db->stream, (est_n + est_g) * 5 / 4 / CH_REC + (uint64_t)db->n_nsegs * std::min<uint32_t>(b.cap_rows, 48u) + (uint64_t)b.k1w_waves * (b.cap_rows + ARENA_GRAB) + 4096)) return 1;
+        // (the band-emit state: the sorted arrays follow the BAND's records — its estimate plus an eighth plus 4096 records for what a sampled estimate
+        // of a few rows misses, the margin under KMDB_POOL_PERCENT at that percentage too — not the 4096 chunks the whole matrix's arrays start from)
+        const uint64_t sorted_chunks = b.emit_band ? ((est_n + est_g) * 9 / 8 + 4096 * (knobs.pool_percent ? std::min<uint64_t>(knobs.pool_percent, 100) : 100) / 100) / WCH_REC + 1
+                                                   : (est_n + est_g) * 9 / 8 / WCH_REC + 4096;
+        if (alloc_wide_pool(b, db->stream, sorted_chunks)) return 1;
     } else {
         if (alloc_record_pool(b, db->stream, est_n * 3 / 2 / CH_REC + (b.dense_narrow ? 0u : (uint64_t)db->n_nsegs * 8) + 4096)) return 1;
         if (alloc_wide_pool(b, db->stream, est_g * 3 / 2 / WCH_REC + (uint64_t)(K1W_MAX_WAVES + 64) * (WIDE_GRAB + 2) + (uint64_t)db->n_nsegs * (WIDE_GRAB / 2) + 1024)) return 1;
     }
-    if (verbose) fprintf(stderr, "[kmdb] prepare: record pools %.2f GB\n", kmdb_blocks_device_bytes(db) / 1e9);
+    if (verbose) fprintf(stderr, "[kmdb] prepare: record pools %.2f GB\n", state_device_bytes(db, b) / 1e9);
     phase("record pools (hipMalloc)");
     return 0;
 }
@@ -3533,14 +3667,19 @@ static int blocks_prepare_impl(kmdb_db* db) {
 // the state's destructor frees every array it holds
 void kmdb_blocks_release(kmdb_db* db) { db->blocks.reset(); }
 
-uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
-    if (!db->blocks || !db->blocks->counters) return 0;
-    const BlocksState& b = *db->blocks;
+static uint64_t state_device_bytes(const kmdb_db* db, const BlocksState& b) {
+    if (!b.counters) return 0;
     return db->P * (8 + 4 + 4 + 16 + 4) + (b.dmask ? (uint64_t)db->n_nsegs * db->nseg_nodes * 12 : 0u) + b.pair_cap * 10 + ((b.pool_cap << CH_SHIFT) * 20) + b.pool_cap * 16 + b.wide_cap * 4 + (db->P / 64) * 12 + (uint64_t)db->n_nsegs * 8 +
            (uint64_t)b.call_state_n_decode * 4 +
-           (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.n_states * 12 +
+           (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.cap_states * 12 +
            (uint64_t)b.NB * (b.l2_node_cap / 64u) * 12 + (uint64_t)b.l2_ent_cap * 26 + (uint64_t)b.l2_node_cap * 4;
 }
+// both states of the handle: the whole matrix's and, once a band-emit call made it, the band's
+uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
+    return (db->blocks ? state_device_bytes(db, *db->blocks) : 0u) + (db->band_blocks ? state_device_bytes(db, *db->band_blocks) : 0u);
+}
+uint64_t kmdb_blocks_whole_state_bytes(const kmdb_db* db) { return db->blocks ? state_device_bytes(db, *db->blocks) : 0u; }
+uint64_t kmdb_blocks_band_state_bytes(const kmdb_db* db) { return db->band_blocks ? state_device_bytes(db, *db->band_blocks) : 0u; }
 
 namespace {
 
@@ -3620,19 +3759,21 @@ int a2a_narrow_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, 
     q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
     q.fn_mask = b.fn_mask; q.fn_blk = b.fn_blk; q.widebits = b.widebits; q.wide_base = b.wide_base; q.wide_slice_cnt = b.wide_slice_cnt;
     q.P = (uint32_t)db->P; q.nseg_nodes = db->nseg_nodes; q.n_segs = db->n_nsegs; q.chain_cap = db->chain_cap;
-    q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.NB); q.n_keys = b.NB;
+    // (g_rows: the block rows the open-chunk table and the row tables are indexed by — all NB of them, or the band's under band emit)
+    q.emit_lo = emit_lo; q.emit_hi = emit_hi; q.tbits = b.dense_narrow ? 0u : arena_table_bits(b.g_rows); q.n_keys = b.g_rows;
     q.all_wide = b.dense_narrow ? 1u : 0u;
     q.pool = pool_view(b, b.dense_narrow);
+    q.band_xlo = b.g_xlo; q.band_xhi = b.g_xhi; q.band_sbase = b.g_sbase;
     // a wave's chain table grows with the depth of the tree: as many waves per workgroup as 144 KB of LDS hold
-    const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, b.row_mode ? b.NB : 0u);
+    const size_t wave_lds = k1n_wave_bytes(q.chain_cap, q.tbits, q.n_keys, b.row_mode ? b.g_rows : 0u);
     const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(K1N_WAVES, (144u << 10) / wave_lds));
     const size_t lds = wave_lds * waves;
-    q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = b.tile_touched; q.direct_ctr = b.direct_ctr;
+    q.M = M; q.N = (uint32_t)db->N; q.bwidth = db->width; q.touched = touched_view(b); q.direct_ctr = b.direct_ctr;
     q.dmask = b.dmask; q.dwx = b.dwx; q.slice_cnt = b.slice_cnt;
     // (mode 1 holds 48 accumulator registers beside the narrow kernel's 95: three waves per SIMD without spills, or four with 72 bytes of
     // scratch per lane, 76 in row mode — KMDB_K1N_MINW=4, A/B)
     // the instantiation of the call's record path: the attribute and the launch take the same function
-    const K1nPick pick = k1n_pick(b.k1n_mode, b.knobs.k1n_minw, b.row_mode);
+    const K1nPick pick = b.emit_band ? k1n_band_pick(b.k1n_mode, b.row_mode) : k1n_pick(b.k1n_mode, b.knobs.k1n_minw, b.row_mode);
     HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((q.n_segs + waves - 1) / waves), block(WAVE * waves);
     if (!b.have_counts && kmdb_verbose())
@@ -3651,7 +3792,7 @@ int a2a_slice_apply(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hi
     DParams d{};
     d.dmask = b.dmask; d.dwx = b.dwx; d.slice_cnt = b.slice_cnt; d.n_segs = db->n_nsegs; d.nseg_nodes = db->nseg_nodes;
     const uint32_t sl = b.knobs.k2d_slices;
-    d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = b.tile_touched;
+    d.slices = sl; d.M = M; d.N = (uint32_t)db->N; d.bwidth = db->width; d.touched = touched_view(b);
     const uint32_t waves = (db->n_nsegs + sl - 1u) / sl;
     if (waves) {
         if (b.band_on) hipLaunchKernelGGL(k2d_band_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s2, d, BandArg<true>{b.band});
@@ -3684,10 +3825,10 @@ int a2a_group_and_apply_chunks(kmdb_db* db, BlocksState& b, uint32_t* M, hipStre
     if (grid) {
         if (b.band_on)
             hipLaunchKernelGGL(k2_apply_kernel<true>, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
-                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched, BandArg<true>{b.band});
+                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, touched_view(b), BandArg<true>{b.band});
         else
             hipLaunchKernelGGL(k2_apply_kernel<false>, dim3(grid), dim3(256), 0, s2, b.rec, b.recw, b.sorted_key, b.sorted_id, b.chunk_fill, b.n_states,
-                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, b.tile_touched, BandArg<false>{});
+                               b.ct_offs + b.n_states, M, (uint32_t)db->N, db->width, win, touched_view(b), BandArg<false>{});
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(db->ev_side[1], s2));
@@ -3753,11 +3894,12 @@ int a2a_wide_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, ui
     q.seg_anc = b.wrun_anc; q.seg_anc_n = b.wrun_anc_n;
     // LDS of a wave: rows of a batch (at least one full list: as many entries as there are blocks), the chain list, the chain
     q.chain_cap = db->chain_cap; q.e_cap = (b.NB + 2u + 3u) & ~3u; q.arena_cap = std::max<uint32_t>(K1W_ARENA_MIN, (b.NB + 2u + 63u) & ~63u);
-    q.n_rows = b.row_mode ? b.NB : 0u;
+    q.n_rows = b.row_mode ? b.g_rows : 0u;
+    q.band_xlo = b.g_xlo; q.band_xhi = b.g_xhi; q.band_sbase = b.g_sbase;
     const size_t wave_lds = k1w_wave_bytes(q.arena_cap, q.e_cap, q.chain_cap, q.n_rows);
     const uint32_t waves = wave_lds * K1W_WAVES <= (size_t)(64u << 10) ? (uint32_t)K1W_WAVES : 1u;
     // the instantiation of the call's record path: the attribute, the occupancy query and the launch take the same function
-    const K1wPick pick = k1w_pick(b.row_mode, b.l2_on);
+    const K1wPick pick = b.emit_band ? k1w_band_pick(b.row_mode, b.l2_on) : k1w_pick(b.row_mode, b.l2_on);
     HIP_TRY(hipFuncSetAttribute((const void*)pick.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wave_lds * waves)));
     // As many waves as the chip holds at once, each with an equal share of the runs (dealt round-robin): with more, the waves
     // beyond the first round start when the first ones end, and all take equally long — 1.6 rounds cost 2 (measured at 10 000
@@ -3785,12 +3927,13 @@ int a2a_wide_emit(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, ui
         hipLaunchKernelGGL(l2_offsets_kernel, dim3(1), dim3(64), 0, st, b.l2_len, NB, b.l2_cursors, W, b.l2_loff);
         hipLaunchKernelGGL(l2_lists_kernel, dim3((b.l2_ent_cap + 255u) / 256u), dim3(256), 0, st, b.l2_ent_g, b.l2_ent_blk, b.l2_ent_mask, b.l2_node_w,
                            b.l2_ent_cap, W, b.l2_bitmap, b.l2_rank, b.l2_loff, b.l2_list_mask, b.l2_list_w, b.l2_cursors);
+        // (the tiles: every block pair, or — band emit — the band's streams alone, counted from its first: BandWin::sbase)
         if (b.band_on)
-            hipLaunchKernelGGL(l2_join_apply_kernel<true>, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
-                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched, BandArg<true>{b.band});
+            hipLaunchKernelGGL(l2_join_apply_kernel<true>, dim3(b.emit_band ? b.n_states : NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask,
+                               b.l2_list_w, b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, touched_view(b), BandArg<true>{b.band});
         else
             hipLaunchKernelGGL(l2_join_apply_kernel<false>, dim3(NB * (NB + 1u) / 2u), dim3(64 * L2_WAVES), 0, st, b.l2_bitmap, b.l2_rank, b.l2_list_mask, b.l2_list_w,
-                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, b.tile_touched, BandArg<false>{});
+                               b.l2_loff, W, NB, M, (uint32_t)db->N, db->width, touched_view(b), BandArg<false>{});
     }
     return 0;
 }
@@ -3802,18 +3945,19 @@ void a2a_apply_stream_jobs(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t
     if (L.k2jobs) {
         if (b.band_on)
             hipLaunchKernelGGL(k2_jobs_kernel<true>, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
-                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width,
-                               b.tile_touched, BandArg<true>{b.band});
+                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, state_digit_bits(b), M, (uint32_t)db->N, db->width,
+                               touched_view(b), BandArg<true>{b.band});
         else
             hipLaunchKernelGGL(k2_jobs_kernel<false>, dim3(L.k2jobs), dim3(256), 0, st, b.swkey, (const WideRec*)b.swrec, b.k2j_start, b.k2j_jobs, b.counters + KCTR_K2JOBS,
-                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, wide_digit_bits(b.key_bits), M, (uint32_t)db->N, db->width,
-                               b.tile_touched, BandArg<false>{});
+                               (uint32_t)b.k2j_cap, (uint32_t)b.sorted_cap, b.rec_pshift, (uint32_t)b.key_bits, state_digit_bits(b), M, (uint32_t)db->N, db->width,
+                               touched_view(b), BandArg<false>{});
     }
 }
 // ---- 8. many streams: chunk table grouped (stream chunks -> side stream), then the sort inside the block rows and its apply
 int a2a_sort_apply_rows(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st, hipStream_t s2, Launched& L) {
     if (a2a_group_and_apply_chunks(db, b, M, st, s2)) return 1;
-    const uint32_t NB = b.NB, pool_cap = (uint32_t)b.pool_cap, kmask = (1u << b.key_bits) - 1u;
+    // (NB: the block rows of the tables — all of them, or the band's under band emit; bins: the streams of the last of them)
+    const uint32_t NB = b.g_rows, bins = b.g_bins, pool_cap = (uint32_t)b.pool_cap, kmask = (1u << b.key_bits) - 1u;
     uint32_t* row_job = b.rs_rows, *row_tab = b.rs_rows + (NB + 1);
     {
         // the row chunks grouped by row
@@ -3823,27 +3967,29 @@ int a2a_sort_apply_rows(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st
         HIP_TRY(prim::exclusive_sum(b.rg_tmp, tbg, b.rg_hist.get(), b.rg_offs.get(), (int)rg_ne, st));
         hipLaunchKernelGGL(rg_scatter_kernel, dim3(b.rg_blocks), dim3(RG_THREADS), NB * 4, st, b.chunk_key, pool_cap, b.n_states, NB, b.rg_offs, b.row_ids);
     }
-    hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters);
-    const RsRows R{b.rg_offs, b.row_ids, b.rg_blocks, NB, row_job, row_tab};
+    if (b.emit_band) hipLaunchKernelGGL(rs_rows_band_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters, b.g_xlo);
+    else hipLaunchKernelGGL(rs_rows_kernel, dim3(1), dim3(1024), 0, st, b.rg_offs, b.rg_blocks, NB, row_job, row_tab, b.counters);
+    const RsRows R{b.rg_offs, b.row_ids, b.rg_blocks, NB, row_job, row_tab, b.g_xlo, b.g_sbase, bins};
     // jobs and table entries: measured by the previous call, else their upper bounds (workgroups beyond the last job leave at once)
     const uint32_t jobs_bound = (uint32_t)(pool_cap / RS_JOB_CHUNKS + NB + 1);
     const uint32_t jobs = b.have_counts ? std::min<uint32_t>(jobs_bound, with_slack(b.last_n_rowjobs)) : jobs_bound;
     L.rowjobs = jobs;
-    const size_t ne = std::min<size_t>(b.rs_entries, (size_t)jobs * NB + 1);
+    const size_t ne = std::min<size_t>(b.rs_entries, (size_t)jobs * bins + 1);
     HIP_TRY(hipMemsetAsync(b.rs_hist, 0, ne * 4, st));
     // (16 chunks' key words requested together; 4, round 4's, and 8 at 10 000 samples: apply step 6.08 / 5.88 against 5.85 ms, profiles/r05_j14 — the
     // kernel waits for its loads)
-    hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), NB * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
+    hipLaunchKernelGGL(rs_hist_kernel<16>, dim3(jobs), dim3(256), bins * 4, st, R, b.chunk_fill, b.recw, kmask, b.rs_hist);
     size_t tb = b.rs_tmp_bytes;
     HIP_TRY(prim::exclusive_sum(b.rs_tmp, tb, b.rs_hist.get(), b.rs_offs.get(), (int)ne, st));
     const uint32_t* total_ptr = b.rs_offs + (ne - 1);
     HIP_TRY(hipMemcpyAsync(b.counters + KCTR_WIDE_RECORDS, total_ptr, 4, hipMemcpyDeviceToDevice, st));
     // (Sorting and applying bands of block rows side by side on two streams was measured at 10 000 samples: 2 / 4 / 8 bands 18.4 / 17.0 /
     // 18.7 ms against 16.5 for one — the two kernels do not complement each other.)
-    HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(NB, b.rec_pshift != 0)));
-    hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(NB, b.rec_pshift != 0), st, R, b.chunk_fill, b.recw, (const WideRec*)b.rec.get(), kmask,
+    HIP_TRY(hipFuncSetAttribute((const void*)rs_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_scatter_lds(bins, b.rec_pshift != 0)));
+    hipLaunchKernelGGL(rs_scatter_kernel, dim3((jobs + 7u) & ~7u), dim3(CS_THREADS), rs_scatter_lds(bins, b.rec_pshift != 0), st, R, b.chunk_fill, b.recw, (const WideRec*)b.rec.get(), kmask,
                        b.rs_offs, (uint32_t)b.sorted_cap, b.swkey, (WideRec*)b.swrec, b.counters, b.rec_pshift ? 1u : 0u);
-    hipLaunchKernelGGL(k2j_starts_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
+    if (b.emit_band) hipLaunchKernelGGL(k2j_starts_band_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
+    else hipLaunchKernelGGL(k2j_starts_kernel, dim3((b.n_states + 1u + 255u) / 256u), dim3(256), 0, st, R, b.rs_offs, b.n_states, b.k2j_start);
     a2a_apply_stream_jobs(db, b, M, st, L);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3903,7 +4049,7 @@ int a2a_enlarge_pools(kmdb_db* db, BlocksState& b, const uint32_t* c) {
             if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the sort too\n");
             if (alloc_wide_pool(b, db->stream, b.wide_pool_cap + b.est_records * 5 / 4 / WCH_REC + (uint64_t)db->n_nsegs * (WIDE_GRAB + 2))) return 1;
             want = 0;
-        } else if (b.row_mode && !b.dense_narrow && b.NB > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
+        } else if (b.row_mode && !b.dense_narrow && b.g_rows > (1u << ST_MAX_BITS) && (b.pool_cap << CH_SHIFT) > 8 * (b.est_records + (1u << 22))) {
             // the same with row chunks: the diagonal records join the rows
             b.dense_narrow = true;
             if (verbose) fprintf(stderr, "[kmdb] record chunks of the narrow kernel are evicted nearly empty: its records go through the row chunks too\n");
@@ -3987,15 +4133,14 @@ int a2a_settle(kmdb_db* db, BlocksState& b, hipStream_t st, const Launched& L, b
 // one attempt of the whole pipeline; *retry is set when a pool was too small (it has been enlarged)
 // decode: run K0 (the first slice of a call does; what it leaves — the local (block, mask) pairs of every node — serves all slices)
 // band (may be null): M holds that band of rows only — the emit stages run as ever, every apply launch takes its BAND instantiation
-int blocks_attempt(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry, const kmdb_band_desc* band) {
-    BlocksState& b = *db->blocks;
+int blocks_attempt(kmdb_db* db, BlocksState& b, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, bool decode, hipStream_t st, bool* retry, const kmdb_band_desc* band) {
     hipStream_t s2 = db->stream2;
     *retry = false;
     b.band_on = band != nullptr;
     if (band) {
-        // (row_lo < row_hi <= N: the caller's checks; an empty band never gets here)
+        // (row_lo < row_hi <= N: the caller's checks; an empty band never gets here.  sbase: 0 but for the band-emit state, whose keys count from its first stream)
         b.band = BandWin{(uint32_t)band->row_lo, (uint32_t)band->row_hi, (uint32_t)(band->row_lo / db->width), (uint32_t)((band->row_hi - 1) / db->width), band->cell_lo,
-                         b.band_units.get()};
+                         b.band_units.get(), b.g_sbase};
     }
     Launched L;
     if (b.have_counts) L.raw = (uint32_t)std::min<uint64_t>(with_slack(b.last_n_raw), b.row_mode ? 0xFFFFFFFFull : b.wide_pool_cap);
@@ -4049,12 +4194,22 @@ static int blocks_read_band_units(BlocksState& b, hipStream_t st) {
 }
 
 int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band) {
-    BlocksState& b = *db->blocks;
+    // band emit runs on the handle's second state (made and fitted to the band by kmdb_blocks_band_prepare); nothing of the whole-matrix state is touched,
+    // the reason it may hold — why the whole matrix cannot go through the pipeline — included: what this call finds is left in band_fallback_reason
+    const bool emit = band && band->emit;
+    BlocksState& b = emit ? *db->band_blocks : *db->blocks;
+    struct ReasonSwap {
+        kmdb_db* db; bool on; std::string whole;
+        ReasonSwap(kmdb_db* d, bool o) : db(d), on(o) { if (on) { whole.swap(db->fallback_reason); db->band_fallback_reason.clear(); } }
+        ~ReasonSwap() { if (on) { db->band_fallback_reason.swap(db->fallback_reason); db->fallback_reason.swap(whole); } }
+    } reason_swap{db, emit};
     // what a repeated round zeroes: the words of M — the whole triangle, or the band's cells only
     const uint64_t cells = band ? band->cells : db->N * (db->N - 1) / 2;
     if (band && !b.band_units) DEV_ALLOC(b.band_units, (size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS);
     struct BandOff { BlocksState& b; ~BandOff() { b.band_on = false; } } band_off{b};      // (the state never names a band beyond its call)
+    b.attempts = 0;
     for (int round = 0; round < 64; ++round) {
+        ++b.attempts;
         if (band) HIP_TRY(hipMemsetAsync(b.band_units, 0, (size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS * 4, st));
         // (the tiles this call adds to, all its slices: tile_touched is cleared by the prologue of the round's first attempt, the one that decodes)
         // the slices of [emit_lo, emit_hi) one after the other, adding into the same matrix; a pass that had to enlarge a pool (or
@@ -4074,7 +4229,7 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
             if (b.have_counts) { b.last_n_wide = sc.n_wide; b.last_n_chunks = sc.n_chunks; b.last_n_raw = sc.n_raw; b.last_n_rowjobs = sc.n_rowjobs; b.last_n_sorted = sc.n_sorted; b.last_n_k2jobs = sc.n_k2jobs; }
             if (!b.have_counts) db->last_call_sized = true;
             bool retry = false;
-            if (blocks_attempt(db, M, lo, hi, !decoded, st, &retry, band)) { blocks_join_side_streams(db); return 1; }
+            if (blocks_attempt(db, b, M, lo, hi, !decoded, st, &retry, band)) { blocks_join_side_streams(db); return 1; }
             decoded = true;
             if (!db->fallback_reason.empty()) return 0;
             if (retry) { again = true; for (auto& c : b.slice_counts) c.valid = false; }
@@ -4102,3 +4257,107 @@ const unsigned char* kmdb_blocks_tile_touched(const kmdb_db* db) { return db->bl
 kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db) { return db->blocks ? db->blocks->last_band_units : kmdb_blocks_band_units{}; }
 int kmdb_blocks_k1n_mode(const kmdb_db* db) { return db->blocks ? db->blocks->k1n_mode : -1; }
 uint32_t kmdb_blocks_n_slices(const kmdb_db* db) { return db->blocks ? std::max<uint32_t>(1u, db->blocks->n_slices) : 1u; }
+
+// ------------------------------------------------------------------------------------------
+// band emit: the handle's second state (kmdb_db.band_blocks), keyed relative to the band
+// ------------------------------------------------------------------------------------------
+// KMDB_K1N_MODE as a band-emit state would read it (the whole-matrix state of a collection beyond 2^22 block pairs never got as far as its switches)
+int kmdb_blocks_band_k1n_mode(const kmdb_db* db) { return db->band_blocks ? db->band_blocks->knobs.k1n_mode : blocks_read_knobs().k1n_mode; }
+
+// Why band emit cannot take this band ("": it can).  The streams: relative keys must leave all-ones free in 22 bits of a key word (KMDB_BAND_MAX_STREAMS, a
+// test switch, lowers the limit; values above 2^22 are clamped).  The bytes: a list of the wide kernel may have as many entries as the collection has blocks.
+std::string kmdb_blocks_band_refusal(const kmdb_db* db, const kmdb_band_geometry* g) {
+    const uint64_t cap = std::min<uint64_t>(1ull << 22, db->band_max_streams ? db->band_max_streams : 1ull << 22);      // (read once per handle: a2a_rows_records.hip)
+    if (g->n_streams + 1 >= cap)
+        return "the band's " + std::to_string(g->n_streams) + " streams (block rows " + std::to_string(g->x_lo) + " to " + std::to_string(g->x_hi) + " of width " +
+               std::to_string(db->width) + ") reach the limit of " + std::to_string(cap) + " streams of a band";
+    const uint32_t NB = (uint32_t)((db->N + db->width - 1) / db->width);
+    if (NB >= BNONE) return "the collection's " + std::to_string(NB) + " blocks exceed the " + std::to_string(BNONE) + " a block index holds";
+    const size_t bytes = k1w_wave_bytes(std::max<uint32_t>(K1W_ARENA_MIN, (NB + 2u + 63u) & ~63u), (NB + 2u + 3u) & ~3u, db->chain_cap, g->n_rows);
+    if (bytes > (size_t)(152u << 10))
+        return "the lists of the wide-node kernel need " + std::to_string(bytes) + " bytes of LDS per wave (" + std::to_string(NB) + " blocks, root paths of up to " +
+               std::to_string(db->max_depth) + " nodes, " + std::to_string(g->n_rows) + " block rows in the band), beyond the " + std::to_string(152u << 10) + " bytes there are";
+    return "";
+}
+
+// The band-emit state fitted to the band `g` (not refused: kmdb_blocks_band_refusal): made at the handle's first such call, made anew — what it held is
+// released first — when a band needs more streams, block rows or bins than it was made for or takes the other record path (the path follows the BAND's streams
+// against CS_MAX_KEYS; KMDB_ROW_MODE forces it).  Its pools follow the whole matrix's sampled estimate scaled to the band's share of the cells.
+int kmdb_blocks_band_prepare(kmdb_db* db, const kmdb_band_geometry* g, uint64_t band_cells) {
+    const uint32_t n_streams = (uint32_t)g->n_streams, n_rows = g->n_rows, bins = g->x_hi + 1u;
+    BlocksState* old = db->band_blocks.get();
+    const BlocksKnobs knobs = old ? old->knobs : blocks_read_knobs();
+    if (knobs.k1n_mode == 1) return kmdb_set_error("kmdb_blocks_band_prepare: KMDB_K1N_MODE=1 has no band form");
+    bool row_mode = n_streams > CS_MAX_KEYS;
+    if (knobs.row_mode >= 0) row_mode = knobs.row_mode != 0;
+    // (KMDB_ROW_MODE=0 is followed as far as the one-pass sort's LDS — 160 KB, 1 KB of them the kernel's own — holds a cursor per stream of the band:
+    // some 10 000 streams of packed records, 9 400 of unpacked ones; beyond that the band takes the many-streams path whatever the switch says)
+    const bool packed = db->width <= 54u && knobs.rec_packed;
+    if (!row_mode && cs_scatter_lds(n_streams, packed) + 1024u > (size_t)(160u << 10)) row_mode = true;
+    const bool fits = old && old->row_mode == row_mode && n_streams <= old->cap_states && n_rows <= old->cap_rows && bins <= old->cap_bins;
+    if (!fits) {
+        // A state that is outgrown doubles the streams and the bins it held, up to what the whole collection has: the bands of a run walked top-down each need more streams than
+        // the one before, and a state made anew per band would free and allocate the per-node arrays and the pools every time.  (Few streams: the sort's
+        // tables are [streams][3072 workgroups], so the capacity stays at what its LDS can hold.)
+        const uint32_t NB_all = (uint32_t)((db->N + db->width - 1) / db->width);
+        const uint64_t whole_states = std::min<uint64_t>((uint64_t)NB_all * (NB_all + 1) / 2, (1ull << 22) - 2);
+        uint64_t grow_states = old ? std::min<uint64_t>(2ull * old->cap_states, whole_states) : 0;
+        if (!row_mode) grow_states = std::min<uint64_t>(grow_states, 8192);
+        const uint32_t cap_states = (uint32_t)std::max<uint64_t>(n_streams, grow_states),
+                       cap_rows = std::max(n_rows, old ? old->cap_rows : 0u),          // (the pools hold an open chunk per row and wave: rows are not doubled)
+                       cap_bins = std::max(bins, old ? std::min(2u * old->cap_bins, NB_all) : 0u);
+        if (old && kmdb_verbose())
+            fprintf(stderr, "[kmdb] band emit: the band state is made anew for %u streams, %u block rows (it held %u, %u)\n", cap_states, cap_rows, old->cap_states, old->cap_rows);
+        db->band_blocks.reset();
+        std::unique_ptr<BlocksState, BlocksStateDelete> nb(new BlocksState());
+        BlocksState& b = *nb;
+        b.knobs = knobs;
+        b.emit_band = true;
+        b.forced_row_mode = row_mode ? 1 : 0;
+        b.NB = (uint32_t)((db->N + db->width - 1) / db->width);
+        b.n_states = n_streams; b.cap_states = cap_states; b.cap_rows = cap_rows; b.cap_bins = cap_bins;
+        b.g_rows = n_rows; b.g_bins = bins; b.g_xlo = g->x_lo; b.g_xhi = g->x_hi; b.g_sbase = (uint32_t)g->stream_base;
+        // the band's share of the whole matrix's sampled estimate (a block row's records go with its cells, roughly; too small is enlarged as ever)
+        const BlocksState* w = db->blocks.get();
+        const uint64_t total = db->N * (db->N - 1) / 2;
+        const double frac = total ? std::min(1.0, (double)band_cells / (double)total) : 1.0;
+        const uint64_t est_n = w ? (uint64_t)((double)w->est_n0 * frac) + 1 : 1, est_g = w ? (uint64_t)((double)w->est_g0 * frac) + 1 : 1,
+                       est_l2 = w ? (uint64_t)((double)w->est_l20 * frac) : 0;
+        b.est_records = est_n + est_g;
+        b.est_n0 = est_n; b.est_g0 = est_g; b.est_l20 = est_l2; b.est_stride = w ? w->est_stride : 1u;
+        if (blocks_alloc_working_set(db, b, est_n, est_g, est_l2, b.est_stride, [](const char*) {})) return 1;
+        db->band_blocks = std::move(nb);
+    }
+    BlocksState& b = *db->band_blocks;
+    if (b.g_xlo != g->x_lo || b.g_xhi != g->x_hi || !fits) {
+        // another band: what the last call measured (launch sizes, the waves the chip holds of the wide kernel at its LDS) belongs to its geometry
+        for (auto& c : b.slice_counts) c.valid = false;
+        b.have_counts = false; b.k1w_slots = 0;
+    }
+    b.n_states = n_streams;
+    b.g_rows = n_rows; b.g_bins = bins; b.g_xlo = g->x_lo; b.g_xhi = g->x_hi; b.g_sbase = (uint32_t)g->stream_base;
+    {
+        int key_bits = 1;
+        while ((1ull << key_bits) <= (uint64_t)b.n_states + 1) ++key_bits;          // streams; all-ones = never written
+        b.key_bits = key_bits;
+        // the weight digits of an unpacked key word as the whole-matrix call cuts them (its stream bits, 22 beyond its limit): a weight then makes as many
+        // records in a band as in the whole call, and the bands' records add up to the whole call's
+        int whole_bits = 1;
+        const uint64_t whole_states = (uint64_t)b.NB * (b.NB + 1) / 2;
+        while (whole_bits < 22 && (1ull << whole_bits) <= whole_states + 1) ++whole_bits;
+        b.digit_bits = wide_digit_bits(std::max(whole_bits, key_bits));
+    }
+    return 0;
+}
+
+kmdb_blocks_band_info kmdb_blocks_band_last(const kmdb_db* db, bool band_state) {
+    kmdb_blocks_band_info o{};
+    const BlocksState* s = band_state ? db->band_blocks.get() : db->blocks.get();
+    if (!s) return o;
+    const BlocksState& b = *s;
+    o.key_bits = (uint32_t)b.key_bits; o.row_mode = b.row_mode ? 1u : 0u; o.l2_on = b.l2_on ? 1u : 0u; o.attempts = b.attempts;
+    o.slices = std::max<uint32_t>(1u, b.n_slices);
+    o.records = b.last_records; o.est_records = b.est_records;
+    o.units = b.last_band_units;
+    return o;
+}

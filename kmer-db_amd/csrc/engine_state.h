@@ -112,6 +112,13 @@ struct kmdb_db {
     // ---- the band call through the block-record pipeline (a2a_rows_records.hip; its device state is the pipeline's own)
     kmdb_all2all_rows_records_stats rr_stats{};  // the last such call on the handle (kmdb_all2all_rows_records_stats_get)
     kmdb_all2all_banded_records_stats banded_rr_stats{};   // the last banded call on the records path (kmdb_all2all_banded_records_stats_get)
+    // ---- band emit (a2a_blocks.hip): the pipeline's second state, keyed relative to a band's first stream — made by the handle's first band-emit call,
+    // made anew when a later band needs more; the whole-matrix state above is not touched by it
+    std::unique_ptr<BlocksState, BlocksStateDelete> band_blocks;
+    std::string band_fallback_reason;   // why the last band-emit call gave up inside the pipeline ("" = it did not); fallback_reason stays the whole matrix's
+    uint64_t band_max_streams = 0;      // KMDB_BAND_MAX_STREAMS as read with it (0: unset, 0 or no number — the limit is 2^22)
+    int band_emit_mode = -2;            // KMDB_BAND_EMIT as read at the handle's first records band call: -1 unset, 0, 1 (-2: not read yet)
+    kmdb_all2all_rows_band_emit_stats be_stats{};   // the last records band call on the handle (kmdb_all2all_rows_band_emit_stats_get)
     // hashtables (new2all)
     uint64_t n_buckets = 0;
     DevBuf<uint64_t> bucket_offset;
@@ -174,11 +181,24 @@ int kmdb_blocks_prepare(kmdb_db* db);
 // per call: decode, narrow / wide emit, apply — everything that depends on a sample id happens here
 // band == nullptr: M is the whole triangle.  Else M holds the rows [row_lo, row_hi) only — `cells` words, the first of them cell `cell_lo` = tri(row_lo) of
 // the triangle: decode, emit and sort run whole, the apply stage culls the block rows outside the band and windows its write-back (a2a_rows_records.hip)
-struct kmdb_band_desc { uint64_t row_lo, row_hi, cell_lo, cells; };
+// emit: the band-emit form — the call runs on the handle's second state (kmdb_blocks_band_prepare fitted it to this band): the emit kernels write the records of
+// the band's block rows alone, keyed relative to its first stream, and every later stage works on the band's streams only
+struct kmdb_band_desc { uint64_t row_lo, row_hi, cell_lo, cells; bool emit = false; };
 int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band = nullptr);
+// ---- band emit (a2a_blocks.hip; a2a_rows_records.hip decides which form a band call takes)
+// KMDB_K1N_MODE as the band-emit state reads it; why band emit cannot take the band g ("": it can); the state made or fitted for g, band_cells = its cells
+int kmdb_blocks_band_k1n_mode(const kmdb_db* db);
+std::string kmdb_blocks_band_refusal(const kmdb_db* db, const kmdb_band_geometry* g);
+int kmdb_blocks_band_prepare(kmdb_db* db, const kmdb_band_geometry* g, uint64_t band_cells);
+// the two states' device bytes (kmdb_blocks_device_bytes is their sum); the band-emit state after its last call: kmdb_blocks_band_last, below
+uint64_t kmdb_blocks_whole_state_bytes(const kmdb_db* db);
+uint64_t kmdb_blocks_band_state_bytes(const kmdb_db* db);
 // the apply units of the last band call: stream jobs, window runs of stream chunks, slices' tiles of first-block records, second-level tiles
 struct kmdb_blocks_band_units { uint64_t jobs, jobs_run, runs, runs_run, slices, slices_run, tiles, tiles_run; };
 kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db);
+struct kmdb_blocks_band_info { uint32_t key_bits, row_mode, l2_on, attempts, slices; uint64_t records, est_records; kmdb_blocks_band_units units; };
+// (of the band-emit state, or of the whole-matrix state after a parent-form band call)
+kmdb_blocks_band_info kmdb_blocks_band_last(const kmdb_db* db, bool band_state);
 // what a band caller asks before it runs: the narrow kernel's mode (KMDB_K1N_MODE; 1 writes the matrix itself), passes over the pattern stream per call
 int kmdb_blocks_k1n_mode(const kmdb_db* db);
 uint32_t kmdb_blocks_n_slices(const kmdb_db* db);

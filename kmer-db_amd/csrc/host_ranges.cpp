@@ -136,3 +136,25 @@ extern "C" int kmdbh_range_plan(const kmdb_db_view* view, uint32_t n_ranges, uin
             range_of[p] = (uint32_t)(std::upper_bound(plan.cut.begin(), plan.cut.end(), plan.pre[p]) - plan.cut.begin()) - 1u;
     return 0;
 }
+
+// ---- the geometry of a band of rows in the block-record pipeline's streams (kmdb_amd.h: kmdb_band_geometry; a2a_rows_records.hip calls this very function).
+// Block (X, Y), Y <= X, of `width` sample ids a side is stream tri32(X) + Y, tri32(x) = x (x + 1) / 2; the band [row_lo, row_hi) owns the streams of the
+// block rows row_lo / width .. (row_hi - 1) / width, keyed from the first of them on.
+extern "C" int kmdbh_band_streams(uint64_t n_samples, uint32_t width, uint64_t row_lo, uint64_t row_hi, kmdb_band_geometry* out) {
+    const char* who = "kmdbh_band_streams";
+    if (!out) return kmdb_set_error(std::string(who) + ": null argument");
+    if (width < 32 || width > 64) return kmdb_set_error(std::string(who) + ": a block width of " + std::to_string(width) + " lies outside 32 .. 64");
+    if (row_lo > row_hi) return kmdb_set_error(std::string(who) + ": row_lo > row_hi (" + std::to_string(row_lo) + " > " + std::to_string(row_hi) + ")");
+    if (row_hi > n_samples) return kmdb_set_error(std::string(who) + ": row_hi " + std::to_string(row_hi) + " > the " + std::to_string(n_samples) + " samples");
+    *out = kmdb_band_geometry{};
+    out->fits = 1;
+    if (row_lo == row_hi) return 0;                              // an empty band owns nothing
+    const uint64_t x_lo = row_lo / width, x_hi = (row_hi - 1) / width;
+    if (x_hi >= (1ull << 31)) return kmdb_set_error(std::string(who) + ": more than 2^31 block rows");
+    auto tri = [](uint64_t x) { return x * (x + 1) / 2; };
+    out->x_lo = (uint32_t)x_lo; out->x_hi = (uint32_t)x_hi; out->n_rows = (uint32_t)(x_hi - x_lo + 1);
+    out->n_streams = tri(x_hi + 1) - tri(x_lo);
+    out->stream_base = tri(x_lo);
+    out->fits = out->n_streams + 1 < (1ull << 22) ? 1u : 0u;
+    return 0;
+}

@@ -269,7 +269,14 @@ void report_rows_records_stats(const kmdb_db* d, uint64_t lo, uint64_t hi) {
               << (rs.path == KMDB_ROWS_RECORDS_PATH_RECORDS ? "block records" : rs.path == KMDB_ROWS_RECORDS_PATH_TREE ? "tree fallback" : "nothing to do")
               << ", block rows " << rs.x_lo << " to " << rs.x_hi << " of width " << rs.width << ", " << rs.records << " records, apply units run / total " << rs.units_run
               << " / " << rs.units_total << ", " << rs.slices << " slices, sized call " << rs.sized_call << ", decode " << rs.k0_ms << " ms, narrow " << rs.k1n_ms
-              << " ms, wide " << rs.k1g_ms << " ms, apply " << rs.k2_ms << " ms, call " << rs.kernel_ms << " ms, peak " << rs.peak_device_bytes << " bytes" << std::endl;
+              << " ms, wide " << rs.k1g_ms << " ms, apply " << rs.k2_ms << " ms, call " << rs.kernel_ms << " ms, peak " << rs.peak_device_bytes << " bytes";
+    // the form the call took (KMDB_BAND_EMIT; beyond 2^22 block pairs band emit by itself), the band's streams and the band-emit state
+    kmdb_all2all_rows_band_emit_stats be{};
+    if (!kmdb_all2all_rows_band_emit_stats_get(d, &be))
+        std::cerr << ", form " << (be.form == KMDB_BAND_EMIT_FORM_BAND ? "band emit" : be.form == KMDB_BAND_EMIT_FORM_WHOLE ? "whole emit" : "none") << ", " << be.n_streams
+                  << " streams from " << be.stream_base << " in " << be.key_bits << " key bits, " << be.attempts << " attempts, band state " << be.state_bytes
+                  << " bytes, whole state " << be.whole_state_bytes << " bytes";
+    std::cerr << std::endl;
 }
 // -band-path <tree|tiled|records>: the band call of -rows / -band-rows
 enum class BandPath { unset, tree, tiled, records };
@@ -2923,8 +2930,12 @@ void usage() {
                  "                                  rows added cell by cell (the default of -rows); tiled: rows summed in LDS tiles (the default of\n"
                  "                                  -band-rows); records: the block-record pipeline of the whole-matrix call (decode, emit and sort run whole,\n"
                  "                                  the matrix-core apply on the band's block rows alone).  <output> holds the same bytes in all three.\n"
-                 "                                  Refused without -rows / -band-rows, with any other value and in any other mode; up to about 185 000\n"
-                 "                                  samples (2^22 block pairs), KMDB_K1N_MODE=1 is refused.  KMDB_VERBOSE: one line per band.\n";
+                 "                                  Refused without -rows / -band-rows, with any other value and in any other mode; KMDB_K1N_MODE=1 is\n"
+                 "                                  refused.  Beyond 2^22 block pairs (about 185 000 samples at width 64) records takes band emit by itself:\n"
+                 "                                  the records of the band's block rows alone, keyed relative to the band — fewer than 2^22 streams per band\n"
+                 "                                  and at most some 7 500 blocks (240 000 samples at width 32, 480 000 at width 64), else the band comes from\n"
+                 "                                  tree.  KMDB_BAND_EMIT=1 | 0: band emit for every band | never.  KMDB_VERBOSE: one line per band with the\n"
+                 "                                  form (whole emit | band emit), the band's streams and the band state's bytes.\n";
 }
 
 }  // namespace
