@@ -660,6 +660,13 @@ def _sample_texts(seqs):
     return keep, (C.c_void_p * max(n, 1))(*ptrs), (C.c_size_t * max(n, 1))(*lens), n
 
 
+def _stats_dict(fn, Struct, *args):
+    """the Struct that the getter fn(*args, pointer to it) fills, as a dict of its fields (a "reserved" field left out)"""
+    s = Struct()
+    _check(fn(*args, C.byref(s)))
+    return {f: getattr(s, f) for f, _ in Struct._fields_ if f != "reserved"}
+
+
 def _rows_out(raw):
     try:
         return SparseRows(raw)
@@ -684,9 +691,7 @@ class SparseRows:
 def band_streams(n_samples, width, row_lo, row_hi):
     """kmdbh_band_streams (host only, no GPU): the geometry of the band [row_lo, row_hi) in the block-record pipeline's streams at block width `width`
     as a dict of kmdb_band_geometry's fields"""
-    g = _BandGeometry()
-    _check(lib().kmdbh_band_streams(int(n_samples), int(width), int(row_lo), int(row_hi), C.byref(g)))
-    return {f: getattr(g, f) for f, _ in _BandGeometry._fields_}
+    return _stats_dict(lib().kmdbh_band_streams, _BandGeometry, int(n_samples), int(width), int(row_lo), int(row_hi))
 
 
 class DeviceDB:
@@ -748,75 +753,63 @@ class DeviceDB:
         o = _opts(self.device, shard, flags, stream)
         _check(lib().kmdb_all2all_dense_device(self._d, C.c_void_p(dev_ptr), C.byref(o)))
 
-    def all2all_rows(self, row_lo, row_hi, shard=(0, 1), flags=0):
-        """kmdb_all2all_rows: rows [row_lo, row_hi) of the matrix alone — the cells tri(row_lo) .. tri(row_hi) of the lower triangle, tri(i) =
-        i (i - 1) / 2, as a numpy uint32 array; nothing else of the triangle is computed or held anywhere"""
+    def _band_host(self, fn, row_lo, row_hi, shard, flags):
+        """a band call's host form fn: the cells of the rows [row_lo, row_hi) as a numpy uint32 array"""
         lo, hi = int(row_lo), int(row_hi)
         cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
         out = np.zeros(max(1, cells), dtype=np.uint32)
         o = _opts(self.device, shard, flags)
-        _check(lib().kmdb_all2all_rows(self._d, lo, hi, out.ctypes.data, C.byref(o)))
+        _check(fn(self._d, lo, hi, out.ctypes.data, C.byref(o)))
         return out[:cells]
+
+    def _band_device(self, fn, dev_ptr, row_lo, row_hi, stream, shard, flags):
+        """a band call's device form fn: the same cells left in device memory at dev_ptr"""
+        o = _opts(self.device, shard, flags, stream)
+        _check(fn(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+
+    def all2all_rows(self, row_lo, row_hi, shard=(0, 1), flags=0):
+        """kmdb_all2all_rows: rows [row_lo, row_hi) of the matrix alone — the cells tri(row_lo) .. tri(row_hi) of the lower triangle, tri(i) =
+        i (i - 1) / 2, as a numpy uint32 array; nothing else of the triangle is computed or held anywhere"""
+        return self._band_host(lib().kmdb_all2all_rows, row_lo, row_hi, shard, flags)
 
     def all2all_rows_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
         """kmdb_all2all_rows_device: the same band left in device memory at dev_ptr (e.g. a torch tensor's .data_ptr()): the layout
         sparse_from_dense_device (cell_lo = tri(row_lo), cell_hi = tri(row_hi)) and Distance.take_cells (row_lo) take"""
-        o = _opts(self.device, shard, flags, stream)
-        _check(lib().kmdb_all2all_rows_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+        self._band_device(lib().kmdb_all2all_rows_device, dev_ptr, row_lo, row_hi, stream, shard, flags)
 
     def all2all_rows_stats(self):
         """kmdb_all2all_rows_stats_get: the last band call on the handle"""
-        s = _All2allRowsStats()
-        _check(lib().kmdb_all2all_rows_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allRowsStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_rows_stats_get, _All2allRowsStats, self._d)
 
     def all2all_rows_tiled(self, row_lo, row_hi, shard=(0, 1), flags=0):
         """kmdb_all2all_rows_tiled: the band of all2all_rows, bit for bit, its rows summed in LDS tiles (KMDB_ROWS_TILE_COLS, KMDB_ROWS_TILE_HITS)"""
-        lo, hi = int(row_lo), int(row_hi)
-        cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
-        out = np.zeros(max(1, cells), dtype=np.uint32)
-        o = _opts(self.device, shard, flags)
-        _check(lib().kmdb_all2all_rows_tiled(self._d, lo, hi, out.ctypes.data, C.byref(o)))
-        return out[:cells]
+        return self._band_host(lib().kmdb_all2all_rows_tiled, row_lo, row_hi, shard, flags)
 
     def all2all_rows_tiled_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
         """kmdb_all2all_rows_tiled_device: the same band left in device memory at dev_ptr, the layout of all2all_rows_device"""
-        o = _opts(self.device, shard, flags, stream)
-        _check(lib().kmdb_all2all_rows_tiled_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+        self._band_device(lib().kmdb_all2all_rows_tiled_device, dev_ptr, row_lo, row_hi, stream, shard, flags)
 
     def all2all_rows_tiled_stats(self):
         """kmdb_all2all_rows_tiled_stats_get: the last tiled band call on the handle"""
-        s = _All2allRowsTiledStats()
-        _check(lib().kmdb_all2all_rows_tiled_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allRowsTiledStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_rows_tiled_stats_get, _All2allRowsTiledStats, self._d)
 
     def all2all_rows_records(self, row_lo, row_hi, shard=(0, 1), flags=0):
         """kmdb_all2all_rows_records: the band of all2all_rows, bit for bit, through the block-record pipeline (decode, emit, sort whole; the apply
         stage on the band's block rows alone)"""
-        lo, hi = int(row_lo), int(row_hi)
-        cells = max(0, hi * (hi - 1) // 2 - lo * (lo - 1) // 2) if 0 <= lo <= hi <= self.N else 0       # (a refused range: the library says why)
-        out = np.zeros(max(1, cells), dtype=np.uint32)
-        o = _opts(self.device, shard, flags)
-        _check(lib().kmdb_all2all_rows_records(self._d, lo, hi, out.ctypes.data, C.byref(o)))
-        return out[:cells]
+        return self._band_host(lib().kmdb_all2all_rows_records, row_lo, row_hi, shard, flags)
 
     def all2all_rows_records_device(self, dev_ptr, row_lo, row_hi, stream=None, shard=(0, 1), flags=0):
         """kmdb_all2all_rows_records_device: the same band left in device memory at dev_ptr, the layout of all2all_rows_device"""
-        o = _opts(self.device, shard, flags, stream)
-        _check(lib().kmdb_all2all_rows_records_device(self._d, int(row_lo), int(row_hi), C.c_void_p(dev_ptr), C.byref(o)))
+        self._band_device(lib().kmdb_all2all_rows_records_device, dev_ptr, row_lo, row_hi, stream, shard, flags)
 
     def all2all_rows_records_stats(self):
         """kmdb_all2all_rows_records_stats_get: the last band call through the block-record pipeline on the handle"""
-        s = _All2allRowsRecordsStats()
-        _check(lib().kmdb_all2all_rows_records_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allRowsRecordsStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_rows_records_stats_get, _All2allRowsRecordsStats, self._d)
 
     def all2all_rows_band_emit_stats(self):
         """kmdb_all2all_rows_band_emit_stats_get: the form the last records band call on the handle took (BAND_EMIT_FORM_*), its band's geometry in the
         pipeline's streams, and the band-emit state"""
-        s = _All2allRowsBandEmitStats()
-        _check(lib().kmdb_all2all_rows_band_emit_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allRowsBandEmitStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_rows_band_emit_stats_get, _All2allRowsBandEmitStats, self._d)
 
     def band_streams(self, row_lo, row_hi, width=None):
         """kmdbh_band_streams for this handle's samples; width: the handle's block width (known after its first all2all or band call) unless given"""
@@ -824,9 +817,7 @@ class DeviceDB:
 
     def all2all_banded_records_stats(self):
         """kmdb_all2all_banded_records_stats_get: the last banded call with path="records" on the handle"""
-        s = _All2allBandedRecordsStats()
-        _check(lib().kmdb_all2all_banded_records_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allBandedRecordsStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_banded_records_stats_get, _All2allBandedRecordsStats, self._d)
 
     def all2all_sparse_filtered_banded(self, band_rows, filters, sample_kmers, measure=None, shard=(0, 1), path=None):
         """kmdb_all2all_sparse_filtered_banded: all2all_sparse_filtered walked in bands of band_rows rows — one band resident at a time, the same
@@ -847,16 +838,11 @@ class DeviceDB:
             _check(lib().kmdb_all2all_sparse_filtered_banded_path(self._d, int(band_rows), BAND_PATHS.index(path) if isinstance(path, str) else int(path), fs,
                                                                   len(filters), None if cnt is None else cnt.ctypes.data,
                                                                   -1 if measure is None else METRICS.index(measure), C.byref(raw), C.byref(o)))
-        try:
-            return SparseRows(raw)
-        finally:
-            lib().kmdb_sparse_free(C.byref(raw))
+        return _rows_out(raw)
 
     def all2all_banded_stats(self):
         """kmdb_all2all_banded_stats_get: the last banded call on the handle"""
-        s = _All2allBandedStats()
-        _check(lib().kmdb_all2all_banded_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _All2allBandedStats._fields_}
+        return _stats_dict(lib().kmdb_all2all_banded_stats_get, _All2allBandedStats, self._d)
 
     def all2all_sparse(self, shard=(0, 1)):
         raw = _Sparse()
@@ -932,9 +918,7 @@ class DeviceDB:
 
     def sample_stats(self):
         """kmdb_db_sample_stats: the last sampled call on the handle"""
-        s = _SampleStats()
-        _check(lib().kmdb_db_sample_stats(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+        return _stats_dict(lib().kmdb_db_sample_stats, _SampleStats, self._d)
 
     def new2all(self, queries):
         qs = [np.ascontiguousarray(q, np.uint64) for q in queries]
@@ -997,9 +981,7 @@ class DeviceDB:
 
     def db2db_stats(self):
         """kmdb_db2db_stats_get: the last db2db call with this handle as the row database"""
-        s = _Db2dbStats()
-        _check(lib().kmdb_db2db_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _Db2dbStats._fields_}
+        return _stats_dict(lib().kmdb_db2db_stats_get, _Db2dbStats, self._d)
 
     def db2db_sampled(self, col, criterion, count, row_kmers, col_kmers, filters=()):
         """kmdb_db2db_sampled: the -sample-rows candidates of the cell (this database's samples = rows, `col`'s = columns), selected on the device.
@@ -1034,9 +1016,7 @@ class DeviceDB:
 
     def db2db_sample_stats(self):
         """kmdb_db2db_sample_stats_get: the last sampled db2db (or rectangle) call with this handle as the row database"""
-        s = _SampleStats()
-        _check(lib().kmdb_db2db_sample_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+        return _stats_dict(lib().kmdb_db2db_sample_stats_get, _SampleStats, self._d)
 
     def new2all_seq(self, seqs, fraction=1.0, start_fraction=0.0, preserve_strand=False, alphabet=None):
         """queries given as sequence text (bytes / str); k-mer extraction, minhash filter, sort + unique on the device.
@@ -1135,20 +1115,14 @@ class DeviceDB:
 
     def new2all_sample_stats(self):
         """kmdb_new2all_sample_stats_get: the last sampled new2all (or query-rows) call on the handle"""
-        s = _SampleStats()
-        _check(lib().kmdb_new2all_sample_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+        return _stats_dict(lib().kmdb_new2all_sample_stats_get, _SampleStats, self._d)
 
     def new2all_sparse_stats(self):
         """kmdb_new2all_sparse_stats_get: the last sparse new2all call on the handle"""
-        s = _New2allSparseStats()
-        _check(lib().kmdb_new2all_sparse_stats_get(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _New2allSparseStats._fields_}
+        return _stats_dict(lib().kmdb_new2all_sparse_stats_get, _New2allSparseStats, self._d)
 
     def stats(self):
-        s = _Stats()
-        _check(lib().kmdb_db_stats(self._d, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _Stats._fields_}
+        return _stats_dict(lib().kmdb_db_stats, _Stats, self._d)
 
     def fallback_reason(self):
         """why the last all2all call could not take the block-record pipeline ("" when it did)"""
@@ -1284,26 +1258,16 @@ class NodeDB:
 
     def new2all_sample_stats(self):
         """kmdb_node_new2all_sample_stats_get: the last sampled new2all call on the node (sums over the devices, the slowest select_ms)"""
-        s = _SampleStats()
-        _check(lib().kmdb_node_new2all_sample_stats_get(self._n, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _SampleStats._fields_ if f != "reserved"}
+        return _stats_dict(lib().kmdb_node_new2all_sample_stats_get, _SampleStats, self._n)
 
     def new2all_sparse_stats(self):
         """kmdb_node_new2all_sparse_stats_get: the last sparse new2all call on the node (sums over the devices, the slowest compact_ms)"""
-        s = _New2allSparseStats()
-        _check(lib().kmdb_node_new2all_sparse_stats_get(self._n, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in _New2allSparseStats._fields_}
+        return _stats_dict(lib().kmdb_node_new2all_sparse_stats_get, _New2allSparseStats, self._n)
 
     def stats(self):
-        s = _NodeStats()
-        _check(lib().kmdb_node_stats_get(self._n, C.byref(s)))
-        out = {f: getattr(s, f) for f, _ in _NodeStats._fields_}
-        out["partition"] = PARTITIONS[s.partition]
-        out["devices"] = []
-        for slot in range(s.n_devices):
-            ds = _NodeDeviceStats()
-            _check(lib().kmdb_node_device_stats_get(self._n, slot, C.byref(ds)))
-            out["devices"].append({f: getattr(ds, f) for f, _ in _NodeDeviceStats._fields_})
+        out = _stats_dict(lib().kmdb_node_stats_get, _NodeStats, self._n)
+        out["partition"] = PARTITIONS[out["partition"]]
+        out["devices"] = [_stats_dict(lib().kmdb_node_device_stats_get, _NodeDeviceStats, self._n, slot) for slot in range(out["n_devices"])]
         return out
 
     def close(self):
@@ -1431,17 +1395,13 @@ def minhash_batch(seqs, k, alphabet="nt", fraction=1.0, start_fraction=0.0, devi
 def minhash_stats():
     """kmdb_minhash_stats_get: the last minhash_batch call of this thread as a dict (stage times in ms from HIP events, kept / unique words,
     device bytes of the largest piece)"""
-    st = _MinhashStats()
-    _check(lib().kmdb_minhash_stats_get(C.byref(st)))
-    return {f: getattr(st, f) for f, _ in _MinhashStats._fields_}
+    return _stats_dict(lib().kmdb_minhash_stats_get, _MinhashStats)
 
 
 def minhash_long_stats():
     """kmdb_minhash_long_stats_get: the long samples of the last minhash_batch call of this thread as a dict (samples cut into sections, their
     sections, words into and out of the merge-unions, the unions' ms from HIP events and bytes, peak device bytes)"""
-    st = _MinhashLongStats()
-    _check(lib().kmdb_minhash_long_stats_get(C.byref(st)))
-    return {f: getattr(st, f) for f, _ in _MinhashLongStats._fields_}
+    return _stats_dict(lib().kmdb_minhash_long_stats_get, _MinhashLongStats)
 
 
 def sorted_union_geometry():
@@ -1500,9 +1460,7 @@ class Builder:
         return self
 
     def seed_stats(self):
-        st = _BuildSeedStats()
-        _check(lib().kmdb_build_seed_stats_get(self._b, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in _BuildSeedStats._fields_}
+        return _stats_dict(lib().kmdb_build_seed_stats_get, _BuildSeedStats, self._b)
 
     @staticmethod
     def _names(names):
@@ -1539,14 +1497,10 @@ class Builder:
         return DeviceDB._wrap(d, dev, host.N), host
 
     def handoff_stats(self):
-        st = _BuildHandoffStats()
-        _check(lib().kmdb_build_handoff_stats_get(self._b, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in _BuildHandoffStats._fields_}
+        return _stats_dict(lib().kmdb_build_handoff_stats_get, _BuildHandoffStats, self._b)
 
     def stats(self):
-        st = _BuildStats()
-        _check(lib().kmdb_build_stats_get(self._b, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in _BuildStats._fields_}
+        return _stats_dict(lib().kmdb_build_stats_get, _BuildStats, self._b)
 
     def close(self):
         if self._b:
@@ -1696,14 +1650,10 @@ class Distance:
         return out
 
     def parts_stats(self):
-        st = _DistancePartsStats()
-        _check(lib().kmdb_distance_parts_stats_get(self._d, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in _DistancePartsStats._fields_}
+        return _stats_dict(lib().kmdb_distance_parts_stats_get, _DistancePartsStats, self._d)
 
     def stats(self):
-        st = _DistanceStats()
-        _check(lib().kmdb_distance_stats_get(self._d, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in _DistanceStats._fields_}
+        return _stats_dict(lib().kmdb_distance_stats_get, _DistanceStats, self._d)
 
     def close(self):
         if self._d:

@@ -5,7 +5,7 @@
 // subtree weight W to column c for every id c < r of its root path (full lists ascend strictly: "in front of r" is "id < r", no position and no id
 // stack are needed).  uint32 adds form a group, so a run of consecutive ids [s, s + len) is entered into a tile as a difference, +W at s and -W
 // (modulo 2^32) at s + len, and one inclusive prefix sum over the tile gives the cells exactly.
-//   band_select_kernel  a lane per DFS node: the superset rule of rows_select_kernel, restated
+//   band_select_kernel  a lane per DFS node: the superset rule of rows_select_kernel, the same code (band_select.h)
 //   band_hits_kernel    a lane per selected node walks the node's OWN list and finds its ids inside the band (a "hit" = (row, node)): a count
 //                       pass, an exclusive sum of the per-row counts, a write pass — the hits grouped by row, sizes known before anything is written
 //   (host)              the job table from one copy of the per-row counts: job = (row r, tile [c0, c0 + T) with c0 < r, a share of the row's hits)
@@ -14,6 +14,7 @@
 //                       workgroup-wide inclusive scan, and every non-zero cell goes to the zeroed band with one atomicAdd (shares of a tile meet there)
 // Not done here: the list of one node is decoded by one lane per hit however long it is — a root with thousands of local ids inside the band is
 // thousands of hits in different rows, spread over workgroups, but each of them decodes the list again (a wave-cooperative decode: DESIGN.md §4).
+#include "band_select.h"
 #include "device_common.h"
 #include "engine_internal.h"
 #include "prim.h"
@@ -54,28 +55,8 @@ struct BandParams {
     uint32_t hits_lds;              // 1: the hit passes count per row in LDS first (a band of at most BAND_HITS_LDS_ROWS rows)
 };
 
-// the predicate of rows_select_kernel (a2a_rows.hip): the node has a local id (l > 0), a column to pair it with (n > 1) and a weight, its last id is
-// not in front of the band and its first id — behind the last id of the nearest ancestor that has one — can be inside it.  No list is read.
-__device__ __forceinline__ bool band_selects(const BandParams& p, uint32_t i) {
-    const uint4 m = p.meta[i];
-    const uint32_t W = p.wprefix[p.sub_end[i]] - p.wprefix[i];
-    if (!(m.y > 0 && m.x > 1 && W != 0 && m.z >= p.row_lo)) return false;
-    int32_t q = p.parent[i];
-    while (q >= 0 && p.meta[q].y == 0) q = p.parent[q];
-    return q < 0 || (uint64_t)p.meta[q].z + 1 < p.row_hi;
-}
-
-__global__ __launch_bounds__(256) void band_select_kernel(BandParams p) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane = lane_id();
-    const bool take = i < p.P && band_selects(p, i);
-    const unsigned long long bal = __ballot(take);
-    if (bal == 0) return;
-    uint32_t base = 0;
-    if (lane == (uint32_t)__builtin_ctzll(bal)) base = (uint32_t)atomicAdd(&p.counters[0], (unsigned long long)__popcll(bal));
-    base = bcast(base, (uint32_t)__builtin_ctzll(bal));
-    if (take) p.sel[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = i;
-}
+// the select rule and its compaction: band_select.h
+__global__ __launch_bounds__(256) void band_select_kernel(BandParams p) { band_select_nodes(p); }
 
 // A lane per selected node: the ids of the node's own list inside the band.  WRITE false: they are counted per row (and the node, and its hits,
 // in the counters); true: every one takes the next place of its row's group, which the count pass sized.
@@ -220,8 +201,6 @@ __global__ __launch_bounds__(BAND_THREADS) void band_apply_kernel(BandParams p) 
     if (tid == 0 && done[0]) { atomicAdd(&p.counters[3], done[0]); atomicAdd(&p.counters[4], done[1]); }
 }
 
-uint64_t tri_h(uint64_t i) { return i ? i * (i - 1) / 2 : 0; }
-
 // what the tiled call keeps on the handle between calls
 uint64_t band_device_bytes(const kmdb_db* db) {
     return db->band_sel.bytes() + db->band_counters.bytes() + db->band_rows.bytes() + db->band_hits.bytes() + db->band_jobs.bytes() + db->band_scan_tmp.bytes();
@@ -247,9 +226,9 @@ int band_switches(const char* who, uint32_t& tile_cols, uint32_t& tile_hits) {
     return 0;
 }
 
-int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipStream_t st) {
+int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, const kmdb_opts*, hipStream_t st) {
     const uint64_t P = db->P;
-    const uint64_t cell_lo = tri_h(row_lo), band_cells = tri_h(row_hi) - cell_lo;
+    const uint64_t band_cells = kmdb_tri(row_hi) - kmdb_tri(row_lo);
     uint32_t tile_cols = 0, tile_hits = 0;
     if (band_switches(who, tile_cols, tile_hits)) return 1;
     kmdb_all2all_rows_tiled_stats& bs = db->band_stats;
@@ -261,7 +240,6 @@ int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint6
     bool ran = false;
     uint64_t n_jobs = 0;
     if (row_hi > row_lo && P) {                                     // (row 0 alone has no cell, but a node may hold it: the stats count that node)
-        if (kmdb_ensure_v1_arrays(db)) return 1;
         const uint64_t rows1 = row_hi - row_lo + 1;
         if (!db->band_sel) {
             DEV_ALLOC(db->band_sel, P);
@@ -282,11 +260,8 @@ int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint6
         if (band_cells) HIP_TRY(hipMemsetAsync(out, 0, band_cells * 4, st));
         HIP_TRY(hipMemsetAsync(db->band_counters, 0, 8 * sizeof(unsigned long long), st));
         HIP_TRY(hipMemsetAsync(db->band_rows, 0, 3 * rows1 * sizeof(uint32_t), st));
-        // subtree weights = differences of the exclusive scan of w in DFS order, as in a2a_rows.hip
-        HIP_TRY(prim::exclusive_sum(db->v1_scan_tmp, db->v1_scan_tmp_bytes, db->w.get(), db->wprefix.get(), (int)(P + 1), st));
         BandParams p{};
-        p.meta = db->meta; p.bitpos = db->bitpos; p.parent = db->parent; p.sub_end = db->sub_end; p.wprefix = db->wprefix; p.bits = db->bits;
-        p.P = (uint32_t)P; p.row_lo = (uint32_t)row_lo; p.row_hi = (uint32_t)row_hi; p.cell_lo = cell_lo; p.out = out;
+        if (band_node_params(db, p, out, row_lo, row_hi, st)) return 1;
         p.sel = db->band_sel; p.counters = db->band_counters;
         p.row_cnt = db->band_rows; p.row_ofs = db->band_rows + rows1; p.row_cur = db->band_rows + 2 * rows1;
         p.tile_cols = tile_cols;
@@ -372,45 +347,17 @@ int band_run(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint6
         bs.nodes_selected = c[0]; bs.nodes_applied = c[1]; bs.hits = c[2]; bs.runs = c[3]; bs.updates = c[4];
         bs.jobs = n_jobs;
     }
-    const uint64_t now = band_device_bytes(db);
-    db->stats.device_bytes = db->stats.device_bytes - db->band_bytes_counted + now;
-    db->band_bytes_counted = now;
+    kmdb_recount_bytes(db, db->band_bytes_counted, band_device_bytes(db));
     return 0;
 }
 
 }  // namespace
 
 extern "C" int kmdb_all2all_rows_tiled_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts) {
-    const char* who = "kmdb_all2all_rows_tiled_device";
-    if (!db) return kmdb_set_error(std::string(who) + ": null argument");
-    if (kmdb_band_check(who, db, row_lo, row_hi, opts)) return 1;
-    const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
-    if (!out_cells_dev && band_cells) return kmdb_set_error(std::string(who) + ": null argument");
-    HIP_TRY(hipSetDevice(db->device));
-    if (kmdb_band_check_bytes(who, band_cells, false)) return 1;
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
-    const int rc = band_run(who, db, (uint32_t*)out_cells_dev, row_lo, row_hi, st);
-    kmdb_release_staging(db);
-    return rc;
+    return kmdb_band_call("kmdb_all2all_rows_tiled_device", db, row_lo, row_hi, out_cells_dev, false, opts, band_run);
 }
-
 extern "C" int kmdb_all2all_rows_tiled(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts) {
-    const char* who = "kmdb_all2all_rows_tiled";
-    if (!db) return kmdb_set_error(std::string(who) + ": null argument");
-    if (kmdb_band_check(who, db, row_lo, row_hi, opts)) return 1;
-    const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
-    if (!out_cells_host && band_cells) return kmdb_set_error(std::string(who) + ": null argument");
-    HIP_TRY(hipSetDevice(db->device));
-    if (kmdb_band_check_bytes(who, band_cells, true)) return 1;
-    DevBuf<uint32_t> band;
-    DEV_ALLOC(band, std::max<uint64_t>(band_cells, 1));
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
-    int rc = band_run(who, db, band, row_lo, row_hi, st);
-    if (!rc && band_cells && hipMemcpy(out_cells_host, band, band_cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = kmdb_set_error(std::string(who) + ": copy back failed");
-    band.reset();
-    kmdb_release_staging(db);
-    return rc;
+    return kmdb_band_call("kmdb_all2all_rows_tiled", db, row_lo, row_hi, out_cells_host, true, opts, band_run);
 }
 
 extern "C" int kmdb_all2all_rows_tiled_stats_get(const kmdb_db* db, kmdb_all2all_rows_tiled_stats* out) {
@@ -434,7 +381,7 @@ static int banded_run(const char* who, kmdb_db* db, uint64_t band_rows, int path
     uint64_t max_cells = 0;
     for (uint64_t lo = 0; lo < N; lo += std::min<uint64_t>(band_rows, N - lo)) {
         const uint64_t hi = lo + std::min<uint64_t>(band_rows, N - lo);
-        max_cells = std::max(max_cells, tri_h(hi) - tri_h(lo));
+        max_cells = std::max(max_cells, kmdb_tri(hi) - kmdb_tri(lo));
     }
     if (kmdb_band_check_bytes(who, max_cells, true)) return 1;
     kmdb_all2all_banded_stats bt{};
@@ -449,7 +396,7 @@ static int banded_run(const char* who, kmdb_db* db, uint64_t band_rows, int path
     int rc = 0;
     for (uint64_t lo = 0; lo < N && !rc;) {
         const uint64_t hi = lo + std::min<uint64_t>(band_rows, N - lo);
-        if (path == KMDB_BAND_PATH_TILED) rc = band_run(who, db, band, lo, hi, st);
+        if (path == KMDB_BAND_PATH_TILED) rc = band_run(who, db, band, lo, hi, opts, st);
         else if (path == KMDB_BAND_PATH_TREE) rc = kmdb_all2all_rows_device(db, lo, hi, band, opts);
         else rc = kmdb_all2all_rows_records_device(db, lo, hi, band, opts);
         if (rc) break;
@@ -465,7 +412,7 @@ static int banded_run(const char* who, kmdb_db* db, uint64_t band_rows, int path
         }
         bt.peak_device_bytes = std::max<uint64_t>(bt.peak_device_bytes, db->stats.device_bytes + band.bytes());
         kmdb_sparse_rows part{};
-        rc = kmdb_sparse_from_dense_device(db, band, tri_h(lo), tri_h(hi), filters, n_filters, sample_kmers, measure, &part, opts);
+        rc = kmdb_sparse_from_dense_device(db, band, kmdb_tri(lo), kmdb_tri(hi), filters, n_filters, sample_kmers, measure, &part, opts);
         if (rc) break;
         const uint64_t a = part.row_ptr[lo], b = part.row_ptr[hi];
         col.insert(col.end(), part.col + a, part.col + b);

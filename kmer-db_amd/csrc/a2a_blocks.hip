@@ -3237,7 +3237,8 @@ struct BlocksState {
     uint64_t est_n0 = 0, est_g0 = 0, est_l20 = 0;   // the sampled estimate as the width estimate left it: narrow, wide, and the part the second level replaces
     uint32_t est_stride = 1;
     uint32_t attempts = 0;          // attempts of the last call (1 + repeats)
-    int forced_row_mode = -1;       // band emit: the record path kmdb_blocks_band_prepare chose for the state (0 / 1); -1: by the streams and KMDB_ROW_MODE
+    std::string gave_up;            // why the last call's attempt gave up at run time ("" = it did not): kmdb_blocks_run publishes it to the handle
+    int forced_row_mode = -1;      // band emit: the record path kmdb_blocks_band_prepare chose for the state (0 / 1); -1: by the streams and KMDB_ROW_MODE
 
     ~BlocksState() { if (h_counters) (void)hipHostFree(h_counters); }
 };
@@ -3674,12 +3675,12 @@ static uint64_t state_device_bytes(const kmdb_db* db, const BlocksState& b) {
            (b.wide_pool_cap << WCH_SHIFT) * (b.row_mode ? 20 : 40) + b.rs_entries * 8 + (uint64_t)b.cap_states * 12 +
            (uint64_t)b.NB * (b.l2_node_cap / 64u) * 12 + (uint64_t)b.l2_ent_cap * 26 + (uint64_t)b.l2_node_cap * 4;
 }
-// both states of the handle: the whole matrix's and, once a band-emit call made it, the band's
-uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) {
-    return (db->blocks ? state_device_bytes(db, *db->blocks) : 0u) + (db->band_blocks ? state_device_bytes(db, *db->band_blocks) : 0u);
+uint64_t kmdb_blocks_state_bytes(const kmdb_db* db, bool band_state) {
+    const BlocksState* s = band_state ? db->band_blocks.get() : db->blocks.get();
+    return s ? state_device_bytes(db, *s) : 0u;
 }
-uint64_t kmdb_blocks_whole_state_bytes(const kmdb_db* db) { return db->blocks ? state_device_bytes(db, *db->blocks) : 0u; }
-uint64_t kmdb_blocks_band_state_bytes(const kmdb_db* db) { return db->band_blocks ? state_device_bytes(db, *db->band_blocks) : 0u; }
+// both states of the handle: the whole matrix's and, once a band-emit call made it, the band's
+uint64_t kmdb_blocks_device_bytes(const kmdb_db* db) { return kmdb_blocks_state_bytes(db, false) + kmdb_blocks_state_bytes(db, true); }
 
 namespace {
 
@@ -4023,7 +4024,7 @@ int a2a_sort_apply_flat(kmdb_db* db, BlocksState& b, uint32_t* M, hipStream_t st
     return 0;
 }
 // a pool ran over (results invalid): it is enlarged — or, at the limit of what a pool can index, the call takes more slices of the pattern stream —
-// and the call repeated.  Leaves db->fallback_reason when neither is possible.
+// and the call repeated.  Leaves b.gave_up when neither is possible.
 int a2a_enlarge_pools(kmdb_db* db, BlocksState& b, const uint32_t* c) {
     const bool verbose = kmdb_verbose();
     if (c[KCTR_PAIR_OVERFLOW]) {
@@ -4033,7 +4034,7 @@ int a2a_enlarge_pools(kmdb_db* db, BlocksState& b, const uint32_t* c) {
     if (c[KCTR_WIDE_OVERFLOW]) {
         const uint64_t want = b.wide_pool_cap * 2;
         if ((want << WCH_SHIFT) >= pool_slot_limit(b)) {
-            if (b.n_slices >= (1u << 16)) { db->fallback_reason = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
+            if (b.n_slices >= (1u << 16)) { b.gave_up = "more block records than a pool can index from the nodes with many blocks in a 65536th of the patterns"; return 0; }
             b.n_slices *= 2;                                  // the pools stay as they are: half as many patterns per pass
             if (verbose) fprintf(stderr, "[kmdb] wide record pool at its limit: %u slices of the pattern stream per call\n", b.n_slices);
             return 0;
@@ -4057,7 +4058,7 @@ int a2a_enlarge_pools(kmdb_db* db, BlocksState& b, const uint32_t* c) {
             want = 0;
         } else if ((want << CH_SHIFT) >= pool_slot_limit(b)) {
             if (b.n_slices >= (1u << 16)) {
-                db->fallback_reason = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(b.n_states) + " streams, " + std::to_string(b.pool_cap) + " chunks were not enough)";
+                b.gave_up = "more block records than a pool can index in a 65536th of the patterns (" + std::to_string(b.n_states) + " streams, " + std::to_string(b.pool_cap) + " chunks were not enough)";
                 return 0;
             }
             b.n_slices *= 2;
@@ -4079,7 +4080,7 @@ int a2a_settle(kmdb_db* db, BlocksState& b, hipStream_t st, const Launched& L, b
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t* c = b.h_counters;
     if (c[KCTR_LIST_OVERFLOW] || c[KCTR_SLOW]) {
-        db->fallback_reason = "internal: the wide-node kernel lost a list (chain miss " + std::to_string(c[KCTR_SLOW]) + ", arena overflow " + std::to_string(c[KCTR_LIST_OVERFLOW]) + ")";
+        b.gave_up = "internal: the wide-node kernel lost a list (chain miss " + std::to_string(c[KCTR_SLOW]) + ", arena overflow " + std::to_string(c[KCTR_LIST_OVERFLOW]) + ")";
         return 0;
     }
     if (c[KCTR_L2_OVERFLOW]) {
@@ -4090,7 +4091,7 @@ int a2a_settle(kmdb_db* db, BlocksState& b, hipStream_t st, const Launched& L, b
     }
     if (c[KCTR_PAIR_OVERFLOW] || c[KCTR_POOL_OVERFLOW] || c[KCTR_WIDE_OVERFLOW]) {
         if (a2a_enlarge_pools(db, b, c)) return 1;
-        if (db->fallback_reason.empty()) { b.have_counts = false; *retry = true; }
+        if (b.gave_up.empty()) { b.have_counts = false; *retry = true; }
         return 0;
     }
     if (b.have_counts && (c[KCTR_NWIDE] != b.last_n_wide || c[KCTR_CHUNKS] != b.last_n_chunks ||
@@ -4195,14 +4196,12 @@ static int blocks_read_band_units(BlocksState& b, hipStream_t st) {
 
 int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band) {
     // band emit runs on the handle's second state (made and fitted to the band by kmdb_blocks_band_prepare); nothing of the whole-matrix state is touched,
-    // the reason it may hold — why the whole matrix cannot go through the pipeline — included: what this call finds is left in band_fallback_reason
+    // the reason the handle may hold — why the whole matrix cannot go through the pipeline — included: an attempt that gives up says so on the state it
+    // ran on (gave_up), and that is published to the reason of this call's form
     const bool emit = band && band->emit;
     BlocksState& b = emit ? *db->band_blocks : *db->blocks;
-    struct ReasonSwap {
-        kmdb_db* db; bool on; std::string whole;
-        ReasonSwap(kmdb_db* d, bool o) : db(d), on(o) { if (on) { whole.swap(db->fallback_reason); db->band_fallback_reason.clear(); } }
-        ~ReasonSwap() { if (on) { db->band_fallback_reason.swap(db->fallback_reason); db->fallback_reason.swap(whole); } }
-    } reason_swap{db, emit};
+    b.gave_up.clear();
+    if (emit) db->band_fallback_reason.clear();                     // (per call; the whole matrix's is empty, or its callers would not be here, and sticks)
     // what a repeated round zeroes: the words of M — the whole triangle, or the band's cells only
     const uint64_t cells = band ? band->cells : db->N * (db->N - 1) / 2;
     if (band && !b.band_units) DEV_ALLOC(b.band_units, (size_t)BAND_UNIT_SLOTS * BAND_UNIT_WORDS);
@@ -4231,7 +4230,7 @@ int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi
             bool retry = false;
             if (blocks_attempt(db, b, M, lo, hi, !decoded, st, &retry, band)) { blocks_join_side_streams(db); return 1; }
             decoded = true;
-            if (!db->fallback_reason.empty()) return 0;
+            if (!b.gave_up.empty()) { (emit ? db->band_fallback_reason : db->fallback_reason) = b.gave_up; return 0; }
             if (retry) { again = true; for (auto& c : b.slice_counts) c.valid = false; }
             else {
                 sc = BlocksState::SliceCounts{true, lo, hi, b.last_n_wide, b.last_n_chunks, b.last_n_raw, b.last_n_rowjobs, b.last_n_sorted, b.last_n_k2jobs};
@@ -4254,15 +4253,14 @@ kmdb_blocks_counts kmdb_blocks_last_counts(const kmdb_db* db) {
     return kmdb_blocks_counts{b.last_records, b.last_n_direct, b.last_n_wide, b.last_n_chunks, b.l2_on ? b.last_l2_nodes : 0u};
 }
 const unsigned char* kmdb_blocks_tile_touched(const kmdb_db* db) { return db->blocks ? db->blocks->tile_touched.get() : nullptr; }
-kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db) { return db->blocks ? db->blocks->last_band_units : kmdb_blocks_band_units{}; }
-int kmdb_blocks_k1n_mode(const kmdb_db* db) { return db->blocks ? db->blocks->k1n_mode : -1; }
-uint32_t kmdb_blocks_n_slices(const kmdb_db* db) { return db->blocks ? std::max<uint32_t>(1u, db->blocks->n_slices) : 1u; }
+int kmdb_blocks_k1n_mode(const kmdb_db* db, bool band_state) {
+    if (!band_state) return db->blocks ? db->blocks->k1n_mode : -1;
+    return db->band_blocks ? db->band_blocks->knobs.k1n_mode : blocks_read_knobs().k1n_mode;
+}
 
 // ------------------------------------------------------------------------------------------
 // band emit: the handle's second state (kmdb_db.band_blocks), keyed relative to the band
 // ------------------------------------------------------------------------------------------
-// KMDB_K1N_MODE as a band-emit state would read it (the whole-matrix state of a collection beyond 2^22 block pairs never got as far as its switches)
-int kmdb_blocks_band_k1n_mode(const kmdb_db* db) { return db->band_blocks ? db->band_blocks->knobs.k1n_mode : blocks_read_knobs().k1n_mode; }
 
 // Why band emit cannot take this band ("": it can).  The streams: relative keys must leave all-ones free in 22 bits of a key word (KMDB_BAND_MAX_STREAMS, a
 // test switch, lowers the limit; values above 2^22 are clamped).  The bytes: a list of the wide kernel may have as many entries as the collection has blocks.

@@ -11,9 +11,9 @@
 // uint32 adds wrap and commute: the band is bit-exact with the same cells of kmdb_all2all_dense_device in any order.
 // Not done here: a node is one wave's work however long its list is (a root with thousands of local ids under a wide band is applied by
 // a single wave; splitting it is left open).
+#include "band_select.h"
 #include "device_common.h"
 #include "engine_internal.h"
-#include "prim.h"
 
 #include <algorithm>
 #include <string>
@@ -43,28 +43,8 @@ struct RowsParams {
     uint32_t n_waves;
 };
 
-// A node's local ids lie strictly between its parent's last id and its own last id (inclusive), so: it has one (l > 0), it has a column to pair
-// with (n > 1), it carries a weight, its last id is not in front of the band and its first id can be inside it.  A superset: no list is read.
-__global__ __launch_bounds__(256) void rows_select_kernel(RowsParams p) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane = lane_id();
-    bool take = false;
-    if (i < p.P) {
-        const uint4 m = p.meta[i];
-        const uint32_t W = p.wprefix[p.sub_end[i]] - p.wprefix[i];
-        if (m.y > 0 && m.x > 1 && W != 0 && m.z >= p.row_lo) {
-            int32_t q = p.parent[i];
-            while (q >= 0 && p.meta[q].y == 0) q = p.parent[q];            // (a pattern without ids of its own has no last id to go by)
-            take = q < 0 || (uint64_t)p.meta[q].z + 1 < p.row_hi;
-        }
-    }
-    const unsigned long long bal = __ballot(take);
-    if (bal == 0) return;
-    uint32_t base = 0;
-    if (lane == (uint32_t)__builtin_ctzll(bal)) base = (uint32_t)atomicAdd(&p.counters[0], (unsigned long long)__popcll(bal));
-    base = bcast(base, (uint32_t)__builtin_ctzll(bal));
-    if (take) p.sel[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = i;
-}
+// the select rule and its compaction: band_select.h
+__global__ __launch_bounds__(256) void rows_select_kernel(RowsParams p) { band_select_nodes(p); }
 
 // One selected node on the id stack `stack` (LDS or global scratch; stack[0 .. n) is the node's full list when this returns to the adds).
 // GLOBAL: the stack is global memory — its writes are fenced for the wave's other lanes; an LDS stack needs the compiler kept in order only.
@@ -128,21 +108,18 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void rows_apply_kernel(Rows
     if (lane == 0 && updates) atomicAdd(&p.counters[2], updates);
 }
 
-uint64_t tri_h(uint64_t i) { return i ? i * (i - 1) / 2 : 0; }
-
 // what the band path keeps on the handle between calls
 uint64_t rows_device_bytes(const kmdb_db* db) { return db->rows_sel.bytes() + db->rows_counters.bytes(); }
 
-int rows_run(kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipStream_t st) {
+int rows_run(const char*, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, const kmdb_opts*, hipStream_t st) {
     const uint64_t N = db->N, P = db->P;
-    const uint64_t cell_lo = tri_h(row_lo), band_cells = tri_h(row_hi) - cell_lo;
+    const uint64_t band_cells = kmdb_tri(row_hi) - kmdb_tri(row_lo);
     kmdb_all2all_rows_stats& rs = db->rows_stats;
     rs = kmdb_all2all_rows_stats{};
     rs.band_cells = band_cells;
     HIP_TRY(hipEventRecord(db->ev[0], st));
     bool ran = false;
     if (row_hi > row_lo && P) {                                     // (row 0 alone has no cell, but a node may hold it: the stats count that node)
-        if (kmdb_ensure_v1_arrays(db)) return 1;
         if (!db->rows_sel) {
             DEV_ALLOC(db->rows_sel, P);
             DEV_ALLOC(db->rows_counters, 4);
@@ -159,11 +136,8 @@ int rows_run(kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipSt
         rs.scratch_bytes = db->rows_sel.bytes() + db->rows_counters.bytes() + db->stack_scratch.bytes();
         if (band_cells) HIP_TRY(hipMemsetAsync(out, 0, band_cells * 4, st));
         HIP_TRY(hipMemsetAsync(db->rows_counters, 0, 4 * sizeof(unsigned long long), st));
-        // subtree weights (reference similarity_calculator.cpp:64-72) = differences of the exclusive scan of w in DFS order, as before the v1 kernels
-        HIP_TRY(prim::exclusive_sum(db->v1_scan_tmp, db->v1_scan_tmp_bytes, db->w.get(), db->wprefix.get(), (int)(P + 1), st));
         RowsParams p{};
-        p.meta = db->meta; p.bitpos = db->bitpos; p.parent = db->parent; p.sub_end = db->sub_end; p.wprefix = db->wprefix; p.bits = db->bits;
-        p.P = (uint32_t)P; p.row_lo = (uint32_t)row_lo; p.row_hi = (uint32_t)row_hi; p.cell_lo = cell_lo; p.out = out;
+        if (band_node_params(db, p, out, row_lo, row_hi, st)) return 1;
         p.sel = db->rows_sel; p.counters = db->rows_counters; p.stack_scratch = db->stack_scratch; p.stack_stride = (uint32_t)stride; p.n_waves = n_waves;
         HIP_TRY(hipEventRecord(db->ev[1], st));
         hipLaunchKernelGGL(rows_select_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, p);
@@ -189,9 +163,7 @@ int rows_run(kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, hipSt
         HIP_TRY(hipMemcpy(c, db->rows_counters, sizeof c, hipMemcpyDeviceToHost));
         rs.nodes_selected = c[0]; rs.nodes_applied = c[1]; rs.updates = c[2];
     }
-    const uint64_t now = rows_device_bytes(db);
-    db->stats.device_bytes = db->stats.device_bytes - db->rows_bytes_counted + now;
-    db->rows_bytes_counted = now;
+    kmdb_recount_bytes(db, db->rows_bytes_counted, rows_device_bytes(db));
     return 0;
 }
 
@@ -220,35 +192,32 @@ int kmdb_band_check_bytes(const char* who, uint64_t band_cells, bool against_fre
     return 0;
 }
 
-extern "C" int kmdb_all2all_rows_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts) {
-    if (!db) return kmdb_set_error("kmdb_all2all_rows_device: null argument");
-    if (kmdb_band_check("kmdb_all2all_rows_device", db, row_lo, row_hi, opts)) return 1;
-    const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
-    if (!out_cells_dev && band_cells) return kmdb_set_error("kmdb_all2all_rows_device: null argument");
+// Everything the six band entry points share, in one order: the refusals — null handle; range, shard, flags, query shard; null buffer for a band with
+// cells; a band beyond the device — then the stream, the form's runner (on a band buffer of the call's own when `out` is host memory: made, copied back
+// and released here) and the upload's host buffers given back.
+int kmdb_band_call(const char* who, kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out, bool host_out, const kmdb_opts* opts, kmdb_band_runner run) {
+    if (!db) return kmdb_set_error(std::string(who) + ": null argument");
+    if (kmdb_band_check(who, db, row_lo, row_hi, opts)) return 1;
+    const uint64_t band_cells = kmdb_tri(row_hi) - kmdb_tri(row_lo);
+    if (!out && band_cells) return kmdb_set_error(std::string(who) + ": null argument");
     HIP_TRY(hipSetDevice(db->device));
-    if (kmdb_band_check_bytes("kmdb_all2all_rows_device", band_cells, false)) return 1;
+    if (kmdb_band_check_bytes(who, band_cells, host_out)) return 1;
+    DevBuf<uint32_t> band;
+    if (host_out) DEV_ALLOC(band, std::max<uint64_t>(band_cells, 1));
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
-    const int rc = rows_run(db, (uint32_t*)out_cells_dev, row_lo, row_hi, st);
+    int rc = run(who, db, host_out ? band.get() : (uint32_t*)out, row_lo, row_hi, opts, st);
+    if (host_out && !rc && band_cells && hipMemcpy(out, band, band_cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = kmdb_set_error(std::string(who) + ": copy back failed");
+    band.reset();
     kmdb_release_staging(db);
     return rc;
 }
 
+extern "C" int kmdb_all2all_rows_device(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out_cells_dev, const kmdb_opts* opts) {
+    return kmdb_band_call("kmdb_all2all_rows_device", db, row_lo, row_hi, out_cells_dev, false, opts, rows_run);
+}
 extern "C" int kmdb_all2all_rows(kmdb_db* db, uint64_t row_lo, uint64_t row_hi, uint32_t* out_cells_host, const kmdb_opts* opts) {
-    if (!db) return kmdb_set_error("kmdb_all2all_rows: null argument");
-    if (kmdb_band_check("kmdb_all2all_rows", db, row_lo, row_hi, opts)) return 1;
-    const uint64_t band_cells = tri_h(row_hi) - tri_h(row_lo);
-    if (!out_cells_host && band_cells) return kmdb_set_error("kmdb_all2all_rows: null argument");
-    HIP_TRY(hipSetDevice(db->device));
-    if (kmdb_band_check_bytes("kmdb_all2all_rows", band_cells, true)) return 1;
-    DevBuf<uint32_t> band;
-    DEV_ALLOC(band, std::max<uint64_t>(band_cells, 1));
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : db->stream;
-    int rc = rows_run(db, band, row_lo, row_hi, st);
-    if (!rc && band_cells && hipMemcpy(out_cells_host, band, band_cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = kmdb_set_error("kmdb_all2all_rows: copy back failed");
-    band.reset();
-    kmdb_release_staging(db);
-    return rc;
+    return kmdb_band_call("kmdb_all2all_rows", db, row_lo, row_hi, out_cells_host, true, opts, rows_run);
 }
 
 // Device memory for a caller that has no HIP of its own (the command-line front-end keeps a band between the band call and its consumers)

@@ -371,6 +371,21 @@ extern "C" int kmdb_db_stats(const kmdb_db* db, kmdb_stats* out) {
 // ------------------------------------------------------------------------------------------
 // dense all2all
 // ------------------------------------------------------------------------------------------
+// (engine_state.h) what run_dense and the band call of a2a_rows_records.hip do before and after kmdb_blocks_run
+int kmdb_blocks_ensure_prepared(kmdb_db* db) {
+    if (db->blocks_prepared) return 0;
+    if (kmdb_blocks_prepare(db)) return 1;
+    db->blocks_bytes_counted = kmdb_blocks_device_bytes(db);
+    db->stats.device_bytes += db->blocks_bytes_counted;
+    db->stats.width = db->width;
+    return 0;
+}
+int kmdb_blocks_stage_ms(kmdb_db* db, float ms[4]) {
+    HIP_TRY(hipEventElapsedTime(&ms[0], db->ev[1], db->ev_k[0]));
+    for (int i = 1; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], db->ev_k[i - 1], db->ev_k[i]));
+    return 0;
+}
+
 namespace {
 
 // the whole dense pipeline on `st`; M is device memory of N(N-1)/2 uint32
@@ -391,12 +406,7 @@ int run_dense(kmdb_db* db, uint32_t* M, const kmdb_opts* opts, hipStream_t st) {
     db->stats.n_records = 0; db->stats.n_direct = 0; db->stats.n_wide = 0; db->stats.n_chunks = 0; db->stats.tile_flushes = 0; db->stats.sized_call = 0;
     if (!cells || !P) { HIP_TRY(hipEventRecord(db->ev[1], st)); HIP_TRY(hipEventRecord(db->ev[2], st)); return 0; }
     const bool forced_v1 = (flags & (KMDB_FLAG_FORCE_GLOBAL_ATOMICS | KMDB_FLAG_FORCE_DIRECT | KMDB_FLAG_FORCE_TILE)) != 0;
-    if (!forced_v1 && !db->blocks_prepared) {
-        if (kmdb_blocks_prepare(db)) return 1;
-        db->blocks_bytes_counted = kmdb_blocks_device_bytes(db);
-        db->stats.device_bytes += db->blocks_bytes_counted;
-        db->stats.width = db->width;
-    }
+    if (!forced_v1 && kmdb_blocks_ensure_prepared(db)) return 1;
     if (!forced_v1 && db->fallback_reason.empty()) {
         // block-record pipeline (flat form: on-disk weights, no subtree sums needed)
         HIP_TRY(hipEventRecord(db->ev[1], st));
@@ -447,21 +457,16 @@ int finish_stats(kmdb_db* db, hipStream_t st) {
     HIP_TRY(hipEventElapsedTime(&a, db->ev[0], db->ev[3]));
     db->stats.kernel_ms = a;
     if (db->stats.path == KMDB_PATH_RECORDS) {
-        float k0 = 0, k1n = 0, k1g = 0, k2 = 0;
-        HIP_TRY(hipEventElapsedTime(&k0, db->ev[1], db->ev_k[0]));
-        HIP_TRY(hipEventElapsedTime(&k1n, db->ev_k[0], db->ev_k[1]));
-        HIP_TRY(hipEventElapsedTime(&k1g, db->ev_k[1], db->ev_k[2]));
-        HIP_TRY(hipEventElapsedTime(&k2, db->ev_k[2], db->ev_k[3]));
-        db->stats.k0_ms = k0; db->stats.k1n_ms = k1n; db->stats.k1g_ms = k1g; db->stats.k1_ms = k1n + k1g; db->stats.k2_ms = k2;
+        float k[4];
+        if (kmdb_blocks_stage_ms(db, k)) return 1;
+        db->stats.k0_ms = k[0]; db->stats.k1n_ms = k[1]; db->stats.k1g_ms = k[2]; db->stats.k1_ms = k[1] + k[2]; db->stats.k2_ms = k[3];
         const kmdb_blocks_counts last = kmdb_blocks_last_counts(db);
         db->stats.n_records = last.records; db->stats.n_wide = last.wide; db->stats.n_chunks = last.chunks;
         db->stats.n_joined = last.joined;
         db->stats.n_direct = last.direct;
         // the pipeline's arrays grow inside calls (second-level arrays on the first call, pools enlarged by a quarter or doubled): what is
         // resident NOW, not what the preparation allocated
-        const uint64_t now = kmdb_blocks_device_bytes(db);
-        db->stats.device_bytes = db->stats.device_bytes - db->blocks_bytes_counted + now;
-        db->blocks_bytes_counted = now;
+        kmdb_recount_bytes(db, db->blocks_bytes_counted, kmdb_blocks_device_bytes(db));
     } else if (db->v1_counters && db->stats.path != KMDB_PATH_NONE) {
         unsigned long long c[8];
         HIP_TRY(hipMemcpy(c, db->v1_counters, sizeof c, hipMemcpyDeviceToHost));

@@ -119,6 +119,13 @@ constexpr int KMDB_ROWS_LDS_CAP = 1024;   // a full list of up to this many ids 
 // (against_free: its free memory — the call allocates the band itself).  0, or 1 with the error set.
 int kmdb_band_check(const char* who, const kmdb_db* db, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts);
 int kmdb_band_check_bytes(const char* who, uint64_t band_cells, bool against_free);
+// cells in front of row i of the lower triangle (the host's; the kernels' is tri64 of device_common.h)
+inline uint64_t kmdb_tri(uint64_t i) { return i ? i * (i - 1) / 2 : 0; }
+// A band entry point whole (a2a_rows.hip): null handle, kmdb_band_check, null buffer for a band with cells, the device, kmdb_band_check_bytes, the stream,
+// `run` — the form's own work, `out` device memory for it — and kmdb_release_staging.  host_out: `out` is host memory; the band is made on the device for
+// the call, copied back and released.
+typedef int (*kmdb_band_runner)(const char* who, kmdb_db* db, uint32_t* out, uint64_t row_lo, uint64_t row_hi, const kmdb_opts* opts, hipStream_t st);
+int kmdb_band_call(const char* who, kmdb_db* db, uint64_t row_lo, uint64_t row_hi, void* out, bool host_out, const kmdb_opts* opts, kmdb_band_runner run);
 
 // sort + matrix-core accumulation of block records into a dense n_rows x n_cols matrix (a2a_blocks.hip; used by db2db.hip).
 // Record = 16 bytes {row mask, column mask} + key word {stream = row block * nbc + column block | (weight digit | digit index << d) << key_bits},

@@ -1,6 +1,6 @@
 // engine_state.h — the HBM-resident database shared by the translation units of libkmdb_amd.so
 // (engine.hip: entry points, layout.hip: upload, a2a_v1.hip: scatter kernels, a2a_blocks.hip: block-record pipeline, a2a_rows.hip: a band of
-// the matrix's rows, a2a_band.hip: the same band summed in LDS tiles and a run walked in bands, a2a_rows_records.hip: the same band through the
+// the matrix's rows, a2a_band.hip: the same band summed in LDS tiles and a run walked in bands (band_select.h: what the two share), a2a_rows_records.hip: the same band through the
 // block-record pipeline, node_arrays.hip: the node arrays of the v1 kernels and of new2all).
 #pragma once
 #include "kmdb_amd.h"
@@ -185,25 +185,35 @@ int kmdb_blocks_prepare(kmdb_db* db);
 // the band's block rows alone, keyed relative to its first stream, and every later stage works on the band's streams only
 struct kmdb_band_desc { uint64_t row_lo, row_hi, cell_lo, cells; bool emit = false; };
 int kmdb_blocks_run(kmdb_db* db, uint32_t* M, uint32_t emit_lo, uint32_t emit_hi, hipStream_t st, const kmdb_band_desc* band = nullptr);
+// A give-up inside the run (the pools at what they can index, a list lost by the wide kernel) is written to the state that ran and published when the
+// call returns 0: to db->fallback_reason by the whole-matrix state (sticky: the handle skips the pipeline from then on), to db->band_fallback_reason by
+// the band-emit state ("" again at its next call).
 // ---- band emit (a2a_blocks.hip; a2a_rows_records.hip decides which form a band call takes)
-// KMDB_K1N_MODE as the band-emit state reads it; why band emit cannot take the band g ("": it can); the state made or fitted for g, band_cells = its cells
-int kmdb_blocks_band_k1n_mode(const kmdb_db* db);
+// why band emit cannot take the band g ("": it can); the state made or fitted for g, band_cells = its cells
 std::string kmdb_blocks_band_refusal(const kmdb_db* db, const kmdb_band_geometry* g);
 int kmdb_blocks_band_prepare(kmdb_db* db, const kmdb_band_geometry* g, uint64_t band_cells);
-// the two states' device bytes (kmdb_blocks_device_bytes is their sum); the band-emit state after its last call: kmdb_blocks_band_last, below
-uint64_t kmdb_blocks_whole_state_bytes(const kmdb_db* db);
-uint64_t kmdb_blocks_band_state_bytes(const kmdb_db* db);
-// the apply units of the last band call: stream jobs, window runs of stream chunks, slices' tiles of first-block records, second-level tiles
+// ---- what a band caller reads of one of the two states (band_state: the band-emit state; else the whole-matrix state)
+// the narrow kernel's mode, asked before the run (KMDB_K1N_MODE; 1 writes the matrix itself): of the state, -1 without a whole-matrix state, as a
+// band-emit state yet to be made would read it (the whole-matrix state of a collection beyond 2^22 block pairs never got as far as its switches)
+int kmdb_blocks_k1n_mode(const kmdb_db* db, bool band_state);
+// the state's device bytes (kmdb_blocks_device_bytes is the sum of both)
+uint64_t kmdb_blocks_state_bytes(const kmdb_db* db, bool band_state);
+// the state's last band call; units: stream jobs, window runs of stream chunks, slices' tiles of first-block records, second-level tiles of the apply stage
 struct kmdb_blocks_band_units { uint64_t jobs, jobs_run, runs, runs_run, slices, slices_run, tiles, tiles_run; };
-kmdb_blocks_band_units kmdb_blocks_last_band_units(const kmdb_db* db);
 struct kmdb_blocks_band_info { uint32_t key_bits, row_mode, l2_on, attempts, slices; uint64_t records, est_records; kmdb_blocks_band_units units; };
-// (of the band-emit state, or of the whole-matrix state after a parent-form band call)
 kmdb_blocks_band_info kmdb_blocks_band_last(const kmdb_db* db, bool band_state);
-// what a band caller asks before it runs: the narrow kernel's mode (KMDB_K1N_MODE; 1 writes the matrix itself), passes over the pattern stream per call
-int kmdb_blocks_k1n_mode(const kmdb_db* db);
-uint32_t kmdb_blocks_n_slices(const kmdb_db* db);
 void kmdb_blocks_release(kmdb_db* db);
 uint64_t kmdb_blocks_device_bytes(const kmdb_db* db);
+// ---- the lines every caller of the pipeline repeats (engine.hip)
+// kmdb_blocks_prepare at the handle's first call that needs it, its arrays entered into stats.device_bytes
+int kmdb_blocks_ensure_prepared(kmdb_db* db);
+// the last run's stage times from the call's events: ms[0 .. 3] = decode (from ev[1]), narrow emit, wide emit, apply
+int kmdb_blocks_stage_ms(kmdb_db* db, float ms[4]);
+// a share of stats.device_bytes whose arrays are made and grow inside calls, counted again: `counted` is what stats holds of it, `now` what is resident
+inline void kmdb_recount_bytes(kmdb_db* db, uint64_t& counted, uint64_t now) {
+    db->stats.device_bytes = db->stats.device_bytes - counted + now;
+    counted = now;
+}
 // what the last kmdb_blocks_run found (the statistics of the call), and the tiles it added to: [block pairs] != 0, or null without a working set
 struct kmdb_blocks_counts { uint64_t records, direct; uint32_t wide, chunks, joined; };
 kmdb_blocks_counts kmdb_blocks_last_counts(const kmdb_db* db);

@@ -121,6 +121,14 @@ struct Filters {
         return common >= kmer_lo && common <= kmer_hi;
     }
 };
+// the -min / -max bounds as a call takes them (the library applies at most 8: every site decides what it passes beyond that)
+std::vector<kmdb_cell_filter> cell_filters(const Filters& f) {
+    std::vector<kmdb_cell_filter> fl;
+    for (auto& kv : f.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
+    if (f.kmer_lo != 0 || f.kmer_hi != std::numeric_limits<uint32_t>::max())
+        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)f.kmer_lo, (double)f.kmer_hi});
+    return fl;
+}
 
 // -sample-rows [<criterion>:]<count> (all2all-sp, all2all-parts; reference src/sampler.h, src/params.cpp:533-557, src/array.h:450-540): every
 // sample keeps at most `count` of its neighbours — every pair (i, j) that passes the filters is offered to row i AND to row j, so the sampled
@@ -245,7 +253,7 @@ struct DeviceBand {
     DeviceBand& operator=(const DeviceBand&) = delete;
 };
 // KMDB_VERBOSE: what the last band call on the handle did
-void report_rows_stats(const kmdb_db* d) {
+void report_rows_stats(const kmdb_db* d, uint64_t, uint64_t) {
     kmdb_all2all_rows_stats rs{};
     if (!std::getenv("KMDB_VERBOSE") || kmdb_all2all_rows_stats_get(d, &rs)) return;
     std::cerr << "[kmdb] all2all rows: " << rs.band_cells << " cells, nodes selected / applied / updates " << rs.nodes_selected << " / " << rs.nodes_applied << " / "
@@ -298,6 +306,12 @@ uint64_t largest_band_cells(uint64_t lo, uint64_t hi, uint64_t R) {
     for (uint64_t b = lo; b < hi; b += std::min(R, hi - b)) cells = std::max(cells, tri(b + std::min(R, hi - b)) - tri(b));
     return cells;
 }
+// the stripe of rows [i0, i1) a table is written by: the rows from i0 that hold `budget` cells together (row i has i), one at least, none from `hi` on
+uint64_t next_stripe(uint64_t i0, uint64_t hi, uint64_t budget) {
+    uint64_t i1 = i0, cells = 0;
+    while (i1 < hi && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+    return i1;
+}
 
 struct BuildInput;
 struct Common {
@@ -311,16 +325,27 @@ struct Common {
         const char* e = std::getenv("KMDB_ROWS_TILED");
         return band_rows != 0 || (e && e[0] == '1');
     }
-    // the band [lo, hi) into device memory at `dev` by the call this run takes
+    // the band call this run takes: its device form, its host form, its KMDB_VERBOSE report
+    struct BandCall {
+        int (*to_device)(kmdb_db*, uint64_t, uint64_t, void*, const kmdb_opts*);
+        int (*to_host)(kmdb_db*, uint64_t, uint64_t, uint32_t*, const kmdb_opts*);
+        void (*report)(const kmdb_db*, uint64_t, uint64_t);
+    };
+    BandCall band_call() const {
+        if (band_path == BandPath::records) return {kmdb_all2all_rows_records_device, kmdb_all2all_rows_records, report_rows_records_stats};
+        if (tiled()) return {kmdb_all2all_rows_tiled_device, kmdb_all2all_rows_tiled, report_rows_tiled_stats};
+        return {kmdb_all2all_rows_device, kmdb_all2all_rows, report_rows_stats};
+    }
+    // the band [lo, hi) into device memory at `dev`, or into host memory
     void band_to_device(kmdb_db* d, uint64_t lo, uint64_t hi, void* dev, const kmdb_opts& o) const {
-        if (band_path == BandPath::records) { check(kmdb_all2all_rows_records_device(d, lo, hi, dev, &o)); report_rows_records_stats(d, lo, hi); }
-        else if (tiled()) { check(kmdb_all2all_rows_tiled_device(d, lo, hi, dev, &o)); report_rows_tiled_stats(d, lo, hi); }
-        else { check(kmdb_all2all_rows_device(d, lo, hi, dev, &o)); report_rows_stats(d); }
+        const BandCall b = band_call();
+        check(b.to_device(d, lo, hi, dev, &o));
+        b.report(d, lo, hi);
     }
     void band_to_host(kmdb_db* d, uint64_t lo, uint64_t hi, uint32_t* host, const kmdb_opts& o) const {
-        if (band_path == BandPath::records) { check(kmdb_all2all_rows_records(d, lo, hi, host, &o)); report_rows_records_stats(d, lo, hi); }
-        else if (tiled()) { check(kmdb_all2all_rows_tiled(d, lo, hi, host, &o)); report_rows_tiled_stats(d, lo, hi); }
-        else { check(kmdb_all2all_rows(d, lo, hi, host, &o)); report_rows_stats(d); }
+        const BandCall b = band_call();
+        check(b.to_host(d, lo, hi, host, &o));
+        b.report(d, lo, hi);
     }
     uint64_t seed_samples = 0;               // -from-samples -extend-from <old.db>: the samples of <old.db> (set by open_database)
     std::shared_ptr<BuildInput> from_samples;     // all2all | all2all-sp -from-samples: build's input switches; the "database" argument is the sample list
@@ -431,9 +456,35 @@ void open_database(Db& db, const std::string& source, Common& c, const kmdb_opts
 // all2all -sparse | all2all-sp with -rows: the band is accumulated and compacted where it lies (kmdb_all2all_rows_device, then
 // kmdb_sparse_from_dense_device on the cells [tri(lo), tri(hi))), the host applies every bound again as the full run does, and the header and the
 // lines of samples lo .. hi - 1 are written.  Neither the triangle nor the band exists on the host.
-int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs, const std::string& path, uint64_t lo, uint64_t hi) {
+// The lines of a sparse table, one sample's at a time: its cells in cols / vals — filter() takes those of row i of `sp` that pass every bound —
+// formatted, written and counted.
+struct SparseRowWriter {
+    Db& db;
+    const Filters& filters;
+    std::ofstream& ofs;
     const uint64_t n = kmdbh_db_n_samples(db.h);
     const int k = (int)kmdbh_db_kmer_length(db.h);
+    std::vector<char> row = std::vector<char>(10000 + n * 100);
+    std::vector<uint32_t> cols, vals;
+    size_t saved = 0;
+    void filter(const kmdb_sparse_rows& sp, uint64_t i) {
+        for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
+            if (filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
+                cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
+            }
+    }
+    void write(uint64_t i) {
+        const char* name = kmdbh_db_sample_name(db.h, i);
+        if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
+        size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
+        ofs.write(row.data(), (std::streamsize)len);
+        saved += cols.size();
+        cols.clear(); vals.clear();
+    }
+};
+
+int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs, const std::string& path, uint64_t lo, uint64_t hi) {
+    const uint64_t n = kmdbh_db_n_samples(db.h);
     // -band-rows <R>: the same for every band of R rows in turn — one band buffer on the device, the header once, the bands' lines one after another
     const bool banded = c.band_rows != 0;
     const uint64_t R = banded ? c.band_rows : std::max<uint64_t>(hi - lo, 1);
@@ -441,16 +492,11 @@ int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs,
     if (banded) std::cerr << " in bands of " << R << " rows, storing them in " << path;
     std::cerr << "...";
     auto t0 = clk::now();
-    std::vector<kmdb_cell_filter> fl;
-    for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-    if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
-        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+    std::vector<kmdb_cell_filter> fl = cell_filters(c.filters);
     if (fl.size() > 8) fl.clear();                              // (the host-side pass below applies every bound anyway)
     std::vector<uint32_t> counts(std::max<uint64_t>(n, 1));
     for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
-    std::vector<char> row(10000 + n * 100);
-    std::vector<uint32_t> cols, vals;
-    size_t saved = 0;
+    SparseRowWriter w{db, c.filters, ofs};
     {
         DeviceBand band(c.device, largest_band_cells(lo, hi, R));
         for (uint64_t b_lo = lo;;) {                            // (an empty range: one empty band, so that the header is written)
@@ -467,25 +513,14 @@ int write_sparse_band(Db& db, Common& c, const kmdb_opts& o, std::ofstream& ofs,
                 db.uploaded();
                 write_header(db, ofs);
             }
-            for (uint64_t i = b_lo; i < b_hi; ++i) {
-                cols.clear(); vals.clear();
-                for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
-                    if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
-                        cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
-                    }
-                const char* name = kmdbh_db_sample_name(db.h, i);
-                if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
-                size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
-                ofs.write(row.data(), (std::streamsize)len);
-                saved += cols.size();
-            }
+            for (uint64_t i = b_lo; i < b_hi; ++i) { w.filter(sp, i); w.write(i); }
             kmdb_sparse_free(&sp);
             b_lo = b_hi;
             if (b_lo >= hi) break;
         }
     }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
-    std::cerr << "No. saved pairs: " << saved << std::endl;
+    std::cerr << "No. saved pairs: " << w.saved << std::endl;
     return finish(db, ofs, path);
 }
 
@@ -535,52 +570,51 @@ int run_all2all(std::vector<std::string>& args, Common& c) {
     size_t name_max = 0;
     for (uint64_t i = 0; i < n; ++i) name_max = std::max(name_max, std::strlen(kmdbh_db_sample_name(db.h, i)));
     for (uint64_t b_lo = r_lo; b_lo < r_hi;) {
-    const uint64_t b_hi = b_lo + std::min(R, r_hi - b_lo);     // (one band: the whole range unless -band-rows cuts it)
-    if (b_lo != r_lo) c.band_to_host(db.d, b_lo, b_hi, m.data(), o);
-    cell_lo = tri(b_lo);
-    for (uint64_t i0 = b_lo; i0 < b_hi;) {
-        uint64_t i1 = i0, cells_in = 0;
-        while (i1 < b_hi && (i1 == i0 || cells_in + i1 <= (32u << 20))) { cells_in += i1; ++i1; }
-        std::vector<std::vector<char>> text(nthr);
-        std::atomic<int> failed{0};
-        auto work = [&](int t) {
-            // thread t: the rows [a, b) of the stripe holding its share of the cells
-            auto cut = [&](int q) -> uint64_t {
-                const double lo = (double)i0 * (double)i0, hi = (double)i1 * (double)i1;
-                uint64_t r = (uint64_t)std::sqrt(lo + (hi - lo) * q / nthr);
-                return std::min<uint64_t>(i1, std::max<uint64_t>(i0, r));
-            };
-            const uint64_t a = t == 0 ? i0 : cut(t), b = t + 1 == nthr ? i1 : cut(t + 1);
-            std::vector<char>& out = text[t];
-            std::vector<uint32_t> cols, vals;
-            size_t used = 0;
-            for (uint64_t i = a; i < b; ++i) {
-                const uint32_t* r = m.data() + (tri(i) - cell_lo);
-                const char* name = kmdbh_db_sample_name(db.h, i);
-                const size_t need = 64 + name_max + i * (c.sparse ? 22 : 11);
-                if (out.size() < used + need) out.resize(std::max(out.size() * 2, used + need));
-                if (c.sparse) {
-                    cols.clear(); vals.clear();
-                    for (uint64_t j = 0; j < i; ++j)     // LowerTriangularMatrix::compact + saveRowSparse (array.h:169-181,259-262)
-                        if (r[j] && c.filters.pass(r[j], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, j), k)) {
-                            cols.push_back((uint32_t)j); vals.push_back(r[j]);
-                        }
-                    used += kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), out.data() + used);
-                } else {
-                    used += kmdbh_format_dense_row(name, kmdbh_db_sample_kmers(db.h, i), r, i, out.data() + used);
+        const uint64_t b_hi = b_lo + std::min(R, r_hi - b_lo);     // (one band: the whole range unless -band-rows cuts it)
+        if (b_lo != r_lo) c.band_to_host(db.d, b_lo, b_hi, m.data(), o);
+        cell_lo = tri(b_lo);
+        for (uint64_t i0 = b_lo; i0 < b_hi;) {
+            const uint64_t i1 = next_stripe(i0, b_hi, 32u << 20);
+            std::vector<std::vector<char>> text(nthr);
+            std::atomic<int> failed{0};
+            auto work = [&](int t) {
+                // thread t: the rows [a, b) of the stripe holding its share of the cells
+                auto cut = [&](int q) -> uint64_t {
+                    const double lo = (double)i0 * (double)i0, hi = (double)i1 * (double)i1;
+                    uint64_t r = (uint64_t)std::sqrt(lo + (hi - lo) * q / nthr);
+                    return std::min<uint64_t>(i1, std::max<uint64_t>(i0, r));
+                };
+                const uint64_t a = t == 0 ? i0 : cut(t), b = t + 1 == nthr ? i1 : cut(t + 1);
+                std::vector<char>& out = text[t];
+                std::vector<uint32_t> cols, vals;
+                size_t used = 0;
+                for (uint64_t i = a; i < b; ++i) {
+                    const uint32_t* r = m.data() + (tri(i) - cell_lo);
+                    const char* name = kmdbh_db_sample_name(db.h, i);
+                    const size_t need = 64 + name_max + i * (c.sparse ? 22 : 11);
+                    if (out.size() < used + need) out.resize(std::max(out.size() * 2, used + need));
+                    if (c.sparse) {
+                        cols.clear(); vals.clear();
+                        for (uint64_t j = 0; j < i; ++j)     // LowerTriangularMatrix::compact + saveRowSparse (array.h:169-181,259-262)
+                            if (r[j] && c.filters.pass(r[j], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, j), k)) {
+                                cols.push_back((uint32_t)j); vals.push_back(r[j]);
+                            }
+                        used += kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), out.data() + used);
+                    } else {
+                        used += kmdbh_format_dense_row(name, kmdbh_db_sample_kmers(db.h, i), r, i, out.data() + used);
+                    }
                 }
-            }
-            out.resize(used);
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nthr; ++t) pool.emplace_back([&, t]() { try { work(t); } catch (...) { failed = 1; } });
-        work(0);
-        for (auto& th : pool) th.join();
-        if (failed) throw std::runtime_error("out of memory while formatting the table");
-        for (auto& tx : text) ofs.write(tx.data(), (std::streamsize)tx.size());
-        i0 = i1;
-    }
-    b_lo = b_hi;
+                out.resize(used);
+            };
+            std::vector<std::thread> pool;
+            for (int t = 1; t < nthr; ++t) pool.emplace_back([&, t]() { try { work(t); } catch (...) { failed = 1; } });
+            work(0);
+            for (auto& th : pool) th.join();
+            if (failed) throw std::runtime_error("out of memory while formatting the table");
+            for (auto& tx : text) ofs.write(tx.data(), (std::streamsize)tx.size());
+            i0 = i1;
+        }
+        b_lo = b_hi;
     }
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
     return finish(db, ofs, args[1]);
@@ -615,10 +649,7 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     kmdb_sparse_rows sp{};
     {
         // the -min / -max filters go with the call: cells that miss a bound never leave the device
-        std::vector<kmdb_cell_filter> fl;
-        for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-        if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
-            fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
+        std::vector<kmdb_cell_filter> fl = cell_filters(c.filters);
         std::vector<uint32_t> counts(n);
         for (uint64_t i = 0; i < n; ++i) counts[i] = (uint32_t)kmdbh_db_sample_kmers(db.h, i);
         if (c.sampler.on() && c.sampler.best) {
@@ -644,9 +675,7 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
     std::cerr << "Storing matrix of common k-mers in " << args[1] << "...";
     t0 = clk::now();
     write_header(db, ofs);
-    std::vector<char> row(10000 + n * 100);
-    std::vector<uint32_t> cols, vals;
-    size_t saved = 0;
+    SparseRowWriter w{db, c.filters, ofs};
     const bool sampled_rows = c.sampler.on() && c.sampler.best;      // `sp` holds the rows to write
     if (c.sampler.on() && !sampled_rows) {
         // -sample-rows <count>, the random strategy (console_all2all_sparse.cpp:70-76, array.h:450-540): every pair that passes the filters is
@@ -662,23 +691,14 @@ int run_all2all_sp(std::vector<std::string>& args, Common& c) {
             }
     }
     for (uint64_t i = 0; i < n; ++i) {
-        cols.clear(); vals.clear();
-        if (sampled_rows) { cols.assign(sp.col + sp.row_ptr[i], sp.col + sp.row_ptr[i + 1]); vals.assign(sp.val + sp.row_ptr[i], sp.val + sp.row_ptr[i + 1]); }
-        else if (c.sampler.on()) c.sampler.finish_row(i, cols, vals);
-        else
-        for (uint64_t e = sp.row_ptr[i]; e < sp.row_ptr[i + 1]; ++e)   // compact2's filter (array.h:424-427)
-            if (c.filters.pass(sp.val[e], (uint32_t)kmdbh_db_sample_kmers(db.h, i), (uint32_t)kmdbh_db_sample_kmers(db.h, sp.col[e]), k)) {
-                cols.push_back(sp.col[e]); vals.push_back(sp.val[e]);
-            }
-        const char* name = kmdbh_db_sample_name(db.h, i);
-        if (row.size() < 10000 + n * 100 + std::strlen(name)) row.resize(10000 + n * 100 + std::strlen(name));
-        size_t len = kmdbh_format_sparse_row(name, kmdbh_db_sample_kmers(db.h, i), cols.data(), vals.data(), cols.size(), row.data());
-        ofs.write(row.data(), (std::streamsize)len);
-        saved += cols.size();
+        if (sampled_rows) { w.cols.assign(sp.col + sp.row_ptr[i], sp.col + sp.row_ptr[i + 1]); w.vals.assign(sp.val + sp.row_ptr[i], sp.val + sp.row_ptr[i + 1]); }
+        else if (c.sampler.on()) c.sampler.finish_row(i, w.cols, w.vals);
+        else w.filter(sp, i);
+        w.write(i);
     }
     kmdb_sparse_free(&sp);
     std::cerr << "OK (" << since(t0) << " seconds)" << std::endl;
-    std::cerr << "No. saved pairs: " << saved << std::endl;
+    std::cerr << "No. saved pairs: " << w.saved << std::endl;
     return finish(db, ofs, args[1]);
 }
 
@@ -775,11 +795,8 @@ int run_all2all_parts(std::vector<std::string>& args, Common& c) {
     std::condition_variable cv;
     std::exception_ptr failure;
     // the -min / -max bounds go with every cell's call (as for all2all-sp); the k-mer counts as the library takes them (num_kmers_t = uint32)
-    std::vector<kmdb_cell_filter> fl;
-    for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-    if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
-        fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
-    const std::vector<kmdb_cell_filter> fl_all = fl;              // every bound: what a sampled call takes (a selection without a bound is no superset)
+    std::vector<kmdb_cell_filter> fl = cell_filters(c.filters);
+    const std::vector<kmdb_cell_filter> fl_all = fl;             // every bound: what a sampled call takes (a selection without a bound is no superset)
     if (fl.size() > 8) fl.clear();                                // (the rows are checked with every bound below anyway)
     std::vector<uint32_t> counts32(counts.begin(), counts.end());
     const bool dense_cells = std::getenv("KMDB_PARTS_DENSE_CELLS") != nullptr;
@@ -1644,11 +1661,7 @@ int run_new2all(std::vector<std::string>& args, Common& c) {
     std::vector<kmdb_cell_filter> fl;
     std::vector<uint32_t> sample_counts(n);
     for (uint64_t j = 0; j < n; ++j) sample_counts[j] = (uint32_t)kmdbh_db_sample_kmers(db.h, j);
-    if (sparse_on_device) {
-        for (auto& kv : c.filters.metric) fl.push_back(kmdb_cell_filter{kmdbh_metric_id(kv.first.c_str()), 0, kv.second.lo, kv.second.hi});
-        if (c.filters.kmer_lo != 0 || c.filters.kmer_hi != std::numeric_limits<uint32_t>::max())
-            fl.push_back(kmdb_cell_filter{KMDB_METRIC_NUM_KMERS, 0, (double)c.filters.kmer_lo, (double)c.filters.kmer_hi});
-    }
+    if (sparse_on_device) fl = cell_filters(c.filters);
     auto flush = [&]() {
         if (batch.empty()) return;
         std::vector<size_t> cnts(batch.size());
@@ -2245,8 +2258,7 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
                 for (size_t mi = 0; mi < nm; ++mi) {
                     check(kmdb_distance_take_cells_device(hs[mi].d, band->p, b_lo, names.data()));
                     for (uint64_t i0 = b_lo; i0 < b_hi;) {
-                        uint64_t i1 = i0, cells = 0;
-                        while (i1 < b_hi && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+                        const uint64_t i1 = next_stripe(i0, b_hi, budget);
                         kmdb_distance_out piece{};
                         check(kmdb_distance_matrix_rows(hs[mi].d, i0, i1, &piece));
                         if (!ws[mi]->push(piece)) throw std::runtime_error("Cannot write the output file " + paths[mi]);
@@ -2311,8 +2323,7 @@ int run_all2all_distance(std::vector<std::string>& args, Common& c, const std::v
         std::string error;
         try {
             for (uint64_t i0 = r_lo; i0 < r_hi;) {
-                uint64_t i1 = i0, cells = 0;
-                while (i1 < r_hi && (i1 == i0 || cells + i1 <= budget)) { cells += i1; ++i1; }
+                const uint64_t i1 = next_stripe(i0, r_hi, budget);
                 kmdb_distance_out piece{};
                 check(kmdb_distance_matrix_rows(h.d, i0, i1, &piece));
                 if (!w->push(piece)) break;
