@@ -461,9 +461,12 @@ struct K0Params {
     const uint32_t* bitrel;
     const uint64_t* blkbase;
     const uint64_t* bits;
-    const uint32_t* perm;          // nullptr: all nodes in DFS order, long ones skipped; else: the long nodes
+    const uint32_t* perm;          // the long launch: its nodes, most work first
+    const uint16_t* order;         // the short launch: the nodes of every window of 1 << win_shift DFS nodes by decreasing work (kmdb_db.k0_order) ...
+    const uint32_t* live;          // ... and how many of them it decodes (kmdb_db.k0_live)
+    uint32_t win_shift;
+    uint32_t n_items;              // the short launch's workgroups that have a window: 256 ranks of a window each
     uint32_t P;                    // nodes of this launch
-    uint32_t short_ids;            // lists of more ids belong to the long launch (kmdb_db.short_max_ids)
     BlockMap bm;
     unsigned long long* p0_mask;   // first pair inline
     uint32_t* p0_info;             // block | npairs << 16
@@ -479,48 +482,36 @@ constexpr int K0_RELW = 8;                 // non-empty 64-id words of a long li
 constexpr int K0_SINGLE_PASS = 1;          // 0: every list spanning 64 ids or more is walked twice, as in round 3 (A/B)
 template <bool LONG>
 __global__ __launch_bounds__(256) void k0_decode_kernel(const K0Params q) {
-    // two launches cover the nodes: perm == nullptr walks ALL nodes in DFS order (coalesced) and skips the ones whose
-    // stream does not fit three registers; those few are listed in perm, most work first, and decoded by the second
+    // two launches cover the nodes: the short one takes every node whose stream fits three registers, window by window of the DFS order
+    // (all its global accesses stay inside the window); the few others are listed in perm, most work first, and decoded by the long
     // launch so that no wave waits on one long stream
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t i = 0;
     bool live;
-    if (q.perm) {
+    if constexpr (LONG) {
+        const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
         live = t < q.P;
         if (live) i = q.perm[t];
     } else {
-        // DFS-order launch: the 256 nodes of the block are re-dealt to its threads by decreasing amount of work
-        // (counting sort in LDS), so every wave runs decode loops of similar length while all global accesses
-        // of the block stay inside its own 256-node window
-        __shared__ uint32_t bins[64];
-        __shared__ uint16_t order[256];
-        if (threadIdx.x < 64) bins[threadIdx.x] = 0;
-        __syncthreads();
-        const uint2 kt = t < q.P ? q.k0in[t] : make_uint2(0u, 0u);          // l, last id, stream bits (kmdb_k0_pack)
-        const uint32_t tl = kmdb_k0_l(kt), tbits = kmdb_k0_bits(kt);
-        // work of a node ~ number of codes that are not "0" ~ stream bits beyond one per delta
-        uint32_t key = 0;                                                    // 0: nothing to decode here
-        if (t < q.P && tl > 1 && !kmdb_long_node(tl, tbits, q.short_ids)) {
-            key = 1u + (tbits - (tl - 1u));
-            key = key > 63u ? 63u : key;
-        }
-        atomicAdd(&bins[63u - key], 1u);                                     // bin 0 = most work
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const uint32_t c = bins[threadIdx.x];
-            bins[threadIdx.x] = wave_incl_scan(c, threadIdx.x) - c;
-        }
-        __syncthreads();
-        order[atomicAdd(&bins[63u - key], 1u)] = (uint16_t)threadIdx.x;
-        __syncthreads();
-        i = blockIdx.x * blockDim.x + order[threadIdx.x];
-        live = i < q.P;
+        // The nodes of a window are dealt to its threads by decreasing amount of work, 64 to a wave, so every wave runs decode loops of
+        // similar length.  The order is the layout's (it depends on the list heads alone: made once per database, lay_k0_order_kernel);
+        // a wave whose ranks all lie behind the window's live count has nothing to decode.  The workgroups of a window wider than 256
+        // nodes run on one XCD (the grid is a multiple of 8 windows): the lines of p0_mask / p0_info they fill together are completed in one L2.
+        // (Windows go to the XCDs in turn, window w to XCD w % 8 — workgroup b runs on XCD b % 8.  One contiguous eighth of the DFS order per XCD, as
+        // xcd_contiguous deals the sort's jobs, was measured slower: 2.31 / 1.82 ms against 1.95 / 1.58 ms at windows of 1024 / 4096 nodes)
+        const uint32_t sub_shift = q.win_shift - 8u;                         // log2 of the workgroups per window: 0 unless KMDB_K0_WINDOW widens it
+        const uint32_t k = blockIdx.x >> 3;                                  // the workgroup's place among its XCD's
+        const uint32_t w = sub_shift ? ((k >> sub_shift) << 3) + (blockIdx.x & 7u) : blockIdx.x;
+        if ((w << sub_shift) >= q.n_items) return;
+        const uint32_t r = ((k & ((1u << sub_shift) - 1u)) << 8) + threadIdx.x;
+        const uint32_t n_live = q.live[w];
+        if ((r & ~63u) >= n_live) return;
+        live = r < n_live;
+        if (live) i = (w << q.win_shift) + q.order[((size_t)w << q.win_shift) + r];
     }
     const BlockMap bm = q.bm;
     const uint2 km = live ? q.k0in[i] : make_uint2(0u, 0u);
     const uint32_t l = kmdb_k0_l(km), last = kmdb_k0_last(km), nbits = kmdb_k0_bits(km);
-    if (!q.perm && kmdb_long_node(l, nbits, q.short_ids)) live = false;
     using Cursor = RunCursor32<LONG ? 16 : 6, LONG>;
     uint32_t npairs = 0, blk0 = 0, need = 0, span = 0, bit0 = 0;
     unsigned long long mask0 = 0, m1 = 0, m2 = 0;
@@ -576,9 +567,14 @@ __global__ __launch_bounds__(256) void k0_decode_kernel(const K0Params q) {
         // Pass 1 walks the stream run by run and builds the list RELATIVE to its (still unknown) first id:
         // bit k of R <=> id_0 + k is in the list.  pattern_t::decodeSamples (reference src/pattern.cpp:99-109)
         // gets id_0 the same way: last id minus the sum of the deltas.
-        pos = q.blkbase[i >> 8] + q.bitrel[i];
         unsigned long long R = 1ull;
-        {
+        if (!LONG && kmdb_k0_run_only(l, nbits)) {
+            // (short launch) l - 1 deltas in l - 1 bits: all of them 1, the list is one run of l <= 64 ids.  No stream word is read; these
+            // lanes and the single ids sort last, so whole waves of them skip the cursor and its loop (the branch below is wave-uniform there).
+            R = (2ull << (l - 1u)) - 1ull;
+            span = l - 1u;
+        } else {
+            pos = q.blkbase[i >> 8] + q.bitrel[i];
             Cursor c(q.bits, pos);
             uint32_t rem = l - 1;
             // the long launch keeps the WHOLE relative list, not only its first 64 ids: the non-empty 64-id words (word index, mask)
@@ -3736,7 +3732,7 @@ void a2a_prologue(BlocksState& b, hipStream_t st, bool decode) {
 int a2a_decode(kmdb_db* db, BlocksState& b, hipStream_t st) {
     const uint32_t P = (uint32_t)db->P;
     K0Params q{};
-    q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.perm = nullptr; q.P = P; q.short_ids = db->short_max_ids;
+    q.k0in = db->k0in; q.bitrel = db->bitrel; q.blkbase = db->blkbase; q.bits = db->bits; q.perm = nullptr; q.P = P;
     q.bm = BlockMap{db->width, (uint32_t)((1ull << 32) / db->width) + 1u};
     q.p0_mask = b.p0_mask; q.p0_info = b.p0_info; q.pair_ofs = b.pair_ofs; q.pair_blk = b.pair_blk; q.pair_mask = b.pair_mask;
     // sub-pools of the pair pool: enough of them that their cursors are not hot, few enough that one wave's need fits a share
@@ -3745,7 +3741,15 @@ int a2a_decode(kmdb_db* db, BlocksState& b, hipStream_t st) {
     // three quarters of the pool in sub-pools, the rest shared
     q.pair_cursor = b.pair_cursor; q.n_regions = nreg; q.region_cap = (uint32_t)(b.pair_cap * 3 / 4 / nreg);
     q.spill_cap = (uint32_t)(b.pair_cap - (uint64_t)q.region_cap * nreg); q.counters = b.counters;
-    hipLaunchKernelGGL((k0_decode_kernel<false>), dim3((P + 255) / 256), dim3(256), 0, st, q);
+    // the short launch: 256 ranks of a window per workgroup.  A window wider than that (reached through KMDB_K0_WINDOW alone: the default is 256) takes
+    // several workgroups, and the grid is rounded up to whole groups of 8 windows: the kernel deals the windows to the 8 XCDs in turn
+    q.order = db->k0_order; q.live = db->k0_live;
+    q.win_shift = 8;
+    while ((1u << q.win_shift) < db->k0_window) ++q.win_shift;
+    const uint32_t wgs_per_win = db->k0_window >> 8;
+    q.n_items = (uint32_t)((db->P + db->k0_window - 1) / db->k0_window) * wgs_per_win;
+    const uint32_t grid = wgs_per_win > 1 ? (q.n_items + 8u * wgs_per_win - 1u) / (8u * wgs_per_win) * (8u * wgs_per_win) : q.n_items;
+    if (grid) hipLaunchKernelGGL((k0_decode_kernel<false>), dim3(grid), dim3(256), 0, st, q);
     if (db->n_long) {
         q.perm = db->long_nodes; q.P = db->n_long;
         hipLaunchKernelGGL((k0_decode_kernel<true>), dim3((db->n_long + 255) / 256), dim3(256), 0, st, q);

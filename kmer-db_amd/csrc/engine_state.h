@@ -43,6 +43,10 @@ struct kmdb_db {
     DevBuf<uint32_t> sub_end;       // [P] DFS index one past the node's subtree
     DevBuf<uint32_t> long_nodes;    // nodes whose stream does not fit the short decoder, most work first
     uint32_t n_long = 0;
+    // the short decode launch's work order (kmdb_k0_key): the nodes of every window of k0_window consecutive DFS nodes by decreasing key
+    DevBuf<uint16_t> k0_order;      // [windows][k0_window] offset of the node inside its window; the part-filled last window is padded (key 0)
+    DevBuf<uint32_t> k0_live;       // [windows] nodes of the window the short launch decodes: the first k0_live[w] entries of its order
+    uint32_t k0_window = 256;       // a power of two from 256 to 4096, fixed at upload (KMDB_K0_WINDOW)
     uint32_t nseg_nodes = 2048;     // nodes per slice of the DFS stream (one wave each)
     uint32_t n_nsegs = 0;
     DevBuf<uint32_t> nseg_anc;      // [n_nsegs][chain_cap] root path of every slice's first node
@@ -158,6 +162,19 @@ __host__ __device__ inline uint32_t kmdb_k0_last(uint2 km) { return km.y & (KMDB
 __host__ __device__ inline uint32_t kmdb_k0_bits(uint2 km) { return ((km.x >> KMDB_ID_BITS) << 12) | (km.y >> KMDB_ID_BITS); }
 constexpr uint32_t KMDB_SHORT_MAX_IDS = 48, KMDB_SHORT_MAX_BITS = 128;     // (ids: the default of kmdb_db.short_max_ids, KMDB_SHORT_IDS at upload.  Measured, profiles/r05_j4: 32 -> 48 ids takes 0.14 ms off the decode at c2 and 0.5 ms at 10 000 samples — the lists of a clade of 50 fit —, 56 and 64 lose: the short launch walks a list that spans 64 ids or more twice)
 __host__ __device__ inline bool kmdb_long_node(uint32_t l, uint32_t num_bits, uint32_t max_ids) { return l > max_ids || num_bits > KMDB_SHORT_MAX_BITS; }
+// The short launch's work per node, from the header fields alone (no stream bit is read): the same for every call on a database, so the layout
+// sorts by it once.  0: not the short launch's (a long node; the padding of the last window) — sorts last, outside the live count.
+// 1: a single id, or an empty list (its p0_info = 0 is this launch's to write, in every call: K1n reads it).  2: a single run — l - 1 deltas in l - 1 stream bits are all 1 —; neither reads its stream.  Above: 2 + the stream bits
+// beyond one per delta (~ the codes that are not "0"), capped at 63.
+__host__ __device__ inline bool kmdb_k0_run_only(uint32_t l, uint32_t num_bits) { return l > 1 && num_bits <= l - 1u; }
+__host__ __device__ inline uint32_t kmdb_k0_key(uint32_t l, uint32_t num_bits, uint32_t max_ids) {
+    if (kmdb_long_node(l, num_bits, max_ids)) return 0u;
+    if (l <= 1) return 1u;
+    if (kmdb_k0_run_only(l, num_bits)) return 2u;
+    const uint32_t extra = num_bits - (l - 1u);
+    return extra > 61u ? 63u : 2u + extra;
+}
+constexpr uint32_t KMDB_K0_WINDOW_MIN = 256, KMDB_K0_WINDOW_MAX = 4096, KMDB_K0_WINDOW_DEFAULT = 256;       // (wider windows run fewer instructions and take longer: DESIGN.md §8)
 constexpr int KMDB_CHAIN_MAX = 4096;  // longest root path (in nodes) the chain table of the narrow kernel holds (20 B of LDS per node and wave:
                                       // the deeper the tree, the fewer waves share a workgroup)
 

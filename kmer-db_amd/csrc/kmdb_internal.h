@@ -65,6 +65,10 @@ int kmdb_layout_from_device(kmdb_db* db, const kmdb_layout_device_source* src, i
 // engine.hip: the handle kmdb_db_upload would return for the same database, made from the source; opts as for kmdb_db_upload
 struct kmdb_opts;
 int kmdb_db_from_device(kmdb_layout_device_source* src, const kmdb_opts* opts, int with_hashtables, kmdb_db** out);
+// layout.hip (tests; not part of include/kmdb_amd.h): the short decode launch's work order read back — the window, the number of windows, every
+// window's node offsets by decreasing key (n_windows * window of them), its live count, and the list heads (l, stream bits) of the P nodes in DFS
+// order.  Every output may be null: a first call with the two sizes alone tells how much the others hold.
+extern "C" int kmdb_debug_k0_order(const kmdb_db* db, uint32_t* window, uint64_t* n_windows, uint16_t* order, uint32_t* live, uint32_t* l, uint32_t* num_bits);
 
 // ---- minhash.hip: the extractor behind kmdb_minhash_batch_seq_alphabet with the lists LEFT ON THE DEVICE (build.hip adds them to its
 // tree from there).  The batch is cut into pieces as for the public entry; for every piece `sink` is called once, after the piece's last

@@ -196,6 +196,31 @@ __global__ void lay_long_keys_kernel(const uint2* __restrict__ k0in, const uint3
     const uint32_t l = kmdb_k0_l(km);
     keys[t] = kmdb_k0_bits(km) - (l ? l - 1u : 0u);                     // work of a node ~ stream bits beyond one per delta
 }
+// The short decode launch's work order: one workgroup per window of W consecutive DFS nodes sorts them by decreasing kmdb_k0_key (counting sort in LDS
+// over the 64 keys) and writes every node's offset inside the window at its rank, and the number of nodes with a key above 0.  The slots of the last
+// window behind node P - 1 count as key 0.  Reads the heads of the lists alone.
+__global__ __launch_bounds__(256) void lay_k0_order_kernel(const uint2* __restrict__ k0in, uint32_t P, uint32_t W, uint32_t short_ids, uint16_t* __restrict__ order,
+                                                           uint32_t* __restrict__ live) {
+    __shared__ uint32_t bins[64];
+    const uint64_t base = (uint64_t)blockIdx.x * W;
+    auto key_of = [&](uint32_t r) -> uint32_t {
+        if (base + r >= P) return 0u;
+        const uint2 km = k0in[base + r];
+        return kmdb_k0_key(kmdb_k0_l(km), kmdb_k0_bits(km), short_ids);
+    };
+    if (threadIdx.x < 64) bins[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < W; r += 256) atomicAdd(&bins[63u - key_of(r)], 1u);          // bin 0 = most work
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const uint32_t c = bins[threadIdx.x];
+        const uint32_t first = wave_incl_scan(c, threadIdx.x) - c;
+        bins[threadIdx.x] = first;
+        if (threadIdx.x == 63) live[blockIdx.x] = first;                                            // (bin 63 = key 0 starts where the live nodes end)
+    }
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < W; r += 256) order[base + atomicAdd(&bins[63u - key_of(r)], 1u)] = (uint16_t)r;
+}
 // root path of the first node of every slice, root first
 __global__ void lay_seg_anc_kernel(const int32_t* __restrict__ parent, const uint16_t* __restrict__ dflag, uint32_t P, uint32_t nseg_nodes, uint32_t n_segs,
                                    uint32_t chain_cap, uint32_t* __restrict__ anc, uint32_t* __restrict__ anc_n) {
@@ -721,8 +746,24 @@ int lay_device_stage(kmdb_db* db, LayIn& in, LayPhase& phase) {
         HIP_TRY(prim::sort_pairs_desc(tmp2.get(), tb2, lk.get(), lk2.get(), sel.get(), db->long_nodes.get(), (int)hs.n_long, 0, 32, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    // the short launch's work order, per window of k0_window DFS nodes (a power of two)
+    db->k0_window = KMDB_K0_WINDOW_DEFAULT;
+    if (const char* e = getenv("KMDB_K0_WINDOW")) if (*e) {
+        const uint32_t want = (uint32_t)std::max(0, atoi(e));
+        uint32_t w = KMDB_K0_WINDOW_MIN;
+        while (w < KMDB_K0_WINDOW_MAX && w < want) w <<= 1;
+        db->k0_window = w;
+    }
+    const uint64_t n_windows = (P + db->k0_window - 1) / db->k0_window;
+    DEV_ALLOC(db->k0_order, std::max<uint64_t>(n_windows * db->k0_window, 1));
+    DEV_ALLOC(db->k0_live, std::max<uint64_t>(n_windows, 1));
+    if (n_windows) {
+        hipLaunchKernelGGL(lay_k0_order_kernel, dim3((unsigned)n_windows), dim3(256), 0, st, db->k0in, (uint32_t)P, db->k0_window, db->short_max_ids,
+                           db->k0_order.get(), db->k0_live.get());
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(st));
-    phase("device: slices + long nodes");
+    phase("device: slices + long nodes + decode order");
 
     db->stats.algorithmic_bytes = hs.alg + 4ull * (N ? N * (N - 1) / 2 : 0);
     db->stats.tree_updates = hs.upd;
@@ -730,10 +771,33 @@ int lay_device_stage(kmdb_db* db, LayIn& in, LayPhase& phase) {
     db->stats.n_segments = db->n_nsegs;
     db->stats.n_patterns = P;
     db->stats.h2d_bytes = in.h2d_bytes;
-    db->stats.device_bytes = P * (8 + 4 + 4 + 4 + 4 + 2 + 4) + n_bit_words * 8 + (uint64_t)db->n_nsegs * db->chain_cap * 4 + in.dev_ht_bytes;
+    db->stats.device_bytes = P * (8 + 4 + 4 + 4 + 4 + 2 + 4) + n_bit_words * 8 + (uint64_t)db->n_nsegs * db->chain_cap * 4 + in.dev_ht_bytes +
+                             n_windows * db->k0_window * 2 + n_windows * 4;
     return 0;
 }
 }  // namespace
+
+// (tests) the short launch's work order as the handle holds it.  window / n_windows: its geometry; order: n_windows * window offsets; live: n_windows
+// counts; l, num_bits: the P list heads in DFS order that the keys were made from.  Every output may be null.
+extern "C" int kmdb_debug_k0_order(const kmdb_db* db, uint32_t* window, uint64_t* n_windows, uint16_t* order, uint32_t* live, uint32_t* l, uint32_t* num_bits) {
+    if (!db) return kmdb_set_error("kmdb_debug_k0_order: null handle");
+    const uint64_t nw = (db->P + db->k0_window - 1) / db->k0_window;
+    if (window) *window = db->k0_window;
+    if (n_windows) *n_windows = nw;
+    HIP_TRY(hipSetDevice(db->device));
+    HIP_TRY(hipStreamSynchronize(db->stream));
+    if (order && nw) HIP_TRY(hipMemcpy(order, db->k0_order.get(), nw * db->k0_window * 2, hipMemcpyDeviceToHost));
+    if (live && nw) HIP_TRY(hipMemcpy(live, db->k0_live.get(), nw * 4, hipMemcpyDeviceToHost));
+    if ((l || num_bits) && db->P) {
+        std::vector<uint2> km(db->P);
+        HIP_TRY(hipMemcpy(km.data(), db->k0in.get(), db->P * sizeof(uint2), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < db->P; ++i) {
+            if (l) l[i] = kmdb_k0_l(km[i]);
+            if (num_bits) num_bits[i] = kmdb_k0_bits(km[i]);
+        }
+    }
+    return 0;
+}
 
 // The second source of the device stage: a builder's state at the end of its finish stages (c) and (d) (build.hip), read where it lies.
 // No pattern field, stream word or table slot visits the host: one kernel narrows the fields, the tables go device to device, and the
